@@ -1,20 +1,29 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X: pairwise interactions/s (+ steps/s) of the
-N-body force-and-integrate step at N = 65 536, with the roofline of the dominant kernel and the CPU
-oracle timed beside it.
+N-body force-and-integrate step at N = 65 536, with the roofline of the dominant kernel (and, with
+--full, the CPU oracle timed beside it).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bf|bh] [--n BODIES]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bf|bh] [--n BODIES] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one Simulation::step (half drift, retain, forces, kick + half drift) of ALL bodies.
 Inputs are resident in HBM before the timed region.  The default line is configs[1] (65 536-body
-brute force, the configuration the metric is quoted on); on one GPU it also carries a `bh` object with
-configs[2] (65 536-body Barnes-Hut, theta = 0.5) run both ways -- octree built on the host every step
-(north_star's configuration) and built on the device -- each with its own step time, build / copy /
-walk split, node visits and roofline.  With N ranks the bodies are split into N contiguous index
-blocks; every rank exchanges its half-drifted positions once per step with an RCCL all-gather issued by
-the library itself.  The control plane -- the 128-byte communicator id from rank 0, barriers, the
+brute force, the configuration the metric is quoted on).  A plain run measures that line alone: set-up,
+preheat and warm-up, the K timed steps (with the roofline of the dominant kernel from their own HIP
+events), the outputs if --dump-outputs is given, the line.  --full adds everything else, each run after
+the metric's steps: on one GPU a `bh` object with configs[2] (65 536-body Barnes-Hut, theta = 0.5) run
+both ways -- octree built on the host every step (north_star's configuration) and built on the device --
+each with its own step time, build / copy / walk split, node visits and roofline, the reference driver's
+workload and the CPU oracle; with N ranks configs[3] and configs[4].
+
+--dump-outputs DIR writes the state the timed steps left (what get_points() returns: position, velocity,
+acceleration, mass) as float32 DIR/<field>.npy (DIR/rank<r>_<field>.npy with N ranks); above 64 MB in all,
+a fixed, seeded sample of the bodies.  The inputs depend on the arguments alone (--seed).
+
+With N ranks the bodies are split into N contiguous index blocks; every rank exchanges its half-drifted
+positions once per step with an RCCL all-gather issued by the library itself.  The control plane -- the
+128-byte communicator id from rank 0, barriers, the
 max-over-ranks of the wall time -- is nbody-llm_amd/rendezvous.py (stdlib sockets): a rank process never
 imports torch, so libnbody_hip.so runs on the /opt/rocm HIP and RCCL it was compiled against (torch
 bundles its own, older, under the same SONAMEs); `torch.distributed.run` is only the launcher that sets
@@ -74,15 +83,20 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=["bf", "bh"], default="bf",
-                    help="bf = configs[1] (65 536-body brute force, the metric's config, + the bh object on one GPU); "
+                    help="bf = configs[1] (65 536-body brute force, the metric's config; with --full + the bh object on one GPU); "
                          "bh = configs[2] alone as the top-level line")
     ap.add_argument("--n", type=int, default=65536, help="bodies over all GPUs")
     ap.add_argument("--math", choices=["fast", "strict"], default="fast")
     ap.add_argument("--theta", type=float, default=0.5, help="Barnes-Hut opening angle (theta2 = theta^2)")
     ap.add_argument("--tree", choices=["host", "device"], default="host",
                     help="--workload bh: octree build on the host (north_star, bit-exact) or on the device (SURVEY F3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-bh", action="store_true", help="default line without the configs[2] object")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the metric does not need: the configs[2] object and the reference driver's workload (one GPU), "
+                         "configs[3] and configs[4] (N > 1 GPUs) and the CPU oracle (one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left, one float32 .npy per particle field (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle")
+    ap.add_argument("--no-bh", action="store_true", help="--full without the configs[2] object")
     ap.add_argument("--profile-every", type=int, default=4, help="HIP events around every k-th launch of the dominant kernel (an event pair "
                     "costs the stream ~11 us: bracketing every launch makes the steps it measures 1.5-3 %% longer)")
     ap.add_argument("--spatial-n", type=int, default=1 << 22, help="N > 1 GPUs: bodies of the configs[4] object (0: leave it out)")
@@ -96,7 +110,10 @@ def parse():
                     help="untimed steps before the warm-up, reported as preheat_steps: the chip settles on the clock it holds under this kernel "
                          "only after ~50 steps (DESIGN.md 3.2), and the driver's invocation is 5 + 20 steps; -1: 100 at the metric's size, else 0")
     ap.add_argument("--seed", type=int, default=20250523)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def load_json(name):
@@ -219,6 +236,21 @@ def bh_roofline(n_local, kernel_ms, launches, visits_per_launch, tree, math="fas
 
 
 _PARKED = []
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files together, over all ranks
+DUMP_SEED = 20250524
+
+
+def dump_outputs(out_dir, points, rank, world):
+    """--dump-outputs: one .npy per particle field of what get_points() returned after the last timed step.  Above this
+    rank's share of DUMP_BYTES a fixed, seeded sample of the bodies (in their stored order) is written instead."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // world - 4096   # (headers)
+    if points.nbytes > budget:
+        keep = budget // points.dtype.itemsize
+        points = points[np.sort(np.random.default_rng(DUMP_SEED).choice(len(points), keep, replace=False))]
+    prefix = "" if world == 1 else f"rank{rank}_"
+    for field in points.dtype.names:
+        np.save(os.path.join(out_dir, f"{prefix}{field}.npy"), np.ascontiguousarray(points[field]))
 
 
 def retire(sim, world):
@@ -233,8 +265,9 @@ def retire(sim, world):
         sim.close()
 
 
-def run(nb, args, workload, tree, ics, box, st, rank, world, local_rank, rdzv, ident_fn, preheat=0):
-    """[preheat +] W warm-up + K timed steps of one workload; returns (elapsed, stats, n_after)."""
+def run(nb, args, workload, tree, ics, box, st, rank, world, local_rank, rdzv, ident_fn, preheat=0, dump_dir=None):
+    """[preheat +] W warm-up + K timed steps of one workload; returns (elapsed, stats, n_after).  dump_dir: the state after
+    the last timed step goes there (dump_outputs)."""
     n = len(ics)
     method = nb.BRUTE_FORCE if workload == "bf" else nb.BARNES_HUT
     math_mode = nb.FAST if args.math == "fast" else nb.STRICT
@@ -264,6 +297,8 @@ def run(nb, args, workload, tree, ics, box, st, rank, world, local_rank, rdzv, i
     elapsed = time.perf_counter() - t0
     stats = sim.stats()
     sim.set_profiling(False)
+    if dump_dir is not None:
+        dump_outputs(dump_dir, sim.get_points(), rank, world)
     n_after = sim.count_global() if world == 1 else None
     retire(sim, world)
     return elapsed, stats, n_after
@@ -387,7 +422,8 @@ def main():
         main_guard.daemon = True
         main_guard.start()
     try:
-        elapsed, stats, n_after = run(nb, args, args.workload, args.tree, ics, box, st, rank, world, local_rank, rdzv, ident_fn, preheat=preheat)
+        elapsed, stats, n_after = run(nb, args, args.workload, args.tree, ics, box, st, rank, world, local_rank, rdzv, ident_fn, preheat=preheat,
+                                      dump_dir=args.dump_outputs)
         mine = [elapsed, float(stats.interactions), stats.force_kernel_ms, float(stats.force_launches), float(stats.node_visits),
                 float(stats.force_kernel_interactions)]
         gathered = rdzv.allgather(mine) if rdzv is not None else [mine]
@@ -440,7 +476,7 @@ def main():
             result["bh"] = bh_record(args, n, args.tree, elapsed, stats)
 
     # configs[2] beside the metric's line: both tree builds, one GPU only (the driver's N = 1 record)
-    if args.workload == "bf" and world == 1 and not args.no_bh:
+    if args.full and args.workload == "bf" and world == 1 and not args.no_bh:
         bh = {}
         for tree in ("host", "device"):
             e2, s2, _ = run(nb, args, "bh", tree, ics, box, st, rank, world, local_rank, None, None)
@@ -452,7 +488,7 @@ def main():
     # exchange runs with > 1 rank only here (a one-GPU box cannot rehearse it), so it is fenced: an error or a rank that
     # does not come back within --spatial-timeout leaves a note in the line instead of taking the metric with it.
     extras = world > 1 or (rdzv is not None and os.environ.get("NBODY_BENCH_FORCE_EXTRAS"))   # (the env switch: a 1-rank rehearsal of this block)
-    if args.workload == "bf" and extras and not args.no_bh and (args.spatial_n > 0 or args.large_n > 0):
+    if args.full and args.workload == "bf" and extras and not args.no_bh and (args.spatial_n > 0 or args.large_n > 0):
         import threading
 
         def give_up():
@@ -528,7 +564,7 @@ def main():
     # the reference's own benchmark (src/main.rs:52-129 through its Simulation trait): the 100 000-body disc, Barnes-Hut,
     # theta2 = 1, dt = 3e-2, g_soft = 0.02 -- the only workload with published numbers (its authors' perf CSVs,
     # other hardware, f64, 32 CPU threads: context, not a vs_baseline)
-    if args.workload == "bf" and world == 1 and not args.no_bh and args.driver_n > 0:
+    if args.full and args.workload == "bf" and world == 1 and not args.no_bh and args.driver_n > 0:
         ref = {}
         rbox = ((0.0, 0.0, 0.0), 10.0)
         rst = dict(g=1.0, g_soft=0.02, dt=3e-2, theta2=1.0)
@@ -558,7 +594,7 @@ def main():
             }
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg is timed at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU leg is timed at N = 1 only
             orc = graft.load_oracle()
             result["cpu_baseline"] = cpu_baseline(orc, ics, st, box, args.workload)
             if "bh" in result and args.workload == "bf":
