@@ -141,7 +141,11 @@ CrossPlan make_cross_plan(int rank, int world, int seg_cap, int n_own_upper);
 void launch_bf_cross(hipStream_t s, const Shard& sh, const CrossPlan& p, const int4* d_slices, float4* res_planes,
                      float4* xplanes, float4* send, size_t plane_stride, float g_soft2);
 
-// K5: BarnesHutSimulation::calc_force (barnes_hut.rs:185-203) over a linearised octree
+// K5: BarnesHutSimulation::calc_force (barnes_hut.rs:185-203) over a linearised octree.
+// The walk's node range is cut into at most kMaxSplit segments; the ancestors of a split point are listed down to kMaxAnc
+// levels.  The split's int array (f32 and f64 walks alike): first[kMaxSplit + 1] | n_anc[kMaxSplit] | anc[kMaxSplit][kMaxAnc]
+constexpr int kMaxSplit = 64, kMaxAnc = 192;
+constexpr size_t kSplitInts = size_t(kMaxSplit) + 1 + kMaxSplit + size_t(kMaxSplit) * kMaxAnc;
 struct TreeDev {
     const float4* nodes = nullptr;   // 2 per node: {com.x, com.y, com.z, mass}, {width^2, skip (int bits), hot score (int bits), leaf body}
     int n_nodes = 0;
@@ -150,7 +154,7 @@ struct TreeDev {
     // node-range split of the walk (kernels_bh.hip WalkSplit); n_split = 1: none
     int n_split = 1;
     const int* split_first = nullptr;   // [n_split + 1]
-    const int* split_anc = nullptr;     // [n_split][192]
+    const int* split_anc = nullptr;     // [n_split][kMaxAnc]
     const int* split_n_anc = nullptr;   // [n_split]
     float4* split_planes = nullptr;     // [n_split][split_stride]
     size_t split_stride = 0;
@@ -238,7 +242,7 @@ void launch_tree_split_anc(hipStream_t s, const TreeDevWork& work, int n, int n_
 
 // the walk's {accepted, visited} counters: this many u64 pairs, to be summed by the reader
 #define NBODY_WALK_COUNTER_SLOTS 1024u
-// split points and their ancestors from the node array itself (first [n_split + 1], n_anc [n_split], anc [n_split][192]; range: device {begin, end})
+// split points and their ancestors from the node array itself (first [n_split + 1], n_anc [n_split], anc [n_split][kMaxAnc]; range: device {begin, end})
 void launch_walk_split_scan(hipStream_t s, const float4* nodes, const int* range, int n_split, int* first, int* n_anc, int* anc, int first_given = 0);
 void launch_bh_walk(hipStream_t s, const Shard& sh, const TreeDev& t, float g, float g_soft2, float theta2,
                     int fast_math, unsigned long long* counters /* [NBODY_WALK_COUNTER_SLOTS][2]: accepted, visited */, int leaf_direct = 0,

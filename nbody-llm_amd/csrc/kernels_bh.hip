@@ -49,7 +49,6 @@ struct WalkSplit {
     int store_work;          // k_bh_walk, one segment: the body's visit count goes to acc.w (spatial shards balance by it)
     int xcd_blocks;          // k_bh_walk_duo: gridDim.x / 8 when the lane groups are dealt to the XCDs in eighths of the tree order, else 0
 };
-constexpr int kMaxAnc = 192;
 
 template <bool DIRECT = false>
 __device__ __forceinline__ int walk_entry(const NodeDev* __restrict__ nodes, const WalkSplit& sp, int seg,

@@ -57,12 +57,11 @@ void launch_bh_walk(hipStream_t s, const Dev& d, const Node64* nodes, int n_node
 struct WalkSplit64 {
     int n_seg;
     const int* first;      // [n_seg + 1]
-    const int* anc;        // [n_seg][kMaxAnc64]
+    const int* anc;        // [n_seg][nbody::kMaxAnc] (kernels.h)
     const int* n_anc;      // [n_seg]
     double4* planes;       // [n_seg][plane_stride], by tree-order position
     size_t plane_stride;
 };
-constexpr int kMaxAnc64 = 192;
 void launch_bh_walk_fast(hipStream_t s, const Dev& d, const Node64* nodes, int n_nodes, const int* order, int n_order, double g, double eps2,
                          double theta2, unsigned long long* counters, int leaf_direct, const WalkSplit64& split, int bodies_per_lane = 1,
                          const double* kick_dt = nullptr /* fuse integrate_after_force into the plane reduction */, int* kicked = nullptr);

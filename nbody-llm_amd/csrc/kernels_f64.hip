@@ -303,7 +303,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_walk_direct(const Node64* __r
 __device__ __forceinline__ int walk_entry64(const Node64* __restrict__ nodes, const WalkSplit64& sp, int seg, const double4 p, double theta2, bool direct) {
     const int na = sp.n_anc[seg];
     for (int k = 0; k < na; ++k) {
-        const Node64 nd = nodes[sp.anc[seg * kMaxAnc64 + k]];
+        const Node64 nd = nodes[sp.anc[seg * nbody::kMaxAnc + k]];
         const double rx = nd.x - p.x, ry = nd.y - p.y, rz = nd.z - p.z;
         const double r2 = (rx * rx + ry * ry) + rz * rz;
         if (direct && r2 < 1e-10) return nd.skip;

@@ -23,35 +23,12 @@
 
 static thread_local std::string g_create_err;
 
-namespace {
-
-using clk = std::chrono::steady_clock;
-inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
-
 int fail(NbodyHandle* h, int code, const std::string& msg) {
     if (h) h->err = msg; else g_create_err = msg;
     return code;
 }
 
-#define HIP_TRY(h, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail(h, NBODY_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
-    } while (0)
-
-#define TP_TRY(h, expr)                                                                               \
-    do {                                                                                              \
-        int r_ = (expr);                                                                              \
-        if (r_ != NBODY_OK) return fail(h, r_, std::string(#expr) + ": " + (h)->tp->error());         \
-    } while (0)
-
-void* pinned_alloc(size_t n) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return nullptr;
-    return p;
-}
-void pinned_free(void* p) { (void)hipHostFree(p); }
+namespace {
 
 int use_device(NbodyHandle* h) {
     nbody::bind_tuning(&h->tune);   // the launchers below read this handle's knobs (kernels.h)
@@ -215,28 +192,6 @@ int sharded_remove_point(NbodyHandle* h, size_t index) {
     return comm_check(h);
 }
 
-struct ForceTimer {  // HIP events around a force-kernel launch, on the launch stream
-    NbodyHandle* h;
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    explicit ForceTimer(NbodyHandle* hh) : h(hh) {
-        h->timed_this = false;
-        if (!h->profiling) return;
-        // (an event pair costs the stream ~11 us: with nbody_set_profiling(h, k > 1) only every k-th launch is bracketed)
-        if (h->profile_every > 1 && (h->profile_tick++ % unsigned(h->profile_every)) != 0) return;
-        h->timed_this = true;
-        if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); }
-        else {
-            if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.second) != hipSuccess) { ev = {nullptr, nullptr}; return; }
-        }
-        (void)hipEventRecord(ev.first, h->stream);
-    }
-    ~ForceTimer() {
-        if (!ev.first) return;
-        (void)hipEventRecord(ev.second, h->stream);
-        h->ev_pending.push_back(ev);
-    }
-};
-
 int drain_events(NbodyHandle* h) {
     if (h->ev_pending.empty()) return NBODY_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -394,21 +349,8 @@ int bf_forces(NbodyHandle* h) {
 }
 
 int ensure_tree_dev(NbodyHandle* h, size_t nodes, size_t order) {
-    if (nodes > h->d_node_cap) {
-        if (h->d_nodes) (void)hipFree(h->d_nodes);
-        h->d_nodes = nullptr; h->d_node_cap = 0;
-        size_t cap = nodes + nodes / 4 + 1024;
-        HIP_TRY(h, hipMalloc(&h->d_nodes, cap * 2 * sizeof(float4)));
-        h->d_node_cap = cap;
-    }
-    if (order > h->d_order_cap) {
-        if (h->d_order) (void)hipFree(h->d_order);
-        h->d_order = nullptr; h->d_order_cap = 0;
-        size_t cap = order + order / 4 + 1024;
-        HIP_TRY(h, hipMalloc(&h->d_order, cap * sizeof(int)));
-        h->d_order_cap = cap;
-    }
-    return NBODY_OK;
+    int rc = grow_dev(h, h->d_nodes, h->d_node_cap, nodes, sizeof(nbody::NodeRec));
+    return rc ? rc : grow_dev(h, h->d_order, h->d_order_cap, order, sizeof(int));
 }
 
 // BarnesHutSimulation::update_forces (barnes_hut.rs:250-263): rebuild the tree from the current
@@ -498,6 +440,25 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
 #endif
 }
 
+// the end of every f32 force pass: the buffers of the strict and the experimental walks, the walk over td (+ the kick and half
+// drift when a step asked for them and the plane reduction can take them along)
+int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
+    int rc = ensure_nested_stack(h, &td);
+    if (!rc) rc = setup_lds_walk(h, &td, n_tree);
+    if (rc) return rc;
+    {
+        ForceTimer t(h);
+        int kicked = 0;
+        nbody::launch_bh_walk(h->stream, h->sh, td, h->g, h->g_soft * h->g_soft, h->theta2,
+                              h->cfg.math_mode == NBODY_MATH_FAST, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
+                              h->kick_pending ? &h->kick_dt : nullptr, &kicked);
+        if (kicked) h->kick_pending = false;  // the plane reduction applied the kick + half drift
+    }
+    if (td.hot_cap > 0) HIP_TRY(h, hipMemcpyAsync(h->h_hot_info, h->d_hot_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipGetLastError());
+    return NBODY_OK;
+}
+
 int bh_forces(NbodyHandle* h) {
     Shard& sh = h->sh;
     {
@@ -518,129 +479,24 @@ int bh_forces(NbodyHandle* h) {
     }
     h->host_tree_once = false;
     h->tree_on_device = false;
-    auto t0 = clk::now();
-    // positions of every segment (upper-bound counts) + the live counts, one sync
-    for (int s = 0; s < sh.n_seg; ++s) {
-        size_t cnt = size_t(h->seg_count_host[s]);
-        if (cnt)
-            HIP_TRY(h, hipMemcpyAsync(h->h_pos + 4 * size_t(s) * sh.seg_cap, sh.pos_all + size_t(s) * sh.seg_cap,
-                                      cnt * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->h_counts, sh.seg_count, sizeof(int) * sh.n_seg, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int s = 0; s < sh.n_seg; ++s) h->seg_count_host[s] = h->h_counts[s];
-    h->n_local = size_t(h->h_counts[sh.my_seg]);
-    h->count_dirty = false;
-    double copy_ms = ms_since(t0);
-
-    auto t1 = clk::now();
-    nbody::build_octree(h->h_pos, sh.n_seg, sh.seg_cap, h->h_counts, h->center, h->width, *h->pool, h->tree_scratch, h->tree);
-    if (h->tree.too_deep) return fail(h, NBODY_ERR_TREE_DEPTH, "octree deeper than NBODY_MAX_TREE_DEPTH (coincident bodies?)");
-    // bodies of the own segment in tree order (ids are s*seg_cap + j)
-    const int32_t* order = h->tree.order;
-    size_t n_order = h->tree.n_order;
-    if (sh.n_seg > 1) {
-        h->own_order.clear();
-        const int lo = sh.my_seg * sh.seg_cap, hi = lo + sh.seg_cap;
-        for (size_t k = 0; k < h->tree.n_order; ++k) {
-            int id = h->tree.order[k];
-            if (id >= lo && id < hi) h->own_order.push_back(id - lo);
-        }
-        order = h->own_order.data();
-        n_order = h->own_order.size();
-    }
-    h->stats.tree_build_ms += ms_since(t1);
-    h->stats.tree_nodes = h->tree.n_nodes;
-
-    auto t2 = clk::now();
-    int rc = ensure_tree_dev(h, h->tree.n_nodes, n_order);
+    HostTreePass<float, float4> pass{reinterpret_cast<const float*>(sh.pos_all), sh.seg_count, sh.n_seg, sh.seg_cap, sh.my_seg, h->h_pos,
+                                     h->h_counts, h->seg_count_host, h->n_local, h->count_dirty, h->center, h->width, h->tree,
+                                     h->tree_scratch, h->own_order, h->d_nodes, h->d_node_cap, h->d_order, h->d_order_cap};
+    int rc = pass.run(h);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->d_nodes, h->tree.nodes, h->tree.n_nodes * sizeof(nbody::NodeRec), hipMemcpyHostToDevice, h->stream));
-    if (n_order) HIP_TRY(h, hipMemcpyAsync(h->d_order, order, n_order * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (sh.n_seg > 1) HIP_TRY(h, hipStreamSynchronize(h->stream));  // own_order is pageable and reused
-    h->stats.tree_copy_ms += copy_ms + ms_since(t2);
-
+    // split the node range over several waves per body group when there are too few bodies to fill the chip (>= 8 waves per
+    // SIMD wanted: the walk is bound by the latency of dependent loads).  ~3 waves per wave slot of the chip (256 CUs x 32),
+    // handed out heaviest first (nbody::tuning().bh_walk_order): the launch lasts as long as its slowest wave, and smaller
+    // pieces started in the right order shorten that tail (N = 65 536: 24 segments 0.310 ms, 8 segments 0.336 ms; tools/tune_bh_order.py)
+    const int K = walk_split_plan(pass.n_order, h->cfg.math_mode != NBODY_MATH_STRICT, h->theta2, h->tree.n_nodes).segments;
+    rc = h->split.ensure(h, K, size_t(sh.seg_cap));
+    if (!rc) rc = h->split.list_on_host(h, h->stream, h->tree.nodes, int(h->tree.n_nodes), K);
+    if (rc) return rc;
     nbody::TreeDev td;
     td.nodes = h->d_nodes; td.n_nodes = int(h->tree.n_nodes);
-    td.order = h->d_order; td.n_order = int(n_order);
-    // split the node range over several waves per body group when there are too few bodies to fill
-    // the chip (>= 8 waves per SIMD wanted: the walk is bound by the latency of dependent loads)
-    {
-        constexpr int kMaxSplit = 64, kMaxAnc = 192;
-        // ~3 waves per wave slot of the chip (256 CUs x 32), handed out heaviest first (nbody::tuning().bh_walk_order): the launch
-        // lasts as long as its slowest wave, and smaller pieces started in the right order shorten that tail
-        // (N = 65 536: 24 segments 0.310 ms, 8 segments 0.336 ms; tools/tune_bh_order.py)
-        int K = nbody::walk_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT, kMaxSplit, h->theta2).segments;
-        // strict math is the parity path: one segment, so every lane adds in the reference's order (bit-exact)
-        if (h->cfg.math_mode == NBODY_MATH_STRICT && nbody::tuning().bh_walk_split <= 0) K = 1;
-        while (nbody::tuning().bh_walk_split <= 0 && K > 1 && size_t(K) * 16 > h->tree.n_nodes) K /= 2;   // (a pinned split is taken as given)
-        if (K > 1) {
-            if (!h->d_split) {
-                HIP_TRY(h, hipMalloc(&h->d_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int)));
-                HIP_TRY(h, hipHostMalloc(&h->h_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int), hipHostMallocDefault));
-            }
-            int* first = h->h_split;
-            int* n_anc = first + kMaxSplit + 1;
-            int* anc = n_anc + kMaxSplit;
-            const nbody::NodeRec* nd = h->tree.nodes;
-            const int nn = int(h->tree.n_nodes);
-            for (int k = 0; k <= K; ++k) first[k] = int((long long)nn * k / K);
-            for (int k = 0; k < K; ++k) {  // ancestors of first[k]: walk down from the root along the skip links
-                int cnt = 0, j = 0;
-                const int target = first[k];
-                while (j != target && cnt < kMaxAnc) {
-                    anc[k * kMaxAnc + cnt++] = j;          // j < target < skip(j): an ancestor
-                    int c = j + 1;                         // its first child
-                    while (nd[c].b.skip <= target) c = nd[c].b.skip;  // siblings in orthant order
-                    j = c;
-                }
-                n_anc[k] = cnt;
-            }
-            const size_t ints = size_t(kMaxSplit + 1 + kMaxSplit + K * kMaxAnc);
-            HIP_TRY(h, hipMemcpyAsync(h->d_split, h->h_split, ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            const size_t need = size_t(K) * sh.seg_cap;
-            if (need > h->walk_planes_cap) {
-                if (h->d_walk_planes) (void)hipFree(h->d_walk_planes);
-                h->d_walk_planes = nullptr; h->walk_planes_cap = 0;
-                HIP_TRY(h, hipMalloc(&h->d_walk_planes, need * sizeof(float4)));
-                h->walk_planes_cap = need;
-            }
-            td.n_split = K;
-            td.split_first = h->d_split;
-            td.split_n_anc = h->d_split + kMaxSplit + 1;
-            td.split_anc = h->d_split + kMaxSplit + 1 + kMaxSplit;
-            td.split_planes = h->d_walk_planes;
-            td.split_stride = size_t(sh.seg_cap);
-        } else {
-            if (!h->d_split) {
-                HIP_TRY(h, hipMalloc(&h->d_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int)));
-                HIP_TRY(h, hipHostMalloc(&h->h_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int), hipHostMallocDefault));
-            }
-            h->h_split[0] = 0; h->h_split[1] = int(h->tree.n_nodes); h->h_split[kMaxSplit + 1] = 0;
-            HIP_TRY(h, hipMemcpyAsync(h->d_split, h->h_split, (kMaxSplit + 2) * sizeof(int), hipMemcpyHostToDevice, h->stream));
-            td.n_split = 1;
-            td.split_first = h->d_split;
-            td.split_n_anc = h->d_split + kMaxSplit + 1;
-            td.split_anc = h->d_split + kMaxSplit + 1 + kMaxSplit;
-        }
-    }
-    {
-        int rc_ns = ensure_nested_stack(h, &td);
-        if (rc_ns) return rc_ns;
-        rc_ns = setup_lds_walk(h, &td, h->tree.n_order);
-        if (rc_ns) return rc_ns;
-    }
-    {
-        ForceTimer t(h);
-        int kicked = 0;
-        nbody::launch_bh_walk(h->stream, sh, td, h->g, h->g_soft * h->g_soft, h->theta2,
-                              h->cfg.math_mode == NBODY_MATH_FAST, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
-                              h->kick_pending ? &h->kick_dt : nullptr, &kicked);
-        if (kicked) h->kick_pending = false;  // the plane reduction applied the kick + half drift
-    }
-    if (td.hot_cap > 0) HIP_TRY(h, hipMemcpyAsync(h->h_hot_info, h->d_hot_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipGetLastError());
-    return NBODY_OK;
+    td.order = h->d_order; td.n_order = int(pass.n_order);
+    walk_split_view(h->split, K, size_t(sh.seg_cap), &td);
+    return walk_tree(h, td, h->tree.n_order);
 }
 
 // Barnes-Hut force pass with the octree built on the device (kernels_tree.hip): no positions go to
@@ -650,27 +506,18 @@ int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
     auto t1 = clk::now();
     const bool sharded = sh.n_seg > 1;
     const size_t n_cap = size_t(sh.seg_cap) * sh.n_seg;  // the tree holds the bodies of every segment
-    if (h->tree_ws_cap < n_cap) {
-        if (h->d_tree_ws) (void)hipFree(h->d_tree_ws);
-        if (h->d_tree_cat) (void)hipFree(h->d_tree_cat);
-        h->d_tree_ws = nullptr; h->d_tree_cat = nullptr; h->tree_ws_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_tree_ws, nbody::tree_build_workspace_bytes(n_cap)));
-        if (sharded) HIP_TRY(h, hipMalloc(&h->d_tree_cat, nbody::tree_cat_bytes(n_cap)));
-        h->tree_ws_cap = n_cap;
-    }
-    if (!h->d_tree_info) {
-        HIP_TRY(h, hipMalloc(&h->d_tree_info, 4 * sizeof(int)));
-        HIP_TRY(h, hipHostMalloc(&h->h_tree_info, 4 * sizeof(int), hipHostMallocDefault));
-    }
+    TreeBuildBufs& tb = h->tree_bufs;
+    int rc = tb.ensure(h, n_cap, sharded ? nbody::tree_cat_bytes(n_cap) : 0);
+    if (rc) return rc;
     const size_t tot_upper = total_upper(h);
     // a Plummer sphere gives ~1.5 nodes per body; 4 per body + the count read-back below catch the rest
-    int rc = ensure_tree_dev(h, std::max<size_t>(h->d_node_cap, 4 * tot_upper + 64), tot_upper);
+    rc = ensure_tree_dev(h, std::max<size_t>(h->d_node_cap, 4 * tot_upper + 64), tot_upper);
     if (rc) return rc;
     nbody::TreeCat cat;
     const float4* tree_pos = sh.own_pos();
     const int* tree_count = sh.own_count();
     if (sharded) {  // every GPU builds the same tree over the gathered bodies of all segments
-        cat = nbody::tree_cat_layout(h->d_tree_cat, n_cap);
+        cat = nbody::tree_cat_layout(tb.cat, n_cap);
         nbody::launch_tree_cat(h->stream, sh, cat);
         tree_pos = cat.pos;
         tree_count = cat.info;
@@ -678,29 +525,29 @@ int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
     nbody::TreeDevWork work;
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (nbody::build_octree_device(h->stream, tree_pos, tree_count, int(tot_upper), h->center, h->width,
-                                       h->d_tree_ws, n_cap, h->d_nodes, int(h->d_node_cap), h->d_order, h->d_tree_info,
+                                       tb.ws, n_cap, h->d_nodes, int(h->d_node_cap), h->d_order, tb.d_info,
                                        &work, nbody::tuning().bh_walk_variant == 3) != 0)
             return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
         HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(h->h_tree_info, h->d_tree_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(tb.h_info, tb.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         if (sharded)
             HIP_TRY(h, hipMemcpyAsync(h->h_counts, sh.seg_count, sizeof(int) * sh.n_seg, hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (!sharded) h->h_counts[0] = h->h_tree_info[2];  // one shard: the tree's body count is the live count
-        if (!(h->h_tree_info[1] & 2)) break;
-        rc = ensure_tree_dev(h, size_t(h->h_tree_info[0]) + 64, tot_upper);  // more nodes than allowed for: grow, rebuild
+        if (!sharded) h->h_counts[0] = tb.h_info[2];  // one shard: the tree's body count is the live count
+        if (!(tb.h_info[1] & 2)) break;
+        rc = ensure_tree_dev(h, size_t(tb.h_info[0]) + 64, tot_upper);  // more nodes than allowed for: grow, rebuild
         if (rc) return rc;
     }
     for (int s = 0; s < sh.n_seg; ++s) h->seg_count_host[s] = h->h_counts[s];
     h->n_local = size_t(h->h_counts[sh.my_seg]);
     h->count_dirty = false;
-    if (h->h_tree_info[1] & 5) { *fell_back = true; return NBODY_OK; }   // deeper than 42 levels / a clump beyond the build's sort: host build
-    const int n_nodes = h->h_tree_info[0];
+    if (tb.h_info[1] & 5) { *fell_back = true; return NBODY_OK; }   // deeper than 42 levels / a clump beyond the build's sort: host build
+    const int n_nodes = tb.h_info[0];
     const size_t n_order = h->n_local;             // bodies this GPU walks
     const size_t n_tree = total_upper(h);          // bodies in the tree (now exact)
     const int* d_walk_order = h->d_order;
     if (sharded) {
-        if (nbody::launch_tree_own_order(h->stream, h->d_order, cat, int(n_tree), h->d_tree_ws, nbody::tree_build_tmp_bytes(n_cap)) != 0)
+        if (nbody::launch_tree_own_order(h->stream, h->d_order, cat, int(n_tree), tb.ws, nbody::tree_build_tmp_bytes(n_cap)) != 0)
             return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
         d_walk_order = cat.own_order;
     }
@@ -709,130 +556,53 @@ int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
     h->tree_on_device = true;
     h->tree.n_nodes = size_t(n_nodes);  // (the host copy is filled on demand by nbody_tree_export)
 
-    constexpr int kMaxSplit = 64, kMaxAnc = 192;
-    if (!h->d_split) {
-        HIP_TRY(h, hipMalloc(&h->d_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int)));
-        HIP_TRY(h, hipHostMalloc(&h->h_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int), hipHostMallocDefault));
-    }
-    int K = nbody::walk_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT, kMaxSplit, h->theta2).segments;
-    if (h->cfg.math_mode == NBODY_MATH_STRICT && nbody::tuning().bh_walk_split <= 0) K = 1;  // parity path: the reference's sum order
-    while (nbody::tuning().bh_walk_split <= 0 && K > 1 && K * 16 > n_nodes) K /= 2;
-    if (n_order == 0) K = 1;
+    const int K = walk_split_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT, h->theta2, size_t(n_nodes)).segments;
+    rc = h->split.ensure(h, K, size_t(sh.seg_cap));
+    if (rc) return rc;
+    if (n_tree > 0) h->split.list_on_device(h->stream, work, int(n_tree), n_nodes, K);
     nbody::TreeDev td;
     td.nodes = h->d_nodes; td.n_nodes = n_nodes;
     td.order = d_walk_order; td.n_order = int(n_order);
-    td.n_split = K;
-    td.split_first = h->d_split;
-    td.split_n_anc = h->d_split + kMaxSplit + 1;
-    td.split_anc = h->d_split + kMaxSplit + 1 + kMaxSplit;
-    if (n_tree > 0)
-        nbody::launch_tree_split_anc(h->stream, work, int(n_tree), n_nodes, K, h->d_split, h->d_split + kMaxSplit + 1,
-                                     h->d_split + kMaxSplit + 1 + kMaxSplit, kMaxAnc);
-    if (K > 1) {
-        const size_t need = size_t(K) * sh.seg_cap;
-        if (need > h->walk_planes_cap) {
-            if (h->d_walk_planes) (void)hipFree(h->d_walk_planes);
-            h->d_walk_planes = nullptr; h->walk_planes_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_walk_planes, need * sizeof(float4)));
-            h->walk_planes_cap = need;
-        }
-        td.split_planes = h->d_walk_planes;
-        td.split_stride = size_t(sh.seg_cap);
-    }
-    {
-        int rc_ns = ensure_nested_stack(h, &td);
-        if (rc_ns) return rc_ns;
-        rc_ns = setup_lds_walk(h, &td, n_tree);
-        if (rc_ns) return rc_ns;
-    }
-    {
-        ForceTimer t(h);
-        int kicked = 0;
-        nbody::launch_bh_walk(h->stream, sh, td, h->g, h->g_soft * h->g_soft, h->theta2,
-                              h->cfg.math_mode == NBODY_MATH_FAST, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
-                              h->kick_pending ? &h->kick_dt : nullptr, &kicked);
-        if (kicked) h->kick_pending = false;  // the plane reduction applied the kick + half drift
-    }
-    if (td.hot_cap > 0) HIP_TRY(h, hipMemcpyAsync(h->h_hot_info, h->d_hot_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipGetLastError());
-    return NBODY_OK;
+    walk_split_view(h->split, K, size_t(sh.seg_cap), &td);
+    return walk_tree(h, td, n_tree);
 }
 
 // The same force pass with nothing read back: the node count, the live body count and the build's flags stay on the
-// device (d_tree_info); the split points are placed by k_tree_split_anc from the device's node count, the walk takes
+// device (TreeBuildBufs::d_info); the split points are placed by k_tree_split_anc from the device's node count, the walk takes
 // its body count from the device, and a build that needs the host poisons the run (see NbodyHandle::async_bh).
 int bh_walk_device_tree_async(NbodyHandle* h) {
     Shard& sh = h->sh;
     auto t1 = clk::now();
-    const size_t n_cap = size_t(sh.seg_cap);
-    if (h->tree_ws_cap < n_cap) {
-        if (h->d_tree_ws) (void)hipFree(h->d_tree_ws);
-        h->d_tree_ws = nullptr; h->tree_ws_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_tree_ws, nbody::tree_build_workspace_bytes(n_cap)));
-        h->tree_ws_cap = n_cap;
-    }
-    if (!h->d_tree_info) {
-        HIP_TRY(h, hipMalloc(&h->d_tree_info, 4 * sizeof(int)));
-        HIP_TRY(h, hipHostMalloc(&h->h_tree_info, 4 * sizeof(int), hipHostMallocDefault));
-    }
+    TreeBuildBufs& tb = h->tree_bufs;
+    int rc = tb.ensure(h, size_t(sh.seg_cap), 0);
+    if (rc) return rc;
     const size_t n_upper = h->n_local;   // an upper bound of the live count
-    int rc = ensure_tree_dev(h, std::max<size_t>(h->d_node_cap, 4 * n_upper + 64), n_upper);
+    rc = ensure_tree_dev(h, std::max<size_t>(h->d_node_cap, 4 * n_upper + 64), n_upper);
     if (rc) return rc;
     if (h->pending.empty()) HIP_TRY(h, hipMemsetAsync(h->d_poison + 1, 0, sizeof(int), h->stream));   // steps completed: counted from here
-    constexpr int kMaxSplit = 64, kMaxAnc = 192;
-    if (!h->d_split) {
-        HIP_TRY(h, hipMalloc(&h->d_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int)));
-        HIP_TRY(h, hipHostMalloc(&h->h_split, (kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc) * sizeof(int), hipHostMallocDefault));
-    }
-    int K = nbody::walk_plan(n_upper, h->cfg.math_mode != NBODY_MATH_STRICT, kMaxSplit, h->theta2).segments;
-    if (h->cfg.math_mode == NBODY_MATH_STRICT && nbody::tuning().bh_walk_split <= 0) K = 1;  // parity path: the reference's sum order
-    while (nbody::tuning().bh_walk_split <= 0 && K > 1 && size_t(K) * 16 > n_upper) K /= 2;   // (a tree has at least as many nodes as bodies)
-    if (n_upper == 0) K = 1;
+    // (a tree has at least as many nodes as bodies)
+    const int K = walk_split_plan(n_upper, h->cfg.math_mode != NBODY_MATH_STRICT, h->theta2, n_upper).segments;
+    rc = h->split.ensure(h, K, size_t(sh.seg_cap));
+    if (rc) return rc;
     // the walk's split points ride in the build's last launch (they also make a build that needs the host sticky: Shard::poison)
-    nbody::TreeSplitReq req;
-    req.n_split = K; req.first = h->d_split; req.n_anc = h->d_split + kMaxSplit + 1; req.anc = h->d_split + kMaxSplit + 1 + kMaxSplit;
-    req.max_anc = kMaxAnc; req.info = h->d_tree_info; req.poison = h->d_poison;
+    const nbody::TreeSplitReq req = h->split.request(K, tb.d_info, h->d_poison);
     nbody::TreeDevWork work;
-    if (nbody::build_octree_device(h->stream, sh.own_pos(), sh.own_count(), int(n_upper), h->center, h->width, h->d_tree_ws, n_cap,
-                                   h->d_nodes, int(h->d_node_cap), h->d_order, h->d_tree_info, &work, 0, n_upper > 0 ? &req : nullptr) != 0)
+    if (nbody::build_octree_device(h->stream, sh.own_pos(), sh.own_count(), int(n_upper), h->center, h->width, tb.ws, size_t(sh.seg_cap),
+                                   h->d_nodes, int(h->d_node_cap), h->d_order, tb.d_info, &work, 0, n_upper > 0 ? &req : nullptr) != 0)
         return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
     HIP_TRY(h, hipGetLastError());
     h->stats.tree_build_ms += ms_since(t1);   // (enqueue time: nothing is waited for)
     h->tree_on_device = true;
+    if (n_upper == 0)   // (no build was enqueued: the empty root's one segment, as a launch of its own)
+        h->split.list_on_device(h->stream, work, 0, int(h->d_node_cap), K, tb.d_info, h->d_poison);
     nbody::TreeDev td;
     td.nodes = h->d_nodes; td.n_nodes = int(h->d_node_cap);   // (the plain walks end at the split points, not at n_nodes)
     td.order = h->d_order; td.n_order = int(n_upper);
-    td.n_order_dev = h->d_tree_info + 2;
+    td.n_order_dev = tb.d_info + 2;
     td.poison = h->d_poison;
-    td.n_split = K;
-    td.split_first = h->d_split;
-    td.split_n_anc = h->d_split + kMaxSplit + 1;
-    td.split_anc = h->d_split + kMaxSplit + 1 + kMaxSplit;
-    if (n_upper == 0)   // (no build was enqueued: the empty root's one segment, as a launch of its own)
-        nbody::launch_tree_split_anc(h->stream, work, int(n_upper), int(h->d_node_cap), K, h->d_split, h->d_split + kMaxSplit + 1,
-                                     h->d_split + kMaxSplit + 1 + kMaxSplit, kMaxAnc, h->d_tree_info, h->d_poison);
-    if (K > 1) {
-        const size_t need = size_t(K) * sh.seg_cap;
-        if (need > h->walk_planes_cap) {
-            if (h->d_walk_planes) (void)hipFree(h->d_walk_planes);
-            h->d_walk_planes = nullptr; h->walk_planes_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_walk_planes, need * sizeof(float4)));
-            h->walk_planes_cap = need;
-        }
-        td.split_planes = h->d_walk_planes;
-        td.split_stride = size_t(sh.seg_cap);
-    }
-    rc = ensure_nested_stack(h, &td);
+    walk_split_view(h->split, K, size_t(sh.seg_cap), &td);
+    rc = walk_tree(h, td, n_upper);
     if (rc) return rc;
-    {
-        ForceTimer t(h);
-        int kicked = 0;
-        nbody::launch_bh_walk(h->stream, sh, td, h->g, h->g_soft * h->g_soft, h->theta2,
-                              h->cfg.math_mode == NBODY_MATH_FAST, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
-                              h->kick_pending ? &h->kick_dt : nullptr, &kicked);
-        if (kicked) h->kick_pending = false;  // the plane reduction applied the kick + half drift
-    }
-    HIP_TRY(h, hipGetLastError());
     h->last_step_async = true;
     h->count_dirty = true;
     return NBODY_OK;
@@ -844,11 +614,11 @@ int resolve_async(NbodyHandle* h) {
     if (!h->async_bh) return NBODY_OK;
     for (int round = 0; round < 1000000; ++round) {
         HIP_TRY(h, hipMemcpyAsync(h->h_poison, h->d_poison, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (h->d_tree_info) HIP_TRY(h, hipMemcpyAsync(h->h_poison + 2, h->d_tree_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (h->tree_bufs.d_info) HIP_TRY(h, hipMemcpyAsync(h->h_poison + 2, h->tree_bufs.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         const int flags = h->h_poison[0], done = h->h_poison[1];
         if (!flags) {
-            if (h->tree_on_device && h->d_tree_info) {   // what the last build produced
+            if (h->tree_on_device && h->tree_bufs.d_info) {   // what the last build produced
                 h->tree.n_nodes = size_t(h->h_poison[2]);
                 h->stats.tree_nodes = uint64_t(h->h_poison[2]);
             }
@@ -1012,10 +782,12 @@ void free_all(NbodyHandle* h) {
     nbody64::destroy(h);
     nbody::let::destroy(h);
     void* dev[] = {h->sh.pos_all, h->sh.vel, h->sh.acc, h->sh.seg_count, h->sh.escaped, h->sh.keep, h->sh.tile_state, h->sh.epoch, h->sh.inter, h->d_poison, h->d_aos,
-                   h->d_nodes, h->d_order, h->d_split, h->d_walk_planes, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_tree_ws, h->d_tree_cat, h->d_nested_stack, h->d_tree_info, h->d_counters, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
+                   h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {h->h_aos, h->h_pos, h->h_counts, h->h_counters, h->h_split, h->h_tree_info, h->h_hot_info, h->h_poison};
+    void* host[] = {h->h_aos, h->h_pos, h->h_counts, h->h_counters, h->h_hot_info, h->h_poison};
     for (void* p : host) if (p) (void)hipHostFree(p);
+    h->split.release();
+    h->tree_bufs.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1964,16 +1736,18 @@ int nbody_host_cross_plan(int rank, int world, int seg_cap, int n_own, int* ipt,
     return NBODY_OK;
 }
 
-// Host-only entry (no device needed): where the variable-size rounds of the spatial step (migrants, tree nodes) put their
-// messages, from the all-gathered G x G count matrix -- the arithmetic sender and receiver of every pair share.
+// Host-only entry (no device needed): the launch shapes the library's defaults give n_bodies -- the Barnes-Hut walk's bodies
+// per lane and node-range segments (walk_plan) and the symmetric kernel's bodies per lane -- for tests of the rule.
 int nbody_host_launch_plan(size_t n_bodies, float theta2, int fast_math, int out[3]) {
     if (!out) return NBODY_ERR_INVALID;
     nbody::bind_tuning(nullptr);   // (the library's defaults, not some handle's knobs)
-    const nbody::WalkPlan p = nbody::walk_plan(n_bodies, fast_math != 0, 64, theta2);
+    const nbody::WalkPlan p = nbody::walk_plan(n_bodies, fast_math != 0, nbody::kMaxSplit, theta2);
     out[0] = p.bodies_per_lane; out[1] = p.segments; out[2] = nbody::sym_bodies_per_lane(n_bodies);
     return NBODY_OK;
 }
 
+// Host-only entry (no device needed): where the variable-size rounds of the spatial step (migrants, tree nodes) put their
+// messages, from the all-gathered G x G count matrix -- the arithmetic sender and receiver of every pair share.
 int nbody_host_exchange_layout(const int* matrix, int world, int rank, long long clamp, int packed_send, size_t send_stride,
                                size_t* out_at, size_t* n_out, size_t* in_at, size_t* n_in, size_t* total_in) {
     if (!matrix || world < 1 || world > 16 || rank < 0 || rank >= world || !out_at || !n_out || !in_at || !n_in) return NBODY_ERR_INVALID;

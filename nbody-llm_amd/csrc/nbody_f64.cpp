@@ -9,7 +9,6 @@
 #include "kernels_f64.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -44,47 +43,17 @@ struct State {
     int stack_levels = 0;
     double* d_energy = nullptr;
     size_t energy_blocks = 0;
-    // device-side build (NBODY_TREE_DEVICE): kernels_tree.hip instantiated for double
-    void* d_tree_ws = nullptr;
     const double* kick_dt = nullptr;   // inside a step: the dt the force pass may apply itself (fast walk, split node range)
     int kicked = 0;
-    void* d_tree_cat = nullptr;   // sharded worlds, device build: the gathered live bodies + the own-order filter's arrays
-    size_t tree_ws_cap = 0;    // bodies the workspace is sized for
-    int* d_tree_info = nullptr;   // [4] {nodes, flags, bodies}
-    int* h_tree_info = nullptr;   // pinned
+    // device-side build (NBODY_TREE_DEVICE): kernels_tree.hip instantiated for double
+    TreeBuildBufs tree_bufs;
     nbody::TreeDevWork tree_work;
     bool tree_on_device = false;  // where the last tree lives (nbody_tree_export)
     size_t dev_nodes = 0;
-    // fast walk (NBODY_MATH_FAST): node-range split points and the segments' partial sums
-    int* d_split = nullptr;       // [kMaxSplit + 1 + kMaxSplit + kMaxSplit * kMaxAnc64] first[], n_anc[], anc[][]
-    int* h_split = nullptr;       // pinned mirror (host-built tree)
-    double4* d_planes = nullptr;  // [K][cap]
-    size_t planes_cap = 0;
+    WalkSplitBuf<double4> split;  // fast walk (NBODY_MATH_FAST): the node-range split
 };
 
 namespace {
-
-using clk = std::chrono::steady_clock;
-inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
-
-int fail(NbodyHandle* h, int code, const std::string& msg) {
-    h->err = msg;
-    return code;
-}
-
-#define HIP_TRY(h, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail(h, NBODY_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
-    } while (0)
-
-void* pinned_alloc(size_t n) {
-    void* p = nullptr;
-    if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return nullptr;
-    return p;
-}
-void pinned_free(void* p) { (void)hipHostFree(p); }
 
 int ensure_aos(NbodyHandle* h, State& s, size_t records) {
     if (records <= s.aos_cap) return NBODY_OK;
@@ -115,22 +84,6 @@ int push_count(NbodyHandle* h, State& s) {
     return NBODY_OK;
 }
 
-struct ForceTimer {  // HIP events around a force-kernel launch, on the launch stream (as in nbody_api.cpp)
-    NbodyHandle* h;
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    explicit ForceTimer(NbodyHandle* hh) : h(hh) {
-        if (!h->profiling) return;
-        if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); }
-        else if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.second) != hipSuccess) { ev = {nullptr, nullptr}; return; }
-        (void)hipEventRecord(ev.first, h->stream);
-    }
-    ~ForceTimer() {
-        if (!ev.first) return;
-        (void)hipEventRecord(ev.second, h->stream);
-        h->ev_pending.push_back(ev);
-    }
-};
-
 int bf_forces(NbodyHandle* h, State& s) {
     const double eps2 = s.g_soft * s.g_soft;  // brute_force.rs:69
     {
@@ -138,7 +91,7 @@ int bf_forces(NbodyHandle* h, State& s) {
         launch_bf_strict(h->stream, s.d, int(s.n_local), s.g, eps2);
     }
     HIP_TRY(h, hipGetLastError());
-    if (h->profiling && s.n_local > 0) {
+    if (h->timed_this && s.n_local > 0) {
         uint64_t tot = 0;
         for (int c : s.count_upper) tot += uint64_t(c);
         h->stats.force_kernel_interactions += uint64_t(s.n_local) * (tot - 1);
@@ -161,50 +114,16 @@ int ensure_stack(NbodyHandle* h, State& s, int levels) {   // the nested sums' s
 // The fast walk (NBODY_MATH_FAST on an f64 handle): one running sum per lane, node range split over K segments so that a
 // few ten thousand bodies still fill the chip.  `host_nodes` != nullptr: the split points' ancestors are listed here from
 // the host-built tree; nullptr: by k_tree_split_anc from the device build's arrays (n_tree bodies).
-constexpr int kMaxSplit = 64;
 int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const int* order, int n_order, const nbody::NodeRecT<double>* host_nodes, int n_tree,
               int k_done = 0 /* > 0: the split points of this many segments are on the device already (they rode in the build) */) {
-    constexpr size_t kSplitInts = kMaxSplit + 1 + kMaxSplit + size_t(kMaxSplit) * kMaxAnc64;
-    if (!s.d_split) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_split), kSplitInts * sizeof(int)));
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&s.h_split), kSplitInts * sizeof(int), hipHostMallocDefault));
-    }
-    const nbody::WalkPlan plan = nbody::walk_plan(size_t(n_order), true, kMaxSplit, float(s.theta2));   // (bodies per lane x segments: kernels.h)
-    int K = plan.segments;
-    while (nbody::tuning().bh_walk_split <= 0 && K > 1 && K * 16 > n_nodes) K /= 2;
-    if (k_done > 0) K = k_done;
     if (n_order == 0 || n_nodes <= 0) return NBODY_OK;
-    int* first = s.d_split;
-    int* n_anc = s.d_split + kMaxSplit + 1;
-    int* anc = s.d_split + kMaxSplit + 1 + kMaxSplit;
-    if (k_done > 0) {
-    } else if (host_nodes) {
-        int* hf = s.h_split;
-        int* hn = hf + kMaxSplit + 1;
-        int* ha = hn + kMaxSplit;
-        for (int k = 0; k <= K; ++k) hf[k] = int((long long)n_nodes * k / K);
-        for (int k = 0; k < K; ++k) {   // ancestors of first[k]: down from the root along the skip links
-            int cnt = 0, j = 0;
-            const int target = hf[k];
-            while (j != target && cnt < kMaxAnc64) {
-                ha[k * kMaxAnc64 + cnt++] = j;
-                int c = j + 1;
-                while (host_nodes[c].b.skip <= target) c = host_nodes[c].b.skip;
-                j = c;
-            }
-            hn[k] = cnt;
-        }
-        HIP_TRY(h, hipMemcpyAsync(s.d_split, s.h_split, (kMaxSplit + 1 + kMaxSplit + size_t(K) * kMaxAnc64) * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    } else {
-        nbody::launch_tree_split_anc(h->stream, s.tree_work, n_tree, n_nodes, K, first, n_anc, anc, kMaxAnc64);
-    }
-    if (K > 1 && size_t(K) * size_t(s.d.cap) > s.planes_cap) {
-        if (s.d_planes) (void)hipFree(s.d_planes);
-        s.d_planes = nullptr; s.planes_cap = 0;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_planes), size_t(K) * size_t(s.d.cap) * sizeof(double4)));
-        s.planes_cap = size_t(K) * size_t(s.d.cap);
-    }
-    WalkSplit64 sp{K, first, anc, n_anc, s.d_planes, size_t(s.d.cap)};
+    const nbody::WalkPlan plan = walk_split_plan(size_t(n_order), true, float(s.theta2), size_t(n_nodes));   // (bodies per lane x segments: kernels.h)
+    const int K = k_done > 0 ? k_done : plan.segments;
+    int rc = s.split.ensure(h, K, size_t(s.d.cap));
+    if (!rc && !k_done && host_nodes) rc = s.split.list_on_host(h, h->stream, host_nodes, n_nodes, K);
+    if (rc) return rc;
+    if (!k_done && !host_nodes) s.split.list_on_device(h->stream, s.tree_work, n_tree, n_nodes, K);
+    const WalkSplit64 sp = walk_split_view(s.split, K, size_t(s.d.cap));
     {
         ForceTimer t(h);
         launch_bh_walk_fast(h->stream, s.d, nodes, n_nodes, order, n_order, s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
@@ -226,18 +145,9 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     size_t tot_upper = 0;
     for (int g = 0; g < G; ++g) tot_upper += size_t(s.count_upper[size_t(g)]);
     if (!sharded) tot_upper = s.n_local;
-    if (s.tree_ws_cap < cap) {
-        if (s.d_tree_ws) (void)hipFree(s.d_tree_ws);
-        if (s.d_tree_cat) (void)hipFree(s.d_tree_cat);
-        s.d_tree_ws = nullptr; s.d_tree_cat = nullptr; s.tree_ws_cap = 0;
-        HIP_TRY(h, hipMalloc(&s.d_tree_ws, nbody::tree_build_workspace_bytes(cap)));
-        if (sharded) HIP_TRY(h, hipMalloc(&s.d_tree_cat, nbody::tree_cat_bytes64(cap)));
-        s.tree_ws_cap = cap;
-    }
-    if (!s.d_tree_info) {
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_tree_info), 4 * sizeof(int)));
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&s.h_tree_info), 4 * sizeof(int), hipHostMallocDefault));
-    }
+    TreeBuildBufs& tb = s.tree_bufs;
+    int rc = tb.ensure(h, cap, sharded ? nbody::tree_cat_bytes64(cap) : 0);
+    if (rc) return rc;
     if (cap > s.order_cap) {
         if (s.d_order) (void)hipFree(s.d_order);
         s.d_order = nullptr; s.order_cap = 0;
@@ -249,7 +159,7 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     nbody::TreeCat cat;
     if (sharded) {
         double4* pos_cat = nullptr;
-        cat = nbody::tree_cat_layout64(s.d_tree_cat, cap, &pos_cat);
+        cat = nbody::tree_cat_layout64(tb.cat, cap, &pos_cat);
         nbody::launch_tree_cat64(h->stream, s.d.pos_all, s.d.seg_count, G, s.d.cap, s.d.my_seg, pos_cat, cat.info);
         tree_pos = pos_cat;
         tree_count = cat.info;
@@ -258,16 +168,10 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     nbody::TreeSplitReq req;
     int k_pre = 0;
     if (!sharded && h->cfg.math_mode == NBODY_MATH_FAST && tot_upper > 0) {
-        constexpr size_t kSplitInts = kMaxSplit + 1 + kMaxSplit + size_t(kMaxSplit) * kMaxAnc64;
-        if (!s.d_split) {
-            HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_split), kSplitInts * sizeof(int)));
-            HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&s.h_split), kSplitInts * sizeof(int), hipHostMallocDefault));
-        }
-        int K = nbody::walk_plan(tot_upper, true, kMaxSplit, float(s.theta2)).segments;
-        while (nbody::tuning().bh_walk_split <= 0 && K > 1 && size_t(K) * 16 > tot_upper) K /= 2;   // (a tree has at least as many nodes as bodies)
-        req.n_split = K; req.first = s.d_split; req.n_anc = s.d_split + kMaxSplit + 1; req.anc = s.d_split + kMaxSplit + 1 + kMaxSplit;
-        req.max_anc = kMaxAnc64; req.info = s.d_tree_info; req.poison = nullptr;
-        k_pre = K;
+        k_pre = walk_split_plan(tot_upper, true, float(s.theta2), tot_upper).segments;   // (a tree has at least as many nodes as bodies)
+        rc = s.split.ensure(h, k_pre, size_t(s.d.cap));
+        if (rc) return rc;
+        req = s.split.request(k_pre, tb.d_info, nullptr);
     }
     for (int attempt = 0; attempt < 2; ++attempt) {
         if (s.node_cap < 2 * tot_upper + 64) {
@@ -277,40 +181,40 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
             HIP_TRY(h, hipMalloc(&s.d_nodes, want * sizeof(Node64)));
             s.node_cap = want;
         }
-        if (nbody::build_octree_device_f64(h->stream, tree_pos, tree_count, int(tot_upper), s.center, s.width, s.d_tree_ws, s.tree_ws_cap, s.d_nodes,
-                                           int(std::min<size_t>(s.node_cap, 0x7fffffff)), s.d_order, s.d_tree_info, &s.tree_work, k_pre ? &req : nullptr) != 0)
+        if (nbody::build_octree_device_f64(h->stream, tree_pos, tree_count, int(tot_upper), s.center, s.width, tb.ws, tb.cap, s.d_nodes,
+                                           int(std::min<size_t>(s.node_cap, 0x7fffffff)), s.d_order, tb.d_info, &s.tree_work, k_pre ? &req : nullptr) != 0)
             return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
-        HIP_TRY(h, hipMemcpyAsync(s.h_tree_info, s.d_tree_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(tb.h_info, tb.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         if (sharded) HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d.seg_count, sizeof(int) * size_t(G), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (s.h_tree_info[1] & 5) { *fell_back = true; return NBODY_OK; }
-        if (!(s.h_tree_info[1] & 2)) break;
-        s.dev_nodes = size_t(s.h_tree_info[0]);   // the array was too small: the build says how many it needs
+        if (tb.h_info[1] & 5) { *fell_back = true; return NBODY_OK; }
+        if (!(tb.h_info[1] & 2)) break;
+        s.dev_nodes = size_t(tb.h_info[0]);   // the array was too small: the build says how many it needs
         s.node_cap = 0;
         if (attempt == 1) return fail(h, NBODY_ERR_CAPACITY, "device octree build: node array too small twice");
     }
     if (sharded) {   // the live counts of every block, and the own bodies' places in the tree order
         size_t total = 0;
         for (int g = 0; g < G; ++g) { s.count_upper[size_t(g)] = s.h_count[g]; total += size_t(s.h_count[g]); }
-        s.dev_nodes = size_t(s.h_tree_info[0]);
+        s.dev_nodes = size_t(tb.h_info[0]);
         s.n_local = size_t(s.h_count[s.d.my_seg]);
         s.count_dirty = false;
         s.tree_on_device = true;
-        if (nbody::launch_tree_own_order(h->stream, s.d_order, cat, int(total), s.d_tree_ws, nbody::tree_build_tmp_bytes(cap)) != 0)
+        if (nbody::launch_tree_own_order(h->stream, s.d_order, cat, int(total), tb.ws, nbody::tree_build_tmp_bytes(cap)) != 0)
             return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
         h->stats.tree_build_ms += ms_since(t0);
         h->stats.tree_nodes = s.dev_nodes;
         return fast_walk(h, s, s.d_nodes, int(s.dev_nodes), cat.own_order, int(s.n_local), nullptr, int(total));
     }
-    s.dev_nodes = size_t(s.h_tree_info[0]);
-    s.n_local = size_t(s.h_tree_info[2]);
+    s.dev_nodes = size_t(tb.h_info[0]);
+    s.n_local = size_t(tb.h_info[2]);
     s.count_dirty = false;
     s.tree_on_device = true;
     h->stats.tree_build_ms += ms_since(t0);
     h->stats.tree_nodes = s.dev_nodes;
     if (h->cfg.math_mode == NBODY_MATH_FAST) return fast_walk(h, s, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), nullptr, int(s.n_local), k_pre);
     const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
-    if (!direct) { int rc = ensure_stack(h, s, 45); if (rc) return rc; }   // (the device build goes to 42 levels)
+    if (!direct) { rc = ensure_stack(h, s, 45); if (rc) return rc; }   // (the device build goes to 42 levels)
     {
         ForceTimer t(h);
         launch_bh_walk(h->stream, s.d, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
@@ -328,60 +232,17 @@ int bh_forces(NbodyHandle* h, State& s) {
         if (rc || !fell_back) return rc;
     }
     s.tree_on_device = false;
-    auto t0 = clk::now();
-    const int G = s.d.n_seg;
-    for (int g = 0; g < G; ++g) {   // every block's positions (upper-bound counts) + the live counts, one synchronisation
-        const size_t cnt = size_t(s.count_upper[size_t(g)]);
-        if (cnt) HIP_TRY(h, hipMemcpyAsync(s.h_pos + 4 * size_t(g) * s.d.cap, s.d.pos_all + size_t(g) * s.d.cap, cnt * sizeof(double4), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d.seg_count, sizeof(int) * G, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int g = 0; g < G; ++g) s.count_upper[size_t(g)] = s.h_count[g];
-    s.n_local = size_t(s.h_count[s.d.my_seg]);
-    s.count_dirty = false;
-    const double copy_ms = ms_since(t0);
-    auto t1 = clk::now();
-    nbody::build_octree<double>(s.h_pos, G, s.d.cap, s.h_count, s.center, s.width, *h->pool, s.scratch, s.tree);
-    if (s.tree.too_deep) return fail(h, NBODY_ERR_TREE_DEPTH, "octree deeper than NBODY_MAX_TREE_DEPTH (coincident bodies?)");
-    // the own bodies in tree order (ids are block * cap + index in the block)
-    const int32_t* order = s.tree.order;
-    size_t n_order = s.tree.n_order;
-    if (G > 1) {
-        s.own_order.clear();
-        const int lo = s.d.my_seg * s.d.cap, hi = lo + s.d.cap;
-        for (size_t k = 0; k < s.tree.n_order; ++k) {
-            const int id = s.tree.order[k];
-            if (id >= lo && id < hi) s.own_order.push_back(id - lo);
-        }
-        order = s.own_order.data();
-        n_order = s.own_order.size();
-    }
-    h->stats.tree_build_ms += ms_since(t1);
-    h->stats.tree_nodes = s.tree.n_nodes;
-    auto t2 = clk::now();
-    if (s.tree.n_nodes > s.node_cap) {
-        if (s.d_nodes) (void)hipFree(s.d_nodes);
-        s.d_nodes = nullptr; s.node_cap = 0;
-        const size_t cap = s.tree.n_nodes + s.tree.n_nodes / 4 + 1024;
-        HIP_TRY(h, hipMalloc(&s.d_nodes, cap * sizeof(Node64)));
-        s.node_cap = cap;
-    }
-    if (n_order > s.order_cap) {
-        if (s.d_order) (void)hipFree(s.d_order);
-        s.d_order = nullptr; s.order_cap = 0;
-        const size_t cap = n_order + n_order / 4 + 1024;
-        HIP_TRY(h, hipMalloc(&s.d_order, cap * sizeof(int)));
-        s.order_cap = cap;
-    }
     static_assert(sizeof(nbody::NodeRecT<double>) == sizeof(Node64), "host and device node records must agree");
-    HIP_TRY(h, hipMemcpyAsync(s.d_nodes, s.tree.nodes, s.tree.n_nodes * sizeof(Node64), hipMemcpyHostToDevice, h->stream));
-    if (n_order) HIP_TRY(h, hipMemcpyAsync(s.d_order, order, n_order * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    if (G > 1) HIP_TRY(h, hipStreamSynchronize(h->stream));   // own_order is pageable and reused
-    h->stats.tree_copy_ms += copy_ms + ms_since(t2);
+    HostTreePass<double, Node64> pass{reinterpret_cast<const double*>(s.d.pos_all), s.d.seg_count, s.d.n_seg, s.d.cap, s.d.my_seg, s.h_pos,
+                                      s.h_count, s.count_upper, s.n_local, s.count_dirty, s.center, s.width, s.tree, s.scratch, s.own_order,
+                                      s.d_nodes, s.node_cap, s.d_order, s.order_cap};
+    int rc = pass.run(h);
+    if (rc) return rc;
+    const size_t n_order = pass.n_order;
     if (h->cfg.math_mode == NBODY_MATH_FAST)
         return fast_walk(h, s, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.tree.nodes, int(s.tree.n_order));
     const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
-    if (!direct) { int rc = ensure_stack(h, s, s.tree.max_depth + 2); if (rc) return rc; }   // the tree's depth
+    if (!direct) { rc = ensure_stack(h, s, s.tree.max_depth + 2); if (rc) return rc; }   // the tree's depth
     {
         ForceTimer t(h);
         launch_bh_walk(h->stream, s.d, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.g, s.g_soft * s.g_soft, s.theta2,
@@ -473,10 +334,12 @@ void destroy(NbodyHandle* h) {
     if (!s) return;
     s->tree.clear();
     void* dev[] = {s->d.pos_all, s->d.vel, s->d.acc, s->d.seg_count, s->d.escaped, s->d.keep, s->d.tile_state, s->d.epoch, s->d.inter,
-                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_tree_ws, s->d_tree_cat, s->d_tree_info, s->d_split, s->d_planes};
+                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {s->h_count, s->h_aos, s->h_pos, s->h_tree_info, s->h_split};
+    void* host[] = {s->h_count, s->h_aos, s->h_pos};
     for (void* p : host) if (p) (void)hipHostFree(p);
+    s->tree_bufs.release();
+    s->split.release();
     delete s;
     h->f64 = nullptr;
 }

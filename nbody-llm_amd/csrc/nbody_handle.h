@@ -2,12 +2,14 @@
 #pragma once
 #include "../../include/nbody_hip.h"
 #include "kernels.h"
+#include "kernels_f64.h"
 #include "octree_host.h"
 
 #include "transport.h"
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <memory>
 #include <string>
 #include <utility>
@@ -18,6 +20,155 @@ using nbody::Shard;
 
 namespace nbody64 { struct State; }   // F = f64 handles (nbody_f64.cpp)
 namespace nbody { namespace let { struct State; } }   // spatial shards (nbody_let.cpp)
+struct NbodyHandle;
+
+// ---- host helpers of every translation unit behind the handle
+
+// records msg as the handle's error (h == nullptr: as nbody_create's) and returns code (nbody_api.cpp)
+int fail(NbodyHandle* h, int code, const std::string& msg);
+
+#define HIP_TRY(h, expr)                                                                              \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess)                                                                         \
+            return fail(h, NBODY_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
+    } while (0)
+
+#define TP_TRY(h, expr)                                                                               \
+    do {                                                                                              \
+        int r_ = (expr);                                                                              \
+        if (r_ != NBODY_OK) return fail(h, r_, std::string(#expr) + ": " + (h)->tp->error());         \
+    } while (0)
+
+using clk = std::chrono::steady_clock;
+inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
+
+inline void* pinned_alloc(size_t n) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return nullptr;
+    return p;
+}
+inline void pinned_free(void* p) { (void)hipHostFree(p); }
+
+// ---- the Barnes-Hut walk's node-range split (kernels.h kMaxSplit: the layout of its int array), for f32 and f64 walks:
+// the buffers, the number of segments, the listing of the split points' ancestors, the walk's view of them
+
+// segments of a walk over n_walk bodies: walk_plan's, halved while a segment would hold fewer than 16 of n_bound nodes;
+// strict math walks in one piece (the reference's sum order); a pinned NBODY_BH_SPLIT is taken as given; no bodies: one
+inline nbody::WalkPlan walk_split_plan(size_t n_walk, bool fast_math, float theta2, size_t n_bound) {
+    nbody::WalkPlan p = nbody::walk_plan(n_walk, fast_math, nbody::kMaxSplit, theta2);
+    const bool pinned = nbody::tuning().bh_walk_split > 0;
+    if (!fast_math && !pinned) p.segments = 1;
+    while (!pinned && p.segments > 1 && size_t(p.segments) * 16 > n_bound) p.segments /= 2;
+    if (n_walk == 0) p.segments = 1;
+    return p;
+}
+
+template <class V>   // float4 (f32 walk) or double4 (f64): the segments' partial sums
+struct WalkSplitBuf {
+    int* d = nullptr;        // [kSplitInts] first[] | n_anc[] | anc[][]
+    int* h = nullptr;        // pinned mirror (ancestors listed on the host)
+    V* planes = nullptr;     // [K][stride] partial sums of the segments, grow-only
+    size_t planes_cap = 0;   // V entries
+
+    int* first() const { return d; }
+    int* n_anc() const { return d + nbody::kMaxSplit + 1; }
+    int* anc() const { return d + 2 * nbody::kMaxSplit + 1; }
+
+    // the int array, and planes for K segments of `stride` bodies
+    int ensure(NbodyHandle* hh, int K, size_t stride) {
+        if (!d) {
+            HIP_TRY(hh, hipMalloc(&d, nbody::kSplitInts * sizeof(int)));
+            HIP_TRY(hh, hipHostMalloc(&h, nbody::kSplitInts * sizeof(int), hipHostMallocDefault));
+        }
+        const size_t need = size_t(K) * stride;
+        if (K > 1 && need > planes_cap) {
+            if (planes) (void)hipFree(planes);
+            planes = nullptr; planes_cap = 0;
+            HIP_TRY(hh, hipMalloc(&planes, need * sizeof(V)));
+            planes_cap = need;
+        }
+        return NBODY_OK;
+    }
+    // K equal parts of a host-built tree's n_nodes; the ancestors of each split point found down from the root along the skip links
+    template <class F>
+    int list_on_host(NbodyHandle* hh, hipStream_t s, const nbody::NodeRecT<F>* nodes, int n_nodes, int K) {
+        int* hf = h;
+        int* hn = h + nbody::kMaxSplit + 1;
+        int* ha = h + 2 * nbody::kMaxSplit + 1;
+        for (int k = 0; k <= K; ++k) hf[k] = int((long long)n_nodes * k / K);
+        for (int k = 0; k < K; ++k) {
+            int cnt = 0, j = 0;
+            const int target = hf[k];
+            while (j != target && cnt < nbody::kMaxAnc) {
+                ha[k * nbody::kMaxAnc + cnt++] = j;   // j < target < skip(j): an ancestor
+                int c = j + 1;                        // its first child
+                while (nodes[c].b.skip <= target) c = nodes[c].b.skip;   // siblings in orthant order
+                j = c;
+            }
+            hn[k] = cnt;
+        }
+        HIP_TRY(hh, hipMemcpyAsync(d, h, (2 * size_t(nbody::kMaxSplit) + 1 + size_t(K) * nbody::kMaxAnc) * sizeof(int), hipMemcpyHostToDevice, s));
+        return NBODY_OK;
+    }
+    // the same from the device build's arrays (info != nullptr: its node and body counts are read on the device)
+    void list_on_device(hipStream_t s, const nbody::TreeDevWork& work, int n, int n_nodes, int K, const int* info = nullptr, int* poison = nullptr) const {
+        nbody::launch_tree_split_anc(s, work, n, n_nodes, K, first(), n_anc(), anc(), nbody::kMaxAnc, info, poison);
+    }
+    // ... or in the build's last launch
+    nbody::TreeSplitReq request(int K, const int* info, int* poison) const {
+        nbody::TreeSplitReq r;
+        r.n_split = K; r.first = first(); r.n_anc = n_anc(); r.anc = anc(); r.max_anc = nbody::kMaxAnc; r.info = info; r.poison = poison;
+        return r;
+    }
+    void release() {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        if (planes) (void)hipFree(planes);
+        d = h = nullptr; planes = nullptr; planes_cap = 0;
+    }
+};
+
+// the walks' views of K segments
+inline void walk_split_view(const WalkSplitBuf<float4>& b, int K, size_t stride, nbody::TreeDev* td) {
+    td->n_split = K;
+    td->split_first = b.first(); td->split_n_anc = b.n_anc(); td->split_anc = b.anc();
+    if (K > 1) { td->split_planes = b.planes; td->split_stride = stride; }
+}
+inline nbody64::WalkSplit64 walk_split_view(const WalkSplitBuf<double4>& b, int K, size_t stride) {
+    return nbody64::WalkSplit64{K, b.first(), b.anc(), b.n_anc(), b.planes, stride};
+}
+
+// ---- the device build's buffers (kernels_tree.hip), f32 and f64
+struct TreeBuildBufs {
+    void* ws = nullptr;        // workspace (keys, sort buffers, scans)
+    void* cat = nullptr;       // sharded worlds: concatenated positions, own-order list
+    size_t cap = 0;            // bodies both are sized for
+    int* d_info = nullptr;     // [4] node count, flags, bodies in the tree
+    int* h_info = nullptr;     // pinned
+
+    // for n_cap bodies; cat_bytes = 0: no concatenation buffer (one shard)
+    int ensure(NbodyHandle* hh, size_t n_cap, size_t cat_bytes) {
+        if (cap < n_cap) {
+            if (ws) (void)hipFree(ws);
+            if (cat) (void)hipFree(cat);
+            ws = nullptr; cat = nullptr; cap = 0;
+            HIP_TRY(hh, hipMalloc(&ws, nbody::tree_build_workspace_bytes(n_cap)));
+            if (cat_bytes) HIP_TRY(hh, hipMalloc(&cat, cat_bytes));
+            cap = n_cap;
+        }
+        if (!d_info) {
+            HIP_TRY(hh, hipMalloc(&d_info, 4 * sizeof(int)));
+            HIP_TRY(hh, hipHostMalloc(&h_info, 4 * sizeof(int), hipHostMallocDefault));
+        }
+        return NBODY_OK;
+    }
+    void release() {
+        for (void* p : {ws, cat, static_cast<void*>(d_info)}) if (p) (void)hipFree(p);
+        if (h_info) (void)hipHostFree(h_info);
+        *this = TreeBuildBufs{};
+    }
+};
 
 struct NbodyHandle {
     NbodyConfig cfg{};
@@ -51,19 +202,12 @@ struct NbodyHandle {
     float* h_pos = nullptr;    // pinned: all segments' positions
     int* h_counts = nullptr;   // pinned: all segments' counts
     std::vector<int32_t> own_order;
-    void* d_tree_ws = nullptr;   // device-build workspace (keys, sort buffers, scans)
-    void* d_tree_cat = nullptr;  // sharded device build: concatenated positions, own-order list
+    TreeBuildBufs tree_bufs;     // the device build's
     float4* d_nested_stack = nullptr;  // strict Barnes-Hut: per-lane stack of open cells (k_bh_walk_nested)
     size_t nested_cap = 0;
     int nested_levels = 0;
-    size_t tree_ws_cap = 0;      // bodies it is sized for
-    int* d_tree_info = nullptr;  // [3] node count, flags, bodies in the tree
-    int* h_tree_info = nullptr;  // pinned
     bool tree_on_device = false; // the last tree was built on the device (export copies it back)
-    int* d_split = nullptr;      // [33 + 32 + 32*192] ints: first[], n_anc[], anc[][192]
-    int* h_split = nullptr;      // pinned mirror
-    float4* d_walk_planes = nullptr;
-    size_t walk_planes_cap = 0;  // float4 entries
+    WalkSplitBuf<float4> split;  // the walk's node-range split
     // fast walk with the most-visited records in LDS (kernels_bh.hip, variant 3)
     float4* d_walk = nullptr;    // [walk_cap + 1] records with explicit links
     int* d_unified = nullptr;    // [walk_cap + 1]
@@ -138,3 +282,108 @@ struct NbodyHandle {
     std::string err;
 };
 
+
+// ---- helpers that need the handle
+
+// grow-only device array: to n + n / 4 + 1024 elements of elem_bytes when it holds fewer than n
+template <class T>
+int grow_dev(NbodyHandle* h, T*& p, size_t& cap, size_t n, size_t elem_bytes) {
+    if (n <= cap) return NBODY_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const size_t want = n + n / 4 + 1024;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&p), want * elem_bytes));
+    cap = want;
+    return NBODY_OK;
+}
+
+struct ForceTimer {  // HIP events around a force-kernel launch, on the launch stream
+    NbodyHandle* h;
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    explicit ForceTimer(NbodyHandle* hh) : h(hh) {
+        h->timed_this = false;
+        if (!h->profiling) return;
+        // (an event pair costs the stream ~11 us: with nbody_set_profiling(h, k > 1) only every k-th launch is bracketed)
+        if (h->profile_every > 1 && (h->profile_tick++ % unsigned(h->profile_every)) != 0) return;
+        h->timed_this = true;
+        if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); }
+        else {
+            if (hipEventCreate(&ev.first) != hipSuccess || hipEventCreate(&ev.second) != hipSuccess) { ev = {nullptr, nullptr}; return; }
+        }
+        (void)hipEventRecord(ev.first, h->stream);
+    }
+    ~ForceTimer() {
+        if (!ev.first) return;
+        (void)hipEventRecord(ev.second, h->stream);
+        h->ev_pending.push_back(ev);
+    }
+};
+
+// The tree of a Barnes-Hut force pass built on the host (BarnesHutSimulation::update_forces, barnes_hut.rs:250-263), F = float
+// or double: every block's positions and live counts back with one synchronisation, build_octree<F>, the own bodies in tree
+// order (ids are block * seg_cap + index in the block), the nodes and that order up to the device.
+template <class F, class NodeDev>
+struct HostTreePass {
+    const F* pos_all;                  // device [n_seg][seg_cap][4]
+    const int* seg_count;              // device [n_seg] live counts
+    int n_seg, seg_cap, my_seg;
+    F* h_pos;                          // pinned, as pos_all
+    int* h_counts;                     // pinned [n_seg]
+    std::vector<int>& count_host;      // every block's live count: upper bounds going in, exact coming out
+    size_t& n_local;
+    bool& count_dirty;
+    const F* center;
+    F width;
+    nbody::HostTreeT<F>& tree;
+    nbody::BuildScratchT<F>& scratch;
+    std::vector<int32_t>& own_order;
+    NodeDev*& d_nodes;                 // one NodeRecT<F> per node
+    size_t& node_cap;
+    int*& d_order;
+    size_t& order_cap;
+    size_t n_order = 0;                // out: own bodies in the tree
+
+    int run(NbodyHandle* h) {
+        auto t0 = clk::now();
+        for (int g = 0; g < n_seg; ++g) {
+            const size_t cnt = size_t(count_host[size_t(g)]);
+            if (cnt)
+                HIP_TRY(h, hipMemcpyAsync(h_pos + 4 * size_t(g) * seg_cap, pos_all + 4 * size_t(g) * seg_cap, cnt * 4 * sizeof(F),
+                                          hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(h, hipMemcpyAsync(h_counts, seg_count, sizeof(int) * n_seg, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (int g = 0; g < n_seg; ++g) count_host[size_t(g)] = h_counts[g];
+        n_local = size_t(h_counts[my_seg]);
+        count_dirty = false;
+        const double copy_ms = ms_since(t0);
+
+        auto t1 = clk::now();
+        nbody::build_octree<F>(h_pos, n_seg, seg_cap, h_counts, center, width, *h->pool, scratch, tree);
+        if (tree.too_deep) return fail(h, NBODY_ERR_TREE_DEPTH, "octree deeper than NBODY_MAX_TREE_DEPTH (coincident bodies?)");
+        const int32_t* order = tree.order;
+        n_order = tree.n_order;
+        if (n_seg > 1) {
+            own_order.clear();
+            const int lo = my_seg * seg_cap, hi = lo + seg_cap;
+            for (size_t k = 0; k < tree.n_order; ++k) {
+                const int id = tree.order[k];
+                if (id >= lo && id < hi) own_order.push_back(id - lo);
+            }
+            order = own_order.data();
+            n_order = own_order.size();
+        }
+        h->stats.tree_build_ms += ms_since(t1);
+        h->stats.tree_nodes = tree.n_nodes;
+
+        auto t2 = clk::now();
+        int rc = grow_dev(h, d_nodes, node_cap, tree.n_nodes, sizeof(nbody::NodeRecT<F>));
+        if (!rc) rc = grow_dev(h, d_order, order_cap, n_order, sizeof(int));
+        if (rc) return rc;
+        HIP_TRY(h, hipMemcpyAsync(d_nodes, tree.nodes, tree.n_nodes * sizeof(nbody::NodeRecT<F>), hipMemcpyHostToDevice, h->stream));
+        if (n_order) HIP_TRY(h, hipMemcpyAsync(d_order, order, n_order * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (n_seg > 1) HIP_TRY(h, hipStreamSynchronize(h->stream));   // own_order is pageable and reused
+        h->stats.tree_copy_ms += copy_ms + ms_since(t2);
+        return NBODY_OK;
+    }
+};

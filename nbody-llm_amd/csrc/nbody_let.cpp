@@ -67,7 +67,7 @@ struct State {
     void* d_layout = nullptr;
     int* d_zero = nullptr;        // [1] = 0: the slice is emitted with local indices
     size_t staged = 0;            // emulation: records in the staging buffer so far
-    int* d_seg_first = nullptr;   // [kWalkMaxSplit + 1] first node of every walk segment | [kWalkMaxSplit] ancestor counts | [kWalkMaxSplit][192] ancestors
+    int* d_seg_first = nullptr;   // [kMaxSplit + 1] first node of every walk segment | [kMaxSplit] ancestor counts | [kMaxSplit][kMaxAnc] ancestors
     float4* d_walk_planes = nullptr;   // [segments][stride] the segments' partial accelerations
     size_t walk_planes_cap = 0;
     uint64_t send_regrown = 0;    // times the export buffer had to grow (and the lists were written again)
@@ -111,21 +111,6 @@ struct State {
 namespace {
 
 constexpr long long kNoClamp = 0x7fffffffLL;   // the lists travel whole (exchange_layout's clamp)
-constexpr int kWalkMaxSplit = 64;              // node-range segments of the walk (kernels_bh.hip WalkSplit), at most
-
-int fail(NbodyHandle* h, int code, const std::string& msg) { h->err = msg; return code; }
-
-#define HIP_TRY(h, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess)                                                                         \
-            return fail(h, NBODY_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
-    } while (0)
-#define TP_TRY(h, expr)                                                                               \
-    do {                                                                                              \
-        int r_ = (expr);                                                                              \
-        if (r_ != NBODY_OK) return fail(h, r_, std::string(#expr) + ": " + (h)->tp->error());         \
-    } while (0)
 
 // phase timing: an event at both ends of a phase, on the handle's stream; account() adds the five durations up
 struct PhaseTimer {
@@ -345,7 +330,7 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick) {
     // the walk's shape for this many bodies (kernels.h walk_plan): bodies per lane inside launch_bh_walk, node-range segments here
     // -- a rank with 10^5-10^6 bodies is a few thousand waves at one segment, not enough to fill the chip
     const bool fast = h->cfg.math_mode != NBODY_MATH_STRICT;
-    int K = h->n_local > 0 ? walk_plan(h->n_local, fast, kWalkMaxSplit, h->theta2).segments : 1;
+    int K = h->n_local > 0 ? walk_plan(h->n_local, fast, kMaxSplit, h->theta2).segments : 1;
     while (K > 1 && size_t(K) * 16 > h->n_local) K /= 2;   // (a tree has at least as many nodes as bodies; tiny ranks walk in one piece)
     // the nodes this rank holds, in global-index order, links = positions; first[] of the unsplit walk = {0, nodes held}
     {
@@ -373,10 +358,10 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick) {
         }
         // the segments start at global node indices total k / K (launch_assemble found where those fall in the held array); their
         // ancestors come from the held array itself (the local build's arrays know the slice only)
-        launch_walk_split_scan(h->stream, s.d_held, s.d_split, K, s.d_seg_first, s.d_seg_first + kWalkMaxSplit + 1, s.d_seg_first + 2 * kWalkMaxSplit + 1, 1);
+        launch_walk_split_scan(h->stream, s.d_held, s.d_split, K, s.d_seg_first, s.d_seg_first + kMaxSplit + 1, s.d_seg_first + 2 * kMaxSplit + 1, 1);
         td.split_first = s.d_seg_first;
-        td.split_n_anc = s.d_seg_first + kWalkMaxSplit + 1;
-        td.split_anc = s.d_seg_first + 2 * kWalkMaxSplit + 1;
+        td.split_n_anc = s.d_seg_first + kMaxSplit + 1;
+        td.split_anc = s.d_seg_first + 2 * kMaxSplit + 1;
         td.split_planes = s.d_walk_planes;
         td.split_stride = stride;
     } else {
@@ -442,7 +427,7 @@ int create(NbodyHandle* h) {
     if ((rc = dev_alloc(h, &s.d_pred, size_t(s.G) * s.G))) return rc;
     if ((rc = dev_alloc(h, &s.d_top_nodes, size_t(s.G) * kLevels * 2))) return rc;
     if ((rc = dev_alloc(h, &s.d_list_first, size_t(s.G) + 1))) return rc;
-    if ((rc = dev_alloc(h, &s.d_seg_first, size_t(2 * kWalkMaxSplit + 1 + kWalkMaxSplit * 192)))) return rc;
+    if ((rc = dev_alloc(h, &s.d_seg_first, kSplitInts))) return rc;
     if ((rc = dev_alloc(h, &s.d_in_n, size_t(s.G)))) return rc;
     if ((rc = dev_alloc(h, &s.d_zero, 1))) return rc;
     if ((rc = dev_alloc(h, reinterpret_cast<char**>(&s.d_layout), layout_bytes()))) return rc;

@@ -91,6 +91,12 @@ def test_statistics_and_profiling(gpu):
         assert sim.stats().force_kernel_interactions == 2 * n * (n - 1)
         sim.reset_stats()
         assert sim.stats().steps == 0
+    # f64 handles keep the same contract: set_profiling(k > 1) brackets every k-th force launch only
+    with nb.Simulation(nb.plummer(n, f64=True), *BOX, method=nb.BARNES_HUT, math_mode=nb.FAST) as sim:
+        sim.set_profiling(2)
+        sim.steps(4)
+        s = sim.stats()
+        assert (s.steps, s.force_launches) == (4, 2) and s.force_kernel_ms > 0
 
 
 def test_many_handles_share_a_device(gpu, orc):
