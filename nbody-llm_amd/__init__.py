@@ -351,6 +351,11 @@ class Simulation:
     def update_forces(self):
         self._check(lib.nbody_update_forces(self._h))
 
+    def upload(self, points: np.ndarray):
+        """Replace the bodies (nbody_upload: at most the capacity; a rank of a sharded world keeps its index block)."""
+        points = np.ascontiguousarray(points, dtype=self.dtype)
+        self._check(lib.nbody_upload(self._h, points.ctypes.data, points.shape[0], self.dtype.itemsize))
+
     def add_point(self, particle: np.ndarray):
         p = np.ascontiguousarray(particle, dtype=self.dtype).reshape(1)
         self._check(lib.nbody_add_point(self._h, p.ctypes.data))

@@ -190,8 +190,10 @@ def test_clone_is_independent(gpu, orc):
 
 @pytest.mark.parametrize("n,eps", [(1024, 0.0), (3000, 0.0), (4097, 1e-2), (20000, 1e-2)])
 def test_fast_accelerations_within_tolerance(gpu, orc, n, eps):
-    """fast kernel (v_rsq_f32 + FMA + wave-split partner range) vs the f32 oracle: <= 1e-5 of the
-    largest acceleration; the f64 oracle on the same inputs bounds what f32 itself can do."""
+    """fast math vs the f32 oracle: <= 1e-5 of the largest acceleration, <= 1e-4 per body.  Every size here is at
+    least sym_min_bodies (1024), so update_forces runs the symmetric kernel k_bf_sym (4 bodies per lane up to 10 240
+    bodies, else 8); the LDS-tiled one-sided k_bf_fast runs below 1024.  A full sum cannot see one wrong pair at
+    20 000 bodies: tests/test_bf_pair_coverage_gpu.py checks every kernel pair by pair."""
     nb = gpu
     sd, st = settings(nb, g_soft=eps)
     ics = nb.plummer(n, seed=n)
@@ -211,8 +213,9 @@ def test_fast_accelerations_within_tolerance(gpu, orc, n, eps):
 @pytest.mark.parametrize("n,eps", [(8192, 0.0), (8193, 0.0), (8704, 1e-2), (9000, 0.0), (12345, 1e-2), (16384, 0.0),
                                    (33000, 1e-2)])
 def test_fast_symmetric_kernel_sizes(gpu, orc, n, eps):
-    """n >= 8192 takes the symmetric kernel (kernels_bf_sym.hip): odd and even numbers of resident
-    sets (8193 -> 17 sets, 9000 -> 18), partial last set, zero softening (self and padding pairs)."""
+    """The symmetric kernel (kernels_bf_sym.hip, from sym_min_bodies = 1024 bodies up) at mid sizes: resident sets
+    of 256 bodies up to 10 240 bodies (8193 -> 33 sets, 9000 -> 36), of 512 beyond (12345 -> 25, 16384 -> 32, 33000
+    -> 65); partial last set, zero softening (self and padding pairs)."""
     nb = gpu
     sd, st = settings(nb, g_soft=eps, g=1.25)
     ics = nb.plummer(n, seed=n)

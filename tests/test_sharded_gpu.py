@@ -6,6 +6,7 @@ Oracle of the sharded run = the 1-shard run (and the CPU oracle): strict math bi
 import numpy as np
 import pytest
 
+from bf_probe import PROBE_G, check_probe, probe_columns, probe_records, set_probe
 from conftest import Knob, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +118,33 @@ def test_cross_shard_pairs_are_dealt_exactly_once(gpu):
         m = got["mass"].astype(np.float64)[:, None]
         p = (got["acceleration"].astype(np.float64) * m).sum(0)
         assert np.abs(p).max() < 2e-6 * np.abs(got["acceleration"].astype(np.float64) * m).sum(), G
+        for s in sims:
+            s.close()
+
+
+def test_cross_shard_pairs_are_dealt_exactly_once_probed(gpu):
+    """Worlds of the same sizes as above, pair by pair: momentum conservation cannot see a block of pairs dropped or dealt to
+    both GPUs (each is applied to both bodies).  In a probe world only body k has mass, so every body receives exactly
+    the one term of its pair with k (tests/bf_probe.py); k runs over the ends of every shard block, the first body the
+    higher of two opposite ranks keeps resident, the resident-set boundaries of 512 bodies and a few seeded bodies."""
+    nb = gpu
+    eps = 1e-2
+    for G in (2, 3, 4, 5, 8):
+        n = 4096 * G + 777
+        pos = nb.plummer(n + 256, seed=G)["position"]
+        pos = np.ascontiguousarray(pos[np.abs(pos).max(1) < 30.0][:n])   # (all inside the box: none leaves)
+        assert len(pos) == n
+        rec = probe_records(nb.PARTICLE_DTYPE, pos)
+        sims = make_world(nb, rec, G, BOX, nb.Settings(g=PROBE_G, g_soft=eps), nb.BRUTE_FORCE, nb.FAST)
+        chunks_cap = ((n + G - 1) // G + 63) // 64
+        split = ((chunks_cap + 7) // 8 + 1) // 2 * 8 * 64    # make_cross_plan's opposite-rank cut, in bodies
+        cols = probe_columns(n, blocks=[nb.shard_range(n, r, G) for r in range(G)], set_sizes=(512,), offsets=(split,),
+                             n_random=4, every_below=0)
+        for k in cols:
+            for s in sims:
+                s.upload(set_probe(rec, k))
+            nb.sharded_step(sims)
+            check_probe(gather(sims)["acceleration"], pos, k, PROBE_G, eps, what=f"G={G}")
         for s in sims:
             s.close()
 
