@@ -437,6 +437,91 @@ size_t bh_step_by(Body<F>* p, size_t n, const Settings<F>& s, const Box3<F>& box
     return n;
 }
 
+// ---------------------------------------------------------------- reference walk over a node list (checker, not the reference)
+// The fast walks' decisions over a linearised tree as nbody_tree_export[_f64] returns it ({com, mass}, width, skip in
+// pre-order), made in the walk's precision F with the kernels' own expressions (nbody-llm_amd/csrc/kernels_bh.hip,
+// k_bh_walk / walk_entry; kernels_f64.hip, k_bh_walk_fast64): r2 = (rx*rx + ry*ry) + rz*rz, accepted when
+// w2 < theta2 * r2 with w2 = width * width; DIRECT skips a node with r2 < 1e-10 whole and evaluates a leaf (skip == i + 1)
+// that fails the test.  The accepted terms g m r / (r2 + eps2)^(3/2) are summed in A (double for the f32 walk, long double
+// for the f64 walk) from the F inputs, so S holds no rounding of the walk's own; T = sum of |term| is the scale an
+// accumulation error is relative to.  Nothing else in this file uses it.
+template <class F, class A>
+struct ListWalk {
+    const F* com_mass;   // [n_nodes][4]
+    const F* width;      // [n_nodes]
+    const int32_t* skip; // [n_nodes]
+    long n_nodes;
+    F theta2, g, eps2;
+    bool direct;
+
+    // one body: S[3], T, counts; `list` (may be null) receives the accepted node indices
+    void walk(const F p[3], double S[3], double* T, uint64_t* n_acc, uint64_t* n_vis, std::vector<int32_t>* list) const {
+        A sx = 0, sy = 0, sz = 0, st = 0;
+        uint64_t na = 0, nv = 0;
+        long i = 0;
+        while (i < n_nodes) {
+            const F* a = com_mass + 4 * i;
+            const F rx = a[0] - p[0], ry = a[1] - p[1], rz = a[2] - p[2];
+            const F r2 = (rx * rx + ry * ry) + rz * rz;
+            const F w = width[i];
+            const F w2 = w * w;
+            const long sk = skip[i];
+            ++nv;
+            bool take;
+            if (direct) {
+                if (r2 < F(1e-10)) { i = sk; continue; }
+                take = w2 < theta2 * r2 || sk == i + 1;
+            } else {
+                take = w2 < theta2 * r2;
+            }
+            if (!take) { i = i + 1; continue; }
+            const A dx = A(a[0]) - A(p[0]), dy = A(a[1]) - A(p[1]), dz = A(a[2]) - A(p[2]);
+            const A d2 = (dx * dx + dy * dy) + dz * dz + A(eps2);
+            const A k = A(g) * A(a[3]) / (d2 * std::sqrt(d2));
+            const A tx = dx * k, ty = dy * k, tz = dz * k;
+            sx += tx; sy += ty; sz += tz;
+            st += std::sqrt(tx * tx + ty * ty + tz * tz);
+            ++na;
+            if (list) list->push_back(int32_t(i));
+            i = sk;
+        }
+        S[0] = double(sx); S[1] = double(sy); S[2] = double(sz);
+        *T = double(st);
+        *n_acc = na;
+        *n_vis = nv;
+    }
+};
+
+// pos: [n][3] walk positions.  S: [n][3], T, acc, vis: [n] per body.  list_body >= 0: that body's accepted nodes go to
+// list[0 .. min(count, list_cap)); returns the count (0 when list_body < 0)
+template <class F, class A>
+long bh_walk_list(const F* com_mass, const F* width, const int32_t* skip, size_t n_nodes, const F* pos, size_t n,
+                  F theta2, int leaf_mode, F g, F g_soft, int threads, double* S, double* T, uint64_t* acc, uint64_t* vis,
+                  long list_body, int32_t* list, size_t list_cap) {
+    const ListWalk<F, A> w{com_mass, width, skip, long(n_nodes), theta2, g, F(g_soft * g_soft), leaf_mode == 1};
+    auto work = [&](size_t k0, size_t k1) {
+        for (size_t k = k0; k < k1; ++k) w.walk(pos + 3 * k, S + 3 * k, T + k, acc + k, vis + k, nullptr);
+    };
+    const int T_ = std::max(1, std::min(16, threads));
+    if (T_ <= 1 || n < 256) work(0, n);
+    else {
+        std::vector<std::thread> pool;
+        size_t chunk = (n + T_ - 1) / T_;
+        for (int t = 0; t < T_; ++t) {
+            size_t k0 = std::min(n, t * chunk), k1 = std::min(n, k0 + chunk);
+            if (k0 < k1) pool.emplace_back(work, k0, k1);
+        }
+        for (auto& th : pool) th.join();
+    }
+    if (list_body < 0 || size_t(list_body) >= n) return 0;
+    std::vector<int32_t> l;
+    double s3[3], t1;
+    uint64_t a1, v1;
+    w.walk(pos + 3 * list_body, s3, &t1, &a1, &v1, &l);
+    if (list) std::memcpy(list, l.data(), std::min(l.size(), list_cap) * sizeof(int32_t));
+    return long(l.size());
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ C entry points
@@ -530,5 +615,17 @@ size_t bh_step_by(Body<F>* p, size_t n, const Settings<F>& s, const Box3<F>& box
 
 ORACLE_API(float, f32)
 ORACLE_API(double, f64)
+
+// the reference walk over an exported node list (bh_walk_list above); s = {theta2, g, g_soft}
+#define ORACLE_WALK_LIST(F, A, SFX)                                                                             \
+    extern "C" long oracle_bh_walk_list_##SFX(const F* com_mass, const F* width, const int32_t* skip,           \
+                                              size_t n_nodes, const F* pos, size_t n, const F s[3],             \
+                                              int leaf_mode, int threads, double* S, double* T, uint64_t* acc,  \
+                                              uint64_t* vis, long list_body, int32_t* list, size_t list_cap) {  \
+        return bh_walk_list<F, A>(com_mass, width, skip, n_nodes, pos, n, s[0], leaf_mode, s[1], s[2],         \
+                                  threads, S, T, acc, vis, list_body, list, list_cap);                          \
+    }
+ORACLE_WALK_LIST(float, double, f32)
+ORACLE_WALK_LIST(double, long double, f64)
 
 extern "C" int oracle_hardware_threads() { return int(std::thread::hardware_concurrency()); }

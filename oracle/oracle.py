@@ -193,6 +193,40 @@ def bh_tree_cells(a, center, width) -> np.ndarray:
     return out
 
 
+def bh_walk_list(tree, pos, theta2, g, g_soft, leaf_mode=0, threads=16, list_body=-1) -> dict:
+    """The fast walks' decisions over an exported node list (`tree`: com_mass [m, 4], width [m], skip [m], as
+    Simulation.tree() or bh_build_tree return them; its float type is the walk's precision), with the accepted terms
+    summed in high precision.  `pos` [n, 3] are the walk positions.  Returns S [n, 3] (f64), T [n] (sum of |term|),
+    accepted [n] and visited [n] (uint64) per body, and `list`: body `list_body`'s accepted node indices in visit order."""
+    com = np.ascontiguousarray(tree["com_mass"])
+    ft = com.dtype.type
+    if ft not in (np.float32, np.float64):
+        raise TypeError(f"tree of {com.dtype}")
+    sfx, ct = ("f32", C.c_float) if ft is np.float32 else ("f64", C.c_double)
+    width = np.ascontiguousarray(tree["width"], ft)
+    skip = np.ascontiguousarray(tree["skip"], np.int32)
+    p = np.ascontiguousarray(np.asarray(pos).reshape(-1, 3), ft)
+    m, n = len(width), len(p)
+    S = np.zeros((n, 3), np.float64)
+    T = np.zeros(n, np.float64)
+    acc = np.zeros(n, np.uint64)
+    vis = np.zeros(n, np.uint64)
+    fn = getattr(lib(), f"oracle_bh_walk_list_{sfx}")
+    fn.restype = C.c_long
+    ptr = lambda x: C.c_void_p(x.ctypes.data)   # noqa: E731
+    args = [ptr(com), ptr(width), ptr(skip), C.c_size_t(m), ptr(p), C.c_size_t(n), _arr(ct, [theta2, g, g_soft]),
+            C.c_int(leaf_mode), C.c_int(max(1, min(16, int(threads)))), ptr(S), ptr(T), ptr(acc), ptr(vis)]
+    lst = np.zeros(0, np.int32)
+    if 0 <= list_body < n:   # the body's list alone first (its length), then the whole walk with the list
+        one = np.ascontiguousarray(p[list_body:list_body + 1])
+        s1, t1, a1, v1 = np.zeros(3), np.zeros(1), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+        k = fn(*args[:4], ptr(one), C.c_size_t(1), *args[6:9], ptr(s1), ptr(t1), ptr(a1), ptr(v1),
+               C.c_long(0), None, C.c_size_t(0))
+        lst = np.zeros(k, np.int32)
+    fn(*args, C.c_long(list_body if len(lst) else -1), ptr(lst) if len(lst) else None, C.c_size_t(len(lst)))
+    return dict(S=S, T=T, accepted=acc, visited=vis, list=lst)
+
+
 def energy(a, g=1.0, g_soft=0.0, threads=0):
     """f64 (KE, PE) of a state."""
     s, _, _ = _sfx(a)

@@ -19,7 +19,10 @@ Measured (round 3, Plummer seed 20250523, theta = 0.5, g_soft = 0.01; median / 9
   2^20    host   REFERENCE 5.9e-7 / 4.4e-6 / 3.7e-5, 109     DIRECT 7.7e-8 / 6.5e-7 / 4.0e-6,   0
   2^20    device REFERENCE 6.2e-7 / 4.7e-6 / 4.9e-4, 217     DIRECT 2.5e-7 / 1.6e-6 / 4.8e-4, 120     (accepted nodes: -46 of 2.1e9)
 At 2^20 with the device tree one flipped test near the core moves a body by 2e-4 of the FIELD's largest acceleration: "<= 1e-5 of
-max|a|" holds for the host tree at every size and for the device tree at 65 536, not for the device tree at 2^20."""
+max|a|" holds for the host tree at every size and for the device tree at 65 536, not for the device tree at 2^20.
+SURVEY section 8(d)'s criterion, relative L2 over the field ||a - a_oracle||_2 / ||a_oracle||_2 <= 1e-5, holds in every case and is
+asserted; measured on an MI355X (same seed, theta2 = 0.25): 1.4e-7 to 8.7e-7 on the host tree, 1.5e-7 to 7.4e-7 on the device tree at
+65 536 bodies and 1.0e-6 (REFERENCE) / 1.3e-6 (DIRECT) on the device tree at 2^20."""
 import numpy as np
 import pytest
 
@@ -56,11 +59,13 @@ def test_fast_walk_error_relative_to_each_bodys_own_acceleration(gpu, orc, n, le
     med, p999, worst = float(np.median(err)), float(np.quantile(err, 0.999)), float(err.max())
     beyond5, beyond3 = int(np.count_nonzero(err > 1e-5)), int(np.count_nonzero(err > 1e-3))
     field = float(np.abs(got - ref).max() / np.abs(ref).max())
+    l2 = float(np.linalg.norm(got - ref) / np.linalg.norm(ref))
     print(f"\nbh fast parity n={n} tree={tree} leaf={leaf}: per-body |da|/|a| median {med:.2e} p99.9 {p999:.2e} max {worst:.2e}; "
-          f"bodies beyond 1e-5: {beyond5}, beyond 1e-3: {beyond3}; max|da|/max|a| {field:.2e}; "
+          f"bodies beyond 1e-5: {beyond5}, beyond 1e-3: {beyond3}; max|da|/max|a| {field:.2e}; L2 {l2:.2e}; "
           f"accepted {s.interactions} (oracle {acc_n}), visited {s.node_visits} (oracle {vis_n})")
     assert own.min() > 0
     assert med < 1e-6 and p999 < 2e-5 and beyond3 == 0
+    assert l2 <= 1e-5
     if tree == "host":   # the oracle's tree bit for bit: the same opening tests, rounding only
         assert (s.interactions, s.node_visits) == (acc_n, vis_n)
         assert worst < 1e-4 and field < 1e-5
