@@ -74,7 +74,9 @@ enum {
 
 /* the reference's `F: Float` (src/shared.rs:12-44) */
 enum { NBODY_F32 = 0,  /* PointParticle<f32,3>: every path of this library */
-       NBODY_F64 = 1 }; /* PointParticle<f64,3> (80-byte records).  Brute force: the strict kernel.  Barnes-Hut, NBODY_MATH_STRICT: the
+       NBODY_F64 = 1 }; /* PointParticle<f64,3> (80-byte records).  Brute force: NBODY_MATH_STRICT the reference's loop (bit-exact),
+                          NBODY_MATH_FAST every unordered pair once (rsqrt + FMA, planes added in a fixed order: each body
+                          within 1e-14 of the sum of its terms' magnitudes).  Barnes-Hut, NBODY_MATH_STRICT: the
                           reference's nested sums on the host-built tree (NBODY_TREE_HOST, also what AUTO means then): positions,
                           velocities, accelerations and node counts bit-equal to the reference's rounding sequence in f64 (oracle/:
                           the same templated restatement); with NBODY_TREE_DEVICE the tree is built on the device (same cells, centres
@@ -129,6 +131,9 @@ void nbody_destroy(NbodyHandle* h);
 /* `Clone` supertrait (shared.rs:80; BH clone drops the tree, barnes_hut.rs:113-135; the visualiser's reset depends on it,
  * vis.rs:217-220).  Any handle; the clone of a sharded handle has no communicator: call nbody_comm_init on it. */
 int nbody_clone(const NbodyHandle* h, NbodyHandle** out);
+/* The configuration the handle runs with: tree_build after NBODY_TREE_AUTO and the spatial shards' override, math_mode as it
+ * runs, the rest as created (struct_size = sizeof(NbodyConfig)). */
+int nbody_get_config(const NbodyHandle* h, NbodyConfig* out);
 
 /* ---- state in / out ------------------------------------------------------------------------ */
 /* Replaces the body vector (the `points: Vec<P>` argument of Simulation::new).  In a sharded run
@@ -202,7 +207,7 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */
 /* Per handle; the library exports no mutable globals.  Names (csrc/kernels.h struct Tuning): cross_sym, sym_packed,
  * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
- * bh_reduce_split, tree_max_tie; the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

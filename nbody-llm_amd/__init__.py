@@ -73,6 +73,7 @@ DECLARED_SYMBOLS = [
     "nbody_debug_let_bounds", "nbody_debug_let_set_balance",
     "nbody_comm_local_id", "nbody_comm_transport", "nbody_host_exchange_layout",
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
+    "nbody_get_config",
 ]
 
 
@@ -173,6 +174,7 @@ _sig("nbody_host_launch_plan", _i, _sz, _f, _i, C.POINTER(_i))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
+_sig("nbody_get_config", _i, _H, C.POINTER(NbodyConfig))
 _sig("nbody_abi_version", _i)
 _sig("nbody_device_count", _i)
 
@@ -411,6 +413,13 @@ class Simulation:
             self._check(lib.nbody_set_bounds_f64(self._h, (C.c_double * 3)(*[float(x) for x in center]), float(width)))
         else:
             self._check(lib.nbody_set_bounds(self._h, (C.c_float * 3)(*[float(x) for x in center]), float(width)))
+
+    @property
+    def config(self) -> dict:
+        """The configuration the handle runs with (nbody_get_config): tree_build after TREE_AUTO, math_mode as it runs."""
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        return {name: getattr(cfg, name) for name, _ in NbodyConfig._fields_}
 
     def clone(self) -> "Simulation":
         h = _H()

@@ -31,6 +31,11 @@ struct Tuning {
     int bh_walk_order = 1;      // 1: a group's segments are dispatched nearest-first (heaviest first), 0: in index order
     int bh_reduce_split = 1;    // 1: four waves per 64 bodies in the walk's plane reduction when there are >= 8 segments
     int tree_max_tie = 64;      // device build: largest run of equal 63-bit keys that gets second keys (beyond: "too deep")
+    int bf64_min_bodies = 10240; // f64 fast brute force, own block: from this many bodies k_bf64_sym + the left-over pairs, below it k_bf64_os alone
+                                // (steps/s one-sided against symmetric: 8 192 bodies 13 340 / 12 580, 12 288: 5 250 / 6 760; profiles/bf64_bench_strict_vs_fast.jsonl)
+    int bf64_ipt = 0;           // k_bf64_sym: bodies per lane of a resident set: 0 from the block's size (kernels_f64.h), 4, 8
+    int bf64_rot = 0;           // k_bf64_sym: 0 = the chunk's positions in LDS, only the accumulators rotate; 1 = positions rotate too
+    int bf64_waves = 0;         // f64 fast brute force: waves a launch's slices are sized for; 0 = 2048
     // the following select code that only the tuning build carries (make -C csrc tuning: -DNBODY_TUNING); the release
     // library refuses any value but the default
     int bh_walk_variant = 0;    // 1 wave-cooperative, 2 two lanes per body, 3 hot records in LDS, 4 cooperative window, 5 cooperative block walk  [NBODY_BH_VARIANT]

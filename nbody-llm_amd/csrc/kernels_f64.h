@@ -67,4 +67,25 @@ void launch_bh_walk_fast(hipStream_t s, const Dev& d, const Node64* nodes, int n
                          const double* kick_dt = nullptr /* fuse integrate_after_force into the plane reduction */, int* kicked = nullptr);
 void launch_energy(hipStream_t s, const Dev& d, int n_upper, double eps2, double* out2);
 
+// fast brute force (NBODY_MATH_FAST on an f64 handle, kernels_bf64.hip).  Planes of double4[n_pad]: [0, sym_sets) the
+// travelling-side sums of set distance d, [sym_sets, sym_sets + K) the resident-side sums of slice k, then k_own slices of
+// the one-sided own-block pairs, then k_remote slices of the other blocks' bodies; every row is written once a pass.
+constexpr int kBf64SmallIptBelow = 16384;   // up to this many bodies k_bf64_sym keeps 4 bodies per lane, beyond it 8
+struct Bf64Plan {
+    bool sym = false;       // k_bf64_sym + the left-over pairs (else k_bf64_os over every own pair)
+    int ipt = 0, rot = 0;   // bodies per lane of a resident set; rotation scheme (Tuning::bf64_rot)
+    int A = 0, sym_sets = 0, K = 0;
+    int groups = 0;         // 64-body groups of the padded own block
+    int k_own = 0, k_remote = 0;
+    int n_planes = 0;
+    size_t n_pad = 0;
+};
+Bf64Plan make_bf64_plan(int n_upper, int n_remote_upper, int n_seg);
+uint64_t bf64_sym_pairs(const Bf64Plan& p, size_t n);   // unordered pairs of real bodies k_bf64_sym evaluates
+void launch_bf64_sym(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2);
+void launch_bf64_own(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2);      // left-over (or all) own pairs
+void launch_bf64_remote(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2);   // the other blocks' bodies
+void launch_bf64_reduce(hipStream_t s, const Dev& d, const Bf64Plan& p, const double4* planes, int n_upper, double g,
+                        const double* kick_dt /* != nullptr: integrate_after_force rides along */);
+
 }  // namespace nbody64

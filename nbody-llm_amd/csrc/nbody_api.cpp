@@ -828,10 +828,10 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
     if (h->cfg.tree_build == NBODY_TREE_AUTO)   // the bit-exact path keeps the reference's (host) build
         h->cfg.tree_build = cfg->math_mode == NBODY_MATH_FAST ? NBODY_TREE_DEVICE : NBODY_TREE_HOST;
     if (h->cfg.dtype == NBODY_F64) {
-        // F = f64: brute force always runs the strict kernel; Barnes-Hut strict = the reference's nested sums on the host-built
-        // tree (bit-exact) unless the device build is asked for, fast = one running sum per lane over a split node range, on
-        // the device-built tree unless the host build is asked for (AUTO: as for f32)
-        if (cfg->method == NBODY_BRUTE_FORCE) h->cfg.math_mode = NBODY_MATH_STRICT;
+        // F = f64: brute force strict = the reference's loop (k_bf_strict, bit-exact), fast = every unordered pair once
+        // (kernels_bf64.hip); Barnes-Hut strict = the reference's nested sums on the host-built tree (bit-exact) unless the
+        // device build is asked for, fast = one running sum per lane over a split node range, on the device-built tree
+        // unless the host build is asked for (AUTO: as for f32)
         if (cfg->tree_build == NBODY_TREE_AUTO) h->cfg.tree_build = h->cfg.math_mode == NBODY_MATH_FAST ? NBODY_TREE_DEVICE : NBODY_TREE_HOST;
         if (cfg->world_size > 1 && h->cfg.math_mode != NBODY_MATH_FAST) h->cfg.tree_build = NBODY_TREE_HOST;   // (a sharded f64 world in strict math builds the replicated tree on the host; fast math: on the device, from the gathered positions)
     }
@@ -1571,6 +1571,8 @@ const Knob kKnobs[] = {
     {"cross_wpb", &nbody::Tuning::cross_wpb, false}, {"bh_walk_split", &nbody::Tuning::bh_walk_split, false},
     {"bh_walk_order", &nbody::Tuning::bh_walk_order, false}, {"bh_reduce_split", &nbody::Tuning::bh_reduce_split, false},
     {"tree_max_tie", &nbody::Tuning::tree_max_tie, false},
+    {"bf64_min_bodies", &nbody::Tuning::bf64_min_bodies, false}, {"bf64_ipt", &nbody::Tuning::bf64_ipt, false},
+    {"bf64_rot", &nbody::Tuning::bf64_rot, false}, {"bf64_waves", &nbody::Tuning::bf64_waves, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},
@@ -1598,6 +1600,12 @@ int nbody_get_tuning(const NbodyHandle* h, const char* name, int* value) {
     for (const Knob& k : kKnobs)
         if (std::strcmp(k.name, name) == 0) { *value = h->tune.*(k.field); return NBODY_OK; }
     return NBODY_ERR_INVALID;
+}
+
+int nbody_get_config(const NbodyHandle* h, NbodyConfig* out) {
+    if (!h || !out) return NBODY_ERR_INVALID;
+    *out = h->cfg;   // (as created, with tree_build and math_mode resolved at nbody_create)
+    return NBODY_OK;
 }
 
 int nbody_is_tuning_build(void) {

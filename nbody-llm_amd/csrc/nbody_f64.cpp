@@ -4,7 +4,8 @@
 // equal the oracle's f64 instantiation bit for bit -- on one shard and over index-block shards alike (the blocks'
 // positions and live counts are exchanged once per step through the handle's transport; partners and tree bodies keep
 // their global order).  NBODY_MATH_FAST: the fast walk (one running sum per lane, split node range), device build on one
-// shard.  Bodies cross the boundary as 80-byte records.
+// shard; brute force every unordered pair once (kernels_bf64.hip), the other blocks' bodies one-sided.  Bodies cross the
+// boundary as 80-byte records.
 #include "nbody_f64.h"
 #include "kernels_f64.h"
 
@@ -51,6 +52,13 @@ struct State {
     bool tree_on_device = false;  // where the last tree lives (nbody_tree_export)
     size_t dev_nodes = 0;
     WalkSplitBuf<double4> split;  // fast walk (NBODY_MATH_FAST): the node-range split
+    // fast brute force (NBODY_MATH_FAST): kernels_bf64.hip's plan, re-made when the body counts or the knobs change, and
+    // its partial-sum planes (grow only)
+    Bf64Plan bf_plan;
+    long long bf_plan_key[6] = {-1, -1, -1, -1, -1, -1};
+    uint64_t bf_sym_pairs = 0;
+    double4* d_planes = nullptr;
+    size_t planes_cap = 0;        // double4 entries
 };
 
 namespace {
@@ -84,8 +92,61 @@ int push_count(NbodyHandle* h, State& s) {
     return NBODY_OK;
 }
 
+int ensure_bf_plan(NbodyHandle* h, State& s, size_t n_remote) {
+    const nbody::Tuning& t = nbody::tuning();
+    const long long key[6] = {(long long)s.n_local, (long long)n_remote, t.bf64_min_bodies, t.bf64_ipt, t.bf64_rot, t.bf64_waves};
+    if (std::equal(key, key + 6, s.bf_plan_key)) return NBODY_OK;
+    const Bf64Plan plan = make_bf64_plan(int(s.n_local), int(std::min<size_t>(n_remote, 0x7fffffff)), s.d.n_seg);
+    const size_t need = size_t(plan.n_planes) * plan.n_pad;
+    if (need > s.planes_cap) {
+        if (s.d_planes) (void)hipFree(s.d_planes);
+        s.d_planes = nullptr; s.planes_cap = 0;
+        std::fill(s.bf_plan_key, s.bf_plan_key + 6, -1LL);   // (a failed allocation leaves no plan behind: the next pass tries again)
+        HIP_TRY(h, hipMalloc(&s.d_planes, need * sizeof(double4)));
+        s.planes_cap = need;
+    }
+    s.bf_plan = plan;
+    s.bf_sym_pairs = bf64_sym_pairs(plan, s.n_local);
+    std::copy(key, key + 6, s.bf_plan_key);   // only once the planes exist for this plan
+    return NBODY_OK;
+}
+
+// NBODY_MATH_FAST: every own pair once (k_bf64_sym + the left-over pairs one-sided) or, below Tuning::bf64_min_bodies,
+// every own pair one-sided; the other blocks' bodies one-sided from the gathered positions; then the planes in a fixed
+// order, with the step's kick when there is one.  Enqueues only (no host synchronisation unless the planes grow).
+int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
+    if (s.n_local == 0) return NBODY_OK;
+    uint64_t tot = 0;
+    for (int c : s.count_upper) tot += uint64_t(c);
+    const size_t n_remote = size_t(tot) - std::min<size_t>(size_t(tot), size_t(s.count_upper[size_t(s.d.my_seg)]));
+    int rc = ensure_bf_plan(h, s, n_remote);
+    if (rc) return rc;
+    const Bf64Plan& p = s.bf_plan;
+    uint64_t timed = 0;   // directed interactions of the launch the HIP events bracket (the dominant one)
+    if (p.sym && p.sym_sets > 0) {
+        {
+            ForceTimer t(h);
+            launch_bf64_sym(h->stream, s.d, p, s.d_planes, eps2);
+        }
+        timed = 2 * s.bf_sym_pairs;
+        launch_bf64_own(h->stream, s.d, p, s.d_planes, eps2);
+    } else {   // (with one or two resident sets the left-over pairs are all of them)
+        ForceTimer t(h);
+        launch_bf64_own(h->stream, s.d, p, s.d_planes, eps2);
+        timed = uint64_t(s.n_local) * uint64_t(s.n_local - 1);
+    }
+    const bool timed_this = h->timed_this;
+    launch_bf64_remote(h->stream, s.d, p, s.d_planes, eps2);
+    launch_bf64_reduce(h->stream, s.d, p, s.d_planes, int(s.n_local), s.g, s.kick_dt);
+    if (s.kick_dt) s.kicked = 1;
+    HIP_TRY(h, hipGetLastError());
+    if (timed_this) h->stats.force_kernel_interactions += timed;
+    return NBODY_OK;
+}
+
 int bf_forces(NbodyHandle* h, State& s) {
     const double eps2 = s.g_soft * s.g_soft;  // brute_force.rs:69
+    if (h->cfg.math_mode == NBODY_MATH_FAST) return bf_forces_fast(h, s, eps2);
     {
         ForceTimer t(h);
         launch_bf_strict(h->stream, s.d, int(s.n_local), s.g, eps2);
@@ -334,7 +395,7 @@ void destroy(NbodyHandle* h) {
     if (!s) return;
     s->tree.clear();
     void* dev[] = {s->d.pos_all, s->d.vel, s->d.acc, s->d.seg_count, s->d.escaped, s->d.keep, s->d.tile_state, s->d.epoch, s->d.inter,
-                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy};
+                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {s->h_count, s->h_aos, s->h_pos};
     for (void* p : host) if (p) (void)hipHostFree(p);

@@ -10,7 +10,7 @@ RCCL refuses to put two ranks on one device.  With "rccl", rank r uses device r 
 
 cfg (JSON): world, address (socket path), out (directory), transport, device (ipc: the shared device),
   sim {method bf|bh, math fast|strict, shard index|spatial, tree auto|host|device, leaf reference|direct, tuning {knob: value}},
-  ics {kind plummer|disc, n, seed, mass_jitter (seed or null)}, box [[cx, cy, cz], width], settings {g, g_soft, dt, theta2},
+  ics {kind plummer|disc, n, seed, mass_jitter (seed or null), probe (body index or null), probe_mass}, box [[cx, cy, cz], width], settings {g, g_soft, dt, theta2},
   schedule [["steps", k] | ["step_by", dt] | ["update_forces"] | ["settings", {...}] | ["sync"]], env {NAME: value},
   env_by_rank {"r": {NAME: value}}.
 Every rank leaves out/rank<r>.npz (its bodies; spatial shards: + their indices in the uploaded vector) and
@@ -49,6 +49,11 @@ def make_ics(nb, ics: dict) -> np.ndarray:
         pts["mass"] *= np.random.default_rng(int(ics["mass_jitter"])).uniform(0.5, 1.5, len(pts)).astype(pts["mass"].dtype)
     if ics.get("velocity_scale") is not None:
         pts["velocity"] *= pts["velocity"].dtype.type(ics["velocity_scale"])
+    if ics.get("probe") is not None:   # a probe world (tests/bf_probe.py): f32-representable positions, at rest, one body with mass
+        pts["position"] = pts["position"].astype(np.float32)
+        pts["velocity"] = 0.0
+        pts["mass"] = 0.0
+        pts["mass"][int(ics["probe"])] = float(ics.get("probe_mass", 0.75))
     return pts
 
 
