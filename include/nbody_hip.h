@@ -194,6 +194,23 @@ int nbody_reset_stats(NbodyHandle* h);
 /* f64 kinetic and potential energy of this rank's view (world_size == 1: the whole system),
  * evaluated on the device: KE = sum 1/2 m v^2, PE = -g sum_{i<j} m_i m_j / sqrt(r^2 + g_soft^2). */
 int nbody_energy(NbodyHandle* h, double* kinetic, double* potential);
+/* Per-body potentials and the energy of a whole world (SURVEY.md section 8 row d), at the handle's CURRENT positions. */
+enum { NBODY_POTENTIAL_PAIRS = 0,   /* the exact pair sum over every body of the world: differences, terms and sums in f64 on either
+                                       dtype, every unordered pair of a block once; not for NBODY_SHARD_SPATIAL handles */
+       NBODY_POTENTIAL_TREE  = 1 }; /* Barnes-Hut handles: the monopole sum over the tree, O(N log N).  A tree is built first, as
+                                       nbody_update_forces builds it for that handle (after the call nbody_tree_export reports THIS
+                                       tree), and walked with the force walk's opening tests under the NBODY_LEAF_DIRECT rule
+                                       whatever the handle's leaf_mode (a potential without its near field is of no use to anybody);
+                                       terms m / sqrt(r2 + g_soft^2) in the handle's precision, summed in f64 */
+/* phi_i = -g * sum_j m_j / sqrt(|x_j - x_i|^2 + g_soft^2) for this rank's bodies, in nbody_download's order, in f64 on
+ * either dtype.  Collective on a handle of a multi-rank world.  counts (may be NULL) = {terms summed, opening tests} of
+ * this call on this rank (PAIRS: 0, 0).  phi may be NULL to count.  Accelerations, velocities, positions, elapsed and
+ * NbodyStats.steps / interactions / node_visits are not touched: a step taken afterwards gives the bits it would have given
+ * without the call.  NBODY_SHARD_SPATIAL handles: TREE only (PAIRS: NBODY_ERR_INVALID, a rank does not hold the world's bodies); no
+ * body migrates and no ownership bound moves because of the call -- the pass runs on a scratch copy of the rank. */
+int nbody_potentials(NbodyHandle* h, int mode, double* phi, size_t cap, size_t* n_out, uint64_t counts[2]);
+/* KE = sum 1/2 m v^2 and PE = 1/2 sum_i m_i phi_i over ALL ranks (the same two numbers on every rank); collective. */
+int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potential);
 /* Linearised octree of the last Barnes-Hut force pass: per node {com xyz, mass}, width, skip
  * index (first node after the subtree, depth-first pre-order).  Arrays may be NULL to count. */
 int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* skip, size_t cap, size_t* n_nodes);

@@ -55,6 +55,7 @@ PARTICLE_DTYPE64 = np.dtype(
 )
 assert PARTICLE_DTYPE64.itemsize == 80
 F32, F64 = 0, 1
+POTENTIAL_PAIRS, POTENTIAL_TREE = 0, 1   # nbody_potentials / nbody_energy_world: the exact pair sum | the monopole sum over the tree
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
@@ -73,7 +74,7 @@ DECLARED_SYMBOLS = [
     "nbody_debug_let_bounds", "nbody_debug_let_set_balance",
     "nbody_comm_local_id", "nbody_comm_transport", "nbody_host_exchange_layout",
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
-    "nbody_get_config",
+    "nbody_get_config", "nbody_potentials", "nbody_energy_world",
 ]
 
 
@@ -133,6 +134,8 @@ _sig("nbody_set_profiling", _i, _H, _i)
 _sig("nbody_stats", _i, _H, C.POINTER(NbodyStats))
 _sig("nbody_reset_stats", _i, _H)
 _sig("nbody_energy", _i, _H, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("nbody_potentials", _i, _H, _i, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
+_sig("nbody_energy_world", _i, _H, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_tree_export", _i, _H, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_tree_export_cells", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_last_error", C.c_char_p, _H)
@@ -449,6 +452,25 @@ class Simulation:
     def energy(self) -> tuple[float, float]:
         ke, pe = C.c_double(), C.c_double()
         self._check(lib.nbody_energy(self._h, C.byref(ke), C.byref(pe)))
+        return float(ke.value), float(pe.value)
+
+    def potentials(self, mode: int = POTENTIAL_PAIRS) -> tuple[np.ndarray, tuple[int, int]]:
+        """(phi [n] f64 of this rank's bodies in get_points() order, (terms summed, opening tests)) at the current positions;
+        collective on a multi-rank world.  POTENTIAL_TREE: Barnes-Hut handles, O(N log N)."""
+        # (sized from the capacity, not from nbody_count: that call refreshes the host's view of the body count, which a chain
+        # of steps enqueued without read-back sizes its launches from -- nbody_potentials itself leaves the view as it was)
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        n = C.c_size_t(0)
+        phi = np.zeros(max(int(cfg.capacity), 1), np.float64)
+        counts = (C.c_uint64 * 2)()
+        self._check(lib.nbody_potentials(self._h, int(mode), phi.ctypes.data, len(phi), C.byref(n), counts))
+        return phi[: n.value], (int(counts[0]), int(counts[1]))
+
+    def energy_world(self, mode: int = POTENTIAL_PAIRS) -> tuple[float, float]:
+        """(KE, PE) of the whole world, the same on every rank; collective."""
+        ke, pe = C.c_double(), C.c_double()
+        self._check(lib.nbody_energy_world(self._h, int(mode), C.byref(ke), C.byref(pe)))
         return float(ke.value), float(pe.value)
 
     def tree(self):

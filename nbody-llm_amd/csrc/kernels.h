@@ -41,7 +41,7 @@ struct Tuning {
     int bh_walk_variant = 0;    // 1 wave-cooperative, 2 two lanes per body, 3 hot records in LDS, 4 cooperative window, 5 cooperative block walk  [NBODY_BH_VARIANT]
     int bh_walk_lds_block = 1024;  // variant 3: threads per workgroup                                                              [NBODY_BH_LDS_BLOCK]
     int bh_hot_cap = 2048;      // variant 3: node records staged in LDS per workgroup                                              [NBODY_BH_HOT]
-    int bh_walk_debug = 0;      // 1: per-wave start/end stamps (tools/bh_wave_times.py)
+    int bh_walk_debug = 0;      // 1: per-wave start/end stamps (tools/bh_wave_times.py); 2: the potential walk accumulates in f32 (timing experiment)
     int sym_debug = 0;          // 4: in-kernel cycle stamps (tools/sym_cycles.py); 5-7: timing experiments that do not compute the forces
 };
 const Tuning& tuning();                 // of the handle this thread is serving; the defaults outside a call

@@ -18,6 +18,7 @@
 // neighbours and follow nearly the same path: their node reads coalesce into a few 32-byte
 // sectors that stay in L1/L2 (the whole node array is 32 B x n_nodes, ~4 MB at N = 65 536).
 #include "kernels.h"
+#include "kernels_pot.h"
 
 namespace nbody {
 
@@ -1142,6 +1143,95 @@ void launch_bh_walk(hipStream_t s, const Shard& sh, const TreeDev& t, float g, f
                                t.n_order, sh.acc, sh.own_pos(), sh.vel, 0.f, sh.poison, t.n_order_dev, t.store_work);
         }
     }
+}
+
+// ---- nbody_potentials(NBODY_POTENTIAL_TREE): S = sum m / sqrt(r2 + eps2) over the nodes the NBODY_LEAF_DIRECT force walk
+// accepts (whatever the handle's leaf mode: a potential without its near field is of no use).  The opening tests are
+// k_bh_walk<.., DIRECT = true>'s, so {accepted, visited} equal that walk's; a term is an IEEE sqrt and divide in f32, the
+// running sum is f64.  One body per lane over the node-range split; every (segment, body) entry of the f64 planes is written
+// once and k_pot_reduce adds them in segment order: the same bits from run to run.  The force walk's planes, counters and
+// accelerations are not touched.
+// ACC = float exists in the tuning build only: the timing experiment that says what the f64 add costs
+template <class ACC>
+__global__ __launch_bounds__(kWalkBlock) void k_bh_pot_walk(const NodeDev* __restrict__ nodes, const int* __restrict__ order, int n_order,
+                                                            const float4* __restrict__ own_pos, float eps2, float theta2,
+                                                            unsigned long long* __restrict__ counters, WalkSplit split,
+                                                            double* __restrict__ planes, size_t plane_stride) {
+    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
+    if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);   // (spatial shards: the host's count is an upper bound)
+    const int K = gridDim.y;   // a group's segments nearest-first, as k_bh_walk dispatches them
+    const int diag = int((long long)blockIdx.x * K / gridDim.x);
+    const int kk = blockIdx.y;
+    const int seg = ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+    const int s1 = split.first[seg + 1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < n_order) {
+        const float4 p = own_pos[order[t]];
+        ACC sum = 0;
+        int i = walk_entry<true>(nodes, split, seg, p, theta2);
+        while (i < s1) {
+            const float4 A = nodes[i].a;
+            const float2 B = *reinterpret_cast<const float2*>(&nodes[i].b);
+            asm volatile("" :: "v"(A.w), "v"(B.y));   // (both loads whole and ahead of the branches: see k_bh_walk)
+            const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
+            const float r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = __float_as_int(B.y);
+            ++n_vis;
+            if (r2 < 1e-10f) { i = skip; continue; }                  // skipped whole (how a body skips itself)
+            if (B.x < theta2 * r2 || skip == i + 1) {                  // accepted cell, or a leaf that failed the test
+                sum += ACC(A.w / __builtin_sqrtf(r2 + eps2));
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        planes[size_t(seg) * plane_stride + t] = double(sum);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_acc += __shfl_down(n_acc, off);
+        n_vis += __shfl_down(n_vis, off);
+    }
+    if ((threadIdx.x & 63) == 0 && counters) {
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
+        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pot_reduce(const double* __restrict__ planes, int n_seg, size_t plane_stride,
+                                                    const int* __restrict__ order, int n_order, double* __restrict__ sum,
+                                                    const int* __restrict__ n_order_dev) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (n_order_dev) n_order = min(n_order, *n_order_dev);
+    if (t >= n_order) return;
+    double s = 0.0;
+    for (int k = 0; k < n_seg; ++k) s += planes[size_t(k) * plane_stride + t];   // segment order
+    sum[order[t]] = s;
+}
+
+void launch_pot_reduce(hipStream_t s, const double* planes, int n_seg, size_t plane_stride, const int* order, int n_order, double* sum,
+                       const int* n_order_dev) {
+    if (n_order <= 0) return;
+    hipLaunchKernelGGL(k_pot_reduce, dim3((n_order + 255) / 256), dim3(256), 0, s, planes, n_seg, plane_stride, order, n_order, sum, n_order_dev);
+}
+
+void launch_bh_pot_walk(hipStream_t s, const float4* own_pos, const TreeDev& t, float g_soft2, float theta2, double* planes,
+                        size_t plane_stride, double* sum, unsigned long long* counters) {
+    if (t.n_order <= 0) return;
+    WalkSplit sp{};
+    sp.n_seg = t.n_split; sp.first = t.split_first; sp.anc = t.split_anc; sp.n_anc = t.split_n_anc;
+    sp.n_order_dev = t.n_order_dev;
+    const dim3 grid((t.n_order + kWalkBlock - 1) / kWalkBlock, t.n_split);
+#ifdef NBODY_TUNING
+    if (tuning().bh_walk_debug == 2)   // timing experiment: an f32 running sum (the result is then good to ~1e-5 only)
+        hipLaunchKernelGGL(k_bh_pot_walk<float>, grid, dim3(kWalkBlock), 0, s, reinterpret_cast<const NodeDev*>(t.nodes), t.order, t.n_order, own_pos,
+                           g_soft2, theta2, counters, sp, planes, plane_stride);
+    else
+#endif
+    hipLaunchKernelGGL(k_bh_pot_walk<double>, grid, dim3(kWalkBlock), 0, s, reinterpret_cast<const NodeDev*>(t.nodes), t.order, t.n_order, own_pos,
+                       g_soft2, theta2, counters, sp, planes, plane_stride);
+    launch_pot_reduce(s, planes, t.n_split, plane_stride, t.order, t.n_order, sum, t.n_order_dev);
 }
 
 }  // namespace nbody

@@ -403,6 +403,51 @@ __global__ __launch_bounds__(256) void k_bh_reduce64(const double4* __restrict__
     }
 }
 
+// ---- nbody_potentials(NBODY_POTENTIAL_TREE) on an f64 handle: kernels_bh.hip k_bh_pot_walk for 64-byte records -- the DIRECT
+// walk's opening tests, a term m / sqrt(r2 + eps2) with IEEE sqrt and divide, one f64 entry per (segment, body)
+__global__ __launch_bounds__(kWalkBlock) void k_bh_pot_walk64(const Node64* __restrict__ nodes, const int* __restrict__ order, int n_order,
+                                                              const double4* __restrict__ pos, double eps2, double theta2,
+                                                              unsigned long long* __restrict__ counters, WalkSplit64 split,
+                                                              double* __restrict__ planes, size_t plane_stride) {
+    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
+    const int K = gridDim.y;
+    const int diag = int((long long)blockIdx.x * K / gridDim.x);
+    const int kk = blockIdx.y;
+    const int seg = ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+    const int s1 = split.first[seg + 1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < n_order) {
+        const double4 p = pos[order[t]];
+        double sum = 0.0;
+        int i = walk_entry64(nodes, split, seg, p, theta2, true);
+        while (i < s1) {
+            const Node64 nd = nodes[i];
+            const double rx = nd.x - p.x, ry = nd.y - p.y, rz = nd.z - p.z;
+            const double r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = nd.skip;
+            ++n_vis;
+            if (r2 < 1e-10) { i = skip; continue; }
+            if (nd.w2 < theta2 * r2 || skip == i + 1) {
+                sum += nd.m / __builtin_sqrt(r2 + eps2);
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        planes[size_t(seg) * plane_stride + t] = sum;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_acc += __shfl_down(n_acc, off);
+        n_vis += __shfl_down(n_vis, off);
+    }
+    if ((threadIdx.x & 63) == 0 && counters) {
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
+        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
+    }
+}
+
 // ---- diagnostics: KE and pair-potential row sums, per-block partials {KE, sum_j m_i m_j / d_ij}
 constexpr int kEnergyBlock = 256;
 __global__ __launch_bounds__(kEnergyBlock) void k_energy(const double4* __restrict__ pos, const double4* __restrict__ vel,
@@ -504,6 +549,12 @@ void launch_bh_walk_fast(hipStream_t s, const Dev& d, const Node64* nodes, int n
                                d.acc, d.pos, d.vel, 0.0);
         }
     }
+}
+void launch_bh_pot_walk(hipStream_t s, const double4* pos, const Node64* nodes, const int* order, int n_order, double eps2, double theta2,
+                        const WalkSplit64& split, double* planes, size_t plane_stride, unsigned long long* counters) {
+    if (n_order <= 0) return;
+    hipLaunchKernelGGL(k_bh_pot_walk64, dim3(blocks_for(n_order, kWalkBlock), split.n_seg), dim3(kWalkBlock), 0, s, nodes, order, n_order, pos,
+                       eps2, theta2, counters, split, planes, plane_stride);
 }
 void launch_energy(hipStream_t s, const Dev& d, int n_upper, double eps2, double* out2) {
     if (n_upper <= 0) return;

@@ -8,6 +8,7 @@
 #include "nbody_handle.h"
 #include "nbody_f64.h"
 #include "nbody_let.h"
+#include "nbody_pot.h"
 
 #include <algorithm>
 #include <chrono>
@@ -357,6 +358,8 @@ int ensure_tree_dev(NbodyHandle* h, size_t nodes, size_t order) {
 // positions, then one walk per body.
 int bh_walk_device_tree(NbodyHandle* h, bool* fell_back);
 int bh_walk_device_tree_async(NbodyHandle* h);
+int bh_walk_host_tree(NbodyHandle* h);
+void free_all(NbodyHandle* h);
 int resolve_async(NbodyHandle* h);
 int step_end(NbodyHandle* h, float dt);
 int step_impl(NbodyHandle* h, float dt);
@@ -443,6 +446,15 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
 // the end of every f32 force pass: the buffers of the strict and the experimental walks, the walk over td (+ the kick and half
 // drift when a step asked for them and the plane reduction can take them along)
 int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
+    if (h->pot.walking) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the same tree, order and split points, walked for potentials
+        const size_t stride = (size_t(std::max(td.n_order, 1)) + 63) / 64 * 64;
+        int rc = nbody::pot::ensure_planes(h, size_t(td.n_split) * stride);
+        if (rc) return rc;
+        nbody::launch_bh_pot_walk(h->stream, h->sh.own_pos(), td, h->g_soft * h->g_soft, h->theta2, h->pot.d_planes, stride, h->pot.d_sum,
+                                  h->pot.d_counts);
+        HIP_TRY(h, hipGetLastError());
+        return NBODY_OK;
+    }
     int rc = ensure_nested_stack(h, &td);
     if (!rc) rc = setup_lds_walk(h, &td, n_tree);
     if (rc) return rc;
@@ -460,7 +472,6 @@ int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
 }
 
 int bh_forces(NbodyHandle* h) {
-    Shard& sh = h->sh;
     {
         int rc = exchange_wait(h);
         if (rc) return rc;
@@ -478,6 +489,12 @@ int bh_forces(NbodyHandle* h) {
         // deeper than 42 levels somewhere: this step's tree comes from the host build below
     }
     h->host_tree_once = false;
+    return bh_walk_host_tree(h);
+}
+
+// the force pass on the tree built on the host
+int bh_walk_host_tree(NbodyHandle* h) {
+    Shard& sh = h->sh;
     h->tree_on_device = false;
     HostTreePass<float, float4> pass{reinterpret_cast<const float*>(sh.pos_all), sh.seg_count, sh.n_seg, sh.seg_cap, sh.my_seg, h->h_pos,
                                      h->h_counts, h->seg_count_host, h->n_local, h->count_dirty, h->center, h->width, h->tree,
@@ -488,7 +505,7 @@ int bh_forces(NbodyHandle* h) {
     // SIMD wanted: the walk is bound by the latency of dependent loads).  ~3 waves per wave slot of the chip (256 CUs x 32),
     // handed out heaviest first (nbody::tuning().bh_walk_order): the launch lasts as long as its slowest wave, and smaller
     // pieces started in the right order shorten that tail (N = 65 536: 24 segments 0.310 ms, 8 segments 0.336 ms; tools/tune_bh_order.py)
-    const int K = walk_split_plan(pass.n_order, h->cfg.math_mode != NBODY_MATH_STRICT, h->theta2, h->tree.n_nodes).segments;
+    const int K = walk_split_plan(pass.n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, h->tree.n_nodes).segments;
     rc = h->split.ensure(h, K, size_t(sh.seg_cap));
     if (!rc) rc = h->split.list_on_host(h, h->stream, h->tree.nodes, int(h->tree.n_nodes), K);
     if (rc) return rc;
@@ -556,7 +573,7 @@ int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
     h->tree_on_device = true;
     h->tree.n_nodes = size_t(n_nodes);  // (the host copy is filled on demand by nbody_tree_export)
 
-    const int K = walk_split_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT, h->theta2, size_t(n_nodes)).segments;
+    const int K = walk_split_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, size_t(n_nodes)).segments;
     rc = h->split.ensure(h, K, size_t(sh.seg_cap));
     if (rc) return rc;
     if (n_tree > 0) h->split.list_on_device(h->stream, work, int(n_tree), n_nodes, K);
@@ -765,6 +782,127 @@ int step_impl(NbodyHandle* h, float dt) {
     return rc;
 }
 
+// NBODY_POTENTIAL_TREE on a spatial rank.  After a step the bodies have half-drifted and some lie outside their rank's key
+// range; the slice-and-halo build needs every rank's bodies to BE a key range, so the pass has to migrate them -- and the call
+// must migrate nothing, redraw no bound and touch no balance state.  So the pass runs on a scratch clone of the rank
+// (nbody_clone: bodies, ids, visit-count weights, bounds) that borrows this handle's transport for its exchanges and is
+// destroyed afterwards: in the clones' world the strays migrate, every rank builds its slice, receives its halo and walks the
+// nodes it holds for potentials (let::potential_pass: the force pass, last phase swapped).  The sums then go home: every rank
+// all-gathers {index in the uploaded vector, S} of the bodies it walked, and each owner picks out its own bodies by index.
+// The handle itself is read, never written: bodies, bounds, weights, prediction, statistics and the host's view of the count
+// stay as they were.  counts = what the clone of this rank walked.
+int spatial_walk(NbodyHandle* h, NbodyHandle* twin, int n_orig) {
+    const int G = h->cfg.world_size, cap = h->sh.seg_cap;
+    PotBufs& p = h->pot;
+    int rc = nbody::let::potential_pass(twin);
+    if (rc) return fail(h, rc, twin->err);
+    rc = nbody::pot::begin(h, size_t(cap));
+    if (!rc) rc = grow_dev(h, p.d_rec, p.rec_cap, size_t(G) * size_t(cap), sizeof(nbody::PotRec));
+    const size_t n_ids = size_t(h->cfg.capacity) + 1;
+    if (!rc) rc = grow_dev(h, p.d_slot_of, p.slot_cap, n_ids, sizeof(int));
+    if (rc) return rc;
+    if (!p.d_rec_count) HIP_TRY(h, hipMalloc(&p.d_rec_count, sizeof(int) * size_t(G)));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the counters' reset: what follows is ordered on the clone's stream)
+    hipStream_t ts = twin->stream;
+    nbody::PotRec* rec = static_cast<nbody::PotRec*>(p.d_rec);
+    nbody::launch_pot_pack(ts, twin->sh.ids, twin->pot.d_sum, twin->sh.own_count(), cap, rec + size_t(h->cfg.rank) * size_t(cap));
+    HIP_TRY(h, hipMemcpyAsync(p.d_rec_count + h->cfg.rank, twin->sh.own_count(), sizeof(int), hipMemcpyDeviceToDevice, ts));
+    if (twin->comm_ready) {
+        TP_TRY(twin, twin->tp->group_begin());
+        TP_TRY(twin, twin->tp->all_gather(rec, size_t(cap) * sizeof(nbody::PotRec), ts));
+        TP_TRY(twin, twin->tp->all_gather(p.d_rec_count, sizeof(int), ts));
+        TP_TRY(twin, twin->tp->group_end());
+    }
+    HIP_TRY(h, hipMemsetAsync(p.d_slot_of, 0xFF, n_ids * sizeof(int), ts));
+    nbody::launch_pot_scatter(ts, h->sh.ids, h->sh.own_count(), n_orig, p.d_slot_of, int(std::min<size_t>(n_ids, 0x7fffffff)), rec, p.d_rec_count, G, cap, p.d_sum);
+    HIP_TRY(h, hipMemcpyAsync(p.d_counts, twin->pot.d_counts, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ts));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(ts));
+    if (twin->tp) { rc = twin->tp->check(); if (rc) return fail(h, rc, twin->tp->error()); }
+    return NBODY_OK;
+}
+
+int spatial_potentials(NbodyHandle* h, size_t* n_own, nbody::PotBodies* bodies, double* g) {
+    if (!h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    if (h->cfg.world_size > 1 && !h->comm_ready) return fail(h, NBODY_ERR_COMM, "world_size > 1 but nbody_comm_init has not been called");
+    const size_t saved_n = h->n_local;   // (nbody_clone refreshes the host's view of the count; the next walk's shape is drawn from the bound)
+    const bool saved_dirty = h->count_dirty;
+    const std::vector<int> saved_counts = h->seg_count_host;
+    NbodyHandle* twin = nullptr;
+    int rc = nbody_clone(h, &twin);
+    const int n_orig = int(h->n_local);   // exact now
+    h->n_local = saved_n; h->count_dirty = saved_dirty; h->seg_count_host = saved_counts;
+    if (rc) return fail(h, rc, std::string("nbody_potentials: scratch clone: ") + nbody_last_error(nullptr));
+    twin->tp = std::move(h->tp);          // the clones' world talks over this world's transport
+    twin->comm_ready = h->comm_ready;
+    nbody::bind_tuning(&twin->tune);
+    rc = spatial_walk(h, twin, n_orig);
+    if (rc && !twin->err.empty()) h->err = twin->err;
+    h->tp = std::move(twin->tp);
+    twin->comm_ready = false;
+    nbody::bind_tuning(&h->tune);
+    free_all(twin);
+    (void)hipSetDevice(h->device);
+    if (rc) return rc;
+    bodies->pos_all = h->sh.pos_all; bodies->vel = h->sh.vel; bodies->seg_count = h->sh.seg_count;
+    bodies->f64 = 0; bodies->n_seg = 1; bodies->seg_cap = h->sh.seg_cap; bodies->my_seg = 0;
+    bodies->world = h->comm_ready ? h->cfg.world_size : 1;
+    *g = double(h->g);
+    *n_own = size_t(n_orig);
+    return NBODY_OK;
+}
+
+// nbody_potentials / nbody_energy_world on an f32 handle: S_i = sum m_j / sqrt(r2 + g_soft^2) of the own bodies into
+// PotBufs::d_sum, at the CURRENT positions.  Index-block shards gather them first (in place: pos_all holds the other blocks
+// as of mid-step, and the next step's exchange overwrites them again).  TREE mode runs the handle's own force pass -- host or
+// device build, the same cells -- with PotBufs::walking set, so its last phase is the potential walk: accelerations, the
+// walk counters and the force planes are not written.  The host's view of the body counts is put back as it was: a step
+// chain enqueued without read-back sizes its launches from the bound it has, and must do so with or without this call.
+int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g) {
+    if (mode != NBODY_POTENTIAL_PAIRS && mode != NBODY_POTENTIAL_TREE) return fail(h, NBODY_ERR_INVALID, "mode must be NBODY_POTENTIAL_PAIRS or NBODY_POTENTIAL_TREE");
+    if (h->let && mode == NBODY_POTENTIAL_PAIRS)
+        return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_PAIRS is not possible on NBODY_SHARD_SPATIAL handles (a rank does not hold the world's bodies): NBODY_POTENTIAL_TREE is the mode for them");
+    if (h->let) return spatial_potentials(h, n_own, bodies, g);
+    if (mode == NBODY_POTENTIAL_TREE && h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_TREE needs a Barnes-Hut handle");
+    if (h->f64) return nbody64::potentials_device(h, mode, n_own, bodies, g);
+    if (mode == NBODY_POTENTIAL_TREE && !h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    Shard& sh = h->sh;
+    int rc = resolve_async(h);
+    if (!rc) rc = exchange_wait(h);
+    if (rc) return rc;
+    if (sh.n_seg > 1) {
+        if (!h->comm_ready) return fail(h, NBODY_ERR_COMM, "world_size > 1 but nbody_comm_init has not been called");
+        TP_TRY(h, h->tp->group_begin());
+        TP_TRY(h, h->tp->all_gather(sh.pos_all, size_t(sh.seg_cap) * sizeof(float4), h->stream));
+        TP_TRY(h, h->tp->all_gather(sh.seg_count, sizeof(int), h->stream));
+        TP_TRY(h, h->tp->group_end());
+    }
+    const size_t saved_n = h->n_local;
+    const bool saved_dirty = h->count_dirty, saved_once = h->host_tree_once;
+    const std::vector<int> saved_counts = h->seg_count_host;
+    h->count_dirty = true;
+    rc = sync_count(h);
+    if (!rc) rc = nbody::pot::begin(h, size_t(sh.seg_cap));
+    bodies->pos_all = sh.pos_all; bodies->vel = sh.vel; bodies->seg_count = sh.seg_count;
+    bodies->f64 = 0; bodies->n_seg = sh.n_seg; bodies->seg_cap = sh.seg_cap; bodies->my_seg = sh.my_seg;
+    bodies->world = sh.n_seg;
+    *g = double(h->g);
+    if (!rc && mode == NBODY_POTENTIAL_PAIRS) {
+        const size_t n = h->n_local;
+        rc = nbody::pot::pairs(h, *bodies, n, total_upper(h) - n, double(h->g_soft) * double(h->g_soft));
+    } else if (!rc) {
+        PotWalkScope walking(h->pot);
+        const bool on_device = h->cfg.tree_build == NBODY_TREE_DEVICE;
+        bool fell_back = false;
+        if (on_device) rc = bh_walk_device_tree(h, &fell_back);
+        if (!rc && (fell_back || !on_device)) rc = bh_walk_host_tree(h);   // (deeper than the device build goes: the host build, as the force pass does)
+    }
+    *n_own = h->n_local;
+    h->n_local = saved_n; h->count_dirty = saved_dirty; h->seg_count_host = saved_counts; h->host_tree_once = saved_once;
+    if (rc) return rc;
+    return comm_check(h);
+}
+
 void free_all(NbodyHandle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
@@ -788,6 +926,7 @@ void free_all(NbodyHandle* h) {
     for (void* p : host) if (p) (void)hipHostFree(p);
     h->split.release();
     h->tree_bufs.release();
+    h->pot.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1378,6 +1517,30 @@ int nbody_energy(NbodyHandle* h, double* kinetic, double* potential) {
     if (kinetic) *kinetic = ke;
     if (potential) *potential = -0.5 * double(h->g) * pe;  // every unordered pair was met twice
     return NBODY_OK;
+}
+
+int nbody_potentials(NbodyHandle* h, int mode, double* phi, size_t cap, size_t* n_out, uint64_t counts[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = use_device(h);
+    if (rc) return rc;
+    size_t n = 0;
+    nbody::PotBodies bodies;
+    double g = 0.0;
+    rc = potentials_device(h, mode, &n, &bodies, &g);
+    if (rc) return rc;
+    return nbody::pot::download(h, n, g, phi, cap, n_out, counts);
+}
+
+int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potential) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = use_device(h);
+    if (rc) return rc;
+    size_t n = 0;
+    nbody::PotBodies bodies;
+    double g = 0.0;
+    rc = potentials_device(h, mode, &n, &bodies, &g);
+    if (rc) return rc;
+    return nbody::pot::energy(h, bodies, n, g, kinetic, potential);
 }
 
 int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* skip, size_t cap, size_t* n_nodes) {

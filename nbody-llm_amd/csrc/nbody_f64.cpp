@@ -8,6 +8,7 @@
 // boundary as 80-byte records.
 #include "nbody_f64.h"
 #include "kernels_f64.h"
+#include "nbody_pot.h"
 
 #include <algorithm>
 #include <cmath>
@@ -185,6 +186,15 @@ int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const 
     if (rc) return rc;
     if (!k_done && !host_nodes) s.split.list_on_device(h->stream, s.tree_work, n_tree, n_nodes, K);
     const WalkSplit64 sp = walk_split_view(s.split, K, size_t(s.d.cap));
+    if (h->pot.walking) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the same tree, order and split points, walked for potentials
+        const size_t stride = (size_t(n_order) + 63) / 64 * 64;
+        rc = nbody::pot::ensure_planes(h, size_t(K) * stride);
+        if (rc) return rc;
+        launch_bh_pot_walk(h->stream, s.d.pos, nodes, order, n_order, s.g_soft * s.g_soft, s.theta2, sp, h->pot.d_planes, stride, h->pot.d_counts);
+        nbody::launch_pot_reduce(h->stream, h->pot.d_planes, K, stride, order, n_order, h->pot.d_sum);
+        HIP_TRY(h, hipGetLastError());
+        return NBODY_OK;
+    }
     {
         ForceTimer t(h);
         launch_bh_walk_fast(h->stream, s.d, nodes, n_nodes, order, n_order, s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
@@ -273,7 +283,7 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     s.tree_on_device = true;
     h->stats.tree_build_ms += ms_since(t0);
     h->stats.tree_nodes = s.dev_nodes;
-    if (h->cfg.math_mode == NBODY_MATH_FAST) return fast_walk(h, s, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), nullptr, int(s.n_local), k_pre);
+    if (h->cfg.math_mode == NBODY_MATH_FAST || h->pot.walking) return fast_walk(h, s, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), nullptr, int(s.n_local), k_pre);
     const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
     if (!direct) { rc = ensure_stack(h, s, 45); if (rc) return rc; }   // (the device build goes to 42 levels)
     {
@@ -300,7 +310,7 @@ int bh_forces(NbodyHandle* h, State& s) {
     int rc = pass.run(h);
     if (rc) return rc;
     const size_t n_order = pass.n_order;
-    if (h->cfg.math_mode == NBODY_MATH_FAST)
+    if (h->cfg.math_mode == NBODY_MATH_FAST || h->pot.walking)   // (the potential walk runs over the split in strict math too)
         return fast_walk(h, s, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.tree.nodes, int(s.tree.n_order));
     const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
     if (!direct) { rc = ensure_stack(h, s, s.tree.max_depth + 2); if (rc) return rc; }   // the tree's depth
@@ -639,6 +649,37 @@ int energy(NbodyHandle* h, double* kinetic, double* potential) {
     }
     if (kinetic) *kinetic = ke;
     if (potential) *potential = -0.5 * s.g * pe;  // every unordered pair was met twice
+    return NBODY_OK;
+}
+
+// nbody_potentials / nbody_energy_world on an f64 handle (nbody_api.cpp potentials_device has the f32 twin and the contract)
+int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g) {
+    State& s = *h->f64;
+    if (mode == NBODY_POTENTIAL_TREE && !s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    int rc = exchange(h, s);   // sharded: every block's current positions and live count
+    if (rc) return rc;
+    const size_t saved_n = s.n_local;
+    const bool saved_dirty = s.count_dirty;
+    const std::vector<int> saved_upper = s.count_upper;
+    s.count_dirty = true;
+    rc = sync_count(h, s);
+    if (!rc) rc = nbody::pot::begin(h, size_t(s.d.cap));
+    bodies->pos_all = s.d.pos_all; bodies->vel = s.d.vel; bodies->seg_count = s.d.seg_count;
+    bodies->f64 = 1; bodies->n_seg = s.d.n_seg; bodies->seg_cap = s.d.cap; bodies->my_seg = s.d.my_seg;
+    bodies->world = s.d.n_seg;
+    *g = s.g;
+    if (!rc && mode == NBODY_POTENTIAL_PAIRS) {
+        size_t tot = 0;
+        for (int c : s.count_upper) tot += size_t(c);
+        rc = nbody::pot::pairs(h, *bodies, s.n_local, tot - s.n_local, s.g_soft * s.g_soft);
+    } else if (!rc) {
+        PotWalkScope walking(h->pot);
+        rc = bh_forces(h, s);
+    }
+    *n_own = s.n_local;
+    s.n_local = saved_n; s.count_dirty = saved_dirty; s.count_upper = saved_upper;
+    if (rc) return rc;
+    if (h->tp) { rc = h->tp->check(); if (rc) return fail(h, rc, h->tp->error()); }
     return NBODY_OK;
 }
 

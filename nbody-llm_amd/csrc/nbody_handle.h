@@ -170,6 +170,43 @@ struct TreeBuildBufs {
     }
 };
 
+// nbody_potentials / nbody_energy_world (nbody_pot.cpp): buffers of their own -- a call writes none of the force pass's
+struct PotBufs {
+    bool walking = false;         // an NBODY_POTENTIAL_TREE call is under way: the force pass builds its tree as usual and its
+                                  // last phase walks for potentials (always over the node-range split, DIRECT leaf rule)
+    double* d_sum = nullptr;      // [sum_cap] S_i = sum m_j / sqrt(r2 + eps2) per own body, indexed like the own segment
+    size_t sum_cap = 0;
+    double* d_planes = nullptr;   // partial sums of the walk's segments / the pair kernels' slices, grow-only
+    size_t planes_cap = 0;        // doubles
+    unsigned long long* d_counts = nullptr;   // [NBODY_WALK_COUNTER_SLOTS][2] accepted, visited of the call under way
+    unsigned long long* h_counts = nullptr;   // pinned
+    double* d_part = nullptr;     // [2 * part_blocks] per-block {KE, sum m S}
+    size_t part_blocks = 0;
+    // spatial shards: the sums travel from the ranks that walked the bodies back to their owners (kernels_pot.h PotRec)
+    void* d_rec = nullptr;        // [world][seg_cap] records, all-gathered
+    size_t rec_cap = 0;           // records
+    int* d_rec_count = nullptr;   // [world]
+    int* d_slot_of = nullptr;     // [slot_cap] index in the uploaded vector -> own slot, -1
+    size_t slot_cap = 0;
+    void release() {
+        for (void* p : {static_cast<void*>(d_sum), static_cast<void*>(d_planes), static_cast<void*>(d_counts), static_cast<void*>(d_part), d_rec,
+                        static_cast<void*>(d_rec_count), static_cast<void*>(d_slot_of)})
+            if (p) (void)hipFree(p);
+        if (h_counts) (void)hipHostFree(h_counts);
+        *this = PotBufs{};
+    }
+};
+
+// the only way PotBufs::walking is set: for the lifetime of this object, so that no return path of a force pass run for
+// potentials can leave the handle walking for potentials when the next step comes
+struct PotWalkScope {
+    PotBufs& p;
+    explicit PotWalkScope(PotBufs& pb) : p(pb) { p.walking = true; }
+    ~PotWalkScope() { p.walking = false; }
+    PotWalkScope(const PotWalkScope&) = delete;
+    PotWalkScope& operator=(const PotWalkScope&) = delete;
+};
+
 struct NbodyHandle {
     NbodyConfig cfg{};
     nbody::Tuning tune;        // this handle's launch-shape and scheme knobs (nbody_set_tuning; NBODY_* environment at create)
@@ -268,6 +305,7 @@ struct NbodyHandle {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_free;
     double* d_energy = nullptr;
     size_t energy_blocks = 0;
+    PotBufs pot;
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;

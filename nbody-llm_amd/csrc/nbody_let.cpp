@@ -21,6 +21,7 @@
 // process on one GPU and do them as device-to-device copies (debug_phase / debug_exchange) -- same kernels, same buffers.
 #include "nbody_let.h"
 #include "kernels_let.h"
+#include "nbody_pot.h"
 
 #include <algorithm>
 #include <cstring>
@@ -324,7 +325,7 @@ int phase3(NbodyHandle* h, State& s) {
 }
 
 // the walk over the assembled array (+ kick + half drift when this is a step)
-int phase4(NbodyHandle* h, State& s, float dt, bool kick) {
+int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = false) {
     Shard& sh = h->sh;
     PhaseTimer timer(h, s, 4);
     // the walk's shape for this many bodies (kernels.h walk_plan): bodies per lane inside launch_bh_walk, node-range segments here
@@ -368,6 +369,14 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick) {
         td.split_first = s.d_split;          // {0, nodes held} (k_let_layout)
         td.split_n_anc = s.d_split + 2;      // 0
         td.split_anc = s.d_split + 2;
+    }
+    if (potentials) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the held nodes and split points of the force walk, walked for potentials
+        const size_t stride = (std::max<size_t>(h->n_local, 1) + 63) / 64 * 64;
+        int rc = pot::ensure_planes(h, size_t(K) * stride);
+        if (rc) return rc;
+        launch_bh_pot_walk(h->stream, sh.own_pos(), td, h->g_soft * h->g_soft, h->theta2, h->pot.d_planes, stride, h->pot.d_sum, h->pot.d_counts);
+        HIP_TRY(h, hipGetLastError());
+        return NBODY_OK;
     }
     int kicked = 0;
     launch_bh_walk(h->stream, sh, td, h->g, h->g_soft * h->g_soft, h->theta2, fast ? 1 : 0, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
@@ -892,7 +901,7 @@ static int draw_prediction(NbodyHandle* h, State& s, const int* mig_m) {
 // posted with sizes drawn from the previous step's counts (draw_prediction); if some pair has more migrants than that, every
 // rank sees it in the all-gathered matrix (kFlagMigSpill), nothing is committed, and after the synchronisation the round is
 // made again with the exact sizes and phases 1-3 are repeated (NbodyLetStats.migrant_respills counts such steps).
-static int pass(NbodyHandle* h, float dt, bool is_step) {
+static int pass(NbodyHandle* h, float dt, bool is_step, bool potentials = false) {
     State& s = *h->let;
     const int G = s.G, gg = G * G;
     if (G > 1 && !h->comm_ready) return fail(h, NBODY_ERR_COMM, "world_size > 1 but nbody_comm_init has not been called");
@@ -980,7 +989,7 @@ static int pass(NbodyHandle* h, float dt, bool is_step) {
         rc = variable_round(h, s, reinterpret_cast<const char*>(s.d_let_send), reinterpret_cast<char*>(s.d_let_recv), sizeof(LetRecord), out_at, n_out, in_at, n_in);
         if (rc) return rc;
     }
-    rc = phase4(h, s, dt, is_step);
+    rc = phase4(h, s, dt, is_step, potentials);
     if (rc) return rc;
     s.ev_set ^= 1;   // (the next pass records into the other set; this one's are read once they have completed)
     s.count_delta = 0;   // (the table count_global reads is this pass's)
@@ -990,6 +999,14 @@ static int pass(NbodyHandle* h, float dt, bool is_step) {
 int step(NbodyHandle* h, float dt) { return pass(h, dt, true); }
 
 int update_forces(NbodyHandle* h) { return pass(h, 0.f, false); }
+
+// The force pass at the current positions with its last phase walking for potentials: S_i of the bodies this rank holds
+// AFTER the pass's migration into PotBufs::d_sum, in the order of Shard::ids.  The pass migrates bodies and redraws the
+// bounds like any other, so nbody_potentials runs it on a scratch clone of the rank (nbody_api.cpp), never on the handle.
+int potential_pass(NbodyHandle* h) {
+    int rc = pot::begin(h, size_t(h->sh.seg_cap));
+    return rc ? rc : pass(h, 0.f, false, true);
+}
 
 // ---- one-process emulation: phases and exchanges driven from outside
 int debug_phase(NbodyHandle* h, int phase, float dt) {

@@ -18,6 +18,7 @@ int add_point(NbodyHandle* h, const void* particle);    // collective
 int remove_point(NbodyHandle* h, size_t index);         // collective
 int step(NbodyHandle* h, float dt);         // one step with the RCCL exchanges
 int update_forces(NbodyHandle* h);
+int potential_pass(NbodyHandle* h);         // update_forces with its last phase walking for potentials (PotBufs::d_sum); for a scratch clone
 int stats(NbodyHandle* h, NbodyLetStats* out);
 int reset_stats(NbodyHandle* h);
 // offsets and record counts of the variable-size rounds, from the all-gathered count matrix (host arithmetic)

@@ -11,7 +11,7 @@ RCCL refuses to put two ranks on one device.  With "rccl", rank r uses device r 
 cfg (JSON): world, address (socket path), out (directory), transport, device (ipc: the shared device),
   sim {method bf|bh, math fast|strict, shard index|spatial, tree auto|host|device, leaf reference|direct, tuning {knob: value}},
   ics {kind plummer|disc, n, seed, mass_jitter (seed or null), probe (body index or null), probe_mass}, box [[cx, cy, cz], width], settings {g, g_soft, dt, theta2},
-  schedule [["steps", k] | ["step_by", dt] | ["update_forces"] | ["settings", {...}] | ["sync"]], env {NAME: value},
+  schedule [["steps", k] | ["step_by", dt] | ["update_forces"] | ["settings", {...}] | ["sync"] | ["potentials", "pairs" | "tree"] | ["energy_world", "pairs" | "tree"]], env {NAME: value},
   env_by_rank {"r": {NAME: value}}.
 Every rank leaves out/rank<r>.npz (its bodies; spatial shards: + their indices in the uploaded vector) and
 out/rank<r>.json (counts, statistics, wall time of the schedule); a failing rank leaves out/rank<r>.err.
@@ -71,9 +71,11 @@ def make_sim(nb, cfg: dict, points: np.ndarray, rank: int, world: int, device: i
         tuning=sim_cfg.get("tuning"))
 
 
-def run_schedule(nb, sim, schedule, reattach=None):
+def run_schedule(nb, sim, schedule, reattach=None, record=None):
     """Runs the schedule; returns the simulation it ended with (a "clone" entry replaces it by its clone, whose communicator
-    `reattach(clone)` sets up again -- nbody_clone does not carry one over)."""
+    `reattach(clone)` sets up again -- nbody_clone does not carry one over).  record: a dict that receives what the
+    "potentials" and "energy_world" entries returned, in schedule order."""
+    mode_of = {"pairs": nb.POTENTIAL_PAIRS, "tree": nb.POTENTIAL_TREE}
     for item in schedule:
         op = item[0]
         if op == "add_point":        # [x, y, z, vx, vy, vz, mass]: Vec::push (collective in a sharded world)
@@ -98,6 +100,13 @@ def run_schedule(nb, sim, schedule, reattach=None):
             sim.settings = nb.Settings(**item[1])
         elif op == "sync":
             sim.sync()
+        elif op in ("potentials", "energy_world"):   # ["potentials", "pairs" | "tree"]: collective; a refusal is recorded, not raised
+            try:
+                got = sim.potentials(mode_of[item[1]]) if op == "potentials" else sim.energy_world(mode_of[item[1]])
+            except nb.NbodyError as e:
+                got = e
+            if record is not None:
+                record.setdefault(op, []).append(got)
         else:
             raise ValueError(f"unknown schedule entry {item}")
     return sim
@@ -125,15 +134,26 @@ def _rank_main(cfg: dict, rank: int, failed: list) -> None:
             twin.comm_init(rdzv.bcast_bytes((nb.comm_local_id() if ipc else nb.comm_unique_id()) if rank == 0 else None))
 
         t0 = time.perf_counter()
-        sim = run_schedule(nb, sim, cfg["schedule"], reattach)
+        record: dict = {}
+        sim = run_schedule(nb, sim, cfg["schedule"], reattach, record)
         sim.sync()
         wall = time.perf_counter() - t0
         pts = sim.get_points()
         arrays = {"points": pts.view(np.uint8)}
         if cfg["sim"].get("shard", "index") == "spatial":
             arrays["ids"] = sim.download_ids()
+        refused = lambda e: {"error": int(e.code), "message": str(e)}   # noqa: E731
+        potentials = []   # per "potentials" entry: {"counts": [terms, tests]} with the values in arrays["phi<k>"], or the refusal
+        for k, got in enumerate(record.get("potentials", [])):
+            if isinstance(got, Exception):
+                potentials.append(refused(got))
+            else:
+                arrays[f"phi{k}"] = got[0]
+                potentials.append({"counts": list(got[1])})
+        energies = [refused(e) if isinstance(e, Exception) else list(e) for e in record.get("energy_world", [])]
         st = sim.stats()
-        meta = {"rank": rank, "f64": bool(sim.f64), "count": int(len(pts)), "count_global": int(sim.count_global()), "wall_s": wall, "elapsed": sim.elapsed(),
+        meta = {"potentials": potentials, "energy_world": energies,
+                "rank": rank, "f64": bool(sim.f64), "count": int(len(pts)), "count_global": int(sim.count_global()), "wall_s": wall, "elapsed": sim.elapsed(),
                 "transport": sim.comm_transport(), "steps": int(st.steps), "interactions": int(st.interactions),
                 "node_visits": int(st.node_visits), "tree_nodes": int(st.tree_nodes), "local_range": list(sim.local_range())}
         if cfg["sim"].get("shard", "index") == "spatial":
@@ -229,6 +249,9 @@ def run_world(cfg: dict, ranks_per_process: int = 1, timeout: float = 180.0) -> 
         meta["points"] = z["points"].view(nb.PARTICLE_DTYPE64 if meta.get("f64") else nb.PARTICLE_DTYPE)
         if "ids" in z:
             meta["ids"] = z["ids"]
+        for k, rec in enumerate(meta.get("potentials", [])):
+            if f"phi{k}" in z:
+                rec["phi"] = z[f"phi{k}"]
         results.append(meta)
     return results
 
