@@ -211,6 +211,26 @@ enum { NBODY_POTENTIAL_PAIRS = 0,   /* the exact pair sum over every body of the
 int nbody_potentials(NbodyHandle* h, int mode, double* phi, size_t cap, size_t* n_out, uint64_t counts[2]);
 /* KE = sum 1/2 m v^2 and PE = 1/2 sum_i m_i phi_i over ALL ranks (the same two numbers on every rank); collective. */
 int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potential);
+/* The field of the world's bodies at caller-chosen points, at the handle's CURRENT positions:
+ *   acc(x) = g * sum_j m_j (x_j - x) / (|x_j - x|^2 + g_soft^2)^(3/2),   phi(x) = -g * sum_j m_j / sqrt(|x_j - x|^2 + g_soft^2)
+ * over ALL bodies of the world.  xyz: n_points f64 triples on either dtype; an f32 handle rounds each coordinate to the nearest
+ * f32 once and the result is the field at the rounded point (a probe at a body's stored position coincides with it).  acc
+ * [n_points][3] and phi [n_points] are f64, in the caller's order; either may be NULL, both NULL only counts.  n_points == 0 is
+ * valid (TREE still builds its tree).  counts (may be NULL) = {terms summed, opening tests} of this call (PAIRS: 0, 0).
+ *   NBODY_POTENTIAL_PAIRS  either method: coordinates widened to f64, differences, terms and sums in f64; a body at r2 == 0
+ *                          exactly is skipped.
+ *   NBODY_POTENTIAL_TREE   Barnes-Hut handles with bounds set: the tree nbody_update_forces would build (nbody_tree_export
+ *                          reports it afterwards), walked with nbody_potentials(TREE)'s tests -- r2 in the handle's precision, a
+ *                          node with r2 < 1e-10 skipped whole, w2 < theta2 * r2 accepts, a leaf that fails is evaluated whatever
+ *                          the handle's leaf_mode.  Terms in the handle's precision (q = r2 + g_soft^2, inv = 1 / sqrt(q), scalar
+ *                          m * inv, vector d * ((m * inv) / q)), the four sums in f64.
+ * math_mode has no influence.  Points outside the box are legal; a point with a non-finite coordinate gets NaN outputs and
+ * disturbs no other point.  TREE works in the handle's number range: a finite point so far away that r2 overflows (beyond
+ * ~1e19 from the bodies on an f32 handle) gets exact zeros.  The same call twice gives the same bits, and permuting the points permutes the results bit for bit.
+ * Collective on a world of index-block shards: every rank passes its own points (possibly none) and gets the whole world's field
+ * at them.  NBODY_SHARD_SPATIAL handles are refused (NBODY_ERR_INVALID): a rank holds neither the world's bodies nor the tree
+ * around a foreign point.  Like nbody_potentials the call leaves no trace in the state, the statistics or a later step. */
+int nbody_field_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]);
 /* Linearised octree of the last Barnes-Hut force pass: per node {com xyz, mass}, width, skip
  * index (first node after the subtree, depth-first pre-order).  Arrays may be NULL to count. */
 int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* skip, size_t cap, size_t* n_nodes);

@@ -74,7 +74,7 @@ DECLARED_SYMBOLS = [
     "nbody_debug_let_bounds", "nbody_debug_let_set_balance",
     "nbody_comm_local_id", "nbody_comm_transport", "nbody_host_exchange_layout",
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
-    "nbody_get_config", "nbody_potentials", "nbody_energy_world",
+    "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at",
 ]
 
 
@@ -136,6 +136,7 @@ _sig("nbody_reset_stats", _i, _H)
 _sig("nbody_energy", _i, _H, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_potentials", _i, _H, _i, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
 _sig("nbody_energy_world", _i, _H, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("nbody_field_at", _i, _H, _i, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64))
 _sig("nbody_tree_export", _i, _H, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_tree_export_cells", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_last_error", C.c_char_p, _H)
@@ -466,6 +467,19 @@ class Simulation:
         counts = (C.c_uint64 * 2)()
         self._check(lib.nbody_potentials(self._h, int(mode), phi.ctypes.data, len(phi), C.byref(n), counts))
         return phi[: n.value], (int(counts[0]), int(counts[1]))
+
+    def field_at(self, points, mode: int = POTENTIAL_PAIRS, acc: bool = True, phi: bool = True):
+        """(acc [M, 3] f64 | None, phi [M] f64 | None, (terms summed, opening tests)) of ALL bodies of the world at the M
+        given points (any array-like [M, 3]), at the current positions; collective on a multi-rank world.  An f32 handle
+        evaluates at the points rounded to f32."""
+        xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+        m = len(xyz)
+        a = np.zeros((m, 3), np.float64) if acc else None
+        p = np.zeros(m, np.float64) if phi else None
+        counts = (C.c_uint64 * 2)()
+        self._check(lib.nbody_field_at(self._h, int(mode), xyz.ctypes.data if m else None, m, a.ctypes.data if acc else None,
+                                       p.ctypes.data if phi else None, counts))
+        return a, p, (int(counts[0]), int(counts[1]))
 
     def energy_world(self, mode: int = POTENTIAL_PAIRS) -> tuple[float, float]:
         """(KE, PE) of the whole world, the same on every rank; collective."""

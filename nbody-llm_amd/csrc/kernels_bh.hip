@@ -19,6 +19,7 @@
 // sectors that stay in L1/L2 (the whole node array is 32 B x n_nodes, ~4 MB at N = 65 536).
 #include "kernels.h"
 #include "kernels_pot.h"
+#include "kernels_field.h"
 
 namespace nbody {
 
@@ -1232,6 +1233,81 @@ void launch_bh_pot_walk(hipStream_t s, const float4* own_pos, const TreeDev& t, 
     hipLaunchKernelGGL(k_bh_pot_walk<double>, grid, dim3(kWalkBlock), 0, s, reinterpret_cast<const NodeDev*>(t.nodes), t.order, t.n_order, own_pos,
                        g_soft2, theta2, counters, sp, planes, plane_stride);
     launch_pot_reduce(s, planes, t.n_split, plane_stride, t.order, t.n_order, sum, t.n_order_dev);
+}
+
+// ---- nbody_field_at(NBODY_POTENTIAL_TREE): k_bh_pot_walk for caller-chosen points, with the vector sum beside the scalar one.
+// Lane t walks probe idx[t] (the batch in Morton order: neighbouring lanes follow nearly the same path), rounded to f32 once.
+// The tests are k_bh_pot_walk's, so {accepted, visited} equal oracle.bh_walk_list(.., leaf_mode = 1) at the rounded points.  A
+// term: q = r2 + eps2, inv = 1 / sqrt(q), scalar m * inv, vector d * ((m * inv) / q) -- the divide instead of two more products
+// with inv keeps a component within 15 u of its exact value (tests/field_list.py counts) -- in f32, the four sums in f64.
+// A non-finite probe compares false everywhere: it steps through every node (each branch advances i) and ends with NaN sums.
+template <bool VEC, bool SCAL>
+__global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk(const NodeDev* __restrict__ nodes, const double* __restrict__ xyz,
+                                                              const int* __restrict__ idx, int n, float eps2, float theta2,
+                                                              unsigned long long* __restrict__ counters, WalkSplit split,
+                                                              double4* __restrict__ planes, size_t plane_stride) {
+    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
+    const int K = gridDim.y;   // a group's segments nearest-first, as k_bh_walk dispatches them
+    const int diag = int((long long)blockIdx.x * K / gridDim.x);
+    const int kk = blockIdx.y;
+    const int seg = ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+    const int s1 = split.first[seg + 1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < n) {
+        const size_t c = size_t(idx[t]);
+        const float4 p = make_float4(float(xyz[3 * c]), float(xyz[3 * c + 1]), float(xyz[3 * c + 2]), 0.f);
+        const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+        double ax = 0.0, ay = 0.0, az = 0.0, sum = 0.0;
+        int i = walk_entry<true>(nodes, split, seg, p, theta2);
+        while (i < s1) {
+            const float4 A = nodes[i].a;
+            const float2 B = *reinterpret_cast<const float2*>(&nodes[i].b);
+            asm volatile("" :: "v"(A.w), "v"(B.y));   // (both loads whole and ahead of the branches: see k_bh_walk)
+            const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
+            const float r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = __float_as_int(B.y);
+            ++n_vis;
+            if (r2 < 1e-10f) { i = skip; continue; }                  // skipped whole (a probe on a body skips it)
+            if (B.x < theta2 * r2 || skip == i + 1) {                  // accepted cell, or a leaf that failed the test
+                const float q = r2 + eps2;
+                const float st = A.w * (1.0f / __builtin_sqrtf(q));
+                if (SCAL) sum += double(st);
+                if (VEC) {
+                    const float k = st / q;
+                    ax += double(rx * k); ay += double(ry * k); az += double(rz * k);
+                }
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        if (VEC || SCAL) {
+            const double bad = __longlong_as_double(0x7ff8000000000000ll);
+            planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_acc += __shfl_down(n_acc, off);
+        n_vis += __shfl_down(n_vis, off);
+    }
+    if ((threadIdx.x & 63) == 0 && counters) {
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
+        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
+    }
+}
+
+void launch_bh_field_walk(hipStream_t s, const FieldTree& t, const double* xyz, const int* idx, int n, float eps2, float theta2, int want,
+                          double4* planes, size_t stride, unsigned long long* counters) {
+    if (n <= 0) return;
+    WalkSplit sp{};
+    sp.n_seg = t.K; sp.first = t.first; sp.anc = t.anc; sp.n_anc = t.n_anc;
+    const dim3 grid((n + kWalkBlock - 1) / kWalkBlock, t.K);
+    const NodeDev* nodes = static_cast<const NodeDev*>(t.nodes);
+#define FIELD_WALK(V, S) hipLaunchKernelGGL((k_bh_field_walk<V, S>), grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
+    if (want == 3) FIELD_WALK(true, true); else if (want == 1) FIELD_WALK(true, false); else if (want == 2) FIELD_WALK(false, true); else FIELD_WALK(false, false);
+#undef FIELD_WALK
 }
 
 }  // namespace nbody

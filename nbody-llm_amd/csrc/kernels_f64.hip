@@ -6,6 +6,7 @@
 // Compiled with -ffp-contract=off; f64 sqrt and divide are correctly rounded on gfx950.
 #include "kernels_f64.h"
 #include "kernels.h"   // nbody::tuning()
+#include "kernels_field.h"
 
 #include <algorithm>
 
@@ -448,6 +449,63 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_pot_walk64(const Node64* __re
     }
 }
 
+// ---- nbody_field_at(NBODY_POTENTIAL_TREE) on an f64 handle: kernels_bh.hip k_bh_field_walk for 64-byte records (the same
+// tests, terms and NaN rule, all in f64)
+template <bool VEC, bool SCAL>
+__global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk64(const Node64* __restrict__ nodes, const double* __restrict__ xyz,
+                                                                const int* __restrict__ idx, int n, double eps2, double theta2,
+                                                                unsigned long long* __restrict__ counters, WalkSplit64 split,
+                                                                double4* __restrict__ planes, size_t plane_stride) {
+    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
+    const int K = gridDim.y;
+    const int diag = int((long long)blockIdx.x * K / gridDim.x);
+    const int kk = blockIdx.y;
+    const int seg = ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+    const int s1 = split.first[seg + 1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < n) {
+        const size_t c = size_t(idx[t]);
+        const double4 p = make_double4(xyz[3 * c], xyz[3 * c + 1], xyz[3 * c + 2], 0.0);
+        const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+        double ax = 0.0, ay = 0.0, az = 0.0, sum = 0.0;
+        int i = walk_entry64(nodes, split, seg, p, theta2, true);
+        while (i < s1) {
+            const Node64 nd = nodes[i];
+            const double rx = nd.x - p.x, ry = nd.y - p.y, rz = nd.z - p.z;
+            const double r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = nd.skip;
+            ++n_vis;
+            if (r2 < 1e-10) { i = skip; continue; }
+            if (nd.w2 < theta2 * r2 || skip == i + 1) {
+                const double q = r2 + eps2;
+                const double st = nd.m * (1.0 / __builtin_sqrt(q));
+                if (SCAL) sum += st;
+                if (VEC) {
+                    const double k = st / q;
+                    ax += rx * k; ay += ry * k; az += rz * k;
+                }
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        if (VEC || SCAL) {
+            const double bad = __longlong_as_double(0x7ff8000000000000ll);
+            planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_acc += __shfl_down(n_acc, off);
+        n_vis += __shfl_down(n_vis, off);
+    }
+    if ((threadIdx.x & 63) == 0 && counters) {
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
+        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
+    }
+}
+
 // ---- diagnostics: KE and pair-potential row sums, per-block partials {KE, sum_j m_i m_j / d_ij}
 constexpr int kEnergyBlock = 256;
 __global__ __launch_bounds__(kEnergyBlock) void k_energy(const double4* __restrict__ pos, const double4* __restrict__ vel,
@@ -555,6 +613,16 @@ void launch_bh_pot_walk(hipStream_t s, const double4* pos, const Node64* nodes, 
     if (n_order <= 0) return;
     hipLaunchKernelGGL(k_bh_pot_walk64, dim3(blocks_for(n_order, kWalkBlock), split.n_seg), dim3(kWalkBlock), 0, s, nodes, order, n_order, pos,
                        eps2, theta2, counters, split, planes, plane_stride);
+}
+void launch_bh_field_walk(hipStream_t s, const nbody::FieldTree& t, const double* xyz, const int* idx, int n, double eps2, double theta2, int want,
+                          double4* planes, size_t stride, unsigned long long* counters) {
+    if (n <= 0) return;
+    const WalkSplit64 sp{t.K, t.first, t.anc, t.n_anc, nullptr, 0};
+    const dim3 grid(blocks_for(n, kWalkBlock), t.K);
+    const Node64* nodes = static_cast<const Node64*>(t.nodes);
+#define FIELD_WALK(V, S) hipLaunchKernelGGL((k_bh_field_walk64<V, S>), grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
+    if (want == 3) FIELD_WALK(true, true); else if (want == 1) FIELD_WALK(true, false); else if (want == 2) FIELD_WALK(false, true); else FIELD_WALK(false, false);
+#undef FIELD_WALK
 }
 void launch_energy(hipStream_t s, const Dev& d, int n_upper, double eps2, double* out2) {
     if (n_upper <= 0) return;

@@ -25,6 +25,7 @@
 // far below an ulp of the coordinates by then) make the build report "too deep"; the one-GPU caller falls back to the
 // host build (which goes to depth 192 before it gives up), the spatial-shard caller returns NBODY_ERR_TREE_DEPTH.
 #include "kernels.h"
+#include "kernels_field.h"
 #include "kernels_f64.h"   // Node64: the F = f64 instantiation of the build writes 64-byte records
 
 #include <cstring>
@@ -824,6 +825,41 @@ int build_bfs_layout(hipStream_t s, const float4* nodes, int n_nodes, void* work
 }
 
 #endif  // NBODY_TUNING
+
+// ---- nbody_field_at: the probes of a batch in tree order.  The key is the device build's sort key of the probe rounded to
+// the handle's precision; a probe outside the box keeps choosing the outermost orthant on its side (the key saturates: clamped),
+// a NaN coordinate compares false at every level.
+namespace {
+template <class Real> struct Probe3 { Real x, y, z; };
+template <class Real>
+__global__ __launch_bounds__(256) void k_field_keys(const double* __restrict__ xyz, int n, Real cx, Real cy, Real cz, Real width,
+                                                    unsigned long long* __restrict__ keys, int* __restrict__ idx) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const Probe3<Real> p{Real(xyz[3 * size_t(k)]), Real(xyz[3 * size_t(k) + 1]), Real(xyz[3 * size_t(k) + 2])};
+    keys[k] = orthant_key(p, cx, cy, cz, width, 0);
+    idx[k] = k;
+}
+}  // namespace
+
+size_t field_sort_tmp_bytes(size_t n_cap) {
+    size_t b = 0;
+    unsigned long long* k = nullptr; int* v = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_cap, 0, 63, 0);
+    return (b + 255) / 256 * 256;
+}
+
+int field_sort_probes(hipStream_t s, const double* xyz, int n, int f64, const double center[3], double width, void* tmp, size_t tmp_bytes,
+                      unsigned long long* keys, int* idx, size_t n_cap, const int** sorted_idx) {
+    *sorted_idx = idx + n_cap;
+    if (n <= 0) return 0;
+    const dim3 grid((n + 255) / 256), block(256);
+    if (f64) hipLaunchKernelGGL(k_field_keys<double>, grid, block, 0, s, xyz, n, center[0], center[1], center[2], width, keys, idx);
+    else hipLaunchKernelGGL(k_field_keys<float>, grid, block, 0, s, xyz, n, float(center[0]), float(center[1]), float(center[2]), float(width), keys, idx);
+    size_t tb = tmp_bytes;
+    if (rocprim::radix_sort_pairs(tmp, tb, keys, keys + n_cap, idx, idx + n_cap, size_t(n), 0, 63, s) != hipSuccess) return -1;
+    return 0;
+}
 
 // bytes at the start of the build workspace that rocPRIM uses as scratch (free between builds)
 size_t tree_build_tmp_bytes(size_t n_cap) { return scratch_bytes(n_cap); }

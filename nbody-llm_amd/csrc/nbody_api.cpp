@@ -9,6 +9,7 @@
 #include "nbody_f64.h"
 #include "nbody_let.h"
 #include "nbody_pot.h"
+#include "nbody_field.h"
 
 #include <algorithm>
 #include <chrono>
@@ -446,6 +447,12 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
 // the end of every f32 force pass: the buffers of the strict and the experimental walks, the walk over td (+ the kick and half
 // drift when a step asked for them and the plane reduction can take them along)
 int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
+    if (h->pot.walking == kWalkField) {   // nbody_field_at(NBODY_POTENTIAL_TREE): the caller walks this tree for its probes, batch by batch
+        FieldBufs& f = h->field;
+        f.nodes = td.nodes; f.n_nodes = td.n_nodes; f.K = td.n_split;
+        f.first = td.split_first; f.anc = td.split_anc; f.n_anc = td.split_n_anc;
+        return NBODY_OK;
+    }
     if (h->pot.walking) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the same tree, order and split points, walked for potentials
         const size_t stride = (size_t(std::max(td.n_order, 1)) + 63) / 64 * 64;
         int rc = nbody::pot::ensure_planes(h, size_t(td.n_split) * stride);
@@ -505,7 +512,8 @@ int bh_walk_host_tree(NbodyHandle* h) {
     // SIMD wanted: the walk is bound by the latency of dependent loads).  ~3 waves per wave slot of the chip (256 CUs x 32),
     // handed out heaviest first (nbody::tuning().bh_walk_order): the launch lasts as long as its slowest wave, and smaller
     // pieces started in the right order shorten that tail (N = 65 536: 24 segments 0.310 ms, 8 segments 0.336 ms; tools/tune_bh_order.py)
-    const int K = walk_split_plan(pass.n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, h->tree.n_nodes).segments;
+    const int K = h->pot.walking == kWalkField ? field_split_plan(h->field.n_points, h->tree.n_nodes)   // (a field call walks its probes, not the bodies)
+                  : walk_split_plan(pass.n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, h->tree.n_nodes).segments;
     rc = h->split.ensure(h, K, size_t(sh.seg_cap));
     if (!rc) rc = h->split.list_on_host(h, h->stream, h->tree.nodes, int(h->tree.n_nodes), K);
     if (rc) return rc;
@@ -573,7 +581,8 @@ int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
     h->tree_on_device = true;
     h->tree.n_nodes = size_t(n_nodes);  // (the host copy is filled on demand by nbody_tree_export)
 
-    const int K = walk_split_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, size_t(n_nodes)).segments;
+    const int K = h->pot.walking == kWalkField ? field_split_plan(h->field.n_points, size_t(n_nodes))   // (a field call walks its probes, not the bodies)
+                  : walk_split_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, size_t(n_nodes)).segments;
     rc = h->split.ensure(h, K, size_t(sh.seg_cap));
     if (rc) return rc;
     if (n_tree > 0) h->split.list_on_device(h->stream, work, int(n_tree), n_nodes, K);
@@ -858,13 +867,17 @@ int spatial_potentials(NbodyHandle* h, size_t* n_own, nbody::PotBodies* bodies, 
 // device build, the same cells -- with PotBufs::walking set, so its last phase is the potential walk: accelerations, the
 // walk counters and the force planes are not written.  The host's view of the body counts is put back as it was: a step
 // chain enqueued without read-back sizes its launches from the bound it has, and must do so with or without this call.
-int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g) {
+// field = true (nbody_field_at): the same preparation with nothing summed over the bodies -- PAIRS: the gathered positions and
+// live counts; TREE: the force pass up to its last phase, which leaves the tree and its split points in FieldBufs.
+int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g, bool field = false) {
     if (mode != NBODY_POTENTIAL_PAIRS && mode != NBODY_POTENTIAL_TREE) return fail(h, NBODY_ERR_INVALID, "mode must be NBODY_POTENTIAL_PAIRS or NBODY_POTENTIAL_TREE");
+    if (h->let && field)
+        return fail(h, NBODY_ERR_INVALID, "nbody_field_at is not possible on NBODY_SHARD_SPATIAL handles: a rank holds neither the world's bodies nor the tree around a foreign point");
     if (h->let && mode == NBODY_POTENTIAL_PAIRS)
         return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_PAIRS is not possible on NBODY_SHARD_SPATIAL handles (a rank does not hold the world's bodies): NBODY_POTENTIAL_TREE is the mode for them");
     if (h->let) return spatial_potentials(h, n_own, bodies, g);
     if (mode == NBODY_POTENTIAL_TREE && h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_TREE needs a Barnes-Hut handle");
-    if (h->f64) return nbody64::potentials_device(h, mode, n_own, bodies, g);
+    if (h->f64) return nbody64::potentials_device(h, mode, n_own, bodies, g, field);
     if (mode == NBODY_POTENTIAL_TREE && !h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     Shard& sh = h->sh;
     int rc = resolve_async(h);
@@ -889,9 +902,9 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
     *g = double(h->g);
     if (!rc && mode == NBODY_POTENTIAL_PAIRS) {
         const size_t n = h->n_local;
-        rc = nbody::pot::pairs(h, *bodies, n, total_upper(h) - n, double(h->g_soft) * double(h->g_soft));
+        if (!field) rc = nbody::pot::pairs(h, *bodies, n, total_upper(h) - n, double(h->g_soft) * double(h->g_soft));
     } else if (!rc) {
-        PotWalkScope walking(h->pot);
+        PotWalkScope walking(h->pot, field ? kWalkField : kWalkPotentials);
         const bool on_device = h->cfg.tree_build == NBODY_TREE_DEVICE;
         bool fell_back = false;
         if (on_device) rc = bh_walk_device_tree(h, &fell_back);
@@ -927,6 +940,7 @@ void free_all(NbodyHandle* h) {
     h->split.release();
     h->tree_bufs.release();
     h->pot.release();
+    h->field.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -1529,6 +1543,22 @@ int nbody_potentials(NbodyHandle* h, int mode, double* phi, size_t cap, size_t* 
     rc = potentials_device(h, mode, &n, &bodies, &g);
     if (rc) return rc;
     return nbody::pot::download(h, n, g, phi, cap, n_out, counts);
+}
+
+int nbody_field_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (n_points > (size_t(1) << 30)) return fail(h, NBODY_ERR_INVALID, "nbody_field_at: n_points must not exceed 2^30");
+    if (!xyz && n_points > 0) return fail(h, NBODY_ERR_INVALID, "nbody_field_at: xyz is NULL");
+    h->field.n_points = n_points;
+    h->field.nodes = nullptr; h->field.n_nodes = 0; h->field.K = 1;
+    size_t n = 0;
+    nbody::PotBodies bodies;
+    double g = 0.0;
+    rc = potentials_device(h, mode, &n, &bodies, &g, true);
+    if (rc) return rc;
+    return nbody::field::run(h, mode, bodies, g, xyz, n_points, acc, phi, counts);
 }
 
 int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potential) {

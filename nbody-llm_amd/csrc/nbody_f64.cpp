@@ -178,14 +178,21 @@ int ensure_stack(NbodyHandle* h, State& s, int levels) {   // the nested sums' s
 // the host-built tree; nullptr: by k_tree_split_anc from the device build's arrays (n_tree bodies).
 int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const int* order, int n_order, const nbody::NodeRecT<double>* host_nodes, int n_tree,
               int k_done = 0 /* > 0: the split points of this many segments are on the device already (they rode in the build) */) {
-    if (n_order == 0 || n_nodes <= 0) return NBODY_OK;
+    const bool field = h->pot.walking == kWalkField;   // nbody_field_at(TREE): the walk is over the call's probes, not the bodies
+    if ((n_order == 0 && !field) || n_nodes <= 0) return NBODY_OK;
     const nbody::WalkPlan plan = walk_split_plan(size_t(n_order), true, float(s.theta2), size_t(n_nodes));   // (bodies per lane x segments: kernels.h)
-    const int K = k_done > 0 ? k_done : plan.segments;
+    const int K = field ? field_split_plan(h->field.n_points, size_t(n_nodes)) : k_done > 0 ? k_done : plan.segments;
     int rc = s.split.ensure(h, K, size_t(s.d.cap));
     if (!rc && !k_done && host_nodes) rc = s.split.list_on_host(h, h->stream, host_nodes, n_nodes, K);
     if (rc) return rc;
     if (!k_done && !host_nodes) s.split.list_on_device(h->stream, s.tree_work, n_tree, n_nodes, K);
     const WalkSplit64 sp = walk_split_view(s.split, K, size_t(s.d.cap));
+    if (field) {   // the caller walks this tree for its probes, batch by batch (nbody_field.cpp)
+        FieldBufs& f = h->field;
+        f.nodes = nodes; f.n_nodes = n_nodes; f.K = K;
+        f.first = sp.first; f.anc = sp.anc; f.n_anc = sp.n_anc;
+        return NBODY_OK;
+    }
     if (h->pot.walking) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the same tree, order and split points, walked for potentials
         const size_t stride = (size_t(n_order) + 63) / 64 * 64;
         rc = nbody::pot::ensure_planes(h, size_t(K) * stride);
@@ -238,7 +245,7 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     // one shard, fast math: the walk's split points ride in the build's last launch (kernels.h TreeSplitReq)
     nbody::TreeSplitReq req;
     int k_pre = 0;
-    if (!sharded && h->cfg.math_mode == NBODY_MATH_FAST && tot_upper > 0) {
+    if (!sharded && h->cfg.math_mode == NBODY_MATH_FAST && tot_upper > 0 && h->pot.walking != kWalkField) {   // (a field call draws K from its probes)
         k_pre = walk_split_plan(tot_upper, true, float(s.theta2), tot_upper).segments;   // (a tree has at least as many nodes as bodies)
         rc = s.split.ensure(h, k_pre, size_t(s.d.cap));
         if (rc) return rc;
@@ -653,7 +660,7 @@ int energy(NbodyHandle* h, double* kinetic, double* potential) {
 }
 
 // nbody_potentials / nbody_energy_world on an f64 handle (nbody_api.cpp potentials_device has the f32 twin and the contract)
-int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g) {
+int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g, bool field) {
     State& s = *h->f64;
     if (mode == NBODY_POTENTIAL_TREE && !s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     int rc = exchange(h, s);   // sharded: every block's current positions and live count
@@ -671,9 +678,9 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
     if (!rc && mode == NBODY_POTENTIAL_PAIRS) {
         size_t tot = 0;
         for (int c : s.count_upper) tot += size_t(c);
-        rc = nbody::pot::pairs(h, *bodies, s.n_local, tot - s.n_local, s.g_soft * s.g_soft);
+        if (!field) rc = nbody::pot::pairs(h, *bodies, s.n_local, tot - s.n_local, s.g_soft * s.g_soft);
     } else if (!rc) {
-        PotWalkScope walking(h->pot);
+        PotWalkScope walking(h->pot, field ? kWalkField : kWalkPotentials);
         rc = bh_forces(h, s);
     }
     *n_own = s.n_local;

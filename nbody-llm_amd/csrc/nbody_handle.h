@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -62,6 +63,19 @@ inline nbody::WalkPlan walk_split_plan(size_t n_walk, bool fast_math, float thet
     while (!pinned && p.segments > 1 && size_t(p.segments) * 16 > n_bound) p.segments /= 2;
     if (n_walk == 0) p.segments = 1;
     return p;
+}
+
+// nbody_field_at(TREE): segments of the walk over a call's probes.  The field walk runs one probe per lane and never more than
+// kFieldBatch probes per launch, so K is sized for the first batch at one per lane (walk_plan's one-body rule: ~16 384 waves),
+// not from the probe total or the force walk's bodies-per-lane heuristic; pinned NBODY_BH_SPLIT as given; chosen once per call
+constexpr size_t kFieldBatch = 65536;
+inline int field_split_plan(size_t n_points, size_t n_bound) {
+    if (n_points == 0) return 1;
+    if (nbody::tuning().bh_walk_split > 0) return std::min(nbody::tuning().bh_walk_split, nbody::kMaxSplit);
+    const size_t waves = (std::min(n_points, kFieldBatch) + 63) / 64;
+    int K = int(std::min<size_t>(size_t(nbody::kMaxSplit), (16384 + waves - 1) / waves));
+    while (K > 1 && size_t(K) * 16 > n_bound) K /= 2;
+    return std::max(K, 1);
 }
 
 template <class V>   // float4 (f32 walk) or double4 (f64): the segments' partial sums
@@ -171,9 +185,11 @@ struct TreeBuildBufs {
 };
 
 // nbody_potentials / nbody_energy_world (nbody_pot.cpp): buffers of their own -- a call writes none of the force pass's
+enum { kWalkForces = 0, kWalkPotentials = 1, kWalkField = 2 };   // PotBufs::walking
 struct PotBufs {
-    bool walking = false;         // an NBODY_POTENTIAL_TREE call is under way: the force pass builds its tree as usual and its
-                                  // last phase walks for potentials (always over the node-range split, DIRECT leaf rule)
+    int walking = kWalkForces;    // kWalkPotentials: an NBODY_POTENTIAL_TREE call is under way: the force pass builds its tree as usual
+                                  // and its last phase walks for potentials (always over the node-range split, DIRECT leaf rule);
+                                  // kWalkField: nbody_field_at(TREE): the last phase leaves the tree's view in FieldBufs instead
     double* d_sum = nullptr;      // [sum_cap] S_i = sum m_j / sqrt(r2 + eps2) per own body, indexed like the own segment
     size_t sum_cap = 0;
     double* d_planes = nullptr;   // partial sums of the walk's segments / the pair kernels' slices, grow-only
@@ -201,10 +217,38 @@ struct PotBufs {
 // potentials can leave the handle walking for potentials when the next step comes
 struct PotWalkScope {
     PotBufs& p;
-    explicit PotWalkScope(PotBufs& pb) : p(pb) { p.walking = true; }
-    ~PotWalkScope() { p.walking = false; }
+    explicit PotWalkScope(PotBufs& pb, int what = kWalkPotentials) : p(pb) { p.walking = what; }
+    ~PotWalkScope() { p.walking = kWalkForces; }
     PotWalkScope(const PotWalkScope&) = delete;
     PotWalkScope& operator=(const PotWalkScope&) = delete;
+};
+
+// nbody_field_at (nbody_field.cpp): probes go through the device in batches of at most kFieldBatch, so the scratch is bounded:
+// planes of [K <= 64][batch]{ax, ay, az, S} doubles are at most 64 * 65 536 * 32 B = 128 MiB.  Grown on demand, released in
+// free_all, not cloned.
+struct FieldBufs {
+    size_t n_points = 0;          // probes of the call under way: the walk's split count K is drawn from it, once per call
+    // the tree the call's force pass built, as its last phase left it (valid until the next force pass)
+    const void* nodes = nullptr;  // NodeDev (f32) or Node64 (f64) records
+    int n_nodes = 0, K = 1;
+    const int* first = nullptr;   // the split's arrays (WalkSplitBuf)
+    const int* anc = nullptr;
+    const int* n_anc = nullptr;
+    // per-batch scratch, all for kFieldBatch probes
+    double* d_xyz = nullptr;                  // [batch][3] the caller's points
+    unsigned long long* d_keys = nullptr;     // [2][batch] Morton keys, unsorted | sorted
+    int* d_idx = nullptr;                     // [2][batch] place in the batch, unsorted | sorted
+    void* d_sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    double* d_out = nullptr;                  // [batch][3] accelerations | [batch] potentials
+    double* d_planes = nullptr;               // [K][stride] double4 partial sums, grow-only
+    size_t planes_cap = 0;                    // doubles
+    void release() {
+        for (void* p : {static_cast<void*>(d_xyz), static_cast<void*>(d_keys), static_cast<void*>(d_idx), d_sort_tmp, static_cast<void*>(d_out),
+                        static_cast<void*>(d_planes)})
+            if (p) (void)hipFree(p);
+        *this = FieldBufs{};
+    }
 };
 
 struct NbodyHandle {
@@ -306,6 +350,7 @@ struct NbodyHandle {
     double* d_energy = nullptr;
     size_t energy_blocks = 0;
     PotBufs pot;
+    FieldBufs field;
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;

@@ -21,5 +21,6 @@ int energy(NbodyHandle* h, const PotBodies& b, size_t n, double g, double* kinet
 
 namespace nbody64 {
 // S_i of the own bodies into PotBufs::d_sum at the handle's current positions (collective on a sharded world); *n = own bodies
-int potentials_device(NbodyHandle* h, int mode, size_t* n, nbody::PotBodies* bodies, double* g);
+// field = true: nbody_field_at's preparation (nbody_api.cpp potentials_device)
+int potentials_device(NbodyHandle* h, int mode, size_t* n, nbody::PotBodies* bodies, double* g, bool field = false);
 }

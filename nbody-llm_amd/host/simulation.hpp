@@ -162,6 +162,11 @@ public:
     SimulationSettingsT<F>& settings_mut() { settings_dirty_ = true; return settings_; }  // :96
     void sync() { check(nbody_sync(h_)); }
     NbodyStats stats() { NbodyStats s{}; check(nbody_stats(h_, &s)); return s; }
+    // acceleration and potential of all bodies at n caller-chosen points (f64 triples); acc [n][3] / phi [n] may be null
+    void field_at(int mode, const double* xyz, size_t n, double* acc, double* phi, uint64_t counts[2] = nullptr) {
+        push_settings();
+        check(nbody_field_at(h_, mode, xyz, n, acc, phi, counts));
+    }
     NbodyHandle* handle() { return h_; }
 
 protected:

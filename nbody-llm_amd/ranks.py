@@ -71,6 +71,13 @@ def make_sim(nb, cfg: dict, points: np.ndarray, rank: int, world: int, device: i
         tuning=sim_cfg.get("tuning"))
 
 
+def field_probes(spec: dict, rank: int) -> np.ndarray:
+    """The probes rank `rank` passes for a "field_at" schedule entry: counts[rank] points uniform in [-span, span]^3, drawn from
+    (seed, rank) alone."""
+    rng = np.random.default_rng([int(spec["seed"]), int(rank)])
+    return rng.uniform(-float(spec["span"]), float(spec["span"]), size=(int(spec["counts"][rank]), 3))
+
+
 def run_schedule(nb, sim, schedule, reattach=None, record=None):
     """Runs the schedule; returns the simulation it ended with (a "clone" entry replaces it by its clone, whose communicator
     `reattach(clone)` sets up again -- nbody_clone does not carry one over).  record: a dict that receives what the
@@ -103,6 +110,13 @@ def run_schedule(nb, sim, schedule, reattach=None, record=None):
         elif op in ("potentials", "energy_world"):   # ["potentials", "pairs" | "tree"]: collective; a refusal is recorded, not raised
             try:
                 got = sim.potentials(mode_of[item[1]]) if op == "potentials" else sim.energy_world(mode_of[item[1]])
+            except nb.NbodyError as e:
+                got = e
+            if record is not None:
+                record.setdefault(op, []).append(got)
+        elif op == "field_at":   # ["field_at", "pairs" | "tree", {"seed": s, "counts": [per-rank M], "span": L}]: collective; a refusal is recorded
+            try:
+                got = sim.field_at(field_probes(item[2], sim.rank), mode_of[item[1]])
             except nb.NbodyError as e:
                 got = e
             if record is not None:
@@ -150,9 +164,16 @@ def _rank_main(cfg: dict, rank: int, failed: list) -> None:
             else:
                 arrays[f"phi{k}"] = got[0]
                 potentials.append({"counts": list(got[1])})
+        fields = []       # per "field_at" entry: {"counts": ...} with arrays["field_acc<k>"], ["field_phi<k>"], or the refusal
+        for k, got in enumerate(record.get("field_at", [])):
+            if isinstance(got, Exception):
+                fields.append(refused(got))
+            else:
+                arrays[f"field_acc{k}"], arrays[f"field_phi{k}"] = got[0], got[1]
+                fields.append({"counts": list(got[2])})
         energies = [refused(e) if isinstance(e, Exception) else list(e) for e in record.get("energy_world", [])]
         st = sim.stats()
-        meta = {"potentials": potentials, "energy_world": energies,
+        meta = {"potentials": potentials, "energy_world": energies, "field_at": fields,
                 "rank": rank, "f64": bool(sim.f64), "count": int(len(pts)), "count_global": int(sim.count_global()), "wall_s": wall, "elapsed": sim.elapsed(),
                 "transport": sim.comm_transport(), "steps": int(st.steps), "interactions": int(st.interactions),
                 "node_visits": int(st.node_visits), "tree_nodes": int(st.tree_nodes), "local_range": list(sim.local_range())}
@@ -252,6 +273,9 @@ def run_world(cfg: dict, ranks_per_process: int = 1, timeout: float = 180.0) -> 
         for k, rec in enumerate(meta.get("potentials", [])):
             if f"phi{k}" in z:
                 rec["phi"] = z[f"phi{k}"]
+        for k, rec in enumerate(meta.get("field_at", [])):
+            if f"field_phi{k}" in z:
+                rec["acc"], rec["phi"] = z[f"field_acc{k}"], z[f"field_phi{k}"]
         results.append(meta)
     return results
 
