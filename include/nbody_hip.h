@@ -239,6 +239,33 @@ int nbody_tree_export_f64(NbodyHandle* h, double* com_mass, double* width, int32
  * every node, barnes_hut.rs:322-343).  Per node, pre-order: {min xyz, max xyz} as f32 (the renderer casts to f32 anyway,
  * :331-333; an f64 handle's boxes are computed in double first) and its depth (root = 0).  Arrays may be NULL to count. */
 int nbody_tree_export_cells(NbodyHandle* h, float* min_max6, int32_t* depth, size_t cap, size_t* n_nodes);
+/* ---- order of the Barnes-Hut force walk's multipole expansion (no reference counterpart) ------------------------
+ * NBODY_MULTIPOLE_MONOPOLE: an accepted cell acts as a point mass at its centre of mass (the reference's walk, and every
+ * walk of this library by default).  NBODY_MULTIPOLE_QUADRUPOLE: an accepted INTERNAL cell also contributes its traceless
+ * quadrupole tensor about its stored f32 centre of mass c,
+ *     Q = sum_l m_l (3 d_l d_l^T - |d_l|^2 I),   d_l = c_l - c,   over the leaves l of the cell's subtree (a leaf: Q = 0),
+ * computed on the device in f64 from the node array (either tree build) and kept as 6 x f32 per node beside the node
+ * records.  With d = c - x, q = |d|^2 + g_soft^2, inv = 1 / sqrt(q) the term of an accepted internal cell is
+ *     a += g [ M inv^3 d - inv^5 (Q d) + 2.5 inv^7 (d^T Q d) d ]      (the gradient of phi = -g [M inv + 1/2 d^T Q d inv^5]);
+ * leaves contribute their monopole term as before, under the handle's leaf rule.  The opening tests do not change, so
+ * NbodyStats.interactions and node_visits equal the monopole walk's on the same tree; the error per accepted cell falls by
+ * one order in (cell width / distance).
+ *   Accepted on Barnes-Hut, NBODY_F32, NBODY_MATH_FAST, world_size == 1 handles (either tree build, either leaf rule); every
+ * other handle, and any order but 1 or 2, gets NBODY_ERR_INVALID.  NBODY_F64 handles and worlds of several ranks (index
+ * blocks or NBODY_SHARD_SPATIAL) are deliberately out of scope: they walk monopoles.
+ *   May be set at any time between calls; it takes effect at the next force pass (nbody_update_forces, nbody_step_by,
+ * nbody_steps) and affects the force pass only: nbody_potentials(TREE) and nbody_field_at(TREE) stay monopole sums.  Setting
+ * the order back to 1 restores the monopole path exactly (the same bits as a handle that never changed).  nbody_clone
+ * carries the setting.  A handle with the device build keeps enqueueing its steps without read-back.  The walk runs one
+ * body per lane over the node-range split: bh_walk_split, bh_walk_order and bh_reduce_split are honoured, bh_walk_duo is
+ * ignored. */
+enum { NBODY_MULTIPOLE_MONOPOLE = 1,     /* default */
+       NBODY_MULTIPOLE_QUADRUPOLE = 2 };
+int nbody_set_multipole(NbodyHandle* h, int order);
+int nbody_get_multipole(const NbodyHandle* h, int* order);
+/* The quadrupoles of the tree nbody_tree_export reports, in the same node order: 6 floats per node {xx, xy, xz, yy, yz, zz};
+ * q6 may be NULL to count.  NBODY_ERR_INVALID unless the handle's last force pass walked with quadrupoles. */
+int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

@@ -56,6 +56,7 @@ PARTICLE_DTYPE64 = np.dtype(
 assert PARTICLE_DTYPE64.itemsize == 80
 F32, F64 = 0, 1
 POTENTIAL_PAIRS, POTENTIAL_TREE = 0, 1   # nbody_potentials / nbody_energy_world: the exact pair sum | the monopole sum over the tree
+MULTIPOLE_MONOPOLE, MULTIPOLE_QUADRUPOLE = 1, 2   # nbody_set_multipole: order of the Barnes-Hut force walk's expansion
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
@@ -75,6 +76,7 @@ DECLARED_SYMBOLS = [
     "nbody_comm_local_id", "nbody_comm_transport", "nbody_host_exchange_layout",
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
     "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at",
+    "nbody_set_multipole", "nbody_get_multipole", "nbody_tree_export_quadrupoles",
 ]
 
 
@@ -138,6 +140,9 @@ _sig("nbody_potentials", _i, _H, _i, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(
 _sig("nbody_energy_world", _i, _H, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_field_at", _i, _H, _i, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64))
 _sig("nbody_tree_export", _i, _H, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_set_multipole", _i, _H, _i)
+_sig("nbody_get_multipole", _i, _H, C.POINTER(_i))
+_sig("nbody_tree_export_quadrupoles", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_tree_export_cells", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_last_error", C.c_char_p, _H)
 _sig("nbody_comm_unique_id", _i, C.c_void_p)
@@ -498,6 +503,27 @@ class Simulation:
         skip = np.zeros(m, np.int32)
         self._check(export(self._h, com.ctypes.data, w.ctypes.data, skip.ctypes.data, m, C.byref(n)))
         return dict(com_mass=com, width=w, skip=skip)
+
+    @property
+    def multipole(self) -> int:
+        """Order of the Barnes-Hut force walk's expansion: MULTIPOLE_MONOPOLE (1, the default) or MULTIPOLE_QUADRUPOLE (2:
+        f32 fast-math single-shard Barnes-Hut handles only).  Takes effect at the next force pass; clone() carries it."""
+        v = C.c_int(0)
+        self._check(lib.nbody_get_multipole(self._h, C.byref(v)))
+        return int(v.value)
+
+    @multipole.setter
+    def multipole(self, order: int):
+        self._check(lib.nbody_set_multipole(self._h, int(order)))
+
+    def tree_quadrupoles(self) -> np.ndarray:
+        """[n_nodes, 6] f32 {xx, xy, xz, yy, yz, zz} of every node of the tree tree() reports (nbody_tree_export_quadrupoles):
+        only after a force pass that walked with quadrupoles."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_tree_export_quadrupoles(self._h, None, 0, C.byref(n)))
+        q = np.zeros((n.value, 6), np.float32)
+        self._check(lib.nbody_tree_export_quadrupoles(self._h, q.ctypes.data, n.value, C.byref(n)))
+        return q
 
     def tree_cells(self):
         """(min_max [n, 6] f32, depth [n] i32) of every node of the last tree, pre-order: what the reference's renderer draws."""

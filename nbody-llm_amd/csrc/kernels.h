@@ -253,6 +253,9 @@ void launch_bh_walk(hipStream_t s, const Shard& sh, const TreeDev& t, float g, f
                     int fast_math, unsigned long long* counters /* [NBODY_WALK_COUNTER_SLOTS][2]: accepted, visited */, int leaf_direct = 0,
                     const float* kick_dt = nullptr /* fuse integrate_after_force into the plane reduction */,
                     int* kicked = nullptr /* out: 1 if it was applied */);
+// the walk's plane reduction alone (what launch_bh_walk ends with; kernels_quad.hip's walk ends with it too): adds the K > 1
+// segment planes into acc, with the kick + half drift when kick_dt is given (*kicked = 1 then); K = 1: nothing to do
+void launch_bh_reduce(hipStream_t s, const Shard& sh, const TreeDev& t, int fast_math, const float* kick_dt, int* kicked);
 
 // diagnostics: f64 energies of the own segment against all segments; out = {KE, PE_pairs_sum}
 void launch_energy(hipStream_t s, const Shard& sh, int n_upper, double g_soft2, double* out2);

@@ -1073,6 +1073,31 @@ void launch_walk_split_scan(hipStream_t s, const float4* nodes, const int* range
                        first, n_anc, anc, first_given);
 }
 
+// The walk's plane reduction (n_split > 1), with the kick + half drift when kick_dt is given: *kicked = 1 when it applied them
+void launch_bh_reduce(hipStream_t s, const Shard& sh, const TreeDev& t, int fast_math, const float* kick_dt, int* kicked) {
+    if (t.n_split >= 8 && fast_math && tuning().bh_reduce_split) {   // (strict math never splits; the plain form keeps the single walk's order)
+        const dim3 rg((t.n_order + 63) / 64);
+        if (kick_dt) {
+            hipLaunchKernelGGL((k_bh_reduce_split<true, 4>), rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order, t.n_order,
+                               sh.acc, sh.own_pos(), sh.vel, *kick_dt, sh.poison, t.n_order_dev, t.store_work);
+            if (kicked) *kicked = 1;
+        } else {
+            hipLaunchKernelGGL((k_bh_reduce_split<false, 4>), rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order, t.n_order,
+                               sh.acc, sh.own_pos(), sh.vel, 0.f, sh.poison, t.n_order_dev, t.store_work);
+        }
+    } else if (t.n_split > 1) {
+        const dim3 rg((t.n_order + 255) / 256);
+        if (kick_dt) {
+            hipLaunchKernelGGL(k_bh_reduce<true>, rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order,
+                               t.n_order, sh.acc, sh.own_pos(), sh.vel, *kick_dt, sh.poison, t.n_order_dev, t.store_work);
+            if (kicked) *kicked = 1;
+        } else {
+            hipLaunchKernelGGL(k_bh_reduce<false>, rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order,
+                               t.n_order, sh.acc, sh.own_pos(), sh.vel, 0.f, sh.poison, t.n_order_dev, t.store_work);
+        }
+    }
+}
+
 void launch_bh_walk(hipStream_t s, const Shard& sh, const TreeDev& t, float g, float g_soft2, float theta2,
                     int fast_math, unsigned long long* counters, int leaf_direct, const float* kick_dt, int* kicked) {
     if (kicked) *kicked = 0;
@@ -1123,27 +1148,7 @@ void launch_bh_walk(hipStream_t s, const Shard& sh, const TreeDev& t, float g, f
         else { if (fast_math) WALK(k_bh_walk, true); else WALK(k_bh_walk, false); }
 #undef WALK
     }
-    if (t.n_split >= 8 && fast_math && tuning().bh_reduce_split) {   // (strict math never splits; the plain form keeps the single walk's order)
-        const dim3 rg((t.n_order + 63) / 64);
-        if (kick_dt) {
-            hipLaunchKernelGGL((k_bh_reduce_split<true, 4>), rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order, t.n_order,
-                               sh.acc, sh.own_pos(), sh.vel, *kick_dt, sh.poison, t.n_order_dev, t.store_work);
-            if (kicked) *kicked = 1;
-        } else {
-            hipLaunchKernelGGL((k_bh_reduce_split<false, 4>), rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order, t.n_order,
-                               sh.acc, sh.own_pos(), sh.vel, 0.f, sh.poison, t.n_order_dev, t.store_work);
-        }
-    } else if (t.n_split > 1) {
-        const dim3 rg((t.n_order + 255) / 256);
-        if (kick_dt) {
-            hipLaunchKernelGGL(k_bh_reduce<true>, rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order,
-                               t.n_order, sh.acc, sh.own_pos(), sh.vel, *kick_dt, sh.poison, t.n_order_dev, t.store_work);
-            if (kicked) *kicked = 1;
-        } else {
-            hipLaunchKernelGGL(k_bh_reduce<false>, rg, dim3(256), 0, s, t.split_planes, t.n_split, t.split_stride, t.order,
-                               t.n_order, sh.acc, sh.own_pos(), sh.vel, 0.f, sh.poison, t.n_order_dev, t.store_work);
-        }
-    }
+    launch_bh_reduce(s, sh, t, fast_math, kick_dt, kicked);
 }
 
 // ---- nbody_potentials(NBODY_POTENTIAL_TREE): S = sum m / sqrt(r2 + eps2) over the nodes the NBODY_LEAF_DIRECT force walk

@@ -462,6 +462,22 @@ int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
         HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
+    h->quad_pass = h->multipole == NBODY_MULTIPOLE_QUADRUPOLE;
+    if (h->quad_pass) {   // nbody_set_multipole(h, 2): the cells' tensors from the node array as it now stands on the device, then the walk that uses them
+        // (sized like the node array: a step without read-back knows its capacity only, and the build's node count on the device)
+        int rc = grow_dev(h, h->d_quad, h->quad_cap, h->d_node_cap, nbody::kQuadRecBytes);
+        if (rc) return rc;
+        const bool counted_on_device = td.n_order_dev != nullptr;
+        if (td.n_order > 0)
+            nbody::launch_tree_quad(h->stream, td.nodes, td.n_nodes, h->d_quad, counted_on_device ? h->tree_bufs.d_info : nullptr, td.poison);
+        ForceTimer t(h);
+        int kicked = 0;
+        nbody::launch_bh_walk_quad(h->stream, h->sh, td, h->d_quad, h->g, h->g_soft * h->g_soft, h->theta2, h->d_counters,
+                                   h->cfg.leaf_mode == NBODY_LEAF_DIRECT, h->kick_pending ? &h->kick_dt : nullptr, &kicked);
+        if (kicked) h->kick_pending = false;
+        HIP_TRY(h, hipGetLastError());
+        return NBODY_OK;
+    }
     int rc = ensure_nested_stack(h, &td);
     if (!rc) rc = setup_lds_walk(h, &td, n_tree);
     if (rc) return rc;
@@ -487,7 +503,7 @@ int bh_forces(NbodyHandle* h) {
     if (h->cfg.tree_build == NBODY_TREE_DEVICE && !h->host_tree_once) {
         // no read-back at all: single shard, the plain or the strict walk (the experimental walks want the node count)
         const bool plain_walk = h->cfg.math_mode == NBODY_MATH_STRICT || nbody::tuning().bh_walk_variant == 0;
-        if (h->async_bh && plain_walk && !nbody::tuning().bh_walk_debug) return bh_walk_device_tree_async(h);
+        if (h->async_bh && (plain_walk || h->multipole == NBODY_MULTIPOLE_QUADRUPOLE) && !nbody::tuning().bh_walk_debug) return bh_walk_device_tree_async(h);
         int rc = resolve_async(h);
         if (rc) return rc;
         bool fell_back = false;
@@ -933,7 +949,7 @@ void free_all(NbodyHandle* h) {
     nbody64::destroy(h);
     nbody::let::destroy(h);
     void* dev[] = {h->sh.pos_all, h->sh.vel, h->sh.acc, h->sh.seg_count, h->sh.escaped, h->sh.keep, h->sh.tile_state, h->sh.epoch, h->sh.inter, h->d_poison, h->d_aos,
-                   h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
+                   h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {h->h_aos, h->h_pos, h->h_counts, h->h_counters, h->h_hot_info, h->h_poison};
     for (void* p : host) if (p) (void)hipHostFree(p);
@@ -1149,6 +1165,7 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
     }
     h->g = src->g; h->g_soft = src->g_soft; h->dt = src->dt; h->theta2 = src->theta2;
     h->tune = src->tune;
+    h->multipole = src->multipole;
     std::memcpy(h->center, src->center, sizeof(h->center));
     h->width = src->width; h->bnd = src->bnd; h->bounds_set = src->bounds_set;
     h->elapsed = src->elapsed;
@@ -1605,6 +1622,67 @@ int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* sk
         if (width) width[i] = std::sqrt(r.b.w2);  // exact: w2 is the rounded square of the width
         if (skip) skip[i] = r.b.skip;
     }
+    return NBODY_OK;
+}
+
+namespace {
+// why this handle cannot walk with quadrupoles (nullptr: it can)
+const char* quadrupole_refusal(const NbodyHandle* h) {
+    if (h->cfg.method != NBODY_BARNES_HUT) return "brute-force handles sum every pair exactly: there is no expansion to raise";
+    if (h->f64 || h->cfg.dtype != NBODY_F32) return "NBODY_F64 handles walk monopoles only (quadrupoles exist for NBODY_F32)";
+    if (h->cfg.math_mode != NBODY_MATH_FAST) return "NBODY_MATH_STRICT reproduces the reference's monopole sums: quadrupoles need NBODY_MATH_FAST";
+    if (h->let || h->cfg.shard_mode != NBODY_SHARD_INDEX) return "NBODY_SHARD_SPATIAL handles walk monopoles only";
+    if (h->cfg.world_size != 1) return "sharded worlds (world_size > 1) walk monopoles only";
+    return nullptr;
+}
+}  // namespace
+
+int nbody_set_multipole(NbodyHandle* h, int order) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (order != NBODY_MULTIPOLE_MONOPOLE && order != NBODY_MULTIPOLE_QUADRUPOLE)
+        return fail(h, NBODY_ERR_INVALID, "nbody_set_multipole: order must be NBODY_MULTIPOLE_MONOPOLE (1) or NBODY_MULTIPOLE_QUADRUPOLE (2)");
+    if (order == NBODY_MULTIPOLE_QUADRUPOLE)
+        if (const char* why = quadrupole_refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_set_multipole: ") + why);
+    if (order != h->multipole && h->async_bh) {   // steps enqueued without read-back are confirmed (or replayed) under the order they were asked with
+        int rc = use_device(h);
+        if (!rc) rc = resolve_async(h);
+        if (rc) return rc;
+    }
+    h->multipole = order;   // (read by the next force pass)
+    return NBODY_OK;
+}
+
+int nbody_get_multipole(const NbodyHandle* h, int* order) {
+    if (!h || !order) return NBODY_ERR_INVALID;
+    *order = h->multipole;
+    return NBODY_OK;
+}
+
+int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "not a Barnes-Hut handle");
+    if (!h->quad_pass)
+        return fail(h, NBODY_ERR_INVALID, "nbody_tree_export_quadrupoles: the last force pass did not walk with quadrupoles (nbody_set_multipole)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    rc = resolve_async(h);
+    if (rc) return rc;
+    const size_t n = h->tree.n_nodes;
+    if (n_nodes) *n_nodes = n;
+    if (!q6) return NBODY_OK;
+    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "tree export buffer too small");
+    if (n == 0) return NBODY_OK;
+    // of the tree nbody_tree_export reports: the node array as it stands on the device (a tree call of nbody_potentials or
+    // nbody_field_at since the force pass has rebuilt it), through the kernel the force pass runs
+    rc = grow_dev(h, h->d_quad, h->quad_cap, std::max(n, h->d_node_cap), nbody::kQuadRecBytes);
+    if (rc) return rc;
+    nbody::launch_tree_quad(h->stream, h->d_nodes, int(n), h->d_quad, nullptr, nullptr);
+    HIP_TRY(h, hipGetLastError());
+    std::vector<float> rec(8 * n);
+    HIP_TRY(h, hipMemcpyAsync(rec.data(), h->d_quad, n * nbody::kQuadRecBytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 6; ++k) q6[6 * i + k] = rec[8 * i + k];
     return NBODY_OK;
 }
 

@@ -3,6 +3,7 @@
 #include "../../include/nbody_hip.h"
 #include "kernels.h"
 #include "kernels_f64.h"
+#include "kernels_quad.h"
 #include "octree_host.h"
 
 #include "transport.h"
@@ -303,6 +304,11 @@ struct NbodyHandle {
     int hot_threshold = 0;       // NodeB::hot >= this -> staged; steered so that ~hot_cap nodes qualify
     size_t hot_threshold_n = 0;  // body count the threshold was initialised for
     unsigned long long* d_counters = nullptr;  // [NBODY_WALK_COUNTER_SLOTS][2] accepted, visited (summed on read)
+    // nbody_set_multipole: order of the force walk's expansion; 2 = the cells' quadrupole tensors beside the node records
+    int multipole = NBODY_MULTIPOLE_MONOPOLE;
+    float4* d_quad = nullptr;    // [quad_cap] records of kQuadRecBytes, in node order (kernels_quad.h)
+    size_t quad_cap = 0;         // nodes
+    bool quad_pass = false;      // the last force pass walked with quadrupoles (nbody_tree_export_quadrupoles)
     unsigned long long* h_counters = nullptr;  // pinned
 
     // symmetric all-pairs kernel (fast math; single shard: n >= Tuning::sym_min_bodies)

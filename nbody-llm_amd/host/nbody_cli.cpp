@@ -7,7 +7,7 @@
 // (main.rs:124-128).  Extra flags select what the reference needs a source edit for; --dtype f64 runs the
 // reference's own precision (PointParticle<f64,3>, main.rs:52-105); --integrator host steps through the trait's generic
 // `Integrator` parameter (shared.rs:99-104) with a leapfrog on the host instead of the device's fused one; --dump FILE
-// writes the final PointParticle records.
+// writes the final PointParticle records; --multipole 2 adds the cells' quadrupole terms to the Barnes-Hut force walk.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,13 +23,13 @@ static void usage() {
                  "usage: nbody_cli [-t threads] [-n points] [--method bh|bf] [--ic disc|plummer] [--steps K]\n"
                  "                 [--math fast|strict] [--tree auto|host|device] [--leaf reference|direct]\n"
                  "                 [--dtype f32|f64] [--dt x] [--g-soft x] [--theta2 x]\n"
-                 "                 [--width w] [--seed s] [--integrator device|host] [--dump file]\n");
+                 "                 [--width w] [--seed s] [--integrator device|host] [--dump file] [--multipole 1|2]\n");
 }
 
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
-               double width, unsigned long long seed, const std::string& integrator, const std::string& dump) {
+               double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -51,6 +51,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         sim->settings_mut().dt = F(dt);
         sim->settings_mut().g_soft = F(g_soft);
         sim->settings_mut().theta2 = F(theta2);
+        if (multipole != NBODY_MULTIPOLE_MONOPOLE) sim->set_multipole(multipole);   // (refused where it does not apply: nbody_hip.h)
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
         auto start = std::chrono::steady_clock::now();
@@ -85,6 +86,7 @@ int main(int argc, char** argv) {
     std::string method = "bh", ic = "disc", math = "fast", tree = "auto", leaf = "reference", dtype = "f32", integrator = "device", dump;
     double dt = 3e-2, g_soft = 0.02, theta2 = 1.0, width = 10.0;  // main.rs:59,103-105
     unsigned long long seed = 20250523ull;
+    int multipole = NBODY_MULTIPOLE_MONOPOLE;
     bool width_set = false;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -104,9 +106,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--seed")) seed = std::strtoull(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--integrator")) integrator = next();
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
+        else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
         else { usage(); return 2; }
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole);
 }

@@ -167,6 +167,10 @@ public:
         push_settings();
         check(nbody_field_at(h_, mode, xyz, n, acc, phi, counts));
     }
+    // order of the Barnes-Hut force walk's expansion (nbody_set_multipole): NBODY_MULTIPOLE_MONOPOLE, or NBODY_MULTIPOLE_QUADRUPOLE
+    // on f32 fast-math single-shard Barnes-Hut handles; from the next force pass on
+    void set_multipole(int order) { check(nbody_set_multipole(h_, order)); }
+    int multipole() const { int order = 0; check(nbody_get_multipole(h_, &order)); return order; }
     NbodyHandle* handle() { return h_; }
 
 protected:
