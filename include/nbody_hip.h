@@ -197,11 +197,13 @@ int nbody_energy(NbodyHandle* h, double* kinetic, double* potential);
 /* Per-body potentials and the energy of a whole world (SURVEY.md section 8 row d), at the handle's CURRENT positions. */
 enum { NBODY_POTENTIAL_PAIRS = 0,   /* the exact pair sum over every body of the world: differences, terms and sums in f64 on either
                                        dtype, every unordered pair of a block once; not for NBODY_SHARD_SPATIAL handles */
-       NBODY_POTENTIAL_TREE  = 1 }; /* Barnes-Hut handles: the monopole sum over the tree, O(N log N).  A tree is built first, as
+       NBODY_POTENTIAL_TREE  = 1,   /* Barnes-Hut handles: the monopole sum over the tree, O(N log N).  A tree is built first, as
                                        nbody_update_forces builds it for that handle (after the call nbody_tree_export reports THIS
                                        tree), and walked with the force walk's opening tests under the NBODY_LEAF_DIRECT rule
                                        whatever the handle's leaf_mode (a potential without its near field is of no use to anybody);
                                        terms m / sqrt(r2 + g_soft^2) in the handle's precision, summed in f64 */
+       NBODY_POTENTIAL_TREE_QUADRUPOLE = 2 }; /* NBODY_POTENTIAL_TREE with the quadrupole term of every accepted INTERNAL cell: see
+                                       "quadrupole terms in the tree potentials" below */
 /* phi_i = -g * sum_j m_j / sqrt(|x_j - x_i|^2 + g_soft^2) for this rank's bodies, in nbody_download's order, in f64 on
  * either dtype.  Collective on a handle of a multi-rank world.  counts (may be NULL) = {terms summed, opening tests} of
  * this call on this rank (PAIRS: 0, 0).  phi may be NULL to count.  Accelerations, velocities, positions, elapsed and
@@ -231,6 +233,25 @@ int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potent
  * at them.  NBODY_SHARD_SPATIAL handles are refused (NBODY_ERR_INVALID): a rank holds neither the world's bodies nor the tree
  * around a foreign point.  Like nbody_potentials the call leaves no trace in the state, the statistics or a later step. */
 int nbody_field_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]);
+/* ---- quadrupole terms in the tree potentials: NBODY_POTENTIAL_TREE_QUADRUPOLE (no reference counterpart) --------
+ * A mode of nbody_potentials, nbody_energy_world and nbody_field_at, chosen per call and independent of nbody_set_multipole
+ * (which concerns the force pass only).  Everything that defines NBODY_POTENTIAL_TREE holds: the tree nbody_update_forces
+ * would build (nbody_tree_export reports it afterwards), the NBODY_LEAF_DIRECT opening tests whatever the handle's leaf_mode
+ * (r2 in f32 without contraction, r2 < 1e-10 skips the node whole, w2 < theta2 * r2 accepts, a leaf that fails is evaluated),
+ * sums in f64, no trace in the state, the statistics or a later step, no influence of math_mode.  In addition an accepted
+ * INTERNAL cell contributes its quadrupole term, Q being the tensor nbody_set_multipole describes below (about the stored f32
+ * centre, f64 sums, 6 x f32): with d = c - x, q = |d|^2 + g_soft^2, inv = 1 / sqrt(q),
+ *     S   += M inv + 1/2 (d^T Q d) inv^5                              (phi = -g S)
+ *     acc += g [ M inv^3 d - inv^5 (Q d) + 2.5 inv^7 (d^T Q d) d ]    (= -grad phi: the force walk's term),
+ * evaluated in f32 with IEEE sqrt and divide in u = d inv.  An accepted leaf contributes exactly NBODY_POTENTIAL_TREE's term,
+ * so at theta2 = 0 the mode gives NBODY_POTENTIAL_TREE's bits, and counts equal NBODY_POTENTIAL_TREE's on any input.
+ * nbody_field_at's contracts carry over: the same call twice gives the same bits, permuting the points permutes the results,
+ * acc-only and phi-only calls give the combined call's bits, a non-finite point gets NaN and disturbs nobody, a finite point so
+ * far away that r2 overflows gets exact zeros, n_points == 0 is valid.
+ *   Accepted on Barnes-Hut, NBODY_F32, world_size == 1, NBODY_SHARD_INDEX handles with bounds set (either math mode, either
+ * tree build, either leaf rule).  Brute-force handles, NBODY_F64 handles, handles of a multi-rank world and NBODY_SHARD_SPATIAL
+ * handles get NBODY_ERR_INVALID: they are deliberately out of scope.  After a call in this mode nbody_tree_export_quadrupoles
+ * reports the tensors the call used. */
 /* Linearised octree of the last Barnes-Hut force pass: per node {com xyz, mass}, width, skip
  * index (first node after the subtree, depth-first pre-order).  Arrays may be NULL to count. */
 int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* skip, size_t cap, size_t* n_nodes);
@@ -264,7 +285,9 @@ enum { NBODY_MULTIPOLE_MONOPOLE = 1,     /* default */
 int nbody_set_multipole(NbodyHandle* h, int order);
 int nbody_get_multipole(const NbodyHandle* h, int* order);
 /* The quadrupoles of the tree nbody_tree_export reports, in the same node order: 6 floats per node {xx, xy, xz, yy, yz, zz};
- * q6 may be NULL to count.  NBODY_ERR_INVALID unless the handle's last force pass walked with quadrupoles. */
+ * q6 may be NULL to count.  NBODY_ERR_INVALID unless the handle's last force pass walked with quadrupoles or its last tree
+ * was built by a call in NBODY_POTENTIAL_TREE_QUADRUPOLE (a monopole force pass or an NBODY_POTENTIAL_TREE call after that
+ * call: refused again). */
 int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 

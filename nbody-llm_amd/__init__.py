@@ -56,6 +56,7 @@ PARTICLE_DTYPE64 = np.dtype(
 assert PARTICLE_DTYPE64.itemsize == 80
 F32, F64 = 0, 1
 POTENTIAL_PAIRS, POTENTIAL_TREE = 0, 1   # nbody_potentials / nbody_energy_world: the exact pair sum | the monopole sum over the tree
+POTENTIAL_TREE_QUADRUPOLE = 2            # ... | POTENTIAL_TREE with the quadrupole term of every accepted internal cell
 MULTIPOLE_MONOPOLE, MULTIPOLE_QUADRUPOLE = 1, 2   # nbody_set_multipole: order of the Barnes-Hut force walk's expansion
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 
@@ -462,7 +463,8 @@ class Simulation:
 
     def potentials(self, mode: int = POTENTIAL_PAIRS) -> tuple[np.ndarray, tuple[int, int]]:
         """(phi [n] f64 of this rank's bodies in get_points() order, (terms summed, opening tests)) at the current positions;
-        collective on a multi-rank world.  POTENTIAL_TREE: Barnes-Hut handles, O(N log N)."""
+        collective on a multi-rank world.  POTENTIAL_TREE: Barnes-Hut handles, O(N log N).  POTENTIAL_TREE_QUADRUPOLE: the
+        same walk with the accepted internal cells' quadrupole terms (f32 single-shard Barnes-Hut handles)."""
         # (sized from the capacity, not from nbody_count: that call refreshes the host's view of the body count, which a chain
         # of steps enqueued without read-back sizes its launches from -- nbody_potentials itself leaves the view as it was)
         cfg = NbodyConfig()
@@ -476,7 +478,8 @@ class Simulation:
     def field_at(self, points, mode: int = POTENTIAL_PAIRS, acc: bool = True, phi: bool = True):
         """(acc [M, 3] f64 | None, phi [M] f64 | None, (terms summed, opening tests)) of ALL bodies of the world at the M
         given points (any array-like [M, 3]), at the current positions; collective on a multi-rank world.  An f32 handle
-        evaluates at the points rounded to f32."""
+        evaluates at the points rounded to f32.  mode: POTENTIAL_PAIRS, POTENTIAL_TREE, or POTENTIAL_TREE_QUADRUPOLE (the tree
+        sum with the accepted internal cells' quadrupole terms: f32 single-shard Barnes-Hut handles)."""
         xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
         m = len(xyz)
         a = np.zeros((m, 3), np.float64) if acc else None
@@ -487,7 +490,8 @@ class Simulation:
         return a, p, (int(counts[0]), int(counts[1]))
 
     def energy_world(self, mode: int = POTENTIAL_PAIRS) -> tuple[float, float]:
-        """(KE, PE) of the whole world, the same on every rank; collective."""
+        """(KE, PE) of the whole world, the same on every rank; collective.  mode as potentials(): POTENTIAL_TREE_QUADRUPOLE
+        builds PE from the potentials with quadrupole terms."""
         ke, pe = C.c_double(), C.c_double()
         self._check(lib.nbody_energy_world(self._h, int(mode), C.byref(ke), C.byref(pe)))
         return float(ke.value), float(pe.value)
@@ -518,7 +522,8 @@ class Simulation:
 
     def tree_quadrupoles(self) -> np.ndarray:
         """[n_nodes, 6] f32 {xx, xy, xz, yy, yz, zz} of every node of the tree tree() reports (nbody_tree_export_quadrupoles):
-        only after a force pass that walked with quadrupoles."""
+        only after a force pass that walked with quadrupoles, or a potentials / field_at / energy_world call in
+        POTENTIAL_TREE_QUADRUPOLE that built the tree."""
         n = C.c_size_t(0)
         self._check(lib.nbody_tree_export_quadrupoles(self._h, None, 0, C.byref(n)))
         q = np.zeros((n.value, 6), np.float32)

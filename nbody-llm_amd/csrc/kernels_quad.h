@@ -1,8 +1,10 @@
 // kernels_quad.h -- launchers behind nbody_set_multipole(h, NBODY_MULTIPOLE_QUADRUPOLE) (internal to libnbody_hip.so):
 // the cells' traceless quadrupole tensors in a side array beside the 32-byte node records, and the fast f32 walk that adds
-// their term for every accepted internal node (kernels_quad.hip).
+// their term for every accepted internal node (kernels_quad.hip); and the walks of NBODY_POTENTIAL_TREE_QUADRUPOLE, which
+// read the same side array.
 #pragma once
 #include "kernels.h"
+#include "kernels_field.h"
 
 namespace nbody {
 
@@ -20,5 +22,13 @@ void launch_tree_quad(hipStream_t s, const float4* nodes, int n_nodes, float4* q
 // opening tests, the same split planes and counter slots, then launch_bh_reduce.  Tuning::bh_walk_duo is ignored.
 void launch_bh_walk_quad(hipStream_t s, const Shard& sh, const TreeDev& t, const float4* quad, float g, float g_soft2, float theta2,
                          unsigned long long* counters, int leaf_direct, const float* kick_dt, int* kicked);
+
+// NBODY_POTENTIAL_TREE_QUADRUPOLE, nbody_potentials: launch_bh_pot_walk (kernels_pot.h) with the scalar quadrupole part
+// 1/2 (d^T Q d) inv^5 of every accepted internal node, IEEE f32 arithmetic, f64 sums; then launch_pot_reduce.
+void launch_bh_pot_walk_quad(hipStream_t s, const float4* own_pos, const TreeDev& t, const float4* quad, float g_soft2, float theta2,
+                             double* planes, size_t plane_stride, double* sum, unsigned long long* counters);
+// ... nbody_field_at: launch_bh_field_walk (kernels_field.h) with the scalar and the vector part; the caller reduces
+void launch_bh_field_walk_quad(hipStream_t s, const FieldTree& t, const float4* quad, const double* xyz, const int* idx, int n, float eps2,
+                               float theta2, int want, double4* planes, size_t stride, unsigned long long* counters);
 
 }  // namespace nbody

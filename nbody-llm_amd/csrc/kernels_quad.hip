@@ -1,4 +1,5 @@
-// kernels_quad.hip -- quadrupole moments for the fast f32 Barnes-Hut force walk (nbody_set_multipole).
+// kernels_quad.hip -- quadrupole moments for the fast f32 Barnes-Hut force walk (nbody_set_multipole) and for
+// the tree potentials and the field at caller-chosen points (NBODY_POTENTIAL_TREE_QUADRUPOLE).
 //
 // k_tree_quad fills a side array with every node's traceless quadrupole tensor about its stored f32 centre of mass c,
 //     Q = sum_l m_l (3 d_l d_l^T - |d_l|^2 I),   d_l = c_l - c,
@@ -10,6 +11,8 @@
 // (the gradient of phi = -g [M inv + 1/2 d^T Q d inv^5]).  The opening tests are the oracle's f32 expressions, untouched,
 // so {accepted, visited} equal the monopole walk's on the same tree.  The tensor is a second dependent gather, issued
 // only after the opening test has accepted an internal node: opened nodes and leaves never touch the side array.
+// k_bh_pot_walk_quad and k_bh_field_walk_quad are kernels_bh.hip's k_bh_pot_walk<double> and k_bh_field_walk with the same
+// term (and its scalar counterpart) in IEEE f32 arithmetic: see pot_quad_parts below.
 #include "kernels_quad.h"
 
 namespace nbody {
@@ -199,6 +202,161 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const QuadNode* __restri
     }
 }
 
+// ---- NBODY_POTENTIAL_TREE_QUADRUPOLE: the potential walk and the field walk with the term of every accepted internal node.
+// A leaf's term is the monopole walk's, rounded as k_bh_pot_walk / k_bh_field_walk round it.  The quadrupole parts of an
+// internal node, operation by operation (every line one f32 rounding, fmaf one; IEEE sqrt and divide; tests/quad_pot_list.py
+// counts these roundings for its bounds):
+//     q   = r2 + eps2            s = sqrtf(q)            inv = 1.0f / s
+//     u_c = d_c * inv                                                            c = x, y, z      (|u| <= 1)
+//     p_c = fmaf(Q_c0, u_0, fmaf(Q_c1, u_1, Q_c2 * u_2))                         = (Q u)_c
+//     uqu = fmaf(u_0, p_0, fmaf(u_1, p_1, u_2 * p_2))                            = u^T Q u
+//     i2  = inv * inv
+//   scalar   P   = ((0.5f * uqu) * i2) * inv                                     = 1/2 (d^T Q d) inv^5
+//     i4  = i2 * i2              w = (2.5f * uqu) * i4
+//   vector   V_c = fmaf(w, u_c, -(i4 * p_c))                                     = 2.5 inv^7 (d^T Q d) d_c - inv^5 (Q d)_c
+// The monopole parts of an internal node are k_bh_field_walk's: st = M * inv, vector d_c * (st / q).  No power of inv beyond
+// the fourth: nodes closer than 1e-5 are skipped whole, so inv <= 1e5 and i4 <= 1e20.  A probe so far away that r2 overflows
+// has inv = 0, u = 0 (d is finite) and st / q = 0 / inf = 0: every part is an exact zero, never 0 * inf.
+struct QuadParts { float P, Vx, Vy, Vz; };
+
+template <bool VEC, bool SCAL>
+__device__ __forceinline__ QuadParts pot_quad_parts(const QuadDev* __restrict__ quad, int i, float rx, float ry, float rz, float inv) {
+    const float4 Qa = quad[i].a;
+    const float2 Qb = *reinterpret_cast<const float2*>(&quad[i].b);   // {xx, xy, xz, yy}, {yz, zz}: the second gather, one 32-byte sector
+    const float ux = rx * inv, uy = ry * inv, uz = rz * inv;
+    const float px = __builtin_fmaf(Qa.x, ux, __builtin_fmaf(Qa.y, uy, Qa.z * uz));
+    const float py = __builtin_fmaf(Qa.y, ux, __builtin_fmaf(Qa.w, uy, Qb.x * uz));
+    const float pz = __builtin_fmaf(Qa.z, ux, __builtin_fmaf(Qb.x, uy, Qb.y * uz));
+    const float uqu = __builtin_fmaf(ux, px, __builtin_fmaf(uy, py, uz * pz));
+    const float i2 = inv * inv;
+    QuadParts r{0.f, 0.f, 0.f, 0.f};
+    if (SCAL) r.P = ((0.5f * uqu) * i2) * inv;
+    if (VEC) {
+        const float i4 = i2 * i2;
+        const float w = (2.5f * uqu) * i4;
+        r.Vx = __builtin_fmaf(w, ux, -(i4 * px));
+        r.Vy = __builtin_fmaf(w, uy, -(i4 * py));
+        r.Vz = __builtin_fmaf(w, uz, -(i4 * pz));
+    }
+    return r;
+}
+
+__device__ __forceinline__ int nearest_first_seg() {   // a group's segments nearest-first, as k_bh_walk dispatches them
+    const int K = gridDim.y;
+    const int diag = int((long long)blockIdx.x * K / gridDim.x);
+    const int kk = blockIdx.y;
+    return ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+}
+
+__device__ __forceinline__ void add_walk_counts(unsigned long long* __restrict__ counters, unsigned int n_acc, unsigned int n_vis) {
+    for (int off = 32; off > 0; off >>= 1) {
+        n_acc += __shfl_down(n_acc, off);
+        n_vis += __shfl_down(n_vis, off);
+    }
+    if ((threadIdx.x & 63) == 0 && counters) {   // one atomic pair per wave, over the slots k_bh_pot_walk spreads them over
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (NBODY_WALK_COUNTER_SLOTS - 1);
+        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
+        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
+    }
+}
+
+// k_bh_pot_walk<double> (kernels_bh.hip) with the scalar quadrupole part: the same tests, planes and counter slots
+__global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const QuadNode* __restrict__ nodes, const QuadDev* __restrict__ quad,
+                                                                     const int* __restrict__ order, int n_order, const float4* __restrict__ own_pos,
+                                                                     float eps2, float theta2, unsigned long long* __restrict__ counters,
+                                                                     QuadSplit split, double* __restrict__ planes, size_t plane_stride) {
+    const int t = blockIdx.x * kQuadWalkBlock + threadIdx.x;
+    if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);
+    const int seg = nearest_first_seg();
+    const int s1 = split.first[seg + 1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < n_order) {
+        const float4 p = own_pos[order[t]];
+        double sum = 0.0;
+        int i = quad_walk_entry<true>(nodes, split, seg, p, theta2);
+        while (i < s1) {
+            const float4 A = nodes[i].a;
+            const float2 B = *reinterpret_cast<const float2*>(&nodes[i].b);
+            asm volatile("" :: "v"(A.w), "v"(B.y));   // (both loads whole and ahead of the branches: see k_bh_walk)
+            const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
+            const float r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = __float_as_int(B.y);
+            const bool leaf = skip == i + 1;
+            ++n_vis;
+            if (r2 < 1e-10f) { i = skip; continue; }                  // skipped whole (how a body skips itself)
+            if (leaf) {                                                // evaluated whether it passes the test or not: k_bh_pot_walk's term
+                sum += double(A.w / __builtin_sqrtf(r2 + eps2));
+                ++n_acc;
+                i = skip;
+            } else if (B.x < theta2 * r2) {                            // accepted cell
+                const float inv = 1.0f / __builtin_sqrtf(r2 + eps2);
+                sum += double(A.w * inv);
+                sum += double(pot_quad_parts<false, true>(quad, i, rx, ry, rz, inv).P);
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        planes[size_t(seg) * plane_stride + t] = sum;
+    }
+    add_walk_counts(counters, n_acc, n_vis);
+}
+
+// k_bh_field_walk<VEC, SCAL> (kernels_bh.hip) with both quadrupole parts
+template <bool VEC, bool SCAL>
+__global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const QuadNode* __restrict__ nodes, const QuadDev* __restrict__ quad,
+                                                                       const double* __restrict__ xyz, const int* __restrict__ idx, int n,
+                                                                       float eps2, float theta2, unsigned long long* __restrict__ counters,
+                                                                       QuadSplit split, double4* __restrict__ planes, size_t plane_stride) {
+    const int t = blockIdx.x * kQuadWalkBlock + threadIdx.x;
+    const int seg = nearest_first_seg();
+    const int s1 = split.first[seg + 1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < n) {
+        const size_t c = size_t(idx[t]);
+        const float4 p = make_float4(float(xyz[3 * c]), float(xyz[3 * c + 1]), float(xyz[3 * c + 2]), 0.f);
+        const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+        double ax = 0.0, ay = 0.0, az = 0.0, sum = 0.0;
+        int i = quad_walk_entry<true>(nodes, split, seg, p, theta2);
+        while (i < s1) {
+            const float4 A = nodes[i].a;
+            const float2 B = *reinterpret_cast<const float2*>(&nodes[i].b);
+            asm volatile("" :: "v"(A.w), "v"(B.y));   // (both loads whole and ahead of the branches: see k_bh_walk)
+            const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
+            const float r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = __float_as_int(B.y);
+            const bool leaf = skip == i + 1;
+            ++n_vis;
+            if (r2 < 1e-10f) { i = skip; continue; }                  // skipped whole (a probe on a body skips it)
+            if (B.x < theta2 * r2 || leaf) {                           // accepted cell, or a leaf that failed the test
+                const float q = r2 + eps2;
+                const float inv = 1.0f / __builtin_sqrtf(q);
+                const float st = A.w * inv;
+                if (SCAL) sum += double(st);
+                if (VEC) {
+                    const float k = st / q;
+                    ax += double(rx * k); ay += double(ry * k); az += double(rz * k);
+                }
+                if (!leaf && (VEC || SCAL)) {
+                    const QuadParts qp = pot_quad_parts<VEC, SCAL>(quad, i, rx, ry, rz, inv);
+                    if (SCAL) sum += double(qp.P);
+                    if (VEC) { ax += double(qp.Vx); ay += double(qp.Vy); az += double(qp.Vz); }
+                }
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        if (VEC || SCAL) {
+            const double bad = __longlong_as_double(0x7ff8000000000000ll);
+            planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
+        }
+    }
+    add_walk_counts(counters, n_acc, n_vis);
+}
+
 void launch_tree_quad(hipStream_t s, const float4* nodes, int n_nodes, float4* quad, const int* info, const int* poison) {
     if (n_nodes <= 0) return;
     hipLaunchKernelGGL(k_tree_quad, dim3((n_nodes + kQuadBlock - 1) / kQuadBlock), dim3(kQuadBlock), 0, s, reinterpret_cast<const QuadNode*>(nodes),
@@ -220,6 +378,31 @@ void launch_bh_walk_quad(hipStream_t s, const Shard& sh, const TreeDev& t, const
     else { if (leaf_direct) WALKQ(true, kQuadWalkBlock); else WALKQ(false, kQuadWalkBlock); }
 #undef WALKQ
     launch_bh_reduce(s, sh, t, 1, kick_dt, kicked);
+}
+
+void launch_bh_pot_walk_quad(hipStream_t s, const float4* own_pos, const TreeDev& t, const float4* quad, float g_soft2, float theta2,
+                             double* planes, size_t plane_stride, double* sum, unsigned long long* counters) {
+    if (t.n_order <= 0) return;
+    QuadSplit sp{};
+    sp.n_seg = t.n_split; sp.first = t.split_first; sp.anc = t.split_anc; sp.n_anc = t.split_n_anc;
+    sp.n_order_dev = t.n_order_dev;
+    hipLaunchKernelGGL(k_bh_pot_walk_quad, dim3((t.n_order + kQuadWalkBlock - 1) / kQuadWalkBlock, t.n_split), dim3(kQuadWalkBlock), 0, s,
+                       reinterpret_cast<const QuadNode*>(t.nodes), reinterpret_cast<const QuadDev*>(quad), t.order, t.n_order, own_pos, g_soft2, theta2,
+                       counters, sp, planes, plane_stride);
+    launch_pot_reduce(s, planes, t.n_split, plane_stride, t.order, t.n_order, sum, t.n_order_dev);
+}
+
+void launch_bh_field_walk_quad(hipStream_t s, const FieldTree& t, const float4* quad, const double* xyz, const int* idx, int n, float eps2,
+                               float theta2, int want, double4* planes, size_t stride, unsigned long long* counters) {
+    if (n <= 0) return;
+    QuadSplit sp{};
+    sp.n_seg = t.K; sp.first = t.first; sp.anc = t.anc; sp.n_anc = t.n_anc;
+    const dim3 grid((n + kQuadWalkBlock - 1) / kQuadWalkBlock, t.K);
+    const QuadNode* nodes = static_cast<const QuadNode*>(t.nodes);
+    const QuadDev* qd = reinterpret_cast<const QuadDev*>(quad);
+#define FIELD_WALKQ(V, S) hipLaunchKernelGGL((k_bh_field_walk_quad<V, S>), grid, dim3(kQuadWalkBlock), 0, s, nodes, qd, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
+    if (want == 3) FIELD_WALKQ(true, true); else if (want == 1) FIELD_WALKQ(true, false); else if (want == 2) FIELD_WALKQ(false, true); else FIELD_WALKQ(false, false);
+#undef FIELD_WALKQ
 }
 
 }  // namespace nbody

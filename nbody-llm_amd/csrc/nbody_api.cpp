@@ -444,32 +444,52 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
 #endif
 }
 
+// the cells' tensors from the node array as it now stands on the device (k_tree_quad), for the walk that follows
+// (sized like the node array: a step without read-back knows its capacity only, and the build's node count on the device)
+int fill_quadrupoles(NbodyHandle* h, const nbody::TreeDev& td, bool any_nodes) {
+    int rc = grow_dev(h, h->d_quad, h->quad_cap, h->d_node_cap, nbody::kQuadRecBytes);
+    if (rc) return rc;
+    const bool counted_on_device = td.n_order_dev != nullptr;
+    if (any_nodes) nbody::launch_tree_quad(h->stream, td.nodes, td.n_nodes, h->d_quad, counted_on_device ? h->tree_bufs.d_info : nullptr, td.poison);
+    return NBODY_OK;
+}
+
 // the end of every f32 force pass: the buffers of the strict and the experimental walks, the walk over td (+ the kick and half
 // drift when a step asked for them and the plane reduction can take them along)
 int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
+    if (h->pot.walking) {   // a tree call: NBODY_POTENTIAL_TREE_QUADRUPOLE wants the tensors of the tree just built (quad_call: nbody_tree_export_quadrupoles)
+        h->quad_call = h->pot.quad;
+        if (h->pot.quad) {
+            int rc = fill_quadrupoles(h, td, td.n_nodes > 0);
+            if (rc) return rc;
+        }
+    }
     if (h->pot.walking == kWalkField) {   // nbody_field_at(NBODY_POTENTIAL_TREE): the caller walks this tree for its probes, batch by batch
         FieldBufs& f = h->field;
         f.nodes = td.nodes; f.n_nodes = td.n_nodes; f.K = td.n_split;
         f.first = td.split_first; f.anc = td.split_anc; f.n_anc = td.split_n_anc;
+        f.quad = h->pot.quad ? h->d_quad : nullptr;
+        HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
     if (h->pot.walking) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the same tree, order and split points, walked for potentials
         const size_t stride = (size_t(std::max(td.n_order, 1)) + 63) / 64 * 64;
         int rc = nbody::pot::ensure_planes(h, size_t(td.n_split) * stride);
         if (rc) return rc;
-        nbody::launch_bh_pot_walk(h->stream, h->sh.own_pos(), td, h->g_soft * h->g_soft, h->theta2, h->pot.d_planes, stride, h->pot.d_sum,
-                                  h->pot.d_counts);
+        if (h->pot.quad)
+            nbody::launch_bh_pot_walk_quad(h->stream, h->sh.own_pos(), td, h->d_quad, h->g_soft * h->g_soft, h->theta2, h->pot.d_planes, stride,
+                                           h->pot.d_sum, h->pot.d_counts);
+        else
+            nbody::launch_bh_pot_walk(h->stream, h->sh.own_pos(), td, h->g_soft * h->g_soft, h->theta2, h->pot.d_planes, stride, h->pot.d_sum,
+                                      h->pot.d_counts);
         HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
     h->quad_pass = h->multipole == NBODY_MULTIPOLE_QUADRUPOLE;
+    h->quad_call = false;
     if (h->quad_pass) {   // nbody_set_multipole(h, 2): the cells' tensors from the node array as it now stands on the device, then the walk that uses them
-        // (sized like the node array: a step without read-back knows its capacity only, and the build's node count on the device)
-        int rc = grow_dev(h, h->d_quad, h->quad_cap, h->d_node_cap, nbody::kQuadRecBytes);
+        int rc = fill_quadrupoles(h, td, td.n_order > 0);
         if (rc) return rc;
-        const bool counted_on_device = td.n_order_dev != nullptr;
-        if (td.n_order > 0)
-            nbody::launch_tree_quad(h->stream, td.nodes, td.n_nodes, h->d_quad, counted_on_device ? h->tree_bufs.d_info : nullptr, td.poison);
         ForceTimer t(h);
         int kicked = 0;
         nbody::launch_bh_walk_quad(h->stream, h->sh, td, h->d_quad, h->g, h->g_soft * h->g_soft, h->theta2, h->d_counters,
@@ -885,16 +905,30 @@ int spatial_potentials(NbodyHandle* h, size_t* n_own, nbody::PotBodies* bodies, 
 // chain enqueued without read-back sizes its launches from the bound it has, and must do so with or without this call.
 // field = true (nbody_field_at): the same preparation with nothing summed over the bodies -- PAIRS: the gathered positions and
 // live counts; TREE: the force pass up to its last phase, which leaves the tree and its split points in FieldBufs.
+// why this handle cannot take a call in NBODY_POTENTIAL_TREE_QUADRUPOLE (nullptr: it can)
+const char* tree_quadrupole_refusal(const NbodyHandle* h) {
+    if (h->cfg.method != NBODY_BARNES_HUT) return "this mode needs a Barnes-Hut handle (brute-force handles have no tree to expand)";
+    if (h->f64 || h->cfg.dtype != NBODY_F32) return "this mode is not possible on NBODY_F64 handles (the cells' tensors exist for NBODY_F32)";
+    if (h->let || h->cfg.shard_mode != NBODY_SHARD_INDEX) return "this mode is not possible on NBODY_SHARD_SPATIAL handles";
+    if (h->cfg.world_size != 1) return "this mode is not possible on handles of a multi-rank world (world_size > 1)";
+    return nullptr;
+}
+
 int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g, bool field = false) {
-    if (mode != NBODY_POTENTIAL_PAIRS && mode != NBODY_POTENTIAL_TREE) return fail(h, NBODY_ERR_INVALID, "mode must be NBODY_POTENTIAL_PAIRS or NBODY_POTENTIAL_TREE");
+    if (mode != NBODY_POTENTIAL_PAIRS && mode != NBODY_POTENTIAL_TREE && mode != NBODY_POTENTIAL_TREE_QUADRUPOLE)
+        return fail(h, NBODY_ERR_INVALID, "mode must be NBODY_POTENTIAL_PAIRS, NBODY_POTENTIAL_TREE or NBODY_POTENTIAL_TREE_QUADRUPOLE");
+    const bool quad = mode == NBODY_POTENTIAL_TREE_QUADRUPOLE;
+    if (quad)
+        if (const char* why = tree_quadrupole_refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("NBODY_POTENTIAL_TREE_QUADRUPOLE: ") + why);
+    const bool tree = mode != NBODY_POTENTIAL_PAIRS;
     if (h->let && field)
         return fail(h, NBODY_ERR_INVALID, "nbody_field_at is not possible on NBODY_SHARD_SPATIAL handles: a rank holds neither the world's bodies nor the tree around a foreign point");
     if (h->let && mode == NBODY_POTENTIAL_PAIRS)
         return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_PAIRS is not possible on NBODY_SHARD_SPATIAL handles (a rank does not hold the world's bodies): NBODY_POTENTIAL_TREE is the mode for them");
     if (h->let) return spatial_potentials(h, n_own, bodies, g);
-    if (mode == NBODY_POTENTIAL_TREE && h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_TREE needs a Barnes-Hut handle");
+    if (tree && h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "NBODY_POTENTIAL_TREE needs a Barnes-Hut handle");
     if (h->f64) return nbody64::potentials_device(h, mode, n_own, bodies, g, field);
-    if (mode == NBODY_POTENTIAL_TREE && !h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    if (tree && !h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     Shard& sh = h->sh;
     int rc = resolve_async(h);
     if (!rc) rc = exchange_wait(h);
@@ -920,7 +954,7 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
         const size_t n = h->n_local;
         if (!field) rc = nbody::pot::pairs(h, *bodies, n, total_upper(h) - n, double(h->g_soft) * double(h->g_soft));
     } else if (!rc) {
-        PotWalkScope walking(h->pot, field ? kWalkField : kWalkPotentials);
+        PotWalkScope walking(h->pot, field ? kWalkField : kWalkPotentials, quad);
         const bool on_device = h->cfg.tree_build == NBODY_TREE_DEVICE;
         bool fell_back = false;
         if (on_device) rc = bh_walk_device_tree(h, &fell_back);
@@ -1569,7 +1603,7 @@ int nbody_field_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points,
     if (n_points > (size_t(1) << 30)) return fail(h, NBODY_ERR_INVALID, "nbody_field_at: n_points must not exceed 2^30");
     if (!xyz && n_points > 0) return fail(h, NBODY_ERR_INVALID, "nbody_field_at: xyz is NULL");
     h->field.n_points = n_points;
-    h->field.nodes = nullptr; h->field.n_nodes = 0; h->field.K = 1;
+    h->field.nodes = nullptr; h->field.n_nodes = 0; h->field.K = 1; h->field.quad = nullptr;
     size_t n = 0;
     nbody::PotBodies bodies;
     double g = 0.0;
@@ -1661,8 +1695,8 @@ int nbody_get_multipole(const NbodyHandle* h, int* order) {
 int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes) {
     if (!h) return NBODY_ERR_INVALID;
     if (h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "not a Barnes-Hut handle");
-    if (!h->quad_pass)
-        return fail(h, NBODY_ERR_INVALID, "nbody_tree_export_quadrupoles: the last force pass did not walk with quadrupoles (nbody_set_multipole)");
+    if (!h->quad_pass && !h->quad_call)
+        return fail(h, NBODY_ERR_INVALID, "nbody_tree_export_quadrupoles: neither did the last force pass walk with quadrupoles (nbody_set_multipole) nor was the last tree built by a call in NBODY_POTENTIAL_TREE_QUADRUPOLE");
     int rc = use_device(h);
     if (rc) return rc;
     rc = resolve_async(h);

@@ -25,7 +25,7 @@ int ensure(NbodyHandle* h, size_t plane_doubles) {
 int run(NbodyHandle* h, int mode, const PotBodies& b, double g, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]) {
     FieldBufs& f = h->field;
     PotBufs& p = h->pot;
-    const bool tree = mode == NBODY_POTENTIAL_TREE;
+    const bool tree = mode != NBODY_POTENTIAL_PAIRS;   // (NBODY_POTENTIAL_TREE_QUADRUPOLE: f.quad is set)
     const int want = (acc ? 1 : 0) | (phi ? 2 : 0);
     double g_soft = double(h->g_soft), theta2 = double(h->theta2), center[3] = {double(h->center[0]), double(h->center[1]), double(h->center[2])};
     double width = double(h->width);
@@ -57,6 +57,7 @@ int run(NbodyHandle* h, int mode, const PotBodies& b, double g, const double* xy
             if (field_sort_probes(h->stream, f.d_xyz, n, b.f64, center, width, f.d_sort_tmp, f.sort_bytes, f.d_keys, f.d_idx, kFieldBatch, &idx) != 0)
                 return fail(h, NBODY_ERR_HIP, "nbody_field_at: rocPRIM call failed");
             if (b.f64) nbody64::launch_bh_field_walk(h->stream, ft, f.d_xyz, idx, n, g_soft * g_soft, theta2, want, planes, stride, p.d_counts);
+            else if (f.quad) launch_bh_field_walk_quad(h->stream, ft, f.quad, f.d_xyz, idx, n, h->g_soft * h->g_soft, h->theta2, want, planes, stride, p.d_counts);
             else launch_bh_field_walk(h->stream, ft, f.d_xyz, idx, n, h->g_soft * h->g_soft, h->theta2, want, planes, stride, p.d_counts);
             launch_field_reduce(h->stream, planes, K, stride, idx, n, g, d_acc, d_phi);
         } else if (want) {

@@ -191,6 +191,8 @@ struct PotBufs {
     int walking = kWalkForces;    // kWalkPotentials: an NBODY_POTENTIAL_TREE call is under way: the force pass builds its tree as usual
                                   // and its last phase walks for potentials (always over the node-range split, DIRECT leaf rule);
                                   // kWalkField: nbody_field_at(TREE): the last phase leaves the tree's view in FieldBufs instead
+    bool quad = false;            // the call under way is in NBODY_POTENTIAL_TREE_QUADRUPOLE: the last phase fills NbodyHandle::d_quad from
+                                  // the tree it has just built and walks with the quadrupole kernels (kernels_quad.hip)
     double* d_sum = nullptr;      // [sum_cap] S_i = sum m_j / sqrt(r2 + eps2) per own body, indexed like the own segment
     size_t sum_cap = 0;
     double* d_planes = nullptr;   // partial sums of the walk's segments / the pair kernels' slices, grow-only
@@ -218,8 +220,8 @@ struct PotBufs {
 // potentials can leave the handle walking for potentials when the next step comes
 struct PotWalkScope {
     PotBufs& p;
-    explicit PotWalkScope(PotBufs& pb, int what = kWalkPotentials) : p(pb) { p.walking = what; }
-    ~PotWalkScope() { p.walking = kWalkForces; }
+    explicit PotWalkScope(PotBufs& pb, int what = kWalkPotentials, bool quad = false) : p(pb) { p.walking = what; p.quad = quad; }
+    ~PotWalkScope() { p.walking = kWalkForces; p.quad = false; }
     PotWalkScope(const PotWalkScope&) = delete;
     PotWalkScope& operator=(const PotWalkScope&) = delete;
 };
@@ -232,6 +234,7 @@ struct FieldBufs {
     // the tree the call's force pass built, as its last phase left it (valid until the next force pass)
     const void* nodes = nullptr;  // NodeDev (f32) or Node64 (f64) records
     int n_nodes = 0, K = 1;
+    const float4* quad = nullptr; // NBODY_POTENTIAL_TREE_QUADRUPOLE: that tree's tensors (NbodyHandle::d_quad), else null
     const int* first = nullptr;   // the split's arrays (WalkSplitBuf)
     const int* anc = nullptr;
     const int* n_anc = nullptr;
@@ -309,6 +312,7 @@ struct NbodyHandle {
     float4* d_quad = nullptr;    // [quad_cap] records of kQuadRecBytes, in node order (kernels_quad.h)
     size_t quad_cap = 0;         // nodes
     bool quad_pass = false;      // the last force pass walked with quadrupoles (nbody_tree_export_quadrupoles)
+    bool quad_call = false;      // the last tree was built by a call in NBODY_POTENTIAL_TREE_QUADRUPOLE (accepted by that export too)
     unsigned long long* h_counters = nullptr;  // pinned
 
     // symmetric all-pairs kernel (fast math; single shard: n >= Tuning::sym_min_bodies)

@@ -162,7 +162,8 @@ public:
     SimulationSettingsT<F>& settings_mut() { settings_dirty_ = true; return settings_; }  // :96
     void sync() { check(nbody_sync(h_)); }
     NbodyStats stats() { NbodyStats s{}; check(nbody_stats(h_, &s)); return s; }
-    // acceleration and potential of all bodies at n caller-chosen points (f64 triples); acc [n][3] / phi [n] may be null
+    // acceleration and potential of all bodies at n caller-chosen points (f64 triples); acc [n][3] / phi [n] may be null;
+    // mode: NBODY_POTENTIAL_PAIRS, NBODY_POTENTIAL_TREE, or NBODY_POTENTIAL_TREE_QUADRUPOLE (f32 single-shard Barnes-Hut handles)
     void field_at(int mode, const double* xyz, size_t n, double* acc, double* phi, uint64_t counts[2] = nullptr) {
         push_settings();
         check(nbody_field_at(h_, mode, xyz, n, acc, phi, counts));
