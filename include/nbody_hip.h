@@ -289,12 +289,60 @@ int nbody_get_multipole(const NbodyHandle* h, int* order);
  * was built by a call in NBODY_POTENTIAL_TREE_QUADRUPOLE (a monopole force pass or an NBODY_POTENTIAL_TREE call after that
  * call: refused again). */
 int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes);
+/* ---- integrator: a fourth-order Hermite predictor-corrector beside the leapfrog (no reference counterpart) -------
+ * The reference's Simulation is generic over an Integrator (shared.rs:99-104) and ships the leapfrog; this is the integrator of
+ * direct-summation codes (Makino & Aarseth 1992).  It needs, per body, the jerk (the time derivative of the acceleration)
+ * beside the acceleration.  With d = x_j - x_i, w = v_j - v_i, q = |d|^2 + g_soft^2, F(x, v) is the pair sum
+ *     a_i = g sum_j m_j d / q^(3/2)          j_i = g sum_j m_j [ w - 3 (d.w)/q d ] / q^(3/2).
+ * One step of size dt from (x0, v0) with the HELD derivatives (a0, j0):
+ *     xp = x0 + v0 dt + a0 dt^2/2 + j0 dt^3/6           vp = v0 + a0 dt + j0 dt^2/2
+ *     (a1, j1) = F(xp, vp)
+ *     v1 = v0 + (a0 + a1) dt/2 + (j0 - j1) dt^2/12      x1 = x0 + (v0 + v1) dt/2 + (a0 - a1) dt^2/12
+ * then retain (Bounds::contains' rule: inclusive walls, a NaN is outside; order preserved; bounds must be set) on the
+ * CORRECTED positions, carrying pos, vel, acc and jerk together; (x1, v1, a1, j1) become the next (x0, v0, a0, j0), the acc
+ * field of nbody_download is a1, elapsed += dt, NbodyStats.steps += 1, interactions += n (n - 1) per evaluation of F.  dt
+ * may be negative.  Survivors of the retain keep their held (a0, j0): a departed body's pull leaves with the next
+ * evaluation of F, one step later than its record.
+ *   Accepted on NBODY_BRUTE_FORCE, NBODY_F64, world_size == 1 handles in either math mode.  Every other handle gets
+ * NBODY_ERR_INVALID from nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4), and so does any value but 0 or 1; NBODY_F32
+ * handles, Barnes-Hut handles and worlds of several ranks are deliberately out of scope.  NBODY_INTEGRATOR_LEAPFROG is
+ * valid on every handle.  A handle that never selects Hermite runs the leapfrog code untouched, and one that selects it and
+ * the leapfrog again without a step in between gives the bits of one that never did.
+ *   The held (a0, j0) are STALE after nbody_upload, nbody_add_point, nbody_remove_point, nbody_set_settings*, nbody_init
+ * and a change of integrator: the next step (or nbody_suggest_dt) first evaluates F at the current (x, v), one more pass
+ * that interactions counts.  nbody_update_forces on a Hermite handle evaluates F at the current state, stores a and j and
+ * makes them valid.  nbody_clone carries the integrator, the jerk and the validity (and the handle's knobs): a clone
+ * continues bit for bit like its source.  nbody_steps(k) enqueues k steps without a host synchronisation and gives the bits
+ * of k nbody_step_by calls.
+ *   NBODY_MATH_STRICT: one body per lane, partners j in ascending index order (j != i), IEEE sqrt and divide, every product
+ * and sum rounded on its own (no FMA), in this order per pair and component c:
+ *     d = x_j - x_i,  dv = v_j - v_i,  r2 = ((dx dx + dy dy) + dz dz) + g_soft^2,  rv = (dx dvx + dy dvy) + dz dvz,
+ *     w = (g m_j) / (r2 sqrt(r2)),  al = (3 rv) / r2,  a_c += d_c w,  j_c += (dv_c - al d_c) w;
+ * predictor and corrector, with dt2 = dt dt, c2 = dt2 0.5, c3 = (dt2 dt) / 6, h = dt 0.5, c12 = dt2 / 12 rounded once:
+ *     xp = ((x0 + v0 dt) + a0 c2) + j0 c3,            vp = (v0 + a0 dt) + j0 c2,
+ *     v1 = (v0 + (a0 + a1) h) + (j0 - j1) c12,        x1 = (x0 + (v0 + v1) h) + (a0 - a1) c12
+ * (tests/hermite_ref.py restates all of it in numpy, bit for bit).  NBODY_MATH_FAST: every unordered pair once, rsqrt and
+ * FMAs, partial sums added in a fixed order (the same input gives the same bits); predictor and corrector as above.  Each
+ * body's acceleration within nbody_f64's fast brute-force bound, its jerk within 1e-12 of the sum of its terms' magnitudes.
+ * The knobs bf64_min_bodies, bf64_rot and bf64_waves shape the fast pass as they do the leapfrog's; bf64_ipt: four bodies
+ * per lane unless it is 8 (its default 0 means 4 here at every size). */
+enum { NBODY_INTEGRATOR_LEAPFROG = 0, /* default: LeapFrogIntegrator (shared.rs:106-149) */
+       NBODY_INTEGRATOR_HERMITE4 = 1 };
+int nbody_set_integrator(NbodyHandle* h, int integrator);
+int nbody_get_integrator(const NbodyHandle* h, int* integrator);
+/* The held jerk j0 as [n][3] f64, in nbody_download's order; *n_out = how many.  NBODY_ERR_INVALID on a leapfrog handle and
+ * while (a0, j0) are stale (jerk3 == NULL included). */
+int nbody_download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out);
+/* eta * min_i |a_i| / |j_i| over the live bodies with |j_i| > 0 (+inf if there is none), norms sqrt((x^2 + y^2) + z^2) in
+ * f64: reproducible from the downloaded arrays.  Evaluates F first if (a0, j0) are stale.  NBODY_ERR_INVALID on a leapfrog
+ * handle and for eta <= 0. */
+int nbody_suggest_dt(NbodyHandle* h, double eta, double* dt_out);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */
 /* Per handle; the library exports no mutable globals.  Names (csrc/kernels.h struct Tuning): cross_sym, sym_packed,
  * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
- * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

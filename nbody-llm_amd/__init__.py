@@ -58,6 +58,7 @@ F32, F64 = 0, 1
 POTENTIAL_PAIRS, POTENTIAL_TREE = 0, 1   # nbody_potentials / nbody_energy_world: the exact pair sum | the monopole sum over the tree
 POTENTIAL_TREE_QUADRUPOLE = 2            # ... | POTENTIAL_TREE with the quadrupole term of every accepted internal cell
 MULTIPOLE_MONOPOLE, MULTIPOLE_QUADRUPOLE = 1, 2   # nbody_set_multipole: order of the Barnes-Hut force walk's expansion
+LEAPFROG, HERMITE4 = 0, 1   # nbody_set_integrator: the reference's leapfrog | fourth-order Hermite (f64 brute force, one rank)
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
@@ -78,6 +79,7 @@ DECLARED_SYMBOLS = [
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
     "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at",
     "nbody_set_multipole", "nbody_get_multipole", "nbody_tree_export_quadrupoles",
+    "nbody_set_integrator", "nbody_get_integrator", "nbody_download_jerk", "nbody_suggest_dt",
 ]
 
 
@@ -144,6 +146,10 @@ _sig("nbody_tree_export", _i, _H, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POI
 _sig("nbody_set_multipole", _i, _H, _i)
 _sig("nbody_get_multipole", _i, _H, C.POINTER(_i))
 _sig("nbody_tree_export_quadrupoles", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_set_integrator", _i, _H, _i)
+_sig("nbody_get_integrator", _i, _H, C.POINTER(_i))
+_sig("nbody_download_jerk", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_suggest_dt", _i, _H, C.c_double, C.POINTER(C.c_double))
 _sig("nbody_tree_export_cells", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_last_error", C.c_char_p, _H)
 _sig("nbody_comm_unique_id", _i, C.c_void_p)
@@ -519,6 +525,35 @@ class Simulation:
     @multipole.setter
     def multipole(self, order: int):
         self._check(lib.nbody_set_multipole(self._h, int(order)))
+
+    @property
+    def integrator(self) -> int:
+        """LEAPFROG (0, the default) or HERMITE4 (1: brute-force f64 handles of a one-rank world only): what step(), steps()
+        and step_by() advance the bodies with.  clone() carries it."""
+        v = C.c_int(0)
+        self._check(lib.nbody_get_integrator(self._h, C.byref(v)))
+        return int(v.value)
+
+    @integrator.setter
+    def integrator(self, which: int):
+        self._check(lib.nbody_set_integrator(self._h, int(which)))
+
+    def jerk(self) -> np.ndarray:
+        """[n, 3] f64: the jerk a Hermite handle holds, in get_points() order (nbody_download_jerk).  Refused on a leapfrog
+        handle and while the held acceleration and jerk are stale (after upload, add_point, remove_point, a settings change,
+        init() or a change of integrator, until the next step, update_forces() or suggest_dt())."""
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        n = C.c_size_t(0)
+        out = np.zeros((max(int(cfg.capacity), 1), 3), np.float64)
+        self._check(lib.nbody_download_jerk(self._h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value]
+
+    def suggest_dt(self, eta: float) -> float:
+        """eta * min_i |a_i| / |j_i| of a Hermite handle (nbody_suggest_dt): +inf when no body has a jerk."""
+        d = C.c_double(0)
+        self._check(lib.nbody_suggest_dt(self._h, float(eta), C.byref(d)))
+        return float(d.value)
 
     def tree_quadrupoles(self) -> np.ndarray:
         """[n_nodes, 6] f32 {xx, xy, xz, yy, yz, zz} of every node of the tree tree() reports (nbody_tree_export_quadrupoles):

@@ -266,14 +266,14 @@ inline int blocks4(long long waves) { return int((waves + 3) / 4); }
 }  // namespace
 
 // ----------------------------------------------------------------------------------- host side
-Bf64Plan make_bf64_plan(int n_upper, int n_remote_upper, int n_seg) {
+Bf64Plan make_bf64_plan(int n_upper, int n_remote_upper, int n_seg, int force_ipt) {
     const nbody::Tuning& t = nbody::tuning();
     Bf64Plan p;
     const int n = n_upper > 0 ? n_upper : 1;
     p.groups = (n + 63) / 64;
     p.sym = n >= std::max(2, t.bf64_min_bodies);
     if (p.sym) {
-        p.ipt = t.bf64_ipt == 4 || t.bf64_ipt == 8 ? t.bf64_ipt : (n <= kBf64SmallIptBelow ? 4 : 8);
+        p.ipt = force_ipt ? force_ipt : t.bf64_ipt == 4 || t.bf64_ipt == 8 ? t.bf64_ipt : (n <= kBf64SmallIptBelow ? 4 : 8);
         p.rot = t.bf64_rot == 1 ? 1 : 0;
         p.A = (n + 64 * p.ipt - 1) / (64 * p.ipt);
         p.sym_sets = (p.A + 1) / 2 - 1;

@@ -80,7 +80,7 @@ struct Bf64Plan {
     int n_planes = 0;
     size_t n_pad = 0;
 };
-Bf64Plan make_bf64_plan(int n_upper, int n_remote_upper, int n_seg);
+Bf64Plan make_bf64_plan(int n_upper, int n_remote_upper, int n_seg, int force_ipt = 0 /* != 0: this many bodies per lane whatever bf64_ipt says (kernels_hermite.h) */);
 uint64_t bf64_sym_pairs(const Bf64Plan& p, size_t n);   // unordered pairs of real bodies k_bf64_sym evaluates
 void launch_bf64_sym(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2);
 void launch_bf64_own(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2);      // left-over (or all) own pairs

@@ -1,0 +1,553 @@
+// kernels_hermite.hip -- the fourth-order Hermite predictor-corrector (Makino & Aarseth 1992) of brute-force NBODY_F64
+// handles: per pair the acceleration AND its time derivative, the jerk, off one shared 1/sqrt.  With d = x_j - x_i,
+// w = v_j - v_i, q = |d|^2 + g_soft^2:
+//     a_i = g sum_j m_j d / q^(3/2)          j_i = g sum_j m_j [ w - 3 (d.w)/q d ] / q^(3/2)
+//
+//   k_hm_strict     NBODY_MATH_STRICT: one body per lane, partners in ascending index order, IEEE sqrt and divide, separate
+//                   multiplies and adds in the order include/nbody_hip.h states (tests/hermite_ref.py restates it bit for bit)
+//   k_hm_sym        NBODY_MATH_FAST: kernels_bf64.hip's k_bf64_sym with velocities.  A wave keeps a RESIDENT SET of 64*IPT
+//                   bodies in registers (position, mass, velocity, six accumulators: 13 doubles a body); TRAVELLING CHUNKS of
+//                   64 bodies pass through the lanes one lane per step.  ROT = 0: the chunk's positions and velocities sit in
+//                   the wave's own LDS tile, the six travelling accumulators go through the crossbar (12 ds_bpermute_b32 a
+//                   step); ROT = 1: positions and velocities travel too (26 a step).
+//   k_hm_os         one-sided, one body per lane, partners staged 64 at a time in the wave's LDS tile.  MODE 0: every own
+//                   body (small worlds); MODE 1: the pairs k_hm_sym leaves over (the own set and, for even A, the opposite one)
+//   k_hm_reduce     the planes added in a fixed order, times g; CORRECT: the corrector and the retain's flags ride along
+//   k_hm_predict, k_hm_correct, k_hm_compact, k_hm_min_ratio   the small kernels of the step and of nbody_suggest_dt
+//
+// Fast pair arithmetic: rinv = rsqrt(q), rinv^2, rinv^3, nal = (-3 rinv^2) (d.w), u = w + nal d (the vector both sides
+// share), one mass product per side, twelve explicit FMAs (the library builds with -ffp-contract=off).  Every plane entry
+// is written exactly once per launch; there are no atomics on the planes: the same input gives the same bits.
+#include "kernels_hermite.h"
+#include "kernels.h"   // nbody::tuning()
+
+namespace nbody64 {
+
+namespace {
+
+constexpr double kPad = 1.0e100;   // zero-mass padding bodies sit far away and at rest: they exert nothing on real bodies
+
+__device__ __forceinline__ double4 pad_body() { return make_double4(kPad, kPad, kPad, 0.0); }
+__device__ __forceinline__ double4 zero4() { return make_double4(0.0, 0.0, 0.0, 0.0); }
+
+// a double through the LDS crossbar: lane l receives lane (src_x4 / 4)'s value, two 32-bit halves
+__device__ __forceinline__ double rot64(double v, int src_x4) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_ds_bpermute(src_x4, int(b));
+    const int hi = __builtin_amdgcn_ds_bpermute(src_x4, int(b >> 32));
+    return __longlong_as_double((long long)(unsigned)lo | ((long long)hi << 32));
+}
+
+// ------------------------------------------------------------------------------------------ the small kernels
+__global__ __launch_bounds__(256) void k_hm_predict(const double4* __restrict__ pos, const double4* __restrict__ vel,
+                                                    const double4* __restrict__ acc, const double4* __restrict__ jerk,
+                                                    const int* __restrict__ count, double4* __restrict__ xp, double4* __restrict__ vp,
+                                                    HermiteCoef c) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= *count) return;
+    const double4 x0 = pos[k], v0 = vel[k], a0 = acc[k], j0 = jerk[k];
+    double4 x, v;
+    x.x = ((x0.x + v0.x * c.dt) + a0.x * c.c2) + j0.x * c.c3;
+    x.y = ((x0.y + v0.y * c.dt) + a0.y * c.c2) + j0.y * c.c3;
+    x.z = ((x0.z + v0.z * c.dt) + a0.z * c.c2) + j0.z * c.c3;
+    x.w = x0.w;
+    v.x = (v0.x + a0.x * c.dt) + j0.x * c.c2;
+    v.y = (v0.y + a0.y * c.dt) + j0.y * c.c2;
+    v.z = (v0.z + a0.z * c.dt) + j0.z * c.c2;
+    v.w = 0.0;
+    xp[k] = x;
+    vp[k] = v;
+}
+
+// the corrector of body k, in place, and Bounds::contains (shared.rs:210-212: inclusive walls, a NaN is outside)
+__device__ __forceinline__ void correct_one(int k, const double4 a1, const double4 j1, double4* __restrict__ pos, double4* __restrict__ vel,
+                                            double4* __restrict__ acc, double4* __restrict__ jerk, unsigned char* __restrict__ keep,
+                                            int* __restrict__ escaped, const HermiteCoef& c, const Bounds64& b) {
+    const double4 x0 = pos[k], v0 = vel[k], a0 = acc[k], j0 = jerk[k];
+    double4 v, x;
+    v.x = (v0.x + (a0.x + a1.x) * c.h) + (j0.x - j1.x) * c.c12;
+    v.y = (v0.y + (a0.y + a1.y) * c.h) + (j0.y - j1.y) * c.c12;
+    v.z = (v0.z + (a0.z + a1.z) * c.h) + (j0.z - j1.z) * c.c12;
+    v.w = 0.0;
+    x.x = (x0.x + (v0.x + v.x) * c.h) + (a0.x - a1.x) * c.c12;
+    x.y = (x0.y + (v0.y + v.y) * c.h) + (a0.y - a1.y) * c.c12;
+    x.z = (x0.z + (v0.z + v.z) * c.h) + (a0.z - a1.z) * c.c12;
+    x.w = x0.w;
+    pos[k] = x;
+    vel[k] = v;
+    acc[k] = make_double4(a1.x, a1.y, a1.z, 0.0);
+    jerk[k] = make_double4(j1.x, j1.y, j1.z, 0.0);
+    const bool in = (x.x >= b.lo[0]) && (x.x <= b.hi[0]) && (x.y >= b.lo[1]) && (x.y <= b.hi[1]) && (x.z >= b.lo[2]) && (x.z <= b.hi[2]);
+    keep[k] = in ? 1 : 0;
+    if (!in) atomicAdd(escaped, 1);
+}
+
+__global__ __launch_bounds__(256) void k_hm_correct(const double4* __restrict__ a1, const double4* __restrict__ j1, double4* __restrict__ pos,
+                                                    double4* __restrict__ vel, double4* __restrict__ acc, double4* __restrict__ jerk,
+                                                    const int* __restrict__ count, unsigned char* __restrict__ keep,
+                                                    int* __restrict__ escaped, HermiteCoef c, Bounds64 b) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= *count) return;
+    correct_one(k, a1[k], j1[k], pos, vel, acc, jerk, keep, escaped, c, b);
+}
+
+// Vec::retain, one pass over many workgroups, in place: kernels_f64.hip's k_compact with the jerk as a fourth array
+constexpr int kTile = 1024;
+constexpr unsigned long long kAgg = 1ull, kPrefix = 2ull;
+__device__ __forceinline__ unsigned long long tile_word(int epoch, unsigned long long flag, int value) {
+    return ((unsigned long long)(unsigned)epoch << 34) | (flag << 32) | (unsigned long long)(unsigned)value;
+}
+
+__global__ __launch_bounds__(kTile) void k_hm_compact(double4* __restrict__ pos, double4* __restrict__ vel, double4* __restrict__ acc,
+                                                      double4* __restrict__ jerk, const unsigned char* __restrict__ keep,
+                                                      int* __restrict__ count, int* __restrict__ escaped,
+                                                      unsigned long long* __restrict__ tile_state, int* __restrict__ epoch_p) {
+    if (*escaped == 0) return;
+    __shared__ int wave_total[16];
+    __shared__ int excl_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x;
+    const int n = *count;
+    const int epoch = *epoch_p & 0x3fffffff;
+    const int k = tile * kTile + tid;
+    const bool kp = (k < n) && keep[k];
+    double4 p = zero4(), v = p, a = p, j = p;
+    if (kp) { p = pos[k]; v = vel[k]; a = acc[k]; j = jerk[k]; }
+    const unsigned long long m = __ballot(kp);
+    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_total[wave] = __popcll(m);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile's records are in registers before anything is published
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < 16; ++w) {
+        const int t = wave_total[w];
+        if (w < wave) before += t;
+        total += t;
+    }
+    if (tid == 0) {
+        volatile unsigned long long* st = tile_state;
+        int excl = 0;
+        if (tile == 0) {
+            st[0] = tile_word(epoch, kPrefix, total);
+        } else {
+            st[tile] = tile_word(epoch, kAgg, total);
+            __threadfence();
+            for (int t = tile - 1; t >= 0;) {
+                const unsigned long long wd = st[t];
+                if (int(wd >> 34) != epoch) continue;
+                excl += int(unsigned(wd & 0xFFFFFFFFull));
+                if (((wd >> 32) & 3ull) == kPrefix) break;
+                --t;
+            }
+            st[tile] = tile_word(epoch, kPrefix, excl + total);
+        }
+        __threadfence();
+        excl_s = excl;
+        if (tile == int(gridDim.x) - 1) {
+            *count = excl + total;
+            *escaped = 0;
+            *epoch_p = (epoch + 1) & 0x3fffffff;
+        }
+    }
+    __syncthreads();
+    if (kp) {
+        const int d = excl_s + before + in_wave;
+        pos[d] = p; vel[d] = v; acc[d] = a; jerk[d] = j;
+    }
+}
+
+// nbody_suggest_dt: min over the workgroup's live bodies of |a| / |j|, norms sqrt((x^2 + y^2) + z^2); bodies with |j| == 0
+// (or a NaN in it) do not take part.  A minimum does not depend on the order it is taken in.
+__global__ __launch_bounds__(256) void k_hm_min_ratio(const double4* __restrict__ acc, const double4* __restrict__ jerk,
+                                                      const int* __restrict__ count, double* __restrict__ out) {
+    __shared__ double part[4];
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    double r = __builtin_inf();
+    if (k < *count) {
+        const double4 a = acc[k], j = jerk[k];
+        const double na = __builtin_sqrt((a.x * a.x + a.y * a.y) + a.z * a.z);
+        const double nj = __builtin_sqrt((j.x * j.x + j.y * j.y) + j.z * j.z);
+        if (nj > 0.0) r = na / nj;
+    }
+    for (int off = 32; off > 0; off >>= 1) r = fmin(r, __shfl_down(r, off));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = fmin(fmin(part[0], part[1]), fmin(part[2], part[3]));
+}
+
+// ------------------------------------------------------------------------------------------ strict F
+constexpr int kStrictBlock = 256;
+constexpr int kStrictTile = 256;   // positions and velocities: 16 KB of LDS
+
+__global__ __launch_bounds__(kStrictBlock) void k_hm_strict(const double4* __restrict__ x, const double4* __restrict__ v,
+                                                            const int* __restrict__ count, double4* __restrict__ out_a,
+                                                            double4* __restrict__ out_j, double g, double eps2,
+                                                            unsigned long long* __restrict__ inter) {
+    __shared__ double4 tx[kStrictTile], tv[kStrictTile];
+    const int tid = threadIdx.x;
+    const int i = blockIdx.x * kStrictBlock + tid;
+    const int n = *count;
+    if (inter && blockIdx.x == 0 && tid == 0 && n > 0) atomicAdd(inter, (unsigned long long)n * (unsigned long long)(n - 1));
+    const double4 pi = (i < n) ? x[i] : zero4();
+    const double4 vi = (i < n) ? v[i] : zero4();
+    double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+    for (int t0 = 0; t0 < n; t0 += kStrictTile) {
+        const int cnt = min(kStrictTile, n - t0);
+        __syncthreads();
+        if (tid < cnt) { tx[tid] = x[t0 + tid]; tv[tid] = v[t0 + tid]; }
+        __syncthreads();
+        for (int t = 0; t < cnt; ++t) {
+            if (t0 + t == i) continue;   // the i == j pair is never formed
+            const double4 pj = tx[t], vj = tv[t];
+            const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            const double dvx = vj.x - vi.x, dvy = vj.y - vi.y, dvz = vj.z - vi.z;
+            const double r2 = ((dx * dx + dy * dy) + dz * dz) + eps2;
+            const double rv = (dx * dvx + dy * dvy) + dz * dvz;
+            const double w = (g * pj.w) / (r2 * __builtin_sqrt(r2));
+            const double al = (3.0 * rv) / r2;
+            ax += dx * w;
+            ay += dy * w;
+            az += dz * w;
+            jx += (dvx - al * dx) * w;
+            jy += (dvy - al * dy) * w;
+            jz += (dvz - al * dz) * w;
+        }
+    }
+    if (i < n) {
+        out_a[i] = make_double4(ax, ay, az, 0.0);
+        out_j[i] = make_double4(jx, jy, jz, 0.0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ fast F, symmetric
+template <int IPT>
+struct Resident {   // 13 doubles a body; fully unrolled, so every member lives in registers
+    double x[IPT], y[IPT], z[IPT], vx[IPT], vy[IPT], vz[IPT], m[IPT];
+    double ax[IPT], ay[IPT], az[IPT], jx[IPT], jy[IPT], jz[IPT];
+};
+struct Traveller {
+    double x, y, z, vx, vy, vz, m;
+    double ax, ay, az, jx, jy, jz;
+};
+
+// IPT unordered pairs (resident q, traveller), B at a time and stage by stage so that no instruction waits on its predecessor
+constexpr int kPairBatch = 4;   // (as pair_evals64 of kernels_bf64.hip; IPT = 4 stays below 256 registers: two waves per SIMD)
+template <int IPT>
+__device__ __forceinline__ void pair_evals_hm(Resident<IPT>& r, Traveller& t, double eps2) {
+#pragma unroll
+    for (int q0 = 0; q0 < IPT; q0 += kPairBatch) {
+        constexpr int B = kPairBatch;
+        double dx[B], dy[B], dz[B], wx[B], wy[B], wz[B], s[B], rv[B], sj[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+            dx[u] = t.x - r.x[q0 + u]; dy[u] = t.y - r.y[q0 + u]; dz[u] = t.z - r.z[q0 + u];
+            wx[u] = t.vx - r.vx[q0 + u]; wy[u] = t.vy - r.vy[q0 + u]; wz[u] = t.vz - r.vz[q0 + u];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) { s[u] = fma(dx[u], dx[u], eps2); rv[u] = dx[u] * wx[u]; }
+#pragma unroll
+        for (int u = 0; u < B; ++u) { s[u] = fma(dy[u], dy[u], s[u]); rv[u] = fma(dy[u], wy[u], rv[u]); }
+#pragma unroll
+        for (int u = 0; u < B; ++u) { s[u] = fma(dz[u], dz[u], s[u]); rv[u] = fma(dz[u], wz[u], rv[u]); }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) s[u] = rsqrt(s[u]);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) sj[u] = s[u] * s[u];              // rinv^2
+#pragma unroll
+        for (int u = 0; u < B; ++u) s[u] = sj[u] * s[u];              // rinv^3
+#pragma unroll
+        for (int u = 0; u < B; ++u) rv[u] = (-3.0 * sj[u]) * rv[u];   // -3 (d.w) / q
+#pragma unroll
+        for (int u = 0; u < B; ++u) {                                 // u = w - 3 (d.w)/q d: shared by both sides
+            wx[u] = fma(rv[u], dx[u], wx[u]);
+            wy[u] = fma(rv[u], dy[u], wy[u]);
+            wz[u] = fma(rv[u], dz[u], wz[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < B; ++u) sj[u] = t.m * s[u];               // what the traveller does to the resident body
+#pragma unroll
+        for (int u = 0; u < B; ++u) s[u] = r.m[q0 + u] * s[u];        // what the resident body does to the traveller
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+            r.ax[q0 + u] = fma(dx[u], sj[u], r.ax[q0 + u]);
+            r.ay[q0 + u] = fma(dy[u], sj[u], r.ay[q0 + u]);
+            r.az[q0 + u] = fma(dz[u], sj[u], r.az[q0 + u]);
+            r.jx[q0 + u] = fma(wx[u], sj[u], r.jx[q0 + u]);
+            r.jy[q0 + u] = fma(wy[u], sj[u], r.jy[q0 + u]);
+            r.jz[q0 + u] = fma(wz[u], sj[u], r.jz[q0 + u]);
+            t.ax = fma(-dx[u], s[u], t.ax);
+            t.ay = fma(-dy[u], s[u], t.ay);
+            t.az = fma(-dz[u], s[u], t.az);
+            t.jx = fma(-wx[u], s[u], t.jx);
+            t.jy = fma(-wy[u], s[u], t.jy);
+            t.jz = fma(-wz[u], s[u], t.jz);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// 4 waves per workgroup; wave gw = a * K + part is slice `part` of resident set a (k_bf64_sym's decomposition)
+template <int IPT, int ROT>
+__global__ __launch_bounds__(256) void k_hm_sym(const double4* __restrict__ pos, const double4* __restrict__ vel, const int* __restrict__ count,
+                                                int A, int K, int sym_sets, double4* __restrict__ planes, size_t plane_stride, size_t jerk_off,
+                                                double eps2) {
+    __shared__ double4 tile[ROT == 0 ? 4 : 1][2][64];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gw = blockIdx.x * 4 + wv;
+    if (gw >= A * K) return;
+    const int a = gw / K, part = gw - a * K;
+    const int n = *count;
+    const int Cn = A * IPT;                       // chunks in the padded body array
+    const int L = IPT * sym_sets;                 // chunk visits of a set
+    const int k0 = int((long long)L * part / K), k1 = int((long long)L * (part + 1) / K);
+    const int src1 = ((lane + 63) & 63) * 4;      // ds_bpermute address: take from the lane below
+    // eps2 in a VGPR (kernels_bf_sym.hip: an SGPR operand makes the compiler drain all LDS traffic every step)
+    double eps2v = eps2;
+    asm volatile("" : "+v"(eps2v));
+
+    Resident<IPT> r;
+#pragma unroll
+    for (int q = 0; q < IPT; ++q) {
+        const int i = (a * IPT + q) * 64 + lane;
+        const double4 p = (i < n) ? pos[i] : pad_body();
+        const double4 v = (i < n) ? vel[i] : zero4();
+        r.x[q] = p.x; r.y[q] = p.y; r.z[q] = p.z; r.m[q] = p.w;
+        r.vx[q] = v.x; r.vy[q] = v.y; r.vz[q] = v.z;
+        r.ax[q] = r.ay[q] = r.az[q] = r.jx[q] = r.jy[q] = r.jz[q] = 0.0;
+    }
+    auto chunk_of = [&](int k) {
+        int c = (a + 1) * IPT + k;
+        if (c >= Cn) c -= Cn;
+        return c;
+    };
+    double4 nxt_p = pad_body(), nxt_v = zero4();
+    auto load_chunk = [&](int k) {
+        const int j = chunk_of(k) * 64 + lane;
+        nxt_p = (j < n) ? pos[j] : pad_body();
+        nxt_v = (j < n) ? vel[j] : zero4();
+    };
+    if (k0 < k1) load_chunk(k0);
+    for (int k = k0; k < k1; ++k) {
+        const double4 cur_p = nxt_p, cur_v = nxt_v;
+        if (k + 1 < k1) load_chunk(k + 1);
+        Traveller t;
+        t.ax = t.ay = t.az = t.jx = t.jy = t.jz = 0.0;
+        // at step s lane l meets the body that started in lane (l - s) & 63, whose accumulators it holds
+        if (ROT == 0) {
+            tile[wv][0][lane] = cur_p;   // the wave's own tile: its LDS operations complete in program order
+            tile[wv][1][lane] = cur_v;
+            for (int s = 0; s < 64; ++s) {
+                const double4 pj = tile[wv][0][(lane - s) & 63];
+                const double4 vj = tile[wv][1][(lane - s) & 63];
+                t.x = pj.x; t.y = pj.y; t.z = pj.z; t.m = pj.w;
+                t.vx = vj.x; t.vy = vj.y; t.vz = vj.z;
+                pair_evals_hm<IPT>(r, t, eps2v);
+                t.ax = rot64(t.ax, src1); t.ay = rot64(t.ay, src1); t.az = rot64(t.az, src1);
+                t.jx = rot64(t.jx, src1); t.jy = rot64(t.jy, src1); t.jz = rot64(t.jz, src1);
+            }
+        } else {
+            t.x = cur_p.x; t.y = cur_p.y; t.z = cur_p.z; t.m = cur_p.w;
+            t.vx = cur_v.x; t.vy = cur_v.y; t.vz = cur_v.z;
+            for (int s = 0; s < 64; ++s) {
+                // the next step's body is requested before this step's arithmetic: the crossbar latency hides behind it
+                const double x1 = rot64(t.x, src1), y1 = rot64(t.y, src1), z1 = rot64(t.z, src1), m1 = rot64(t.m, src1);
+                const double vx1 = rot64(t.vx, src1), vy1 = rot64(t.vy, src1), vz1 = rot64(t.vz, src1);
+                pair_evals_hm<IPT>(r, t, eps2v);
+                t.ax = rot64(t.ax, src1); t.ay = rot64(t.ay, src1); t.az = rot64(t.az, src1);
+                t.jx = rot64(t.jx, src1); t.jy = rot64(t.jy, src1); t.jz = rot64(t.jz, src1);
+                t.x = x1; t.y = y1; t.z = z1; t.m = m1; t.vx = vx1; t.vy = vy1; t.vz = vz1;
+            }
+        }
+        const int d = k / IPT + 1;   // set distance 1..sym_sets
+        const size_t row = size_t(d - 1) * plane_stride + size_t(chunk_of(k)) * 64 + lane;
+        planes[row] = make_double4(t.ax, t.ay, t.az, 0.0);
+        planes[jerk_off + row] = make_double4(t.jx, t.jy, t.jz, 0.0);
+    }
+    double4* __restrict__ out = planes + size_t(sym_sets + part) * plane_stride;
+#pragma unroll
+    for (int q = 0; q < IPT; ++q) {
+        const size_t row = size_t(a * IPT + q) * 64 + lane;
+        out[row] = make_double4(r.ax[q], r.ay[q], r.az[q], 0.0);
+        out[jerk_off + row] = make_double4(r.jx[q], r.jy[q], r.jz[q], 0.0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------ fast F, one-sided
+// 4 waves per workgroup; wave gw = group * K + slice: bodies group*64 + lane against slice `slice` of the partner list
+// (MODE 0: every own body; MODE 1: the own set and, for even A, the opposite set).  Output: plane `slice`, rows
+// group*64 .. group*64+63 (every row, padding included).
+template <int MODE>
+__global__ __launch_bounds__(256) void k_hm_os(const double4* __restrict__ pos, const double4* __restrict__ vel, const int* __restrict__ count,
+                                               int set_size, int A, int groups, int K, double4* __restrict__ planes, size_t plane_stride,
+                                               size_t jerk_off, double eps2) {
+    __shared__ double4 tile[4][2][64];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gw = blockIdx.x * 4 + wv;
+    if (gw >= groups * K) return;
+    const int group = gw / K, slice = gw - group * K;
+    const int n = *count;
+    const int i = group * 64 + lane;
+    const double4 pi = (i < n) ? pos[i] : pad_body();
+    const double4 vi = (i < n) ? vel[i] : zero4();
+    const int a = (group * 64) / set_size;       // (MODE 1: the set of all 64 bodies of the group)
+    double eps2v = eps2;
+    asm volatile("" : "+v"(eps2v));
+    const int nw = MODE == 0 ? 1 : ((A % 2 == 0 && A > 1) ? 2 : 1);
+    int wlo[2] = {0, 0}, whi[2] = {0, 0};
+    long long R = 0;
+    for (int w = 0; w < nw; ++w) {
+        if (MODE == 0) { wlo[w] = 0; whi[w] = n; }
+        else {
+            int set = (w == 0) ? a : a + A / 2;
+            if (set >= A) set -= A;
+            wlo[w] = min(n, set * set_size);
+            whi[w] = min(n, wlo[w] + set_size);
+        }
+        R += whi[w] - wlo[w];
+    }
+    const long long r0 = R * slice / K, r1 = R * (slice + 1) / K;
+    double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+    long long first = 0;   // index of the window's first body in the concatenated partner list
+    for (int w = 0; w < nw; ++w) {
+        const int len = whi[w] - wlo[w];
+        const long long lo = max(r0, first), hi = min(r1, first + len);
+        if (lo < hi) {
+            const double4* __restrict__ ps = pos + wlo[w];   // ps[c - first]: partner c
+            const double4* __restrict__ vs = vel + wlo[w];
+            const long long self = (i >= wlo[w] && i < whi[w]) ? first + (i - wlo[w]) : -1;   // the own body's place in the list
+            double4 nxt_p = pad_body(), nxt_v = zero4();
+            if (lo + lane < hi) { nxt_p = ps[lo + lane - first]; nxt_v = vs[lo + lane - first]; }
+            for (long long c0 = lo; c0 < hi; c0 += 64) {
+                tile[wv][0][lane] = nxt_p;   // the wave's own tile: its LDS operations complete in program order
+                tile[wv][1][lane] = nxt_v;
+                if (c0 + 64 + lane < hi) { nxt_p = ps[c0 + 64 + lane - first]; nxt_v = vs[c0 + 64 + lane - first]; }
+                const int cnt = int(min(64LL, hi - c0));
+                for (int t = 0; t < cnt; ++t) {
+                    const double4 pj = tile[wv][0][t];   // wave-uniform address: an LDS broadcast
+                    const double4 vj = tile[wv][1][t];
+                    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+                    double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
+                    const double q = fma(dz, dz, fma(dy, dy, fma(dx, dx, eps2v)));
+                    const double rv = fma(dz, wz, fma(dy, wy, dx * wx));
+                    double rinv = rsqrt(q);
+                    rinv = (c0 + t == self) ? 0.0 : rinv;   // the i == j pair is never formed (with g_soft = 0 its rsqrt is inf)
+                    const double rinv2 = rinv * rinv;
+                    const double nal = (-3.0 * rinv2) * rv;
+                    const double sj = pj.w * (rinv2 * rinv);
+                    wx = fma(nal, dx, wx);
+                    wy = fma(nal, dy, wy);
+                    wz = fma(nal, dz, wz);
+                    ax = fma(dx, sj, ax);
+                    ay = fma(dy, sj, ay);
+                    az = fma(dz, sj, az);
+                    jx = fma(wx, sj, jx);
+                    jy = fma(wy, sj, jy);
+                    jz = fma(wz, sj, jz);
+                }
+            }
+        }
+        first += len;
+    }
+    const size_t row = size_t(slice) * plane_stride + i;
+    planes[row] = make_double4(ax, ay, az, 0.0);
+    planes[jerk_off + row] = make_double4(jx, jy, jz, 0.0);
+}
+
+// the planes added in a fixed order, times g; CORRECT: the corrector (k_hm_correct's arithmetic) rides along
+template <bool CORRECT>
+__global__ __launch_bounds__(256) void k_hm_reduce(const double4* __restrict__ planes, int n_planes, size_t plane_stride, size_t jerk_off,
+                                                   const int* __restrict__ count, double g, double4* __restrict__ out_a,
+                                                   double4* __restrict__ out_j, double4* __restrict__ pos, double4* __restrict__ vel,
+                                                   double4* __restrict__ acc, double4* __restrict__ jerk, unsigned char* __restrict__ keep,
+                                                   int* __restrict__ escaped, HermiteCoef c, Bounds64 b, unsigned long long* __restrict__ inter) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int n = *count;
+    if (inter && i == 0 && n > 0) atomicAdd(inter, (unsigned long long)n * (unsigned long long)(n - 1));
+    if (i >= n) return;
+    double sx = 0.0, sy = 0.0, sz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
+    for (int p = 0; p < n_planes; ++p) {
+        const double4 va = planes[size_t(p) * plane_stride + i];
+        const double4 vj = planes[jerk_off + size_t(p) * plane_stride + i];
+        sx += va.x; sy += va.y; sz += va.z;
+        tx += vj.x; ty += vj.y; tz += vj.z;
+    }
+    const double4 a1 = make_double4(g * sx, g * sy, g * sz, 0.0);
+    const double4 j1 = make_double4(g * tx, g * ty, g * tz, 0.0);
+    if (CORRECT) correct_one(i, a1, j1, pos, vel, acc, jerk, keep, escaped, c, b);
+    else { out_a[i] = a1; out_j[i] = j1; }
+}
+
+inline int blocks_for(long long n, int per) { return int((n + per - 1) / per); }
+
+}  // namespace
+
+// ----------------------------------------------------------------------------------- host side
+void launch_hm_predict(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, const HermiteCoef& c) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_hm_predict, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.count, hd.xp, hd.vp, c);
+}
+
+void launch_hm_strict(hipStream_t s, const Dev& d, const double4* x, const double4* v, double4* out_a, double4* out_j, int n_upper, double g, double eps2) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_hm_strict, dim3(blocks_for(n_upper, kStrictBlock)), dim3(kStrictBlock), 0, s, x, v, d.count, out_a, out_j, g, eps2, d.inter);
+}
+
+void launch_hm_correct(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, const HermiteCoef& c, const Bounds64& b) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_hm_correct, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, hd.a1, hd.j1, d.pos, d.vel, d.acc, hd.jerk, d.count, d.keep,
+                       d.escaped, c, b);
+}
+
+void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_hm_compact, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.count, d.escaped,
+                       d.tile_state, d.epoch);
+}
+
+int launch_hm_min_ratio(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper) {
+    if (n_upper <= 0) return 0;
+    const int blocks = blocks_for(n_upper, 256);
+    hipLaunchKernelGGL(k_hm_min_ratio, dim3(blocks), dim3(256), 0, s, d.acc, hd.jerk, d.count, hd.ratio);
+    return blocks;
+}
+
+void launch_hm_sym(hipStream_t s, const Dev& d, const Bf64Plan& p, const double4* x, const double4* v, double4* planes, double eps2) {
+    if (!p.sym || p.sym_sets <= 0) return;
+    const dim3 grid(blocks_for((long long)p.A * p.K, 4)), block(256);
+    const size_t joff = size_t(p.n_planes) * p.n_pad;
+#define HMSYM(I, R) hipLaunchKernelGGL((k_hm_sym<I, R>), grid, block, 0, s, x, v, d.count, p.A, p.K, p.sym_sets, planes, p.n_pad, joff, eps2)
+    if (p.ipt == 8) { if (p.rot) HMSYM(8, 1); else HMSYM(8, 0); }
+    else { if (p.rot) HMSYM(4, 1); else HMSYM(4, 0); }   // (hermite_ipt() yields nothing else)
+#undef HMSYM
+}
+
+void launch_hm_own(hipStream_t s, const Dev& d, const Bf64Plan& p, const double4* x, const double4* v, double4* planes, double eps2) {
+    double4* out = planes + size_t(p.sym_sets + p.K) * p.n_pad;
+    const dim3 grid(blocks_for((long long)p.groups * p.k_own, 4)), block(256);
+    const size_t joff = size_t(p.n_planes) * p.n_pad;
+    if (p.sym)
+        hipLaunchKernelGGL(k_hm_os<1>, grid, block, 0, s, x, v, d.count, 64 * p.ipt, p.A, p.groups, p.k_own, out, p.n_pad, joff, eps2);
+    else
+        hipLaunchKernelGGL(k_hm_os<0>, grid, block, 0, s, x, v, d.count, 64, 1, p.groups, p.k_own, out, p.n_pad, joff, eps2);
+}
+
+void launch_hm_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const Bf64Plan& p, const double4* planes, int n_upper, double g,
+                      double4* out_a, double4* out_j, const HermiteCoef* c, const Bounds64& b) {
+    if (n_upper <= 0) return;
+    const dim3 grid(blocks_for(n_upper, 256)), block(256);
+    const size_t joff = size_t(p.n_planes) * p.n_pad;
+    if (c)
+        hipLaunchKernelGGL(k_hm_reduce<true>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.count, g, out_a, out_j, d.pos, d.vel, d.acc,
+                           hd.jerk, d.keep, d.escaped, *c, b, d.inter);
+    else
+        hipLaunchKernelGGL(k_hm_reduce<false>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.count, g, out_a, out_j, d.pos, d.vel, d.acc,
+                           hd.jerk, d.keep, d.escaped, HermiteCoef{}, b, d.inter);
+}
+
+}  // namespace nbody64

@@ -1179,6 +1179,7 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
     rc = create_impl(&src->cfg, &h);
     if (rc) return rc;
     if (src->f64) {
+        h->tune = src->tune;   // (the knobs shape the fast passes' sums: a clone continues bit for bit like its source)
         rc = nbody64::clone_state(s, h);
         if (rc) { g_create_err = h->err; free_all(h); return rc; }
         *out = h;
@@ -1690,6 +1691,46 @@ int nbody_get_multipole(const NbodyHandle* h, int* order) {
     if (!h || !order) return NBODY_ERR_INVALID;
     *order = h->multipole;
     return NBODY_OK;
+}
+
+// ---- nbody_set_integrator: the fourth-order Hermite predictor-corrector of nbody_f64.cpp / kernels_hermite.hip
+int nbody_set_integrator(NbodyHandle* h, int integrator) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (integrator != NBODY_INTEGRATOR_LEAPFROG && integrator != NBODY_INTEGRATOR_HERMITE4)
+        return fail(h, NBODY_ERR_INVALID, "nbody_set_integrator: integrator must be NBODY_INTEGRATOR_LEAPFROG (0) or NBODY_INTEGRATOR_HERMITE4 (1)");
+    if (integrator == NBODY_INTEGRATOR_HERMITE4) {
+        const char* why = h->cfg.method != NBODY_BRUTE_FORCE ? "Barnes-Hut handles step with the leapfrog only"
+                        : !h->f64                           ? "NBODY_F32 handles step with the leapfrog only"
+                        : h->cfg.world_size != 1            ? "handles of a multi-rank world step with the leapfrog only"
+                                                            : nullptr;
+        if (why) return fail(h, NBODY_ERR_INVALID, std::string("nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): ") + why + " (brute-force NBODY_F64 handles with world_size == 1 take it)");
+    }
+    if (!h->f64) return NBODY_OK;   // the leapfrog, which is all such a handle runs
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody64::set_integrator(h, integrator);
+}
+
+int nbody_get_integrator(const NbodyHandle* h, int* integrator) {
+    if (!h || !integrator) return NBODY_ERR_INVALID;
+    *integrator = h->f64 ? nbody64::get_integrator(h) : NBODY_INTEGRATOR_LEAPFROG;
+    return NBODY_OK;
+}
+
+int nbody_download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (!h->f64) return fail(h, NBODY_ERR_INVALID, "nbody_download_jerk: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody64::download_jerk(h, jerk3, cap, n_out);
+}
+
+int nbody_suggest_dt(NbodyHandle* h, double eta, double* dt_out) {
+    if (!h || !dt_out) return h ? fail(h, NBODY_ERR_INVALID, "null argument") : NBODY_ERR_INVALID;
+    if (!h->f64) return fail(h, NBODY_ERR_INVALID, "nbody_suggest_dt: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody64::suggest_dt(h, eta, dt_out);
 }
 
 int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes) {

@@ -8,6 +8,7 @@
 // boundary as 80-byte records.
 #include "nbody_f64.h"
 #include "kernels_f64.h"
+#include "kernels_hermite.h"
 #include "nbody_pot.h"
 
 #include <algorithm>
@@ -60,6 +61,16 @@ struct State {
     uint64_t bf_sym_pairs = 0;
     double4* d_planes = nullptr;
     size_t planes_cap = 0;        // double4 entries
+    // nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): the held jerk, the predicted state and the pair-jerk planes
+    // (kernels_hermite.h); acc holds the held a0.  hm_valid: (acc, jerk) are F at the current (pos, vel)
+    int integrator = NBODY_INTEGRATOR_LEAPFROG;
+    bool hm_valid = false;
+    HermiteDev hm;
+    Bf64Plan hm_plan;
+    long long hm_plan_key[5] = {-1, -1, -1, -1, -1};
+    uint64_t hm_sym_pairs = 0;
+    double4* d_hm_planes = nullptr;
+    size_t hm_planes_cap = 0;     // double4 entries
 };
 
 namespace {
@@ -142,6 +153,98 @@ int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
     if (s.kick_dt) s.kicked = 1;
     HIP_TRY(h, hipGetLastError());
     if (timed_this) h->stats.force_kernel_interactions += timed;
+    return NBODY_OK;
+}
+
+// ---- the fourth-order Hermite step (kernels_hermite.hip)
+int ensure_hermite(NbodyHandle* h, State& s) {
+    if (s.hm.jerk) return NBODY_OK;
+    const size_t cap = size_t(s.d.cap);
+    double4** arr[] = {&s.hm.jerk, &s.hm.xp, &s.hm.vp, &s.hm.a1, &s.hm.j1};
+    for (double4** a : arr) {
+        HIP_TRY(h, hipMalloc(a, cap * sizeof(double4)));
+        HIP_TRY(h, hipMemsetAsync(*a, 0, cap * sizeof(double4), h->stream));
+    }
+    HIP_TRY(h, hipMalloc(&s.hm.ratio, ((cap + 255) / 256) * sizeof(double)));
+    return NBODY_OK;
+}
+
+int ensure_hm_plan(NbodyHandle* h, State& s) {
+    const nbody::Tuning& t = nbody::tuning();
+    const long long key[5] = {(long long)s.n_local, t.bf64_min_bodies, t.bf64_ipt, t.bf64_rot, t.bf64_waves};
+    if (std::equal(key, key + 5, s.hm_plan_key)) return NBODY_OK;
+    const Bf64Plan plan = make_bf64_plan(int(s.n_local), 0, 1, hermite_ipt(t.bf64_ipt));
+    const size_t need = 2 * size_t(plan.n_planes) * plan.n_pad;                // accelerations, then jerks
+    if (need > s.hm_planes_cap) {
+        if (s.d_hm_planes) (void)hipFree(s.d_hm_planes);
+        s.d_hm_planes = nullptr; s.hm_planes_cap = 0;
+        std::fill(s.hm_plan_key, s.hm_plan_key + 5, -1LL);
+        HIP_TRY(h, hipMalloc(&s.d_hm_planes, need * sizeof(double4)));
+        s.hm_planes_cap = need;
+    }
+    s.hm_plan = plan;
+    s.hm_sym_pairs = bf64_sym_pairs(plan, s.n_local);
+    std::copy(key, key + 5, s.hm_plan_key);
+    return NBODY_OK;
+}
+
+// (a, j) = F(x, v).  c == nullptr: into (out_a, out_j); else the corrector follows (in place on pos / vel / acc / jerk, with
+// the retain's flags): a kernel of its own in strict math, inside the plane reduce in fast math.  Enqueues only.
+int hm_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, double4* out_a, double4* out_j, const HermiteCoef* c) {
+    if (s.n_local == 0) return NBODY_OK;
+    const double eps2 = s.g_soft * s.g_soft;
+    const uint64_t all = uint64_t(s.n_local) * uint64_t(s.n_local - 1);
+    if (h->cfg.math_mode != NBODY_MATH_FAST) {
+        {
+            ForceTimer t(h);
+            launch_hm_strict(h->stream, s.d, x, v, c ? s.hm.a1 : out_a, c ? s.hm.j1 : out_j, int(s.n_local), s.g, eps2);
+        }
+        if (h->timed_this) h->stats.force_kernel_interactions += all;
+        if (c) launch_hm_correct(h->stream, s.d, s.hm, int(s.n_local), *c, s.bnd);
+        HIP_TRY(h, hipGetLastError());
+        return NBODY_OK;
+    }
+    int rc = ensure_hm_plan(h, s);
+    if (rc) return rc;
+    const Bf64Plan& p = s.hm_plan;
+    uint64_t timed = 0;
+    if (p.sym && p.sym_sets > 0) {
+        {
+            ForceTimer t(h);
+            launch_hm_sym(h->stream, s.d, p, x, v, s.d_hm_planes, eps2);
+        }
+        timed = 2 * s.hm_sym_pairs;
+        launch_hm_own(h->stream, s.d, p, x, v, s.d_hm_planes, eps2);
+    } else {   // (with one or two resident sets the left-over pairs are all of them)
+        ForceTimer t(h);
+        launch_hm_own(h->stream, s.d, p, x, v, s.d_hm_planes, eps2);
+        timed = all;
+    }
+    if (h->timed_this) h->stats.force_kernel_interactions += timed;
+    launch_hm_reduce(h->stream, s.d, s.hm, p, s.d_hm_planes, int(s.n_local), s.g, out_a, out_j, c, s.bnd);
+    HIP_TRY(h, hipGetLastError());
+    return NBODY_OK;
+}
+
+int hm_refresh(NbodyHandle* h, State& s) {   // the held (a0, j0) at the current (x, v)
+    int rc = hm_eval(h, s, s.d.pos, s.d.vel, s.d.acc, s.hm.jerk, nullptr);
+    if (!rc) s.hm_valid = true;
+    return rc;
+}
+
+int hm_step(NbodyHandle* h, State& s, double dt) {
+    if (!s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    int rc = s.hm_valid ? NBODY_OK : hm_refresh(h, s);
+    if (rc) return rc;
+    const HermiteCoef c = hermite_coef(dt);
+    launch_hm_predict(h->stream, s.d, s.hm, int(s.n_local), c);
+    rc = hm_eval(h, s, s.hm.xp, s.hm.vp, nullptr, nullptr, &c);   // + corrector
+    if (rc) return rc;
+    launch_hm_compact(h->stream, s.d, s.hm, int(s.n_local));     // retain, on the corrected positions
+    s.count_dirty = true;
+    HIP_TRY(h, hipGetLastError());
+    s.elapsed += dt;
+    h->stats.steps += 1;
     return NBODY_OK;
 }
 
@@ -345,6 +448,7 @@ int exchange(NbodyHandle* h, State& s) {
 }
 
 int step_impl(NbodyHandle* h, State& s, double dt) {
+    if (s.integrator == NBODY_INTEGRATOR_HERMITE4) return hm_step(h, s, dt);
     if (!s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     launch_drift_half(h->stream, s.d, int(s.n_local), dt, s.bnd);   // integrate_pre_force
     launch_compact(h->stream, s.d, int(s.n_local));                 // retain
@@ -412,7 +516,8 @@ void destroy(NbodyHandle* h) {
     if (!s) return;
     s->tree.clear();
     void* dev[] = {s->d.pos_all, s->d.vel, s->d.acc, s->d.seg_count, s->d.escaped, s->d.keep, s->d.tile_state, s->d.epoch, s->d.inter,
-                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes};
+                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes,
+                   s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->d_hm_planes};
     for (void* p : dev) if (p) (void)hipFree(p);
     void* host[] = {s->h_count, s->h_aos, s->h_pos};
     for (void* p : host) if (p) (void)hipHostFree(p);
@@ -434,6 +539,13 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
     HIP_TRY(dst, hipMemcpyAsync(b.d.acc, a.d.acc, cap * sizeof(double4), hipMemcpyDeviceToDevice, dst->stream));
     HIP_TRY(dst, hipMemcpyAsync(b.d.seg_count, a.d.seg_count, sizeof(int) * a.d.n_seg, hipMemcpyDeviceToDevice, dst->stream));
     b.count_upper = a.count_upper;
+    if (a.integrator == NBODY_INTEGRATOR_HERMITE4) {   // + the held jerk and whether it is valid: the clone steps like its source
+        rc = ensure_hermite(dst, b);
+        if (rc) return rc;
+        HIP_TRY(dst, hipMemcpyAsync(b.hm.jerk, a.hm.jerk, cap * sizeof(double4), hipMemcpyDeviceToDevice, dst->stream));
+        b.integrator = a.integrator;
+        b.hm_valid = a.hm_valid;
+    }
     HIP_TRY(dst, hipStreamSynchronize(dst->stream));
     b.g = a.g; b.g_soft = a.g_soft; b.dt = a.dt; b.theta2 = a.theta2;
     std::memcpy(b.center, a.center, sizeof(b.center));
@@ -470,6 +582,7 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
     HIP_TRY(h, hipMemcpyAsync(s.d.seg_count, s.h_count, sizeof(int) * G, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     s.count_dirty = false;
+    s.hm_valid = false;
     return NBODY_OK;
 }
 
@@ -526,6 +639,7 @@ int add_point(NbodyHandle* h, const void* particle) {   // Vec::push (brute_forc
     launch_aos_to_soa(h->stream, s.d_aos, 10, 1, s.d, s.n_local);
     HIP_TRY(h, hipGetLastError());
     s.n_local += 1;
+    s.hm_valid = false;
     return push_count(h, s);
 }
 
@@ -542,12 +656,14 @@ int remove_point(NbodyHandle* h, size_t index) {   // Vec::swap_remove (brute_fo
         HIP_TRY(h, hipMemcpyAsync(s.d.acc + index, s.d.acc + last, sizeof(double4), hipMemcpyDeviceToDevice, h->stream));
     }
     s.n_local = last;
+    s.hm_valid = false;
     return push_count(h, s);
 }
 
 int set_settings(NbodyHandle* h, double g, double g_soft, double dt, double theta2) {
     State& s = *h->f64;
     s.g = g; s.g_soft = g_soft; s.dt = dt; s.theta2 = theta2;
+    s.hm_valid = false;
     return NBODY_OK;
 }
 
@@ -581,6 +697,7 @@ void get_bounds(const NbodyHandle* h, double center[3], double* width) {
 
 int init(NbodyHandle* h) {
     h->f64->elapsed = 0.0;
+    h->f64->hm_valid = false;
     return NBODY_OK;
 }
 
@@ -598,9 +715,61 @@ int steps(NbodyHandle* h, int k) {
 int update_forces(NbodyHandle* h) {
     State& s = *h->f64;
     if (h->cfg.method == NBODY_BARNES_HUT && !s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    if (s.integrator == NBODY_INTEGRATOR_HERMITE4) return hm_refresh(h, s);
     int rc = exchange(h, s);
     if (rc) return rc;
     return forces(h, s);
+}
+
+int set_integrator(NbodyHandle* h, int integrator) {   // (nbody_api.cpp has checked that the handle may run it)
+    State& s = *h->f64;
+    if (integrator == s.integrator) return NBODY_OK;
+    if (integrator == NBODY_INTEGRATOR_HERMITE4) {
+        int rc = ensure_hermite(h, s);
+        if (rc) return rc;
+    }
+    s.integrator = integrator;
+    s.hm_valid = false;
+    return NBODY_OK;
+}
+
+int get_integrator(const NbodyHandle* h) { return h->f64->integrator; }
+
+int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out) {
+    State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_download_jerk: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    if (!s.hm_valid) return fail(h, NBODY_ERR_INVALID, "nbody_download_jerk: the held acceleration and jerk are stale (the next step or nbody_update_forces evaluates them)");
+    int rc = sync_count(h, s);
+    if (rc) return rc;
+    const size_t n = s.n_local;
+    if (n_out) *n_out = n;
+    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "download buffer too small");
+    if (n == 0) return NBODY_OK;
+    if (!jerk3) return fail(h, NBODY_ERR_INVALID, "null buffer");
+    std::vector<double> tmp(4 * n);
+    HIP_TRY(h, hipMemcpyAsync(tmp.data(), s.hm.jerk, n * sizeof(double4), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < n; ++k) { jerk3[3 * k] = tmp[4 * k]; jerk3[3 * k + 1] = tmp[4 * k + 1]; jerk3[3 * k + 2] = tmp[4 * k + 2]; }
+    return NBODY_OK;
+}
+
+int suggest_dt(NbodyHandle* h, double eta, double* dt_out) {
+    State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_suggest_dt: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    if (!(eta > 0.0)) return fail(h, NBODY_ERR_INVALID, "nbody_suggest_dt: eta must be > 0");
+    int rc = s.hm_valid ? NBODY_OK : hm_refresh(h, s);
+    if (rc) return rc;
+    double lowest = HUGE_VAL;
+    const int blocks = launch_hm_min_ratio(h->stream, s.d, s.hm, int(s.n_local));
+    if (blocks > 0) {
+        HIP_TRY(h, hipGetLastError());
+        std::vector<double> part(static_cast<size_t>(blocks));
+        HIP_TRY(h, hipMemcpyAsync(part.data(), s.hm.ratio, size_t(blocks) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (double r : part) lowest = std::min(lowest, r);
+    }
+    *dt_out = eta * lowest;
+    return NBODY_OK;
 }
 
 double elapsed(const NbodyHandle* h) { return h->f64->elapsed; }

@@ -25,6 +25,11 @@ double elapsed(const NbodyHandle* h);
 int stats(NbodyHandle* h, NbodyStats* out);
 int reset_stats(NbodyHandle* h);
 int energy(NbodyHandle* h, double* kinetic, double* potential);
+// the fourth-order Hermite integrator (brute force, one rank; include/nbody_hip.h "integrator")
+int set_integrator(NbodyHandle* h, int integrator);
+int get_integrator(const NbodyHandle* h);
+int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out);
+int suggest_dt(NbodyHandle* h, double eta, double* dt_out);
 int tree_export(NbodyHandle* h, double* com_mass, double* width, int32_t* skip, size_t cap, size_t* n_nodes);
 
 }  // namespace nbody64

@@ -6,7 +6,8 @@
 //     Performance: <x> steps/second
 // (main.rs:124-128).  Extra flags select what the reference needs a source edit for; --dtype f64 runs the
 // reference's own precision (PointParticle<f64,3>, main.rs:52-105); --integrator host steps through the trait's generic
-// `Integrator` parameter (shared.rs:99-104) with a leapfrog on the host instead of the device's fused one; --dump FILE
+// `Integrator` parameter (shared.rs:99-104) with a leapfrog on the host instead of the device's fused one, --integrator
+// hermite runs the device's fourth-order Hermite step (--method bf --dtype f64 only; leapfrog = device, the default); --dump FILE
 // writes the final PointParticle records; --multipole 2 adds the cells' quadrupole terms to the Barnes-Hut force walk.
 #include <chrono>
 #include <cstdio>
@@ -23,7 +24,7 @@ static void usage() {
                  "usage: nbody_cli [-t threads] [-n points] [--method bh|bf] [--ic disc|plummer] [--steps K]\n"
                  "                 [--math fast|strict] [--tree auto|host|device] [--leaf reference|direct]\n"
                  "                 [--dtype f32|f64] [--dt x] [--g-soft x] [--theta2 x]\n"
-                 "                 [--width w] [--seed s] [--integrator device|host] [--dump file] [--multipole 1|2]\n");
+                 "                 [--width w] [--seed s] [--integrator device|leapfrog|host|hermite] [--dump file] [--multipole 1|2]\n");
 }
 
 template <class F>
@@ -52,6 +53,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         sim->settings_mut().g_soft = F(g_soft);
         sim->settings_mut().theta2 = F(theta2);
         if (multipole != NBODY_MULTIPOLE_MONOPOLE) sim->set_multipole(multipole);   // (refused where it does not apply: nbody_hip.h)
+        if (integrator == "hermite") sim->set_integrator(NBODY_INTEGRATOR_HERMITE4);
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
         auto start = std::chrono::steady_clock::now();
@@ -108,6 +110,11 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
         else { usage(); return 2; }
+    }
+    if (integrator != "device" && integrator != "leapfrog" && integrator != "host" && integrator != "hermite") { usage(); return 2; }
+    if (integrator == "hermite" && (dtype != "f64" || method != "bf")) {
+        std::fprintf(stderr, "--integrator hermite needs --dtype f64 and --method bf\n");
+        return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
     if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole);

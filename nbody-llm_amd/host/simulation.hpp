@@ -172,6 +172,10 @@ public:
     // on f32 fast-math single-shard Barnes-Hut handles; from the next force pass on
     void set_multipole(int order) { check(nbody_set_multipole(h_, order)); }
     int multipole() const { int order = 0; check(nbody_get_multipole(h_, &order)); return order; }
+    // what step(), steps() and step_by() advance the bodies with (nbody_set_integrator): NBODY_INTEGRATOR_LEAPFROG, or
+    // NBODY_INTEGRATOR_HERMITE4 on brute-force f64 handles of a one-rank world
+    void set_integrator(int integrator) { check(nbody_set_integrator(h_, integrator)); }
+    int integrator() const { int which = 0; check(nbody_get_integrator(h_, &which)); return which; }
     NbodyHandle* handle() { return h_; }
 
 protected:
