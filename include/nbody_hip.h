@@ -337,6 +337,54 @@ int nbody_download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out
  * f64: reproducible from the downloaded arrays.  Evaluates F first if (a0, j0) are stale.  NBODY_ERR_INVALID on a leapfrog
  * handle and for eta <= 0. */
 int nbody_suggest_dt(NbodyHandle* h, double eta, double* dt_out);
+/* ---- block steps: individual time steps of a Hermite handle, quantised to powers of two (Makino & Aarseth 1992; no
+ * reference counterpart) --------
+ * nbody_set_block_steps(h, eta, max_level) with eta > 0 and 1 <= max_level <= 20 switches them on, (0, 0) off (the default).
+ * They are a setting of a Hermite handle: accepted exactly where NBODY_INTEGRATOR_HERMITE4 is and only while it is selected
+ * (a leapfrog handle, every handle that refuses HERMITE4 and every other (eta, max_level) get NBODY_ERR_INVALID, from all
+ * five calls below); nbody_set_integrator(NBODY_INTEGRATOR_LEAPFROG) switches them off.  A handle that never switches them
+ * on runs the shared-step code untouched, and one that switches them on and off again without a step in between gives the
+ * bits of one that never did.
+ *   One nbody_step_by(dt) is then a MACRO STEP.  With L = max_level it has T = 2^L ticks of tick = dt 2^-L (exact).  Body i
+ * holds a level l_i in [0, L], a step of s_i = T >> l_i ticks, the tick tau_i of its last correction (all 0 at the start) and
+ * (x0, v0, a0, j0) valid at tau_i.  Until every tau_i = T, one BLOCK STEP:
+ *   1. tau* = min_i (tau_i + s_i); the ACTIVE SET is the bodies with tau_i + s_i == tau*, in ascending index order (integers).
+ *   2. ALL bodies are predicted to tau*: dp_i = f64(tau* - tau_i) tick, c2 = (dp dp) 0.5, c3 = ((dp dp) dp) / 6,
+ *      xp = ((x0 + v0 dp) + a0 c2) + j0 c3, vp = (v0 + a0 dp) + j0 c2.
+ *   3. (a1, j1) = F(xp, vp) for the active bodies only; the partners are all n predicted bodies, the active ones included.
+ *      NBODY_MATH_STRICT: the per-pair expressions above, partners j in ascending index order, j != i.  NBODY_MATH_FAST: rsqrt
+ *      and FMAs, the partner range cut into slices whose sums are added in a fixed order (the same input gives the same
+ *      bits); per row the bounds of the shared step's fast pass.
+ *   4. the corrector on the active bodies with h_i = f64(s_i) tick in place of dt: h = h_i 0.5, c12 = (h_i h_i) / 12.
+ *   5. the new level of each active body; per component c, every product and sum rounded on its own:
+ *        da = a0 - a1,  h2 = h h,  h3 = h2 h,  a3_c = (da_c 12 + (j0_c + j1_c) (h 6)) / h3,
+ *        a2_c = ((da_c (-6) - (j0_c 4 + j1_c 2) h) / h2) + a3_c h      (the second derivative at the END of the step),
+ *        norms sqrt((x^2 + y^2) + z^2) of a1, j1, a2, a3,
+ *        dtc = sqrt(eta ((|a| |a2| + |j| |j|) / (|j| |a3| + |a2| |a2|))),
+ *        wanted level l*: l = 0; s = |dt|; while (s > dtc && l < L) { s *= 0.5; ++l; }   (a NaN dtc gives 0, dtc == 0 gives L);
+ *      l* > l_i: l_i = l* (any finer step is commensurate); l* < l_i, l_i > 0 and tau* mod (T >> (l_i - 1)) == 0: l_i - 1 (a
+ *      step doubles at most once, and only on its own grid); otherwise unchanged.
+ *   6. tau_i = tau* for the active bodies; (x1, v1, a1, j1) become their held values.
+ * Commensurability guarantees that the last block step ends with every body at T.  Then the retain on the corrected
+ * positions, as the shared step does (no body leaves inside a macro step); the levels are carried with pos, vel, acc and
+ * jerk.  elapsed += dt, NbodyStats.steps += 1, interactions += n_active (n - 1) per block step.  dt may be negative; the
+ * levels depend on |dt| only.  dt == 0 takes the shared-step path.
+ *   START LEVELS come from the held derivatives: dtc = eta (|a| / |j|), fed to the same loop.  They are assigned whenever
+ * the levels are INVALID: wherever (a0, j0) are stale (above), after nbody_set_block_steps, after a shared step, and when
+ * |dt| differs in bits from the previous macro step's.  nbody_update_forces on such a handle evaluates F and assigns start
+ * levels for the settings' dt.  nbody_clone carries eta, max_level, the levels and their validity: the clone continues bit
+ * for bit.  nbody_steps(k) gives the bits of k nbody_step_by calls; on a handle with block steps on it SYNCHRONISES WITH THE
+ * HOST (once per block step: the schedule's 8 bytes are read back to size the force launch), everywhere else it stays
+ * asynchronous.  tests/hermite_block_ref.py restates the macro step in numpy, bit for bit beside a strict handle. */
+int nbody_set_block_steps(NbodyHandle* h, double eta, int max_level);
+int nbody_get_block_steps(const NbodyHandle* h, double* eta, int* max_level);
+/* The levels l_i, per body, in nbody_download's order; *n_out = how many.  NBODY_ERR_INVALID while the levels are invalid. */
+int nbody_download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out);
+/* out = {block steps, body updates (the sum of the active sets' sizes)} since nbody_reset_stats */
+int nbody_block_step_counts(NbodyHandle* h, uint64_t out[2]);
+/* test hook: F = (a, j) as [n_ids][3] f64 at the handle's CURRENT (x, v) for the listed bodies, through the active-set
+ * kernels of the handle's math mode; ids distinct and < n, else NBODY_ERR_INVALID; leaves no trace in state or statistics */
+int nbody_debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

@@ -80,6 +80,8 @@ DECLARED_SYMBOLS = [
     "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at",
     "nbody_set_multipole", "nbody_get_multipole", "nbody_tree_export_quadrupoles",
     "nbody_set_integrator", "nbody_get_integrator", "nbody_download_jerk", "nbody_suggest_dt",
+    "nbody_set_block_steps", "nbody_get_block_steps", "nbody_download_levels", "nbody_block_step_counts",
+    "nbody_debug_hermite_forces_of",
 ]
 
 
@@ -150,6 +152,11 @@ _sig("nbody_set_integrator", _i, _H, _i)
 _sig("nbody_get_integrator", _i, _H, C.POINTER(_i))
 _sig("nbody_download_jerk", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_suggest_dt", _i, _H, C.c_double, C.POINTER(C.c_double))
+_sig("nbody_set_block_steps", _i, _H, C.c_double, _i)
+_sig("nbody_get_block_steps", _i, _H, C.POINTER(C.c_double), C.POINTER(_i))
+_sig("nbody_download_levels", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_block_step_counts", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_debug_hermite_forces_of", _i, _H, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
 _sig("nbody_tree_export_cells", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_last_error", C.c_char_p, _H)
 _sig("nbody_comm_unique_id", _i, C.c_void_p)
@@ -554,6 +561,46 @@ class Simulation:
         d = C.c_double(0)
         self._check(lib.nbody_suggest_dt(self._h, float(eta), C.byref(d)))
         return float(d.value)
+
+    @property
+    def block_steps(self) -> tuple[float, int]:
+        """(eta, max_level) of a Hermite handle's block individual time steps (nbody_set_block_steps); (0.0, 0): off, the
+        default.  With them on, step_by(dt) is a macro step of 2**max_level ticks in which body i advances by dt * 2**-level_i
+        and only the due bodies are evaluated; steps() then synchronises with the host.  clone() carries the setting."""
+        eta, lv = C.c_double(0), C.c_int(0)
+        rc = lib.nbody_get_block_steps(self._h, C.byref(eta), C.byref(lv))
+        if rc:
+            raise NbodyError(rc, "nbody_get_block_steps: the handle runs the leapfrog integrator (nbody_set_integrator)")
+        return float(eta.value), int(lv.value)
+
+    @block_steps.setter
+    def block_steps(self, eta_levels):
+        eta, levels = eta_levels
+        self._check(lib.nbody_set_block_steps(self._h, float(eta), int(levels)))
+
+    def levels(self) -> np.ndarray:
+        """[n] i32: the block-step level of every body, in get_points() order (nbody_download_levels).  Refused while the
+        levels are invalid: until the first macro step or update_forces() after whatever made them so."""
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        n = C.c_size_t(0)
+        out = np.zeros(max(int(cfg.capacity), 1), np.int32)
+        self._check(lib.nbody_download_levels(self._h, out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value]
+
+    def block_step_counts(self) -> tuple[int, int]:
+        """(block steps, body updates) since reset_stats() (nbody_block_step_counts)."""
+        out = (C.c_uint64 * 2)()
+        self._check(lib.nbody_block_step_counts(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def hermite_forces_of(self, ids) -> tuple[np.ndarray, np.ndarray]:
+        """Test hook (nbody_debug_hermite_forces_of): (a [k, 3], j [k, 3]) f64 of the listed bodies at the current state,
+        through the active-set kernels."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        a, j = np.zeros((len(ids), 3), np.float64), np.zeros((len(ids), 3), np.float64)
+        self._check(lib.nbody_debug_hermite_forces_of(self._h, ids.ctypes.data, len(ids), a.ctypes.data, j.ctypes.data))
+        return a, j
 
     def tree_quadrupoles(self) -> np.ndarray:
         """[n_nodes, 6] f32 {xx, xy, xz, yy, yz, zz} of every node of the tree tree() reports (nbody_tree_export_quadrupoles):

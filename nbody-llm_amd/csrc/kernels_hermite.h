@@ -29,7 +29,8 @@ void launch_hm_strict(hipStream_t s, const Dev& d, const double4* x, const doubl
 //   v1 = (v0 + (a0 + a1) * h) + (j0 - j1) * c12,  x1 = (x0 + (v0 + v1) * h) + (a0 - a1) * c12
 void launch_hm_correct(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, const HermiteCoef& c, const Bounds64& b);
 // Vec::retain over pos, vel, acc and jerk together (k_compact's tile scan with a fourth array)
-void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper);
+// level != nullptr: the block-step levels travel along
+void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, int* level = nullptr);
 // per-workgroup minima of |a_i| / |j_i| over live bodies with |j_i| > 0 (+inf where there is none) -> hd.ratio; returns the workgroups
 int launch_hm_min_ratio(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper);
 
@@ -46,5 +47,40 @@ void launch_hm_own(hipStream_t s, const Dev& d, const Bf64Plan& p, const double4
 // on pos / vel / acc / jerk, as launch_hm_correct).  Adds n (n - 1) to Dev::inter.
 void launch_hm_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const Bf64Plan& p, const double4* planes, int n_upper, double g,
                       double4* out_a, double4* out_j, const HermiteCoef* c, const Bounds64& b);
+
+// ---- block individual time steps (nbody_set_block_steps; include/nbody_hip.h "block steps")
+// what a handle with block steps keeps beside HermiteDev
+struct BlockDev {
+    int* level = nullptr;        // [cap] l_i: body i steps by T >> l_i ticks; carried across macro steps (and by the retain)
+    int* tau = nullptr;          // [cap] tick of body i's last correction within the macro step
+    int* list = nullptr;         // [cap] the due bodies of the block step, ascending
+    int* tile_count = nullptr;   // [ceil(cap / 1024)] due bodies per 1024-body tile
+    int* smin = nullptr;         // [2] min (tau_i + s_i) of this block step and the slot armed for the next; then
+    int* sched = nullptr;        // [2] = smin + 2: {tau*, due bodies}, what the host reads back once per block step
+    double4* planes = nullptr;   // k_hm_act's partial sums: K planes of accelerations, then K of jerks, groups * 64 rows each
+    size_t plane_rows = 0;       // rows of one kind the buffer holds (hm_act_plane_rows)
+};
+// start levels from the held (a0, j0): dtc = eta (|a| / |j|), l = 0, s = |dt|, while (s > dtc && l < max_level) { s *= 0.5; ++l; }
+void launch_hmb_start_levels(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_upper, double eta, double abs_dt,
+                             int max_level);
+// one block step's schedule, three launches: tau* = min (tau_i + (T >> l_i)) into bd.smin[slot] (bd.smin[slot ^ 1] re-armed);
+// the due bodies' indices ascending into bd.list and {tau*, how many} into bd.sched; every body predicted to tau* into
+// (hd.xp, hd.vp) with its own dp = f64(tau* - tau_i) tick.  bd.smin holds 0x7f7f7f7f in both slots before a macro step's first.
+void launch_hmb_schedule(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_upper, int T, double tick, int slot);
+// NBODY_MATH_FAST, F of the n_act listed bodies against all n of (x, v): 64-body groups x K partner slices, about bf64_waves
+// waves (default 2048), a slice no shorter than one 64-partner tile
+struct HmActPlan { int groups = 0, K = 1; };
+HmActPlan make_hm_act_plan(int n_act, int n);
+size_t hm_act_plane_rows(int cap);   // rows of one kind (accelerations or jerks) any plan of a handle of this capacity needs
+void launch_hm_act(hipStream_t s, const Dev& d, const BlockDev& bd, const HmActPlan& p, const double4* x, const double4* v, double eps2);
+// NBODY_MATH_STRICT: one listed body per lane, partners ascending; row p of (hd.a1, hd.j1) belongs to bd.list[p]
+void launch_hm_act_strict(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_act, const double4* x, const double4* v,
+                          double g, double eps2);
+// the due bodies' (a1, j1) (p != nullptr: the K planes in a fixed order, times g; else rows of hd.a1 / hd.j1), the corrector
+// with h_i = f64(T >> l_i) tick, the step criterion and the new level, tau_i = tau*; adds n_act (n - 1) to Dev::inter
+void launch_hmb_finish(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, const HmActPlan* p, int n_act, double g, int T,
+                       int max_level, double tick, double abs_dt, double eta, const Bounds64& b);
+// the planes alone into rows of (hd.a1, hd.j1): nbody_debug_hermite_forces_of on a fast handle
+void launch_hm_act_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, const HmActPlan& p, int n_act, double g);
 
 }  // namespace nbody64

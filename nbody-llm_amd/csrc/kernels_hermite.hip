@@ -14,12 +14,16 @@
 //                   body (small worlds); MODE 1: the pairs k_hm_sym leaves over (the own set and, for even A, the opposite one)
 //   k_hm_reduce     the planes added in a fixed order, times g; CORRECT: the corrector and the retain's flags ride along
 //   k_hm_predict, k_hm_correct, k_hm_compact, k_hm_min_ratio   the small kernels of the step and of nbody_suggest_dt
+//   k_hmb_*, k_hm_act, k_hm_act_strict   block individual time steps (nbody_set_block_steps): the schedule of a block step, F
+//                   of the due bodies alone against everybody, and the corrector with the step criterion (further down)
 //
 // Fast pair arithmetic: rinv = rsqrt(q), rinv^2, rinv^3, nal = (-3 rinv^2) (d.w), u = w + nal d (the vector both sides
 // share), one mass product per side, twelve explicit FMAs (the library builds with -ffp-contract=off).  Every plane entry
 // is written exactly once per launch; there are no atomics on the planes: the same input gives the same bits.
 #include "kernels_hermite.h"
 #include "kernels.h"   // nbody::tuning()
+
+#include <algorithm>
 
 namespace nbody64 {
 
@@ -98,10 +102,13 @@ __device__ __forceinline__ unsigned long long tile_word(int epoch, unsigned long
     return ((unsigned long long)(unsigned)epoch << 34) | (flag << 32) | (unsigned long long)(unsigned)value;
 }
 
+// LV: the block-step levels travel with the four arrays
+template <bool LV>
 __global__ __launch_bounds__(kTile) void k_hm_compact(double4* __restrict__ pos, double4* __restrict__ vel, double4* __restrict__ acc,
                                                       double4* __restrict__ jerk, const unsigned char* __restrict__ keep,
                                                       int* __restrict__ count, int* __restrict__ escaped,
-                                                      unsigned long long* __restrict__ tile_state, int* __restrict__ epoch_p) {
+                                                      unsigned long long* __restrict__ tile_state, int* __restrict__ epoch_p,
+                                                      int* __restrict__ level) {
     if (*escaped == 0) return;
     __shared__ int wave_total[16];
     __shared__ int excl_s;
@@ -112,7 +119,8 @@ __global__ __launch_bounds__(kTile) void k_hm_compact(double4* __restrict__ pos,
     const int k = tile * kTile + tid;
     const bool kp = (k < n) && keep[k];
     double4 p = zero4(), v = p, a = p, j = p;
-    if (kp) { p = pos[k]; v = vel[k]; a = acc[k]; j = jerk[k]; }
+    int lv = 0;
+    if (kp) { p = pos[k]; v = vel[k]; a = acc[k]; j = jerk[k]; if (LV) lv = level[k]; }
     const unsigned long long m = __ballot(kp);
     const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) wave_total[wave] = __popcll(m);
@@ -153,6 +161,7 @@ __global__ __launch_bounds__(kTile) void k_hm_compact(double4* __restrict__ pos,
     if (kp) {
         const int d = excl_s + before + in_wave;
         pos[d] = p; vel[d] = v; acc[d] = a; jerk[d] = j;
+        if (LV) level[d] = lv;
     }
 }
 
@@ -483,6 +492,273 @@ __global__ __launch_bounds__(256) void k_hm_reduce(const double4* __restrict__ p
     else { out_a[i] = a1; out_j[i] = j1; }
 }
 
+// ------------------------------------------------------------------------------------------ block individual time steps
+// One macro step of T = 2^L ticks (include/nbody_hip.h "block steps").  Body i sits at tick tau[i] with a step of T >> level[i]
+// ticks.  A block step: k_hmb_min (tau* = the earliest due tick), k_hmb_count + k_hmb_list (the due bodies' indices in
+// ascending order, and every body predicted to tau*), k_hm_act / k_hm_act_strict (F of the listed bodies against all n
+// predicted ones), k_hmb_finish (planes, corrector, step criterion, new level).  No kernel hands data to another workgroup
+// of its own launch: tau*, the per-tile counts and the list cross launch boundaries only.
+constexpr int kNever = 0x7f7f7f7f;   // (what the host's memset writes into BlockDev::smin)
+
+// the level a step of |dt| 2^-l must reach to be <= dtc (a NaN dtc gives 0, dtc == 0 gives max_level)
+__device__ __forceinline__ int level_for(double dtc, double abs_dt, int max_level) {
+    int l = 0;
+    double s = abs_dt;
+    while (s > dtc && l < max_level) { s *= 0.5; ++l; }
+    return l;
+}
+__device__ __forceinline__ double norm3(double x, double y, double z) { return __builtin_sqrt((x * x + y * y) + z * z); }
+
+// start levels from the held derivatives: dtc = eta (|a| / |j|)
+__global__ __launch_bounds__(256) void k_hmb_start(const double4* __restrict__ acc, const double4* __restrict__ jerk, const int* __restrict__ count,
+                                                   int* __restrict__ level, double eta, double abs_dt, int max_level) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= *count) return;
+    const double4 a = acc[k], j = jerk[k];
+    const double dtc = eta * (norm3(a.x, a.y, a.z) / norm3(j.x, j.y, j.z));
+    level[k] = level_for(dtc, abs_dt, max_level);
+}
+
+// smin[slot] = min_i (tau_i + s_i); the other slot is re-armed for the next block step
+__global__ __launch_bounds__(256) void k_hmb_min(const int* __restrict__ tau, const int* __restrict__ level, const int* __restrict__ count, int T,
+                                                 int* __restrict__ smin, int slot) {
+    __shared__ int part[4];
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    int r = kNever;
+    if (k < *count) r = tau[k] + (T >> level[k]);
+    for (int off = 32; off > 0; off >>= 1) r = min(r, __shfl_down(r, off));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        atomicMin(smin + slot, min(min(part[0], part[1]), min(part[2], part[3])));   // (a minimum does not depend on the order)
+        if (blockIdx.x == 0) smin[slot ^ 1] = kNever;
+    }
+}
+
+// due bodies of every 1024-body tile
+__global__ __launch_bounds__(kTile) void k_hmb_count(const int* __restrict__ tau, const int* __restrict__ level, const int* __restrict__ count, int T,
+                                                     const int* __restrict__ smin, int slot, int* __restrict__ tile_count) {
+    __shared__ int wave_total[16];
+    const int tid = threadIdx.x;
+    const int k = blockIdx.x * kTile + tid;
+    const bool due = (k < *count) && (tau[k] + (T >> level[k]) == smin[slot]);
+    const unsigned long long m = __ballot(due);
+    if ((tid & 63) == 0) wave_total[tid >> 6] = __popcll(m);
+    __syncthreads();
+    if (tid == 0) {
+        int total = 0;
+        for (int w = 0; w < 16; ++w) total += wave_total[w];
+        tile_count[blockIdx.x] = total;
+    }
+}
+
+// the due bodies' indices, ascending, into list; every body predicted to tau* (k_hm_predict's expressions with the body's own
+// dp = f64(tau* - tau_i) tick and hermite_coef's c2, c3); the last tile reports {tau*, how many are due}
+__global__ __launch_bounds__(kTile) void k_hmb_list(const double4* __restrict__ pos, const double4* __restrict__ vel, const double4* __restrict__ acc,
+                                                    const double4* __restrict__ jerk, const int* __restrict__ tau, const int* __restrict__ level,
+                                                    const int* __restrict__ count, int T, double tick, const int* __restrict__ smin, int slot,
+                                                    const int* __restrict__ tile_count, int* __restrict__ list, int* __restrict__ sched,
+                                                    double4* __restrict__ xp, double4* __restrict__ vp) {
+    __shared__ int wave_total[16];
+    __shared__ int red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tile = blockIdx.x;
+    const int n = *count;
+    const int tstar = smin[slot];
+    const int k = tile * kTile + tid;
+    bool due = false;
+    if (k < n) {
+        const int tk = tau[k];
+        due = tk + (T >> level[k]) == tstar;
+        const double dp = double(tstar - tk) * tick;
+        const double c2 = (dp * dp) * 0.5, c3 = ((dp * dp) * dp) / 6.0;
+        const double4 x0 = pos[k], v0 = vel[k], a0 = acc[k], j0 = jerk[k];
+        double4 x, v;
+        x.x = ((x0.x + v0.x * dp) + a0.x * c2) + j0.x * c3;
+        x.y = ((x0.y + v0.y * dp) + a0.y * c2) + j0.y * c3;
+        x.z = ((x0.z + v0.z * dp) + a0.z * c2) + j0.z * c3;
+        x.w = x0.w;
+        v.x = (v0.x + a0.x * dp) + j0.x * c2;
+        v.y = (v0.y + a0.y * dp) + j0.y * c2;
+        v.z = (v0.z + a0.z * dp) + j0.z * c2;
+        v.w = 0.0;
+        xp[k] = x;
+        vp[k] = v;
+    }
+    int before_tiles = 0;   // due bodies of the tiles below this one: integer sums, any order
+    for (int t = tid; t < tile; t += kTile) before_tiles += tile_count[t];
+    for (int off = 32; off > 0; off >>= 1) before_tiles += __shfl_down(before_tiles, off);
+    const unsigned long long m = __ballot(due);
+    if (lane == 0) { wave_total[wave] = __popcll(m); red[wave] = before_tiles; }
+    __syncthreads();
+    int excl = 0, before = 0, total = 0;
+    for (int w = 0; w < 16; ++w) {
+        excl += red[w];
+        if (w < wave) before += wave_total[w];
+        total += wave_total[w];
+    }
+    if (due) list[excl + before + __popcll(m & ((1ull << lane) - 1ull))] = k;
+    if (tid == 0 && tile == int(gridDim.x) - 1) { sched[0] = tstar; sched[1] = excl + total; }
+}
+
+// NBODY_MATH_FAST: F of the listed bodies.  4 waves per workgroup; wave gw = group * K + slice: the bodies list[group*64 + lane]
+// against partners [n slice / K, n (slice + 1) / K) of ALL n bodies of (x, v), staged 64 at a time through the wave's own LDS
+// tile (k_hm_os<0>'s loop and arithmetic).  Output: plane `slice`, rows group*64 .. group*64+63: every row of every plane is
+// written exactly once, padding rows and empty slices included.
+__global__ __launch_bounds__(256) void k_hm_act(const double4* __restrict__ x, const double4* __restrict__ v, const int* __restrict__ count,
+                                                const int* __restrict__ list, const int* __restrict__ n_act_p, int groups, int K,
+                                                double4* __restrict__ planes, size_t plane_stride, size_t jerk_off, double eps2) {
+    __shared__ double4 tile[4][2][64];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int gw = blockIdx.x * 4 + wv;
+    if (gw >= groups * K) return;
+    const int group = gw / K, slice = gw - group * K;
+    const int n = *count;
+    const int p = group * 64 + lane;
+    const int i = (p < *n_act_p) ? list[p] : -1;   // (-1: a padding lane; no partner has that index)
+    const double4 pi = (i >= 0) ? x[i] : pad_body();
+    const double4 vi = (i >= 0) ? v[i] : zero4();
+    double eps2v = eps2;
+    asm volatile("" : "+v"(eps2v));
+    const int lo = int((long long)n * slice / K), hi = int((long long)n * (slice + 1) / K);
+    double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+    double4 nxt_p = pad_body(), nxt_v = zero4();
+    if (lo + lane < hi) { nxt_p = x[lo + lane]; nxt_v = v[lo + lane]; }
+    for (int c0 = lo; c0 < hi; c0 += 64) {
+        tile[wv][0][lane] = nxt_p;   // the wave's own tile: its LDS operations complete in program order
+        tile[wv][1][lane] = nxt_v;
+        if (c0 + 64 + lane < hi) { nxt_p = x[c0 + 64 + lane]; nxt_v = v[c0 + 64 + lane]; }
+        const int cnt = min(64, hi - c0);
+        for (int t = 0; t < cnt; ++t) {
+            const double4 pj = tile[wv][0][t];   // wave-uniform address: an LDS broadcast
+            const double4 vj = tile[wv][1][t];
+            const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
+            const double q = fma(dz, dz, fma(dy, dy, fma(dx, dx, eps2v)));
+            const double rv = fma(dz, wz, fma(dy, wy, dx * wx));
+            double rinv = rsqrt(q);
+            rinv = (c0 + t == i) ? 0.0 : rinv;   // the i == j pair is never formed (with g_soft = 0 its rsqrt is inf)
+            const double rinv2 = rinv * rinv;
+            const double nal = (-3.0 * rinv2) * rv;
+            const double sj = pj.w * (rinv2 * rinv);
+            wx = fma(nal, dx, wx);
+            wy = fma(nal, dy, wy);
+            wz = fma(nal, dz, wz);
+            ax = fma(dx, sj, ax);
+            ay = fma(dy, sj, ay);
+            az = fma(dz, sj, az);
+            jx = fma(wx, sj, jx);
+            jy = fma(wy, sj, jy);
+            jz = fma(wz, sj, jz);
+        }
+    }
+    const size_t row = size_t(slice) * plane_stride + size_t(p);
+    planes[row] = make_double4(ax, ay, az, 0.0);
+    planes[jerk_off + row] = make_double4(jx, jy, jz, 0.0);
+}
+
+// NBODY_MATH_STRICT: one listed body per lane, partners in ascending index order (k_hm_strict's expressions); row p of the
+// outputs belongs to list[p]
+__global__ __launch_bounds__(kStrictBlock) void k_hm_act_strict(const double4* __restrict__ x, const double4* __restrict__ v,
+                                                                const int* __restrict__ count, const int* __restrict__ list,
+                                                                const int* __restrict__ n_act_p, double4* __restrict__ out_a,
+                                                                double4* __restrict__ out_j, double g, double eps2) {
+    __shared__ double4 tx[kStrictTile], tv[kStrictTile];
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x * kStrictBlock + tid;
+    const int n = *count;
+    const int i = (p < *n_act_p) ? list[p] : -1;
+    const double4 pi = (i >= 0) ? x[i] : zero4();
+    const double4 vi = (i >= 0) ? v[i] : zero4();
+    double ax = 0.0, ay = 0.0, az = 0.0, jx = 0.0, jy = 0.0, jz = 0.0;
+    for (int t0 = 0; t0 < n; t0 += kStrictTile) {
+        const int cnt = min(kStrictTile, n - t0);
+        __syncthreads();
+        if (tid < cnt) { tx[tid] = x[t0 + tid]; tv[tid] = v[t0 + tid]; }
+        __syncthreads();
+        for (int t = 0; t < cnt; ++t) {
+            if (t0 + t == i) continue;   // the i == j pair is never formed
+            const double4 pj = tx[t], vj = tv[t];
+            const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+            const double dvx = vj.x - vi.x, dvy = vj.y - vi.y, dvz = vj.z - vi.z;
+            const double r2 = ((dx * dx + dy * dy) + dz * dz) + eps2;
+            const double rv = (dx * dvx + dy * dvy) + dz * dvz;
+            const double w = (g * pj.w) / (r2 * __builtin_sqrt(r2));
+            const double al = (3.0 * rv) / r2;
+            ax += dx * w;
+            ay += dy * w;
+            az += dz * w;
+            jx += (dvx - al * dx) * w;
+            jy += (dvy - al * dy) * w;
+            jz += (dvz - al * dz) * w;
+        }
+    }
+    if (i >= 0) {
+        out_a[p] = make_double4(ax, ay, az, 0.0);
+        out_j[p] = make_double4(jx, jy, jz, 0.0);
+    }
+}
+
+// what a block step does to its due bodies, one per lane: (a1, j1) from the K planes added in a fixed order, times g (PLANES)
+// or from row p of (in_a, in_j); STEP: the corrector with the body's own h = f64(s_i) tick, the a2 / a3 step criterion, the new
+// level, tau_i = tau* -- the due body's state is read and written once; else (a1, j1) go to row p of (out_a, out_j)
+template <bool PLANES, bool STEP>
+__global__ __launch_bounds__(256) void k_hmb_finish(const double4* __restrict__ planes, int n_planes, size_t plane_stride, size_t jerk_off,
+                                                    const double4* __restrict__ in_a, const double4* __restrict__ in_j, double4* __restrict__ out_a,
+                                                    double4* __restrict__ out_j, const int* __restrict__ count, const int* __restrict__ list,
+                                                    const int* __restrict__ sched, double g, double4* __restrict__ pos, double4* __restrict__ vel,
+                                                    double4* __restrict__ acc, double4* __restrict__ jerk, unsigned char* __restrict__ keep,
+                                                    int* __restrict__ escaped, int* __restrict__ tau, int* __restrict__ level, int T, int max_level,
+                                                    double tick, double abs_dt, double eta, Bounds64 b, unsigned long long* __restrict__ inter) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int n_act = sched[1];
+    if (STEP && inter && p == 0 && n_act > 0) atomicAdd(inter, (unsigned long long)n_act * (unsigned long long)(*count - 1));
+    if (p >= n_act) return;
+    double4 a1, j1;
+    if (PLANES) {
+        double sx = 0.0, sy = 0.0, sz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
+        for (int q = 0; q < n_planes; ++q) {
+            const double4 va = planes[size_t(q) * plane_stride + p];
+            const double4 vj = planes[jerk_off + size_t(q) * plane_stride + p];
+            sx += va.x; sy += va.y; sz += va.z;
+            tx += vj.x; ty += vj.y; tz += vj.z;
+        }
+        a1 = make_double4(g * sx, g * sy, g * sz, 0.0);
+        j1 = make_double4(g * tx, g * ty, g * tz, 0.0);
+    } else {
+        a1 = in_a[p];
+        j1 = in_j[p];
+    }
+    if (!STEP) { out_a[p] = a1; out_j[p] = j1; return; }
+    const int i = list[p];
+    const int tstar = sched[0];
+    const int l = level[i];
+    const double h = double(T >> l) * tick;
+    const double4 a0 = acc[i], j0 = jerk[i];
+    HermiteCoef c{};
+    c.h = h * 0.5;
+    c.c12 = (h * h) / 12.0;
+    correct_one(i, a1, j1, pos, vel, acc, jerk, keep, escaped, c, b);
+    const double h2 = h * h, h3 = h2 * h, h6 = h * 6.0;
+    const double dax = a0.x - a1.x, day = a0.y - a1.y, daz = a0.z - a1.z;
+    const double a3x = (dax * 12.0 + (j0.x + j1.x) * h6) / h3;
+    const double a3y = (day * 12.0 + (j0.y + j1.y) * h6) / h3;
+    const double a3z = (daz * 12.0 + (j0.z + j1.z) * h6) / h3;
+    const double a2x = ((dax * -6.0 - (j0.x * 4.0 + j1.x * 2.0) * h) / h2) + a3x * h;   // the second derivative at the END of the step
+    const double a2y = ((day * -6.0 - (j0.y * 4.0 + j1.y * 2.0) * h) / h2) + a3y * h;
+    const double a2z = ((daz * -6.0 - (j0.z * 4.0 + j1.z * 2.0) * h) / h2) + a3z * h;
+    const double na = norm3(a1.x, a1.y, a1.z), nj = norm3(j1.x, j1.y, j1.z);
+    const double n2 = norm3(a2x, a2y, a2z), n3 = norm3(a3x, a3y, a3z);
+    const double dtc = __builtin_sqrt(eta * ((na * n2 + nj * nj) / (nj * n3 + n2 * n2)));
+    const int want = level_for(dtc, abs_dt, max_level);
+    int nl = l;
+    if (want > l) nl = want;                                                   // any finer step is commensurate
+    else if (want < l && l > 0 && (tstar % (T >> (l - 1))) == 0) nl = l - 1;   // a step doubles once, and only on its own grid
+    level[i] = nl;
+    tau[i] = tstar;
+}
+
 inline int blocks_for(long long n, int per) { return int((n + per - 1) / per); }
 
 }  // namespace
@@ -504,10 +780,14 @@ void launch_hm_correct(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_
                        d.escaped, c, b);
 }
 
-void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper) {
+void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, int* level) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_hm_compact, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.count, d.escaped,
-                       d.tile_state, d.epoch);
+    if (level)
+        hipLaunchKernelGGL(k_hm_compact<true>, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.count,
+                           d.escaped, d.tile_state, d.epoch, level);
+    else
+        hipLaunchKernelGGL(k_hm_compact<false>, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.count,
+                           d.escaped, d.tile_state, d.epoch, level);
 }
 
 int launch_hm_min_ratio(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper) {
@@ -548,6 +828,69 @@ void launch_hm_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const B
     else
         hipLaunchKernelGGL(k_hm_reduce<false>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.count, g, out_a, out_j, d.pos, d.vel, d.acc,
                            hd.jerk, d.keep, d.escaped, HermiteCoef{}, b, d.inter);
+}
+
+// ----------------------------------------------------------------------------------- block steps, host side
+void launch_hmb_start_levels(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_upper, double eta, double abs_dt,
+                             int max_level) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_hmb_start, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.acc, hd.jerk, d.count, bd.level, eta, abs_dt, max_level);
+}
+
+void launch_hmb_schedule(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_upper, int T, double tick, int slot) {
+    if (n_upper <= 0) return;
+    const int tiles = blocks_for(n_upper, kTile);
+    hipLaunchKernelGGL(k_hmb_min, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, bd.tau, bd.level, d.count, T, bd.smin, slot);
+    hipLaunchKernelGGL(k_hmb_count, dim3(tiles), dim3(kTile), 0, s, bd.tau, bd.level, d.count, T, bd.smin, slot, bd.tile_count);
+    hipLaunchKernelGGL(k_hmb_list, dim3(tiles), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, bd.tau, bd.level, d.count, T, tick, bd.smin, slot,
+                       bd.tile_count, bd.list, bd.sched, hd.xp, hd.vp);
+}
+
+HmActPlan make_hm_act_plan(int n_act, int n) {
+    HmActPlan p;
+    const int want = nbody::tuning().bf64_waves > 0 ? nbody::tuning().bf64_waves : 2048;
+    p.groups = blocks_for(n_act, 64);
+    p.K = std::max(1, std::min(want / std::max(1, p.groups), blocks_for(n, 64)));   // (a slice holds a 64-partner tile or more)
+    return p;
+}
+
+size_t hm_act_plane_rows(int cap) {
+    const int want = nbody::tuning().bf64_waves > 0 ? nbody::tuning().bf64_waves : 2048;
+    return size_t(std::max(want, blocks_for(cap, 64))) * 64;   // K groups <= max(want, groups)
+}
+
+void launch_hm_act(hipStream_t s, const Dev& d, const BlockDev& bd, const HmActPlan& p, const double4* x, const double4* v, double eps2) {
+    if (p.groups <= 0) return;
+    const size_t stride = size_t(p.groups) * 64;
+    hipLaunchKernelGGL(k_hm_act, dim3(blocks_for((long long)p.groups * p.K, 4)), dim3(256), 0, s, x, v, d.count, bd.list, bd.sched + 1, p.groups, p.K,
+                       bd.planes, stride, size_t(p.K) * stride, eps2);
+}
+
+void launch_hm_act_strict(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_act, const double4* x, const double4* v,
+                          double g, double eps2) {
+    if (n_act <= 0) return;
+    hipLaunchKernelGGL(k_hm_act_strict, dim3(blocks_for(n_act, kStrictBlock)), dim3(kStrictBlock), 0, s, x, v, d.count, bd.list, bd.sched + 1, hd.a1,
+                       hd.j1, g, eps2);
+}
+
+void launch_hmb_finish(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, const HmActPlan* p, int n_act, double g, int T,
+                       int max_level, double tick, double abs_dt, double eta, const Bounds64& b) {
+    if (n_act <= 0) return;
+    const dim3 grid(blocks_for(n_act, 256)), block(256);
+    const size_t stride = p ? size_t(p->groups) * 64 : 0;
+#define HMFIN(PL) hipLaunchKernelGGL((k_hmb_finish<PL, true>), grid, block, 0, s, bd.planes, p ? p->K : 0, stride, size_t(p ? p->K : 0) * stride, hd.a1, \
+                                     hd.j1, nullptr, nullptr, d.count, bd.list, bd.sched, g, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.escaped, bd.tau,  \
+                                     bd.level, T, max_level, tick, abs_dt, eta, b, d.inter)
+    if (p) HMFIN(true); else HMFIN(false);
+#undef HMFIN
+}
+
+void launch_hm_act_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, const HmActPlan& p, int n_act, double g) {
+    if (n_act <= 0) return;
+    const size_t stride = size_t(p.groups) * 64;
+    hipLaunchKernelGGL((k_hmb_finish<true, false>), dim3(blocks_for(n_act, 256)), dim3(256), 0, s, bd.planes, p.K, stride, size_t(p.K) * stride, nullptr,
+                       nullptr, hd.a1, hd.j1, d.count, bd.list, bd.sched, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                       0.0, 0.0, 0.0, Bounds64{}, nullptr);
 }
 
 }  // namespace nbody64

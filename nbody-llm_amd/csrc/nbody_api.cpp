@@ -1733,6 +1733,42 @@ int nbody_suggest_dt(NbodyHandle* h, double eta, double* dt_out) {
     return nbody64::suggest_dt(h, eta, dt_out);
 }
 
+// ---- block individual time steps of a Hermite handle (nbody_f64.cpp hm_block_step): accepted where HERMITE4 is, while it is selected
+int nbody_set_block_steps(NbodyHandle* h, double eta, int max_level) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (!h->f64) return fail(h, NBODY_ERR_INVALID, "nbody_set_block_steps: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody64::set_block_steps(h, eta, max_level);
+}
+
+int nbody_get_block_steps(const NbodyHandle* h, double* eta, int* max_level) {
+    if (!h || !h->f64) return NBODY_ERR_INVALID;
+    return nbody64::get_block_steps(h, eta, max_level);
+}
+
+int nbody_download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (!h->f64) return fail(h, NBODY_ERR_INVALID, "nbody_download_levels: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody64::download_levels(h, level, cap, n_out);
+}
+
+int nbody_block_step_counts(NbodyHandle* h, uint64_t out[2]) {
+    if (!h || !out) return h ? fail(h, NBODY_ERR_INVALID, "null argument") : NBODY_ERR_INVALID;
+    if (!h->f64) return fail(h, NBODY_ERR_INVALID, "nbody_block_step_counts: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    return nbody64::block_step_counts(h, out);
+}
+
+int nbody_debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (!h->f64) return fail(h, NBODY_ERR_INVALID, "nbody_debug_hermite_forces_of: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody64::debug_hermite_forces_of(h, ids, n_ids, acc3, jerk3);
+}
+
 int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t* n_nodes) {
     if (!h) return NBODY_ERR_INVALID;
     if (h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "not a Barnes-Hut handle");

@@ -71,6 +71,15 @@ struct State {
     uint64_t hm_sym_pairs = 0;
     double4* d_hm_planes = nullptr;
     size_t hm_planes_cap = 0;     // double4 entries
+    // nbody_set_block_steps: block individual time steps of a Hermite handle (off: blk_L == 0).  lv_valid: blk.level holds
+    // levels assigned for a macro step of |dt| == lv_dt from derivatives that are still the held ones (needs hm_valid too)
+    double blk_eta = 0.0;
+    int blk_L = 0;
+    bool lv_valid = false;
+    double lv_dt = 0.0;
+    BlockDev blk;
+    int* h_sched = nullptr;       // pinned [2]: {tau*, due bodies} of the block step
+    uint64_t blk_steps = 0, blk_updates = 0;   // since nbody_reset_stats
 };
 
 namespace {
@@ -229,10 +238,117 @@ int hm_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, double
 int hm_refresh(NbodyHandle* h, State& s) {   // the held (a0, j0) at the current (x, v)
     int rc = hm_eval(h, s, s.d.pos, s.d.vel, s.d.acc, s.hm.jerk, nullptr);
     if (!rc) s.hm_valid = true;
+    s.lv_valid = false;   // (levels belong to the derivatives they were drawn from)
     return rc;
 }
 
+// ---- block individual time steps (kernels_hermite.hip, "block individual time steps")
+int ensure_block(NbodyHandle* h, State& s) {
+    BlockDev& b = s.blk;
+    const size_t cap = size_t(s.d.cap);
+    if (!b.level) {
+        int** arr[] = {&b.level, &b.tau, &b.list};
+        for (int** a : arr) {
+            HIP_TRY(h, hipMalloc(a, cap * sizeof(int)));
+            HIP_TRY(h, hipMemsetAsync(*a, 0, cap * sizeof(int), h->stream));
+        }
+        HIP_TRY(h, hipMalloc(&b.tile_count, ((cap + 1023) / 1024) * sizeof(int)));
+        HIP_TRY(h, hipMalloc(&b.smin, 4 * sizeof(int)));
+        HIP_TRY(h, hipMemsetAsync(b.smin, 0, 4 * sizeof(int), h->stream));
+        b.sched = b.smin + 2;
+        HIP_TRY(h, hipHostMalloc(&s.h_sched, 2 * sizeof(int), hipHostMallocDefault));
+    }
+    const size_t rows = hm_act_plane_rows(s.d.cap);   // (follows the bf64_waves knob)
+    if (rows > b.plane_rows) {
+        if (b.planes) (void)hipFree(b.planes);
+        b.planes = nullptr; b.plane_rows = 0;
+        HIP_TRY(h, hipMalloc(&b.planes, 2 * rows * sizeof(double4)));   // accelerations, then jerks
+        b.plane_rows = rows;
+    }
+    return NBODY_OK;
+}
+
+bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) == 0; }
+
+// start levels for macro steps of |dt| = abs_dt from the held (valid) derivatives
+int assign_levels(NbodyHandle* h, State& s, double abs_dt) {
+    int rc = ensure_block(h, s);
+    if (rc) return rc;
+    launch_hmb_start_levels(h->stream, s.d, s.hm, s.blk, int(s.n_local), s.blk_eta, abs_dt, s.blk_L);
+    HIP_TRY(h, hipGetLastError());
+    s.lv_valid = true;
+    s.lv_dt = abs_dt;
+    return NBODY_OK;
+}
+
+// F of the bodies bd.list names (their number is on the device in bd.sched[1] and here in n_act) against all n of (x, v),
+// through the active-set kernels of the handle's math mode.  Fast math: into the planes (*plan says how); strict: rows of
+// (hm.a1, hm.j1).  Enqueues only.
+int hm_act_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, int n_act, HmActPlan* plan) {
+    const double eps2 = s.g_soft * s.g_soft;
+    if (h->cfg.math_mode == NBODY_MATH_FAST) {
+        *plan = make_hm_act_plan(n_act, int(s.n_local));
+        if (size_t(plan->K) * size_t(plan->groups) * 64 > s.blk.plane_rows) return fail(h, NBODY_ERR_CAPACITY, "block steps: the active-set planes are too small for this launch");
+        launch_hm_act(h->stream, s.d, s.blk, *plan, x, v, eps2);
+    } else {
+        launch_hm_act_strict(h->stream, s.d, s.hm, s.blk, n_act, x, v, s.g, eps2);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return NBODY_OK;
+}
+
+// One nbody_step_by(dt) of a handle with block steps on: a macro step of T = 2^L ticks (include/nbody_hip.h "block steps").
+// The host reads {tau*, due bodies} back once per block step and sizes the force launch from them.
+int hm_block_step(NbodyHandle* h, State& s, double dt) {
+    if (!s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    int rc = sync_count(h, s);   // the exact body count: nothing leaves inside a macro step
+    if (!rc && !s.hm_valid) rc = hm_refresh(h, s);
+    if (!rc) rc = ensure_block(h, s);
+    if (rc) return rc;
+    const double abs_dt = std::fabs(dt);
+    if (!s.lv_valid || !same_bits(abs_dt, s.lv_dt)) {
+        rc = assign_levels(h, s, abs_dt);
+        if (rc) return rc;
+    }
+    const int n = int(s.n_local);
+    const int L = s.blk_L, T = 1 << L;
+    const double tick = std::ldexp(dt, -L);
+    const bool fast = h->cfg.math_mode == NBODY_MATH_FAST;
+    if (n > 0) {
+        HIP_TRY(h, hipMemsetAsync(s.blk.tau, 0, size_t(n) * sizeof(int), h->stream));
+        HIP_TRY(h, hipMemsetAsync(s.blk.smin, 0x7f, 2 * sizeof(int), h->stream));
+        for (int k = 0;; ++k) {
+            launch_hmb_schedule(h->stream, s.d, s.hm, s.blk, n, T, tick, k & 1);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(s.h_sched, s.blk.sched, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            const int tstar = s.h_sched[0], n_act = s.h_sched[1];
+            if (tstar <= 0 || tstar > T || n_act <= 0 || n_act > n || k >= T)
+                return fail(h, NBODY_ERR_HIP, "block steps: the schedule kernels reported an impossible block step");
+            HmActPlan plan;
+            {
+                ForceTimer t(h);
+                rc = hm_act_eval(h, s, s.hm.xp, s.hm.vp, n_act, &plan);
+            }
+            if (rc) return rc;
+            if (h->timed_this) h->stats.force_kernel_interactions += uint64_t(n_act) * uint64_t(n - 1);
+            launch_hmb_finish(h->stream, s.d, s.hm, s.blk, fast ? &plan : nullptr, n_act, s.g, T, L, tick, abs_dt, s.blk_eta, s.bnd);
+            HIP_TRY(h, hipGetLastError());
+            s.blk_steps += 1;
+            s.blk_updates += uint64_t(n_act);
+            if (tstar == T) break;   // commensurate steps: every body is due at T
+        }
+        launch_hm_compact(h->stream, s.d, s.hm, n, s.blk.level);   // retain, on the corrected positions; the levels travel along
+        s.count_dirty = true;
+        HIP_TRY(h, hipGetLastError());
+    }
+    s.elapsed += dt;
+    h->stats.steps += 1;
+    return NBODY_OK;
+}
+
 int hm_step(NbodyHandle* h, State& s, double dt) {
+    if (s.blk_L > 0 && dt != 0.0) return hm_block_step(h, s, dt);
     if (!s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     int rc = s.hm_valid ? NBODY_OK : hm_refresh(h, s);
     if (rc) return rc;
@@ -242,6 +358,7 @@ int hm_step(NbodyHandle* h, State& s, double dt) {
     if (rc) return rc;
     launch_hm_compact(h->stream, s.d, s.hm, int(s.n_local));     // retain, on the corrected positions
     s.count_dirty = true;
+    s.lv_valid = false;   // (a shared step does not carry block-step levels)
     HIP_TRY(h, hipGetLastError());
     s.elapsed += dt;
     h->stats.steps += 1;
@@ -517,9 +634,10 @@ void destroy(NbodyHandle* h) {
     s->tree.clear();
     void* dev[] = {s->d.pos_all, s->d.vel, s->d.acc, s->d.seg_count, s->d.escaped, s->d.keep, s->d.tile_state, s->d.epoch, s->d.inter,
                    s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes,
-                   s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->d_hm_planes};
+                   s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->d_hm_planes,
+                   s->blk.level, s->blk.tau, s->blk.list, s->blk.tile_count, s->blk.smin, s->blk.planes};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {s->h_count, s->h_aos, s->h_pos};
+    void* host[] = {s->h_count, s->h_aos, s->h_pos, s->h_sched};
     for (void* p : host) if (p) (void)hipHostFree(p);
     s->tree_bufs.release();
     s->split.release();
@@ -545,6 +663,14 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
         HIP_TRY(dst, hipMemcpyAsync(b.hm.jerk, a.hm.jerk, cap * sizeof(double4), hipMemcpyDeviceToDevice, dst->stream));
         b.integrator = a.integrator;
         b.hm_valid = a.hm_valid;
+        b.blk_eta = a.blk_eta; b.blk_L = a.blk_L;   // + the block-step setting, the levels and whether they are valid
+        if (a.blk_L > 0 && a.lv_valid) {
+            rc = ensure_block(dst, b);
+            if (rc) return rc;
+            HIP_TRY(dst, hipMemcpyAsync(b.blk.level, a.blk.level, cap * sizeof(int), hipMemcpyDeviceToDevice, dst->stream));
+            b.lv_valid = true;
+            b.lv_dt = a.lv_dt;
+        }
     }
     HIP_TRY(dst, hipStreamSynchronize(dst->stream));
     b.g = a.g; b.g_soft = a.g_soft; b.dt = a.dt; b.theta2 = a.theta2;
@@ -715,7 +841,14 @@ int steps(NbodyHandle* h, int k) {
 int update_forces(NbodyHandle* h) {
     State& s = *h->f64;
     if (h->cfg.method == NBODY_BARNES_HUT && !s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
-    if (s.integrator == NBODY_INTEGRATOR_HERMITE4) return hm_refresh(h, s);
+    if (s.integrator == NBODY_INTEGRATOR_HERMITE4) {
+        int rc = hm_refresh(h, s);
+        if (!rc && s.blk_L > 0) {   // + start levels for a macro step of the settings' dt
+            rc = sync_count(h, s);
+            if (!rc) rc = assign_levels(h, s, std::fabs(s.dt));
+        }
+        return rc;
+    }
     int rc = exchange(h, s);
     if (rc) return rc;
     return forces(h, s);
@@ -730,6 +863,93 @@ int set_integrator(NbodyHandle* h, int integrator) {   // (nbody_api.cpp has che
     }
     s.integrator = integrator;
     s.hm_valid = false;
+    s.lv_valid = false;
+    if (integrator != NBODY_INTEGRATOR_HERMITE4) { s.blk_eta = 0.0; s.blk_L = 0; }   // block steps are a setting of a Hermite handle
+    return NBODY_OK;
+}
+
+int set_block_steps(NbodyHandle* h, double eta, int max_level) {
+    State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_set_block_steps: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    const bool off = eta == 0.0 && max_level == 0;
+    if (!off && !(eta > 0.0 && max_level >= 1 && max_level <= 20))
+        return fail(h, NBODY_ERR_INVALID, "nbody_set_block_steps: eta must be > 0 and max_level in 1..20, or (0, 0) to switch block steps off");
+    if (!off) {
+        int rc = ensure_block(h, s);
+        if (rc) return rc;
+    }
+    s.blk_eta = off ? 0.0 : eta;
+    s.blk_L = off ? 0 : max_level;
+    s.lv_valid = false;
+    return NBODY_OK;
+}
+
+int get_block_steps(const NbodyHandle* h, double* eta, int* max_level) {
+    const State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return NBODY_ERR_INVALID;
+    if (eta) *eta = s.blk_eta;
+    if (max_level) *max_level = s.blk_L;
+    return NBODY_OK;
+}
+
+int download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out) {
+    State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_download_levels: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    if (s.blk_L == 0 || !s.hm_valid || !s.lv_valid)
+        return fail(h, NBODY_ERR_INVALID, "nbody_download_levels: the levels are invalid (block steps are off, or the next step or nbody_update_forces assigns them)");
+    int rc = sync_count(h, s);
+    if (rc) return rc;
+    const size_t n = s.n_local;
+    if (n_out) *n_out = n;
+    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "download buffer too small");
+    if (n == 0) return NBODY_OK;
+    if (!level) return fail(h, NBODY_ERR_INVALID, "null buffer");
+    static_assert(sizeof(int) == sizeof(int32_t), "levels are 32-bit");
+    HIP_TRY(h, hipMemcpyAsync(level, s.blk.level, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return NBODY_OK;
+}
+
+int block_step_counts(NbodyHandle* h, uint64_t out[2]) {
+    State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_block_step_counts: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    out[0] = s.blk_steps;
+    out[1] = s.blk_updates;
+    return NBODY_OK;
+}
+
+int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3) {
+    State& s = *h->f64;
+    if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_debug_hermite_forces_of: the handle runs the leapfrog integrator (nbody_set_integrator)");
+    int rc = sync_count(h, s);
+    if (rc) return rc;
+    const size_t n = s.n_local;
+    if (n_ids > n) return fail(h, NBODY_ERR_INVALID, "nbody_debug_hermite_forces_of: more ids than bodies (ids must be distinct and < n)");
+    if (n_ids == 0) return NBODY_OK;
+    if (!ids || !acc3 || !jerk3) return fail(h, NBODY_ERR_INVALID, "null buffer");
+    std::vector<unsigned char> seen(n, 0);
+    for (size_t k = 0; k < n_ids; ++k) {
+        if (ids[k] < 0 || size_t(ids[k]) >= n || seen[size_t(ids[k])]) return fail(h, NBODY_ERR_INVALID, "nbody_debug_hermite_forces_of: ids must be distinct and < n");
+        seen[size_t(ids[k])] = 1;
+    }
+    rc = ensure_block(h, s);
+    if (rc) return rc;
+    const int n_act = int(n_ids);
+    const int head[2] = {0, n_act};   // (list, sched, planes, a1 and j1 are scratch that every block step rewrites)
+    HIP_TRY(h, hipMemcpyAsync(s.blk.list, ids, n_ids * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(s.blk.sched, head, sizeof(head), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (pageable sources)
+    HmActPlan plan;
+    rc = hm_act_eval(h, s, s.d.pos, s.d.vel, n_act, &plan);
+    if (rc) return rc;
+    if (h->cfg.math_mode == NBODY_MATH_FAST) launch_hm_act_reduce(h->stream, s.d, s.hm, s.blk, plan, n_act, s.g);
+    HIP_TRY(h, hipGetLastError());
+    std::vector<double> ta(4 * n_ids), tj(4 * n_ids);
+    HIP_TRY(h, hipMemcpyAsync(ta.data(), s.hm.a1, n_ids * sizeof(double4), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(tj.data(), s.hm.j1, n_ids * sizeof(double4), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t k = 0; k < n_ids; ++k)
+        for (int c = 0; c < 3; ++c) { acc3[3 * k + c] = ta[4 * k + c]; jerk3[3 * k + c] = tj[4 * k + c]; }
     return NBODY_OK;
 }
 
@@ -798,6 +1018,7 @@ int stats(NbodyHandle* h, NbodyStats* out) {
 int reset_stats(NbodyHandle* h) {
     State& s = *h->f64;
     HIP_TRY(h, hipMemsetAsync(s.d.inter, 0, sizeof(unsigned long long), h->stream));
+    s.blk_steps = 0; s.blk_updates = 0;
     return NBODY_OK;
 }
 

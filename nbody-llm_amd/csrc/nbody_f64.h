@@ -30,6 +30,12 @@ int set_integrator(NbodyHandle* h, int integrator);
 int get_integrator(const NbodyHandle* h);
 int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out);
 int suggest_dt(NbodyHandle* h, double eta, double* dt_out);
+// block individual time steps of a Hermite handle (include/nbody_hip.h "block steps"); refused on a leapfrog handle
+int set_block_steps(NbodyHandle* h, double eta, int max_level);
+int get_block_steps(const NbodyHandle* h, double* eta, int* max_level);
+int download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out);
+int block_step_counts(NbodyHandle* h, uint64_t out[2]);
+int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3);
 int tree_export(NbodyHandle* h, double* com_mass, double* width, int32_t* skip, size_t cap, size_t* n_nodes);
 
 }  // namespace nbody64

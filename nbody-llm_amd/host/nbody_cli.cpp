@@ -24,13 +24,15 @@ static void usage() {
                  "usage: nbody_cli [-t threads] [-n points] [--method bh|bf] [--ic disc|plummer] [--steps K]\n"
                  "                 [--math fast|strict] [--tree auto|host|device] [--leaf reference|direct]\n"
                  "                 [--dtype f32|f64] [--dt x] [--g-soft x] [--theta2 x]\n"
-                 "                 [--width w] [--seed s] [--integrator device|leapfrog|host|hermite] [--dump file] [--multipole 1|2]\n");
+                 "                 [--width w] [--seed s] [--integrator device|leapfrog|host|hermite] [--dump file] [--multipole 1|2]\n"
+                 "                 [--block-steps ETA:LEVELS]   (with --integrator hermite: block individual time steps)\n");
 }
 
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
-               double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole) {
+               double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
+               double block_eta, int block_levels) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -54,6 +56,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         sim->settings_mut().theta2 = F(theta2);
         if (multipole != NBODY_MULTIPOLE_MONOPOLE) sim->set_multipole(multipole);   // (refused where it does not apply: nbody_hip.h)
         if (integrator == "hermite") sim->set_integrator(NBODY_INTEGRATOR_HERMITE4);
+        if (block_levels > 0) sim->set_block_steps(block_eta, block_levels);   // every --dt is then a macro step of 2^LEVELS ticks
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
         auto start = std::chrono::steady_clock::now();
@@ -70,6 +73,11 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         std::printf("Performance: %.2f steps/second\n", double(steps) / secs);
         NbodyStats st = sim->stats();
         std::printf("Bodies left: %zu  interactions/second: %.4e\n", sim->get_points().size(), double(st.interactions) / secs);
+        if (block_levels > 0) {
+            uint64_t counts[2] = {0, 0};
+            sim->block_step_counts(counts);
+            std::printf("Block steps: %llu  body updates: %llu\n", (unsigned long long)counts[0], (unsigned long long)counts[1]);
+        }
         if (!dump.empty()) {
             std::FILE* f = std::fopen(dump.c_str(), "wb");
             if (!f) { std::fprintf(stderr, "cannot write %s\n", dump.c_str()); return 1; }
@@ -90,6 +98,9 @@ int main(int argc, char** argv) {
     unsigned long long seed = 20250523ull;
     int multipole = NBODY_MULTIPOLE_MONOPOLE;
     bool width_set = false;
+    double block_eta = 0.0;
+    int block_levels = 0;
+    bool block_set = false;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -109,6 +120,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--integrator")) integrator = next();
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--block-steps")) {
+            char* end = nullptr;
+            const char* arg = next();
+            block_eta = std::strtod(arg, &end);
+            if (end == arg || *end != ':' || !(block_eta > 0.0)) { usage(); return 2; }
+            block_levels = std::atoi(end + 1);
+            if (block_levels < 1 || block_levels > 20) { usage(); return 2; }
+            block_set = true;
+        }
         else { usage(); return 2; }
     }
     if (integrator != "device" && integrator != "leapfrog" && integrator != "host" && integrator != "hermite") { usage(); return 2; }
@@ -116,7 +136,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--integrator hermite needs --dtype f64 and --method bf\n");
         return 2;
     }
+    if (block_set && integrator != "hermite") {
+        std::fprintf(stderr, "--block-steps needs --integrator hermite\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels);
 }

@@ -176,6 +176,19 @@ public:
     // NBODY_INTEGRATOR_HERMITE4 on brute-force f64 handles of a one-rank world
     void set_integrator(int integrator) { check(nbody_set_integrator(h_, integrator)); }
     int integrator() const { int which = 0; check(nbody_get_integrator(h_, &which)); return which; }
+    // block individual time steps of a Hermite handle (nbody_set_block_steps): eta > 0 and 1 <= max_level <= 20 switch them on,
+    // (0, 0) off; step_by(dt) is then a macro step of 2^max_level ticks and steps() synchronises with the host
+    void set_block_steps(double eta, int max_level) { check(nbody_set_block_steps(h_, eta, max_level)); }
+    void block_steps(double* eta, int* max_level) const { check(nbody_get_block_steps(h_, eta, max_level)); }
+    std::vector<int32_t> levels() {   // per body, in get_points() order; refused while the levels are invalid
+        size_t n = 0;
+        check(nbody_count(h_, &n));
+        std::vector<int32_t> out(n);
+        check(nbody_download_levels(h_, out.data(), out.size(), &n));
+        out.resize(n);
+        return out;
+    }
+    void block_step_counts(uint64_t out[2]) { check(nbody_block_step_counts(h_, out)); }   // {block steps, body updates}
     NbodyHandle* handle() { return h_; }
 
 protected:
