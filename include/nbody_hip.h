@@ -385,6 +385,65 @@ int nbody_block_step_counts(NbodyHandle* h, uint64_t out[2]);
 /* test hook: F = (a, j) as [n_ids][3] f64 at the handle's CURRENT (x, v) for the listed bodies, through the active-set
  * kernels of the handle's math mode; ids distinct and < n, else NBODY_ERR_INVALID; leaves no trace in state or statistics */
 int nbody_debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3);
+/* ---- tracers: massless particles that ride in the bodies' field (no reference counterpart) ------------------------
+ * A handle may hold, beside its bodies, a second vector of M TRACERS (PointParticle records; the mass field is ignored on
+ * upload and written as 0 on download).  Tracers feel the bodies and exert nothing.  They are not bodies: they are in no tree,
+ * they are not counted by nbody_count, nbody_download, nbody_energy*, nbody_potentials or nbody_field_at, they do not change
+ * NbodyStats, and they never act on a body or on each other.  A handle that never uploads tracers runs the code it ran
+ * before untouched, and one that uploads a tracer set and then an empty one without a step in between gives the bits of a
+ * handle that never did.
+ *   One nbody_step_by(dt) with tracers runs the reference's leapfrog (shared.rs:106-149) on BOTH vectors:
+ *     1. half drift of bodies and tracers, x += (v * 0.5) * dt;
+ *     2. retain of both by Bounds::contains (inclusive walls, a NaN is outside), order preserved, each vector on its own;
+ *     3. the body force pass exactly as without tracers;
+ *     4. the tracer force pass over the retained, half-drifted bodies;
+ *     5. kick + half drift of both.
+ * (The brute-force passes 3 and 4 read the same positions and write disjoint state; the library enqueues 4 first.  Under
+ * Barnes-Hut 4 reads the tree of 3, not the bodies, and follows it.)
+ * nbody_update_forces evaluates the tracers' accelerations too.  nbody_steps(k) gives the bits of k nbody_step_by calls and
+ * stays enqueue-only: the live tracer count after a retain stays on the device, and launches are sized from the host's upper
+ * bound, as for the bodies.  nbody_clone carries the tracers; nbody_upload of bodies leaves them alone.
+ *   The tracer force pass, brute force:
+ *     NBODY_MATH_STRICT  the strict body kernel's expression with no self index: a = 0, then for bodies j ascending
+ *                        r = p_t - p_j, d = sqrt((rx rx + ry ry) + rz rz + g_soft^2), f = g / ((d d) d), a_c -= (r_c f) m_j;
+ *                        no contraction, IEEE sqrt and divide.  These are the bits a zero-mass body appended after the
+ *                        bodies gets from the reference's loop (brute_force.rs:64-82), as long as no two tracers coincide
+ *                        (two coincident massless bodies give 0 * inf there when g_soft = 0; tracers never meet each other).
+ *                        A tracer exactly on a body with g_soft = 0 gets NaN, as that appended body would.
+ *     NBODY_MATH_FAST    the fast body kernel's pair arithmetic: d = p_j - p_t, an FMA chain into r2 = |d|^2 + g_soft^2,
+ *                        v_rsq_f32, (m_j rinv) (rinv rinv), FMAs into three f32 sums, a = g * sum.  The body range is cut into
+ *                        K slices (nbody_host_tracer_plan) whose partial sums are added in slice order.  No atomics: the same
+ *                        input gives the same bits, and permuting the tracers permutes the results bit for bit.  Each
+ *                        tracer is within (16 + n) 2^-24 g T of the exact sum, n = bodies, T = the sum of its terms'
+ *                        magnitudes (tests/tracer_ref.py counts the roundings).
+ *                        The plan is drawn from the tracer and body counts at their uploads, not from the live counts, so
+ *                        the bits do not depend on when the caller reads a count back.
+ *   The tracer force pass, Barnes-Hut (either math mode, either tree build): the tracers walk the tree the body force pass
+ * has just built, before anything overwrites it.  They are visited in the Morton order of their positions and use the force
+ * walk's opening tests (r2 = (x x + y y) + z z in f32 without contraction, w^2 < theta2 r2) and the handle's leaf rule: under
+ * NBODY_LEAF_REFERENCE a leaf that fails the test adds nothing, under NBODY_LEAF_DIRECT a leaf is always added and a cell whose
+ * centre of mass lies within 1e-5 of the tracer is skipped whole.  Every accepted node adds the fast walk's monopole term
+ * (g m) rsq(r2 + g_soft^2)^3 (c - p) into three f32 sums; partial sums over runs of the walk's node-range segments are added in
+ * run order, with no atomics.  The multipole setting does not apply: tracers walk MONOPOLES whatever nbody_set_multipole says,
+ * and NBODY_MATH_STRICT handles use the same term.  There is no bit-exact claim here (zero-mass bodies would change the
+ * reference's tree); a tracer is within 4.5e-6 T of the f64 sum of its own node list (tests/bh_list.py).  With the device
+ * build the steps stay enqueue-only.
+ *   Accepted on NBODY_F32, world_size == 1 handles of both methods.  NBODY_F64 handles and handles of a multi-rank world get
+ * NBODY_ERR_INVALID from every tracer call: they are deliberately out of scope.  nbody_last_error names the call. */
+/* Replaces the tracer set; n == 0 removes it.  capacity = the most tracers the handle may ever hold, 0 means n; n > capacity:
+ * NBODY_ERR_CAPACITY. */
+int nbody_tracers_upload(NbodyHandle* h, const void* aos, size_t n, size_t stride_bytes, size_t capacity);
+/* Reads the live tracers back in vector order; the acc field holds the last tracer force pass, the mass field 0. */
+int nbody_tracers_download(NbodyHandle* h, void* aos, size_t cap, size_t stride_bytes, size_t* n_out);
+/* Number of live tracers. */
+int nbody_tracers_count(NbodyHandle* h, size_t* n_out);
+/* out = {directed interactions (live tracers x live bodies per pass; Barnes-Hut: accepted nodes), opening tests (0 under brute
+ * force)} over the tracer force passes since nbody_reset_stats, counted on the device. */
+int nbody_tracer_stats(NbodyHandle* h, uint64_t out[2]);
+/* Host-only (no device needed), like nbody_host_launch_plan: the fast tracer pass's shape for n_tracers tracers and n_bodies
+ * bodies; out = {tracers per lane, tracer groups (of 256 x tracers per lane), body slices K, slice length}.  Slice k covers
+ * bodies [k * length, min(n_bodies, (k + 1) * length)). */
+int nbody_host_tracer_plan(size_t n_tracers, size_t n_bodies, int out[4]);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

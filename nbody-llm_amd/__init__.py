@@ -63,6 +63,7 @@ SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ran
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
+    "nbody_tracers_upload", "nbody_tracers_download", "nbody_tracers_count", "nbody_tracer_stats", "nbody_host_tracer_plan",
     "nbody_create", "nbody_destroy", "nbody_clone", "nbody_upload", "nbody_download", "nbody_count",
     "nbody_count_global", "nbody_add_point", "nbody_remove_point", "nbody_set_settings", "nbody_get_settings",
     "nbody_set_bounds", "nbody_init", "nbody_step_by", "nbody_steps", "nbody_update_forces", "nbody_elapsed",
@@ -194,6 +195,11 @@ _sig("nbody_debug_let_bounds", _i, _H, C.c_void_p)
 _sig("nbody_debug_let_set_balance", _i, _H, _i)
 _sig("nbody_host_exchange_layout", _i, C.c_void_p, _i, _i, C.c_longlong, _i, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_sz))
 _sig("nbody_host_launch_plan", _i, _sz, _f, _i, C.POINTER(_i))
+_sig("nbody_tracers_upload", _i, _H, C.c_void_p, _sz, _sz, _sz)
+_sig("nbody_tracers_download", _i, _H, C.c_void_p, _sz, _sz, C.POINTER(_sz))
+_sig("nbody_tracers_count", _i, _H, C.POINTER(_sz))
+_sig("nbody_tracer_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_host_tracer_plan", _i, _sz, _sz, C.POINTER(_i))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -228,6 +234,16 @@ def launch_plan(n_bodies: int, theta2: float = 0.25, fast_math: bool = True) -> 
     if rc != 0:
         raise NbodyError(rc, "nbody_host_launch_plan")
     return {"walk_bodies_per_lane": out[0], "walk_segments": out[1], "sym_bodies_per_lane": out[2]}
+
+
+def host_tracer_plan(n_tracers: int, n_bodies: int) -> dict:
+    """The fast tracer pass's shape for that many tracers and bodies (nbody_host_tracer_plan; no device needed): slice k of
+    the bodies is [k * slice_len, min(n_bodies, (k + 1) * slice_len))."""
+    out = (C.c_int * 4)()
+    rc = lib.nbody_host_tracer_plan(int(n_tracers), int(n_bodies), out)
+    if rc != 0:
+        raise NbodyError(rc, "nbody_host_tracer_plan")
+    return {"tracers_per_lane": out[0], "groups": out[1], "slices": out[2], "slice_len": out[3]}
 
 
 def is_tuning_build() -> bool:
@@ -394,6 +410,32 @@ class Simulation:
         out = np.zeros(n.value, dtype=self.dtype)
         self._check(lib.nbody_download(self._h, out.ctypes.data, n.value, self.dtype.itemsize, C.byref(n)))
         return out[: n.value]
+
+    # -- tracers: massless particles in the bodies' field (nbody_tracers_*; PointParticle<f32,3> records, mass ignored)
+    def set_tracers(self, rec: np.ndarray, capacity: int | None = None):
+        """Replace the tracer set (an empty array removes it); capacity = the most tracers the handle may ever hold."""
+        rec = np.ascontiguousarray(rec, dtype=PARTICLE_DTYPE)
+        self._check(lib.nbody_tracers_upload(self._h, rec.ctypes.data, rec.shape[0], PARTICLE_DTYPE.itemsize, int(capacity or 0)))
+
+    def get_tracers(self) -> np.ndarray:
+        """The live tracers; `acceleration` holds the last tracer force pass, `mass` 0."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_tracers_count(self._h, C.byref(n)))
+        out = np.zeros(n.value, dtype=PARTICLE_DTYPE)
+        self._check(lib.nbody_tracers_download(self._h, out.ctypes.data, n.value, PARTICLE_DTYPE.itemsize, C.byref(n)))
+        return out[: n.value]
+
+    @property
+    def n_tracers(self) -> int:
+        n = C.c_size_t(0)
+        self._check(lib.nbody_tracers_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def tracer_stats(self) -> tuple[int, int]:
+        """(directed interactions, or accepted nodes under Barnes-Hut; opening tests) of the tracer force passes since reset_stats."""
+        out = (C.c_uint64 * 2)()
+        self._check(lib.nbody_tracer_stats(self._h, out))
+        return int(out[0]), int(out[1])
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

@@ -20,6 +20,9 @@
 #include "kernels.h"
 #include "kernels_pot.h"
 #include "kernels_field.h"
+#include "kernels_tracer.h"
+
+#include <algorithm>
 
 namespace nbody {
 
@@ -1313,6 +1316,130 @@ void launch_bh_field_walk(hipStream_t s, const FieldTree& t, const double* xyz, 
 #define FIELD_WALK(V, S) hipLaunchKernelGGL((k_bh_field_walk<V, S>), grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
     if (want == 3) FIELD_WALK(true, true); else if (want == 1) FIELD_WALK(true, false); else if (want == 2) FIELD_WALK(false, true); else FIELD_WALK(false, false);
 #undef FIELD_WALK
+}
+
+// ---- tracers on a Barnes-Hut handle (kernels_tracer.h): k_bh_walk<FAST = true, DIRECT> for particles that are in no tree.
+// Lane t walks tracer idx[t] (the live tracers in Morton order) over the nodes the body pass just built, with that walk's
+// opening tests (r2 in f32 without contraction, w^2 < theta2 r2), the handle's leaf rule and the fast walk's monopole term,
+// summed in f32.  The body walk's K node-range segments are taken in `groups` runs of consecutive segments, run y being
+// segments [K y / groups, K (y + 1) / groups): a walk that enters at the run's first split point and ends at its last visits
+// exactly the nodes the K single segments would, in the same order.  groups == 1: the lane holds the whole sum, stores it
+// and takes the kick + half drift along; groups > 1: every (run, tracer) entry of the planes is written once and
+// k_tr_bh_reduce adds them in run order.  No atomics on the sums.  A tracer has no leaf of its own, so under the reference
+// rule nothing is skipped, and under NBODY_LEAF_DIRECT a tracer within 1e-5 of a cell's centre of mass skips that cell, as a
+// body would.  {accepted, visited} go to the tracer statistics, one atomic pair per wave over kCounterSlots slots.
+__device__ __forceinline__ void tr_bh_kick_drift(float4* __restrict__ pos, float4* __restrict__ vel, int b, float ax, float ay, float az, float dt) {
+    float4 p = pos[b], v = vel[b];
+    v.x += ax * dt;                 // shared.rs:144
+    v.y += ay * dt;
+    v.z += az * dt;
+    p.x += (v.x * 0.5f) * dt;       // shared.rs:146
+    p.y += (v.y * 0.5f) * dt;
+    p.z += (v.z * 0.5f) * dt;
+    vel[b] = v;
+    pos[b] = p;
+}
+
+template <bool DIRECT>
+__global__ __launch_bounds__(kWalkBlock) void k_tr_bh_walk(const NodeDev* __restrict__ nodes, const int* __restrict__ idx, int m_upper,
+                                                           const int* __restrict__ m_dev, float4* __restrict__ tr_pos,
+                                                           float4* __restrict__ tr_vel, float4* __restrict__ tr_acc, float g, float eps2,
+                                                           float theta2, unsigned long long* __restrict__ counters, WalkSplit split,
+                                                           int do_kick, float dt) {
+    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
+    if (split.poison && *split.poison) return;
+    const int m = min(m_upper, *m_dev);
+    const int K = split.n_seg, groups = gridDim.y;   // groups <= K: no run is empty
+    const int k0 = int((long long)K * blockIdx.y / groups), k1 = int((long long)K * (blockIdx.y + 1) / groups);
+    const int s1 = split.first[k1];
+    unsigned int n_acc = 0, n_vis = 0;
+    if (t < m) {
+        const int b = idx[t];
+        const float4 p = tr_pos[b];
+        float ax = 0.f, ay = 0.f, az = 0.f;
+        int i = walk_entry<DIRECT>(nodes, split, k0, p, theta2);
+        while (i < s1) {
+            const float4 A = nodes[i].a;
+            const float2 B = *reinterpret_cast<const float2*>(&nodes[i].b);
+            asm volatile("" :: "v"(A.w), "v"(B.y));   // (both loads whole and ahead of the branches: see k_bh_walk)
+            const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
+            const float r2 = (rx * rx + ry * ry) + rz * rz;
+            const int skip = __float_as_int(B.y);
+            ++n_vis;
+            if (DIRECT && r2 < 1e-10f) { i = skip; continue; }
+            if (B.x < theta2 * r2 || (DIRECT && skip == i + 1)) {
+                const float rinv = __builtin_amdgcn_rsqf(r2 + eps2);
+                const float k = (g * A.w) * ((rinv * rinv) * rinv);
+                ax += rx * k; ay += ry * k; az += rz * k;
+                ++n_acc;
+                i = skip;
+            } else {
+                i = i + 1;
+            }
+        }
+        if (groups > 1) {
+            split.planes[size_t(blockIdx.y) * split.plane_stride + t] = make_float4(ax, ay, az, 0.f);
+        } else {
+            tr_acc[b] = make_float4(ax, ay, az, 0.f);
+            if (do_kick) tr_bh_kick_drift(tr_pos, tr_vel, b, ax, ay, az, dt);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_acc += __shfl_down(n_acc, off);
+        n_vis += __shfl_down(n_vis, off);
+    }
+    if ((threadIdx.x & 63) == 0 && counters) {
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
+        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_tr_bh_reduce(const float4* __restrict__ planes, int groups, size_t plane_stride,
+                                                      const int* __restrict__ idx, int m_upper, const int* __restrict__ m_dev,
+                                                      float4* __restrict__ tr_pos, float4* __restrict__ tr_vel,
+                                                      float4* __restrict__ tr_acc, int do_kick, float dt, const int* __restrict__ poison) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (poison && *poison) return;
+    if (t >= min(m_upper, *m_dev)) return;
+    float sx = 0.f, sy = 0.f, sz = 0.f;
+    for (int k = 0; k < groups; ++k) {   // run order = the order one walk over the whole range adds them in
+        const float4 v = planes[size_t(k) * plane_stride + t];
+        sx += v.x; sy += v.y; sz += v.z;
+    }
+    const int b = idx[t];
+    tr_acc[b] = make_float4(sx, sy, sz, 0.f);
+    if (do_kick) tr_bh_kick_drift(tr_pos, tr_vel, b, sx, sy, sz, dt);
+}
+
+int tracer_walk_groups(size_t m_upper, int n_split) {
+    // as many runs as bring the launch to ~16 384 waves (8 per SIMD of 256 CUs), at most the body walk's segments
+    const size_t waves = std::max<size_t>(1, (m_upper + kWalkBlock - 1) / kWalkBlock);
+    const size_t want = (16384 + waves - 1) / waves;
+    return int(std::max<size_t>(1, std::min<size_t>(want, size_t(std::max(n_split, 1)))));
+}
+
+void launch_tr_bh_walk(hipStream_t s, const Shard& tr, int m_upper, const int* idx, const TreeDev& t, int groups, float4* planes,
+                       size_t plane_stride, float g, float g_soft2, float theta2, int leaf_direct, const float* kick_dt,
+                       unsigned long long* counters) {
+    if (m_upper <= 0) return;
+    WalkSplit sp{};
+    sp.n_seg = t.n_split; sp.first = t.split_first; sp.anc = t.split_anc; sp.n_anc = t.split_n_anc;
+    sp.planes = planes; sp.plane_stride = plane_stride;
+    sp.poison = t.poison;
+    const dim3 grid((m_upper + kWalkBlock - 1) / kWalkBlock, groups);
+    const NodeDev* nodes = reinterpret_cast<const NodeDev*>(t.nodes);
+    const int do_kick = kick_dt ? 1 : 0;
+    const float dt = kick_dt ? *kick_dt : 0.f;
+    if (leaf_direct)
+        hipLaunchKernelGGL(k_tr_bh_walk<true>, grid, dim3(kWalkBlock), 0, s, nodes, idx, m_upper, tr.own_count(), tr.own_pos(), tr.vel, tr.acc, g,
+                           g_soft2, theta2, counters, sp, do_kick, dt);
+    else
+        hipLaunchKernelGGL(k_tr_bh_walk<false>, grid, dim3(kWalkBlock), 0, s, nodes, idx, m_upper, tr.own_count(), tr.own_pos(), tr.vel, tr.acc, g,
+                           g_soft2, theta2, counters, sp, do_kick, dt);
+    if (groups > 1)
+        hipLaunchKernelGGL(k_tr_bh_reduce, dim3((m_upper + 255) / 256), dim3(256), 0, s, planes, groups, plane_stride, idx, m_upper, tr.own_count(),
+                           tr.own_pos(), tr.vel, tr.acc, do_kick, dt, t.poison);
 }
 
 }  // namespace nbody

@@ -861,6 +861,28 @@ int field_sort_probes(hipStream_t s, const double* xyz, int n, int f64, const do
     return 0;
 }
 
+// ---- tracers on a Barnes-Hut handle: the live tracers in tree order.  Their positions are float4 with the count on the device,
+// which is the build's own key kernel's input (k_tree_keys: the same orthant_key as k_field_keys, the unused tail keyed all
+// ones), followed by the sort the field probes use, over all 64 bits so that the tail stays behind every live tracer.
+size_t tracer_sort_tmp_bytes(size_t n_cap) {
+    size_t b = 0;
+    unsigned long long* k = nullptr; int* v = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_cap, 0, 64, 0);
+    return (b + 255) / 256 * 256;
+}
+
+int tracer_sort(hipStream_t s, const float4* pos, const int* d_count, int n_upper, const float center[3], float width, void* tmp, size_t tmp_bytes,
+                unsigned long long* keys, int* idx, size_t n_cap, int* scratch_info, const int** sorted_idx) {
+    *sorted_idx = idx + n_cap;
+    if (n_upper <= 0) return 0;
+    // (scratch_info [3]: k_tree_keys clears a build's node count and flags through it; [2] takes the group counter it is handed)
+    hipLaunchKernelGGL((k_tree_keys<float4, float>), dim3((n_upper + 255) / 256), dim3(256), 0, s, pos, d_count, n_upper, center[0], center[1], center[2],
+                       width, keys, idx, scratch_info, scratch_info + 2);
+    size_t tb = tmp_bytes;
+    if (rocprim::radix_sort_pairs(tmp, tb, keys, keys + n_cap, idx, idx + n_cap, size_t(n_upper), 0, 64, s) != hipSuccess) return -1;
+    return 0;
+}
+
 // bytes at the start of the build workspace that rocPRIM uses as scratch (free between builds)
 size_t tree_build_tmp_bytes(size_t n_cap) { return scratch_bytes(n_cap); }
 

@@ -10,6 +10,7 @@
 #include "nbody_let.h"
 #include "nbody_pot.h"
 #include "nbody_field.h"
+#include "nbody_tracer.h"
 
 #include <algorithm>
 #include <chrono>
@@ -44,17 +45,6 @@ void compute_bounds(NbodyHandle* h) {
         h->bnd.lo[i] = h->center[i] + (-hw);  // add_scalar(-half_width), shared.rs:224
         h->bnd.hi[i] = h->center[i] + hw;     // shared.rs:228
     }
-}
-
-int ensure_aos(NbodyHandle* h, size_t records) {
-    if (records <= h->aos_cap) return NBODY_OK;
-    if (h->d_aos) (void)hipFree(h->d_aos);
-    if (h->h_aos) (void)hipHostFree(h->h_aos);
-    h->d_aos = nullptr; h->h_aos = nullptr; h->aos_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_aos, records * 10 * sizeof(float)));
-    HIP_TRY(h, hipHostMalloc(&h->h_aos, records * 10 * sizeof(float), hipHostMallocDefault));
-    h->aos_cap = records;
-    return NBODY_OK;
 }
 
 // refresh the host view of the own count (one 4-byte D2H + sync), only when it may be stale
@@ -496,7 +486,7 @@ int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
                                    h->cfg.leaf_mode == NBODY_LEAF_DIRECT, h->kick_pending ? &h->kick_dt : nullptr, &kicked);
         if (kicked) h->kick_pending = false;
         HIP_TRY(h, hipGetLastError());
-        return NBODY_OK;
+        return nbody::tracer::tree_forces(h, td);   // (tracers walk monopoles whatever the multipole setting)
     }
     int rc = ensure_nested_stack(h, &td);
     if (!rc) rc = setup_lds_walk(h, &td, n_tree);
@@ -511,7 +501,7 @@ int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
     }
     if (td.hot_cap > 0) HIP_TRY(h, hipMemcpyAsync(h->h_hot_info, h->d_hot_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipGetLastError());
-    return NBODY_OK;
+    return nbody::tracer::tree_forces(h, td);   // the tracers' walk of the same tree, before anything overwrites it
 }
 
 int bh_forces(NbodyHandle* h) {
@@ -775,6 +765,7 @@ int step_begin(NbodyHandle* h, float dt) {
     nbody::launch_compact(h->stream, h->sh, int(h->n_local));                 // retain
     h->count_dirty = true;
     HIP_TRY(h, hipGetLastError());
+    if (nbody::tracer::on(h)) return nbody::tracer::drift_retain(h, dt);      // the same two on the tracer vector
     return NBODY_OK;
 }
 
@@ -782,7 +773,16 @@ int step_begin(NbodyHandle* h, float dt) {
 int step_forces(NbodyHandle* h, float dt) {
     h->kick_pending = true;   // a force pass that ends in a plane reduction applies the kick itself
     h->kick_dt = dt;
+    if (nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE) {
+        // the tracers' force pass over the half-drifted, retained bodies, with the tracers' kick + half drift.  It reads the
+        // bodies' positions and writes tracer state only, so it goes BEFORE the body pass, whose tail may move the bodies
+        int rc = nbody::tracer::forces(h, &h->kick_dt);
+        if (rc) { h->kick_pending = false; return rc; }
+    }
+    // (Barnes-Hut: the tracers walk the tree this pass builds, right after the bodies' walk: walk_tree)
+    h->tr.kick_pending = nbody::tracer::on(h);
     int rc = forces_begin(h);                                                  // update_forces
+    h->tr.kick_pending = false;
     if (rc) { h->kick_pending = false; h->tail_pending = false; }
     return rc;
 }
@@ -982,6 +982,7 @@ void free_all(NbodyHandle* h) {
     h->tree.clear();
     nbody64::destroy(h);
     nbody::let::destroy(h);
+    nbody::tracer::release(h);
     void* dev[] = {h->sh.pos_all, h->sh.vel, h->sh.acc, h->sh.seg_count, h->sh.escaped, h->sh.keep, h->sh.tile_state, h->sh.epoch, h->sh.inter, h->d_poison, h->d_aos,
                    h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
     for (void* p : dev) if (p) (void)hipFree(p);
@@ -1211,6 +1212,8 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
         rc = nbody::let::clone_state(s, h);
         if (rc) { g_create_err = h->err; free_all(h); return rc; }
     }
+    rc = nbody::tracer::clone_state(s, h);
+    if (rc) { g_create_err = h->err; free_all(h); return rc; }
     // like the reference's BH clone (barnes_hut.rs:113-135) the tree is not carried over; neither
     // are the communicator (call nbody_comm_init on the clone) and the statistics
     *out = h;
@@ -1466,11 +1469,65 @@ int nbody_update_forces(NbodyHandle* h) {
     rc = exchange_begin(h);
     if (rc) return rc;
     rc = forces(h);
+    if (!rc && nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE) rc = nbody::tracer::forces(h, nullptr);   // (Barnes-Hut: inside the pass, walk_tree)
     if (rc || !h->last_step_async) return rc;
     h->last_step_async = false;
     rc = resolve_async(h);              // (a force pass outside a step is confirmed at once)
     if (rc || !h->host_tree_once) return rc;
     return forces(h);                   // its build needed the host: once more, on the host-built tree
+}
+
+// ---- tracers (nbody_tracer.cpp)
+namespace {
+// binds the device, refuses the handles that take no tracers, naming the entry point, and confirms the steps enqueued without
+// a read-back (a poisoned run is replayed first: the tracers ride in those steps, so every reader and the upload come after them,
+// like nbody_download, nbody_count, nbody_stats and nbody_upload on the bodies' side)
+int tracer_enter(NbodyHandle* h, const char* call) {
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (const char* why = nbody::tracer::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return resolve_async(h);
+}
+}  // namespace
+
+int nbody_tracers_upload(NbodyHandle* h, const void* aos, size_t n, size_t stride, size_t capacity) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = tracer_enter(h, "nbody_tracers_upload");
+    if (rc) return rc;
+    if (!aos && n) return fail(h, NBODY_ERR_INVALID, "nbody_tracers_upload: null argument");
+    if (stride < 40 || stride % 4) return fail(h, NBODY_ERR_INVALID, "nbody_tracers_upload: stride must be a multiple of 4 and >= 40 bytes");
+    return nbody::tracer::upload(h, aos, n, stride, capacity);
+}
+
+int nbody_tracers_download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = tracer_enter(h, "nbody_tracers_download");
+    if (rc) return rc;
+    if (stride < 40 || stride % 4) return fail(h, NBODY_ERR_INVALID, "nbody_tracers_download: stride must be a multiple of 4 and >= 40 bytes");
+    return nbody::tracer::download(h, aos, cap, stride, n_out);
+}
+
+int nbody_tracers_count(NbodyHandle* h, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = tracer_enter(h, "nbody_tracers_count");
+    if (rc) return rc;
+    if (!n_out) return fail(h, NBODY_ERR_INVALID, "nbody_tracers_count: null argument");
+    return nbody::tracer::count(h, n_out);
+}
+
+int nbody_tracer_stats(NbodyHandle* h, uint64_t out[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = tracer_enter(h, "nbody_tracer_stats");
+    if (rc) return rc;
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_tracer_stats: null argument");
+    return nbody::tracer::stats(h, out);
+}
+
+int nbody_host_tracer_plan(size_t n_tracers, size_t n_bodies, int out[4]) {
+    if (!out) return NBODY_ERR_INVALID;
+    const nbody::TracerPlan p = nbody::tracer_plan(n_tracers, n_bodies);
+    out[0] = p.ipt; out[1] = p.groups; out[2] = p.K; out[3] = p.slice_len;
+    return NBODY_OK;
 }
 
 int nbody_elapsed(const NbodyHandle* h, float* out) {
@@ -1513,7 +1570,7 @@ int nbody_stats(NbodyHandle* h, NbodyStats* out) {
     if (rc) return rc;
     if (h->f64) return nbody64::stats(h, out);
     if (h->cfg.method == NBODY_BRUTE_FORCE) {
-        unsigned long long* hv = reinterpret_cast<unsigned long long*>(h->h_poison + 4);   // (pinned scratch)
+        unsigned long long* hv = reinterpret_cast<unsigned long long*>(h->h_poison + kScratchStats);
         HIP_TRY(h, hipMemcpyAsync(hv, h->sh.inter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         h->stats.interactions = *hv;
@@ -1545,6 +1602,8 @@ int nbody_reset_stats(NbodyHandle* h) {
     if (h->let) { rc = nbody::let::reset_stats(h); if (rc) return rc; }
     if (h->f64) { rc = nbody64::reset_stats(h); if (rc) return rc; }
     else HIP_TRY(h, hipMemsetAsync(h->sh.inter, 0, sizeof(unsigned long long), h->stream));
+    rc = nbody::tracer::reset_stats(h);
+    if (rc) return rc;
     if (h->d_counters) {
         HIP_TRY(h, hipMemsetAsync(h->d_counters, 0, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -997,7 +997,7 @@ double elapsed(const NbodyHandle* h) { return h->f64->elapsed; }
 int stats(NbodyHandle* h, NbodyStats* out) {
     State& s = *h->f64;
     if (h->cfg.method == NBODY_BRUTE_FORCE) {
-        unsigned long long* hv = reinterpret_cast<unsigned long long*>(h->h_poison + 4);   // (pinned scratch)
+        unsigned long long* hv = reinterpret_cast<unsigned long long*>(h->h_poison + kScratchStats);
         HIP_TRY(h, hipMemcpyAsync(hv, s.d.inter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         h->stats.interactions = *hv;

@@ -255,6 +255,28 @@ struct FieldBufs {
     }
 };
 
+// nbody_tracers_* (nbody_tracer.cpp): massless particles beside the bodies.  Their state is a second Shard of one segment, so
+// the integrate and compact kernels run on it unchanged; n_host == 0 (no tracers) keeps every step path as it was.
+struct TracerState {
+    Shard sh;                    // pos (.w = 0), vel, acc, count, escape flag, keep flags, compaction words; the bodies' poison flag, no ids
+    size_t cap = 0;              // tracers the arrays hold
+    size_t n_host = 0;           // host view of the live count: exact after an upload or a read-back, an upper bound after a step
+    bool dirty = false;          // a retain may have dropped tracers since n_host was read
+    float4* d_planes = nullptr;  // [K][padded tracers] partial sums of the fast pass's body slices, grow-only
+    size_t planes_cap = 0;       // float4 entries
+    unsigned long long* d_stats = nullptr;   // [NBODY_WALK_COUNTER_SLOTS][2] directed interactions or accepted nodes, opening tests of the tracer passes
+    // the tracer count at the upload: the fast passes' shapes are drawn from it (and the bodies' n_at_upload), not from
+    // n_host / n_local, which a read-back refreshes
+    size_t n_plan = 0;
+    // Barnes-Hut handles: the tracers in tree order (keys and indices, unsorted | sorted), rocPRIM's scratch, the key kernel's info words
+    unsigned long long* d_keys = nullptr;    // [2][sort_cap]
+    int* d_idx = nullptr;                    // [2][sort_cap]
+    void* d_sort_tmp = nullptr;
+    int* d_info = nullptr;                   // [3]
+    size_t sort_bytes = 0, sort_cap = 0;
+    bool kick_pending = false;   // a step's tracer walk takes the kick + half drift along (dt: NbodyHandle::kick_dt)
+};
+
 struct NbodyHandle {
     NbodyConfig cfg{};
     nbody::Tuning tune;        // this handle's launch-shape and scheme knobs (nbody_set_tuning; NBODY_* environment at create)
@@ -348,7 +370,7 @@ struct NbodyHandle {
     bool last_step_async = false;
     bool host_tree_once = false;        // the next force pass builds its tree on the host (the replayed step)
     int* d_poison = nullptr;            // [2] sticky flags, steps completed (Shard::poison)
-    int* h_poison = nullptr;            // pinned [8]: poison[2] + tree info[3]
+    int* h_poison = nullptr;            // pinned [8]: poison[2] + tree info[3]; between their own synchronisations also scratch, at the offsets below
 
     // diagnostics
     NbodyStats stats{};
@@ -361,6 +383,7 @@ struct NbodyHandle {
     size_t energy_blocks = 0;
     PotBufs pot;
     FieldBufs field;
+    TracerState tr;
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;
@@ -377,6 +400,22 @@ struct NbodyHandle {
 
 
 // ---- helpers that need the handle
+
+// NbodyHandle::h_poison as pinned scratch for small read-backs: each user copies, synchronises and reads at once
+constexpr int kScratchStats = 4;          // one u64 ([4..5]): nbody_stats' interaction count
+constexpr int kScratchTracerCount = 6;    // one int: the live tracer count, up and down
+
+// staging for `records` PointParticle records of 10 floats (bodies and tracers alike): device and pinned host, grow-only
+inline int ensure_aos(NbodyHandle* h, size_t records) {
+    if (records <= h->aos_cap) return NBODY_OK;
+    if (h->d_aos) (void)hipFree(h->d_aos);
+    if (h->h_aos) (void)hipHostFree(h->h_aos);
+    h->d_aos = nullptr; h->h_aos = nullptr; h->aos_cap = 0;
+    HIP_TRY(h, hipMalloc(&h->d_aos, records * 10 * sizeof(float)));
+    HIP_TRY(h, hipHostMalloc(&h->h_aos, records * 10 * sizeof(float), hipHostMallocDefault));
+    h->aos_cap = records;
+    return NBODY_OK;
+}
 
 // grow-only device array: to n + n / 4 + 1024 elements of elem_bytes when it holds fewer than n
 template <class T>

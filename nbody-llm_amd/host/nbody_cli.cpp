@@ -8,7 +8,9 @@
 // reference's own precision (PointParticle<f64,3>, main.rs:52-105); --integrator host steps through the trait's generic
 // `Integrator` parameter (shared.rs:99-104) with a leapfrog on the host instead of the device's fused one, --integrator
 // hermite runs the device's fourth-order Hermite step (--method bf --dtype f64 only; leapfrog = device, the default); --dump FILE
-// writes the final PointParticle records; --multipole 2 adds the cells' quadrupole terms to the Barnes-Hut force walk.
+// writes the final PointParticle records; --multipole 2 adds the cells' quadrupole terms to the Barnes-Hut force walk;
+// --tracers M scatters M massless tracers in the workload's disc or sphere (the IC generator with seed + 1) and reports their
+// interactions per second on a line of its own.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,14 +27,15 @@ static void usage() {
                  "                 [--math fast|strict] [--tree auto|host|device] [--leaf reference|direct]\n"
                  "                 [--dtype f32|f64] [--dt x] [--g-soft x] [--theta2 x]\n"
                  "                 [--width w] [--seed s] [--integrator device|leapfrog|host|hermite] [--dump file] [--multipole 1|2]\n"
-                 "                 [--block-steps ETA:LEVELS]   (with --integrator hermite: block individual time steps)\n");
+                 "                 [--block-steps ETA:LEVELS]   (with --integrator hermite: block individual time steps)\n"
+                 "                 [--tracers M]   (massless tracers in the same disc or sphere; --dtype f32)\n");
 }
 
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
-               double block_eta, int block_levels) {
+               double block_eta, int block_levels, size_t n_tracers) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -57,6 +60,12 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (multipole != NBODY_MULTIPOLE_MONOPOLE) sim->set_multipole(multipole);   // (refused where it does not apply: nbody_hip.h)
         if (integrator == "hermite") sim->set_integrator(NBODY_INTEGRATOR_HERMITE4);
         if (block_levels > 0) sim->set_block_steps(block_eta, block_levels);   // every --dt is then a macro step of 2^LEVELS ticks
+        if (n_tracers) {   // the same generator with the next seed: tracers where the bodies are (the disc's star left out)
+            std::vector<nbody::PointParticleT<float>> tr(n_tracers + 1);
+            if (ic == "disc") { if (nbody_ic_disc(tr.data(), n_tracers, sizeof(tr[0]), seed + 1)) return 1; tr.erase(tr.begin()); }
+            else { tr.resize(n_tracers); if (nbody_ic_plummer(tr.data(), n_tracers, sizeof(tr[0]), seed + 1)) return 1; }
+            sim->set_tracers(tr);
+        }
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
         auto start = std::chrono::steady_clock::now();
@@ -73,6 +82,11 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         std::printf("Performance: %.2f steps/second\n", double(steps) / secs);
         NbodyStats st = sim->stats();
         std::printf("Bodies left: %zu  interactions/second: %.4e\n", sim->get_points().size(), double(st.interactions) / secs);
+        if (n_tracers) {
+            uint64_t ts[2] = {0, 0};
+            sim->tracer_stats(ts);
+            std::printf("Tracers left: %zu  tracer interactions/second: %.4e\n", sim->n_tracers(), double(ts[0]) / secs);
+        }
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -101,6 +115,7 @@ int main(int argc, char** argv) {
     double block_eta = 0.0;
     int block_levels = 0;
     bool block_set = false;
+    size_t n_tracers = 0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -120,6 +135,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--integrator")) integrator = next();
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--block-steps")) {
             char* end = nullptr;
             const char* arg = next();
@@ -141,6 +157,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers);
 }

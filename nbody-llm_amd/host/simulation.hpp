@@ -189,6 +189,21 @@ public:
         return out;
     }
     void block_step_counts(uint64_t out[2]) { check(nbody_block_step_counts(h_, out)); }   // {block steps, body updates}
+    // tracers: massless particles in the bodies' field (nbody_tracers_*): PointParticle<f32,3> records whatever F is, the mass
+    // ignored; f32 handles of a one-rank world (brute force and Barnes-Hut), every other handle throws NBODY_ERR_INVALID
+    void set_tracers(const std::vector<PointParticleT<float>>& rec, size_t capacity = 0) {
+        check(nbody_tracers_upload(h_, rec.data(), rec.size(), sizeof(PointParticleT<float>), capacity));
+    }
+    std::vector<PointParticleT<float>> get_tracers() {   // acc = the last tracer force pass, mass = 0
+        size_t n = 0;
+        check(nbody_tracers_count(h_, &n));
+        std::vector<PointParticleT<float>> out(n);
+        check(nbody_tracers_download(h_, out.data(), out.size(), sizeof(PointParticleT<float>), &n));
+        out.resize(n);
+        return out;
+    }
+    size_t n_tracers() { size_t n = 0; check(nbody_tracers_count(h_, &n)); return n; }
+    void tracer_stats(uint64_t out[2]) { check(nbody_tracer_stats(h_, out)); }   // {directed interactions, opening tests}
     NbodyHandle* handle() { return h_; }
 
 protected:
