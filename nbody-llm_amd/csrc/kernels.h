@@ -64,8 +64,8 @@ struct Shard {
     int* seg_count = nullptr;    // [n_seg] bodies alive per segment
     int* escaped = nullptr;      // [1] bodies of the own segment flagged out of bounds by drift
     unsigned char* keep = nullptr;  // [seg_cap] 1 = in bounds
-    // K4 (parallel retain): per-tile status words of the decoupled look-back {epoch | flag | count} and the epoch
-    unsigned long long* tile_state = nullptr;   // [ceil(seg_cap / 1024)]
+    // K4 (parallel retain, retain.h): per-tile status words of the decoupled look-back {epoch | flag | count} and the epoch
+    unsigned long long* tile_state = nullptr;   // [ceil(seg_cap / 1024) + 1]
     int* epoch = nullptr;                       // [1]
     // Barnes-Hut steps enqueued without a host round trip (device tree): [0] != 0 = "poisoned" (a build needed the
     // host: deeper than the device build's 21 levels, or more nodes than allocated) -- every kernel that changes the

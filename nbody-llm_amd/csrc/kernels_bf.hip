@@ -16,55 +16,62 @@
 // Both are fp32-VALU bound (20 flop per directed pair against 16 B of HBM traffic per body):
 // partner positions are read once per workgroup from L2 and broadcast from LDS with
 // ds_read_b128, one LDS instruction per 64*IPT pair evaluations.
-#include "kernels.h"
+#include "real.h"
 
 namespace nbody {
 
-// NbodyStats::interactions of a brute-force pass: n_own * (n_total - 1) from the live counts (one thread per launch)
+// NbodyStats::interactions of a brute-force pass: n_own * (n_total - 1) from the live counts (one thread per launch).
+// n_own > 0 is guard enough: the own segment is one of the n_seg, so n_total >= n_own > 0 and n_total - 1 cannot wrap,
+// and an empty own segment would add zero whatever the others hold.
 __device__ __forceinline__ void count_interactions(unsigned long long* inter, const int* seg_count, int n_seg, int n_own) {
     long long tot = 0;
     for (int s = 0; s < n_seg; ++s) tot += seg_count[s];
-    if (tot > 0) atomicAdd(inter, (unsigned long long)n_own * (unsigned long long)(tot - 1));
+    if (n_own > 0) atomicAdd(inter, (unsigned long long)n_own * (unsigned long long)(tot - 1));
 }
 
 // ------------------------------------------------------------------------------------ strict
+// One definition for F = f32 and F = f64 (real.h); the partner tile is 16 KB of LDS in both: 1 024 float4 or 512 double4.
 constexpr int kStrictBlock = 256;
-constexpr int kStrictTile = 1024;
+template <class F> constexpr int kStrictTile = 16384 / int(sizeof(typename Real<F>::V4));
 
-__global__ __launch_bounds__(kStrictBlock) void k_bf_strict(const float4* __restrict__ pos_all,
+template <class F>
+__global__ __launch_bounds__(kStrictBlock) void k_bf_strict(const typename Real<F>::V4* __restrict__ pos_all,
                                                             const int* __restrict__ seg_count, int n_seg, int seg_cap,
-                                                            int my_seg, float4* __restrict__ acc, float g, float eps2,
+                                                            int my_seg, typename Real<F>::V4* __restrict__ acc, F g, F eps2,
                                                             unsigned long long* __restrict__ inter) {
-    __shared__ float4 tile[kStrictTile];
+    using V4 = typename Real<F>::V4;
+    __shared__ V4 tile[kStrictTile<F>];
     const int tid = threadIdx.x;
     const int i = blockIdx.x * kStrictBlock + tid;
     const int n_own = seg_count[my_seg];
     if (inter && blockIdx.x == 0 && tid == 0) count_interactions(inter, seg_count, n_seg, n_own);
-    const float4 pi = (i < n_own) ? pos_all[size_t(my_seg) * seg_cap + i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    float ax = 0.f, ay = 0.f, az = 0.f;  // brute_force.rs:65-67
+    const V4 pi = (i < n_own) ? pos_all[size_t(my_seg) * seg_cap + i] : Real<F>::make4(0, 0, 0, 0);
+    F ax = 0, ay = 0, az = 0;  // brute_force.rs:65-67
+    // partners in ascending GLOBAL index: the segments in rank order, each in its own order (a G-shard run adds in the
+    // one-shard run's order: bit-equal)
     for (int s = 0; s < n_seg; ++s) {
         const int ns = seg_count[s];
-        const float4* __restrict__ ps = pos_all + size_t(s) * seg_cap;
+        const V4* __restrict__ ps = pos_all + size_t(s) * seg_cap;
         const int self = (s == my_seg) ? i : -1;
-        for (int t0 = 0; t0 < ns; t0 += kStrictTile) {
-            const int cnt = min(kStrictTile, ns - t0);
+        for (int t0 = 0; t0 < ns; t0 += kStrictTile<F>) {
+            const int cnt = min(kStrictTile<F>, ns - t0);
             __syncthreads();
             for (int k = tid; k < cnt; k += kStrictBlock) tile[k] = ps[t0 + k];
             __syncthreads();
             for (int j = 0; j < cnt; ++j) {
                 if (t0 + j == self) continue;  // the reference never forms the i == j pair (:70-71)
-                const float4 pj = tile[j];
-                const float rx = pi.x - pj.x, ry = pi.y - pj.y, rz = pi.z - pj.z;  // :72
-                const float r_dist = __builtin_sqrtf((rx * rx + ry * ry) + rz * rz + eps2);  // :73
-                const float r_cubed = r_dist * r_dist * r_dist;                    // :74
-                const float force = (g / r_cubed);                         // :77
+                const V4 pj = tile[j];
+                const F rx = pi.x - pj.x, ry = pi.y - pj.y, rz = pi.z - pj.z;  // :72
+                const F r_dist = Real<F>::sqrt((rx * rx + ry * ry) + rz * rz + eps2);  // :73
+                const F r_cubed = r_dist * r_dist * r_dist;                    // :74
+                const F force = (g / r_cubed);                         // :77
                 ax -= (rx * force) * pj.w;                                         // :78
                 ay -= (ry * force) * pj.w;
                 az -= (rz * force) * pj.w;
             }
         }
     }
-    if (i < n_own) acc[i] = make_float4(ax, ay, az, 0.f);
+    if (i < n_own) acc[i] = Real<F>::make4(ax, ay, az, 0);
 }
 
 // -------------------------------------------------------------------------------------- fast
@@ -168,9 +175,17 @@ __global__ __launch_bounds__(WAVES * 64) void k_bf_fast(const float4* __restrict
 void launch_bf_forces_strict(hipStream_t s, const Shard& sh, int n_upper, float g, float g_soft2) {
     if (n_upper <= 0) return;
     int blocks = (n_upper + kStrictBlock - 1) / kStrictBlock;
-    hipLaunchKernelGGL(k_bf_strict, dim3(blocks), dim3(kStrictBlock), 0, s, sh.pos_all, sh.seg_count, sh.n_seg,
+    hipLaunchKernelGGL(k_bf_strict<float>, dim3(blocks), dim3(kStrictBlock), 0, s, sh.pos_all, sh.seg_count, sh.n_seg,
                        sh.seg_cap, sh.my_seg, sh.acc, g, g_soft2, sh.inter);
 }
+}  // namespace nbody
+void nbody64::launch_bf_strict(hipStream_t s, const Dev& d, int n_upper, double g, double eps2) {   // F = f64 (kernels_f64.h)
+    if (n_upper <= 0) return;
+    int blocks = (n_upper + nbody::kStrictBlock - 1) / nbody::kStrictBlock;
+    hipLaunchKernelGGL(nbody::k_bf_strict<double>, dim3(blocks), dim3(nbody::kStrictBlock), 0, s, d.pos_all, d.seg_count, d.n_seg, d.cap,
+                       d.my_seg, d.acc, g, eps2, d.inter);
+}
+namespace nbody {
 
 template <int IPT, int WAVES, int TILE>
 static void launch_fast_cfg(hipStream_t s, const Shard& sh, int n_upper, float g, float eps2) {

@@ -21,13 +21,13 @@
 #include "kernels_pot.h"
 #include "kernels_field.h"
 #include "kernels_tracer.h"
+#include "walk_common.h"
 
 #include <algorithm>
 
 namespace nbody {
 
 constexpr int kWalkBlock = 64;   // one wave per workgroup: four body groups from different parts of the tree per CU (0.33 ms against 0.36 with 256)
-constexpr unsigned kCounterSlots = NBODY_WALK_COUNTER_SLOTS;  // {accepted, visited} pairs the waves' counts are spread over
 
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 struct alignas(32) NodeDev { float4 a; float4 b; };  // {com, mass}, {width^2, skip bits, width, leaf body}
@@ -91,11 +91,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk(const NodeDev* __restrict__ n
     // the dispatcher, which hands out workgroups in blockIdx order (x fastest), starts the heavy ones first.
     int seg = blockIdx.y;
     if (split.diag_first) {
-        const int K = gridDim.y;
-        const int diag = int((long long)blockIdx.x * K / gridDim.x);
-        const int kk = blockIdx.y;
-        const int off = (kk & 1) ? (kk + 1) / 2 : -(kk / 2);
-        seg = ((diag + off) % K + K) % K;
+        seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
     }
     if (split.poison && *split.poison) return;
     if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);
@@ -175,17 +171,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk(const NodeDev* __restrict__ n
     }
 #endif
     // one atomic pair per wave
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        // one atomic pair per wave, spread over kCounterSlots address pairs: 16 384 atomics on ONE address
-        // pair serialise in L2 at ~13 ns each (0.21 ms per walk at 8 segments, measured with theta2 = 1e9)
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 // Two bodies per lane (round 3).  What bounds k_bh_walk is the L1's address rate for divergent gathers, and
@@ -234,11 +220,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_duo(const NodeDev* __restrict
     const int t = bx * BLOCK + threadIdx.x;   // the bodies at places BPL t .. BPL t + BPL - 1 of the tree order
     int seg = blockIdx.y;
     if (split.diag_first) {
-        const int K = gridDim.y;
-        const int diag = int((long long)bx * K / gridDim.x);
-        const int kk = blockIdx.y;
-        const int off = (kk & 1) ? (kk + 1) / 2 : -(kk / 2);
-        seg = ((diag + off) % K + K) % K;
+        seg = nearest_first_segment(bx, gridDim.x, blockIdx.y, gridDim.y);
     }
     if (split.poison && *split.poison) return;
     if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);
@@ -281,12 +263,13 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_duo(const NodeDev* __restrict
                     make_float4(ax[q], ay[q], az[q], split.store_work ? float(v[q]) : 0.f);
         }
     }
+    // (add_walk_counts written out: through the helper the compiler orders this kernel's registers differently)
     for (int off = 32; off > 0; off >>= 1) {
         n_acc += __shfl_down(n_acc, off);
         n_vis += __shfl_down(n_vis, off);
     }
     if ((threadIdx.x & 63) == 0 && counters) {
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (NBODY_WALK_COUNTER_SLOTS - 1);
         atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
         atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
     }
@@ -355,17 +338,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_walk_wave(const NodeDev* __re
         i = __builtin_amdgcn_readfirstlane(__ballot(wants_children) != 0ull ? i + 1 : __float_as_int(B.y));
     }
     if (live) *(split.n_seg > 1 ? split.planes + size_t(seg) * split.plane_stride + t : acc + b) = make_float4(ax, ay, az, 0.f);  // :260
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        // one atomic pair per wave, spread over kCounterSlots address pairs: 16 384 atomics on ONE address
-        // pair serialise in L2 at ~13 ns each (0.21 ms per walk at 8 segments, measured with theta2 = 1e9)
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 
@@ -435,17 +408,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_walk_pair(const NodeDev* __re
         *(split.n_seg > 1 ? split.planes + size_t(seg) * split.plane_stride + tb : acc + b) =
             make_float4(ax, ay, az, split.store_work ? float(n_vis) : 0.f);  // :260
     if (half) { n_acc = 0; n_vis = 0; }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        // one atomic pair per wave, spread over kCounterSlots address pairs: 16 384 atomics on ONE address
-        // pair serialise in L2 at ~13 ns each (0.21 ms per walk at 8 segments, measured with theta2 = 1e9)
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 #endif  // NBODY_TUNING
@@ -522,17 +485,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_walk_nested(const NodeDev* __
         }
         acc[b] = make_float4(ox, oy, oz, 0.f);  // :260
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        // one atomic pair per wave, spread over kCounterSlots address pairs: 16 384 atomics on ONE address
-        // pair serialise in L2 at ~13 ns each (0.21 ms per walk at 8 segments, measured with theta2 = 1e9)
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 
@@ -597,11 +550,7 @@ __global__ __launch_bounds__(64) void k_bh_walk_coop(const NodeDev* __restrict__
     const unsigned long long r_start = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull;
     int seg = blockIdx.y;
     if (split.diag_first) {   // heaviest (nearest) segments of a body group first, see k_bh_walk
-        const int K = gridDim.y;
-        const int diag = int((long long)blockIdx.x * K / gridDim.x);
-        const int kk = blockIdx.y;
-        const int off = (kk & 1) ? (kk + 1) / 2 : -(kk / 2);
-        seg = ((diag + off) % K + K) % K;
+        seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
     }
     const int s1 = split.first[seg + 1];
     const int t = blockIdx.x * 64 + lane;
@@ -680,7 +629,7 @@ __global__ __launch_bounds__(64) void k_bh_walk_coop(const NodeDev* __restrict__
         }
     }
     if (lane == 0 && counters) {
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (NBODY_WALK_COUNTER_SLOTS - 1);
         atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
         atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
     }
@@ -714,11 +663,7 @@ __global__ __launch_bounds__(64) void k_bh_walk_block(const NodeDev* __restrict_
     const unsigned long long r_start = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull;
     int seg = blockIdx.y;
     if (split.diag_first) {   // heaviest (nearest) segments of a body group first, see k_bh_walk
-        const int K = gridDim.y;
-        const int diag = int((long long)blockIdx.x * K / gridDim.x);
-        const int kk = blockIdx.y;
-        const int off = (kk & 1) ? (kk + 1) / 2 : -(kk / 2);
-        seg = ((diag + off) % K + K) % K;
+        seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
     }
     const int s0 = split.first[seg], s1 = split.first[seg + 1];
     const int t = blockIdx.x * 64 + lane;
@@ -796,7 +741,7 @@ __global__ __launch_bounds__(64) void k_bh_walk_block(const NodeDev* __restrict_
         }
     }
     if (lane == 0 && counters) {
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
+        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (NBODY_WALK_COUNTER_SLOTS - 1);
         atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
         atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
     }
@@ -908,15 +853,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_lds(const NodeDev* __restrict
         *(split.n_seg > 1 ? split.planes + size_t(seg) * split.plane_stride + t : acc + b) =
             make_float4(ax, ay, az, split.store_work ? float(n_vis) : 0.f);  // :260
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        const unsigned slot = unsigned(wv) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, unsigned(wv), n_acc, n_vis);
 }
 
 }  // namespace nbody
@@ -1168,10 +1105,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_pot_walk(const NodeDev* __res
                                                             double* __restrict__ planes, size_t plane_stride) {
     const int t = blockIdx.x * kWalkBlock + threadIdx.x;
     if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);   // (spatial shards: the host's count is an upper bound)
-    const int K = gridDim.y;   // a group's segments nearest-first, as k_bh_walk dispatches them
-    const int diag = int((long long)blockIdx.x * K / gridDim.x);
-    const int kk = blockIdx.y;
-    const int seg = ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+    const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);   // (as k_bh_walk dispatches them)
     const int s1 = split.first[seg + 1];
     unsigned int n_acc = 0, n_vis = 0;
     if (t < n_order) {
@@ -1197,15 +1131,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_pot_walk(const NodeDev* __res
         }
         planes[size_t(seg) * plane_stride + t] = double(sum);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 __global__ __launch_bounds__(256) void k_pot_reduce(const double* __restrict__ planes, int n_seg, size_t plane_stride,
@@ -1255,10 +1181,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk(const NodeDev* __r
                                                               unsigned long long* __restrict__ counters, WalkSplit split,
                                                               double4* __restrict__ planes, size_t plane_stride) {
     const int t = blockIdx.x * kWalkBlock + threadIdx.x;
-    const int K = gridDim.y;   // a group's segments nearest-first, as k_bh_walk dispatches them
-    const int diag = int((long long)blockIdx.x * K / gridDim.x);
-    const int kk = blockIdx.y;
-    const int seg = ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
+    const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);   // (as k_bh_walk dispatches them)
     const int s1 = split.first[seg + 1];
     unsigned int n_acc = 0, n_vis = 0;
     if (t < n) {
@@ -1295,15 +1218,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk(const NodeDev* __r
             planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 void launch_bh_field_walk(hipStream_t s, const FieldTree& t, const double* xyz, const int* idx, int n, float eps2, float theta2, int want,
@@ -1327,7 +1242,7 @@ void launch_bh_field_walk(hipStream_t s, const FieldTree& t, const double* xyz, 
 // and takes the kick + half drift along; groups > 1: every (run, tracer) entry of the planes is written once and
 // k_tr_bh_reduce adds them in run order.  No atomics on the sums.  A tracer has no leaf of its own, so under the reference
 // rule nothing is skipped, and under NBODY_LEAF_DIRECT a tracer within 1e-5 of a cell's centre of mass skips that cell, as a
-// body would.  {accepted, visited} go to the tracer statistics, one atomic pair per wave over kCounterSlots slots.
+// body would.  {accepted, visited} go to the tracer statistics, one atomic pair per wave (walk_common.h).
 __device__ __forceinline__ void tr_bh_kick_drift(float4* __restrict__ pos, float4* __restrict__ vel, int b, float ax, float ay, float az, float dt) {
     float4 p = pos[b], v = vel[b];
     v.x += ax * dt;                 // shared.rs:144
@@ -1384,15 +1299,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_tr_bh_walk(const NodeDev* __rest
             if (do_kick) tr_bh_kick_drift(tr_pos, tr_vel, b, ax, ay, az, dt);
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (kCounterSlots - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 __global__ __launch_bounds__(256) void k_tr_bh_reduce(const float4* __restrict__ planes, int groups, size_t plane_stride,

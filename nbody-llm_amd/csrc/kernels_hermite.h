@@ -28,7 +28,7 @@ void launch_hm_strict(hipStream_t s, const Dev& d, const double4* x, const doubl
 // the corrector on (hd.a1, hd.j1), in place on pos / vel / acc / jerk, with Bounds::contains' flags for the retain:
 //   v1 = (v0 + (a0 + a1) * h) + (j0 - j1) * c12,  x1 = (x0 + (v0 + v1) * h) + (a0 - a1) * c12
 void launch_hm_correct(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, const HermiteCoef& c, const Bounds64& b);
-// Vec::retain over pos, vel, acc and jerk together (k_compact's tile scan with a fourth array)
+// Vec::retain over pos, vel, acc and jerk together (retain.h's tile scan with a fourth array)
 // level != nullptr: the block-step levels travel along
 void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, int* level = nullptr);
 // per-workgroup minima of |a_i| / |j_i| over live bodies with |j_i| > 0 (+inf where there is none) -> hd.ratio; returns the workgroups

@@ -13,7 +13,8 @@
 //   k_hm_os         one-sided, one body per lane, partners staged 64 at a time in the wave's LDS tile.  MODE 0: every own
 //                   body (small worlds); MODE 1: the pairs k_hm_sym leaves over (the own set and, for even A, the opposite one)
 //   k_hm_reduce     the planes added in a fixed order, times g; CORRECT: the corrector and the retain's flags ride along
-//   k_hm_predict, k_hm_correct, k_hm_compact, k_hm_min_ratio   the small kernels of the step and of nbody_suggest_dt
+//   k_hm_predict, k_hm_correct, k_hm_compact, k_hm_min_ratio   the small kernels of the step and of nbody_suggest_dt (the
+//                   retain's look-back scan is retain.h's, shared with the leapfrog handles' k_compact)
 //   k_hmb_*, k_hm_act, k_hm_act_strict   block individual time steps (nbody_set_block_steps): the schedule of a block step, F
 //                   of the due bodies alone against everybody, and the corrector with the step criterion (further down)
 //
@@ -22,6 +23,7 @@
 // is written exactly once per launch; there are no atomics on the planes: the same input gives the same bits.
 #include "kernels_hermite.h"
 #include "kernels.h"   // nbody::tuning()
+#include "retain.h"
 
 #include <algorithm>
 
@@ -95,12 +97,9 @@ __global__ __launch_bounds__(256) void k_hm_correct(const double4* __restrict__ 
     correct_one(k, a1[k], j1[k], pos, vel, acc, jerk, keep, escaped, c, b);
 }
 
-// Vec::retain, one pass over many workgroups, in place: kernels_f64.hip's k_compact with the jerk as a fourth array
-constexpr int kTile = 1024;
-constexpr unsigned long long kAgg = 1ull, kPrefix = 2ull;
-__device__ __forceinline__ unsigned long long tile_word(int epoch, unsigned long long flag, int value) {
-    return ((unsigned long long)(unsigned)epoch << 34) | (flag << 32) | (unsigned long long)(unsigned)value;
-}
+// Vec::retain, one pass over many workgroups, in place: retain.h's look-back scan; what moves with a Hermite body is the
+// jerk as a fourth array and, LV, its block-step level
+constexpr int kTile = nbody::kCompactTile;   // (the block-step schedule below counts in the same tiles)
 
 // LV: the block-step levels travel with the four arrays
 template <bool LV>
@@ -110,59 +109,11 @@ __global__ __launch_bounds__(kTile) void k_hm_compact(double4* __restrict__ pos,
                                                       unsigned long long* __restrict__ tile_state, int* __restrict__ epoch_p,
                                                       int* __restrict__ level) {
     if (*escaped == 0) return;
-    __shared__ int wave_total[16];
-    __shared__ int excl_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tile = blockIdx.x;
-    const int n = *count;
-    const int epoch = *epoch_p & 0x3fffffff;
-    const int k = tile * kTile + tid;
-    const bool kp = (k < n) && keep[k];
     double4 p = zero4(), v = p, a = p, j = p;
     int lv = 0;
-    if (kp) { p = pos[k]; v = vel[k]; a = acc[k]; j = jerk[k]; if (LV) lv = level[k]; }
-    const unsigned long long m = __ballot(kp);
-    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(m);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this tile's records are in registers before anything is published
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int w = 0; w < 16; ++w) {
-        const int t = wave_total[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    if (tid == 0) {
-        volatile unsigned long long* st = tile_state;
-        int excl = 0;
-        if (tile == 0) {
-            st[0] = tile_word(epoch, kPrefix, total);
-        } else {
-            st[tile] = tile_word(epoch, kAgg, total);
-            __threadfence();
-            for (int t = tile - 1; t >= 0;) {
-                const unsigned long long wd = st[t];
-                if (int(wd >> 34) != epoch) continue;
-                excl += int(unsigned(wd & 0xFFFFFFFFull));
-                if (((wd >> 32) & 3ull) == kPrefix) break;
-                --t;
-            }
-            st[tile] = tile_word(epoch, kPrefix, excl + total);
-        }
-        __threadfence();
-        excl_s = excl;
-        if (tile == int(gridDim.x) - 1) {
-            *count = excl + total;
-            *escaped = 0;
-            *epoch_p = (epoch + 1) & 0x3fffffff;
-        }
-    }
-    __syncthreads();
-    if (kp) {
-        const int d = excl_s + before + in_wave;
-        pos[d] = p; vel[d] = v; acc[d] = a; jerk[d] = j;
-        if (LV) level[d] = lv;
-    }
+    nbody::retain_tile(keep, count, escaped, tile_state, epoch_p,
+                       [&](int k) { p = pos[k]; v = vel[k]; a = acc[k]; j = jerk[k]; if (LV) lv = level[k]; },
+                       [&](int d) { pos[d] = p; vel[d] = v; acc[d] = a; jerk[d] = j; if (LV) level[d] = lv; });
 }
 
 // nbody_suggest_dt: min over the workgroup's live bodies of |a| / |j|, norms sqrt((x^2 + y^2) + z^2); bodies with |j| == 0

@@ -1,187 +1,166 @@
-// kernels_integrate.hip -- O(N) kernels around the force pass (gfx950).
+// kernels_integrate.hip -- O(N) kernels around the force pass (gfx950), written once for F = f32 and F = f64 (real.h)
+// with the launchers of both (kernels.h, kernels_f64.h).
 //
-// K0  AoS <-> SoA transposition of PointParticle<f32,3> records (shared.rs:151-158)
+// K0  AoS <-> SoA transposition of PointParticle<F,3> records (shared.rs:151-158)
 // K1  drift_half    = LeapFrogIntegrator::integrate_pre_force (shared.rs:135-140)
 //                     + the Bounds::contains test (shared.rs:210-212) that retain() applies next
-// K4  compact       = Vec::retain (brute_force.rs:86, barnes_hut.rs:267), order preserving, one pass over many workgroups
+// K4  compact       = Vec::retain (brute_force.rs:86, barnes_hut.rs:267), order preserving, one pass over many workgroups:
+//                     the look-back scan is retain.h's, here is what moves with a leapfrog body
 // K3  kick_drift    = LeapFrogIntegrator::integrate_after_force (shared.rs:141-148)
 //
-// All are pure streaming kernels, 16 B per lane per access (1 KiB per wave instruction).
+// All are pure streaming kernels, 16 B (f32) or 32 B (f64) per lane per access.
 // Compiled with -ffp-contract=off: (v*0.5)*dt and a*dt are rounded products, then added, exactly
 // as the reference's nalgebra expressions evaluate.
-#include "kernels.h"
+#include "real.h"
+#include "retain.h"
 
 #include <algorithm>
 
 namespace nbody {
 
-__global__ __launch_bounds__(256) void k_aos_to_soa(const float* __restrict__ aos, int stride_f, int n,
-                                                    float4* __restrict__ pos, float4* __restrict__ vel,
-                                                    float4* __restrict__ acc) {
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
+// F = float: the f32 handles (poison: Shard::poison, may be null); F = double: the f64 handles (nbody64, no poison)
+template <class F>
+__global__ __launch_bounds__(256) void k_aos_to_soa(const F* __restrict__ aos, int stride, int n, typename Real<F>::V4* __restrict__ pos,
+                                                    typename Real<F>::V4* __restrict__ vel, typename Real<F>::V4* __restrict__ acc) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const float* p = aos + size_t(k) * stride_f;
-    pos[k] = make_float4(p[0], p[1], p[2], p[9]);
-    if (vel) vel[k] = make_float4(p[3], p[4], p[5], 0.f);  // other shards' segments carry positions only
-    if (acc) acc[k] = make_float4(p[6], p[7], p[8], 0.f);
+    const F* p = aos + size_t(k) * stride;
+    pos[k] = Real<F>::make4(p[0], p[1], p[2], p[9]);
+    if (vel) vel[k] = Real<F>::make4(p[3], p[4], p[5], F(0));  // other shards' segments carry positions only
+    if (acc) acc[k] = Real<F>::make4(p[6], p[7], p[8], F(0));
 }
 
-__global__ __launch_bounds__(256) void k_soa_to_aos(float* __restrict__ aos, int stride_f, int n,
-                                                    const float4* __restrict__ pos, const float4* __restrict__ vel,
-                                                    const float4* __restrict__ acc) {
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
+template <class F>
+__global__ __launch_bounds__(256) void k_soa_to_aos(F* __restrict__ aos, int stride, int n, const typename Real<F>::V4* __restrict__ pos,
+                                                    const typename Real<F>::V4* __restrict__ vel,
+                                                    const typename Real<F>::V4* __restrict__ acc) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    float4 p = pos[k], v = vel[k], a = acc[k];
-    float* o = aos + size_t(k) * stride_f;
+    const typename Real<F>::V4 p = pos[k], v = vel[k], a = acc[k];
+    F* o = aos + size_t(k) * stride;
     o[0] = p.x; o[1] = p.y; o[2] = p.z;
     o[3] = v.x; o[4] = v.y; o[5] = v.z;
     o[6] = a.x; o[7] = a.y; o[8] = a.z;
     o[9] = p.w;
 }
 
-__global__ __launch_bounds__(256) void k_drift_half(float4* __restrict__ pos, const float4* __restrict__ vel,
+template <class F>
+__global__ __launch_bounds__(256) void k_drift_half(typename Real<F>::V4* __restrict__ pos, const typename Real<F>::V4* __restrict__ vel,
                                                     const int* __restrict__ count, unsigned char* __restrict__ keep,
-                                                    int* __restrict__ escaped, float dt, BoundsF b,
+                                                    int* __restrict__ escaped, F dt, typename Real<F>::Bounds b,
                                                     const int* __restrict__ poison) {
     if (poison && *poison) return;
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= *count) return;
-    float4 p = pos[k];
-    float4 v = vel[k];
-    p.x += (v.x * 0.5f) * dt;
-    p.y += (v.y * 0.5f) * dt;
-    p.z += (v.z * 0.5f) * dt;
+    typename Real<F>::V4 p = pos[k];
+    const typename Real<F>::V4 v = vel[k];
+    p.x += (v.x * Real<F>::half) * dt;
+    p.y += (v.y * Real<F>::half) * dt;
+    p.z += (v.z * Real<F>::half) * dt;
     pos[k] = p;
     // inclusive, component-wise; a NaN fails every comparison and is dropped
-    bool in = (p.x >= b.lo[0]) && (p.x <= b.hi[0]) && (p.y >= b.lo[1]) && (p.y <= b.hi[1]) &&
-              (p.z >= b.lo[2]) && (p.z <= b.hi[2]);
+    const bool in = (p.x >= b.lo[0]) && (p.x <= b.hi[0]) && (p.y >= b.lo[1]) && (p.y <= b.hi[1]) &&
+                    (p.z >= b.lo[2]) && (p.z <= b.hi[2]);
     keep[k] = in ? 1 : 0;
     if (!in) atomicAdd(escaped, 1);
 }
 
-__global__ __launch_bounds__(256) void k_kick_drift(float4* __restrict__ pos, float4* __restrict__ vel,
-                                                    const float4* __restrict__ acc, const int* __restrict__ count,
-                                                    float dt, int* __restrict__ poison) {
+template <class F>
+__global__ __launch_bounds__(256) void k_kick_drift(typename Real<F>::V4* __restrict__ pos, typename Real<F>::V4* __restrict__ vel,
+                                                    const typename Real<F>::V4* __restrict__ acc, const int* __restrict__ count,
+                                                    F dt, int* __restrict__ poison) {
     if (poison && *poison) return;
-    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.x * 256 + threadIdx.x;
     if (k == 0 && poison) atomicAdd(poison + 1, 1);   // a step of an unsynchronised Barnes-Hut run is complete
     if (k >= *count) return;
-    float4 p = pos[k], v = vel[k], a = acc[k];
+    typename Real<F>::V4 p = pos[k], v = vel[k];
+    const typename Real<F>::V4 a = acc[k];
     v.x += a.x * dt;
     v.y += a.y * dt;
     v.z += a.z * dt;
-    p.x += (v.x * 0.5f) * dt;
-    p.y += (v.y * 0.5f) * dt;
-    p.z += (v.z * 0.5f) * dt;
+    p.x += (v.x * Real<F>::half) * dt;
+    p.y += (v.y * Real<F>::half) * dt;
+    p.z += (v.z * Real<F>::half) * dt;
     vel[k] = v;
     pos[k] = p;
 }
 
-// K4: Vec::retain (brute_force.rs:86, barnes_hut.rs:267) -- order-preserving compaction of the own segment, in
-// place, in ONE pass over many workgroups (round 1 walked the segment with a single 1 024-thread workgroup: an escape
-// at N = 2^22 serialised 4 096 chunk iterations on one CU, ms-scale).  Launched every step, every workgroup returns at
-// once unless drift_half flagged an escape.
-//   * a tile = 1 024 consecutive bodies, one per thread; the thread loads its record, the workgroup counts and ranks
-//     its survivors (wave ballots + 16 wave totals in LDS);
-//   * tiles learn how many survivors precede them by decoupled look-back: a tile publishes {its own count}, then adds
-//     up its predecessors' published counts backwards until it meets one that already knows its inclusive prefix, and
-//     publishes its own inclusive prefix.  Status words carry the launch's epoch, so they never need resetting;
-//   * in place: a survivor moves to an index <= its own, i.e. into the source range of its own or an EARLIER tile.  A
-//     tile publishes only after its own records are in registers, and a tile's prefix is built from published words
-//     only, so -- by induction over the tiles it looked back over -- every earlier tile has finished reading before
-//     this tile knows where to write; inside a tile a barrier separates the loads from the stores.
-constexpr int kCompactTile = 1024;
-constexpr unsigned long long kTileAgg = 1ull, kTilePrefix = 2ull;
-__device__ __forceinline__ unsigned long long tile_word(int epoch, unsigned long long flag, int value) {
-    return ((unsigned long long)(unsigned)epoch << 34) | (flag << 32) | (unsigned long long)(unsigned)value;
-}
-
-__global__ __launch_bounds__(kCompactTile) void k_compact(float4* __restrict__ pos, float4* __restrict__ vel,
-                                                          float4* __restrict__ acc, const unsigned char* __restrict__ keep,
+// K4: retain.h's look-back scan; what moves with a leapfrog body is three arrays and, on spatial shards, its id (else null)
+template <class F>
+__global__ __launch_bounds__(kCompactTile) void k_compact(typename Real<F>::V4* __restrict__ pos, typename Real<F>::V4* __restrict__ vel,
+                                                          typename Real<F>::V4* __restrict__ acc, const unsigned char* __restrict__ keep,
                                                           int* __restrict__ count, int* __restrict__ escaped,
                                                           unsigned long long* __restrict__ tile_state, int* __restrict__ epoch_p,
                                                           const int* __restrict__ poison, int* __restrict__ ids) {
     if (poison && *poison) return;
     if (*escaped == 0) return;
-    __shared__ int wave_total[16];
-    __shared__ int excl_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tile = blockIdx.x;
-    const int n = *count;
-    const int epoch = *epoch_p & 0x3fffffff;
-    const int k = tile * kCompactTile + tid;
-    const bool kp = (k < n) && keep[k];
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), v = p, a = p;
+    typename Real<F>::V4 p = Real<F>::make4(0, 0, 0, 0), v = p, a = p;
     int id = 0;
-    if (kp) { p = pos[k]; v = vel[k]; a = acc[k]; if (ids) id = ids[k]; }
-    const unsigned long long m = __ballot(kp);
-    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(m);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's records are in registers ...
-    __syncthreads();                                   // ... and so are the whole tile's
-    int before = 0, total = 0;
-    for (int w = 0; w < 16; ++w) {
-        const int t = wave_total[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    if (tid == 0) {
-        volatile unsigned long long* st = tile_state;
-        int excl = 0;
-        if (tile == 0) {
-            st[0] = tile_word(epoch, kTilePrefix, total);
-        } else {
-            st[tile] = tile_word(epoch, kTileAgg, total);
-            __threadfence();
-            for (int j = tile - 1; j >= 0;) {
-                const unsigned long long wd = st[j];
-                if (int(wd >> 34) != epoch) continue;            // not published in this launch yet: look again
-                excl += int(unsigned(wd & 0xFFFFFFFFull));
-                if (((wd >> 32) & 3ull) == kTilePrefix) break;   // everything before j is in this word
-                --j;
-            }
-            st[tile] = tile_word(epoch, kTilePrefix, excl + total);
-        }
-        __threadfence();
-        excl_s = excl;
-        if (tile == int(gridDim.x) - 1) {   // the last tile's inclusive prefix is the new body count
-            *count = excl + total;
-            *escaped = 0;
-            *epoch_p = (epoch + 1) & 0x3fffffff;
-        }
-    }
-    __syncthreads();
-    if (kp) {
-        const int d = excl_s + before + in_wave;
-        pos[d] = p; vel[d] = v; acc[d] = a;
-        if (ids) ids[d] = id;
-    }
+    retain_tile(keep, count, escaped, tile_state, epoch_p,
+                [&](int k) { p = pos[k]; v = vel[k]; a = acc[k]; if (ids) id = ids[k]; },
+                [&](int d) { pos[d] = p; vel[d] = v; acc[d] = a; if (ids) ids[d] = id; });
 }
 
 static inline int blocks_for(int n, int bs) { return n <= 0 ? 0 : (n + bs - 1) / bs; }
 
 void launch_aos_to_soa(hipStream_t s, const float* aos, int stride_f, int n, float4* pos, float4* vel, float4* acc) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_aos_to_soa, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_f, n, pos, vel, acc);
+    hipLaunchKernelGGL(k_aos_to_soa<float>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_f, n, pos, vel, acc);
 }
 void launch_soa_to_aos(hipStream_t s, float* aos, int stride_f, int n, const float4* pos, const float4* vel, const float4* acc) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_soa_to_aos, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_f, n, pos, vel, acc);
+    hipLaunchKernelGGL(k_soa_to_aos<float>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_f, n, pos, vel, acc);
 }
 void launch_drift_half(hipStream_t s, const Shard& sh, int n_upper, float dt, BoundsF b) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_drift_half, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, sh.own_pos(), sh.vel,
+    hipLaunchKernelGGL(k_drift_half<float>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, sh.own_pos(), sh.vel,
                        sh.own_count(), sh.keep, sh.escaped, dt, b, sh.poison);
 }
 void launch_compact(hipStream_t s, const Shard& sh, int n_upper) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_compact, dim3(blocks_for(n_upper, kCompactTile)), dim3(kCompactTile), 0, s, sh.own_pos(), sh.vel, sh.acc,
+    hipLaunchKernelGGL(k_compact<float>, dim3(blocks_for(n_upper, kCompactTile)), dim3(kCompactTile), 0, s, sh.own_pos(), sh.vel, sh.acc,
                        sh.keep, sh.own_count(), sh.escaped, sh.tile_state, sh.epoch, sh.poison, sh.ids);
 }
 void launch_kick_drift(hipStream_t s, const Shard& sh, int n_upper, float dt) {
     // (launched even for an empty shard: the step counter of an unsynchronised run rides in it)
-    hipLaunchKernelGGL(k_kick_drift, dim3(std::max(1, blocks_for(n_upper, 256))), dim3(256), 0, s, sh.own_pos(), sh.vel, sh.acc,
+    hipLaunchKernelGGL(k_kick_drift<float>, dim3(std::max(1, blocks_for(n_upper, 256))), dim3(256), 0, s, sh.own_pos(), sh.vel, sh.acc,
                        sh.own_count(), dt, sh.poison);
 }
 
 }  // namespace nbody
+
+// F = f64 (kernels_f64.h): one shard's own block, no poison word; an empty block launches nothing
+namespace nbody64 {
+using nbody::blocks_for;
+
+void launch_aos_to_soa(hipStream_t s, const double* aos, int stride_d, int n, const Dev& d, size_t first) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(nbody::k_aos_to_soa<double>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_d, n, d.pos + first, d.vel + first,
+                       d.acc + first);
+}
+void launch_aos_to_pos(hipStream_t s, const double* aos, int stride_d, int n, double4* pos) {   // another shard's block: positions only
+    if (n <= 0) return;
+    hipLaunchKernelGGL(nbody::k_aos_to_soa<double>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_d, n, pos, (double4*)nullptr,
+                       (double4*)nullptr);
+}
+void launch_soa_to_aos(hipStream_t s, double* aos, int stride_d, int n, const Dev& d) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(nbody::k_soa_to_aos<double>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_d, n, d.pos, d.vel, d.acc);
+}
+void launch_drift_half(hipStream_t s, const Dev& d, int n_upper, double dt, const Bounds64& b) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(nbody::k_drift_half<double>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.pos, d.vel, d.count, d.keep, d.escaped, dt,
+                       b, (const int*)nullptr);
+}
+void launch_compact(hipStream_t s, const Dev& d, int n_upper) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(nbody::k_compact<double>, dim3(blocks_for(n_upper, nbody::kCompactTile)), dim3(nbody::kCompactTile), 0, s, d.pos, d.vel,
+                       d.acc, d.keep, d.count, d.escaped, d.tile_state, d.epoch, (const int*)nullptr, (int*)nullptr);
+}
+void launch_kick_drift(hipStream_t s, const Dev& d, int n_upper, double dt) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(nbody::k_kick_drift<double>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.pos, d.vel, d.acc, d.count, dt,
+                       (int*)nullptr);
+}
+
+}  // namespace nbody64

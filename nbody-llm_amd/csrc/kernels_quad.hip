@@ -14,6 +14,7 @@
 // k_bh_pot_walk_quad and k_bh_field_walk_quad are kernels_bh.hip's k_bh_pot_walk<double> and k_bh_field_walk with the same
 // term (and its scalar counterpart) in IEEE f32 arithmetic: see pot_quad_parts below.
 #include "kernels_quad.h"
+#include "walk_common.h"
 
 namespace nbody {
 
@@ -156,11 +157,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const QuadNode* __restri
     const int t = blockIdx.x * BLOCK + threadIdx.x;
     int seg = blockIdx.y;
     if (split.diag_first) {   // a body group's segments nearest its own place in the tree first (k_bh_walk)
-        const int K = gridDim.y;
-        const int diag = int((long long)blockIdx.x * K / gridDim.x);
-        const int kk = blockIdx.y;
-        const int off = (kk & 1) ? (kk + 1) / 2 : -(kk / 2);
-        seg = ((diag + off) % K + K) % K;
+        seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
     }
     if (split.poison && *split.poison) return;
     if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);
@@ -191,15 +188,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const QuadNode* __restri
         }
         *(split.n_seg > 1 ? split.planes + size_t(seg) * split.plane_stride + t : acc + b) = make_float4(ax, ay, az, 0.f);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {   // one atomic pair per wave, over the slots k_bh_walk spreads them over
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (NBODY_WALK_COUNTER_SLOTS - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 // ---- NBODY_POTENTIAL_TREE_QUADRUPOLE: the potential walk and the field walk with the term of every accepted internal node.
@@ -241,25 +230,6 @@ __device__ __forceinline__ QuadParts pot_quad_parts(const QuadDev* __restrict__ 
     return r;
 }
 
-__device__ __forceinline__ int nearest_first_seg() {   // a group's segments nearest-first, as k_bh_walk dispatches them
-    const int K = gridDim.y;
-    const int diag = int((long long)blockIdx.x * K / gridDim.x);
-    const int kk = blockIdx.y;
-    return ((diag + ((kk & 1) ? (kk + 1) / 2 : -(kk / 2))) % K + K) % K;
-}
-
-__device__ __forceinline__ void add_walk_counts(unsigned long long* __restrict__ counters, unsigned int n_acc, unsigned int n_vis) {
-    for (int off = 32; off > 0; off >>= 1) {
-        n_acc += __shfl_down(n_acc, off);
-        n_vis += __shfl_down(n_vis, off);
-    }
-    if ((threadIdx.x & 63) == 0 && counters) {   // one atomic pair per wave, over the slots k_bh_pot_walk spreads them over
-        const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & (NBODY_WALK_COUNTER_SLOTS - 1);
-        atomicAdd(&counters[2 * slot], (unsigned long long)n_acc);
-        atomicAdd(&counters[2 * slot + 1], (unsigned long long)n_vis);
-    }
-}
-
 // k_bh_pot_walk<double> (kernels_bh.hip) with the scalar quadrupole part: the same tests, planes and counter slots
 __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const QuadNode* __restrict__ nodes, const QuadDev* __restrict__ quad,
                                                                      const int* __restrict__ order, int n_order, const float4* __restrict__ own_pos,
@@ -267,7 +237,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const QuadN
                                                                      QuadSplit split, double* __restrict__ planes, size_t plane_stride) {
     const int t = blockIdx.x * kQuadWalkBlock + threadIdx.x;
     if (split.n_order_dev) n_order = min(n_order, *split.n_order_dev);
-    const int seg = nearest_first_seg();
+    const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);   // (as k_bh_walk dispatches them)
     const int s1 = split.first[seg + 1];
     unsigned int n_acc = 0, n_vis = 0;
     if (t < n_order) {
@@ -300,7 +270,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const QuadN
         }
         planes[size_t(seg) * plane_stride + t] = sum;
     }
-    add_walk_counts(counters, n_acc, n_vis);
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 // k_bh_field_walk<VEC, SCAL> (kernels_bh.hip) with both quadrupole parts
@@ -310,7 +280,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const Qua
                                                                        float eps2, float theta2, unsigned long long* __restrict__ counters,
                                                                        QuadSplit split, double4* __restrict__ planes, size_t plane_stride) {
     const int t = blockIdx.x * kQuadWalkBlock + threadIdx.x;
-    const int seg = nearest_first_seg();
+    const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);   // (as k_bh_walk dispatches them)
     const int s1 = split.first[seg + 1];
     unsigned int n_acc = 0, n_vis = 0;
     if (t < n) {
@@ -354,7 +324,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const Qua
             planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
         }
     }
-    add_walk_counts(counters, n_acc, n_vis);
+    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
 void launch_tree_quad(hipStream_t s, const float4* nodes, int n_nodes, float4* quad, const int* info, const int* poison) {

@@ -61,6 +61,41 @@ def test_brute_force_f64_with_escapes_settings_and_negative_dt(gpu, orc):
         assert eq(got[f], ref[f]), f
 
 
+def test_f64_retain_keeps_order_over_many_tiles(gpu):
+    """tests/test_async_and_retain_gpu.py's test_parallel_retain_keeps_order_at_large_n on an f64 handle: 5 000 bodies are
+    five tiles of the look-back retain; with g = 0 a step is x += (v/2) dt twice with the retain in between, which numpy
+    reproduces exactly in float64 (the same expression order).  ~10 % of the bodies leave in one step."""
+    nb = gpu
+    n = 5000
+    rng = np.random.default_rng(n)
+    ics = np.zeros(n, nb.PARTICLE_DTYPE64)
+    ics["position"] = rng.uniform(-1.0, 1.0, (n, 3))
+    ics["velocity"] = rng.normal(0.0, 1.0, (n, 3))
+    ics["mass"] = rng.uniform(0.5, 1.5, n)
+    dt = np.float64(0.1)
+    with nb.Simulation(ics, (0.0, 0.0, 0.0), 2.1, method=nb.BRUTE_FORCE, math_mode=nb.STRICT) as sim:
+        assert sim.f64
+        sim.settings = nb.Settings(0.0, 0.0, float(dt), 0.25)
+        sim.init()
+        sim.steps(2)
+        got = sim.get_points()
+        assert len(sim) == len(got)
+    x, v, m = ics["position"].copy(), ics["velocity"].copy(), ics["mass"]
+    half = (v * np.float64(0.5)) * dt
+    lo, hi = np.float64(0.0) + np.float64(-1.05), np.float64(0.0) + np.float64(1.05)
+    left = []
+    for _ in range(2):
+        x = x + half
+        keep = np.all((x >= lo) & (x <= hi), axis=1)
+        left.append([int((~keep[t:t + 1024]).sum()) for t in range(0, len(keep), 1024)])
+        x, half, v, m = x[keep], half[keep], v[keep], m[keep]
+        x = x + half                                   # (a = 0: the kick leaves v alone)
+    assert len(left[0]) == 5 and min(left[0]) > 0 and min(left[1]) > 0, left    # bodies leave from every tile, in both steps
+    assert 0.5 * n < len(x) < 0.95 * n and len(got) == len(x)
+    assert eq(got["mass"], m) and eq(got["velocity"], v)
+    assert eq(got["position"], x)
+
+
 @pytest.mark.parametrize("leaf", ["reference", "direct"])
 @pytest.mark.parametrize("n,theta2", [(1, 0.25), (2, 0.25), (9, 1.0), (1000, 0.25), (5000, 0.5), (20000, 0.25)])
 def test_barnes_hut_f64_counts_tree_and_accelerations(gpu, orc, n, theta2, leaf):

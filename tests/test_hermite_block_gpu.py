@@ -23,8 +23,8 @@ def eq(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
-def make(nb, x, v, m, math, block=(ETA, L), eps=G_SOFT, dt=1 / 16, hermite=True, **tuning):
-    sim = nb.Simulation(hr.records(nb.PARTICLE_DTYPE64, x, v, m), *hr.BOX, method=nb.BRUTE_FORCE, math_mode=math, f64=True, tuning=tuning)
+def make(nb, x, v, m, math, block=(ETA, L), eps=G_SOFT, dt=1 / 16, hermite=True, box=hr.BOX, **tuning):
+    sim = nb.Simulation(hr.records(nb.PARTICLE_DTYPE64, x, v, m), *box, method=nb.BRUTE_FORCE, math_mode=math, f64=True, tuning=tuning)
     sim.settings = nb.Settings(g=hr.G, g_soft=eps, dt=dt, theta2=0.5)
     if hermite:
         sim.integrator = nb.HERMITE4
@@ -92,6 +92,34 @@ def test_strict_macro_steps_bit_for_bit(gpu, leaver):
         assert sim.stats().steps == len(MACRO)
         print(f"\n[hermite block] strict n={len(x)}: {bsteps} block steps, {updates} body updates, levels up to {levels.max()}")
         assert levels.max() >= 3 and bsteps > len(MACRO)       # the pair does step below the field
+
+
+def test_strict_levels_move_with_their_bodies_across_a_tile_boundary(gpu):
+    """The retain with the block-step levels as a fifth array, over two tiles: 1 100 bodies, a box of width 2.4 that about an
+    eighth of the bodies on either side of index 1 024 are outside of at the end of the first macro step (the restatement's
+    mask is asserted to say so).  The second macro step has the same |dt|, so it runs on the levels that were moved.
+    (The restatement takes about 4.5 s a macro step at this size.)"""
+    nb = gpu
+    x, v, m = br.tight_pair_world(1100)
+    box = ((0.0, 0.0, 0.0), 2.4)
+    ref = br.Handle(x, v, m, ETA, L, eps=G_SOFT, box=box)
+    ref.update_forces()
+    unbounded, _ = br.macro_step(ref.state, None, 1 / 16, ETA, L, eps=G_SOFT, box=((0.0, 0.0, 0.0), np.inf))
+    keep = hr.contains(unbounded[0], *box)
+    for part in (keep[:1024], keep[1024:]):
+        assert part.any() and not part.all(), "needs leavers and survivors on both sides of index 1 024"
+    with make(nb, x, v, m, nb.STRICT, box=box) as sim:
+        for k in range(2):
+            sim.step_by(1 / 16)
+            ref.step_by(1 / 16)
+            assert len(sim) == len(ref.levels) == (int(keep.sum()) if k == 0 else len(sim)), f"macro step {k + 1}"
+            assert same_state(state_of(sim), ref.state), f"macro step {k + 1}"
+            assert np.array_equal(sim.levels(), ref.levels), f"macro step {k + 1}"
+            assert sim.block_step_counts() == (ref.log["block_steps"], ref.log["updates"]), f"macro step {k + 1}"
+            assert sim.stats().interactions == ref.interactions and sim.elapsed() == ref.elapsed, f"macro step {k + 1}"
+            if k == 0:   # the survivors from beyond index 1 024 are the last ones now, and they differ in level
+                assert len(np.unique(ref.levels[-int(keep[1024:].sum()):])) >= 3
+        assert ref.log["all_at_T"] and ref.log["off_grid"] == 0
 
 
 # ---------------------------------------------------------------------------------------------- 2. eta -> infinity

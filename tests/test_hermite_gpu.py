@@ -21,8 +21,8 @@ def eq(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
-def make(nb, x, v, m, math, hermite=True, capacity=None, dt=DT, **tuning):
-    sim = nb.Simulation(hr.records(nb.PARTICLE_DTYPE64, x, v, m), *hr.BOX, method=nb.BRUTE_FORCE, math_mode=math, f64=True,
+def make(nb, x, v, m, math, hermite=True, capacity=None, dt=DT, box=hr.BOX, **tuning):
+    sim = nb.Simulation(hr.records(nb.PARTICLE_DTYPE64, x, v, m), *box, method=nb.BRUTE_FORCE, math_mode=math, f64=True,
                         capacity=capacity, tuning=tuning)
     sim.settings = nb.Settings(g=hr.G, g_soft=hr.EPS, dt=dt, theta2=0.5)
     if hermite:
@@ -89,6 +89,31 @@ def test_strict_trajectory_bit_for_bit(gpu, leaver):
             assert st.interactions == 4 * 257 * 256 + 5 * 256 * 255
     if leaver:
         assert eq(ref[4], np.delete(m, 100))
+
+
+def test_strict_retain_across_tile_boundaries_bit_for_bit(gpu):
+    """The retain's look-back over several tiles with the Hermite payload (four arrays): 2 304 bodies are tiles of
+    1 024 + 1 024 + 256, and a box of width 2.4 (two standard deviations of the cluster a side) drops about an eighth of every
+    tile in the first step_by and a few more bodies of both remaining tiles in the second, longer one.  The masks the
+    restatement retains by are asserted to do so, then state and count are compared bit for bit."""
+    nb = gpu
+    x, v, m = hr.world(2304)
+    box = ((0.0, 0.0, 0.0), 2.4)
+    ref = hr.start(x, v, m)
+    with make(nb, x, v, m, nb.STRICT, box=box) as sim:
+        sim.init()
+        for k, (dt, tiles) in enumerate(((DT, 3), (4.0 * DT, 2))):
+            unbounded = hr.hermite_step(ref, dt, box=((0.0, 0.0, 0.0), np.inf))
+            keep = hr.contains(unbounded[0], *box)
+            assert len(keep) > 1024 * (tiles - 1), f"step {k + 1}: the state no longer spans {tiles} tiles"
+            for t in range(tiles):
+                part = keep[1024 * t:1024 * (t + 1)]
+                assert part.any() and not part.all(), f"step {k + 1}, tile {t}: needs leavers and survivors"
+            ref = hr.hermite_step(ref, dt, box=box)
+            assert eq(ref[0], unbounded[0][keep])
+            sim.step_by(dt)
+            assert len(sim) == len(ref[0]) == int(keep.sum()), f"step {k + 1}"
+            assert same_state(state_of(sim), ref), f"step {k + 1}"
 
 
 # ---------------------------------------------------------------------------------------------- 2. fast math, every row
