@@ -156,7 +156,7 @@ struct TreeDev {
     int n_nodes = 0;
     const int* order = nullptr;      // own bodies (index into the own segment) in tree order
     int n_order = 0;
-    // node-range split of the walk (kernels_bh.hip WalkSplit); n_split = 1: none
+    // node-range split of the walk (walk_common.h WalkSplit); n_split = 1: none
     int n_split = 1;
     const int* split_first = nullptr;   // [n_split + 1]
     const int* split_anc = nullptr;     // [n_split][kMaxAnc]

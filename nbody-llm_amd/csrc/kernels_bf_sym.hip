@@ -27,6 +27,7 @@
 // fast math only (v_rsq_f32 + FMA; summation order differs from the reference): tolerance 1e-5.
 #include "kernels.h"
 #include "bf_pair.h"
+#include "real.h"   // kick_half_drift
 
 #include <algorithm>
 
@@ -386,13 +387,7 @@ __global__ __launch_bounds__(256) void k_bf_sym_reduce(const float4* __restrict_
     }
     const float4 a = make_float4(g * sx, g * sy, g * sz, 0.f);
     acc[i] = a;
-    if (KICK) {
-        float4 p = pos[i], v = vel[i];
-        v.x += a.x * dt; v.y += a.y * dt; v.z += a.z * dt;
-        p.x += (v.x * 0.5f) * dt; p.y += (v.y * 0.5f) * dt; p.z += (v.z * 0.5f) * dt;
-        vel[i] = v;
-        pos[i] = p;
-    }
+    if (KICK) kick_half_drift(pos, vel, i, a.x, a.y, a.z, dt);
 }
 
 // The same with Q waves per 64 bodies, each adding up a contiguous run of the planes (fixed split, fixed order: still
@@ -436,13 +431,7 @@ __global__ __launch_bounds__(64 * Q) void k_bf_sym_reduce_split(const float4* __
     }
     const float4 a = make_float4(g * sx, g * sy, g * sz, 0.f);
     acc[i] = a;
-    if (KICK) {
-        float4 p = pos[i], v = vel[i];
-        v.x += a.x * dt; v.y += a.y * dt; v.z += a.z * dt;
-        p.x += (v.x * 0.5f) * dt; p.y += (v.y * 0.5f) * dt; p.z += (v.z * 0.5f) * dt;
-        vel[i] = v;
-        pos[i] = p;
-    }
+    if (KICK) kick_half_drift(pos, vel, i, a.x, a.y, a.z, dt);
 }
 
 }  // namespace nbody

@@ -29,49 +29,6 @@ namespace nbody {
 
 constexpr int kWalkBlock = 64;   // one wave per workgroup: four body groups from different parts of the tree per CU (0.33 ms against 0.36 with 256)
 
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-struct alignas(32) NodeDev { float4 a; float4 b; };  // {com, mass}, {width^2, skip bits, width, leaf body}
-
-// The node index range [0, n_nodes) can be cut into n_seg contiguous segments walked by different
-// waves (more waves in flight: at N = 65 536 one wave per 64 bodies is only one wave per SIMD and the
-// walk is bound by the latency of its dependent node loads).  A body's walk enters segment k at the
-// first node >= first[k] that it would visit: to know, replay the opening tests of the ancestors of
-// node first[k] (root first; the host lists them, at most NBODY_MAX_TREE_DEPTH): an accepted
-// ancestor's skip link is where the walk resumes.  Ancestors are only tested here -- they are
-// counted and accumulated by the segment that contains them -- so every (body, node) pair is
-// evaluated by exactly one segment and the counters stay exact.
-struct WalkSplit {
-    int n_seg;
-    const int* first;        // [n_seg + 1] node index where each segment starts; first[n_seg] = n_nodes
-    const int* anc;          // [n_seg][kMaxAnc] ancestors of first[k], root first
-    const int* n_anc;        // [n_seg]
-    float4* planes;          // [n_seg][plane_stride] partial accelerations (n_seg > 1), indexed by the body's place in `order`
-                             // (tree order): the walk's lanes and the reduction's both touch consecutive entries
-    size_t plane_stride;
-    int diag_first;          // k_bh_walk: segments of a body group in order of distance from its own place in the tree
-    const int* poison;       // unsynchronised steps: != 0 -> do nothing (Shard::poison); may be null
-    const int* n_order_dev;  // unsynchronised steps: the live number of bodies to walk (the host's is an upper bound); may be null
-    int store_work;          // k_bh_walk, one segment: the body's visit count goes to acc.w (spatial shards balance by it)
-    int xcd_blocks;          // k_bh_walk_duo: gridDim.x / 8 when the lane groups are dealt to the XCDs in eighths of the tree order, else 0
-};
-
-template <bool DIRECT = false>
-__device__ __forceinline__ int walk_entry(const NodeDev* __restrict__ nodes, const WalkSplit& sp, int seg,
-                                          const float4 p, float theta2) {
-    const int s0 = sp.first[seg];
-    const int na = sp.n_anc[seg];
-    for (int k = 0; k < na; ++k) {
-        const int j = sp.anc[seg * kMaxAnc + k];
-        const float4 A = nodes[j].a;
-        const float4 B = nodes[j].b;
-        const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
-        const float r2 = (rx * rx + ry * ry) + rz * rz;
-        if (DIRECT && r2 < 1e-10f) return __float_as_int(B.y);  // NBODY_LEAF_DIRECT: skipped whole
-        if (B.x < theta2 * r2) return __float_as_int(B.y);  // accepted: the walk resumes after its subtree
-    }
-    return s0;  // every ancestor was opened: the walk arrives at first[seg] itself
-}
-
 #ifdef NBODY_TUNING
 __device__ unsigned long long nbody_bh_stamps[3 * 65536];  // diagnostic build only (DBG): per wave start, end (100 MHz ticks), iterations
 #endif
@@ -120,15 +77,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk(const NodeDev* __restrict__ n
                 const int skip = __float_as_int(B.y);
                 if (r2 < 1e-10f) { i = skip; continue; }                        // llm :933-935 (the body's own leaf: r2 = 0)
                 if (B.x < theta2 * r2 || skip == i + 1) {                       // llm :938 accepted cell, :958-972 leaf
-                    float k;
-                    if (FAST) {
-                        const float rinv = __builtin_amdgcn_rsqf(r2 + eps2);
-                        k = (g * A.w) * ((rinv * rinv) * rinv);
-                    } else {
-                        const float inv_r = 1.0f / __builtin_sqrtf(r2 + eps2);  // llm :942
-                        const float inv_r3 = inv_r * inv_r * inv_r;             // llm :944
-                        k = g * A.w * inv_r3;                                   // llm :947
-                    }
+                    const float k = monopole_k<FAST, true>(g, A.w, r2, eps2);
                     ax += rx * k; ay += ry * k; az += rz * k;                   // llm :950-952: one running sum
                     ++n_acc;
                     i = skip;
@@ -138,15 +87,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk(const NodeDev* __restrict__ n
                 continue;
             }
             if (B.x < theta2 * r2) {                                            // :192
-                float k;
-                if (FAST) {
-                    const float rinv = __builtin_amdgcn_rsqf(r2 + eps2);
-                    k = (g * A.w) * ((rinv * rinv) * rinv);
-                } else {
-                    const float r_dist = __builtin_sqrtf(r2 + eps2);                 // :193
-                    const float r_cubed = r_dist * r_dist * r_dist;             // :194
-                    k = ((g * A.w) / r_cubed);                            // :195
-                }
+                const float k = monopole_k<FAST, false>(g, A.w, r2, eps2);
                 ax += rx * k; ay += ry * k; az += rz * k;
                 ++n_acc;
                 i = __float_as_int(B.y);
@@ -190,9 +131,7 @@ __device__ __forceinline__ int duo_visit(const float4 A, const float2 B, int i, 
     if (DIRECT) {
         if (r2 < 1e-10f) return skip;                                   // llm :933-935
         if (B.x < theta2 * r2 || skip == i + 1) {                       // llm :938, :958-972
-            float k;
-            if (FAST) { const float rinv = __builtin_amdgcn_rsqf(r2 + eps2); k = (g * A.w) * ((rinv * rinv) * rinv); }
-            else { const float inv_r = 1.0f / __builtin_sqrtf(r2 + eps2); const float inv_r3 = inv_r * inv_r * inv_r; k = g * A.w * inv_r3; }
+            const float k = monopole_k<FAST, true>(g, A.w, r2, eps2);
             ax += rx * k; ay += ry * k; az += rz * k;
             ++n_acc;
             return skip;
@@ -200,9 +139,7 @@ __device__ __forceinline__ int duo_visit(const float4 A, const float2 B, int i, 
         return i + 1;
     }
     if (B.x < theta2 * r2) {                                            // :192
-        float k;
-        if (FAST) { const float rinv = __builtin_amdgcn_rsqf(r2 + eps2); k = (g * A.w) * ((rinv * rinv) * rinv); }
-        else { const float r_dist = __builtin_sqrtf(r2 + eps2); const float r_cubed = r_dist * r_dist * r_dist; k = ((g * A.w) / r_cubed); }
+        const float k = monopole_k<FAST, false>(g, A.w, r2, eps2);
         ax += rx * k; ay += ry * k; az += rz * k;
         ++n_acc;
         return skip;
@@ -276,6 +213,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_duo(const NodeDev* __restrict
 }
 
 #ifdef NBODY_TUNING   // ---- experimental walks (variants 1 and 2): measured, slower, kept reproducible in the tuning build only
+typedef float f32x8 __attribute__((ext_vector_type(8)));   // k_bh_walk_wave: a node record in eight SGPRs
 // Wave-cooperative form of the same walk.  The 64 lanes of a wave hold 64 neighbouring bodies
 // (tree order) and step through the UNION of their node sequences together: the node index is
 // wave-uniform, so the 32-byte node record arrives by scalar load in SGPRs (no divergent gather),
@@ -882,17 +820,7 @@ __global__ __launch_bounds__(256) void k_bh_reduce(const float4* __restrict__ pl
         sx += v.x; sy += v.y; sz += v.z; sw += v.w;
     }
     acc[b] = make_float4(sx, sy, sz, store_work ? sw : 0.f);   // (w: the body's visit count, a sum of small integers: exact)
-    if (KICK) {
-        float4 p = pos[b], v = vel[b];
-        v.x += sx * dt;                 // shared.rs:144
-        v.y += sy * dt;
-        v.z += sz * dt;
-        p.x += (v.x * 0.5f) * dt;       // shared.rs:146
-        p.y += (v.y * 0.5f) * dt;
-        p.z += (v.z * 0.5f) * dt;
-        vel[b] = v;
-        pos[b] = p;
-    }
+    if (KICK) kick_half_drift(pos, vel, b, sx, sy, sz, dt);
 }
 
 // The same with Q waves per 64 bodies: wave q adds the planes of the segments [q n_seg / Q, (q + 1) n_seg / Q) and wave 0
@@ -924,13 +852,7 @@ __global__ __launch_bounds__(64 * Q) void k_bh_reduce_split(const float4* __rest
     for (int w = 1; w < Q; ++w) { sx += part[w][0][lane]; sy += part[w][1][lane]; sz += part[w][2][lane]; sw += part[w][3][lane]; }
     const int b = order[t];
     acc[b] = make_float4(sx, sy, sz, store_work ? sw : 0.f);
-    if (KICK) {
-        float4 p = pos[b], v = vel[b];
-        v.x += sx * dt; v.y += sy * dt; v.z += sz * dt;                                       // shared.rs:144
-        p.x += (v.x * 0.5f) * dt; p.y += (v.y * 0.5f) * dt; p.z += (v.z * 0.5f) * dt;         // shared.rs:146
-        vel[b] = v;
-        pos[b] = p;
-    }
+    if (KICK) kick_half_drift(pos, vel, b, sx, sy, sz, dt);
 }
 
 #ifdef NBODY_TUNING
@@ -1243,18 +1165,6 @@ void launch_bh_field_walk(hipStream_t s, const FieldTree& t, const double* xyz, 
 // k_tr_bh_reduce adds them in run order.  No atomics on the sums.  A tracer has no leaf of its own, so under the reference
 // rule nothing is skipped, and under NBODY_LEAF_DIRECT a tracer within 1e-5 of a cell's centre of mass skips that cell, as a
 // body would.  {accepted, visited} go to the tracer statistics, one atomic pair per wave (walk_common.h).
-__device__ __forceinline__ void tr_bh_kick_drift(float4* __restrict__ pos, float4* __restrict__ vel, int b, float ax, float ay, float az, float dt) {
-    float4 p = pos[b], v = vel[b];
-    v.x += ax * dt;                 // shared.rs:144
-    v.y += ay * dt;
-    v.z += az * dt;
-    p.x += (v.x * 0.5f) * dt;       // shared.rs:146
-    p.y += (v.y * 0.5f) * dt;
-    p.z += (v.z * 0.5f) * dt;
-    vel[b] = v;
-    pos[b] = p;
-}
-
 template <bool DIRECT>
 __global__ __launch_bounds__(kWalkBlock) void k_tr_bh_walk(const NodeDev* __restrict__ nodes, const int* __restrict__ idx, int m_upper,
                                                            const int* __restrict__ m_dev, float4* __restrict__ tr_pos,
@@ -1283,8 +1193,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_tr_bh_walk(const NodeDev* __rest
             ++n_vis;
             if (DIRECT && r2 < 1e-10f) { i = skip; continue; }
             if (B.x < theta2 * r2 || (DIRECT && skip == i + 1)) {
-                const float rinv = __builtin_amdgcn_rsqf(r2 + eps2);
-                const float k = (g * A.w) * ((rinv * rinv) * rinv);
+                const float k = monopole_k<true, DIRECT>(g, A.w, r2, eps2);
                 ax += rx * k; ay += ry * k; az += rz * k;
                 ++n_acc;
                 i = skip;
@@ -1296,7 +1205,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_tr_bh_walk(const NodeDev* __rest
             split.planes[size_t(blockIdx.y) * split.plane_stride + t] = make_float4(ax, ay, az, 0.f);
         } else {
             tr_acc[b] = make_float4(ax, ay, az, 0.f);
-            if (do_kick) tr_bh_kick_drift(tr_pos, tr_vel, b, ax, ay, az, dt);
+            if (do_kick) kick_half_drift(tr_pos, tr_vel, b, ax, ay, az, dt);
         }
     }
     add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
@@ -1316,7 +1225,7 @@ __global__ __launch_bounds__(256) void k_tr_bh_reduce(const float4* __restrict__
     }
     const int b = idx[t];
     tr_acc[b] = make_float4(sx, sy, sz, 0.f);
-    if (do_kick) tr_bh_kick_drift(tr_pos, tr_vel, b, sx, sy, sz, dt);
+    if (do_kick) kick_half_drift(tr_pos, tr_vel, b, sx, sy, sz, dt);
 }
 
 int tracer_walk_groups(size_t m_upper, int n_split) {

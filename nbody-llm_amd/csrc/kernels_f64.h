@@ -52,7 +52,7 @@ void launch_bh_walk(hipStream_t s, const Dev& d, const Node64* nodes, int n_node
                     double theta2, unsigned long long* counters, int leaf_direct, Open64* stack, size_t stack_stride);
 // fast f64 walk (NBODY_MATH_FAST on an f64 handle): one running sum per lane instead of the reference's nested sums,
 // rsqrt + FMA instead of sqrt and divide, and the node index range cut into n_seg segments walked by different waves
-// (kernels_bh.hip WalkSplit: a body's walk enters segment k where the replay of the opening tests of first[k]'s
+// (walk_common.h WalkSplit: a body's walk enters segment k where the replay of the opening tests of first[k]'s
 // ancestors says it would); the K partial sums are added in segment order by launch_bh_reduce64.
 struct WalkSplit64 {
     int n_seg;

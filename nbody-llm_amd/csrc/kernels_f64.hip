@@ -207,17 +207,7 @@ __global__ __launch_bounds__(256) void k_bh_reduce64(const double4* __restrict__
     }
     const int b = order[t];
     acc[b] = make_double4(sx, sy, sz, 0.0);
-    if (KICK) {
-        double4 p = pos[b], v = vel[b];
-        v.x += sx * dt;
-        v.y += sy * dt;
-        v.z += sz * dt;
-        p.x += (v.x * 0.5) * dt;
-        p.y += (v.y * 0.5) * dt;
-        p.z += (v.z * 0.5) * dt;
-        vel[b] = v;
-        pos[b] = p;
-    }
+    if (KICK) nbody::kick_half_drift(pos, vel, b, sx, sy, sz, dt);
 }
 
 // ---- nbody_potentials(NBODY_POTENTIAL_TREE) on an f64 handle: kernels_bh.hip k_bh_pot_walk for 64-byte records -- the DIRECT

@@ -9,13 +9,12 @@
 //   k_field_reduce  planes added in plane order, times +g / -g, to the caller's place (TREE: through the sorted index).
 // Every plane entry is written exactly once per batch and there are no atomics: the same bits from run to run.
 #include "kernels_field.h"
+#include "real.h"   // widen
 
 namespace nbody {
 
 namespace {
 
-__device__ __forceinline__ double4 widen(const double4 p) { return p; }
-__device__ __forceinline__ double4 widen(const float4 p) { return make_double4(double(p.x), double(p.y), double(p.z), double(p.w)); }
 // the probe as the handle sees it: rounded to the nearest f32 once on f32 handles
 __device__ __forceinline__ double round_to(const float4*, double v) { return double(float(v)); }
 __device__ __forceinline__ double round_to(const double4*, double v) { return v; }

@@ -14,6 +14,7 @@
 //   k_pot_pairs_reduce   the planes added in plane order.
 // Every plane entry is written exactly once per call and there are no atomics: the same bits from run to run.
 #include "kernels_pot.h"
+#include "real.h"   // widen
 
 namespace nbody {
 
@@ -24,8 +25,6 @@ namespace {
 constexpr double kPad = 1.0e100;
 
 __device__ __forceinline__ double4 pad_body() { return make_double4(kPad, kPad, kPad, 0.0); }
-__device__ __forceinline__ double4 widen(const double4 p) { return p; }
-__device__ __forceinline__ double4 widen(const float4 p) { return make_double4(double(p.x), double(p.y), double(p.z), double(p.w)); }
 
 __device__ __forceinline__ double rot64(double v, int src_x4) {   // lane l receives lane (src_x4 / 4)'s value
     const long long b = __double_as_longlong(v);

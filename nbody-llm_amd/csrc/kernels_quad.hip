@@ -20,7 +20,6 @@ namespace nbody {
 
 constexpr int kQuadWalkBlock = 64;   // as k_bh_walk: one wave per workgroup when the node range is split
 
-struct alignas(32) QuadNode { float4 a; float4 b; };  // a node record as kernels_bh.hip reads it: {com, mass}, {width^2, skip bits, width, leaf body}
 struct alignas(32) QuadDev { float4 a; float4 b; };   // {xx, xy, xz, yy}, {yz, zz, 0, 0}
 
 // ---- the tensors
@@ -30,7 +29,7 @@ constexpr int kQuadSerial = 64;    // a node with at most this many descendants 
 struct Sum6 {
     double xx = 0., xy = 0., xz = 0., yy = 0., yz = 0., zz = 0.;
     // the term of node j about c if j is a leaf (an internal node's leaves follow it in the range)
-    __device__ __forceinline__ void add_leaf(const QuadNode* __restrict__ nodes, int j, double cx, double cy, double cz) {
+    __device__ __forceinline__ void add_leaf(const NodeDev* __restrict__ nodes, int j, double cx, double cy, double cz) {
         const float4 A = nodes[j].a;
         if (__float_as_int(nodes[j].b.y) != j + 1) return;
         const double dx = double(A.x) - cx, dy = double(A.y) - cy, dz = double(A.z) - cz, m = double(A.w);   // exact differences
@@ -54,7 +53,7 @@ struct Sum6 {
 // the same few sectors) are summed by their own thread; the workgroup then sums each of its large ones together, in a
 // fixed order (lane stride, shuffle tree, waves in order): the same bits from run to run.  The root's range is the whole
 // array, summed by the 256 threads of workgroup 0 -- the launch lasts as long as that one sum.
-__global__ __launch_bounds__(kQuadBlock) void k_tree_quad(const QuadNode* __restrict__ nodes, int n_nodes, QuadDev* __restrict__ quad,
+__global__ __launch_bounds__(kQuadBlock) void k_tree_quad(const NodeDev* __restrict__ nodes, int n_nodes, QuadDev* __restrict__ quad,
                                                           const int* __restrict__ info, const int* __restrict__ poison) {
     __shared__ int big[kQuadBlock];
     __shared__ int n_big;
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(kQuadBlock) void k_tree_quad(const QuadNode* __rest
 }
 
 // ---- the walk
-struct QuadSplit {           // kernels_bh.hip WalkSplit, what the one-body-per-lane walk reads of it
+struct QuadSplit {           // walk_common.h WalkSplit, what the one-body-per-lane walk reads of it
     int n_seg;
     const int* first;        // [n_seg + 1]
     const int* anc;          // [n_seg][kMaxAnc] ancestors of first[k], root first
@@ -109,9 +108,9 @@ struct QuadSplit {           // kernels_bh.hip WalkSplit, what the one-body-per-
     const int* n_order_dev;  // unsynchronised steps: the live number of bodies to walk; may be null
 };
 
-// kernels_bh.hip walk_entry: the first node >= first[seg] the body's walk visits (the opening tests of first[seg]'s ancestors)
+// walk_common.h walk_entry: the first node >= first[seg] the body's walk visits (the opening tests of first[seg]'s ancestors)
 template <bool DIRECT>
-__device__ __forceinline__ int quad_walk_entry(const QuadNode* __restrict__ nodes, const QuadSplit& sp, int seg, const float4 p, float theta2) {
+__device__ __forceinline__ int quad_walk_entry(const NodeDev* __restrict__ nodes, const QuadSplit& sp, int seg, const float4 p, float theta2) {
     const int na = sp.n_anc[seg];
     for (int k = 0; k < na; ++k) {
         const int j = sp.anc[seg * kMaxAnc + k];
@@ -132,7 +131,7 @@ __device__ __forceinline__ void quad_term(const float4 A, const QuadDev* __restr
                                           float r2, float g, float eps2, float& ax, float& ay, float& az) {
     const float rinv = __builtin_amdgcn_rsqf(r2 + eps2);
     if (!internal) {   // a leaf: the monopole term as k_bh_walk<FAST> rounds it
-        const float k = (g * A.w) * ((rinv * rinv) * rinv);
+        const float k = monopole_k<true, true>(g, A.w, r2, eps2);
         ax += rx * k; ay += ry * k; az += rz * k;
         return;
     }
@@ -150,7 +149,7 @@ __device__ __forceinline__ void quad_term(const float4 A, const QuadDev* __restr
 }
 
 template <bool DIRECT, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const QuadNode* __restrict__ nodes, const QuadDev* __restrict__ quad,
+__global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const NodeDev* __restrict__ nodes, const QuadDev* __restrict__ quad,
                                                         const int* __restrict__ order, int n_order, const float4* __restrict__ own_pos,
                                                         float4* __restrict__ acc, float g, float eps2, float theta2,
                                                         unsigned long long* __restrict__ counters, QuadSplit split) {
@@ -231,7 +230,7 @@ __device__ __forceinline__ QuadParts pot_quad_parts(const QuadDev* __restrict__ 
 }
 
 // k_bh_pot_walk<double> (kernels_bh.hip) with the scalar quadrupole part: the same tests, planes and counter slots
-__global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const QuadNode* __restrict__ nodes, const QuadDev* __restrict__ quad,
+__global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const NodeDev* __restrict__ nodes, const QuadDev* __restrict__ quad,
                                                                      const int* __restrict__ order, int n_order, const float4* __restrict__ own_pos,
                                                                      float eps2, float theta2, unsigned long long* __restrict__ counters,
                                                                      QuadSplit split, double* __restrict__ planes, size_t plane_stride) {
@@ -275,7 +274,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const QuadN
 
 // k_bh_field_walk<VEC, SCAL> (kernels_bh.hip) with both quadrupole parts
 template <bool VEC, bool SCAL>
-__global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const QuadNode* __restrict__ nodes, const QuadDev* __restrict__ quad,
+__global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const NodeDev* __restrict__ nodes, const QuadDev* __restrict__ quad,
                                                                        const double* __restrict__ xyz, const int* __restrict__ idx, int n,
                                                                        float eps2, float theta2, unsigned long long* __restrict__ counters,
                                                                        QuadSplit split, double4* __restrict__ planes, size_t plane_stride) {
@@ -329,7 +328,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const Qua
 
 void launch_tree_quad(hipStream_t s, const float4* nodes, int n_nodes, float4* quad, const int* info, const int* poison) {
     if (n_nodes <= 0) return;
-    hipLaunchKernelGGL(k_tree_quad, dim3((n_nodes + kQuadBlock - 1) / kQuadBlock), dim3(kQuadBlock), 0, s, reinterpret_cast<const QuadNode*>(nodes),
+    hipLaunchKernelGGL(k_tree_quad, dim3((n_nodes + kQuadBlock - 1) / kQuadBlock), dim3(kQuadBlock), 0, s, reinterpret_cast<const NodeDev*>(nodes),
                        n_nodes, reinterpret_cast<QuadDev*>(quad), info, poison);
 }
 
@@ -343,7 +342,7 @@ void launch_bh_walk_quad(hipStream_t s, const Shard& sh, const TreeDev& t, const
     sp.diag_first = tuning().bh_walk_order;
     sp.poison = t.poison; sp.n_order_dev = t.n_order_dev;
 #define WALKQ(DIRECT, BLK) hipLaunchKernelGGL((k_bh_walk_quad<DIRECT, BLK>), dim3((t.n_order + BLK - 1) / BLK, t.n_split), dim3(BLK), 0, s, \
-                                              reinterpret_cast<const QuadNode*>(t.nodes), reinterpret_cast<const QuadDev*>(quad), t.order, t.n_order, sh.own_pos(), sh.acc, g, g_soft2, theta2, counters, sp)
+                                              reinterpret_cast<const NodeDev*>(t.nodes), reinterpret_cast<const QuadDev*>(quad), t.order, t.n_order, sh.own_pos(), sh.acc, g, g_soft2, theta2, counters, sp)
     if (t.n_split <= 2) { if (leaf_direct) WALKQ(true, 256); else WALKQ(false, 256); }   // (k_bh_walk's rule: enough bodies to fill the chip)
     else { if (leaf_direct) WALKQ(true, kQuadWalkBlock); else WALKQ(false, kQuadWalkBlock); }
 #undef WALKQ
@@ -357,7 +356,7 @@ void launch_bh_pot_walk_quad(hipStream_t s, const float4* own_pos, const TreeDev
     sp.n_seg = t.n_split; sp.first = t.split_first; sp.anc = t.split_anc; sp.n_anc = t.split_n_anc;
     sp.n_order_dev = t.n_order_dev;
     hipLaunchKernelGGL(k_bh_pot_walk_quad, dim3((t.n_order + kQuadWalkBlock - 1) / kQuadWalkBlock, t.n_split), dim3(kQuadWalkBlock), 0, s,
-                       reinterpret_cast<const QuadNode*>(t.nodes), reinterpret_cast<const QuadDev*>(quad), t.order, t.n_order, own_pos, g_soft2, theta2,
+                       reinterpret_cast<const NodeDev*>(t.nodes), reinterpret_cast<const QuadDev*>(quad), t.order, t.n_order, own_pos, g_soft2, theta2,
                        counters, sp, planes, plane_stride);
     launch_pot_reduce(s, planes, t.n_split, plane_stride, t.order, t.n_order, sum, t.n_order_dev);
 }
@@ -368,7 +367,7 @@ void launch_bh_field_walk_quad(hipStream_t s, const FieldTree& t, const float4* 
     QuadSplit sp{};
     sp.n_seg = t.K; sp.first = t.first; sp.anc = t.anc; sp.n_anc = t.n_anc;
     const dim3 grid((n + kQuadWalkBlock - 1) / kQuadWalkBlock, t.K);
-    const QuadNode* nodes = static_cast<const QuadNode*>(t.nodes);
+    const NodeDev* nodes = static_cast<const NodeDev*>(t.nodes);
     const QuadDev* qd = reinterpret_cast<const QuadDev*>(quad);
 #define FIELD_WALKQ(V, S) hipLaunchKernelGGL((k_bh_field_walk_quad<V, S>), grid, dim3(kQuadWalkBlock), 0, s, nodes, qd, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
     if (want == 3) FIELD_WALKQ(true, true); else if (want == 1) FIELD_WALKQ(true, false); else if (want == 2) FIELD_WALKQ(false, true); else FIELD_WALKQ(false, false);

@@ -11,6 +11,7 @@
 //            once, and k_tr_reduce adds the planes in plane order (and takes the kick along).  No atomics on the sums: the
 //            same input gives the same bits, and a tracer's result depends on its position and the plan only.
 #include "kernels_tracer.h"
+#include "real.h"   // kick_half_drift
 
 #include <algorithm>
 
@@ -70,19 +71,6 @@ __global__ __launch_bounds__(kTrStrictBlock) void k_tr_bf_strict(const float4* _
 }
 
 // -------------------------------------------------------------------------------------- fast
-// integrate_after_force (shared.rs:141-148), k_kick_drift's arithmetic for one particle
-__device__ __forceinline__ void tr_kick_drift(float4* __restrict__ pos, float4* __restrict__ vel, int i, float ax, float ay, float az, float dt) {
-    float4 p = pos[i], v = vel[i];
-    v.x += ax * dt;
-    v.y += ay * dt;
-    v.z += az * dt;
-    p.x += (v.x * 0.5f) * dt;
-    p.y += (v.y * 0.5f) * dt;
-    p.z += (v.z * 0.5f) * dt;
-    vel[i] = v;
-    pos[i] = p;
-}
-
 template <int IPT>
 __global__ __launch_bounds__(kTrBlock) void k_tr_bf_fast(const float4* __restrict__ body_pos, const int* __restrict__ body_count,
                                                          float4* __restrict__ tr_pos, float4* __restrict__ tr_vel,
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(kTrBlock) void k_tr_bf_fast(const float4* __restric
         } else if (i < m) {
             const float fx = g * ax[q], fy = g * ay[q], fz = g * az[q];
             tr_acc[i] = make_float4(fx, fy, fz, 0.f);
-            if (do_kick) tr_kick_drift(tr_pos, tr_vel, i, fx, fy, fz, dt);
+            if (do_kick) kick_half_drift(tr_pos, tr_vel, i, fx, fy, fz, dt);
         }
     }
 }
@@ -156,7 +144,7 @@ __global__ __launch_bounds__(256) void k_tr_reduce(const float4* __restrict__ pl
     }
     const float fx = g * sx, fy = g * sy, fz = g * sz;
     tr_acc[i] = make_float4(fx, fy, fz, 0.f);
-    if (do_kick) tr_kick_drift(tr_pos, tr_vel, i, fx, fy, fz, dt);
+    if (do_kick) kick_half_drift(tr_pos, tr_vel, i, fx, fy, fz, dt);
 }
 
 void launch_tr_bf_strict(hipStream_t s, const Shard& tr, int m_upper, const Shard& bodies, float g, float g_soft2,
