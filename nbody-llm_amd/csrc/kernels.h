@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "shard.h"
+
 namespace nbody {
 
 // Launch-shape and scheme knobs of ONE handle (NbodyHandle::tune): set at nbody_create from the documented NBODY_*
@@ -53,48 +55,20 @@ struct WalkPlan { int bodies_per_lane; int segments; };
 WalkPlan walk_plan(size_t n_order, bool fast_math, int max_segments, float theta2);
 void bind_tuning(const Tuning* t);      // (nullptr: back to the defaults)
 
-// Device-resident body state of one shard.  Positions of ALL shards live in `pos_all`
-// (world_size segments of `seg_cap` float4 {x,y,z,m}); velocities and accelerations only for
-// the shard's own segment.  Body counts are device-resident so that bodies can leave the box
-// (Vec::retain, brute_force.rs:86) without a host round trip.
-struct Shard {
-    float4* pos_all = nullptr;   // [n_seg * seg_cap]  {x, y, z, mass}
-    float4* vel = nullptr;       // [seg_cap]          {vx, vy, vz, 0}
-    float4* acc = nullptr;       // [seg_cap]          {ax, ay, az, 0}
-    int* seg_count = nullptr;    // [n_seg] bodies alive per segment
-    int* escaped = nullptr;      // [1] bodies of the own segment flagged out of bounds by drift
-    unsigned char* keep = nullptr;  // [seg_cap] 1 = in bounds
-    // K4 (parallel retain, retain.h): per-tile status words of the decoupled look-back {epoch | flag | count} and the epoch
-    unsigned long long* tile_state = nullptr;   // [ceil(seg_cap / 1024) + 1]
-    int* epoch = nullptr;                       // [1]
-    // Barnes-Hut steps enqueued without a host round trip (device tree): [0] != 0 = "poisoned" (a build needed the
-    // host: deeper than the device build's 21 levels, or more nodes than allocated) -- every kernel that changes the
-    // state then does nothing until the host has dealt with it; [1] = steps completed since the host last looked
-    int* poison = nullptr;
-    int* ids = nullptr;                         // [seg_cap] spatial shards: index of each own body in the uploaded vector (moves with it)
-    unsigned long long* inter = nullptr;        // [1] brute force: directed interactions evaluated, n_own * (n_total - 1) per force pass from the LIVE counts
-    int n_seg = 1;
-    int seg_cap = 0;
-    int my_seg = 0;
-    float4* own_pos() const { return pos_all + size_t(my_seg) * seg_cap; }
-    int* own_count() const { return seg_count + my_seg; }
-};
-
-struct BoundsF {  // Bounds::min()/max() (shared.rs:223-229) evaluated once on the host in f32
-    float lo[3];
-    float hi[3];
-};
-
-// K0: PointParticle<f32,3> AoS (stride in floats) <-> SoA
-void launch_aos_to_soa(hipStream_t s, const float* aos, int stride_f, int n, float4* pos, float4* vel, float4* acc);
-void launch_soa_to_aos(hipStream_t s, float* aos, int stride_f, int n, const float4* pos, const float4* vel, const float4* acc);
-
+// K0-K4, written once for F = f32 and F = f64 over ShardT<F> (kernels_integrate.hip instantiates both)
+// K0: PointParticle<F,3> AoS (stride in elements of F) <-> SoA
+template <class F>
+void launch_aos_to_soa(hipStream_t s, const F* aos, int stride, int n, typename ShardT<F>::V4* pos, typename ShardT<F>::V4* vel,
+                       typename ShardT<F>::V4* acc);
+template <class F>
+void launch_soa_to_aos(hipStream_t s, F* aos, int stride, int n, const typename ShardT<F>::V4* pos, const typename ShardT<F>::V4* vel,
+                       const typename ShardT<F>::V4* acc);
 // K1: integrate_pre_force (shared.rs:135-140) + Bounds::contains flags (shared.rs:210-212)
-void launch_drift_half(hipStream_t s, const Shard& sh, int n_upper, float dt, BoundsF b);
+template <class F> void launch_drift_half(hipStream_t s, const ShardT<F>& sh, int n_upper, F dt, const typename RealTypes<F>::Bounds& b);
 // K4: Vec::retain (brute_force.rs:86): in-place order-preserving compaction, no-op unless *escaped
-void launch_compact(hipStream_t s, const Shard& sh, int n_upper);
-// K3: integrate_after_force (shared.rs:141-148)
-void launch_kick_drift(hipStream_t s, const Shard& sh, int n_upper, float dt);
+template <class F> void launch_compact(hipStream_t s, const ShardT<F>& sh, int n_upper);
+// K3: integrate_after_force (shared.rs:141-148); an empty shard launches one block only when sh.poison is set
+template <class F> void launch_kick_drift(hipStream_t s, const ShardT<F>& sh, int n_upper, F dt);
 
 // K2: BruteForceSimulation::update_forces (brute_force.rs:64-82)
 void launch_bf_forces_strict(hipStream_t s, const Shard& sh, int n_upper, float g, float g_soft2);

@@ -182,7 +182,7 @@ void launch_bf_forces_strict(hipStream_t s, const Shard& sh, int n_upper, float 
 void nbody64::launch_bf_strict(hipStream_t s, const Dev& d, int n_upper, double g, double eps2) {   // F = f64 (kernels_f64.h)
     if (n_upper <= 0) return;
     int blocks = (n_upper + nbody::kStrictBlock - 1) / nbody::kStrictBlock;
-    hipLaunchKernelGGL(nbody::k_bf_strict<double>, dim3(blocks), dim3(nbody::kStrictBlock), 0, s, d.pos_all, d.seg_count, d.n_seg, d.cap,
+    hipLaunchKernelGGL(nbody::k_bf_strict<double>, dim3(blocks), dim3(nbody::kStrictBlock), 0, s, d.pos_all, d.seg_count, d.n_seg, d.seg_cap,
                        d.my_seg, d.acc, g, eps2, d.inter);
 }
 namespace nbody {

@@ -309,7 +309,7 @@ uint64_t bf64_sym_pairs(const Bf64Plan& p, size_t n) {
 void launch_bf64_sym(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2) {
     if (!p.sym || p.sym_sets <= 0) return;
     const dim3 grid(blocks4((long long)p.A * p.K)), block(256);
-#define SYM64(I, R) hipLaunchKernelGGL((k_bf64_sym<I, R>), grid, block, 0, s, d.pos, d.count, p.A, p.K, p.sym_sets, planes, p.n_pad, eps2)
+#define SYM64(I, R) hipLaunchKernelGGL((k_bf64_sym<I, R>), grid, block, 0, s, d.own_pos(), d.own_count(), p.A, p.K, p.sym_sets, planes, p.n_pad, eps2)
     if (p.ipt == 4) { if (p.rot) SYM64(4, 1); else SYM64(4, 0); }
     else { if (p.rot) SYM64(8, 1); else SYM64(8, 0); }
 #undef SYM64
@@ -319,17 +319,17 @@ void launch_bf64_own(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* pl
     double4* out = planes + size_t(p.sym_sets + p.K) * p.n_pad;
     const dim3 grid(blocks4((long long)p.groups * p.k_own)), block(256);
     if (p.sym)
-        hipLaunchKernelGGL(k_bf64_os<1>, grid, block, 0, s, d.pos_all, d.seg_count, d.n_seg, d.cap, d.my_seg, 64 * p.ipt, p.A, p.groups, p.k_own,
+        hipLaunchKernelGGL(k_bf64_os<1>, grid, block, 0, s, d.pos_all, d.seg_count, d.n_seg, d.seg_cap, d.my_seg, 64 * p.ipt, p.A, p.groups, p.k_own,
                            out, p.n_pad, eps2);
     else
-        hipLaunchKernelGGL(k_bf64_os<0>, grid, block, 0, s, d.pos_all, d.seg_count, d.n_seg, d.cap, d.my_seg, 64, 1, p.groups, p.k_own,
+        hipLaunchKernelGGL(k_bf64_os<0>, grid, block, 0, s, d.pos_all, d.seg_count, d.n_seg, d.seg_cap, d.my_seg, 64, 1, p.groups, p.k_own,
                            out, p.n_pad, eps2);
 }
 
 void launch_bf64_remote(hipStream_t s, const Dev& d, const Bf64Plan& p, double4* planes, double eps2) {
     if (p.k_remote <= 0 || d.n_seg < 2) return;
     double4* out = planes + size_t(p.sym_sets + p.K + p.k_own) * p.n_pad;
-    hipLaunchKernelGGL(k_bf64_os<2>, dim3(blocks4((long long)p.groups * p.k_remote)), dim3(256), 0, s, d.pos_all, d.seg_count, d.n_seg, d.cap,
+    hipLaunchKernelGGL(k_bf64_os<2>, dim3(blocks4((long long)p.groups * p.k_remote)), dim3(256), 0, s, d.pos_all, d.seg_count, d.n_seg, d.seg_cap,
                        d.my_seg, 64, 1, p.groups, p.k_remote, out, p.n_pad, eps2);
 }
 
@@ -337,10 +337,10 @@ void launch_bf64_reduce(hipStream_t s, const Dev& d, const Bf64Plan& p, const do
     if (n_upper <= 0) return;
     const dim3 grid((n_upper + 255) / 256), block(256);
     if (kick_dt)
-        hipLaunchKernelGGL(k_bf64_reduce<true>, grid, block, 0, s, planes, p.n_planes, p.n_pad, d.count, g, d.acc, d.pos, d.vel, *kick_dt,
+        hipLaunchKernelGGL(k_bf64_reduce<true>, grid, block, 0, s, planes, p.n_planes, p.n_pad, d.own_count(), g, d.acc, d.own_pos(), d.vel, *kick_dt,
                            d.seg_count, d.n_seg, d.inter);
     else
-        hipLaunchKernelGGL(k_bf64_reduce<false>, grid, block, 0, s, planes, p.n_planes, p.n_pad, d.count, g, d.acc, d.pos, d.vel, 0.0,
+        hipLaunchKernelGGL(k_bf64_reduce<false>, grid, block, 0, s, planes, p.n_planes, p.n_pad, d.own_count(), g, d.acc, d.own_pos(), d.vel, 0.0,
                            d.seg_count, d.n_seg, d.inter);
 }
 

@@ -333,9 +333,9 @@ void launch_bh_walk(hipStream_t s, const Dev& d, const Node64* nodes, int n_node
     if (n_order <= 0) return;
     const dim3 grid(blocks_for(n_order, kWalkBlock));
     if (leaf_direct)
-        hipLaunchKernelGGL(k_bh_walk_direct, grid, dim3(kWalkBlock), 0, s, nodes, n_nodes, order, n_order, d.pos, d.acc, g, eps2, theta2, counters);
+        hipLaunchKernelGGL(k_bh_walk_direct, grid, dim3(kWalkBlock), 0, s, nodes, n_nodes, order, n_order, d.own_pos(), d.acc, g, eps2, theta2, counters);
     else
-        hipLaunchKernelGGL(k_bh_walk_nested, grid, dim3(kWalkBlock), 0, s, nodes, order, n_order, d.pos, d.acc, g, eps2, theta2, counters,
+        hipLaunchKernelGGL(k_bh_walk_nested, grid, dim3(kWalkBlock), 0, s, nodes, order, n_order, d.own_pos(), d.acc, g, eps2, theta2, counters,
                            stack, stack_stride);
 }
 void launch_bh_walk_fast(hipStream_t s, const Dev& d, const Node64* nodes, int n_nodes, const int* order, int n_order, double g, double eps2,
@@ -346,7 +346,7 @@ void launch_bh_walk_fast(hipStream_t s, const Dev& d, const Node64* nodes, int n
     const int gx = int(blocks_for((n_order + bpl - 1) / bpl, kWalkBlock)), gx8 = (gx + 7) / 8 * 8;
     const int xcd_blocks = nbody::tuning().bh_walk_xcd ? gx8 / 8 : 0;
     const dim3 grid(xcd_blocks ? gx8 : gx, split.n_seg);
-#define WALK64(D, B) hipLaunchKernelGGL((k_bh_walk_fast64<D, B>), grid, dim3(kWalkBlock), 0, s, nodes, n_nodes, order, n_order, d.pos, d.acc, g, eps2, theta2, counters, split, xcd_blocks)
+#define WALK64(D, B) hipLaunchKernelGGL((k_bh_walk_fast64<D, B>), grid, dim3(kWalkBlock), 0, s, nodes, n_nodes, order, n_order, d.own_pos(), d.acc, g, eps2, theta2, counters, split, xcd_blocks)
 #define WALK64_B(D) do { if (bpl == 6) WALK64(D, 6); else if (bpl == 4) WALK64(D, 4); else if (bpl == 3) WALK64(D, 3); else if (bpl == 2) WALK64(D, 2); else WALK64(D, 1); } while (0)
     if (leaf_direct) WALK64_B(true); else WALK64_B(false);
 #undef WALK64_B
@@ -354,11 +354,11 @@ void launch_bh_walk_fast(hipStream_t s, const Dev& d, const Node64* nodes, int n
     if (split.n_seg > 1) {
         if (kick_dt) {   // (every own body is in `order` exactly once: the kick reaches them all)
             hipLaunchKernelGGL(k_bh_reduce64<true>, dim3(blocks_for(n_order, 256)), dim3(256), 0, s, split.planes, split.n_seg, split.plane_stride, order, n_order,
-                               d.acc, d.pos, d.vel, *kick_dt);
+                               d.acc, d.own_pos(), d.vel, *kick_dt);
             if (kicked) *kicked = 1;
         } else {
             hipLaunchKernelGGL(k_bh_reduce64<false>, dim3(blocks_for(n_order, 256)), dim3(256), 0, s, split.planes, split.n_seg, split.plane_stride, order, n_order,
-                               d.acc, d.pos, d.vel, 0.0);
+                               d.acc, d.own_pos(), d.vel, 0.0);
         }
     }
 }
@@ -380,7 +380,7 @@ void launch_bh_field_walk(hipStream_t s, const nbody::FieldTree& t, const double
 }
 void launch_energy(hipStream_t s, const Dev& d, int n_upper, double eps2, double* out2) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_energy, dim3(blocks_for(n_upper, kEnergyBlock)), dim3(kEnergyBlock), 0, s, d.pos, d.vel, d.count, eps2, out2);
+    hipLaunchKernelGGL(k_energy, dim3(blocks_for(n_upper, kEnergyBlock)), dim3(kEnergyBlock), 0, s, d.own_pos(), d.vel, d.own_count(), eps2, out2);
 }
 
 }  // namespace nbody64

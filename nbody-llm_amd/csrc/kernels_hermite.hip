@@ -717,34 +717,34 @@ inline int blocks_for(long long n, int per) { return int((n + per - 1) / per); }
 // ----------------------------------------------------------------------------------- host side
 void launch_hm_predict(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, const HermiteCoef& c) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_hm_predict, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.count, hd.xp, hd.vp, c);
+    hipLaunchKernelGGL(k_hm_predict, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.own_pos(), d.vel, d.acc, hd.jerk, d.own_count(), hd.xp, hd.vp, c);
 }
 
 void launch_hm_strict(hipStream_t s, const Dev& d, const double4* x, const double4* v, double4* out_a, double4* out_j, int n_upper, double g, double eps2) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_hm_strict, dim3(blocks_for(n_upper, kStrictBlock)), dim3(kStrictBlock), 0, s, x, v, d.count, out_a, out_j, g, eps2, d.inter);
+    hipLaunchKernelGGL(k_hm_strict, dim3(blocks_for(n_upper, kStrictBlock)), dim3(kStrictBlock), 0, s, x, v, d.own_count(), out_a, out_j, g, eps2, d.inter);
 }
 
 void launch_hm_correct(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, const HermiteCoef& c, const Bounds64& b) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_hm_correct, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, hd.a1, hd.j1, d.pos, d.vel, d.acc, hd.jerk, d.count, d.keep,
+    hipLaunchKernelGGL(k_hm_correct, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, hd.a1, hd.j1, d.own_pos(), d.vel, d.acc, hd.jerk, d.own_count(), d.keep,
                        d.escaped, c, b);
 }
 
 void launch_hm_compact(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper, int* level) {
     if (n_upper <= 0) return;
     if (level)
-        hipLaunchKernelGGL(k_hm_compact<true>, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.count,
+        hipLaunchKernelGGL(k_hm_compact<true>, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.own_pos(), d.vel, d.acc, hd.jerk, d.keep, d.own_count(),
                            d.escaped, d.tile_state, d.epoch, level);
     else
-        hipLaunchKernelGGL(k_hm_compact<false>, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.count,
+        hipLaunchKernelGGL(k_hm_compact<false>, dim3(blocks_for(n_upper, kTile)), dim3(kTile), 0, s, d.own_pos(), d.vel, d.acc, hd.jerk, d.keep, d.own_count(),
                            d.escaped, d.tile_state, d.epoch, level);
 }
 
 int launch_hm_min_ratio(hipStream_t s, const Dev& d, const HermiteDev& hd, int n_upper) {
     if (n_upper <= 0) return 0;
     const int blocks = blocks_for(n_upper, 256);
-    hipLaunchKernelGGL(k_hm_min_ratio, dim3(blocks), dim3(256), 0, s, d.acc, hd.jerk, d.count, hd.ratio);
+    hipLaunchKernelGGL(k_hm_min_ratio, dim3(blocks), dim3(256), 0, s, d.acc, hd.jerk, d.own_count(), hd.ratio);
     return blocks;
 }
 
@@ -752,7 +752,7 @@ void launch_hm_sym(hipStream_t s, const Dev& d, const Bf64Plan& p, const double4
     if (!p.sym || p.sym_sets <= 0) return;
     const dim3 grid(blocks_for((long long)p.A * p.K, 4)), block(256);
     const size_t joff = size_t(p.n_planes) * p.n_pad;
-#define HMSYM(I, R) hipLaunchKernelGGL((k_hm_sym<I, R>), grid, block, 0, s, x, v, d.count, p.A, p.K, p.sym_sets, planes, p.n_pad, joff, eps2)
+#define HMSYM(I, R) hipLaunchKernelGGL((k_hm_sym<I, R>), grid, block, 0, s, x, v, d.own_count(), p.A, p.K, p.sym_sets, planes, p.n_pad, joff, eps2)
     if (p.ipt == 8) { if (p.rot) HMSYM(8, 1); else HMSYM(8, 0); }
     else { if (p.rot) HMSYM(4, 1); else HMSYM(4, 0); }   // (hermite_ipt() yields nothing else)
 #undef HMSYM
@@ -763,9 +763,9 @@ void launch_hm_own(hipStream_t s, const Dev& d, const Bf64Plan& p, const double4
     const dim3 grid(blocks_for((long long)p.groups * p.k_own, 4)), block(256);
     const size_t joff = size_t(p.n_planes) * p.n_pad;
     if (p.sym)
-        hipLaunchKernelGGL(k_hm_os<1>, grid, block, 0, s, x, v, d.count, 64 * p.ipt, p.A, p.groups, p.k_own, out, p.n_pad, joff, eps2);
+        hipLaunchKernelGGL(k_hm_os<1>, grid, block, 0, s, x, v, d.own_count(), 64 * p.ipt, p.A, p.groups, p.k_own, out, p.n_pad, joff, eps2);
     else
-        hipLaunchKernelGGL(k_hm_os<0>, grid, block, 0, s, x, v, d.count, 64, 1, p.groups, p.k_own, out, p.n_pad, joff, eps2);
+        hipLaunchKernelGGL(k_hm_os<0>, grid, block, 0, s, x, v, d.own_count(), 64, 1, p.groups, p.k_own, out, p.n_pad, joff, eps2);
 }
 
 void launch_hm_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const Bf64Plan& p, const double4* planes, int n_upper, double g,
@@ -774,10 +774,10 @@ void launch_hm_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const B
     const dim3 grid(blocks_for(n_upper, 256)), block(256);
     const size_t joff = size_t(p.n_planes) * p.n_pad;
     if (c)
-        hipLaunchKernelGGL(k_hm_reduce<true>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.count, g, out_a, out_j, d.pos, d.vel, d.acc,
+        hipLaunchKernelGGL(k_hm_reduce<true>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.own_count(), g, out_a, out_j, d.own_pos(), d.vel, d.acc,
                            hd.jerk, d.keep, d.escaped, *c, b, d.inter);
     else
-        hipLaunchKernelGGL(k_hm_reduce<false>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.count, g, out_a, out_j, d.pos, d.vel, d.acc,
+        hipLaunchKernelGGL(k_hm_reduce<false>, grid, block, 0, s, planes, p.n_planes, p.n_pad, joff, d.own_count(), g, out_a, out_j, d.own_pos(), d.vel, d.acc,
                            hd.jerk, d.keep, d.escaped, HermiteCoef{}, b, d.inter);
 }
 
@@ -785,15 +785,15 @@ void launch_hm_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, const B
 void launch_hmb_start_levels(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_upper, double eta, double abs_dt,
                              int max_level) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_hmb_start, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.acc, hd.jerk, d.count, bd.level, eta, abs_dt, max_level);
+    hipLaunchKernelGGL(k_hmb_start, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.acc, hd.jerk, d.own_count(), bd.level, eta, abs_dt, max_level);
 }
 
 void launch_hmb_schedule(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_upper, int T, double tick, int slot) {
     if (n_upper <= 0) return;
     const int tiles = blocks_for(n_upper, kTile);
-    hipLaunchKernelGGL(k_hmb_min, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, bd.tau, bd.level, d.count, T, bd.smin, slot);
-    hipLaunchKernelGGL(k_hmb_count, dim3(tiles), dim3(kTile), 0, s, bd.tau, bd.level, d.count, T, bd.smin, slot, bd.tile_count);
-    hipLaunchKernelGGL(k_hmb_list, dim3(tiles), dim3(kTile), 0, s, d.pos, d.vel, d.acc, hd.jerk, bd.tau, bd.level, d.count, T, tick, bd.smin, slot,
+    hipLaunchKernelGGL(k_hmb_min, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, bd.tau, bd.level, d.own_count(), T, bd.smin, slot);
+    hipLaunchKernelGGL(k_hmb_count, dim3(tiles), dim3(kTile), 0, s, bd.tau, bd.level, d.own_count(), T, bd.smin, slot, bd.tile_count);
+    hipLaunchKernelGGL(k_hmb_list, dim3(tiles), dim3(kTile), 0, s, d.own_pos(), d.vel, d.acc, hd.jerk, bd.tau, bd.level, d.own_count(), T, tick, bd.smin, slot,
                        bd.tile_count, bd.list, bd.sched, hd.xp, hd.vp);
 }
 
@@ -813,14 +813,14 @@ size_t hm_act_plane_rows(int cap) {
 void launch_hm_act(hipStream_t s, const Dev& d, const BlockDev& bd, const HmActPlan& p, const double4* x, const double4* v, double eps2) {
     if (p.groups <= 0) return;
     const size_t stride = size_t(p.groups) * 64;
-    hipLaunchKernelGGL(k_hm_act, dim3(blocks_for((long long)p.groups * p.K, 4)), dim3(256), 0, s, x, v, d.count, bd.list, bd.sched + 1, p.groups, p.K,
+    hipLaunchKernelGGL(k_hm_act, dim3(blocks_for((long long)p.groups * p.K, 4)), dim3(256), 0, s, x, v, d.own_count(), bd.list, bd.sched + 1, p.groups, p.K,
                        bd.planes, stride, size_t(p.K) * stride, eps2);
 }
 
 void launch_hm_act_strict(hipStream_t s, const Dev& d, const HermiteDev& hd, const BlockDev& bd, int n_act, const double4* x, const double4* v,
                           double g, double eps2) {
     if (n_act <= 0) return;
-    hipLaunchKernelGGL(k_hm_act_strict, dim3(blocks_for(n_act, kStrictBlock)), dim3(kStrictBlock), 0, s, x, v, d.count, bd.list, bd.sched + 1, hd.a1,
+    hipLaunchKernelGGL(k_hm_act_strict, dim3(blocks_for(n_act, kStrictBlock)), dim3(kStrictBlock), 0, s, x, v, d.own_count(), bd.list, bd.sched + 1, hd.a1,
                        hd.j1, g, eps2);
 }
 
@@ -830,7 +830,7 @@ void launch_hmb_finish(hipStream_t s, const Dev& d, const HermiteDev& hd, const 
     const dim3 grid(blocks_for(n_act, 256)), block(256);
     const size_t stride = p ? size_t(p->groups) * 64 : 0;
 #define HMFIN(PL) hipLaunchKernelGGL((k_hmb_finish<PL, true>), grid, block, 0, s, bd.planes, p ? p->K : 0, stride, size_t(p ? p->K : 0) * stride, hd.a1, \
-                                     hd.j1, nullptr, nullptr, d.count, bd.list, bd.sched, g, d.pos, d.vel, d.acc, hd.jerk, d.keep, d.escaped, bd.tau,  \
+                                     hd.j1, nullptr, nullptr, d.own_count(), bd.list, bd.sched, g, d.own_pos(), d.vel, d.acc, hd.jerk, d.keep, d.escaped, bd.tau,  \
                                      bd.level, T, max_level, tick, abs_dt, eta, b, d.inter)
     if (p) HMFIN(true); else HMFIN(false);
 #undef HMFIN
@@ -840,7 +840,7 @@ void launch_hm_act_reduce(hipStream_t s, const Dev& d, const HermiteDev& hd, con
     if (n_act <= 0) return;
     const size_t stride = size_t(p.groups) * 64;
     hipLaunchKernelGGL((k_hmb_finish<true, false>), dim3(blocks_for(n_act, 256)), dim3(256), 0, s, bd.planes, p.K, stride, size_t(p.K) * stride, nullptr,
-                       nullptr, hd.a1, hd.j1, d.count, bd.list, bd.sched, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                       nullptr, hd.a1, hd.j1, d.own_count(), bd.list, bd.sched, g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
                        0.0, 0.0, 0.0, Bounds64{}, nullptr);
 }
 

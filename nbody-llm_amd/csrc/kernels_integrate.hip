@@ -1,5 +1,5 @@
 // kernels_integrate.hip -- O(N) kernels around the force pass (gfx950), written once for F = f32 and F = f64 (real.h)
-// with the launchers of both (kernels.h, kernels_f64.h).
+// with their launchers over ShardT<F> (kernels.h).
 //
 // K0  AoS <-> SoA transposition of PointParticle<F,3> records (shared.rs:151-158)
 // K1  drift_half    = LeapFrogIntegrator::integrate_pre_force (shared.rs:135-140)
@@ -18,7 +18,7 @@
 
 namespace nbody {
 
-// F = float: the f32 handles (poison: Shard::poison, may be null); F = double: the f64 handles (nbody64, no poison)
+// F = float: the f32 handles (poison: Shard::poison, may be null); F = double: the f64 handles (poison and ids null)
 template <class F>
 __global__ __launch_bounds__(256) void k_aos_to_soa(const F* __restrict__ aos, int stride, int n, typename Real<F>::V4* __restrict__ pos,
                                                     typename Real<F>::V4* __restrict__ vel, typename Real<F>::V4* __restrict__ acc) {
@@ -103,64 +103,53 @@ __global__ __launch_bounds__(kCompactTile) void k_compact(typename Real<F>::V4* 
 
 static inline int blocks_for(int n, int bs) { return n <= 0 ? 0 : (n + bs - 1) / bs; }
 
-void launch_aos_to_soa(hipStream_t s, const float* aos, int stride_f, int n, float4* pos, float4* vel, float4* acc) {
+template <class F>
+void launch_aos_to_soa(hipStream_t s, const F* aos, int stride, int n, typename ShardT<F>::V4* pos, typename ShardT<F>::V4* vel,
+                       typename ShardT<F>::V4* acc) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_aos_to_soa<float>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_f, n, pos, vel, acc);
+    hipLaunchKernelGGL(k_aos_to_soa<F>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride, n, pos, vel, acc);
 }
-void launch_soa_to_aos(hipStream_t s, float* aos, int stride_f, int n, const float4* pos, const float4* vel, const float4* acc) {
+template <class F>
+void launch_soa_to_aos(hipStream_t s, F* aos, int stride, int n, const typename ShardT<F>::V4* pos, const typename ShardT<F>::V4* vel,
+                       const typename ShardT<F>::V4* acc) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_soa_to_aos<float>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_f, n, pos, vel, acc);
+    hipLaunchKernelGGL(k_soa_to_aos<F>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride, n, pos, vel, acc);
 }
-void launch_drift_half(hipStream_t s, const Shard& sh, int n_upper, float dt, BoundsF b) {
+template <class F>
+void launch_drift_half(hipStream_t s, const ShardT<F>& sh, int n_upper, F dt, const typename RealTypes<F>::Bounds& b) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_drift_half<float>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, sh.own_pos(), sh.vel,
-                       sh.own_count(), sh.keep, sh.escaped, dt, b, sh.poison);
+    hipLaunchKernelGGL(k_drift_half<F>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, sh.own_pos(), sh.vel, sh.own_count(), sh.keep,
+                       sh.escaped, dt, b, sh.poison);
 }
-void launch_compact(hipStream_t s, const Shard& sh, int n_upper) {
+template <class F>
+void launch_compact(hipStream_t s, const ShardT<F>& sh, int n_upper) {
     if (n_upper <= 0) return;
-    hipLaunchKernelGGL(k_compact<float>, dim3(blocks_for(n_upper, kCompactTile)), dim3(kCompactTile), 0, s, sh.own_pos(), sh.vel, sh.acc,
+    hipLaunchKernelGGL(k_compact<F>, dim3(blocks_for(n_upper, kCompactTile)), dim3(kCompactTile), 0, s, sh.own_pos(), sh.vel, sh.acc,
                        sh.keep, sh.own_count(), sh.escaped, sh.tile_state, sh.epoch, sh.poison, sh.ids);
 }
-void launch_kick_drift(hipStream_t s, const Shard& sh, int n_upper, float dt) {
-    // (launched even for an empty shard: the step counter of an unsynchronised run rides in it)
-    hipLaunchKernelGGL(k_kick_drift<float>, dim3(std::max(1, blocks_for(n_upper, 256))), dim3(256), 0, s, sh.own_pos(), sh.vel, sh.acc,
-                       sh.own_count(), dt, sh.poison);
+template <class F>
+void launch_kick_drift(hipStream_t s, const ShardT<F>& sh, int n_upper, F dt) {
+    // with a poison word even an empty shard launches one block: the step counter of an unsynchronised run rides in it
+    const int blocks = blocks_for(n_upper, 256);
+    if (blocks == 0 && !sh.poison) return;
+    hipLaunchKernelGGL(k_kick_drift<F>, dim3(std::max(1, blocks)), dim3(256), 0, s, sh.own_pos(), sh.vel, sh.acc, sh.own_count(), dt,
+                       sh.poison);
 }
+
+#define NBODY_INTEGRATE_LAUNCHERS(F, V4)                                                                              \
+    template void launch_aos_to_soa<F>(hipStream_t, const F*, int, int, V4*, V4*, V4*);                               \
+    template void launch_soa_to_aos<F>(hipStream_t, F*, int, int, const V4*, const V4*, const V4*);                   \
+    template void launch_drift_half<F>(hipStream_t, const ShardT<F>&, int, F, const RealTypes<F>::Bounds&);           \
+    template void launch_compact<F>(hipStream_t, const ShardT<F>&, int);                                              \
+    template void launch_kick_drift<F>(hipStream_t, const ShardT<F>&, int, F);
+NBODY_INTEGRATE_LAUNCHERS(float, float4)
+NBODY_INTEGRATE_LAUNCHERS(double, double4)
+#undef NBODY_INTEGRATE_LAUNCHERS
 
 }  // namespace nbody
 
-// F = f64 (kernels_f64.h): one shard's own block, no poison word; an empty block launches nothing
 namespace nbody64 {
-using nbody::blocks_for;
-
-void launch_aos_to_soa(hipStream_t s, const double* aos, int stride_d, int n, const Dev& d, size_t first) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(nbody::k_aos_to_soa<double>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_d, n, d.pos + first, d.vel + first,
-                       d.acc + first);
-}
 void launch_aos_to_pos(hipStream_t s, const double* aos, int stride_d, int n, double4* pos) {   // another shard's block: positions only
-    if (n <= 0) return;
-    hipLaunchKernelGGL(nbody::k_aos_to_soa<double>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_d, n, pos, (double4*)nullptr,
-                       (double4*)nullptr);
+    nbody::launch_aos_to_soa<double>(s, aos, stride_d, n, pos, nullptr, nullptr);
 }
-void launch_soa_to_aos(hipStream_t s, double* aos, int stride_d, int n, const Dev& d) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(nbody::k_soa_to_aos<double>, dim3(blocks_for(n, 256)), dim3(256), 0, s, aos, stride_d, n, d.pos, d.vel, d.acc);
-}
-void launch_drift_half(hipStream_t s, const Dev& d, int n_upper, double dt, const Bounds64& b) {
-    if (n_upper <= 0) return;
-    hipLaunchKernelGGL(nbody::k_drift_half<double>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.pos, d.vel, d.count, d.keep, d.escaped, dt,
-                       b, (const int*)nullptr);
-}
-void launch_compact(hipStream_t s, const Dev& d, int n_upper) {
-    if (n_upper <= 0) return;
-    hipLaunchKernelGGL(nbody::k_compact<double>, dim3(blocks_for(n_upper, nbody::kCompactTile)), dim3(nbody::kCompactTile), 0, s, d.pos, d.vel,
-                       d.acc, d.keep, d.count, d.escaped, d.tile_state, d.epoch, (const int*)nullptr, (int*)nullptr);
-}
-void launch_kick_drift(hipStream_t s, const Dev& d, int n_upper, double dt) {
-    if (n_upper <= 0) return;
-    hipLaunchKernelGGL(nbody::k_kick_drift<double>, dim3(blocks_for(n_upper, 256)), dim3(256), 0, s, d.pos, d.vel, d.acc, d.count, dt,
-                       (int*)nullptr);
-}
-
 }  // namespace nbody64

@@ -39,32 +39,6 @@ int use_device(NbodyHandle* h) {
     return NBODY_OK;
 }
 
-void compute_bounds(NbodyHandle* h) {
-    float hw = h->width * 0.5f;  // Bounds::new
-    for (int i = 0; i < 3; ++i) {
-        h->bnd.lo[i] = h->center[i] + (-hw);  // add_scalar(-half_width), shared.rs:224
-        h->bnd.hi[i] = h->center[i] + hw;     // shared.rs:228
-    }
-}
-
-// refresh the host view of the own count (one 4-byte D2H + sync), only when it may be stale
-int sync_count(NbodyHandle* h) {
-    if (!h->count_dirty) return NBODY_OK;
-    HIP_TRY(h, hipMemcpyAsync(h->h_counts, h->sh.seg_count, sizeof(int) * h->sh.n_seg, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int s = 0; s < h->sh.n_seg; ++s) h->seg_count_host[s] = h->h_counts[s];
-    h->n_local = size_t(h->h_counts[h->sh.my_seg]);
-    h->count_dirty = false;
-    return NBODY_OK;
-}
-
-int push_counts(NbodyHandle* h) {
-    for (int s = 0; s < h->sh.n_seg; ++s) h->h_counts[s] = h->seg_count_host[s];
-    HIP_TRY(h, hipMemcpyAsync(h->sh.seg_count, h->h_counts, sizeof(int) * h->sh.n_seg, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));  // h_counts is reused
-    return NBODY_OK;
-}
-
 size_t total_upper(const NbodyHandle* h) {
     size_t t = 0;
     for (int c : h->seg_count_host) t += size_t(c);
@@ -103,6 +77,15 @@ int comm_check(NbodyHandle* h) {
     return rc ? fail(h, rc, h->tp->error()) : NBODY_OK;
 }
 
+int fail_if_hip(NbodyHandle* h, hipError_t e) { return e == hipSuccess ? NBODY_OK : fail(h, NBODY_ERR_HIP, hipGetErrorString(e)); }
+
+// a record's stride holds the 10 F of a PointParticle<F,3> and keeps them aligned
+int check_stride(NbodyHandle* h, size_t stride) {
+    const size_t e = h->f64 ? sizeof(double) : sizeof(float);
+    if (stride >= 10 * e && stride % e == 0) return NBODY_OK;
+    return fail(h, NBODY_ERR_INVALID, h->f64 ? "f64 handle: stride must be a multiple of 8 and >= 80 bytes" : "stride must be a multiple of 4 and >= 40 bytes");
+}
+
 // ---- Vec::push / Vec::swap_remove on a world of index-block shards (collective: every rank makes the same call).
 // The global vector is the concatenation of the ranks' blocks, so push appends to the LAST rank's block and
 // swap_remove(i) moves the world's last body into slot i -- across ranks if they differ (one 40-byte message).
@@ -113,14 +96,7 @@ int sharded_counts_exact(NbodyHandle* h) {   // every rank learns every block's 
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     TP_TRY(h, h->tp->all_gather(h->sh.seg_count, sizeof(int), h->stream));
     h->count_dirty = true;
-    return sync_count(h);
-}
-
-int push_own_count(NbodyHandle* h) {
-    h->h_counts[h->sh.my_seg] = int(h->n_local);
-    HIP_TRY(h, hipMemcpyAsync(h->sh.own_count(), h->h_counts + h->sh.my_seg, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NBODY_OK;
+    return h->sync_count(h, h->stream);
 }
 
 int sharded_add_point(NbodyHandle* h, const void* particle) {
@@ -129,19 +105,10 @@ int sharded_add_point(NbodyHandle* h, const void* particle) {
     const int G = h->sh.n_seg, last = G - 1;
     if (total_upper(h) >= h->cfg.capacity || h->seg_count_host[last] >= h->sh.seg_cap)
         return fail(h, NBODY_ERR_CAPACITY, "capacity exhausted (a push goes to the end of the vector: the last rank's block is full)");
-    if (h->sh.my_seg == last) {
-        const float* p = static_cast<const float*>(particle);
-        float4 rec[3] = {make_float4(p[0], p[1], p[2], p[9]), make_float4(p[3], p[4], p[5], 0.f), make_float4(p[6], p[7], p[8], 0.f)};
-        const size_t k = h->n_local;
-        HIP_TRY(h, hipMemcpyAsync(h->sh.own_pos() + k, &rec[0], sizeof(float4), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->sh.vel + k, &rec[1], sizeof(float4), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->sh.acc + k, &rec[2], sizeof(float4), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->n_local = k + 1;
-        rc = push_own_count(h);
-        if (rc) return rc;
-    }
-    h->seg_count_host[last] += 1;   // (every rank: the bound its grids are sized from; the device copy arrives with the next exchange)
+    // every rank raises its bound of the last block (its grids are sized from it; the device copy arrives with the next
+    // exchange); the rank that owns the block does so by storing the body
+    if (h->sh.my_seg == last) return h->push_one(h, h->stream, particle);
+    h->seg_count_host[last] += 1;
     return NBODY_OK;
 }
 
@@ -162,7 +129,7 @@ int sharded_remove_point(NbodyHandle* h, size_t index) {
             HIP_TRY(h, hipMemcpyAsync(h->sh.acc + j, h->sh.acc + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
         }
     } else if (me == last || me == r) {
-        rc = ensure_aos(h, 2);
+        rc = h->ensure_aos(h, 2);
         if (rc) return rc;
         if (me == last) {   // the world's last body as one PointParticle record, to the rank that holds slot `index`
             nbody::launch_soa_to_aos(h->stream, h->d_aos, 10, 1, h->sh.own_pos() + tail, h->sh.vel + tail, h->sh.acc + tail);
@@ -175,7 +142,7 @@ int sharded_remove_point(NbodyHandle* h, size_t index) {
     }
     if (me == last) {
         h->n_local = tail;
-        rc = push_own_count(h);
+        rc = h->push_own_count(h, h->stream);
         if (rc) return rc;
     } else {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -693,7 +660,7 @@ int resolve_async(NbodyHandle* h) {
         h->elapsed = rest[0].elapsed_before;
         h->stats.steps -= rest.size();
         h->host_tree_once = true;             // (cleared by the force pass that uses it)
-        int rc = sync_count(h);
+        int rc = h->sync_count(h, h->stream);
         if (rc) return rc;
         rc = step_end(h, rest[0].dt);         // forces on the host-built tree, kick + half drift
         if (rc) return rc;
@@ -944,7 +911,7 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
     const bool saved_dirty = h->count_dirty, saved_once = h->host_tree_once;
     const std::vector<int> saved_counts = h->seg_count_host;
     h->count_dirty = true;
-    rc = sync_count(h);
+    rc = h->sync_count(h, h->stream);
     if (!rc) rc = nbody::pot::begin(h, size_t(sh.seg_cap));
     bodies->pos_all = sh.pos_all; bodies->vel = sh.vel; bodies->seg_count = sh.seg_count;
     bodies->f64 = 0; bodies->n_seg = sh.n_seg; bodies->seg_cap = sh.seg_cap; bodies->my_seg = sh.my_seg;
@@ -983,10 +950,10 @@ void free_all(NbodyHandle* h) {
     nbody64::destroy(h);
     nbody::let::destroy(h);
     nbody::tracer::release(h);
-    void* dev[] = {h->sh.pos_all, h->sh.vel, h->sh.acc, h->sh.seg_count, h->sh.escaped, h->sh.keep, h->sh.tile_state, h->sh.epoch, h->sh.inter, h->d_poison, h->d_aos,
-                   h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
+    h->release();
+    void* dev[] = {h->d_poison, h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {h->h_aos, h->h_pos, h->h_counts, h->h_counters, h->h_hot_info, h->h_poison};
+    void* host[] = {h->h_pos, h->h_counters, h->h_hot_info, h->h_poison};
     for (void* p : host) if (p) (void)hipHostFree(p);
     h->split.release();
     h->tree_bufs.release();
@@ -1051,26 +1018,27 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
     } while (0)
     CREATE_TRY(hipSetDevice(dev));
     CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    if (cfg->dtype == NBODY_F64) {   // the state of an f64 handle lives in nbody64::State
-        CREATE_TRY(hipHostMalloc(&h->h_poison, 8 * sizeof(int), hipHostMallocDefault));
-        if (cfg->method == NBODY_BARNES_HUT) {
-            int threads = cfg->host_threads > 0 ? cfg->host_threads : std::min(16, std::max(1, int(std::thread::hardware_concurrency()) - 2));
-            h->pool.reset(new nbody::WorkerPool(std::max(1, threads)));
-            CREATE_TRY(hipMalloc(&h->d_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
-            CREATE_TRY(hipMemsetAsync(h->d_counters, 0, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), h->stream));
-            CREATE_TRY(hipHostMalloc(&h->h_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), hipHostMallocDefault));
-        }
-        h->sh.n_seg = cfg->world_size; h->sh.my_seg = cfg->rank; h->sh.seg_cap = int((cfg->capacity + cfg->world_size - 1) / cfg->world_size);
-        h->seg_count_host.assign(size_t(cfg->world_size), 0);
+    CREATE_TRY(hipHostMalloc(&h->h_poison, 8 * sizeof(int), hipHostMallocDefault));
+    if (cfg->method == NBODY_BARNES_HUT) {
+        // default: the cores this process may run on, at most 16 (a GPU's share of the host; more
+        // threads than top-level subtrees only add wake-up latency)
+        int threads = cfg->host_threads > 0 ? cfg->host_threads : std::min(16, std::max(1, int(std::thread::hardware_concurrency()) - 2));
+        h->pool.reset(new nbody::WorkerPool(std::max(1, threads)));
+        CREATE_TRY(hipMalloc(&h->d_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
+        CREATE_TRY(hipMemsetAsync(h->d_counters, 0, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), h->stream));
+        CREATE_TRY(hipHostMalloc(&h->h_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), hipHostMallocDefault));
+    }
+    Shard& sh = h->sh;
+    sh.n_seg = cfg->world_size;
+    sh.my_seg = cfg->rank;
+    sh.seg_cap = int((cfg->capacity + cfg->world_size - 1) / cfg->world_size);   // bodies an index block can hold
+    if (cfg->dtype == NBODY_F64) {   // the bodies of an f64 handle live in nbody64::State (this store keeps the shape only)
+        h->seg_count_host.assign(size_t(sh.n_seg), 0);
         int rc64 = nbody64::create(h);
         if (rc64) return bail(rc64);
         *out = h;
         return NBODY_OK;
     }
-    Shard& sh = h->sh;
-    sh.n_seg = cfg->world_size;
-    sh.my_seg = cfg->rank;
-    sh.seg_cap = int((cfg->capacity + cfg->world_size - 1) / cfg->world_size);
     const bool spatial = cfg->shard_mode == NBODY_SHARD_SPATIAL;
     if (spatial) {   // a spatial handle holds its own bodies only (no gathered positions): one segment, with room for immigrants
         sh.n_seg = 1;
@@ -1079,46 +1047,16 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
         // owns more than the average; NBODY_ERR_CAPACITY beyond that)
         if (cfg->world_size > 1) sh.seg_cap = int(std::min<uint64_t>(cfg->capacity, 4 * uint64_t(sh.seg_cap) + 64));
     }
-    const size_t cap = size_t(sh.seg_cap);
-    CREATE_TRY(hipMalloc(&sh.pos_all, size_t(sh.n_seg) * cap * sizeof(float4)));
-    CREATE_TRY(hipMalloc(&sh.vel, cap * sizeof(float4)));
-    CREATE_TRY(hipMalloc(&sh.acc, cap * sizeof(float4)));
-    CREATE_TRY(hipMalloc(&sh.seg_count, sizeof(int) * sh.n_seg));
-    CREATE_TRY(hipMalloc(&sh.escaped, sizeof(int)));
-    CREATE_TRY(hipMalloc(&sh.keep, cap));
-    CREATE_TRY(hipMemsetAsync(sh.pos_all, 0, size_t(sh.n_seg) * cap * sizeof(float4), h->stream));
-    CREATE_TRY(hipMemsetAsync(sh.vel, 0, cap * sizeof(float4), h->stream));
-    CREATE_TRY(hipMemsetAsync(sh.acc, 0, cap * sizeof(float4), h->stream));
-    CREATE_TRY(hipMemsetAsync(sh.seg_count, 0, sizeof(int) * sh.n_seg, h->stream));
-    CREATE_TRY(hipMemsetAsync(sh.escaped, 0, sizeof(int), h->stream));
-    CREATE_TRY(hipMemsetAsync(sh.keep, 1, cap, h->stream));
     {
-        const size_t tiles = (cap + 1023) / 1024 + 1;
-        CREATE_TRY(hipMalloc(&sh.tile_state, tiles * sizeof(unsigned long long)));
-        CREATE_TRY(hipMemsetAsync(sh.tile_state, 0, tiles * sizeof(unsigned long long), h->stream));
-        CREATE_TRY(hipMalloc(&sh.epoch, sizeof(int)));
-        CREATE_TRY(hipMemsetAsync(sh.epoch, 0, sizeof(int), h->stream));
-        CREATE_TRY(hipMemsetAsync(sh.epoch, 1, 1, h->stream));   // epoch = 1: the zeroed status words belong to no launch
-        CREATE_TRY(hipMalloc(&sh.inter, sizeof(unsigned long long)));
-        CREATE_TRY(hipMemsetAsync(sh.inter, 0, sizeof(unsigned long long), h->stream));
-        CREATE_TRY(hipMalloc(&h->d_poison, 2 * sizeof(int)));
-        CREATE_TRY(hipMemsetAsync(h->d_poison, 0, 2 * sizeof(int), h->stream));
-        CREATE_TRY(hipHostMalloc(&h->h_poison, 8 * sizeof(int), hipHostMallocDefault));
+        int rc = h->alloc(h, h->stream);
+        if (rc) return bail(rc);
     }
-    CREATE_TRY(hipHostMalloc(&h->h_counts, sizeof(int) * sh.n_seg, hipHostMallocDefault));
-    h->seg_count_host.assign(sh.n_seg, 0);
+    CREATE_TRY(hipMalloc(&h->d_poison, 2 * sizeof(int)));
+    CREATE_TRY(hipMemsetAsync(h->d_poison, 0, 2 * sizeof(int), h->stream));
     if (cfg->method == NBODY_BARNES_HUT) {
-        // default: the cores this process may run on, at most 16 (a GPU's share of the host; more
-        // threads than top-level subtrees only add wake-up latency)
-        int threads = cfg->host_threads > 0 ? cfg->host_threads : std::min(16, std::max(1, int(std::thread::hardware_concurrency()) - 2));
-        if (threads < 1) threads = 1;
-        h->pool.reset(new nbody::WorkerPool(threads));
         h->tree.alloc = pinned_alloc;
         h->tree.release = pinned_free;
-        CREATE_TRY(hipHostMalloc(&h->h_pos, size_t(sh.n_seg) * cap * sizeof(float4), hipHostMallocDefault));
-        CREATE_TRY(hipMalloc(&h->d_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
-        CREATE_TRY(hipMemsetAsync(h->d_counters, 0, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), h->stream));
-        CREATE_TRY(hipHostMalloc(&h->h_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), hipHostMallocDefault));
+        CREATE_TRY(hipHostMalloc(&h->h_pos, size_t(sh.n_seg) * size_t(sh.seg_cap) * sizeof(float4), hipHostMallocDefault));
     }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
@@ -1174,39 +1112,23 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
     if (rc) return rc;
     rc = resolve_async(s);
     if (rc) return rc;
-    if (!s->f64) rc = sync_count(s);
+    if (!s->f64) rc = s->sync_count(s, s->stream);
     if (rc) return rc;
     NbodyHandle* h = nullptr;
     rc = create_impl(&src->cfg, &h);
     if (rc) return rc;
+    h->tune = src->tune;   // (the knobs shape the fast passes' sums: a clone continues bit for bit like its source)
     if (src->f64) {
-        h->tune = src->tune;   // (the knobs shape the fast passes' sums: a clone continues bit for bit like its source)
         rc = nbody64::clone_state(s, h);
         if (rc) { g_create_err = h->err; free_all(h); return rc; }
         *out = h;
         return NBODY_OK;
     }
-    const Shard& a = src->sh;
-    const size_t cap = size_t(a.seg_cap);
-    hipError_t e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->sh.pos_all, a.pos_all, size_t(a.n_seg) * cap * sizeof(float4), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->sh.vel, a.vel, cap * sizeof(float4), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->sh.acc, a.acc, cap * sizeof(float4), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->sh.seg_count, a.seg_count, sizeof(int) * a.n_seg, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        g_create_err = std::string("clone copy: ") + hipGetErrorString(e);
-        free_all(h);
-        return NBODY_ERR_HIP;
-    }
-    h->g = src->g; h->g_soft = src->g_soft; h->dt = src->dt; h->theta2 = src->theta2;
-    h->tune = src->tune;
+    rc = fail_if_hip(h, hipStreamSynchronize(s->stream));
+    if (!rc) rc = h->copy_from(h, h->stream, *src);
+    if (!rc) rc = fail_if_hip(h, hipStreamSynchronize(h->stream));
+    if (rc) { g_create_err = "clone copy: " + h->err; free_all(h); return rc; }
     h->multipole = src->multipole;
-    std::memcpy(h->center, src->center, sizeof(h->center));
-    h->width = src->width; h->bnd = src->bnd; h->bounds_set = src->bounds_set;
-    h->elapsed = src->elapsed;
-    h->n_local = src->n_local;
-    h->seg_count_host = src->seg_count_host;
     h->first_global = src->first_global; h->n_at_upload = src->n_at_upload;
     if (src->let) {   // spatial shards: + the bodies' ids and the ownership bounds
         rc = nbody::let::clone_state(s, h);
@@ -1222,62 +1144,30 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
 
 int nbody_upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
     if (!h || (!aos && n)) return fail(h, NBODY_ERR_INVALID, "null argument");
-    if (stride < 40 || stride % 4) return fail(h, NBODY_ERR_INVALID, "stride must be a multiple of 4 and >= 40 bytes");
-    if (n > h->cfg.capacity) return fail(h, NBODY_ERR_CAPACITY, "more bodies than NbodyConfig.capacity");
-    int rc = use_device(h);
+    int rc = check_stride(h, stride);
     if (rc) return rc;
-    if (h->f64) return (n && !aos) ? NBODY_ERR_INVALID : nbody64::upload(h, aos, n, stride);
+    if (n > h->cfg.capacity) return fail(h, NBODY_ERR_CAPACITY, "more bodies than NbodyConfig.capacity");
+    rc = use_device(h);
+    if (rc) return rc;
+    if (h->f64) return nbody64::upload(h, aos, n, stride);
     if (h->let) return nbody::let::upload(h, aos, n, stride);
     rc = resolve_async(h);
     if (rc) return rc;
-    Shard& sh = h->sh;
-    const size_t G = size_t(sh.n_seg);
-    const size_t blk = (n + G - 1) / G;  // contiguous index blocks keep the ascending-partner order
-    rc = ensure_aos(h, n);
-    if (rc) return rc;
-    const char* src = static_cast<const char*>(aos);
-    for (size_t k = 0; k < n; ++k) std::memcpy(h->h_aos + 10 * k, src + k * stride, 40);
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_aos, h->h_aos, n * 40, hipMemcpyHostToDevice, h->stream));
-    for (size_t s = 0; s < G; ++s) {
-        size_t lo = std::min(n, s * blk), hi = std::min(n, lo + blk);
-        h->seg_count_host[s] = int(hi - lo);
-        bool own = int(s) == sh.my_seg;
-        nbody::launch_aos_to_soa(h->stream, h->d_aos + 10 * lo, 10, int(hi - lo), sh.pos_all + s * size_t(sh.seg_cap),
-                                 own ? sh.vel : nullptr, own ? sh.acc : nullptr);
-        if (own) { h->first_global = lo; h->n_at_upload = hi - lo; h->n_local = hi - lo; }
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemsetAsync(sh.escaped, 0, sizeof(int), h->stream));
-    h->count_dirty = false;
-    return push_counts(h);
+    rc = h->upload_blocks(h, h->stream, aos, n, stride, &h->first_global);
+    h->n_at_upload = h->n_local;
+    return rc;
 }
 
 int nbody_download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out) {
     if (!h) return NBODY_ERR_INVALID;
-    if (stride < 40 || stride % 4) return fail(h, NBODY_ERR_INVALID, "stride must be a multiple of 4 and >= 40 bytes");
-    int rc = use_device(h);
+    int rc = check_stride(h, stride);
+    if (rc) return rc;
+    rc = use_device(h);
     if (rc) return rc;
     if (h->f64) return nbody64::download(h, aos, cap, stride, n_out);
     rc = resolve_async(h);
     if (rc) return rc;
-    rc = sync_count(h);
-    if (rc) return rc;
-    const size_t n = h->n_local;
-    if (n_out) *n_out = n;
-    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "download buffer too small");
-    if (n == 0) return NBODY_OK;
-    if (!aos) return fail(h, NBODY_ERR_INVALID, "null buffer");
-    rc = ensure_aos(h, n);
-    if (rc) return rc;
-    nbody::launch_soa_to_aos(h->stream, h->d_aos, 10, int(n), h->sh.own_pos(), h->sh.vel, h->sh.acc);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->h_aos, h->d_aos, n * 40, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    rc = comm_check(h);   // (bodies of a run whose exchange broke down are not handed out as results)
-    if (rc) return rc;
-    char* dst = static_cast<char*>(aos);
-    for (size_t k = 0; k < n; ++k) std::memcpy(dst + k * stride, h->h_aos + 10 * k, 40);
-    return NBODY_OK;
+    return h->download_own(h, h->stream, aos, cap, stride, n_out, comm_check);   // (bodies of a run whose exchange broke down are not handed out as results)
 }
 
 int nbody_count(NbodyHandle* h, size_t* n_out) {
@@ -1287,7 +1177,7 @@ int nbody_count(NbodyHandle* h, size_t* n_out) {
     if (h->f64) return nbody64::count(h, n_out);
     rc = resolve_async(h);
     if (rc) return rc;
-    rc = sync_count(h);
+    rc = h->sync_count(h, h->stream);
     if (rc) return rc;
     *n_out = h->n_local;
     return NBODY_OK;
@@ -1301,7 +1191,7 @@ int nbody_count_global(NbodyHandle* h, size_t* n_out) {
     if (h->let) return nbody::let::count_global(h, n_out);
     rc = resolve_async(h);
     if (rc) return rc;
-    rc = sync_count(h);
+    rc = h->sync_count(h, h->stream);
     if (rc) return rc;
     *n_out = total_upper(h);
     return NBODY_OK;
@@ -1316,19 +1206,7 @@ int nbody_add_point(NbodyHandle* h, const void* particle) {
     if (h->sh.n_seg != 1) return sharded_add_point(h, particle);
     rc = resolve_async(h);
     if (rc) return rc;
-    rc = sync_count(h);
-    if (rc) return rc;
-    if (h->n_local >= size_t(h->sh.seg_cap)) return fail(h, NBODY_ERR_CAPACITY, "capacity exhausted");
-    const float* p = static_cast<const float*>(particle);
-    float4 rec[3] = {make_float4(p[0], p[1], p[2], p[9]), make_float4(p[3], p[4], p[5], 0.f), make_float4(p[6], p[7], p[8], 0.f)};
-    const size_t k = h->n_local;
-    HIP_TRY(h, hipMemcpyAsync(h->sh.pos_all + k, &rec[0], sizeof(float4), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->sh.vel + k, &rec[1], sizeof(float4), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->sh.acc + k, &rec[2], sizeof(float4), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->n_local = k + 1;
-    h->seg_count_host[0] = int(h->n_local);
-    return push_counts(h);
+    return h->push_one(h, h->stream, particle);
 }
 
 int nbody_remove_point(NbodyHandle* h, size_t index) {
@@ -1340,58 +1218,36 @@ int nbody_remove_point(NbodyHandle* h, size_t index) {
     if (h->sh.n_seg != 1) return sharded_remove_point(h, index);
     rc = resolve_async(h);
     if (rc) return rc;
-    rc = sync_count(h);
-    if (rc) return rc;
-    if (index >= h->n_local) return fail(h, NBODY_ERR_INVALID, "swap_remove index out of range");  // Vec::swap_remove panics
-    const size_t last = h->n_local - 1;
-    if (index != last) {
-        HIP_TRY(h, hipMemcpyAsync(h->sh.pos_all + index, h->sh.pos_all + last, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->sh.vel + index, h->sh.vel + last, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->sh.acc + index, h->sh.acc + last, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-    }
-    h->n_local = last;
-    h->seg_count_host[0] = int(last);
-    return push_counts(h);
-}
-
-int nbody_set_settings(NbodyHandle* h, float g, float g_soft, float dt, float theta2) {
-    if (!h) return NBODY_ERR_INVALID;
-    if (h->f64) return nbody64::set_settings(h, double(g), double(g_soft), double(dt), double(theta2));
-    h->g = g; h->g_soft = g_soft; h->dt = dt; h->theta2 = theta2;
-    return NBODY_OK;
-}
-
-int nbody_get_settings(const NbodyHandle* h, float* g, float* g_soft, float* dt, float* theta2) {
-    if (!h) return NBODY_ERR_INVALID;
-    if (h->f64) {
-        double a, b, c, d;
-        nbody64::get_settings(h, &a, &b, &c, &d);
-        if (g) *g = float(a);
-        if (g_soft) *g_soft = float(b);
-        if (dt) *dt = float(c);
-        if (theta2) *theta2 = float(d);
-        return NBODY_OK;
-    }
-    if (g) *g = h->g;
-    if (g_soft) *g_soft = h->g_soft;
-    if (dt) *dt = h->dt;
-    if (theta2) *theta2 = h->theta2;
-    return NBODY_OK;
+    return h->swap_remove_one(h, h->stream, index);
 }
 
 int nbody_set_settings_f64(NbodyHandle* h, double g, double g_soft, double dt, double theta2) {
     if (!h) return NBODY_ERR_INVALID;
     if (h->f64) return nbody64::set_settings(h, g, g_soft, dt, theta2);
-    return nbody_set_settings(h, float(g), float(g_soft), float(dt), float(theta2));
+    h->set_settings(float(g), float(g_soft), float(dt), float(theta2));
+    return NBODY_OK;
+}
+
+int nbody_set_settings(NbodyHandle* h, float g, float g_soft, float dt, float theta2) {
+    return nbody_set_settings_f64(h, double(g), double(g_soft), double(dt), double(theta2));   // (f32 -> f64 -> f32 is exact)
 }
 
 int nbody_get_settings_f64(const NbodyHandle* h, double* g, double* g_soft, double* dt, double* theta2) {
     if (!h) return NBODY_ERR_INVALID;
     if (h->f64) return nbody64::get_settings(h, g, g_soft, dt, theta2);
-    if (g) *g = double(h->g);
-    if (g_soft) *g_soft = double(h->g_soft);
-    if (dt) *dt = double(h->dt);
-    if (theta2) *theta2 = double(h->theta2);
+    h->get_settings(g, g_soft, dt, theta2);
+    return NBODY_OK;
+}
+
+int nbody_get_settings(const NbodyHandle* h, float* g, float* g_soft, float* dt, float* theta2) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (!h->f64) { h->get_settings(g, g_soft, dt, theta2); return NBODY_OK; }
+    double v[4];
+    nbody64::get_settings(h, &v[0], &v[1], &v[2], &v[3]);
+    if (g) *g = float(v[0]);
+    if (g_soft) *g_soft = float(v[1]);
+    if (dt) *dt = float(v[2]);
+    if (theta2) *theta2 = float(v[3]);
     return NBODY_OK;
 }
 
@@ -1399,20 +1255,14 @@ int nbody_set_bounds_f64(NbodyHandle* h, const double center[3], double width) {
     if (!h || !center) return NBODY_ERR_INVALID;
     if (h->f64) return nbody64::set_bounds(h, center, width);
     const float c[3] = {float(center[0]), float(center[1]), float(center[2])};
-    return nbody_set_bounds(h, c, float(width));
+    h->set_bounds(c, float(width));
+    return NBODY_OK;
 }
 
 int nbody_set_bounds(NbodyHandle* h, const float center[3], float width) {
     if (!h || !center) return NBODY_ERR_INVALID;
-    if (h->f64) {
-        const double c[3] = {double(center[0]), double(center[1]), double(center[2])};
-        return nbody64::set_bounds(h, c, double(width));
-    }
-    std::memcpy(h->center, center, sizeof(h->center));
-    h->width = width;
-    compute_bounds(h);
-    h->bounds_set = true;
-    return NBODY_OK;
+    const double c[3] = {double(center[0]), double(center[1]), double(center[2])};
+    return nbody_set_bounds_f64(h, c, double(width));   // (f32 -> f64 -> f32 is exact)
 }
 
 int nbody_init(NbodyHandle* h) {
@@ -1620,7 +1470,7 @@ int nbody_energy(NbodyHandle* h, double* kinetic, double* potential) {
         return fail(h, NBODY_ERR_INVALID, "nbody_energy is not supported on NBODY_SHARD_SPATIAL handles of a world of more than one rank");
     rc = resolve_async(h);
     if (rc) return rc;
-    rc = sync_count(h);
+    rc = h->sync_count(h, h->stream);
     if (rc) return rc;
     const size_t n = h->n_local;
     const size_t blocks = (n + 255) / 256;

@@ -17,22 +17,8 @@
 
 namespace nbody64 {
 
-struct State {
-    Dev d;
-    double g = 1.0, g_soft = 0.0, dt = 1e-3, theta2 = 0.5;   // shared.rs:69-78
-    double center[3] = {0.0, 0.0, 0.0};
-    double width = 0.0;
-    Bounds64 bnd{};
-    bool bounds_set = false;
-    double elapsed = 0.0;
-    size_t n_local = 0;        // host view of the body count (an upper bound while count_dirty)
-    bool count_dirty = false;
-    int* h_count = nullptr;    // pinned [n_seg + 1]: the blocks' live counts
-    std::vector<int> count_upper;   // host bound of every block's live count (counts only shrink between uploads)
+struct State : BodyStore<double> {   // (the bodies, their host view and the settings: nbody_handle.h)
     std::vector<int> own_order;
-    double* d_aos = nullptr;   // staging for PointParticle<f64,3> records
-    double* h_aos = nullptr;   // pinned
-    size_t aos_cap = 0;
     // Barnes-Hut
     nbody::HostTreeT<double> tree;
     nbody::BuildScratchT<double> scratch;
@@ -84,40 +70,11 @@ struct State {
 
 namespace {
 
-int ensure_aos(NbodyHandle* h, State& s, size_t records) {
-    if (records <= s.aos_cap) return NBODY_OK;
-    if (s.d_aos) (void)hipFree(s.d_aos);
-    if (s.h_aos) (void)hipHostFree(s.h_aos);
-    s.d_aos = nullptr; s.h_aos = nullptr; s.aos_cap = 0;
-    HIP_TRY(h, hipMalloc(&s.d_aos, records * 10 * sizeof(double)));
-    HIP_TRY(h, hipHostMalloc(&s.h_aos, records * 10 * sizeof(double), hipHostMallocDefault));
-    s.aos_cap = records;
-    return NBODY_OK;
-}
-
-int sync_count(NbodyHandle* h, State& s) {
-    if (!s.count_dirty) return NBODY_OK;
-    HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d.seg_count, sizeof(int) * s.d.n_seg, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    for (int g = 0; g < s.d.n_seg; ++g) s.count_upper[size_t(g)] = s.h_count[g];
-    s.n_local = size_t(s.h_count[s.d.my_seg]);
-    s.count_dirty = false;
-    return NBODY_OK;
-}
-
-int push_count(NbodyHandle* h, State& s) {
-    s.h_count[s.d.n_seg] = int(s.n_local);
-    s.count_upper[size_t(s.d.my_seg)] = int(s.n_local);
-    HIP_TRY(h, hipMemcpyAsync(s.d.count, s.h_count + s.d.n_seg, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return NBODY_OK;
-}
-
 int ensure_bf_plan(NbodyHandle* h, State& s, size_t n_remote) {
     const nbody::Tuning& t = nbody::tuning();
     const long long key[6] = {(long long)s.n_local, (long long)n_remote, t.bf64_min_bodies, t.bf64_ipt, t.bf64_rot, t.bf64_waves};
     if (std::equal(key, key + 6, s.bf_plan_key)) return NBODY_OK;
-    const Bf64Plan plan = make_bf64_plan(int(s.n_local), int(std::min<size_t>(n_remote, 0x7fffffff)), s.d.n_seg);
+    const Bf64Plan plan = make_bf64_plan(int(s.n_local), int(std::min<size_t>(n_remote, 0x7fffffff)), s.sh.n_seg);
     const size_t need = size_t(plan.n_planes) * plan.n_pad;
     if (need > s.planes_cap) {
         if (s.d_planes) (void)hipFree(s.d_planes);
@@ -138,8 +95,8 @@ int ensure_bf_plan(NbodyHandle* h, State& s, size_t n_remote) {
 int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
     if (s.n_local == 0) return NBODY_OK;
     uint64_t tot = 0;
-    for (int c : s.count_upper) tot += uint64_t(c);
-    const size_t n_remote = size_t(tot) - std::min<size_t>(size_t(tot), size_t(s.count_upper[size_t(s.d.my_seg)]));
+    for (int c : s.seg_count_host) tot += uint64_t(c);
+    const size_t n_remote = size_t(tot) - std::min<size_t>(size_t(tot), size_t(s.seg_count_host[size_t(s.sh.my_seg)]));
     int rc = ensure_bf_plan(h, s, n_remote);
     if (rc) return rc;
     const Bf64Plan& p = s.bf_plan;
@@ -147,18 +104,18 @@ int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
     if (p.sym && p.sym_sets > 0) {
         {
             ForceTimer t(h);
-            launch_bf64_sym(h->stream, s.d, p, s.d_planes, eps2);
+            launch_bf64_sym(h->stream, s.sh, p, s.d_planes, eps2);
         }
         timed = 2 * s.bf_sym_pairs;
-        launch_bf64_own(h->stream, s.d, p, s.d_planes, eps2);
+        launch_bf64_own(h->stream, s.sh, p, s.d_planes, eps2);
     } else {   // (with one or two resident sets the left-over pairs are all of them)
         ForceTimer t(h);
-        launch_bf64_own(h->stream, s.d, p, s.d_planes, eps2);
+        launch_bf64_own(h->stream, s.sh, p, s.d_planes, eps2);
         timed = uint64_t(s.n_local) * uint64_t(s.n_local - 1);
     }
     const bool timed_this = h->timed_this;
-    launch_bf64_remote(h->stream, s.d, p, s.d_planes, eps2);
-    launch_bf64_reduce(h->stream, s.d, p, s.d_planes, int(s.n_local), s.g, s.kick_dt);
+    launch_bf64_remote(h->stream, s.sh, p, s.d_planes, eps2);
+    launch_bf64_reduce(h->stream, s.sh, p, s.d_planes, int(s.n_local), s.g, s.kick_dt);
     if (s.kick_dt) s.kicked = 1;
     HIP_TRY(h, hipGetLastError());
     if (timed_this) h->stats.force_kernel_interactions += timed;
@@ -168,7 +125,7 @@ int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
 // ---- the fourth-order Hermite step (kernels_hermite.hip)
 int ensure_hermite(NbodyHandle* h, State& s) {
     if (s.hm.jerk) return NBODY_OK;
-    const size_t cap = size_t(s.d.cap);
+    const size_t cap = size_t(s.sh.seg_cap);
     double4** arr[] = {&s.hm.jerk, &s.hm.xp, &s.hm.vp, &s.hm.a1, &s.hm.j1};
     for (double4** a : arr) {
         HIP_TRY(h, hipMalloc(a, cap * sizeof(double4)));
@@ -206,10 +163,10 @@ int hm_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, double
     if (h->cfg.math_mode != NBODY_MATH_FAST) {
         {
             ForceTimer t(h);
-            launch_hm_strict(h->stream, s.d, x, v, c ? s.hm.a1 : out_a, c ? s.hm.j1 : out_j, int(s.n_local), s.g, eps2);
+            launch_hm_strict(h->stream, s.sh, x, v, c ? s.hm.a1 : out_a, c ? s.hm.j1 : out_j, int(s.n_local), s.g, eps2);
         }
         if (h->timed_this) h->stats.force_kernel_interactions += all;
-        if (c) launch_hm_correct(h->stream, s.d, s.hm, int(s.n_local), *c, s.bnd);
+        if (c) launch_hm_correct(h->stream, s.sh, s.hm, int(s.n_local), *c, s.bnd);
         HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
@@ -220,23 +177,23 @@ int hm_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, double
     if (p.sym && p.sym_sets > 0) {
         {
             ForceTimer t(h);
-            launch_hm_sym(h->stream, s.d, p, x, v, s.d_hm_planes, eps2);
+            launch_hm_sym(h->stream, s.sh, p, x, v, s.d_hm_planes, eps2);
         }
         timed = 2 * s.hm_sym_pairs;
-        launch_hm_own(h->stream, s.d, p, x, v, s.d_hm_planes, eps2);
+        launch_hm_own(h->stream, s.sh, p, x, v, s.d_hm_planes, eps2);
     } else {   // (with one or two resident sets the left-over pairs are all of them)
         ForceTimer t(h);
-        launch_hm_own(h->stream, s.d, p, x, v, s.d_hm_planes, eps2);
+        launch_hm_own(h->stream, s.sh, p, x, v, s.d_hm_planes, eps2);
         timed = all;
     }
     if (h->timed_this) h->stats.force_kernel_interactions += timed;
-    launch_hm_reduce(h->stream, s.d, s.hm, p, s.d_hm_planes, int(s.n_local), s.g, out_a, out_j, c, s.bnd);
+    launch_hm_reduce(h->stream, s.sh, s.hm, p, s.d_hm_planes, int(s.n_local), s.g, out_a, out_j, c, s.bnd);
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
 }
 
 int hm_refresh(NbodyHandle* h, State& s) {   // the held (a0, j0) at the current (x, v)
-    int rc = hm_eval(h, s, s.d.pos, s.d.vel, s.d.acc, s.hm.jerk, nullptr);
+    int rc = hm_eval(h, s, s.sh.own_pos(), s.sh.vel, s.sh.acc, s.hm.jerk, nullptr);
     if (!rc) s.hm_valid = true;
     s.lv_valid = false;   // (levels belong to the derivatives they were drawn from)
     return rc;
@@ -245,7 +202,7 @@ int hm_refresh(NbodyHandle* h, State& s) {   // the held (a0, j0) at the current
 // ---- block individual time steps (kernels_hermite.hip, "block individual time steps")
 int ensure_block(NbodyHandle* h, State& s) {
     BlockDev& b = s.blk;
-    const size_t cap = size_t(s.d.cap);
+    const size_t cap = size_t(s.sh.seg_cap);
     if (!b.level) {
         int** arr[] = {&b.level, &b.tau, &b.list};
         for (int** a : arr) {
@@ -258,7 +215,7 @@ int ensure_block(NbodyHandle* h, State& s) {
         b.sched = b.smin + 2;
         HIP_TRY(h, hipHostMalloc(&s.h_sched, 2 * sizeof(int), hipHostMallocDefault));
     }
-    const size_t rows = hm_act_plane_rows(s.d.cap);   // (follows the bf64_waves knob)
+    const size_t rows = hm_act_plane_rows(s.sh.seg_cap);   // (follows the bf64_waves knob)
     if (rows > b.plane_rows) {
         if (b.planes) (void)hipFree(b.planes);
         b.planes = nullptr; b.plane_rows = 0;
@@ -274,7 +231,7 @@ bool same_bits(double a, double b) { return std::memcmp(&a, &b, sizeof(double)) 
 int assign_levels(NbodyHandle* h, State& s, double abs_dt) {
     int rc = ensure_block(h, s);
     if (rc) return rc;
-    launch_hmb_start_levels(h->stream, s.d, s.hm, s.blk, int(s.n_local), s.blk_eta, abs_dt, s.blk_L);
+    launch_hmb_start_levels(h->stream, s.sh, s.hm, s.blk, int(s.n_local), s.blk_eta, abs_dt, s.blk_L);
     HIP_TRY(h, hipGetLastError());
     s.lv_valid = true;
     s.lv_dt = abs_dt;
@@ -289,9 +246,9 @@ int hm_act_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, in
     if (h->cfg.math_mode == NBODY_MATH_FAST) {
         *plan = make_hm_act_plan(n_act, int(s.n_local));
         if (size_t(plan->K) * size_t(plan->groups) * 64 > s.blk.plane_rows) return fail(h, NBODY_ERR_CAPACITY, "block steps: the active-set planes are too small for this launch");
-        launch_hm_act(h->stream, s.d, s.blk, *plan, x, v, eps2);
+        launch_hm_act(h->stream, s.sh, s.blk, *plan, x, v, eps2);
     } else {
-        launch_hm_act_strict(h->stream, s.d, s.hm, s.blk, n_act, x, v, s.g, eps2);
+        launch_hm_act_strict(h->stream, s.sh, s.hm, s.blk, n_act, x, v, s.g, eps2);
     }
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
@@ -301,7 +258,7 @@ int hm_act_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, in
 // The host reads {tau*, due bodies} back once per block step and sizes the force launch from them.
 int hm_block_step(NbodyHandle* h, State& s, double dt) {
     if (!s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
-    int rc = sync_count(h, s);   // the exact body count: nothing leaves inside a macro step
+    int rc = s.sync_count(h, h->stream);   // the exact body count: nothing leaves inside a macro step
     if (!rc && !s.hm_valid) rc = hm_refresh(h, s);
     if (!rc) rc = ensure_block(h, s);
     if (rc) return rc;
@@ -318,7 +275,7 @@ int hm_block_step(NbodyHandle* h, State& s, double dt) {
         HIP_TRY(h, hipMemsetAsync(s.blk.tau, 0, size_t(n) * sizeof(int), h->stream));
         HIP_TRY(h, hipMemsetAsync(s.blk.smin, 0x7f, 2 * sizeof(int), h->stream));
         for (int k = 0;; ++k) {
-            launch_hmb_schedule(h->stream, s.d, s.hm, s.blk, n, T, tick, k & 1);
+            launch_hmb_schedule(h->stream, s.sh, s.hm, s.blk, n, T, tick, k & 1);
             HIP_TRY(h, hipGetLastError());
             HIP_TRY(h, hipMemcpyAsync(s.h_sched, s.blk.sched, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -332,13 +289,13 @@ int hm_block_step(NbodyHandle* h, State& s, double dt) {
             }
             if (rc) return rc;
             if (h->timed_this) h->stats.force_kernel_interactions += uint64_t(n_act) * uint64_t(n - 1);
-            launch_hmb_finish(h->stream, s.d, s.hm, s.blk, fast ? &plan : nullptr, n_act, s.g, T, L, tick, abs_dt, s.blk_eta, s.bnd);
+            launch_hmb_finish(h->stream, s.sh, s.hm, s.blk, fast ? &plan : nullptr, n_act, s.g, T, L, tick, abs_dt, s.blk_eta, s.bnd);
             HIP_TRY(h, hipGetLastError());
             s.blk_steps += 1;
             s.blk_updates += uint64_t(n_act);
             if (tstar == T) break;   // commensurate steps: every body is due at T
         }
-        launch_hm_compact(h->stream, s.d, s.hm, n, s.blk.level);   // retain, on the corrected positions; the levels travel along
+        launch_hm_compact(h->stream, s.sh, s.hm, n, s.blk.level);   // retain, on the corrected positions; the levels travel along
         s.count_dirty = true;
         HIP_TRY(h, hipGetLastError());
     }
@@ -353,10 +310,10 @@ int hm_step(NbodyHandle* h, State& s, double dt) {
     int rc = s.hm_valid ? NBODY_OK : hm_refresh(h, s);
     if (rc) return rc;
     const HermiteCoef c = hermite_coef(dt);
-    launch_hm_predict(h->stream, s.d, s.hm, int(s.n_local), c);
+    launch_hm_predict(h->stream, s.sh, s.hm, int(s.n_local), c);
     rc = hm_eval(h, s, s.hm.xp, s.hm.vp, nullptr, nullptr, &c);   // + corrector
     if (rc) return rc;
-    launch_hm_compact(h->stream, s.d, s.hm, int(s.n_local));     // retain, on the corrected positions
+    launch_hm_compact(h->stream, s.sh, s.hm, int(s.n_local));     // retain, on the corrected positions
     s.count_dirty = true;
     s.lv_valid = false;   // (a shared step does not carry block-step levels)
     HIP_TRY(h, hipGetLastError());
@@ -370,19 +327,19 @@ int bf_forces(NbodyHandle* h, State& s) {
     if (h->cfg.math_mode == NBODY_MATH_FAST) return bf_forces_fast(h, s, eps2);
     {
         ForceTimer t(h);
-        launch_bf_strict(h->stream, s.d, int(s.n_local), s.g, eps2);
+        launch_bf_strict(h->stream, s.sh, int(s.n_local), s.g, eps2);
     }
     HIP_TRY(h, hipGetLastError());
     if (h->timed_this && s.n_local > 0) {
         uint64_t tot = 0;
-        for (int c : s.count_upper) tot += uint64_t(c);
+        for (int c : s.seg_count_host) tot += uint64_t(c);
         h->stats.force_kernel_interactions += uint64_t(s.n_local) * (tot - 1);
     }
     return NBODY_OK;
 }
 
 int ensure_stack(NbodyHandle* h, State& s, int levels) {   // the nested sums' stack: one entry per open cell on the lane's path
-    const size_t lanes = (size_t(s.d.cap) + 255) / 256 * 256;
+    const size_t lanes = (size_t(s.sh.seg_cap) + 255) / 256 * 256;
     if (lanes > s.stack_lanes || levels > s.stack_levels) {
         if (s.d_stack) (void)hipFree(s.d_stack);
         s.d_stack = nullptr; s.stack_lanes = 0; s.stack_levels = 0;
@@ -402,11 +359,11 @@ int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const 
     if ((n_order == 0 && !field) || n_nodes <= 0) return NBODY_OK;
     const nbody::WalkPlan plan = walk_split_plan(size_t(n_order), true, float(s.theta2), size_t(n_nodes));   // (bodies per lane x segments: kernels.h)
     const int K = field ? field_split_plan(h->field.n_points, size_t(n_nodes)) : k_done > 0 ? k_done : plan.segments;
-    int rc = s.split.ensure(h, K, size_t(s.d.cap));
+    int rc = s.split.ensure(h, K, size_t(s.sh.seg_cap));
     if (!rc && !k_done && host_nodes) rc = s.split.list_on_host(h, h->stream, host_nodes, n_nodes, K);
     if (rc) return rc;
     if (!k_done && !host_nodes) s.split.list_on_device(h->stream, s.tree_work, n_tree, n_nodes, K);
-    const WalkSplit64 sp = walk_split_view(s.split, K, size_t(s.d.cap));
+    const WalkSplit64 sp = walk_split_view(s.split, K, size_t(s.sh.seg_cap));
     if (field) {   // the caller walks this tree for its probes, batch by batch (nbody_field.cpp)
         FieldBufs& f = h->field;
         f.nodes = nodes; f.n_nodes = n_nodes; f.K = K;
@@ -417,14 +374,14 @@ int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const 
         const size_t stride = (size_t(n_order) + 63) / 64 * 64;
         rc = nbody::pot::ensure_planes(h, size_t(K) * stride);
         if (rc) return rc;
-        launch_bh_pot_walk(h->stream, s.d.pos, nodes, order, n_order, s.g_soft * s.g_soft, s.theta2, sp, h->pot.d_planes, stride, h->pot.d_counts);
+        launch_bh_pot_walk(h->stream, s.sh.own_pos(), nodes, order, n_order, s.g_soft * s.g_soft, s.theta2, sp, h->pot.d_planes, stride, h->pot.d_counts);
         nbody::launch_pot_reduce(h->stream, h->pot.d_planes, K, stride, order, n_order, h->pot.d_sum);
         HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
     {
         ForceTimer t(h);
-        launch_bh_walk_fast(h->stream, s.d, nodes, n_nodes, order, n_order, s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
+        launch_bh_walk_fast(h->stream, s.sh, nodes, n_nodes, order, n_order, s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
                             h->cfg.leaf_mode == NBODY_LEAF_DIRECT ? 1 : 0, sp, std::min(3, plan.bodies_per_lane), s.kick_dt, &s.kicked);   // (64-byte records, doubles in registers: beyond three per lane the f64 walk loses again -- tools/f64_walk_probe.py)
     }
     HIP_TRY(h, hipGetLastError());
@@ -437,11 +394,11 @@ int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const 
 int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     *fell_back = false;
     auto t0 = clk::now();
-    const int G = s.d.n_seg;
+    const int G = s.sh.n_seg;
     const bool sharded = G > 1;   // every rank builds the world's tree from the gathered positions (fast math; kernels_tree.hip k_tree_cat64)
-    const size_t cap = size_t(s.d.cap) * size_t(G);
+    const size_t cap = size_t(s.sh.seg_cap) * size_t(G);
     size_t tot_upper = 0;
-    for (int g = 0; g < G; ++g) tot_upper += size_t(s.count_upper[size_t(g)]);
+    for (int g = 0; g < G; ++g) tot_upper += size_t(s.seg_count_host[size_t(g)]);
     if (!sharded) tot_upper = s.n_local;
     TreeBuildBufs& tb = s.tree_bufs;
     int rc = tb.ensure(h, cap, sharded ? nbody::tree_cat_bytes64(cap) : 0);
@@ -452,13 +409,13 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
         HIP_TRY(h, hipMalloc(&s.d_order, cap * sizeof(int)));
         s.order_cap = cap;
     }
-    const double4* tree_pos = s.d.pos;
-    const int* tree_count = s.d.count;
+    const double4* tree_pos = s.sh.own_pos();
+    const int* tree_count = s.sh.own_count();
     nbody::TreeCat cat;
     if (sharded) {
         double4* pos_cat = nullptr;
         cat = nbody::tree_cat_layout64(tb.cat, cap, &pos_cat);
-        nbody::launch_tree_cat64(h->stream, s.d.pos_all, s.d.seg_count, G, s.d.cap, s.d.my_seg, pos_cat, cat.info);
+        nbody::launch_tree_cat64(h->stream, s.sh.pos_all, s.sh.seg_count, G, s.sh.seg_cap, s.sh.my_seg, pos_cat, cat.info);
         tree_pos = pos_cat;
         tree_count = cat.info;
     }
@@ -467,7 +424,7 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     int k_pre = 0;
     if (!sharded && h->cfg.math_mode == NBODY_MATH_FAST && tot_upper > 0 && h->pot.walking != kWalkField) {   // (a field call draws K from its probes)
         k_pre = walk_split_plan(tot_upper, true, float(s.theta2), tot_upper).segments;   // (a tree has at least as many nodes as bodies)
-        rc = s.split.ensure(h, k_pre, size_t(s.d.cap));
+        rc = s.split.ensure(h, k_pre, size_t(s.sh.seg_cap));
         if (rc) return rc;
         req = s.split.request(k_pre, tb.d_info, nullptr);
     }
@@ -483,7 +440,7 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
                                            int(std::min<size_t>(s.node_cap, 0x7fffffff)), s.d_order, tb.d_info, &s.tree_work, k_pre ? &req : nullptr) != 0)
             return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
         HIP_TRY(h, hipMemcpyAsync(tb.h_info, tb.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (sharded) HIP_TRY(h, hipMemcpyAsync(s.h_count, s.d.seg_count, sizeof(int) * size_t(G), hipMemcpyDeviceToHost, h->stream));
+        if (sharded) HIP_TRY(h, hipMemcpyAsync(s.h_counts, s.sh.seg_count, sizeof(int) * size_t(G), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         if (tb.h_info[1] & 5) { *fell_back = true; return NBODY_OK; }
         if (!(tb.h_info[1] & 2)) break;
@@ -493,9 +450,9 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     }
     if (sharded) {   // the live counts of every block, and the own bodies' places in the tree order
         size_t total = 0;
-        for (int g = 0; g < G; ++g) { s.count_upper[size_t(g)] = s.h_count[g]; total += size_t(s.h_count[g]); }
+        for (int g = 0; g < G; ++g) { s.seg_count_host[size_t(g)] = s.h_counts[g]; total += size_t(s.h_counts[g]); }
         s.dev_nodes = size_t(tb.h_info[0]);
-        s.n_local = size_t(s.h_count[s.d.my_seg]);
+        s.n_local = size_t(s.h_counts[s.sh.my_seg]);
         s.count_dirty = false;
         s.tree_on_device = true;
         if (nbody::launch_tree_own_order(h->stream, s.d_order, cat, int(total), tb.ws, nbody::tree_build_tmp_bytes(cap)) != 0)
@@ -515,7 +472,7 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     if (!direct) { rc = ensure_stack(h, s, 45); if (rc) return rc; }   // (the device build goes to 42 levels)
     {
         ForceTimer t(h);
-        launch_bh_walk(h->stream, s.d, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
+        launch_bh_walk(h->stream, s.sh, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
                        direct ? 1 : 0, s.d_stack, s.stack_lanes);
     }
     HIP_TRY(h, hipGetLastError());
@@ -524,15 +481,15 @@ int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
 
 // BarnesHutSimulation::update_forces (barnes_hut.rs:250-263): rebuild the tree (host, f64), one walk per body
 int bh_forces(NbodyHandle* h, State& s) {
-    if (h->cfg.tree_build == NBODY_TREE_DEVICE && (s.d.n_seg == 1 || h->cfg.math_mode == NBODY_MATH_FAST)) {   // (a sharded world: fast math only, create says so)
+    if (h->cfg.tree_build == NBODY_TREE_DEVICE && (s.sh.n_seg == 1 || h->cfg.math_mode == NBODY_MATH_FAST)) {   // (a sharded world: fast math only, create says so)
         bool fell_back = false;
         int rc = bh_forces_device(h, s, &fell_back);
         if (rc || !fell_back) return rc;
     }
     s.tree_on_device = false;
     static_assert(sizeof(nbody::NodeRecT<double>) == sizeof(Node64), "host and device node records must agree");
-    HostTreePass<double, Node64> pass{reinterpret_cast<const double*>(s.d.pos_all), s.d.seg_count, s.d.n_seg, s.d.cap, s.d.my_seg, s.h_pos,
-                                      s.h_count, s.count_upper, s.n_local, s.count_dirty, s.center, s.width, s.tree, s.scratch, s.own_order,
+    HostTreePass<double, Node64> pass{reinterpret_cast<const double*>(s.sh.pos_all), s.sh.seg_count, s.sh.n_seg, s.sh.seg_cap, s.sh.my_seg, s.h_pos,
+                                      s.h_counts, s.seg_count_host, s.n_local, s.count_dirty, s.center, s.width, s.tree, s.scratch, s.own_order,
                                       s.d_nodes, s.node_cap, s.d_order, s.order_cap};
     int rc = pass.run(h);
     if (rc) return rc;
@@ -543,7 +500,7 @@ int bh_forces(NbodyHandle* h, State& s) {
     if (!direct) { rc = ensure_stack(h, s, s.tree.max_depth + 2); if (rc) return rc; }   // the tree's depth
     {
         ForceTimer t(h);
-        launch_bh_walk(h->stream, s.d, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.g, s.g_soft * s.g_soft, s.theta2,
+        launch_bh_walk(h->stream, s.sh, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.g, s.g_soft * s.g_soft, s.theta2,
                        h->d_counters, direct ? 1 : 0, s.d_stack, s.stack_lanes);
     }
     HIP_TRY(h, hipGetLastError());
@@ -554,11 +511,11 @@ int forces(NbodyHandle* h, State& s) { return h->cfg.method == NBODY_BARNES_HUT 
 
 // index-block shards: the once-per-step exchange, in place, on the handle's stream
 int exchange(NbodyHandle* h, State& s) {
-    if (s.d.n_seg == 1 && !h->comm_ready) return NBODY_OK;
+    if (s.sh.n_seg == 1 && !h->comm_ready) return NBODY_OK;
     if (!h->comm_ready) return fail(h, NBODY_ERR_COMM, "world_size > 1 but nbody_comm_init has not been called");
     int rc = h->tp->group_begin();
-    if (!rc) rc = h->tp->all_gather(s.d.pos_all, size_t(s.d.cap) * sizeof(double4), h->stream);
-    if (!rc) rc = h->tp->all_gather(s.d.seg_count, sizeof(int), h->stream);
+    if (!rc) rc = h->tp->all_gather(s.sh.pos_all, size_t(s.sh.seg_cap) * sizeof(double4), h->stream);
+    if (!rc) rc = h->tp->all_gather(s.sh.seg_count, sizeof(int), h->stream);
     if (!rc) rc = h->tp->group_end();
     if (rc) return fail(h, rc, "f64 exchange: " + h->tp->error());
     return NBODY_OK;
@@ -567,8 +524,8 @@ int exchange(NbodyHandle* h, State& s) {
 int step_impl(NbodyHandle* h, State& s, double dt) {
     if (s.integrator == NBODY_INTEGRATOR_HERMITE4) return hm_step(h, s, dt);
     if (!s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
-    launch_drift_half(h->stream, s.d, int(s.n_local), dt, s.bnd);   // integrate_pre_force
-    launch_compact(h->stream, s.d, int(s.n_local));                 // retain
+    launch_drift_half(h->stream, s.sh, int(s.n_local), dt, s.bnd);   // integrate_pre_force
+    launch_compact(h->stream, s.sh, int(s.n_local));                 // retain
     s.count_dirty = true;
     HIP_TRY(h, hipGetLastError());
     int rc = exchange(h, s);                                        // sharded: every block's positions and live count
@@ -577,7 +534,7 @@ int step_impl(NbodyHandle* h, State& s, double dt) {
     rc = forces(h, s);                                              // update_forces
     s.kick_dt = nullptr;
     if (rc) return rc;
-    if (!s.kicked) launch_kick_drift(h->stream, s.d, int(s.n_local), dt);   // integrate_after_force
+    if (!s.kicked) launch_kick_drift(h->stream, s.sh, int(s.n_local), dt);   // integrate_after_force
     HIP_TRY(h, hipGetLastError());
     s.elapsed += dt;                                                // elapsed += dt
     h->stats.steps += 1;
@@ -590,39 +547,13 @@ int create(NbodyHandle* h) {
     State* sp = new State();
     h->f64 = sp;
     State& s = *sp;
-    const int G = h->cfg.world_size;
-    const size_t cap = (size_t(h->cfg.capacity) + size_t(G) - 1) / size_t(G);   // bodies a block can hold
-    s.d.cap = int(cap);
-    s.d.n_seg = G;
-    s.d.my_seg = h->cfg.rank;
-    s.count_upper.assign(size_t(G), 0);
-    HIP_TRY(h, hipMalloc(&s.d.pos_all, size_t(G) * cap * sizeof(double4)));
-    s.d.pos = s.d.pos_all + size_t(s.d.my_seg) * cap;
-    HIP_TRY(h, hipMalloc(&s.d.vel, cap * sizeof(double4)));
-    HIP_TRY(h, hipMalloc(&s.d.acc, cap * sizeof(double4)));
-    HIP_TRY(h, hipMalloc(&s.d.seg_count, sizeof(int) * G));
-    s.d.count = s.d.seg_count + s.d.my_seg;
-    HIP_TRY(h, hipMalloc(&s.d.escaped, sizeof(int)));
-    HIP_TRY(h, hipMalloc(&s.d.keep, cap));
-    const size_t tiles = (cap + 1023) / 1024 + 1;
-    HIP_TRY(h, hipMalloc(&s.d.tile_state, tiles * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMalloc(&s.d.epoch, sizeof(int)));
-    HIP_TRY(h, hipMalloc(&s.d.inter, sizeof(unsigned long long)));
-    HIP_TRY(h, hipMemsetAsync(s.d.pos_all, 0, size_t(G) * cap * sizeof(double4), h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.vel, 0, cap * sizeof(double4), h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.acc, 0, cap * sizeof(double4), h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.seg_count, 0, sizeof(int) * G, h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.escaped, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.keep, 1, cap, h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.tile_state, 0, tiles * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.epoch, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(s.d.epoch, 1, 1, h->stream));   // epoch = 1
-    HIP_TRY(h, hipMemsetAsync(s.d.inter, 0, sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipHostMalloc(&s.h_count, (size_t(G) + 1) * sizeof(int), hipHostMallocDefault));
+    s.sh.n_seg = h->sh.n_seg; s.sh.my_seg = h->sh.my_seg; s.sh.seg_cap = h->sh.seg_cap;   // (index blocks: nbody_api.cpp create_impl)
+    int rc = s.alloc(h, h->stream);
+    if (rc) return rc;
     if (h->cfg.method == NBODY_BARNES_HUT) {
         s.tree.alloc = pinned_alloc;
         s.tree.release = pinned_free;
-        HIP_TRY(h, hipHostMalloc(&s.h_pos, size_t(G) * cap * sizeof(double4), hipHostMallocDefault));
+        HIP_TRY(h, hipHostMalloc(&s.h_pos, size_t(s.sh.n_seg) * size_t(s.sh.seg_cap) * sizeof(double4), hipHostMallocDefault));
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NBODY_OK;
@@ -632,12 +563,12 @@ void destroy(NbodyHandle* h) {
     State* s = h->f64;
     if (!s) return;
     s->tree.clear();
-    void* dev[] = {s->d.pos_all, s->d.vel, s->d.acc, s->d.seg_count, s->d.escaped, s->d.keep, s->d.tile_state, s->d.epoch, s->d.inter,
-                   s->d_aos, s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes,
+    s->release();
+    void* dev[] = {s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes,
                    s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->d_hm_planes,
                    s->blk.level, s->blk.tau, s->blk.list, s->blk.tile_count, s->blk.smin, s->blk.planes};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {s->h_count, s->h_aos, s->h_pos, s->h_sched};
+    void* host[] = {s->h_pos, s->h_sched};
     for (void* p : host) if (p) (void)hipHostFree(p);
     s->tree_bufs.release();
     s->split.release();
@@ -648,15 +579,12 @@ void destroy(NbodyHandle* h) {
 int clone_state(NbodyHandle* src, NbodyHandle* dst) {
     State& a = *src->f64;
     State& b = *dst->f64;
-    int rc = sync_count(src, a);
+    int rc = a.sync_count(src, src->stream);
     if (rc) return rc;
-    const size_t cap = size_t(a.d.cap);
+    const size_t cap = size_t(a.sh.seg_cap);
     HIP_TRY(dst, hipStreamSynchronize(src->stream));
-    HIP_TRY(dst, hipMemcpyAsync(b.d.pos_all, a.d.pos_all, size_t(a.d.n_seg) * cap * sizeof(double4), hipMemcpyDeviceToDevice, dst->stream));
-    HIP_TRY(dst, hipMemcpyAsync(b.d.vel, a.d.vel, cap * sizeof(double4), hipMemcpyDeviceToDevice, dst->stream));
-    HIP_TRY(dst, hipMemcpyAsync(b.d.acc, a.d.acc, cap * sizeof(double4), hipMemcpyDeviceToDevice, dst->stream));
-    HIP_TRY(dst, hipMemcpyAsync(b.d.seg_count, a.d.seg_count, sizeof(int) * a.d.n_seg, hipMemcpyDeviceToDevice, dst->stream));
-    b.count_upper = a.count_upper;
+    rc = b.copy_from(dst, dst->stream, a);
+    if (rc) return rc;
     if (a.integrator == NBODY_INTEGRATOR_HERMITE4) {   // + the held jerk and whether it is valid: the clone steps like its source
         rc = ensure_hermite(dst, b);
         if (rc) return rc;
@@ -673,69 +601,24 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
         }
     }
     HIP_TRY(dst, hipStreamSynchronize(dst->stream));
-    b.g = a.g; b.g_soft = a.g_soft; b.dt = a.dt; b.theta2 = a.theta2;
-    std::memcpy(b.center, a.center, sizeof(b.center));
-    b.width = a.width; b.bnd = a.bnd; b.bounds_set = a.bounds_set;
-    b.elapsed = a.elapsed;
-    b.n_local = a.n_local;
-    return NBODY_OK;   // (like the reference's BH clone, barnes_hut.rs:113-135, the tree is not carried over)
+    return NBODY_OK;
 }
 
 int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
     State& s = *h->f64;
-    if (stride < 80 || stride % 8) return fail(h, NBODY_ERR_INVALID, "f64 handle: stride must be a multiple of 8 and >= 80 bytes");
-    if (n > size_t(h->cfg.capacity)) return fail(h, NBODY_ERR_CAPACITY, "more bodies than NbodyConfig.capacity");
-    int rc = ensure_aos(h, s, n);
-    if (rc) return rc;
-    const char* src = static_cast<const char*>(aos);
-    for (size_t k = 0; k < n; ++k) std::memcpy(s.h_aos + 10 * k, src + k * stride, 80);
-    if (n) HIP_TRY(h, hipMemcpyAsync(s.d_aos, s.h_aos, n * 80, hipMemcpyHostToDevice, h->stream));
-    const size_t G = size_t(s.d.n_seg), blk = (n + G - 1) / G;   // contiguous index blocks keep the ascending-partner order
-    for (size_t g = 0; g < G; ++g) {
-        const size_t lo = std::min(n, g * blk), hi = std::min(n, lo + blk);
-        s.count_upper[g] = int(hi - lo);
-        s.h_count[g] = int(hi - lo);
-        if (int(g) == s.d.my_seg) {
-            launch_aos_to_soa(h->stream, s.d_aos + 10 * lo, 10, int(hi - lo), s.d, 0);
-            s.n_local = hi - lo;
-            h->first_global = lo; h->n_at_upload = hi - lo;
-        } else {
-            launch_aos_to_pos(h->stream, s.d_aos + 10 * lo, 10, int(hi - lo), s.d.pos_all + g * size_t(s.d.cap));
-        }
-    }
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemsetAsync(s.d.escaped, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemcpyAsync(s.d.seg_count, s.h_count, sizeof(int) * G, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    s.count_dirty = false;
+    int rc = s.upload_blocks(h, h->stream, aos, n, stride, &h->first_global);
+    h->n_at_upload = s.n_local;
     s.hm_valid = false;
-    return NBODY_OK;
+    return rc;
 }
 
 int download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out) {
-    State& s = *h->f64;
-    if (stride < 80 || stride % 8) return fail(h, NBODY_ERR_INVALID, "f64 handle: stride must be a multiple of 8 and >= 80 bytes");
-    int rc = sync_count(h, s);
-    if (rc) return rc;
-    const size_t n = s.n_local;
-    if (n_out) *n_out = n;
-    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "download buffer too small");
-    if (n == 0) return NBODY_OK;
-    if (!aos) return fail(h, NBODY_ERR_INVALID, "null buffer");
-    rc = ensure_aos(h, s, n);
-    if (rc) return rc;
-    launch_soa_to_aos(h->stream, s.d_aos, 10, int(n), s.d);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(s.h_aos, s.d_aos, n * 80, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    char* dst = static_cast<char*>(aos);
-    for (size_t k = 0; k < n; ++k) std::memcpy(dst + k * stride, s.h_aos + 10 * k, 80);
-    return NBODY_OK;
+    return h->f64->download_own(h, h->stream, aos, cap, stride, n_out, nullptr);
 }
 
 int count(NbodyHandle* h, size_t* n_out) {
     State& s = *h->f64;
-    int rc = sync_count(h, s);
+    int rc = s.sync_count(h, h->stream);
     if (rc) return rc;
     *n_out = s.n_local;
     return NBODY_OK;
@@ -744,74 +627,43 @@ int count(NbodyHandle* h, size_t* n_out) {
 int count_global(NbodyHandle* h, size_t* n_out) {   // as of the last exchange
     State& s = *h->f64;
     s.count_dirty = true;
-    int rc = sync_count(h, s);
+    int rc = s.sync_count(h, h->stream);
     if (rc) return rc;
     size_t t = 0;
-    for (int c : s.count_upper) t += size_t(c);
+    for (int c : s.seg_count_host) t += size_t(c);
     *n_out = t;
     return NBODY_OK;
 }
 
-int add_point(NbodyHandle* h, const void* particle) {   // Vec::push (brute_force.rs:92-94)
+int add_point(NbodyHandle* h, const void* particle) {
     State& s = *h->f64;
-    if (s.d.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "add_point on a sharded f64 world is not supported (f32 handles: collective push / swap_remove)");
-    int rc = sync_count(h, s);
-    if (rc) return rc;
-    if (s.n_local >= size_t(s.d.cap)) return fail(h, NBODY_ERR_CAPACITY, "capacity exhausted");
-    rc = ensure_aos(h, s, 1);
-    if (rc) return rc;
-    std::memcpy(s.h_aos, particle, 80);
-    HIP_TRY(h, hipMemcpyAsync(s.d_aos, s.h_aos, 80, hipMemcpyHostToDevice, h->stream));
-    launch_aos_to_soa(h->stream, s.d_aos, 10, 1, s.d, s.n_local);
-    HIP_TRY(h, hipGetLastError());
-    s.n_local += 1;
-    s.hm_valid = false;
-    return push_count(h, s);
+    if (s.sh.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "add_point on a sharded f64 world is not supported (f32 handles: collective push / swap_remove)");
+    int rc = s.push_one(h, h->stream, particle);
+    if (!rc) s.hm_valid = false;
+    return rc;
 }
 
-int remove_point(NbodyHandle* h, size_t index) {   // Vec::swap_remove (brute_force.rs:96-98)
+int remove_point(NbodyHandle* h, size_t index) {
     State& s = *h->f64;
-    if (s.d.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "remove_point on a sharded f64 world is not supported (f32 handles: collective push / swap_remove)");
-    int rc = sync_count(h, s);
-    if (rc) return rc;
-    if (index >= s.n_local) return fail(h, NBODY_ERR_INVALID, "swap_remove index out of range");
-    const size_t last = s.n_local - 1;
-    if (index != last) {
-        HIP_TRY(h, hipMemcpyAsync(s.d.pos + index, s.d.pos + last, sizeof(double4), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(s.d.vel + index, s.d.vel + last, sizeof(double4), hipMemcpyDeviceToDevice, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(s.d.acc + index, s.d.acc + last, sizeof(double4), hipMemcpyDeviceToDevice, h->stream));
-    }
-    s.n_local = last;
-    s.hm_valid = false;
-    return push_count(h, s);
+    if (s.sh.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "remove_point on a sharded f64 world is not supported (f32 handles: collective push / swap_remove)");
+    int rc = s.swap_remove_one(h, h->stream, index);
+    if (!rc) s.hm_valid = false;
+    return rc;
 }
 
 int set_settings(NbodyHandle* h, double g, double g_soft, double dt, double theta2) {
-    State& s = *h->f64;
-    s.g = g; s.g_soft = g_soft; s.dt = dt; s.theta2 = theta2;
-    s.hm_valid = false;
+    h->f64->set_settings(g, g_soft, dt, theta2);
+    h->f64->hm_valid = false;
     return NBODY_OK;
 }
 
 int get_settings(const NbodyHandle* h, double* g, double* g_soft, double* dt, double* theta2) {
-    const State& s = *h->f64;
-    if (g) *g = s.g;
-    if (g_soft) *g_soft = s.g_soft;
-    if (dt) *dt = s.dt;
-    if (theta2) *theta2 = s.theta2;
+    h->f64->get_settings(g, g_soft, dt, theta2);
     return NBODY_OK;
 }
 
 int set_bounds(NbodyHandle* h, const double center[3], double width) {
-    State& s = *h->f64;
-    std::memcpy(s.center, center, sizeof(s.center));
-    s.width = width;
-    const double hw = width * 0.5;  // Bounds::new
-    for (int i = 0; i < 3; ++i) {
-        s.bnd.lo[i] = center[i] + (-hw);  // add_scalar(-half_width), shared.rs:224
-        s.bnd.hi[i] = center[i] + hw;     // shared.rs:228
-    }
-    s.bounds_set = true;
+    h->f64->set_bounds(center, width);
     return NBODY_OK;
 }
 
@@ -844,7 +696,7 @@ int update_forces(NbodyHandle* h) {
     if (s.integrator == NBODY_INTEGRATOR_HERMITE4) {
         int rc = hm_refresh(h, s);
         if (!rc && s.blk_L > 0) {   // + start levels for a macro step of the settings' dt
-            rc = sync_count(h, s);
+            rc = s.sync_count(h, h->stream);
             if (!rc) rc = assign_levels(h, s, std::fabs(s.dt));
         }
         return rc;
@@ -897,7 +749,7 @@ int download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out) {
     if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_download_levels: the handle runs the leapfrog integrator (nbody_set_integrator)");
     if (s.blk_L == 0 || !s.hm_valid || !s.lv_valid)
         return fail(h, NBODY_ERR_INVALID, "nbody_download_levels: the levels are invalid (block steps are off, or the next step or nbody_update_forces assigns them)");
-    int rc = sync_count(h, s);
+    int rc = s.sync_count(h, h->stream);
     if (rc) return rc;
     const size_t n = s.n_local;
     if (n_out) *n_out = n;
@@ -921,7 +773,7 @@ int block_step_counts(NbodyHandle* h, uint64_t out[2]) {
 int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3) {
     State& s = *h->f64;
     if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_debug_hermite_forces_of: the handle runs the leapfrog integrator (nbody_set_integrator)");
-    int rc = sync_count(h, s);
+    int rc = s.sync_count(h, h->stream);
     if (rc) return rc;
     const size_t n = s.n_local;
     if (n_ids > n) return fail(h, NBODY_ERR_INVALID, "nbody_debug_hermite_forces_of: more ids than bodies (ids must be distinct and < n)");
@@ -940,9 +792,9 @@ int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, do
     HIP_TRY(h, hipMemcpyAsync(s.blk.sched, head, sizeof(head), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // (pageable sources)
     HmActPlan plan;
-    rc = hm_act_eval(h, s, s.d.pos, s.d.vel, n_act, &plan);
+    rc = hm_act_eval(h, s, s.sh.own_pos(), s.sh.vel, n_act, &plan);
     if (rc) return rc;
-    if (h->cfg.math_mode == NBODY_MATH_FAST) launch_hm_act_reduce(h->stream, s.d, s.hm, s.blk, plan, n_act, s.g);
+    if (h->cfg.math_mode == NBODY_MATH_FAST) launch_hm_act_reduce(h->stream, s.sh, s.hm, s.blk, plan, n_act, s.g);
     HIP_TRY(h, hipGetLastError());
     std::vector<double> ta(4 * n_ids), tj(4 * n_ids);
     HIP_TRY(h, hipMemcpyAsync(ta.data(), s.hm.a1, n_ids * sizeof(double4), hipMemcpyDeviceToHost, h->stream));
@@ -959,7 +811,7 @@ int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out) {
     State& s = *h->f64;
     if (s.integrator != NBODY_INTEGRATOR_HERMITE4) return fail(h, NBODY_ERR_INVALID, "nbody_download_jerk: the handle runs the leapfrog integrator (nbody_set_integrator)");
     if (!s.hm_valid) return fail(h, NBODY_ERR_INVALID, "nbody_download_jerk: the held acceleration and jerk are stale (the next step or nbody_update_forces evaluates them)");
-    int rc = sync_count(h, s);
+    int rc = s.sync_count(h, h->stream);
     if (rc) return rc;
     const size_t n = s.n_local;
     if (n_out) *n_out = n;
@@ -980,7 +832,7 @@ int suggest_dt(NbodyHandle* h, double eta, double* dt_out) {
     int rc = s.hm_valid ? NBODY_OK : hm_refresh(h, s);
     if (rc) return rc;
     double lowest = HUGE_VAL;
-    const int blocks = launch_hm_min_ratio(h->stream, s.d, s.hm, int(s.n_local));
+    const int blocks = launch_hm_min_ratio(h->stream, s.sh, s.hm, int(s.n_local));
     if (blocks > 0) {
         HIP_TRY(h, hipGetLastError());
         std::vector<double> part(static_cast<size_t>(blocks));
@@ -998,7 +850,7 @@ int stats(NbodyHandle* h, NbodyStats* out) {
     State& s = *h->f64;
     if (h->cfg.method == NBODY_BRUTE_FORCE) {
         unsigned long long* hv = reinterpret_cast<unsigned long long*>(h->h_poison + kScratchStats);
-        HIP_TRY(h, hipMemcpyAsync(hv, s.d.inter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(hv, s.sh.inter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         h->stats.interactions = *hv;
     }
@@ -1017,15 +869,15 @@ int stats(NbodyHandle* h, NbodyStats* out) {
 
 int reset_stats(NbodyHandle* h) {
     State& s = *h->f64;
-    HIP_TRY(h, hipMemsetAsync(s.d.inter, 0, sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(s.sh.inter, 0, sizeof(unsigned long long), h->stream));
     s.blk_steps = 0; s.blk_updates = 0;
     return NBODY_OK;
 }
 
 int energy(NbodyHandle* h, double* kinetic, double* potential) {
     State& s = *h->f64;
-    if (s.d.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "nbody_energy on a sharded f64 world is not supported (a rank holds the velocities of its own block only)");
-    int rc = sync_count(h, s);
+    if (s.sh.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "nbody_energy on a sharded f64 world is not supported (a rank holds the velocities of its own block only)");
+    int rc = s.sync_count(h, h->stream);
     if (rc) return rc;
     const size_t n = s.n_local;
     const size_t blocks = (n + 255) / 256;
@@ -1037,7 +889,7 @@ int energy(NbodyHandle* h, double* kinetic, double* potential) {
             HIP_TRY(h, hipMalloc(&s.d_energy, blocks * 2 * sizeof(double)));
             s.energy_blocks = blocks;
         }
-        launch_energy(h->stream, s.d, int(n), s.g_soft * s.g_soft, s.d_energy);
+        launch_energy(h->stream, s.sh, int(n), s.g_soft * s.g_soft, s.d_energy);
         HIP_TRY(h, hipGetLastError());
         std::vector<double> part(blocks * 2);
         HIP_TRY(h, hipMemcpyAsync(part.data(), s.d_energy, blocks * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1057,24 +909,24 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
     if (rc) return rc;
     const size_t saved_n = s.n_local;
     const bool saved_dirty = s.count_dirty;
-    const std::vector<int> saved_upper = s.count_upper;
+    const std::vector<int> saved_upper = s.seg_count_host;
     s.count_dirty = true;
-    rc = sync_count(h, s);
-    if (!rc) rc = nbody::pot::begin(h, size_t(s.d.cap));
-    bodies->pos_all = s.d.pos_all; bodies->vel = s.d.vel; bodies->seg_count = s.d.seg_count;
-    bodies->f64 = 1; bodies->n_seg = s.d.n_seg; bodies->seg_cap = s.d.cap; bodies->my_seg = s.d.my_seg;
-    bodies->world = s.d.n_seg;
+    rc = s.sync_count(h, h->stream);
+    if (!rc) rc = nbody::pot::begin(h, size_t(s.sh.seg_cap));
+    bodies->pos_all = s.sh.pos_all; bodies->vel = s.sh.vel; bodies->seg_count = s.sh.seg_count;
+    bodies->f64 = 1; bodies->n_seg = s.sh.n_seg; bodies->seg_cap = s.sh.seg_cap; bodies->my_seg = s.sh.my_seg;
+    bodies->world = s.sh.n_seg;
     *g = s.g;
     if (!rc && mode == NBODY_POTENTIAL_PAIRS) {
         size_t tot = 0;
-        for (int c : s.count_upper) tot += size_t(c);
+        for (int c : s.seg_count_host) tot += size_t(c);
         if (!field) rc = nbody::pot::pairs(h, *bodies, s.n_local, tot - s.n_local, s.g_soft * s.g_soft);
     } else if (!rc) {
         PotWalkScope walking(h->pot, field ? kWalkField : kWalkPotentials);
         rc = bh_forces(h, s);
     }
     *n_own = s.n_local;
-    s.n_local = saved_n; s.count_dirty = saved_dirty; s.count_upper = saved_upper;
+    s.n_local = saved_n; s.count_dirty = saved_dirty; s.seg_count_host = saved_upper;
     if (rc) return rc;
     if (h->tp) { rc = h->tp->check(); if (rc) return fail(h, rc, h->tp->error()); }
     return NBODY_OK;

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <utility>
@@ -255,6 +256,213 @@ struct FieldBufs {
     }
 };
 
+// ---- the body vector of a handle, once for F = f32 (a base of NbodyHandle) and F = f64 (a base of nbody64::State): the
+// device arrays, the host's view of them, the settings, and the Vec-like operations that do not depend on how the forces are
+// computed.  The members take the handle (for errors) and the stream they enqueue on.
+
+// contiguous index blocks of a vector of n bodies over G shards (they keep the ascending-partner order): block g is [lo, hi)
+inline void index_block(size_t n, size_t G, size_t g, size_t* lo, size_t* hi) {
+    const size_t blk = (n + G - 1) / G;
+    *lo = std::min(n, g * blk);
+    *hi = std::min(n, *lo + blk);
+}
+
+template <class F>
+struct BodyStore {
+    using V4 = typename nbody::ShardT<F>::V4;
+    static constexpr size_t kRecBytes = 10 * sizeof(F);   // one PointParticle<F,3> record: pos, vel, acc, mass
+
+    nbody::ShardT<F> sh;
+    F g = F(1), g_soft = F(0), dt = F(1e-3), theta2 = F(0.5);  // shared.rs:69-78
+    F center[3] = {F(0), F(0), F(0)};
+    F width = F(0);
+    typename nbody::RealTypes<F>::Bounds bnd{};
+    bool bounds_set = false;
+    F elapsed = F(0);
+
+    size_t n_local = 0;        // host view of the own body count (an upper bound while count_dirty)
+    bool count_dirty = false;  // drift may have dropped bodies since n_local was read
+    std::vector<int> seg_count_host;  // host view of every segment's count (upper bounds likewise; counts only shrink between uploads)
+    int* h_counts = nullptr;   // pinned [n_seg]: all segments' counts on their way up or down
+
+    F* d_aos = nullptr;        // device staging for PointParticle records (bodies and tracers alike), grow-only
+    F* h_aos = nullptr;        // pinned host staging
+    size_t aos_cap = 0;        // records
+
+    // the arrays of sh for its n_seg / seg_cap / my_seg, zeroed (keep flags 1, epoch 1: the zeroed status words belong to no
+    // launch); poison and ids stay null.  Enqueues the fills: the caller synchronises.
+    int alloc(NbodyHandle* h, hipStream_t s) {
+        const size_t cap = size_t(sh.seg_cap), G = size_t(sh.n_seg);
+        const size_t tiles = (cap + 1023) / 1024 + 1;
+        const struct { void** p; size_t bytes; int fill; } arr[] = {
+            {reinterpret_cast<void**>(&sh.pos_all), G * cap * sizeof(V4), 0}, {reinterpret_cast<void**>(&sh.vel), cap * sizeof(V4), 0},
+            {reinterpret_cast<void**>(&sh.acc), cap * sizeof(V4), 0},         {reinterpret_cast<void**>(&sh.seg_count), G * sizeof(int), 0},
+            {reinterpret_cast<void**>(&sh.escaped), sizeof(int), 0},          {reinterpret_cast<void**>(&sh.keep), cap, 1},
+            {reinterpret_cast<void**>(&sh.tile_state), tiles * sizeof(unsigned long long), 0},
+            {reinterpret_cast<void**>(&sh.epoch), sizeof(int), 0},            {reinterpret_cast<void**>(&sh.inter), sizeof(unsigned long long), 0}};
+        for (const auto& a : arr) {
+            HIP_TRY(h, hipMalloc(a.p, a.bytes));
+            HIP_TRY(h, hipMemsetAsync(*a.p, a.fill, a.bytes, s));
+        }
+        HIP_TRY(h, hipMemsetAsync(sh.epoch, 1, 1, s));   // epoch = 1
+        HIP_TRY(h, hipHostMalloc(&h_counts, G * sizeof(int), hipHostMallocDefault));
+        seg_count_host.assign(G, 0);
+        return NBODY_OK;
+    }
+    void release() {
+        for (void* p : {static_cast<void*>(sh.pos_all), static_cast<void*>(sh.vel), static_cast<void*>(sh.acc), static_cast<void*>(sh.seg_count),
+                        static_cast<void*>(sh.escaped), static_cast<void*>(sh.keep), static_cast<void*>(sh.tile_state), static_cast<void*>(sh.epoch),
+                        static_cast<void*>(sh.inter), static_cast<void*>(d_aos)})
+            if (p) (void)hipFree(p);
+        if (h_aos) (void)hipHostFree(h_aos);
+        if (h_counts) (void)hipHostFree(h_counts);
+        sh = nbody::ShardT<F>{};
+        h_counts = nullptr; d_aos = h_aos = nullptr; aos_cap = 0;
+    }
+    // what a clone takes over from `a` (same shape): the bodies of every segment and their counts, enqueued on s once the
+    // caller has synchronised a's stream, and the host view.  Like the reference's BH clone (barnes_hut.rs:113-135), no tree.
+    int copy_from(NbodyHandle* h, hipStream_t s, const BodyStore& a) {
+        const size_t cap = size_t(a.sh.seg_cap), G = size_t(a.sh.n_seg);
+        HIP_TRY(h, hipMemcpyAsync(sh.pos_all, a.sh.pos_all, G * cap * sizeof(V4), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(sh.vel, a.sh.vel, cap * sizeof(V4), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(sh.acc, a.sh.acc, cap * sizeof(V4), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(sh.seg_count, a.sh.seg_count, G * sizeof(int), hipMemcpyDeviceToDevice, s));
+        g = a.g; g_soft = a.g_soft; dt = a.dt; theta2 = a.theta2;
+        std::copy(a.center, a.center + 3, center);
+        width = a.width; bnd = a.bnd; bounds_set = a.bounds_set;
+        elapsed = a.elapsed;
+        n_local = a.n_local;
+        seg_count_host = a.seg_count_host;
+        return NBODY_OK;
+    }
+
+    // staging for `records` PointParticle records: device and pinned host, grow-only
+    int ensure_aos(NbodyHandle* h, size_t records) {
+        if (records <= aos_cap) return NBODY_OK;
+        if (d_aos) (void)hipFree(d_aos);
+        if (h_aos) (void)hipHostFree(h_aos);
+        d_aos = nullptr; h_aos = nullptr; aos_cap = 0;
+        HIP_TRY(h, hipMalloc(&d_aos, records * kRecBytes));
+        HIP_TRY(h, hipHostMalloc(&h_aos, records * kRecBytes, hipHostMallocDefault));
+        aos_cap = records;
+        return NBODY_OK;
+    }
+    // refresh the host view of the counts (one small D2H + sync), only when it may be stale
+    int sync_count(NbodyHandle* h, hipStream_t s) {
+        if (!count_dirty) return NBODY_OK;
+        HIP_TRY(h, hipMemcpyAsync(h_counts, sh.seg_count, sizeof(int) * sh.n_seg, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        for (int k = 0; k < sh.n_seg; ++k) seg_count_host[size_t(k)] = h_counts[k];
+        n_local = size_t(h_counts[sh.my_seg]);
+        count_dirty = false;
+        return NBODY_OK;
+    }
+    // the host's counts of every segment / n_local as the own segment's count to the device; synchronises (h_counts is reused)
+    int push_counts(NbodyHandle* h, hipStream_t s) {
+        for (int k = 0; k < sh.n_seg; ++k) h_counts[k] = seg_count_host[size_t(k)];
+        HIP_TRY(h, hipMemcpyAsync(sh.seg_count, h_counts, sizeof(int) * sh.n_seg, hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        return NBODY_OK;
+    }
+    int push_own_count(NbodyHandle* h, hipStream_t s) {
+        h_counts[sh.my_seg] = int(n_local);
+        HIP_TRY(h, hipMemcpyAsync(sh.own_count(), h_counts + sh.my_seg, sizeof(int), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        return NBODY_OK;
+    }
+
+    void set_settings(F g_, F g_soft_, F dt_, F theta2_) { g = g_; g_soft = g_soft_; dt = dt_; theta2 = theta2_; }
+    template <class T> void get_settings(T* g_, T* g_soft_, T* dt_, T* theta2_) const {
+        if (g_) *g_ = T(g);
+        if (g_soft_) *g_soft_ = T(g_soft);
+        if (dt_) *dt_ = T(dt);
+        if (theta2_) *theta2_ = T(theta2);
+    }
+    void set_bounds(const F c[3], F w) {
+        std::copy(c, c + 3, center);
+        width = w;
+        const F hw = width * F(0.5);  // Bounds::new
+        for (int i = 0; i < 3; ++i) {
+            bnd.lo[i] = center[i] + (-hw);  // add_scalar(-half_width), shared.rs:224
+            bnd.hi[i] = center[i] + hw;     // shared.rs:228
+        }
+        bounds_set = true;
+    }
+
+    // the caller's n records of `stride` bytes into the index blocks: every block's positions, the own block's velocities and
+    // accelerations; *own_first = where the own block starts in the vector (its length is n_local).  Synchronises.
+    int upload_blocks(NbodyHandle* h, hipStream_t s, const void* aos, size_t n, size_t stride, size_t* own_first) {
+        int rc = ensure_aos(h, n);
+        if (rc) return rc;
+        const char* src = static_cast<const char*>(aos);
+        for (size_t k = 0; k < n; ++k) std::memcpy(h_aos + 10 * k, src + k * stride, kRecBytes);
+        if (n) HIP_TRY(h, hipMemcpyAsync(d_aos, h_aos, n * kRecBytes, hipMemcpyHostToDevice, s));
+        for (size_t k = 0; k < size_t(sh.n_seg); ++k) {
+            size_t lo, hi;
+            index_block(n, size_t(sh.n_seg), k, &lo, &hi);
+            seg_count_host[k] = int(hi - lo);
+            const bool own = int(k) == sh.my_seg;
+            nbody::launch_aos_to_soa<F>(s, d_aos + 10 * lo, 10, int(hi - lo), sh.pos_all + k * size_t(sh.seg_cap), own ? sh.vel : nullptr,
+                                        own ? sh.acc : nullptr);
+            if (own) { *own_first = lo; n_local = hi - lo; }
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemsetAsync(sh.escaped, 0, sizeof(int), s));
+        count_dirty = false;
+        return push_counts(h, s);
+    }
+    // the own block's live bodies as records of `stride` bytes; *n_out = their number even when `cap` records are too few.
+    // before_copy_out (may be null) runs after the synchronisation and before anything reaches the caller's buffer.
+    int download_own(NbodyHandle* h, hipStream_t s, void* aos, size_t cap, size_t stride, size_t* n_out, int (*before_copy_out)(NbodyHandle*)) {
+        int rc = sync_count(h, s);
+        if (rc) return rc;
+        const size_t n = n_local;
+        if (n_out) *n_out = n;
+        if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "download buffer too small");
+        if (n == 0) return NBODY_OK;
+        if (!aos) return fail(h, NBODY_ERR_INVALID, "null buffer");
+        rc = ensure_aos(h, n);
+        if (rc) return rc;
+        nbody::launch_soa_to_aos<F>(s, d_aos, 10, int(n), sh.own_pos(), sh.vel, sh.acc);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(h_aos, d_aos, n * kRecBytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (before_copy_out) { rc = before_copy_out(h); if (rc) return rc; }
+        char* dst = static_cast<char*>(aos);
+        for (size_t k = 0; k < n; ++k) std::memcpy(dst + k * stride, h_aos + 10 * k, kRecBytes);
+        return NBODY_OK;
+    }
+    // Vec::push (brute_force.rs:92-94) and Vec::swap_remove (brute_force.rs:96-98) on a world of one shard; both synchronise
+    int push_one(NbodyHandle* h, hipStream_t s, const void* particle) {
+        int rc = sync_count(h, s);
+        if (rc) return rc;
+        if (n_local >= size_t(sh.seg_cap)) return fail(h, NBODY_ERR_CAPACITY, "capacity exhausted");
+        rc = ensure_aos(h, 1);
+        if (rc) return rc;
+        std::memcpy(h_aos, particle, kRecBytes);
+        HIP_TRY(h, hipMemcpyAsync(d_aos, h_aos, kRecBytes, hipMemcpyHostToDevice, s));
+        nbody::launch_aos_to_soa<F>(s, d_aos, 10, 1, sh.own_pos() + n_local, sh.vel + n_local, sh.acc + n_local);
+        HIP_TRY(h, hipGetLastError());
+        n_local += 1;
+        seg_count_host[size_t(sh.my_seg)] = int(n_local);
+        return push_own_count(h, s);
+    }
+    int swap_remove_one(NbodyHandle* h, hipStream_t s, size_t index) {
+        int rc = sync_count(h, s);
+        if (rc) return rc;
+        if (index >= n_local) return fail(h, NBODY_ERR_INVALID, "swap_remove index out of range");  // Vec::swap_remove panics
+        const size_t last = n_local - 1;
+        if (index != last) {
+            HIP_TRY(h, hipMemcpyAsync(sh.own_pos() + index, sh.own_pos() + last, sizeof(V4), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(sh.vel + index, sh.vel + last, sizeof(V4), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(sh.acc + index, sh.acc + last, sizeof(V4), hipMemcpyDeviceToDevice, s));
+        }
+        n_local = last;
+        seg_count_host[size_t(sh.my_seg)] = int(last);
+        return push_own_count(h, s);
+    }
+};
+
 // nbody_tracers_* (nbody_tracer.cpp): massless particles beside the bodies.  Their state is a second Shard of one segment, so
 // the integrate and compact kernels run on it unchanged; n_host == 0 (no tracers) keeps every step path as it was.
 struct TracerState {
@@ -277,27 +485,14 @@ struct TracerState {
     bool kick_pending = false;   // a step's tracer walk takes the kick + half drift along (dt: NbodyHandle::kick_dt)
 };
 
-struct NbodyHandle {
+struct NbodyHandle : BodyStore<float> {
     NbodyConfig cfg{};
     nbody::Tuning tune;        // this handle's launch-shape and scheme knobs (nbody_set_tuning; NBODY_* environment at create)
     int device = 0;
     hipStream_t stream = nullptr;
-    Shard sh;
-    float g = 1.0f, g_soft = 0.0f, dt = 1e-3f, theta2 = 0.5f;  // shared.rs:69-78
-    float center[3] = {0.f, 0.f, 0.f};
-    float width = 0.f;
-    BoundsF bnd{};
-    bool bounds_set = false;
-    float elapsed = 0.f;
-
-    size_t n_local = 0;        // host view of the own body count (an upper bound while count_dirty)
-    bool count_dirty = false;  // drift may have dropped bodies since n_local was read
-    std::vector<int> seg_count_host;  // host view of every segment's count (upper bounds likewise)
-    size_t first_global = 0, n_at_upload = 0;
-
-    float* d_aos = nullptr;    // device staging for PointParticle records
-    float* h_aos = nullptr;    // pinned host staging
-    size_t aos_cap = 0;        // records
+    // (BodyStore<float>: sh, the settings and bounds, n_local / count_dirty / seg_count_host / h_counts, the AoS staging;
+    // an f64 handle keeps its bodies in nbody64::State's BodyStore<double> and leaves this one's arrays null)
+    size_t first_global = 0, n_at_upload = 0;   // the own index block at the last upload (both precisions)
 
     // Barnes-Hut
     std::unique_ptr<nbody::WorkerPool> pool;
@@ -307,7 +502,6 @@ struct NbodyHandle {
     int* d_order = nullptr;
     size_t d_node_cap = 0, d_order_cap = 0;
     float* h_pos = nullptr;    // pinned: all segments' positions
-    int* h_counts = nullptr;   // pinned: all segments' counts
     std::vector<int32_t> own_order;
     TreeBuildBufs tree_bufs;     // the device build's
     float4* d_nested_stack = nullptr;  // strict Barnes-Hut: per-lane stack of open cells (k_bh_walk_nested)
@@ -404,18 +598,6 @@ struct NbodyHandle {
 // NbodyHandle::h_poison as pinned scratch for small read-backs: each user copies, synchronises and reads at once
 constexpr int kScratchStats = 4;          // one u64 ([4..5]): nbody_stats' interaction count
 constexpr int kScratchTracerCount = 6;    // one int: the live tracer count, up and down
-
-// staging for `records` PointParticle records of 10 floats (bodies and tracers alike): device and pinned host, grow-only
-inline int ensure_aos(NbodyHandle* h, size_t records) {
-    if (records <= h->aos_cap) return NBODY_OK;
-    if (h->d_aos) (void)hipFree(h->d_aos);
-    if (h->h_aos) (void)hipHostFree(h->h_aos);
-    h->d_aos = nullptr; h->h_aos = nullptr; h->aos_cap = 0;
-    HIP_TRY(h, hipMalloc(&h->d_aos, records * 10 * sizeof(float)));
-    HIP_TRY(h, hipHostMalloc(&h->h_aos, records * 10 * sizeof(float), hipHostMallocDefault));
-    h->aos_cap = records;
-    return NBODY_OK;
-}
 
 // grow-only device array: to n + n / 4 + 1024 elements of elem_bytes when it holds fewer than n
 template <class T>

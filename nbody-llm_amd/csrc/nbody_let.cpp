@@ -497,14 +497,8 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
     if (own.size() > size_t(sh.seg_cap)) return fail(h, NBODY_ERR_CAPACITY, "NBODY_SHARD_SPATIAL: this rank's key range holds more bodies than its capacity");
     const size_t m = own.size();
     // staging through the handle's AoS buffers (40-byte records)
-    if (m > h->aos_cap) {
-        if (h->d_aos) (void)hipFree(h->d_aos);
-        if (h->h_aos) (void)hipHostFree(h->h_aos);
-        h->d_aos = nullptr; h->h_aos = nullptr; h->aos_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_aos, std::max<size_t>(1, m) * 40));
-        HIP_TRY(h, hipHostMalloc(&h->h_aos, std::max<size_t>(1, m) * 40, hipHostMallocDefault));
-        h->aos_cap = std::max<size_t>(1, m);
-    }
+    int rc_aos = h->ensure_aos(h, std::max<size_t>(1, m));
+    if (rc_aos) return rc_aos;
     for (size_t j = 0; j < m; ++j) std::memcpy(h->h_aos + 10 * j, src + size_t(own[j]) * stride, 40);
     if (m) HIP_TRY(h, hipMemcpyAsync(h->d_aos, h->h_aos, m * 40, hipMemcpyHostToDevice, h->stream));
     launch_aos_to_soa(h->stream, h->d_aos, 10, int(m), sh.own_pos(), sh.vel, sh.acc);

@@ -95,7 +95,7 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride, size_t capa
         return NBODY_OK;
     }
     int rc = ensure(h, cap);
-    if (!rc) rc = ensure_aos(h, n);
+    if (!rc) rc = h->ensure_aos(h, n);
     if (rc) return rc;
     const char* src = static_cast<const char*>(aos);
     for (size_t k = 0; k < n; ++k) {
@@ -125,7 +125,7 @@ int download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out
     if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_tracers_download: buffer too small");
     if (n == 0) return NBODY_OK;
     if (!aos) return fail(h, NBODY_ERR_INVALID, "nbody_tracers_download: null buffer");
-    rc = ensure_aos(h, n);
+    rc = h->ensure_aos(h, n);
     if (rc) return rc;
     nbody::launch_soa_to_aos(h->stream, h->d_aos, 10, int(n), t.sh.pos_all, t.sh.vel, t.sh.acc);   // (pos.w = 0: the mass written)
     HIP_TRY(h, hipGetLastError());

@@ -7,18 +7,14 @@
 
 namespace nbody {
 
-template <class F> struct Real;
-template <> struct Real<float> {
-    using V4 = float4;
-    using Bounds = BoundsF;
+template <class F> struct Real;   // RealTypes<F> (shard.h: V4, Bounds) + the arithmetic only device code can name
+template <> struct Real<float> : RealTypes<float> {
     static constexpr float half = 0.5f;
     static __device__ __forceinline__ V4 make4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
     static __device__ __forceinline__ float sqrt(float x) { return __builtin_sqrtf(x); }   // IEEE (-fhip-fp32-correctly-rounded-divide-sqrt)
     static __device__ __forceinline__ float rsqrt(float x) { return __builtin_amdgcn_rsqf(x); }   // fast math: v_rsq_f32, 1 ulp
 };
-template <> struct Real<double> {
-    using V4 = double4;
-    using Bounds = nbody64::Bounds64;
+template <> struct Real<double> : RealTypes<double> {
     static constexpr double half = 0.5;
     static __device__ __forceinline__ V4 make4(double x, double y, double z, double w) { return make_double4(x, y, z, w); }
     static __device__ __forceinline__ double sqrt(double x) { return __builtin_sqrt(x); }  // correctly rounded on gfx950

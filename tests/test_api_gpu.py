@@ -137,3 +137,113 @@ def test_clone_of_a_handle_with_a_live_communicator(gpu, method):
             assert len(sim) == len(twin) == 3000
         finally:
             twin.close()
+
+
+def test_strided_upload_and_download_f64(gpu):
+    """The same on an f64 handle: an 80-byte PointParticle<f64,3> inside a 96-byte record; stride >= 80, multiple of 8."""
+    nb = gpu
+    n = 300
+    ics = nb.plummer(n, seed=1, f64=True)
+    wide = np.zeros(n, dtype=np.dtype([("p", nb.PARTICLE_DTYPE64), ("tag", "<i8", 2)]))
+    assert wide.dtype.itemsize == 96
+    wide["p"] = ics
+    wide["tag"] = 7
+    with nb.Simulation(ics[:1], *BOX, capacity=n) as sim:
+        sim._check(nb.lib.nbody_upload(sim._h, wide.ctypes.data, n, wide.dtype.itemsize))
+        out = np.zeros(n, dtype=wide.dtype)
+        out["tag"] = 9
+        got_n = C.c_size_t(0)
+        sim._check(nb.lib.nbody_download(sim._h, out.ctypes.data, n, out.dtype.itemsize, C.byref(got_n)))
+        assert got_n.value == n
+        assert out["p"].tobytes() == ics.tobytes() and np.all(out["tag"] == 9)
+        assert nb.lib.nbody_upload(sim._h, wide.ctypes.data, n, 72) == nb.NBODY_ERR_INVALID
+        assert nb.lib.nbody_upload(sim._h, wide.ctypes.data, n, 84) == nb.NBODY_ERR_INVALID     # not a multiple of 8
+        assert nb.lib.nbody_upload(sim._h, wide.ctypes.data, n + 1, 96) == nb.NBODY_ERR_CAPACITY
+        small = np.zeros(10, dtype=nb.PARTICLE_DTYPE64)
+        assert nb.lib.nbody_download(sim._h, small.ctypes.data, 10, 80, C.byref(got_n)) == nb.NBODY_ERR_CAPACITY
+        assert got_n.value == n and b"too small" in nb.lib.nbody_last_error(sim._h)
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+def test_vec_surface_push_swap_remove_retain(gpu, orc, f64):
+    """Vec::push / Vec::swap_remove / Vec::retain on one shard against a Python list, bit for bit in all ten fields.  Capacity
+    1 025: the retain's tile_state has its second tile and the spare word, and the second push lands in that tile."""
+    nb = gpu
+    cap = 1025
+    pool = nb.plummer(cap + 1, seed=5, f64=f64)
+    pool["acceleration"] = pool["velocity"][::-1] * 0.25     # (all ten fields carry something to lose)
+    model = list(range(cap - 2))     # the Vec, as indices into the pool
+
+    def check(sim):
+        got = sim.get_points()
+        assert len(sim) == len(got) == len(model)
+        assert _same_bits(got, pool[model])
+
+    def swap_remove(k):
+        model[k] = model[-1]
+        model.pop()
+
+    with nb.Simulation(pool[: cap - 2], *BOX, capacity=cap, method=nb.BRUTE_FORCE, math_mode=nb.STRICT) as sim:
+        check(sim)
+        for k in (cap - 2, cap - 1):
+            sim.add_point(pool[k])
+            model.append(k)
+            check(sim)
+        assert len(model) == cap
+        assert nb.lib.nbody_add_point(sim._h, pool[cap:].ctypes.data) == nb.NBODY_ERR_CAPACITY
+        check(sim)
+        sim.remove_point(0)
+        swap_remove(0)
+        check(sim)
+        sim.remove_point(len(model) - 1)
+        swap_remove(len(model) - 1)
+        check(sim)
+        assert nb.lib.nbody_remove_point(sim._h, len(model)) == nb.NBODY_ERR_INVALID
+        check(sim)
+
+        # one step in a box that some bodies leave, chosen from the oracle: half of them lie outside this cube
+        sd = dict(g=1.0, g_soft=0.0, dt=1e-3, theta2=0.5)
+        start = pool[model]
+        width = float(np.float32(2.0 * np.median(np.abs(start["position"]).max(axis=1))))
+        center = (0.0, 0.0, 0.0)
+        ref = orc.bf_step_by(start.astype(orc.P64 if f64 else orc.P32), sd, center, width, sd["dt"])
+        assert 0 < len(ref) < len(start)
+        sim.set_bounds(center, width)
+        sim.step()
+        got = sim.get_points()
+        assert len(sim) == len(got) == len(ref)
+        for f in ("position", "velocity", "acceleration", "mass"):     # (the retain keeps the survivors' order)
+            assert got[f].tobytes() == ref[f].tobytes(), f
+
+
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+def test_clone_carries_the_host_view(gpu, f64):
+    """`Clone` (shared.rs:80) takes the settings, the bounds, elapsed, the count and every body field along, and the twin then
+    steps bit for bit like its source (Barnes-Hut, strict: the root cell of the next tree is the bounds the twin was given)."""
+    nb = gpu
+    ics = nb.plummer(301, seed=11, f64=f64)
+    center, width = (0.5, -0.25, 0.125), 48.0
+    with nb.Simulation(ics[:300], center, width, capacity=400, method=nb.BARNES_HUT, math_mode=nb.STRICT) as sim:
+        sim.settings = nb.Settings(0.75, 0.015625, 0.001953125, 0.375)
+        sim.steps(2)
+        sim.add_point(ics[300])
+        twin = sim.clone()
+        try:
+            assert twin.settings == sim.settings == nb.Settings(0.75, 0.015625, 0.001953125, 0.375)
+            assert twin.elapsed() == sim.elapsed() == 2 * 0.001953125
+            assert len(twin) == len(sim) == 301
+            assert _same_bits(twin.get_points(), sim.get_points())
+            sim.steps(2)
+            twin.steps(2)
+            assert twin.elapsed() == sim.elapsed()
+            assert _same_bits(twin.get_points(), sim.get_points())
+            (mm_a, depth_a), (mm_b, depth_b) = sim.tree_cells(), twin.tree_cells()
+            assert _same_bits(mm_a, mm_b) and _same_bits(depth_a, depth_b)
+            c = np.asarray(center, np.float32)
+            assert np.array_equal(mm_b[0], np.concatenate([c - np.float32(24.0), c + np.float32(24.0)]))
+        finally:
+            twin.close()
