@@ -444,6 +444,74 @@ int nbody_tracer_stats(NbodyHandle* h, uint64_t out[2]);
  * bodies; out = {tracers per lane, tracer groups (of 256 x tracers per lane), body slices K, slice length}.  Slice k covers
  * bodies [k * length, min(n_bodies, (k + 1) * length)). */
 int nbody_host_tracer_plan(size_t n_tracers, size_t n_bodies, int out[4]);
+/* ---- external field: static analytic potentials acting on bodies and tracers (no reference counterpart) -----------
+ * A handle may hold up to NBODY_EXTERNAL_MAX COMPONENTS of a smooth background: a halo, a bulge, a disc, a central mass.  In
+ * every kind d = x - center, and g is the handle's g as it stands at the pass.
+ *   NBODY_EXT_PLUMMER         p = {M, b}, b >= 0 (b = 0: a point mass).  phi = -g M / sqrt(|d|^2 + b^2),
+ *                             a = -g M d / (|d|^2 + b^2)^(3/2); the term is skipped (exact zeros) where |d|^2 + b^2 == 0.
+ *   NBODY_EXT_HERNQUIST       p = {M, a}, a > 0, r = |d|.  phi = -g M / (r + a), acc = -g M d / (r (r + a)^2); the acceleration is
+ *                             skipped where r == 0, phi is still evaluated there.
+ *   NBODY_EXT_MIYAMOTO_NAGAI  p = {M, a, b}, a >= 0, b > 0, disc plane z = 0.  B = sqrt(dz^2 + b^2), D = dx^2 + dy^2 + (a + B)^2,
+ *                             phi = -g M / sqrt(D), a_xy = -g M d_xy / D^(3/2), a_z = -g M dz (a + B) / (B D^(3/2)).
+ *   NBODY_EXT_LOGARITHMIC     p = {v0, rc, qy, qz}, rc > 0, qy > 0, qz > 0; independent of g.
+ *                             S = rc^2 + dx^2 + (dy/qy)^2 + (dz/qz)^2, phi = (1/2) v0^2 ln S, a = -v0^2 {dx, dy/qy^2, dz/qz^2} / S.
+ * NBODY_ERR_INVALID (nbody_last_error names the call): a non-finite centre or parameter (all four p of every kind are
+ * looked at: set the unused ones to 0), a parameter outside the ranges above, an unknown kind, a non-zero `reserved`,
+ * n > NBODY_EXTERNAL_MAX.  On an NBODY_F32 handle the values must also be finite and in range once rounded to f32.
+ *   THE ACCELERATION has one arithmetic, whatever math_mode says, in the handle's precision F: centre and parameters are
+ * rounded to F once, sqrt and divide are IEEE, nothing is contracted, every product and sum is rounded on its own, in this
+ * order (d_c = x_c - center_c first):
+ *     PLUMMER         r2 = ((dx dx + dy dy) + dz dz) + b b;  r = sqrt(r2);  f = (g M) / (r2 r);  t_c = -(d_c f)
+ *     HERNQUIST       r = sqrt((dx dx + dy dy) + dz dz);  ra = r + a;  f = (g M) / (r (ra ra));  t_c = -(d_c f)
+ *     MIYAMOTO_NAGAI  B = sqrt(dz dz + b b);  aB = a + B;  D = (dx dx + dy dy) + aB aB;  f = (g M) / (D sqrt(D));
+ *                     fz = (f aB) / B;  t_x = -(dx f),  t_y = -(dy f),  t_z = -(dz fz)
+ *     LOGARITHMIC     yq = dy / qy;  zq = dz / qz;  S = ((rc rc + dx dx) + yq yq) + zq zq;  f = (v0 v0) / S;
+ *                     t_x = -(dx f),  t_y = -((dy / (qy qy)) f),  t_z = -((dz / (qz qz)) f)
+ * s = 0, then for the components in ascending order s_c += t_c (a skipped term adds exact zeros), and the pass's acceleration
+ * becomes acc_c = acc_pass_c + s_c.  tests/external_ref.py restates this in numpy; the accelerations agree bit for bit in both
+ * math modes.
+ *   THE STEP with a field is the leapfrog as it stands -- half drift, retain, the force pass untouched, kick + half drift --
+ * except that the acceleration the kick reads and nbody_download reports is acc_pass + s(x), x the half-drifted, retained
+ * positions.  nbody_update_forces does the same without the kick.  Tracers get the same term at their own positions.
+ * NbodyStats and nbody_tracer_stats do not change.  nbody_clone carries the field.  nbody_steps(k) gives the bits of k
+ * nbody_step_by calls and stays enqueue-only wherever it is without a field.  A handle that never sets a field runs the code
+ * it ran before untouched, and one that sets a field and removes it without a step in between gives the bits of one that
+ * never did.
+ *   THE POTENTIALS (nbody_external_potentials, nbody_external_energy, the phi of nbody_external_at) are f64 on either dtype:
+ * positions widened, centre and parameters as given, the expressions above for phi (Plummer: 0 where skipped), summed over the
+ * components in ascending order, at the handle's CURRENT positions.  nbody_external_at returns f64 acc from the acceleration
+ * expressions in f64 -- the code of nbody_host_external_eval.  A probe with a non-finite coordinate gets NaN and disturbs no
+ * other.  These calls leave no trace in state or statistics.
+ *   nbody_energy*, nbody_potentials and nbody_field_at stay SELF-GRAVITY ONLY; the conserved total is
+ * KE + PE + nbody_external_energy.
+ *   Accepted on world_size == 1, NBODY_SHARD_INDEX handles running the leapfrog: both dtypes, both methods, both math modes,
+ * every tree build and leaf rule, with or without tracers and nbody_set_multipole(2).  Deliberately out of scope, refused with
+ * NBODY_ERR_INVALID: handles of a multi-rank world and NBODY_SHARD_SPATIAL handles (all five handle calls);
+ * nbody_set_external_field with n > 0 while NBODY_INTEGRATOR_HERMITE4 is selected, and nbody_set_integrator(HERMITE4) while a
+ * field is set (the Hermite step would need the field's jerk); time-dependent or moving components; the external term in
+ * nbody_energy*, nbody_potentials or nbody_field_at. */
+#define NBODY_EXTERNAL_MAX 8
+enum { NBODY_EXT_PLUMMER = 0, NBODY_EXT_HERNQUIST = 1, NBODY_EXT_MIYAMOTO_NAGAI = 2, NBODY_EXT_LOGARITHMIC = 3 };
+typedef struct NbodyExternalComponent {
+    int32_t kind;
+    int32_t reserved;
+    double center[3];
+    double p[4];
+} NbodyExternalComponent;
+/* Replaces the field; n == 0 removes it. */
+int nbody_set_external_field(NbodyHandle* h, const NbodyExternalComponent* comps, size_t n);
+/* The components as given; *n_out = how many even when `cap` are too few (NBODY_ERR_CAPACITY then). */
+int nbody_get_external_field(const NbodyHandle* h, NbodyExternalComponent* comps, size_t cap, size_t* n_out);
+/* phi_ext per body, in nbody_download's order; *n_out = how many. */
+int nbody_external_potentials(NbodyHandle* h, double* phi, size_t cap, size_t* n_out);
+/* sum_i m_i phi_ext(x_i): per block of 256 bodies a pairwise tree, the blocks in ascending order; no atomics, the same input
+ * gives the same bits. */
+int nbody_external_energy(NbodyHandle* h, double* potential);
+/* The field of the handle at n_points probes (f64 triples): acc [n][3] and phi [n], either may be NULL. */
+int nbody_external_at(NbodyHandle* h, const double* xyz, size_t n_points, double* acc, double* phi);
+/* Host-only (no device needed), f64: the same for components and g given by the caller. */
+int nbody_host_external_eval(const NbodyExternalComponent* comps, size_t n, double g, const double* xyz, size_t n_points,
+                             double* acc, double* phi);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

@@ -60,6 +60,8 @@ POTENTIAL_TREE_QUADRUPOLE = 2            # ... | POTENTIAL_TREE with the quadrup
 MULTIPOLE_MONOPOLE, MULTIPOLE_QUADRUPOLE = 1, 2   # nbody_set_multipole: order of the Barnes-Hut force walk's expansion
 LEAPFROG, HERMITE4 = 0, 1   # nbody_set_integrator: the reference's leapfrog | fourth-order Hermite (f64 brute force, one rank)
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
+EXTERNAL_MAX = 8   # nbody_set_external_field: components of a static external field, and their kinds
+EXT_PLUMMER, EXT_HERNQUIST, EXT_MIYAMOTO_NAGAI, EXT_LOGARITHMIC = 0, 1, 2, 3
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -83,6 +85,8 @@ DECLARED_SYMBOLS = [
     "nbody_set_integrator", "nbody_get_integrator", "nbody_download_jerk", "nbody_suggest_dt",
     "nbody_set_block_steps", "nbody_get_block_steps", "nbody_download_levels", "nbody_block_step_counts",
     "nbody_debug_hermite_forces_of",
+    "nbody_set_external_field", "nbody_get_external_field", "nbody_external_potentials", "nbody_external_energy",
+    "nbody_external_at", "nbody_host_external_eval",
 ]
 
 
@@ -98,6 +102,11 @@ class NbodyLetStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("steps", "bodies_migrated", "nodes_local", "nodes_global", "nodes_sent", "nodes_received",
                                           "bytes_sent", "bytes_allgather_equivalent")] + [("phase_ms", C.c_double * 5)] + \
                [(k, C.c_uint64) for k in ("host_syncs", "migrant_respills", "node_array_peak_bytes", "node_array_bytes")]
+
+
+class NbodyExternalComponent(C.Structure):
+    """One component of a static external field: kind EXT_*, centre, p = the kind's parameters (include/nbody_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("center", C.c_double * 3), ("p", C.c_double * 4)]
 
 
 class NbodyStats(C.Structure):
@@ -200,6 +209,13 @@ _sig("nbody_tracers_download", _i, _H, C.c_void_p, _sz, _sz, C.POINTER(_sz))
 _sig("nbody_tracers_count", _i, _H, C.POINTER(_sz))
 _sig("nbody_tracer_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_host_tracer_plan", _i, _sz, _sz, C.POINTER(_i))
+_pc = C.POINTER(NbodyExternalComponent)
+_sig("nbody_set_external_field", _i, _H, _pc, _sz)
+_sig("nbody_get_external_field", _i, _H, _pc, _sz, C.POINTER(_sz))
+_sig("nbody_external_potentials", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_external_energy", _i, _H, C.POINTER(C.c_double))
+_sig("nbody_external_at", _i, _H, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
+_sig("nbody_host_external_eval", _i, _pc, _sz, C.c_double, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -254,6 +270,33 @@ class NbodyError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"nbody error {code}: {msg}")
         self.code = code
+
+
+def external_component(kind: int, p, center=(0.0, 0.0, 0.0), reserved: int = 0) -> NbodyExternalComponent:
+    """kind EXT_PLUMMER p = (M, b) | EXT_HERNQUIST (M, a) | EXT_MIYAMOTO_NAGAI (M, a, b) | EXT_LOGARITHMIC (v0, rc, qy, qz);
+    parameters the kind does not use are 0."""
+    p = [float(v) for v in p] + [0.0] * (4 - len(p))
+    return NbodyExternalComponent(int(kind), int(reserved), (C.c_double * 3)(*[float(v) for v in center]), (C.c_double * 4)(*p))
+
+
+def _component_array(comps):
+    comps = list(comps)
+    return (NbodyExternalComponent * max(1, len(comps)))(*comps), len(comps)
+
+
+def host_external_eval(comps, g: float, points, acc: bool = True, phi: bool = True):
+    """(acc [M, 3] f64 | None, phi [M] f64 | None) of the components at the M points, on the host in f64
+    (nbody_host_external_eval; no device needed): the code nbody_external_at runs on the device."""
+    arr, n = _component_array(comps)
+    xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    m = len(xyz)
+    a = np.zeros((m, 3), np.float64) if acc else None
+    v = np.zeros(m, np.float64) if phi else None
+    rc = lib.nbody_host_external_eval(arr, n, float(g), xyz.ctypes.data if m else None, m, a.ctypes.data if acc else None,
+                                      v.ctypes.data if phi else None)
+    if rc:
+        raise NbodyError(rc, (lib.nbody_last_error(None) or b"").decode())
+    return a, v
 
 
 def device_count() -> int:
@@ -436,6 +479,46 @@ class Simulation:
         out = (C.c_uint64 * 2)()
         self._check(lib.nbody_tracer_stats(self._h, out))
         return int(out[0]), int(out[1])
+
+    # -- a static external field acting on bodies and tracers (nbody_set_external_field; leapfrog handles of a one-rank world)
+    @property
+    def external_field(self) -> list:
+        """The components of the handle's external field as given ([]: none).  Assigning a list of NbodyExternalComponent
+        (external_component(...)) replaces it, [] removes it; clone() carries it."""
+        arr = (NbodyExternalComponent * EXTERNAL_MAX)()
+        n = C.c_size_t(0)
+        self._check(lib.nbody_get_external_field(self._h, arr, EXTERNAL_MAX, C.byref(n)))
+        return [external_component(c.kind, list(c.p), list(c.center), c.reserved) for c in arr[: n.value]]
+
+    @external_field.setter
+    def external_field(self, comps):
+        arr, n = _component_array(comps)
+        self._check(lib.nbody_set_external_field(self._h, arr, n))
+
+    def external_potentials(self) -> np.ndarray:
+        """phi_ext [n] f64 of the bodies at their current positions, in get_points() order (nbody_external_potentials)."""
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        n = C.c_size_t(0)
+        phi = np.zeros(max(int(cfg.capacity), 1), np.float64)
+        self._check(lib.nbody_external_potentials(self._h, phi.ctypes.data, len(phi), C.byref(n)))
+        return phi[: n.value]
+
+    def external_energy(self) -> float:
+        """sum m_i phi_ext(x_i): the conserved total is KE + PE + this (energy() stays self-gravity only)."""
+        v = C.c_double(0)
+        self._check(lib.nbody_external_energy(self._h, C.byref(v)))
+        return float(v.value)
+
+    def external_at(self, points, acc: bool = True, phi: bool = True):
+        """(acc [M, 3] f64 | None, phi [M] f64 | None) of the external field alone at the M points (nbody_external_at)."""
+        xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+        m = len(xyz)
+        a = np.zeros((m, 3), np.float64) if acc else None
+        v = np.zeros(m, np.float64) if phi else None
+        self._check(lib.nbody_external_at(self._h, xyz.ctypes.data if m else None, m, a.ctypes.data if acc else None,
+                                          v.ctypes.data if phi else None))
+        return a, v
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

@@ -11,6 +11,7 @@
 #include "nbody_pot.h"
 #include "nbody_field.h"
 #include "nbody_tracer.h"
+#include "nbody_external.h"
 
 #include <algorithm>
 #include <chrono>
@@ -738,16 +739,19 @@ int step_begin(NbodyHandle* h, float dt) {
 
 // update_forces up to (not including) whatever needs other GPUs' partial sums
 int step_forces(NbodyHandle* h, float dt) {
-    h->kick_pending = true;   // a force pass that ends in a plane reduction applies the kick itself
+    // an external field: no pass takes the kick along (they run as nbody_update_forces runs them); step_finish adds the field's
+    // term to the finished accelerations and kicks
+    const bool fuse = !nbody::ext::on(h);
+    h->kick_pending = fuse;   // a force pass that ends in a plane reduction applies the kick itself
     h->kick_dt = dt;
     if (nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE) {
         // the tracers' force pass over the half-drifted, retained bodies, with the tracers' kick + half drift.  It reads the
         // bodies' positions and writes tracer state only, so it goes BEFORE the body pass, whose tail may move the bodies
-        int rc = nbody::tracer::forces(h, &h->kick_dt);
+        int rc = nbody::tracer::forces(h, fuse ? &h->kick_dt : nullptr);
         if (rc) { h->kick_pending = false; return rc; }
     }
     // (Barnes-Hut: the tracers walk the tree this pass builds, right after the bodies' walk: walk_tree)
-    h->tr.kick_pending = nbody::tracer::on(h);
+    h->tr.kick_pending = fuse && nbody::tracer::on(h);
     int rc = forces_begin(h);                                                  // update_forces
     h->tr.kick_pending = false;
     if (rc) { h->kick_pending = false; h->tail_pending = false; }
@@ -757,7 +761,11 @@ int step_forces(NbodyHandle* h, float dt) {
 int step_finish(NbodyHandle* h, float dt) {
     int rc = forces_finish(h);
     if (rc) { h->kick_pending = false; return rc; }
-    if (h->kick_pending) nbody::launch_kick_drift(h->stream, h->sh, int(h->n_local), dt);  // integrate_after_force
+    if (nbody::ext::on(h)) {   // acc += s(x) at the half-drifted, retained positions, then integrate_after_force, bodies and tracers
+        rc = nbody::ext::add(h, h->sh, h->n_local, h->g, &dt, true);
+        if (!rc && nbody::tracer::on(h)) rc = nbody::ext::add(h, h->tr.sh, h->tr.n_host, h->g, &dt, false);
+        if (rc) return rc;
+    } else if (h->kick_pending) nbody::launch_kick_drift(h->stream, h->sh, int(h->n_local), dt);  // integrate_after_force
     h->kick_pending = false;
     HIP_TRY(h, hipGetLastError());
     if (h->ev_pending.size() >= 4096) {  // profiling left on over a long run: fold the timings in now and then
@@ -1118,6 +1126,7 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
     rc = create_impl(&src->cfg, &h);
     if (rc) return rc;
     h->tune = src->tune;   // (the knobs shape the fast passes' sums: a clone continues bit for bit like its source)
+    h->ext = src->ext;     // (and the external field)
     if (src->f64) {
         rc = nbody64::clone_state(s, h);
         if (rc) { g_create_err = h->err; free_all(h); return rc; }
@@ -1320,11 +1329,95 @@ int nbody_update_forces(NbodyHandle* h) {
     if (rc) return rc;
     rc = forces(h);
     if (!rc && nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE) rc = nbody::tracer::forces(h, nullptr);   // (Barnes-Hut: inside the pass, walk_tree)
-    if (rc || !h->last_step_async) return rc;
-    h->last_step_async = false;
-    rc = resolve_async(h);              // (a force pass outside a step is confirmed at once)
-    if (rc || !h->host_tree_once) return rc;
-    return forces(h);                   // its build needed the host: once more, on the host-built tree
+    if (!rc && h->last_step_async) {
+        h->last_step_async = false;
+        rc = resolve_async(h);              // (a force pass outside a step is confirmed at once)
+        if (!rc && h->host_tree_once) rc = forces(h);   // its build needed the host: once more, on the host-built tree
+    }
+    if (rc || !nbody::ext::on(h)) return rc;
+    rc = nbody::ext::add<float>(h, h->sh, h->n_local, h->g, nullptr, false);   // acc += s(x), bodies and tracers
+    if (!rc && nbody::tracer::on(h)) rc = nbody::ext::add<float>(h, h->tr.sh, h->tr.n_host, h->g, nullptr, false);
+    return rc;
+}
+
+// ---- the static external field (nbody_external.cpp)
+namespace {
+// binds the device, refuses the handles that take no field, naming the entry point, and confirms the steps enqueued without a
+// read-back: they were asked for under the field as it stood, and the readers want the positions they produced
+int external_enter(NbodyHandle* h, const char* call) {
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (const char* why = nbody::ext::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return resolve_async(h);
+}
+double g_of(const NbodyHandle* h) {
+    double g = double(h->g);
+    if (h->f64) nbody64::get_settings(h, &g, nullptr, nullptr, nullptr);
+    return g;
+}
+// per body potentials (phi may be null) and sum m phi (energy may be null) at the current positions; *n_out = live bodies
+int external_potentials(NbodyHandle* h, bool want_phi, double* phi, size_t cap, size_t* n_out, double* energy, const char* call) {
+    size_t n = 0;
+    int rc = NBODY_OK;
+    if (h->f64) rc = nbody64::count(h, &n);
+    else { rc = h->sync_count(h, h->stream); n = h->n_local; }
+    if (rc) return rc;
+    if (n_out) *n_out = n;
+    if (want_phi && n > cap) return fail(h, NBODY_ERR_CAPACITY, std::string(call) + ": buffer too small");
+    if (want_phi && n && !phi) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": phi is NULL");
+    if (h->f64) return nbody::ext::potentials(h, nbody64::shard(h), n, g_of(h), phi, energy);
+    return nbody::ext::potentials(h, h->sh, n, g_of(h), phi, energy);
+}
+}  // namespace
+
+int nbody_set_external_field(NbodyHandle* h, const NbodyExternalComponent* comps, size_t n) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = external_enter(h, "nbody_set_external_field");
+    if (rc) return rc;
+    const std::string why = nbody::ext::invalid(comps, n, !h->f64);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, "nbody_set_external_field: " + why);
+    if (n > 0 && h->f64 && nbody64::get_integrator(h) == NBODY_INTEGRATOR_HERMITE4)
+        return fail(h, NBODY_ERR_INVALID, "nbody_set_external_field: the handle runs the Hermite integrator, which would need the field's jerk (out of scope)");
+    h->ext = ExternalField{};
+    h->ext.n = int(n);
+    std::copy(comps, comps + n, h->ext.given);
+    return NBODY_OK;
+}
+
+int nbody_get_external_field(const NbodyHandle* h, NbodyExternalComponent* comps, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    NbodyHandle* hh = const_cast<NbodyHandle*>(h);
+    if (const char* why = nbody::ext::refusal(h)) return fail(hh, NBODY_ERR_INVALID, std::string("nbody_get_external_field: ") + why);
+    const size_t n = size_t(h->ext.n);
+    if (n_out) *n_out = n;
+    if (n > cap) return fail(hh, NBODY_ERR_CAPACITY, "nbody_get_external_field: buffer too small");
+    if (n && !comps) return fail(hh, NBODY_ERR_INVALID, "nbody_get_external_field: comps is NULL");
+    std::copy(h->ext.given, h->ext.given + n, comps);
+    return NBODY_OK;
+}
+
+int nbody_external_potentials(NbodyHandle* h, double* phi, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = external_enter(h, "nbody_external_potentials");
+    if (rc) return rc;
+    return external_potentials(h, true, phi, cap, n_out, nullptr, "nbody_external_potentials");
+}
+
+int nbody_external_energy(NbodyHandle* h, double* potential) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = external_enter(h, "nbody_external_energy");
+    if (rc) return rc;
+    if (!potential) return fail(h, NBODY_ERR_INVALID, "nbody_external_energy: potential is NULL");
+    return external_potentials(h, false, nullptr, 0, nullptr, potential, "nbody_external_energy");
+}
+
+int nbody_external_at(NbodyHandle* h, const double* xyz, size_t n_points, double* acc, double* phi) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = external_enter(h, "nbody_external_at");
+    if (rc) return rc;
+    if (n_points > (size_t(1) << 30)) return fail(h, NBODY_ERR_INVALID, "nbody_external_at: n_points must not exceed 2^30");
+    if (!xyz && n_points > 0) return fail(h, NBODY_ERR_INVALID, "nbody_external_at: xyz is NULL");
+    return nbody::ext::at(h, g_of(h), xyz, n_points, acc, phi);
 }
 
 // ---- tracers (nbody_tracer.cpp)
@@ -1613,6 +1706,8 @@ int nbody_set_integrator(NbodyHandle* h, int integrator) {
                         : h->cfg.world_size != 1            ? "handles of a multi-rank world step with the leapfrog only"
                                                             : nullptr;
         if (why) return fail(h, NBODY_ERR_INVALID, std::string("nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): ") + why + " (brute-force NBODY_F64 handles with world_size == 1 take it)");
+        if (nbody::ext::on(h))
+            return fail(h, NBODY_ERR_INVALID, "nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): an external field is set, and the Hermite step would need its jerk (nbody_set_external_field with n == 0 removes it)");
     }
     if (!h->f64) return NBODY_OK;   // the leapfrog, which is all such a handle runs
     int rc = use_device(h);

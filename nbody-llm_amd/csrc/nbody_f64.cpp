@@ -9,6 +9,7 @@
 #include "nbody_f64.h"
 #include "kernels_f64.h"
 #include "kernels_hermite.h"
+#include "nbody_external.h"
 #include "nbody_pot.h"
 
 #include <algorithm>
@@ -530,11 +531,13 @@ int step_impl(NbodyHandle* h, State& s, double dt) {
     HIP_TRY(h, hipGetLastError());
     int rc = exchange(h, s);                                        // sharded: every block's positions and live count
     if (rc) return rc;
-    s.kick_dt = &dt; s.kicked = 0;                                  // (the fast walk's plane reduction can take the kick along)
+    const bool ext = nbody::ext::on(h);                             // an external field: the pass runs as update_forces does, then
+    s.kick_dt = ext ? nullptr : &dt; s.kicked = 0;                  // acc += s(x) with the kick (else the fast walk's plane reduction can take the kick along)
     rc = forces(h, s);                                              // update_forces
     s.kick_dt = nullptr;
     if (rc) return rc;
-    if (!s.kicked) launch_kick_drift(h->stream, s.sh, int(s.n_local), dt);   // integrate_after_force
+    if (ext) { rc = nbody::ext::add(h, s.sh, s.n_local, s.g, &dt, false); if (rc) return rc; }
+    else if (!s.kicked) launch_kick_drift(h->stream, s.sh, int(s.n_local), dt);   // integrate_after_force
     HIP_TRY(h, hipGetLastError());
     s.elapsed += dt;                                                // elapsed += dt
     h->stats.steps += 1;
@@ -703,7 +706,9 @@ int update_forces(NbodyHandle* h) {
     }
     int rc = exchange(h, s);
     if (rc) return rc;
-    return forces(h, s);
+    rc = forces(h, s);
+    if (!rc && nbody::ext::on(h)) rc = nbody::ext::add<double>(h, s.sh, s.n_local, s.g, nullptr, false);
+    return rc;
 }
 
 int set_integrator(NbodyHandle* h, int integrator) {   // (nbody_api.cpp has checked that the handle may run it)
@@ -806,6 +811,7 @@ int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, do
 }
 
 int get_integrator(const NbodyHandle* h) { return h->f64->integrator; }
+const nbody::ShardT<double>& shard(const NbodyHandle* h) { return h->f64->sh; }
 
 int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out) {
     State& s = *h->f64;

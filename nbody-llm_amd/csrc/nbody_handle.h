@@ -485,6 +485,13 @@ struct TracerState {
     bool kick_pending = false;   // a step's tracer walk takes the kick + half drift along (dt: NbodyHandle::kick_dt)
 };
 
+// nbody_set_external_field (nbody_external.cpp): the components as given (f64); a pass rounds them to its precision.  n == 0 (no
+// field) keeps every step path as it was.
+struct ExternalField {
+    int n = 0;
+    NbodyExternalComponent given[NBODY_EXTERNAL_MAX] = {};
+};
+
 struct NbodyHandle : BodyStore<float> {
     NbodyConfig cfg{};
     nbody::Tuning tune;        // this handle's launch-shape and scheme knobs (nbody_set_tuning; NBODY_* environment at create)
@@ -578,6 +585,7 @@ struct NbodyHandle : BodyStore<float> {
     PotBufs pot;
     FieldBufs field;
     TracerState tr;
+    ExternalField ext;
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;

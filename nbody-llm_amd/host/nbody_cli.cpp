@@ -10,7 +10,8 @@
 // hermite runs the device's fourth-order Hermite step (--method bf --dtype f64 only; leapfrog = device, the default); --dump FILE
 // writes the final PointParticle records; --multipole 2 adds the cells' quadrupole terms to the Barnes-Hut force walk;
 // --tracers M scatters M massless tracers in the workload's disc or sphere (the IC generator with seed + 1) and reports their
-// interactions per second on a line of its own.
+// interactions per second on a line of its own; --external KIND:p0:p1[...][:cx:cy:cz] (repeatable; plummer:M:b, hernquist:M:a,
+// mn:M:a:b, log:v0:rc:qy:qz) adds a component of a static external field and reports the external energy before and after.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,14 +29,42 @@ static void usage() {
                  "                 [--dtype f32|f64] [--dt x] [--g-soft x] [--theta2 x]\n"
                  "                 [--width w] [--seed s] [--integrator device|leapfrog|host|hermite] [--dump file] [--multipole 1|2]\n"
                  "                 [--block-steps ETA:LEVELS]   (with --integrator hermite: block individual time steps)\n"
-                 "                 [--tracers M]   (massless tracers in the same disc or sphere; --dtype f32)\n");
+                 "                 [--tracers M]   (massless tracers in the same disc or sphere; --dtype f32)\n"
+                 "                 [--external plummer:M:b[:cx:cy:cz] | hernquist:M:a[...] | mn:M:a:b[...] | log:v0:rc:qy:qz[...]]   (repeatable)\n");
+}
+
+// KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
+static bool parse_external(const char* arg, NbodyExternalComponent* out) {
+    static const struct { const char* name; int kind; int n_par; } kinds[] = {
+        {"plummer", NBODY_EXT_PLUMMER, 2}, {"hernquist", NBODY_EXT_HERNQUIST, 2}, {"mn", NBODY_EXT_MIYAMOTO_NAGAI, 3}, {"log", NBODY_EXT_LOGARITHMIC, 4}};
+    const char* colon = std::strchr(arg, ':');
+    if (!colon) return false;
+    const std::string name(arg, colon);
+    for (const auto& k : kinds) {
+        if (name != k.name) continue;
+        std::vector<double> v;
+        const char* at = colon;
+        while (*at == ':') {
+            char* end = nullptr;
+            v.push_back(std::strtod(at + 1, &end));
+            if (end == at + 1) return false;
+            at = end;
+        }
+        if (*at || (v.size() != size_t(k.n_par) && v.size() != size_t(k.n_par) + 3)) return false;
+        *out = NbodyExternalComponent{};
+        out->kind = k.kind;
+        for (int i = 0; i < k.n_par; ++i) out->p[i] = v[size_t(i)];
+        if (v.size() > size_t(k.n_par)) for (int i = 0; i < 3; ++i) out->center[i] = v[size_t(k.n_par + i)];
+        return true;
+    }
+    return false;
 }
 
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
-               double block_eta, int block_levels, size_t n_tracers) {
+               double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -66,8 +95,10 @@ static int run(const std::string& method, const std::string& ic, const std::stri
             else { tr.resize(n_tracers); if (nbody_ic_plummer(tr.data(), n_tracers, sizeof(tr[0]), seed + 1)) return 1; }
             sim->set_tracers(tr);
         }
+        if (!external.empty()) sim->set_external_field(external);   // (refused where it does not apply: nbody_hip.h)
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
+        const double ext_before = external.empty() ? 0.0 : sim->external_energy();
         auto start = std::chrono::steady_clock::now();
         if (integrator == "host") {   // the trait's generic Integrator, on the host (simulation.hpp step_by_with)
             nbody::LeapFrogIntegratorT<F> leapfrog;
@@ -87,6 +118,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
             sim->tracer_stats(ts);
             std::printf("Tracers left: %zu  tracer interactions/second: %.4e\n", sim->n_tracers(), double(ts[0]) / secs);
         }
+        if (!external.empty()) std::printf("External energy: %.9e -> %.9e\n", ext_before, sim->external_energy());
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -116,6 +148,7 @@ int main(int argc, char** argv) {
     int block_levels = 0;
     bool block_set = false;
     size_t n_tracers = 0;
+    std::vector<NbodyExternalComponent> external;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -136,6 +169,11 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
         else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
+        else if (!std::strcmp(argv[i], "--external")) {
+            NbodyExternalComponent c;
+            if (!parse_external(next(), &c)) { usage(); return 2; }
+            external.push_back(c);
+        }
         else if (!std::strcmp(argv[i], "--block-steps")) {
             char* end = nullptr;
             const char* arg = next();
@@ -156,7 +194,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--block-steps needs --integrator hermite\n");
         return 2;
     }
+    if (!external.empty() && integrator == "hermite") {
+        std::fprintf(stderr, "--external needs the leapfrog (the Hermite step would need the field's jerk)\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external);
 }

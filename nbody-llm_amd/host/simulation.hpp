@@ -204,6 +204,29 @@ public:
     }
     size_t n_tracers() { size_t n = 0; check(nbody_tracers_count(h_, &n)); return n; }
     void tracer_stats(uint64_t out[2]) { check(nbody_tracer_stats(h_, out)); }   // {directed interactions, opening tests}
+    // a static external field acting on bodies and tracers (nbody_set_external_field): at most NBODY_EXTERNAL_MAX components,
+    // an empty vector removes it; leapfrog handles of a one-rank world, every other handle throws NBODY_ERR_INVALID
+    void set_external_field(const std::vector<NbodyExternalComponent>& comps) {
+        check(nbody_set_external_field(h_, comps.data(), comps.size()));
+    }
+    std::vector<NbodyExternalComponent> external_field() const {
+        std::vector<NbodyExternalComponent> out(NBODY_EXTERNAL_MAX);
+        size_t n = 0;
+        check(nbody_get_external_field(h_, out.data(), out.size(), &n));
+        out.resize(n);
+        return out;
+    }
+    std::vector<double> external_potentials() {   // phi_ext per body, in get_points() order, f64
+        size_t n = 0;
+        check(nbody_count(h_, &n));
+        std::vector<double> out(n);
+        check(nbody_external_potentials(h_, out.data(), out.size(), &n));
+        out.resize(n);
+        return out;
+    }
+    // sum m_i phi_ext(x_i): the conserved total is KE + PE + this (nbody_energy stays self-gravity only)
+    double external_energy() { double v = 0; check(nbody_external_energy(h_, &v)); return v; }
+    void external_at(const double* xyz, size_t n, double* acc, double* phi) { push_settings(); check(nbody_external_at(h_, xyz, n, acc, phi)); }
     NbodyHandle* handle() { return h_; }
 
 protected:

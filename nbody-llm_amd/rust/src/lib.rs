@@ -46,6 +46,21 @@ pub struct NbodyHandle {
     _private: [u8; 0],
 }
 
+/// one component of a static external field (include/nbody_hip.h "external field"): kind NBODY_EXT_*, centre, parameters
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct NbodyExternalComponent {
+    pub kind: i32,
+    pub reserved: i32,
+    pub center: [f64; 3],
+    pub p: [f64; 4],
+}
+pub const NBODY_EXTERNAL_MAX: usize = 8;
+pub const NBODY_EXT_PLUMMER: i32 = 0;
+pub const NBODY_EXT_HERNQUIST: i32 = 1;
+pub const NBODY_EXT_MIYAMOTO_NAGAI: i32 = 2;
+pub const NBODY_EXT_LOGARITHMIC: i32 = 3;
+
 // edition 2024: extern blocks are `unsafe extern`; every item is unsafe to call
 unsafe extern "C" {
     fn nbody_create(cfg: *const NbodyConfig, out: *mut *mut NbodyHandle) -> c_int;
@@ -69,6 +84,12 @@ unsafe extern "C" {
     fn nbody_tree_export_cells(h: *mut NbodyHandle, min_max6: *mut f32, depth: *mut i32, cap: usize, n_nodes: *mut usize) -> c_int;
     fn nbody_set_tuning(h: *mut NbodyHandle, name: *const c_char, value: c_int) -> c_int;
     fn nbody_last_error(h: *const NbodyHandle) -> *const c_char;
+    fn nbody_set_external_field(h: *mut NbodyHandle, comps: *const NbodyExternalComponent, n: usize) -> c_int;
+    fn nbody_get_external_field(h: *const NbodyHandle, comps: *mut NbodyExternalComponent, cap: usize, n_out: *mut usize) -> c_int;
+    fn nbody_external_potentials(h: *mut NbodyHandle, phi: *mut f64, cap: usize, n_out: *mut usize) -> c_int;
+    fn nbody_external_energy(h: *mut NbodyHandle, potential: *mut f64) -> c_int;
+    fn nbody_external_at(h: *mut NbodyHandle, xyz: *const f64, n_points: usize, acc: *mut f64, phi: *mut f64) -> c_int;
+    fn nbody_host_external_eval(comps: *const NbodyExternalComponent, n: usize, g: f64, xyz: *const f64, n_points: usize, acc: *mut f64, phi: *mut f64) -> c_int;
 }
 
 pub const NBODY_BRUTE_FORCE: i32 = 0; // src/manual/brute_force.rs
