@@ -168,23 +168,35 @@ struct TreeDevWork {  // arrays of the last build (inside its workspace)
     const int* wpre = nullptr;                  // exclusive prefix sums of the bodies' weights over the sorted order (tree_scan_sorted with weights)
     const void* incl = nullptr;                 // inclusive f64 prefix sums {m, m x, m y, m z} over the sorted bodies (4 doubles each)
 };
-struct TreeCat {  // sharded runs: side buffer of the device build
-    float4* pos = nullptr;     // live bodies of all segments, concatenated in segment order
+struct TreeCatLists {  // sharded runs: side buffer of the device build, the part that does not depend on the position type
     int* flags = nullptr;
     int* base = nullptr;
     int* own_order = nullptr;  // own bodies in tree order, indices into the own segment
     int* info = nullptr;       // [0] total bodies, [1] first own body in the concatenation, [2] own count
 };
+template <class P4>   // float4 or double4 positions
+struct TreeCat : TreeCatLists {
+    P4* pos = nullptr;         // live bodies of all segments, concatenated in segment order
+};
 size_t tree_build_workspace_bytes(size_t n_cap);
 size_t tree_build_tmp_bytes(size_t n_cap);
-size_t tree_cat_bytes(size_t n_cap);
-TreeCat tree_cat_layout(void* buf, size_t n_cap);
-void launch_tree_cat(hipStream_t s, const Shard& sh, const TreeCat& c);
-// the same for F = f64 (double4 positions; the TreeCat's pos is unused)
-size_t tree_cat_bytes64(size_t n_cap);
-TreeCat tree_cat_layout64(void* buf, size_t n_cap, double4** pos_cat);
-void launch_tree_cat64(hipStream_t s, const double4* pos_all, const int* seg_count, int n_seg, int seg_cap, int my_seg, double4* pos_cat, int* info);
-int launch_tree_own_order(hipStream_t s, const int* order, const TreeCat& c, int n_total_upper, void* tmp, size_t tmp_bytes);
+// bytes and layout of the side buffer for n_cap bodies: positions | flags | base | own_order | info
+inline size_t tree_cat_align(size_t b) { return (b + 255) / 256 * 256; }
+template <class P4> size_t tree_cat_bytes(size_t n_cap) { return tree_cat_align(n_cap * sizeof(P4)) + 3 * tree_cat_align(n_cap * 4) + 256; }
+template <class P4>
+TreeCat<P4> tree_cat_layout(void* buf, size_t n_cap) {
+    char* p = static_cast<char*>(buf);
+    TreeCat<P4> c;
+    c.pos = reinterpret_cast<P4*>(p); p += tree_cat_align(n_cap * sizeof(P4));
+    c.flags = reinterpret_cast<int*>(p); p += tree_cat_align(n_cap * 4);
+    c.base = reinterpret_cast<int*>(p); p += tree_cat_align(n_cap * 4);
+    c.own_order = reinterpret_cast<int*>(p); p += tree_cat_align(n_cap * 4);
+    c.info = reinterpret_cast<int*>(p);
+    return c;
+}
+void launch_tree_cat(hipStream_t s, const Shard& sh, const TreeCat<float4>& c);
+void launch_tree_cat(hipStream_t s, const ShardT<double>& sh, const TreeCat<double4>& c);
+int launch_tree_own_order(hipStream_t s, const int* order, const TreeCatLists& c, int n_total_upper, void* tmp, size_t tmp_bytes);
 // The walk's node-range split points ride in the emit's launch as extra workgroups when the caller asks for them here
 // (unsynchronised single-shard steps: one launch of ~8 us less per step); n_split = 0: not wanted.
 struct TreeSplitReq { int n_split = 0; int* first = nullptr; int* n_anc = nullptr; int* anc = nullptr; int max_anc = 0; const int* info = nullptr; int* poison = nullptr; };
@@ -194,13 +206,13 @@ int build_octree_device(hipStream_t s, const float4* pos, const int* d_count, in
 // level-order copy of a pre-order node array for the cooperative block walk
 size_t bfs_workspace_bytes(size_t n_cap);
 int build_bfs_layout(hipStream_t s, const float4* nodes, int n_nodes, void* workspace, size_t n_cap, float4* out);
-// F = f64 (nbody_f64.cpp): double4 bodies, Node64 records (kernels_f64.h)
 }  // namespace nbody
 namespace nbody64 { struct Node64; }
 namespace nbody {
-int build_octree_device_f64(hipStream_t s, const double4* pos, const int* d_count, int n_upper, const double center[3], double width,
-                            void* workspace, size_t n_cap, nbody64::Node64* nodes, int node_cap, int* order, int* out_info,
-                            TreeDevWork* work, const TreeSplitReq* split = nullptr);
+// build_octree_device for F = f64 (nbody_f64.cpp): double4 bodies, Node64 records (kernels_f64.h); want_hot is ignored
+int build_octree_device(hipStream_t s, const double4* pos, const int* d_count, int n_upper, const double center[3], double width,
+                        void* workspace, size_t n_cap, nbody64::Node64* nodes, int node_cap, int* order, int* out_info,
+                        TreeDevWork* work, int want_hot = 0, const TreeSplitReq* split = nullptr);
 // the build in two halves (spatial shards need the sorted keys of all ranks' ends before the second one)
 int tree_sort_keys(hipStream_t s, const float4* pos, const int* d_count, int n_upper, const float center[3], float width,
                    void* workspace, size_t n_cap, int* out_info, TreeDevWork* work);

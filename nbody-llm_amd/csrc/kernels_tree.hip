@@ -734,9 +734,9 @@ int build_octree_device(hipStream_t s, const float4* pos, const int* d_count, in
 }
 // The same for F = f64: keys from the reference's recurrences in double, centres of mass from the same f64 prefix sums
 // (against the reference's sequential f64 folds they differ in the last bits only), 64-byte node records.
-int build_octree_device_f64(hipStream_t s, const double4* pos, const int* d_count, int n_upper, const double center[3], double width,
-                            void* workspace, size_t n_cap, nbody64::Node64* nodes, int node_cap, int* order, int* out_info,
-                            TreeDevWork* work, const TreeSplitReq* split) {
+int build_octree_device(hipStream_t s, const double4* pos, const int* d_count, int n_upper, const double center[3], double width,
+                        void* workspace, size_t n_cap, nbody64::Node64* nodes, int node_cap, int* order, int* out_info,
+                        TreeDevWork* work, int /* want_hot */, const TreeSplitReq* split) {
     if (sort_keys_t<double4, double>(s, pos, d_count, n_upper, center, width, workspace, n_cap, out_info, work) != 0) return -1;
     if (scan_sorted_t<double4>(s, pos, d_count, n_upper, workspace, n_cap, out_info, nullptr, nullptr) != 0) return -1;
     return emit_nodes_t<double4, double, nbody64::Node64>(s, pos, d_count, width, workspace, n_cap, nodes, node_cap, node_cap, order, out_info, 0,
@@ -886,54 +886,21 @@ int tracer_sort(hipStream_t s, const float4* pos, const int* d_count, int n_uppe
 // bytes at the start of the build workspace that rocPRIM uses as scratch (free between builds)
 size_t tree_build_tmp_bytes(size_t n_cap) { return scratch_bytes(n_cap); }
 
-// sharded runs: bytes of the side buffer (concatenated positions, own-order flags/offsets/list, info)
-size_t tree_cat_bytes(size_t n_cap) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    return al(n_cap * sizeof(float4)) + 3 * al(n_cap * 4) + 256;
+// sharded runs: the side buffer's layout is kernels.h tree_cat_layout<P4>
+void launch_tree_cat(hipStream_t s, const ShardT<double>& sh, const TreeCat<double4>& c) {
+    const int slots = sh.n_seg * sh.seg_cap;
+    hipLaunchKernelGGL(k_tree_cat64, dim3((slots + 255) / 256), dim3(256), 0, s, sh.pos_all, sh.seg_count, sh.n_seg, sh.seg_cap,
+                       sh.my_seg, c.pos, c.info);
 }
 
-TreeCat tree_cat_layout(void* buf, size_t n_cap) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    char* p = static_cast<char*>(buf);
-    TreeCat c;
-    c.pos = reinterpret_cast<float4*>(p); p += al(n_cap * sizeof(float4));
-    c.flags = reinterpret_cast<int*>(p); p += al(n_cap * 4);
-    c.base = reinterpret_cast<int*>(p); p += al(n_cap * 4);
-    c.own_order = reinterpret_cast<int*>(p); p += al(n_cap * 4);
-    c.info = reinterpret_cast<int*>(p);
-    return c;
-}
-
-// F = f64: the side buffer holds double4 positions (tree_cat_bytes64); flags / base / own_order / info as in TreeCat (pos unused)
-size_t tree_cat_bytes64(size_t n_cap) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    return al(n_cap * sizeof(double4)) + 3 * al(n_cap * 4) + 256;
-}
-TreeCat tree_cat_layout64(void* buf, size_t n_cap, double4** pos_cat) {
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    char* p = static_cast<char*>(buf);
-    TreeCat c;
-    *pos_cat = reinterpret_cast<double4*>(p); p += al(n_cap * sizeof(double4));
-    c.pos = nullptr;
-    c.flags = reinterpret_cast<int*>(p); p += al(n_cap * 4);
-    c.base = reinterpret_cast<int*>(p); p += al(n_cap * 4);
-    c.own_order = reinterpret_cast<int*>(p); p += al(n_cap * 4);
-    c.info = reinterpret_cast<int*>(p);
-    return c;
-}
-void launch_tree_cat64(hipStream_t s, const double4* pos_all, const int* seg_count, int n_seg, int seg_cap, int my_seg, double4* pos_cat, int* info) {
-    const int slots = n_seg * seg_cap;
-    hipLaunchKernelGGL(k_tree_cat64, dim3((slots + 255) / 256), dim3(256), 0, s, pos_all, seg_count, n_seg, seg_cap, my_seg, pos_cat, info);
-}
-
-void launch_tree_cat(hipStream_t s, const Shard& sh, const TreeCat& c) {
+void launch_tree_cat(hipStream_t s, const Shard& sh, const TreeCat<float4>& c) {
     const int slots = sh.n_seg * sh.seg_cap;
     hipLaunchKernelGGL(k_tree_cat, dim3((slots + 255) / 256), dim3(256), 0, s, sh.pos_all, sh.seg_count, sh.n_seg, sh.seg_cap,
                        sh.my_seg, c.pos, c.info);
 }
 
 // own bodies in tree order, as indices into the own segment (tmp: the build's workspace, free again)
-int launch_tree_own_order(hipStream_t s, const int* order, const TreeCat& c, int n_total_upper, void* tmp, size_t tmp_bytes) {
+int launch_tree_own_order(hipStream_t s, const int* order, const TreeCatLists& c, int n_total_upper, void* tmp, size_t tmp_bytes) {
     if (n_total_upper <= 0) return 0;
     const dim3 grid((n_total_upper + 255) / 256), block(256);
     hipLaunchKernelGGL(k_tree_own_flags, grid, block, 0, s, order, c.info, c.flags);

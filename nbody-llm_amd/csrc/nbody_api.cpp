@@ -308,11 +308,6 @@ int bf_forces(NbodyHandle* h) {
     return NBODY_OK;
 }
 
-int ensure_tree_dev(NbodyHandle* h, size_t nodes, size_t order) {
-    int rc = grow_dev(h, h->d_nodes, h->d_node_cap, nodes, sizeof(nbody::NodeRec));
-    return rc ? rc : grow_dev(h, h->d_order, h->d_order_cap, order, sizeof(int));
-}
-
 // BarnesHutSimulation::update_forces (barnes_hut.rs:250-263): rebuild the tree from the current
 // positions, then one walk per body.
 int bh_walk_device_tree(NbodyHandle* h, bool* fell_back);
@@ -323,23 +318,14 @@ int resolve_async(NbodyHandle* h);
 int step_end(NbodyHandle* h, float dt);
 int step_impl(NbodyHandle* h, float dt);
 
-// strict math with the reference leaf rule walks with the reference's nested sums (bit-exact): per own body a stack
-// of the open cells on its path, 16 bytes each -- as many levels as the tree is deep (the device build stops at 42;
-// the host build reports its depth), not NBODY_MAX_TREE_DEPTH of them (13 GB at N = 2^22)
-int ensure_nested_stack(NbodyHandle* h, nbody::TreeDev* td) {
+// strict math with the reference leaf rule walks with the reference's nested sums (bit-exact): the store's per-lane stack, as
+// many levels as the last tree is deep (the device build goes to 42; the host build reports its depth)
+int setup_nested_walk(NbodyHandle* h, nbody::TreeDev* td) {
     if (h->cfg.math_mode != NBODY_MATH_STRICT || h->cfg.leaf_mode != NBODY_LEAF_REFERENCE) return NBODY_OK;
-    const size_t lanes = (size_t(h->sh.seg_cap) + 255) / 256 * 256;
-    const int levels = (h->tree_on_device ? 43 : h->tree.max_depth) + 2;   // (the device build goes to 42 levels)
-    if (lanes > h->nested_cap || levels > h->nested_levels) {
-        if (h->d_nested_stack) (void)hipFree(h->d_nested_stack);
-        h->d_nested_stack = nullptr; h->nested_cap = 0; h->nested_levels = 0;
-        const int lv = std::max(levels + 8, 32);
-        HIP_TRY(h, hipMalloc(&h->d_nested_stack, lanes * size_t(lv) * sizeof(float4)));
-        h->nested_cap = lanes;
-        h->nested_levels = lv;
-    }
-    td->nested_stack = h->d_nested_stack;
-    td->nested_stride = h->nested_cap;
+    int rc = h->tree.ensure_stack(h, h->sh.seg_cap, (h->tree.on_device ? 43 : h->tree.host.max_depth) + 2);
+    if (rc) return rc;
+    td->nested_stack = h->tree.d_stack;
+    td->nested_stride = h->tree.stack_lanes;
     return NBODY_OK;
 }
 
@@ -351,27 +337,27 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
     return NBODY_OK;
 #else
     // (its stack holds the 42 levels of the device build; a deeper host-built tree is walked by k_bh_walk)
-    if (h->cfg.math_mode == NBODY_MATH_FAST && nbody::tuning().bh_walk_variant == 5 && (h->tree_on_device || h->tree.max_depth <= 42)) {
-        if (h->bfs_cap < h->d_node_cap) {
+    if (h->cfg.math_mode == NBODY_MATH_FAST && nbody::tuning().bh_walk_variant == 5 && (h->tree.on_device || h->tree.host.max_depth <= 42)) {
+        if (h->bfs_cap < h->tree.node_cap) {
             if (h->d_bfs) (void)hipFree(h->d_bfs);
             if (h->d_bfs_ws) (void)hipFree(h->d_bfs_ws);
             h->d_bfs = nullptr; h->d_bfs_ws = nullptr; h->bfs_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_bfs, h->d_node_cap * 2 * sizeof(float4)));
-            HIP_TRY(h, hipMalloc(&h->d_bfs_ws, nbody::bfs_workspace_bytes(h->d_node_cap)));
-            h->bfs_cap = h->d_node_cap;
+            HIP_TRY(h, hipMalloc(&h->d_bfs, h->tree.node_cap * 2 * sizeof(float4)));
+            HIP_TRY(h, hipMalloc(&h->d_bfs_ws, nbody::bfs_workspace_bytes(h->tree.node_cap)));
+            h->bfs_cap = h->tree.node_cap;
         }
         td->bfs = h->d_bfs; td->bfs_ws = h->d_bfs_ws; td->bfs_cap = h->bfs_cap;
         return NBODY_OK;
     }
     if (h->cfg.math_mode != NBODY_MATH_FAST || nbody::tuning().bh_walk_variant != 3 || nbody::tuning().bh_hot_cap <= 0) return NBODY_OK;
     const int M = std::min(nbody::tuning().bh_hot_cap, 5000);  // 160 KB of LDS per CU, 32 B per record
-    if (h->walk_cap < h->d_node_cap) {
+    if (h->walk_cap < h->tree.node_cap) {
         if (h->d_walk) (void)hipFree(h->d_walk);
         if (h->d_unified) (void)hipFree(h->d_unified);
         h->d_walk = nullptr; h->d_unified = nullptr; h->walk_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_walk, (h->d_node_cap + 1) * 2 * sizeof(float4)));
-        HIP_TRY(h, hipMalloc(&h->d_unified, (h->d_node_cap + 1) * sizeof(int)));
-        h->walk_cap = h->d_node_cap;
+        HIP_TRY(h, hipMalloc(&h->d_walk, (h->tree.node_cap + 1) * 2 * sizeof(float4)));
+        HIP_TRY(h, hipMalloc(&h->d_unified, (h->tree.node_cap + 1) * sizeof(int)));
+        h->walk_cap = h->tree.node_cap;
     }
     if (h->hot_cap != M) {
         if (h->d_hot) (void)hipFree(h->d_hot);
@@ -405,10 +391,10 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
 // the cells' tensors from the node array as it now stands on the device (k_tree_quad), for the walk that follows
 // (sized like the node array: a step without read-back knows its capacity only, and the build's node count on the device)
 int fill_quadrupoles(NbodyHandle* h, const nbody::TreeDev& td, bool any_nodes) {
-    int rc = grow_dev(h, h->d_quad, h->quad_cap, h->d_node_cap, nbody::kQuadRecBytes);
+    int rc = grow_dev(h, h->d_quad, h->quad_cap, h->tree.node_cap, nbody::kQuadRecBytes);
     if (rc) return rc;
     const bool counted_on_device = td.n_order_dev != nullptr;
-    if (any_nodes) nbody::launch_tree_quad(h->stream, td.nodes, td.n_nodes, h->d_quad, counted_on_device ? h->tree_bufs.d_info : nullptr, td.poison);
+    if (any_nodes) nbody::launch_tree_quad(h->stream, td.nodes, td.n_nodes, h->d_quad, counted_on_device ? h->tree.bufs.d_info : nullptr, td.poison);
     return NBODY_OK;
 }
 
@@ -456,7 +442,7 @@ int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
         HIP_TRY(h, hipGetLastError());
         return nbody::tracer::tree_forces(h, td);   // (tracers walk monopoles whatever the multipole setting)
     }
-    int rc = ensure_nested_stack(h, &td);
+    int rc = setup_nested_walk(h, &td);
     if (!rc) rc = setup_lds_walk(h, &td, n_tree);
     if (rc) return rc;
     {
@@ -470,6 +456,20 @@ int walk_tree(NbodyHandle* h, nbody::TreeDev& td, size_t n_tree) {
     if (td.hot_cap > 0) HIP_TRY(h, hipMemcpyAsync(h->h_hot_info, h->d_hot_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipGetLastError());
     return nbody::tracer::tree_forces(h, td);   // the tracers' walk of the same tree, before anything overwrites it
+}
+
+// segments of the walk over the tree just built (a field call walks its probes, not the bodies)
+int split_segments(const NbodyHandle* h, const TreeBuilt& t) {
+    if (h->pot.walking == kWalkField) return field_split_plan(h->field.n_points, size_t(t.n_nodes));
+    return walk_split_plan(t.n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, size_t(t.n_nodes)).segments;
+}
+// the walk over it, once the split points of its K segments are listed
+int walk_built(NbodyHandle* h, const TreeBuilt& t, int K) {
+    nbody::TreeDev td;
+    td.nodes = h->tree.d_nodes; td.n_nodes = t.n_nodes;
+    td.order = t.order; td.n_order = int(t.n_order);
+    walk_split_view(h->tree.split, K, size_t(h->sh.seg_cap), &td);
+    return walk_tree(h, td, t.n_tree);
 }
 
 int bh_forces(NbodyHandle* h) {
@@ -496,95 +496,32 @@ int bh_forces(NbodyHandle* h) {
 // the force pass on the tree built on the host
 int bh_walk_host_tree(NbodyHandle* h) {
     Shard& sh = h->sh;
-    h->tree_on_device = false;
-    HostTreePass<float, float4> pass{reinterpret_cast<const float*>(sh.pos_all), sh.seg_count, sh.n_seg, sh.seg_cap, sh.my_seg, h->h_pos,
-                                     h->h_counts, h->seg_count_host, h->n_local, h->count_dirty, h->center, h->width, h->tree,
-                                     h->tree_scratch, h->own_order, h->d_nodes, h->d_node_cap, h->d_order, h->d_order_cap};
-    int rc = pass.run(h);
+    TreeBuilt t;
+    int rc = h->tree.build_on_host(h, *h, &t);
     if (rc) return rc;
     // split the node range over several waves per body group when there are too few bodies to fill the chip (>= 8 waves per
     // SIMD wanted: the walk is bound by the latency of dependent loads).  ~3 waves per wave slot of the chip (256 CUs x 32),
     // handed out heaviest first (nbody::tuning().bh_walk_order): the launch lasts as long as its slowest wave, and smaller
     // pieces started in the right order shorten that tail (N = 65 536: 24 segments 0.310 ms, 8 segments 0.336 ms; tools/tune_bh_order.py)
-    const int K = h->pot.walking == kWalkField ? field_split_plan(h->field.n_points, h->tree.n_nodes)   // (a field call walks its probes, not the bodies)
-                  : walk_split_plan(pass.n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, h->tree.n_nodes).segments;
-    rc = h->split.ensure(h, K, size_t(sh.seg_cap));
-    if (!rc) rc = h->split.list_on_host(h, h->stream, h->tree.nodes, int(h->tree.n_nodes), K);
+    const int K = split_segments(h, t);
+    rc = h->tree.split.ensure(h, K, size_t(sh.seg_cap));
+    if (!rc) rc = h->tree.split.list_on_host(h, h->stream, h->tree.host.nodes, t.n_nodes, K);
     if (rc) return rc;
-    nbody::TreeDev td;
-    td.nodes = h->d_nodes; td.n_nodes = int(h->tree.n_nodes);
-    td.order = h->d_order; td.n_order = int(pass.n_order);
-    walk_split_view(h->split, K, size_t(sh.seg_cap), &td);
-    return walk_tree(h, td, h->tree.n_order);
+    return walk_built(h, t, K);
 }
 
 // Barnes-Hut force pass with the octree built on the device (kernels_tree.hip): no positions go to
 // the host, no node array comes back; one 8-byte read-back (node count, flags) per step.
 int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
-    Shard& sh = h->sh;
-    auto t1 = clk::now();
-    const bool sharded = sh.n_seg > 1;
-    const size_t n_cap = size_t(sh.seg_cap) * sh.n_seg;  // the tree holds the bodies of every segment
-    TreeBuildBufs& tb = h->tree_bufs;
-    int rc = tb.ensure(h, n_cap, sharded ? nbody::tree_cat_bytes(n_cap) : 0);
+    TreeBuilt t;
+    int rc = h->tree.build_on_device(h, *h, nbody::tuning().bh_walk_variant == 3, nullptr, &t);
+    *fell_back = t.fell_back;
+    if (rc || t.fell_back) return rc;
+    const int K = split_segments(h, t);
+    rc = h->tree.split.ensure(h, K, size_t(h->sh.seg_cap));
     if (rc) return rc;
-    const size_t tot_upper = total_upper(h);
-    // a Plummer sphere gives ~1.5 nodes per body; 4 per body + the count read-back below catch the rest
-    rc = ensure_tree_dev(h, std::max<size_t>(h->d_node_cap, 4 * tot_upper + 64), tot_upper);
-    if (rc) return rc;
-    nbody::TreeCat cat;
-    const float4* tree_pos = sh.own_pos();
-    const int* tree_count = sh.own_count();
-    if (sharded) {  // every GPU builds the same tree over the gathered bodies of all segments
-        cat = nbody::tree_cat_layout(tb.cat, n_cap);
-        nbody::launch_tree_cat(h->stream, sh, cat);
-        tree_pos = cat.pos;
-        tree_count = cat.info;
-    }
-    nbody::TreeDevWork work;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (nbody::build_octree_device(h->stream, tree_pos, tree_count, int(tot_upper), h->center, h->width,
-                                       tb.ws, n_cap, h->d_nodes, int(h->d_node_cap), h->d_order, tb.d_info,
-                                       &work, nbody::tuning().bh_walk_variant == 3) != 0)
-            return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipMemcpyAsync(tb.h_info, tb.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (sharded)
-            HIP_TRY(h, hipMemcpyAsync(h->h_counts, sh.seg_count, sizeof(int) * sh.n_seg, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (!sharded) h->h_counts[0] = tb.h_info[2];  // one shard: the tree's body count is the live count
-        if (!(tb.h_info[1] & 2)) break;
-        rc = ensure_tree_dev(h, size_t(tb.h_info[0]) + 64, tot_upper);  // more nodes than allowed for: grow, rebuild
-        if (rc) return rc;
-    }
-    for (int s = 0; s < sh.n_seg; ++s) h->seg_count_host[s] = h->h_counts[s];
-    h->n_local = size_t(h->h_counts[sh.my_seg]);
-    h->count_dirty = false;
-    if (tb.h_info[1] & 5) { *fell_back = true; return NBODY_OK; }   // deeper than 42 levels / a clump beyond the build's sort: host build
-    const int n_nodes = tb.h_info[0];
-    const size_t n_order = h->n_local;             // bodies this GPU walks
-    const size_t n_tree = total_upper(h);          // bodies in the tree (now exact)
-    const int* d_walk_order = h->d_order;
-    if (sharded) {
-        if (nbody::launch_tree_own_order(h->stream, h->d_order, cat, int(n_tree), tb.ws, nbody::tree_build_tmp_bytes(n_cap)) != 0)
-            return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
-        d_walk_order = cat.own_order;
-    }
-    h->stats.tree_build_ms += ms_since(t1);
-    h->stats.tree_nodes = uint64_t(n_nodes);
-    h->tree_on_device = true;
-    h->tree.n_nodes = size_t(n_nodes);  // (the host copy is filled on demand by nbody_tree_export)
-
-    const int K = h->pot.walking == kWalkField ? field_split_plan(h->field.n_points, size_t(n_nodes))   // (a field call walks its probes, not the bodies)
-                  : walk_split_plan(n_order, h->cfg.math_mode != NBODY_MATH_STRICT || h->pot.walking, h->theta2, size_t(n_nodes)).segments;
-    rc = h->split.ensure(h, K, size_t(sh.seg_cap));
-    if (rc) return rc;
-    if (n_tree > 0) h->split.list_on_device(h->stream, work, int(n_tree), n_nodes, K);
-    nbody::TreeDev td;
-    td.nodes = h->d_nodes; td.n_nodes = n_nodes;
-    td.order = d_walk_order; td.n_order = int(n_order);
-    walk_split_view(h->split, K, size_t(sh.seg_cap), &td);
-    return walk_tree(h, td, n_tree);
+    if (t.n_tree > 0) h->tree.split.list_on_device(h->stream, h->tree.work, int(t.n_tree), t.n_nodes, K);
+    return walk_built(h, t, K);
 }
 
 // The same force pass with nothing read back: the node count, the live body count and the build's flags stay on the
@@ -593,34 +530,34 @@ int bh_walk_device_tree(NbodyHandle* h, bool* fell_back) {
 int bh_walk_device_tree_async(NbodyHandle* h) {
     Shard& sh = h->sh;
     auto t1 = clk::now();
-    TreeBuildBufs& tb = h->tree_bufs;
+    TreeBuildBufs& tb = h->tree.bufs;
     int rc = tb.ensure(h, size_t(sh.seg_cap), 0);
     if (rc) return rc;
     const size_t n_upper = h->n_local;   // an upper bound of the live count
-    rc = ensure_tree_dev(h, std::max<size_t>(h->d_node_cap, 4 * n_upper + 64), n_upper);
+    rc = h->tree.ensure_dev(h, TreeTypes<float>::kNodesPerBody * n_upper + 64, n_upper);
     if (rc) return rc;
     if (h->pending.empty()) HIP_TRY(h, hipMemsetAsync(h->d_poison + 1, 0, sizeof(int), h->stream));   // steps completed: counted from here
     // (a tree has at least as many nodes as bodies)
     const int K = walk_split_plan(n_upper, h->cfg.math_mode != NBODY_MATH_STRICT, h->theta2, n_upper).segments;
-    rc = h->split.ensure(h, K, size_t(sh.seg_cap));
+    rc = h->tree.split.ensure(h, K, size_t(sh.seg_cap));
     if (rc) return rc;
     // the walk's split points ride in the build's last launch (they also make a build that needs the host sticky: Shard::poison)
-    const nbody::TreeSplitReq req = h->split.request(K, tb.d_info, h->d_poison);
-    nbody::TreeDevWork work;
+    const nbody::TreeSplitReq req = h->tree.split.request(K, tb.d_info, h->d_poison);
+    nbody::TreeDevWork& work = h->tree.work;
     if (nbody::build_octree_device(h->stream, sh.own_pos(), sh.own_count(), int(n_upper), h->center, h->width, tb.ws, size_t(sh.seg_cap),
-                                   h->d_nodes, int(h->d_node_cap), h->d_order, tb.d_info, &work, 0, n_upper > 0 ? &req : nullptr) != 0)
+                                   h->tree.d_nodes, int(h->tree.node_cap), h->tree.d_order, tb.d_info, &work, 0, n_upper > 0 ? &req : nullptr) != 0)
         return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
     HIP_TRY(h, hipGetLastError());
     h->stats.tree_build_ms += ms_since(t1);   // (enqueue time: nothing is waited for)
-    h->tree_on_device = true;
+    h->tree.on_device = true;
     if (n_upper == 0)   // (no build was enqueued: the empty root's one segment, as a launch of its own)
-        h->split.list_on_device(h->stream, work, 0, int(h->d_node_cap), K, tb.d_info, h->d_poison);
+        h->tree.split.list_on_device(h->stream, work, 0, int(h->tree.node_cap), K, tb.d_info, h->d_poison);
     nbody::TreeDev td;
-    td.nodes = h->d_nodes; td.n_nodes = int(h->d_node_cap);   // (the plain walks end at the split points, not at n_nodes)
-    td.order = h->d_order; td.n_order = int(n_upper);
+    td.nodes = h->tree.d_nodes; td.n_nodes = int(h->tree.node_cap);   // (the plain walks end at the split points, not at n_nodes)
+    td.order = h->tree.d_order; td.n_order = int(n_upper);
     td.n_order_dev = tb.d_info + 2;
     td.poison = h->d_poison;
-    walk_split_view(h->split, K, size_t(sh.seg_cap), &td);
+    walk_split_view(h->tree.split, K, size_t(sh.seg_cap), &td);
     rc = walk_tree(h, td, n_upper);
     if (rc) return rc;
     h->last_step_async = true;
@@ -634,11 +571,11 @@ int resolve_async(NbodyHandle* h) {
     if (!h->async_bh) return NBODY_OK;
     for (int round = 0; round < 1000000; ++round) {
         HIP_TRY(h, hipMemcpyAsync(h->h_poison, h->d_poison, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (h->tree_bufs.d_info) HIP_TRY(h, hipMemcpyAsync(h->h_poison + 2, h->tree_bufs.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (h->tree.bufs.d_info) HIP_TRY(h, hipMemcpyAsync(h->h_poison + 2, h->tree.bufs.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         const int flags = h->h_poison[0], done = h->h_poison[1];
         if (!flags) {
-            if (h->tree_on_device && h->tree_bufs.d_info) {   // what the last build produced
+            if (h->tree.on_device && h->tree.bufs.d_info) {   // what the last build produced
                 h->tree.n_nodes = size_t(h->h_poison[2]);
                 h->stats.tree_nodes = uint64_t(h->h_poison[2]);
             }
@@ -651,7 +588,7 @@ int resolve_async(NbodyHandle* h) {
         h->pending.clear();
         HIP_TRY(h, hipMemsetAsync(h->d_poison, 0, 2 * sizeof(int), h->stream));
         if (flags & 2) {   // more nodes than the array holds: double it (the bound 4 n + 64 did not hold for this set)
-            int rc = ensure_tree_dev(h, 2 * h->d_node_cap + 64, h->n_local);
+            int rc = h->tree.ensure_dev(h, 2 * h->tree.node_cap + 64, h->n_local);
             if (rc) return rc;
         }
         if (rest.empty()) {   // it was a force pass outside a step (nbody_update_forces): its caller runs it again
@@ -954,17 +891,15 @@ void free_all(NbodyHandle* h) {
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     for (auto& ev : h->ev_pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto& ev : h->ev_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    h->tree.clear();
+    h->tree.release();
     nbody64::destroy(h);
     nbody::let::destroy(h);
     nbody::tracer::release(h);
     h->release();
-    void* dev[] = {h->d_poison, h->d_nodes, h->d_order, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_nested_stack, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
+    void* dev[] = {h->d_poison, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {h->h_pos, h->h_counters, h->h_hot_info, h->h_poison};
+    void* host[] = {h->h_counters, h->h_hot_info, h->h_poison};
     for (void* p : host) if (p) (void)hipHostFree(p);
-    h->split.release();
-    h->tree_bufs.release();
     h->pot.release();
     h->field.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1062,9 +997,8 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
     CREATE_TRY(hipMalloc(&h->d_poison, 2 * sizeof(int)));
     CREATE_TRY(hipMemsetAsync(h->d_poison, 0, 2 * sizeof(int), h->stream));
     if (cfg->method == NBODY_BARNES_HUT) {
-        h->tree.alloc = pinned_alloc;
-        h->tree.release = pinned_free;
-        CREATE_TRY(hipHostMalloc(&h->h_pos, size_t(sh.n_seg) * size_t(sh.seg_cap) * sizeof(float4), hipHostMallocDefault));
+        int rc = h->tree.alloc_host(h, sh);
+        if (rc) return bail(rc);
     }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
@@ -1632,7 +1566,7 @@ int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* sk
     if (h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "not a Barnes-Hut handle");
     if (h->f64) {
         if (com_mass || width) return fail(h, NBODY_ERR_INVALID, "f64 handle: use nbody_tree_export_f64");
-        return nbody64::tree_export(h, nullptr, nullptr, skip, cap, n_nodes);
+        return nbody_tree_export_f64(h, nullptr, nullptr, skip, cap, n_nodes);
     }
     if (h->let)   // (a spatial rank holds its slice and what it imported, never the whole tree)
         return fail(h, NBODY_ERR_INVALID, "nbody_tree_export is not supported on NBODY_SHARD_SPATIAL handles");
@@ -1642,24 +1576,7 @@ int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* sk
         rc = resolve_async(h);
         if (rc) return rc;
     }
-    const size_t n = h->tree.n_nodes;
-    if (n_nodes) *n_nodes = n;
-    if (!com_mass && !width && !skip) return NBODY_OK;
-    if (h->tree_on_device) {  // the octree lives on the device only: fetch it
-        int rc = use_device(h);
-        if (rc) return rc;
-        h->tree.reserve(n, 0);
-        HIP_TRY(h, hipMemcpyAsync(h->tree.nodes, h->d_nodes, n * sizeof(nbody::NodeRec), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "tree export buffer too small");
-    for (size_t i = 0; i < n; ++i) {
-        const nbody::NodeRec& r = h->tree.nodes[i];
-        if (com_mass) { com_mass[4 * i] = r.a.x; com_mass[4 * i + 1] = r.a.y; com_mass[4 * i + 2] = r.a.z; com_mass[4 * i + 3] = r.a.m; }
-        if (width) width[i] = std::sqrt(r.b.w2);  // exact: w2 is the rounded square of the width
-        if (skip) skip[i] = r.b.skip;
-    }
-    return NBODY_OK;
+    return h->tree.export_nodes(h, com_mass, width, skip, cap, n_nodes);
 }
 
 namespace {
@@ -1789,9 +1706,9 @@ int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t*
     if (n == 0) return NBODY_OK;
     // of the tree nbody_tree_export reports: the node array as it stands on the device (a tree call of nbody_potentials or
     // nbody_field_at since the force pass has rebuilt it), through the kernel the force pass runs
-    rc = grow_dev(h, h->d_quad, h->quad_cap, std::max(n, h->d_node_cap), nbody::kQuadRecBytes);
+    rc = grow_dev(h, h->d_quad, h->quad_cap, std::max(n, h->tree.node_cap), nbody::kQuadRecBytes);
     if (rc) return rc;
-    nbody::launch_tree_quad(h->stream, h->d_nodes, int(n), h->d_quad, nullptr, nullptr);
+    nbody::launch_tree_quad(h->stream, h->tree.d_nodes, int(n), h->d_quad, nullptr, nullptr);
     HIP_TRY(h, hipGetLastError());
     std::vector<float> rec(8 * n);
     HIP_TRY(h, hipMemcpyAsync(rec.data(), h->d_quad, n * nbody::kQuadRecBytes, hipMemcpyDeviceToHost, h->stream));
@@ -1805,7 +1722,8 @@ int nbody_tree_export_f64(NbodyHandle* h, double* com_mass, double* width, int32
     if (!h) return NBODY_ERR_INVALID;
     if (h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "not a Barnes-Hut handle");
     if (!h->f64) return fail(h, NBODY_ERR_INVALID, "f32 handle: use nbody_tree_export");
-    return nbody64::tree_export(h, com_mass, width, skip, cap, n_nodes);
+    int rc = use_device(h);
+    return rc ? rc : nbody64::tree_export(h, com_mass, width, skip, cap, n_nodes);
 }
 
 // ---- the cells of the last tree, for drawing (the reference's Barnes-Hut Renderable walks every node's bounds,

@@ -19,28 +19,11 @@
 namespace nbody64 {
 
 struct State : BodyStore<double> {   // (the bodies, their host view and the settings: nbody_handle.h)
-    std::vector<int> own_order;
-    // Barnes-Hut
-    nbody::HostTreeT<double> tree;
-    nbody::BuildScratchT<double> scratch;
-    Node64* d_nodes = nullptr;
-    size_t node_cap = 0;
-    int* d_order = nullptr;
-    size_t order_cap = 0;
-    double* h_pos = nullptr;   // pinned [4 * cap]
-    Open64* d_stack = nullptr; // nested walk: [levels][lanes]
-    size_t stack_lanes = 0;
-    int stack_levels = 0;
+    TreeStore<double> tree;    // Barnes-Hut: the tree, its device arrays, the device build's buffers, the walk's split and stack
     double* d_energy = nullptr;
     size_t energy_blocks = 0;
     const double* kick_dt = nullptr;   // inside a step: the dt the force pass may apply itself (fast walk, split node range)
     int kicked = 0;
-    // device-side build (NBODY_TREE_DEVICE): kernels_tree.hip instantiated for double
-    TreeBuildBufs tree_bufs;
-    nbody::TreeDevWork tree_work;
-    bool tree_on_device = false;  // where the last tree lives (nbody_tree_export)
-    size_t dev_nodes = 0;
-    WalkSplitBuf<double4> split;  // fast walk (NBODY_MATH_FAST): the node-range split
     // fast brute force (NBODY_MATH_FAST): kernels_bf64.hip's plan, re-made when the body counts or the knobs change, and
     // its partial-sum planes (grow only)
     Bf64Plan bf_plan;
@@ -339,18 +322,6 @@ int bf_forces(NbodyHandle* h, State& s) {
     return NBODY_OK;
 }
 
-int ensure_stack(NbodyHandle* h, State& s, int levels) {   // the nested sums' stack: one entry per open cell on the lane's path
-    const size_t lanes = (size_t(s.sh.seg_cap) + 255) / 256 * 256;
-    if (lanes > s.stack_lanes || levels > s.stack_levels) {
-        if (s.d_stack) (void)hipFree(s.d_stack);
-        s.d_stack = nullptr; s.stack_lanes = 0; s.stack_levels = 0;
-        const int lv = std::max(levels + 8, 32);
-        HIP_TRY(h, hipMalloc(&s.d_stack, lanes * size_t(lv) * sizeof(Open64)));
-        s.stack_lanes = lanes; s.stack_levels = lv;
-    }
-    return NBODY_OK;
-}
-
 // The fast walk (NBODY_MATH_FAST on an f64 handle): one running sum per lane, node range split over K segments so that a
 // few ten thousand bodies still fill the chip.  `host_nodes` != nullptr: the split points' ancestors are listed here from
 // the host-built tree; nullptr: by k_tree_split_anc from the device build's arrays (n_tree bodies).
@@ -360,11 +331,11 @@ int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const 
     if ((n_order == 0 && !field) || n_nodes <= 0) return NBODY_OK;
     const nbody::WalkPlan plan = walk_split_plan(size_t(n_order), true, float(s.theta2), size_t(n_nodes));   // (bodies per lane x segments: kernels.h)
     const int K = field ? field_split_plan(h->field.n_points, size_t(n_nodes)) : k_done > 0 ? k_done : plan.segments;
-    int rc = s.split.ensure(h, K, size_t(s.sh.seg_cap));
-    if (!rc && !k_done && host_nodes) rc = s.split.list_on_host(h, h->stream, host_nodes, n_nodes, K);
+    int rc = s.tree.split.ensure(h, K, size_t(s.sh.seg_cap));
+    if (!rc && !k_done && host_nodes) rc = s.tree.split.list_on_host(h, h->stream, host_nodes, n_nodes, K);
     if (rc) return rc;
-    if (!k_done && !host_nodes) s.split.list_on_device(h->stream, s.tree_work, n_tree, n_nodes, K);
-    const WalkSplit64 sp = walk_split_view(s.split, K, size_t(s.sh.seg_cap));
+    if (!k_done && !host_nodes) s.tree.split.list_on_device(h->stream, s.tree.work, n_tree, n_nodes, K);
+    const WalkSplit64 sp = walk_split_view(s.tree.split, K, size_t(s.sh.seg_cap));
     if (field) {   // the caller walks this tree for its probes, batch by batch (nbody_field.cpp)
         FieldBufs& f = h->field;
         f.nodes = nodes; f.n_nodes = n_nodes; f.K = K;
@@ -389,95 +360,39 @@ int fast_walk(NbodyHandle* h, State& s, const Node64* nodes, int n_nodes, const 
     return NBODY_OK;
 }
 
+// the reference's nested sums over the tree just built (strict math): one walk per body, `levels` deep at most
+int strict_walk(NbodyHandle* h, State& s, const TreeBuilt& t, int levels) {
+    const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
+    if (!direct) { int rc = s.tree.ensure_stack(h, s.sh.seg_cap, levels); if (rc) return rc; }
+    {
+        ForceTimer timer(h);
+        launch_bh_walk(h->stream, s.sh, s.tree.d_nodes, t.n_nodes, t.order, int(t.n_order), s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
+                       direct ? 1 : 0, s.tree.d_stack, s.tree.stack_lanes);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return NBODY_OK;
+}
+
 // The tree built on the device (NBODY_TREE_DEVICE; kernels_tree.hip for double): no positions to the host, no nodes
 // back.  Same cells, pre-order and skip links as the host build; centres of mass from f64 prefix sums instead of the
 // reference's sequential f64 folds (last bits).  *fell_back: coincident bodies / > 42 levels -> the caller builds on the host.
 int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
-    *fell_back = false;
-    auto t0 = clk::now();
-    const int G = s.sh.n_seg;
-    const bool sharded = G > 1;   // every rank builds the world's tree from the gathered positions (fast math; kernels_tree.hip k_tree_cat64)
-    const size_t cap = size_t(s.sh.seg_cap) * size_t(G);
-    size_t tot_upper = 0;
-    for (int g = 0; g < G; ++g) tot_upper += size_t(s.seg_count_host[size_t(g)]);
-    if (!sharded) tot_upper = s.n_local;
-    TreeBuildBufs& tb = s.tree_bufs;
-    int rc = tb.ensure(h, cap, sharded ? nbody::tree_cat_bytes64(cap) : 0);
-    if (rc) return rc;
-    if (cap > s.order_cap) {
-        if (s.d_order) (void)hipFree(s.d_order);
-        s.d_order = nullptr; s.order_cap = 0;
-        HIP_TRY(h, hipMalloc(&s.d_order, cap * sizeof(int)));
-        s.order_cap = cap;
-    }
-    const double4* tree_pos = s.sh.own_pos();
-    const int* tree_count = s.sh.own_count();
-    nbody::TreeCat cat;
-    if (sharded) {
-        double4* pos_cat = nullptr;
-        cat = nbody::tree_cat_layout64(tb.cat, cap, &pos_cat);
-        nbody::launch_tree_cat64(h->stream, s.sh.pos_all, s.sh.seg_count, G, s.sh.seg_cap, s.sh.my_seg, pos_cat, cat.info);
-        tree_pos = pos_cat;
-        tree_count = cat.info;
-    }
     // one shard, fast math: the walk's split points ride in the build's last launch (kernels.h TreeSplitReq)
     nbody::TreeSplitReq req;
     int k_pre = 0;
-    if (!sharded && h->cfg.math_mode == NBODY_MATH_FAST && tot_upper > 0 && h->pot.walking != kWalkField) {   // (a field call draws K from its probes)
-        k_pre = walk_split_plan(tot_upper, true, float(s.theta2), tot_upper).segments;   // (a tree has at least as many nodes as bodies)
-        rc = s.split.ensure(h, k_pre, size_t(s.sh.seg_cap));
+    if (s.sh.n_seg == 1 && h->cfg.math_mode == NBODY_MATH_FAST && s.n_local > 0 && h->pot.walking != kWalkField) {   // (a field call draws K from its probes)
+        k_pre = walk_split_plan(s.n_local, true, float(s.theta2), s.n_local).segments;   // (a tree has at least as many nodes as bodies)
+        int rc = s.tree.bufs.ensure(h, size_t(s.sh.seg_cap), 0);   // (the request names the build's info words)
+        if (!rc) rc = s.tree.split.ensure(h, k_pre, size_t(s.sh.seg_cap));
         if (rc) return rc;
-        req = s.split.request(k_pre, tb.d_info, nullptr);
+        req = s.tree.split.request(k_pre, s.tree.bufs.d_info, nullptr);
     }
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        if (s.node_cap < 2 * tot_upper + 64) {
-            if (s.d_nodes) (void)hipFree(s.d_nodes);
-            s.d_nodes = nullptr; s.node_cap = 0;
-            const size_t want = std::max<size_t>(2 * tot_upper + 64, s.dev_nodes + s.dev_nodes / 4 + 1024);
-            HIP_TRY(h, hipMalloc(&s.d_nodes, want * sizeof(Node64)));
-            s.node_cap = want;
-        }
-        if (nbody::build_octree_device_f64(h->stream, tree_pos, tree_count, int(tot_upper), s.center, s.width, tb.ws, tb.cap, s.d_nodes,
-                                           int(std::min<size_t>(s.node_cap, 0x7fffffff)), s.d_order, tb.d_info, &s.tree_work, k_pre ? &req : nullptr) != 0)
-            return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
-        HIP_TRY(h, hipMemcpyAsync(tb.h_info, tb.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        if (sharded) HIP_TRY(h, hipMemcpyAsync(s.h_counts, s.sh.seg_count, sizeof(int) * size_t(G), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (tb.h_info[1] & 5) { *fell_back = true; return NBODY_OK; }
-        if (!(tb.h_info[1] & 2)) break;
-        s.dev_nodes = size_t(tb.h_info[0]);   // the array was too small: the build says how many it needs
-        s.node_cap = 0;
-        if (attempt == 1) return fail(h, NBODY_ERR_CAPACITY, "device octree build: node array too small twice");
-    }
-    if (sharded) {   // the live counts of every block, and the own bodies' places in the tree order
-        size_t total = 0;
-        for (int g = 0; g < G; ++g) { s.seg_count_host[size_t(g)] = s.h_counts[g]; total += size_t(s.h_counts[g]); }
-        s.dev_nodes = size_t(tb.h_info[0]);
-        s.n_local = size_t(s.h_counts[s.sh.my_seg]);
-        s.count_dirty = false;
-        s.tree_on_device = true;
-        if (nbody::launch_tree_own_order(h->stream, s.d_order, cat, int(total), tb.ws, nbody::tree_build_tmp_bytes(cap)) != 0)
-            return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
-        h->stats.tree_build_ms += ms_since(t0);
-        h->stats.tree_nodes = s.dev_nodes;
-        return fast_walk(h, s, s.d_nodes, int(s.dev_nodes), cat.own_order, int(s.n_local), nullptr, int(total));
-    }
-    s.dev_nodes = size_t(tb.h_info[0]);
-    s.n_local = size_t(tb.h_info[2]);
-    s.count_dirty = false;
-    s.tree_on_device = true;
-    h->stats.tree_build_ms += ms_since(t0);
-    h->stats.tree_nodes = s.dev_nodes;
-    if (h->cfg.math_mode == NBODY_MATH_FAST || h->pot.walking) return fast_walk(h, s, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), nullptr, int(s.n_local), k_pre);
-    const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
-    if (!direct) { rc = ensure_stack(h, s, 45); if (rc) return rc; }   // (the device build goes to 42 levels)
-    {
-        ForceTimer t(h);
-        launch_bh_walk(h->stream, s.sh, s.d_nodes, int(s.dev_nodes), s.d_order, int(s.n_local), s.g, s.g_soft * s.g_soft, s.theta2, h->d_counters,
-                       direct ? 1 : 0, s.d_stack, s.stack_lanes);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return NBODY_OK;
+    TreeBuilt t;
+    int rc = s.tree.build_on_device(h, s, false, k_pre ? &req : nullptr, &t);
+    *fell_back = t.fell_back;
+    if (rc || t.fell_back) return rc;
+    if (h->cfg.math_mode == NBODY_MATH_FAST || h->pot.walking) return fast_walk(h, s, s.tree.d_nodes, t.n_nodes, t.order, int(t.n_order), nullptr, int(t.n_tree), k_pre);
+    return strict_walk(h, s, t, 45);   // (the device build goes to 42 levels)
 }
 
 // BarnesHutSimulation::update_forces (barnes_hut.rs:250-263): rebuild the tree (host, f64), one walk per body
@@ -487,25 +402,12 @@ int bh_forces(NbodyHandle* h, State& s) {
         int rc = bh_forces_device(h, s, &fell_back);
         if (rc || !fell_back) return rc;
     }
-    s.tree_on_device = false;
-    static_assert(sizeof(nbody::NodeRecT<double>) == sizeof(Node64), "host and device node records must agree");
-    HostTreePass<double, Node64> pass{reinterpret_cast<const double*>(s.sh.pos_all), s.sh.seg_count, s.sh.n_seg, s.sh.seg_cap, s.sh.my_seg, s.h_pos,
-                                      s.h_counts, s.seg_count_host, s.n_local, s.count_dirty, s.center, s.width, s.tree, s.scratch, s.own_order,
-                                      s.d_nodes, s.node_cap, s.d_order, s.order_cap};
-    int rc = pass.run(h);
+    TreeBuilt t;
+    int rc = s.tree.build_on_host(h, s, &t);
     if (rc) return rc;
-    const size_t n_order = pass.n_order;
     if (h->cfg.math_mode == NBODY_MATH_FAST || h->pot.walking)   // (the potential walk runs over the split in strict math too)
-        return fast_walk(h, s, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.tree.nodes, int(s.tree.n_order));
-    const bool direct = h->cfg.leaf_mode == NBODY_LEAF_DIRECT;
-    if (!direct) { rc = ensure_stack(h, s, s.tree.max_depth + 2); if (rc) return rc; }   // the tree's depth
-    {
-        ForceTimer t(h);
-        launch_bh_walk(h->stream, s.sh, s.d_nodes, int(s.tree.n_nodes), s.d_order, int(n_order), s.g, s.g_soft * s.g_soft, s.theta2,
-                       h->d_counters, direct ? 1 : 0, s.d_stack, s.stack_lanes);
-    }
-    HIP_TRY(h, hipGetLastError());
-    return NBODY_OK;
+        return fast_walk(h, s, s.tree.d_nodes, t.n_nodes, t.order, int(t.n_order), s.tree.host.nodes, int(t.n_tree));
+    return strict_walk(h, s, t, s.tree.host.max_depth + 2);   // the tree's depth
 }
 
 int forces(NbodyHandle* h, State& s) { return h->cfg.method == NBODY_BARNES_HUT ? bh_forces(h, s) : bf_forces(h, s); }
@@ -553,11 +455,7 @@ int create(NbodyHandle* h) {
     s.sh.n_seg = h->sh.n_seg; s.sh.my_seg = h->sh.my_seg; s.sh.seg_cap = h->sh.seg_cap;   // (index blocks: nbody_api.cpp create_impl)
     int rc = s.alloc(h, h->stream);
     if (rc) return rc;
-    if (h->cfg.method == NBODY_BARNES_HUT) {
-        s.tree.alloc = pinned_alloc;
-        s.tree.release = pinned_free;
-        HIP_TRY(h, hipHostMalloc(&s.h_pos, size_t(s.sh.n_seg) * size_t(s.sh.seg_cap) * sizeof(double4), hipHostMallocDefault));
-    }
+    if (h->cfg.method == NBODY_BARNES_HUT) { rc = s.tree.alloc_host(h, s.sh); if (rc) return rc; }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NBODY_OK;
 }
@@ -565,16 +463,13 @@ int create(NbodyHandle* h) {
 void destroy(NbodyHandle* h) {
     State* s = h->f64;
     if (!s) return;
-    s->tree.clear();
+    s->tree.release();
     s->release();
-    void* dev[] = {s->d_nodes, s->d_order, s->d_stack, s->d_energy, s->d_planes,
+    void* dev[] = {s->d_energy, s->d_planes,
                    s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->d_hm_planes,
                    s->blk.level, s->blk.tau, s->blk.list, s->blk.tile_count, s->blk.smin, s->blk.planes};
     for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {s->h_pos, s->h_sched};
-    for (void* p : host) if (p) (void)hipHostFree(p);
-    s->tree_bufs.release();
-    s->split.release();
+    if (s->h_sched) (void)hipHostFree(s->h_sched);
     delete s;
     h->f64 = nullptr;
 }
@@ -939,24 +834,7 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
 }
 
 int tree_export(NbodyHandle* h, double* com_mass, double* width, int32_t* skip, size_t cap, size_t* n_nodes) {
-    State& s = *h->f64;
-    const size_t n = s.tree_on_device ? s.dev_nodes : s.tree.n_nodes;
-    if (n_nodes) *n_nodes = n;
-    if (!com_mass && !width && !skip) return NBODY_OK;
-    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "tree export buffer too small");
-    std::vector<nbody::NodeRecT<double>> from_device;
-    if (s.tree_on_device) {
-        from_device.resize(n);
-        if (n) HIP_TRY(h, hipMemcpy(from_device.data(), s.d_nodes, n * sizeof(Node64), hipMemcpyDeviceToHost));
-    }
-    const nbody::NodeRecT<double>* nodes = s.tree_on_device ? from_device.data() : s.tree.nodes;
-    for (size_t i = 0; i < n; ++i) {
-        const nbody::NodeRecT<double>& r = nodes[i];
-        if (com_mass) { com_mass[4 * i] = r.a.x; com_mass[4 * i + 1] = r.a.y; com_mass[4 * i + 2] = r.a.z; com_mass[4 * i + 3] = r.a.m; }
-        if (width) width[i] = std::sqrt(r.b.w2);  // exact: w2 is the rounded square of the width
-        if (skip) skip[i] = r.b.skip;
-    }
-    return NBODY_OK;
+    return h->f64->tree.export_nodes(h, com_mass, width, skip, cap, n_nodes);
 }
 
 }  // namespace nbody64

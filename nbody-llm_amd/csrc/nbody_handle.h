@@ -12,6 +12,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -463,6 +464,85 @@ struct BodyStore {
     }
 };
 
+// ---- the Barnes-Hut tree of a handle, once for F = f32 (NbodyHandle::tree) and F = f64 (nbody64::State::tree): the host build's
+// tree, the node and order arrays the walks read, the device build's buffers, the walk's node-range split and the strict walk's
+// stack, with the two procedures that fill them.  What walks the tree stays per precision (TreeDev, WalkSplit64 and their kernels).
+template <class F> struct TreeTypes;
+template <> struct TreeTypes<float> {
+    using NodeDev = float4;               // 2 per node: {com, mass}, {width^2, skip, hot, leaf body}
+    using StackEntry = float4;            // an open cell of k_bh_walk_nested
+    static constexpr size_t kNodesPerBody = 4;   // the device build's first guess (a Plummer sphere gives ~1.5; the count read-back catches the rest)
+};
+template <> struct TreeTypes<double> {
+    using NodeDev = nbody64::Node64;
+    using StackEntry = nbody64::Open64;
+    static constexpr size_t kNodesPerBody = 2;   // (64-byte records)
+};
+
+// what a build leaves for the walk that follows
+struct TreeBuilt {
+    bool fell_back = false;       // the device build met bodies deeper than it goes: the caller builds on the host
+    int n_nodes = 0;
+    const int* order = nullptr;   // device: own bodies (indices into the own segment) in tree order
+    size_t n_order = 0;           // own bodies in the tree
+    size_t n_tree = 0;            // bodies in the tree
+};
+
+template <class F>
+struct TreeStore {
+    using V4 = typename nbody::ShardT<F>::V4;
+    using NodeDev = typename TreeTypes<F>::NodeDev;
+    using StackEntry = typename TreeTypes<F>::StackEntry;
+    static_assert(sizeof(nbody::NodeRecT<F>) == (sizeof(F) == 4 ? 2 : 1) * sizeof(NodeDev), "host and device node records must agree");
+
+    nbody::HostTreeT<F> host;            // the last tree built on the host
+    nbody::BuildScratchT<F> scratch;
+    NodeDev* d_nodes = nullptr;          // one NodeRecT<F> per node
+    int* d_order = nullptr;
+    size_t node_cap = 0, order_cap = 0;  // nodes, ints
+    F* h_pos = nullptr;                  // pinned: all segments' positions
+    std::vector<int32_t> own_order;
+    TreeBuildBufs bufs;                  // the device build's
+    nbody::TreeDevWork work;             // arrays of the last device build (inside bufs.ws)
+    bool on_device = false;              // the last tree was built on the device (export copies it back)
+    size_t n_nodes = 0;                  // nodes of the last tree, wherever it was built
+    WalkSplitBuf<V4> split;              // the walk's node-range split
+    StackEntry* d_stack = nullptr;       // strict math, reference leaf rule: per-lane stack of open cells, [stack_levels][stack_lanes]
+    size_t stack_lanes = 0;
+    int stack_levels = 0;
+
+    // a Barnes-Hut handle's host side: node arrays in pinned memory (their upload is one DMA) and the position mirror
+    int alloc_host(NbodyHandle* h, const nbody::ShardT<F>& sh) {
+        host.alloc = pinned_alloc;
+        host.release = pinned_free;
+        HIP_TRY(h, hipHostMalloc(&h_pos, size_t(sh.n_seg) * size_t(sh.seg_cap) * sizeof(V4), hipHostMallocDefault));
+        return NBODY_OK;
+    }
+    void release() {
+        host.clear();
+        for (void* p : {static_cast<void*>(d_nodes), static_cast<void*>(d_order), static_cast<void*>(d_stack)}) if (p) (void)hipFree(p);
+        if (h_pos) (void)hipHostFree(h_pos);
+        d_nodes = nullptr; d_order = nullptr; d_stack = nullptr; h_pos = nullptr;
+        node_cap = order_cap = stack_lanes = 0; stack_levels = 0;
+        bufs.release();
+        split.release();
+    }
+    int ensure_dev(NbodyHandle* h, size_t nodes, size_t order);   // grow-only (grow_dev)
+    // the stack for trees of `levels` levels: one entry per open cell on a lane's path -- as many levels as the tree is deep
+    // (the device build stops at 42; the host build reports its depth), not NBODY_MAX_TREE_DEPTH of them (13 GB at N = 2^22)
+    int ensure_stack(NbodyHandle* h, int seg_cap, int levels);
+    // The tree of a force pass built on the host (BarnesHutSimulation::update_forces, barnes_hut.rs:250-263): every block's
+    // positions and live counts back with one synchronisation, build_octree<F>, the own bodies in tree order (ids are
+    // block * seg_cap + index in the block), the nodes and that order up to the device.
+    int build_on_host(NbodyHandle* h, BodyStore<F>& b, TreeBuilt* out);
+    // The tree built on the device (kernels_tree.hip), over one shard or the concatenated index blocks: no positions go to the
+    // host, no node array comes back; one read-back of {nodes, flags, bodies} and the blocks' live counts.  split (may be null):
+    // the walk's split points ride in the build's last launch.  A node array that proves too small is grown once and rebuilt.
+    int build_on_device(NbodyHandle* h, BodyStore<F>& b, bool want_hot, const nbody::TreeSplitReq* split_req, TreeBuilt* out);
+    // com_mass [4 n] / width [n] / skip [n] (each may be null) of the last tree, fetched from the device when it lives there
+    int export_nodes(NbodyHandle* h, F* com_mass, F* width, int32_t* skip, size_t cap, size_t* n_out);
+};
+
 // nbody_tracers_* (nbody_tracer.cpp): massless particles beside the bodies.  Their state is a second Shard of one segment, so
 // the integrate and compact kernels run on it unchanged; n_host == 0 (no tracers) keeps every step path as it was.
 struct TracerState {
@@ -503,19 +583,7 @@ struct NbodyHandle : BodyStore<float> {
 
     // Barnes-Hut
     std::unique_ptr<nbody::WorkerPool> pool;
-    nbody::HostTree tree;
-    nbody::BuildScratch tree_scratch;
-    float4* d_nodes = nullptr;  // 2 float4 per node: {com, mass}, {width^2, skip, width, leaf body}
-    int* d_order = nullptr;
-    size_t d_node_cap = 0, d_order_cap = 0;
-    float* h_pos = nullptr;    // pinned: all segments' positions
-    std::vector<int32_t> own_order;
-    TreeBuildBufs tree_bufs;     // the device build's
-    float4* d_nested_stack = nullptr;  // strict Barnes-Hut: per-lane stack of open cells (k_bh_walk_nested)
-    size_t nested_cap = 0;
-    int nested_levels = 0;
-    bool tree_on_device = false; // the last tree was built on the device (export copies it back)
-    WalkSplitBuf<float4> split;  // the walk's node-range split
+    TreeStore<float> tree;       // the tree, its device arrays, the device build's buffers, the walk's split and stack
     // fast walk with the most-visited records in LDS (kernels_bh.hip, variant 3)
     float4* d_walk = nullptr;    // [walk_cap + 1] records with explicit links
     int* d_unified = nullptr;    // [walk_cap + 1]
@@ -641,71 +709,150 @@ struct ForceTimer {  // HIP events around a force-kernel launch, on the launch s
     }
 };
 
-// The tree of a Barnes-Hut force pass built on the host (BarnesHutSimulation::update_forces, barnes_hut.rs:250-263), F = float
-// or double: every block's positions and live counts back with one synchronisation, build_octree<F>, the own bodies in tree
-// order (ids are block * seg_cap + index in the block), the nodes and that order up to the device.
-template <class F, class NodeDev>
-struct HostTreePass {
-    const F* pos_all;                  // device [n_seg][seg_cap][4]
-    const int* seg_count;              // device [n_seg] live counts
-    int n_seg, seg_cap, my_seg;
-    F* h_pos;                          // pinned, as pos_all
-    int* h_counts;                     // pinned [n_seg]
-    std::vector<int>& count_host;      // every block's live count: upper bounds going in, exact coming out
-    size_t& n_local;
-    bool& count_dirty;
-    const F* center;
-    F width;
-    nbody::HostTreeT<F>& tree;
-    nbody::BuildScratchT<F>& scratch;
-    std::vector<int32_t>& own_order;
-    NodeDev*& d_nodes;                 // one NodeRecT<F> per node
-    size_t& node_cap;
-    int*& d_order;
-    size_t& order_cap;
-    size_t n_order = 0;                // out: own bodies in the tree
+// ---- TreeStore<F>'s procedures (they need the handle: its stream, worker pool and statistics)
 
-    int run(NbodyHandle* h) {
-        auto t0 = clk::now();
-        for (int g = 0; g < n_seg; ++g) {
-            const size_t cnt = size_t(count_host[size_t(g)]);
-            if (cnt)
-                HIP_TRY(h, hipMemcpyAsync(h_pos + 4 * size_t(g) * seg_cap, pos_all + 4 * size_t(g) * seg_cap, cnt * 4 * sizeof(F),
-                                          hipMemcpyDeviceToHost, h->stream));
-        }
-        HIP_TRY(h, hipMemcpyAsync(h_counts, seg_count, sizeof(int) * n_seg, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (int g = 0; g < n_seg; ++g) count_host[size_t(g)] = h_counts[g];
-        n_local = size_t(h_counts[my_seg]);
-        count_dirty = false;
-        const double copy_ms = ms_since(t0);
+template <class F>
+int TreeStore<F>::ensure_dev(NbodyHandle* h, size_t nodes, size_t order) {
+    int rc = grow_dev(h, d_nodes, node_cap, nodes, sizeof(nbody::NodeRecT<F>));
+    return rc ? rc : grow_dev(h, d_order, order_cap, order, sizeof(int));
+}
 
-        auto t1 = clk::now();
-        nbody::build_octree<F>(h_pos, n_seg, seg_cap, h_counts, center, width, *h->pool, scratch, tree);
-        if (tree.too_deep) return fail(h, NBODY_ERR_TREE_DEPTH, "octree deeper than NBODY_MAX_TREE_DEPTH (coincident bodies?)");
-        const int32_t* order = tree.order;
-        n_order = tree.n_order;
-        if (n_seg > 1) {
-            own_order.clear();
-            const int lo = my_seg * seg_cap, hi = lo + seg_cap;
-            for (size_t k = 0; k < tree.n_order; ++k) {
-                const int id = tree.order[k];
-                if (id >= lo && id < hi) own_order.push_back(id - lo);
-            }
-            order = own_order.data();
-            n_order = own_order.size();
-        }
-        h->stats.tree_build_ms += ms_since(t1);
-        h->stats.tree_nodes = tree.n_nodes;
-
-        auto t2 = clk::now();
-        int rc = grow_dev(h, d_nodes, node_cap, tree.n_nodes, sizeof(nbody::NodeRecT<F>));
-        if (!rc) rc = grow_dev(h, d_order, order_cap, n_order, sizeof(int));
-        if (rc) return rc;
-        HIP_TRY(h, hipMemcpyAsync(d_nodes, tree.nodes, tree.n_nodes * sizeof(nbody::NodeRecT<F>), hipMemcpyHostToDevice, h->stream));
-        if (n_order) HIP_TRY(h, hipMemcpyAsync(d_order, order, n_order * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        if (n_seg > 1) HIP_TRY(h, hipStreamSynchronize(h->stream));   // own_order is pageable and reused
-        h->stats.tree_copy_ms += copy_ms + ms_since(t2);
-        return NBODY_OK;
+template <class F>
+int TreeStore<F>::ensure_stack(NbodyHandle* h, int seg_cap, int levels) {
+    const size_t lanes = (size_t(seg_cap) + 255) / 256 * 256;
+    if (lanes > stack_lanes || levels > stack_levels) {
+        if (d_stack) (void)hipFree(d_stack);
+        d_stack = nullptr; stack_lanes = 0; stack_levels = 0;
+        const int lv = std::max(levels + 8, 32);
+        HIP_TRY(h, hipMalloc(&d_stack, lanes * size_t(lv) * sizeof(StackEntry)));
+        stack_lanes = lanes; stack_levels = lv;
     }
-};
+    return NBODY_OK;
+}
+
+template <class F>
+int TreeStore<F>::build_on_host(NbodyHandle* h, BodyStore<F>& b, TreeBuilt* out) {
+    const nbody::ShardT<F>& sh = b.sh;
+    const int n_seg = sh.n_seg, seg_cap = sh.seg_cap;
+    const F* pos_all = reinterpret_cast<const F*>(sh.pos_all);
+    on_device = false;
+    auto t0 = clk::now();
+    for (int g = 0; g < n_seg; ++g) {
+        const size_t cnt = size_t(b.seg_count_host[size_t(g)]);
+        if (cnt)
+            HIP_TRY(h, hipMemcpyAsync(h_pos + 4 * size_t(g) * seg_cap, pos_all + 4 * size_t(g) * seg_cap, cnt * 4 * sizeof(F),
+                                      hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(b.h_counts, sh.seg_count, sizeof(int) * n_seg, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int g = 0; g < n_seg; ++g) b.seg_count_host[size_t(g)] = b.h_counts[g];
+    b.n_local = size_t(b.h_counts[sh.my_seg]);
+    b.count_dirty = false;
+    const double copy_ms = ms_since(t0);
+
+    auto t1 = clk::now();
+    nbody::build_octree<F>(h_pos, n_seg, seg_cap, b.h_counts, b.center, b.width, *h->pool, scratch, host);
+    n_nodes = host.n_nodes;
+    if (host.too_deep) return fail(h, NBODY_ERR_TREE_DEPTH, "octree deeper than NBODY_MAX_TREE_DEPTH (coincident bodies?)");
+    const int32_t* order = host.order;
+    size_t n_order = host.n_order;
+    if (n_seg > 1) {
+        own_order.clear();
+        const int lo = sh.my_seg * seg_cap, hi = lo + seg_cap;
+        for (size_t k = 0; k < host.n_order; ++k) {
+            const int id = host.order[k];
+            if (id >= lo && id < hi) own_order.push_back(id - lo);
+        }
+        order = own_order.data();
+        n_order = own_order.size();
+    }
+    h->stats.tree_build_ms += ms_since(t1);
+    h->stats.tree_nodes = host.n_nodes;
+
+    auto t2 = clk::now();
+    int rc = ensure_dev(h, host.n_nodes, n_order);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(d_nodes, host.nodes, host.n_nodes * sizeof(nbody::NodeRecT<F>), hipMemcpyHostToDevice, h->stream));
+    if (n_order) HIP_TRY(h, hipMemcpyAsync(d_order, order, n_order * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (n_seg > 1) HIP_TRY(h, hipStreamSynchronize(h->stream));   // own_order is pageable and reused
+    h->stats.tree_copy_ms += copy_ms + ms_since(t2);
+    *out = TreeBuilt{false, int(host.n_nodes), d_order, n_order, host.n_order};
+    return NBODY_OK;
+}
+
+template <class F>
+int TreeStore<F>::build_on_device(NbodyHandle* h, BodyStore<F>& b, bool want_hot, const nbody::TreeSplitReq* split_req, TreeBuilt* out) {
+    const nbody::ShardT<F>& sh = b.sh;
+    *out = TreeBuilt{};
+    auto t0 = clk::now();
+    const bool sharded = sh.n_seg > 1;   // every GPU builds the same tree over the gathered bodies of all segments
+    const size_t n_cap = size_t(sh.seg_cap) * size_t(sh.n_seg);
+    int rc = bufs.ensure(h, n_cap, sharded ? nbody::tree_cat_bytes<V4>(n_cap) : 0);
+    if (rc) return rc;
+    size_t tot_upper = b.n_local;
+    if (sharded) { tot_upper = 0; for (int c : b.seg_count_host) tot_upper += size_t(c); }
+    rc = ensure_dev(h, TreeTypes<F>::kNodesPerBody * tot_upper + 64, tot_upper);
+    if (rc) return rc;
+    nbody::TreeCat<V4> cat;
+    const V4* tree_pos = sh.own_pos();
+    const int* tree_count = sh.own_count();
+    if (sharded) {
+        cat = nbody::tree_cat_layout<V4>(bufs.cat, n_cap);
+        nbody::launch_tree_cat(h->stream, sh, cat);
+        tree_pos = cat.pos;
+        tree_count = cat.info;
+    }
+    for (int attempt = 0;; ++attempt) {
+        if (nbody::build_octree_device(h->stream, tree_pos, tree_count, int(tot_upper), b.center, b.width, bufs.ws, n_cap, d_nodes,
+                                       int(std::min<size_t>(node_cap, 0x7fffffff)), d_order, bufs.d_info, &work, want_hot ? 1 : 0, split_req) != 0)
+            return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(bufs.h_info, bufs.d_info, 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (sharded) HIP_TRY(h, hipMemcpyAsync(b.h_counts, sh.seg_count, sizeof(int) * sh.n_seg, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (!sharded) b.h_counts[0] = bufs.h_info[2];   // one shard: the tree's body count is the live count
+        if (!(bufs.h_info[1] & 2) || (bufs.h_info[1] & 5)) break;
+        if (attempt == 1) return fail(h, NBODY_ERR_CAPACITY, "device octree build: node array too small twice");
+        rc = ensure_dev(h, size_t(bufs.h_info[0]) + 64, tot_upper);   // more nodes than allowed for: the build says how many; grow, rebuild
+        if (rc) return rc;
+    }
+    size_t n_tree = 0;
+    for (int g = 0; g < sh.n_seg; ++g) { b.seg_count_host[size_t(g)] = b.h_counts[g]; n_tree += size_t(b.h_counts[g]); }
+    b.n_local = size_t(b.h_counts[sh.my_seg]);
+    b.count_dirty = false;
+    if (bufs.h_info[1] & 5) { out->fell_back = true; return NBODY_OK; }   // deeper than 42 levels / a clump beyond the build's sort
+    const int* order = d_order;
+    if (sharded) {   // the own bodies' places in the tree order
+        if (nbody::launch_tree_own_order(h->stream, d_order, cat, int(n_tree), bufs.ws, nbody::tree_build_tmp_bytes(n_cap)) != 0)
+            return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
+        order = cat.own_order;
+    }
+    on_device = true;
+    n_nodes = size_t(bufs.h_info[0]);
+    h->stats.tree_build_ms += ms_since(t0);
+    h->stats.tree_nodes = n_nodes;
+    *out = TreeBuilt{false, bufs.h_info[0], order, b.n_local, n_tree};
+    return NBODY_OK;
+}
+
+template <class F>
+int TreeStore<F>::export_nodes(NbodyHandle* h, F* com_mass, F* width, int32_t* skip, size_t cap, size_t* n_out) {
+    const size_t n = n_nodes;
+    if (n_out) *n_out = n;
+    if (!com_mass && !width && !skip) return NBODY_OK;
+    if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "tree export buffer too small");
+    std::vector<nbody::NodeRecT<F>> from_device;
+    if (on_device) {   // the octree lives on the device only: fetch it
+        from_device.resize(n);
+        if (n) HIP_TRY(h, hipMemcpyAsync(from_device.data(), d_nodes, n * sizeof(nbody::NodeRecT<F>), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    const nbody::NodeRecT<F>* nodes = on_device ? from_device.data() : host.nodes;
+    for (size_t i = 0; i < n; ++i) {
+        const nbody::NodeRecT<F>& r = nodes[i];
+        if (com_mass) { com_mass[4 * i] = r.a.x; com_mass[4 * i + 1] = r.a.y; com_mass[4 * i + 2] = r.a.z; com_mass[4 * i + 3] = r.a.m; }
+        if (width) width[i] = std::sqrt(r.b.w2);  // exact: w2 is the rounded square of the width
+        if (skip) skip[i] = r.b.skip;
+    }
+    return NBODY_OK;
+}

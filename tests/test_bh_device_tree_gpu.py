@@ -122,6 +122,72 @@ def test_deeper_than_the_device_build_goes_falls_back_to_the_host_build(gpu, orc
         assert e.value.code == nb.NBODY_ERR_TREE_DEPTH
 
 
+def close_pairs(dtype, box_w=64.0):
+    """64 bodies of mass 1/64 as 32 pairs spread over the box, the two of a pair about 1e-6 of its width apart: every pair
+    hangs below a chain of ~17 cells with one child each, so the tree has ~10 nodes per body.  Every coordinate is a multiple
+    of 2^-14 below 7.1 in size, so the sums m x over any cell are exact in f32 (23 bits) and the host build's f32 folds
+    and the device build's f64 prefix sums give the same centres of mass to the bit."""
+    rng = np.random.default_rng(64)
+    cell = rng.integers(-28, 28, (32, 3))
+    assert len(np.unique(cell, axis=0)) == 32                          # (with this seed)
+    # an odd multiple of 2^-14 and the next multiple lie in the same cell down to level 19 (cells are half-open upwards)
+    base = cell * 0.25 + (2 * rng.integers(0, 8, (32, 3)) + 1) * 2.0 ** -14
+    ics = np.zeros(64, dtype)
+    ics["position"][0::2] = base
+    ics["position"][1::2] = base + 2.0 ** -14                          # 0.95e-6 of the width along every axis
+    ics["mass"] = 1.0 / 64
+    return ics
+
+
+def lattice_pairs(dtype):
+    """1024 bodies of mass 1/1024 as 512 pairs on an 8 x 8 x 8 lattice of pitch 1/4 about the origin, the two of a pair at
+    the lattice point + 2^-13 and + 2^-12 along every axis (1.9e-6 of a width of 64): ~6.6 nodes per body, more than the
+    device build's first node array holds in either precision.  Coordinates are multiples of 2^-13 below 1.01 in size: the
+    sums m x over any cell are exact in f32 (24 bits), as in close_pairs."""
+    a = (np.arange(8) - 4) * 0.25
+    base = np.stack(np.meshgrid(a, a, a, indexing="ij"), axis=-1).reshape(-1, 3) + 2.0 ** -13
+    ics = np.zeros(1024, dtype)
+    ics["position"][0::2] = base
+    ics["position"][1::2] = base + 2.0 ** -13
+    ics["mass"] = 1.0 / 1024
+    return ics
+
+
+def first_node_array(nodes_per_body, n):
+    """records of the device build's first node array: its first guess plus the grow-only helper's slack (grow_dev)"""
+    want = nodes_per_body * n + 64
+    return want + want // 4 + 1024
+
+
+PAIRS = {"close": (close_pairs, False), "lattice": (lattice_pairs, True)}   # fixture, whether the first node array overflows
+
+
+@pytest.mark.parametrize("which", list(PAIRS))
+def test_more_nodes_than_the_first_guess_allows_for(gpu, which):
+    """A tree of more than 4 n + 64 nodes, the device build's first guess.  "close" (64 bodies) still fits the first node
+    array with its slack; "lattice" (1024 bodies, 6769 nodes against 6224 records) does not: the build reports the count
+    it needs, the array is grown and the build runs once more.  Either way the build ends with every node -- the host
+    build's count, links and widths, and in strict math the accelerations of a TREE_HOST handle bit for bit (both fixtures:
+    the two builds' centre-of-mass sums are exact)."""
+    nb = gpu
+    make, overflows = PAIRS[which]
+    sd = dict(g=1.0, g_soft=0.01, dt=1e-3, theta2=0.25)
+    ics = make(nb.PARTICLE_DTYPE)
+    ht = nb.host_build_tree(np.concatenate([ics["position"], ics["mass"][:, None]], axis=1), *BOX)
+    assert len(ht["skip"]) > 4 * len(ics) + 64
+    assert (len(ht["skip"]) > first_node_array(4, len(ics))) == overflows
+    out = {}
+    for build in (nb.TREE_DEVICE, nb.TREE_HOST):
+        with nb.Simulation(ics, *BOX, method=nb.BARNES_HUT, math_mode=nb.STRICT, tree_build=build) as sim:
+            sim.settings = nb.Settings(**sd)
+            sim.update_forces()
+            out[build] = (sim.get_points(), sim.stats(), sim.tree())
+    got, s, t = out[nb.TREE_DEVICE]
+    assert s.tree_nodes == len(ht["skip"]) == len(t["skip"])
+    assert np.array_equal(t["skip"], ht["skip"]) and np.array_equal(t["width"], ht["width"])
+    assert np.array_equal(got["acceleration"].view(np.uint32), out[nb.TREE_HOST][0]["acceleration"].view(np.uint32))
+
+
 @pytest.mark.parametrize("n", [2, 500, 6000])
 def test_bodies_that_share_all_21_levels_get_second_keys_on_the_device(gpu, orc, n):
     """Pairs, a triple and a clump of 9 bodies a few 1e-7 apart (cells of level 21 are 3e-5 wide; at N = 2^22 a Plummer

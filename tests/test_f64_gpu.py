@@ -310,6 +310,65 @@ def test_barnes_hut_f64_device_tree_trajectory_and_close_pairs(gpu, orc):
     assert np.array_equal(got["mass"], ref["mass"])
 
 
+@pytest.mark.parametrize("which", ["close", "lattice"])
+def test_f64_more_nodes_than_the_first_guess_allows_for(gpu, orc, which):
+    """The f64 twin of test_bh_device_tree_gpu.py's test of that name, on its fixtures: a tree of more than 4 n + 64 nodes
+    -- and so of more than the f64 build's first guess of 2 n + 64 -- comes out whole: the oracle's count, links and widths
+    exactly, accelerations within test_barnes_hut_f64_device_tree's tolerances.  "lattice" (6769 nodes against a first
+    node array of 3664 records) is grown and built once more; "close" fits the first array with its slack."""
+    from test_bh_device_tree_gpu import PAIRS, first_node_array
+    nb = gpu
+    make, overflows = PAIRS[which]
+    sd = dict(g=1.0, g_soft=0.01, dt=1e-3, theta2=0.25)
+    ics = make(nb.PARTICLE_DTYPE64)
+    rt = orc.bh_build_tree(ics.astype(orc.P64), BOX[0], BOX[1])
+    assert len(rt["skip"]) > 4 * len(ics) + 64
+    assert (len(rt["skip"]) > first_node_array(2, len(ics))) == overflows
+    ref = ics.copy().astype(orc.P64)
+    orc.bh_update_forces(ref, sd, BOX[0], BOX[1], threads=2)
+    with nb.Simulation(ics, *BOX, method=nb.BARNES_HUT, math_mode=nb.STRICT, tree_build=nb.TREE_DEVICE) as sim:
+        sim.settings = nb.Settings(**sd)
+        sim.update_forces()
+        got = sim.get_points()
+        s = sim.stats()
+        t = sim.tree()
+    assert s.tree_nodes == len(rt["skip"]) == len(t["skip"])
+    assert np.array_equal(t["skip"], rt["skip"]) and eq(t["width"], rt["width"])
+    scale = np.abs(ref["acceleration"]).max() or 1.0
+    err = np.abs(got["acceleration"] - ref["acceleration"]).max(axis=1) / scale
+    print(f"f64 {which} pairs: acceleration error max {err.max():.3e}, bodies beyond 1e-11: {np.count_nonzero(err > 1e-11)}")
+    assert np.count_nonzero(err > 1e-11) <= 1 and err.max(initial=0.0) < 1e-3
+
+
+def test_f64_deeper_than_the_device_build_goes_falls_back_to_the_host_build(gpu, orc):
+    """The f64 twin of test_bh_device_tree_gpu.py's test of that name: two bodies 2e-7 apart in a width-64 box separate
+    only below level 21; with the device build's second keys switched off (tree_max_tie = 1) it reports "too deep" and the
+    pass runs on the host-built tree: the oracle's counts and accelerations bit for bit, and tree() returns the host tree.
+    Coincident bodies raise either way."""
+    nb = gpu
+    sd = dict(g=1.0, g_soft=0.01, dt=1e-3, theta2=0.25)
+    ics = nb.plummer(500, seed=3, f64=True)
+    ics["position"][7] = ics["position"][3] + 2e-7
+    ref = ics.copy().astype(orc.P64)
+    acc_n, vis_n = orc.bh_update_forces(ref, sd, BOX[0], BOX[1], threads=2)
+    rt = orc.bh_build_tree(ics.astype(orc.P64), BOX[0], BOX[1])
+    assert np.log2(BOX[1] / rt["width"].min()) > 22
+    with nb.Simulation(ics, *BOX, method=nb.BARNES_HUT, math_mode=nb.STRICT, tree_build=nb.TREE_DEVICE, tuning=dict(tree_max_tie=1)) as sim:
+        sim.settings = nb.Settings(**sd)
+        sim.update_forces()
+        s = sim.stats()
+        got = sim.get_points()
+        t = sim.tree()
+    assert (s.interactions, s.node_visits, s.tree_nodes) == (acc_n, vis_n, len(rt["skip"]))
+    assert eq(got["acceleration"], ref["acceleration"])
+    assert np.array_equal(t["skip"], rt["skip"]) and eq(t["width"], rt["width"]) and eq(t["com_mass"], rt["com_mass"])
+    ics["position"][7] = ics["position"][3]
+    with nb.Simulation(ics, *BOX, method=nb.BARNES_HUT, tree_build=nb.TREE_DEVICE) as sim:
+        with pytest.raises(nb.NbodyError) as e:
+            sim.update_forces()
+        assert e.value.code == nb.NBODY_ERR_TREE_DEPTH
+
+
 @pytest.mark.parametrize("tree", ["host", "device"])
 @pytest.mark.parametrize("leaf", ["reference", "direct"])
 @pytest.mark.parametrize("n,theta2,split", [(1, 0.25, 0), (2, 0.25, 0), (9, 1.0, 0), (1000, 0.25, 0), (5000, 0.5, 1), (20000, 0.25, 0), (65536, 0.25, 0), (65536, 0.25, 7)])

@@ -254,6 +254,41 @@ def test_barnes_hut_shards_with_device_tree_equal_single_shard(gpu, G, n, box_w)
         s.close()
 
 
+@pytest.mark.parametrize("G,n,box_w", [(2, 300, 64.0), (3, 300, 64.0), (2, 3000, 64.0), (3, 3000, 2.5)])
+def test_barnes_hut_f64_shards_with_device_tree_equal_single_shard(gpu, tmp_path, G, n, box_w):
+    """The f64 twin of the test above: every rank concatenates the gathered f64 blocks (k_tree_cat64), builds the same
+    tree on the device and walks it for its own bodies in the order the own-order filter leaves.  An f64 handle exchanges
+    inside its step (it has no nbody_debug_* hooks), so the ranks are processes over the one-device transport.  Same tree
+    + same per-body walk => the world equals the 1-shard device-tree run bit for bit and the node counts add up exactly;
+    bodies leave the 2.5-wide box on the way.  The node-range split is pinned to 8 segments as above."""
+    nb = gpu
+    from nbody_llm_amd import ranks
+    box = [[0.0, 0.0, 0.0], box_w]
+    sd = dict(g=1.0, g_soft=0.01, dt=5e-3, theta2=0.25)
+    cfg = {"world": G, "out": str(tmp_path / "world"), "transport": "ipc", "device": 0, "box": box, "settings": sd, "env": {},
+           "sim": dict(method="bh", math="fast", tree="device", tuning=dict(bh_walk_split=8)), "ics": dict(n=n, seed=31, f64=True),
+           "schedule": [["steps", 5]]}
+    res = ranks.run_world(cfg, ranks_per_process=1, timeout=120)
+    got = ranks.gather_world(res)
+    ics = ranks.make_ics(nb, cfg["ics"])
+    with ranks.make_sim(nb, cfg, ics, 0, 1, 0) as one:
+        one.settings = nb.Settings(**sd)
+        one.init()
+        one.steps(5)
+        ref = one.get_points()
+        s1 = one.stats()
+    assert got.dtype == nb.PARTICLE_DTYPE64 and all(r["f64"] for r in res)
+    if box_w < 10:
+        assert len(ref) < n
+    assert len(got) == len(ref)
+    for f in FIELDS:
+        print(f"G={G} n={n} {f}: max |world - one| = {np.abs(got[f] - ref[f]).max():.3e}")
+    for f in FIELDS:
+        assert np.array_equal(got[f], ref[f]), f
+    assert sum(r["interactions"] for r in res) == s1.interactions and sum(r["node_visits"] for r in res) == s1.node_visits
+    assert all(r["tree_nodes"] == s1.tree_nodes for r in res)
+
+
 def test_rccl_single_rank_communicator(gpu, orc):
     """The RCCL code path itself (ncclGetUniqueId, ncclCommInitRank, grouped in-place all-gathers on
     the handle's stream) with a world of one: results must not change."""
