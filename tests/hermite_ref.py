@@ -21,11 +21,12 @@ import numpy as np
 
 from bf64_bound import R  # noqa: F401  (the acceleration's bound, re-exported for the Hermite tests)
 
-#: |j_i - S_j,i| <= RJ T_j,i.  bf64_bound.py's convention is 3x the worst value measured on an MI355X over
-#: tests/test_hermite_gpu.py's fast cases; that measurement is still to be made (the test prints its ratios under pytest -s).
-#: Until then the bound stands on arithmetic: at most 12 roundings of 1.1e-16 in a term, and at most 1499 additions of the
-#: same size relative to T_j in a sum of the largest case's 1500 terms: (12 + 1499) * 1.1e-16 = 1.7e-13 (DESIGN.md
-#: section 3.10).  Must stay <= 1e-12; the smallest single term of world(256) is 1.1e-6 T_j.
+#: |j_i - S_j,i| <= RJ T_j,i.  Measured on an MI355X (pytest -s): the worst |j - S_j| / T_j is 6.6e-16 over tests/test_hermite_gpu.py's
+#: fast cases (n = 1500, few slices) and 7.3e-16 over tests/test_hermite_block_gpu.py's k_hm_act rows (n = 1500); 3x that would be
+#: 2.2e-15.  RJ stays at the looser figure arithmetic gives for any order of summation, which the measurement does not violate:
+#: at most 12 roundings of 1.1e-16 in a term, and at most 1499 additions of the same size relative to T_j in a sum of the
+#: largest case's 1500 terms: (12 + 1499) * 1.1e-16 = 1.7e-13.  Must stay <= 1e-12; the smallest single
+#: term of world(256) is 1.1e-6 T_j.  What catches a wrong pair at the plans a user gets is the probe bound, hermite_probe.RJP.
 RJ = 2.0e-13
 
 G, EPS = 1.0, 0.05
@@ -129,17 +130,28 @@ def start(x, v, m, g: float = G, eps: float = EPS, force=strict_aj):
     return np.array(x, np.float64), np.array(v, np.float64), a, j, np.array(m, np.float64)
 
 
-def fast_aj(pos, vel, mass, g: float, eps: float):
-    """F in vectorised f64 (no fixed order): for the order tests, where only the integrator's truncation error matters."""
+def fast_aj(pos, vel, mass, g: float, eps: float, rows=None):
+    """F in vectorised f64 (no fixed order): for the order tests, where only the integrator's truncation error matters.
+    `rows`: those bodies' rows only (a large world is evaluated a block of rows at a time: fast_aj_blocked)."""
     x, v, m = (np.asarray(a, np.float64) for a in (pos, vel, mass))
-    d = x[None, :, :] - x[:, None, :]
-    w = v[None, :, :] - v[:, None, :]
+    r = np.arange(len(x)) if rows is None else np.asarray(rows, np.int64)
+    d = x[None, :, :] - x[r, None, :]
+    w = v[None, :, :] - v[r, None, :]
     q = (d * d).sum(-1) + eps * eps
-    np.fill_diagonal(q, 1.0)
+    self_ = (np.arange(len(r)), r)
+    q[self_] = 1.0
     k = g * m[None, :] / (q * np.sqrt(q))
-    np.fill_diagonal(k, 0.0)
+    k[self_] = 0.0
     dw = (d * w).sum(-1)
     return (d * k[..., None]).sum(1), ((w - (3.0 * dw / q)[..., None] * d) * k[..., None]).sum(1)
+
+
+def fast_aj_blocked(pos, vel, mass, g: float, eps: float, block: int = 256):
+    """fast_aj of every row, `block` rows at a time: the same values in a bounded amount of memory."""
+    parts = [fast_aj(pos, vel, mass, g, eps, rows=np.arange(r0, min(r0 + block, len(pos)))) for r0 in range(0, len(pos), block)]
+    if not parts:
+        return np.zeros((0, 3)), np.zeros((0, 3))
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
 
 def suggest_dt(acc, jerk, eta: float) -> float:
