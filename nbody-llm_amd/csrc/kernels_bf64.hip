@@ -20,22 +20,13 @@
 // launch; there are no atomics on the planes.
 #include "kernels_f64.h"
 #include "kernels.h"   // nbody::tuning()
+#include "pair64.h"
 
 namespace nbody64 {
 
 namespace {
 
-constexpr double kPad = 1.0e100;   // zero-mass padding bodies sit far away: they exert nothing on real bodies
-
-__device__ __forceinline__ double4 pad_body() { return make_double4(kPad, kPad, kPad, 0.0); }
-
-// a double through the LDS crossbar: lane l receives lane (src_x4 / 4)'s value, two 32-bit halves
-__device__ __forceinline__ double rot64(double v, int src_x4) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_ds_bpermute(src_x4, int(b));
-    const int hi = __builtin_amdgcn_ds_bpermute(src_x4, int(b >> 32));
-    return __longlong_as_double((long long)(unsigned)lo | ((long long)hi << 32));
-}
+using namespace pair64;   // kPad, pad_body, rot64, plane_sum
 
 // IPT unordered pairs (resident q, traveller j), written stage by stage so that no instruction waits on its predecessor
 template <int IPT>
@@ -241,12 +232,8 @@ __global__ __launch_bounds__(256) void k_bf64_reduce(const double4* __restrict__
         if (tot > 0) atomicAdd(inter, (unsigned long long)(*count) * (unsigned long long)(tot - 1));
     }
     if (i >= *count) return;
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    for (int p = 0; p < n_planes; ++p) {
-        const double4 v = planes[size_t(p) * plane_stride + i];
-        sx += v.x; sy += v.y; sz += v.z;
-    }
-    const double4 a = make_double4(g * sx, g * sy, g * sz, 0.0);
+    double4 a, no_j;
+    plane_sum<1>(planes, n_planes, plane_stride, 0, i, g, a, no_j);
     acc[i] = a;
     if (KICK) {
         double4 p = pos[i], v = vel[i];

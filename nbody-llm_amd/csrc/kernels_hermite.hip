@@ -23,6 +23,7 @@
 // is written exactly once per launch; there are no atomics on the planes: the same input gives the same bits.
 #include "kernels_hermite.h"
 #include "kernels.h"   // nbody::tuning()
+#include "pair64.h"
 #include "retain.h"
 
 #include <algorithm>
@@ -31,38 +32,34 @@ namespace nbody64 {
 
 namespace {
 
-constexpr double kPad = 1.0e100;   // zero-mass padding bodies sit far away and at rest: they exert nothing on real bodies
-
-__device__ __forceinline__ double4 pad_body() { return make_double4(kPad, kPad, kPad, 0.0); }
-__device__ __forceinline__ double4 zero4() { return make_double4(0.0, 0.0, 0.0, 0.0); }
-
-// a double through the LDS crossbar: lane l receives lane (src_x4 / 4)'s value, two 32-bit halves
-__device__ __forceinline__ double rot64(double v, int src_x4) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_ds_bpermute(src_x4, int(b));
-    const int hi = __builtin_amdgcn_ds_bpermute(src_x4, int(b >> 32));
-    return __longlong_as_double((long long)(unsigned)lo | ((long long)hi << 32));
-}
+using namespace pair64;   // pad_body, zero4, rot64, plane_sum
 
 // ------------------------------------------------------------------------------------------ the small kernels
+// body k predicted over dt: xp = ((x0 + v0 * dt) + a0 * c2) + j0 * c3,  vp = (v0 + a0 * dt) + j0 * c2
+__device__ __forceinline__ void predict_one(int k, const double4* __restrict__ pos, const double4* __restrict__ vel, const double4* __restrict__ acc,
+                                            const double4* __restrict__ jerk, double4* __restrict__ xp, double4* __restrict__ vp, double dt, double c2,
+                                            double c3) {
+    const double4 x0 = pos[k], v0 = vel[k], a0 = acc[k], j0 = jerk[k];
+    double4 x, v;
+    x.x = ((x0.x + v0.x * dt) + a0.x * c2) + j0.x * c3;
+    x.y = ((x0.y + v0.y * dt) + a0.y * c2) + j0.y * c3;
+    x.z = ((x0.z + v0.z * dt) + a0.z * c2) + j0.z * c3;
+    x.w = x0.w;
+    v.x = (v0.x + a0.x * dt) + j0.x * c2;
+    v.y = (v0.y + a0.y * dt) + j0.y * c2;
+    v.z = (v0.z + a0.z * dt) + j0.z * c2;
+    v.w = 0.0;
+    xp[k] = x;
+    vp[k] = v;
+}
+
 __global__ __launch_bounds__(256) void k_hm_predict(const double4* __restrict__ pos, const double4* __restrict__ vel,
                                                     const double4* __restrict__ acc, const double4* __restrict__ jerk,
                                                     const int* __restrict__ count, double4* __restrict__ xp, double4* __restrict__ vp,
                                                     HermiteCoef c) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= *count) return;
-    const double4 x0 = pos[k], v0 = vel[k], a0 = acc[k], j0 = jerk[k];
-    double4 x, v;
-    x.x = ((x0.x + v0.x * c.dt) + a0.x * c.c2) + j0.x * c.c3;
-    x.y = ((x0.y + v0.y * c.dt) + a0.y * c.c2) + j0.y * c.c3;
-    x.z = ((x0.z + v0.z * c.dt) + a0.z * c.c2) + j0.z * c.c3;
-    x.w = x0.w;
-    v.x = (v0.x + a0.x * c.dt) + j0.x * c.c2;
-    v.y = (v0.y + a0.y * c.dt) + j0.y * c.c2;
-    v.z = (v0.z + a0.z * c.dt) + j0.z * c.c2;
-    v.w = 0.0;
-    xp[k] = x;
-    vp[k] = v;
+    predict_one(k, pos, vel, acc, jerk, xp, vp, c.dt, c.c2, c.c3);
 }
 
 // the corrector of body k, in place, and Bounds::contains (shared.rs:210-212: inclusive walls, a NaN is outside)
@@ -338,6 +335,30 @@ __global__ __launch_bounds__(256) void k_hm_sym(const double4* __restrict__ pos,
 }
 
 // ------------------------------------------------------------------------------------------ fast F, one-sided
+// what body j does to body i, one pair (k_hm_os, k_hm_act); self: the i == j pair, which is never formed (with g_soft = 0 its
+// rsqrt is inf)
+__device__ __forceinline__ void one_pair_hm(const double4 pi, const double4 vi, const double4 pj, const double4 vj, bool self, double eps2,
+                                            double& ax, double& ay, double& az, double& jx, double& jy, double& jz) {
+    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+    double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
+    const double q = fma(dz, dz, fma(dy, dy, fma(dx, dx, eps2)));
+    const double rv = fma(dz, wz, fma(dy, wy, dx * wx));
+    double rinv = rsqrt(q);
+    rinv = self ? 0.0 : rinv;
+    const double rinv2 = rinv * rinv;
+    const double nal = (-3.0 * rinv2) * rv;
+    const double sj = pj.w * (rinv2 * rinv);
+    wx = fma(nal, dx, wx);
+    wy = fma(nal, dy, wy);
+    wz = fma(nal, dz, wz);
+    ax = fma(dx, sj, ax);
+    ay = fma(dy, sj, ay);
+    az = fma(dz, sj, az);
+    jx = fma(wx, sj, jx);
+    jy = fma(wy, sj, jy);
+    jz = fma(wz, sj, jz);
+}
+
 // 4 waves per workgroup; wave gw = group * K + slice: bodies group*64 + lane against slice `slice` of the partner list
 // (MODE 0: every own body; MODE 1: the own set and, for even A, the opposite set).  Output: plane `slice`, rows
 // group*64 .. group*64+63 (every row, padding included).
@@ -391,24 +412,7 @@ __global__ __launch_bounds__(256) void k_hm_os(const double4* __restrict__ pos, 
                 for (int t = 0; t < cnt; ++t) {
                     const double4 pj = tile[wv][0][t];   // wave-uniform address: an LDS broadcast
                     const double4 vj = tile[wv][1][t];
-                    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
-                    double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
-                    const double q = fma(dz, dz, fma(dy, dy, fma(dx, dx, eps2v)));
-                    const double rv = fma(dz, wz, fma(dy, wy, dx * wx));
-                    double rinv = rsqrt(q);
-                    rinv = (c0 + t == self) ? 0.0 : rinv;   // the i == j pair is never formed (with g_soft = 0 its rsqrt is inf)
-                    const double rinv2 = rinv * rinv;
-                    const double nal = (-3.0 * rinv2) * rv;
-                    const double sj = pj.w * (rinv2 * rinv);
-                    wx = fma(nal, dx, wx);
-                    wy = fma(nal, dy, wy);
-                    wz = fma(nal, dz, wz);
-                    ax = fma(dx, sj, ax);
-                    ay = fma(dy, sj, ay);
-                    az = fma(dz, sj, az);
-                    jx = fma(wx, sj, jx);
-                    jy = fma(wy, sj, jy);
-                    jz = fma(wz, sj, jz);
+                    one_pair_hm(pi, vi, pj, vj, c0 + t == self, eps2v, ax, ay, az, jx, jy, jz);
                 }
             }
         }
@@ -430,15 +434,8 @@ __global__ __launch_bounds__(256) void k_hm_reduce(const double4* __restrict__ p
     const int n = *count;
     if (inter && i == 0 && n > 0) atomicAdd(inter, (unsigned long long)n * (unsigned long long)(n - 1));
     if (i >= n) return;
-    double sx = 0.0, sy = 0.0, sz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-    for (int p = 0; p < n_planes; ++p) {
-        const double4 va = planes[size_t(p) * plane_stride + i];
-        const double4 vj = planes[jerk_off + size_t(p) * plane_stride + i];
-        sx += va.x; sy += va.y; sz += va.z;
-        tx += vj.x; ty += vj.y; tz += vj.z;
-    }
-    const double4 a1 = make_double4(g * sx, g * sy, g * sz, 0.0);
-    const double4 j1 = make_double4(g * tx, g * ty, g * tz, 0.0);
+    double4 a1, j1;
+    plane_sum<2>(planes, n_planes, plane_stride, jerk_off, i, g, a1, j1);
     if (CORRECT) correct_one(i, a1, j1, pos, vel, acc, jerk, keep, escaped, c, b);
     else { out_a[i] = a1; out_j[i] = j1; }
 }
@@ -503,7 +500,7 @@ __global__ __launch_bounds__(kTile) void k_hmb_count(const int* __restrict__ tau
     }
 }
 
-// the due bodies' indices, ascending, into list; every body predicted to tau* (k_hm_predict's expressions with the body's own
+// the due bodies' indices, ascending, into list; every body predicted to tau* (predict_one with the body's own
 // dp = f64(tau* - tau_i) tick and hermite_coef's c2, c3); the last tile reports {tau*, how many are due}
 __global__ __launch_bounds__(kTile) void k_hmb_list(const double4* __restrict__ pos, const double4* __restrict__ vel, const double4* __restrict__ acc,
                                                     const double4* __restrict__ jerk, const int* __restrict__ tau, const int* __restrict__ level,
@@ -523,18 +520,7 @@ __global__ __launch_bounds__(kTile) void k_hmb_list(const double4* __restrict__ 
         due = tk + (T >> level[k]) == tstar;
         const double dp = double(tstar - tk) * tick;
         const double c2 = (dp * dp) * 0.5, c3 = ((dp * dp) * dp) / 6.0;
-        const double4 x0 = pos[k], v0 = vel[k], a0 = acc[k], j0 = jerk[k];
-        double4 x, v;
-        x.x = ((x0.x + v0.x * dp) + a0.x * c2) + j0.x * c3;
-        x.y = ((x0.y + v0.y * dp) + a0.y * c2) + j0.y * c3;
-        x.z = ((x0.z + v0.z * dp) + a0.z * c2) + j0.z * c3;
-        x.w = x0.w;
-        v.x = (v0.x + a0.x * dp) + j0.x * c2;
-        v.y = (v0.y + a0.y * dp) + j0.y * c2;
-        v.z = (v0.z + a0.z * dp) + j0.z * c2;
-        v.w = 0.0;
-        xp[k] = x;
-        vp[k] = v;
+        predict_one(k, pos, vel, acc, jerk, xp, vp, dp, c2, c3);
     }
     int before_tiles = 0;   // due bodies of the tiles below this one: integer sums, any order
     for (int t = tid; t < tile; t += kTile) before_tiles += tile_count[t];
@@ -554,7 +540,7 @@ __global__ __launch_bounds__(kTile) void k_hmb_list(const double4* __restrict__ 
 
 // NBODY_MATH_FAST: F of the listed bodies.  4 waves per workgroup; wave gw = group * K + slice: the bodies list[group*64 + lane]
 // against partners [n slice / K, n (slice + 1) / K) of ALL n bodies of (x, v), staged 64 at a time through the wave's own LDS
-// tile (k_hm_os<0>'s loop and arithmetic).  Output: plane `slice`, rows group*64 .. group*64+63: every row of every plane is
+// tile (k_hm_os<0>'s loop; one_pair_hm).  Output: plane `slice`, rows group*64 .. group*64+63: every row of every plane is
 // written exactly once, padding rows and empty slices included.
 __global__ __launch_bounds__(256) void k_hm_act(const double4* __restrict__ x, const double4* __restrict__ v, const int* __restrict__ count,
                                                 const int* __restrict__ list, const int* __restrict__ n_act_p, int groups, int K,
@@ -584,24 +570,7 @@ __global__ __launch_bounds__(256) void k_hm_act(const double4* __restrict__ x, c
         for (int t = 0; t < cnt; ++t) {
             const double4 pj = tile[wv][0][t];   // wave-uniform address: an LDS broadcast
             const double4 vj = tile[wv][1][t];
-            const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
-            double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
-            const double q = fma(dz, dz, fma(dy, dy, fma(dx, dx, eps2v)));
-            const double rv = fma(dz, wz, fma(dy, wy, dx * wx));
-            double rinv = rsqrt(q);
-            rinv = (c0 + t == i) ? 0.0 : rinv;   // the i == j pair is never formed (with g_soft = 0 its rsqrt is inf)
-            const double rinv2 = rinv * rinv;
-            const double nal = (-3.0 * rinv2) * rv;
-            const double sj = pj.w * (rinv2 * rinv);
-            wx = fma(nal, dx, wx);
-            wy = fma(nal, dy, wy);
-            wz = fma(nal, dz, wz);
-            ax = fma(dx, sj, ax);
-            ay = fma(dy, sj, ay);
-            az = fma(dz, sj, az);
-            jx = fma(wx, sj, jx);
-            jy = fma(wy, sj, jy);
-            jz = fma(wz, sj, jz);
+            one_pair_hm(pi, vi, pj, vj, c0 + t == i, eps2v, ax, ay, az, jx, jy, jz);
         }
     }
     const size_t row = size_t(slice) * plane_stride + size_t(p);
@@ -668,15 +637,7 @@ __global__ __launch_bounds__(256) void k_hmb_finish(const double4* __restrict__ 
     if (p >= n_act) return;
     double4 a1, j1;
     if (PLANES) {
-        double sx = 0.0, sy = 0.0, sz = 0.0, tx = 0.0, ty = 0.0, tz = 0.0;
-        for (int q = 0; q < n_planes; ++q) {
-            const double4 va = planes[size_t(q) * plane_stride + p];
-            const double4 vj = planes[jerk_off + size_t(q) * plane_stride + p];
-            sx += va.x; sy += va.y; sz += va.z;
-            tx += vj.x; ty += vj.y; tz += vj.z;
-        }
-        a1 = make_double4(g * sx, g * sy, g * sz, 0.0);
-        j1 = make_double4(g * tx, g * ty, g * tz, 0.0);
+        plane_sum<2>(planes, n_planes, plane_stride, jerk_off, p, g, a1, j1);
     } else {
         a1 = in_a[p];
         j1 = in_j[p];

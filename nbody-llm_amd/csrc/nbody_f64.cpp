@@ -18,29 +18,34 @@
 
 namespace nbody64 {
 
+// What a fast all-pairs plane pass keeps between calls: kernels_bf64.hip's plan, re-made when its key (the body counts and
+// the knobs) changes, the unordered pairs its symmetric kernel meets, and the partial-sum planes (grow only) -- `kinds` planes
+// of double4[n_pad] per plane of the plan: 1, the accelerations; 2, the jerks after them (kernels_hermite.h).  ipt_of: the
+// bodies per lane the pass's kernels take for a bf64_ipt knob (nullptr: make_bf64_plan's own choice).
+struct PlanePass {
+    const int kinds;
+    int (*const ipt_of)(int bf64_ipt);
+    Bf64Plan plan;
+    long long key[6] = {-1, -1, -1, -1, -1, -1};
+    uint64_t sym_pairs = 0;
+    double4* d_planes = nullptr;
+    size_t cap = 0;   // double4 entries
+    int ensure(NbodyHandle* h, size_t n_local, size_t n_remote, int n_seg);
+};
+
 struct State : BodyStore<double> {   // (the bodies, their host view and the settings: nbody_handle.h)
     TreeStore<double> tree;    // Barnes-Hut: the tree, its device arrays, the device build's buffers, the walk's split and stack
     double* d_energy = nullptr;
     size_t energy_blocks = 0;
     const double* kick_dt = nullptr;   // inside a step: the dt the force pass may apply itself (fast walk, split node range)
     int kicked = 0;
-    // fast brute force (NBODY_MATH_FAST): kernels_bf64.hip's plan, re-made when the body counts or the knobs change, and
-    // its partial-sum planes (grow only)
-    Bf64Plan bf_plan;
-    long long bf_plan_key[6] = {-1, -1, -1, -1, -1, -1};
-    uint64_t bf_sym_pairs = 0;
-    double4* d_planes = nullptr;
-    size_t planes_cap = 0;        // double4 entries
+    PlanePass bf{1, nullptr};          // fast brute force (NBODY_MATH_FAST): one kind of planes
     // nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): the held jerk, the predicted state and the pair-jerk planes
     // (kernels_hermite.h); acc holds the held a0.  hm_valid: (acc, jerk) are F at the current (pos, vel)
     int integrator = NBODY_INTEGRATOR_LEAPFROG;
     bool hm_valid = false;
     HermiteDev hm;
-    Bf64Plan hm_plan;
-    long long hm_plan_key[5] = {-1, -1, -1, -1, -1};
-    uint64_t hm_sym_pairs = 0;
-    double4* d_hm_planes = nullptr;
-    size_t hm_planes_cap = 0;     // double4 entries
+    PlanePass hmp{2, hermite_ipt};     // the pair-jerk pass: two kinds
     // nbody_set_block_steps: block individual time steps of a Hermite handle (off: blk_L == 0).  lv_valid: blk.level holds
     // levels assigned for a macro step of |dt| == lv_dt from derivatives that are still the held ones (needs hm_valid too)
     double blk_eta = 0.0;
@@ -52,25 +57,45 @@ struct State : BodyStore<double> {   // (the bodies, their host view and the set
     uint64_t blk_steps = 0, blk_updates = 0;   // since nbody_reset_stats
 };
 
+// The plan and the planes for this many own and remote bodies under the current knobs (make_bf64_plan's arguments).  A failed
+// allocation leaves no plan behind (the next pass tries again); the key is set only once the planes exist for this plan.
+int PlanePass::ensure(NbodyHandle* h, size_t n_local, size_t n_remote, int n_seg) {
+    const nbody::Tuning& t = nbody::tuning();
+    const long long want[6] = {(long long)n_local, (long long)n_remote, t.bf64_min_bodies, t.bf64_ipt, t.bf64_rot, t.bf64_waves};
+    if (std::equal(want, want + 6, key)) return NBODY_OK;
+    const Bf64Plan made = make_bf64_plan(int(n_local), int(std::min<size_t>(n_remote, 0x7fffffff)), n_seg, ipt_of ? ipt_of(t.bf64_ipt) : 0);
+    const size_t need = size_t(kinds) * size_t(made.n_planes) * made.n_pad;
+    if (need > cap) {
+        if (d_planes) (void)hipFree(d_planes);
+        d_planes = nullptr; cap = 0;
+        std::fill(key, key + 6, -1LL);
+        HIP_TRY(h, hipMalloc(&d_planes, need * sizeof(double4)));
+        cap = need;
+    }
+    plan = made;
+    sym_pairs = bf64_sym_pairs(made, n_local);
+    std::copy(want, want + 6, key);
+    return NBODY_OK;
+}
+
 namespace {
 
-int ensure_bf_plan(NbodyHandle* h, State& s, size_t n_remote) {
-    const nbody::Tuning& t = nbody::tuning();
-    const long long key[6] = {(long long)s.n_local, (long long)n_remote, t.bf64_min_bodies, t.bf64_ipt, t.bf64_rot, t.bf64_waves};
-    if (std::equal(key, key + 6, s.bf_plan_key)) return NBODY_OK;
-    const Bf64Plan plan = make_bf64_plan(int(s.n_local), int(std::min<size_t>(n_remote, 0x7fffffff)), s.sh.n_seg);
-    const size_t need = size_t(plan.n_planes) * plan.n_pad;
-    if (need > s.planes_cap) {
-        if (s.d_planes) (void)hipFree(s.d_planes);
-        s.d_planes = nullptr; s.planes_cap = 0;
-        std::fill(s.bf_plan_key, s.bf_plan_key + 6, -1LL);   // (a failed allocation leaves no plan behind: the next pass tries again)
-        HIP_TRY(h, hipMalloc(&s.d_planes, need * sizeof(double4)));
-        s.planes_cap = need;
+// The own pairs of a plane pass, `sym` then `own` (launchers of the pass's kernels): every pair once by the symmetric kernel
+// + the left-over pairs one-sided or, without a symmetric part (no plan for one, or one or two resident sets: the left-over
+// pairs are all of them), every pair one-sided.  The HIP events bracket the dominant launch; returns its directed interactions.
+template <class Sym, class Own>
+uint64_t launch_own_pairs(NbodyHandle* h, const PlanePass& pp, size_t n_local, Sym sym, Own own) {
+    if (pp.plan.sym && pp.plan.sym_sets > 0) {
+        {
+            ForceTimer t(h);
+            sym();
+        }
+        own();
+        return 2 * pp.sym_pairs;
     }
-    s.bf_plan = plan;
-    s.bf_sym_pairs = bf64_sym_pairs(plan, s.n_local);
-    std::copy(key, key + 6, s.bf_plan_key);   // only once the planes exist for this plan
-    return NBODY_OK;
+    ForceTimer t(h);
+    own();
+    return uint64_t(n_local) * uint64_t(n_local - 1);
 }
 
 // NBODY_MATH_FAST: every own pair once (k_bf64_sym + the left-over pairs one-sided) or, below Tuning::bf64_min_bodies,
@@ -81,25 +106,15 @@ int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
     uint64_t tot = 0;
     for (int c : s.seg_count_host) tot += uint64_t(c);
     const size_t n_remote = size_t(tot) - std::min<size_t>(size_t(tot), size_t(s.seg_count_host[size_t(s.sh.my_seg)]));
-    int rc = ensure_bf_plan(h, s, n_remote);
+    int rc = s.bf.ensure(h, s.n_local, n_remote, s.sh.n_seg);
     if (rc) return rc;
-    const Bf64Plan& p = s.bf_plan;
-    uint64_t timed = 0;   // directed interactions of the launch the HIP events bracket (the dominant one)
-    if (p.sym && p.sym_sets > 0) {
-        {
-            ForceTimer t(h);
-            launch_bf64_sym(h->stream, s.sh, p, s.d_planes, eps2);
-        }
-        timed = 2 * s.bf_sym_pairs;
-        launch_bf64_own(h->stream, s.sh, p, s.d_planes, eps2);
-    } else {   // (with one or two resident sets the left-over pairs are all of them)
-        ForceTimer t(h);
-        launch_bf64_own(h->stream, s.sh, p, s.d_planes, eps2);
-        timed = uint64_t(s.n_local) * uint64_t(s.n_local - 1);
-    }
+    const Bf64Plan& p = s.bf.plan;
+    double4* planes = s.bf.d_planes;
+    const uint64_t timed = launch_own_pairs(h, s.bf, s.n_local, [&] { launch_bf64_sym(h->stream, s.sh, p, planes, eps2); },
+                                            [&] { launch_bf64_own(h->stream, s.sh, p, planes, eps2); });
     const bool timed_this = h->timed_this;
-    launch_bf64_remote(h->stream, s.sh, p, s.d_planes, eps2);
-    launch_bf64_reduce(h->stream, s.sh, p, s.d_planes, int(s.n_local), s.g, s.kick_dt);
+    launch_bf64_remote(h->stream, s.sh, p, planes, eps2);
+    launch_bf64_reduce(h->stream, s.sh, p, planes, int(s.n_local), s.g, s.kick_dt);
     if (s.kick_dt) s.kicked = 1;
     HIP_TRY(h, hipGetLastError());
     if (timed_this) h->stats.force_kernel_interactions += timed;
@@ -119,59 +134,29 @@ int ensure_hermite(NbodyHandle* h, State& s) {
     return NBODY_OK;
 }
 
-int ensure_hm_plan(NbodyHandle* h, State& s) {
-    const nbody::Tuning& t = nbody::tuning();
-    const long long key[5] = {(long long)s.n_local, t.bf64_min_bodies, t.bf64_ipt, t.bf64_rot, t.bf64_waves};
-    if (std::equal(key, key + 5, s.hm_plan_key)) return NBODY_OK;
-    const Bf64Plan plan = make_bf64_plan(int(s.n_local), 0, 1, hermite_ipt(t.bf64_ipt));
-    const size_t need = 2 * size_t(plan.n_planes) * plan.n_pad;                // accelerations, then jerks
-    if (need > s.hm_planes_cap) {
-        if (s.d_hm_planes) (void)hipFree(s.d_hm_planes);
-        s.d_hm_planes = nullptr; s.hm_planes_cap = 0;
-        std::fill(s.hm_plan_key, s.hm_plan_key + 5, -1LL);
-        HIP_TRY(h, hipMalloc(&s.d_hm_planes, need * sizeof(double4)));
-        s.hm_planes_cap = need;
-    }
-    s.hm_plan = plan;
-    s.hm_sym_pairs = bf64_sym_pairs(plan, s.n_local);
-    std::copy(key, key + 5, s.hm_plan_key);
-    return NBODY_OK;
-}
-
 // (a, j) = F(x, v).  c == nullptr: into (out_a, out_j); else the corrector follows (in place on pos / vel / acc / jerk, with
 // the retain's flags): a kernel of its own in strict math, inside the plane reduce in fast math.  Enqueues only.
 int hm_eval(NbodyHandle* h, State& s, const double4* x, const double4* v, double4* out_a, double4* out_j, const HermiteCoef* c) {
     if (s.n_local == 0) return NBODY_OK;
     const double eps2 = s.g_soft * s.g_soft;
-    const uint64_t all = uint64_t(s.n_local) * uint64_t(s.n_local - 1);
     if (h->cfg.math_mode != NBODY_MATH_FAST) {
         {
             ForceTimer t(h);
             launch_hm_strict(h->stream, s.sh, x, v, c ? s.hm.a1 : out_a, c ? s.hm.j1 : out_j, int(s.n_local), s.g, eps2);
         }
-        if (h->timed_this) h->stats.force_kernel_interactions += all;
+        if (h->timed_this) h->stats.force_kernel_interactions += uint64_t(s.n_local) * uint64_t(s.n_local - 1);
         if (c) launch_hm_correct(h->stream, s.sh, s.hm, int(s.n_local), *c, s.bnd);
         HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
-    int rc = ensure_hm_plan(h, s);
+    int rc = s.hmp.ensure(h, s.n_local, 0, 1);   // (one rank: nobody remote)
     if (rc) return rc;
-    const Bf64Plan& p = s.hm_plan;
-    uint64_t timed = 0;
-    if (p.sym && p.sym_sets > 0) {
-        {
-            ForceTimer t(h);
-            launch_hm_sym(h->stream, s.sh, p, x, v, s.d_hm_planes, eps2);
-        }
-        timed = 2 * s.hm_sym_pairs;
-        launch_hm_own(h->stream, s.sh, p, x, v, s.d_hm_planes, eps2);
-    } else {   // (with one or two resident sets the left-over pairs are all of them)
-        ForceTimer t(h);
-        launch_hm_own(h->stream, s.sh, p, x, v, s.d_hm_planes, eps2);
-        timed = all;
-    }
+    const Bf64Plan& p = s.hmp.plan;
+    double4* planes = s.hmp.d_planes;
+    const uint64_t timed = launch_own_pairs(h, s.hmp, s.n_local, [&] { launch_hm_sym(h->stream, s.sh, p, x, v, planes, eps2); },
+                                            [&] { launch_hm_own(h->stream, s.sh, p, x, v, planes, eps2); });
     if (h->timed_this) h->stats.force_kernel_interactions += timed;
-    launch_hm_reduce(h->stream, s.sh, s.hm, p, s.d_hm_planes, int(s.n_local), s.g, out_a, out_j, c, s.bnd);
+    launch_hm_reduce(h->stream, s.sh, s.hm, p, planes, int(s.n_local), s.g, out_a, out_j, c, s.bnd);
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
 }
@@ -465,8 +450,8 @@ void destroy(NbodyHandle* h) {
     if (!s) return;
     s->tree.release();
     s->release();
-    void* dev[] = {s->d_energy, s->d_planes,
-                   s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->d_hm_planes,
+    void* dev[] = {s->d_energy, s->bf.d_planes,
+                   s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->hmp.d_planes,
                    s->blk.level, s->blk.tau, s->blk.list, s->blk.tile_count, s->blk.smin, s->blk.planes};
     for (void* p : dev) if (p) (void)hipFree(p);
     if (s->h_sched) (void)hipHostFree(s->h_sched);

@@ -155,6 +155,46 @@ def test_probe_knobs(gpu, n, knobs):
     report(f"n={n} {knobs}", plan, cols, worst, rot=knobs.get("bf64_rot", 0))
 
 
+# ---------------------------------------------------------------------------------------------- the two pair laws
+LAW_CASES = [(65, {}), (1025, {}), (257, dict(bf64_min_bodies=2)), (513, dict(bf64_min_bodies=2)), (1025, dict(bf64_min_bodies=2))]
+
+
+@pytest.mark.parametrize("n,knobs", LAW_CASES, ids=[f"{n}-{'min2' if t else 'default'}" for n, t in LAW_CASES])
+def test_acceleration_half_of_the_hermite_law_is_the_gravity_law(gpu, n, knobs):
+    """The same f64 bodies (every body moving) through nbody_update_forces on a leapfrog handle (kernels_bf64.hip: k_bf64_sym,
+    k_bf64_os, k_bf64_reduce) and on a HERMITE4 handle (k_hm_sym, k_hm_os, k_hm_reduce), fast math: the accelerations are
+    bit-equal wherever the two plans coincide -- up to kBf64SmallIptBelow bodies both keep four bodies a lane.  Both laws form
+    rsqrt, the cube, the mass product and the three FMAs a side in the same order, over the same planes in the same order.
+    Default tuning: the one-sided kernels alone (MODE 0); bf64_min_bodies = 2: A = 2 (no symmetric part, two windows), 3 and 5
+    (one window, a last set of one body).  That the plans coincide: each handle's profiled pass must report the restated plan's
+    symmetric pairs, which pins ipt, A and sym_sets in the bf64_min_bodies = 2 cases.  In the two default cases that count is
+    n (n - 1) for any plan; there the equality of the plans (k_own, the plane count) rests on reading make_bf64_plan, which both
+    handles call and which does not look at the bodies per lane when it plans no symmetric part -- the library has no host
+    call that returns this plan."""
+    nb = gpu
+    assert n <= SMALL_IPT_BELOW
+    plan = sym_plan(n, knobs.get("bf64_min_bodies", MIN_BODIES))
+    if knobs:
+        assert plan["sym"] and (plan["ipt"], plan["A"], plan["sym_sets"]) == {257: (4, 2, 0), 513: (4, 3, 1), 1025: (4, 5, 2)}[n]
+    else:
+        assert not plan["sym"]
+    x, v, m = hr.world(n)
+    assert np.abs(v).min() > 0.0
+    rec = hr.records(nb.PARTICLE_DTYPE64, x, v, m)
+    with nb.Simulation(rec, *BOX, method=nb.BRUTE_FORCE, math_mode=nb.FAST, f64=True, tuning=knobs) as sim:
+        sim.settings = nb.Settings(g=hr.G, g_soft=hr.EPS, dt=DT, theta2=0.5)
+        sim.update_forces()
+        a_leapfrog = sim.get_points()["acceleration"]
+        assert_plan(sim, n, plan, f"leapfrog n={n} {knobs}")
+    with hermite(nb, rec, hr.G, hr.EPS, **knobs) as sim:
+        sim.update_forces()
+        a_hermite = sim.get_points()["acceleration"]
+        assert_plan(sim, n, plan, f"hermite n={n} {knobs}")
+    differ = int((np.asarray(a_leapfrog) != np.asarray(a_hermite)).any(1).sum())
+    print(f"\n[pair laws] n={n} {knobs}: {differ} of {n} accelerations differ between the leapfrog and the Hermite handle")
+    assert eq(a_leapfrog, a_hermite), f"{differ} accelerations differ"
+
+
 # ---------------------------------------------------------------------------------------------- probes, hermite_forces_of
 def act_id_lists(n, k):
     """Ascending draws (fixed seed) that reach each arm of make_hm_act_plan, and one shuffled list; body k is in three of them."""
