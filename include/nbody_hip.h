@@ -233,6 +233,29 @@ int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potent
  * at them.  NBODY_SHARD_SPATIAL handles are refused (NBODY_ERR_INVALID): a rank holds neither the world's bodies nor the tree
  * around a foreign point.  Like nbody_potentials the call leaves no trace in the state, the statistics or a later step. */
 int nbody_field_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]);
+/* The tidal tensor of the world's bodies at caller-chosen points, the gradient of nbody_field_at's acceleration, at the handle's
+ * CURRENT positions:
+ *   T_ab(x) = d acc_a / d x_b = g * sum_j m_j [ 3 d_a d_b / q^(5/2) - delta_ab / q^(3/2) ],   d = x_j - x,  q = |d|^2 + g_soft^2
+ * over ALL bodies of the world (symmetric; trace -3 g g_soft^2 sum m / q^(5/2), zero without softening).  Self-gravity only:
+ * the external field is not included.  xyz: n_points f64 triples on either dtype; an f32 handle rounds each coordinate to the
+ * nearest f32 once.  tidal6 [n_points][6] f64 = {xx, xy, xz, yy, yz, zz} (the order of nbody_tree_export_quadrupoles), in the
+ * caller's order; NULL only counts.  n_points == 0 is valid (TREE still builds its tree); n_points > 2^30, or xyz == NULL with
+ * points, is NBODY_ERR_INVALID.  counts as nbody_field_at: {terms summed, opening tests} of this call (PAIRS: 0, 0).
+ *   NBODY_POTENTIAL_PAIRS  either method, either dtype: coordinates widened to f64, everything in f64; a body at r2 == 0
+ *                          exactly is skipped, so a point on a body's stored position gets the tensor of the others.
+ *   NBODY_POTENTIAL_TREE   Barnes-Hut handles with bounds set: nbody_field_at(TREE)'s tree (nbody_tree_export reports it
+ *                          afterwards) and opening tests -- r2 in the handle's precision, a node with r2 < 1e-10 skipped whole,
+ *                          w2 < theta2 * r2 accepts, a leaf that fails is evaluated whatever leaf_mode -- so counts equal
+ *                          nbody_field_at(TREE)'s for the same points.  Monopole terms in the handle's precision, six f64 sums.
+ *   NBODY_POTENTIAL_TREE_QUADRUPOLE is refused (NBODY_ERR_INVALID): the quadrupole term's share of the tensor is out of scope.
+ * A term, every line one rounding (IEEE sqrt and divide, no contraction): inv = 1 / sqrt(q), st = m inv, k = st / q,
+ * k3 = (3 k) / q, u_c = d_c k3; xx += dx u_x - k (yy, zz alike), xy += dx u_y, xz += dx u_z, yz += dy u_z; each sum times g once.
+ * math_mode has no influence.  A point with a non-finite coordinate gets six NaNs and disturbs no other point; under TREE a
+ * finite point so far away that r2 overflows in the handle's precision gets exact zeros.  The same call twice gives the same
+ * bits, and permuting the points permutes the rows bit for bit.  Accepted wherever nbody_field_at accepts the mode: collective
+ * on a world of index-block shards (every rank passes its own points); NBODY_SHARD_SPATIAL handles are refused.  Like
+ * nbody_field_at the call leaves no trace in the state, the statistics, the tracers or a later step. */
+int nbody_tidal_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* tidal6, uint64_t counts[2]);
 /* ---- quadrupole terms in the tree potentials: NBODY_POTENTIAL_TREE_QUADRUPOLE (no reference counterpart) --------
  * A mode of nbody_potentials, nbody_energy_world and nbody_field_at, chosen per call and independent of nbody_set_multipole
  * (which concerns the force pass only).  Everything that defines NBODY_POTENTIAL_TREE holds: the tree nbody_update_forces

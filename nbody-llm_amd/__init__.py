@@ -80,7 +80,7 @@ DECLARED_SYMBOLS = [
     "nbody_debug_let_bounds", "nbody_debug_let_set_balance",
     "nbody_comm_local_id", "nbody_comm_transport", "nbody_host_exchange_layout",
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
-    "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at",
+    "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at", "nbody_tidal_at",
     "nbody_set_multipole", "nbody_get_multipole", "nbody_tree_export_quadrupoles",
     "nbody_set_integrator", "nbody_get_integrator", "nbody_download_jerk", "nbody_suggest_dt",
     "nbody_set_block_steps", "nbody_get_block_steps", "nbody_download_levels", "nbody_block_step_counts",
@@ -154,6 +154,7 @@ _sig("nbody_energy", _i, _H, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_potentials", _i, _H, _i, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
 _sig("nbody_energy_world", _i, _H, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_field_at", _i, _H, _i, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64))
+_sig("nbody_tidal_at", _i, _H, _i, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_uint64))
 _sig("nbody_tree_export", _i, _H, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_set_multipole", _i, _H, _i)
 _sig("nbody_get_multipole", _i, _H, C.POINTER(_i))
@@ -297,6 +298,12 @@ def host_external_eval(comps, g: float, points, acc: bool = True, phi: bool = Tr
     if rc:
         raise NbodyError(rc, (lib.nbody_last_error(None) or b"").decode())
     return a, v
+
+
+def tidal_matrices(t6) -> np.ndarray:
+    """[n, 3, 3] symmetric matrices from Simulation.tidal_at's [n, 6] rows {xx, xy, xz, yy, yz, zz}."""
+    t6 = np.asarray(t6, np.float64).reshape(-1, 6)
+    return t6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
 
 
 def device_count() -> int:
@@ -626,6 +633,18 @@ class Simulation:
         self._check(lib.nbody_field_at(self._h, int(mode), xyz.ctypes.data if m else None, m, a.ctypes.data if acc else None,
                                        p.ctypes.data if phi else None, counts))
         return a, p, (int(counts[0]), int(counts[1]))
+
+    def tidal_at(self, points, mode: int = POTENTIAL_PAIRS, counts: bool = False):
+        """The tidal tensor d acc_a / d x_b of ALL bodies of the world at the M given points (any array-like [M, 3]), at the
+        current positions: [M, 6] f64 rows {xx, xy, xz, yy, yz, zz} (tidal_matrices() expands them); counts=True: (rows,
+        (terms summed, opening tests)).  Self-gravity only; collective on a multi-rank world.  An f32 handle evaluates at the
+        points rounded to f32.  mode: POTENTIAL_PAIRS or POTENTIAL_TREE (monopole terms over field_at's tree and tests)."""
+        xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+        m = len(xyz)
+        t6 = np.zeros((m, 6), np.float64)
+        c = (C.c_uint64 * 2)()
+        self._check(lib.nbody_tidal_at(self._h, int(mode), xyz.ctypes.data if m else None, m, t6.ctypes.data, c))
+        return (t6, (int(c[0]), int(c[1]))) if counts else t6
 
     def energy_world(self, mode: int = POTENTIAL_PAIRS) -> tuple[float, float]:
         """(KE, PE) of the whole world, the same on every rank; collective.  mode as potentials(): POTENTIAL_TREE_QUADRUPOLE

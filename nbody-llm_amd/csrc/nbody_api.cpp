@@ -1533,20 +1533,49 @@ int nbody_potentials(NbodyHandle* h, int mode, double* phi, size_t cap, size_t* 
     return nbody::pot::download(h, n, g, phi, cap, n_out, counts);
 }
 
+namespace {
+// what nbody_field_at and nbody_tidal_at (`who`) share: the checks of the probes and potentials_device(.., field = true)
+int probes_begin(NbodyHandle* h, const char* who, int mode, const double* xyz, size_t n_points, nbody::PotBodies* bodies, double* g) {
+    if (n_points > (size_t(1) << 30)) return fail(h, NBODY_ERR_INVALID, std::string(who) + ": n_points must not exceed 2^30");
+    if (!xyz && n_points > 0) return fail(h, NBODY_ERR_INVALID, std::string(who) + ": xyz is NULL");
+    h->field.n_points = n_points;
+    h->field.nodes = nullptr; h->field.n_nodes = 0; h->field.K = 1; h->field.quad = nullptr;
+    size_t n = 0;
+    return potentials_device(h, mode, &n, bodies, g, true);
+}
+}  // namespace
+
 int nbody_field_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]) {
     if (!h) return NBODY_ERR_INVALID;
     int rc = use_device(h);
     if (rc) return rc;
-    if (n_points > (size_t(1) << 30)) return fail(h, NBODY_ERR_INVALID, "nbody_field_at: n_points must not exceed 2^30");
-    if (!xyz && n_points > 0) return fail(h, NBODY_ERR_INVALID, "nbody_field_at: xyz is NULL");
-    h->field.n_points = n_points;
-    h->field.nodes = nullptr; h->field.n_nodes = 0; h->field.K = 1; h->field.quad = nullptr;
-    size_t n = 0;
     nbody::PotBodies bodies;
     double g = 0.0;
-    rc = potentials_device(h, mode, &n, &bodies, &g, true);
+    rc = probes_begin(h, "nbody_field_at", mode, xyz, n_points, &bodies, &g);
     if (rc) return rc;
-    return nbody::field::run(h, mode, bodies, g, xyz, n_points, acc, phi, counts);
+    nbody::field::Out out;
+    out.acc = acc; out.phi = phi;
+    return nbody::field::run(h, mode, bodies, g, xyz, n_points, out, counts);
+}
+
+int nbody_tidal_at(NbodyHandle* h, int mode, const double* xyz, size_t n_points, double* tidal6, uint64_t counts[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (mode == NBODY_POTENTIAL_TREE_QUADRUPOLE)
+        return fail(h, NBODY_ERR_INVALID, "nbody_tidal_at: NBODY_POTENTIAL_TREE_QUADRUPOLE is not supported (the quadrupole term's share of the tensor is out of scope): NBODY_POTENTIAL_TREE is the tree mode");
+    if (h->let)
+        return fail(h, NBODY_ERR_INVALID, "nbody_tidal_at is not possible on NBODY_SHARD_SPATIAL handles: a rank holds neither the world's bodies nor the tree around a foreign point");
+    nbody::PotBodies bodies;
+    double g = 0.0;
+    rc = probes_begin(h, "nbody_tidal_at", mode, xyz, n_points, &bodies, &g);
+    if (rc) {   // (the preparation's refusals do not know who asked)
+        const std::string why = h->err;
+        return why.find("nbody_tidal_at") == std::string::npos ? fail(h, rc, "nbody_tidal_at: " + why) : rc;
+    }
+    nbody::field::Out out;
+    out.tidal6 = tidal6; out.tidal = true;
+    return nbody::field::run(h, mode, bodies, g, xyz, n_points, out, counts);
 }
 
 int nbody_energy_world(NbodyHandle* h, int mode, double* kinetic, double* potential) {

@@ -1,7 +1,8 @@
-// nbody_field.h -- host side of nbody_field_at for handles of either dtype (nbody_field.cpp).
+// nbody_field.h -- host side of nbody_field_at and nbody_tidal_at for handles of either dtype (nbody_field.cpp).
 #pragma once
 #include "nbody_handle.h"
 #include "kernels_field.h"
+#include "kernels_tidal.h"
 
 namespace nbody { namespace field {
 
@@ -9,6 +10,14 @@ namespace nbody { namespace field {
 // counters are zeroed.  Sends the probes through the device in batches of kFieldBatch: TREE sorts each batch by Morton key,
 // walks it and scatters back in the reduce; PAIRS sums K slices of the body list.  K is chosen once per call, so a probe's
 // bits do not depend on the batch or the lane it lands in.
-int run(NbodyHandle* h, int mode, const PotBodies& b, double g, const double* xyz, size_t n_points, double* acc, double* phi, uint64_t counts[2]);
+// What the call returns: nbody_field_at acc [n][3] and phi [n]; nbody_tidal_at (tidal = true) tidal6 [n][6], through the
+// kernels of kernels_tidal.h over the same batches.  Every pointer may be null (all null: count only).
+struct Out {
+    double* acc = nullptr;
+    double* phi = nullptr;
+    double* tidal6 = nullptr;
+    bool tidal = false;
+};
+int run(NbodyHandle* h, int mode, const PotBodies& b, double g, const double* xyz, size_t n_points, const Out& out, uint64_t counts[2]);
 
 }}  // namespace nbody::field

@@ -229,8 +229,8 @@ struct PotWalkScope {
 };
 
 // nbody_field_at (nbody_field.cpp): probes go through the device in batches of at most kFieldBatch, so the scratch is bounded:
-// planes of [K <= 64][batch]{ax, ay, az, S} doubles are at most 64 * 65 536 * 32 B = 128 MiB.  Grown on demand, released in
-// free_all, not cloned.
+// planes of [K <= 64][batch]{ax, ay, az, S} doubles are at most 64 * 65 536 * 32 B = 128 MiB (nbody_tidal_at: six doubles a
+// row, 192 MiB).  Grown on demand, released in free_all, not cloned.
 struct FieldBufs {
     size_t n_points = 0;          // probes of the call under way: the walk's split count K is drawn from it, once per call
     // the tree the call's force pass built, as its last phase left it (valid until the next force pass)
@@ -246,7 +246,8 @@ struct FieldBufs {
     int* d_idx = nullptr;                     // [2][batch] place in the batch, unsorted | sorted
     void* d_sort_tmp = nullptr;
     size_t sort_bytes = 0;
-    double* d_out = nullptr;                  // [batch][3] accelerations | [batch] potentials
+    double* d_out = nullptr;                  // [batch][3] accelerations | [batch] potentials; nbody_tidal_at: [batch][6]
+    size_t out_cap = 0;                       // doubles: 4 per probe until the first nbody_tidal_at, 6 from then on
     double* d_planes = nullptr;               // [K][stride] double4 partial sums, grow-only
     size_t planes_cap = 0;                    // doubles
     void release() {

@@ -168,6 +168,12 @@ public:
         push_settings();
         check(nbody_field_at(h_, mode, xyz, n, acc, phi, counts));
     }
+    // the tidal tensor d acc_a / d x_b of all bodies at n caller-chosen points (f64 triples): tidal6 [n][6] = {xx, xy, xz, yy, yz, zz},
+    // null only counts; mode: NBODY_POTENTIAL_PAIRS or NBODY_POTENTIAL_TREE (self-gravity only, monopole terms)
+    void tidal_at(int mode, const double* xyz, size_t n, double* tidal6, uint64_t counts[2] = nullptr) {
+        push_settings();
+        check(nbody_tidal_at(h_, mode, xyz, n, tidal6, counts));
+    }
     // order of the Barnes-Hut force walk's expansion (nbody_set_multipole): NBODY_MULTIPOLE_MONOPOLE, or NBODY_MULTIPOLE_QUADRUPOLE
     // on f32 fast-math single-shard Barnes-Hut handles; from the next force pass on
     void set_multipole(int order) { check(nbody_set_multipole(h_, order)); }

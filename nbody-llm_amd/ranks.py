@@ -11,7 +11,8 @@ RCCL refuses to put two ranks on one device.  With "rccl", rank r uses device r 
 cfg (JSON): world, address (socket path), out (directory), transport, device (ipc: the shared device),
   sim {method bf|bh, math fast|strict, shard index|spatial, tree auto|host|device, leaf reference|direct, tuning {knob: value}},
   ics {kind plummer|disc, n, seed, mass_jitter (seed or null), probe (body index or null), probe_mass}, box [[cx, cy, cz], width], settings {g, g_soft, dt, theta2},
-  schedule [["steps", k] | ["step_by", dt] | ["update_forces"] | ["settings", {...}] | ["sync"] | ["potentials", "pairs" | "tree"] | ["energy_world", "pairs" | "tree"]], env {NAME: value},
+  schedule [["steps", k] | ["step_by", dt] | ["update_forces"] | ["settings", {...}] | ["sync"] | ["potentials", "pairs" | "tree"] | ["energy_world", "pairs" | "tree"] |
+    ["field_at" | "tidal_at", "pairs" | "tree", {seed, counts, span}]], env {NAME: value},
   env_by_rank {"r": {NAME: value}}.
 Every rank leaves out/rank<r>.npz (its bodies; spatial shards: + their indices in the uploaded vector) and
 out/rank<r>.json (counts, statistics, wall time of the schedule); a failing rank leaves out/rank<r>.err.
@@ -121,6 +122,13 @@ def run_schedule(nb, sim, schedule, reattach=None, record=None):
                 got = e
             if record is not None:
                 record.setdefault(op, []).append(got)
+        elif op == "tidal_at":   # ["tidal_at", "pairs" | "tree", the spec of "field_at"]: collective; a refusal is recorded
+            try:
+                got = sim.tidal_at(field_probes(item[2], sim.rank), mode_of[item[1]], counts=True)
+            except nb.NbodyError as e:
+                got = e
+            if record is not None:
+                record.setdefault(op, []).append(got)
         else:
             raise ValueError(f"unknown schedule entry {item}")
     return sim
@@ -171,9 +179,16 @@ def _rank_main(cfg: dict, rank: int, failed: list) -> None:
             else:
                 arrays[f"field_acc{k}"], arrays[f"field_phi{k}"] = got[0], got[1]
                 fields.append({"counts": list(got[2])})
+        tidals = []       # per "tidal_at" entry: {"counts": ...} with arrays["tidal<k>"], or the refusal
+        for k, got in enumerate(record.get("tidal_at", [])):
+            if isinstance(got, Exception):
+                tidals.append(refused(got))
+            else:
+                arrays[f"tidal{k}"] = got[0]
+                tidals.append({"counts": list(got[1])})
         energies = [refused(e) if isinstance(e, Exception) else list(e) for e in record.get("energy_world", [])]
         st = sim.stats()
-        meta = {"potentials": potentials, "energy_world": energies, "field_at": fields,
+        meta = {"potentials": potentials, "energy_world": energies, "field_at": fields, "tidal_at": tidals,
                 "rank": rank, "f64": bool(sim.f64), "count": int(len(pts)), "count_global": int(sim.count_global()), "wall_s": wall, "elapsed": sim.elapsed(),
                 "transport": sim.comm_transport(), "steps": int(st.steps), "interactions": int(st.interactions),
                 "node_visits": int(st.node_visits), "tree_nodes": int(st.tree_nodes), "local_range": list(sim.local_range())}
@@ -276,6 +291,9 @@ def run_world(cfg: dict, ranks_per_process: int = 1, timeout: float = 180.0) -> 
         for k, rec in enumerate(meta.get("field_at", [])):
             if f"field_phi{k}" in z:
                 rec["acc"], rec["phi"] = z[f"field_acc{k}"], z[f"field_phi{k}"]
+        for k, rec in enumerate(meta.get("tidal_at", [])):
+            if f"tidal{k}" in z:
+                rec["tidal6"] = z[f"tidal{k}"]
         results.append(meta)
     return results
 

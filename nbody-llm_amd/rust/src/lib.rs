@@ -81,6 +81,7 @@ unsafe extern "C" {
     fn nbody_steps(h: *mut NbodyHandle, k: c_int) -> c_int;
     fn nbody_update_forces(h: *mut NbodyHandle) -> c_int;
     fn nbody_sync(h: *mut NbodyHandle) -> c_int;
+    fn nbody_tidal_at(h: *mut NbodyHandle, mode: c_int, xyz: *const f64, n_points: usize, tidal6: *mut f64, counts: *mut u64) -> c_int;
     fn nbody_tree_export_cells(h: *mut NbodyHandle, min_max6: *mut f32, depth: *mut i32, cap: usize, n_nodes: *mut usize) -> c_int;
     fn nbody_set_tuning(h: *mut NbodyHandle, name: *const c_char, value: c_int) -> c_int;
     fn nbody_last_error(h: *const NbodyHandle) -> *const c_char;
@@ -339,6 +340,17 @@ impl<F: HipFloat, const METHOD: i32> HipSimulation<F, METHOD> {
     pub fn sync(&mut self) {
         let rc = unsafe { nbody_sync(self.handle) };
         self.check(rc);
+    }
+
+    /// The tidal tensor d acc_a / d x_b of all bodies at `points` (include/nbody_hip.h nbody_tidal_at): rows
+    /// {xx, xy, xz, yy, yz, zz}; `mode` 0 = the pair sum, 1 = the monopole sum over the tree (Barnes-Hut).  Self-gravity only.
+    pub fn tidal_at(&mut self, points: &[[f64; 3]], mode: i32) -> Vec<[f64; 6]> {
+        self.push_settings();
+        let mut out = vec![[0.0f64; 6]; points.len()];
+        let xyz = if points.is_empty() { std::ptr::null() } else { points.as_ptr() as *const f64 };
+        let rc = unsafe { nbody_tidal_at(self.handle, mode as c_int, xyz, points.len(), out.as_mut_ptr() as *mut f64, std::ptr::null_mut()) };
+        self.check(rc);
+        out
     }
 
     pub fn options(&self) -> &HipOptions {
