@@ -58,7 +58,7 @@ enum { NBODY_MATH_STRICT = 0, /* sqrt, (d*d)*d, g/r^3, no FMA contraction, partn
 /* where the Barnes-Hut octree is built */
 enum { NBODY_TREE_HOST = 0,    /* host, every step (north_star; barnes_hut.rs:143-183 bit for bit) */
        NBODY_TREE_DEVICE = 1,  /* device: same cells and links, centre-of-mass
-                                  sums in a different order (f64 prefix sums), so node counts may differ
+                                  sums in a different order (double-double prefix sums), so node counts may differ
                                   by a few parts in 1e4; <= 42 levels (a deeper step is built on the host).
                                   Single-shard handles enqueue their steps without any read-back */
        NBODY_TREE_AUTO = 2 };  /* NBODY_MATH_FAST -> device, NBODY_MATH_STRICT -> host (the bit-exact path);

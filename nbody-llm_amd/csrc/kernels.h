@@ -166,7 +166,7 @@ struct TreeDevWork {  // arrays of the last build (inside its workspace)
     const int* ids = nullptr;                   // sorted position -> body
     const unsigned long long* keys2 = nullptr;  // levels 21..41, defined inside groups of equal keys only
     const int* wpre = nullptr;                  // exclusive prefix sums of the bodies' weights over the sorted order (tree_scan_sorted with weights)
-    const void* incl = nullptr;                 // inclusive f64 prefix sums {m, m x, m y, m z} over the sorted bodies (4 doubles each)
+    const void* incl = nullptr;                 // inclusive prefix sums {m, m x, m y, m z} over the sorted bodies (4 doubles each: the high parts of the build's double-double sums)
 };
 struct TreeCatLists {  // sharded runs: side buffer of the device build, the part that does not depend on the position type
     int* flags = nullptr;

@@ -23,7 +23,7 @@
 //     one variable-size send/recv round; the receiver lays the nodes it HOLDS -- its slice and the imports -- out in the order
 //     of their global indices and turns every link into a position in that order (launch_assemble).
 // The walk (k_bh_walk) then runs over that array as over a complete tree: every node a body visits is there.
-// Fast math, device build; node values come from f64 prefix sums over the LOCAL sorted order, so against the single-shard
+// Fast math, device build; node values come from prefix sums over the LOCAL sorted order (the high parts of the build's double-double sums), so against the single-shard
 // device build a centre of mass can differ in its last f32 bit (counts agree to ~1e-6, tested).
 #include "kernels_let.h"
 

@@ -1,8 +1,10 @@
 // kernels_tree.hip -- device-side octree build, the fast-math alternative to
 // octree_host.cpp.  Produces the SAME cells, pre-order and skip links as
 // BarnesHutSimulation::build_tree (src/manual/barnes_hut.rs:143-183); only the centre-of-mass sums
-// differ in rounding (f64 prefix sums over the sorted bodies instead of the reference's sequential
-// f32 folds), which is why the host build stays the default and the strict path.
+// differ in rounding (double-double prefix sums over the sorted bodies instead of the reference's
+// sequential folds in F: every cell's mass and centre come out within 2 (f32) or 4 (f64) units of
+// F's rounding of the exact values, whatever the cell's size -- tests/tree_moments.py counts the
+// roundings and checks every cell), which is why the host build stays the default and the strict path.
 //
 //   1. key[k]  = the body's orthant codes on levels 0..20 (3 bits each), computed with the
 //                reference's own recurrences: code bit i set iff p[i] > center[i]
@@ -14,7 +16,9 @@
 //                delta[k-1]+1 .. delta[k] (cells that contain k and k+1 but not k-1); its leaf sits at
 //                depth max(delta[k-1], delta[k]) + 1 -- the reference splits until a body is alone.
 //   4. an exclusive scan of (opened + 1) gives every node its pre-order index; an inclusive scan of
-//                {m, m x, m y, m z} in f64 gives every cell's mass and centre of mass by subtraction.
+//                {m, m x, m y, m z} in double-double gives every cell's mass and centre of mass by subtraction
+//                (a cell of massless bodies only: mass 0 and a NaN centre, as the reference's 0 / 0, from an exact
+//                integer scan of the bodies that have mass).
 //   5. emit: one thread per body writes its opened cells and its leaf.  A cell's last body is found
 //                by binary search on the sorted keys (all keys sharing its prefix), its skip link is
 //                the pre-order index after that body's leaf.
@@ -29,6 +33,7 @@
 #include "kernels_f64.h"   // Node64: the F = f64 instantiation of the build writes 64-byte records
 
 #include <cstring>
+#include <type_traits>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/block/block_radix_sort.hpp>
@@ -43,9 +48,66 @@ namespace {
 constexpr int kLevels = 21;
 
 struct Sum4 { double m, x, y, z; };
-struct Sum4Plus {
-    __host__ __device__ Sum4 operator()(const Sum4& a, const Sum4& b) const { return Sum4{a.m + b.m, a.x + b.x, a.y + b.y, a.z + b.z}; }
-};
+// The prefix sums are double-double: hi + lo, |lo| <= ulp(hi) / 2, every component of {m, m x, m y, m z} its own pair.  A cell's
+// sums are differences of two prefixes, and a difference carries the rounding of everything sorted before the cell: in
+// plain f64 that is 2^-53 of the prefix (a two-body cell of 1e-12 dust behind a body of mass 1 lost its centre of mass
+// altogether), in double-double about 2^-100 of it (the count is in tests/tree_moments.py).
+struct DD4 { Sum4 hi, lo; };
+
+// s + e = a + b exactly (Knuth; no assumption on the sizes)
+__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+// the same for |a| >= |b| (Dekker)
+__device__ __forceinline__ void fast_two_sum(double a, double b, double& s, double& e) {
+    s = a + b;
+    e = b - (s - a);
+}
+// (ah + al) + (bh + bl), the accurate variant: the error is a few 2^-106 of |a + b| even when the high parts cancel, which is
+// what taking a difference of prefixes does
+__device__ __forceinline__ void dd_add(double ah, double al, double bh, double bl, double& rh, double& rl) {
+    double s, e, t, f;
+    two_sum(ah, bh, s, e);
+    two_sum(al, bl, t, f);
+    e += t;
+    fast_two_sum(s, e, s, e);
+    e += f;
+    fast_two_sum(s, e, rh, rl);
+}
+__device__ __forceinline__ DD4 dd4_add(const DD4& a, const DD4& b) {
+    DD4 r;
+    dd_add(a.hi.m, a.lo.m, b.hi.m, b.lo.m, r.hi.m, r.lo.m);
+    dd_add(a.hi.x, a.lo.x, b.hi.x, b.lo.x, r.hi.x, r.lo.x);
+    dd_add(a.hi.y, a.lo.y, b.hi.y, b.lo.y, r.hi.y, r.lo.y);
+    dd_add(a.hi.z, a.lo.z, b.hi.z, b.lo.z, r.hi.z, r.lo.z);
+    return r;
+}
+// upto - before, rounded to one double per component (hi of the normalised difference is the double nearest to it)
+__device__ __forceinline__ Sum4 dd4_diff(const DD4& upto, const DD4& before) {
+    Sum4 r;
+    double lo;
+    dd_add(upto.hi.m, upto.lo.m, -before.hi.m, -before.lo.m, r.m, lo);
+    dd_add(upto.hi.x, upto.lo.x, -before.hi.x, -before.lo.x, r.x, lo);
+    dd_add(upto.hi.y, upto.lo.y, -before.hi.y, -before.lo.y, r.y, lo);
+    dd_add(upto.hi.z, upto.lo.z, -before.hi.z, -before.lo.z, r.z, lo);
+    return r;
+}
+// What a body's terms are kept as between k_tree_delta_totals and k_tree_scan: f32 bodies' products fit a double, their low
+// parts are all 0 and only the high parts travel (32 bytes a body instead of 64, written once and read once); f64 bodies keep
+// the product's error.
+template <class P4> struct TermOf { using type = Sum4; };
+template <> struct TermOf<double4> { using type = DD4; };
+__device__ __forceinline__ void put_term(Sum4& dst, const DD4& t) { dst = t.hi; }
+__device__ __forceinline__ void put_term(DD4& dst, const DD4& t) { dst = t; }
+__device__ __forceinline__ DD4 get_term(const Sum4& t) { return DD4{t, Sum4{0.0, 0.0, 0.0, 0.0}}; }
+__device__ __forceinline__ DD4 get_term(const DD4& t) { return t; }
+// m * x as a double-double: exact (the FMA gives the product's rounding error; 0 for f32 inputs, whose products fit a double)
+__device__ __forceinline__ void dd_mul(double m, double x, double& hi, double& lo) {
+    hi = m * x;
+    lo = fma(m, x, -hi);
+}
 
 // the orthant codes of kLevels levels starting at level `first` (0: the sort key; kLevels: the tie-break key)
 template <class P4, class Real>
@@ -238,6 +300,7 @@ __global__ __launch_bounds__(256) void k_tree_emit(const unsigned long long* __r
                                                    const int* __restrict__ ids, const P4* __restrict__ pos,
                                                    const int* __restrict__ count, const signed char* __restrict__ delta,
                                                    const int* __restrict__ base, const Sum4* __restrict__ incl,
+                                                   const Sum4* __restrict__ incl_lo, const int* __restrict__ massive,
                                                    Real width, NodeT* __restrict__ nodes, int node_cap,
                                                    int* __restrict__ order, int* __restrict__ out_info, int want_hot,
                                                    const int* __restrict__ edge, const int* __restrict__ node_offset,
@@ -339,13 +402,19 @@ __global__ __launch_bounds__(256) void k_tree_emit(const unsigned long long* __r
             }
         }
         const int j = a;
-        const Sum4 before = (k > 0) ? incl[k - 1] : Sum4{0.0, 0.0, 0.0, 0.0};
-        const Sum4 upto = incl[j];
-        const double m = upto.m - before.m;
+        const Sum4 zero4 = Sum4{0.0, 0.0, 0.0, 0.0};
+        const DD4 before = (k > 0) ? DD4{incl[k - 1], incl_lo[k - 1]} : DD4{zero4, zero4};
+        const DD4 upto = DD4{incl[j], incl_lo[j]};
+        // a cell of massless bodies only: two prefixes associate differently, so their difference need not be 0 even where every
+        // term between them is; the count of bodies with mass is an integer scan and is exact.  Mass 0 and 0 / 0 = NaN for
+        // the centre, as the reference's fold of the cell gives
+        const bool massless = massive[j] - (k > 0 ? massive[k - 1] : 0) == 0;
+        const Sum4 cell = massless ? zero4 : dd4_diff(upto, before);
+        const double m = cell.m;
         Real w = width;
         for (int q = 0; q < d; ++q) w = w * Real(0.5);  // create_orthant halves the width exactly
         const int skip = off + ((j + 1 < n) ? base[j + 1] : total);
-        put_node(nodes, size_t(off + idx), Real((upto.x - before.x) / m), Real((upto.y - before.y) / m), Real((upto.z - before.z) / m), Real(m),
+        put_node(nodes, size_t(off + idx), Real(cell.x / m), Real(cell.y / m), Real(cell.z / m), Real(m),
                  w * w, skip, hot, -1);
     } else {                            // the body's leaf
         const int ld = max(d_prev, d_next) + 1;
@@ -422,58 +491,82 @@ __global__ void k_tree_split_anc(const unsigned long long* __restrict__ keys, co
 }
 
 // ---- the two scans of the build in three launches with a FIXED association order: per body k the exclusive
-// sum of emit_count (its first node's pre-order index) and the inclusive sum of {m, m x, m y, m z} in f64.
+// sum of emit_count (its first node's pre-order index) and the inclusive sum of {m, m x, m y, m z} in double-double.
 // rocPRIM's decoupled look-back scan combines the partial sums of earlier blocks in whatever grouping their
-// completion order allows; f64 addition is not associative, so a centre of mass would now and then differ in its last
-// f32 bit from one run to the next (seen: 1 node in 30 000, every few builds).  Here: (1) k_tree_delta_totals computes
-// delta/emit_count/the Sum4 terms and each tile's totals (1 024 bodies per tile), (2) k_tree_scan adds up the totals of
-// the tiles before its own sequentially (tile order) and scans its tile locally (Hillis-Steele in LDS: a fixed
-// pattern).  One launch each -- the separate rocPRIM integer scan (2 launches) and the three-pass Sum4 scan of
+// completion order allows; neither f64 nor double-double addition is associative, so a centre of mass would now and then
+// differ in its last bit from one run to the next (seen with f64 sums: 1 node in 30 000, every few builds).  Here: (1) k_tree_delta_totals computes
+// delta/emit_count/the Sum4 terms and each tile's totals (256 or 1 024 bodies per tile: scan_items), (2) k_tree_scan adds up the totals of
+// the tiles before its own sequentially (tile order) and scans its tile locally (block_scan: shuffles inside a wave,
+// the four wave totals in LDS: a fixed pattern).  One launch each -- the separate rocPRIM integer scan (2 launches) and the three-pass Sum4 scan of
 // round 1 cost 7 launches of ~5 us with k_tree_delta.
-constexpr int kScanThreads = 256, kScanItems = 4, kScanTile = kScanThreads * kScanItems;
+// ITEMS bodies per thread, kScanThreads * ITEMS per tile: 1 up to kScanSmall bodies (256 workgroups at 65 536 bodies: the two
+// kernels move ~150 bytes per body and 64 workgroups left three quarters of the CUs idle), 4 beyond (every workgroup adds up
+// the totals of all tiles before it, which grows with the square of their number).  Chosen from the launch's body bound, so
+// the association pattern is a function of that bound alone.
+constexpr int kScanThreads = 256, kScanSmall = 1 << 18;
+constexpr int scan_items(int n_upper) { return n_upper <= kScanSmall ? 1 : 4; }
 
-__device__ __forceinline__ Sum4 sum4_add(const Sum4& a, const Sum4& b) { return Sum4{a.m + b.m, a.x + b.x, a.y + b.y, a.z + b.z}; }
+struct ScanItem { DD4 s; int c; int w; int z; int pad; };   // DD4 terms, nodes emitted, weight (spatial shards), bodies with mass
+__device__ __forceinline__ ScanItem item_add(const ScanItem& a, const ScanItem& b) { return ScanItem{dd4_add(a.s, b.s), a.c + b.c, a.w + b.w, a.z + b.z, 0}; }
+__device__ __forceinline__ ScanItem item_zero() { return ScanItem{DD4{Sum4{0.0, 0.0, 0.0, 0.0}, Sum4{0.0, 0.0, 0.0, 0.0}}, 0, 0, 0, 0}; }
 
-struct ScanItem { Sum4 s; int c; int w; };   // Sum4 terms, nodes emitted, weight (spatial shards; rides in the padding)
-__device__ __forceinline__ ScanItem item_add(const ScanItem& a, const ScanItem& b) { return ScanItem{sum4_add(a.s, b.s), a.c + b.c, a.w + b.w}; }
+// A ScanItem one lane up (every lane of the wave calls it)
+__device__ __forceinline__ ScanItem item_shfl_up(const ScanItem& a, int d) {
+    ScanItem r;
+    r.s.hi.m = __shfl_up(a.s.hi.m, d, 64); r.s.hi.x = __shfl_up(a.s.hi.x, d, 64); r.s.hi.y = __shfl_up(a.s.hi.y, d, 64); r.s.hi.z = __shfl_up(a.s.hi.z, d, 64);
+    r.s.lo.m = __shfl_up(a.s.lo.m, d, 64); r.s.lo.x = __shfl_up(a.s.lo.x, d, 64); r.s.lo.y = __shfl_up(a.s.lo.y, d, 64); r.s.lo.z = __shfl_up(a.s.lo.z, d, 64);
+    r.c = __shfl_up(a.c, d, 64); r.w = __shfl_up(a.w, d, 64); r.z = __shfl_up(a.z, d, 64); r.pad = 0;
+    return r;
+}
 
-// inclusive scan of one value per thread over the block (Hillis-Steele in LDS: a fixed pattern)
+// Scan of one value per thread over the block: returns the inclusive sum, `excl` the exclusive one.  Inside a wave of 64 the
+// items move through registers (6 shuffle rounds, no LDS and no barrier: the 80-byte items made the 8 LDS rounds of a
+// Hillis-Steele scan over 256 threads, two barriers each, cost 4 % of a Barnes-Hut step at 65 536 bodies); the THREADS / 64 wave totals
+// meet in LDS and every wave adds the ones before it in wave order.  A fixed pattern: every build associates alike.
+// Every thread of the block calls it.  lds: THREADS / 64 items.
 template <int THREADS>
-__device__ __forceinline__ ScanItem block_inclusive_scan(ScanItem v, ScanItem* lds) {
-    const int t = threadIdx.x;
-    lds[t] = v;
+__device__ __forceinline__ ScanItem block_scan(ScanItem v, ScanItem* lds, ScanItem& excl) {
+    static_assert(THREADS % 64 == 0, "whole waves");
+    const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const ScanItem up = item_shfl_up(v, off);
+        if (lane >= off) v = item_add(up, v);
+    }
+    const ScanItem prev = item_shfl_up(v, 1);
+    __syncthreads();   // (whoever still reads lds from an earlier scan is done)
+    if (lane == 63) lds[wave] = v;
     __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        ScanItem add = ScanItem{Sum4{0.0, 0.0, 0.0, 0.0}, 0, 0};
-        const bool has = t >= off;
-        if (has) add = lds[t - off];
-        __syncthreads();
-        if (has) { v = item_add(add, v); lds[t] = v; }
-        __syncthreads();
+    ScanItem before = item_zero();
+    for (int w = 0; w < wave; ++w) before = item_add(before, lds[w]);
+    excl = lane > 0 ? prev : item_zero();
+    if (wave > 0) {
+        v = item_add(before, v);
+        excl = lane > 0 ? item_add(before, excl) : before;
     }
     return v;
 }
 
 // per sorted body k: delta[k] (common levels with its right neighbour), emit_count[k] (cells it opens + its leaf), the
-// Sum4 term; per tile of kScanTile bodies: the totals of both
-template <class P4>
+// Sum4 term; per tile of kScanThreads * ITEMS bodies: the totals of both
+template <class P4, int ITEMS>
 __global__ __launch_bounds__(kScanThreads) void k_tree_delta_totals(const unsigned long long* __restrict__ keys,
                                                                      const unsigned long long* __restrict__ keys2,
                                                                      const int* __restrict__ ids, const P4* __restrict__ pos,
                                                                      const int* __restrict__ count, signed char* __restrict__ delta,
-                                                                     int* __restrict__ emit_count, Sum4* __restrict__ sums,
-                                                                     int* __restrict__ flags, ScanItem* __restrict__ totals,
+                                                                     int* __restrict__ emit_count, typename TermOf<P4>::type* __restrict__ sums,
+                                                                     int* __restrict__ massive, int* __restrict__ flags, ScanItem* __restrict__ totals,
                                                                      const int* __restrict__ edge, const float4* __restrict__ weight_src,
                                                                      int* __restrict__ weight) {
-    __shared__ ScanItem lds[kScanThreads];
+    __shared__ ScanItem lds[kScanThreads / 64];
     const int n = *count;
     // spatial shards (nbody_let.cpp): this rank's sorted bodies are a contiguous piece of the GLOBAL sorted order, and
     // its first and last body have a neighbour on another rank: edge[0] / edge[1] = levels they share with it (-1: none)
     const int edge_prev = edge ? edge[0] : -1, edge_next = edge ? edge[1] : -1;
-    const int k0 = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-    ScanItem v = ScanItem{Sum4{0.0, 0.0, 0.0, 0.0}, 0, 0};
+    const int k0 = blockIdx.x * (kScanThreads * ITEMS) + threadIdx.x * ITEMS;
+    ScanItem v = item_zero();
 #pragma unroll
-    for (int q = 0; q < kScanItems; ++q) {
+    for (int q = 0; q < ITEMS; ++q) {
         const int k = k0 + q;
         if (k >= n) break;
         const int d_next = (k + 1 < n) ? common_levels2(keys, keys2, k, k + 1) : edge_next;
@@ -484,64 +577,73 @@ __global__ __launch_bounds__(kScanThreads) void k_tree_delta_totals(const unsign
         emit_count[k] = ec;
         const int id = ids[k];
         const P4 p = pos[id];
-        const Sum4 t = Sum4{double(p.w), double(p.w) * double(p.x), double(p.w) * double(p.y), double(p.w) * double(p.z)};
-        sums[k] = t;
+        DD4 t;
+        t.hi.m = double(p.w); t.lo.m = 0.0;
+        dd_mul(double(p.w), double(p.x), t.hi.x, t.lo.x);
+        dd_mul(double(p.w), double(p.y), t.hi.y, t.lo.y);
+        dd_mul(double(p.w), double(p.z), t.hi.z, t.lo.z);
+        put_term(sums[k], t);
+        const int has_mass = p.w != 0 ? 1 : 0;
+        massive[k] = has_mass;
         int w = 0;
         if (weight_src) { w = body_weight(weight_src[id].w); weight[k] = w; }
-        v = item_add(v, ScanItem{t, ec, w});
+        v = item_add(v, ScanItem{t, ec, w, has_mass, 0});
     }
-    v = block_inclusive_scan<kScanThreads>(v, lds);
+    ScanItem excl;
+    v = block_scan<kScanThreads>(v, lds, excl);
     if (threadIdx.x == kScanThreads - 1) totals[blockIdx.x] = v;
 }
 
 // base[k] = exclusive scan of emit_count, incl[k] = inclusive scan of the Sum4 terms
-__global__ __launch_bounds__(kScanThreads) void k_tree_scan(const int* __restrict__ emit_count, const Sum4* __restrict__ sums,
+template <class Term, int ITEMS>
+__global__ __launch_bounds__(kScanThreads) void k_tree_scan(const int* __restrict__ emit_count, const Term* __restrict__ sums,
                                                             const int* __restrict__ count, const ScanItem* __restrict__ totals,
-                                                            int* __restrict__ base, Sum4* __restrict__ incl, int* __restrict__ out_info,
+                                                            int* __restrict__ base, Sum4* __restrict__ incl, Sum4* __restrict__ incl_lo,
+                                                            int* __restrict__ massive /* in: per body 0 / 1; out: inclusive prefix */,
+                                                            int* __restrict__ out_info,
                                                             int* __restrict__ weight /* in: per body; out: exclusive prefix; may be null */) {
-    __shared__ ScanItem lds[kScanThreads];
+    __shared__ ScanItem lds[kScanThreads / 64];
     __shared__ ScanItem carry_s;
     const int n = *count;
-    const int k0 = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
-    if (blockIdx.x * kScanTile >= n) return;
+    const int k0 = blockIdx.x * (kScanThreads * ITEMS) + threadIdx.x * ITEMS;
+    if (blockIdx.x * (kScanThreads * ITEMS) >= n) return;
     // the totals of the tiles before this one: thread t adds its run of consecutive tiles, the block scans the 256
     // partial sums -- a fixed pattern that depends on the tile index only, so every build associates alike (one
     // thread adding 64 totals one after the other was a 16 us chain of dependent loads)
     {
         const int before = int(blockIdx.x);
         const int per = (before + kScanThreads - 1) / kScanThreads;
-        ScanItem run = ScanItem{Sum4{0.0, 0.0, 0.0, 0.0}, 0, 0};
+        ScanItem run = item_zero();
         for (int q = 0; q < per; ++q) {
             const int b = int(threadIdx.x) * per + q;
             if (b < before) run = item_add(run, totals[b]);
         }
-        const ScanItem all = block_inclusive_scan<kScanThreads>(run, lds);
+        ScanItem unused;
+        const ScanItem all = block_scan<kScanThreads>(run, lds, unused);
         if (threadIdx.x == kScanThreads - 1) carry_s = all;
         __syncthreads();
     }
-    ScanItem item[kScanItems];
-    ScanItem v = ScanItem{Sum4{0.0, 0.0, 0.0, 0.0}, 0, 0};
+    ScanItem item[ITEMS];
+    ScanItem v = item_zero();
 #pragma unroll
-    for (int q = 0; q < kScanItems; ++q) {
-        item[q] = (k0 + q < n) ? ScanItem{sums[k0 + q], emit_count[k0 + q], weight ? weight[k0 + q] : 0} : ScanItem{Sum4{0.0, 0.0, 0.0, 0.0}, 0, 0};
+    for (int q = 0; q < ITEMS; ++q) {
+        item[q] = (k0 + q < n) ? ScanItem{get_term(sums[k0 + q]), emit_count[k0 + q], weight ? weight[k0 + q] : 0, massive[k0 + q], 0} : item_zero();
         v = item_add(v, item[q]);
     }
-    const ScanItem inc = block_inclusive_scan<kScanThreads>(v, lds);
-    __syncthreads();
-    lds[threadIdx.x] = inc;
-    __syncthreads();
-    ScanItem run = item_add(carry_s, threadIdx.x > 0 ? lds[threadIdx.x - 1] : ScanItem{Sum4{0.0, 0.0, 0.0, 0.0}, 0, 0});
+    ScanItem excl;
+    (void)block_scan<kScanThreads>(v, lds, excl);
+    ScanItem run = item_add(carry_s, excl);
 #pragma unroll
-    for (int q = 0; q < kScanItems; ++q) {
+    for (int q = 0; q < ITEMS; ++q) {
         if (k0 + q < n) { base[k0 + q] = run.c; if (weight) weight[k0 + q] = run.w; }
         run = item_add(run, item[q]);
-        if (k0 + q < n) incl[k0 + q] = run.s;
+        if (k0 + q < n) { incl[k0 + q] = run.s.hi; incl_lo[k0 + q] = run.s.lo; massive[k0 + q] = run.z; }
         if (k0 + q == n - 1) { out_info[0] = run.c; out_info[2] = n; }   // nodes in all; the live body count rides along (one read-back)
     }
 }
 
 // bytes of scratch the passes need for n_cap bodies
-size_t sum4_scan_tmp_bytes(size_t n_cap) { return ((n_cap + kScanTile - 1) / kScanTile + 1) * sizeof(ScanItem); }
+size_t sum4_scan_tmp_bytes(size_t n_cap) { return ((std::min<size_t>(n_cap, kScanSmall) + kScanThreads - 1) / kScanThreads + (n_cap + 4 * kScanThreads - 1) / (4 * kScanThreads) + 1) * sizeof(ScanItem); }   // (tiles of either size)
 
 // scratch at the start of the build workspace: whatever the rocPRIM sort / integer scan or the Sum4
 // scan asks for, whichever is largest
@@ -611,7 +713,7 @@ __global__ __launch_bounds__(256) void k_tree_own_scatter(const int* __restrict_
 
 size_t tree_build_workspace_bytes(size_t n_cap) {
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    return scratch_bytes(n_cap) + 3 * al(n_cap * 8) + 5 * al(n_cap * 4) + al(n_cap) + 2 * al(n_cap * sizeof(Sum4)) + 256;
+    return scratch_bytes(n_cap) + 3 * al(n_cap * 8) + 5 * al(n_cap * 4) + al(n_cap) + al(n_cap * sizeof(DD4)) + 2 * al(n_cap * sizeof(Sum4)) + al(n_cap * 4) + 256;
 }
 
 namespace {
@@ -620,7 +722,9 @@ struct BuildLayout {
     unsigned long long *keys_in, *keys, *keys2;
     int *ids_in, *ids, *emit_count, *base, *wpre;
     signed char* delta;
-    Sum4 *sums, *incl;
+    void* sums;             // per sorted body: the terms {m, m x, m y, m z} as TermOf<P4> (room for the larger kind)
+    Sum4 *incl, *incl_lo;   // their inclusive prefix sums, high and low parts (two arrays: kernels_let.hip reads the high parts)
+    int* massive;           // inclusive count of bodies whose mass is not 0
     int* counters;   // [1] k_tree_ties: groups listed for the workgroup sort (cleared by k_tree_keys)
 };
 BuildLayout build_layout(void* workspace, size_t n_cap) {
@@ -638,8 +742,10 @@ BuildLayout build_layout(void* workspace, size_t n_cap) {
     L.base = reinterpret_cast<int*>(p); p += al(n_cap * 4);
     L.wpre = reinterpret_cast<int*>(p); p += al(n_cap * 4);
     L.delta = reinterpret_cast<signed char*>(p); p += al(n_cap);
-    L.sums = reinterpret_cast<Sum4*>(p); p += al(n_cap * sizeof(Sum4));
+    L.sums = p; p += al(n_cap * sizeof(DD4));
     L.incl = reinterpret_cast<Sum4*>(p); p += al(n_cap * sizeof(Sum4));
+    L.incl_lo = reinterpret_cast<Sum4*>(p); p += al(n_cap * sizeof(Sum4));
+    L.massive = reinterpret_cast<int*>(p); p += al(n_cap * 4);
     L.counters = reinterpret_cast<int*>(p);   // (the 256 bytes tree_build_workspace_bytes adds at the end)
     return L;
 }
@@ -670,12 +776,17 @@ int scan_sorted_t(hipStream_t s, const P4* pos, const int* d_count, int n_upper,
     const BuildLayout L = build_layout(workspace, n_cap);
     const int n = n_upper;
     if (n <= 0) return 0;
-    const int n_tiles = (n + kScanTile - 1) / kScanTile;
+    using Term = typename TermOf<P4>::type;
     ScanItem* totals = static_cast<ScanItem*>(L.tmp);   // (the sort is done with its scratch)
-    hipLaunchKernelGGL((k_tree_delta_totals<P4>), dim3(n_tiles), dim3(kScanThreads), 0, s, L.keys, L.keys2, L.ids, pos, d_count, L.delta,
-                       L.emit_count, L.sums, out_info + 1, totals, edge, weight_src, L.wpre);
-    hipLaunchKernelGGL(k_tree_scan, dim3(n_tiles), dim3(kScanThreads), 0, s, L.emit_count, L.sums, d_count, totals, L.base, L.incl, out_info,
-                       weight_src ? L.wpre : nullptr);
+    auto launch = [&](auto items) {
+        constexpr int ITEMS = decltype(items)::value;
+        const int n_tiles = (n + kScanThreads * ITEMS - 1) / (kScanThreads * ITEMS);
+        hipLaunchKernelGGL((k_tree_delta_totals<P4, ITEMS>), dim3(n_tiles), dim3(kScanThreads), 0, s, L.keys, L.keys2, L.ids, pos, d_count, L.delta,
+                           L.emit_count, static_cast<Term*>(L.sums), L.massive, out_info + 1, totals, edge, weight_src, L.wpre);
+        hipLaunchKernelGGL((k_tree_scan<Term, ITEMS>), dim3(n_tiles), dim3(kScanThreads), 0, s, L.emit_count, static_cast<const Term*>(L.sums), d_count,
+                           totals, L.base, L.incl, L.incl_lo, L.massive, out_info, weight_src ? L.wpre : nullptr);
+    };
+    if (scan_items(n) == 1) launch(std::integral_constant<int, 1>{}); else launch(std::integral_constant<int, 4>{});
     return 0;
 }
 template <class P4, class Real, class NodeT>
@@ -688,7 +799,7 @@ int emit_nodes_t(hipStream_t s, const P4* pos, const int* d_count, Real width, v
     const int emit_blocks = (std::max(1, slice_cap) + 255) / 256;
     const TreeSplitReq req = split ? *split : TreeSplitReq{};
     hipLaunchKernelGGL((k_tree_emit<P4, Real, NodeT>), dim3(emit_blocks + req.n_split), dim3(256), 0, s, L.keys, L.keys2, L.ids, pos,
-                       d_count, L.delta, L.base, L.incl, width, nodes, node_cap, order, out_info, want_hot, edge, node_offset, parent, depth, req,
+                       d_count, L.delta, L.base, L.incl, L.incl_lo, L.massive, width, nodes, node_cap, order, out_info, want_hot, edge, node_offset, parent, depth, req,
                        emit_blocks);
     return 0;
 }
@@ -732,8 +843,9 @@ int build_octree_device(hipStream_t s, const float4* pos, const int* d_count, in
     if (tree_sort_keys(s, pos, d_count, n_upper, center, width, workspace, n_cap, out_info, work) != 0) return -1;
     return tree_emit_sorted(s, pos, d_count, n_upper, width, workspace, n_cap, nodes, node_cap, order, out_info, want_hot, nullptr, split);
 }
-// The same for F = f64: keys from the reference's recurrences in double, centres of mass from the same f64 prefix sums
-// (against the reference's sequential f64 folds they differ in the last bits only), 64-byte node records.
+// The same for F = f64: keys from the reference's recurrences in double, centres of mass from the same double-double prefix
+// sums (products m x taken exactly with an FMA): within 4 units of 2^-53 of the exact centre, where the reference's
+// sequential f64 fold of n_c bodies is within n_c + 2; 64-byte node records.
 int build_octree_device(hipStream_t s, const double4* pos, const int* d_count, int n_upper, const double center[3], double width,
                         void* workspace, size_t n_cap, nbody64::Node64* nodes, int node_cap, int* order, int* out_info,
                         TreeDevWork* work, int /* want_hot */, const TreeSplitReq* split) {

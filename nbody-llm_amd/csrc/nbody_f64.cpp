@@ -359,8 +359,8 @@ int strict_walk(NbodyHandle* h, State& s, const TreeBuilt& t, int levels) {
 }
 
 // The tree built on the device (NBODY_TREE_DEVICE; kernels_tree.hip for double): no positions to the host, no nodes
-// back.  Same cells, pre-order and skip links as the host build; centres of mass from f64 prefix sums instead of the
-// reference's sequential f64 folds (last bits).  *fell_back: coincident bodies / > 42 levels -> the caller builds on the host.
+// back.  Same cells, pre-order and skip links as the host build; centres of mass from double-double prefix sums instead of the
+// reference's sequential f64 folds (within 4 units of 2^-53 of the exact centre, cell by cell: tests/tree_moments.py).  *fell_back: coincident bodies / > 42 levels -> the caller builds on the host.
 int bh_forces_device(NbodyHandle* h, State& s, bool* fell_back) {
     // one shard, fast math: the walk's split points ride in the build's last launch (kernels.h TreeSplitReq)
     nbody::TreeSplitReq req;

@@ -1,13 +1,15 @@
 """Device-side octree build (NBODY_TREE_DEVICE) against the oracle.
 Index work is exact: the same cells in the same pre-order with the same skip links, widths and
-leaf bodies as barnes_hut.rs:143-183.  The centre-of-mass sums are f64 prefix sums instead of the
-reference's sequential f32 folds: com/mass agree to the rounding of the reference's own fold (n * 2^-24),
+leaf bodies as barnes_hut.rs:143-183.  The centre-of-mass sums are double-double prefix sums instead of the
+reference's sequential f32 folds (every cell is checked against exact sums by tests/tree_moments.py): com/mass agree
+with the reference's to the rounding of the reference's own fold (n * 2^-24),
 so an opening test that sits on the edge can flip: node counts within 1e-3, accelerations <= 1e-5 for
 the equal-mass-ish Plummer sets (the disc's 1 : 3e-5 mass ratio makes the reference's f32 root mass
 itself 2e-4 off the exact sum)."""
 import numpy as np
 import pytest
 
+import tree_moments
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -35,6 +37,8 @@ def build_and_compare(nb, orc, ics, box, sd, math_mode):
     scale = box[1]
     assert np.abs(t["com_mass"][:, :3].astype(np.float64) - rt["com_mass"][:, :3]).max() < tol * scale
     assert np.allclose(t["com_mass"][:, 3], rt["com_mass"][:, 3], rtol=tol, atol=0)
+    # and cell by cell against exact sums over the cell's own bodies, in units of the cell's own rounding
+    assert tree_moments.check_moments(t, scheme=True, host_tree=rt, what=f"device build of {len(ics)} bodies")["massless"] == 0
     return got, ref, s, (acc_n, vis_n)
 
 
@@ -126,7 +130,7 @@ def close_pairs(dtype, box_w=64.0):
     """64 bodies of mass 1/64 as 32 pairs spread over the box, the two of a pair about 1e-6 of its width apart: every pair
     hangs below a chain of ~17 cells with one child each, so the tree has ~10 nodes per body.  Every coordinate is a multiple
     of 2^-14 below 7.1 in size, so the sums m x over any cell are exact in f32 (23 bits) and the host build's f32 folds
-    and the device build's f64 prefix sums give the same centres of mass to the bit."""
+    and the device build's double-double prefix sums give the same centres of mass to the bit."""
     rng = np.random.default_rng(64)
     cell = rng.integers(-28, 28, (32, 3))
     assert len(np.unique(cell, axis=0)) == 32                          # (with this seed)
@@ -238,7 +242,7 @@ def test_device_tree_full_size_65536(gpu, orc):
 
 
 def test_device_tree_trajectory_stays_with_the_host_tree_trajectory(gpu):
-    """What the device build's different rounding of the centres of mass (f64 prefix sums instead of the reference's
+    """What the device build's different rounding of the centres of mass (double-double prefix sums instead of the reference's
     sequential f32 folds) costs over a trajectory: 100 steps of configs[2] (65 536 bodies, theta = 0.5, fast math) with
     the tree built on the device against the same run with the host build.  Per pass the accepted-node counts agree to
     1e-3; after 100 steps the positions differ by a few 1e-7 (the bodies sit at radii ~1, float32 resolution 6e-8), the
@@ -293,7 +297,7 @@ def test_a_clump_inside_one_level_16_cell(gpu, orc, clump):
     if clump > 4096:     # built on the host: exact
         assert (s.interactions, s.node_visits) == (acc_n, vis_n)
         assert np.array_equal(got["acceleration"].view(np.uint32), ref["acceleration"].view(np.uint32))
-    else:                # built on the device: centres of mass from f64 prefix sums.  The reference folds them in f32, which inside
+    else:                # built on the device: centres of mass from double-double prefix sums.  The reference folds them in f32, which inside
         # the clump (bodies 1e-4 apart at |x| ~ 3: an f32 ulp is 2.4e-7) is itself good to a per cent of a separation only:
         # there the two differ by the REFERENCE's rounding, so the accelerations are compared where they are well defined
         assert abs(s.interactions - acc_n) <= 1e-3 * acc_n and abs(s.node_visits - vis_n) <= 1e-3 * vis_n

@@ -5,6 +5,7 @@ walk: to f64 rounding."""
 import numpy as np
 import pytest
 
+import tree_moments
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -258,8 +259,8 @@ def test_f64_tracks_f32(gpu):
 @pytest.mark.parametrize("n,theta2", [(1, 0.25), (2, 0.25), (9, 1.0), (1000, 0.25), (20000, 0.25)])
 def test_barnes_hut_f64_device_tree(gpu, orc, n, theta2, leaf):
     """NBODY_TREE_DEVICE on an f64 handle (kernels_tree.hip instantiated for double): the same cells, pre-order, skip
-    links, widths and leaves as the oracle's f64 tree, bit for bit; centres of mass from f64 prefix sums instead of the
-    reference's sequential f64 folds (1e-13); the strict f64 walk on it visits the same nodes unless an opening test sits
+    links, widths and leaves as the oracle's f64 tree, bit for bit; centres of mass from double-double prefix sums instead of the
+    reference's sequential f64 folds (checked cell by cell against exact sums, tests/tree_moments.py); the strict f64 walk on it visits the same nodes unless an opening test sits
     within that rounding of its threshold."""
     nb = gpu
     sd = dict(g=1.0, g_soft=0.01, dt=1e-3, theta2=theta2)
@@ -280,6 +281,7 @@ def test_barnes_hut_f64_device_tree(gpu, orc, n, theta2, leaf):
     assert np.abs(t["com_mass"][:, :3] - rt["com_mass"][:, :3]).max(initial=0.0) < 1e-12 * BOX[1]
     # (the reference's own sequential fold over n terms carries up to n * 2^-53 of rounding: the bound on the difference)
     assert np.abs(t["com_mass"][:, 3] - rt["com_mass"][:, 3]).max(initial=0.0) < max(4e-15, n * 2.3e-16)
+    assert tree_moments.check_moments(t, scheme=True, host_tree=rt, what=f"f64 device build of {n} bodies")["massless"] == 0   # cell by cell against exact sums
     assert abs(int(s.interactions) - acc_n) <= max(1, 1e-6 * acc_n) and abs(int(s.node_visits) - vis_n) <= max(1, 1e-6 * vis_n)
     scale = np.abs(ref["acceleration"]).max() or 1.0
     err = np.abs(got["acceleration"] - ref["acceleration"]).max(axis=1) / scale
