@@ -535,6 +535,42 @@ int nbody_external_at(NbodyHandle* h, const double* xyz, size_t n_points, double
 /* Host-only (no device needed), f64: the same for components and g given by the caller. */
 int nbody_host_external_eval(const NbodyExternalComponent* comps, size_t n, double g, const double* xyz, size_t n_points,
                              double* acc, double* phi);
+/* ---- diagnostics of the state as a whole: momentum, angular momentum, mass profile (no reference counterpart) -----
+ * Two READ-ONLY calls on a handle's bodies, evaluated on the device, f64 on either dtype (positions, velocities and masses
+ * widened; nothing contracted, every product, sum and difference rounded on its own).  "The bodies" are what nbody_download
+ * would report at that moment -- on a Hermite handle the held (x0, v0).  Tracers are not bodies and are not counted; the
+ * external field plays no part.  Both calls LEAVE NO TRACE: state, NbodyStats, tracers, the validity of a Hermite handle's
+ * held derivatives, block-step levels and the bits of every later step are what they would be without the call (the contract
+ * of nbody_potentials and nbody_external_energy).  They confirm steps enqueued without a read-back, but do not refresh the
+ * host's view of the body count: the launches are sized from its upper bound and read the live count on the device, so the
+ * result is right after a retain has dropped bodies, with no nbody_count in between.  Scratch is allocated and freed inside
+ * the call.  No floating-point atomics: the same input gives the same bits.  Neither call has been timed on an MI355X; their
+ * cost there is not measured.
+ *   nbody_moments: out = {M, X[3], P[3], L[3]}, M = sum m, X = sum m x (the centre of mass is X / M: the caller divides),
+ * P = sum m v, L = sum m (x cross v) about the origin.  Per body the terms are m, m x_c, m v_c and
+ * l_x = (y vz - z vy) m, l_y = (z vx - x vz) m, l_z = (x vy - y vx) m.  Each of the ten sums has nbody_external_energy's
+ * shape: per block of 256 bodies the pairwise tree sum[t] += sum[t + half] for half = 128 ... 1 (rows past the live count
+ * hold +0.0), the block sums then added on the host in ascending block order, starting from +0.0.  tests/diag_ref.py restates
+ * it in numpy, bit for bit.  No bodies: ten exact zeros.
+ *   nbody_lagrangian_radii: radii[k] = the distance from `center` within which the fraction fractions[k] of the bodies' mass
+ * lies.  center == NULL: the centre of mass X / M of nbody_moments, from the same arithmetic (M == 0 gives a NaN centre).
+ * d = x - center, r2 = (dx dx + dy dy) + dz dz.  The bodies are ordered ascending by (r2, index in nbody_download's order); a
+ * body whose r2 is NaN is left out of the order and of the mass, +inf is kept and comes last.  c_j = the inclusive prefix sum
+ * of the masses in that order; *mass_out (may be NULL) = the last c_j; radii[k] = sqrt(r2) (IEEE) of the first body j with
+ * c_j >= fractions[k] * mass_out, the product rounded once (found by binary search: negative masses, which make c_j fall,
+ * are the caller's risk, and a target no prefix reaches gives NaN).  The prefix sums are this library's own double-double
+ * scan with a fixed association order, rounded to f64 once at the end -- not rocPRIM's scan, whose grouping follows the
+ * completion order of its tiles: every c_j lies within n 2^-53 sum|m| of the exact prefix (far closer in fact), and the same
+ * call twice gives the same bits.  With no body left in the order every radius is NaN and *mass_out is 0.  n_frac == 0 is
+ * valid.
+ *   NBODY_ERR_INVALID (nbody_last_error names the call): out NULL; a fraction outside [0, 1] or NaN; n_frac > 2^20; fractions
+ * or radii NULL with n_frac > 0.
+ *   Accepted on every world_size == 1, NBODY_SHARD_INDEX handle: both dtypes, both methods, either math mode, any tree build,
+ * leapfrog or Hermite, block steps on or off, with or without tracers, an external field or nbody_set_multipole(2).
+ * Deliberately out of scope, refused with NBODY_ERR_INVALID: handles of a multi-rank world and NBODY_SHARD_SPATIAL handles. */
+int nbody_moments(NbodyHandle* h, double out[10]);
+int nbody_lagrangian_radii(NbodyHandle* h, const double center[3], const double* fractions, size_t n_frac, double* radii,
+                           double* mass_out);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

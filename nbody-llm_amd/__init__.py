@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -87,6 +88,7 @@ DECLARED_SYMBOLS = [
     "nbody_debug_hermite_forces_of",
     "nbody_set_external_field", "nbody_get_external_field", "nbody_external_potentials", "nbody_external_energy",
     "nbody_external_at", "nbody_host_external_eval",
+    "nbody_moments", "nbody_lagrangian_radii",
 ]
 
 
@@ -217,6 +219,8 @@ _sig("nbody_external_potentials", _i, _H, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_external_energy", _i, _H, C.POINTER(C.c_double))
 _sig("nbody_external_at", _i, _H, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
 _sig("nbody_host_external_eval", _i, _pc, _sz, C.c_double, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
+_sig("nbody_moments", _i, _H, C.POINTER(C.c_double))
+_sig("nbody_lagrangian_radii", _i, _H, C.c_void_p, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_double))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -360,6 +364,10 @@ def host_build_tree(pos4: np.ndarray, center, width: float, threads: int = 1):
     if rc:
         raise NbodyError(rc, "nbody_host_build_tree")
     return dict(com_mass=com, width=w, skip=skip, leaf_body=body, order=order)
+
+
+#: Simulation.moments(): M, the centre of mass X / M, P, L about the origin, and the raw X = sum m x (all f64; com is NaN when M == 0)
+Moments = namedtuple("Moments", ["mass", "com", "momentum", "angular_momentum", "mass_dipole"])
 
 
 @dataclass
@@ -526,6 +534,31 @@ class Simulation:
         self._check(lib.nbody_external_at(self._h, xyz.ctypes.data if m else None, m, a.ctypes.data if acc else None,
                                           v.ctypes.data if phi else None))
         return a, v
+
+    # -- diagnostics of the state as a whole (nbody_moments, nbody_lagrangian_radii): f64, read-only, one-rank index-block handles
+    def moments(self) -> Moments:
+        """Moments(mass, com, momentum, angular_momentum, mass_dipole) of the bodies as get_points() would report them: M = sum m,
+        P = sum m v, L = sum m (x cross v) about the origin, mass_dipole = X = sum m x and com = X / M (nbody_moments; summed on
+        the device in a fixed order, the same input gives the same bits).  Tracers are not counted."""
+        out = (C.c_double * 10)()
+        self._check(lib.nbody_moments(self._h, out))
+        v = np.array(out[:], np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            com = v[1:4] / v[0]
+        return Moments(float(v[0]), com, v[4:7].copy(), v[7:10].copy(), v[1:4].copy())
+
+    def lagrangian_radii(self, fractions, center=None) -> tuple[np.ndarray, float]:
+        """(radii [K] f64, mass): radii[k] is the distance from `center` (None: the centre of mass) within which the fraction
+        fractions[k] of the bodies' mass lies -- the distance of the first body, in ascending (distance, index) order, whose
+        cumulative mass reaches fractions[k] * mass (nbody_lagrangian_radii).  Bodies at a NaN distance are left out."""
+        fr = np.ascontiguousarray(np.asarray(fractions, np.float64).reshape(-1))
+        k = len(fr)
+        radii = np.zeros(k, np.float64)
+        mass = C.c_double(0)
+        c = None if center is None else np.ascontiguousarray(np.asarray(center, np.float64).reshape(3))
+        self._check(lib.nbody_lagrangian_radii(self._h, None if c is None else c.ctypes.data, fr.ctypes.data if k else None, k,
+                                               radii.ctypes.data if k else None, C.byref(mass)))
+        return radii, float(mass.value)
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

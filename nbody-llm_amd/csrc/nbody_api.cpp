@@ -12,6 +12,7 @@
 #include "nbody_field.h"
 #include "nbody_tracer.h"
 #include "nbody_external.h"
+#include "nbody_diag.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1352,6 +1353,42 @@ int nbody_external_at(NbodyHandle* h, const double* xyz, size_t n_points, double
     if (n_points > (size_t(1) << 30)) return fail(h, NBODY_ERR_INVALID, "nbody_external_at: n_points must not exceed 2^30");
     if (!xyz && n_points > 0) return fail(h, NBODY_ERR_INVALID, "nbody_external_at: xyz is NULL");
     return nbody::ext::at(h, g_of(h), xyz, n_points, acc, phi);
+}
+
+// ---- diagnostics of the state as a whole (nbody_diag.cpp)
+namespace {
+// binds the device, refuses the handles the diagnostics do not take, naming the entry point, and confirms the steps enqueued
+// without a read-back (the readers want the state those steps produced).  The host's view of the body count is NOT refreshed:
+// the kernels read the live count on the device.
+int diag_enter(NbodyHandle* h, const char* call) {
+    int rc = use_device(h);
+    if (rc) return rc;
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return resolve_async(h);
+}
+}  // namespace
+
+int nbody_moments(NbodyHandle* h, double out[10]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_moments");
+    if (rc) return rc;
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_moments: out is NULL");
+    if (h->f64) return nbody::diag::moments(h, nbody64::shard(h), nbody64::n_upper(h), out);
+    return nbody::diag::moments(h, h->sh, h->n_local, out);
+}
+
+int nbody_lagrangian_radii(NbodyHandle* h, const double center[3], const double* fractions, size_t n_frac, double* radii, double* mass_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_lagrangian_radii");
+    if (rc) return rc;
+    if (n_frac > (size_t(1) << 20)) return fail(h, NBODY_ERR_INVALID, "nbody_lagrangian_radii: n_frac must not exceed 2^20");
+    if (n_frac > 0 && !fractions) return fail(h, NBODY_ERR_INVALID, "nbody_lagrangian_radii: fractions is NULL");
+    if (n_frac > 0 && !radii) return fail(h, NBODY_ERR_INVALID, "nbody_lagrangian_radii: radii is NULL");
+    for (size_t k = 0; k < n_frac; ++k)
+        if (!(fractions[k] >= 0.0 && fractions[k] <= 1.0))   // (a NaN fails both comparisons)
+            return fail(h, NBODY_ERR_INVALID, "nbody_lagrangian_radii: fraction " + std::to_string(k) + " is not in [0, 1]");
+    if (h->f64) return nbody::diag::lagrangian_radii(h, nbody64::shard(h), nbody64::n_upper(h), center, fractions, n_frac, radii, mass_out);
+    return nbody::diag::lagrangian_radii(h, h->sh, h->n_local, center, fractions, n_frac, radii, mass_out);
 }
 
 // ---- tracers (nbody_tracer.cpp)

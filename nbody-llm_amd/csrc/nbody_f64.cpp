@@ -692,6 +692,7 @@ int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, do
 
 int get_integrator(const NbodyHandle* h) { return h->f64->integrator; }
 const nbody::ShardT<double>& shard(const NbodyHandle* h) { return h->f64->sh; }
+size_t n_upper(const NbodyHandle* h) { return h->f64->n_local; }
 
 int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out) {
     State& s = *h->f64;

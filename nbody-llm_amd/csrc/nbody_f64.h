@@ -37,6 +37,7 @@ int download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out);
 int block_step_counts(NbodyHandle* h, uint64_t out[2]);
 int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3);
 const nbody::ShardT<double>& shard(const NbodyHandle* h);    // the bodies on the device (nbody_external_potentials reads them)
+size_t n_upper(const NbodyHandle* h);   // the host's view of the own body count, an upper bound after a retain (nbody_moments sizes its launches from it)
 int tree_export(NbodyHandle* h, double* com_mass, double* width, int32_t* skip, size_t cap, size_t* n_nodes);
 
 }  // namespace nbody64

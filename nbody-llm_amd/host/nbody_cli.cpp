@@ -11,8 +11,10 @@
 // writes the final PointParticle records; --multipole 2 adds the cells' quadrupole terms to the Barnes-Hut force walk;
 // --tracers M scatters M massless tracers in the workload's disc or sphere (the IC generator with seed + 1) and reports their
 // interactions per second on a line of its own; --external KIND:p0:p1[...][:cx:cy:cz] (repeatable; plummer:M:b, hernquist:M:a,
-// mn:M:a:b, log:v0:rc:qy:qz) adds a component of a static external field and reports the external energy before and after.
+// mn:M:a:b, log:v0:rc:qy:qz) adds a component of a static external field and reports the external energy before and after;
+// --diagnostics prints M, |P|, |L| and the 10 / 50 / 90 % Lagrangian radii about the centre of mass before and after the run.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,7 +32,8 @@ static void usage() {
                  "                 [--width w] [--seed s] [--integrator device|leapfrog|host|hermite] [--dump file] [--multipole 1|2]\n"
                  "                 [--block-steps ETA:LEVELS]   (with --integrator hermite: block individual time steps)\n"
                  "                 [--tracers M]   (massless tracers in the same disc or sphere; --dtype f32)\n"
-                 "                 [--external plummer:M:b[:cx:cy:cz] | hernquist:M:a[...] | mn:M:a:b[...] | log:v0:rc:qy:qz[...]]   (repeatable)\n");
+                 "                 [--external plummer:M:b[:cx:cy:cz] | hernquist:M:a[...] | mn:M:a:b[...] | log:v0:rc:qy:qz[...]]   (repeatable)\n"
+                 "                 [--diagnostics]   (M, |P|, |L| and the 10/50/90 %% Lagrangian radii before and after the run)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -60,11 +63,24 @@ static bool parse_external(const char* arg, NbodyExternalComponent* out) {
     return false;
 }
 
+// one line of --diagnostics: nbody_moments and nbody_lagrangian_radii about the centre of mass
+template <class Sim>
+static void print_diagnostics(Sim& sim, const char* when) {
+    double m[10];
+    sim.moments(m);
+    std::vector<double> radii;
+    const double mass = sim.lagrangian_radii(nullptr, {0.1, 0.5, 0.9}, radii);
+    std::printf("Diagnostics %s: M %.9e  |P| %.9e  |L| %.9e  r10 %.9e  r50 %.9e  r90 %.9e  mass in radii %.9e\n", when, m[0],
+                std::sqrt(m[4] * m[4] + m[5] * m[5] + m[6] * m[6]), std::sqrt(m[7] * m[7] + m[8] * m[8] + m[9] * m[9]), radii[0], radii[1],
+                radii[2], mass);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
-               double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external) {
+               double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
+               bool diagnostics) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -99,6 +115,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
         const double ext_before = external.empty() ? 0.0 : sim->external_energy();
+        if (diagnostics) print_diagnostics(*sim, "before");
         auto start = std::chrono::steady_clock::now();
         if (integrator == "host") {   // the trait's generic Integrator, on the host (simulation.hpp step_by_with)
             nbody::LeapFrogIntegratorT<F> leapfrog;
@@ -119,6 +136,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
             std::printf("Tracers left: %zu  tracer interactions/second: %.4e\n", sim->n_tracers(), double(ts[0]) / secs);
         }
         if (!external.empty()) std::printf("External energy: %.9e -> %.9e\n", ext_before, sim->external_energy());
+        if (diagnostics) print_diagnostics(*sim, "after");
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -149,6 +167,7 @@ int main(int argc, char** argv) {
     bool block_set = false;
     size_t n_tracers = 0;
     std::vector<NbodyExternalComponent> external;
+    bool diagnostics = false;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -168,6 +187,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--integrator")) integrator = next();
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
+        else if (!std::strcmp(argv[i], "--diagnostics")) diagnostics = true;
         else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--external")) {
             NbodyExternalComponent c;
@@ -199,6 +219,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics);
 }

@@ -233,6 +233,16 @@ public:
     // sum m_i phi_ext(x_i): the conserved total is KE + PE + this (nbody_energy stays self-gravity only)
     double external_energy() { double v = 0; check(nbody_external_energy(h_, &v)); return v; }
     void external_at(const double* xyz, size_t n, double* acc, double* phi) { push_settings(); check(nbody_external_at(h_, xyz, n, acc, phi)); }
+    // diagnostics of the state as a whole (nbody_moments, nbody_lagrangian_radii): f64 on either F, read-only, evaluated on the
+    // device; handles of a one-rank world, every other handle throws NBODY_ERR_INVALID
+    void moments(double out[10]) { check(nbody_moments(h_, out)); }   // {M, X[3] = sum m x, P[3], L[3] about the origin}
+    // radii[k]: the distance from center (nullptr: the centre of mass) within which fractions[k] of the mass lies; returns the mass
+    double lagrangian_radii(const double* center, const std::vector<double>& fractions, std::vector<double>& radii) {
+        double mass = 0;
+        radii.assign(fractions.size(), 0.0);
+        check(nbody_lagrangian_radii(h_, center, fractions.data(), fractions.size(), radii.data(), &mass));
+        return mass;
+    }
     NbodyHandle* handle() { return h_; }
 
 protected:

@@ -91,6 +91,8 @@ unsafe extern "C" {
     fn nbody_external_energy(h: *mut NbodyHandle, potential: *mut f64) -> c_int;
     fn nbody_external_at(h: *mut NbodyHandle, xyz: *const f64, n_points: usize, acc: *mut f64, phi: *mut f64) -> c_int;
     fn nbody_host_external_eval(comps: *const NbodyExternalComponent, n: usize, g: f64, xyz: *const f64, n_points: usize, acc: *mut f64, phi: *mut f64) -> c_int;
+    fn nbody_moments(h: *mut NbodyHandle, out: *mut f64) -> c_int;
+    fn nbody_lagrangian_radii(h: *mut NbodyHandle, center: *const f64, fractions: *const f64, n_frac: usize, radii: *mut f64, mass_out: *mut f64) -> c_int;
 }
 
 pub const NBODY_BRUTE_FORCE: i32 = 0; // src/manual/brute_force.rs
