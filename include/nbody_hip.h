@@ -571,6 +571,52 @@ int nbody_host_external_eval(const NbodyExternalComponent* comps, size_t n, doub
 int nbody_moments(NbodyHandle* h, double out[10]);
 int nbody_lagrangian_radii(NbodyHandle* h, const double center[3], const double* fractions, size_t n_frac, double* radii,
                            double* mass_out);
+/* ---- binary census: every body's closest partner in two-body energy, and the mutual bound pairs (no reference counterpart)
+ * Two READ-ONLY calls under the contract of the diagnostics above: "the bodies" are what nbody_download would report (on a
+ * Hermite handle the held (x0, v0)), tracers and the external field play no part, the calls LEAVE NO TRACE in state,
+ * NbodyStats, the validity of a Hermite handle's held derivatives, block-step levels or the bits of any later step, they do
+ * not refresh the host's view of the body count (launches sized from its upper bound, the live count read on the device:
+ * right after a retain with no nbody_count in between), scratch is allocated and freed inside the call, and there are no
+ * floating-point atomics: the same state gives the same bits.
+ *   THE PAIR ENERGY is f64 on either dtype: an NBODY_F32 handle's positions, velocities, masses, g and g_soft are widened
+ * exactly.  Every product, sum and difference is rounded on its own, sqrt and divide are IEEE, nothing is contracted:
+ *     d = x_j - x_i,  w = v_j - v_i,  soft2 = g_soft g_soft
+ *     r2 = ((dx dx + dy dy) + dz dz) + soft2
+ *     w2 = (wx wx + wy wy) + wz wz
+ *     e_ij = 0.5 w2 - (g (m_i + m_j)) / sqrt(r2)
+ * e_ij == e_ji BIT FOR BIT: negation is exact, so d and w have the same squares either way, and the sum of the two masses
+ * commutes.  tests/pairs_ref.py restates both calls in numpy; the device's results are its bits.
+ *   nbody_partners: partner[i] = the j != i with the smallest e_ij, among equal energies the lowest j; energy[i] = that
+ * minimum.  A NaN energy never wins.  A body with no partner -- n == 1, or every e_ij NaN or +inf -- gets partner -1 and
+ * energy +inf.  Coincident bodies without softening give e = -inf by IEEE rules, which DOES win.  Indices are those of
+ * nbody_download's order.  Either array may be NULL; with both NULL the call only counts.  *n_out (may be NULL) = the bodies;
+ * cap < n returns NBODY_ERR_CAPACITY with *n_out set and the arrays untouched.
+ *   nbody_bound_pairs: the MUTUAL pairs -- partner[i] == j, partner[j] == i, e_ij < 0 -- once each with i < j, in ascending i.
+ * The elements are computed on the device in the arithmetic written beside the fields below, with M = m_i + m_j, gm = g M,
+ * e = e_ij (softened as above; the separation is not), h = d cross w formed as hx = dy wz - dz wy, hy = dz wx - dx wz,
+ * hz = dx wy - dy wx, and h2 = (hx hx + hy hy) + hz hz.  A pair at e = -inf is listed (semi_major 0, period 0).  The list is
+ * compacted on the device with an integer prefix sum (rocPRIM's scan: integer addition is associative, its order cannot
+ * show); only the *n_pairs records cross to the host.  *binding_sum (may be NULL) = the sum of `binding` over the list in list
+ * order, starting from +0.0.  pairs == NULL only counts (and still sums, if asked); cap < n_pairs returns NBODY_ERR_CAPACITY
+ * with *n_pairs set, pairs and *binding_sum (0) carrying nothing.  n_pairs may be NULL.
+ *   COST: O(N^2) f64 pair terms, each with an IEEE sqrt and an IEEE divide -- one body per lane, partners staged through LDS,
+ * the grid (groups of 256 bodies) x K partner slices sized by the bf64_waves knob, the K records of a body merged in slice
+ * order, so the result does not depend on K.  It has NOT been measured on an MI355X beyond the single run of
+ * tools/pairs_bench.py that DESIGN 3.16 records (about 0.12 s at 262 144 bodies); nothing asserts or promises a time.
+ *   Accepted on every world_size == 1, NBODY_SHARD_INDEX handle: both dtypes, both methods, either math mode, leapfrog or
+ * Hermite, block steps on or off.  Refused with NBODY_ERR_INVALID (nbody_last_error names the call): handles of a multi-rank
+ * world and NBODY_SHARD_SPATIAL handles. */
+typedef struct NbodyBoundPair {
+    int32_t i, j;          /* indices in nbody_download's order, i < j */
+    double energy;         /* e_ij above, < 0 */
+    double binding;        /* ((m_i m_j) / M) e, M = m_i + m_j */
+    double semi_major;     /* gm / (-2.0 e), gm = g M */
+    double eccentricity;   /* sqrt(q > 0 ? q : 0), q = 1 + ((2 e) h2) / (gm gm) */
+    double period;         /* 6.283185307179586 * (a * sqrt(a / gm)) */
+    double separation;     /* sqrt((dx dx + dy dy) + dz dz), unsoftened */
+} NbodyBoundPair;
+int nbody_partners(NbodyHandle* h, int32_t* partner, double* energy, size_t cap, size_t* n_out);
+int nbody_bound_pairs(NbodyHandle* h, NbodyBoundPair* pairs, size_t cap, size_t* n_pairs, double* binding_sum);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

@@ -89,6 +89,7 @@ DECLARED_SYMBOLS = [
     "nbody_set_external_field", "nbody_get_external_field", "nbody_external_potentials", "nbody_external_energy",
     "nbody_external_at", "nbody_host_external_eval",
     "nbody_moments", "nbody_lagrangian_radii",
+    "nbody_partners", "nbody_bound_pairs",
 ]
 
 
@@ -109,6 +110,18 @@ class NbodyLetStats(C.Structure):
 class NbodyExternalComponent(C.Structure):
     """One component of a static external field: kind EXT_*, centre, p = the kind's parameters (include/nbody_hip.h)."""
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("center", C.c_double * 3), ("p", C.c_double * 4)]
+
+
+class BoundPair(C.Structure):
+    """One mutual bound pair of nbody_bound_pairs (NbodyBoundPair, include/nbody_hip.h "binary census")."""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("energy", C.c_double), ("binding", C.c_double), ("semi_major", C.c_double),
+                ("eccentricity", C.c_double), ("period", C.c_double), ("separation", C.c_double)]
+
+
+#: the same record as a numpy dtype: what Simulation.bound_pairs() returns
+BOUND_PAIR_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("energy", "<f8"), ("binding", "<f8"), ("semi_major", "<f8"),
+                             ("eccentricity", "<f8"), ("period", "<f8"), ("separation", "<f8")])
+assert BOUND_PAIR_DTYPE.itemsize == C.sizeof(BoundPair) == 56
 
 
 class NbodyStats(C.Structure):
@@ -221,6 +234,8 @@ _sig("nbody_external_at", _i, _H, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
 _sig("nbody_host_external_eval", _i, _pc, _sz, C.c_double, C.c_void_p, _sz, C.c_void_p, C.c_void_p)
 _sig("nbody_moments", _i, _H, C.POINTER(C.c_double))
 _sig("nbody_lagrangian_radii", _i, _H, C.c_void_p, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_double))
+_sig("nbody_partners", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_bound_pairs", _i, _H, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_double))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -559,6 +574,30 @@ class Simulation:
         self._check(lib.nbody_lagrangian_radii(self._h, None if c is None else c.ctypes.data, fr.ctypes.data if k else None, k,
                                                radii.ctypes.data if k else None, C.byref(mass)))
         return radii, float(mass.value)
+
+    # -- binary census (nbody_partners, nbody_bound_pairs): f64, read-only, O(N^2) pair energies on the device
+    def partners(self) -> tuple[np.ndarray, np.ndarray]:
+        """(partner [n] int32, energy [n] f64): for every body, in get_points() order, the other body of least two-body energy
+        e_ij = w^2 / 2 - g (m_i + m_j) / sqrt(r^2 + g_soft^2) (the lowest index among equal energies) and that energy; -1 and
+        +inf for a body without a partner (nbody_partners)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_partners(self._h, None, None, 0, C.byref(n)))
+        partner = np.full(n.value, -1, np.int32)
+        energy = np.full(n.value, np.inf, np.float64)
+        self._check(lib.nbody_partners(self._h, partner.ctypes.data if n.value else None, energy.ctypes.data if n.value else None,
+                                       n.value, C.byref(n)))
+        return partner[: n.value], energy[: n.value]
+
+    def bound_pairs(self) -> tuple[np.ndarray, float]:
+        """(pairs, binding_sum): the mutual bound pairs -- each the other's partners(), e < 0 -- as a BOUND_PAIR_DTYPE array in
+        ascending i (i < j) with their orbital elements, and the sum of their binding energies in that order
+        (nbody_bound_pairs)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_partners(self._h, None, None, 0, C.byref(n)))   # (counts only: n bodies hold at most n // 2 pairs)
+        pairs = np.zeros(n.value // 2 + 1, BOUND_PAIR_DTYPE)
+        total = C.c_double(0)
+        self._check(lib.nbody_bound_pairs(self._h, pairs.ctypes.data, len(pairs), C.byref(n), C.byref(total)))
+        return pairs[: n.value].copy(), float(total.value)
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

@@ -1,0 +1,43 @@
+// kernels_pairs.h -- launchers of the binary census (kernels_pairs.hip): every body's partner of least two-body energy, the
+// mutual bound pairs among them and their orbital elements; internal to libnbody_hip.so.
+#pragma once
+#include "nbody_hip.h"   // NbodyBoundPair
+#include "shard.h"
+
+namespace nbody { namespace pairs {
+
+constexpr int kPairBlock = 256;   // bodies per block of k_partner, and partners per LDS tile
+
+inline int blocks_for(int n) { return n <= 0 ? 0 : (n + kPairBlock - 1) / kPairBlock; }
+
+// k_partner's grid for n_upper >= live bodies: groups of kPairBlock bodies x K partner slices, about bf64_waves waves in all
+// (make_hm_act_plan's rule: a slice holds 64 partners or more); slice s of n live bodies is [n s / K, n (s + 1) / K)
+struct PartnerPlan { int groups = 0, K = 1; };
+PartnerPlan make_partner_plan(int n_upper);
+
+// The scratch of one call for n_upper rows, carved out of one allocation of scratch_bytes.
+struct PairScratch {
+    double* rec_e = nullptr;          // [K][groups * kPairBlock] the least energy of (slice, body)
+    int* rec_j = nullptr;             // [K][groups * kPairBlock] and its partner (-1: none)
+    double* energy = nullptr;         // [n_upper] the least energy of a body, +inf: none
+    int* partner = nullptr;           // [n_upper] its partner, -1: none
+    int* flag = nullptr;              // [n_upper] 1 = the first body of a mutual bound pair
+    int* offset = nullptr;            // [n_upper] exclusive prefix sums of flag
+    int* total = nullptr;             // [1] pairs
+    NbodyBoundPair* pairs = nullptr;  // [n_upper / 2 + 1]
+    void* scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+};
+size_t scratch_bytes(size_t n_upper, const PartnerPlan& p, bool want_pairs);
+PairScratch scratch_layout(void* base, size_t n_upper, const PartnerPlan& p, bool want_pairs);
+
+// k_partner and k_partner_merge: w.partner and w.energy of the live bodies (rows past the live count: -1 and +inf)
+template <class F>
+void launch_partners(hipStream_t s, const ShardT<F>& sh, int n_upper, const PartnerPlan& p, double g, double soft2, const PairScratch& w);
+
+// k_pair_flag, the integer scan, k_pair_emit: w.pairs in ascending first index and *w.total of them, from w.partner and
+// w.energy.  Returns 0, or -1 when the scan could not be enqueued.
+template <class F>
+int launch_bound_pairs(hipStream_t s, const ShardT<F>& sh, int n_upper, double g, const PairScratch& w);
+
+}}  // namespace nbody::pairs

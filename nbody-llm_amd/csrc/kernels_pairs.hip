@@ -1,0 +1,215 @@
+// kernels_pairs.hip -- the binary census of a handle's bodies on the device (gfx950), f64 on either dtype: nbody_partners and
+// nbody_bound_pairs (include/nbody_hip.h, "binary census").  Read-only kernels; compiled with -ffp-contract=off (every product,
+// sum and difference rounded on its own; sqrt and divide are IEEE).  No floating-point atomics: the same input gives the same
+// bits.
+//
+//   k_partner        the all-pairs pass.  One body per lane (position, velocity and mass in registers as doubles), the partners
+//                    of a slice staged through LDS in tiles of 256 as k_hm_strict stages its own, j ascending, the best pair
+//                    replaced on e < best only; the grid is (groups of 256 bodies) x K slices, one {energy, index} record per
+//                    (slice, body)
+//   k_partner_merge  the K records of a body in slice order under the same strict <: the lowest j among equal energies,
+//                    whatever K is
+//   k_pair_flag      1 where partner[partner[i]] == i, e < 0 and i < partner[i]
+//   (rocprim::exclusive_scan over the integer flags: integer addition is associative, its order cannot show)
+//   k_pair_emit      the orbital elements of the flagged pairs into their slot of the list
+#include "kernels_pairs.h"
+#include "kernels.h"   // nbody::tuning()
+#include "real.h"      // widen
+
+#include <rocprim/device/device_scan.hpp>
+
+#include <algorithm>
+
+namespace nbody {
+
+using pairs::kPairBlock;
+
+namespace {
+
+__device__ __forceinline__ double inf64() { return __longlong_as_double(0x7ff0000000000000ll); }
+
+// e_ij = 0.5 w2 - (g (m_i + m_j)) / sqrt(r2): d and w change sign with i <-> j, their squares do not, and the sum of the masses
+// commutes -- e_ij == e_ji bit for bit
+__device__ __forceinline__ double pair_energy(const double4 pi, const double4 vi, const double4 pj, const double4 vj, double g, double soft2) {
+    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+    const double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
+    const double r2 = ((dx * dx + dy * dy) + dz * dz) + soft2;
+    const double w2 = (wx * wx + wy * wy) + wz * wz;
+    return 0.5 * w2 - (g * (pi.w + pj.w)) / __builtin_sqrt(r2);
+}
+
+}  // namespace
+
+template <class F>
+__global__ __launch_bounds__(kPairBlock) void k_partner(const typename Real<F>::V4* __restrict__ pos,
+                                                        const typename Real<F>::V4* __restrict__ vel, const int* __restrict__ count,
+                                                        int n_upper, int groups, int K, double g, double soft2,
+                                                        double* __restrict__ rec_e, int* __restrict__ rec_j) {
+    __shared__ double4 tx[kPairBlock], tv[kPairBlock];
+    const int tid = threadIdx.x;
+    const int group = int(blockIdx.x) % groups, slice = int(blockIdx.x) / groups;
+    const int n = min(*count, n_upper);
+    const int i = group * kPairBlock + tid;
+    const bool live = i < n;
+    const double4 pi = live ? widen(pos[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
+    const double4 vi = live ? widen(vel[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
+    const int lo = int((long long)n * slice / K), hi = int((long long)n * (slice + 1) / K);
+    double best = inf64();
+    int best_j = -1;
+    for (int t0 = lo; t0 < hi; t0 += kPairBlock) {
+        const int cnt = min(kPairBlock, hi - t0);
+        __syncthreads();
+        if (tid < cnt) { tx[tid] = widen(pos[t0 + tid]); tv[tid] = widen(vel[t0 + tid]); }
+        __syncthreads();
+        for (int t = 0; t < cnt; ++t) {
+            const double e = pair_energy(pi, vi, tx[t], tv[t], g, soft2);   // wave-uniform addresses: LDS broadcasts
+            if (t0 + t != i && e < best) { best = e; best_j = t0 + t; }     // (a NaN never wins; the i == i pair is left out)
+        }
+    }
+    if (live) {
+        const size_t row = size_t(slice) * (size_t(groups) * kPairBlock) + size_t(i);
+        rec_e[row] = best;
+        rec_j[row] = best_j;
+    }
+}
+
+__global__ __launch_bounds__(kPairBlock) void k_partner_merge(const int* __restrict__ count, int n_upper, int K, size_t stride,
+                                                              const double* __restrict__ rec_e, const int* __restrict__ rec_j,
+                                                              int* __restrict__ partner, double* __restrict__ energy) {
+    const int i = blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= n_upper) return;
+    double best = inf64();
+    int best_j = -1;
+    if (i < *count) {
+        for (int s = 0; s < K; ++s) {   // slices in ascending order hold ascending j
+            const double e = rec_e[size_t(s) * stride + size_t(i)];
+            if (e < best) { best = e; best_j = rec_j[size_t(s) * stride + size_t(i)]; }
+        }
+    }
+    partner[i] = best_j;
+    energy[i] = best;
+}
+
+__global__ __launch_bounds__(kPairBlock) void k_pair_flag(const int* __restrict__ count, int n_upper, const int* __restrict__ partner,
+                                                          const double* __restrict__ energy, int* __restrict__ flag) {
+    const int i = blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= n_upper) return;
+    const int n = min(*count, n_upper);
+    int f = 0;
+    if (i < n) {
+        const int j = partner[i];
+        if (j > i && j < n && partner[j] == i && energy[i] < 0.0) f = 1;
+    }
+    flag[i] = f;
+}
+
+template <class F>
+__global__ __launch_bounds__(kPairBlock) void k_pair_emit(const typename Real<F>::V4* __restrict__ pos,
+                                                          const typename Real<F>::V4* __restrict__ vel, int n_upper, double g,
+                                                          const int* __restrict__ partner, const double* __restrict__ energy,
+                                                          const int* __restrict__ flag, const int* __restrict__ offset,
+                                                          NbodyBoundPair* __restrict__ out, int* __restrict__ total) {
+    const int i = blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= n_upper) return;
+    if (i == n_upper - 1) *total = offset[i] + flag[i];
+    if (!flag[i]) return;
+    const int j = partner[i];
+    const double4 pi = widen(pos[i]), vi = widen(vel[i]), pj = widen(pos[j]), vj = widen(vel[j]);
+    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+    const double wx = vj.x - vi.x, wy = vj.y - vi.y, wz = vj.z - vi.z;
+    const double e = energy[i];
+    const double M = pi.w + pj.w;
+    const double gm = g * M;
+    const double hx = dy * wz - dz * wy, hy = dz * wx - dx * wz, hz = dx * wy - dy * wx;
+    const double h2 = (hx * hx + hy * hy) + hz * hz;
+    const double a = gm / (-2.0 * e);
+    const double q = 1.0 + ((2.0 * e) * h2) / (gm * gm);
+    NbodyBoundPair r;
+    r.i = i;
+    r.j = j;
+    r.energy = e;
+    r.binding = ((pi.w * pj.w) / M) * e;
+    r.semi_major = a;
+    r.eccentricity = __builtin_sqrt(q > 0.0 ? q : 0.0);
+    r.period = 6.283185307179586 * (a * __builtin_sqrt(a / gm));
+    r.separation = __builtin_sqrt((dx * dx + dy * dy) + dz * dz);
+    out[offset[i]] = r;   // (offset < pairs <= n_upper / 2: the first bodies of disjoint pairs)
+}
+
+namespace pairs {
+
+PartnerPlan make_partner_plan(int n_upper) {
+    PartnerPlan p;
+    const int want = nbody::tuning().bf64_waves > 0 ? nbody::tuning().bf64_waves : 2048;
+    p.groups = blocks_for(n_upper);
+    const int waves = p.groups * (kPairBlock / 64);
+    p.K = std::max(1, std::min(want / std::max(1, waves), (n_upper + 63) / 64));   // (a slice holds 64 partners or more)
+    return p;
+}
+
+namespace {
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+size_t scan_tmp_bytes(size_t n_upper) {
+    size_t b = 0;
+    int* v = nullptr;
+    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, n_upper, rocprim::plus<int>(), 0);
+    return b;
+}
+}  // namespace
+
+size_t scratch_bytes(size_t n_upper, const PartnerPlan& p, bool want_pairs) {
+    const size_t rows = size_t(p.K) * size_t(p.groups) * kPairBlock;
+    size_t b = up256(rows * sizeof(double)) + up256(rows * sizeof(int)) + up256(n_upper * sizeof(double)) + up256(n_upper * sizeof(int));
+    if (want_pairs)
+        b += 2 * up256(n_upper * sizeof(int)) + up256(sizeof(int)) + up256((n_upper / 2 + 1) * sizeof(NbodyBoundPair)) +
+             up256(scan_tmp_bytes(n_upper));
+    return b;
+}
+
+PairScratch scratch_layout(void* base, size_t n_upper, const PartnerPlan& p, bool want_pairs) {
+    const size_t rows = size_t(p.K) * size_t(p.groups) * kPairBlock;
+    char* at = static_cast<char*>(base);
+    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+    PairScratch w;
+    w.rec_e = static_cast<double*>(take(rows * sizeof(double)));
+    w.rec_j = static_cast<int*>(take(rows * sizeof(int)));
+    w.energy = static_cast<double*>(take(n_upper * sizeof(double)));
+    w.partner = static_cast<int*>(take(n_upper * sizeof(int)));
+    if (want_pairs) {
+        w.flag = static_cast<int*>(take(n_upper * sizeof(int)));
+        w.offset = static_cast<int*>(take(n_upper * sizeof(int)));
+        w.total = static_cast<int*>(take(sizeof(int)));
+        w.pairs = static_cast<NbodyBoundPair*>(take((n_upper / 2 + 1) * sizeof(NbodyBoundPair)));
+        w.scan_bytes = scan_tmp_bytes(n_upper);
+        w.scan_tmp = take(w.scan_bytes);
+    }
+    return w;
+}
+
+template <class F>
+void launch_partners(hipStream_t s, const ShardT<F>& sh, int n_upper, const PartnerPlan& p, double g, double soft2, const PairScratch& w) {
+    if (n_upper <= 0 || p.groups <= 0) return;
+    hipLaunchKernelGGL(k_partner<F>, dim3(unsigned(p.groups) * unsigned(p.K)), dim3(kPairBlock), 0, s, sh.own_pos(), sh.vel, sh.own_count(),
+                       n_upper, p.groups, p.K, g, soft2, w.rec_e, w.rec_j);
+    hipLaunchKernelGGL(k_partner_merge, dim3(blocks_for(n_upper)), dim3(kPairBlock), 0, s, sh.own_count(), n_upper, p.K,
+                       size_t(p.groups) * kPairBlock, w.rec_e, w.rec_j, w.partner, w.energy);
+}
+
+template <class F>
+int launch_bound_pairs(hipStream_t s, const ShardT<F>& sh, int n_upper, double g, const PairScratch& w) {
+    if (n_upper <= 0) return 0;
+    const int blocks = blocks_for(n_upper);
+    hipLaunchKernelGGL(k_pair_flag, dim3(blocks), dim3(kPairBlock), 0, s, sh.own_count(), n_upper, w.partner, w.energy, w.flag);
+    size_t tb = w.scan_bytes;
+    if (rocprim::exclusive_scan(w.scan_tmp, tb, w.flag, w.offset, 0, size_t(n_upper), rocprim::plus<int>(), s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_pair_emit<F>, dim3(blocks), dim3(kPairBlock), 0, s, sh.own_pos(), sh.vel, n_upper, g, w.partner, w.energy, w.flag,
+                       w.offset, w.pairs, w.total);
+    return 0;
+}
+
+template void launch_partners<float>(hipStream_t, const ShardT<float>&, int, const PartnerPlan&, double, double, const PairScratch&);
+template void launch_partners<double>(hipStream_t, const ShardT<double>&, int, const PartnerPlan&, double, double, const PairScratch&);
+template int launch_bound_pairs<float>(hipStream_t, const ShardT<float>&, int, double, const PairScratch&);
+template int launch_bound_pairs<double>(hipStream_t, const ShardT<double>&, int, double, const PairScratch&);
+
+}}  // namespace nbody::pairs

@@ -13,6 +13,7 @@
 #include "nbody_tracer.h"
 #include "nbody_external.h"
 #include "nbody_diag.h"
+#include "nbody_pairs.h"
 
 #include <algorithm>
 #include <chrono>
@@ -1389,6 +1390,35 @@ int nbody_lagrangian_radii(NbodyHandle* h, const double center[3], const double*
             return fail(h, NBODY_ERR_INVALID, "nbody_lagrangian_radii: fraction " + std::to_string(k) + " is not in [0, 1]");
     if (h->f64) return nbody::diag::lagrangian_radii(h, nbody64::shard(h), nbody64::n_upper(h), center, fractions, n_frac, radii, mass_out);
     return nbody::diag::lagrangian_radii(h, h->sh, h->n_local, center, fractions, n_frac, radii, mass_out);
+}
+
+// ---- binary census (nbody_pairs.cpp): the contract of the diagnostics above, diag_enter included
+namespace {
+void g_and_soft(const NbodyHandle* h, double* g, double* g_soft) {   // the handle's, widened
+    *g = double(h->g);
+    *g_soft = double(h->g_soft);
+    if (h->f64) nbody64::get_settings(h, g, g_soft, nullptr, nullptr);
+}
+}  // namespace
+
+int nbody_partners(NbodyHandle* h, int32_t* partner, double* energy, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_partners");
+    if (rc) return rc;
+    double g = 0.0, g_soft = 0.0;
+    g_and_soft(h, &g, &g_soft);
+    if (h->f64) return nbody::pairs::partners(h, nbody64::shard(h), nbody64::n_upper(h), g, g_soft, partner, energy, cap, n_out);
+    return nbody::pairs::partners(h, h->sh, h->n_local, g, g_soft, partner, energy, cap, n_out);
+}
+
+int nbody_bound_pairs(NbodyHandle* h, NbodyBoundPair* pairs, size_t cap, size_t* n_pairs, double* binding_sum) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_bound_pairs");
+    if (rc) return rc;
+    double g = 0.0, g_soft = 0.0;
+    g_and_soft(h, &g, &g_soft);
+    if (h->f64) return nbody::pairs::bound_pairs(h, nbody64::shard(h), nbody64::n_upper(h), g, g_soft, pairs, cap, n_pairs, binding_sum);
+    return nbody::pairs::bound_pairs(h, h->sh, h->n_local, g, g_soft, pairs, cap, n_pairs, binding_sum);
 }
 
 // ---- tracers (nbody_tracer.cpp)

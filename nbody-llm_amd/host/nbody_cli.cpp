@@ -12,7 +12,8 @@
 // --tracers M scatters M massless tracers in the workload's disc or sphere (the IC generator with seed + 1) and reports their
 // interactions per second on a line of its own; --external KIND:p0:p1[...][:cx:cy:cz] (repeatable; plummer:M:b, hernquist:M:a,
 // mn:M:a:b, log:v0:rc:qy:qz) adds a component of a static external field and reports the external energy before and after;
-// --diagnostics prints M, |P|, |L| and the 10 / 50 / 90 % Lagrangian radii about the centre of mass before and after the run.
+// --diagnostics prints M, |P|, |L| and the 10 / 50 / 90 % Lagrangian radii about the centre of mass before and after the run,
+// and the binary census of the final state (nbody_bound_pairs) on a line of its own; --pairs prints that line alone.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -33,7 +34,8 @@ static void usage() {
                  "                 [--block-steps ETA:LEVELS]   (with --integrator hermite: block individual time steps)\n"
                  "                 [--tracers M]   (massless tracers in the same disc or sphere; --dtype f32)\n"
                  "                 [--external plummer:M:b[:cx:cy:cz] | hernquist:M:a[...] | mn:M:a:b[...] | log:v0:rc:qy:qz[...]]   (repeatable)\n"
-                 "                 [--diagnostics]   (M, |P|, |L| and the 10/50/90 %% Lagrangian radii before and after the run)\n");
+                 "                 [--diagnostics]   (M, |P|, |L| and the 10/50/90 %% Lagrangian radii before and after the run, and --pairs)\n"
+                 "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -75,12 +77,24 @@ static void print_diagnostics(Sim& sim, const char* when) {
                 radii[2], mass);
 }
 
+// the line of --pairs: nbody_bound_pairs; the hardest pair is the one of least binding energy (the first of equals)
+template <class Sim>
+static void print_pairs(Sim& sim) {
+    std::vector<NbodyBoundPair> pairs;
+    const double sum = sim.bound_pairs(pairs);
+    size_t hard = 0;
+    for (size_t k = 1; k < pairs.size(); ++k) if (pairs[k].binding < pairs[hard].binding) hard = k;
+    const double nan = std::nan("");
+    std::printf("Bound pairs: %zu binding %.9e hardest a=%.9e e=%.9e\n", pairs.size(), sum, pairs.empty() ? nan : pairs[hard].semi_major,
+                pairs.empty() ? nan : pairs[hard].eccentricity);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
-               bool diagnostics) {
+               bool diagnostics, bool pairs) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -137,6 +151,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         }
         if (!external.empty()) std::printf("External energy: %.9e -> %.9e\n", ext_before, sim->external_energy());
         if (diagnostics) print_diagnostics(*sim, "after");
+        if (diagnostics || pairs) print_pairs(*sim);
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -167,7 +182,7 @@ int main(int argc, char** argv) {
     bool block_set = false;
     size_t n_tracers = 0;
     std::vector<NbodyExternalComponent> external;
-    bool diagnostics = false;
+    bool diagnostics = false, pairs = false;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -188,6 +203,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--dump")) dump = next();
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
         else if (!std::strcmp(argv[i], "--diagnostics")) diagnostics = true;
+        else if (!std::strcmp(argv[i], "--pairs")) pairs = true;
         else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--external")) {
             NbodyExternalComponent c;
@@ -219,6 +235,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs);
 }

@@ -243,6 +243,29 @@ public:
         check(nbody_lagrangian_radii(h_, center, fractions.data(), fractions.size(), radii.data(), &mass));
         return mass;
     }
+    // binary census (nbody_partners, nbody_bound_pairs): f64 on either F, read-only, O(N^2) pair energies on the device; the
+    // handles moments() takes.  partner[i] = the body of least two-body energy with i (-1: none), energy[i] = that energy
+    void partners(std::vector<int32_t>& partner, std::vector<double>& energy) {
+        size_t n = 0;
+        push_settings();   // (g and g_soft enter the pair energy)
+        check(nbody_partners(h_, nullptr, nullptr, 0, &n));
+        partner.assign(n, -1);
+        energy.assign(n, 0.0);
+        check(nbody_partners(h_, partner.data(), energy.data(), n, &n));
+        partner.resize(n);
+        energy.resize(n);
+    }
+    // the mutual bound pairs in ascending i, i < j, with their orbital elements; returns the sum of their binding energies
+    double bound_pairs(std::vector<NbodyBoundPair>& pairs) {
+        size_t n = 0;
+        double sum = 0;
+        push_settings();
+        check(nbody_partners(h_, nullptr, nullptr, 0, &n));   // (counts only: n bodies hold at most n / 2 pairs)
+        pairs.assign(n / 2 + 1, NbodyBoundPair{});
+        check(nbody_bound_pairs(h_, pairs.data(), pairs.size(), &n, &sum));
+        pairs.resize(n);
+        return sum;
+    }
     NbodyHandle* handle() { return h_; }
 
 protected:

@@ -46,6 +46,20 @@ pub struct NbodyHandle {
     _private: [u8; 0],
 }
 
+/// one mutual bound pair of nbody_bound_pairs (include/nbody_hip.h "binary census")
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct NbodyBoundPair {
+    pub i: i32,
+    pub j: i32,
+    pub energy: f64,
+    pub binding: f64,
+    pub semi_major: f64,
+    pub eccentricity: f64,
+    pub period: f64,
+    pub separation: f64,
+}
+
 /// one component of a static external field (include/nbody_hip.h "external field"): kind NBODY_EXT_*, centre, parameters
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq)]
@@ -93,6 +107,8 @@ unsafe extern "C" {
     fn nbody_host_external_eval(comps: *const NbodyExternalComponent, n: usize, g: f64, xyz: *const f64, n_points: usize, acc: *mut f64, phi: *mut f64) -> c_int;
     fn nbody_moments(h: *mut NbodyHandle, out: *mut f64) -> c_int;
     fn nbody_lagrangian_radii(h: *mut NbodyHandle, center: *const f64, fractions: *const f64, n_frac: usize, radii: *mut f64, mass_out: *mut f64) -> c_int;
+    fn nbody_partners(h: *mut NbodyHandle, partner: *mut i32, energy: *mut f64, cap: usize, n_out: *mut usize) -> c_int;
+    fn nbody_bound_pairs(h: *mut NbodyHandle, pairs: *mut NbodyBoundPair, cap: usize, n_pairs: *mut usize, binding_sum: *mut f64) -> c_int;
 }
 
 pub const NBODY_BRUTE_FORCE: i32 = 0; // src/manual/brute_force.rs
