@@ -21,12 +21,16 @@
 #include "kernels_f64.h"
 #include "kernels.h"   // nbody::tuning()
 #include "pair64.h"
+#include "partner_stream.h"   // Win, n_windows, window
 
 namespace nbody64 {
 
 namespace {
 
 using namespace pair64;   // kPad, pad_body, rot64, plane_sum
+using nbody::Win;
+using nbody::n_windows;
+using nbody::window;
 
 // IPT unordered pairs (resident q, traveller j), written stage by stage so that no instruction waits on its predecessor
 template <int IPT>
@@ -138,27 +142,6 @@ __global__ __launch_bounds__(256) void k_bf64_sym(const double4* __restrict__ po
     double4* __restrict__ out = planes + size_t(sym_sets + part) * plane_stride;
 #pragma unroll
     for (int q = 0; q < IPT; ++q) out[size_t(a * IPT + q) * 64 + lane] = make_double4(axi[q], ayi[q], azi[q], 0.0);
-}
-
-// one window of partners: bodies [lo, hi) of segment seg
-struct Win { int seg, lo, hi; };
-
-template <int MODE>
-__device__ __forceinline__ int n_windows(int n_seg, int A) {
-    return MODE == 0 ? 1 : MODE == 1 ? ((A % 2 == 0 && A > 1) ? 2 : 1) : n_seg - 1;
-}
-
-template <int MODE>
-__device__ __forceinline__ Win window(int w, const int* __restrict__ seg_count, int my_seg, int n_own, int set_size, int A, int a) {
-    if (MODE == 0) return Win{my_seg, 0, n_own};
-    if (MODE == 1) {
-        int set = (w == 0) ? a : a + A / 2;
-        if (set >= A) set -= A;
-        const int lo = min(n_own, set * set_size), hi = min(n_own, lo + set_size);
-        return Win{my_seg, lo, hi};
-    }
-    const int s = w < my_seg ? w : w + 1;   // every other segment, in order
-    return Win{s, 0, seg_count[s]};
 }
 
 // 4 waves per workgroup; wave gw = group * K + slice: bodies group*64 + lane of the own block against slice `slice` of

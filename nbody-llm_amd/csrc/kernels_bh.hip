@@ -20,7 +20,7 @@
 #include "kernels.h"
 #include "kernels_pot.h"
 #include "kernels_field.h"
-#include "kernels_tidal.h"
+#include "probe_term.h"
 #include "kernels_tracer.h"
 #include "walk_common.h"
 
@@ -1092,17 +1092,17 @@ void launch_bh_pot_walk(hipStream_t s, const float4* own_pos, const TreeDev& t, 
     launch_pot_reduce(s, planes, t.n_split, plane_stride, t.order, t.n_order, sum, t.n_order_dev);
 }
 
-// ---- nbody_field_at(NBODY_POTENTIAL_TREE): k_bh_pot_walk for caller-chosen points, with the vector sum beside the scalar one.
-// Lane t walks probe idx[t] (the batch in Morton order: neighbouring lanes follow nearly the same path), rounded to f32 once.
-// The tests are k_bh_pot_walk's, so {accepted, visited} equal oracle.bh_walk_list(.., leaf_mode = 1) at the rounded points.  A
-// term: q = r2 + eps2, inv = 1 / sqrt(q), scalar m * inv, vector d * ((m * inv) / q) -- the divide instead of two more products
-// with inv keeps a component within 15 u of its exact value (tests/field_list.py counts) -- in f32, the four sums in f64.
-// A non-finite probe compares false everywhere: it steps through every node (each branch advances i) and ends with NaN sums.
-template <bool VEC, bool SCAL>
-__global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk(const NodeDev* __restrict__ nodes, const double* __restrict__ xyz,
+// ---- nbody_field_at / nbody_tidal_at (NBODY_POTENTIAL_TREE): k_bh_pot_walk for caller-chosen points, with the sums of a Term
+// (probe_term.h) in place of the scalar one.  Lane t walks probe idx[t] (the batch in Morton order: neighbouring lanes follow
+// nearly the same path), rounded to f32 once.  The tests are k_bh_pot_walk's, so {accepted, visited} equal
+// oracle.bh_walk_list(.., leaf_mode = 1) at the rounded points whatever the Term: there is one loop.  The term is formed in f32,
+// its sums in f64.  A non-finite probe compares false everywhere: it steps through every node (each branch advances i) and
+// ends with NaN sums.
+template <class Term>
+__global__ __launch_bounds__(kWalkBlock) void k_bh_probe_walk(const NodeDev* __restrict__ nodes, const double* __restrict__ xyz,
                                                               const int* __restrict__ idx, int n, float eps2, float theta2,
                                                               unsigned long long* __restrict__ counters, WalkSplit split,
-                                                              double4* __restrict__ planes, size_t plane_stride) {
+                                                              double* __restrict__ planes, size_t plane_stride) {
     const int t = blockIdx.x * kWalkBlock + threadIdx.x;
     const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);   // (as k_bh_walk dispatches them)
     const int s1 = split.first[seg + 1];
@@ -1111,7 +1111,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk(const NodeDev* __r
         const size_t c = size_t(idx[t]);
         const float4 p = make_float4(float(xyz[3 * c]), float(xyz[3 * c + 1]), float(xyz[3 * c + 2]), 0.f);
         const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-        double ax = 0.0, ay = 0.0, az = 0.0, sum = 0.0;
+        double sums[Term::kSums] = {};
         int i = walk_entry<true>(nodes, split, seg, p, theta2);
         while (i < s1) {
             const float4 A = nodes[i].a;
@@ -1123,103 +1123,26 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk(const NodeDev* __r
             ++n_vis;
             if (r2 < 1e-10f) { i = skip; continue; }                  // skipped whole (a probe on a body skips it)
             if (B.x < theta2 * r2 || skip == i + 1) {                  // accepted cell, or a leaf that failed the test
-                const float q = r2 + eps2;
-                const float st = A.w * (1.0f / __builtin_sqrtf(q));
-                if (SCAL) sum += double(st);
-                if (VEC) {
-                    const float k = st / q;
-                    ax += double(rx * k); ay += double(ry * k); az += double(rz * k);
-                }
+                if (Term::kAny) Term::add(sums, rx, ry, rz, A.w, r2 + eps2, false);
                 ++n_acc;
                 i = skip;
             } else {
                 i = i + 1;
             }
         }
-        if (VEC || SCAL) {
-            const double bad = __longlong_as_double(0x7ff8000000000000ll);
-            planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
-        }
+        if (Term::kAny) store_probe_row(planes, seg, plane_stride, t, sums, finite);
     }
     add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
-void launch_bh_field_walk(hipStream_t s, const FieldTree& t, const double* xyz, const int* idx, int n, float eps2, float theta2, int want,
-                          double4* planes, size_t stride, unsigned long long* counters) {
+void launch_bh_probe_walk(hipStream_t s, ProbeTerm term, const FieldTree& t, const double* xyz, const int* idx, int n, float eps2, float theta2,
+                          double* planes, size_t stride, unsigned long long* counters) {
     if (n <= 0) return;
     WalkSplit sp{};
     sp.n_seg = t.K; sp.first = t.first; sp.anc = t.anc; sp.n_anc = t.n_anc;
     const dim3 grid((n + kWalkBlock - 1) / kWalkBlock, t.K);
     const NodeDev* nodes = static_cast<const NodeDev*>(t.nodes);
-#define FIELD_WALK(V, S) hipLaunchKernelGGL((k_bh_field_walk<V, S>), grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
-    if (want == 3) FIELD_WALK(true, true); else if (want == 1) FIELD_WALK(true, false); else if (want == 2) FIELD_WALK(false, true); else FIELD_WALK(false, false);
-#undef FIELD_WALK
-}
-
-// ---- nbody_tidal_at(NBODY_POTENTIAL_TREE): k_bh_field_walk's loop -- entry, loads, opening tests, counters and NaN rule restated
-// line for line, so {accepted, visited} equal that walk's -- with the tidal term of kernels_tidal.h in f32 (k3 = (3 k) / q,
-// u = d k3: the accepted nodes are 1e-5 away or more, so k3 <= 3 m 1e25 stays in range) and six f64 sums.  With r2 = inf:
-// inv = k = k3 = 0 and finite d times 0: exact zeros.  SUMS = false: count only.
-template <bool SUMS>
-__global__ __launch_bounds__(kWalkBlock) void k_bh_tidal_walk(const NodeDev* __restrict__ nodes, const double* __restrict__ xyz,
-                                                              const int* __restrict__ idx, int n, float eps2, float theta2,
-                                                              unsigned long long* __restrict__ counters, WalkSplit split,
-                                                              double2* __restrict__ planes, size_t plane_stride) {
-    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
-    const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);   // (as k_bh_walk dispatches them)
-    const int s1 = split.first[seg + 1];
-    unsigned int n_acc = 0, n_vis = 0;
-    if (t < n) {
-        const size_t c = size_t(idx[t]);
-        const float4 p = make_float4(float(xyz[3 * c]), float(xyz[3 * c + 1]), float(xyz[3 * c + 2]), 0.f);
-        const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-        double xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
-        int i = walk_entry<true>(nodes, split, seg, p, theta2);
-        while (i < s1) {
-            const float4 A = nodes[i].a;
-            const float2 B = *reinterpret_cast<const float2*>(&nodes[i].b);
-            asm volatile("" :: "v"(A.w), "v"(B.y));   // (both loads whole and ahead of the branches: see k_bh_walk)
-            const float rx = A.x - p.x, ry = A.y - p.y, rz = A.z - p.z;
-            const float r2 = (rx * rx + ry * ry) + rz * rz;
-            const int skip = __float_as_int(B.y);
-            ++n_vis;
-            if (r2 < 1e-10f) { i = skip; continue; }                  // skipped whole (a probe on a body skips it)
-            if (B.x < theta2 * r2 || skip == i + 1) {                  // accepted cell, or a leaf that failed the test
-                if (SUMS) {
-                    const float q = r2 + eps2;
-                    const float st = A.w * (1.0f / __builtin_sqrtf(q));
-                    const float k = st / q;
-                    const float k3 = (3.0f * k) / q;
-                    const float ux = rx * k3, uy = ry * k3, uz = rz * k3;
-                    xx += double(rx * ux - k); yy += double(ry * uy - k); zz += double(rz * uz - k);
-                    xy += double(rx * uy); xz += double(rx * uz); yz += double(ry * uz);
-                }
-                ++n_acc;
-                i = skip;
-            } else {
-                i = i + 1;
-            }
-        }
-        if (SUMS) {
-            const double bad = __longlong_as_double(0x7ff8000000000000ll);
-            double2* __restrict__ row = planes + (size_t(seg) * plane_stride + t) * kTidalRow;
-            row[0] = finite ? make_double2(xx, xy) : make_double2(bad, bad);
-            row[1] = finite ? make_double2(xz, yy) : make_double2(bad, bad);
-            row[2] = finite ? make_double2(yz, zz) : make_double2(bad, bad);
-        }
-    }
-    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
-}
-
-void launch_bh_tidal_walk(hipStream_t s, const FieldTree& t, const double* xyz, const int* idx, int n, float eps2, float theta2, int sums,
-                          double2* planes, size_t stride, unsigned long long* counters) {
-    if (n <= 0) return;
-    WalkSplit sp{};
-    sp.n_seg = t.K; sp.first = t.first; sp.anc = t.anc; sp.n_anc = t.n_anc;
-    const dim3 grid((n + kWalkBlock - 1) / kWalkBlock, t.K);
-    const NodeDev* nodes = static_cast<const NodeDev*>(t.nodes);
-    if (sums) hipLaunchKernelGGL(k_bh_tidal_walk<true>, grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride);
-    else hipLaunchKernelGGL(k_bh_tidal_walk<false>, grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride);
+    NBODY_PROBE_TERM(term, hipLaunchKernelGGL(k_bh_probe_walk<Term>, grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride));
 }
 
 // ---- tracers on a Barnes-Hut handle (kernels_tracer.h): k_bh_walk<FAST = true, DIRECT> for particles that are in no tree.

@@ -8,7 +8,7 @@
 #include "kernels_f64.h"
 #include "kernels.h"   // nbody::tuning()
 #include "kernels_field.h"
-#include "kernels_tidal.h"
+#include "probe_term.h"
 #include "walk_common.h"
 
 #include <algorithm>
@@ -245,13 +245,13 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_pot_walk64(const Node64* __re
     add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
-// ---- nbody_field_at(NBODY_POTENTIAL_TREE) on an f64 handle: kernels_bh.hip k_bh_field_walk for 64-byte records (the same
-// tests, terms and NaN rule, all in f64)
-template <bool VEC, bool SCAL>
-__global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk64(const Node64* __restrict__ nodes, const double* __restrict__ xyz,
+// ---- nbody_field_at / nbody_tidal_at (NBODY_POTENTIAL_TREE) on an f64 handle: kernels_bh.hip k_bh_probe_walk for 64-byte
+// records (the same tests, Term and NaN rule, all in f64)
+template <class Term>
+__global__ __launch_bounds__(kWalkBlock) void k_bh_probe_walk64(const Node64* __restrict__ nodes, const double* __restrict__ xyz,
                                                                 const int* __restrict__ idx, int n, double eps2, double theta2,
                                                                 unsigned long long* __restrict__ counters, WalkSplit64 split,
-                                                                double4* __restrict__ planes, size_t plane_stride) {
+                                                                double* __restrict__ planes, size_t plane_stride) {
     const int t = blockIdx.x * kWalkBlock + threadIdx.x;
     const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
     const int s1 = split.first[seg + 1];
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk64(const Node64* __
         const size_t c = size_t(idx[t]);
         const double4 p = make_double4(xyz[3 * c], xyz[3 * c + 1], xyz[3 * c + 2], 0.0);
         const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-        double ax = 0.0, ay = 0.0, az = 0.0, sum = 0.0;
+        double sums[Term::kSums] = {};
         int i = walk_entry64(nodes, split, seg, p, theta2, true);
         while (i < s1) {
             const Node64 nd = nodes[i];
@@ -270,74 +270,14 @@ __global__ __launch_bounds__(kWalkBlock) void k_bh_field_walk64(const Node64* __
             ++n_vis;
             if (r2 < 1e-10) { i = skip; continue; }
             if (nd.w2 < theta2 * r2 || skip == i + 1) {
-                const double q = r2 + eps2;
-                const double st = nd.m * (1.0 / __builtin_sqrt(q));
-                if (SCAL) sum += st;
-                if (VEC) {
-                    const double k = st / q;
-                    ax += rx * k; ay += ry * k; az += rz * k;
-                }
+                if (Term::kAny) Term::add(sums, rx, ry, rz, nd.m, r2 + eps2, false);
                 ++n_acc;
                 i = skip;
             } else {
                 i = i + 1;
             }
         }
-        if (VEC || SCAL) {
-            const double bad = __longlong_as_double(0x7ff8000000000000ll);
-            planes[size_t(seg) * plane_stride + t] = finite ? make_double4(ax, ay, az, sum) : make_double4(bad, bad, bad, bad);
-        }
-    }
-    add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
-}
-
-// ---- nbody_tidal_at(NBODY_POTENTIAL_TREE) on an f64 handle: k_bh_field_walk64's loop restated (the same entry, tests, counters
-// and NaN rule, so the counts agree) with the tidal term of kernels_tidal.h, all in f64.  SUMS = false: count only.
-template <bool SUMS>
-__global__ __launch_bounds__(kWalkBlock) void k_bh_tidal_walk64(const Node64* __restrict__ nodes, const double* __restrict__ xyz,
-                                                                const int* __restrict__ idx, int n, double eps2, double theta2,
-                                                                unsigned long long* __restrict__ counters, WalkSplit64 split,
-                                                                double2* __restrict__ planes, size_t plane_stride) {
-    const int t = blockIdx.x * kWalkBlock + threadIdx.x;
-    const int seg = nearest_first_segment(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
-    const int s1 = split.first[seg + 1];
-    unsigned int n_acc = 0, n_vis = 0;
-    if (t < n) {
-        const size_t c = size_t(idx[t]);
-        const double4 p = make_double4(xyz[3 * c], xyz[3 * c + 1], xyz[3 * c + 2], 0.0);
-        const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-        double xx = 0.0, xy = 0.0, xz = 0.0, yy = 0.0, yz = 0.0, zz = 0.0;
-        int i = walk_entry64(nodes, split, seg, p, theta2, true);
-        while (i < s1) {
-            const Node64 nd = nodes[i];
-            const double rx = nd.x - p.x, ry = nd.y - p.y, rz = nd.z - p.z;
-            const double r2 = (rx * rx + ry * ry) + rz * rz;
-            const int skip = nd.skip;
-            ++n_vis;
-            if (r2 < 1e-10) { i = skip; continue; }
-            if (nd.w2 < theta2 * r2 || skip == i + 1) {
-                if (SUMS) {
-                    const double q = r2 + eps2;
-                    const double st = nd.m * (1.0 / __builtin_sqrt(q));
-                    const double k = st / q;
-                    const double k3 = (3.0 * k) / q;
-                    const double ux = rx * k3, uy = ry * k3, uz = rz * k3;
-                    xx += rx * ux - k; yy += ry * uy - k; zz += rz * uz - k;
-                    xy += rx * uy; xz += rx * uz; yz += ry * uz;
-                }
-                ++n_acc;
-                i = skip;
-            } else {
-                i = i + 1;
-            }
-        }
-        if (SUMS) {
-            const double bad = __longlong_as_double(0x7ff8000000000000ll);
-            double2* __restrict__ row = planes + (size_t(seg) * plane_stride + t) * nbody::kTidalRow;
-            row[0] = finite ? make_double2(xx, xy) : make_double2(bad, bad);
-            row[1] = finite ? make_double2(xz, yy) : make_double2(bad, bad);
-            row[2] = finite ? make_double2(yz, zz) : make_double2(bad, bad);
-        }
+        if (Term::kAny) nbody::store_probe_row(planes, seg, plane_stride, t, sums, finite);
     }
     add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
@@ -420,24 +360,13 @@ void launch_bh_pot_walk(hipStream_t s, const double4* pos, const Node64* nodes, 
     hipLaunchKernelGGL(k_bh_pot_walk64, dim3(blocks_for(n_order, kWalkBlock), split.n_seg), dim3(kWalkBlock), 0, s, nodes, order, n_order, pos,
                        eps2, theta2, counters, split, planes, plane_stride);
 }
-void launch_bh_field_walk(hipStream_t s, const nbody::FieldTree& t, const double* xyz, const int* idx, int n, double eps2, double theta2, int want,
-                          double4* planes, size_t stride, unsigned long long* counters) {
+void launch_bh_probe_walk(hipStream_t s, nbody::ProbeTerm term, const nbody::FieldTree& t, const double* xyz, const int* idx, int n, double eps2,
+                          double theta2, double* planes, size_t stride, unsigned long long* counters) {
     if (n <= 0) return;
     const WalkSplit64 sp{t.K, t.first, t.anc, t.n_anc, nullptr, 0};
     const dim3 grid(blocks_for(n, kWalkBlock), t.K);
     const Node64* nodes = static_cast<const Node64*>(t.nodes);
-#define FIELD_WALK(V, S) hipLaunchKernelGGL((k_bh_field_walk64<V, S>), grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride)
-    if (want == 3) FIELD_WALK(true, true); else if (want == 1) FIELD_WALK(true, false); else if (want == 2) FIELD_WALK(false, true); else FIELD_WALK(false, false);
-#undef FIELD_WALK
-}
-void launch_bh_tidal_walk(hipStream_t s, const nbody::FieldTree& t, const double* xyz, const int* idx, int n, double eps2, double theta2, int sums,
-                          double2* planes, size_t stride, unsigned long long* counters) {
-    if (n <= 0) return;
-    const WalkSplit64 sp{t.K, t.first, t.anc, t.n_anc, nullptr, 0};
-    const dim3 grid(blocks_for(n, kWalkBlock), t.K);
-    const Node64* nodes = static_cast<const Node64*>(t.nodes);
-    if (sums) hipLaunchKernelGGL(k_bh_tidal_walk64<true>, grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride);
-    else hipLaunchKernelGGL(k_bh_tidal_walk64<false>, grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride);
+    NBODY_PROBE_TERM(term, hipLaunchKernelGGL(k_bh_probe_walk64<Term>, grid, dim3(kWalkBlock), 0, s, nodes, xyz, idx, n, eps2, theta2, counters, sp, planes, stride));
 }
 void launch_energy(hipStream_t s, const Dev& d, int n_upper, double eps2, double* out2) {
     if (n_upper <= 0) return;

@@ -7,31 +7,24 @@
 //                 wave's LDS tile, lane l reads the one it meets and holds that body's running sum, which moves one lane
 //                 per step (2 ds_bpermute_b32).  Set a meets the chunks of sets a+1 .. a+ceil(A/2)-1 (cyclic): every
 //                 unordered pair between different sets at those distances is evaluated once and credited to both bodies.
-//   k_pot_os      one-sided, one body per lane, partners staged 64 at a time in the wave's LDS tile.  MODE 0: every own
+//   k_pot_os      one-sided, one body per lane, partners through the wave's LDS tile (partner_stream.h).  MODE 0: every own
 //                 body (small blocks); MODE 1: what k_pot_sym leaves over (the own set and, for even A, the opposite
 //                 set); MODE 2: the other index blocks' bodies (between shards the sum is one-sided: the travelling side
 //                 would have to be sent back to its owner, and this is a diagnostic, not the step).
 //   k_pot_pairs_reduce   the planes added in plane order.
 // Every plane entry is written exactly once per call and there are no atomics: the same bits from run to run.
 #include "kernels_pot.h"
-#include "real.h"   // widen
+#include "pair64.h"
+#include "partner_stream.h"
 
 namespace nbody {
 
 namespace {
 
-// zero-mass padding bodies sit far away: they add nothing to real bodies.  Where two padding bodies meet with eps2 = 0 the term
-// is 0 * inf = NaN: it lands in the padding bodies' own rows (>= the live count) only, which k_pot_pairs_reduce never reads.
-constexpr double kPad = 1.0e100;
-
-__device__ __forceinline__ double4 pad_body() { return make_double4(kPad, kPad, kPad, 0.0); }
-
-__device__ __forceinline__ double rot64(double v, int src_x4) {   // lane l receives lane (src_x4 / 4)'s value
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_ds_bpermute(src_x4, int(b));
-    const int hi = __builtin_amdgcn_ds_bpermute(src_x4, int(b >> 32));
-    return __longlong_as_double((long long)(unsigned)lo | ((long long)hi << 32));
-}
+// pad_body: where two padding bodies meet with eps2 = 0 the term is 0 * inf = NaN: it lands in the padding bodies' own rows
+// (>= the live count) only, which k_pot_pairs_reduce never reads
+using nbody64::pair64::pad_body;
+using nbody64::pair64::rot64;
 
 __device__ __forceinline__ double inv_dist(const double4 a, double bx, double by, double bz, double eps2) {
     const double dx = a.x - bx, dy = a.y - by, dz = a.z - bz;
@@ -95,26 +88,6 @@ __global__ __launch_bounds__(256) void k_pot_sym(const P* __restrict__ pos, cons
     for (int q = 0; q < IPT; ++q) out[size_t(a * IPT + q) * 64 + lane] = si[q];
 }
 
-struct Win { int seg, lo, hi; };   // one window of partners: bodies [lo, hi) of segment seg
-
-template <int MODE>
-__device__ __forceinline__ int n_windows(int n_seg, int A) {
-    return MODE == 0 ? 1 : MODE == 1 ? ((A % 2 == 0 && A > 1) ? 2 : 1) : n_seg - 1;
-}
-
-template <int MODE>
-__device__ __forceinline__ Win window(int w, const int* __restrict__ seg_count, int my_seg, int n_own, int set_size, int A, int a) {
-    if (MODE == 0) return Win{my_seg, 0, n_own};
-    if (MODE == 1) {
-        int set = (w == 0) ? a : a + A / 2;
-        if (set >= A) set -= A;
-        const int lo = min(n_own, set * set_size), hi = min(n_own, lo + set_size);
-        return Win{my_seg, lo, hi};
-    }
-    const int s = w < my_seg ? w : w + 1;   // every other segment, in order
-    return Win{s, 0, seg_count[s]};
-}
-
 // 4 waves per workgroup; wave gw = group * K + slice: bodies group*64 + lane of the own block against slice `slice` of the
 // partner list.  Output: plane `slice`, rows group*64 .. group*64+63 (every row, padding included).
 template <class P, int MODE>
@@ -131,36 +104,13 @@ __global__ __launch_bounds__(256) void k_pot_os(const P* __restrict__ pos_all, c
     const int i = group * 64 + lane;
     const double4 pi = (i < n_own) ? widen(pos_all[size_t(my_seg) * seg_cap + i]) : pad_body();
     const int a = (group * 64) / set_size;       // (MODE 1: the set of all 64 bodies of the group)
-    const int nw = n_windows<MODE>(n_seg, A);
-    long long R = 0;
-    for (int w = 0; w < nw; ++w) {
-        const Win win = window<MODE>(w, seg_count, my_seg, n_own, set_size, A, a);
-        R += max(0, win.hi - win.lo);
-    }
-    const long long r0 = R * slice / K, r1 = R * (slice + 1) / K;
     double sum = 0.0;
-    long long first = 0;   // index of the window's first body in the concatenated partner list
-    for (int w = 0; w < nw; ++w) {
-        const Win win = window<MODE>(w, seg_count, my_seg, n_own, set_size, A, a);
-        const int len = max(0, win.hi - win.lo);
-        const long long lo = max(r0, first), hi = min(r1, first + len);
-        if (lo < hi) {
-            const P* __restrict__ ps = pos_all + size_t(win.seg) * seg_cap + win.lo;   // ps[c - first]: partner c
-            const long long self = (win.seg == my_seg && i >= win.lo && i < win.hi) ? first + (i - win.lo) : -1;
-            double4 nxt = (lo + lane < hi) ? widen(ps[lo + lane - first]) : pad_body();
-            for (long long c0 = lo; c0 < hi; c0 += 64) {
-                tile[wv][lane] = nxt;   // the wave's own tile: its LDS operations complete in program order
-                if (c0 + 64 + lane < hi) nxt = widen(ps[c0 + 64 + lane - first]);
-                const int cnt = int(min(64LL, hi - c0));
-                for (int t = 0; t < cnt; ++t) {
-                    const double4 pj = tile[wv][t];   // wave-uniform address: an LDS broadcast
-                    const double term = pj.w * inv_dist(pj, pi.x, pi.y, pi.z, eps2);
-                    sum += (c0 + t == self) ? 0.0 : term;   // no i == j term
-                }
-            }
-        }
-        first += len;
-    }
+    stream_partners(
+        tile[wv], lane, pos_all, seg_cap, n_windows<MODE>(n_seg, A), [&](int w) { return window<MODE>(w, seg_count, my_seg, n_own, set_size, A, a); },
+        slice, K, [&](const double4 pj, int seg, int j) {
+            const double term = pj.w * inv_dist(pj, pi.x, pi.y, pi.z, eps2);
+            sum += (seg == my_seg && j == i) ? 0.0 : term;   // no i == j term
+        });
     planes[size_t(slice) * plane_stride + i] = sum;
 }
 

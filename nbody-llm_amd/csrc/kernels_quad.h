@@ -27,7 +27,7 @@ void launch_bh_walk_quad(hipStream_t s, const Shard& sh, const TreeDev& t, const
 // 1/2 (d^T Q d) inv^5 of every accepted internal node, IEEE f32 arithmetic, f64 sums; then launch_pot_reduce.
 void launch_bh_pot_walk_quad(hipStream_t s, const float4* own_pos, const TreeDev& t, const float4* quad, float g_soft2, float theta2,
                              double* planes, size_t plane_stride, double* sum, unsigned long long* counters);
-// ... nbody_field_at: launch_bh_field_walk (kernels_field.h) with the scalar and the vector part; the caller reduces
+// ... nbody_field_at: launch_bh_probe_walk (kernels_field.h) with the scalar and the vector part; the caller reduces
 void launch_bh_field_walk_quad(hipStream_t s, const FieldTree& t, const float4* quad, const double* xyz, const int* idx, int n, float eps2,
                                float theta2, int want, double4* planes, size_t stride, unsigned long long* counters);
 

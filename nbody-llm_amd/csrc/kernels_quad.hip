@@ -11,7 +11,7 @@
 // (the gradient of phi = -g [M inv + 1/2 d^T Q d inv^5]).  The opening tests are the oracle's f32 expressions, untouched,
 // so {accepted, visited} equal the monopole walk's on the same tree.  The tensor is a second dependent gather, issued
 // only after the opening test has accepted an internal node: opened nodes and leaves never touch the side array.
-// k_bh_pot_walk_quad and k_bh_field_walk_quad are kernels_bh.hip's k_bh_pot_walk<double> and k_bh_field_walk with the same
+// k_bh_pot_walk_quad and k_bh_field_walk_quad are kernels_bh.hip's k_bh_pot_walk<double> and k_bh_probe_walk with the same
 // term (and its scalar counterpart) in IEEE f32 arithmetic: see pot_quad_parts below.
 #include "kernels_quad.h"
 #include "walk_common.h"
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const NodeDev* __restric
 }
 
 // ---- NBODY_POTENTIAL_TREE_QUADRUPOLE: the potential walk and the field walk with the term of every accepted internal node.
-// A leaf's term is the monopole walk's, rounded as k_bh_pot_walk / k_bh_field_walk round it.  The quadrupole parts of an
+// A leaf's term is the monopole walk's, rounded as k_bh_pot_walk / k_bh_probe_walk round it.  The quadrupole parts of an
 // internal node, operation by operation (every line one f32 rounding, fmaf one; IEEE sqrt and divide; tests/quad_pot_list.py
 // counts these roundings for its bounds):
 //     q   = r2 + eps2            s = sqrtf(q)            inv = 1.0f / s
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(BLOCK) void k_bh_walk_quad(const NodeDev* __restric
 //   scalar   P   = ((0.5f * uqu) * i2) * inv                                     = 1/2 (d^T Q d) inv^5
 //     i4  = i2 * i2              w = (2.5f * uqu) * i4
 //   vector   V_c = fmaf(w, u_c, -(i4 * p_c))                                     = 2.5 inv^7 (d^T Q d) d_c - inv^5 (Q d)_c
-// The monopole parts of an internal node are k_bh_field_walk's: st = M * inv, vector d_c * (st / q).  No power of inv beyond
+// The monopole parts of an internal node are k_bh_probe_walk's: st = M * inv, vector d_c * (st / q).  No power of inv beyond
 // the fourth: nodes closer than 1e-5 are skipped whole, so inv <= 1e5 and i4 <= 1e20.  A probe so far away that r2 overflows
 // has inv = 0, u = 0 (d is finite) and st / q = 0 / inf = 0: every part is an exact zero, never 0 * inf.
 struct QuadParts { float P, Vx, Vy, Vz; };
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_pot_walk_quad(const NodeD
     add_walk_counts(counters, blockIdx.x + blockIdx.y * gridDim.x, n_acc, n_vis);
 }
 
-// k_bh_field_walk<VEC, SCAL> (kernels_bh.hip) with both quadrupole parts
+// k_bh_probe_walk<FieldTerm<VEC, SCAL>> (kernels_bh.hip) with both quadrupole parts
 template <bool VEC, bool SCAL>
 __global__ __launch_bounds__(kQuadWalkBlock) void k_bh_field_walk_quad(const NodeDev* __restrict__ nodes, const QuadDev* __restrict__ quad,
                                                                        const double* __restrict__ xyz, const int* __restrict__ idx, int n,

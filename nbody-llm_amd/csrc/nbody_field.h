@@ -2,7 +2,6 @@
 #pragma once
 #include "nbody_handle.h"
 #include "kernels_field.h"
-#include "kernels_tidal.h"
 
 namespace nbody { namespace field {
 
@@ -10,8 +9,8 @@ namespace nbody { namespace field {
 // counters are zeroed.  Sends the probes through the device in batches of kFieldBatch: TREE sorts each batch by Morton key,
 // walks it and scatters back in the reduce; PAIRS sums K slices of the body list.  K is chosen once per call, so a probe's
 // bits do not depend on the batch or the lane it lands in.
-// What the call returns: nbody_field_at acc [n][3] and phi [n]; nbody_tidal_at (tidal = true) tidal6 [n][6], through the
-// kernels of kernels_tidal.h over the same batches.  Every pointer may be null (all null: count only).
+// What the call returns: nbody_field_at acc [n][3] and phi [n]; nbody_tidal_at (tidal = true) tidal6 [n][6], the same
+// kernels with another ProbeTerm over the same batches.  Every pointer may be null (all null: count only).
 struct Out {
     double* acc = nullptr;
     double* phi = nullptr;

@@ -166,6 +166,25 @@ def test_pair_field_against_numpy(gpu, orc, f64, method):
     report(f"PAIRS {'f64' if f64 else 'f32'} {method}", worst)
 
 
+NP_SWITCH = 16384   # probes up to which the pair kernel keeps one per lane (probe_term.h kOnePerLaneUpTo)
+
+
+@pytest.mark.parametrize("f64", [False, True])
+def test_pairs_beyond_the_probes_per_lane_switch(gpu, f64):
+    nb = gpu
+    rec = bodies(nb, 300, seed=11, f64=f64)
+    rng = np.random.default_rng(12)
+    pts = np.concatenate([rec["position"].astype(np.float64)[:100], rng.uniform(-32, 32, (NP_SWITCH + 1 - 100, 3))])
+    ref = field_list.pair_field(rec, pts, 0.01)
+    with nb.Simulation(rec, *BOX, method=nb.BRUTE_FORCE) as sim:
+        sim.settings = nb.Settings(G, 0.01, 1e-3, 0.25)
+        acc, phi, counts = sim.field_at(pts, nb.POTENTIAL_PAIRS)
+        worst = field_list.check_field(acc, phi, counts, ref, G, "pairs", f64, 300, what="PAIRS four probes per lane")
+        a1, p1, _ = sim.field_at(pts[:64], nb.POTENTIAL_PAIRS)   # one probe per lane: the same sums in the same order
+        assert np.array_equal(a1.view(np.uint64), acc[:64].view(np.uint64)) and np.array_equal(p1.view(np.uint64), phi[:64].view(np.uint64))
+    report(f"PAIRS {'f64' if f64 else 'f32'} M={NP_SWITCH + 1}", worst)
+
+
 # ---------------------------------------------------------------------------------------------- 4. determinism
 @pytest.mark.parametrize("mode", ["tree", "pairs"])
 @pytest.mark.parametrize("f64", [False, True])

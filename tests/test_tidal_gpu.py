@@ -13,7 +13,7 @@ import tidal_list
 pytestmark = pytest.mark.gpu
 BOX = ((0.0, 0.0, 0.0), 64.0)
 G = 1.25
-NP_SWITCH = 16384   # probes up to which k_tidal_pairs keeps one per lane (kernels_tidal.hip)
+NP_SWITCH = 16384   # probes up to which the pair kernel keeps one per lane (probe_term.h kOnePerLaneUpTo)
 BATCH = 65536       # probes per batch (nbody_handle.h kFieldBatch)
 _refs: dict = {}    # references computed once, shared between the parametrised cases, never written to
 
