@@ -198,42 +198,22 @@ int ensure_sym_plan(NbodyHandle* h) {
             p.n_planes += p.k_os;
         }
     }
-    if (!h->d_sym_bounds) HIP_TRY(h, hipMalloc(&h->d_sym_bounds, 128 * sizeof(int)));
+    if (!h->d_sym_bounds) HIP_TRY(h, h->mem.dev(h->d_sym_bounds, 128 * sizeof(int)));
     HIP_TRY(h, hipMemcpyAsync(h->d_sym_bounds, p.bounds.data(), p.bounds.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // p.bounds is pageable
-    const size_t need = size_t(p.n_planes) * p.plane_stride;
-    if (need > h->planes_cap) {
-        if (h->d_planes) (void)hipFree(h->d_planes);
-        h->d_planes = nullptr; h->planes_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_planes, need * sizeof(float4)));
-        h->planes_cap = need;
-    }
+    HIP_TRY(h, grow_dev(h, h->d_planes, h->planes_cap, size_t(p.n_planes) * p.plane_stride, sizeof(float4), Grow::exact));
     if (h->cross_on) {
         const nbody::CrossPlan& c = h->cross;
-        if (c.slices.size() > h->cross_slices_cap) {
-            if (h->d_cross_slices) (void)hipFree(h->d_cross_slices);
-            h->d_cross_slices = nullptr; h->cross_slices_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_cross_slices, (c.slices.size() + 64) * sizeof(int4)));
-            h->cross_slices_cap = c.slices.size() + 64;
-        }
+        if (c.slices.size() > h->cross_slices_cap)
+            HIP_TRY(h, grow_dev(h, h->d_cross_slices, h->cross_slices_cap, c.slices.size() + 64, sizeof(int4), Grow::exact));
         if (!c.slices.empty()) {
             HIP_TRY(h, hipMemcpyAsync(h->d_cross_slices, c.slices.data(), c.slices.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
         }
         const size_t xneed = size_t(std::max(1, c.parts.n)) * size_t(c.A) * p.plane_stride;
-        if (xneed > h->xplanes_cap) {
-            if (h->d_xplanes) (void)hipFree(h->d_xplanes);
-            h->d_xplanes = nullptr; h->xplanes_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_xplanes, xneed * sizeof(float4)));
-            h->xplanes_cap = xneed;
-        }
+        HIP_TRY(h, grow_dev(h, h->d_xplanes, h->xplanes_cap, xneed, sizeof(float4), Grow::exact));
         const size_t sneed = size_t(std::max(1, c.parts.n)) * p.plane_stride;
-        if (sneed > h->send_cap) {
-            if (h->d_send) (void)hipFree(h->d_send);
-            h->d_send = nullptr; h->send_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_send, sneed * sizeof(float4)));
-            h->send_cap = sneed;
-        }
+        HIP_TRY(h, grow_dev(h, h->d_send, h->send_cap, sneed, sizeof(float4), Grow::exact));
     }
     return NBODY_OK;
 }
@@ -341,11 +321,9 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
     // (its stack holds the 42 levels of the device build; a deeper host-built tree is walked by k_bh_walk)
     if (h->cfg.math_mode == NBODY_MATH_FAST && nbody::tuning().bh_walk_variant == 5 && (h->tree.on_device || h->tree.host.max_depth <= 42)) {
         if (h->bfs_cap < h->tree.node_cap) {
-            if (h->d_bfs) (void)hipFree(h->d_bfs);
-            if (h->d_bfs_ws) (void)hipFree(h->d_bfs_ws);
-            h->d_bfs = nullptr; h->d_bfs_ws = nullptr; h->bfs_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_bfs, h->tree.node_cap * 2 * sizeof(float4)));
-            HIP_TRY(h, hipMalloc(&h->d_bfs_ws, nbody::bfs_workspace_bytes(h->tree.node_cap)));
+            h->bfs_cap = 0;
+            HIP_TRY(h, h->mem.dev(h->d_bfs, h->tree.node_cap * 2 * sizeof(float4)));
+            HIP_TRY(h, h->mem.dev(h->d_bfs_ws, nbody::bfs_workspace_bytes(h->tree.node_cap)));
             h->bfs_cap = h->tree.node_cap;
         }
         td->bfs = h->d_bfs; td->bfs_ws = h->d_bfs_ws; td->bfs_cap = h->bfs_cap;
@@ -354,25 +332,22 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
     if (h->cfg.math_mode != NBODY_MATH_FAST || nbody::tuning().bh_walk_variant != 3 || nbody::tuning().bh_hot_cap <= 0) return NBODY_OK;
     const int M = std::min(nbody::tuning().bh_hot_cap, 5000);  // 160 KB of LDS per CU, 32 B per record
     if (h->walk_cap < h->tree.node_cap) {
-        if (h->d_walk) (void)hipFree(h->d_walk);
-        if (h->d_unified) (void)hipFree(h->d_unified);
-        h->d_walk = nullptr; h->d_unified = nullptr; h->walk_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_walk, (h->tree.node_cap + 1) * 2 * sizeof(float4)));
-        HIP_TRY(h, hipMalloc(&h->d_unified, (h->tree.node_cap + 1) * sizeof(int)));
+        h->walk_cap = 0;
+        HIP_TRY(h, h->mem.dev(h->d_walk, (h->tree.node_cap + 1) * 2 * sizeof(float4)));
+        HIP_TRY(h, h->mem.dev(h->d_unified, (h->tree.node_cap + 1) * sizeof(int)));
         h->walk_cap = h->tree.node_cap;
     }
     if (h->hot_cap != M) {
-        if (h->d_hot) (void)hipFree(h->d_hot);
-        h->d_hot = nullptr; h->hot_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_hot, size_t(M) * 2 * sizeof(float4)));
+        h->hot_cap = 0;
+        HIP_TRY(h, h->mem.dev(h->d_hot, size_t(M) * 2 * sizeof(float4)));
         HIP_TRY(h, hipMemsetAsync(h->d_hot, 0, size_t(M) * 2 * sizeof(float4), h->stream));
         h->hot_cap = M;
         h->hot_threshold_n = 0;
     }
     if (!h->d_hot_info) {
-        HIP_TRY(h, hipMalloc(&h->d_hot_info, 2 * sizeof(int)));
+        HIP_TRY(h, h->mem.dev(h->d_hot_info, 2 * sizeof(int)));
         HIP_TRY(h, hipMemsetAsync(h->d_hot_info, 0, 2 * sizeof(int), h->stream));
-        HIP_TRY(h, hipHostMalloc(&h->h_hot_info, 2 * sizeof(int), hipHostMallocDefault));
+        HIP_TRY(h, h->mem.pin(h->h_hot_info, 2 * sizeof(int)));
         h->h_hot_info[0] = h->h_hot_info[1] = 0;
     }
     if (h->hot_threshold_n == 0 || n_tree > 2 * h->hot_threshold_n || 2 * n_tree < h->hot_threshold_n) {
@@ -393,8 +368,7 @@ int setup_lds_walk(NbodyHandle* h, nbody::TreeDev* td, size_t n_tree) {
 // the cells' tensors from the node array as it now stands on the device (k_tree_quad), for the walk that follows
 // (sized like the node array: a step without read-back knows its capacity only, and the build's node count on the device)
 int fill_quadrupoles(NbodyHandle* h, const nbody::TreeDev& td, bool any_nodes) {
-    int rc = grow_dev(h, h->d_quad, h->quad_cap, h->tree.node_cap, nbody::kQuadRecBytes);
-    if (rc) return rc;
+    HIP_TRY(h, grow_dev(h, h->d_quad, h->quad_cap, h->tree.node_cap, nbody::kQuadRecBytes, Grow::quarter));
     const bool counted_on_device = td.n_order_dev != nullptr;
     if (any_nodes) nbody::launch_tree_quad(h->stream, td.nodes, td.n_nodes, h->d_quad, counted_on_device ? h->tree.bufs.d_info : nullptr, td.poison);
     return NBODY_OK;
@@ -756,11 +730,11 @@ int spatial_walk(NbodyHandle* h, NbodyHandle* twin, int n_orig) {
     int rc = nbody::let::potential_pass(twin);
     if (rc) return fail(h, rc, twin->err);
     rc = nbody::pot::begin(h, size_t(cap));
-    if (!rc) rc = grow_dev(h, p.d_rec, p.rec_cap, size_t(G) * size_t(cap), sizeof(nbody::PotRec));
-    const size_t n_ids = size_t(h->cfg.capacity) + 1;
-    if (!rc) rc = grow_dev(h, p.d_slot_of, p.slot_cap, n_ids, sizeof(int));
     if (rc) return rc;
-    if (!p.d_rec_count) HIP_TRY(h, hipMalloc(&p.d_rec_count, sizeof(int) * size_t(G)));
+    HIP_TRY(h, grow_dev(h, p.d_rec, p.rec_cap, size_t(G) * size_t(cap), sizeof(nbody::PotRec), Grow::quarter));
+    const size_t n_ids = size_t(h->cfg.capacity) + 1;
+    HIP_TRY(h, grow_dev(h, p.d_slot_of, p.slot_cap, n_ids, sizeof(int), Grow::quarter));
+    if (!p.d_rec_count) HIP_TRY(h, h->mem.dev(p.d_rec_count, sizeof(int) * size_t(G)));
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the counters' reset: what follows is ordered on the clone's stream)
     hipStream_t ts = twin->stream;
     nbody::PotRec* rec = static_cast<nbody::PotRec*>(p.d_rec);
@@ -893,17 +867,10 @@ void free_all(NbodyHandle* h) {
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     for (auto& ev : h->ev_pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto& ev : h->ev_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    h->tree.release();
-    nbody64::destroy(h);
+    nbody64::destroy(h);      // (the states and their events; their memory is the registry's like everything else)
     nbody::let::destroy(h);
-    nbody::tracer::release(h);
-    h->release();
-    void* dev[] = {h->d_poison, h->d_walk, h->d_unified, h->d_hot, h->d_hot_info, h->d_bfs, h->d_bfs_ws, h->d_counters, h->d_quad, h->d_energy, h->d_sym_bounds, h->d_planes, h->d_cross_slices, h->d_xplanes, h->d_send};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    void* host[] = {h->h_counters, h->h_hot_info, h->h_poison};
-    for (void* p : host) if (p) (void)hipHostFree(p);
-    h->pot.release();
-    h->field.release();
+    h->tree.host.clear();     // (the host octree's pinned node arrays are its own: nbody_handle.h pinned_alloc)
+    h->mem.release_all();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -958,20 +925,20 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
     auto bail = [&](int rc) { g_create_err = h->err; free_all(h); return rc; };
 #define CREATE_TRY(expr)                                                                                  \
     do {                                                                                                  \
-        hipError_t e_ = (expr);                                                                           \
-        if (e_ != hipSuccess) { h->err = std::string(#expr) + ": " + hipGetErrorString(e_); return bail(NBODY_ERR_HIP); } \
+        const int rc_ = [&] { HIP_TRY(h, expr); return int(NBODY_OK); }();                                \
+        if (rc_) return bail(rc_);                                                                        \
     } while (0)
     CREATE_TRY(hipSetDevice(dev));
     CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CREATE_TRY(hipHostMalloc(&h->h_poison, 8 * sizeof(int), hipHostMallocDefault));
+    CREATE_TRY(h->mem.pin(h->h_poison, 8 * sizeof(int)));
     if (cfg->method == NBODY_BARNES_HUT) {
         // default: the cores this process may run on, at most 16 (a GPU's share of the host; more
         // threads than top-level subtrees only add wake-up latency)
         int threads = cfg->host_threads > 0 ? cfg->host_threads : std::min(16, std::max(1, int(std::thread::hardware_concurrency()) - 2));
         h->pool.reset(new nbody::WorkerPool(std::max(1, threads)));
-        CREATE_TRY(hipMalloc(&h->d_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
+        CREATE_TRY(h->mem.dev(h->d_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
         CREATE_TRY(hipMemsetAsync(h->d_counters, 0, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), h->stream));
-        CREATE_TRY(hipHostMalloc(&h->h_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), hipHostMallocDefault));
+        CREATE_TRY(h->mem.pin(h->h_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
     }
     Shard& sh = h->sh;
     sh.n_seg = cfg->world_size;
@@ -996,7 +963,7 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
         int rc = h->alloc(h, h->stream);
         if (rc) return bail(rc);
     }
-    CREATE_TRY(hipMalloc(&h->d_poison, 2 * sizeof(int)));
+    CREATE_TRY(h->mem.dev(h->d_poison, 2 * sizeof(int)));
     CREATE_TRY(hipMemsetAsync(h->d_poison, 0, 2 * sizeof(int), h->stream));
     if (cfg->method == NBODY_BARNES_HUT) {
         int rc = h->tree.alloc_host(h, sh);
@@ -1570,12 +1537,7 @@ int nbody_energy(NbodyHandle* h, double* kinetic, double* potential) {
     const size_t blocks = (n + 255) / 256;
     double ke = 0.0, pe = 0.0;
     if (blocks) {
-        if (blocks > h->energy_blocks) {
-            if (h->d_energy) (void)hipFree(h->d_energy);
-            h->d_energy = nullptr; h->energy_blocks = 0;
-            HIP_TRY(h, hipMalloc(&h->d_energy, blocks * 2 * sizeof(double)));
-            h->energy_blocks = blocks;
-        }
+        HIP_TRY(h, grow_dev(h, h->d_energy, h->energy_blocks, blocks, 2 * sizeof(double), Grow::exact));
         nbody::launch_energy(h->stream, h->sh, int(n), double(h->g_soft) * double(h->g_soft), h->d_energy);
         HIP_TRY(h, hipGetLastError());
         std::vector<double> part(blocks * 2);
@@ -1802,8 +1764,7 @@ int nbody_tree_export_quadrupoles(NbodyHandle* h, float* q6, size_t cap, size_t*
     if (n == 0) return NBODY_OK;
     // of the tree nbody_tree_export reports: the node array as it stands on the device (a tree call of nbody_potentials or
     // nbody_field_at since the force pass has rebuilt it), through the kernel the force pass runs
-    rc = grow_dev(h, h->d_quad, h->quad_cap, std::max(n, h->tree.node_cap), nbody::kQuadRecBytes);
-    if (rc) return rc;
+    HIP_TRY(h, grow_dev(h, h->d_quad, h->quad_cap, std::max(n, h->tree.node_cap), nbody::kQuadRecBytes, Grow::quarter));
     nbody::launch_tree_quad(h->stream, h->tree.d_nodes, int(n), h->d_quad, nullptr, nullptr);
     HIP_TRY(h, hipGetLastError());
     std::vector<float> rec(8 * n);

@@ -19,15 +19,14 @@ int moments(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double out[10])
     for (int q = 0; q < kMoments; ++q) out[q] = 0.0;
     const size_t blocks = size_t(blocks_for(int(n_upper)));
     if (!blocks) return NBODY_OK;
-    double* d = nullptr;   // [blocks][kMoments] block sums
-    HIP_TRY(h, hipMalloc(&d, blocks * kMoments * sizeof(double)));
+    ScratchDev scratch(h->mem);   // [blocks][kMoments] block sums
+    HIP_TRY(h, scratch.alloc(blocks * kMoments * sizeof(double)));
+    double* d = scratch.get<double>();
     launch_diag_moments<F>(h->stream, sh, int(n_upper), d);
     std::vector<double> part(blocks * kMoments);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    HIP_TRY(h, e);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(part.data(), d, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (size_t b = 0; b < blocks; ++b)   // blocks in ascending order
         for (int q = 0; q < kMoments; ++q) out[q] += part[b * kMoments + q];
     return NBODY_OK;
@@ -49,9 +48,9 @@ int lagrangian_radii(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const 
         if (rc) return rc;
         for (int k = 0; k < 3; ++k) c[k] = mom[1 + k] / mom[0];
     }
-    void* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, radii_scratch_bytes(n_upper, n_frac)));
-    const RadiiScratch w = radii_scratch_layout(d, n_upper, n_frac);
+    ScratchDev scratch(h->mem);
+    HIP_TRY(h, scratch.alloc(radii_scratch_bytes(n_upper, n_frac)));
+    const RadiiScratch w = radii_scratch_layout(scratch.get(), n_upper, n_frac);
     std::vector<double> out(n_frac + 1);
     // (c, fractions and out are pageable: the copies return once the data has left or reached them)
     hipError_t e = hipMemcpyAsync(w.center, c, sizeof(c), hipMemcpyHostToDevice, h->stream);
@@ -64,7 +63,6 @@ int lagrangian_radii(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const 
     if (e == hipSuccess && !sort_failed) e = hipMemcpyAsync(out.data(), w.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     const hipError_t e_sync = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = e_sync;
-    (void)hipFree(d);
     HIP_TRY(h, e);
     if (sort_failed) return fail(h, NBODY_ERR_HIP, "nbody_lagrangian_radii: rocPRIM call failed");
     for (size_t k = 0; k < n_frac; ++k) radii[k] = out[k];

@@ -97,16 +97,15 @@ int potentials(NbodyHandle* h, const ShardT<F>& sh, size_t n, double g, double* 
     if (energy) *energy = 0.0;
     const size_t blocks = size_t(blocks_for(int(n)));
     if (!blocks) return NBODY_OK;
-    double* d = nullptr;   // [n] potentials | [blocks] block sums
-    HIP_TRY(h, hipMalloc(&d, (n + blocks) * sizeof(double)));
+    ScratchDev scratch(h->mem);   // [n] potentials | [blocks] block sums
+    HIP_TRY(h, scratch.alloc((n + blocks) * sizeof(double)));
+    double* d = scratch.get<double>();
     launch_ext_phi<F>(h->stream, sh, int(n), rounded<double>(h->ext), g, phi ? d : nullptr, d + n);
     std::vector<double> part(blocks);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && phi) e = hipMemcpyAsync(phi, d, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d + n, blocks * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d);
-    HIP_TRY(h, e);
+    HIP_TRY(h, hipGetLastError());
+    if (phi) HIP_TRY(h, hipMemcpyAsync(phi, d, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(part.data(), d + n, blocks * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     double sum = 0.0;
     for (size_t b = 0; b < blocks; ++b) sum += part[b];   // blocks in ascending order
     if (energy) *energy = sum;
@@ -118,24 +117,21 @@ template int potentials<double>(NbodyHandle*, const ShardT<double>&, size_t, dou
 int at(NbodyHandle* h, double g, const double* xyz, size_t n_points, double* acc, double* phi) {
     if (!n_points || (!acc && !phi)) return NBODY_OK;
     const size_t batch = std::min(n_points, kFieldBatch);
-    double* d = nullptr;   // [batch][3] points | [batch][3] accelerations | [batch] potentials
-    HIP_TRY(h, hipMalloc(&d, batch * 7 * sizeof(double)));
+    ScratchDev scratch(h->mem);   // [batch][3] points | [batch][3] accelerations | [batch] potentials
+    HIP_TRY(h, scratch.alloc(batch * 7 * sizeof(double)));
+    double* d = scratch.get<double>();
     double* d_acc = d + 3 * batch;
     double* d_phi = d + 6 * batch;
     const FieldT<double> f = rounded<double>(h->ext);
-    hipError_t e = hipSuccess;
-    for (size_t at0 = 0; at0 < n_points && e == hipSuccess; at0 += batch) {
+    for (size_t at0 = 0; at0 < n_points; at0 += batch) {
         const size_t n = std::min(batch, n_points - at0);
-        e = hipMemcpyAsync(d, xyz + 3 * at0, n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream);
-        if (e != hipSuccess) break;
+        HIP_TRY(h, hipMemcpyAsync(d, xyz + 3 * at0, n * 3 * sizeof(double), hipMemcpyHostToDevice, h->stream));
         launch_ext_at(h->stream, d, int(n), f, g, acc ? d_acc : nullptr, phi ? d_phi : nullptr);
-        e = hipGetLastError();
-        if (e == hipSuccess && acc) e = hipMemcpyAsync(acc + 3 * at0, d_acc, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess && phi) e = hipMemcpyAsync(phi + at0, d_phi, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // (the batch's buffers are reused by the next one)
+        HIP_TRY(h, hipGetLastError());
+        if (acc) HIP_TRY(h, hipMemcpyAsync(acc + 3 * at0, d_acc, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (phi) HIP_TRY(h, hipMemcpyAsync(phi + at0, d_phi, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the batch's buffers are reused by the next one)
     }
-    (void)hipFree(d);
-    HIP_TRY(h, e);
     return NBODY_OK;
 }
 

@@ -65,13 +65,8 @@ int PlanePass::ensure(NbodyHandle* h, size_t n_local, size_t n_remote, int n_seg
     if (std::equal(want, want + 6, key)) return NBODY_OK;
     const Bf64Plan made = make_bf64_plan(int(n_local), int(std::min<size_t>(n_remote, 0x7fffffff)), n_seg, ipt_of ? ipt_of(t.bf64_ipt) : 0);
     const size_t need = size_t(kinds) * size_t(made.n_planes) * made.n_pad;
-    if (need > cap) {
-        if (d_planes) (void)hipFree(d_planes);
-        d_planes = nullptr; cap = 0;
-        std::fill(key, key + 6, -1LL);
-        HIP_TRY(h, hipMalloc(&d_planes, need * sizeof(double4)));
-        cap = need;
-    }
+    if (need > cap) std::fill(key, key + 6, -1LL);
+    HIP_TRY(h, grow_dev(h, d_planes, cap, need, sizeof(double4), Grow::exact));
     plan = made;
     sym_pairs = bf64_sym_pairs(made, n_local);
     std::copy(want, want + 6, key);
@@ -127,10 +122,10 @@ int ensure_hermite(NbodyHandle* h, State& s) {
     const size_t cap = size_t(s.sh.seg_cap);
     double4** arr[] = {&s.hm.jerk, &s.hm.xp, &s.hm.vp, &s.hm.a1, &s.hm.j1};
     for (double4** a : arr) {
-        HIP_TRY(h, hipMalloc(a, cap * sizeof(double4)));
+        HIP_TRY(h, h->mem.dev(*a, cap * sizeof(double4)));
         HIP_TRY(h, hipMemsetAsync(*a, 0, cap * sizeof(double4), h->stream));
     }
-    HIP_TRY(h, hipMalloc(&s.hm.ratio, ((cap + 255) / 256) * sizeof(double)));
+    HIP_TRY(h, h->mem.dev(s.hm.ratio, ((cap + 255) / 256) * sizeof(double)));
     return NBODY_OK;
 }
 
@@ -175,22 +170,17 @@ int ensure_block(NbodyHandle* h, State& s) {
     if (!b.level) {
         int** arr[] = {&b.level, &b.tau, &b.list};
         for (int** a : arr) {
-            HIP_TRY(h, hipMalloc(a, cap * sizeof(int)));
+            HIP_TRY(h, h->mem.dev(*a, cap * sizeof(int)));
             HIP_TRY(h, hipMemsetAsync(*a, 0, cap * sizeof(int), h->stream));
         }
-        HIP_TRY(h, hipMalloc(&b.tile_count, ((cap + 1023) / 1024) * sizeof(int)));
-        HIP_TRY(h, hipMalloc(&b.smin, 4 * sizeof(int)));
+        HIP_TRY(h, h->mem.dev(b.tile_count, ((cap + 1023) / 1024) * sizeof(int)));
+        HIP_TRY(h, h->mem.dev(b.smin, 4 * sizeof(int)));
         HIP_TRY(h, hipMemsetAsync(b.smin, 0, 4 * sizeof(int), h->stream));
         b.sched = b.smin + 2;
-        HIP_TRY(h, hipHostMalloc(&s.h_sched, 2 * sizeof(int), hipHostMallocDefault));
+        HIP_TRY(h, h->mem.pin(s.h_sched, 2 * sizeof(int)));
     }
     const size_t rows = hm_act_plane_rows(s.sh.seg_cap);   // (follows the bf64_waves knob)
-    if (rows > b.plane_rows) {
-        if (b.planes) (void)hipFree(b.planes);
-        b.planes = nullptr; b.plane_rows = 0;
-        HIP_TRY(h, hipMalloc(&b.planes, 2 * rows * sizeof(double4)));   // accelerations, then jerks
-        b.plane_rows = rows;
-    }
+    HIP_TRY(h, grow_dev(h, b.planes, b.plane_rows, rows, 2 * sizeof(double4), Grow::exact));   // accelerations, then jerks
     return NBODY_OK;
 }
 
@@ -448,14 +438,7 @@ int create(NbodyHandle* h) {
 void destroy(NbodyHandle* h) {
     State* s = h->f64;
     if (!s) return;
-    s->tree.release();
-    s->release();
-    void* dev[] = {s->d_energy, s->bf.d_planes,
-                   s->hm.jerk, s->hm.xp, s->hm.vp, s->hm.a1, s->hm.j1, s->hm.ratio, s->hmp.d_planes,
-                   s->blk.level, s->blk.tau, s->blk.list, s->blk.tile_count, s->blk.smin, s->blk.planes};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    if (s->h_sched) (void)hipHostFree(s->h_sched);
-    delete s;
+    delete s;   // (its device and pinned blocks are the handle's registry's)
     h->f64 = nullptr;
 }
 
@@ -770,12 +753,7 @@ int energy(NbodyHandle* h, double* kinetic, double* potential) {
     const size_t blocks = (n + 255) / 256;
     double ke = 0.0, pe = 0.0;
     if (blocks) {
-        if (blocks > s.energy_blocks) {
-            if (s.d_energy) (void)hipFree(s.d_energy);
-            s.d_energy = nullptr; s.energy_blocks = 0;
-            HIP_TRY(h, hipMalloc(&s.d_energy, blocks * 2 * sizeof(double)));
-            s.energy_blocks = blocks;
-        }
+        HIP_TRY(h, grow_dev(h, s.d_energy, s.energy_blocks, blocks, 2 * sizeof(double), Grow::exact));
         launch_energy(h->stream, s.sh, int(n), s.g_soft * s.g_soft, s.d_energy);
         HIP_TRY(h, hipGetLastError());
         std::vector<double> part(blocks * 2);

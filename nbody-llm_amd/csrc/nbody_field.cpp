@@ -12,17 +12,14 @@ int ensure(NbodyHandle* h, size_t plane_doubles, size_t out_doubles) {
     FieldBufs& f = h->field;
     if (!f.sort_bytes) f.sort_bytes = std::max<size_t>(field_sort_tmp_bytes(kFieldBatch), 256);
     // (each on its own: a call that ran out of memory half way leaves the next one to allocate the rest)
-    if (!f.d_xyz) HIP_TRY(h, hipMalloc(&f.d_xyz, kFieldBatch * 3 * sizeof(double)));
-    if (!f.d_keys) HIP_TRY(h, hipMalloc(&f.d_keys, 2 * kFieldBatch * sizeof(unsigned long long)));
-    if (!f.d_idx) HIP_TRY(h, hipMalloc(&f.d_idx, 2 * kFieldBatch * sizeof(int)));
-    if (!f.d_sort_tmp) HIP_TRY(h, hipMalloc(&f.d_sort_tmp, f.sort_bytes));
-    if (f.out_cap < out_doubles) {   // (exactly what is asked for: nbody_field_at alone never holds more than its four per probe)
-        if (f.d_out) (void)hipFree(f.d_out);
-        f.d_out = nullptr; f.out_cap = 0;
-        HIP_TRY(h, hipMalloc(&f.d_out, out_doubles * sizeof(double)));
-        f.out_cap = out_doubles;
-    }
-    return grow_dev(h, f.d_planes, f.planes_cap, plane_doubles, sizeof(double));
+    if (!f.d_xyz) HIP_TRY(h, h->mem.dev(f.d_xyz, kFieldBatch * 3 * sizeof(double)));
+    if (!f.d_keys) HIP_TRY(h, h->mem.dev(f.d_keys, 2 * kFieldBatch * sizeof(unsigned long long)));
+    if (!f.d_idx) HIP_TRY(h, h->mem.dev(f.d_idx, 2 * kFieldBatch * sizeof(int)));
+    if (!f.d_sort_tmp) HIP_TRY(h, h->mem.dev(f.d_sort_tmp, f.sort_bytes));
+    // (exactly what is asked for: nbody_field_at alone never holds more than its four per probe)
+    HIP_TRY(h, grow_dev(h, f.d_out, f.out_cap, out_doubles, sizeof(double), Grow::exact));
+    HIP_TRY(h, grow_dev(h, f.d_planes, f.planes_cap, plane_doubles, sizeof(double), Grow::quarter));
+    return NBODY_OK;
 }
 
 }  // namespace

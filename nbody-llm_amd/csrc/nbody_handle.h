@@ -5,6 +5,7 @@
 #include "kernels_f64.h"
 #include "kernels_quad.h"
 #include "octree_host.h"
+#include "handle_mem.h"
 
 #include "transport.h"
 
@@ -31,9 +32,10 @@ struct NbodyHandle;
 // records msg as the handle's error (h == nullptr: as nbody_create's) and returns code (nbody_api.cpp)
 int fail(NbodyHandle* h, int code, const std::string& msg);
 
+// (expr: a hipError_t, or the int a HandleMem operation hands through from the seam below)
 #define HIP_TRY(h, expr)                                                                              \
     do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
+        hipError_t e_ = hipError_t(expr);                                                                     \
         if (e_ != hipSuccess)                                                                         \
             return fail(h, NBODY_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
     } while (0)
@@ -47,12 +49,23 @@ int fail(NbodyHandle* h, int code, const std::string& msg);
 using clk = std::chrono::steady_clock;
 inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
 
+// ---- memory: every device and pinned block of a handle is taken from and given back to its HandleMem (NbodyHandle::mem), which
+// reaches the runtime through this seam and nowhere else; free_all releases whatever is live in one call
+inline int hip_dev_alloc(void** p, size_t n) { return int(hipMalloc(p, n)); }
+inline void hip_dev_free(void* p) { (void)hipFree(p); }
+inline int hip_pin_alloc(void** p, size_t n) { return int(hipHostMalloc(p, n, hipHostMallocDefault)); }
+inline void hip_pin_free(void* p) { (void)hipHostFree(p); }
+constexpr nbody::MemSeam kHipSeam{hip_dev_alloc, hip_dev_free, hip_pin_alloc, hip_pin_free};
+using nbody::Grow;
+nbody::HandleMem& mem_of(NbodyHandle* h);   // h->mem, for the structures declared before the handle
+
+// the host octree's node arrays (HostTreeT's allocator hooks carry no context): pinned through the same seam, owned and freed
+// by the HostTreeT itself
 inline void* pinned_alloc(size_t n) {
     void* p = nullptr;
-    if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return nullptr;
-    return p;
+    return hip_pin_alloc(&p, n) == 0 ? p : nullptr;
 }
-inline void pinned_free(void* p) { (void)hipHostFree(p); }
+inline void pinned_free(void* p) { hip_pin_free(p); }
 
 // ---- the Barnes-Hut walk's node-range split (kernels.h kMaxSplit: the layout of its int array), for f32 and f64 walks:
 // the buffers, the number of segments, the listing of the split points' ancestors, the walk's view of them
@@ -95,16 +108,10 @@ struct WalkSplitBuf {
     // the int array, and planes for K segments of `stride` bodies
     int ensure(NbodyHandle* hh, int K, size_t stride) {
         if (!d) {
-            HIP_TRY(hh, hipMalloc(&d, nbody::kSplitInts * sizeof(int)));
-            HIP_TRY(hh, hipHostMalloc(&h, nbody::kSplitInts * sizeof(int), hipHostMallocDefault));
+            HIP_TRY(hh, mem_of(hh).dev(d, nbody::kSplitInts * sizeof(int)));
+            HIP_TRY(hh, mem_of(hh).pin(h, nbody::kSplitInts * sizeof(int)));
         }
-        const size_t need = size_t(K) * stride;
-        if (K > 1 && need > planes_cap) {
-            if (planes) (void)hipFree(planes);
-            planes = nullptr; planes_cap = 0;
-            HIP_TRY(hh, hipMalloc(&planes, need * sizeof(V)));
-            planes_cap = need;
-        }
+        if (K > 1) HIP_TRY(hh, mem_of(hh).grow(planes, planes_cap, size_t(K) * stride, sizeof(V), Grow::exact));
         return NBODY_OK;
     }
     // K equal parts of a host-built tree's n_nodes; the ancestors of each split point found down from the root along the skip links
@@ -138,12 +145,6 @@ struct WalkSplitBuf {
         r.n_split = K; r.first = first(); r.n_anc = n_anc(); r.anc = anc(); r.max_anc = nbody::kMaxAnc; r.info = info; r.poison = poison;
         return r;
     }
-    void release() {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        if (planes) (void)hipFree(planes);
-        d = h = nullptr; planes = nullptr; planes_cap = 0;
-    }
 };
 
 // the walks' views of K segments
@@ -166,24 +167,18 @@ struct TreeBuildBufs {
 
     // for n_cap bodies; cat_bytes = 0: no concatenation buffer (one shard)
     int ensure(NbodyHandle* hh, size_t n_cap, size_t cat_bytes) {
-        if (cap < n_cap) {
-            if (ws) (void)hipFree(ws);
-            if (cat) (void)hipFree(cat);
-            ws = nullptr; cat = nullptr; cap = 0;
-            HIP_TRY(hh, hipMalloc(&ws, nbody::tree_build_workspace_bytes(n_cap)));
-            if (cat_bytes) HIP_TRY(hh, hipMalloc(&cat, cat_bytes));
+        if (cap < n_cap) {   // (two blocks under one cap: each replaces its old one)
+            cap = 0;
+            HIP_TRY(hh, mem_of(hh).dev(ws, nbody::tree_build_workspace_bytes(n_cap)));
+            mem_of(hh).free_dev(cat);
+            if (cat_bytes) HIP_TRY(hh, mem_of(hh).dev(cat, cat_bytes));
             cap = n_cap;
         }
         if (!d_info) {
-            HIP_TRY(hh, hipMalloc(&d_info, 4 * sizeof(int)));
-            HIP_TRY(hh, hipHostMalloc(&h_info, 4 * sizeof(int), hipHostMallocDefault));
+            HIP_TRY(hh, mem_of(hh).dev(d_info, 4 * sizeof(int)));
+            HIP_TRY(hh, mem_of(hh).pin(h_info, 4 * sizeof(int)));
         }
         return NBODY_OK;
-    }
-    void release() {
-        for (void* p : {ws, cat, static_cast<void*>(d_info)}) if (p) (void)hipFree(p);
-        if (h_info) (void)hipHostFree(h_info);
-        *this = TreeBuildBufs{};
     }
 };
 
@@ -209,13 +204,6 @@ struct PotBufs {
     int* d_rec_count = nullptr;   // [world]
     int* d_slot_of = nullptr;     // [slot_cap] index in the uploaded vector -> own slot, -1
     size_t slot_cap = 0;
-    void release() {
-        for (void* p : {static_cast<void*>(d_sum), static_cast<void*>(d_planes), static_cast<void*>(d_counts), static_cast<void*>(d_part), d_rec,
-                        static_cast<void*>(d_rec_count), static_cast<void*>(d_slot_of)})
-            if (p) (void)hipFree(p);
-        if (h_counts) (void)hipHostFree(h_counts);
-        *this = PotBufs{};
-    }
 };
 
 // the only way PotBufs::walking is set: for the lifetime of this object, so that no return path of a force pass run for
@@ -230,7 +218,7 @@ struct PotWalkScope {
 
 // nbody_field_at (nbody_field.cpp): probes go through the device in batches of at most kFieldBatch, so the scratch is bounded:
 // planes of [K <= 64][batch]{ax, ay, az, S} doubles are at most 64 * 65 536 * 32 B = 128 MiB (nbody_tidal_at: six doubles a
-// row, 192 MiB).  Grown on demand, released in free_all, not cloned.
+// row, 192 MiB).  Grown on demand, not cloned.
 struct FieldBufs {
     size_t n_points = 0;          // probes of the call under way: the walk's split count K is drawn from it, once per call
     // the tree the call's force pass built, as its last phase left it (valid until the next force pass)
@@ -250,12 +238,6 @@ struct FieldBufs {
     size_t out_cap = 0;                       // doubles: 4 per probe until the first nbody_tidal_at, 6 from then on
     double* d_planes = nullptr;               // [K][stride] double4 partial sums, grow-only
     size_t planes_cap = 0;                    // doubles
-    void release() {
-        for (void* p : {static_cast<void*>(d_xyz), static_cast<void*>(d_keys), static_cast<void*>(d_idx), d_sort_tmp, static_cast<void*>(d_out),
-                        static_cast<void*>(d_planes)})
-            if (p) (void)hipFree(p);
-        *this = FieldBufs{};
-    }
 };
 
 // ---- the body vector of a handle, once for F = f32 (a base of NbodyHandle) and F = f64 (a base of nbody64::State): the
@@ -267,6 +249,41 @@ inline void index_block(size_t n, size_t G, size_t g, size_t* lo, size_t* hi) {
     const size_t blk = (n + G - 1) / G;
     *lo = std::min(n, g * blk);
     *hi = std::min(n, *lo + blk);
+}
+
+// The arrays of a shard (the bodies' and the tracers') for its n_seg / seg_cap, zeroed (keep flags 1, epoch 1: the zeroed status
+// words belong to no launch); `inter` only when asked for; poison and ids stay as they are.  Enqueues the fills on s: the caller
+// synchronises.  shard_free gives the same arrays back and leaves an empty shard.
+template <class F>
+int shard_alloc(NbodyHandle* h, hipStream_t s, nbody::ShardT<F>& sh, bool with_inter) {
+    using V4 = typename nbody::ShardT<F>::V4;
+    const size_t cap = size_t(sh.seg_cap), G = size_t(sh.n_seg);
+    const size_t tiles = (cap + 1023) / 1024 + 1;
+    nbody::HandleMem& mem = mem_of(h);
+    const auto arr = [&](auto*& p, size_t bytes, int fill) {
+        HIP_TRY(h, mem.dev(p, bytes));
+        HIP_TRY(h, hipMemsetAsync(p, fill, bytes, s));
+        return int(NBODY_OK);
+    };
+    int rc = arr(sh.pos_all, G * cap * sizeof(V4), 0);
+    if (!rc) rc = arr(sh.vel, cap * sizeof(V4), 0);
+    if (!rc) rc = arr(sh.acc, cap * sizeof(V4), 0);
+    if (!rc) rc = arr(sh.seg_count, G * sizeof(int), 0);
+    if (!rc) rc = arr(sh.escaped, sizeof(int), 0);
+    if (!rc) rc = arr(sh.keep, cap, 1);
+    if (!rc) rc = arr(sh.tile_state, tiles * sizeof(unsigned long long), 0);
+    if (!rc) rc = arr(sh.epoch, sizeof(int), 0);
+    if (!rc && with_inter) rc = arr(sh.inter, sizeof(unsigned long long), 0);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemsetAsync(sh.epoch, 1, 1, s));   // epoch = 1
+    return NBODY_OK;
+}
+template <class F>
+void shard_free(NbodyHandle* h, nbody::ShardT<F>& sh) {
+    nbody::HandleMem& mem = mem_of(h);
+    mem.free_dev(sh.pos_all); mem.free_dev(sh.vel); mem.free_dev(sh.acc); mem.free_dev(sh.seg_count); mem.free_dev(sh.escaped);
+    mem.free_dev(sh.keep); mem.free_dev(sh.tile_state); mem.free_dev(sh.epoch); mem.free_dev(sh.inter);
+    sh = nbody::ShardT<F>{};
 }
 
 template <class F>
@@ -291,35 +308,13 @@ struct BodyStore {
     F* h_aos = nullptr;        // pinned host staging
     size_t aos_cap = 0;        // records
 
-    // the arrays of sh for its n_seg / seg_cap / my_seg, zeroed (keep flags 1, epoch 1: the zeroed status words belong to no
-    // launch); poison and ids stay null.  Enqueues the fills: the caller synchronises.
+    // the arrays of sh for its n_seg / seg_cap / my_seg (shard_alloc: the caller synchronises) and the pinned counts
     int alloc(NbodyHandle* h, hipStream_t s) {
-        const size_t cap = size_t(sh.seg_cap), G = size_t(sh.n_seg);
-        const size_t tiles = (cap + 1023) / 1024 + 1;
-        const struct { void** p; size_t bytes; int fill; } arr[] = {
-            {reinterpret_cast<void**>(&sh.pos_all), G * cap * sizeof(V4), 0}, {reinterpret_cast<void**>(&sh.vel), cap * sizeof(V4), 0},
-            {reinterpret_cast<void**>(&sh.acc), cap * sizeof(V4), 0},         {reinterpret_cast<void**>(&sh.seg_count), G * sizeof(int), 0},
-            {reinterpret_cast<void**>(&sh.escaped), sizeof(int), 0},          {reinterpret_cast<void**>(&sh.keep), cap, 1},
-            {reinterpret_cast<void**>(&sh.tile_state), tiles * sizeof(unsigned long long), 0},
-            {reinterpret_cast<void**>(&sh.epoch), sizeof(int), 0},            {reinterpret_cast<void**>(&sh.inter), sizeof(unsigned long long), 0}};
-        for (const auto& a : arr) {
-            HIP_TRY(h, hipMalloc(a.p, a.bytes));
-            HIP_TRY(h, hipMemsetAsync(*a.p, a.fill, a.bytes, s));
-        }
-        HIP_TRY(h, hipMemsetAsync(sh.epoch, 1, 1, s));   // epoch = 1
-        HIP_TRY(h, hipHostMalloc(&h_counts, G * sizeof(int), hipHostMallocDefault));
-        seg_count_host.assign(G, 0);
+        const int rc = shard_alloc(h, s, sh, true);
+        if (rc) return rc;
+        HIP_TRY(h, mem_of(h).pin(h_counts, size_t(sh.n_seg) * sizeof(int)));
+        seg_count_host.assign(size_t(sh.n_seg), 0);
         return NBODY_OK;
-    }
-    void release() {
-        for (void* p : {static_cast<void*>(sh.pos_all), static_cast<void*>(sh.vel), static_cast<void*>(sh.acc), static_cast<void*>(sh.seg_count),
-                        static_cast<void*>(sh.escaped), static_cast<void*>(sh.keep), static_cast<void*>(sh.tile_state), static_cast<void*>(sh.epoch),
-                        static_cast<void*>(sh.inter), static_cast<void*>(d_aos)})
-            if (p) (void)hipFree(p);
-        if (h_aos) (void)hipHostFree(h_aos);
-        if (h_counts) (void)hipHostFree(h_counts);
-        sh = nbody::ShardT<F>{};
-        h_counts = nullptr; d_aos = h_aos = nullptr; aos_cap = 0;
     }
     // what a clone takes over from `a` (same shape): the bodies of every segment and their counts, enqueued on s once the
     // caller has synchronised a's stream, and the host view.  Like the reference's BH clone (barnes_hut.rs:113-135), no tree.
@@ -341,11 +336,9 @@ struct BodyStore {
     // staging for `records` PointParticle records: device and pinned host, grow-only
     int ensure_aos(NbodyHandle* h, size_t records) {
         if (records <= aos_cap) return NBODY_OK;
-        if (d_aos) (void)hipFree(d_aos);
-        if (h_aos) (void)hipHostFree(h_aos);
-        d_aos = nullptr; h_aos = nullptr; aos_cap = 0;
-        HIP_TRY(h, hipMalloc(&d_aos, records * kRecBytes));
-        HIP_TRY(h, hipHostMalloc(&h_aos, records * kRecBytes, hipHostMallocDefault));
+        aos_cap = 0;   // (the device block and its pinned mirror under one cap: each replaces its old one)
+        HIP_TRY(h, mem_of(h).dev(d_aos, records * kRecBytes));
+        HIP_TRY(h, mem_of(h).pin(h_aos, records * kRecBytes));
         aos_cap = records;
         return NBODY_OK;
     }
@@ -516,17 +509,8 @@ struct TreeStore {
     int alloc_host(NbodyHandle* h, const nbody::ShardT<F>& sh) {
         host.alloc = pinned_alloc;
         host.release = pinned_free;
-        HIP_TRY(h, hipHostMalloc(&h_pos, size_t(sh.n_seg) * size_t(sh.seg_cap) * sizeof(V4), hipHostMallocDefault));
+        HIP_TRY(h, mem_of(h).pin(h_pos, size_t(sh.n_seg) * size_t(sh.seg_cap) * sizeof(V4)));
         return NBODY_OK;
-    }
-    void release() {
-        host.clear();
-        for (void* p : {static_cast<void*>(d_nodes), static_cast<void*>(d_order), static_cast<void*>(d_stack)}) if (p) (void)hipFree(p);
-        if (h_pos) (void)hipHostFree(h_pos);
-        d_nodes = nullptr; d_order = nullptr; d_stack = nullptr; h_pos = nullptr;
-        node_cap = order_cap = stack_lanes = 0; stack_levels = 0;
-        bufs.release();
-        split.release();
     }
     int ensure_dev(NbodyHandle* h, size_t nodes, size_t order);   // grow-only (grow_dev)
     // the stack for trees of `levels` levels: one entry per open cell on a lane's path -- as many levels as the tree is deep
@@ -574,6 +558,7 @@ struct ExternalField {
 };
 
 struct NbodyHandle : BodyStore<float> {
+    nbody::HandleMem mem{kHipSeam};   // every device and pinned block of this handle, its f64 / spatial state included
     NbodyConfig cfg{};
     nbody::Tuning tune;        // this handle's launch-shape and scheme knobs (nbody_set_tuning; NBODY_* environment at create)
     int device = 0;
@@ -676,16 +661,31 @@ struct NbodyHandle : BodyStore<float> {
 constexpr int kScratchStats = 4;          // one u64 ([4..5]): nbody_stats' interaction count
 constexpr int kScratchTracerCount = 6;    // one int: the live tracer count, up and down
 
-// grow-only device array: to n + n / 4 + 1024 elements of elem_bytes when it holds fewer than n
+inline nbody::HandleMem& mem_of(NbodyHandle* h) { return h->mem; }
+
+// grow-only device array: to grow_cap(rule, n) elements of elem_bytes when it holds fewer than n (HandleMem::grow: a failure
+// leaves p null and cap 0).  kGrowSync: the stream is synchronised before the old block goes (something enqueued may still
+// read it); kGrowZero: the new block is zeroed on the stream.  For HIP_TRY.
+enum { kGrowSync = 1, kGrowZero = 2 };
 template <class T>
-int grow_dev(NbodyHandle* h, T*& p, size_t& cap, size_t n, size_t elem_bytes) {
-    if (n <= cap) return NBODY_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    const size_t want = n + n / 4 + 1024;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&p), want * elem_bytes));
-    cap = want;
-    return NBODY_OK;
+hipError_t grow_dev(NbodyHandle* h, T*& p, size_t& cap, size_t n, size_t elem_bytes, Grow rule, int how = 0) {
+    if (n <= cap) return hipSuccess;
+    if ((how & kGrowSync) && p) {
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) return e;
+    }
+    const int e = h->mem.grow(p, cap, n, elem_bytes, rule);
+    if (e) return hipError_t(e);
+    return (how & kGrowZero) ? hipMemsetAsync(p, 0, cap * elem_bytes, h->stream) : hipSuccess;
+}
+// ... keeping the first `keep` elements (HandleMem::grow_keep); the stream is synchronised before the old block goes
+template <class T>
+hipError_t grow_dev_keep(NbodyHandle* h, T*& p, size_t& cap, size_t n, size_t elem_bytes, Grow rule, size_t keep) {
+    return hipError_t(h->mem.grow_keep(p, cap, n, elem_bytes, rule, keep, [h](void* fresh, const void* old, size_t bytes) {
+        hipError_t e = bytes ? hipMemcpyAsync(fresh, old, bytes, hipMemcpyDeviceToDevice, h->stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        return int(e);
+    }));
 }
 
 struct ForceTimer {  // HIP events around a force-kernel launch, on the launch stream
@@ -714,18 +714,18 @@ struct ForceTimer {  // HIP events around a force-kernel launch, on the launch s
 
 template <class F>
 int TreeStore<F>::ensure_dev(NbodyHandle* h, size_t nodes, size_t order) {
-    int rc = grow_dev(h, d_nodes, node_cap, nodes, sizeof(nbody::NodeRecT<F>));
-    return rc ? rc : grow_dev(h, d_order, order_cap, order, sizeof(int));
+    HIP_TRY(h, grow_dev(h, d_nodes, node_cap, nodes, sizeof(nbody::NodeRecT<F>), Grow::quarter));
+    HIP_TRY(h, grow_dev(h, d_order, order_cap, order, sizeof(int), Grow::quarter));
+    return NBODY_OK;
 }
 
 template <class F>
 int TreeStore<F>::ensure_stack(NbodyHandle* h, int seg_cap, int levels) {
     const size_t lanes = (size_t(seg_cap) + 255) / 256 * 256;
-    if (lanes > stack_lanes || levels > stack_levels) {
-        if (d_stack) (void)hipFree(d_stack);
-        d_stack = nullptr; stack_lanes = 0; stack_levels = 0;
+    if (lanes > stack_lanes || levels > stack_levels) {   // (a cap of two dimensions: the block replaces its old one)
+        stack_lanes = 0; stack_levels = 0;
         const int lv = std::max(levels + 8, 32);
-        HIP_TRY(h, hipMalloc(&d_stack, lanes * size_t(lv) * sizeof(StackEntry)));
+        HIP_TRY(h, h->mem.dev(d_stack, lanes * size_t(lv) * sizeof(StackEntry)));
         stack_lanes = lanes; stack_levels = lv;
     }
     return NBODY_OK;

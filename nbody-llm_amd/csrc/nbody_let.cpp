@@ -150,8 +150,9 @@ unsigned long long host_key(const float* p, const float c[3], float width) {   /
     return key;
 }
 
+// n (at least one) zeroed T into *p, in place of the block it held
 template <class T> int dev_alloc(NbodyHandle* h, T** p, size_t n) {
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(1, n) * sizeof(T)));
+    HIP_TRY(h, h->mem.dev(*p, std::max<size_t>(1, n) * sizeof(T)));
     HIP_TRY(h, hipMemsetAsync(*p, 0, std::max<size_t>(1, n) * sizeof(T), h->stream));
     return NBODY_OK;
 }
@@ -159,10 +160,7 @@ template <class T> int dev_alloc(NbodyHandle* h, T** p, size_t n) {
 int ensure_node_buffers(NbodyHandle* h, State& s) {
     const Shard& sh = h->sh;
     const int want_local = 4 * sh.seg_cap + 64;
-    if (s.local_cap < want_local) {
-        for (void* p : {(void*)s.d_parent, (void*)s.d_depth, (void*)s.d_node_flags, (void*)s.d_let_send, (void*)s.d_slice, (void*)s.d_node_mask, (void*)s.d_block_n})
-            if (p) (void)hipFree(p);
-        s.d_parent = nullptr; s.d_depth = nullptr; s.d_node_flags = nullptr; s.d_let_send = nullptr; s.d_slice = nullptr; s.d_node_mask = nullptr; s.d_block_n = nullptr;
+    if (s.local_cap < want_local) {   // (seven blocks under one cap: each replaces its old one; a failure leaves the cap, so the next pass starts over)
         int rc;
         if ((rc = dev_alloc(h, &s.d_slice, size_t(want_local) * 2))) return rc;
         if ((rc = dev_alloc(h, &s.d_node_mask, size_t(want_local)))) return rc;
@@ -173,38 +171,19 @@ int ensure_node_buffers(NbodyHandle* h, State& s) {
         // exports and imports: room for a quarter of the slice's node capacity each -- the body capacity's worth of nodes, several
         // times what the tests and the configs' sizes move (0.2-0.7 of the slice's LIVE nodes); both grow when a step needs more
         const size_t lists = size_t(want_local) / size_t(std::max(1, tuning().let_list_div)) + 1024;
-        s.let_send_cap = lists;
-        if ((rc = dev_alloc(h, &s.d_let_send, s.let_send_cap))) return rc;
-        if (s.let_recv_cap < lists) {
-            if (s.d_let_recv) (void)hipFree(s.d_let_recv);
-            s.d_let_recv = nullptr; s.let_recv_cap = 0;
-            if ((rc = dev_alloc(h, &s.d_let_recv, lists))) return rc;
-            s.let_recv_cap = lists;
-        }
+        s.let_send_cap = 0;
+        HIP_TRY(h, grow_dev(h, s.d_let_send, s.let_send_cap, lists, sizeof(LetRecord), Grow::exact, kGrowZero));
+        HIP_TRY(h, grow_dev(h, s.d_let_recv, s.let_recv_cap, lists, sizeof(LetRecord), Grow::exact, kGrowZero));
         s.local_cap = want_local;
     }
     // what the walk runs over: room for the slice and for as many imports as the staging buffer takes -- a rank's own
     // capacity decides it, not the world's size
-    if (s.held_cap < size_t(s.local_cap) + s.let_recv_cap) {
-        if (s.d_held) (void)hipFree(s.d_held);
-        s.d_held = nullptr; s.held_cap = 0;
+    HIP_TRY(h, grow_dev(h, s.d_held, s.held_cap, size_t(s.local_cap) + s.let_recv_cap, 2 * sizeof(float4), Grow::exact, kGrowZero));
+    if (s.ws_cap < size_t(sh.seg_cap)) {   // (four blocks under one cap)
         int rc;
-        if ((rc = dev_alloc(h, &s.d_held, (size_t(s.local_cap) + s.let_recv_cap) * 2))) return rc;
-        s.held_cap = size_t(s.local_cap) + s.let_recv_cap;
-    }
-    if (s.ws_cap < size_t(sh.seg_cap)) {
-        if (s.d_ws) (void)hipFree(s.d_ws);
-        if (s.d_order) (void)hipFree(s.d_order);
-        if (s.d_send_mig) (void)hipFree(s.d_send_mig);
-        if (s.d_dest_of) (void)hipFree(s.d_dest_of);
-        s.d_ws = nullptr; s.d_order = nullptr; s.d_send_mig = nullptr; s.d_dest_of = nullptr;
-        {
-            int rc;
-            if ((rc = dev_alloc(h, &s.d_send_mig, size_t(sh.seg_cap)))) return rc;
-            if ((rc = dev_alloc(h, &s.d_dest_of, size_t(sh.seg_cap)))) return rc;
-        }
-        HIP_TRY(h, hipMalloc(&s.d_ws, tree_build_workspace_bytes(size_t(sh.seg_cap))));
-        int rc;
+        if ((rc = dev_alloc(h, &s.d_send_mig, size_t(sh.seg_cap)))) return rc;
+        if ((rc = dev_alloc(h, &s.d_dest_of, size_t(sh.seg_cap)))) return rc;
+        HIP_TRY(h, h->mem.dev(s.d_ws, tree_build_workspace_bytes(size_t(sh.seg_cap))));
         if ((rc = dev_alloc(h, &s.d_order, size_t(sh.seg_cap)))) return rc;
         s.ws_cap = size_t(sh.seg_cap);
     }
@@ -213,15 +192,7 @@ int ensure_node_buffers(NbodyHandle* h, State& s) {
 
 // room for `need` immigrants; the first `keep` records of the old buffer survive a reallocation
 int ensure_mig_recv(NbodyHandle* h, State& s, size_t need, size_t keep) {
-    if (need <= s.mig_recv_cap) return NBODY_OK;
-    const size_t cap = need + need / 2 + 1024;
-    Migrant* fresh = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&fresh), cap * sizeof(Migrant)));
-    if (keep > 0 && s.d_recv_mig) HIP_TRY(h, hipMemcpyAsync(fresh, s.d_recv_mig, keep * sizeof(Migrant), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (s.d_recv_mig) (void)hipFree(s.d_recv_mig);
-    s.d_recv_mig = fresh;
-    s.mig_recv_cap = cap;
+    HIP_TRY(h, grow_dev_keep(h, s.d_recv_mig, s.mig_recv_cap, need, sizeof(Migrant), Grow::half, keep));
     return NBODY_OK;
 }
 
@@ -229,19 +200,8 @@ int ensure_mig_recv(NbodyHandle* h, State& s, size_t need, size_t keep) {
 // the array the walk runs over.  Called at points where the host is synchronised with the stream or about to be.
 int ensure_let_recv(NbodyHandle* h, State& s, size_t need, size_t keep) {
     if (need <= s.let_recv_cap) return NBODY_OK;
-    const size_t cap = need + need / 4 + 1024;
-    LetRecord* fresh = nullptr;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&fresh), cap * sizeof(LetRecord)));
-    if (keep > 0 && s.d_let_recv) HIP_TRY(h, hipMemcpyAsync(fresh, s.d_let_recv, keep * sizeof(LetRecord), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (s.d_let_recv) (void)hipFree(s.d_let_recv);
-    s.d_let_recv = fresh;
-    s.let_recv_cap = cap;
-    if (s.d_held) (void)hipFree(s.d_held);
-    s.d_held = nullptr; s.held_cap = 0;
-    int rc = dev_alloc(h, &s.d_held, (size_t(s.local_cap) + s.let_recv_cap) * 2);
-    if (rc) return rc;
-    s.held_cap = size_t(s.local_cap) + s.let_recv_cap;
+    HIP_TRY(h, grow_dev_keep(h, s.d_let_recv, s.let_recv_cap, need, sizeof(LetRecord), Grow::quarter, keep));
+    HIP_TRY(h, grow_dev(h, s.d_held, s.held_cap, size_t(s.local_cap) + s.let_recv_cap, 2 * sizeof(float4), Grow::exact, kGrowZero));
     return NBODY_OK;
 }
 
@@ -249,11 +209,7 @@ int ensure_let_recv(NbodyHandle* h, State& s, size_t need, size_t keep) {
 // partners are still on the device).  Called where the host has just read this pass's counts.
 int ensure_let_send(NbodyHandle* h, State& s, size_t need) {
     if (need <= s.let_send_cap) return NBODY_OK;
-    if (s.d_let_send) (void)hipFree(s.d_let_send);
-    s.d_let_send = nullptr; s.let_send_cap = 0;
-    const size_t cap = need + need / 4 + 1024;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_let_send), cap * sizeof(LetRecord)));
-    s.let_send_cap = cap;
+    HIP_TRY(h, grow_dev(h, s.d_let_send, s.let_send_cap, need, sizeof(LetRecord), Grow::quarter));
     s.send_regrown += 1;
     launch_pack(h->stream, s.local_cap, s.d_tree_info, s.d_slice, s.d_top_nodes, s.d_offsets, s.d_top_index, s.d_depth, s.d_node_mask, s.d_block_n,
                 s.d_list_first, s.G, s.me, s.d_let_send, s.let_send_cap);
@@ -350,13 +306,8 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = fals
     td.n_split = K;
     if (K > 1) {
         const size_t stride = (h->n_local + 1023) / 1024 * 1024;
-        if (size_t(K) * stride > s.walk_planes_cap) {
-            if (s.d_walk_planes) (void)hipFree(s.d_walk_planes);
-            s.d_walk_planes = nullptr; s.walk_planes_cap = 0;
-            const size_t want = size_t(K) * stride + size_t(K) * stride / 8;
-            HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_walk_planes), want * sizeof(float4)));
-            s.walk_planes_cap = want;
-        }
+        if (size_t(K) * stride > s.walk_planes_cap)   // (an eighth of headroom: the size asked for is the size taken)
+            HIP_TRY(h, grow_dev(h, s.d_walk_planes, s.walk_planes_cap, size_t(K) * stride + size_t(K) * stride / 8, sizeof(float4), Grow::exact));
         // the segments start at global node indices total k / K (launch_assemble found where those fall in the held array); their
         // ancestors come from the held array itself (the local build's arrays know the slice only)
         launch_walk_split_scan(h->stream, s.d_held, s.d_split, K, s.d_seg_first, s.d_seg_first + kMaxSplit + 1, s.d_seg_first + 2 * kMaxSplit + 1, 1);
@@ -431,7 +382,7 @@ int create(NbodyHandle* h) {
     if ((rc = dev_alloc(h, &s.d_let_count, size_t(s.G)))) return rc;
     if ((rc = dev_alloc(h, &s.d_let_matrix, size_t(s.G) * s.G))) return rc;
     if ((rc = dev_alloc(h, &h->sh.ids, size_t(h->sh.seg_cap)))) return rc;
-    HIP_TRY(h, hipHostMalloc(&s.h_pin, (size_t(report_ints(s.G)) + 64) * sizeof(int), hipHostMallocDefault));
+    HIP_TRY(h, h->mem.pin(s.h_pin, (size_t(report_ints(s.G)) + 64) * sizeof(int)));
     if ((rc = dev_alloc(h, &s.d_report, size_t(report_ints(s.G))))) return rc;
     if ((rc = dev_alloc(h, &s.d_pred, size_t(s.G) * s.G))) return rc;
     if ((rc = dev_alloc(h, &s.d_top_nodes, size_t(s.G) * kLevels * 2))) return rc;
@@ -440,8 +391,8 @@ int create(NbodyHandle* h) {
     if ((rc = dev_alloc(h, &s.d_in_n, size_t(s.G)))) return rc;
     if ((rc = dev_alloc(h, &s.d_zero, 1))) return rc;
     if ((rc = dev_alloc(h, reinterpret_cast<char**>(&s.d_layout), layout_bytes()))) return rc;
-    HIP_TRY(h, hipHostMalloc(&s.h_in_pin, size_t(s.G) * sizeof(int), hipHostMallocDefault));
-    HIP_TRY(h, hipHostMalloc(&s.h_pred_pin, size_t(s.G) * s.G * sizeof(int), hipHostMallocDefault));
+    HIP_TRY(h, h->mem.pin(s.h_in_pin, size_t(s.G) * sizeof(int)));
+    HIP_TRY(h, h->mem.pin(s.h_pred_pin, size_t(s.G) * s.G * sizeof(int)));
     s.h_pred.assign(size_t(s.G) * s.G, 0);
     h->sh.poison = s.d_flags;   // a raised flag stops every kernel that would change the state
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -451,17 +402,7 @@ int create(NbodyHandle* h) {
 void destroy(NbodyHandle* h) {
     State* s = h->let;
     if (!s) return;
-    void* dev[] = {s->d_bounds, s->d_bounds_scratch, s->d_weight_sum, s->d_send_mig, s->d_recv_mig, s->d_send_count, s->d_send_off, s->d_mig_cursor, s->d_mig_matrix, s->d_dest_of, s->d_new_count, s->d_flags, s->d_box_ord,
-                   s->d_ends, s->d_edge, s->d_rb, s->d_offsets, s->d_top_index, s->d_split, s->d_slice, s->d_held, s->d_top_nodes, s->d_node_mask,
-                   s->d_block_n, s->d_in_n, s->d_layout, s->d_zero, s->d_list_first, s->d_seg_first, s->d_walk_planes, s->d_order, s->d_tree_info,
-                   s->d_ws, s->d_parent, s->d_depth, s->d_upper_ok, s->d_node_flags, s->d_let_count, s->d_let_send,
-                   s->d_let_recv, s->d_let_matrix, h->sh.ids, s->d_report, s->d_pred, s->d_slot_out};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    h->sh.ids = nullptr;
-    h->sh.poison = nullptr;
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
-    if (s->h_pred_pin) (void)hipHostFree(s->h_pred_pin);
-    if (s->h_in_pin) (void)hipHostFree(s->h_in_pin);
+    h->sh.poison = nullptr;   // (it pointed into this state; the blocks themselves are the handle's registry's)
     if (s->ev_made) for (auto& set : s->ev) for (hipEvent_t e : set) (void)hipEventDestroy(e);
     delete s;
     h->let = nullptr;
@@ -873,13 +814,7 @@ static int draw_prediction(NbodyHandle* h, State& s, const int* mig_m) {
             if (b == s.me) in_need += size_t(p);
         }
     // (the host is synchronised here: growing a buffer costs nothing but the call)
-    if (out_need > s.slot_out_cap) {
-        if (s.d_slot_out) (void)hipFree(s.d_slot_out);
-        s.d_slot_out = nullptr; s.slot_out_cap = 0;
-        const size_t cap = out_need + out_need / 2 + 1024;
-        HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s.d_slot_out), cap * sizeof(Migrant)));
-        s.slot_out_cap = cap;
-    }
+    HIP_TRY(h, grow_dev(h, s.d_slot_out, s.slot_out_cap, out_need, sizeof(Migrant), Grow::half));
     int rc = ensure_mig_recv(h, s, in_need, 0);
     if (rc) return rc;
     std::memcpy(s.h_pred_pin, s.h_pred.data(), sizeof(int) * size_t(G) * G);

@@ -29,21 +29,18 @@ int partners(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, doub
         return NBODY_OK;
     }
     const PartnerPlan plan = make_partner_plan(int(n_upper));
-    void* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, scratch_bytes(n_upper, plan, false)));
-    const PairScratch w = scratch_layout(d, n_upper, plan, false);
+    ScratchDev scratch(h->mem);
+    HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, plan, false)));
+    const PairScratch w = scratch_layout(scratch.get(), n_upper, plan, false);
     launch_partners<F>(h->stream, sh, int(n_upper), plan, g, g_soft * g_soft, w);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = read_live(h, sh, &live);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, read_live(h, sh, &live));
     const size_t n = std::min(size_t(std::max(live, 0)), n_upper);
     const bool fits = n <= cap;
     // (partner and energy are pageable: the copies return once the data has reached them)
-    if (e == hipSuccess && fits && n && partner) e = hipMemcpyAsync(partner, w.partner, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && fits && n && energy) e = hipMemcpyAsync(energy, w.energy, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e_sync = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = e_sync;
-    (void)hipFree(d);
-    HIP_TRY(h, e);
+    if (fits && n && partner) HIP_TRY(h, hipMemcpyAsync(partner, w.partner, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (fits && n && energy) HIP_TRY(h, hipMemcpyAsync(energy, w.energy, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (n_out) *n_out = n;
     if (!fits) return fail(h, NBODY_ERR_CAPACITY, "nbody_partners: buffer too small");
     return NBODY_OK;
@@ -58,31 +55,27 @@ int bound_pairs(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, d
     if (binding_sum) *binding_sum = 0.0;
     if (!n_upper) return NBODY_OK;
     const PartnerPlan plan = make_partner_plan(int(n_upper));
-    void* d = nullptr;
-    HIP_TRY(h, hipMalloc(&d, scratch_bytes(n_upper, plan, true)));
-    const PairScratch w = scratch_layout(d, n_upper, plan, true);
+    ScratchDev scratch(h->mem);
+    HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, plan, true)));
+    const PairScratch w = scratch_layout(scratch.get(), n_upper, plan, true);
     launch_partners<F>(h->stream, sh, int(n_upper), plan, g, g_soft * g_soft, w);
     const bool scan_failed = launch_bound_pairs<F>(h->stream, sh, int(n_upper), g, w) != 0;
     int total = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && !scan_failed) e = hipMemcpyAsync(&total, w.total, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    hipError_t e_sync = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = e_sync;
+    HIP_TRY(h, hipGetLastError());
+    if (!scan_failed) HIP_TRY(h, hipMemcpyAsync(&total, w.total, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (scan_failed) return fail(h, NBODY_ERR_HIP, "nbody_bound_pairs: rocPRIM call failed");
     const size_t np = std::min(size_t(std::max(total, 0)), n_upper / 2);
     const bool fits = !pairs || np <= cap;
     // only the np records of the list cross to the host: into the caller's buffer, or into one of the call's own when the
     // caller wants their binding energies alone
     std::vector<NbodyBoundPair> own;
     const NbodyBoundPair* list = pairs;
-    if (e == hipSuccess && !scan_failed && fits && np && (pairs || binding_sum)) {
+    if (fits && np && (pairs || binding_sum)) {
         if (!pairs) { own.resize(np); list = own.data(); }
-        e = hipMemcpyAsync(const_cast<NbodyBoundPair*>(list), w.pairs, np * sizeof(NbodyBoundPair), hipMemcpyDeviceToHost, h->stream);
-        e_sync = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) e = e_sync;
+        HIP_TRY(h, hipMemcpyAsync(const_cast<NbodyBoundPair*>(list), w.pairs, np * sizeof(NbodyBoundPair), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    (void)hipFree(d);
-    HIP_TRY(h, e);
-    if (scan_failed) return fail(h, NBODY_ERR_HIP, "nbody_bound_pairs: rocPRIM call failed");
     if (n_pairs) *n_pairs = np;
     if (!fits) return fail(h, NBODY_ERR_CAPACITY, "nbody_bound_pairs: buffer too small");
     if (binding_sum) {

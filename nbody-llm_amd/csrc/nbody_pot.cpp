@@ -9,18 +9,20 @@ namespace nbody { namespace pot {
 
 int begin(NbodyHandle* h, size_t bodies) {
     PotBufs& p = h->pot;
-    int rc = grow_dev(h, p.d_sum, p.sum_cap, std::max<size_t>(bodies, 1), sizeof(double));
-    if (rc) return rc;
+    HIP_TRY(h, grow_dev(h, p.d_sum, p.sum_cap, std::max<size_t>(bodies, 1), sizeof(double), Grow::quarter));
     const size_t cb = 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long);
     if (!p.d_counts) {
-        HIP_TRY(h, hipMalloc(&p.d_counts, cb));
-        HIP_TRY(h, hipHostMalloc(&p.h_counts, cb, hipHostMallocDefault));
+        HIP_TRY(h, h->mem.dev(p.d_counts, cb));
+        HIP_TRY(h, h->mem.pin(p.h_counts, cb));
     }
     HIP_TRY(h, hipMemsetAsync(p.d_counts, 0, cb, h->stream));
     return NBODY_OK;
 }
 
-int ensure_planes(NbodyHandle* h, size_t doubles) { return grow_dev(h, h->pot.d_planes, h->pot.planes_cap, doubles, sizeof(double)); }
+int ensure_planes(NbodyHandle* h, size_t doubles) {
+    HIP_TRY(h, grow_dev(h, h->pot.d_planes, h->pot.planes_cap, doubles, sizeof(double), Grow::quarter));
+    return NBODY_OK;
+}
 
 int pairs(NbodyHandle* h, const PotBodies& b, size_t n, size_t n_remote, double eps2) {
     if (n == 0) return NBODY_OK;
@@ -54,8 +56,7 @@ int energy(NbodyHandle* h, const PotBodies& b, size_t n, double g, double* kinet
     const size_t blocks = (n + 255) / 256;
     double mine[2] = {0.0, 0.0};
     if (blocks) {
-        int rc = grow_dev(h, p.d_part, p.part_blocks, blocks, 2 * sizeof(double));
-        if (rc) return rc;
+        HIP_TRY(h, grow_dev(h, p.d_part, p.part_blocks, blocks, 2 * sizeof(double), Grow::quarter));
         launch_pot_energy(h->stream, b, p.d_sum, int(n), p.d_part);
         HIP_TRY(h, hipGetLastError());
         std::vector<double> part(blocks * 2);

@@ -18,14 +18,6 @@ const char* refusal(const NbodyHandle* h) {
     return nullptr;
 }
 
-void release(NbodyHandle* h) {
-    TracerState& t = h->tr;
-    void* dev[] = {t.sh.pos_all, t.sh.vel, t.sh.acc, t.sh.seg_count, t.sh.escaped, t.sh.keep, t.sh.tile_state, t.sh.epoch, t.d_planes, t.d_stats,
-                   t.d_keys, t.d_idx, t.d_sort_tmp, t.d_info};
-    for (void* p : dev) if (p) (void)hipFree(p);
-    t = TracerState{};
-}
-
 namespace {
 
 // the statistics words: {accepted or directed interactions, opening tests} pairs the walk's waves are spread over (the
@@ -36,33 +28,18 @@ constexpr size_t kStatWords = 2 * size_t(NBODY_WALK_COUNTER_SLOTS);
 int ensure(NbodyHandle* h, size_t cap) {
     TracerState& t = h->tr;
     if (!t.d_stats) {
-        HIP_TRY(h, hipMalloc(&t.d_stats, kStatWords * sizeof(unsigned long long)));
+        HIP_TRY(h, h->mem.dev(t.d_stats, kStatWords * sizeof(unsigned long long)));
         HIP_TRY(h, hipMemsetAsync(t.d_stats, 0, kStatWords * sizeof(unsigned long long), h->stream));
     }
     if (cap <= t.cap) return NBODY_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    void* old[] = {t.sh.pos_all, t.sh.vel, t.sh.acc, t.sh.seg_count, t.sh.escaped, t.sh.keep, t.sh.tile_state, t.sh.epoch};
-    for (void* p : old) if (p) (void)hipFree(p);
-    t.sh = Shard{};
+    shard_free(h, t.sh);
     t.cap = 0;
     Shard& sh = t.sh;
     sh.n_seg = 1; sh.my_seg = 0; sh.seg_cap = int(cap);
     sh.poison = h->sh.poison;   // (steps enqueued without read-back: the half drift and the retain stop with the bodies')
-    const size_t tiles = (cap + 1023) / 1024 + 1;
-    HIP_TRY(h, hipMalloc(&sh.pos_all, cap * sizeof(float4)));
-    HIP_TRY(h, hipMalloc(&sh.vel, cap * sizeof(float4)));
-    HIP_TRY(h, hipMalloc(&sh.acc, cap * sizeof(float4)));
-    HIP_TRY(h, hipMalloc(&sh.seg_count, sizeof(int)));
-    HIP_TRY(h, hipMalloc(&sh.escaped, sizeof(int)));
-    HIP_TRY(h, hipMalloc(&sh.keep, cap));
-    HIP_TRY(h, hipMalloc(&sh.tile_state, tiles * sizeof(unsigned long long)));
-    HIP_TRY(h, hipMalloc(&sh.epoch, sizeof(int)));
-    HIP_TRY(h, hipMemsetAsync(sh.seg_count, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(sh.escaped, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(sh.keep, 1, cap, h->stream));
-    HIP_TRY(h, hipMemsetAsync(sh.tile_state, 0, tiles * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipMemsetAsync(sh.epoch, 0, sizeof(int), h->stream));
-    HIP_TRY(h, hipMemsetAsync(sh.epoch, 1, 1, h->stream));   // epoch = 1: the zeroed status words belong to no launch
+    const int rc = shard_alloc(h, h->stream, sh, false);   // (no interaction counter: the statistics words above)
+    if (rc) return rc;
     t.cap = cap;
     return NBODY_OK;
 }
@@ -89,8 +66,9 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride, size_t capa
     if (cap == 0) {   // the empty set and no room asked for: the handle is as if it never had tracers
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         unsigned long long* keep_stats = t.d_stats;
-        t.d_stats = nullptr;
-        release(h);
+        shard_free(h, t.sh);
+        h->mem.free_dev(t.d_planes); h->mem.free_dev(t.d_keys); h->mem.free_dev(t.d_idx); h->mem.free_dev(t.d_sort_tmp); h->mem.free_dev(t.d_info);
+        t = TracerState{};
         t.d_stats = keep_stats;
         return NBODY_OK;
     }
@@ -200,12 +178,7 @@ int forces(NbodyHandle* h, const float* kick_dt) {
         const nbody::TracerPlan p = nbody::tracer_plan(t.n_plan, std::max(h->n_at_upload, h->n_local));
         if (p.K > 1) {
             const size_t need = size_t(p.K) * nbody::tracer_plan_pad(p);
-            if (need > t.planes_cap) {
-                if (t.d_planes) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(t.d_planes); }
-                t.d_planes = nullptr; t.planes_cap = 0;
-                HIP_TRY(h, hipMalloc(&t.d_planes, need * sizeof(float4)));
-                t.planes_cap = need;
-            }
+            HIP_TRY(h, grow_dev(h, t.d_planes, t.planes_cap, need, sizeof(float4), Grow::exact, kGrowSync));
         }
         nbody::launch_tr_bf_fast(h->stream, t.sh, m, h->sh, p, t.d_planes, h->g, eps2, kick_dt, t.d_stats);
     }
@@ -224,14 +197,12 @@ int tree_forces(NbodyHandle* h, const nbody::TreeDev& td) {
     const int m = int(t.n_host);
     if (t.sort_cap < t.cap) {   // the sort's buffers, sized for the capacity once
         HIP_TRY(h, hipStreamSynchronize(h->stream));
-        void* old[] = {t.d_keys, t.d_idx, t.d_sort_tmp};
-        for (void* p : old) if (p) (void)hipFree(p);
-        t.d_keys = nullptr; t.d_idx = nullptr; t.d_sort_tmp = nullptr; t.sort_cap = 0;
+        t.sort_cap = 0;   // (three blocks under one cap: each replaces its old one)
         t.sort_bytes = std::max<size_t>(nbody::tracer_sort_tmp_bytes(t.cap), 256);
-        HIP_TRY(h, hipMalloc(&t.d_keys, 2 * t.cap * sizeof(unsigned long long)));
-        HIP_TRY(h, hipMalloc(&t.d_idx, 2 * t.cap * sizeof(int)));
-        HIP_TRY(h, hipMalloc(&t.d_sort_tmp, t.sort_bytes));
-        if (!t.d_info) HIP_TRY(h, hipMalloc(&t.d_info, 3 * sizeof(int)));
+        HIP_TRY(h, h->mem.dev(t.d_keys, 2 * t.cap * sizeof(unsigned long long)));
+        HIP_TRY(h, h->mem.dev(t.d_idx, 2 * t.cap * sizeof(int)));
+        HIP_TRY(h, h->mem.dev(t.d_sort_tmp, t.sort_bytes));
+        if (!t.d_info) HIP_TRY(h, h->mem.dev(t.d_info, 3 * sizeof(int)));
         t.sort_cap = t.cap;
     }
     const int* idx = nullptr;
@@ -242,13 +213,7 @@ int tree_forces(NbodyHandle* h, const nbody::TreeDev& td) {
     const int groups = nbody::tracer_walk_groups(t.n_plan, td.n_split);
     const size_t stride = (t.cap + 63) / 64 * 64;
     if (groups > 1) {
-        const size_t need = size_t(groups) * stride;
-        if (need > t.planes_cap) {
-            if (t.d_planes) { HIP_TRY(h, hipStreamSynchronize(h->stream)); (void)hipFree(t.d_planes); }
-            t.d_planes = nullptr; t.planes_cap = 0;
-            HIP_TRY(h, hipMalloc(&t.d_planes, need * sizeof(float4)));
-            t.planes_cap = need;
-        }
+        HIP_TRY(h, grow_dev(h, t.d_planes, t.planes_cap, size_t(groups) * stride, sizeof(float4), Grow::exact, kGrowSync));
     }
     nbody::launch_tr_bh_walk(h->stream, t.sh, m, idx, td, groups, t.d_planes, stride, h->g, h->g_soft * h->g_soft, h->theta2,
                              h->cfg.leaf_mode == NBODY_LEAF_DIRECT, kick ? &h->kick_dt : nullptr, t.d_stats);

@@ -16,7 +16,6 @@ int count(NbodyHandle* h, size_t* n_out);
 int stats(NbodyHandle* h, uint64_t out[2]);
 int reset_stats(NbodyHandle* h);
 int clone_state(const NbodyHandle* src, NbodyHandle* dst);   // (src's stream is idle)
-void release(NbodyHandle* h);
 
 // the step's pieces, enqueued on the handle's stream; each returns at once when the handle has no tracers
 int drift_retain(NbodyHandle* h, float dt);                  // half drift + retain of the tracer vector

@@ -247,3 +247,68 @@ def test_clone_carries_the_host_view(gpu, f64):
             assert np.array_equal(mm_b[0], np.concatenate([c - np.float32(24.0), c + np.float32(24.0)]))
         finally:
             twin.close()
+
+
+REGROW_CONFIGS = ["bf-fast-f32", "bh-device-tracers-f32", "bf-hermite-block-f64", "bh-f64"]
+
+
+def _regrow_handle(nb, config, bodies):
+    f64 = config.endswith("f64")
+    bh = config.startswith("bh")
+    sim = nb.Simulation(bodies, *BOX, capacity=4096, f64=f64, method=nb.BARNES_HUT if bh else nb.BRUTE_FORCE, math_mode=nb.FAST,
+                        tree_build=nb.TREE_DEVICE if config == "bh-device-tracers-f32" else nb.TREE_AUTO)
+    sim.settings = nb.Settings(g=1.0, g_soft=0.05, dt=1.0 / 256, theta2=0.5)
+    if config == "bf-hermite-block-f64":
+        sim.integrator = nb.HERMITE4
+        sim.block_steps = (0.02, 3)
+    return sim
+
+
+def _regrow_half(nb, sim, config, bodies, tracers, probes):
+    """upload, three steps, every lazily allocating reader once: everything the caller can see afterwards, as bytes"""
+    f64 = config.endswith("f64")
+    bh = config.startswith("bh")
+    sim.upload(bodies)
+    if not f64:
+        sim.set_tracers(tracers)
+    sim.steps(3)
+    seen = {"points": sim.get_points()}
+    if not f64:
+        seen["tracers"] = sim.get_tracers()
+    for name, mode in [("pairs", nb.POTENTIAL_PAIRS)] + ([("tree", nb.POTENTIAL_TREE)] if bh else []):
+        phi, counts = sim.potentials(mode)
+        acc, fphi, fcounts = sim.field_at(probes, mode)
+        tidal, tcounts = sim.tidal_at(probes, mode, counts=True)
+        seen.update({f"phi-{name}": phi, f"field-acc-{name}": acc, f"field-phi-{name}": fphi, f"tidal-{name}": tidal,
+                     f"counts-{name}": np.array([counts, fcounts, tcounts], np.uint64)})
+    m = sim.moments()
+    seen["moments"] = np.concatenate([[m.mass], m.com, m.momentum, m.angular_momentum, m.mass_dipole])
+    radii, mass = sim.lagrangian_radii([0.1, 0.5, 0.9])
+    seen["radii"] = np.append(radii, mass)
+    seen["partner"], seen["partner-energy"] = sim.partners()
+    seen["energy"] = np.array(sim.energy(), np.float64)
+    return {k: (v.dtype.str, v.shape, np.ascontiguousarray(v).tobytes()) for k, v in seen.items()}
+
+
+@pytest.mark.parametrize("config", REGROW_CONFIGS)
+def test_every_regrow_path_gives_the_bits_of_a_fresh_handle(gpu, config):
+    """A handle whose buffers were first sized for 200 bodies and 64 tracers and then regrown for 4 000 and 2 000 -- the body
+    staging, the symmetric / plane / walk / tree buffers, the tracer arrays, planes and sort buffers, and the scratch of every
+    reader -- reports, byte for byte, what a fresh handle reports that only ever saw the larger set: every downloaded array and
+    every reader's output.  Then both are destroyed with every buffer live, created again, and the same holds once more."""
+    nb = gpu
+    f64 = config.endswith("f64")
+    small, large = nb.plummer(200, seed=3, f64=f64), nb.plummer(4000, seed=4, f64=f64)
+    rng = np.random.default_rng(17)
+    tracers = np.zeros(2000, nb.PARTICLE_DTYPE)
+    tracers["position"] = rng.uniform(-1.3, 1.3, (2000, 3))
+    tracers["velocity"] = rng.uniform(-0.3, 0.3, (2000, 3))
+    probes = rng.uniform(-1.5, 1.5, (100, 3))
+    for _ in range(2):
+        with _regrow_handle(nb, config, small) as a, _regrow_handle(nb, config, large) as b:
+            _regrow_half(nb, a, config, small, tracers[:64], probes)
+            got_a = _regrow_half(nb, a, config, large, tracers, probes)
+            got_b = _regrow_half(nb, b, config, large, tracers, probes)
+            assert got_a.keys() == got_b.keys()
+            for key in got_a:
+                assert got_a[key] == got_b[key], key
