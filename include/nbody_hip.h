@@ -621,7 +621,7 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */
 /* Per handle; the library exports no mutable globals.  Names (csrc/kernels.h struct Tuning): cross_sym, sym_packed,
- * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
+ * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, sym_opp_rot, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
  * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,

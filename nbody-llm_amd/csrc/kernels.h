@@ -26,6 +26,7 @@ struct Tuning {
     int sym_k = 0;              // k_bf_sym: waves (slices) per resident set; 0 = by the plan's rule
     int sym_min_bodies = 1024;  // single shard: below this the LDS-tiled one-sided kernel runs instead of k_bf_sym (measured: 18 against 26 us at 1 024 bodies, 28 against 43 at 4 096)
     int sym_reduce_split = 1;   // plane reduction: 1 = several waves per 64 bodies, 0 = one thread per body
+    int sym_opp_rot = 1;        // k_bf_sym, even A >= 4: 1 = sets a < A/2 meet their opposite set a + A/2 in the rotation, 0 = those pairs one-sidedly (sym_rest_wave)
     int cross_slots = 3072;     // k_bf_cross: waves the chunk visits are dealt to
     int cross_ipt = 0;          // k_bf_cross: resident bodies per lane: 0 = by rule, 4, 8
     int cross_wpb = 4;          // k_bf_cross: waves per workgroup: 4, 8, 12
@@ -82,12 +83,15 @@ struct SymPlan {
     int wpb = 16;         // waves per workgroup (CU-sized: 12 by default)
     int res_combine = 0;  // 1: K % wpb == 0, resident-side sums of a workgroup are combined in LDS
     int k_res = 0;        // resident-side planes (K, or K / wpb when combined)
-    int sym_sets = 0;     // sets met symmetrically = ceil(A/2) - 1
+    int sym_sets = 0;     // sets every set meets symmetrically = ceil(A/2) - 1
+    int opp = 0;          // 1: A even, a rotation pass, Tuning::sym_opp_rot: sets a < A/2 also meet set a + A/2 (IPT more chunk visits)
+    int n_trav = 0;       // travelling-side planes = sym_sets + opp (the last one, set distance A/2, holds rows of sets >= A/2 only)
     int n_planes = 0;     // partial-sum planes (own-shard kernels + k_os one-sided planes of a sharded run)
     int k_os = 0;         // slices per resident set of the one-sided remote kernel (0 = single shard)
     size_t n_pad = 0;     // padded body count (A * 64 * ipt)
     size_t plane_stride = 0;  // float4 entries per plane (>= n_pad; sharded runs: also >= the shard capacity)
-    std::vector<int> bounds;  // K+1 cut points of a set's chunk sequence
+    std::vector<int> bounds;  // K+1 cut points of a set's chunk sequence (ipt * sym_sets visits)
+    std::vector<int> bounds_long;  // the same for the sets that also meet their opposite set (ipt more visits; == bounds without opp)
 };
 SymPlan make_sym_plan(int n_upper);
 int sym_bodies_per_lane(size_t n);   // 8, or 4 for small shards (Tuning::sym_ipt)

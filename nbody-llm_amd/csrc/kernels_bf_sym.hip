@@ -16,13 +16,22 @@
 // (v_rsq_f32); the scalar form (NBODY_SYM_PACKED=0) takes 388 at 2.37 GHz.  fp32-issue bound either way.
 //
 // Decomposition (balanced by construction): with A resident sets, set a meets the chunks of sets
-// a+1 .. a+ceil(A/2)-1 (cyclic) symmetrically (k_bf_sym); the pairs inside a set and, for even
-// A, with the opposite set are evaluated one-sidedly by k_bf_sym_rest (~3 % of the evaluations).
+// a+1 .. a+ceil(A/2)-1 (cyclic) symmetrically (k_bf_sym).  For even A >= 4 (Tuning::sym_opp_rot,
+// the default) the sets of the lower half, a < A/2, also meet their opposite set a + A/2, as the
+// last IPT chunk visits of their sequence: every pair of two different sets is then evaluated once
+// on the packed core, and the lower half's sets have IPT visits more (their own table of cuts).
+// What is left -- the pairs inside a set and, where the rotation did not take it (sym_opp_rot = 0,
+// or A = 2: no rotation pass), the opposite set -- is evaluated one-sidedly by k_bf_sym_rest
+// (own sets alone: 1/A of the interactions).
 // The chunk sequence of a set is cut into K equal parts, one per wave.
-// Partial sums go to "planes" of float4[n_pad]: plane d-1 receives the travelling-side sums of
-// set distance d, plane sym_sets+p the resident-side sums of slice p of each set, the last
-// plane k_bf_sym_rest's; every plane entry is written exactly once per launch, so the reduction
-// (k_bf_sym_reduce) adds the planes in a fixed order: deterministic, no atomics.
+// Partial sums go to "planes" of float4[n_pad], added in this order: planes 0 .. sym_sets-1
+// receive the travelling-side sums of set distance d = plane + 1; with the opposite set in the
+// rotation plane sym_sets follows with those of set distance A/2, of which only the rows of the sets
+// >= A/2 are ever written (the reduction skips the plane for the bodies below n_pad/2: it is never
+// cleared); then (n_trav = sym_sets or sym_sets + 1 planes on) plane n_trav+p holds the resident-side
+// sums of slice p of each set (for the lower half's sets they include the opposite set), and the
+// last plane k_bf_sym_rest's.  Every plane entry that is read was written exactly once in this
+// launch, so the reduction (k_bf_sym_reduce) adds the planes in a fixed order: deterministic, no atomics.
 //
 // fast math only (v_rsq_f32 + FMA; summation order differs from the reference): tolerance 1e-5.
 #include "kernels.h"
@@ -42,11 +51,11 @@ __device__ unsigned long long nbody_sym_stamps[3 * 8192];  // diagnostic builds 
 }  // namespace
 
 template <int IPT>
-__device__ __forceinline__ void sym_rest_wave(const float4* __restrict__ pos, int n, int A, int group, int slice,
+__device__ __forceinline__ void sym_rest_wave(const float4* __restrict__ pos, int n, int A, int opp, int group, int slice,
                                               int n_slices, float& ax, float& ay, float& az, float eps2);
 
 template <int IPT, int NW>
-__device__ __forceinline__ void sym_rest_block(const float4* __restrict__ pos, int n, int A, int group,
+__device__ __forceinline__ void sym_rest_block(const float4* __restrict__ pos, int n, int A, int opp, int group,
                                                float4* __restrict__ plane, float eps2, float (*red)[3][64]);
 
 // WPB waves per workgroup, sized so that exactly one (WPB = 16) or two (WPB = 12) workgroups fit a
@@ -55,7 +64,7 @@ __device__ __forceinline__ void sym_rest_block(const float4* __restrict__ pos, i
 // long as the fullest SIMD (measured with in-kernel stamps: wave lifetimes 560-960 us, +55 %).
 template <int IPT, int WPB, int DBG = 0, bool PK = false>
 __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ pos, const int* __restrict__ count,
-                                                     int A, int K, const int* __restrict__ bounds, int sym_sets,
+                                                     int A, int K, const int* __restrict__ bounds, int n_trav, int opp,
                                                      float4* __restrict__ planes, size_t plane_stride, float eps2,
                                                      int res_combine) {
     const int lane = threadIdx.x & 63;
@@ -67,10 +76,11 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ 
     const int n_main_blocks = (A * K + WPB - 1) / WPB;
     if (int(blockIdx.x) >= n_main_blocks) {
         // tail filler: the workgroups after the rotation workgroups are dispatched as CUs fall free
-        // and do the own-set / opposite-set pairs (64 bodies per workgroup) inside the same launch
+        // and do the own-set pairs (and the opposite-set pairs the rotation did not take; 64 bodies per
+        // workgroup) inside the same launch
         __shared__ float red[WPB - 1][3][64];
-        sym_rest_block<IPT, WPB>(pos, *count, A, blockIdx.x - n_main_blocks,
-                                 planes + size_t(sym_sets + (res_combine ? K / WPB : K)) * plane_stride, eps2, red);
+        sym_rest_block<IPT, WPB>(pos, *count, A, opp, blockIdx.x - n_main_blocks,
+                                 planes + size_t(n_trav + (res_combine ? K / WPB : K)) * plane_stride, eps2, red);
         return;
     }
     const int gw = blockIdx.x * WPB + (wslot & 3) * (WPB / 4) + (wslot >> 2);  // global slice index
@@ -79,7 +89,10 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ 
     const int part = gw - a * K;                 // this wave's slice of the set's chunk sequence
     const int n = *count;
     const int Cn = A * IPT;                      // chunks in the padded body array
-    const int k0 = bounds[part], k1 = bounds[part + 1];
+    // opp: the sets of the lower half also meet their opposite set a + A/2, as the last IPT chunk visits
+    // of their sequence, and are cut by the second table (128 entries further on)
+    const int* __restrict__ cuts = bounds + ((opp && a < (A >> 1)) ? 128 : 0);
+    const int k0 = cuts[part], k1 = cuts[part + 1];
     const int src_lane = ((lane + 63) & 63) * 4;  // ds_bpermute address: take from the lane below
     const int src_lane2 = ((lane + 62) & 63) * 4; // two lanes below
     // eps2 lives in a VGPR: with an SGPR operand the compiler cannot tell inside the loop whether the
@@ -96,7 +109,7 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ 
         axi[q] = ayi[q] = azi[q] = 0.f;
     }
 
-    // chunk k of this set's sequence: the chunks of the next sym_sets sets, in cyclic order
+    // chunk k of this set's sequence: the chunks of the next sym_sets (+ 1 with opp, lower half) sets, in cyclic order
     auto chunk_of = [&](int k) {
         int c = (a + 1) * IPT + k;
         if (c >= Cn) c -= Cn;
@@ -159,7 +172,7 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ 
             }
         }
         if (PK) { axj = axj2.x + axj2.y; ayj = ayj2.x + ayj2.y; azj = azj2.x + azj2.y; }
-        const int d = k / IPT + 1;  // set distance 1..sym_sets
+        const int d = k / IPT + 1;  // set distance 1..n_trav (A/2, the last plane, from the lower half's sets only)
         planes[size_t(d - 1) * plane_stride + size_t(chunk_of(k)) * 64 + lane] = make_float4(axj, ayj, azj, 0.f);
     }
     if (PK) { unpack_pairs<IPT>(axi2, axi); unpack_pairs<IPT>(ayi2, ayi); unpack_pairs<IPT>(azi2, azi); }
@@ -194,7 +207,7 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ 
         }
         __syncthreads();
         if (rel == 0) {
-            float4* __restrict__ out = planes + size_t(sym_sets + part / WPB) * plane_stride;
+            float4* __restrict__ out = planes + size_t(n_trav + part / WPB) * plane_stride;
 #pragma unroll
             for (int q = 0; q < IPT; ++q) {
                 float sx = axi[q], sy = ayi[q], sz = azi[q];
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_sym(const float4* __restrict__ 
         return;
     }
     // resident side: one plane per slice index
-    float4* __restrict__ out = planes + size_t(sym_sets + part) * plane_stride;
+    float4* __restrict__ out = planes + size_t(n_trav + part) * plane_stride;
 #pragma unroll
     for (int q = 0; q < IPT; ++q) out[size_t(a * IPT + q) * 64 + lane] = make_float4(axi[q], ayi[q], azi[q], 0.f);
 }
@@ -300,13 +313,13 @@ __global__ __launch_bounds__(WPB * 64) void k_bf_os(const float4* __restrict__ p
 }
 
 // The pairs the rotation scheme leaves out: every body against its own set (self excluded) and,
-// when A is even, against the opposite set -- one-sided, since the opposite set does the same for
-// ours.  64 bodies per workgroup, the 1 or 2 windows of 64*IPT partners split over 8 waves whose
-// partner index is wave-uniform (scalar loads); ~3 % of the pair evaluations.
+// when A is even and the rotation did not take it (opp = 0), against the opposite set -- one-sided,
+// since the opposite set does the same for ours.  64 bodies per workgroup, the 1 or 2 windows of
+// 64*IPT partners split over 8 waves whose partner index is wave-uniform (scalar loads).
 // One wave's share of those pairs: 64 bodies (one per lane) against slice `slice` of `n_slices` of
 // each of the 1 or 2 windows; the caller adds the slices up.
 template <int IPT>
-__device__ __forceinline__ void sym_rest_wave(const float4* __restrict__ pos, int n, int A, int group, int slice,
+__device__ __forceinline__ void sym_rest_wave(const float4* __restrict__ pos, int n, int A, int opp, int group, int slice,
                                               int n_slices, float& ax, float& ay, float& az, float eps2) {
     constexpr int SET = 64 * IPT;
     const int lane = threadIdx.x & 63;
@@ -314,7 +327,7 @@ __device__ __forceinline__ void sym_rest_wave(const float4* __restrict__ pos, in
     const int a = (group * 64) / SET;
     const float4 pi = (i < n) ? pos[i] : make_float4(PAD_POS, PAD_POS, PAD_POS, 0.f);
     ax = ay = az = 0.f;
-    const int n_win = (A % 2 == 0 && A > 1) ? 2 : 1;
+    const int n_win = (A % 2 == 0 && A > 1 && !opp) ? 2 : 1;   // (opp: the rotation took the opposite set)
     for (int w = 0; w < n_win; ++w) {
         int set = (w == 0) ? a : a + A / 2;
         if (set >= A) set -= A;
@@ -337,12 +350,12 @@ __device__ __forceinline__ void sym_rest_wave(const float4* __restrict__ pos, in
 
 // a workgroup of NW waves: 64 bodies, the windows cut into NW slices, slices added in wave order
 template <int IPT, int NW>
-__device__ __forceinline__ void sym_rest_block(const float4* __restrict__ pos, int n, int A, int group,
+__device__ __forceinline__ void sym_rest_block(const float4* __restrict__ pos, int n, int A, int opp, int group,
                                                float4* __restrict__ plane, float eps2, float (*red)[3][64]) {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float ax, ay, az;
-    sym_rest_wave<IPT>(pos, n, A, group, wv, NW, ax, ay, az, eps2);
+    sym_rest_wave<IPT>(pos, n, A, opp, group, wv, NW, ax, ay, az, eps2);
     if (wv > 0) { red[wv - 1][0][lane] = ax; red[wv - 1][1][lane] = ay; red[wv - 1][2][lane] = az; }
     __syncthreads();
     if (wv == 0) {
@@ -357,7 +370,7 @@ template <int IPT>
 __global__ __launch_bounds__(512) void k_bf_sym_rest(const float4* __restrict__ pos, const int* __restrict__ count,
                                                      int A, float4* __restrict__ plane, float eps2) {
     __shared__ float red[7][3][64];
-    sym_rest_block<IPT, 8>(pos, *count, A, blockIdx.x, plane, eps2, red);
+    sym_rest_block<IPT, 8>(pos, *count, A, 0, blockIdx.x, plane, eps2, red);
 }
 
 // the fixed-order sum of the planes; optionally followed at once by integrate_after_force
@@ -367,7 +380,8 @@ __global__ __launch_bounds__(256) void k_bf_sym_reduce(const float4* __restrict_
                                                        size_t plane_stride, const int* __restrict__ count, float g,
                                                        float4* __restrict__ acc, float4* __restrict__ pos,
                                                        float4* __restrict__ vel, float dt, const int* __restrict__ seg_count,
-                                                       int n_seg, unsigned long long* __restrict__ inter) {
+                                                       int n_seg, unsigned long long* __restrict__ inter, int opp_plane,
+                                                       int opp_first) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (inter && i == 0) {   // NbodyStats::interactions of this force pass, from the live counts
         long long tot = 0;
@@ -379,6 +393,7 @@ __global__ __launch_bounds__(256) void k_bf_sym_reduce(const float4* __restrict_
     // flops are free, and with ~1000 planes at N = 2^20 a plain f32 sum would dominate the error
     float sx = 0.f, sy = 0.f, sz = 0.f, cx = 0.f, cy = 0.f, cz = 0.f;
     for (int p = 0; p < n_planes; ++p) {
+        if (p == opp_plane && i < opp_first) continue;   // (never written: only sets >= A/2 travel at distance A/2)
         const float4 v = planes[size_t(p) * plane_stride + i];
         const float yx = v.x - cx, yy = v.y - cy, yz = v.z - cz;
         const float tx = sx + yx, ty = sy + yy, tz = sz + yz;
@@ -398,7 +413,7 @@ __global__ __launch_bounds__(64 * Q) void k_bf_sym_reduce_split(const float4* __
                                                                 const int* __restrict__ count, float g, float4* __restrict__ acc,
                                                                 float4* __restrict__ pos, float4* __restrict__ vel, float dt,
                                                                 const int* __restrict__ seg_count, int n_seg,
-                                                                unsigned long long* __restrict__ inter) {
+                                                                unsigned long long* __restrict__ inter, int opp_plane, int opp_first) {
     __shared__ float part[Q][3][64];
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int i = blockIdx.x * 64 + lane;
@@ -412,6 +427,7 @@ __global__ __launch_bounds__(64 * Q) void k_bf_sym_reduce_split(const float4* __
     if (i < n) {
         const int p0 = int((long long)n_planes * q / Q), p1 = int((long long)n_planes * (q + 1) / Q);
         for (int p = p0; p < p1; ++p) {
+            if (p == opp_plane && i < opp_first) continue;   // (never written: only sets >= A/2 travel at distance A/2)
             const float4 v = planes[size_t(p) * plane_stride + i];
             const float yx = v.x - cx, yy = v.y - cy, yz = v.z - cz;
             const float tx = sx + yx, ty = sy + yy, tz = sz + yz;
@@ -493,11 +509,17 @@ SymPlan make_sym_plan(int n_upper) {
     p.K = K;
     p.res_combine = (K % p.wpb == 0) ? 1 : 0;    // a workgroup = wpb slices of one set: one resident plane per workgroup
     p.k_res = p.res_combine ? K / p.wpb : K;
-    p.n_planes = p.sym_sets + p.k_res + 1;       // travelling-side, resident-side, own/opposite set
+    // even A with a rotation pass: the sets of the lower half meet their opposite set in the rotation too
+    p.opp = (tuning().sym_opp_rot && p.A % 2 == 0 && p.sym_sets >= 1) ? 1 : 0;
+    p.n_trav = p.sym_sets + p.opp;
+    p.n_planes = p.n_trav + p.k_res + 1;         // travelling-side, resident-side, own (/ opposite) set
     p.n_pad = size_t(p.A) * 64 * IPT;
     p.plane_stride = p.n_pad;
     p.bounds.resize(K + 1);
     for (int part = 0; part <= K; ++part) p.bounds[part] = int((long long)L * part / K);
+    const int L_long = L + (p.opp ? IPT : 0);    // the lower half's sets: IPT chunk visits more, over the same K slices
+    p.bounds_long.resize(K + 1);
+    for (int part = 0; part <= K; ++part) p.bounds_long[part] = int((long long)L_long * part / K);
     return p;
 }
 
@@ -513,6 +535,8 @@ uint64_t sym_main_pairs(const SymPlan& p, size_t n) {
     uint64_t pairs = 0;
     for (int a = 0; a < p.A; ++a)
         for (int d = 1; d <= p.sym_sets; ++d) pairs += uint64_t(size_of(a)) * uint64_t(size_of((a + d) % p.A));
+    if (p.opp)
+        for (int a = 0; a < p.A / 2; ++a) pairs += uint64_t(size_of(a)) * uint64_t(size_of(a + p.A / 2));
     return pairs;
 }
 
@@ -523,14 +547,14 @@ void launch_bf_sym_main(hipStream_t s, const Shard& sh, const SymPlan& p, const 
     const int main_blocks = (p.A * p.K + p.wpb - 1) / p.wpb;
     const int rest_blocks = int(p.n_pad / 64);  // one workgroup per 64 bodies
     const dim3 grid(main_blocks + rest_blocks), block(p.wpb * 64);
-#define SYM_LAUNCH(WPB, DBG) hipLaunchKernelGGL((k_bf_sym<8, WPB, DBG, PKV>), grid, block, 0, s, sh.own_pos(), sh.own_count(), p.A, p.K, d_bounds, p.sym_sets, planes, p.plane_stride, g_soft2, p.res_combine)
+#define SYM_LAUNCH(WPB, DBG) hipLaunchKernelGGL((k_bf_sym<8, WPB, DBG, PKV>), grid, block, 0, s, sh.own_pos(), sh.own_count(), p.A, p.K, d_bounds, p.n_trav, p.opp, planes, p.plane_stride, g_soft2, p.res_combine)
 #ifdef NBODY_TUNING   // in-kernel stamps (tools/sym_cycles.py: 4) and timing experiments that do not compute the forces (5-7)
     const int dbg = tuning().sym_debug;
 #else
     constexpr int dbg = 0;
 #endif
     if (p.ipt == 4) {   // half-size resident sets (4 bodies per lane): twice the waves for small shards
-        hipLaunchKernelGGL((k_bf_sym<4, 4, 0, true>), grid, block, 0, s, sh.own_pos(), sh.own_count(), p.A, p.K, d_bounds, p.sym_sets, planes, p.plane_stride, g_soft2, p.res_combine);
+        hipLaunchKernelGGL((k_bf_sym<4, 4, 0, true>), grid, block, 0, s, sh.own_pos(), sh.own_count(), p.A, p.K, d_bounds, p.n_trav, p.opp, planes, p.plane_stride, g_soft2, p.res_combine);
         return;
     }
     if (tuning().sym_packed) {
@@ -576,17 +600,17 @@ void launch_bf_sym_tail(hipStream_t s, const Shard& sh, const SymPlan& p, float4
                         float g_soft2, const float* kick_dt) {
     if (n_upper <= 0) return;
     if (p.sym_sets == 0) {  // no rotation pass: the resident-side planes are never written
-        float4* resident0 = planes + size_t(p.sym_sets) * p.plane_stride;
+        float4* resident0 = planes + size_t(p.n_trav) * p.plane_stride;
         (void)hipMemsetAsync(resident0, 0, size_t(p.k_res) * p.plane_stride * sizeof(float4), s);
         if (p.ipt == 4)
             hipLaunchKernelGGL(k_bf_sym_rest<4>, dim3(int(p.n_pad / 64)), dim3(512), 0, s, sh.own_pos(),
-                               sh.own_count(), p.A, planes + size_t(p.sym_sets + p.k_res) * p.plane_stride, g_soft2);
+                               sh.own_count(), p.A, planes + size_t(p.n_trav + p.k_res) * p.plane_stride, g_soft2);
         else
         hipLaunchKernelGGL(k_bf_sym_rest<8>, dim3(int(p.n_pad / 64)), dim3(512), 0, s, sh.own_pos(),
-                           sh.own_count(), p.A, planes + size_t(p.sym_sets + p.k_res) * p.plane_stride, g_soft2);
+                           sh.own_count(), p.A, planes + size_t(p.n_trav + p.k_res) * p.plane_stride, g_soft2);
     }
     const float dt = kick_dt ? *kick_dt : 0.f;
-#define REDUCE_ARGS planes, p.n_planes, p.plane_stride, sh.own_count(), g, sh.acc, sh.own_pos(), sh.vel, dt, sh.seg_count, sh.n_seg, sh.inter
+#define REDUCE_ARGS planes, p.n_planes, p.plane_stride, sh.own_count(), g, sh.acc, sh.own_pos(), sh.vel, dt, sh.seg_count, sh.n_seg, sh.inter, (p.opp ? p.n_trav - 1 : -1), int(p.n_pad / 2)
     if (tuning().sym_reduce_split && p.n_planes >= 16) {   // several waves per 64 bodies: 16 for small shards, 4 otherwise
         const dim3 grid((n_upper + 63) / 64);
         if (n_upper <= 16384) {

@@ -175,7 +175,7 @@ constexpr size_t kShardedSymMinBodies = 2048; // sharded: own-own symmetric + re
 int ensure_sym_plan(NbodyHandle* h) {
     const size_t set = size_t(64) * size_t(nbody::sym_bodies_per_lane(std::max<size_t>(1, h->n_local)));   // bodies of a resident set (make_sym_plan)
     const int A = int((std::max<size_t>(1, h->n_local) + set - 1) / set);  // (an empty shard still plans one set)
-    const int knobs = nbody::tuning().sym_wpb * 100 + nbody::tuning().sym_rounds + nbody::tuning().sym_k * 10000 + nbody::tuning().sym_ipt * 1000000;
+    const int knobs = nbody::tuning().sym_wpb * 100 + nbody::tuning().sym_rounds + nbody::tuning().sym_k * 10000 + nbody::tuning().sym_ipt * 1000000 + (nbody::tuning().sym_opp_rot ? 500000000 : 0);
     if (h->sym_plan.A == A && h->sym_plan.ipt * 64 == int(set) && h->d_sym_bounds && h->sym_waves == knobs) return NBODY_OK;
     h->sym_waves = knobs;
     h->sym_plan = nbody::make_sym_plan(int(std::max<size_t>(1, h->n_local)));
@@ -198,8 +198,10 @@ int ensure_sym_plan(NbodyHandle* h) {
             p.n_planes += p.k_os;
         }
     }
-    if (!h->d_sym_bounds) HIP_TRY(h, h->mem.dev(h->d_sym_bounds, 128 * sizeof(int)));
+    // two cut tables of up to 127 entries: [0, 128) every set's, [128, 256) that of the sets that also meet their opposite set
+    if (!h->d_sym_bounds) HIP_TRY(h, h->mem.dev(h->d_sym_bounds, 2 * 128 * sizeof(int)));
     HIP_TRY(h, hipMemcpyAsync(h->d_sym_bounds, p.bounds.data(), p.bounds.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_sym_bounds + 128, p.bounds_long.data(), p.bounds_long.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));  // p.bounds is pageable
     HIP_TRY(h, grow_dev(h, h->d_planes, h->planes_cap, size_t(p.n_planes) * p.plane_stride, sizeof(float4), Grow::exact));
     if (h->cross_on) {
@@ -1928,6 +1930,7 @@ const Knob kKnobs[] = {
     {"bf_fast_variant", &nbody::Tuning::bf_fast_variant, false}, {"sym_wpb", &nbody::Tuning::sym_wpb, false}, {"sym_ipt", &nbody::Tuning::sym_ipt, false}, {"let_list_div", &nbody::Tuning::let_list_div, false}, {"bh_walk_duo", &nbody::Tuning::bh_walk_duo, false}, {"bh_walk_xcd", &nbody::Tuning::bh_walk_xcd, false},
     {"sym_rounds", &nbody::Tuning::sym_rounds, false}, {"sym_k", &nbody::Tuning::sym_k, false},
     {"sym_min_bodies", &nbody::Tuning::sym_min_bodies, false}, {"sym_reduce_split", &nbody::Tuning::sym_reduce_split, false},
+    {"sym_opp_rot", &nbody::Tuning::sym_opp_rot, false},
     {"cross_slots", &nbody::Tuning::cross_slots, false}, {"cross_ipt", &nbody::Tuning::cross_ipt, false},
     {"cross_wpb", &nbody::Tuning::cross_wpb, false}, {"bh_walk_split", &nbody::Tuning::bh_walk_split, false},
     {"bh_walk_order", &nbody::Tuning::bh_walk_order, false}, {"bh_reduce_split", &nbody::Tuning::bh_reduce_split, false},
