@@ -617,6 +617,63 @@ typedef struct NbodyBoundPair {
 } NbodyBoundPair;
 int nbody_partners(NbodyHandle* h, int32_t* partner, double* energy, size_t cap, size_t* n_out);
 int nbody_bound_pairs(NbodyHandle* h, NbodyBoundPair* pairs, size_t cap, size_t* n_pairs, double* binding_sum);
+/* ---- sticky mergers: every body's nearest body, the mutual contacts within a radius, and their merger (no reference
+ * counterpart) -----
+ * The "sticky sphere" rule of direct N-body codes: two bodies closer than a merge distance become one body at their centre of
+ * mass, with their total mass and momentum.  nbody_nearest and nbody_contacts are READ-ONLY calls under the exact contract of
+ * the binary census above (the bodies are what nbody_download would report, no trace in state, NbodyStats, validity flags or
+ * the bits of any later step, no refresh of the host's view of the count, launches sized from its upper bound: right after a
+ * retain with no nbody_count in between, scratch inside the call, no floating-point atomics).  nbody_merge_contacts WRITES.
+ *   THE METRIC is f64 on either dtype (an NBODY_F32 handle's positions are widened exactly), unsoftened, nothing contracted:
+ *     d = x_j - x_i,  r2 = (dx dx + dy dy) + dz dz
+ * r2_ij == r2_ji BIT FOR BIT.  tests/merge_ref.py restates all three calls in numpy; the device's results are its bits.
+ *   nbody_nearest: nearest[i] = the j != i of least r2, among equal r2 the lowest j; dist2[i] = that r2.  A NaN r2 never wins.
+ * A body with no partner -- n == 1, or every r2 NaN -- gets -1 and +inf.  r2 == +inf cannot win either: a candidate replaces
+ * the best so far on r2 < best only, which is false against the initial +inf, so a body whose every r2 is +inf or NaN also
+ * gets -1 and +inf.  Either array may be NULL; with both NULL the call only counts.  *n_out (may be NULL) = the bodies;
+ * cap < n returns NBODY_ERR_CAPACITY with *n_out set and the arrays untouched.
+ *   nbody_contacts: the MUTUAL pairs -- nearest[i] == j, nearest[j] == i -- with r2 < R2, R2 = radius * radius rounded once,
+ * the comparison STRICT; once each with i < j, in ascending i.  w = v_j - v_i, w2 = (wx wx + wy wy) + wz wz, in f64 from the
+ * widened values; `into` is filled as if the merge happened.  list == NULL only counts; cap < n_contacts returns
+ * NBODY_ERR_CAPACITY with *n_contacts set and the list carrying nothing.  n_contacts may be NULL.
+ *   nbody_merge_contacts: the same list, then applied.  list != NULL with cap < n_contacts returns NBODY_ERR_CAPACITY with
+ * *n_contacts set and the state UNTOUCHED (the check comes before any write); list == NULL merges and reports the count.  For
+ * each pair, in f64, every operation rounded on its own:
+ *     M = m_i + m_j
+ *     q_c = ((m_i q_i,c) + (m_j q_j,c)) / M      q in {position, velocity, acceleration}, per component c
+ * (M == 0: q_c = (q_i,c + q_j,c) * 0.5); on a Hermite handle the held jerk is carried the same way; on an NBODY_F32 handle
+ * each result and M are then rounded to f32 once.  The mass-weighted acceleration is the physically right one: the mutual
+ * forces cancel.  The merged record replaces body i, body j is removed, and everybody else keeps their relative order --
+ * Vec::retain's rule, carried out by the handle's own retain kernels.
+ *   ONE CALL MERGES DISJOINT PAIRS ONLY; a clump of k bodies needs repeated calls, `while (n_contacts > 0)`.  That loop ends,
+ * and ends with no pair left inside the radius: IF ANY PAIR HAS r2 < R2, AT LEAST ONE CONTACT IS FOUND.  At the global
+ * minimum of r2 take the lowest index a that takes part in a minimal pair, and b = nearest[a]: r2_ab is minimal, and among
+ * the bodies tied at that distance from b, a is the lowest index (every one of them takes part in a minimal pair), so
+ * nearest[b] == a.  Each merging call removes at least one body.
+ *   EFFECTS of a call that merged at least one pair are those of nbody_remove_point: the host's body count is exact
+ * (n - n_contacts); a Barnes-Hut handle's tree and its exports are those of the state before the call until the next force
+ * pass; a Hermite handle's held (a0, j0) are STALE and its block-step levels INVALID.  NbodyStats, tracers, the external
+ * field, settings, bounds, elapsed, the integrator and the multipole order are untouched.  A call that found NO contact
+ * leaves no trace at all, like the read-only calls.  Like nbody_remove_point the call first confirms enqueued steps.
+ *   COST: O(N^2) f64 pair terms of 3 subtractions, 3 products, 2 sums and a compare -- nbody_partners' frame (one body per
+ * lane, partners through LDS, groups x K slices sized by bf64_waves, the K records merged in slice order: the bits do not
+ * depend on K) without velocities, sqrt or divide.  NOT MEASURED on an MI355X beyond the single run of tools/merge_bench.py that
+ * DESIGN 3.17 records (about 0.03 s at 262 144 bodies); nothing asserts or promises a time.
+ *   Accepted on every world_size == 1, NBODY_SHARD_INDEX handle: both dtypes, both methods, either math mode, any tree build,
+ * leapfrog or Hermite, block steps on or off, with or without tracers, an external field or quadrupoles.  Refused with
+ * NBODY_ERR_INVALID (nbody_last_error names the call): radius not finite or <= 0 (the two calls that take one); handles of a
+ * multi-rank world and NBODY_SHARD_SPATIAL handles (all three). */
+typedef struct NbodyContact {
+    int32_t i, j;        /* indices BEFORE the call, nbody_download's order, i < j: i survives, j is absorbed */
+    int32_t into;        /* index of the merged body AFTER the merge: i minus the absorbed bodies below i */
+    int32_t reserved;    /* 0 */
+    double separation;   /* sqrt(r2), IEEE, unsoftened */
+    double mass;         /* M = m_i + m_j */
+    double dkinetic;     /* -0.5 (((m_i m_j) / M) w2) <= 0: kinetic energy the merger removes; 0 when M == 0 */
+} NbodyContact;
+int nbody_nearest(NbodyHandle* h, int32_t* nearest, double* dist2, size_t cap, size_t* n_out);
+int nbody_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts);
+int nbody_merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

@@ -90,6 +90,7 @@ DECLARED_SYMBOLS = [
     "nbody_external_at", "nbody_host_external_eval",
     "nbody_moments", "nbody_lagrangian_radii",
     "nbody_partners", "nbody_bound_pairs",
+    "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
 ]
 
 
@@ -122,6 +123,18 @@ class BoundPair(C.Structure):
 BOUND_PAIR_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("energy", "<f8"), ("binding", "<f8"), ("semi_major", "<f8"),
                              ("eccentricity", "<f8"), ("period", "<f8"), ("separation", "<f8")])
 assert BOUND_PAIR_DTYPE.itemsize == C.sizeof(BoundPair) == 56
+
+
+class NbodyContact(C.Structure):
+    """One mutual contact of nbody_contacts / nbody_merge_contacts (include/nbody_hip.h "sticky mergers")."""
+    _fields_ = [("i", C.c_int32), ("j", C.c_int32), ("into", C.c_int32), ("reserved", C.c_int32), ("separation", C.c_double),
+                ("mass", C.c_double), ("dkinetic", C.c_double)]
+
+
+#: the same record as a numpy dtype: what Simulation.contacts() and Simulation.merge_contacts() return
+CONTACT_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("into", "<i4"), ("reserved", "<i4"), ("separation", "<f8"), ("mass", "<f8"),
+                          ("dkinetic", "<f8")])
+assert CONTACT_DTYPE.itemsize == C.sizeof(NbodyContact) == 40
 
 
 class NbodyStats(C.Structure):
@@ -236,6 +249,9 @@ _sig("nbody_moments", _i, _H, C.POINTER(C.c_double))
 _sig("nbody_lagrangian_radii", _i, _H, C.c_void_p, C.c_void_p, _sz, C.c_void_p, C.POINTER(C.c_double))
 _sig("nbody_partners", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_bound_pairs", _i, _H, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_double))
+_sig("nbody_nearest", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_merge_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -598,6 +614,37 @@ class Simulation:
         total = C.c_double(0)
         self._check(lib.nbody_bound_pairs(self._h, pairs.ctypes.data, len(pairs), C.byref(n), C.byref(total)))
         return pairs[: n.value].copy(), float(total.value)
+
+    # -- sticky mergers (nbody_nearest, nbody_contacts, nbody_merge_contacts): f64 distances, O(N^2) on the device
+    def nearest(self) -> tuple[np.ndarray, np.ndarray]:
+        """(nearest [n] int32, dist2 [n] f64): for every body, in get_points() order, the other body at the least unsoftened
+        squared distance (the lowest index among equal distances) and that r2; -1 and +inf for a body without one
+        (nbody_nearest)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_nearest(self._h, None, None, 0, C.byref(n)))
+        nearest = np.full(n.value, -1, np.int32)
+        dist2 = np.full(n.value, np.inf, np.float64)
+        self._check(lib.nbody_nearest(self._h, nearest.ctypes.data if n.value else None, dist2.ctypes.data if n.value else None,
+                                      n.value, C.byref(n)))
+        return nearest[: n.value], dist2[: n.value]
+
+    def _contact_list(self, call, radius: float) -> np.ndarray:
+        n = C.c_size_t(0)
+        self._check(lib.nbody_nearest(self._h, None, None, 0, C.byref(n)))   # (counts only: n bodies hold at most n // 2 contacts)
+        out = np.zeros(n.value // 2 + 1, CONTACT_DTYPE)
+        self._check(call(self._h, float(radius), out.ctypes.data, len(out), C.byref(n)))
+        return out[: n.value].copy()
+
+    def contacts(self, radius: float) -> np.ndarray:
+        """The mutual nearest pairs closer than `radius` (strictly) as a CONTACT_DTYPE array in ascending i (i < j); read-only
+        (nbody_contacts)."""
+        return self._contact_list(lib.nbody_contacts, radius)
+
+    def merge_contacts(self, radius: float) -> np.ndarray:
+        """Merges every contacts(radius) pair into one body at its centre of mass (total mass, momentum, mass-weighted
+        acceleration) in row i, removes row j, keeps everybody else's order, and returns the list.  One call merges disjoint
+        pairs: repeat while the list is not empty (nbody_merge_contacts)."""
+        return self._contact_list(lib.nbody_merge_contacts, radius)
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

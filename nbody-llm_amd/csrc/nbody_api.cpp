@@ -1390,6 +1390,43 @@ int nbody_bound_pairs(NbodyHandle* h, NbodyBoundPair* pairs, size_t cap, size_t*
     return nbody::pairs::bound_pairs(h, h->sh, h->n_local, g, g_soft, pairs, cap, n_pairs, binding_sum);
 }
 
+// ---- sticky mergers (nbody_pairs.cpp): nearest and contacts under the census's contract; merge_contacts begins like
+// nbody_remove_point (diag_enter settles enqueued steps and a poisoned device build) and, when it merged, ends like it
+namespace {
+int contact_radius(NbodyHandle* h, const char* call, double radius) {
+    if (std::isfinite(radius) && radius > 0.0) return NBODY_OK;
+    return fail(h, NBODY_ERR_INVALID, std::string(call) + ": radius must be finite and > 0");
+}
+}  // namespace
+
+int nbody_nearest(NbodyHandle* h, int32_t* nearest, double* dist2, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_nearest");
+    if (rc) return rc;
+    if (h->f64) return nbody::pairs::nearest(h, nbody64::shard(h), nbody64::n_upper(h), nearest, dist2, cap, n_out);
+    return nbody::pairs::nearest(h, h->sh, h->n_local, nearest, dist2, cap, n_out);
+}
+
+int nbody_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_contacts");
+    if (!rc) rc = contact_radius(h, "nbody_contacts", radius);
+    if (rc) return rc;
+    if (h->f64) return nbody::pairs::contacts(h, nbody64::shard(h), nbody64::n_upper(h), radius, list, cap, n_contacts);
+    return nbody::pairs::contacts(h, h->sh, h->n_local, radius, list, cap, n_contacts);
+}
+
+int nbody_merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_merge_contacts");
+    if (!rc) rc = contact_radius(h, "nbody_merge_contacts", radius);
+    if (rc) return rc;
+    if (h->f64) return nbody64::merge_contacts(h, radius, list, cap, n_contacts);
+    // (an f32 handle keeps nothing beside the count that a removal makes stale: every force pass builds its tree anew)
+    return nbody::pairs::merge_contacts<float>(h, *h, radius, list, cap, n_contacts, nullptr,
+                                               [](NbodyHandle* hh, int n_upper) { nbody::launch_compact(hh->stream, hh->sh, n_upper); });
+}
+
 // ---- tracers (nbody_tracer.cpp)
 namespace {
 // binds the device, refuses the handles that take no tracers, naming the entry point, and confirms the steps enqueued without

@@ -10,6 +10,7 @@
 #include "kernels_f64.h"
 #include "kernels_hermite.h"
 #include "nbody_external.h"
+#include "nbody_pairs.h"
 #include "nbody_pot.h"
 
 #include <algorithm>
@@ -501,6 +502,12 @@ int count_global(NbodyHandle* h, size_t* n_out) {   // as of the last exchange
     return NBODY_OK;
 }
 
+namespace {
+// what nbody_remove_point and a merging nbody_merge_contacts leave stale beside the count: the held (a0, j0), and with them the
+// block-step levels
+void removed(State& s) { s.hm_valid = false; }
+}  // namespace
+
 int add_point(NbodyHandle* h, const void* particle) {
     State& s = *h->f64;
     if (s.sh.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "add_point on a sharded f64 world is not supported (f32 handles: collective push / swap_remove)");
@@ -513,7 +520,23 @@ int remove_point(NbodyHandle* h, size_t index) {
     State& s = *h->f64;
     if (s.sh.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "remove_point on a sharded f64 world is not supported (f32 handles: collective push / swap_remove)");
     int rc = s.swap_remove_one(h, h->stream, index);
-    if (!rc) s.hm_valid = false;
+    if (!rc) removed(s);
+    return rc;
+}
+
+// nbody_merge_contacts: the retain of the handle's integrator (a Hermite handle's carries the jerk and, with block steps on,
+// the levels), then what a removal leaves behind
+int merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts) {
+    State& s = *h->f64;
+    const bool hermite = s.integrator == NBODY_INTEGRATOR_HERMITE4;
+    size_t n = 0;
+    int rc = nbody::pairs::merge_contacts<double>(h, s, radius, list, cap, &n, hermite ? s.hm.jerk : nullptr, [](NbodyHandle* hh, int n_upper) {
+        State& st = *hh->f64;
+        if (st.integrator == NBODY_INTEGRATOR_HERMITE4) launch_hm_compact(hh->stream, st.sh, st.hm, n_upper, st.blk_L > 0 ? st.blk.level : nullptr);
+        else nbody::launch_compact(hh->stream, st.sh, n_upper);
+    });
+    if (n_contacts) *n_contacts = n;
+    if (!rc && n) removed(s);
     return rc;
 }
 

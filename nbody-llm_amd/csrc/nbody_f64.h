@@ -13,6 +13,7 @@ int count(NbodyHandle* h, size_t* n_out);
 int count_global(NbodyHandle* h, size_t* n_out);
 int add_point(NbodyHandle* h, const void* particle);
 int remove_point(NbodyHandle* h, size_t index);
+int merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts);   // nbody_pairs.h, + a removal's bookkeeping
 int set_settings(NbodyHandle* h, double g, double g_soft, double dt, double theta2);
 int get_settings(const NbodyHandle* h, double* g, double* g_soft, double* dt, double* theta2);
 int set_bounds(NbodyHandle* h, const double center[3], double width);

@@ -452,9 +452,15 @@ struct BodyStore {
             HIP_TRY(h, hipMemcpyAsync(sh.vel + index, sh.vel + last, sizeof(V4), hipMemcpyDeviceToDevice, s));
             HIP_TRY(h, hipMemcpyAsync(sh.acc + index, sh.acc + last, sizeof(V4), hipMemcpyDeviceToDevice, s));
         }
-        n_local = last;
-        seg_count_host[size_t(sh.my_seg)] = int(last);
+        set_own_count(last);
         return push_own_count(h, s);
+    }
+    // the host's view after bodies were removed outside a step (swap_remove_one; nbody_merge_contacts, whose retain has
+    // written the device's count already): exact
+    void set_own_count(size_t n) {
+        n_local = n;
+        seg_count_host[size_t(sh.my_seg)] = int(n);
+        count_dirty = false;
     }
 };
 

@@ -1,8 +1,11 @@
 // nbody_pairs.cpp -- nbody_partners and nbody_bound_pairs (include/nbody_hip.h, "binary census"): the scratch of a call, the
 // launches of kernels_pairs.hip, and the copies of what the caller asked for -- n partners, or the n_pairs records of the list.
+// nbody_nearest, nbody_contacts and nbody_merge_contacts ("sticky mergers") are the same three steps under the distance metric,
+// and the last one then writes the merged records and runs the handle's retain.
 #include "nbody_pairs.h"
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 namespace nbody { namespace pairs {
@@ -87,5 +90,110 @@ int bound_pairs(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, d
 }
 template int bound_pairs<float>(NbodyHandle*, const ShardT<float>&, size_t, double, double, NbodyBoundPair*, size_t, size_t*, double*);
 template int bound_pairs<double>(NbodyHandle*, const ShardT<double>&, size_t, double, double, NbodyBoundPair*, size_t, size_t*, double*);
+
+// ---- sticky mergers
+template <class F>
+int nearest(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, int32_t* nearest_out, double* dist2, size_t cap, size_t* n_out) {
+    if (n_out) *n_out = 0;
+    if (!n_upper) return NBODY_OK;
+    int live = 0;
+    if (!nearest_out && !dist2) {   // counts only
+        HIP_TRY(h, read_live(h, sh, &live));
+        if (n_out) *n_out = std::min(size_t(std::max(live, 0)), n_upper);
+        return NBODY_OK;
+    }
+    const PartnerPlan plan = make_partner_plan(int(n_upper));
+    ScratchDev scratch(h->mem);
+    HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, plan, false)));
+    const PairScratch w = scratch_layout(scratch.get(), n_upper, plan, false);
+    launch_nearest<F>(h->stream, sh, int(n_upper), plan, w);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, read_live(h, sh, &live));
+    const size_t n = std::min(size_t(std::max(live, 0)), n_upper);
+    const bool fits = n <= cap;
+    if (fits && n && nearest_out) HIP_TRY(h, hipMemcpyAsync(nearest_out, w.partner, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    if (fits && n && dist2) HIP_TRY(h, hipMemcpyAsync(dist2, w.energy, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (n_out) *n_out = n;
+    if (!fits) return fail(h, NBODY_ERR_CAPACITY, "nbody_nearest: buffer too small");
+    return NBODY_OK;
+}
+template int nearest<float>(NbodyHandle*, const ShardT<float>&, size_t, int32_t*, double*, size_t, size_t*);
+template int nearest<double>(NbodyHandle*, const ShardT<double>&, size_t, int32_t*, double*, size_t, size_t*);
+
+namespace {
+// the scratch of a call, the nearest pass and the contact list on the device: *np contacts among *live bodies (n_upper > 0)
+template <class F>
+int find_contacts(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double radius, const char* call, ScratchDev& scratch, PairScratch* w,
+                  size_t* np, size_t* live_out) {
+    const PartnerPlan plan = make_partner_plan(int(n_upper));
+    HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, plan, true)));
+    *w = scratch_layout(scratch.get(), n_upper, plan, true);
+    launch_nearest<F>(h->stream, sh, int(n_upper), plan, *w);
+    const bool scan_failed = launch_contacts<F>(h->stream, sh, int(n_upper), radius * radius, *w) != 0;
+    int total = 0, live = 0;
+    HIP_TRY(h, hipGetLastError());
+    if (!scan_failed) HIP_TRY(h, hipMemcpyAsync(&total, w->total, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, read_live(h, sh, &live));
+    if (scan_failed) return fail(h, NBODY_ERR_HIP, std::string(call) + ": rocPRIM call failed");
+    *live_out = std::min(size_t(std::max(live, 0)), n_upper);
+    *np = std::min(size_t(std::max(total, 0)), *live_out / 2);
+    return NBODY_OK;
+}
+
+// the np records of the list to the caller, `into` filled: i minus the absorbed bodies below i
+int copy_contacts(NbodyHandle* h, const PairScratch& w, NbodyContact* list, size_t np) {
+    if (!list || !np) return NBODY_OK;
+    HIP_TRY(h, hipMemcpyAsync(list, w.contacts, np * sizeof(NbodyContact), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<int32_t> gone(np);
+    for (size_t k = 0; k < np; ++k) gone[k] = list[k].j;
+    std::sort(gone.begin(), gone.end());
+    for (size_t k = 0; k < np; ++k) list[k].into = list[k].i - int32_t(std::lower_bound(gone.begin(), gone.end(), list[k].i) - gone.begin());
+    return NBODY_OK;
+}
+}  // namespace
+
+template <class F>
+int contacts(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double radius, NbodyContact* list, size_t cap, size_t* n_contacts) {
+    if (n_contacts) *n_contacts = 0;
+    if (!n_upper) return NBODY_OK;
+    ScratchDev scratch(h->mem);
+    PairScratch w;
+    size_t np = 0, live = 0;
+    int rc = find_contacts<F>(h, sh, n_upper, radius, "nbody_contacts", scratch, &w, &np, &live);
+    if (rc) return rc;
+    if (n_contacts) *n_contacts = np;
+    if (list && np > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_contacts: buffer too small");
+    return copy_contacts(h, w, list, np);
+}
+template int contacts<float>(NbodyHandle*, const ShardT<float>&, size_t, double, NbodyContact*, size_t, size_t*);
+template int contacts<double>(NbodyHandle*, const ShardT<double>&, size_t, double, NbodyContact*, size_t, size_t*);
+
+template <class F>
+int merge_contacts(NbodyHandle* h, BodyStore<F>& b, double radius, NbodyContact* list, size_t cap, size_t* n_contacts,
+                   typename ShardT<F>::V4* jerk, void (*retain)(NbodyHandle*, int)) {
+    if (n_contacts) *n_contacts = 0;
+    const size_t n_upper = b.n_local;
+    if (!n_upper) return NBODY_OK;
+    ScratchDev scratch(h->mem);
+    PairScratch w;
+    size_t np = 0, live = 0;
+    int rc = find_contacts<F>(h, b.sh, n_upper, radius, "nbody_merge_contacts", scratch, &w, &np, &live);
+    if (rc) return rc;
+    if (n_contacts) *n_contacts = np;
+    if (list && np > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_merge_contacts: buffer too small");
+    if (!np) return NBODY_OK;   // (nothing of the handle's has been written, its view of the count included)
+    launch_merge<F>(h->stream, b.sh, jerk, int(n_upper), w);
+    retain(h, int(n_upper));
+    HIP_TRY(h, hipGetLastError());
+    rc = copy_contacts(h, w, list, np);
+    if (rc) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    b.set_own_count(live - np);   // exact: the retain dropped the np absorbed bodies of `live`
+    return NBODY_OK;
+}
+template int merge_contacts<float>(NbodyHandle*, BodyStore<float>&, double, NbodyContact*, size_t, size_t*, float4*, void (*)(NbodyHandle*, int));
+template int merge_contacts<double>(NbodyHandle*, BodyStore<double>&, double, NbodyContact*, size_t, size_t*, double4*, void (*)(NbodyHandle*, int));
 
 }}  // namespace nbody::pairs

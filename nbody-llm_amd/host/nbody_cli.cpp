@@ -13,7 +13,9 @@
 // interactions per second on a line of its own; --external KIND:p0:p1[...][:cx:cy:cz] (repeatable; plummer:M:b, hernquist:M:a,
 // mn:M:a:b, log:v0:rc:qy:qz) adds a component of a static external field and reports the external energy before and after;
 // --diagnostics prints M, |P|, |L| and the 10 / 50 / 90 % Lagrangian radii about the centre of mass before and after the run,
-// and the binary census of the final state (nbody_bound_pairs) on a line of its own; --pairs prints that line alone.
+// and the binary census of the final state (nbody_bound_pairs) on a line of its own; --pairs prints that line alone;
+// --merge RADIUS[:EVERY] runs nbody_merge_contacts after every EVERY-th step (default 1: sticky spheres of that merge distance)
+// and prints how many bodies were absorbed, in how many calls, on a line of its own.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -35,7 +37,8 @@ static void usage() {
                  "                 [--tracers M]   (massless tracers in the same disc or sphere; --dtype f32)\n"
                  "                 [--external plummer:M:b[:cx:cy:cz] | hernquist:M:a[...] | mn:M:a:b[...] | log:v0:rc:qy:qz[...]]   (repeatable)\n"
                  "                 [--diagnostics]   (M, |P|, |L| and the 10/50/90 %% Lagrangian radii before and after the run, and --pairs)\n"
-                 "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n");
+                 "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n"
+                 "                 [--merge RADIUS[:EVERY]]   (after every EVERY-th step, merge the mutual nearest pairs closer than RADIUS)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -94,7 +97,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
-               bool diagnostics, bool pairs) {
+               bool diagnostics, bool pairs, double merge_radius, size_t merge_every) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -130,13 +133,19 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         sim->init();
         const double ext_before = external.empty() ? 0.0 : sim->external_energy();
         if (diagnostics) print_diagnostics(*sim, "before");
+        size_t merged = 0, merge_calls = 0;
+        const auto merge_after = [&](size_t i) {   // --merge: one call after step i + 1 when it is an EVERY-th one
+            if (!(merge_radius > 0.0) || (i + 1) % merge_every) return;
+            merged += sim->merge_contacts(merge_radius).size();
+            merge_calls += 1;
+        };
         auto start = std::chrono::steady_clock::now();
         if (integrator == "host") {   // the trait's generic Integrator, on the host (simulation.hpp step_by_with)
             nbody::LeapFrogIntegratorT<F> leapfrog;
             leapfrog.init();
-            for (size_t i = 0; i < steps; ++i) sim->step_by_with(leapfrog, F(dt));
+            for (size_t i = 0; i < steps; ++i) { sim->step_by_with(leapfrog, F(dt)); merge_after(i); }
         } else {
-            for (size_t i = 0; i < steps; ++i) sim->step();
+            for (size_t i = 0; i < steps; ++i) { sim->step(); merge_after(i); }
         }
         sim->sync();
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
@@ -152,6 +161,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (!external.empty()) std::printf("External energy: %.9e -> %.9e\n", ext_before, sim->external_energy());
         if (diagnostics) print_diagnostics(*sim, "after");
         if (diagnostics || pairs) print_pairs(*sim);
+        if (merge_radius > 0.0) std::printf("Merged: %zu bodies in %zu calls\n", merged, merge_calls);
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -183,6 +193,8 @@ int main(int argc, char** argv) {
     size_t n_tracers = 0;
     std::vector<NbodyExternalComponent> external;
     bool diagnostics = false, pairs = false;
+    double merge_radius = 0.0;
+    size_t merge_every = 1;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -204,6 +216,17 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--multipole")) multipole = std::atoi(next());
         else if (!std::strcmp(argv[i], "--diagnostics")) diagnostics = true;
         else if (!std::strcmp(argv[i], "--pairs")) pairs = true;
+        else if (!std::strcmp(argv[i], "--merge")) {
+            char* end = nullptr;
+            const char* arg = next();
+            merge_radius = std::strtod(arg, &end);
+            if (end == arg || !(merge_radius > 0.0) || !std::isfinite(merge_radius) || (*end && *end != ':')) { usage(); return 2; }
+            if (*end == ':') {
+                const long long every = std::atoll(end + 1);
+                if (every < 1) { usage(); return 2; }
+                merge_every = size_t(every);
+            }
+        }
         else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--external")) {
             NbodyExternalComponent c;
@@ -235,6 +258,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every);
 }

@@ -266,6 +266,37 @@ public:
         pairs.resize(n);
         return sum;
     }
+    // sticky mergers (nbody_nearest, nbody_contacts, nbody_merge_contacts): f64 unsoftened distances on either F, O(N^2) on the
+    // device; the handles moments() takes.  nearest[i] = the body at the least squared distance from i (-1: none), dist2[i] = it
+    void nearest(std::vector<int32_t>& nearest, std::vector<double>& dist2) {
+        size_t n = 0;
+        check(nbody_nearest(h_, nullptr, nullptr, 0, &n));
+        nearest.assign(n, -1);
+        dist2.assign(n, 0.0);
+        check(nbody_nearest(h_, nearest.data(), dist2.data(), n, &n));
+        nearest.resize(n);
+        dist2.resize(n);
+    }
+    // the mutual nearest pairs closer than `radius` (strictly), in ascending i, i < j; read-only
+    std::vector<NbodyContact> contacts(double radius) {
+        size_t n = 0;
+        check(nbody_nearest(h_, nullptr, nullptr, 0, &n));   // (counts only: n bodies hold at most n / 2 contacts)
+        std::vector<NbodyContact> list(n / 2 + 1);
+        check(nbody_contacts(h_, radius, list.data(), list.size(), &n));
+        list.resize(n);
+        return list;
+    }
+    // the same pairs merged: body i becomes the pair's centre of mass, body j is removed, everybody else keeps their order.
+    // One call merges disjoint pairs: repeat while the list is not empty.
+    std::vector<NbodyContact> merge_contacts(double radius) {
+        size_t n = 0;
+        check(nbody_nearest(h_, nullptr, nullptr, 0, &n));
+        std::vector<NbodyContact> list(n / 2 + 1);
+        check(nbody_merge_contacts(h_, radius, list.data(), list.size(), &n));
+        list.resize(n);
+        if (n) dirty_ = true;
+        return list;
+    }
     NbodyHandle* handle() { return h_; }
 
 protected:
