@@ -789,7 +789,7 @@ int energy(NbodyHandle* h, double* kinetic, double* potential) {
     return NBODY_OK;
 }
 
-// nbody_potentials / nbody_energy_world on an f64 handle (nbody_api.cpp potentials_device has the f32 twin and the contract)
+// nbody_potentials / nbody_energy_world on an f64 handle (nbody_f32.cpp potentials_device is the f32 twin and has the contract)
 int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies* bodies, double* g, bool field) {
     State& s = *h->f64;
     if (mode == NBODY_POTENTIAL_TREE && !s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");

@@ -23,6 +23,7 @@
 using nbody::BoundsF;
 using nbody::Shard;
 
+namespace nbody32 { struct State; }   // F = f32 handles (nbody_f32.cpp)
 namespace nbody64 { struct State; }   // F = f64 handles (nbody_f64.cpp)
 namespace nbody { namespace let { struct State; } }   // spatial shards (nbody_let.cpp)
 struct NbodyHandle;
@@ -31,6 +32,9 @@ struct NbodyHandle;
 
 // records msg as the handle's error (h == nullptr: as nbody_create's) and returns code (nbody_api.cpp)
 int fail(NbodyHandle* h, int code, const std::string& msg);
+// anything the transport noticed behind the host's back (a device-side wait that ran out of time, a peer that gave up), as the
+// handle's error (nbody_api.cpp)
+int comm_check(NbodyHandle* h);
 
 // (expr: a hipError_t, or the int a HandleMem operation hands through from the seam below)
 #define HIP_TRY(h, expr)                                                                              \
@@ -553,7 +557,6 @@ struct TracerState {
     void* d_sort_tmp = nullptr;
     int* d_info = nullptr;                   // [3]
     size_t sort_bytes = 0, sort_cap = 0;
-    bool kick_pending = false;   // a step's tracer walk takes the kick + half drift along (dt: NbodyHandle::kick_dt)
 };
 
 // nbody_set_external_field (nbody_external.cpp): the components as given (f64); a pass rounds them to its precision.  n == 0 (no
@@ -576,19 +579,6 @@ struct NbodyHandle : BodyStore<float> {
     // Barnes-Hut
     std::unique_ptr<nbody::WorkerPool> pool;
     TreeStore<float> tree;       // the tree, its device arrays, the device build's buffers, the walk's split and stack
-    // fast walk with the most-visited records in LDS (kernels_bh.hip, variant 3)
-    float4* d_walk = nullptr;    // [walk_cap + 1] records with explicit links
-    int* d_unified = nullptr;    // [walk_cap + 1]
-    size_t walk_cap = 0;         // nodes
-    float4* d_bfs = nullptr;     // cooperative block walk (variant 5): level-order copy of the nodes
-    void* d_bfs_ws = nullptr;
-    size_t bfs_cap = 0;          // nodes
-    float4* d_hot = nullptr;     // [hot_cap] records
-    int hot_cap = 0;
-    int* d_hot_info = nullptr;   // [2] slot counter, nodes flagged by the last pass
-    int* h_hot_info = nullptr;   // pinned; refreshed after every walk, read after the next step's first sync
-    int hot_threshold = 0;       // NodeB::hot >= this -> staged; steered so that ~hot_cap nodes qualify
-    size_t hot_threshold_n = 0;  // body count the threshold was initialised for
     unsigned long long* d_counters = nullptr;  // [NBODY_WALK_COUNTER_SLOTS][2] accepted, visited (summed on read)
     // nbody_set_multipole: order of the force walk's expansion; 2 = the cells' quadrupole tensors beside the node records
     int multipole = NBODY_MULTIPOLE_MONOPOLE;
@@ -597,39 +587,7 @@ struct NbodyHandle : BodyStore<float> {
     bool quad_pass = false;      // the last force pass walked with quadrupoles (nbody_tree_export_quadrupoles)
     bool quad_call = false;      // the last tree was built by a call in NBODY_POTENTIAL_TREE_QUADRUPOLE (accepted by that export too)
     unsigned long long* h_counters = nullptr;  // pinned
-
-    // symmetric all-pairs kernel (fast math; single shard: n >= Tuning::sym_min_bodies)
-    nbody::SymPlan sym_plan;
-    int* d_sym_bounds = nullptr;
-    float4* d_planes = nullptr;
-    size_t planes_cap = 0;  // float4 entries
-    int sym_waves = 0;
-    // symmetric scheme across shards (kernels_bf_cross.hip)
-    nbody::CrossPlan cross;
-    bool cross_on = false;
-    int4* d_cross_slices = nullptr;
-    size_t cross_slices_cap = 0;
-    float4* d_xplanes = nullptr;   // [parts.n][A][plane_stride] travelling-side sums for other shards' bodies
-    float4* d_send = nullptr;      // [parts.n][plane_stride] what goes back to their owners
-    size_t xplanes_cap = 0, send_cap = 0;
-    int recv_plane0 = 0;           // first plane that receives the other shards' partial sums
-    bool tail_pending = false;     // the plane reduction has not been launched yet (waits for the partials)
-    bool partials_in_flight = false;
-    hipEvent_t ev_partials_ready = nullptr, ev_partials_done = nullptr;
-    bool kick_pending = false;  // step_end asks the force pass to fuse integrate_after_force if it can
-    float kick_dt = 0.f;
-    uint64_t sym_pairs = 0;   // unordered pairs the rotation kernel covers at the current n_local
-    size_t sym_pairs_n = 0;
-
-    // Barnes-Hut with the device build, single shard: steps are enqueued without reading anything back.  A build
-    // that needs the host (deeper than 21 levels, node array too small) sets a sticky flag on the device that turns
-    // every later state-changing kernel into a no-op; the host looks at it at the next synchronisation point and
-    // replays from the step that failed (resolve_async).
-    bool async_bh = false;
-    struct PendingStep { float dt; float elapsed_before; };
-    std::vector<PendingStep> pending;   // steps enqueued since the host last confirmed the device's progress
-    bool last_step_async = false;
-    bool host_tree_once = false;        // the next force pass builds its tree on the host (the replayed step)
+    // Barnes-Hut steps enqueued without a read-back (nbody_f32.cpp State::async_bh): what a build that needs the host sets
     int* d_poison = nullptr;            // [2] sticky flags, steps completed (Shard::poison)
     int* h_poison = nullptr;            // pinned [8]: poison[2] + tree info[3]; between their own synchronisations also scratch, at the offsets below
 
@@ -640,8 +598,6 @@ struct NbodyHandle : BodyStore<float> {
     unsigned profile_tick = 0;
     bool timed_this = false;     // the launch under way is one of the bracketed ones
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_free;
-    double* d_energy = nullptr;
-    size_t energy_blocks = 0;
     PotBufs pot;
     FieldBufs field;
     TracerState tr;
@@ -654,8 +610,10 @@ struct NbodyHandle : BodyStore<float> {
     hipEvent_t ev_drifted = nullptr, ev_gathered = nullptr;
     bool exchange_in_flight = false;
 
+    // what each engine keeps beside the above, private to its translation unit
+    nbody32::State* f32 = nullptr;   // NbodyConfig.dtype == NBODY_F32: the force passes' plans and planes, the step chain's flags
     nbody64::State* f64 = nullptr;   // NbodyConfig.dtype == NBODY_F64: the whole state lives here
-    nbody::let::State* let = nullptr; // NbodyConfig.shard_mode == NBODY_SHARD_SPATIAL: the halo-exchange machinery
+    nbody::let::State* let = nullptr; // NbodyConfig.shard_mode == NBODY_SHARD_SPATIAL (beside f32): the halo-exchange machinery
 
     std::string err;
 };
@@ -715,6 +673,21 @@ struct ForceTimer {  // HIP events around a force-kernel launch, on the launch s
         h->ev_pending.push_back(ev);
     }
 };
+// folds the bracketed launches' timings into the statistics (synchronises when there are any)
+inline int drain_events(NbodyHandle* h) {
+    if (h->ev_pending.empty()) return NBODY_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (auto& ev : h->ev_pending) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) {
+            h->stats.force_kernel_ms += ms;
+            h->stats.force_launches += 1;
+        }
+        h->ev_free.push_back(ev);
+    }
+    h->ev_pending.clear();
+    return NBODY_OK;
+}
 
 // ---- TreeStore<F>'s procedures (they need the handle: its stream, worker pool and statistics)
 

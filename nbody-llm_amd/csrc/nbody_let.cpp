@@ -931,7 +931,7 @@ int update_forces(NbodyHandle* h) { return pass(h, 0.f, false); }
 
 // The force pass at the current positions with its last phase walking for potentials: S_i of the bodies this rank holds
 // AFTER the pass's migration into PotBufs::d_sum, in the order of Shard::ids.  The pass migrates bodies and redraws the
-// bounds like any other, so nbody_potentials runs it on a scratch clone of the rank (nbody_api.cpp), never on the handle.
+// bounds like any other, so nbody_potentials runs it on a scratch clone of the rank (nbody_f32.cpp), never on the handle.
 int potential_pass(NbodyHandle* h) {
     int rc = pot::begin(h, size_t(h->sh.seg_cap));
     return rc ? rc : pass(h, 0.f, false, true);

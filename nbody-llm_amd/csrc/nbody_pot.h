@@ -19,8 +19,11 @@ int energy(NbodyHandle* h, const PotBodies& b, size_t n, double g, double* kinet
 
 }}  // namespace nbody::pot
 
-namespace nbody64 {
 // S_i of the own bodies into PotBufs::d_sum at the handle's current positions (collective on a sharded world); *n = own bodies
-// field = true: nbody_field_at's preparation (nbody_api.cpp potentials_device)
+// field = true: nbody_field_at's preparation (nbody_f32.cpp potentials_device has the contract, nbody_api.cpp's the checks)
+namespace nbody64 {
+int potentials_device(NbodyHandle* h, int mode, size_t* n, nbody::PotBodies* bodies, double* g, bool field = false);
+}
+namespace nbody32 {
 int potentials_device(NbodyHandle* h, int mode, size_t* n, nbody::PotBodies* bodies, double* g, bool field = false);
 }

@@ -189,11 +189,9 @@ int forces(NbodyHandle* h, const float* kick_dt) {
 // Barnes-Hut: called by the body force pass right after its walk, with the tree it built (nothing has overwritten it yet).
 // The tracers are keyed and sorted into tree order, then walk td's nodes over td's split points; the kick + half drift of a
 // step ride in the walk or in its reduction.  Everything is enqueued: the device build's steps stay without a read-back.
-int tree_forces(NbodyHandle* h, const nbody::TreeDev& td) {
+int tree_forces(NbodyHandle* h, const nbody::TreeDev& td, const float* kick_dt) {
     if (!on(h)) return NBODY_OK;
     TracerState& t = h->tr;
-    const bool kick = t.kick_pending;
-    t.kick_pending = false;
     const int m = int(t.n_host);
     if (t.sort_cap < t.cap) {   // the sort's buffers, sized for the capacity once
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -216,7 +214,7 @@ int tree_forces(NbodyHandle* h, const nbody::TreeDev& td) {
         HIP_TRY(h, grow_dev(h, t.d_planes, t.planes_cap, size_t(groups) * stride, sizeof(float4), Grow::exact, kGrowSync));
     }
     nbody::launch_tr_bh_walk(h->stream, t.sh, m, idx, td, groups, t.d_planes, stride, h->g, h->g_soft * h->g_soft, h->theta2,
-                             h->cfg.leaf_mode == NBODY_LEAF_DIRECT, kick ? &h->kick_dt : nullptr, t.d_stats);
+                             h->cfg.leaf_mode == NBODY_LEAF_DIRECT, kick_dt, t.d_stats);
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
 }

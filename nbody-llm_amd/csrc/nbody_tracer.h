@@ -20,6 +20,6 @@ int clone_state(const NbodyHandle* src, NbodyHandle* dst);   // (src's stream is
 // the step's pieces, enqueued on the handle's stream; each returns at once when the handle has no tracers
 int drift_retain(NbodyHandle* h, float dt);                  // half drift + retain of the tracer vector
 int forces(NbodyHandle* h, const float* kick_dt);            // brute force: the tracer force pass over the bodies as they stand; kick_dt: + kick and half drift
-int tree_forces(NbodyHandle* h, const nbody::TreeDev& td);   // Barnes-Hut: the tracers' walk of the tree the body pass just built (+ the kick when TracerState::kick_pending)
+int tree_forces(NbodyHandle* h, const nbody::TreeDev& td, const float* kick_dt);   // Barnes-Hut: the tracers' walk of the tree the body pass just built; kick_dt: likewise
 
 }}  // namespace nbody::tracer

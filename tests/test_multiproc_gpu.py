@@ -1,6 +1,6 @@
 """The PRODUCTION multi-rank step with G real ranks on ONE GPU: every rank a fresh process (G = 8: four processes of
 two rank threads -- a GPU box admits six GPU processes), each calling nbody_step_by / nbody_steps on its own handle;
-the library's own exchange code (exchange_begin / partials_begin in nbody_api.cpp, let::pass in nbody_let.cpp: count
+the library's own exchange code (exchange_begin / partials_begin in nbody_f32.cpp, let::pass in nbody_let.cpp: count
 matrices, variable-size rounds, the communication stream and its events, the host synchronisations) runs over the
 one-device transport of csrc/transport_ipc.hip instead of RCCL, which refuses two ranks on one device.  No
 nbody_debug_* hook is involved; the control plane is nbody-llm_amd/rendezvous.py (stdlib sockets, no torch).
