@@ -674,6 +674,63 @@ typedef struct NbodyContact {
 int nbody_nearest(NbodyHandle* h, int32_t* nearest, double* dist2, size_t cap, size_t* n_out);
 int nbody_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts);
 int nbody_merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts);
+/* ---- friends-of-friends groups: which bodies belong together, and the catalogue of the clumps (no reference counterpart) ---
+ * The friends-of-friends (FoF) group finder of N-body work: two bodies closer than a linking length are friends, a group is a
+ * connected component of the friendship graph.  Two READ-ONLY calls under the exact contract of the binary census and
+ * nbody_nearest above (the bodies are what nbody_download would report -- on a Hermite handle the held (x0, v0) --, tracers
+ * and the external field play no part, no trace in state, NbodyStats, validity flags, levels or the bits of any later step,
+ * no refresh of the host's view of the count, launches sized from its upper bound and the live count read on the device:
+ * right after a retain with no nbody_count in between, scratch through the handle's registry and freed inside the call, no
+ * floating-point atomics: the same state gives the same bits).
+ *   THE LINK is nbody_nearest's metric, f64 on either dtype (an NBODY_F32 handle's positions are widened exactly), unsoftened,
+ * nothing contracted:
+ *     d = x_j - x_i,  r2 = (dx dx + dy dy) + dz dz
+ * Bodies i and j are linked iff r2 < B2, B2 = linking_length * linking_length rounded once; the comparison is STRICT, as in
+ * nbody_contacts.  A NaN r2 never links: a body with a NaN or infinite coordinate is A GROUP OF ITS OWN.  r2_ij == r2_ji bit
+ * for bit, so the relation is symmetric and each unordered pair is looked at once.  tests/fof_ref.py restates both calls in
+ * numpy; the device's results are its integers and its bits.
+ *   nbody_fof_labels: label[i] = THE LOWEST INDEX in i's connected component (indices are those of nbody_download's order).
+ * Pure integers, fully determined by the state: they do not depend on launch shape, scheduling or the bf64_waves knob.
+ * *n_out (may be NULL) = the bodies; *n_groups_out (may be NULL) = the components among them, singletons included.
+ * label == NULL only counts; cap < n returns NBODY_ERR_CAPACITY with *n_out and *n_groups_out set and the array untouched.
+ *   nbody_fof_groups: the components with count >= min_members, in ascending `first`.  members holds their bodies, group after
+ * group, each group in ascending index; offset and count index into it; *n_members is the total.  Either array may be NULL
+ * (counts only); if either non-NULL array is too small the call returns NBODY_ERR_CAPACITY with both counts set and nothing
+ * written.  n_groups and n_members may be NULL.  THE SEVEN SUMS of a group have a fixed association order.  With its members
+ * k = 0 .. count-1 in ascending index:
+ *     1. lane t = k mod 64 adds its terms in ascending k, starting from +0.0;
+ *     2. the terms are m, m x_c and m v_c (f64 from the widened values), each product rounded once;
+ *     3. then sum[t] += sum[t + half] for half = 32, 16, ... 1; the result is sum[0].
+ * One wave per listed group does this; it mirrors the 256-wide tree of nbody_moments and nbody_external_energy.  The centre of
+ * mass is mx / mass and the mean velocity mv / mass: the caller divides.
+ *   HOW: an all-pairs pass on nbody_nearest's frame (one body per lane, partners through LDS, groups of 256 bodies x K slices
+ * sized by bf64_waves, only j > i evaluated) whose lanes unite linked bodies in a lock-free union-find -- every write an
+ * atomic compare-and-swap or minimum that lowers a word, nobody ever waits for anybody; afterwards the one root of a component
+ * is its lowest index whatever the order of events was.  The catalogue is integer work: sizes by integer atomic adds, slots
+ * and offsets by rocPRIM's integer scans, the member list by its stable radix sort.  Only the labels, or the listed records
+ * and members, cross to the host.
+ *   COST: O(N^2 / 2) f64 pair terms of 3 subtractions, 3 products, 2 sums and a compare, plus union-find traffic that depends
+ * on the state (nothing for a world without links; a few atomic operations per linked pair).  NOT MEASURED on an MI355X beyond the
+ * single run of tools/fof_bench.py that DESIGN 3.18 records (about 0.025 s at 262 144 bodies of a Plummer sphere with few
+ * links, against 0.030 s of nbody_nearest); nothing asserts or promises a time.
+ *   Accepted on every world_size == 1, NBODY_SHARD_INDEX handle: both dtypes, both methods, either math mode, any tree build,
+ * leapfrog or Hermite, block steps on or off, with or without tracers, an external field or quadrupoles.  Refused with
+ * NBODY_ERR_INVALID (nbody_last_error names the call): a linking length that is not finite or is <= 0; min_members < 1;
+ * handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
+ *   OUT OF SCOPE: a tree-accelerated neighbour search; periodic boundaries; linking in velocity space; unbinding; group
+ * finding on multi-rank or spatial handles; any change to an existing call. */
+typedef struct NbodyGroup {          /* 72 bytes */
+    int32_t first;     /* lowest member index (nbody_download's order) = the group's label */
+    int32_t count;     /* members */
+    int32_t offset;    /* of its members in the member list */
+    int32_t reserved;  /* 0 */
+    double mass;       /* sum m */
+    double mx[3];      /* sum m x   (centre of mass = mx / mass: the caller divides) */
+    double mv[3];      /* sum m v */
+} NbodyGroup;
+int nbody_fof_labels(NbodyHandle* h, double linking_length, int32_t* label, size_t cap, size_t* n_out, size_t* n_groups_out);
+int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, NbodyGroup* groups, size_t group_cap, size_t* n_groups,
+                     int32_t* members, size_t member_cap, size_t* n_members);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

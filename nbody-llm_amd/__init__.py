@@ -91,6 +91,7 @@ DECLARED_SYMBOLS = [
     "nbody_moments", "nbody_lagrangian_radii",
     "nbody_partners", "nbody_bound_pairs",
     "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
+    "nbody_fof_labels", "nbody_fof_groups",
 ]
 
 
@@ -135,6 +136,18 @@ class NbodyContact(C.Structure):
 CONTACT_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("into", "<i4"), ("reserved", "<i4"), ("separation", "<f8"), ("mass", "<f8"),
                           ("dkinetic", "<f8")])
 assert CONTACT_DTYPE.itemsize == C.sizeof(NbodyContact) == 40
+
+
+class NbodyGroup(C.Structure):
+    """One listed group of nbody_fof_groups (include/nbody_hip.h "friends-of-friends groups")."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("offset", C.c_int32), ("reserved", C.c_int32), ("mass", C.c_double),
+                ("mx", C.c_double * 3), ("mv", C.c_double * 3)]
+
+
+#: the same record as a numpy dtype: what Simulation.fof_groups() returns
+GROUP_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("offset", "<i4"), ("reserved", "<i4"), ("mass", "<f8"),
+                        ("mx", "<f8", (3,)), ("mv", "<f8", (3,))])
+assert GROUP_DTYPE.itemsize == C.sizeof(NbodyGroup) == 72
 
 
 class NbodyStats(C.Structure):
@@ -252,6 +265,8 @@ _sig("nbody_bound_pairs", _i, _H, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c
 _sig("nbody_nearest", _i, _H, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_merge_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_fof_labels", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(_sz))
+_sig("nbody_fof_groups", _i, _H, C.c_double, _i, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -645,6 +660,31 @@ class Simulation:
         acceleration) in row i, removes row j, keeps everybody else's order, and returns the list.  One call merges disjoint
         pairs: repeat while the list is not empty (nbody_merge_contacts)."""
         return self._contact_list(lib.nbody_merge_contacts, radius)
+
+    # -- friends-of-friends groups (nbody_fof_labels, nbody_fof_groups): f64 distances, read-only, O(N^2 / 2) on the device
+    def fof_labels(self, b: float) -> tuple[np.ndarray, int]:
+        """(labels [n] int32, n_groups): labels[i] is the lowest index of i's group, in get_points() order -- two bodies closer
+        than the linking length `b` (strictly) are friends, a group is a connected component of friendship; n_groups counts the
+        groups, singletons included (nbody_fof_labels)."""
+        n, groups = C.c_size_t(0), C.c_size_t(0)
+        self._check(lib.nbody_fof_labels(self._h, float(b), None, 0, C.byref(n), None))   # (the bodies only)
+        labels = np.full(n.value, -1, np.int32)
+        self._check(lib.nbody_fof_labels(self._h, float(b), labels.ctypes.data if n.value else None, n.value, C.byref(n), C.byref(groups)))
+        return labels[: n.value], int(groups.value)
+
+    def fof_groups(self, b: float, min_members: int = 2) -> tuple[np.ndarray, np.ndarray]:
+        """(groups, members): the friends-of-friends groups of linking length `b` with at least min_members bodies as a
+        GROUP_DTYPE array in ascending `first` (= the group's fof_labels() label), and their bodies [int32], group after group,
+        each in ascending index: group k's are members[offset : offset + count].  mass = sum m, mx = sum m x, mv = sum m v, summed
+        in a fixed order; the centre of mass is mx / mass (nbody_fof_groups)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_fof_labels(self._h, float(b), None, 0, C.byref(n), None))   # (the bodies only: an upper bound of both)
+        groups = np.zeros(n.value // max(int(min_members), 1) + 1, GROUP_DTYPE)
+        members = np.full(n.value + 1, -1, np.int32)
+        ng, nm = C.c_size_t(0), C.c_size_t(0)
+        self._check(lib.nbody_fof_groups(self._h, float(b), int(min_members), groups.ctypes.data, len(groups), C.byref(ng),
+                                         members.ctypes.data, len(members), C.byref(nm)))
+        return groups[: ng.value].copy(), members[: nm.value].copy()
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

@@ -1,0 +1,45 @@
+// kernels_fof.h -- launchers of the friends-of-friends group finder (kernels_fof.hip): the connected components of "closer
+// than a linking length" over all pairs, every body's label (the lowest index of its component), and the catalogue of the
+// components with at least min_members bodies.  Internal to libnbody_hip.so.
+#pragma once
+#include "nbody_hip.h"      // NbodyGroup
+#include "kernels_pairs.h"  // PartnerPlan, kPairBlock: k_fof_link runs on k_partner's frame
+#include "shard.h"
+
+namespace nbody { namespace fof {
+
+// The scratch of one call for n_upper rows, carved out of one allocation of scratch_bytes.
+struct FofScratch {
+    int* parent = nullptr;      // [n_upper] the union-find forest (-1 past the live count); dead after k_fof_flatten
+    int* label = nullptr;       // [n_upper] the root of a live row = the lowest index of its component (-1 past the live count)
+    int* size = nullptr;        // [n_upper] members of the component whose root the row is, else 0
+    int* flag = nullptr;        // [n_upper] 1 = a root with size >= min_members: a listed group
+    int* listed = nullptr;      // [n_upper] size where flag, else 0
+    int* slot = nullptr;        // [n_upper] exclusive prefix sums of flag: the group's place in the catalogue
+    int* offset = nullptr;      // [n_upper] exclusive prefix sums of listed: of the group's members in the member list
+    int* slot_root = nullptr;   // [n_upper] the root of the group in each slot
+    unsigned* keys = nullptr;   // [2 n_upper] a row's group slot, or INT_MAX when its component is not listed; in | out
+    int* rows = nullptr;        // [2 n_upper] the row index; in | out: out = the member list, then everybody else
+    int* total = nullptr;       // [2] listed groups, their members
+    void* scan_tmp = nullptr;
+    size_t scan_bytes = 0;
+    void* sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    const int* members(size_t n_upper) const { return rows + n_upper; }
+};
+size_t scratch_bytes(size_t n_upper);
+FofScratch scratch_layout(void* base, size_t n_upper);
+
+// k_fof_init, k_fof_link<F> on the grid of `p`, k_fof_flatten: w.label and w.size of the live rows for the links r2 < B2
+template <class F>
+void launch_components(hipStream_t s, const ShardT<F>& sh, int n_upper, const pairs::PartnerPlan& p, double B2, const FofScratch& w);
+
+// k_fof_flag, the two integer scans, k_fof_slots: w.flag, w.slot, w.offset, w.slot_root, w.keys and w.total; `sort`: the
+// stable radix sort of (slot, row) after them: w.members().  Returns 0, or -1 when a rocPRIM call could not be enqueued.
+int launch_catalogue(hipStream_t s, int n_upper, int min_members, bool sort, const FofScratch& w);
+
+// k_fof_sums<F>, one wave per listed group: out[0 .. n_groups), every field (out: device memory)
+template <class F>
+void launch_sums(hipStream_t s, const ShardT<F>& sh, int n_upper, int n_groups, const FofScratch& w, NbodyGroup* out);
+
+}}  // namespace nbody::fof

@@ -11,6 +11,7 @@
 #include "nbody_external.h"
 #include "nbody_diag.h"
 #include "nbody_pairs.h"
+#include "nbody_fof.h"
 
 #include <algorithm>
 #include <chrono>
@@ -572,6 +573,36 @@ int nbody_merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size
     if (rc) return rc;
     if (h->f64) return nbody64::merge_contacts(h, radius, list, cap, n_contacts);
     return nbody32::merge_contacts(h, radius, list, cap, n_contacts);
+}
+
+// ---- friends-of-friends groups (nbody_fof.cpp): two read-only calls under the census's contract
+namespace {
+int fof_enter(NbodyHandle* h, const char* call, double linking_length) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    if (std::isfinite(linking_length) && linking_length > 0.0) return NBODY_OK;
+    return fail(h, NBODY_ERR_INVALID, std::string(call) + ": linking_length must be finite and > 0");
+}
+}  // namespace
+
+int nbody_fof_labels(NbodyHandle* h, double linking_length, int32_t* label, size_t cap, size_t* n_out, size_t* n_groups_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = fof_enter(h, "nbody_fof_labels", linking_length);
+    if (rc) return rc;
+    if (h->f64) return nbody::fof::labels(h, nbody64::shard(h), nbody64::n_upper(h), linking_length, label, cap, n_out, n_groups_out);
+    return nbody::fof::labels(h, h->sh, h->n_local, linking_length, label, cap, n_out, n_groups_out);
+}
+
+int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, NbodyGroup* groups, size_t group_cap, size_t* n_groups,
+                     int32_t* members, size_t member_cap, size_t* n_members) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = fof_enter(h, "nbody_fof_groups", linking_length);
+    if (rc) return rc;
+    if (min_members < 1) return fail(h, NBODY_ERR_INVALID, "nbody_fof_groups: min_members must be >= 1");
+    if (h->f64)
+        return nbody::fof::groups(h, nbody64::shard(h), nbody64::n_upper(h), linking_length, min_members, groups, group_cap, n_groups,
+                                  members, member_cap, n_members);
+    return nbody::fof::groups(h, h->sh, h->n_local, linking_length, min_members, groups, group_cap, n_groups, members, member_cap, n_members);
 }
 
 // ---- tracers (nbody_tracer.cpp)

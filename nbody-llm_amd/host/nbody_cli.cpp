@@ -15,7 +15,9 @@
 // --diagnostics prints M, |P|, |L| and the 10 / 50 / 90 % Lagrangian radii about the centre of mass before and after the run,
 // and the binary census of the final state (nbody_bound_pairs) on a line of its own; --pairs prints that line alone;
 // --merge RADIUS[:EVERY] runs nbody_merge_contacts after every EVERY-th step (default 1: sticky spheres of that merge distance)
-// and prints how many bodies were absorbed, in how many calls, on a line of its own.
+// and prints how many bodies were absorbed, in how many calls, on a line of its own; --fof B[:MIN] prints the friends-of-friends
+// groups of the final state for the linking length B (nbody_fof_groups): how many have at least MIN members (default 2), the
+// members and the mass of the largest, and the fraction of bodies in no listed group.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -38,7 +40,8 @@ static void usage() {
                  "                 [--external plummer:M:b[:cx:cy:cz] | hernquist:M:a[...] | mn:M:a:b[...] | log:v0:rc:qy:qz[...]]   (repeatable)\n"
                  "                 [--diagnostics]   (M, |P|, |L| and the 10/50/90 %% Lagrangian radii before and after the run, and --pairs)\n"
                  "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n"
-                 "                 [--merge RADIUS[:EVERY]]   (after every EVERY-th step, merge the mutual nearest pairs closer than RADIUS)\n");
+                 "                 [--merge RADIUS[:EVERY]]   (after every EVERY-th step, merge the mutual nearest pairs closer than RADIUS)\n"
+                 "                 [--fof B[:MIN]]   (the friends-of-friends groups of the final state: linking length B, at least MIN members, default 2)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -92,12 +95,24 @@ static void print_pairs(Sim& sim) {
                 pairs.empty() ? nan : pairs[hard].eccentricity);
 }
 
+// the line of --fof: nbody_fof_groups; the largest group is the one of most members (the first of equals)
+template <class Sim>
+static void print_fof(Sim& sim, double b, int min_members) {
+    std::vector<int32_t> members;
+    const std::vector<NbodyGroup> groups = sim.fof_groups(b, members, min_members);
+    size_t big = 0;
+    for (size_t k = 1; k < groups.size(); ++k) if (groups[k].count > groups[big].count) big = k;
+    const size_t n = sim.get_points().size();
+    std::printf("FoF groups: %zu largest %d mass %.9e ungrouped %.6f\n", groups.size(), groups.empty() ? 0 : groups[big].count,
+                groups.empty() ? 0.0 : groups[big].mass, n ? double(n - members.size()) / double(n) : 0.0);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
-               bool diagnostics, bool pairs, double merge_radius, size_t merge_every) {
+               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -162,6 +177,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (diagnostics) print_diagnostics(*sim, "after");
         if (diagnostics || pairs) print_pairs(*sim);
         if (merge_radius > 0.0) std::printf("Merged: %zu bodies in %zu calls\n", merged, merge_calls);
+        if (fof_b > 0.0) print_fof(*sim, fof_b, fof_min);
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -195,6 +211,8 @@ int main(int argc, char** argv) {
     bool diagnostics = false, pairs = false;
     double merge_radius = 0.0;
     size_t merge_every = 1;
+    double fof_b = 0.0;
+    int fof_min = 2;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -225,6 +243,16 @@ int main(int argc, char** argv) {
                 const long long every = std::atoll(end + 1);
                 if (every < 1) { usage(); return 2; }
                 merge_every = size_t(every);
+            }
+        }
+        else if (!std::strcmp(argv[i], "--fof")) {
+            char* end = nullptr;
+            const char* arg = next();
+            fof_b = std::strtod(arg, &end);
+            if (end == arg || !(fof_b > 0.0) || !std::isfinite(fof_b) || (*end && *end != ':')) { usage(); return 2; }
+            if (*end == ':') {
+                fof_min = std::atoi(end + 1);
+                if (fof_min < 1) { usage(); return 2; }
             }
         }
         else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
@@ -258,6 +286,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min);
 }

@@ -297,6 +297,29 @@ public:
         if (n) dirty_ = true;
         return list;
     }
+    // friends-of-friends groups (nbody_fof_labels, nbody_fof_groups): bodies closer than the linking length b (strictly, f64
+    // unsoftened distances on either F) are friends, a group is a connected component; read-only, the handles moments() takes.
+    // labels[i] = the lowest index of i's group; returns the number of groups, singletons included
+    size_t fof_labels(double b, std::vector<int32_t>& labels) {
+        size_t n = 0, n_groups = 0;
+        check(nbody_fof_labels(h_, b, nullptr, 0, &n, nullptr));   // (the bodies only)
+        labels.assign(n, -1);
+        check(nbody_fof_labels(h_, b, labels.data(), n, &n, &n_groups));
+        labels.resize(n);
+        return n_groups;
+    }
+    // the groups of at least min_members bodies in ascending `first`, and their bodies, group after group, each in ascending
+    // index: group k's are members[offset .. offset + count)
+    std::vector<NbodyGroup> fof_groups(double b, std::vector<int32_t>& members, int min_members = 2) {
+        size_t n = 0, n_groups = 0, n_members = 0;
+        check(nbody_fof_labels(h_, b, nullptr, 0, &n, nullptr));   // (the bodies only: an upper bound of both counts)
+        std::vector<NbodyGroup> groups(n / size_t(min_members > 0 ? min_members : 1) + 1);
+        members.assign(n + 1, -1);
+        check(nbody_fof_groups(h_, b, min_members, groups.data(), groups.size(), &n_groups, members.data(), members.size(), &n_members));
+        groups.resize(n_groups);
+        members.resize(n_members);
+        return groups;
+    }
     NbodyHandle* handle() { return h_; }
 
 protected:
