@@ -1,9 +1,8 @@
 // nbody_api.cpp -- the C ABI of include/nbody_hip.h: the creation and the end of a handle, and the entry points.  An entry
 // point checks its arguments, binds the handle's device and hands on to the engine the handle runs: nbody_f64.cpp (F = f64),
 // nbody_let.cpp (spatial shards) or nbody_f32.cpp (F = f32 on one shard or over index blocks, where the step chain is described).
-#include "nbody_handle.h"
-#include "nbody_f32.h"
-#include "nbody_f64.h"
+// The bodies and their settings are the engine's: a call that only reads them, whatever the precision, goes through with_bodies.
+#include "nbody_engine.h"
 #include "nbody_let.h"
 #include "nbody_pot.h"
 #include "nbody_field.h"
@@ -89,10 +88,9 @@ void free_all(NbodyHandle* h) {
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     for (auto& ev : h->ev_pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto& ev : h->ev_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    nbody32::destroy(h);      // (the states and their events; their memory is the registry's like everything else)
+    nbody::let::destroy(h);   // (the states, their events and host octrees; their device memory is the registry's like everything else)
+    nbody32::destroy(h);
     nbody64::destroy(h);
-    nbody::let::destroy(h);
-    h->tree.host.clear();     // (the host octree's pinned node arrays are its own: nbody_handle.h pinned_alloc)
     h->mem.release_all();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -164,12 +162,11 @@ int create_impl(const NbodyConfig* cfg, NbodyHandle** out) {
         CREATE_TRY(h->mem.pin(h->h_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long)));
     }
 #undef CREATE_TRY
-    Shard& sh = h->sh;
+    ShardShape& sh = h->shape;
     sh.n_seg = cfg->world_size;
     sh.my_seg = cfg->rank;
     sh.seg_cap = int((cfg->capacity + cfg->world_size - 1) / cfg->world_size);   // bodies an index block can hold
-    if (cfg->dtype == NBODY_F64) {   // the bodies of an f64 handle live in nbody64::State (this store keeps the shape only)
-        h->seg_count_host.assign(size_t(sh.n_seg), 0);
+    if (cfg->dtype == NBODY_F64) {
         int rc64 = nbody64::create(h);
         if (rc64) return bail(rc64);
         *out = h;
@@ -309,7 +306,7 @@ int nbody_remove_point(NbodyHandle* h, size_t index) {
 int nbody_set_settings_f64(NbodyHandle* h, double g, double g_soft, double dt, double theta2) {
     if (!h) return NBODY_ERR_INVALID;
     if (h->f64) return nbody64::set_settings(h, g, g_soft, dt, theta2);
-    h->set_settings(float(g), float(g_soft), float(dt), float(theta2));
+    nbody32::bodies(h).set_settings(float(g), float(g_soft), float(dt), float(theta2));
     return NBODY_OK;
 }
 
@@ -319,28 +316,19 @@ int nbody_set_settings(NbodyHandle* h, float g, float g_soft, float dt, float th
 
 int nbody_get_settings_f64(const NbodyHandle* h, double* g, double* g_soft, double* dt, double* theta2) {
     if (!h) return NBODY_ERR_INVALID;
-    if (h->f64) return nbody64::get_settings(h, g, g_soft, dt, theta2);
-    h->get_settings(g, g_soft, dt, theta2);
-    return NBODY_OK;
+    return with_bodies(h, [&](const auto& b) { b.get_settings(g, g_soft, dt, theta2); return int(NBODY_OK); });
 }
 
 int nbody_get_settings(const NbodyHandle* h, float* g, float* g_soft, float* dt, float* theta2) {
     if (!h) return NBODY_ERR_INVALID;
-    if (!h->f64) { h->get_settings(g, g_soft, dt, theta2); return NBODY_OK; }
-    double v[4];
-    nbody64::get_settings(h, &v[0], &v[1], &v[2], &v[3]);
-    if (g) *g = float(v[0]);
-    if (g_soft) *g_soft = float(v[1]);
-    if (dt) *dt = float(v[2]);
-    if (theta2) *theta2 = float(v[3]);
-    return NBODY_OK;
+    return with_bodies(h, [&](const auto& b) { b.get_settings(g, g_soft, dt, theta2); return int(NBODY_OK); });
 }
 
 int nbody_set_bounds_f64(NbodyHandle* h, const double center[3], double width) {
     if (!h || !center) return NBODY_ERR_INVALID;
     if (h->f64) return nbody64::set_bounds(h, center, width);
     const float c[3] = {float(center[0]), float(center[1]), float(center[2])};
-    h->set_bounds(c, float(width));
+    nbody32::bodies(h).set_bounds(c, float(width));
     return NBODY_OK;
 }
 
@@ -380,7 +368,7 @@ int nbody_steps(NbodyHandle* h, int k) {
     if (rc) return rc;
     if (h->f64) return nbody64::steps(h, k);
     if (h->let) {
-        for (int i = 0; i < k; ++i) { rc = nbody::let::step(h, h->dt); if (rc) return rc; }
+        for (int i = 0; i < k; ++i) { rc = nbody::let::step(h, nbody32::bodies(h).dt); if (rc) return rc; }
         return NBODY_OK;
     }
     return nbody32::steps(h, k);
@@ -391,7 +379,7 @@ int nbody_update_forces(NbodyHandle* h) {
     int rc = use_device(h);
     if (rc) return rc;
     if (h->f64) return nbody64::update_forces(h);
-    if (h->let) return h->bounds_set ? nbody::let::update_forces(h) : fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    if (h->let) return nbody32::bodies(h).bounds_set ? nbody::let::update_forces(h) : fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     return nbody32::update_forces(h);
 }
 
@@ -405,23 +393,18 @@ int external_enter(NbodyHandle* h, const char* call) {
     if (const char* why = nbody::ext::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
     return nbody32::resolve_async(h);
 }
-double g_of(const NbodyHandle* h) {
-    double g = double(h->g);
-    if (h->f64) nbody64::get_settings(h, &g, nullptr, nullptr, nullptr);
-    return g;
-}
+double g_of(const NbodyHandle* h) { return with_bodies(h, [](const auto& b) { return double(b.g); }); }
 // per body potentials (phi may be null) and sum m phi (energy may be null) at the current positions; *n_out = live bodies
 int external_potentials(NbodyHandle* h, bool want_phi, double* phi, size_t cap, size_t* n_out, double* energy, const char* call) {
-    size_t n = 0;
-    int rc = NBODY_OK;
-    if (h->f64) rc = nbody64::count(h, &n);
-    else { rc = h->sync_count(h, h->stream); n = h->n_local; }
-    if (rc) return rc;
-    if (n_out) *n_out = n;
-    if (want_phi && n > cap) return fail(h, NBODY_ERR_CAPACITY, std::string(call) + ": buffer too small");
-    if (want_phi && n && !phi) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": phi is NULL");
-    if (h->f64) return nbody::ext::potentials(h, nbody64::shard(h), n, g_of(h), phi, energy);
-    return nbody::ext::potentials(h, h->sh, n, g_of(h), phi, energy);
+    return with_bodies(h, [&](auto& b) {
+        const int rc = b.sync_count(h, h->stream);
+        if (rc) return rc;
+        const size_t n = b.n_local;
+        if (n_out) *n_out = n;
+        if (want_phi && n > cap) return fail(h, NBODY_ERR_CAPACITY, std::string(call) + ": buffer too small");
+        if (want_phi && n && !phi) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": phi is NULL");
+        return nbody::ext::potentials(h, b.sh, n, double(b.g), phi, energy);
+    });
 }
 }  // namespace
 
@@ -493,8 +476,7 @@ int nbody_moments(NbodyHandle* h, double out[10]) {
     int rc = diag_enter(h, "nbody_moments");
     if (rc) return rc;
     if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_moments: out is NULL");
-    if (h->f64) return nbody::diag::moments(h, nbody64::shard(h), nbody64::n_upper(h), out);
-    return nbody::diag::moments(h, h->sh, h->n_local, out);
+    return with_bodies(h, [&](auto& b) { return nbody::diag::moments(h, b.sh, b.n_local, out); });
 }
 
 int nbody_lagrangian_radii(NbodyHandle* h, const double center[3], const double* fractions, size_t n_frac, double* radii, double* mass_out) {
@@ -507,37 +489,22 @@ int nbody_lagrangian_radii(NbodyHandle* h, const double center[3], const double*
     for (size_t k = 0; k < n_frac; ++k)
         if (!(fractions[k] >= 0.0 && fractions[k] <= 1.0))   // (a NaN fails both comparisons)
             return fail(h, NBODY_ERR_INVALID, "nbody_lagrangian_radii: fraction " + std::to_string(k) + " is not in [0, 1]");
-    if (h->f64) return nbody::diag::lagrangian_radii(h, nbody64::shard(h), nbody64::n_upper(h), center, fractions, n_frac, radii, mass_out);
-    return nbody::diag::lagrangian_radii(h, h->sh, h->n_local, center, fractions, n_frac, radii, mass_out);
+    return with_bodies(h, [&](auto& b) { return nbody::diag::lagrangian_radii(h, b.sh, b.n_local, center, fractions, n_frac, radii, mass_out); });
 }
 
-// ---- binary census (nbody_pairs.cpp): the contract of the diagnostics above, diag_enter included
-namespace {
-void g_and_soft(const NbodyHandle* h, double* g, double* g_soft) {   // the handle's, widened
-    *g = double(h->g);
-    *g_soft = double(h->g_soft);
-    if (h->f64) nbody64::get_settings(h, g, g_soft, nullptr, nullptr);
-}
-}  // namespace
-
+// ---- binary census (nbody_pairs.cpp): the contract of the diagnostics above, diag_enter included; g and g_soft widened
 int nbody_partners(NbodyHandle* h, int32_t* partner, double* energy, size_t cap, size_t* n_out) {
     if (!h) return NBODY_ERR_INVALID;
     int rc = diag_enter(h, "nbody_partners");
     if (rc) return rc;
-    double g = 0.0, g_soft = 0.0;
-    g_and_soft(h, &g, &g_soft);
-    if (h->f64) return nbody::pairs::partners(h, nbody64::shard(h), nbody64::n_upper(h), g, g_soft, partner, energy, cap, n_out);
-    return nbody::pairs::partners(h, h->sh, h->n_local, g, g_soft, partner, energy, cap, n_out);
+    return with_bodies(h, [&](auto& b) { return nbody::pairs::partners(h, b.sh, b.n_local, double(b.g), double(b.g_soft), partner, energy, cap, n_out); });
 }
 
 int nbody_bound_pairs(NbodyHandle* h, NbodyBoundPair* pairs, size_t cap, size_t* n_pairs, double* binding_sum) {
     if (!h) return NBODY_ERR_INVALID;
     int rc = diag_enter(h, "nbody_bound_pairs");
     if (rc) return rc;
-    double g = 0.0, g_soft = 0.0;
-    g_and_soft(h, &g, &g_soft);
-    if (h->f64) return nbody::pairs::bound_pairs(h, nbody64::shard(h), nbody64::n_upper(h), g, g_soft, pairs, cap, n_pairs, binding_sum);
-    return nbody::pairs::bound_pairs(h, h->sh, h->n_local, g, g_soft, pairs, cap, n_pairs, binding_sum);
+    return with_bodies(h, [&](auto& b) { return nbody::pairs::bound_pairs(h, b.sh, b.n_local, double(b.g), double(b.g_soft), pairs, cap, n_pairs, binding_sum); });
 }
 
 // ---- sticky mergers (nbody_pairs.cpp): nearest and contacts under the census's contract; merge_contacts begins like
@@ -553,8 +520,7 @@ int nbody_nearest(NbodyHandle* h, int32_t* nearest, double* dist2, size_t cap, s
     if (!h) return NBODY_ERR_INVALID;
     int rc = diag_enter(h, "nbody_nearest");
     if (rc) return rc;
-    if (h->f64) return nbody::pairs::nearest(h, nbody64::shard(h), nbody64::n_upper(h), nearest, dist2, cap, n_out);
-    return nbody::pairs::nearest(h, h->sh, h->n_local, nearest, dist2, cap, n_out);
+    return with_bodies(h, [&](auto& b) { return nbody::pairs::nearest(h, b.sh, b.n_local, nearest, dist2, cap, n_out); });
 }
 
 int nbody_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts) {
@@ -562,8 +528,7 @@ int nbody_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap
     int rc = diag_enter(h, "nbody_contacts");
     if (!rc) rc = contact_radius(h, "nbody_contacts", radius);
     if (rc) return rc;
-    if (h->f64) return nbody::pairs::contacts(h, nbody64::shard(h), nbody64::n_upper(h), radius, list, cap, n_contacts);
-    return nbody::pairs::contacts(h, h->sh, h->n_local, radius, list, cap, n_contacts);
+    return with_bodies(h, [&](auto& b) { return nbody::pairs::contacts(h, b.sh, b.n_local, radius, list, cap, n_contacts); });
 }
 
 int nbody_merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts) {
@@ -589,8 +554,7 @@ int nbody_fof_labels(NbodyHandle* h, double linking_length, int32_t* label, size
     if (!h) return NBODY_ERR_INVALID;
     int rc = fof_enter(h, "nbody_fof_labels", linking_length);
     if (rc) return rc;
-    if (h->f64) return nbody::fof::labels(h, nbody64::shard(h), nbody64::n_upper(h), linking_length, label, cap, n_out, n_groups_out);
-    return nbody::fof::labels(h, h->sh, h->n_local, linking_length, label, cap, n_out, n_groups_out);
+    return with_bodies(h, [&](auto& b) { return nbody::fof::labels(h, b.sh, b.n_local, linking_length, label, cap, n_out, n_groups_out); });
 }
 
 int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, NbodyGroup* groups, size_t group_cap, size_t* n_groups,
@@ -599,10 +563,9 @@ int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, Nbo
     int rc = fof_enter(h, "nbody_fof_groups", linking_length);
     if (rc) return rc;
     if (min_members < 1) return fail(h, NBODY_ERR_INVALID, "nbody_fof_groups: min_members must be >= 1");
-    if (h->f64)
-        return nbody::fof::groups(h, nbody64::shard(h), nbody64::n_upper(h), linking_length, min_members, groups, group_cap, n_groups,
-                                  members, member_cap, n_members);
-    return nbody::fof::groups(h, h->sh, h->n_local, linking_length, min_members, groups, group_cap, n_groups, members, member_cap, n_members);
+    return with_bodies(h, [&](auto& b) {
+        return nbody::fof::groups(h, b.sh, b.n_local, linking_length, min_members, groups, group_cap, n_groups, members, member_cap, n_members);
+    });
 }
 
 // ---- tracers (nbody_tracer.cpp)
@@ -660,13 +623,13 @@ int nbody_host_tracer_plan(size_t n_tracers, size_t n_bodies, int out[4]) {
 
 int nbody_elapsed(const NbodyHandle* h, float* out) {
     if (!h || !out) return NBODY_ERR_INVALID;
-    *out = h->f64 ? float(nbody64::elapsed(h)) : h->elapsed;
+    *out = with_bodies(h, [](const auto& b) { return float(b.elapsed); });
     return NBODY_OK;
 }
 
 int nbody_elapsed_f64(const NbodyHandle* h, double* out) {
     if (!h || !out) return NBODY_ERR_INVALID;
-    *out = h->f64 ? nbody64::elapsed(h) : double(h->elapsed);
+    *out = with_bodies(h, [](const auto& b) { return double(b.elapsed); });
     return NBODY_OK;
 }
 
@@ -817,7 +780,7 @@ int nbody_tree_export(NbodyHandle* h, float* com_mass, float* width, int32_t* sk
         rc = nbody32::resolve_async(h);
         if (rc) return rc;
     }
-    return h->tree.export_nodes(h, com_mass, width, skip, cap, n_nodes);
+    return nbody32::bodies(h).tree.export_nodes(h, com_mass, width, skip, cap, n_nodes);
 }
 
 namespace {
@@ -945,7 +908,7 @@ int nbody_tree_export_f64(NbodyHandle* h, double* com_mass, double* width, int32
     if (h->cfg.method != NBODY_BARNES_HUT) return fail(h, NBODY_ERR_INVALID, "not a Barnes-Hut handle");
     if (!h->f64) return fail(h, NBODY_ERR_INVALID, "f32 handle: use nbody_tree_export");
     int rc = use_device(h);
-    return rc ? rc : nbody64::tree_export(h, com_mass, width, skip, cap, n_nodes);
+    return rc ? rc : nbody64::bodies(h).tree.export_nodes(h, com_mass, width, skip, cap, n_nodes);
 }
 
 // ---- the cells of the last tree, for drawing (the reference's Barnes-Hut Renderable walks every node's bounds,
@@ -987,33 +950,21 @@ void cells_from_preorder(const F* com_mass, const int32_t* skip, size_t n, const
 
 int nbody_tree_export_cells(NbodyHandle* h, float* min_max6, int32_t* depth, size_t cap, size_t* n_nodes) {
     if (!h) return NBODY_ERR_INVALID;
+    // (the count first, through the precision's own entry point: its refusals and the settling of enqueued steps)
     size_t n = 0;
-    if (h->f64) {
-        int rc = nbody_tree_export_f64(h, nullptr, nullptr, nullptr, 0, &n);
-        if (rc) return rc;
-        if (n_nodes) *n_nodes = n;
-        if (!min_max6 && !depth) return NBODY_OK;
-        if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "tree export buffer too small");
-        std::vector<double> cm(4 * n), w(n);
-        std::vector<int32_t> sk(n);
-        rc = nbody_tree_export_f64(h, cm.data(), w.data(), sk.data(), n, &n);
-        if (rc) return rc;
-        double c[3], width;
-        nbody64::get_bounds(h, c, &width);
-        cells_from_preorder<double>(cm.data(), sk.data(), n, c, width, min_max6, depth);
-        return NBODY_OK;
-    }
-    int rc = nbody_tree_export(h, nullptr, nullptr, nullptr, 0, &n);
+    int rc = h->f64 ? nbody_tree_export_f64(h, nullptr, nullptr, nullptr, 0, &n) : nbody_tree_export(h, nullptr, nullptr, nullptr, 0, &n);
     if (rc) return rc;
     if (n_nodes) *n_nodes = n;
     if (!min_max6 && !depth) return NBODY_OK;
     if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "tree export buffer too small");
-    std::vector<float> cm(4 * n), w(n);
-    std::vector<int32_t> sk(n);
-    rc = nbody_tree_export(h, cm.data(), w.data(), sk.data(), n, &n);
-    if (rc) return rc;
-    cells_from_preorder<float>(cm.data(), sk.data(), n, h->center, h->width, min_max6, depth);
-    return NBODY_OK;
+    return with_bodies(h, [&](auto& b) {
+        using F = std::remove_reference_t<decltype(b.width)>;
+        std::vector<F> cm(4 * n);
+        std::vector<int32_t> sk(n);
+        const int rc2 = b.tree.export_nodes(h, cm.data(), nullptr, sk.data(), n, &n);
+        if (!rc2) cells_from_preorder<F>(cm.data(), sk.data(), n, b.center, b.width, min_max6, depth);
+        return rc2;
+    });
 }
 
 int nbody_comm_unique_id(void* id_bytes) {
@@ -1061,7 +1012,7 @@ int nbody_comm_init(NbodyHandle* h, const void* id_bytes) {
         HIP_TRY(h, hipEventCreateWithFlags(&h->ev_gathered, hipEventDisableTiming));
     }
     Agreement mine{NBODY_ABI_VERSION, h->cfg.method, h->cfg.math_mode, h->cfg.leaf_mode, h->cfg.tree_build, h->cfg.dtype, h->cfg.shard_mode,
-                   h->cfg.world_size, h->sh.seg_cap, nbody::tuning().cross_sym, nbody::tuning().sym_packed, nbody::tuning().bf_fast_variant, nbody::tuning().bh_walk_variant,
+                   h->cfg.world_size, h->shape.seg_cap, nbody::tuning().cross_sym, nbody::tuning().sym_packed, nbody::tuning().bf_fast_variant, nbody::tuning().bh_walk_variant,
                    nbody::tuning().bh_walk_split, h->cfg.capacity};
     std::vector<Agreement> all(size_t(h->cfg.world_size));
     TP_TRY(h, h->tp->host_all_gather(&mine, all.data(), sizeof(Agreement)));
@@ -1200,15 +1151,17 @@ int nbody_debug_step_begin(NbodyHandle* h, float dt) {
 int nbody_debug_import_segment(NbodyHandle* h, NbodyHandle* peer) {
     if (!h || !peer) return NBODY_ERR_INVALID;
     if (h->f64 || peer->f64) return fail(h, NBODY_ERR_INVALID, "f64 handles are single-shard");
-    if (h->sh.n_seg != peer->sh.n_seg || h->sh.seg_cap != peer->sh.seg_cap) return fail(h, NBODY_ERR_INVALID, "peer has a different sharding");
+    auto& b = nbody32::bodies(h);
+    const Shard& from = nbody32::bodies(peer).sh;
+    if (b.sh.n_seg != from.n_seg || b.sh.seg_cap != from.seg_cap) return fail(h, NBODY_ERR_INVALID, "peer has a different sharding");
     int rc = use_device(h);
     if (rc) return rc;
-    const int s = peer->sh.my_seg;
+    const int s = from.my_seg;
     HIP_TRY(h, hipStreamSynchronize(peer->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->sh.pos_all + size_t(s) * h->sh.seg_cap, peer->sh.own_pos(), size_t(h->sh.seg_cap) * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->sh.seg_count + s, peer->sh.own_count(), sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b.sh.pos_all + size_t(s) * b.sh.seg_cap, from.own_pos(), size_t(b.sh.seg_cap) * sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b.sh.seg_count + s, from.own_count(), sizeof(int), hipMemcpyDeviceToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->count_dirty = true;
+    b.count_dirty = true;
     return NBODY_OK;
 }
 

@@ -1,11 +1,16 @@
 // nbody_f32.h -- F = f32 handles (NbodyConfig.dtype == NBODY_F32) on one shard or over index-block shards, and the body store
-// of a spatial shard: internal entry points behind include/nbody_hip.h.  Name for name what nbody_f64.h has for F = f64.
+// of a spatial shard: internal entry points behind include/nbody_hip.h.  Name for name what nbody_f64.h has for F = f64; what
+// the two are the same text in is nbody_engine.h's.
 #pragma once
 #include "nbody_handle.h"
 
 namespace nbody32 {
 
-int create(NbodyHandle* h);                                   // after the stream (and, for Barnes-Hut, pool + counters) exist and the shard has its shape
+// the bodies, their settings and the tree of an f32 handle (a base of nbody_f32.cpp's State)
+EngineBodies<float>& bodies(NbodyHandle* h);
+const EngineBodies<float>& bodies(const NbodyHandle* h);
+
+int create(NbodyHandle* h);                                   // after the stream (and, for Barnes-Hut, pool + counters) exist and the handle has its shape
 void destroy(NbodyHandle* h);
 int clone_state(NbodyHandle* src, NbodyHandle* dst);
 int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride);

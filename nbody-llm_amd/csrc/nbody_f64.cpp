@@ -6,7 +6,7 @@
 // their global order).  NBODY_MATH_FAST: the fast walk (one running sum per lane, split node range), device build on one
 // shard; brute force every unordered pair once (kernels_bf64.hip), the other blocks' bodies one-sided.  Bodies cross the
 // boundary as 80-byte records.
-#include "nbody_f64.h"
+#include "nbody_engine.h"
 #include "kernels_f64.h"
 #include "kernels_hermite.h"
 #include "nbody_external.h"
@@ -34,10 +34,7 @@ struct PlanePass {
     int ensure(NbodyHandle* h, size_t n_local, size_t n_remote, int n_seg);
 };
 
-struct State : BodyStore<double> {   // (the bodies, their host view and the settings: nbody_handle.h)
-    TreeStore<double> tree;    // Barnes-Hut: the tree, its device arrays, the device build's buffers, the walk's split and stack
-    double* d_energy = nullptr;
-    size_t energy_blocks = 0;
+struct State : EngineBodies<double> {   // (the bodies, their host view, the settings and the tree: nbody_handle.h)
     const double* kick_dt = nullptr;   // inside a step: the dt the force pass may apply itself (fast walk, split node range)
     int kicked = 0;
     PlanePass bf{1, nullptr};          // fast brute force (NBODY_MATH_FAST): one kind of planes
@@ -99,9 +96,8 @@ uint64_t launch_own_pairs(NbodyHandle* h, const PlanePass& pp, size_t n_local, S
 // order, with the step's kick when there is one.  Enqueues only (no host synchronisation unless the planes grow).
 int bf_forces_fast(NbodyHandle* h, State& s, double eps2) {
     if (s.n_local == 0) return NBODY_OK;
-    uint64_t tot = 0;
-    for (int c : s.seg_count_host) tot += uint64_t(c);
-    const size_t n_remote = size_t(tot) - std::min<size_t>(size_t(tot), size_t(s.seg_count_host[size_t(s.sh.my_seg)]));
+    const size_t tot = engine::total_upper(s);
+    const size_t n_remote = tot - std::min<size_t>(tot, size_t(s.seg_count_host[size_t(s.sh.my_seg)]));
     int rc = s.bf.ensure(h, s.n_local, n_remote, s.sh.n_seg);
     if (rc) return rc;
     const Bf64Plan& p = s.bf.plan;
@@ -290,11 +286,7 @@ int bf_forces(NbodyHandle* h, State& s) {
         launch_bf_strict(h->stream, s.sh, int(s.n_local), s.g, eps2);
     }
     HIP_TRY(h, hipGetLastError());
-    if (h->timed_this && s.n_local > 0) {
-        uint64_t tot = 0;
-        for (int c : s.seg_count_host) tot += uint64_t(c);
-        h->stats.force_kernel_interactions += uint64_t(s.n_local) * (tot - 1);
-    }
+    if (h->timed_this && s.n_local > 0) h->stats.force_kernel_interactions += uint64_t(s.n_local) * (uint64_t(engine::total_upper(s)) - 1);
     return NBODY_OK;
 }
 
@@ -391,13 +383,7 @@ int forces(NbodyHandle* h, State& s) { return h->cfg.method == NBODY_BARNES_HUT 
 // index-block shards: the once-per-step exchange, in place, on the handle's stream
 int exchange(NbodyHandle* h, State& s) {
     if (s.sh.n_seg == 1 && !h->comm_ready) return NBODY_OK;
-    if (!h->comm_ready) return fail(h, NBODY_ERR_COMM, "world_size > 1 but nbody_comm_init has not been called");
-    int rc = h->tp->group_begin();
-    if (!rc) rc = h->tp->all_gather(s.sh.pos_all, size_t(s.sh.seg_cap) * sizeof(double4), h->stream);
-    if (!rc) rc = h->tp->all_gather(s.sh.seg_count, sizeof(int), h->stream);
-    if (!rc) rc = h->tp->group_end();
-    if (rc) return fail(h, rc, "f64 exchange: " + h->tp->error());
-    return NBODY_OK;
+    return engine::gather_blocks(h, s, h->stream);
 }
 
 int step_impl(NbodyHandle* h, State& s, double dt) {
@@ -424,12 +410,14 @@ int step_impl(NbodyHandle* h, State& s, double dt) {
 
 }  // namespace
 
+EngineBodies<double>& bodies(NbodyHandle* h) { return *h->f64; }
+const EngineBodies<double>& bodies(const NbodyHandle* h) { return *h->f64; }
+
 int create(NbodyHandle* h) {
     State* sp = new State();
     h->f64 = sp;
     State& s = *sp;
-    s.sh.n_seg = h->sh.n_seg; s.sh.my_seg = h->sh.my_seg; s.sh.seg_cap = h->sh.seg_cap;   // (index blocks: nbody_api.cpp create_impl)
-    int rc = s.alloc(h, h->stream);
+    int rc = s.alloc(h, h->stream, h->shape);
     if (rc) return rc;
     if (h->cfg.method == NBODY_BARNES_HUT) { rc = s.tree.alloc_host(h, s.sh); if (rc) return rc; }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -472,34 +460,19 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
 }
 
 int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
-    State& s = *h->f64;
-    int rc = s.upload_blocks(h, h->stream, aos, n, stride, &h->first_global);
-    h->n_at_upload = s.n_local;
-    s.hm_valid = false;
-    return rc;
+    h->f64->hm_valid = false;
+    return engine::upload(h, *h->f64, aos, n, stride);
 }
 
 int download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out) {
     return h->f64->download_own(h, h->stream, aos, cap, stride, n_out, nullptr);
 }
 
-int count(NbodyHandle* h, size_t* n_out) {
-    State& s = *h->f64;
-    int rc = s.sync_count(h, h->stream);
-    if (rc) return rc;
-    *n_out = s.n_local;
-    return NBODY_OK;
-}
+int count(NbodyHandle* h, size_t* n_out) { return engine::count(h, *h->f64, n_out); }
 
-int count_global(NbodyHandle* h, size_t* n_out) {   // as of the last exchange
-    State& s = *h->f64;
-    s.count_dirty = true;
-    int rc = s.sync_count(h, h->stream);
-    if (rc) return rc;
-    size_t t = 0;
-    for (int c : s.seg_count_host) t += size_t(c);
-    *n_out = t;
-    return NBODY_OK;
+int count_global(NbodyHandle* h, size_t* n_out) {
+    h->f64->count_dirty = true;   // (the exchange wrote the other blocks' counts behind the host's back)
+    return engine::count_global(h, *h->f64, n_out);
 }
 
 namespace {
@@ -546,20 +519,9 @@ int set_settings(NbodyHandle* h, double g, double g_soft, double dt, double thet
     return NBODY_OK;
 }
 
-int get_settings(const NbodyHandle* h, double* g, double* g_soft, double* dt, double* theta2) {
-    h->f64->get_settings(g, g_soft, dt, theta2);
-    return NBODY_OK;
-}
-
 int set_bounds(NbodyHandle* h, const double center[3], double width) {
     h->f64->set_bounds(center, width);
     return NBODY_OK;
-}
-
-void get_bounds(const NbodyHandle* h, double center[3], double* width) {
-    const State& s = *h->f64;
-    std::memcpy(center, s.center, sizeof(s.center));
-    *width = s.width;
 }
 
 int init(NbodyHandle* h) {
@@ -697,8 +659,6 @@ int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, do
 }
 
 int get_integrator(const NbodyHandle* h) { return h->f64->integrator; }
-const nbody::ShardT<double>& shard(const NbodyHandle* h) { return h->f64->sh; }
-size_t n_upper(const NbodyHandle* h) { return h->f64->n_local; }
 
 int download_jerk(NbodyHandle* h, double* jerk3, size_t cap, size_t* n_out) {
     State& s = *h->f64;
@@ -737,56 +697,17 @@ int suggest_dt(NbodyHandle* h, double eta, double* dt_out) {
     return NBODY_OK;
 }
 
-double elapsed(const NbodyHandle* h) { return h->f64->elapsed; }
-
-int stats(NbodyHandle* h, NbodyStats* out) {
-    State& s = *h->f64;
-    if (h->cfg.method == NBODY_BRUTE_FORCE) {
-        unsigned long long* hv = reinterpret_cast<unsigned long long*>(h->h_poison + kScratchStats);
-        HIP_TRY(h, hipMemcpyAsync(hv, s.sh.inter, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->stats.interactions = *hv;
-    }
-    if (h->d_counters) {
-        HIP_TRY(h, hipMemcpyAsync(h->h_counters, h->d_counters, 2 * NBODY_WALK_COUNTER_SLOTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        unsigned long long acc_sum = 0, vis_sum = 0;
-        for (unsigned k = 0; k < NBODY_WALK_COUNTER_SLOTS; ++k) { acc_sum += h->h_counters[2 * k]; vis_sum += h->h_counters[2 * k + 1]; }
-        h->stats.interactions = acc_sum;
-        h->stats.force_kernel_interactions = acc_sum;
-        h->stats.node_visits = vis_sum;
-    }
-    *out = h->stats;
-    return NBODY_OK;
-}
+int stats(NbodyHandle* h, NbodyStats* out) { return engine::stats(h, *h->f64, out); }
 
 int reset_stats(NbodyHandle* h) {
-    State& s = *h->f64;
-    HIP_TRY(h, hipMemsetAsync(s.sh.inter, 0, sizeof(unsigned long long), h->stream));
-    s.blk_steps = 0; s.blk_updates = 0;
-    return NBODY_OK;
+    h->f64->blk_steps = 0; h->f64->blk_updates = 0;
+    return engine::reset_stats(h, *h->f64);
 }
 
 int energy(NbodyHandle* h, double* kinetic, double* potential) {
     State& s = *h->f64;
     if (s.sh.n_seg > 1) return fail(h, NBODY_ERR_INVALID, "nbody_energy on a sharded f64 world is not supported (a rank holds the velocities of its own block only)");
-    int rc = s.sync_count(h, h->stream);
-    if (rc) return rc;
-    const size_t n = s.n_local;
-    const size_t blocks = (n + 255) / 256;
-    double ke = 0.0, pe = 0.0;
-    if (blocks) {
-        HIP_TRY(h, grow_dev(h, s.d_energy, s.energy_blocks, blocks, 2 * sizeof(double), Grow::exact));
-        launch_energy(h->stream, s.sh, int(n), s.g_soft * s.g_soft, s.d_energy);
-        HIP_TRY(h, hipGetLastError());
-        std::vector<double> part(blocks * 2);
-        HIP_TRY(h, hipMemcpyAsync(part.data(), s.d_energy, blocks * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        for (size_t b = 0; b < blocks; ++b) { ke += part[2 * b]; pe += part[2 * b + 1]; }
-    }
-    if (kinetic) *kinetic = ke;
-    if (potential) *potential = -0.5 * s.g * pe;  // every unordered pair was met twice
-    return NBODY_OK;
+    return engine::energy(h, s, kinetic, potential);
 }
 
 // nbody_potentials / nbody_energy_world on an f64 handle (nbody_f32.cpp potentials_device is the f32 twin and has the contract)
@@ -795,33 +716,16 @@ int potentials_device(NbodyHandle* h, int mode, size_t* n_own, nbody::PotBodies*
     if (mode == NBODY_POTENTIAL_TREE && !s.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     int rc = exchange(h, s);   // sharded: every block's current positions and live count
     if (rc) return rc;
-    const size_t saved_n = s.n_local;
-    const bool saved_dirty = s.count_dirty;
-    const std::vector<int> saved_upper = s.seg_count_host;
-    s.count_dirty = true;
-    rc = s.sync_count(h, h->stream);
-    if (!rc) rc = nbody::pot::begin(h, size_t(s.sh.seg_cap));
-    bodies->pos_all = s.sh.pos_all; bodies->vel = s.sh.vel; bodies->seg_count = s.sh.seg_count;
-    bodies->f64 = 1; bodies->n_seg = s.sh.n_seg; bodies->seg_cap = s.sh.seg_cap; bodies->my_seg = s.sh.my_seg;
-    bodies->world = s.sh.n_seg;
-    *g = s.g;
+    engine::PotView<double> view(s);   // (the host's view of the counts: exact for the call, put back when it ends)
+    rc = view.begin(h, bodies, g);
     if (!rc && mode == NBODY_POTENTIAL_PAIRS) {
-        size_t tot = 0;
-        for (int c : s.seg_count_host) tot += size_t(c);
-        if (!field) rc = nbody::pot::pairs(h, *bodies, s.n_local, tot - s.n_local, s.g_soft * s.g_soft);
+        if (!field) rc = nbody::pot::pairs(h, *bodies, s.n_local, engine::total_upper(s) - s.n_local, s.g_soft * s.g_soft);
     } else if (!rc) {
         PotWalkScope walking(h->pot, field ? kWalkField : kWalkPotentials);
         rc = bh_forces(h, s);
     }
     *n_own = s.n_local;
-    s.n_local = saved_n; s.count_dirty = saved_dirty; s.seg_count_host = saved_upper;
-    if (rc) return rc;
-    if (h->tp) { rc = h->tp->check(); if (rc) return fail(h, rc, h->tp->error()); }
-    return NBODY_OK;
-}
-
-int tree_export(NbodyHandle* h, double* com_mass, double* width, int32_t* skip, size_t cap, size_t* n_nodes) {
-    return h->f64->tree.export_nodes(h, com_mass, width, skip, cap, n_nodes);
+    return rc ? rc : comm_check(h);
 }
 
 }  // namespace nbody64

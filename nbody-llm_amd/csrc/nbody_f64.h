@@ -4,7 +4,11 @@
 
 namespace nbody64 {
 
-int create(NbodyHandle* h);                                   // after the stream (and, for Barnes-Hut, pool + counters) exist
+// the bodies, their settings and the tree of an f64 handle (a base of nbody_f64.cpp's State)
+EngineBodies<double>& bodies(NbodyHandle* h);
+const EngineBodies<double>& bodies(const NbodyHandle* h);
+
+int create(NbodyHandle* h);                                   // after the stream (and, for Barnes-Hut, pool + counters) exist and the handle has its shape
 void destroy(NbodyHandle* h);
 int clone_state(NbodyHandle* src, NbodyHandle* dst);
 int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride);
@@ -14,15 +18,12 @@ int count_global(NbodyHandle* h, size_t* n_out);
 int add_point(NbodyHandle* h, const void* particle);
 int remove_point(NbodyHandle* h, size_t index);
 int merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size_t cap, size_t* n_contacts);   // nbody_pairs.h, + a removal's bookkeeping
-int set_settings(NbodyHandle* h, double g, double g_soft, double dt, double theta2);
-int get_settings(const NbodyHandle* h, double* g, double* g_soft, double* dt, double* theta2);
+int set_settings(NbodyHandle* h, double g, double g_soft, double dt, double theta2);   // (the setters and init invalidate the Hermite state)
 int set_bounds(NbodyHandle* h, const double center[3], double width);
-void get_bounds(const NbodyHandle* h, double center[3], double* width);
 int init(NbodyHandle* h);
 int step_by(NbodyHandle* h, double dt);
 int steps(NbodyHandle* h, int k);
 int update_forces(NbodyHandle* h);
-double elapsed(const NbodyHandle* h);
 int stats(NbodyHandle* h, NbodyStats* out);
 int reset_stats(NbodyHandle* h);
 int energy(NbodyHandle* h, double* kinetic, double* potential);
@@ -37,8 +38,5 @@ int get_block_steps(const NbodyHandle* h, double* eta, int* max_level);
 int download_levels(NbodyHandle* h, int32_t* level, size_t cap, size_t* n_out);
 int block_step_counts(NbodyHandle* h, uint64_t out[2]);
 int debug_hermite_forces_of(NbodyHandle* h, const int32_t* ids, size_t n_ids, double* acc3, double* jerk3);
-const nbody::ShardT<double>& shard(const NbodyHandle* h);    // the bodies on the device (nbody_external_potentials reads them)
-size_t n_upper(const NbodyHandle* h);   // the host's view of the own body count, an upper bound after a retain (nbody_moments sizes its launches from it)
-int tree_export(NbodyHandle* h, double* com_mass, double* width, int32_t* skip, size_t cap, size_t* n_nodes);
 
 }  // namespace nbody64

@@ -1,6 +1,6 @@
 // nbody_field.cpp -- nbody_field_at and nbody_tidal_at behind the preparation they share with nbody_potentials: the batches.
 #include "nbody_field.h"
-#include "nbody_f64.h"
+#include "nbody_engine.h"
 
 #include <algorithm>
 
@@ -35,13 +35,12 @@ int run(NbodyHandle* h, int mode, const PotBodies& b, double g, const double* xy
     const ProbeTerm term = tidal ? (vec ? ProbeTerm::Tidal : ProbeTerm::TidalCount)
                                  : vec && phi ? ProbeTerm::Field : vec ? ProbeTerm::FieldAcc : phi ? ProbeTerm::FieldPhi : ProbeTerm::FieldCount;
     const size_t per = probe_sums(term);   // doubles per plane row and per probe of d_out
-    double g_soft = double(h->g_soft), theta2 = double(h->theta2), center[3] = {double(h->center[0]), double(h->center[1]), double(h->center[2])};
-    double width = double(h->width);
-    if (b.f64) {
-        double g64 = 0.0, dt = 0.0;
-        nbody64::get_settings(h, &g64, &g_soft, &dt, &theta2);
-        nbody64::get_bounds(h, center, &width);
-    }
+    double g_soft = 0.0, theta2 = 0.0, center[3] = {0.0, 0.0, 0.0}, width = 0.0;
+    with_bodies(h, [&](const auto& st) {   // the settings and the root box of the handle's store, widened
+        g_soft = double(st.g_soft); theta2 = double(st.theta2); width = double(st.width);
+        std::copy(st.center, st.center + 3, center);
+        return 0;
+    });
     const size_t n_bodies = size_t(b.seg_cap) * size_t(b.n_seg);   // (an upper bound is all the slice count needs)
     // once per call: the walk's segments (the force pass drew them from n_points), or the pair kernel's slices
     const size_t first_batch = std::min(n_points, kFieldBatch);
@@ -68,10 +67,10 @@ int run(NbodyHandle* h, int mode, const PotBodies& b, double g, const double* xy
             } else if (b.f64) {
                 nbody64::launch_bh_probe_walk(h->stream, term, ft, f.d_xyz, idx, n, g_soft * g_soft, theta2, f.d_planes, stride, p.d_counts);
             } else if (f.quad && !tidal) {
-                launch_bh_field_walk_quad(h->stream, ft, f.quad, f.d_xyz, idx, n, h->g_soft * h->g_soft, h->theta2, (vec ? 1 : 0) | (phi ? 2 : 0),
+                launch_bh_field_walk_quad(h->stream, ft, f.quad, f.d_xyz, idx, n, float(g_soft) * float(g_soft), float(theta2), (vec ? 1 : 0) | (phi ? 2 : 0),
                                           reinterpret_cast<double4*>(f.d_planes), stride, p.d_counts);
             } else {
-                launch_bh_probe_walk(h->stream, term, ft, f.d_xyz, idx, n, h->g_soft * h->g_soft, h->theta2, f.d_planes, stride, p.d_counts);
+                launch_bh_probe_walk(h->stream, term, ft, f.d_xyz, idx, n, float(g_soft) * float(g_soft), float(theta2), f.d_planes, stride, p.d_counts);
             }
             launch_probe_reduce(h->stream, term, f.d_planes, K, stride, idx, n, g, d_vec, d_phi);
         }

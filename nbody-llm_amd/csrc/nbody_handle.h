@@ -1,4 +1,5 @@
-// nbody_handle.h -- the handle behind include/nbody_hip.h (internal to libnbody_hip.so).
+// nbody_handle.h -- the handle behind include/nbody_hip.h (internal to libnbody_hip.so).  The handle itself holds nothing of a
+// precision: the bodies, their settings and the tree are its engine's (EngineBodies<F> below; nbody_f32.h / nbody_f64.h bodies(h)).
 #pragma once
 #include "../../include/nbody_hip.h"
 #include "kernels.h"
@@ -244,7 +245,11 @@ struct FieldBufs {
     size_t planes_cap = 0;                    // doubles
 };
 
-// ---- the body vector of a handle, once for F = f32 (a base of NbodyHandle) and F = f64 (a base of nbody64::State): the
+// how a handle's bodies are sharded (NbodyHandle::shape, drawn by nbody_api.cpp create_impl): index blocks, or the one
+// segment of a spatial rank
+struct ShardShape { int n_seg = 1, my_seg = 0, seg_cap = 0; };
+
+// ---- the body vector of a handle, for F = f32 and F = f64 (a base of EngineBodies<F> below): the
 // device arrays, the host's view of them, the settings, and the Vec-like operations that do not depend on how the forces are
 // computed.  The members take the handle (for errors) and the stream they enqueue on.
 
@@ -312,8 +317,9 @@ struct BodyStore {
     F* h_aos = nullptr;        // pinned host staging
     size_t aos_cap = 0;        // records
 
-    // the arrays of sh for its n_seg / seg_cap / my_seg (shard_alloc: the caller synchronises) and the pinned counts
-    int alloc(NbodyHandle* h, hipStream_t s) {
+    // the arrays of sh in the handle's shape (shard_alloc: the caller synchronises) and the pinned counts
+    int alloc(NbodyHandle* h, hipStream_t s, const ShardShape& shape) {
+        sh.n_seg = shape.n_seg; sh.my_seg = shape.my_seg; sh.seg_cap = shape.seg_cap;
         const int rc = shard_alloc(h, s, sh, true);
         if (rc) return rc;
         HIP_TRY(h, mem_of(h).pin(h_counts, size_t(sh.n_seg) * sizeof(int)));
@@ -468,7 +474,7 @@ struct BodyStore {
     }
 };
 
-// ---- the Barnes-Hut tree of a handle, once for F = f32 (NbodyHandle::tree) and F = f64 (nbody64::State::tree): the host build's
+// ---- the Barnes-Hut tree of a handle, for F = f32 and F = f64 (EngineBodies<F>::tree): the host build's
 // tree, the node and order arrays the walks read, the device build's buffers, the walk's node-range split and the strict walk's
 // stack, with the two procedures that fill them.  What walks the tree stays per precision (TreeDev, WalkSplit64 and their kernels).
 template <class F> struct TreeTypes;
@@ -538,6 +544,15 @@ struct TreeStore {
     int export_nodes(NbodyHandle* h, F* com_mass, F* width, int32_t* skip, size_t cap, size_t* n_out);
 };
 
+// ---- what both engines keep per precision: nbody32::State and nbody64::State derive from it and keep the rest private to
+// their translation units; every other unit reaches it through nbody32::bodies(h) / nbody64::bodies(h)
+template <class F>
+struct EngineBodies : BodyStore<F> {
+    TreeStore<F> tree;           // Barnes-Hut: the tree, its device arrays, the device build's buffers, the walk's split and stack
+    double* d_energy = nullptr;  // nbody_energy: per-block {KE, pair sum}
+    size_t energy_blocks = 0;
+};
+
 // nbody_tracers_* (nbody_tracer.cpp): massless particles beside the bodies.  Their state is a second Shard of one segment, so
 // the integrate and compact kernels run on it unchanged; n_host == 0 (no tracers) keeps every step path as it was.
 struct TracerState {
@@ -566,19 +581,17 @@ struct ExternalField {
     NbodyExternalComponent given[NBODY_EXTERNAL_MAX] = {};
 };
 
-struct NbodyHandle : BodyStore<float> {
+struct NbodyHandle {
     nbody::HandleMem mem{kHipSeam};   // every device and pinned block of this handle, its f64 / spatial state included
     NbodyConfig cfg{};
     nbody::Tuning tune;        // this handle's launch-shape and scheme knobs (nbody_set_tuning; NBODY_* environment at create)
     int device = 0;
     hipStream_t stream = nullptr;
-    // (BodyStore<float>: sh, the settings and bounds, n_local / count_dirty / seg_count_host / h_counts, the AoS staging;
-    // an f64 handle keeps its bodies in nbody64::State's BodyStore<double> and leaves this one's arrays null)
+    ShardShape shape;          // the bodies themselves: f32 / f64 below
     size_t first_global = 0, n_at_upload = 0;   // the own index block at the last upload (both precisions)
 
     // Barnes-Hut
     std::unique_ptr<nbody::WorkerPool> pool;
-    TreeStore<float> tree;       // the tree, its device arrays, the device build's buffers, the walk's split and stack
     unsigned long long* d_counters = nullptr;  // [NBODY_WALK_COUNTER_SLOTS][2] accepted, visited (summed on read)
     // nbody_set_multipole: order of the force walk's expansion; 2 = the cells' quadrupole tensors beside the node records
     int multipole = NBODY_MULTIPOLE_MONOPOLE;
@@ -610,9 +623,9 @@ struct NbodyHandle : BodyStore<float> {
     hipEvent_t ev_drifted = nullptr, ev_gathered = nullptr;
     bool exchange_in_flight = false;
 
-    // what each engine keeps beside the above, private to its translation unit
-    nbody32::State* f32 = nullptr;   // NbodyConfig.dtype == NBODY_F32: the force passes' plans and planes, the step chain's flags
-    nbody64::State* f64 = nullptr;   // NbodyConfig.dtype == NBODY_F64: the whole state lives here
+    // the engine of the handle's precision: its EngineBodies<F> and what it keeps beside them, private to its translation unit
+    nbody32::State* f32 = nullptr;   // NbodyConfig.dtype == NBODY_F32
+    nbody64::State* f64 = nullptr;   // NbodyConfig.dtype == NBODY_F64
     nbody::let::State* let = nullptr; // NbodyConfig.shard_mode == NBODY_SHARD_SPATIAL (beside f32): the halo-exchange machinery
 
     std::string err;

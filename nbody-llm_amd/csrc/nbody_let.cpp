@@ -20,6 +20,7 @@
 // Production (`step`) does the exchanges through the handle's transport on its stream; the tests also run G handles of one
 // process on one GPU and do them as device-to-device copies (debug_phase / debug_exchange) -- same kernels, same buffers.
 #include "nbody_let.h"
+#include "nbody_f32.h"
 #include "kernels_let.h"
 #include "nbody_pot.h"
 
@@ -158,7 +159,8 @@ template <class T> int dev_alloc(NbodyHandle* h, T** p, size_t n) {
 }
 
 int ensure_node_buffers(NbodyHandle* h, State& s) {
-    const Shard& sh = h->sh;
+    auto& b = nbody32::bodies(h);
+    const Shard& sh = b.sh;
     const int want_local = 4 * sh.seg_cap + 64;
     if (s.local_cap < want_local) {   // (seven blocks under one cap: each replaces its old one; a failure leaves the cap, so the next pass starts over)
         int rc;
@@ -219,44 +221,47 @@ int ensure_let_send(NbodyHandle* h, State& s, size_t need) {
 
 // ---- the phases (everything is enqueued on h->stream; nothing here waits for the device)
 int phase0(NbodyHandle* h, State& s, float dt, bool drift) {
-    Shard& sh = h->sh;
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
     PhaseTimer timer(h, s, 0);
     int rc = ensure_node_buffers(h, s);
     if (rc) return rc;
     if (drift) {
-        if (!h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
-        launch_drift_half(h->stream, sh, int(h->n_local), dt, h->bnd);   // integrate_pre_force
+        if (!b.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+        launch_drift_half(h->stream, sh, int(b.n_local), dt, b.bnd);   // integrate_pre_force
     }
-    launch_classify(h->stream, sh, int(h->n_local), h->center, h->width, s.d_bounds, s.G, s.me, s.d_dest_of, s.d_send_mig, s.d_send_count,
+    launch_classify(h->stream, sh, int(b.n_local), b.center, b.width, s.d_bounds, s.G, s.me, s.d_dest_of, s.d_send_mig, s.d_send_count,
                     s.d_send_off, s.d_mig_cursor, drift);
     s.mig_in = 0;
-    launch_compact(h->stream, sh, int(h->n_local));                      // retain, and the emigrants leave
-    h->count_dirty = true;
+    launch_compact(h->stream, sh, int(b.n_local));                      // retain, and the emigrants leave
+    b.count_dirty = true;
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
 }
 
 // slots_in >= 0: the immigrants sit in receive slots of the predicted sizes (launch_append_slots); -1: packed, s.mig_in of them
 int phase1(NbodyHandle* h, State& s, int slots_in = -1) {
-    Shard& sh = h->sh;
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
     PhaseTimer timer(h, s, 1);
     if (slots_in >= 0) launch_append_slots(h->stream, sh, s.d_recv_mig, slots_in, s.d_mig_matrix, s.d_pred, s.G, s.me, s.d_flags, s.d_new_count, s.d_send_count);
     else launch_append(h->stream, sh, s.d_recv_mig, s.mig_in, s.G, s.d_flags, s.d_new_count, s.d_send_count);
     // the host's bound of the own count: what was there before the retain + what arrived
-    h->n_local = std::min<size_t>(size_t(sh.seg_cap), h->n_local + size_t(s.mig_in));
-    if (tree_sort_keys(h->stream, sh.own_pos(), sh.own_count(), int(h->n_local), h->center, h->width, s.d_ws, s.ws_cap, s.d_tree_info, &s.work) != 0)
+    b.n_local = std::min<size_t>(size_t(sh.seg_cap), b.n_local + size_t(s.mig_in));
+    if (tree_sort_keys(h->stream, sh.own_pos(), sh.own_count(), int(b.n_local), b.center, b.width, s.d_ws, s.ws_cap, s.d_tree_info, &s.work) != 0)
         return fail(h, NBODY_ERR_HIP, "device octree build: rocPRIM call failed");
-    launch_ends(h->stream, sh, int(h->n_local), s.work.keys, s.work.ids, s.d_box_ord, s.d_weight_sum, s.d_ends + s.me);
+    launch_ends(h->stream, sh, int(b.n_local), s.work.keys, s.work.ids, s.d_box_ord, s.d_weight_sum, s.d_ends + s.me);
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
 }
 
 int phase2(NbodyHandle* h, State& s) {
-    Shard& sh = h->sh;
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
     PhaseTimer timer(h, s, 2);
     launch_edges(h->stream, s.d_ends, s.G, s.me, s.d_edge);
     // delta, the scans: how many nodes my slice has, every body's first node, the prefix sums the spanning cells need
-    if (tree_scan_sorted(h->stream, sh.own_pos(), sh.own_count(), int(h->n_local), s.d_ws, s.ws_cap, s.d_tree_info, s.d_edge, sh.acc) != 0)
+    if (tree_scan_sorted(h->stream, sh.own_pos(), sh.own_count(), int(b.n_local), s.d_ws, s.ws_cap, s.d_tree_info, s.d_edge, sh.acc) != 0)
         return fail(h, NBODY_ERR_HIP, "device octree build failed");
     launch_contrib(h->stream, sh, s.work, s.d_tree_info, s.d_ends, s.d_edge, s.G, s.me, s.d_rb + s.me, s.by_work, s.d_flags);
     HIP_TRY(h, hipGetLastError());
@@ -264,17 +269,18 @@ int phase2(NbodyHandle* h, State& s) {
 }
 
 int phase3(NbodyHandle* h, State& s) {
-    Shard& sh = h->sh;
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
     PhaseTimer timer(h, s, 3);
     HIP_TRY(h, hipMemsetAsync(s.d_let_count, 0, sizeof(int) * s.G, h->stream));
     launch_offsets(h->stream, s.d_rb, s.G, s.d_offsets, s.d_flags, s.rebalance ? s.d_bounds : s.d_bounds_scratch);
     // my slice of the world's node array, with local indices and links (the wire and the assembly shift them)
-    if (tree_emit_nodes(h->stream, sh.own_pos(), sh.own_count(), int(h->n_local), h->width, s.d_ws, s.ws_cap, s.d_slice, s.local_cap, s.local_cap,
+    if (tree_emit_nodes(h->stream, sh.own_pos(), sh.own_count(), int(b.n_local), b.width, s.d_ws, s.ws_cap, s.d_slice, s.local_cap, s.local_cap,
                         s.d_order, s.d_tree_info, 0, s.d_edge, s.d_zero, s.d_parent, s.d_depth) != 0)
         return fail(h, NBODY_ERR_HIP, "device octree build failed");
-    launch_finalize(h->stream, s.d_rb, s.d_ends, s.G, s.me, h->width, s.d_slice, s.d_offsets, s.d_top_index, s.d_top_nodes);
+    launch_finalize(h->stream, s.d_rb, s.d_ends, s.G, s.me, b.width, s.d_slice, s.d_offsets, s.d_top_index, s.d_top_nodes);
     launch_flags_and_pack(h->stream, s.local_cap, s.d_tree_info, s.d_edge, s.d_slice, s.d_top_nodes, s.d_offsets, s.d_top_index, s.d_ends, s.G, s.me,
-                          h->theta2, s.d_parent, s.d_depth, s.d_upper_ok, s.d_node_flags, s.d_node_mask, s.d_block_n, s.d_let_count, s.d_list_first,
+                          b.theta2, s.d_parent, s.d_depth, s.d_upper_ok, s.d_node_flags, s.d_node_mask, s.d_block_n, s.d_let_count, s.d_list_first,
                           s.d_let_send, s.let_send_cap, s.prune);
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
@@ -282,13 +288,14 @@ int phase3(NbodyHandle* h, State& s) {
 
 // the walk over the assembled array (+ kick + half drift when this is a step)
 int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = false) {
-    Shard& sh = h->sh;
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
     PhaseTimer timer(h, s, 4);
     // the walk's shape for this many bodies (kernels.h walk_plan): bodies per lane inside launch_bh_walk, node-range segments here
     // -- a rank with 10^5-10^6 bodies is a few thousand waves at one segment, not enough to fill the chip
     const bool fast = h->cfg.math_mode != NBODY_MATH_STRICT;
-    int K = h->n_local > 0 ? walk_plan(h->n_local, fast, kMaxSplit, h->theta2).segments : 1;
-    while (K > 1 && size_t(K) * 16 > h->n_local) K /= 2;   // (a tree has at least as many nodes as bodies; tiny ranks walk in one piece)
+    int K = b.n_local > 0 ? walk_plan(b.n_local, fast, kMaxSplit, b.theta2).segments : 1;
+    while (K > 1 && size_t(K) * 16 > b.n_local) K /= 2;   // (a tree has at least as many nodes as bodies; tiny ranks walk in one piece)
     // the nodes this rank holds, in global-index order, links = positions; first[] of the unsplit walk = {0, nodes held}
     {
         size_t staged_upper = 0;
@@ -299,13 +306,13 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = fals
     }
     TreeDev td;
     td.nodes = s.d_held; td.n_nodes = int(std::min<size_t>(s.held_cap, 0x7fffffff));
-    td.order = s.d_order; td.n_order = int(h->n_local);
+    td.order = s.d_order; td.n_order = int(b.n_local);
     td.n_order_dev = sh.own_count();
     td.poison = s.d_flags;
     td.store_work = 1;
     td.n_split = K;
     if (K > 1) {
-        const size_t stride = (h->n_local + 1023) / 1024 * 1024;
+        const size_t stride = (b.n_local + 1023) / 1024 * 1024;
         if (size_t(K) * stride > s.walk_planes_cap)   // (an eighth of headroom: the size asked for is the size taken)
             HIP_TRY(h, grow_dev(h, s.d_walk_planes, s.walk_planes_cap, size_t(K) * stride + size_t(K) * stride / 8, sizeof(float4), Grow::exact));
         // the segments start at global node indices total k / K (launch_assemble found where those fall in the held array); their
@@ -322,19 +329,19 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = fals
         td.split_anc = s.d_split + 2;
     }
     if (potentials) {   // nbody_potentials(NBODY_POTENTIAL_TREE): the held nodes and split points of the force walk, walked for potentials
-        const size_t stride = (std::max<size_t>(h->n_local, 1) + 63) / 64 * 64;
+        const size_t stride = (std::max<size_t>(b.n_local, 1) + 63) / 64 * 64;
         int rc = pot::ensure_planes(h, size_t(K) * stride);
         if (rc) return rc;
-        launch_bh_pot_walk(h->stream, sh.own_pos(), td, h->g_soft * h->g_soft, h->theta2, h->pot.d_planes, stride, h->pot.d_sum, h->pot.d_counts);
+        launch_bh_pot_walk(h->stream, sh.own_pos(), td, b.g_soft * b.g_soft, b.theta2, h->pot.d_planes, stride, h->pot.d_sum, h->pot.d_counts);
         HIP_TRY(h, hipGetLastError());
         return NBODY_OK;
     }
     int kicked = 0;
-    launch_bh_walk(h->stream, sh, td, h->g, h->g_soft * h->g_soft, h->theta2, fast ? 1 : 0, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
+    launch_bh_walk(h->stream, sh, td, b.g, b.g_soft * b.g_soft, b.theta2, fast ? 1 : 0, h->d_counters, h->cfg.leaf_mode == NBODY_LEAF_DIRECT,
                    kick ? &dt : nullptr, &kicked);
     if (kick) {
-        if (!kicked) launch_kick_drift(h->stream, sh, int(h->n_local), dt);   // integrate_after_force (K > 1: it rode in the plane reduction)
-        h->elapsed += dt;
+        if (!kicked) launch_kick_drift(h->stream, sh, int(b.n_local), dt);   // integrate_after_force (K > 1: it rode in the plane reduction)
+        b.elapsed += dt;
         h->stats.steps += 1;
     }
     HIP_TRY(h, hipGetLastError());
@@ -345,6 +352,7 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = fals
 }  // namespace
 
 int create(NbodyHandle* h) {
+    auto& b = nbody32::bodies(h);
     State* sp = new State();
     h->let = sp;
     State& s = *sp;
@@ -381,7 +389,7 @@ int create(NbodyHandle* h) {
     if ((rc = dev_alloc(h, &s.d_upper_ok, kLevels))) return rc;
     if ((rc = dev_alloc(h, &s.d_let_count, size_t(s.G)))) return rc;
     if ((rc = dev_alloc(h, &s.d_let_matrix, size_t(s.G) * s.G))) return rc;
-    if ((rc = dev_alloc(h, &h->sh.ids, size_t(h->sh.seg_cap)))) return rc;
+    if ((rc = dev_alloc(h, &b.sh.ids, size_t(b.sh.seg_cap)))) return rc;
     HIP_TRY(h, h->mem.pin(s.h_pin, (size_t(report_ints(s.G)) + 64) * sizeof(int)));
     if ((rc = dev_alloc(h, &s.d_report, size_t(report_ints(s.G))))) return rc;
     if ((rc = dev_alloc(h, &s.d_pred, size_t(s.G) * s.G))) return rc;
@@ -394,7 +402,7 @@ int create(NbodyHandle* h) {
     HIP_TRY(h, h->mem.pin(s.h_in_pin, size_t(s.G) * sizeof(int)));
     HIP_TRY(h, h->mem.pin(s.h_pred_pin, size_t(s.G) * s.G * sizeof(int)));
     s.h_pred.assign(size_t(s.G) * s.G, 0);
-    h->sh.poison = s.d_flags;   // a raised flag stops every kernel that would change the state
+    b.sh.poison = s.d_flags;   // a raised flag stops every kernel that would change the state
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NBODY_OK;
 }
@@ -402,7 +410,7 @@ int create(NbodyHandle* h) {
 void destroy(NbodyHandle* h) {
     State* s = h->let;
     if (!s) return;
-    h->sh.poison = nullptr;   // (it pointed into this state; the blocks themselves are the handle's registry's)
+    nbody32::bodies(h).sh.poison = nullptr;   // (it pointed into this state; the blocks themselves are the handle's registry's)
     if (s->ev_made) for (auto& set : s->ev) for (hipEvent_t e : set) (void)hipEventDestroy(e);
     delete s;
     h->let = nullptr;
@@ -410,16 +418,17 @@ void destroy(NbodyHandle* h) {
 
 // Every rank passes the same full vector.  Bounds = the G-quantiles of the keys; this rank keeps the bodies of its range.
 int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
+    auto& b = nbody32::bodies(h);
     State& s = *h->let;
-    Shard& sh = h->sh;
-    if (!h->bounds_set) return fail(h, NBODY_ERR_INVALID, "NBODY_SHARD_SPATIAL: nbody_set_bounds must come before nbody_upload (the shards are key ranges of the root box)");
+    Shard& sh = b.sh;
+    if (!b.bounds_set) return fail(h, NBODY_ERR_INVALID, "NBODY_SHARD_SPATIAL: nbody_set_bounds must come before nbody_upload (the shards are key ranges of the root box)");
     const char* src = static_cast<const char*>(aos);
     std::vector<unsigned long long> key(n);
     std::vector<uint32_t> idx(n);
     for (size_t k = 0; k < n; ++k) {
         float p[3];
         std::memcpy(p, src + k * stride, 12);
-        key[k] = host_key(p, h->center, h->width);
+        key[k] = host_key(p, b.center, b.width);
         idx[k] = uint32_t(k);
     }
     std::sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return key[a] != key[b] ? key[a] < key[b] : a < b; });
@@ -438,32 +447,33 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
     if (own.size() > size_t(sh.seg_cap)) return fail(h, NBODY_ERR_CAPACITY, "NBODY_SHARD_SPATIAL: this rank's key range holds more bodies than its capacity");
     const size_t m = own.size();
     // staging through the handle's AoS buffers (40-byte records)
-    int rc_aos = h->ensure_aos(h, std::max<size_t>(1, m));
+    int rc_aos = b.ensure_aos(h, std::max<size_t>(1, m));
     if (rc_aos) return rc_aos;
-    for (size_t j = 0; j < m; ++j) std::memcpy(h->h_aos + 10 * j, src + size_t(own[j]) * stride, 40);
-    if (m) HIP_TRY(h, hipMemcpyAsync(h->d_aos, h->h_aos, m * 40, hipMemcpyHostToDevice, h->stream));
-    launch_aos_to_soa(h->stream, h->d_aos, 10, int(m), sh.own_pos(), sh.vel, sh.acc);
+    for (size_t j = 0; j < m; ++j) std::memcpy(b.h_aos + 10 * j, src + size_t(own[j]) * stride, 40);
+    if (m) HIP_TRY(h, hipMemcpyAsync(b.d_aos, b.h_aos, m * 40, hipMemcpyHostToDevice, h->stream));
+    launch_aos_to_soa(h->stream, b.d_aos, 10, int(m), sh.own_pos(), sh.vel, sh.acc);
     if (m) HIP_TRY(h, hipMemcpyAsync(sh.ids, own.data(), m * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(sh.escaped, 0, sizeof(int), h->stream));
     HIP_TRY(h, hipMemsetAsync(s.d_send_count, 0, sizeof(int) * s.G, h->stream));
     HIP_TRY(h, hipMemsetAsync(s.d_flags, 0, 4 * sizeof(int), h->stream));
     s.have_pred = false;   // (the first step after an upload learns the migrant counts the slow way)
-    h->n_local = m;
-    h->seg_count_host[0] = int(m);
-    h->h_counts[0] = int(m);
-    HIP_TRY(h, hipMemcpyAsync(sh.seg_count, h->h_counts, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    b.n_local = m;
+    b.seg_count_host[0] = int(m);
+    b.h_counts[0] = int(m);
+    HIP_TRY(h, hipMemcpyAsync(sh.seg_count, b.h_counts, sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // own[] and the staging are reused
-    h->count_dirty = false;
+    b.count_dirty = false;
     h->first_global = 0; h->n_at_upload = m;
     return NBODY_OK;
 }
 
 int download_ids(NbodyHandle* h, int32_t* ids, size_t cap, size_t* n_out) {
-    Shard& sh = h->sh;
-    HIP_TRY(h, hipMemcpyAsync(h->h_counts, sh.seg_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
+    HIP_TRY(h, hipMemcpyAsync(b.h_counts, sh.seg_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t n = size_t(h->h_counts[0]);
-    h->n_local = n; h->seg_count_host[0] = int(n); h->count_dirty = false;
+    const size_t n = size_t(b.h_counts[0]);
+    b.n_local = n; b.seg_count_host[0] = int(n); b.count_dirty = false;
     if (n_out) *n_out = n;
     if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "download buffer too small");
     if (n && ids) {
@@ -509,8 +519,9 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
     State& a = *src->let;
     State& b = *dst->let;
     HIP_TRY(src, hipStreamSynchronize(src->stream));
-    const size_t cap = size_t(src->sh.seg_cap);
-    HIP_TRY(dst, hipMemcpyAsync(dst->sh.ids, src->sh.ids, cap * sizeof(int), hipMemcpyDeviceToDevice, dst->stream));
+    const Shard& from = nbody32::bodies(src).sh;
+    const size_t cap = size_t(from.seg_cap);
+    HIP_TRY(dst, hipMemcpyAsync(nbody32::bodies(dst).sh.ids, from.ids, cap * sizeof(int), hipMemcpyDeviceToDevice, dst->stream));
     HIP_TRY(dst, hipMemcpyAsync(b.d_bounds, a.d_bounds, (size_t(a.G) + 1) * sizeof(unsigned long long), hipMemcpyDeviceToDevice, dst->stream));
     HIP_TRY(dst, hipMemcpyAsync(b.d_ends, a.d_ends, size_t(a.G) * sizeof(EndInfo), hipMemcpyDeviceToDevice, dst->stream));   // (count_global reads it)
     HIP_TRY(dst, hipStreamSynchronize(dst->stream));
@@ -524,12 +535,13 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
 namespace {
 // exact own count + the own ids on the host (ascending copy in `sorted`)
 int fetch_ids(NbodyHandle* h, std::vector<int>& ids, std::vector<int>& sorted) {
-    Shard& sh = h->sh;
-    HIP_TRY(h, hipMemcpyAsync(h->h_counts, sh.seg_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    auto& b = nbody32::bodies(h);
+    Shard& sh = b.sh;
+    HIP_TRY(h, hipMemcpyAsync(b.h_counts, sh.seg_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->n_local = size_t(h->h_counts[0]); h->seg_count_host[0] = int(h->n_local); h->count_dirty = false;
-    ids.resize(h->n_local);
-    if (h->n_local) HIP_TRY(h, hipMemcpy(ids.data(), sh.ids, h->n_local * sizeof(int), hipMemcpyDeviceToHost));
+    b.n_local = size_t(b.h_counts[0]); b.seg_count_host[0] = int(b.n_local); b.count_dirty = false;
+    ids.resize(b.n_local);
+    if (b.n_local) HIP_TRY(h, hipMemcpy(ids.data(), sh.ids, b.n_local * sizeof(int), hipMemcpyDeviceToHost));
     sorted = ids;
     std::sort(sorted.begin(), sorted.end());
     return NBODY_OK;
@@ -547,9 +559,10 @@ int gather_ll(NbodyHandle* h, long long mine, std::vector<long long>& all) {
     return NBODY_OK;
 }
 int push_count(NbodyHandle* h) {
-    h->h_counts[0] = int(h->n_local);
-    h->seg_count_host[0] = int(h->n_local);
-    HIP_TRY(h, hipMemcpyAsync(h->sh.seg_count, h->h_counts, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    auto& b = nbody32::bodies(h);
+    b.h_counts[0] = int(b.n_local);
+    b.seg_count_host[0] = int(b.n_local);
+    HIP_TRY(h, hipMemcpyAsync(b.sh.seg_count, b.h_counts, sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return NBODY_OK;
 }
@@ -557,9 +570,10 @@ int push_count(NbodyHandle* h) {
 
 // Vec::push: the body goes to the rank whose key range holds it; its place in the vector is the next free index
 int add_point(NbodyHandle* h, const void* particle) {
+    auto& b = nbody32::bodies(h);
     State& s = *h->let;
-    Shard& sh = h->sh;
-    if (!h->bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
+    Shard& sh = b.sh;
+    if (!b.bounds_set) return fail(h, NBODY_ERR_INVALID, "nbody_set_bounds has not been called");
     std::vector<int> ids, sorted;
     int rc = fetch_ids(h, ids, sorted);
     if (rc) return rc;
@@ -570,22 +584,22 @@ int add_point(NbodyHandle* h, const void* particle) {
     std::vector<unsigned long long> bounds(size_t(s.G) + 1);
     HIP_TRY(h, hipMemcpy(bounds.data(), s.d_bounds, bounds.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     const float* p = static_cast<const float*>(particle);
-    const unsigned long long key = host_key(p, h->center, h->width);
+    const unsigned long long key = host_key(p, b.center, b.width);
     int owner = 0;
     for (int r = 1; r < s.G; ++r) if (bounds[size_t(r)] <= key) owner = r;
     long long ok = 1;
     if (owner == s.me) {
-        if (h->n_local >= size_t(sh.seg_cap)) ok = 0;
+        if (b.n_local >= size_t(sh.seg_cap)) ok = 0;
         else {
             float4 rec[3] = {make_float4(p[0], p[1], p[2], p[9]), make_float4(p[3], p[4], p[5], 0.f), make_float4(p[6], p[7], p[8], 0.f)};
             const int id32 = int(id);
-            const size_t k = h->n_local;
+            const size_t k = b.n_local;
             HIP_TRY(h, hipMemcpyAsync(sh.own_pos() + k, &rec[0], sizeof(float4), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(sh.vel + k, &rec[1], sizeof(float4), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(sh.acc + k, &rec[2], sizeof(float4), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(sh.ids + k, &id32, sizeof(int), hipMemcpyHostToDevice, h->stream));
             HIP_TRY(h, hipStreamSynchronize(h->stream));
-            h->n_local = k + 1;
+            b.n_local = k + 1;
             rc = push_count(h);
             if (rc) return rc;
         }
@@ -601,8 +615,9 @@ int add_point(NbodyHandle* h, const void* particle) {
 // Vec::swap_remove(index): `index` counts the world's bodies in the order of their indices in the vector; the body with
 // the largest index takes the removed one's place (its index), as the reference's last element does
 int remove_point(NbodyHandle* h, size_t index) {
+    auto& b = nbody32::bodies(h);
     State& s = *h->let;
-    Shard& sh = h->sh;
+    Shard& sh = b.sh;
     std::vector<int> ids, sorted;
     int rc = fetch_ids(h, ids, sorted);
     if (rc) return rc;
@@ -637,14 +652,14 @@ int remove_point(NbodyHandle* h, size_t index) {
             auto vit = std::find(ids.begin(), ids.end(), victim);
             if (vit != ids.end() && size_t(vit - ids.begin()) == at) vit = std::find(vit + 1, ids.end(), victim);
             if (vit != ids.end()) {
-                const size_t j = size_t(vit - ids.begin()), tail = h->n_local - 1;
+                const size_t j = size_t(vit - ids.begin()), tail = b.n_local - 1;
                 if (j != tail) {
                     HIP_TRY(h, hipMemcpyAsync(sh.own_pos() + j, sh.own_pos() + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
                     HIP_TRY(h, hipMemcpyAsync(sh.vel + j, sh.vel + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
                     HIP_TRY(h, hipMemcpyAsync(sh.acc + j, sh.acc + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
                     HIP_TRY(h, hipMemcpyAsync(sh.ids + j, sh.ids + tail, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
                 }
-                h->n_local = tail;
+                b.n_local = tail;
                 rc = push_count(h);
                 if (rc) return rc;
             }
@@ -654,14 +669,14 @@ int remove_point(NbodyHandle* h, size_t index) {
     }
     auto vit = std::find(ids.begin(), ids.end(), victim);
     if (vit != ids.end()) {
-        const size_t j = size_t(vit - ids.begin()), tail = h->n_local - 1;
+        const size_t j = size_t(vit - ids.begin()), tail = b.n_local - 1;
         if (j != tail) {
             HIP_TRY(h, hipMemcpyAsync(sh.own_pos() + j, sh.own_pos() + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(sh.vel + j, sh.vel + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(sh.acc + j, sh.acc + tail, sizeof(float4), hipMemcpyDeviceToDevice, h->stream));
             HIP_TRY(h, hipMemcpyAsync(sh.ids + j, sh.ids + tail, sizeof(int), hipMemcpyDeviceToDevice, h->stream));
         }
-        h->n_local = tail;
+        b.n_local = tail;
         rc = push_count(h);
         if (rc) return rc;
     }
@@ -696,6 +711,7 @@ int reset_stats(NbodyHandle* h) {
 
 // bookkeeping after a pass, from the numbers of the step's report block (rep = h_pin after the copy of d_report)
 static void account_from(NbodyHandle* h, State& s, const int* rep) {
+    auto& b = nbody32::bodies(h);
     const int G = s.G, gg = G * G;
     const int* let_m = rep;
     const int* offsets = rep + 2 * gg;
@@ -714,9 +730,9 @@ static void account_from(NbodyHandle* h, State& s, const int* rep) {
     s.st.nodes_global += uint64_t(std::max(0, offsets[G]));
     s.node_array_peak = std::max<uint64_t>(s.node_array_peak, uint64_t(std::max(0, tree_info[0])) + rec);
     h->stats.tree_nodes = uint64_t(std::max(1, offsets[G]));   // (an empty world: the reference's empty root, barnes_hut.rs:145)
-    h->n_local = size_t(std::max(0, tree_info[2]));            // the live own count (bodies in the local build)
-    h->seg_count_host[0] = int(h->n_local);
-    h->count_dirty = false;
+    b.n_local = size_t(std::max(0, tree_info[2]));            // the live own count (bodies in the local build)
+    b.seg_count_host[0] = int(b.n_local);
+    b.count_dirty = false;
     const uint64_t partners = uint64_t(std::max(0, G - 1));
     const uint64_t migrated_now = uint64_t(std::max(0, flags[2]));
     s.st.bytes_sent += sent * sizeof(LetRecord) + (migrated_now - std::min(migrated_now, s.migrated_seen)) * sizeof(Migrant) +
@@ -792,8 +808,9 @@ static int variable_round(NbodyHandle* h, State& s, const char* send, char* recv
 
 // exchange 0 with the sizes the host knows exactly (m = the migrant count matrix on the host)
 static int migrants_exact(NbodyHandle* h, State& s, const int* m) {
+    auto& b = nbody32::bodies(h);
     size_t out_at[kMaxRanks], n_out[kMaxRanks], in_at[kMaxRanks], n_in[kMaxRanks];
-    const size_t total_in = exchange_layout(m, s.G, s.me, (long long)h->sh.seg_cap, true, 0, out_at, n_out, in_at, n_in);
+    const size_t total_in = exchange_layout(m, s.G, s.me, (long long)b.sh.seg_cap, true, 0, out_at, n_out, in_at, n_in);
     int rc = ensure_mig_recv(h, s, total_in, 0);
     if (rc) return rc;
     rc = variable_round(h, s, reinterpret_cast<const char*>(s.d_send_mig), reinterpret_cast<char*>(s.d_recv_mig), sizeof(Migrant), out_at, n_out, in_at, n_in);
@@ -804,11 +821,12 @@ static int migrants_exact(NbodyHandle* h, State& s, const int* m) {
 
 // what the next step posts its migrant messages with: twice the last count and a little, the same on every rank
 static int draw_prediction(NbodyHandle* h, State& s, const int* mig_m) {
+    const long long seg_cap = nbody32::bodies(h).sh.seg_cap;
     const int G = s.G;
     size_t out_need = 0, in_need = 0;
     for (int a = 0; a < G; ++a)
         for (int b = 0; b < G; ++b) {
-            const int p = a == b ? 0 : int(std::min<long long>(2LL * std::max(0, mig_m[a * G + b]) + 32, (long long)h->sh.seg_cap));
+            const int p = a == b ? 0 : int(std::min<long long>(2LL * std::max(0, mig_m[a * G + b]) + 32, seg_cap));
             s.h_pred[size_t(a) * G + b] = p;
             if (a == s.me) out_need += size_t(p);
             if (b == s.me) in_need += size_t(p);
@@ -831,6 +849,7 @@ static int draw_prediction(NbodyHandle* h, State& s, const int* mig_m) {
 // rank sees it in the all-gathered matrix (kFlagMigSpill), nothing is committed, and after the synchronisation the round is
 // made again with the exact sizes and phases 1-3 are repeated (NbodyLetStats.migrant_respills counts such steps).
 static int pass(NbodyHandle* h, float dt, bool is_step, bool potentials = false) {
+    auto& b = nbody32::bodies(h);
     State& s = *h->let;
     const int G = s.G, gg = G * G;
     if (G > 1 && !h->comm_ready) return fail(h, NBODY_ERR_COMM, "world_size > 1 but nbody_comm_init has not been called");
@@ -848,8 +867,8 @@ static int pass(NbodyHandle* h, float dt, bool is_step, bool potentials = false)
         TP_TRY(h, h->tp->all_gather(s.d_mig_matrix, sizeof(int) * size_t(G), h->stream));
         if (s.have_pred) {
             launch_spec_check(h->stream, s.d_mig_matrix, s.d_pred, G, s.d_flags);
-            launch_slot_migrants(h->stream, s.d_send_mig, int(std::min<size_t>(h->n_local, size_t(h->sh.seg_cap))), s.d_send_off, s.d_pred, G, s.me, s.d_slot_out);
-            const size_t total_in = exchange_layout(s.h_pred.data(), G, s.me, (long long)h->sh.seg_cap, true, 0, out_at, n_out, in_at, n_in);
+            launch_slot_migrants(h->stream, s.d_send_mig, int(std::min<size_t>(b.n_local, size_t(b.sh.seg_cap))), s.d_send_off, s.d_pred, G, s.me, s.d_slot_out);
+            const size_t total_in = exchange_layout(s.h_pred.data(), G, s.me, (long long)b.sh.seg_cap, true, 0, out_at, n_out, in_at, n_in);
             rc = variable_round(h, s, reinterpret_cast<const char*>(s.d_slot_out), reinterpret_cast<char*>(s.d_recv_mig), sizeof(Migrant), out_at, n_out, in_at, n_in);
             if (rc) return rc;
             slots_in = int(total_in);
@@ -862,7 +881,7 @@ static int pass(NbodyHandle* h, float dt, bool is_step, bool potentials = false)
             if (rc) return rc;
         }
     }
-    const size_t n_before = h->n_local;   // (phase 1 raises the host's bound by what may arrive: a repeated round starts from here again)
+    const size_t n_before = b.n_local;   // (phase 1 raises the host's bound by what may arrive: a repeated round starts from here again)
     const int* rep = s.h_pin;
     for (int attempt = 0;; ++attempt) {
         rc = phase1(h, s, slots_in);
@@ -888,7 +907,7 @@ static int pass(NbodyHandle* h, float dt, bool is_step, bool potentials = false)
         if ((f & ~kFlagMigSpill) || attempt > 0) return flags_to_error(h, s, (f & ~kFlagMigSpill) ? (f & ~kFlagMigSpill) : f);
         s.spills += 1;
         HIP_TRY(h, hipMemsetAsync(s.d_flags, 0, sizeof(int), h->stream));
-        h->n_local = n_before;
+        b.n_local = n_before;
         std::vector<int> mig(rep + gg, rep + 2 * gg);   // (h_pin is about to be reused)
         rc = migrants_exact(h, s, mig.data());
         if (rc) return rc;
@@ -933,7 +952,8 @@ int update_forces(NbodyHandle* h) { return pass(h, 0.f, false); }
 // AFTER the pass's migration into PotBufs::d_sum, in the order of Shard::ids.  The pass migrates bodies and redraws the
 // bounds like any other, so nbody_potentials runs it on a scratch clone of the rank (nbody_f32.cpp), never on the handle.
 int potential_pass(NbodyHandle* h) {
-    int rc = pot::begin(h, size_t(h->sh.seg_cap));
+    auto& b = nbody32::bodies(h);
+    int rc = pot::begin(h, size_t(b.sh.seg_cap));
     return rc ? rc : pass(h, 0.f, false, true);
 }
 

@@ -5,6 +5,7 @@
 // enqueued on the handle's stream; the live tracer count stays on the device and launches are sized from the host's upper
 // bound, as for the bodies.
 #include "nbody_tracer.h"
+#include "nbody_f32.h"
 
 #include <algorithm>
 #include <cstring>
@@ -26,6 +27,7 @@ constexpr size_t kStatWords = 2 * size_t(NBODY_WALK_COUNTER_SLOTS);
 
 // arrays for `cap` tracers (replaces smaller ones; the contents are the caller's to fill) and the statistics words
 int ensure(NbodyHandle* h, size_t cap) {
+    auto& b = nbody32::bodies(h);
     TracerState& t = h->tr;
     if (!t.d_stats) {
         HIP_TRY(h, h->mem.dev(t.d_stats, kStatWords * sizeof(unsigned long long)));
@@ -37,7 +39,7 @@ int ensure(NbodyHandle* h, size_t cap) {
     t.cap = 0;
     Shard& sh = t.sh;
     sh.n_seg = 1; sh.my_seg = 0; sh.seg_cap = int(cap);
-    sh.poison = h->sh.poison;   // (steps enqueued without read-back: the half drift and the retain stop with the bodies')
+    sh.poison = b.sh.poison;   // (steps enqueued without read-back: the half drift and the retain stop with the bodies')
     const int rc = shard_alloc(h, h->stream, sh, false);   // (no interaction counter: the statistics words above)
     if (rc) return rc;
     t.cap = cap;
@@ -59,6 +61,7 @@ int sync_count(NbodyHandle* h) {
 }  // namespace
 
 int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride, size_t capacity) {
+    auto& b = nbody32::bodies(h);
     TracerState& t = h->tr;
     const size_t cap = capacity ? capacity : n;
     if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_tracers_upload: more tracers than the capacity given");
@@ -73,15 +76,15 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride, size_t capa
         return NBODY_OK;
     }
     int rc = ensure(h, cap);
-    if (!rc) rc = h->ensure_aos(h, n);
+    if (!rc) rc = b.ensure_aos(h, n);
     if (rc) return rc;
     const char* src = static_cast<const char*>(aos);
     for (size_t k = 0; k < n; ++k) {
-        std::memcpy(h->h_aos + 10 * k, src + k * stride, 36);
-        h->h_aos[10 * k + 9] = 0.f;   // the mass field is ignored: a tracer has none
+        std::memcpy(b.h_aos + 10 * k, src + k * stride, 36);
+        b.h_aos[10 * k + 9] = 0.f;   // the mass field is ignored: a tracer has none
     }
-    if (n) HIP_TRY(h, hipMemcpyAsync(h->d_aos, h->h_aos, n * 40, hipMemcpyHostToDevice, h->stream));
-    nbody::launch_aos_to_soa(h->stream, h->d_aos, 10, int(n), t.sh.pos_all, t.sh.vel, t.sh.acc);
+    if (n) HIP_TRY(h, hipMemcpyAsync(b.d_aos, b.h_aos, n * 40, hipMemcpyHostToDevice, h->stream));
+    nbody::launch_aos_to_soa(h->stream, b.d_aos, 10, int(n), t.sh.pos_all, t.sh.vel, t.sh.acc);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipMemsetAsync(t.sh.escaped, 0, sizeof(int), h->stream));
     int* hv = h->h_poison + kScratchTracerCount;
@@ -95,6 +98,7 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride, size_t capa
 }
 
 int download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out) {
+    auto& b = nbody32::bodies(h);
     int rc = sync_count(h);
     if (rc) return rc;
     TracerState& t = h->tr;
@@ -103,14 +107,14 @@ int download(NbodyHandle* h, void* aos, size_t cap, size_t stride, size_t* n_out
     if (n > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_tracers_download: buffer too small");
     if (n == 0) return NBODY_OK;
     if (!aos) return fail(h, NBODY_ERR_INVALID, "nbody_tracers_download: null buffer");
-    rc = h->ensure_aos(h, n);
+    rc = b.ensure_aos(h, n);
     if (rc) return rc;
-    nbody::launch_soa_to_aos(h->stream, h->d_aos, 10, int(n), t.sh.pos_all, t.sh.vel, t.sh.acc);   // (pos.w = 0: the mass written)
+    nbody::launch_soa_to_aos(h->stream, b.d_aos, 10, int(n), t.sh.pos_all, t.sh.vel, t.sh.acc);   // (pos.w = 0: the mass written)
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(h->h_aos, h->d_aos, n * 40, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(b.h_aos, b.d_aos, n * 40, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     char* dst = static_cast<char*>(aos);
-    for (size_t k = 0; k < n; ++k) std::memcpy(dst + k * stride, h->h_aos + 10 * k, 40);
+    for (size_t k = 0; k < n; ++k) std::memcpy(dst + k * stride, b.h_aos + 10 * k, 40);
     return NBODY_OK;
 }
 
@@ -154,9 +158,10 @@ int clone_state(const NbodyHandle* src, NbodyHandle* dst) {
 }
 
 int drift_retain(NbodyHandle* h, float dt) {
+    auto& b = nbody32::bodies(h);
     if (!on(h)) return NBODY_OK;
     TracerState& t = h->tr;
-    nbody::launch_drift_half(h->stream, t.sh, int(t.n_host), dt, h->bnd);
+    nbody::launch_drift_half(h->stream, t.sh, int(t.n_host), dt, b.bnd);
     nbody::launch_compact(h->stream, t.sh, int(t.n_host));
     t.dirty = true;
     HIP_TRY(h, hipGetLastError());
@@ -164,23 +169,24 @@ int drift_retain(NbodyHandle* h, float dt) {
 }
 
 int forces(NbodyHandle* h, const float* kick_dt) {
+    auto& b = nbody32::bodies(h);
     if (!on(h)) return NBODY_OK;
     TracerState& t = h->tr;
-    const float eps2 = h->g_soft * h->g_soft;
+    const float eps2 = b.g_soft * b.g_soft;
     const int m = int(t.n_host);
     if (h->cfg.math_mode == NBODY_MATH_STRICT) {
-        nbody::launch_tr_bf_strict(h->stream, t.sh, m, h->sh, h->g, eps2, t.d_stats);
+        nbody::launch_tr_bf_strict(h->stream, t.sh, m, b.sh, b.g, eps2, t.d_stats);
         if (kick_dt) nbody::launch_kick_drift(h->stream, t.sh, m, *kick_dt);
     } else {
         // the plan is drawn from the counts at the uploads of the tracers and of the bodies, not from the host's current view
         // of them, which a read-back after an escape refreshes: the slice partition, and with it the bits, do not depend on
         // when the caller looks
-        const nbody::TracerPlan p = nbody::tracer_plan(t.n_plan, std::max(h->n_at_upload, h->n_local));
+        const nbody::TracerPlan p = nbody::tracer_plan(t.n_plan, std::max(h->n_at_upload, b.n_local));
         if (p.K > 1) {
             const size_t need = size_t(p.K) * nbody::tracer_plan_pad(p);
             HIP_TRY(h, grow_dev(h, t.d_planes, t.planes_cap, need, sizeof(float4), Grow::exact, kGrowSync));
         }
-        nbody::launch_tr_bf_fast(h->stream, t.sh, m, h->sh, p, t.d_planes, h->g, eps2, kick_dt, t.d_stats);
+        nbody::launch_tr_bf_fast(h->stream, t.sh, m, b.sh, p, t.d_planes, b.g, eps2, kick_dt, t.d_stats);
     }
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;
@@ -190,6 +196,7 @@ int forces(NbodyHandle* h, const float* kick_dt) {
 // The tracers are keyed and sorted into tree order, then walk td's nodes over td's split points; the kick + half drift of a
 // step ride in the walk or in its reduction.  Everything is enqueued: the device build's steps stay without a read-back.
 int tree_forces(NbodyHandle* h, const nbody::TreeDev& td, const float* kick_dt) {
+    auto& b = nbody32::bodies(h);
     if (!on(h)) return NBODY_OK;
     TracerState& t = h->tr;
     const int m = int(t.n_host);
@@ -204,7 +211,7 @@ int tree_forces(NbodyHandle* h, const nbody::TreeDev& td, const float* kick_dt) 
         t.sort_cap = t.cap;
     }
     const int* idx = nullptr;
-    if (nbody::tracer_sort(h->stream, t.sh.own_pos(), t.sh.own_count(), m, h->center, h->width, t.d_sort_tmp, t.sort_bytes, t.d_keys, t.d_idx,
+    if (nbody::tracer_sort(h->stream, t.sh.own_pos(), t.sh.own_count(), m, b.center, b.width, t.d_sort_tmp, t.sort_bytes, t.d_keys, t.d_idx,
                            t.sort_cap, t.d_info, &idx) != 0)
         return fail(h, NBODY_ERR_HIP, "tracer force pass: rocPRIM call failed");
     // (runs drawn from the upload-time count, like the brute-force plan: see forces)
@@ -213,7 +220,7 @@ int tree_forces(NbodyHandle* h, const nbody::TreeDev& td, const float* kick_dt) 
     if (groups > 1) {
         HIP_TRY(h, grow_dev(h, t.d_planes, t.planes_cap, size_t(groups) * stride, sizeof(float4), Grow::exact, kGrowSync));
     }
-    nbody::launch_tr_bh_walk(h->stream, t.sh, m, idx, td, groups, t.d_planes, stride, h->g, h->g_soft * h->g_soft, h->theta2,
+    nbody::launch_tr_bh_walk(h->stream, t.sh, m, idx, td, groups, t.d_planes, stride, b.g, b.g_soft * b.g_soft, b.theta2,
                              h->cfg.leaf_mode == NBODY_LEAF_DIRECT, kick_dt, t.d_stats);
     HIP_TRY(h, hipGetLastError());
     return NBODY_OK;

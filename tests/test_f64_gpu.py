@@ -236,6 +236,29 @@ def test_f32_entry_points_on_an_f64_handle_and_back(gpu):
                 call()
 
 
+def test_settings_getters_of_the_other_width(gpu):
+    """nbody_get_settings (f32) on an NBODY_F64 handle rounds the handle's f64 settings once; nbody_get_settings_f64 on an
+    NBODY_F32 handle widens its f32 settings exactly.  Both read the store of the handle's own precision (96 bodies)."""
+    import ctypes as C
+    nb = gpu
+    given = (1.0, 0.1, 1e-3, 0.3)
+    rounded = [float(np.float32(x)) for x in given]
+    with nb.Simulation(nb.plummer(96, seed=59, f64=True), *BOX, method=nb.BRUTE_FORCE) as sim:
+        assert sim.f64
+        sim.settings = nb.Settings(*given)
+        v = [C.c_float() for _ in given]
+        sim._check(nb.lib.nbody_get_settings(sim._h, *[C.byref(x) for x in v]))
+        assert [x.value for x in v] == rounded and sim.settings == nb.Settings(*given)
+        sim._check(nb.lib.nbody_get_settings(sim._h, None, None, C.byref(v[0]), None))   # (each pointer may be null)
+        assert v[0].value == rounded[2]
+    with nb.Simulation(nb.plummer(96, seed=59), *BOX, method=nb.BRUTE_FORCE) as sim:
+        assert not sim.f64
+        sim.settings = nb.Settings(*given)
+        d = [C.c_double() for _ in given]
+        sim._check(nb.lib.nbody_get_settings_f64(sim._h, *[C.byref(x) for x in d]))
+        assert [x.value for x in d] == rounded
+
+
 def test_f64_tracks_f32(gpu):
     """Sanity across precisions: the f32 strict run stays within float32 rounding of the f64 run of the same (f32) ICs."""
     nb = gpu
