@@ -731,6 +731,53 @@ typedef struct NbodyGroup {          /* 72 bytes */
 int nbody_fof_labels(NbodyHandle* h, double linking_length, int32_t* label, size_t cap, size_t* n_out, size_t* n_groups_out);
 int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, NbodyGroup* groups, size_t group_cap, size_t* n_groups,
                      int32_t* members, size_t member_cap, size_t* n_members);
+/* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
+ * nbody_fof_labels, nbody_fof_groups, nbody_contacts and nbody_merge_contacts ask a FIXED-RADIUS question: only bodies closer
+ * than the linking length or the radius can matter.  nbody_set_pair_search selects how these four calls find such pairs;
+ * nothing else reads the setting (nbody_nearest, nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs).
+ *   NBODY_SEARCH_ALL_PAIRS (the default) is the code as it stands: a handle that never sets the mode runs it untouched.
+ *   NBODY_SEARCH_CELLS sorts the bodies by the cell of a uniform grid and looks at the 27 surrounding cells only.  THE GRID IS
+ * NOT A TREE -- one level, cells of one size, no opening criterion, nothing approximated -- AND IT CHANGES NO RESULT: all four
+ * calls return exactly what they return under NBODY_SEARCH_ALL_PAIRS.  Labels, group counts, member lists and contact lists are
+ * equal integer for integer; the seven sums of each group and every NbodyContact field are equal BIT FOR BIT; the state after
+ * nbody_merge_contacts is equal bit for bit.  Every other clause of those calls' contracts holds as written (read-only calls
+ * leave no trace, the live count is read on the device, scratch goes through the handle's registry and is freed inside the
+ * call, no floating-point atomics, the same state gives the same bits).  The record behind nbody_pair_search_stats is the only
+ * new thing a call leaves behind.
+ *   THE GRID (csrc/cell_grid.h, restated in tests/cells_ref.py), all f64, every operation rounded on its own:
+ *     a body is GRIDDED iff its three coordinates are finite (an NBODY_F32 handle's are widened exactly);
+ *     lo_c, hi_c = min and max of the gridded bodies' coordinate c (a zero bound counts as +0.0);  E = max_c (hi_c - lo_c);
+ *     side = max(length * (1 + 2^-20), E * 2^-20)         (length: the linking length or the radius of the call)
+ *     k_c  = min((uint64) floor((x_c - lo_c) / side), 2^21 - 1);   key = k_x << 42 | k_y << 21 | k_z
+ *     usable = isfinite(E) && isfinite(side) && isfinite(length * length)
+ * A CANDIDATE PAIR is an unordered pair of gridded bodies whose cell indices differ by at most 1 on every axis.  Every pair
+ * with r2 < length * length in the calls' own rounded arithmetic is a candidate pair (DESIGN 3.19 has the proof); a body that
+ * is not gridded has r2 = NaN or +inf to everybody, so it links to and touches nobody under either mode.
+ *   FALLBACK RULE: if the grid is not usable (coordinates near +-1e308, say) or no body is gridded, the call runs the
+ * all-pairs pass and the record reads {0, 0, 0, 0}.
+ *   nbody_set_pair_search may be called at any time between calls; setting a mode and setting it back without a call in
+ * between leaves no trace.  nbody_clone carries the mode; the clone's record starts at zero.
+ *   nbody_pair_search_stats: out = {1 if the last of the four calls on this handle ran the cell search, else 0; bodies gridded;
+ * occupied cells (distinct keys); candidate pairs}.  Integers formed on the device; they depend on the state and the length
+ * only, not on the launch shape.  A call that returns before any pair is looked at (no bodies; nbody_fof_labels with label
+ * and n_groups_out both NULL) leaves the record as it was.
+ *   nbody_host_cell_grid (host only, no device needed): the grid this library would draw for n points {x, y, z} and a length
+ * (finite and > 0, else NBODY_ERR_INVALID): lo, side, usable and -- key != NULL -- every point's key (all ones for a point
+ * that is not gridded, and for every point when the grid is not usable).  With no gridded point lo = 0 and E = 0.
+ *   COST: O(N log N) for the radix sort of (key, row) and the binary searches that find a column of cells among the sorted
+ * keys, plus one f64 pair term per candidate pair (nbody_contacts: two, one from either side).  One cell holding every body
+ * is legal and merely slow.  NOT MEASURED on an MI355X beyond the single run of tools/cells_bench.py that the table of DESIGN
+ * 3.19 records; nothing asserts or promises a time, and nothing chooses a mode for the caller.
+ *   Accepted wherever nbody_fof_labels is accepted.  Refused with NBODY_ERR_INVALID (all three handle calls; nbody_last_error
+ * names the call): a mode other than 0 or 1; handles of a multi-rank world; NBODY_SHARD_SPATIAL handles.  A NULL handle is
+ * refused without touching a device. */
+enum { NBODY_SEARCH_ALL_PAIRS = 0,  /* default: every pair is looked at */
+       NBODY_SEARCH_CELLS = 1 };    /* the 27 cells around a body's own */
+int nbody_set_pair_search(NbodyHandle* h, int mode);
+int nbody_get_pair_search(const NbodyHandle* h, int* mode);
+int nbody_pair_search_stats(NbodyHandle* h, uint64_t out[4]);
+int nbody_host_cell_grid(const double* xyz, size_t n, double length, double lo[3], double* side, uint64_t* key /* [n], may be NULL */,
+                         int* usable);
 const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last create/clone error */
 
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */

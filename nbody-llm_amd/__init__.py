@@ -63,6 +63,7 @@ LEAPFROG, HERMITE4 = 0, 1   # nbody_set_integrator: the reference's leapfrog | f
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 EXTERNAL_MAX = 8   # nbody_set_external_field: components of a static external field, and their kinds
 EXT_PLUMMER, EXT_HERNQUIST, EXT_MIYAMOTO_NAGAI, EXT_LOGARITHMIC = 0, 1, 2, 3
+SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how fof_labels, fof_groups, contacts and merge_contacts find their pairs
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -92,6 +93,7 @@ DECLARED_SYMBOLS = [
     "nbody_partners", "nbody_bound_pairs",
     "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
     "nbody_fof_labels", "nbody_fof_groups",
+    "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
 
@@ -267,6 +269,10 @@ _sig("nbody_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_merge_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_fof_labels", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(_sz))
 _sig("nbody_fof_groups", _i, _H, C.c_double, _i, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_set_pair_search", _i, _H, _i)
+_sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
+_sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_host_cell_grid", _i, C.c_void_p, _sz, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.POINTER(_i))
 _sig("nbody_set_tuning", _i, _H, C.c_char_p, _i)
 _sig("nbody_get_tuning", _i, _H, C.c_char_p, C.POINTER(_i))
 _sig("nbody_is_tuning_build", _i)
@@ -348,6 +354,22 @@ def host_external_eval(comps, g: float, points, acc: bool = True, phi: bool = Tr
     if rc:
         raise NbodyError(rc, (lib.nbody_last_error(None) or b"").decode())
     return a, v
+
+
+def cell_grid(points, length: float, keys: bool = True) -> dict:
+    """The uniform grid NBODY_SEARCH_CELLS would draw for the points [n, 3] (f64) and a linking length or radius
+    (nbody_host_cell_grid; no device needed): dict(lo [3] f64, side, usable, keys [n] uint64 | None).  A point with a NaN or
+    infinite coordinate, and every point of a grid that is not usable, has the all-ones key."""
+    xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n = len(xyz)
+    lo = (C.c_double * 3)()
+    side, usable = C.c_double(0.0), C.c_int(0)
+    key = np.zeros(n, np.uint64) if keys else None
+    rc = lib.nbody_host_cell_grid(xyz.ctypes.data if n else None, n, float(length), lo, C.byref(side), key.ctypes.data if keys and n else None,
+                                  C.byref(usable))
+    if rc:
+        raise NbodyError(rc, "nbody_host_cell_grid: the length must be finite and > 0")
+    return dict(lo=np.array(lo[:], np.float64), side=float(side.value), usable=bool(usable.value), keys=key)
 
 
 def tidal_matrices(t6) -> np.ndarray:
@@ -685,6 +707,26 @@ class Simulation:
         self._check(lib.nbody_fof_groups(self._h, float(b), int(min_members), groups.ctypes.data, len(groups), C.byref(ng),
                                          members.ctypes.data, len(members), C.byref(nm)))
         return groups[: ng.value].copy(), members[: nm.value].copy()
+
+    # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits
+    @property
+    def pair_search(self) -> int:
+        """How fof_labels, fof_groups, contacts and merge_contacts find their pairs: SEARCH_ALL_PAIRS (0, the default) or
+        SEARCH_CELLS (1: bodies sorted by the cell of a uniform grid).  It changes no result; clone() carries it."""
+        v = C.c_int(0)
+        self._check(lib.nbody_get_pair_search(self._h, C.byref(v)))
+        return int(v.value)
+
+    @pair_search.setter
+    def pair_search(self, mode: int):
+        self._check(lib.nbody_set_pair_search(self._h, int(mode)))
+
+    def pair_search_stats(self) -> tuple[int, int, int, int]:
+        """(1 if the last fixed-radius call ran the cell search else 0, bodies gridded, occupied cells, candidate pairs)
+        (nbody_pair_search_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_pair_search_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def __len__(self) -> int:
         n = C.c_size_t(0)

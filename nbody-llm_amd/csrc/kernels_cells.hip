@@ -1,0 +1,293 @@
+// kernels_cells.hip -- the cell-list pair search of nbody_fof_labels, nbody_fof_groups, nbody_contacts and
+// nbody_merge_contacts under NBODY_SEARCH_CELLS (include/nbody_hip.h, "pair search"), on the device (gfx950).  Compiled with
+// -ffp-contract=off; the grid is cell_grid.h's, the metric is k_fof_link's pair_dist2, the union is fof_union.h's.  No
+// floating-point atomics, and no lane ever waits for another lane, wave or workgroup.  Every kernel reads the handle's state
+// and writes the call's scratch only.
+//
+//   k_cells_bounds   min and max of the live, gridded bodies' coordinates and their number: doubles mapped to integers of the
+//                    same order, reduced over the wave with shuffles, then one integer atomicMin / atomicMax per wave and
+//                    bound (exact, and the order of arrival cannot show)
+//   (the host reads the seven words, draws the grid with make_grid and decides whether it is usable)
+//   k_cells_keys     key[i] of every row (rows past the live count and ungridded bodies: all ones), row[i] = i
+//   (rocprim::radix_sort_pairs, stable, on (key, row): the gridded bodies cell after cell, ascending row within a cell)
+//   k_cells_gather   the positions in that order; the distinct keys counted from the boundary flags (an integer atomicAdd)
+//   k_cells_link     one gridded body per lane in key order, so a wave's lanes share cells.  The three cells k_z - 1 .. k_z + 1
+//                    of one (k_x, k_y) column are one contiguous key range, clamped at the walls: two binary searches over
+//                    the sorted keys find it.  Key order is (k_x, k_y, k_z) order, so every candidate that stands after the
+//                    lane's own place lies in the rest of its own column or in the four columns (0, +1), (+1, -1), (+1, 0),
+//                    (+1, +1): each unordered candidate pair is evaluated once, from its earlier body.  Where r2 < B2 the
+//                    lane unites the ORIGINAL indices (fof_union.h; the proof that stale reads are harmless is DESIGN 3.18's)
+//   k_cells_nearest  the same walk over all nine columns: the least r2 < R2 and among equal r2 the lowest ORIGINAL index -- a
+//                    rule on (r2, index) alone, so the order in which cells are visited cannot show
+// Both walks count their candidate pairs (place t after place s) in integers: shuffles, then one atomicAdd per wave.
+#include "kernels_cells.h"
+#include "fof_union.h"
+#include "real.h"      // widen
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+
+namespace nbody {
+
+using pairs::kPairBlock;
+using cells::kCellBits;
+using cells::kCellMax;
+
+namespace {
+
+__device__ __forceinline__ int live_count(const int* __restrict__ count, int n_upper) { return max(0, min(*count, n_upper)); }
+
+// a double as an integer of the same order (-0.0 below +0.0), and back
+__host__ __device__ inline unsigned long long ordered_of(double v) {
+    unsigned long long u;
+    __builtin_memcpy(&u, &v, sizeof(u));
+    return (u >> 63) ? ~u : u | (1ull << 63);
+}
+inline double double_of(unsigned long long o) {
+    const unsigned long long u = (o >> 63) ? o & ~(1ull << 63) : ~o;
+    double v;
+    __builtin_memcpy(&v, &u, sizeof(v));
+    return v;
+}
+
+// the first place in keys[lo, hi) whose key is >= k (kAfter: > k); hi when there is none
+template <bool kAfter>
+__device__ __forceinline__ int key_bound(const uint64_t* __restrict__ keys, int lo, int hi, uint64_t k) {
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        const uint64_t v = keys[mid];
+        if (kAfter ? v <= k : v < k) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// the places [a, b) of column (cx, cy), cells z0 .. z1, among the n gridded bodies; false: the column lies outside the grid
+__device__ __forceinline__ bool column_range(const uint64_t* __restrict__ keys, int from, int n, long long cx, long long cy, uint64_t z0,
+                                             uint64_t z1, int* a, int* b) {
+    if (cx < 0 || cy < 0 || cx > (long long)kCellMax || cy > (long long)kCellMax) return false;
+    *a = key_bound<false>(keys, from, n, cells::cell_key(uint64_t(cx), uint64_t(cy), z0));
+    *b = key_bound<true>(keys, *a, n, cells::cell_key(uint64_t(cx), uint64_t(cy), z1));
+    return true;
+}
+
+// the sum of v over the wave into *total (an integer: the order cannot show); every lane of the wave calls it
+__device__ __forceinline__ void wave_add(unsigned long long v, unsigned long long* total) {
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (threadIdx.x % 64 == 0 && v) atomicAdd(total, v);
+}
+
+}  // namespace
+
+template <class F>
+__global__ __launch_bounds__(kPairBlock) void k_cells_bounds(const typename Real<F>::V4* __restrict__ pos, const int* __restrict__ count,
+                                                             int n_upper, cells::BoundsWords* out) {
+    const int i = blockIdx.x * kPairBlock + threadIdx.x;
+    unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0ull, 0ull, 0ull}, g = 0;
+    if (i < live_count(count, n_upper)) {
+        const double4 p = widen(pos[i]);
+        if (cells::gridded(p.x, p.y, p.z)) {
+            g = 1;
+            lo[0] = hi[0] = ordered_of(p.x);
+            lo[1] = hi[1] = ordered_of(p.y);
+            lo[2] = hi[2] = ordered_of(p.z);
+        }
+    }
+    for (int off = 32; off >= 1; off >>= 1) {   // (every lane of the wave is here)
+        for (int c = 0; c < 3; ++c) {
+            const unsigned long long l = __shfl_xor(lo[c], off, 64), h = __shfl_xor(hi[c], off, 64);
+            lo[c] = l < lo[c] ? l : lo[c];
+            hi[c] = h > hi[c] ? h : hi[c];
+        }
+        g += __shfl_xor(g, off, 64);
+    }
+    if (threadIdx.x % 64 == 0 && g) {
+        for (int c = 0; c < 3; ++c) {
+            atomicMin(&out->lo[c], lo[c]);
+            atomicMax(&out->hi[c], hi[c]);
+        }
+        atomicAdd(&out->gridded, g);
+    }
+}
+
+template <class F>
+__global__ __launch_bounds__(kPairBlock) void k_cells_keys(const typename Real<F>::V4* __restrict__ pos, const int* __restrict__ count,
+                                                           int n_upper, cells::Grid g, uint64_t* __restrict__ keys, int* __restrict__ rows) {
+    const int i = blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= n_upper) return;
+    uint64_t key = cells::kNoKey;
+    if (i < live_count(count, n_upper)) {
+        const double4 p = widen(pos[i]);
+        key = cells::body_key(g, p.x, p.y, p.z);
+    }
+    keys[i] = key;
+    rows[i] = i;
+}
+
+// (the n_gridded keys that are not all ones stand first after the sort)
+template <class F>
+__global__ __launch_bounds__(kPairBlock) void k_cells_gather(const typename Real<F>::V4* __restrict__ pos, int n_gridded,
+                                                             const uint64_t* __restrict__ keys, const int* __restrict__ rows,
+                                                             double4* __restrict__ spos, cells::Counters* counters) {
+    const int s = blockIdx.x * kPairBlock + threadIdx.x;
+    unsigned long long head = 0;
+    if (s < n_gridded) {
+        spos[s] = widen(pos[rows[s]]);   // (rows[s] < the live count <= n_upper)
+        head = s == 0 || keys[s] != keys[s - 1];
+    }
+    wave_add(head, &counters->occupied);
+}
+
+__global__ __launch_bounds__(kPairBlock) void k_cells_link(int n_gridded, const uint64_t* __restrict__ keys, const int* __restrict__ rows,
+                                                           const double4* __restrict__ spos, double B2, int* parent,
+                                                           cells::Counters* counters) {
+    const int s = blockIdx.x * kPairBlock + threadIdx.x;
+    unsigned long long cand = 0;
+    if (s < n_gridded) {
+        const uint64_t key = keys[s];
+        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
+        const uint64_t kz = key & kCellMax;
+        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;   // clamped at the walls
+        const double4 pi = spos[s];
+        const int i = rows[s];
+        const fof::DevParent forest{parent};
+        for (int c = 0; c < 5; ++c) {   // (0, 0) | (0, +1) | (+1, -1), (+1, 0), (+1, +1)
+            const int dx = c >= 2, dy = c == 0 ? 0 : c == 1 ? 1 : c - 3;
+            int a, b;
+            if (!column_range(keys, s + 1, n_gridded, kx + dx, ky + dy, c == 0 ? kz : z0, z1, &a, &b)) continue;
+            // (own column: from the lane's own cell on, the places after s; the cell below holds earlier places only)
+            cand += (unsigned long long)(b - a);
+            for (int t = a; t < b; ++t) {
+                const double r2 = fof::pair_dist2(pi, spos[t]);
+                if (r2 < B2) fof::fof_link(forest, i, rows[t]);   // (strict; a NaN never links)
+            }
+        }
+    }
+    wave_add(cand, &counters->candidates);
+}
+
+__global__ __launch_bounds__(kPairBlock) void k_cells_nearest_init(int n_upper, int* __restrict__ partner, double* __restrict__ energy) {
+    const int i = blockIdx.x * kPairBlock + threadIdx.x;
+    if (i >= n_upper) return;
+    partner[i] = -1;
+    energy[i] = __longlong_as_double(0x7ff0000000000000ll);
+}
+
+__global__ __launch_bounds__(kPairBlock) void k_cells_nearest(int n_gridded, const uint64_t* __restrict__ keys, const int* __restrict__ rows,
+                                                              const double4* __restrict__ spos, double R2, int* __restrict__ partner,
+                                                              double* __restrict__ energy, cells::Counters* counters) {
+    const int s = blockIdx.x * kPairBlock + threadIdx.x;
+    unsigned long long cand = 0;
+    if (s < n_gridded) {
+        const uint64_t key = keys[s];
+        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
+        const uint64_t kz = key & kCellMax;
+        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;
+        const double4 pi = spos[s];
+        double best = __longlong_as_double(0x7ff0000000000000ll);
+        int best_j = -1;
+        for (int c = 0; c < 9; ++c) {
+            int a, b;
+            if (!column_range(keys, 0, n_gridded, kx + (c / 3 - 1), ky + (c % 3 - 1), z0, z1, &a, &b)) continue;
+            const int after = max(a, s + 1);
+            if (b > after) cand += (unsigned long long)(b - after);
+            for (int t = a; t < b; ++t) {
+                const double r2 = fof::pair_dist2(pi, spos[t]);
+                if (t == s || !(r2 < R2)) continue;   // (strict; a NaN is never within R)
+                const int j = rows[t];
+                if (r2 < best || (r2 == best && j < best_j)) { best = r2; best_j = j; }
+            }
+        }
+        partner[rows[s]] = best_j;
+        energy[rows[s]] = best;
+    }
+    wave_add(cand, &counters->candidates);
+}
+
+namespace cells {
+
+size_t bounds_of(const BoundsWords& w, double lo[3], double hi[3]) {
+    for (int c = 0; c < 3; ++c) {
+        lo[c] = w.gridded ? double_of(w.lo[c]) : 0.0;
+        hi[c] = w.gridded ? double_of(w.hi[c]) : 0.0;
+    }
+    return size_t(w.gridded);
+}
+
+namespace {
+size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+size_t sort_tmp_bytes(size_t n_upper) {
+    size_t b = 0;
+    uint64_t* k = nullptr;
+    int* v = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_upper, 0, 64, 0);
+    return b;
+}
+}  // namespace
+
+size_t scratch_bytes(size_t n_upper) {
+    return up256(sizeof(Counters)) + up256(2 * n_upper * sizeof(uint64_t)) + up256(2 * n_upper * sizeof(int)) +
+           up256(n_upper * sizeof(double4)) + up256(sort_tmp_bytes(n_upper));
+}
+
+CellScratch scratch_layout(void* base, size_t n_upper) {
+    char* at = static_cast<char*>(base);
+    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+    CellScratch w;
+    w.counters = static_cast<Counters*>(take(sizeof(Counters)));
+    w.keys = static_cast<uint64_t*>(take(2 * n_upper * sizeof(uint64_t)));
+    w.rows = static_cast<int*>(take(2 * n_upper * sizeof(int)));
+    w.spos = static_cast<double4*>(take(n_upper * sizeof(double4)));
+    w.sort_bytes = sort_tmp_bytes(n_upper);
+    w.sort_tmp = take(w.sort_bytes);
+    return w;
+}
+
+template <class F>
+void launch_bounds(hipStream_t s, const ShardT<F>& sh, int n_upper, BoundsWords* bounds) {
+    (void)hipMemsetAsync(bounds, 0, sizeof(BoundsWords), s);
+    (void)hipMemsetAsync(bounds->lo, 0xff, sizeof(bounds->lo), s);   // (a device address: nothing is read here)
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_cells_bounds<F>, dim3(pairs::blocks_for(n_upper)), dim3(kPairBlock), 0, s, sh.own_pos(), sh.own_count(), n_upper,
+                       bounds);
+}
+
+template <class F>
+int launch_order(hipStream_t s, const ShardT<F>& sh, int n_upper, int n_gridded, const Grid& g, const CellScratch& w) {
+    (void)hipMemsetAsync(w.counters, 0, sizeof(Counters), s);
+    if (n_upper <= 0) return 0;
+    hipLaunchKernelGGL(k_cells_keys<F>, dim3(pairs::blocks_for(n_upper)), dim3(kPairBlock), 0, s, sh.own_pos(), sh.own_count(), n_upper, g,
+                       w.keys, w.rows);
+    size_t tb = w.sort_bytes;
+    if (rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys, w.keys + n_upper, w.rows, w.rows + n_upper, size_t(n_upper), 0, 64, s) != hipSuccess)
+        return -1;
+    if (n_gridded > 0)
+        hipLaunchKernelGGL(k_cells_gather<F>, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, sh.own_pos(), n_gridded,
+                           w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, w.counters);
+    return 0;
+}
+
+void launch_link_components(hipStream_t s, const int* live_count, int n_upper, int n_gridded, double B2, const CellScratch& w,
+                            const fof::FofScratch& f) {
+    if (n_upper <= 0) return;
+    fof::launch_forest_init(s, live_count, n_upper, f);
+    if (n_gridded > 0)
+        hipLaunchKernelGGL(k_cells_link, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded, w.sorted_keys(size_t(n_upper)),
+                           w.sorted_rows(size_t(n_upper)), w.spos, B2, f.parent, w.counters);
+    fof::launch_flatten(s, live_count, n_upper, f);
+}
+
+void launch_nearest_within(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, const pairs::PairScratch& p) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_cells_nearest_init, dim3(pairs::blocks_for(n_upper)), dim3(kPairBlock), 0, s, n_upper, p.partner, p.energy);
+    if (n_gridded > 0)
+        hipLaunchKernelGGL(k_cells_nearest, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
+                           w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, R2, p.partner, p.energy, w.counters);
+}
+
+template void launch_bounds<float>(hipStream_t, const ShardT<float>&, int, BoundsWords*);
+template void launch_bounds<double>(hipStream_t, const ShardT<double>&, int, BoundsWords*);
+template int launch_order<float>(hipStream_t, const ShardT<float>&, int, int, const Grid&, const CellScratch&);
+template int launch_order<double>(hipStream_t, const ShardT<double>&, int, int, const Grid&, const CellScratch&);
+
+}}  // namespace nbody::cells

@@ -8,6 +8,23 @@
 
 namespace nbody { namespace fof {
 
+#if defined(__HIPCC__)
+// ---- what every link pass shares on the device (k_fof_link; k_cells_link of kernels_cells.hip)
+// parent[] in global memory under the three operations of fof_union.h
+struct DevParent {
+    int* p;
+    __device__ __forceinline__ int load(int x) const { return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ __forceinline__ int cas(int x, int expect, int want) const { return atomicCAS(p + x, expect, want); }
+    __device__ __forceinline__ void lower(int x, int v) const { atomicMin(p + x, v); }
+};
+
+// r2_ij = (dx dx + dy dy) + dz dz, unsoftened (nbody_nearest's metric): r2_ij == r2_ji bit for bit
+__device__ __forceinline__ double pair_dist2(const double4 pi, const double4 pj) {
+    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+    return (dx * dx + dy * dy) + dz * dz;
+}
+#endif
+
 // The scratch of one call for n_upper rows, carved out of one allocation of scratch_bytes.
 struct FofScratch {
     int* parent = nullptr;      // [n_upper] the union-find forest (-1 past the live count); dead after k_fof_flatten
@@ -33,6 +50,9 @@ FofScratch scratch_layout(void* base, size_t n_upper);
 // k_fof_init, k_fof_link<F> on the grid of `p`, k_fof_flatten: w.label and w.size of the live rows for the links r2 < B2
 template <class F>
 void launch_components(hipStream_t s, const ShardT<F>& sh, int n_upper, const pairs::PartnerPlan& p, double B2, const FofScratch& w);
+// its first and last launch alone, for a link pass of another kind between them (kernels_cells.hip)
+void launch_forest_init(hipStream_t s, const int* count, int n_upper, const FofScratch& w);
+void launch_flatten(hipStream_t s, const int* count, int n_upper, const FofScratch& w);
 
 // k_fof_flag, the two integer scans, k_fof_slots: w.flag, w.slot, w.offset, w.slot_root, w.keys and w.total; `sort`: the
 // stable radix sort of (slot, row) after them: w.members().  Returns 0, or -1 when a rocPRIM call could not be enqueued.

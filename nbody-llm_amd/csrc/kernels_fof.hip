@@ -36,22 +36,10 @@
 namespace nbody {
 
 using pairs::kPairBlock;
+using fof::DevParent;     // kernels_fof.h: shared with k_cells_link
+using fof::pair_dist2;
 
 namespace {
-
-// parent[] in global memory under the three operations of fof_union.h
-struct DevParent {
-    int* p;
-    __device__ __forceinline__ int load(int x) const { return __hip_atomic_load(p + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ __forceinline__ int cas(int x, int expect, int want) const { return atomicCAS(p + x, expect, want); }
-    __device__ __forceinline__ void lower(int x, int v) const { atomicMin(p + x, v); }
-};
-
-// r2_ij = (dx dx + dy dy) + dz dz, unsoftened (nbody_nearest's metric): r2_ij == r2_ji bit for bit
-__device__ __forceinline__ double pair_dist2(const double4 pi, const double4 pj) {
-    const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
 
 __device__ __forceinline__ int live_count(const int* __restrict__ count, int n_upper) { return max(0, min(*count, n_upper)); }
 
@@ -216,11 +204,20 @@ FofScratch scratch_layout(void* base, size_t n_upper) {
 template <class F>
 void launch_components(hipStream_t s, const ShardT<F>& sh, int n_upper, const pairs::PartnerPlan& p, double B2, const FofScratch& w) {
     if (n_upper <= 0 || p.groups <= 0) return;
-    const int blocks = pairs::blocks_for(n_upper);
-    hipLaunchKernelGGL(k_fof_init, dim3(blocks), dim3(kPairBlock), 0, s, sh.own_count(), n_upper, w.parent, w.size);
+    launch_forest_init(s, sh.own_count(), n_upper, w);
     hipLaunchKernelGGL(k_fof_link<F>, dim3(unsigned(p.groups) * unsigned(p.K)), dim3(kPairBlock), 0, s, sh.own_pos(), sh.own_count(),
                        n_upper, p.groups, p.K, B2, w.parent);
-    hipLaunchKernelGGL(k_fof_flatten, dim3(blocks), dim3(kPairBlock), 0, s, sh.own_count(), n_upper, w.parent, w.label, w.size);
+    launch_flatten(s, sh.own_count(), n_upper, w);
+}
+
+void launch_forest_init(hipStream_t s, const int* count, int n_upper, const FofScratch& w) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_fof_init, dim3(pairs::blocks_for(n_upper)), dim3(kPairBlock), 0, s, count, n_upper, w.parent, w.size);
+}
+
+void launch_flatten(hipStream_t s, const int* count, int n_upper, const FofScratch& w) {
+    if (n_upper <= 0) return;
+    hipLaunchKernelGGL(k_fof_flatten, dim3(pairs::blocks_for(n_upper)), dim3(kPairBlock), 0, s, count, n_upper, w.parent, w.label, w.size);
 }
 
 int launch_catalogue(hipStream_t s, int n_upper, int min_members, bool sort, const FofScratch& w) {

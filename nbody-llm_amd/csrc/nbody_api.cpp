@@ -11,6 +11,7 @@
 #include "nbody_diag.h"
 #include "nbody_pairs.h"
 #include "nbody_fof.h"
+#include "nbody_cells.h"
 
 #include <algorithm>
 #include <chrono>
@@ -566,6 +567,51 @@ int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, Nbo
     return with_bodies(h, [&](auto& b) {
         return nbody::fof::groups(h, b.sh, b.n_local, linking_length, min_members, groups, group_cap, n_groups, members, member_cap, n_members);
     });
+}
+
+// ---- pair search (nbody_cells.cpp): a setting of the handle that the four fixed-radius calls above read, and their record
+namespace {
+int search_refusal(NbodyHandle* h, const char* call) {
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return NBODY_OK;
+}
+}  // namespace
+
+int nbody_set_pair_search(NbodyHandle* h, int mode) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (int rc = search_refusal(h, "nbody_set_pair_search")) return rc;
+    if (mode != NBODY_SEARCH_ALL_PAIRS && mode != NBODY_SEARCH_CELLS)
+        return fail(h, NBODY_ERR_INVALID, "nbody_set_pair_search: mode must be NBODY_SEARCH_ALL_PAIRS (0) or NBODY_SEARCH_CELLS (1)");
+    h->search.mode = mode;   // (read by the next fixed-radius call)
+    return NBODY_OK;
+}
+
+int nbody_get_pair_search(const NbodyHandle* h, int* mode) {
+    if (!h) return NBODY_ERR_INVALID;
+    NbodyHandle* hh = const_cast<NbodyHandle*>(h);
+    if (int rc = search_refusal(hh, "nbody_get_pair_search")) return rc;
+    if (!mode) return fail(hh, NBODY_ERR_INVALID, "nbody_get_pair_search: mode is NULL");
+    *mode = h->search.mode;
+    return NBODY_OK;
+}
+
+int nbody_pair_search_stats(NbodyHandle* h, uint64_t out[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (int rc = search_refusal(h, "nbody_pair_search_stats")) return rc;
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_pair_search_stats: out is NULL");
+    std::copy(h->search.last, h->search.last + 4, out);
+    return NBODY_OK;
+}
+
+int nbody_host_cell_grid(const double* xyz, size_t n, double length, double lo[3], double* side, uint64_t* key, int* usable) {
+    if ((!xyz && n) || !lo || !side || !usable) return NBODY_ERR_INVALID;
+    if (!(std::isfinite(length) && length > 0.0)) return NBODY_ERR_INVALID;   // (the lengths the fixed-radius calls accept)
+    nbody::cells::Grid g;
+    (void)nbody::cells::host_grid(xyz, n, 3, length, &g, key);
+    std::copy(g.lo, g.lo + 3, lo);
+    *side = g.side;
+    *usable = g.usable;
+    return NBODY_OK;
 }
 
 // ---- tracers (nbody_tracer.cpp)

@@ -769,6 +769,7 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
     if (!rc) rc = fail_if_hip(dst, hipStreamSynchronize(dst->stream));
     if (rc) return fail(dst, rc, "clone copy: " + dst->err);
     dst->multipole = src->multipole;
+    dst->search.mode = src->search.mode;   // (the clone's statistics start at zero)
     dst->first_global = src->first_global; dst->n_at_upload = src->n_at_upload;
     // like the reference's BH clone (barnes_hut.rs:113-135) the tree is not carried over; neither
     // are the communicator (call nbody_comm_init on the clone) and the statistics

@@ -456,6 +456,7 @@ int clone_state(NbodyHandle* src, NbodyHandle* dst) {
         }
     }
     HIP_TRY(dst, hipStreamSynchronize(dst->stream));
+    dst->search.mode = src->search.mode;   // (the clone's statistics start at zero)
     return NBODY_OK;
 }
 

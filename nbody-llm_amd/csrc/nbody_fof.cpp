@@ -2,6 +2,7 @@
 // call, the launches of kernels_fof.hip, and the copies of what the caller asked for -- n labels, or the listed records and
 // their members.
 #include "nbody_fof.h"
+#include "nbody_cells.h"
 
 #include <algorithm>
 #include <string>
@@ -17,14 +18,22 @@ int find_groups(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double link
     const pairs::PartnerPlan plan = pairs::make_partner_plan(int(n_upper));
     HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper)));
     *w = scratch_layout(scratch.get(), n_upper);
-    launch_components<F>(h->stream, sh, int(n_upper), plan, linking_length * linking_length, *w);
+    // the links: over the cells of a grid when the handle asks for it and one can be drawn (nbody_cells.h), else over all pairs
+    cells::Search search(h->mem);
+    cells::Counters counted;
+    int rc = cells::prepare<F>(h, sh, n_upper, linking_length, call, &search);
+    if (rc) return rc;
+    if (search.on) cells::launch_link_components(h->stream, sh.own_count(), int(n_upper), search.n_gridded, linking_length * linking_length, search.w, *w);
+    else launch_components<F>(h->stream, sh, int(n_upper), plan, linking_length * linking_length, *w);
     const bool prim_failed = launch_catalogue(h->stream, int(n_upper), min_members, sort, *w) != 0;
     int total[2] = {0, 0}, live = 0;
     HIP_TRY(h, hipGetLastError());
     if (!prim_failed) HIP_TRY(h, hipMemcpyAsync(total, w->total, sizeof(total), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(&live, sh.own_count(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    rc = cells::fetch_counters(h, search, &counted);   // and the synchronisation
+    if (rc) return rc;
     if (prim_failed) return fail(h, NBODY_ERR_HIP, std::string(call) + ": rocPRIM call failed");
+    cells::record(h, search, counted);
     *live_out = std::min(size_t(std::max(live, 0)), n_upper);
     *n_members = std::min(size_t(std::max(total[1], 0)), *live_out);
     *n_groups = std::min(size_t(std::max(total[0], 0)), *n_members);

@@ -581,6 +581,13 @@ struct ExternalField {
     NbodyExternalComponent given[NBODY_EXTERNAL_MAX] = {};
 };
 
+// nbody_set_pair_search: how the fixed-radius calls find their pairs, and what the last of them left for
+// nbody_pair_search_stats (nbody_cells.h).  Nothing else reads it.
+struct PairSearch {
+    int mode = NBODY_SEARCH_ALL_PAIRS;
+    uint64_t last[4] = {0, 0, 0, 0};   // {ran the cell search, bodies gridded, occupied cells, candidate pairs}
+};
+
 struct NbodyHandle {
     nbody::HandleMem mem{kHipSeam};   // every device and pinned block of this handle, its f64 / spatial state included
     NbodyConfig cfg{};
@@ -615,6 +622,7 @@ struct NbodyHandle {
     FieldBufs field;
     TracerState tr;
     ExternalField ext;
+    PairSearch search;
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;

@@ -3,6 +3,7 @@
 // nbody_nearest, nbody_contacts and nbody_merge_contacts ("sticky mergers") are the same three steps under the distance metric,
 // and the last one then writes the merged records and runs the handle's retain.
 #include "nbody_pairs.h"
+#include "nbody_cells.h"
 
 #include <algorithm>
 #include <string>
@@ -129,13 +130,23 @@ int find_contacts(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double ra
     const PartnerPlan plan = make_partner_plan(int(n_upper));
     HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, plan, true)));
     *w = scratch_layout(scratch.get(), n_upper, plan, true);
-    launch_nearest<F>(h->stream, sh, int(n_upper), plan, *w);
+    // every body's nearest: within the radius over the cells of a grid when the handle asks for it and one can be drawn
+    // (nbody_cells.h: a contact is a mutual nearest pair inside the radius either way), else over all pairs
+    cells::Search search(h->mem);
+    cells::Counters counted;
+    int rc = cells::prepare<F>(h, sh, n_upper, radius, call, &search);
+    if (rc) return rc;
+    if (search.on) cells::launch_nearest_within(h->stream, int(n_upper), search.n_gridded, radius * radius, search.w, *w);
+    else launch_nearest<F>(h->stream, sh, int(n_upper), plan, *w);
     const bool scan_failed = launch_contacts<F>(h->stream, sh, int(n_upper), radius * radius, *w) != 0;
     int total = 0, live = 0;
     HIP_TRY(h, hipGetLastError());
     if (!scan_failed) HIP_TRY(h, hipMemcpyAsync(&total, w->total, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, read_live(h, sh, &live));
+    HIP_TRY(h, hipMemcpyAsync(&live, sh.own_count(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    rc = cells::fetch_counters(h, search, &counted);   // and the synchronisation
+    if (rc) return rc;
     if (scan_failed) return fail(h, NBODY_ERR_HIP, std::string(call) + ": rocPRIM call failed");
+    cells::record(h, search, counted);
     *live_out = std::min(size_t(std::max(live, 0)), n_upper);
     *np = std::min(size_t(std::max(total, 0)), *live_out / 2);
     return NBODY_OK;

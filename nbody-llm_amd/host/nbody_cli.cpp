@@ -17,7 +17,9 @@
 // --merge RADIUS[:EVERY] runs nbody_merge_contacts after every EVERY-th step (default 1: sticky spheres of that merge distance)
 // and prints how many bodies were absorbed, in how many calls, on a line of its own; --fof B[:MIN] prints the friends-of-friends
 // groups of the final state for the linking length B (nbody_fof_groups): how many have at least MIN members (default 2), the
-// members and the mass of the largest, and the fraction of bodies in no listed group.
+// members and the mass of the largest, and the fraction of bodies in no listed group; --pair-search cells lets --merge and
+// --fof find their pairs over the cells of a uniform grid (nbody_set_pair_search: the same results) and prints what the last
+// such call gridded on a line of its own.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -41,7 +43,8 @@ static void usage() {
                  "                 [--diagnostics]   (M, |P|, |L| and the 10/50/90 %% Lagrangian radii before and after the run, and --pairs)\n"
                  "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n"
                  "                 [--merge RADIUS[:EVERY]]   (after every EVERY-th step, merge the mutual nearest pairs closer than RADIUS)\n"
-                 "                 [--fof B[:MIN]]   (the friends-of-friends groups of the final state: linking length B, at least MIN members, default 2)\n");
+                 "                 [--fof B[:MIN]]   (the friends-of-friends groups of the final state: linking length B, at least MIN members, default 2)\n"
+                 "                 [--pair-search all|cells]   (how --merge and --fof find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -112,7 +115,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
-               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min) {
+               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int pair_search) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -136,6 +139,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         sim->settings_mut().theta2 = F(theta2);
         if (multipole != NBODY_MULTIPOLE_MONOPOLE) sim->set_multipole(multipole);   // (refused where it does not apply: nbody_hip.h)
         if (integrator == "hermite") sim->set_integrator(NBODY_INTEGRATOR_HERMITE4);
+        if (pair_search != NBODY_SEARCH_ALL_PAIRS) sim->set_pair_search(pair_search);
         if (block_levels > 0) sim->set_block_steps(block_eta, block_levels);   // every --dt is then a macro step of 2^LEVELS ticks
         if (n_tracers) {   // the same generator with the next seed: tracers where the bodies are (the disc's star left out)
             std::vector<nbody::PointParticleT<float>> tr(n_tracers + 1);
@@ -178,6 +182,12 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (diagnostics || pairs) print_pairs(*sim);
         if (merge_radius > 0.0) std::printf("Merged: %zu bodies in %zu calls\n", merged, merge_calls);
         if (fof_b > 0.0) print_fof(*sim, fof_b, fof_min);
+        if (pair_search == NBODY_SEARCH_CELLS) {
+            uint64_t ps[4] = {0, 0, 0, 0};
+            sim->pair_search_stats(ps);
+            std::printf("Pair search: cells %llu gridded %llu occupied %llu candidates %llu\n", (unsigned long long)ps[0], (unsigned long long)ps[1],
+                        (unsigned long long)ps[2], (unsigned long long)ps[3]);
+        }
         if (block_levels > 0) {
             uint64_t counts[2] = {0, 0};
             sim->block_step_counts(counts);
@@ -212,6 +222,7 @@ int main(int argc, char** argv) {
     double merge_radius = 0.0;
     size_t merge_every = 1;
     double fof_b = 0.0;
+    int pair_search = NBODY_SEARCH_ALL_PAIRS;
     int fof_min = 2;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -244,6 +255,12 @@ int main(int argc, char** argv) {
                 if (every < 1) { usage(); return 2; }
                 merge_every = size_t(every);
             }
+        }
+        else if (!std::strcmp(argv[i], "--pair-search")) {
+            const std::string mode = next();
+            if (mode == "cells") pair_search = NBODY_SEARCH_CELLS;
+            else if (mode == "all") pair_search = NBODY_SEARCH_ALL_PAIRS;
+            else { usage(); return 2; }
         }
         else if (!std::strcmp(argv[i], "--fof")) {
             char* end = nullptr;
@@ -286,6 +303,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search);
 }

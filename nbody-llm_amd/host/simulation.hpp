@@ -320,6 +320,16 @@ public:
         members.resize(n_members);
         return groups;
     }
+    // how fof_labels, fof_groups, contacts and merge_contacts find their pairs (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
+    // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
+    // last of those calls ran the cell search, bodies gridded, occupied cells, candidate pairs} (nbody_pair_search_stats)
+    void set_pair_search(int mode) { check(nbody_set_pair_search(h_, mode)); }
+    int pair_search() const { int mode = 0; check(nbody_get_pair_search(h_, &mode)); return mode; }
+    void pair_search_stats(uint64_t out[4]) { check(nbody_pair_search_stats(h_, out)); }
+    // the grid that search would draw for n points {x, y, z} (nbody_host_cell_grid; host only)
+    static int host_cell_grid(const double* xyz, size_t n, double length, double lo[3], double* side, uint64_t* key, int* usable) {
+        return nbody_host_cell_grid(xyz, n, length, lo, side, key, usable);
+    }
     NbodyHandle* handle() { return h_; }
 
 protected:
