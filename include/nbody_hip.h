@@ -731,10 +731,83 @@ typedef struct NbodyGroup {          /* 72 bytes */
 int nbody_fof_labels(NbodyHandle* h, double linking_length, int32_t* label, size_t cap, size_t* n_out, size_t* n_groups_out);
 int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, NbodyGroup* groups, size_t group_cap, size_t* n_groups,
                      int32_t* members, size_t member_cap, size_t* n_members);
+/* ---- neighbours within a radius: every body's neighbour list, local densities and the density centre (no reference
+ * counterpart) -----
+ * Who are all my neighbours within r, and how dense is it here?  Three READ-ONLY calls under the exact contract of nbody_nearest
+ * and nbody_fof_labels above (the bodies are what nbody_download would report -- on a Hermite handle the held (x0, v0) --,
+ * tracers and the external field play no part, no trace in state, NbodyStats, validity flags, levels or the bits of any later
+ * step, no refresh of the host's view of the count, launches sized from its upper bound and the live count read on the device:
+ * right after a retain with no nbody_count in between, scratch through the handle's registry and freed inside the call, no
+ * floating-point atomics: the same state gives the same bits).  Fixed radius only: this is not a k-nearest-neighbour search.
+ *   THE RELATION is nbody_nearest's metric and nbody_contacts' comparison, f64 on either dtype (an NBODY_F32 handle's positions
+ * are widened exactly), unsoftened, nothing contracted:
+ *     d = x_j - x_i,  r2 = (dx dx + dy dy) + dz dz,  R2 = radius * radius rounded once
+ * j is a neighbour of i iff j != i and r2 < R2, STRICTLY.  NaN and +inf never qualify: a body with a non-finite coordinate
+ * has no neighbours and is nobody's neighbour.  r2_ij == r2_ji bit for bit, so the relation is symmetric.
+ * tests/within_ref.py restates all three calls in numpy; the device's results are its integers and its bits.
+ *   nbody_neighbors_within: a CSR list.  The neighbours of body i are neighbor[offset[i] .. offset[i + 1]) in ASCENDING index
+ * (indices are those of nbody_download's order); offset[0] = 0 and offset[n] = *n_neighbors_out, which is twice the number of
+ * unordered pairs inside the radius.  Pure integers, fully determined by the state and the radius: they do not depend on
+ * launch shape, scheduling, the bf64_waves knob or the search mode.  offset holds n + 1 entries and may be NULL; `cap` counts
+ * bodies (an array of cap + 1 entries).  neighbor == NULL only counts; offset is still written if it is given.  *n_out (may
+ * be NULL) = the bodies, *n_neighbors_out (may be NULL) = the directed neighbours.  If cap < n with offset non-NULL, or
+ * neighbor_cap < *n_neighbors_out with neighbor non-NULL, the call returns NBODY_ERR_CAPACITY with both counts set and nothing
+ * written.  A TOTAL ABOVE 2^31 - 1 DIRECTED NEIGHBOURS ALSO RETURNS NBODY_ERR_CAPACITY, with both counts set (the total is
+ * counted in 64 bits) and a message that says to use a smaller radius: every device-side index and every rocPRIM size
+ * argument stays inside 32 bits, and the library does not pretend otherwise.  nbody_density and nbody_density_center refuse
+ * such a radius the same way.
+ *   nbody_density: for each body the terms are its neighbours within `radius` AND THE BODY ITSELF, taken in ascending index; the
+ * body's own term is evaluated at u = 0 without computing r2, so a body with a NaN coordinate gets its own term only.
+ * count[i] = the number of terms (>= 1).  Masses are widened to f64, every product and sum is rounded on its own, sqrt and
+ * divide are IEEE, and the sum s starts from +0.0 and runs in that one sequential order:
+ *     NBODY_KERNEL_TOP_HAT       s += m_j;   rho = s / (4.1887902047863905 * ((radius radius) radius))
+ *     NBODY_KERNEL_CUBIC_SPLINE  the M4 kernel of Monaghan & Lattanzio (1985) with support `radius`:
+ *         hs = radius * 0.5,  u = sqrt(r2) / hs
+ *         u < 1.0:    w = (1.0 - 1.5 (u u)) + 0.75 ((u u) u)
+ *         otherwise:  t = 2.0 - u;  w = 0.25 ((t t) t)
+ *         s += m_j w;   rho = s / (3.141592653589793 * ((hs hs) hs))
+ * sqrt(fl(radius^2)) == radius in IEEE arithmetic and sqrt is monotonic, so sqrt(r2) <= radius for every neighbour, u <= 2
+ * and t IS NEVER NEGATIVE: that is why there is no clamp.  Either output may be NULL; *n_out (may be NULL) = the bodies;
+ * cap < n returns NBODY_ERR_CAPACITY with *n_out set and the arrays untouched.  The density is computed FROM THE CSR LIST of
+ * nbody_neighbors_within, built in scratch by the same code -- that is what makes its bits independent of the search mode and
+ * of the launch shape.  What it costs: scratch of 4 bytes per directed neighbour (8 under NBODY_SEARCH_CELLS, whose lists are
+ * sorted out of place, plus rocPRIM's temporary storage) on top of 8 bytes per (body, partner slice).
+ *   nbody_density_center: the density-weighted centre of Casertano & Hut (1985),
+ *     center_c = (sum_i rho_i x_i,c) / (sum_i rho_i)       rho from nbody_density, each term rho_i x_i,c rounded once
+ * The four sums have nbody_moments' shape: per block of 256 bodies the pairwise tree half = 128 ... 1, rows past the live
+ * count adding +0.0, the block sums added on the host in ascending block order starting from +0.0; then three divides.
+ * *rho_sum (may be NULL) = sum_i rho_i.  With no bodies the centre is NaN and *rho_sum is 0.  A body with a non-finite
+ * coordinate has a finite density (its own term) and makes that coordinate of the centre non-finite, as it does for
+ * nbody_moments.  The result is meant to be passed straight into nbody_lagrangian_radii(h, center, ...).
+ *   HOW: under NBODY_SEARCH_ALL_PAIRS two passes on nbody_nearest's frame (one body per lane, partners through LDS, groups of
+ * 256 bodies x K slices sized by bf64_waves) that both evaluate r2: a count pass writing the count of every (body, slice)
+ * body-major, rocPRIM's integer exclusive scan over that array, and a fill pass writing each slice's neighbours in ascending j
+ * at its place -- ascending lists without a sort, whatever K is.  Under NBODY_SEARCH_CELLS the same two passes walk the 27
+ * cells around a body's own, and each list is then put into ascending order by rocPRIM's segmented radix sort of the integer
+ * keys.  All of it is integer work: the order of events cannot show.  The densities are one lane per body walking its list.
+ *   COST: all pairs: 2 N^2 f64 pair terms of 3 subtractions, 3 products, 2 sums and a compare; cells: O(N log N) for the grid
+ * plus two pair terms per candidate pair and side, and the sort; either way one gather, and for the spline one sqrt and one
+ * divide, per directed neighbour.  NOT MEASURED on an MI355X beyond the single run of tools/within_bench.py that DESIGN 3.20
+ * records (262 144 bodies of a sparse Plummer world: about 0.057 s over all pairs against 0.030 s of nbody_nearest, about
+ * 0.002 s over the cells); nothing asserts or promises a time.
+ *   Accepted and refused exactly where nbody_fof_labels is: every world_size == 1, NBODY_SHARD_INDEX handle is accepted (both
+ * dtypes, both methods, either math mode, any tree build, leapfrog or Hermite, block steps on or off, with or without tracers,
+ * an external field or quadrupoles).  Refused with NBODY_ERR_INVALID (nbody_last_error names the call): a radius that is not
+ * finite or is <= 0; an unknown kernel id; center NULL; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL
+ * handle is refused without touching a device.
+ *   OUT OF SCOPE: k-nearest neighbours; adaptive smoothing lengths; densities at arbitrary probe points; periodic boundaries;
+ * multi-rank or spatial handles; any change to an existing call's results. */
+enum { NBODY_KERNEL_TOP_HAT = 0,        /* the mass inside the sphere over its volume */
+       NBODY_KERNEL_CUBIC_SPLINE = 1 }; /* the M4 spline with support `radius` */
+int nbody_neighbors_within(NbodyHandle* h, double radius, uint64_t* offset /* [n + 1], may be NULL */, size_t cap,
+                           int32_t* neighbor /* may be NULL: count only */, size_t neighbor_cap, size_t* n_out, uint64_t* n_neighbors_out);
+int nbody_density(NbodyHandle* h, double radius, int kernel, double* rho, int32_t* count, size_t cap, size_t* n_out);
+int nbody_density_center(NbodyHandle* h, double radius, int kernel, double center[3], double* rho_sum);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
- * nbody_fof_labels, nbody_fof_groups, nbody_contacts and nbody_merge_contacts ask a FIXED-RADIUS question: only bodies closer
- * than the linking length or the radius can matter.  nbody_set_pair_search selects how these four calls find such pairs;
- * nothing else reads the setting (nbody_nearest, nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs).
+ * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density and
+ * nbody_density_center ask a FIXED-RADIUS question: only bodies closer than the linking length or the radius can matter.
+ * nbody_set_pair_search selects how these seven calls find such pairs; nothing else reads the setting (nbody_nearest,
+ * nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs).
  *   NBODY_SEARCH_ALL_PAIRS (the default) is the code as it stands: a handle that never sets the mode runs it untouched.
  *   NBODY_SEARCH_CELLS sorts the bodies by the cell of a uniform grid and looks at the 27 surrounding cells only.  THE GRID IS
  * NOT A TREE -- one level, cells of one size, no opening criterion, nothing approximated -- AND IT CHANGES NO RESULT: all four

@@ -63,7 +63,8 @@ LEAPFROG, HERMITE4 = 0, 1   # nbody_set_integrator: the reference's leapfrog | f
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 EXTERNAL_MAX = 8   # nbody_set_external_field: components of a static external field, and their kinds
 EXT_PLUMMER, EXT_HERNQUIST, EXT_MIYAMOTO_NAGAI, EXT_LOGARITHMIC = 0, 1, 2, 3
-SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how fof_labels, fof_groups, contacts and merge_contacts find their pairs
+SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how the fixed-radius calls (fof_*, contacts, neighbors_within, density*) find their pairs
+KERNEL_TOP_HAT, KERNEL_CUBIC_SPLINE = 0, 1   # nbody_density / nbody_density_center: the mass in the sphere over its volume | the M4 spline
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -93,6 +94,7 @@ DECLARED_SYMBOLS = [
     "nbody_partners", "nbody_bound_pairs",
     "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
     "nbody_fof_labels", "nbody_fof_groups",
+    "nbody_neighbors_within", "nbody_density", "nbody_density_center",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -269,6 +271,9 @@ _sig("nbody_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_merge_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_fof_labels", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(_sz))
 _sig("nbody_fof_groups", _i, _H, C.c_double, _i, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_neighbors_within", _i, _H, C.c_double, C.c_void_p, _sz, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
+_sig("nbody_density", _i, _H, C.c_double, _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_density_center", _i, _H, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -708,10 +713,43 @@ class Simulation:
                                          members.ctypes.data, len(members), C.byref(nm)))
         return groups[: ng.value].copy(), members[: nm.value].copy()
 
+    # -- neighbours within a radius (nbody_neighbors_within, nbody_density, nbody_density_center): f64, read-only, on the device
+    def neighbors_within(self, radius: float) -> tuple[np.ndarray, np.ndarray]:
+        """(offset [n + 1] uint64, neighbor [offset[n]] int32): a CSR list -- the bodies closer to body i than `radius` (strictly;
+        unsoftened f64 distances) are neighbor[offset[i] : offset[i + 1]], in ascending index, in get_points() order; offset[n]
+        is twice the number of pairs inside the radius (nbody_neighbors_within)."""
+        n, total = C.c_size_t(0), C.c_uint64(0)
+        self._check(lib.nbody_neighbors_within(self._h, float(radius), None, 0, None, 0, C.byref(n), C.byref(total)))   # (counts only)
+        offset = np.zeros(n.value + 1, np.uint64)
+        neighbor = np.full(total.value, -1, np.int32)
+        self._check(lib.nbody_neighbors_within(self._h, float(radius), offset.ctypes.data, n.value, neighbor.ctypes.data if total.value else None,
+                                               total.value, C.byref(n), C.byref(total)))
+        return offset[: n.value + 1], neighbor[: total.value]
+
+    def density(self, radius: float, kernel: int = KERNEL_CUBIC_SPLINE) -> tuple[np.ndarray, np.ndarray]:
+        """(rho [n] f64, count [n] int32): the density at every body from its neighbours within `radius` and the body itself --
+        KERNEL_TOP_HAT: their mass over the sphere's volume; KERNEL_CUBIC_SPLINE: the M4 spline with support `radius` -- summed
+        in ascending index, and the number of terms (>= 1) (nbody_density)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_density(self._h, float(radius), int(kernel), None, None, 0, C.byref(n)))   # (the bodies)
+        rho = np.zeros(n.value, np.float64)
+        count = np.zeros(n.value, np.int32)
+        self._check(lib.nbody_density(self._h, float(radius), int(kernel), rho.ctypes.data if n.value else None,
+                                      count.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return rho[: n.value], count[: n.value]
+
+    def density_center(self, radius: float, kernel: int = KERNEL_CUBIC_SPLINE) -> tuple[np.ndarray, float]:
+        """(center [3] f64, rho_sum): the density-weighted centre sum rho_i x_i / sum rho_i of Casertano & Hut with density()'s
+        rho, summed in moments()' fixed order -- what lagrangian_radii(fractions, center=...) wants (nbody_density_center)."""
+        center = (C.c_double * 3)()
+        total = C.c_double(0)
+        self._check(lib.nbody_density_center(self._h, float(radius), int(kernel), center, C.byref(total)))
+        return np.array(center[:], np.float64), float(total.value)
+
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits
     @property
     def pair_search(self) -> int:
-        """How fof_labels, fof_groups, contacts and merge_contacts find their pairs: SEARCH_ALL_PAIRS (0, the default) or
+        """How fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density and density_center find their pairs: SEARCH_ALL_PAIRS (0, the default) or
         SEARCH_CELLS (1: bodies sorted by the cell of a uniform grid).  It changes no result; clone() carries it."""
         v = C.c_int(0)
         self._check(lib.nbody_get_pair_search(self._h, C.byref(v)))

@@ -60,4 +60,11 @@ void launch_link_components(hipStream_t s, const int* live_count, int n_upper, i
 // or -1 and +inf -- what launch_nearest leaves wherever launch_contacts looks; w.counters->candidates
 void launch_nearest_within(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, const pairs::PairScratch& p);
 
+// k_cells_within<false>: found[i] of every gridded row = the bodies j != i with r2 < R2 (the other rows are left as they are:
+// the caller zeroed them), their number added to *total in 64 bits; w.counters->candidates
+void launch_within_count(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, int* found, unsigned long long* total);
+// k_cells_within<true>: those bodies' indices at raw[offset[i]] on, in the order of the walk over the cells (not ascending);
+// cap: the words of raw
+void launch_within_fill(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, const int* offset, int* raw, size_t cap);
+
 }}  // namespace nbody::cells

@@ -19,7 +19,9 @@
 //                    lane unites the ORIGINAL indices (fof_union.h; the proof that stale reads are harmless is DESIGN 3.18's)
 //   k_cells_nearest  the same walk over all nine columns: the least r2 < R2 and among equal r2 the lowest ORIGINAL index -- a
 //                    rule on (r2, index) alone, so the order in which cells are visited cannot show
-// Both walks count their candidate pairs (place t after place s) in integers: shuffles, then one atomicAdd per wave.
+//   k_cells_within   k_cells_nearest's walk for the neighbour lists of kernels_within.h: a pass that counts every body's
+//                    neighbours with r2 < R2, and after the caller's integer scan a pass that writes their ORIGINAL indices
+// The walks count their candidate pairs (place t after place s) in integers: shuffles, then one atomicAdd per wave.
 #include "kernels_cells.h"
 #include "fof_union.h"
 #include "real.h"      // widen
@@ -204,6 +206,47 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_nearest(int n_gridded, con
     wave_add(cand, &counters->candidates);
 }
 
+// kFill == false: found[rows[s]] = the t != s of the nine columns with r2 < R2, their sum in 64 bits, and the candidate pairs as
+// k_cells_nearest counts them.  kFill == true: the same walk again, the ORIGINAL indices written at offset[rows[s]] on, in the
+// order of the walk (cells::launch_within_fill's caller sorts each list afterwards: integers, one result)
+template <bool kFill>
+__global__ __launch_bounds__(kPairBlock) void k_cells_within(int n_gridded, const uint64_t* __restrict__ keys, const int* __restrict__ rows,
+                                                             const double4* __restrict__ spos, double R2, int* __restrict__ found,
+                                                             const int* __restrict__ offset, int* __restrict__ raw, unsigned cap,
+                                                             unsigned long long* total, cells::Counters* counters) {
+    const int s = blockIdx.x * kPairBlock + threadIdx.x;
+    unsigned long long cand = 0, hits = 0;
+    if (s < n_gridded) {
+        const uint64_t key = keys[s];
+        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
+        const uint64_t kz = key & kCellMax;
+        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;
+        const double4 pi = spos[s];
+        unsigned at = kFill ? unsigned(offset[rows[s]]) : 0u;
+        for (int c = 0; c < 9; ++c) {
+            int a, b;
+            if (!column_range(keys, 0, n_gridded, kx + (c / 3 - 1), ky + (c % 3 - 1), z0, z1, &a, &b)) continue;
+            const int after = max(a, s + 1);
+            if (!kFill && b > after) cand += (unsigned long long)(b - after);
+            for (int t = a; t < b; ++t) {
+                const double r2 = fof::pair_dist2(pi, spos[t]);
+                if (t == s || !(r2 < R2)) continue;   // (strict; a NaN is never within R)
+                if constexpr (kFill) {
+                    if (at < cap) raw[at] = rows[t];   // (at < cap always: the count pass saw the same state)
+                    ++at;
+                } else {
+                    ++hits;
+                }
+            }
+        }
+        if constexpr (!kFill) found[rows[s]] = int(hits);
+    }
+    if constexpr (!kFill) {
+        wave_add(hits, total);
+        wave_add(cand, &counters->candidates);
+    }
+}
+
 namespace cells {
 
 size_t bounds_of(const BoundsWords& w, double lo[3], double hi[3]) {
@@ -283,6 +326,20 @@ void launch_nearest_within(hipStream_t s, int n_upper, int n_gridded, double R2,
     if (n_gridded > 0)
         hipLaunchKernelGGL(k_cells_nearest, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
                            w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, R2, p.partner, p.energy, w.counters);
+}
+
+void launch_within_count(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, int* found, unsigned long long* total) {
+    if (n_upper <= 0 || n_gridded <= 0) return;
+    hipLaunchKernelGGL(k_cells_within<false>, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
+                       w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, R2, found, static_cast<const int*>(nullptr),
+                       static_cast<int*>(nullptr), 0u, total, w.counters);
+}
+
+void launch_within_fill(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, const int* offset, int* raw, size_t cap) {
+    if (n_upper <= 0 || n_gridded <= 0 || !cap) return;
+    hipLaunchKernelGGL(k_cells_within<true>, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
+                       w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, R2, static_cast<int*>(nullptr), offset, raw,
+                       unsigned(cap), static_cast<unsigned long long*>(nullptr), static_cast<Counters*>(nullptr));
 }
 
 template void launch_bounds<float>(hipStream_t, const ShardT<float>&, int, BoundsWords*);

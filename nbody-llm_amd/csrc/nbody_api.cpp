@@ -11,6 +11,7 @@
 #include "nbody_diag.h"
 #include "nbody_pairs.h"
 #include "nbody_fof.h"
+#include "nbody_within.h"
 #include "nbody_cells.h"
 
 #include <algorithm>
@@ -569,7 +570,48 @@ int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, Nbo
     });
 }
 
-// ---- pair search (nbody_cells.cpp): a setting of the handle that the four fixed-radius calls above read, and their record
+// ---- neighbours within a radius (nbody_within.cpp): three read-only calls under the census's contract
+namespace {
+int within_enter(NbodyHandle* h, const char* call, double radius) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    if (std::isfinite(radius) && radius > 0.0) return NBODY_OK;
+    return fail(h, NBODY_ERR_INVALID, std::string(call) + ": radius must be finite and > 0");
+}
+int within_kernel(NbodyHandle* h, const char* call, int kernel) {
+    if (kernel == NBODY_KERNEL_TOP_HAT || kernel == NBODY_KERNEL_CUBIC_SPLINE) return NBODY_OK;
+    return fail(h, NBODY_ERR_INVALID, std::string(call) + ": kernel must be NBODY_KERNEL_TOP_HAT (0) or NBODY_KERNEL_CUBIC_SPLINE (1)");
+}
+}  // namespace
+
+int nbody_neighbors_within(NbodyHandle* h, double radius, uint64_t* offset, size_t cap, int32_t* neighbor, size_t neighbor_cap, size_t* n_out,
+                           uint64_t* n_neighbors_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = within_enter(h, "nbody_neighbors_within", radius);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) {
+        return nbody::within::neighbors(h, b.sh, b.n_local, radius, offset, cap, neighbor, neighbor_cap, n_out, n_neighbors_out);
+    });
+}
+
+int nbody_density(NbodyHandle* h, double radius, int kernel, double* rho, int32_t* count, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = within_enter(h, "nbody_density", radius);
+    if (!rc) rc = within_kernel(h, "nbody_density", kernel);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) { return nbody::within::density(h, b.sh, b.n_local, radius, kernel, rho, count, cap, n_out); });
+}
+
+int nbody_density_center(NbodyHandle* h, double radius, int kernel, double center[3], double* rho_sum) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = within_enter(h, "nbody_density_center", radius);
+    if (!rc) rc = within_kernel(h, "nbody_density_center", kernel);
+    if (rc) return rc;
+    if (!center) return fail(h, NBODY_ERR_INVALID, "nbody_density_center: center is NULL");
+    return with_bodies(h, [&](auto& b) { return nbody::within::density_center(h, b.sh, b.n_local, radius, kernel, center, rho_sum); });
+}
+
+// ---- pair search (nbody_cells.cpp): a setting of the handle that the seven fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
     if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);

@@ -19,7 +19,9 @@
 // groups of the final state for the linking length B (nbody_fof_groups): how many have at least MIN members (default 2), the
 // members and the mass of the largest, and the fraction of bodies in no listed group; --pair-search cells lets --merge and
 // --fof find their pairs over the cells of a uniform grid (nbody_set_pair_search: the same results) and prints what the last
-// such call gridded on a line of its own.
+// such call gridded on a line of its own; --density R[:tophat|spline] (default spline) prints the density centre of the final
+// state (nbody_density_center), the largest density and its body (nbody_density) and the half-mass Lagrangian radius about
+// that centre, on a line of its own, and honours --pair-search.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -44,7 +46,8 @@ static void usage() {
                  "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n"
                  "                 [--merge RADIUS[:EVERY]]   (after every EVERY-th step, merge the mutual nearest pairs closer than RADIUS)\n"
                  "                 [--fof B[:MIN]]   (the friends-of-friends groups of the final state: linking length B, at least MIN members, default 2)\n"
-                 "                 [--pair-search all|cells]   (how --merge and --fof find their pairs: all pairs, or the cells of a uniform grid)\n");
+                 "                 [--density R[:tophat|spline]]   (the density centre of the final state, the largest density, r50 about that centre)\n"
+                 "                 [--pair-search all|cells]   (how --merge, --fof and --density find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -110,12 +113,29 @@ static void print_fof(Sim& sim, double b, int min_members) {
                 groups.empty() ? 0.0 : groups[big].mass, n ? double(n - members.size()) / double(n) : 0.0);
 }
 
+// the line of --density: nbody_density_center, nbody_density (the densest body: the first of equals) and the half-mass
+// Lagrangian radius about the density centre
+template <class Sim>
+static void print_density(Sim& sim, double radius, int kernel) {
+    double center[3];
+    const double rho_sum = sim.density_center(radius, kernel, center);
+    std::vector<double> rho, radii;
+    std::vector<int32_t> count;
+    sim.density(radius, kernel, rho, count);
+    size_t top = 0;
+    for (size_t k = 1; k < rho.size(); ++k) if (rho[k] > rho[top]) top = k;
+    sim.lagrangian_radii(center, {0.5}, radii);
+    std::printf("Density: center %.17e %.17e %.17e rho_sum %.17e max %.17e body %ld terms %d r50 %.17e\n", center[0], center[1], center[2], rho_sum,
+                rho.empty() ? std::nan("") : rho[top], rho.empty() ? -1L : long(top), rho.empty() ? 0 : int(count[top]), radii[0]);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
-               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int pair_search) {
+               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int pair_search,
+               double density_radius, int density_kernel) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -182,6 +202,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (diagnostics || pairs) print_pairs(*sim);
         if (merge_radius > 0.0) std::printf("Merged: %zu bodies in %zu calls\n", merged, merge_calls);
         if (fof_b > 0.0) print_fof(*sim, fof_b, fof_min);
+        if (density_radius > 0.0) print_density(*sim, density_radius, density_kernel);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -224,6 +245,8 @@ int main(int argc, char** argv) {
     double fof_b = 0.0;
     int pair_search = NBODY_SEARCH_ALL_PAIRS;
     int fof_min = 2;
+    double density_radius = 0.0;
+    int density_kernel = NBODY_KERNEL_CUBIC_SPLINE;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -272,6 +295,18 @@ int main(int argc, char** argv) {
                 if (fof_min < 1) { usage(); return 2; }
             }
         }
+        else if (!std::strcmp(argv[i], "--density")) {
+            char* end = nullptr;
+            const char* arg = next();
+            density_radius = std::strtod(arg, &end);
+            if (end == arg || !(density_radius > 0.0) || !std::isfinite(density_radius) || (*end && *end != ':')) { usage(); return 2; }
+            if (*end == ':') {
+                const std::string kind = end + 1;
+                if (kind == "tophat") density_kernel = NBODY_KERNEL_TOP_HAT;
+                else if (kind == "spline") density_kernel = NBODY_KERNEL_CUBIC_SPLINE;
+                else { usage(); return 2; }
+            }
+        }
         else if (!std::strcmp(argv[i], "--tracers")) n_tracers = std::strtoull(next(), nullptr, 10);
         else if (!std::strcmp(argv[i], "--external")) {
             NbodyExternalComponent c;
@@ -303,6 +338,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search, density_radius, density_kernel);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search, density_radius, density_kernel);
 }

@@ -320,7 +320,38 @@ public:
         members.resize(n_members);
         return groups;
     }
-    // how fof_labels, fof_groups, contacts and merge_contacts find their pairs (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
+    // neighbours within a radius (nbody_neighbors_within, nbody_density, nbody_density_center): f64 unsoftened distances on
+    // either F, strictly inside the radius; read-only, the handles moments() takes.  The neighbours of body i are
+    // neighbor[offset[i] .. offset[i + 1]) in ascending index; offset has n + 1 entries
+    void neighbors_within(double radius, std::vector<uint64_t>& offset, std::vector<int32_t>& neighbor) {
+        size_t n = 0;
+        uint64_t total = 0;
+        check(nbody_neighbors_within(h_, radius, nullptr, 0, nullptr, 0, &n, &total));   // (counts only)
+        offset.assign(n + 1, 0);
+        neighbor.assign(size_t(total), -1);
+        check(nbody_neighbors_within(h_, radius, offset.data(), n, total ? neighbor.data() : nullptr, size_t(total), &n, &total));
+        offset.resize(n + 1);
+        neighbor.resize(size_t(total));
+    }
+    // rho[i]: the density at body i from its neighbours within `radius` and itself (kernel: NBODY_KERNEL_TOP_HAT or
+    // NBODY_KERNEL_CUBIC_SPLINE), count[i]: the number of terms
+    void density(double radius, int kernel, std::vector<double>& rho, std::vector<int32_t>& count) {
+        size_t n = 0;
+        check(nbody_density(h_, radius, kernel, nullptr, nullptr, 0, &n));   // (the bodies)
+        rho.assign(n, 0.0);
+        count.assign(n, 0);
+        check(nbody_density(h_, radius, kernel, rho.data(), count.data(), n, &n));
+        rho.resize(n);
+        count.resize(n);
+    }
+    // the density-weighted centre (what lagrangian_radii's `center` wants); returns the sum of the densities
+    double density_center(double radius, int kernel, double center[3]) {
+        double sum = 0;
+        check(nbody_density_center(h_, radius, kernel, center, &sum));
+        return sum;
+    }
+    // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density and density_center find their pairs
+    // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
     // last of those calls ran the cell search, bodies gridded, occupied cells, candidate pairs} (nbody_pair_search_stats)
     void set_pair_search(int mode) { check(nbody_set_pair_search(h_, mode)); }
