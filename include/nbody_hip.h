@@ -731,6 +731,82 @@ typedef struct NbodyGroup {          /* 72 bytes */
 int nbody_fof_labels(NbodyHandle* h, double linking_length, int32_t* label, size_t cap, size_t* n_out, size_t* n_groups_out);
 int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, NbodyGroup* groups, size_t group_cap, size_t* n_groups,
                      int32_t* members, size_t member_cap, size_t* n_members);
+/* ---- self-bound subsets of friends-of-friends groups: FoF, then iterative unbinding (no reference counterpart) ----------------
+ * A FoF group says "these bodies are close"; it does not say "these bodies belong together": fly-through bodies, chance
+ * alignments and bridges are in the catalogue too.  nbody_fof_bound_groups does what halo and cluster finders do next: it
+ * evaluates every member's energy inside its own group, strips the unbound members, and repeats until nobody is unbound.
+ * READ-ONLY under the exact contract of nbody_fof_groups above (the bodies are what nbody_download would report -- on a
+ * Hermite handle the held (x0, v0) --, tracers and the external field play no part, no trace in state, NbodyStats, validity
+ * flags, levels or the bits of any later step, no refresh of the host's view of the count, launches sized from its upper bound
+ * and the live count read on the device: right after a retain with no nbody_count in between, scratch through the handle's
+ * registry and freed inside the call, no floating-point atomics: the same state gives the same bits).
+ *   STEP 0 is the FoF groups of nbody_fof_groups(linking_length, min_members): the same link, the same catalogue, and
+ * nbody_set_pair_search is honoured; the nbody_pair_search_stats record is what that call would leave.  The unbinding passes
+ * never use the grid.
+ *   AN EVALUATION PASS.  For each listed FoF group take its members in ascending index at positions k = 0 .. fof_count-1.  The
+ * group holds an alive flag per position, all 1 at the start.  Everything is f64 from exactly widened values, every product,
+ * sum and difference is rounded on its own, sqrt and divide are IEEE, nothing is contracted.
+ *     1. GROUP SUMS.  The seven sums (m, m x_c, m v_c) of the alive members in nbody_fof_groups' shape: lane t = k mod 64 adds
+ *        its alive members in ascending k, starting from +0.0 -- k is the position in the FoF list, not a rank among the
+ *        alive; a dead member adds nothing --, then sum[t] += sum[t + half] for half = 32 .. 1.  V_c = mv_c / mass.
+ *     2. PER-MEMBER ENERGY.  For each alive i: soft2 = g_soft g_soft.  The partner list is cut into tiles of 256 consecutive
+ *        positions (k div 256).  s = +0.0; for each tile in ascending order: p = +0.0; for k ascending in the tile, if k is
+ *        alive and k != k_i:
+ *            d = x_k - x_i,  r2 = ((dx dx + dy dy) + dz dz) + soft2,  p += m_k / sqrt(r2)
+ *        then s += p -- every tile is added, also one with no live partner.  phi_i = -(g s);  u = v_i - V,
+ *        u2 = (ux ux + uy uy) + uz uz,  e_i = 0.5 u2 + phi_i.  (The tile rule lets an implementation stage 256 partners through
+ *        LDS; the result does not depend on any launch-shape knob.)
+ *     3. VERDICT.  Member i is UNBOUND iff !(e_i < 0): a NaN energy is unbound, -inf is bound (coincident members without
+ *        softening get -inf).
+ *   THE LOOP of a group, passes t = 0, 1, ...: evaluate the alive set; if nobody is unbound stop with converged = 1; else if
+ * t + 1 == max_iterations stop with converged = 0 -- nobody is removed by this last pass, so the reported energies always
+ * describe the reported set --; else clear the alive flag of EVERY unbound member AT ONCE; if fewer than min_members remain
+ * the group is DISSOLVED and is not listed.  iterations = t + 1.  Groups proceed independently.
+ *   OUTPUT.  The surviving groups in ascending `first`; members holds their alive bodies, group after group, each in ascending
+ * index; energy[k] (may be NULL) is the e_i of members[k] from the group's last pass.  kinetic and potential are sums in the
+ * shape of step 1 over the alive members (k still the position in the FoF list) of the terms (0.5 m_i) u2_i and
+ * (0.5 m_i) phi_i of the last pass; mass, mx and mv are the last pass's seven sums.  `first` stays the label of the FoF group
+ * -- its lowest index, which need not be a bound member.  A converged group has every e_i < 0.  Compaction and offsets are
+ * integer work (flags, rocPRIM integer scans, a stable order): the order of events cannot show.  tests/unbind_ref.py restates
+ * the call in numpy; the device's results are its integers and its bits.
+ *   NULL AND CAPACITY FORMS are nbody_fof_groups': any array may be NULL (the call only counts -- it still runs every pass);
+ * a non-NULL array that is too small returns NBODY_ERR_CAPACITY with both counts set and nothing written.  energy is sized by
+ * member_cap.  n_groups and n_members may be NULL.
+ *   HOW: one launch chain per pass serves every group still running: one wave per group for the seven sums, then the energy
+ * kernel -- one member per lane, a block per 256 consecutive positions of the FoF member list, so a group of n_g members is
+ * spread over n_g / 256 blocks; where a block's rows share a group the tile of 256 partners is staged through LDS, where they
+ * do not (small groups, the ends of a large one) each lane reads its own group's partners directly, in the same order --,
+ * then one wave per group for the verdict.  The host reads back one integer per pass: the groups still running.
+ *   COST: per pass, the sum over the groups still running of n_g^2 f64 pair terms (n_g = fof_count: dead positions are
+ * skipped, not compacted), each with a sqrt and a divide, plus nbody_fof_groups' own cost once.  Scratch: nbody_fof_groups'
+ * (48 bytes per body plus rocPRIM's temporaries) plus 48 bytes per listed FoF member and 184 bytes per listed FoF group (at
+ * most 140 bytes per body in all at min_members = 2).  NOT MEASURED on an MI355X beyond the single run of
+ * tools/fof_bound_bench.py that DESIGN 3.21 records (one run: about 0.073 s at 262 144 f64 bodies of a Plummer sphere plus six
+ * blobs of 16 384, 13 passes and at least 7.5e9 pair terms, against 0.026 s of nbody_fof_groups on the same state); nothing
+ * asserts or promises a time.
+ *   Accepted wherever nbody_fof_groups is.  Refused with NBODY_ERR_INVALID (nbody_last_error names the call): everything
+ * nbody_fof_groups refuses; min_members < 2; max_iterations < 1 or > 1024.  A NULL handle is refused without touching a
+ * device.  Negative masses and g <= 0 are the caller's risk (with g <= 0 every group dissolves, which is correct).
+ *   OUT OF SCOPE: stripping only the most unbound fraction per pass; tree-accelerated group potentials; substructure
+ * (sub-halos, saddle points); a per-body bound-label array; unbinding of user-supplied member lists; periodic boundaries;
+ * multi-rank and spatial handles; any change to an existing call. */
+typedef struct NbodyBoundGroup {      /* 96 bytes */
+    int32_t first;        /* label of the FoF group it came from (its lowest index), NOT necessarily a bound member */
+    int32_t fof_count;    /* members of that FoF group */
+    int32_t count;        /* bound members reported */
+    int32_t offset;       /* of its bound members in the member list */
+    int32_t iterations;   /* evaluation passes this group went through, >= 1 */
+    int32_t converged;    /* 1: its last pass found nobody unbound; 0: stopped by max_iterations */
+    double mass;          /* of the reported members */
+    double mx[3];         /* sum m x */
+    double mv[3];         /* sum m v */
+    double kinetic;       /* sum (0.5 m_i) u2_i, u relative to the group's mean velocity */
+    double potential;     /* sum (0.5 m_i) phi_i, phi from the reported members only */
+} NbodyBoundGroup;
+int nbody_fof_bound_groups(NbodyHandle* h, double linking_length, int min_members, int max_iterations,
+                           NbodyBoundGroup* groups, size_t group_cap, size_t* n_groups,
+                           int32_t* members, size_t member_cap, size_t* n_members,
+                           double* energy /* [n_members], parallel to members; may be NULL */);
 /* ---- neighbours within a radius: every body's neighbour list, local densities and the density centre (no reference
  * counterpart) -----
  * Who are all my neighbours within r, and how dense is it here?  Three READ-ONLY calls under the exact contract of nbody_nearest

@@ -93,7 +93,7 @@ DECLARED_SYMBOLS = [
     "nbody_moments", "nbody_lagrangian_radii",
     "nbody_partners", "nbody_bound_pairs",
     "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
-    "nbody_fof_labels", "nbody_fof_groups",
+    "nbody_fof_labels", "nbody_fof_groups", "nbody_fof_bound_groups",
     "nbody_neighbors_within", "nbody_density", "nbody_density_center",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
@@ -152,6 +152,20 @@ class NbodyGroup(C.Structure):
 GROUP_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("offset", "<i4"), ("reserved", "<i4"), ("mass", "<f8"),
                         ("mx", "<f8", (3,)), ("mv", "<f8", (3,))])
 assert GROUP_DTYPE.itemsize == C.sizeof(NbodyGroup) == 72
+
+
+class NbodyBoundGroup(C.Structure):
+    """One reported group of nbody_fof_bound_groups (include/nbody_hip.h "self-bound subsets of friends-of-friends groups")."""
+    _fields_ = [("first", C.c_int32), ("fof_count", C.c_int32), ("count", C.c_int32), ("offset", C.c_int32),
+                ("iterations", C.c_int32), ("converged", C.c_int32), ("mass", C.c_double), ("mx", C.c_double * 3),
+                ("mv", C.c_double * 3), ("kinetic", C.c_double), ("potential", C.c_double)]
+
+
+#: the same record as a numpy dtype: what Simulation.fof_bound_groups() returns
+BOUND_GROUP_DTYPE = np.dtype([("first", "<i4"), ("fof_count", "<i4"), ("count", "<i4"), ("offset", "<i4"), ("iterations", "<i4"),
+                              ("converged", "<i4"), ("mass", "<f8"), ("mx", "<f8", (3,)), ("mv", "<f8", (3,)), ("kinetic", "<f8"),
+                              ("potential", "<f8")])
+assert BOUND_GROUP_DTYPE.itemsize == C.sizeof(NbodyBoundGroup) == 96
 
 
 class NbodyStats(C.Structure):
@@ -271,6 +285,7 @@ _sig("nbody_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_merge_contacts", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_fof_labels", _i, _H, C.c_double, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(_sz))
 _sig("nbody_fof_groups", _i, _H, C.c_double, _i, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_fof_bound_groups", _i, _H, C.c_double, _i, _i, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p)
 _sig("nbody_neighbors_within", _i, _H, C.c_double, C.c_void_p, _sz, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
 _sig("nbody_density", _i, _H, C.c_double, _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_density_center", _i, _H, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -712,6 +727,24 @@ class Simulation:
         self._check(lib.nbody_fof_groups(self._h, float(b), int(min_members), groups.ctypes.data, len(groups), C.byref(ng),
                                          members.ctypes.data, len(members), C.byref(nm)))
         return groups[: ng.value].copy(), members[: nm.value].copy()
+
+    def fof_bound_groups(self, b: float, min_members: int = 2, max_iterations: int = 32) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(groups, members, energy): the self-bound subsets of the fof_groups(b, min_members) groups.  Every member's energy
+        e = 0.5 u2 + phi is evaluated inside its own group (u relative to the group's mean velocity, phi softened, from the
+        group's members only), all members with !(e < 0) are stripped at once, and the pass repeats until nobody is unbound or
+        max_iterations passes have run; a group left with fewer than min_members bodies is dropped.  groups is a
+        BOUND_GROUP_DTYPE array in ascending `first` (the FoF label, which need not be a bound member), members [int32] the
+        bound bodies, group after group in ascending index, energy [f64] their e from the group's last pass
+        (nbody_fof_bound_groups)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_fof_labels(self._h, float(b), None, 0, C.byref(n), None))   # (the bodies only: an upper bound of both)
+        groups = np.zeros(n.value // max(int(min_members), 1) + 1, BOUND_GROUP_DTYPE)
+        members = np.full(n.value + 1, -1, np.int32)
+        energy = np.zeros(n.value + 1, np.float64)
+        ng, nm = C.c_size_t(0), C.c_size_t(0)
+        self._check(lib.nbody_fof_bound_groups(self._h, float(b), int(min_members), int(max_iterations), groups.ctypes.data, len(groups),
+                                               C.byref(ng), members.ctypes.data, len(members), C.byref(nm), energy.ctypes.data))
+        return groups[: ng.value].copy(), members[: nm.value].copy(), energy[: nm.value].copy()
 
     # -- neighbours within a radius (nbody_neighbors_within, nbody_density, nbody_density_center): f64, read-only, on the device
     def neighbors_within(self, radius: float) -> tuple[np.ndarray, np.ndarray]:

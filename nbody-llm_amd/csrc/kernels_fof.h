@@ -5,6 +5,9 @@
 #include "nbody_hip.h"      // NbodyGroup
 #include "kernels_pairs.h"  // PartnerPlan, kPairBlock: k_fof_link runs on k_partner's frame
 #include "shard.h"
+#if defined(__HIPCC__)
+#include "real.h"           // widen
+#endif
 
 namespace nbody { namespace fof {
 
@@ -22,6 +25,30 @@ struct DevParent {
 __device__ __forceinline__ double pair_dist2(const double4 pi, const double4 pj) {
     const double dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
     return (dx * dx + dy * dy) + dz * dz;
+}
+
+// THE SEVEN SUMS of one group in the header's order, by one wave: who[k], k = 0 .. cnt-1, are its members in ascending index;
+// lane t = k mod 64 adds its terms in ascending k from +0.0 -- m, m x_c, m v_c, each product rounded once -- then sum[t] +=
+// sum[t + half] for half = 32, 16, ... 1: lane 0 holds the result.  alive (may be nullptr: everybody) is parallel to who: a
+// member whose flag is 0 adds nothing, and k stays its position in who (k_fof_sums; k_unbind_sums of kernels_unbind.hip).
+template <class F>
+__device__ __forceinline__ void seven_sums(const typename Real<F>::V4* __restrict__ pos, const typename Real<F>::V4* __restrict__ vel,
+                                           const int* __restrict__ who, int cnt, const int* __restrict__ alive, int lane, double s[7]) {
+    for (int c = 0; c < 7; ++c) s[c] = 0.0;
+    for (int k = lane; k < cnt; k += 64) {
+        if (alive && !alive[k]) continue;
+        const int b = who[k];
+        const double4 p = widen(pos[b]), v = widen(vel[b]);
+        s[0] += p.w;
+        s[1] += p.w * p.x;
+        s[2] += p.w * p.y;
+        s[3] += p.w * p.z;
+        s[4] += p.w * v.x;
+        s[5] += p.w * v.y;
+        s[6] += p.w * v.z;
+    }
+    for (int half = 32; half >= 1; half >>= 1)
+        for (int c = 0; c < 7; ++c) s[c] += __shfl_down(s[c], half, 64);   // (lanes >= half carry sums nobody reads)
 }
 #endif
 

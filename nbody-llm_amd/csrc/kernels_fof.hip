@@ -119,8 +119,8 @@ __global__ __launch_bounds__(kPairBlock) void k_fof_slots(int n_upper, const int
     rows[i] = i;
 }
 
-// One wave per listed group, members k = 0 .. count-1 in ascending index: lane t = k mod 64 adds its terms in ascending k from
-// +0.0 -- m, m x_c, m v_c, each product rounded once -- then sum[t] += sum[t + half] for half = 32, 16, ... 1.
+// One wave per listed group, members k = 0 .. count-1 in ascending index: the seven sums in the header's order (seven_sums of
+// kernels_fof.h), and the record.
 template <class F>
 __global__ __launch_bounds__(kPairBlock) void k_fof_sums(const typename Real<F>::V4* __restrict__ pos,
                                                          const typename Real<F>::V4* __restrict__ vel, int n_groups,
@@ -132,20 +132,8 @@ __global__ __launch_bounds__(kPairBlock) void k_fof_sums(const typename Real<F>:
     if (g >= n_groups) return;   // (wave-uniform)
     const int root = slot_root[g];
     const int cnt = size[root], off = offset[root];
-    double s[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = lane; k < cnt; k += 64) {
-        const int b = members[off + k];
-        const double4 p = widen(pos[b]), v = widen(vel[b]);
-        s[0] += p.w;
-        s[1] += p.w * p.x;
-        s[2] += p.w * p.y;
-        s[3] += p.w * p.z;
-        s[4] += p.w * v.x;
-        s[5] += p.w * v.y;
-        s[6] += p.w * v.z;
-    }
-    for (int half = 32; half >= 1; half >>= 1)
-        for (int c = 0; c < 7; ++c) s[c] += __shfl_down(s[c], half, 64);   // (lanes >= half carry sums nobody reads)
+    double s[7];
+    fof::seven_sums<F>(pos, vel, members + off, cnt, nullptr, lane, s);
     if (lane == 0) {
         NbodyGroup r;
         r.first = root;

@@ -542,7 +542,7 @@ int nbody_merge_contacts(NbodyHandle* h, double radius, NbodyContact* list, size
     return nbody32::merge_contacts(h, radius, list, cap, n_contacts);
 }
 
-// ---- friends-of-friends groups (nbody_fof.cpp): two read-only calls under the census's contract
+// ---- friends-of-friends groups and their self-bound subsets (nbody_fof.cpp): three read-only calls under the census's contract
 namespace {
 int fof_enter(NbodyHandle* h, const char* call, double linking_length) {
     int rc = diag_enter(h, call);
@@ -567,6 +567,20 @@ int nbody_fof_groups(NbodyHandle* h, double linking_length, int min_members, Nbo
     if (min_members < 1) return fail(h, NBODY_ERR_INVALID, "nbody_fof_groups: min_members must be >= 1");
     return with_bodies(h, [&](auto& b) {
         return nbody::fof::groups(h, b.sh, b.n_local, linking_length, min_members, groups, group_cap, n_groups, members, member_cap, n_members);
+    });
+}
+
+int nbody_fof_bound_groups(NbodyHandle* h, double linking_length, int min_members, int max_iterations, NbodyBoundGroup* groups,
+                           size_t group_cap, size_t* n_groups, int32_t* members, size_t member_cap, size_t* n_members, double* energy) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = fof_enter(h, "nbody_fof_bound_groups", linking_length);
+    if (rc) return rc;
+    if (min_members < 2) return fail(h, NBODY_ERR_INVALID, "nbody_fof_bound_groups: min_members must be >= 2");
+    if (max_iterations < 1 || max_iterations > 1024)
+        return fail(h, NBODY_ERR_INVALID, "nbody_fof_bound_groups: max_iterations must be in 1 .. 1024");
+    return with_bodies(h, [&](auto& b) {
+        return nbody::fof::bound_groups(h, b.sh, b.n_local, double(b.g), double(b.g_soft), linking_length, min_members, max_iterations,
+                                        groups, group_cap, n_groups, members, member_cap, n_members, energy);
     });
 }
 

@@ -16,5 +16,12 @@ int labels(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double linking_l
 template <class F>
 int groups(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double linking_length, int min_members, NbodyGroup* groups,
            size_t group_cap, size_t* n_groups, int32_t* members, size_t member_cap, size_t* n_members);
+// nbody_fof_bound_groups: groups' catalogue, then evaluation passes (kernels_unbind.h) until no listed group has an unbound
+// member or max_iterations is reached; one integer crosses to the host per pass.  The caller has also checked min_members >= 2
+// and 1 <= max_iterations <= 1024.
+template <class F>
+int bound_groups(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, double g_soft, double linking_length, int min_members,
+                 int max_iterations, NbodyBoundGroup* groups, size_t group_cap, size_t* n_groups, int32_t* members, size_t member_cap,
+                 size_t* n_members, double* energy);
 
 }}  // namespace nbody::fof

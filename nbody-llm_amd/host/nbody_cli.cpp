@@ -17,7 +17,10 @@
 // --merge RADIUS[:EVERY] runs nbody_merge_contacts after every EVERY-th step (default 1: sticky spheres of that merge distance)
 // and prints how many bodies were absorbed, in how many calls, on a line of its own; --fof B[:MIN] prints the friends-of-friends
 // groups of the final state for the linking length B (nbody_fof_groups): how many have at least MIN members (default 2), the
-// members and the mass of the largest, and the fraction of bodies in no listed group; --pair-search cells lets --merge and
+// members and the mass of the largest, and the fraction of bodies in no listed group; --fof-bound ITER (with --fof) prints one
+// more line after it: the self-bound subsets of those groups after at most ITER unbinding passes (nbody_fof_bound_groups, at
+// least max(MIN, 2) members): how many groups, their members, how many FoF groups dissolved, and the members, kinetic and
+// potential energy of the largest; --pair-search cells lets --merge and
 // --fof find their pairs over the cells of a uniform grid (nbody_set_pair_search: the same results) and prints what the last
 // such call gridded on a line of its own; --density R[:tophat|spline] (default spline) prints the density centre of the final
 // state (nbody_density_center), the largest density and its body (nbody_density) and the half-mass Lagrangian radius about
@@ -46,6 +49,7 @@ static void usage() {
                  "                 [--pairs]   (the mutual bound pairs of the final state: count, binding energy, the hardest pair)\n"
                  "                 [--merge RADIUS[:EVERY]]   (after every EVERY-th step, merge the mutual nearest pairs closer than RADIUS)\n"
                  "                 [--fof B[:MIN]]   (the friends-of-friends groups of the final state: linking length B, at least MIN members, default 2)\n"
+                 "                 [--fof-bound ITER]   (with --fof: the self-bound subsets of those groups after at most ITER unbinding passes)\n"
                  "                 [--density R[:tophat|spline]]   (the density centre of the final state, the largest density, r50 about that centre)\n"
                  "                 [--pair-search all|cells]   (how --merge, --fof and --density find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
@@ -113,6 +117,22 @@ static void print_fof(Sim& sim, double b, int min_members) {
                 groups.empty() ? 0.0 : groups[big].mass, n ? double(n - members.size()) / double(n) : 0.0);
 }
 
+// the line of --fof-bound: nbody_fof_bound_groups on the groups of at least max(min_members, 2) bodies; the largest bound group
+// is the one of most bound members (the first of equals)
+template <class Sim>
+static void print_fof_bound(Sim& sim, double b, int min_members, int max_iterations) {
+    const int least = min_members > 2 ? min_members : 2;
+    std::vector<int32_t> members;
+    std::vector<double> energy;
+    const size_t fof_groups = sim.fof_groups(b, members, least).size();
+    const std::vector<NbodyBoundGroup> groups = sim.fof_bound_groups(b, members, energy, least, max_iterations);
+    size_t big = 0;
+    for (size_t k = 1; k < groups.size(); ++k) if (groups[k].count > groups[big].count) big = k;
+    std::printf("FoF bound groups: %zu members %zu dissolved %zu largest %d kinetic %.9e potential %.9e\n", groups.size(), members.size(),
+                fof_groups - groups.size(), groups.empty() ? 0 : groups[big].count, groups.empty() ? 0.0 : groups[big].kinetic,
+                groups.empty() ? 0.0 : groups[big].potential);
+}
+
 // the line of --density: nbody_density_center, nbody_density (the densest body: the first of equals) and the half-mass
 // Lagrangian radius about the density centre
 template <class Sim>
@@ -134,7 +154,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
-               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int pair_search,
+               bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
                double density_radius, int density_kernel) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
@@ -202,6 +222,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (diagnostics || pairs) print_pairs(*sim);
         if (merge_radius > 0.0) std::printf("Merged: %zu bodies in %zu calls\n", merged, merge_calls);
         if (fof_b > 0.0) print_fof(*sim, fof_b, fof_min);
+        if (fof_b > 0.0 && fof_bound > 0) print_fof_bound(*sim, fof_b, fof_min, fof_bound);
         if (density_radius > 0.0) print_density(*sim, density_radius, density_kernel);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
@@ -244,7 +265,7 @@ int main(int argc, char** argv) {
     size_t merge_every = 1;
     double fof_b = 0.0;
     int pair_search = NBODY_SEARCH_ALL_PAIRS;
-    int fof_min = 2;
+    int fof_min = 2, fof_bound = 0;
     double density_radius = 0.0;
     int density_kernel = NBODY_KERNEL_CUBIC_SPLINE;
     for (int i = 1; i < argc; ++i) {
@@ -295,6 +316,10 @@ int main(int argc, char** argv) {
                 if (fof_min < 1) { usage(); return 2; }
             }
         }
+        else if (!std::strcmp(argv[i], "--fof-bound")) {
+            fof_bound = std::atoi(next());
+            if (fof_bound < 1 || fof_bound > 1024) { usage(); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -337,7 +362,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--external needs the leapfrog (the Hermite step would need the field's jerk)\n");
         return 2;
     }
+    if (fof_bound && !(fof_b > 0.0)) {
+        std::fprintf(stderr, "--fof-bound needs --fof\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search, density_radius, density_kernel);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, pair_search, density_radius, density_kernel);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel);
 }

@@ -320,6 +320,23 @@ public:
         members.resize(n_members);
         return groups;
     }
+    // the self-bound subsets of those groups (nbody_fof_bound_groups): every member's energy inside its own group, the unbound
+    // stripped at once, repeated until nobody is unbound or max_iterations passes have run; groups left with fewer than
+    // min_members (>= 2) bodies are dropped.  members and energy (the e of the group's last pass) are parallel
+    std::vector<NbodyBoundGroup> fof_bound_groups(double b, std::vector<int32_t>& members, std::vector<double>& energy, int min_members = 2,
+                                                  int max_iterations = 32) {
+        size_t n = 0, n_groups = 0, n_members = 0;
+        check(nbody_fof_labels(h_, b, nullptr, 0, &n, nullptr));   // (the bodies only: an upper bound of both counts)
+        std::vector<NbodyBoundGroup> groups(n / size_t(min_members > 0 ? min_members : 1) + 1);
+        members.assign(n + 1, -1);
+        energy.assign(n + 1, 0.0);
+        check(nbody_fof_bound_groups(h_, b, min_members, max_iterations, groups.data(), groups.size(), &n_groups, members.data(),
+                                     members.size(), &n_members, energy.data()));
+        groups.resize(n_groups);
+        members.resize(n_members);
+        energy.resize(n_members);
+        return groups;
+    }
     // neighbours within a radius (nbody_neighbors_within, nbody_density, nbody_density_center): f64 unsoftened distances on
     // either F, strictly inside the radius; read-only, the handles moments() takes.  The neighbours of body i are
     // neighbor[offset[i] .. offset[i + 1]) in ascending index; offset has n + 1 entries
