@@ -879,11 +879,82 @@ int nbody_neighbors_within(NbodyHandle* h, double radius, uint64_t* offset /* [n
                            int32_t* neighbor /* may be NULL: count only */, size_t neighbor_cap, size_t* n_out, uint64_t* n_neighbors_out);
 int nbody_density(NbodyHandle* h, double radius, int kernel, double* rho, int32_t* count, size_t cap, size_t* n_out);
 int nbody_density_center(NbodyHandle* h, double radius, int kernel, double center[3], double* rho_sum);
+/* ---- pair-separation counts: how many pairs stand at each separation (no reference counterpart) -----
+ * The calls above answer a question about one threshold.  These two count the pairs in every bin of separation at once --
+ * DD(r), what the two-point correlation function, the radial distribution function and the correlation dimension are computed
+ * from; the cross form (bodies against caller points) is the DR term of the Landy-Szalay estimator and, with one point, the
+ * number profile in shells about a centre.  Two READ-ONLY calls under the exact contract of nbody_nearest and nbody_fof_labels
+ * (the bodies are what nbody_download would report -- on a Hermite handle the held (x0, v0) --, tracers and the external field
+ * play no part, no trace in state, NbodyStats, validity flags, levels or the bits of any later step, no refresh of the host's
+ * view of the count beyond what nbody_neighbors_within does -- none --, launches sized from its upper bound and the live count
+ * read on the device: right after a retain with no nbody_count in between, scratch through the handle's registry and freed
+ * inside the call).  THE RESULT IS INTEGERS ONLY: it is exact, and it does not depend on launch shape, scheduling, the
+ * bf64_waves, pair_hist_combine and pair_hist_flush knobs or the search mode.  No floating-point atomics anywhere.
+ *   THE EDGES: n_bins + 1 of them, 1 <= n_bins <= NBODY_PAIR_COUNT_MAX_BINS.  E2[b] = edges[b] * edges[b], each rounded once in
+ * f64.  Valid: every edge finite, edges[0] >= 0, every E2[b] finite and E2 STRICTLY ascending -- the squares, not the edges:
+ * that is what rules out ties after rounding (1e-200 and 2e-200 both square to 0) and overflow (1e200).  Anything else, and
+ * counts == NULL, is NBODY_ERR_INVALID and nbody_last_error names the call.
+ *   THE METRIC is nbody_nearest's, formed as csrc/kernels_pairs.hip forms it, f64 on either dtype (an NBODY_F32 handle's
+ * positions are widened exactly), unsoftened, nothing contracted into an FMA:
+ *     d = x_j - x_i,  r2 = (dx dx + dy dy) + dz dz
+ *   THE BIN RULE: the pair is counted in bin b iff E2[b] <= r2 && r2 < E2[b + 1] -- closed below, open above.  outside[0]
+ * counts the pairs with r2 < E2[0]; outside[1] counts everything else, !(r2 < E2[n_bins]): a NaN or +inf separation (a body
+ * with a non-finite coordinate) lands there and in no bin.  outside may be NULL.
+ *   nbody_pair_counts covers every unordered pair i < j of live bodies, once.  INVARIANT:
+ *     sum(counts) + outside[0] + outside[1] == n (n - 1) / 2       for the live count n, always.
+ *   nbody_pair_counts_at covers every (body, point) pair, n m of them, with d = point - body, the same metric and the same
+ * rule; a point that coincides with a body is a pair of r2 = 0 like any other (bin 0 when edges[0] == 0).  INVARIANT: the sum
+ * is n m.  m == 0 is valid and gives all zeros; points == NULL with m > 0 is NBODY_ERR_INVALID; non-finite point coordinates
+ * are allowed and land in outside[1].  points: m rows of {x, y, z} as doubles.
+ *   Counts are 64 bits end to end: THERE IS NO CAPACITY REFUSAL (today's other route to DD(r), nbody_neighbors_within once per
+ * edge, is refused as soon as a radius holds more than 2^31 - 1 directed neighbours).
+ *   PAIR SEARCH: nbody_pair_counts reads nbody_set_pair_search (below).  Under NBODY_SEARCH_CELLS the grid is drawn for the
+ * length |edges[n_bins]| and only the 27 surrounding cells are examined: every pair with r2 < E2[n_bins] is a candidate pair
+ * there; outside[1] is then n (n - 1) / 2 less everything the walk counted, an integer subtraction -- bodies that cannot be
+ * gridded are there by construction.  The record behind nbody_pair_search_stats is what the call leaves, with the candidates
+ * counted as nbody_fof_labels counts them; a grid that cannot be drawn falls back to all pairs, as everywhere else.
+ * nbody_pair_counts_at ALWAYS looks at all pairs and does not touch the record: a cell search for foreign points is out of
+ * scope here.
+ *   HOW: k_pair_hist (csrc/kernels_paircount.hip) on nbody_nearest's frame -- one body per lane, the partners (the bodies, or
+ * the caller's points in batches of 2^20) through LDS in tiles of 256, groups of 256 bodies x K slices sized by bf64_waves;
+ * in nbody_pair_counts a lane counts only j > i and whole tiles below a block's first row are skipped, so the work is N^2 / 2
+ * pair terms.  E2 stands in LDS; the bin is a branch-free binary search over it, ceil(log2(n_bins)) steps, 10 for 1 024 bins.
+ * Counts go to a block-private LDS histogram of 32-bit words with LDS integer atomics; the block adds its words to the call's
+ * 64-bit array with vector integer atomics at its end -- and after every 65 535 tiles: 256 lanes x 256 partners x T tiles put
+ * at most 65 536 T counts into one word, and 65 536 x 65 535 = 2^32 - 65 536 < 2^32 (the pair_hist_flush knob lowers T).  In a
+ * clustered world most pairs fall into few bins and the lanes of a wave meet on one LDS word; the pair_hist_combine knob
+ * selects the remedy: 0 none, 1 the lanes that share the first counting lane's slot add their number once (two ballots), 2
+ * every distinct slot of the wave does.  Under NBODY_SEARCH_CELLS k_cells_pair_hist (csrc/kernels_cells.hip) walks
+ * nbody_fof_labels' half of the 27 cells, every candidate pair once, with the same bin function and the same histogram; a
+ * lane there sends its counts beyond the first 256 T straight to the 64-bit array, which keeps the same bound.
+ *   COST: all pairs: N^2 / 2 (n m) f64 pair terms of 3 subtractions, 3 products and 2 sums, each followed by 2 + ceil(log2(n_bins))
+ * LDS reads and compares and one LDS atomic.  NOT MEASURED on an MI355X beyond the single run of tools/pair_counts_bench.py
+ * that DESIGN 3.22 records (f32 brute-force handles, log bins from 1e-3 to 32, whole calls): at 262 144 bodies of a Plummer
+ * world about 0.184 s with 32 bins and 0.305 s with 1 024, 6.1 and 10.2 times nbody_nearest on the same handle (0.030 s, and
+ * twice the pair terms); at 65 536 bodies 0.024 s and 0.040 s, 8.8 and 14.9 times.  A clumpy world with a third of its pairs
+ * in one bin took the same time within 1.5 %: contention on the LDS words is not the limit, both combining forms of
+ * pair_hist_combine were slower (1: by 10 to 14 %, 2: by a factor 1.8 to 4.8) and 0 is the default.  Over the cells with a
+ * last edge of two mean spacings: 1.2 to 1.5 ms at 262 144 Plummer bodies, 12 to 20 ms in the clumpy world.  What limits the
+ * all-pairs kernel has not been measured; nothing asserts or promises a time.
+ *   Accepted and refused exactly where nbody_fof_labels is: every world_size == 1, NBODY_SHARD_INDEX handle is accepted (both
+ * dtypes, both methods, either math mode, any tree build, leapfrog or Hermite, block steps on or off, with or without tracers,
+ * an external field or quadrupoles).  Refused with NBODY_ERR_INVALID (nbody_last_error names the call): invalid edges or n_bins
+ * as above; NULL counts; NULL points with m > 0; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle
+ * is refused without touching a device.
+ *   OUT OF SCOPE: weighted (mass- or velocity-product) histograms -- they need a fixed-order float sum; periodic boundaries; a
+ * cell search for nbody_pair_counts_at; multi-rank handles; the estimators built from the counts (xi, g(r)) -- README has the
+ * two-line recipe. */
+#define NBODY_PAIR_COUNT_MAX_BINS 1024
+int nbody_pair_counts(NbodyHandle* h, const double* edges /* [n_bins + 1] */, int n_bins, uint64_t* counts /* [n_bins] */,
+                      uint64_t outside[2] /* may be NULL */);
+int nbody_pair_counts_at(NbodyHandle* h, const double* points /* [m][3] f64 */, size_t m, const double* edges, int n_bins,
+                         uint64_t* counts, uint64_t outside[2] /* may be NULL */);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
- * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density and
- * nbody_density_center ask a FIXED-RADIUS question: only bodies closer than the linking length or the radius can matter.
- * nbody_set_pair_search selects how these seven calls find such pairs; nothing else reads the setting (nbody_nearest,
- * nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs).
+ * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
+ * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
+ * radius or the last bin edge can matter.  nbody_set_pair_search selects how these eight calls find such pairs; nothing else
+ * reads the setting (nbody_nearest, nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs;
+ * nbody_pair_counts_at always looks at all pairs).
  *   NBODY_SEARCH_ALL_PAIRS (the default) is the code as it stands: a handle that never sets the mode runs it untouched.
  *   NBODY_SEARCH_CELLS sorts the bodies by the cell of a uniform grid and looks at the 27 surrounding cells only.  THE GRID IS
  * NOT A TREE -- one level, cells of one size, no opening criterion, nothing approximated -- AND IT CHANGES NO RESULT: all four
@@ -896,7 +967,7 @@ int nbody_density_center(NbodyHandle* h, double radius, int kernel, double cente
  *   THE GRID (csrc/cell_grid.h, restated in tests/cells_ref.py), all f64, every operation rounded on its own:
  *     a body is GRIDDED iff its three coordinates are finite (an NBODY_F32 handle's are widened exactly);
  *     lo_c, hi_c = min and max of the gridded bodies' coordinate c (a zero bound counts as +0.0);  E = max_c (hi_c - lo_c);
- *     side = max(length * (1 + 2^-20), E * 2^-20)         (length: the linking length or the radius of the call)
+ *     side = max(length * (1 + 2^-20), E * 2^-20)         (length: the linking length, the radius or |edges[n_bins]| of the call)
  *     k_c  = min((uint64) floor((x_c - lo_c) / side), 2^21 - 1);   key = k_x << 42 | k_y << 21 | k_z
  *     usable = isfinite(E) && isfinite(side) && isfinite(length * length)
  * A CANDIDATE PAIR is an unordered pair of gridded bodies whose cell indices differ by at most 1 on every axis.  Every pair
@@ -932,7 +1003,8 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
 /* ---- launch-shape and scheme knobs of one handle (no reference counterpart) --------------------------------- */
 /* Per handle; the library exports no mutable globals.  Names (csrc/kernels.h struct Tuning): cross_sym, sym_packed,
  * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, sym_opp_rot, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
- * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8),
+ * pair_hist_combine, pair_hist_flush (nbody_pair_counts and nbody_pair_counts_at: they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

@@ -63,8 +63,9 @@ LEAPFROG, HERMITE4 = 0, 1   # nbody_set_integrator: the reference's leapfrog | f
 SHARD_INDEX, SHARD_SPATIAL = 0, 1   # index blocks + all-gather | Morton-key ranges + halo exchange (Barnes-Hut, fast math)
 EXTERNAL_MAX = 8   # nbody_set_external_field: components of a static external field, and their kinds
 EXT_PLUMMER, EXT_HERNQUIST, EXT_MIYAMOTO_NAGAI, EXT_LOGARITHMIC = 0, 1, 2, 3
-SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how the fixed-radius calls (fof_*, contacts, neighbors_within, density*) find their pairs
+SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how the fixed-radius calls (fof_*, contacts, neighbors_within, density*, pair_counts) find their pairs
 KERNEL_TOP_HAT, KERNEL_CUBIC_SPLINE = 0, 1   # nbody_density / nbody_density_center: the mass in the sphere over its volume | the M4 spline
+PAIR_COUNT_MAX_BINS = 1024   # nbody_pair_counts / nbody_pair_counts_at: the most bins of one call (NBODY_PAIR_COUNT_MAX_BINS)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -95,6 +96,7 @@ DECLARED_SYMBOLS = [
     "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
     "nbody_fof_labels", "nbody_fof_groups", "nbody_fof_bound_groups",
     "nbody_neighbors_within", "nbody_density", "nbody_density_center",
+    "nbody_pair_counts", "nbody_pair_counts_at",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -289,6 +291,8 @@ _sig("nbody_fof_bound_groups", _i, _H, C.c_double, _i, _i, C.c_void_p, _sz, C.PO
 _sig("nbody_neighbors_within", _i, _H, C.c_double, C.c_void_p, _sz, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
 _sig("nbody_density", _i, _H, C.c_double, _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_density_center", _i, _H, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("nbody_pair_counts", _i, _H, C.c_void_p, _i, C.c_void_p, C.c_void_p)
+_sig("nbody_pair_counts_at", _i, _H, C.c_void_p, _sz, C.c_void_p, _i, C.c_void_p, C.c_void_p)
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -779,10 +783,35 @@ class Simulation:
         self._check(lib.nbody_density_center(self._h, float(radius), int(kernel), center, C.byref(total)))
         return np.array(center[:], np.float64), float(total.value)
 
+    # -- pair-separation counts (nbody_pair_counts, nbody_pair_counts_at): integers, read-only, on the device
+    def pair_counts(self, edges) -> tuple[np.ndarray, np.ndarray]:
+        """(counts [n_bins] uint64, outside [2] uint64): the unordered pairs i < j of bodies whose unsoftened f64 squared
+        separation r2 has edges[b]**2 <= r2 < edges[b + 1]**2; outside = the pairs below edges[0]**2 and everything else
+        (beyond the last edge, or not finite).  counts.sum() + outside.sum() == n (n - 1) / 2.  Honours pair_search
+        (nbody_pair_counts)."""
+        edges = np.ascontiguousarray(edges, np.float64).reshape(-1)
+        n_bins = len(edges) - 1
+        counts = np.zeros(max(n_bins, 0), np.uint64)
+        outside = np.zeros(2, np.uint64)
+        self._check(lib.nbody_pair_counts(self._h, edges.ctypes.data, n_bins, counts.ctypes.data, outside.ctypes.data))
+        return counts, outside
+
+    def pair_counts_at(self, points, edges) -> tuple[np.ndarray, np.ndarray]:
+        """(counts [n_bins] uint64, outside [2] uint64): the same over every (body, point) pair, d = point - body, for points
+        [m][3] f64; always over all pairs.  counts.sum() + outside.sum() == n m (nbody_pair_counts_at)."""
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        edges = np.ascontiguousarray(edges, np.float64).reshape(-1)
+        n_bins = len(edges) - 1
+        counts = np.zeros(max(n_bins, 0), np.uint64)
+        outside = np.zeros(2, np.uint64)
+        self._check(lib.nbody_pair_counts_at(self._h, points.ctypes.data if len(points) else None, len(points), edges.ctypes.data, n_bins,
+                                             counts.ctypes.data, outside.ctypes.data))
+        return counts, outside
+
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits
     @property
     def pair_search(self) -> int:
-        """How fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density and density_center find their pairs: SEARCH_ALL_PAIRS (0, the default) or
+        """How fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs: SEARCH_ALL_PAIRS (0, the default) or
         SEARCH_CELLS (1: bodies sorted by the cell of a uniform grid).  It changes no result; clone() carries it."""
         v = C.c_int(0)
         self._check(lib.nbody_get_pair_search(self._h, C.byref(v)))

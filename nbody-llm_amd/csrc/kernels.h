@@ -39,6 +39,9 @@ struct Tuning {
     int bf64_ipt = 0;           // k_bf64_sym: bodies per lane of a resident set: 0 from the block's size (kernels_f64.h), 4, 8
     int bf64_rot = 0;           // k_bf64_sym: 0 = the chunk's positions in LDS, only the accumulators rotate; 1 = positions rotate too
     int bf64_waves = 0;         // f64 fast brute force: waves a launch's slices are sized for; 0 = 2048
+    int pair_hist_combine = 0;  // k_pair_hist: lanes of a wave that hit one slot at the same partner: 0 each adds its own 1, 1 the first counting lane's
+                                // slot is added once for all its lanes, 2 every distinct slot is (kernels_paircount.h hist_add)
+    int pair_hist_flush = 0;    // k_pair_hist / k_cells_pair_hist: tiles of 256 partners between two flushes of a block's LDS words; 0 = 65 535, the most
     // the following select code that only the tuning build carries (make -C csrc tuning: -DNBODY_TUNING); the release
     // library refuses any value but the default
     int bh_walk_variant = 0;    // 1 wave-cooperative, 2 two lanes per body, 3 hot records in LDS, 4 cooperative window, 5 cooperative block walk  [NBODY_BH_VARIANT]

@@ -67,4 +67,10 @@ void launch_within_count(hipStream_t s, int n_upper, int n_gridded, double R2, c
 // cap: the words of raw
 void launch_within_fill(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, const int* offset, int* raw, size_t cap);
 
+// k_cells_pair_hist: every candidate pair with r2 < e2[n_bins] added to hist[slot of its r2] (kernels_paircount.h: slot 0 below
+// e2[0], slot b + 1 bin b; hist[n_bins + 1] is left alone: the caller subtracts); e2 [n_bins + 1] and hist [n_bins + 2] on the
+// device; flush_tiles: HistPlan's; w.counters->candidates as launch_link_components counts them
+void launch_pair_hist(hipStream_t s, int n_upper, int n_gridded, const CellScratch& w, const double* e2, int n_bins, int flush_tiles,
+                      unsigned long long* hist);
+
 }}  // namespace nbody::cells

@@ -21,9 +21,12 @@
 //                    rule on (r2, index) alone, so the order in which cells are visited cannot show
 //   k_cells_within   k_cells_nearest's walk for the neighbour lists of kernels_within.h: a pass that counts every body's
 //                    neighbours with r2 < R2, and after the caller's integer scan a pass that writes their ORIGINAL indices
+//   k_cells_pair_hist  k_cells_link's walk for the binned pair counts of kernels_paircount.h: every candidate pair once, its r2
+//                    binned by bin_slot, counted in a block-private LDS histogram that is added to the call's 64-bit slots
 // The walks count their candidate pairs (place t after place s) in integers: shuffles, then one atomicAdd per wave.
 #include "kernels_cells.h"
 #include "fof_union.h"
+#include "kernels_paircount.h"   // bin_slot, hist_begin, hist_flush
 #include "real.h"      // widen
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -247,6 +250,49 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_within(int n_gridded, cons
     }
 }
 
+// The binned pair counts of kernels_paircount.h over k_cells_link's walk: every candidate pair is evaluated once, from its
+// earlier place (the body with the lower original row of the two when they share a cell), and counted in the slot of its r2 --
+// but for the last slot: the pairs with !(r2 < E2[n_bins]) are not all candidates, so the caller obtains their number by
+// subtraction.  A lane's first lane_budget counts go to the block's LDS words, any further one straight to the 64-bit slots
+// (kernels_paircount.h: the overflow bound); the block adds its words at its end.
+__global__ __launch_bounds__(kPairBlock) void k_cells_pair_hist(int n_gridded, const uint64_t* __restrict__ keys,
+                                                                const double4* __restrict__ spos, const double* __restrict__ e2_global,
+                                                                int n_bins, int top, unsigned lane_budget, unsigned long long* out,
+                                                                cells::Counters* counters) {
+    __shared__ double e2[paircount::kMaxBins + 1];
+    __shared__ unsigned hist[paircount::kSlots];
+    paircount::hist_begin(e2_global, n_bins, e2, hist);
+    __syncthreads();
+    const int s = blockIdx.x * kPairBlock + threadIdx.x;
+    unsigned long long cand = 0;
+    if (s < n_gridded) {
+        const uint64_t key = keys[s];
+        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
+        const uint64_t kz = key & kCellMax;
+        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;   // clamped at the walls
+        const double4 pi = spos[s];
+        unsigned used = 0;
+        for (int c = 0; c < 5; ++c) {   // (0, 0) | (0, +1) | (+1, -1), (+1, 0), (+1, +1)
+            const int dx = c >= 2, dy = c == 0 ? 0 : c == 1 ? 1 : c - 3;
+            int a, b;
+            if (!column_range(keys, s + 1, n_gridded, kx + dx, ky + dy, c == 0 ? kz : z0, z1, &a, &b)) continue;
+            cand += (unsigned long long)(b - a);
+            for (int t = a; t < b; ++t) {
+                const int slot = paircount::bin_slot(e2, n_bins, top, fof::pair_dist2(pi, spos[t]));
+                if (slot > n_bins) continue;   // (beyond the last edge, or a NaN: counted by subtraction)
+                if (used < lane_budget) {
+                    atomicAdd(hist + slot, 1u);
+                    ++used;
+                } else {
+                    atomicAdd(out + slot, 1ull);
+                }
+            }
+        }
+    }
+    paircount::hist_flush(hist, n_bins, out);
+    wave_add(cand, &counters->candidates);
+}
+
 namespace cells {
 
 size_t bounds_of(const BoundsWords& w, double lo[3], double hi[3]) {
@@ -340,6 +386,14 @@ void launch_within_fill(hipStream_t s, int n_upper, int n_gridded, double R2, co
     hipLaunchKernelGGL(k_cells_within<true>, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
                        w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, R2, static_cast<int*>(nullptr), offset, raw,
                        unsigned(cap), static_cast<unsigned long long*>(nullptr), static_cast<Counters*>(nullptr));
+}
+
+void launch_pair_hist(hipStream_t s, int n_upper, int n_gridded, const CellScratch& w, const double* e2, int n_bins, int flush_tiles,
+                      unsigned long long* hist) {
+    if (n_upper <= 0 || n_gridded <= 0) return;
+    hipLaunchKernelGGL(k_cells_pair_hist, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
+                       w.sorted_keys(size_t(n_upper)), w.spos, e2, n_bins, paircount::search_top(n_bins),
+                       unsigned(flush_tiles) * unsigned(kPairBlock), hist, w.counters);
 }
 
 template void launch_bounds<float>(hipStream_t, const ShardT<float>&, int, BoundsWords*);

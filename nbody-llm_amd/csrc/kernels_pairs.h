@@ -15,6 +15,8 @@ inline int blocks_for(int n) { return n <= 0 ? 0 : (n + kPairBlock - 1) / kPairB
 // (make_hm_act_plan's rule: a slice holds 64 partners or more); slice s of n live bodies is [n s / K, n (s + 1) / K)
 struct PartnerPlan { int groups = 0, K = 1; };
 PartnerPlan make_partner_plan(int n_upper);
+// the same rule for n_upper bodies against `partners` partners that are not the bodies themselves (k_pair_hist's cross form)
+PartnerPlan make_partner_plan(int n_upper, int partners);
 
 // The scratch of one call for n_upper rows, carved out of one allocation of scratch_bytes.
 struct PairScratch {

@@ -226,12 +226,14 @@ __global__ __launch_bounds__(kPairBlock) void k_contact_emit(typename Real<F>::V
 
 namespace pairs {
 
-PartnerPlan make_partner_plan(int n_upper) {
+PartnerPlan make_partner_plan(int n_upper) { return make_partner_plan(n_upper, n_upper); }
+
+PartnerPlan make_partner_plan(int n_upper, int partners) {
     PartnerPlan p;
     const int want = nbody::tuning().bf64_waves > 0 ? nbody::tuning().bf64_waves : 2048;
     p.groups = blocks_for(n_upper);
     const int waves = p.groups * (kPairBlock / 64);
-    p.K = std::max(1, std::min(want / std::max(1, waves), (n_upper + 63) / 64));   // (a slice holds 64 partners or more)
+    p.K = std::max(1, std::min(want / std::max(1, waves), (partners + 63) / 64));   // (a slice holds 64 partners or more)
     return p;
 }
 

@@ -12,6 +12,7 @@
 #include "nbody_pairs.h"
 #include "nbody_fof.h"
 #include "nbody_within.h"
+#include "nbody_paircount.h"
 #include "nbody_cells.h"
 
 #include <algorithm>
@@ -625,7 +626,38 @@ int nbody_density_center(NbodyHandle* h, double radius, int kernel, double cente
     return with_bodies(h, [&](auto& b) { return nbody::within::density_center(h, b.sh, b.n_local, radius, kernel, center, rho_sum); });
 }
 
-// ---- pair search (nbody_cells.cpp): a setting of the handle that the seven fixed-radius calls above read, and their record
+// ---- pair-separation counts (nbody_paircount.cpp): two read-only calls under the census's contract
+namespace {
+int pair_counts_enter(NbodyHandle* h, const char* call, const double* edges, int n_bins, const uint64_t* counts, std::vector<double>* e2) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    const std::string why = nbody::paircount::squared_edges(edges, n_bins, e2);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    if (!counts) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": counts is NULL");
+    return NBODY_OK;
+}
+}  // namespace
+
+int nbody_pair_counts(NbodyHandle* h, const double* edges, int n_bins, uint64_t* counts, uint64_t outside[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    std::vector<double> e2;
+    int rc = pair_counts_enter(h, "nbody_pair_counts", edges, n_bins, counts, &e2);
+    if (rc) return rc;
+    const double length = std::fabs(edges[n_bins]);   // (its square is E2[n_bins], the largest)
+    return with_bodies(h, [&](auto& b) { return nbody::paircount::pair_counts(h, b.sh, b.n_local, e2, length, counts, outside); });
+}
+
+int nbody_pair_counts_at(NbodyHandle* h, const double* points, size_t m, const double* edges, int n_bins, uint64_t* counts,
+                         uint64_t outside[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    std::vector<double> e2;
+    int rc = pair_counts_enter(h, "nbody_pair_counts_at", edges, n_bins, counts, &e2);
+    if (rc) return rc;
+    if (m && !points) return fail(h, NBODY_ERR_INVALID, "nbody_pair_counts_at: points is NULL");
+    return with_bodies(h, [&](auto& b) { return nbody::paircount::pair_counts_at(h, b.sh, b.n_local, points, m, e2, counts, outside); });
+}
+
+// ---- pair search (nbody_cells.cpp): a setting of the handle that the eight fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
     if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
@@ -1151,6 +1183,7 @@ const Knob kKnobs[] = {
     {"tree_max_tie", &nbody::Tuning::tree_max_tie, false},
     {"bf64_min_bodies", &nbody::Tuning::bf64_min_bodies, false}, {"bf64_ipt", &nbody::Tuning::bf64_ipt, false},
     {"bf64_rot", &nbody::Tuning::bf64_rot, false}, {"bf64_waves", &nbody::Tuning::bf64_waves, false},
+    {"pair_hist_combine", &nbody::Tuning::pair_hist_combine, false}, {"pair_hist_flush", &nbody::Tuning::pair_hist_flush, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},

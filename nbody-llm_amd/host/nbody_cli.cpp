@@ -24,7 +24,12 @@
 // --fof find their pairs over the cells of a uniform grid (nbody_set_pair_search: the same results) and prints what the last
 // such call gridded on a line of its own; --density R[:tophat|spline] (default spline) prints the density centre of the final
 // state (nbody_density_center), the largest density and its body (nbody_density) and the half-mass Lagrangian radius about
-// that centre, on a line of its own, and honours --pair-search.
+// that centre, on a line of its own, and honours --pair-search; --pair-counts LO:HI:BINS[:log|lin] (default log, which needs
+// LO > 0) prints the binned pair-separation counts of the final state (nbody_pair_counts), one line per bin with its two edges
+// and its count, then the `outside` line, and honours --pair-search.  The BINS + 1 edges are formed here in f64:
+//     edges[0] = LO,  edges[BINS] = HI,  and for 0 < b < BINS
+//     lin: edges[b] = LO + (HI - LO) * (double(b) / double(BINS))      log: edges[b] = LO * pow(HI / LO, double(b) / double(BINS))
+// and printed with 17 significant digits, which name each double exactly.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -51,7 +56,8 @@ static void usage() {
                  "                 [--fof B[:MIN]]   (the friends-of-friends groups of the final state: linking length B, at least MIN members, default 2)\n"
                  "                 [--fof-bound ITER]   (with --fof: the self-bound subsets of those groups after at most ITER unbinding passes)\n"
                  "                 [--density R[:tophat|spline]]   (the density centre of the final state, the largest density, r50 about that centre)\n"
-                 "                 [--pair-search all|cells]   (how --merge, --fof and --density find their pairs: all pairs, or the cells of a uniform grid)\n");
+                 "                 [--pair-counts LO:HI:BINS[:log|lin]]   (the pairs of the final state per bin of separation; log needs LO > 0)\n"
+                 "                 [--pair-search all|cells]   (how --merge, --fof, --density and --pair-counts find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -149,13 +155,34 @@ static void print_density(Sim& sim, double radius, int kernel) {
                 rho.empty() ? std::nan("") : rho[top], rho.empty() ? -1L : long(top), rho.empty() ? 0 : int(count[top]), radii[0]);
 }
 
+// the edges of --pair-counts (the formula stands at the top of this file)
+static std::vector<double> pair_count_edges(double lo, double hi, int bins, bool log_bins) {
+    std::vector<double> edges(size_t(bins) + 1);
+    for (int b = 0; b <= bins; ++b) {
+        const double f = double(b) / double(bins);
+        edges[size_t(b)] = b == 0 ? lo : b == bins ? hi : log_bins ? lo * std::pow(hi / lo, f) : lo + (hi - lo) * f;
+    }
+    return edges;
+}
+
+// the lines of --pair-counts: nbody_pair_counts over `edges`
+template <class Sim>
+static void print_pair_counts(Sim& sim, const std::vector<double>& edges) {
+    std::vector<uint64_t> counts;
+    uint64_t outside[2] = {0, 0};
+    sim.pair_counts(edges, counts, outside);
+    for (size_t b = 0; b < counts.size(); ++b)
+        std::printf("Pair count: bin %zu %.17e %.17e %llu\n", b, edges[b], edges[b + 1], (unsigned long long)counts[b]);
+    std::printf("Pair counts outside: below %llu beyond %llu\n", (unsigned long long)outside[0], (unsigned long long)outside[1]);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
-               double density_radius, int density_kernel) {
+               double density_radius, int density_kernel, const std::vector<double>& pair_edges) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -224,6 +251,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (fof_b > 0.0) print_fof(*sim, fof_b, fof_min);
         if (fof_b > 0.0 && fof_bound > 0) print_fof_bound(*sim, fof_b, fof_min, fof_bound);
         if (density_radius > 0.0) print_density(*sim, density_radius, density_kernel);
+        if (!pair_edges.empty()) print_pair_counts(*sim, pair_edges);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -268,6 +296,7 @@ int main(int argc, char** argv) {
     int fof_min = 2, fof_bound = 0;
     double density_radius = 0.0;
     int density_kernel = NBODY_KERNEL_CUBIC_SPLINE;
+    std::vector<double> pair_edges;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -320,6 +349,27 @@ int main(int argc, char** argv) {
             fof_bound = std::atoi(next());
             if (fof_bound < 1 || fof_bound > 1024) { usage(); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--pair-counts")) {
+            char* end = nullptr;
+            const char* arg = next();
+            const double lo = std::strtod(arg, &end);
+            if (end == arg || *end != ':') { usage(); return 2; }
+            arg = end + 1;
+            const double hi = std::strtod(arg, &end);
+            if (end == arg || *end != ':') { usage(); return 2; }
+            arg = end + 1;
+            const long bins = std::strtol(arg, &end, 10);
+            if (end == arg || (*end && *end != ':')) { usage(); return 2; }
+            bool log_bins = true;
+            if (*end == ':') {
+                const std::string kind = end + 1;
+                if (kind == "lin") log_bins = false;
+                else if (kind != "log") { usage(); return 2; }
+            }
+            if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo >= 0.0) || !(hi > lo) || bins < 1 || bins > NBODY_PAIR_COUNT_MAX_BINS ||
+                (log_bins && !(lo > 0.0))) { usage(); return 2; }
+            pair_edges = pair_count_edges(lo, hi, int(bins), log_bins);
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -367,6 +417,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges);
 }

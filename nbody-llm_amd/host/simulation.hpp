@@ -367,7 +367,19 @@ public:
         check(nbody_density_center(h_, radius, kernel, center, &sum));
         return sum;
     }
-    // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density and density_center find their pairs
+    // pair-separation counts (nbody_pair_counts, nbody_pair_counts_at): counts[b] = the pairs whose unsoftened f64 squared
+    // separation r2 has edges[b]^2 <= r2 < edges[b + 1]^2 (edges: n_bins + 1 of them), outside = {the pairs below edges[0]^2,
+    // everything else}; integers, read-only, the handles moments() takes.  pair_counts: every pair i < j of bodies, honours
+    // set_pair_search; pair_counts_at: every (body, point) pair for xyz = m points {x, y, z}, always over all pairs
+    void pair_counts(const std::vector<double>& edges, std::vector<uint64_t>& counts, uint64_t outside[2]) {
+        counts.assign(edges.empty() ? 0 : edges.size() - 1, 0);
+        check(nbody_pair_counts(h_, edges.data(), int(edges.size()) - 1, counts.data(), outside));
+    }
+    void pair_counts_at(const std::vector<double>& xyz, const std::vector<double>& edges, std::vector<uint64_t>& counts, uint64_t outside[2]) {
+        counts.assign(edges.empty() ? 0 : edges.size() - 1, 0);
+        check(nbody_pair_counts_at(h_, xyz.data(), xyz.size() / 3, edges.data(), int(edges.size()) - 1, counts.data(), outside));
+    }
+    // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs
     // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
     // last of those calls ran the cell search, bodies gridded, occupied cells, candidate pairs} (nbody_pair_search_stats)
