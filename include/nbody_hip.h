@@ -814,7 +814,7 @@ int nbody_fof_bound_groups(NbodyHandle* h, double linking_length, int min_member
  * tracers and the external field play no part, no trace in state, NbodyStats, validity flags, levels or the bits of any later
  * step, no refresh of the host's view of the count, launches sized from its upper bound and the live count read on the device:
  * right after a retain with no nbody_count in between, scratch through the handle's registry and freed inside the call, no
- * floating-point atomics: the same state gives the same bits).  Fixed radius only: this is not a k-nearest-neighbour search.
+ * floating-point atomics: the same state gives the same bits).  Fixed radius only: every body's k nearest neighbours are nbody_knn's, below.
  *   THE RELATION is nbody_nearest's metric and nbody_contacts' comparison, f64 on either dtype (an NBODY_F32 handle's positions
  * are widened exactly), unsoftened, nothing contracted:
  *     d = x_j - x_i,  r2 = (dx dx + dy dy) + dz dz,  R2 = radius * radius rounded once
@@ -871,7 +871,7 @@ int nbody_fof_bound_groups(NbodyHandle* h, double linking_length, int min_member
  * an external field or quadrupoles).  Refused with NBODY_ERR_INVALID (nbody_last_error names the call): a radius that is not
  * finite or is <= 0; an unknown kernel id; center NULL; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL
  * handle is refused without touching a device.
- *   OUT OF SCOPE: k-nearest neighbours; adaptive smoothing lengths; densities at arbitrary probe points; periodic boundaries;
+ *   OUT OF SCOPE: k nearest neighbours (nbody_knn and nbody_knn_density, below); adaptive smoothing lengths; densities at arbitrary probe points; periodic boundaries;
  * multi-rank or spatial handles; any change to an existing call's results. */
 enum { NBODY_KERNEL_TOP_HAT = 0,        /* the mass inside the sphere over its volume */
        NBODY_KERNEL_CUBIC_SPLINE = 1 }; /* the M4 spline with support `radius` */
@@ -879,6 +879,70 @@ int nbody_neighbors_within(NbodyHandle* h, double radius, uint64_t* offset /* [n
                            int32_t* neighbor /* may be NULL: count only */, size_t neighbor_cap, size_t* n_out, uint64_t* n_neighbors_out);
 int nbody_density(NbodyHandle* h, double radius, int kernel, double* rho, int32_t* count, size_t cap, size_t* n_out);
 int nbody_density_center(NbodyHandle* h, double radius, int kernel, double center[3], double* rho_sum);
+/* ---- k nearest neighbours: every body's exact k nearest bodies, and the Casertano-Hut density (no reference counterpart) -----
+ * Who are my k nearest, however far they are?  Three READ-ONLY calls under the exact contract of nbody_nearest (the bodies are
+ * what nbody_download would report -- on a Hermite handle the held (x0, v0) --, tracers and the external field play no part,
+ * no trace in state, NbodyStats, validity flags, levels or the bits of any later step, no refresh of the host's view of the
+ * count, launches sized from its upper bound and the live count read on the device: right after a retain with no nbody_count in
+ * between, scratch through the handle's registry and freed inside the call, no floating-point atomics: the same state gives
+ * the same bits).  The search is EXACT: no tree, no opening criterion, nothing approximated.
+ *   THE METRIC is nbody_nearest's, formed as csrc/kernels_pairs.hip forms it, f64 on either dtype (an NBODY_F32 handle's
+ * positions are widened exactly), unsoftened, nothing contracted into an FMA:
+ *     d = x_j - x_i,  r2 = (dx dx + dy dy) + dz dz
+ *   THE ORDER AND THE OUTPUTS: row i of neighbor and dist2 (k entries each, row-major [n][k], indices those of nbody_download's
+ * order) holds the k bodies j != i that come first in the order (r2 ascending, then j ascending), in that order, and their r2.
+ * A body enters only if r2 < +inf: a NaN or infinite r2 never enters, as in nbody_nearest.  A row with fewer than k such bodies
+ * is padded with -1 and +inf.  nbody_knn(k = 1) is nbody_nearest, integer for integer and bit for bit.  tests/knn_ref.py
+ * restates all three calls in numpy; the device's results are its integers and its bits.
+ *   SIZES AND REFUSALS: cap and *n_out follow nbody_nearest's protocol; cap counts ROWS (arrays of cap k entries).  Either array
+ * may be NULL; neighbor == NULL && dist2 == NULL only counts (*n_out = the bodies, nothing searched, stats zeroed).  cap < n
+ * returns NBODY_ERR_CAPACITY with *n_out set and nothing written.  1 <= k <= NBODY_KNN_MAX_K, else NBODY_ERR_INVALID; k >= n is
+ * valid and gives padded rows.  WHY 32: the bound keeps a block's 256 per-lane lists of (f64, i32) entries -- 256 x 32 x 12
+ * bytes = 96 KiB -- within a CU's 160 KiB of LDS beside a partner tile of 8 KiB; the constant is part of the ABI wherever an
+ * implementation keeps its lists.
+ *   radius_hint AND THE PAIR SEARCH: THE RESULT NEVER DEPENDS on radius_hint, on the search mode, on the tuning knobs or on the
+ * launch shape.  radius_hint must be 0 or finite and > 0, else NBODY_ERR_INVALID.  Under NBODY_SEARCH_ALL_PAIRS, or with
+ * radius_hint == 0, or when the grid is not usable (pair search, below), every row is answered by the all-pairs pass.  Under
+ * NBODY_SEARCH_CELLS with a hint the grid is drawn for length = radius_hint by the code of the fixed-radius calls; every
+ * gridded row gathers its top k among the bodies of its 27 cells with r2 < R2 = radius_hint * radius_hint (rounded once).  A row
+ * that found at least k is FINISHED: everything it did not see has r2 >= R2, which exceeds everything it kept, so
+ * the answer is exact and no tie can straddle the boundary.  The rows that found fewer than k, and the rows that are not
+ * gridded, are compacted in ascending index into a list, and a second all-pairs pass answers exactly the rows of that list.
+ * There is no radius doubling and no iteration: a hint that is too small costs the all-pairs pass for the rows it failed, never
+ * a wrong answer.  stats (may be NULL) = {rows answered from the cells, rows answered by the all-pairs pass}; their sum is *n_out.
+ * nbody_pair_search_stats afterwards holds what a fixed-radius call with that length leaves when the cell search ran;
+ * otherwise the record is unchanged.
+ *   nbody_knn_density: Casertano & Hut's (1985) estimator, generalised to unequal masses.  k >= 2, else NBODY_ERR_INVALID.  For a
+ * row whose list is complete (k neighbours), with masses widened to f64 and every operation rounded on its own:
+ *     M = the masses of its first k - 1 neighbours, added sequentially in list order from +0.0
+ *     r2 = dist2[k - 1],  r = sqrt(r2),  rho = M / (4.1887902047863905 * ((r r) r)),  rk2 = r2
+ * (the constant and the association are NBODY_KERNEL_TOP_HAT's; the body itself and its k-th neighbour are not counted, as in
+ * the paper).  A row whose list is incomplete gets rho = +0.0 and rk2 = +inf.  r == 0 -- k bodies coincident with the body --
+ * gives the IEEE result of the division (+inf, or NaN for massless neighbours), reported as it is.  rho and rk2 [n] follow
+ * nbody_density's protocol: either may be NULL, both NULL only counts, cap < n returns NBODY_ERR_CAPACITY with *n_out set.
+ *   nbody_knn_density_center: nbody_density_center with that rho -- the same block sums (per block of 256 bodies the pairwise
+ * tree), added on the host in ascending block order from +0.0, then three divides; *rho_sum (may be NULL) = sum_i rho_i.  With
+ * no complete row the centre is NaN.  The result is meant to be passed straight into nbody_lagrangian_radii(h, center, ...).
+ *   HOW: k_knn_pairs (csrc/kernels_knn.hip) on nbody_nearest's frame -- one row per lane, partners through LDS in tiles of 256,
+ * groups of 256 rows x K slices sized by bf64_waves.  A lane keeps its sorted list in LDS as [slot][lane]; the r2 of the list's
+ * last entry stands in a register as the admission threshold, so after the first tiles almost every partner costs one compare
+ * beyond nbody_nearest's pair term.  k_knn_merge merges a row's K slice lists in ascending slice order under the same order, so
+ * K cannot show.  k_cells_knn (csrc/kernels_cells.hip) walks the 27 cells with the same lists.
+ *   COST: all pairs: N^2 f64 pair terms of 3 subtractions, 3 products, 2 sums and a compare, plus about k ln(N / k) insertions of
+ * O(k) LDS moves per row.  Scratch: 12 k bytes per row for the result and as much per (row, slice).  NOT MEASURED on an MI355X
+ * beyond the single run of tools/knn_bench.py that DESIGN 3.23 records; nothing asserts or promises a time.
+ *   Accepted and refused exactly where nbody_neighbors_within is.  Refused with NBODY_ERR_INVALID (nbody_last_error names the
+ * call): k or radius_hint as above; center NULL; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle
+ * is refused without touching a device.
+ *   OUT OF SCOPE: k > 32; a tree search; approximate search; radius doubling or an iterated fallback; the neighbours of foreign
+ * points; periodic boundaries; SPH gather / scatter kernels with per-body smoothing lengths (dist2[i k + k - 1] is what a
+ * caller builds those from); multi-rank and spatial handles. */
+enum { NBODY_KNN_MAX_K = 32 };
+int nbody_knn(NbodyHandle* h, int k, double radius_hint, int32_t* neighbor /* [n][k] */, double* dist2 /* [n][k] */, size_t cap,
+              size_t* n_out, uint64_t stats[2] /* may be NULL */);
+int nbody_knn_density(NbodyHandle* h, int k, double radius_hint, double* rho /* [n] */, double* rk2 /* [n], may be NULL */, size_t cap,
+                      size_t* n_out);
+int nbody_knn_density_center(NbodyHandle* h, int k, double radius_hint, double center[3], double* rho_sum);
 /* ---- pair-separation counts: how many pairs stand at each separation (no reference counterpart) -----
  * The calls above answer a question about one threshold.  These two count the pairs in every bin of separation at once --
  * DD(r), what the two-point correlation function, the radial distribution function and the correlation dimension are computed
@@ -953,8 +1017,12 @@ int nbody_pair_counts_at(NbodyHandle* h, const double* points /* [m][3] f64 */, 
  * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
  * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
  * radius or the last bin edge can matter.  nbody_set_pair_search selects how these eight calls find such pairs; nothing else
- * reads the setting (nbody_nearest, nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs;
- * nbody_pair_counts_at always looks at all pairs).
+ * reads the setting as they do (nbody_nearest, nbody_partners and nbody_bound_pairs are not fixed-radius and stay all-pairs;
+ * nbody_pair_counts_at always looks at all pairs).  nbody_knn, nbody_knn_density and nbody_knn_density_center ask no
+ * fixed-radius question either, but read the setting through their radius_hint: under NBODY_SEARCH_CELLS and with a hint > 0
+ * they draw the grid for that length, answer from the 27 cells every row that finds its k bodies inside the hint, and answer the
+ * other rows by the all-pairs pass -- the result is the same bits whatever the mode and the hint are; with radius_hint == 0 or
+ * under NBODY_SEARCH_ALL_PAIRS they look at all pairs and leave the record behind nbody_pair_search_stats as it was.
  *   NBODY_SEARCH_ALL_PAIRS (the default) is the code as it stands: a handle that never sets the mode runs it untouched.
  *   NBODY_SEARCH_CELLS sorts the bodies by the cell of a uniform grid and looks at the 27 surrounding cells only.  THE GRID IS
  * NOT A TREE -- one level, cells of one size, no opening criterion, nothing approximated -- AND IT CHANGES NO RESULT: all four

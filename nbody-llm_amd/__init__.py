@@ -65,6 +65,7 @@ EXTERNAL_MAX = 8   # nbody_set_external_field: components of a static external f
 EXT_PLUMMER, EXT_HERNQUIST, EXT_MIYAMOTO_NAGAI, EXT_LOGARITHMIC = 0, 1, 2, 3
 SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how the fixed-radius calls (fof_*, contacts, neighbors_within, density*, pair_counts) find their pairs
 KERNEL_TOP_HAT, KERNEL_CUBIC_SPLINE = 0, 1   # nbody_density / nbody_density_center: the mass in the sphere over its volume | the M4 spline
+KNN_MAX_K = 32   # nbody_knn, nbody_knn_density, nbody_knn_density_center: the largest k (NBODY_KNN_MAX_K)
 PAIR_COUNT_MAX_BINS = 1024   # nbody_pair_counts / nbody_pair_counts_at: the most bins of one call (NBODY_PAIR_COUNT_MAX_BINS)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
@@ -96,6 +97,7 @@ DECLARED_SYMBOLS = [
     "nbody_nearest", "nbody_contacts", "nbody_merge_contacts",
     "nbody_fof_labels", "nbody_fof_groups", "nbody_fof_bound_groups",
     "nbody_neighbors_within", "nbody_density", "nbody_density_center",
+    "nbody_knn", "nbody_knn_density", "nbody_knn_density_center",
     "nbody_pair_counts", "nbody_pair_counts_at",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
@@ -291,6 +293,9 @@ _sig("nbody_fof_bound_groups", _i, _H, C.c_double, _i, _i, C.c_void_p, _sz, C.PO
 _sig("nbody_neighbors_within", _i, _H, C.c_double, C.c_void_p, _sz, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
 _sig("nbody_density", _i, _H, C.c_double, _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
 _sig("nbody_density_center", _i, _H, C.c_double, _i, C.POINTER(C.c_double), C.POINTER(C.c_double))
+_sig("nbody_knn", _i, _H, _i, C.c_double, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64))
+_sig("nbody_knn_density", _i, _H, _i, C.c_double, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz))
+_sig("nbody_knn_density_center", _i, _H, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_pair_counts", _i, _H, C.c_void_p, _i, C.c_void_p, C.c_void_p)
 _sig("nbody_pair_counts_at", _i, _H, C.c_void_p, _sz, C.c_void_p, _i, C.c_void_p, C.c_void_p)
 _sig("nbody_set_pair_search", _i, _H, _i)
@@ -781,6 +786,48 @@ class Simulation:
         center = (C.c_double * 3)()
         total = C.c_double(0)
         self._check(lib.nbody_density_center(self._h, float(radius), int(kernel), center, C.byref(total)))
+        return np.array(center[:], np.float64), float(total.value)
+
+    # -- k nearest neighbours (nbody_knn, nbody_knn_density, nbody_knn_density_center): f64, exact, read-only, on the device
+    def knn(self, k: int, radius_hint: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
+        """(neighbor [n, k] int32, dist2 [n, k] f64): row i holds the k bodies j != i that come first in the order (unsoftened f64
+        squared distance ascending, then index ascending) and those r2, in get_points() order; a row with fewer than k bodies at
+        a finite distance is padded with -1 and +inf.  1 <= k <= KNN_MAX_K.  radius_hint (0, or finite and > 0) never changes the
+        result: under SEARCH_CELLS the rows that find k bodies closer than the hint are answered from the 27 cells around them,
+        the others by the all-pairs pass -- knn_stats() says how many of each (nbody_knn)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_knn(self._h, int(k), float(radius_hint), None, None, 0, C.byref(n), None))   # (counts only)
+        neighbor = np.full((n.value, int(k)), -1, np.int32)
+        dist2 = np.full((n.value, int(k)), np.inf, np.float64)
+        stats = (C.c_uint64 * 2)()
+        self._check(lib.nbody_knn(self._h, int(k), float(radius_hint), neighbor.ctypes.data if n.value else None,
+                                  dist2.ctypes.data if n.value else None, n.value, C.byref(n), stats))
+        self._knn_stats = (int(stats[0]), int(stats[1]))
+        return neighbor[: n.value], dist2[: n.value]
+
+    def knn_stats(self) -> tuple[int, int]:
+        """(rows answered from the cells, rows answered by the all-pairs pass) of this object's last knn() call; (0, 0) before
+        the first (the `stats` of nbody_knn)."""
+        return getattr(self, "_knn_stats", (0, 0))
+
+    def knn_density(self, k: int, radius_hint: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
+        """(rho [n] f64, rk2 [n] f64): Casertano & Hut's density at every body from its k nearest neighbours (k >= 2) -- the mass
+        of the first k - 1, summed in list order, over the volume of the sphere that reaches the k-th -- and the squared distance
+        to the k-th; +0.0 and +inf for a body with fewer than k neighbours (nbody_knn_density)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_knn_density(self._h, int(k), float(radius_hint), None, None, 0, C.byref(n)))   # (the bodies)
+        rho = np.zeros(n.value, np.float64)
+        rk2 = np.full(n.value, np.inf, np.float64)
+        self._check(lib.nbody_knn_density(self._h, int(k), float(radius_hint), rho.ctypes.data if n.value else None,
+                                          rk2.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return rho[: n.value], rk2[: n.value]
+
+    def knn_density_center(self, k: int, radius_hint: float = 0.0) -> tuple[np.ndarray, float]:
+        """(center [3] f64, rho_sum): the density-weighted centre sum rho_i x_i / sum rho_i of Casertano & Hut with knn_density()'s
+        rho, summed in moments()' fixed order -- what lagrangian_radii(fractions, center=...) wants (nbody_knn_density_center)."""
+        center = (C.c_double * 3)()
+        total = C.c_double(0)
+        self._check(lib.nbody_knn_density_center(self._h, int(k), float(radius_hint), center, C.byref(total)))
         return np.array(center[:], np.float64), float(total.value)
 
     # -- pair-separation counts (nbody_pair_counts, nbody_pair_counts_at): integers, read-only, on the device

@@ -67,6 +67,11 @@ void launch_within_count(hipStream_t s, int n_upper, int n_gridded, double R2, c
 // cap: the words of raw
 void launch_within_fill(hipStream_t s, int n_upper, int n_gridded, double R2, const CellScratch& w, const int* offset, int* raw, size_t cap);
 
+// k_cells_knn: row i's k {index, r2} at neighbor[i k] / dist2[i k] on, for every gridded row -- the at most k bodies j != i with
+// r2 < R2 that come first in (r2, j), padded with {-1, +inf} --, and found[i] = how many (zeroed here for every row first);
+// the other rows' lists are left alone; 1 <= k <= NBODY_KNN_MAX_K; w.counters->candidates as launch_nearest_within counts them
+void launch_knn(hipStream_t s, int n_upper, int n_gridded, int k, double R2, const CellScratch& w, int* found, int* neighbor, double* dist2);
+
 // k_cells_pair_hist: every candidate pair with r2 < e2[n_bins] added to hist[slot of its r2] (kernels_paircount.h: slot 0 below
 // e2[0], slot b + 1 bin b; hist[n_bins + 1] is left alone: the caller subtracts); e2 [n_bins + 1] and hist [n_bins + 2] on the
 // device; flush_tiles: HistPlan's; w.counters->candidates as launch_link_components counts them

@@ -21,12 +21,16 @@
 //                    rule on (r2, index) alone, so the order in which cells are visited cannot show
 //   k_cells_within   k_cells_nearest's walk for the neighbour lists of kernels_within.h: a pass that counts every body's
 //                    neighbours with r2 < R2, and after the caller's integer scan a pass that writes their ORIGINAL indices
+//   k_cells_knn      k_cells_nearest's walk for the lists of kernels_knn.h: every gridded body's at most k nearest among the bodies
+//                    with r2 < R2, in (r2, ORIGINAL index) order, and how many it found
 //   k_cells_pair_hist  k_cells_link's walk for the binned pair counts of kernels_paircount.h: every candidate pair once, its r2
 //                    binned by bin_slot, counted in a block-private LDS histogram that is added to the call's 64-bit slots
 // The walks count their candidate pairs (place t after place s) in integers: shuffles, then one atomicAdd per wave.
 #include "kernels_cells.h"
 #include "fof_union.h"
 #include "kernels_paircount.h"   // bin_slot, hist_begin, hist_flush
+#include "kernels_knn.h"   // list_slots
+#include "knn_list.h"
 #include "real.h"      // widen
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -250,6 +254,49 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_within(int n_gridded, cons
     }
 }
 
+// k_cells_within's walk for the lists of kernels_knn.h: the at most k bodies t != s of the nine columns with r2 < R2 that come
+// first in (r2, ORIGINAL index), kept in the lane's LDS list (knn_list.h) -- a rule on (r2, index) alone, so the order in which
+// the cells are visited cannot show --, written as row rows[s]'s k {index, r2} padded with {-1, +inf}; found[rows[s]] = how
+// many; the candidate pairs as k_cells_nearest counts them.  The last entry of a full list stands in registers: a candidate that
+// does not come before it costs two compares.
+template <int kSlots>
+__global__ __launch_bounds__(kPairBlock) void k_cells_knn(int n_gridded, const uint64_t* __restrict__ keys, const int* __restrict__ rows,
+                                                          const double4* __restrict__ spos, double R2, int k, int* __restrict__ found,
+                                                          int* __restrict__ neighbor, double* __restrict__ dist2,
+                                                          cells::Counters* counters) {
+    __shared__ knn::ListLds<kSlots> lists;
+    const int tid = threadIdx.x;
+    const int s = blockIdx.x * kPairBlock + tid;
+    unsigned long long cand = 0;
+    if (s < n_gridded) {
+        const uint64_t key = keys[s];
+        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
+        const uint64_t kz = key & kCellMax;
+        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;
+        const double4 pi = spos[s];
+        knn::ListState st;
+        for (int c = 0; c < 9; ++c) {
+            int a, b;
+            if (!column_range(keys, 0, n_gridded, kx + (c / 3 - 1), ky + (c % 3 - 1), z0, z1, &a, &b)) continue;
+            const int after = max(a, s + 1);
+            if (b > after) cand += (unsigned long long)(b - after);
+            for (int t = a; t < b; ++t) {
+                const double r2 = fof::pair_dist2(pi, spos[t]);
+                if (t == s || !(r2 < R2)) continue;   // (strict; a NaN is never within R)
+                const int j = rows[t];
+                if (st.admits(r2, j)) knn::list_insert(lists, tid, k, st, r2, j);
+            }
+        }
+        const size_t row = size_t(rows[s]);   // (< the live count <= n_upper)
+        found[row] = st.held;
+        for (int slot = 0; slot < k; ++slot) {
+            neighbor[row * size_t(k) + size_t(slot)] = slot < st.held ? lists.j[slot][tid] : -1;
+            dist2[row * size_t(k) + size_t(slot)] = slot < st.held ? lists.r2[slot][tid] : knn::list_inf();
+        }
+    }
+    wave_add(cand, &counters->candidates);
+}
+
 // The binned pair counts of kernels_paircount.h over k_cells_link's walk: every candidate pair is evaluated once, from its
 // earlier place (the body with the lower original row of the two when they share a cell), and counted in the slot of its r2 --
 // but for the last slot: the pairs with !(r2 < E2[n_bins]) are not all candidates, so the caller obtains their number by
@@ -386,6 +433,19 @@ void launch_within_fill(hipStream_t s, int n_upper, int n_gridded, double R2, co
     hipLaunchKernelGGL(k_cells_within<true>, dim3(pairs::blocks_for(n_gridded)), dim3(kPairBlock), 0, s, n_gridded,
                        w.sorted_keys(size_t(n_upper)), w.sorted_rows(size_t(n_upper)), w.spos, R2, static_cast<int*>(nullptr), offset, raw,
                        unsigned(cap), static_cast<unsigned long long*>(nullptr), static_cast<Counters*>(nullptr));
+}
+
+void launch_knn(hipStream_t s, int n_upper, int n_gridded, int k, double R2, const CellScratch& w, int* found, int* neighbor, double* dist2) {
+    if (n_upper <= 0 || k < 1 || k > knn::kSlotsLarge) return;
+    (void)hipMemsetAsync(found, 0, size_t(n_upper) * sizeof(int), s);
+    if (n_gridded <= 0) return;
+    const dim3 grid(pairs::blocks_for(n_gridded)), block(kPairBlock);
+    if (knn::list_slots(k) == knn::kSlotsSmall)
+        hipLaunchKernelGGL(k_cells_knn<knn::kSlotsSmall>, grid, block, 0, s, n_gridded, w.sorted_keys(size_t(n_upper)),
+                           w.sorted_rows(size_t(n_upper)), w.spos, R2, k, found, neighbor, dist2, w.counters);
+    else
+        hipLaunchKernelGGL(k_cells_knn<knn::kSlotsLarge>, grid, block, 0, s, n_gridded, w.sorted_keys(size_t(n_upper)),
+                           w.sorted_rows(size_t(n_upper)), w.spos, R2, k, found, neighbor, dist2, w.counters);
 }
 
 void launch_pair_hist(hipStream_t s, int n_upper, int n_gridded, const CellScratch& w, const double* e2, int n_bins, int flush_tiles,

@@ -12,6 +12,7 @@
 #include "nbody_pairs.h"
 #include "nbody_fof.h"
 #include "nbody_within.h"
+#include "nbody_knn.h"
 #include "nbody_paircount.h"
 #include "nbody_cells.h"
 
@@ -624,6 +625,40 @@ int nbody_density_center(NbodyHandle* h, double radius, int kernel, double cente
     if (rc) return rc;
     if (!center) return fail(h, NBODY_ERR_INVALID, "nbody_density_center: center is NULL");
     return with_bodies(h, [&](auto& b) { return nbody::within::density_center(h, b.sh, b.n_local, radius, kernel, center, rho_sum); });
+}
+
+// ---- k nearest neighbours (nbody_knn.cpp): three read-only calls under the census's contract
+namespace {
+int knn_enter(NbodyHandle* h, const char* call, int k, int k_min, double radius_hint) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    if (k < k_min || k > NBODY_KNN_MAX_K)
+        return fail(h, NBODY_ERR_INVALID, std::string(call) + ": k must be in " + std::to_string(k_min) + " .. " + std::to_string(int(NBODY_KNN_MAX_K)));
+    if (radius_hint == 0.0 || (std::isfinite(radius_hint) && radius_hint > 0.0)) return NBODY_OK;
+    return fail(h, NBODY_ERR_INVALID, std::string(call) + ": radius_hint must be 0, or finite and > 0");
+}
+}  // namespace
+
+int nbody_knn(NbodyHandle* h, int k, double radius_hint, int32_t* neighbor, double* dist2, size_t cap, size_t* n_out, uint64_t stats[2]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = knn_enter(h, "nbody_knn", k, 1, radius_hint);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) { return nbody::knn::neighbors(h, b.sh, b.n_local, k, radius_hint, neighbor, dist2, cap, n_out, stats); });
+}
+
+int nbody_knn_density(NbodyHandle* h, int k, double radius_hint, double* rho, double* rk2, size_t cap, size_t* n_out) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = knn_enter(h, "nbody_knn_density", k, 2, radius_hint);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) { return nbody::knn::density(h, b.sh, b.n_local, k, radius_hint, rho, rk2, cap, n_out); });
+}
+
+int nbody_knn_density_center(NbodyHandle* h, int k, double radius_hint, double center[3], double* rho_sum) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = knn_enter(h, "nbody_knn_density_center", k, 2, radius_hint);
+    if (rc) return rc;
+    if (!center) return fail(h, NBODY_ERR_INVALID, "nbody_knn_density_center: center is NULL");
+    return with_bodies(h, [&](auto& b) { return nbody::knn::density_center(h, b.sh, b.n_local, k, radius_hint, center, rho_sum); });
 }
 
 // ---- pair-separation counts (nbody_paircount.cpp): two read-only calls under the census's contract

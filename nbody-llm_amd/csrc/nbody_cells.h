@@ -1,6 +1,7 @@
 // nbody_cells.h -- the host side of the cell-list pair search (include/nbody_hip.h, "pair search"): what a fixed-radius call
 // (nbody_fof.cpp find_groups, nbody_pairs.cpp find_contacts, nbody_within.cpp Lists::count) does before its pair pass when the handle is in
-// NBODY_SEARCH_CELLS, and the record it leaves behind.  Internal to libnbody_hip.so.
+// NBODY_SEARCH_CELLS, and the record it leaves behind.  nbody_knn.cpp Rows::run does the same for the length of its radius hint.
+// Internal to libnbody_hip.so.
 #pragma once
 #include "nbody_handle.h"
 #include "kernels_cells.h"

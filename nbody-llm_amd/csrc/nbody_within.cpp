@@ -175,6 +175,28 @@ template int density<float>(NbodyHandle*, const ShardT<float>&, size_t, double, 
 template int density<double>(NbodyHandle*, const ShardT<double>&, size_t, double, int, double*, int32_t*, size_t, size_t*);
 
 template <class F>
+int center_sums(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const double* d_rho, double sum[kCenterSums]) {
+    for (int q = 0; q < kCenterSums; ++q) sum[q] = 0.0;
+    if (!n_upper) return NBODY_OK;
+    const size_t blocks = size_t(pairs::blocks_for(int(n_upper)));
+    ScratchDev out(h->mem);   // [blocks][kCenterSums] block sums
+    HIP_TRY(h, out.alloc(blocks * kCenterSums * sizeof(double)));
+    double* d_part = out.get<double>();
+    launch_center<F>(h->stream, sh, int(n_upper), d_rho, d_part);
+    std::vector<double> part(blocks * kCenterSums);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e_sync = hipStreamSynchronize(h->stream);
+    HIP_TRY(h, e);
+    HIP_TRY(h, e_sync);
+    for (size_t b = 0; b < blocks; ++b)   // blocks in ascending order
+        for (int q = 0; q < kCenterSums; ++q) sum[q] += part[b * kCenterSums + q];
+    return NBODY_OK;
+}
+template int center_sums<float>(NbodyHandle*, const ShardT<float>&, size_t, const double*, double*);
+template int center_sums<double>(NbodyHandle*, const ShardT<double>&, size_t, const double*, double*);
+
+template <class F>
 int density_center(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double radius, int kernel, double center[3], double* rho_sum) {
     double sum[kCenterSums] = {0.0, 0.0, 0.0, 0.0};
     const auto finish = [&]() {
@@ -192,25 +214,15 @@ int density_center(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double r
     if (!lists.live) return finish();
     rc = lists.fill();
     if (rc) return rc;
-    const size_t blocks = size_t(pairs::blocks_for(int(n_upper)));
-    ScratchDev out(h->mem);   // [n_upper] rho | [blocks][kCenterSums] block sums
-    const size_t rho_bytes = (n_upper * sizeof(double) + 255) / 256 * 256;
-    HIP_TRY(h, out.alloc(rho_bytes + blocks * kCenterSums * sizeof(double)));
+    ScratchDev out(h->mem);   // [n_upper] rho
+    HIP_TRY(h, out.alloc(n_upper * sizeof(double)));
     double* d_rho = out.get<double>();
-    double* d_part = reinterpret_cast<double*>(out.get<char>() + rho_bytes);
     double hs, norm;
     kernel_constants(radius, kernel, &hs, &norm);
     launch_density<F>(h->stream, sh, int(n_upper), kernel == NBODY_KERNEL_CUBIC_SPLINE, hs, norm, lists.c.offset, lists.l.neighbor, d_rho,
                       nullptr);
-    launch_center<F>(h->stream, sh, int(n_upper), d_rho, d_part);
-    std::vector<double> part(blocks * kCenterSums);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e_sync = hipStreamSynchronize(h->stream);
-    HIP_TRY(h, e);
-    HIP_TRY(h, e_sync);
-    for (size_t b = 0; b < blocks; ++b)   // blocks in ascending order
-        for (int q = 0; q < kCenterSums; ++q) sum[q] += part[b * kCenterSums + q];
+    rc = center_sums<F>(h, sh, n_upper, d_rho, sum);
+    if (rc) return rc;
     return finish();
 }
 template int density_center<float>(NbodyHandle*, const ShardT<float>&, size_t, double, int, double*, double*);

@@ -19,4 +19,10 @@ int density(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double radius, 
 template <class F>
 int density_center(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double radius, int kernel, double center[3], double* rho_sum);
 
+// The centre's four sums {sum rho, sum rho x, sum rho y, sum rho z} for rho [n_upper] on the device (already enqueued on the
+// handle's stream): k_within_center's block sums, added on the host in ascending block order from +0.0.  Synchronises.
+// nbody_knn_density_center (nbody_knn.cpp) ends with it too.
+template <class F>
+int center_sums(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const double* d_rho, double sum[kCenterSums]);
+
 }}  // namespace nbody::within

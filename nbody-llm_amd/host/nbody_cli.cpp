@@ -26,10 +26,14 @@
 // state (nbody_density_center), the largest density and its body (nbody_density) and the half-mass Lagrangian radius about
 // that centre, on a line of its own, and honours --pair-search; --pair-counts LO:HI:BINS[:log|lin] (default log, which needs
 // LO > 0) prints the binned pair-separation counts of the final state (nbody_pair_counts), one line per bin with its two edges
-// and its count, then the `outside` line, and honours --pair-search.  The BINS + 1 edges are formed here in f64:
+// and its count, then the `outside` line, and honours --pair-search; --knn K[:HINT] prints, for the final state, the median and
+// the largest distance to a body's K-th nearest neighbour (nbody_knn; among the bodies that have K), how many rows the cells and
+// the all-pairs pass answered (HINT and --pair-search cells: the same numbers otherwise) and, for K >= 2, the Casertano-Hut
+// density centre (nbody_knn_density_center), on a line of its own.  The BINS + 1 edges of --pair-counts are formed here in f64:
 //     edges[0] = LO,  edges[BINS] = HI,  and for 0 < b < BINS
 //     lin: edges[b] = LO + (HI - LO) * (double(b) / double(BINS))      log: edges[b] = LO * pow(HI / LO, double(b) / double(BINS))
 // and printed with 17 significant digits, which name each double exactly.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -57,7 +61,8 @@ static void usage() {
                  "                 [--fof-bound ITER]   (with --fof: the self-bound subsets of those groups after at most ITER unbinding passes)\n"
                  "                 [--density R[:tophat|spline]]   (the density centre of the final state, the largest density, r50 about that centre)\n"
                  "                 [--pair-counts LO:HI:BINS[:log|lin]]   (the pairs of the final state per bin of separation; log needs LO > 0)\n"
-                 "                 [--pair-search all|cells]   (how --merge, --fof, --density and --pair-counts find their pairs: all pairs, or the cells of a uniform grid)\n");
+                 "                 [--knn K[:HINT]]   (every body's K nearest neighbours, 1 <= K <= 32: the median and largest K-th distance, the Casertano-Hut centre)\n"
+                 "                 [--pair-search all|cells]   (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -155,6 +160,28 @@ static void print_density(Sim& sim, double radius, int kernel) {
                 rho.empty() ? std::nan("") : rho[top], rho.empty() ? -1L : long(top), rho.empty() ? 0 : int(count[top]), radii[0]);
 }
 
+// the line of --knn: nbody_knn (the K-th distances of the complete rows, sorted; the median is the upper one of an even number)
+// and, for K >= 2, nbody_knn_density_center
+template <class Sim>
+static void print_knn(Sim& sim, int k, double hint) {
+    std::vector<int32_t> neighbor;
+    std::vector<double> dist2, rk;
+    uint64_t stats[2] = {0, 0};
+    sim.knn(k, hint, neighbor, dist2, stats);
+    for (size_t i = 0; i * size_t(k) < dist2.size(); ++i)
+        if (neighbor[i * size_t(k) + size_t(k - 1)] >= 0) rk.push_back(std::sqrt(dist2[i * size_t(k) + size_t(k - 1)]));
+    std::sort(rk.begin(), rk.end());
+    const double nan = std::nan("");
+    std::printf("kNN: k %d rk median %.17e max %.17e cells %llu all-pairs %llu", k, rk.empty() ? nan : rk[rk.size() / 2],
+                rk.empty() ? nan : rk.back(), (unsigned long long)stats[0], (unsigned long long)stats[1]);
+    if (k >= 2) {
+        double center[3];
+        sim.knn_density_center(k, hint, center);
+        std::printf(" center %.17e %.17e %.17e", center[0], center[1], center[2]);
+    }
+    std::printf("\n");
+}
+
 // the edges of --pair-counts (the formula stands at the top of this file)
 static std::vector<double> pair_count_edges(double lo, double hi, int bins, bool log_bins) {
     std::vector<double> edges(size_t(bins) + 1);
@@ -182,7 +209,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
-               double density_radius, int density_kernel, const std::vector<double>& pair_edges) {
+               double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -252,6 +279,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (fof_b > 0.0 && fof_bound > 0) print_fof_bound(*sim, fof_b, fof_min, fof_bound);
         if (density_radius > 0.0) print_density(*sim, density_radius, density_kernel);
         if (!pair_edges.empty()) print_pair_counts(*sim, pair_edges);
+        if (knn_k > 0) print_knn(*sim, knn_k, knn_hint);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -297,6 +325,8 @@ int main(int argc, char** argv) {
     double density_radius = 0.0;
     int density_kernel = NBODY_KERNEL_CUBIC_SPLINE;
     std::vector<double> pair_edges;
+    int knn_k = 0;
+    double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
         if (!std::strcmp(argv[i], "-t") || !std::strcmp(argv[i], "--threads")) threads = std::strtoull(next(), nullptr, 10);
@@ -370,6 +400,18 @@ int main(int argc, char** argv) {
                 (log_bins && !(lo > 0.0))) { usage(); return 2; }
             pair_edges = pair_count_edges(lo, hi, int(bins), log_bins);
         }
+        else if (!std::strcmp(argv[i], "--knn")) {
+            char* end = nullptr;
+            const char* arg = next();
+            const long k = std::strtol(arg, &end, 10);
+            if (end == arg || k < 1 || k > NBODY_KNN_MAX_K || (*end && *end != ':')) { usage(); return 2; }
+            knn_k = int(k);
+            if (*end == ':') {
+                arg = end + 1;
+                knn_hint = std::strtod(arg, &end);
+                if (end == arg || *end || !(knn_hint > 0.0) || !std::isfinite(knn_hint)) { usage(); return 2; }
+            }
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -417,6 +459,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint);
 }

@@ -367,6 +367,35 @@ public:
         check(nbody_density_center(h_, radius, kernel, center, &sum));
         return sum;
     }
+    // k nearest neighbours (nbody_knn, nbody_knn_density, nbody_knn_density_center): exact, f64 unsoftened distances on either F;
+    // read-only, the handles moments() takes.  Row i of neighbor / dist2 (k entries each) holds the k bodies j != i first in
+    // (r2 ascending, j ascending) and their r2, padded with -1 and +inf; radius_hint (0: none) never changes the result -- under
+    // NBODY_SEARCH_CELLS the rows that find k bodies inside it are answered from the cells; stats = {those rows, the others}
+    void knn(int k, double radius_hint, std::vector<int32_t>& neighbor, std::vector<double>& dist2, uint64_t stats[2] = nullptr) {
+        size_t n = 0;
+        check(nbody_knn(h_, k, radius_hint, nullptr, nullptr, 0, &n, nullptr));   // (counts only)
+        neighbor.assign(n * size_t(k), -1);
+        dist2.assign(n * size_t(k), 0.0);
+        check(nbody_knn(h_, k, radius_hint, n ? neighbor.data() : nullptr, n ? dist2.data() : nullptr, n, &n, stats));
+        neighbor.resize(n * size_t(k));
+        dist2.resize(n * size_t(k));
+    }
+    // rho[i]: Casertano & Hut's density at body i from its k nearest neighbours (k >= 2), rk2[i]: the squared distance to the k-th
+    void knn_density(int k, double radius_hint, std::vector<double>& rho, std::vector<double>& rk2) {
+        size_t n = 0;
+        check(nbody_knn_density(h_, k, radius_hint, nullptr, nullptr, 0, &n));   // (the bodies)
+        rho.assign(n, 0.0);
+        rk2.assign(n, 0.0);
+        check(nbody_knn_density(h_, k, radius_hint, n ? rho.data() : nullptr, n ? rk2.data() : nullptr, n, &n));
+        rho.resize(n);
+        rk2.resize(n);
+    }
+    // the centre weighted with that density (what lagrangian_radii's `center` wants); returns the sum of the densities
+    double knn_density_center(int k, double radius_hint, double center[3]) {
+        double sum = 0;
+        check(nbody_knn_density_center(h_, k, radius_hint, center, &sum));
+        return sum;
+    }
     // pair-separation counts (nbody_pair_counts, nbody_pair_counts_at): counts[b] = the pairs whose unsoftened f64 squared
     // separation r2 has edges[b]^2 <= r2 < edges[b + 1]^2 (edges: n_bins + 1 of them), outside = {the pairs below edges[0]^2,
     // everything else}; integers, read-only, the handles moments() takes.  pair_counts: every pair i < j of bodies, honours

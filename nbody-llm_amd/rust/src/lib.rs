@@ -109,6 +109,9 @@ unsafe extern "C" {
     fn nbody_lagrangian_radii(h: *mut NbodyHandle, center: *const f64, fractions: *const f64, n_frac: usize, radii: *mut f64, mass_out: *mut f64) -> c_int;
     fn nbody_partners(h: *mut NbodyHandle, partner: *mut i32, energy: *mut f64, cap: usize, n_out: *mut usize) -> c_int;
     fn nbody_bound_pairs(h: *mut NbodyHandle, pairs: *mut NbodyBoundPair, cap: usize, n_pairs: *mut usize, binding_sum: *mut f64) -> c_int;
+    fn nbody_knn(h: *mut NbodyHandle, k: c_int, radius_hint: f64, neighbor: *mut i32, dist2: *mut f64, cap: usize, n_out: *mut usize, stats: *mut u64) -> c_int;
+    fn nbody_knn_density(h: *mut NbodyHandle, k: c_int, radius_hint: f64, rho: *mut f64, rk2: *mut f64, cap: usize, n_out: *mut usize) -> c_int;
+    fn nbody_knn_density_center(h: *mut NbodyHandle, k: c_int, radius_hint: f64, center: *mut f64, rho_sum: *mut f64) -> c_int;
 }
 
 pub const NBODY_BRUTE_FORCE: i32 = 0; // src/manual/brute_force.rs
@@ -369,6 +372,53 @@ impl<F: HipFloat, const METHOD: i32> HipSimulation<F, METHOD> {
         let rc = unsafe { nbody_tidal_at(self.handle, mode as c_int, xyz, points.len(), out.as_mut_ptr() as *mut f64, std::ptr::null_mut()) };
         self.check(rc);
         out
+    }
+
+    /// Every body's exact `k` nearest bodies (include/nbody_hip.h nbody_knn): rows of `k` indices and unsoftened f64 squared
+    /// distances in the order (r2 ascending, index ascending), padded with -1 and +inf.  `radius_hint` (0.0: none) never changes
+    /// the result.  Returns (neighbor [n * k], dist2 [n * k], [rows answered from the cells, rows answered by the all-pairs pass]).
+    pub fn knn(&mut self, k: usize, radius_hint: f64) -> (Vec<i32>, Vec<f64>, [u64; 2]) {
+        self.push_settings();
+        let mut n = 0usize;
+        let rc = unsafe { nbody_knn(self.handle, k as c_int, radius_hint, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n, std::ptr::null_mut()) };
+        self.check(rc);
+        let mut neighbor = vec![-1i32; n * k];
+        let mut dist2 = vec![f64::INFINITY; n * k];
+        let mut stats = [0u64; 2];
+        if n > 0 {
+            let rc = unsafe { nbody_knn(self.handle, k as c_int, radius_hint, neighbor.as_mut_ptr(), dist2.as_mut_ptr(), n, &mut n, stats.as_mut_ptr()) };
+            self.check(rc);
+        }
+        neighbor.truncate(n * k);
+        dist2.truncate(n * k);
+        (neighbor, dist2, stats)
+    }
+
+    /// Casertano & Hut's density at every body from its `k` nearest neighbours, k >= 2 (nbody_knn_density): (rho [n], rk2 [n]).
+    pub fn knn_density(&mut self, k: usize, radius_hint: f64) -> (Vec<f64>, Vec<f64>) {
+        self.push_settings();
+        let mut n = 0usize;
+        let rc = unsafe { nbody_knn_density(self.handle, k as c_int, radius_hint, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut n) };
+        self.check(rc);
+        let mut rho = vec![0.0f64; n];
+        let mut rk2 = vec![f64::INFINITY; n];
+        if n > 0 {
+            let rc = unsafe { nbody_knn_density(self.handle, k as c_int, radius_hint, rho.as_mut_ptr(), rk2.as_mut_ptr(), n, &mut n) };
+            self.check(rc);
+        }
+        rho.truncate(n);
+        rk2.truncate(n);
+        (rho, rk2)
+    }
+
+    /// The centre weighted with that density and the sum of the densities (nbody_knn_density_center).
+    pub fn knn_density_center(&mut self, k: usize, radius_hint: f64) -> ([f64; 3], f64) {
+        self.push_settings();
+        let mut center = [0.0f64; 3];
+        let mut rho_sum = 0.0f64;
+        let rc = unsafe { nbody_knn_density_center(self.handle, k as c_int, radius_hint, center.as_mut_ptr(), &mut rho_sum) };
+        self.check(rc);
+        (center, rho_sum)
     }
 
     pub fn options(&self) -> &HipOptions {
