@@ -1013,6 +1013,94 @@ int nbody_pair_counts(NbodyHandle* h, const double* edges /* [n_bins + 1] */, in
                       uint64_t outside[2] /* may be NULL */);
 int nbody_pair_counts_at(NbodyHandle* h, const double* points /* [m][3] f64 */, size_t m, const double* edges, int n_bins,
                          uint64_t* counts, uint64_t outside[2] /* may be NULL */);
+/* ---- grid deposit: the bodies assigned to a regular grid, NGP / CIC / TSC (no reference counterpart) ---------------------
+ * Every call above answers a question at points.  nbody_deposit gives a field on a regular grid -- a column-density image, a
+ * density cube, a momentum or m v^2 map, the input of a power spectrum or a particle-mesh step -- without nbody_download and
+ * a host loop.  A READ-ONLY call under the contract of nbody_pair_counts (the bodies are what nbody_download would report --
+ * on a Hermite handle the held (x0, v0) --, an NBODY_F32 handle's values are widened exactly, tracers and the external field
+ * play no part, no trace in state, NbodyStats, tracers, validity flags, levels or the bits of any later step, no refresh of the
+ * host's view of the count, launches sized from its upper bound and the live count read on the device: right after a retain
+ * with no nbody_count in between, scratch through the handle's registry and freed inside the call).  The only thing a call
+ * leaves behind is the record nbody_deposit_stats reads.
+ *   THE SAME STATE GIVES THE SAME BITS, whatever the launch shape, the scheduling and the deposit_sort, deposit_combine and
+ * deposit_lds knobs are: the cells accumulate in 64-bit FIXED POINT with integer additions, which are associative.  No
+ * floating-point atomics anywhere.  A plain f64 scatter-add does not have this property: a 4 099-body Plummer world of unequal
+ * masses deposited NGP on 16^3 cells differs in 109 cells between two orders of the bodies (tests/test_deposit_checker.py).
+ *   THE ARITHMETIC (csrc/deposit_grid.h, restated in tests/deposit_ref.py), all f64, every operation rounded on its own,
+ * nothing contracted into an FMA.  q is the body's quantity: m | m vx | m vy | m vz | m ((vx vx + vy vy) + vz vz) | 1.0.
+ *     u_c = (x_c - origin_c) / spacing      on each axis c that is not ignored (project_axis)
+ *     a body is SKIPPED when any of x, y, z, q is not finite, or when !(|u_c| < 2^31) on an axis that is not ignored
+ *     NGP: i = floor(u), weight 1
+ *     CIC: s = u - 0.5, i0 = floor(s), f = s - i0; cells i0, i0 + 1 get the weights 1.0 - f, f
+ *     TSC: i = floor(u), d = (u - i) - 0.5, a = 0.5 - d, b = 0.5 + d; cells i - 1, i, i + 1 get 0.5 (a a), 0.75 - d d, 0.5 (b b)
+ *     the ignored axis has one stencil cell, index 0, weight 1.0 (dims there must be 1): a column map
+ *     a term is t = q ((wx wy) wz) into cell (ix, iy, iz)
+ *     periodic: every index goes mod dims_c into [0, dims_c); otherwise a term whose cell is off the grid is dropped
+ *   A body that is not skipped is INSIDE if every cell of its stencil lands on the grid (cells of weight zero included),
+ * OUTSIDE if none does, PARTIAL otherwise; counts = {inside, partial, outside, skipped} add up to the live count n.  Under
+ * periodic wrap partial and outside are 0.
+ *   THE SCALE.  n = the live count (skipped bodies included), L = ceil(log2(n)) (0 for n = 1), e = the frexp exponent of the
+ * largest |q| among the bodies that are not skipped (a maximum is exact in any order), S = 61 - e - L.  Every term becomes
+ *     k = llrint(ldexp(t, S))    (ties to even);    acc[cell] += k  in int64;    grid[cell] = ldexp((double) acc[cell], -S)
+ * No body, or every q zero: every cell is +0.0.  No cell can overflow: the weights of a body are non-negative and sum to
+ * 1 (1 + eps), so sum |t| 2^S <= n 2^e 2^S (1 + eps) <= 2^61 (1 + eps), and rounding adds at most 27 n / 2 <= 2^35.
+ *   WHAT IT COSTS IN ACCURACY: every term is rounded to 2^-(61 - L) of the heaviest body's q (2^-41 for 2^20 bodies), so a
+ * cell is a DETERMINISTIC sum, not a correctly rounded one: its absolute error is at most (terms in the cell) / 2 of that
+ * unit plus one final rounding, and a cell holding bodies 2^40 times lighter than the heaviest loses them.
+ *   grid: [nx][ny][nz] row-major doubles, cap = the doubles it holds.  cap smaller than nx ny nz: NBODY_ERR_CAPACITY, grid
+ * untouched.  grid == NULL: only counts is filled (cap is not looked at).  counts may be NULL.
+ *   nbody_host_deposit is the same arithmetic on the host (no device needed) for n caller points {x, y, z} and their q; the
+ * quantity field of the spec is ignored.  xyz or q NULL with n > 0, or n > 2^31 - 1, is NBODY_ERR_INVALID.
+ *   nbody_deposit_stats: out = {1 once a call on this handle reached the device else 0, the plan of the last such call as
+ * deposit_sort | deposit_combine << 1 | deposit_lds << 2, the terms that landed on the grid, the 64-bit atomics that went to
+ * global memory}.  The last number depends on the plan and, with deposit_lds, on scheduling; nothing else does.  IT IS A
+ * DIAGNOSTIC AID for tools/deposit_bench.py and the tests of the plans, NOT A STABLE CONTRACT: what the four words mean may
+ * change with the kernels, and no program should decide anything by them.  The record is the one thing a call leaves behind.
+ *   HOW (csrc/kernels_deposit.hip): k_deposit_q -- q of every row, the largest |q| by an integer atomicMax on its bits, the four
+ * counts; k_deposit_keys and the stable rocPRIM radix sort that the cell search uses -- the rows ordered by home cell;
+ * k_deposit -- one lane per body of that order: for every stencil offset the lanes of a wave whose terms hit the same cell
+ * stand in a run, a segmented integer scan over the run by shuffles leaves the run's sum in its last lane, which alone adds
+ * it -- to a block-private LDS table of 1 024 tagged int64 slots (deposit_lds = 1; a slot taken by another cell sends the
+ * addition to global memory), or with one 64-bit vector atomic, relaxed, agent scope, to the cell; k_deposit_convert -- int64
+ * to f64 in place; one copy to the host.  deposit_sort = 0, deposit_combine = 0, deposit_lds = 0 is the plain variant, one
+ * atomic per term from unsorted bodies: the baseline and the cross-check.
+ *   COST: O(N log N) for the sort, 1 | 8 | 27 terms per body, 8 bytes of scratch per cell and 24 per body beside the sort's
+ * own.  NOT TIMED ON AN MI355X beyond the single run of tools/deposit_bench.py that DESIGN 3.24 records (2^20 Plummer bodies,
+ * f32 handle, whole calls): 1.3 to 3.0 ms a call onto 128^3 and 512 x 512 x 1; the default plan (1, 1, 1) sends 5 to 15 times
+ * fewer atomics to global memory than the plain variant, is 1.39 times faster for TSC on the cube and 2 to 13 % SLOWER in the
+ * other five cases, where the call is mostly its fixed part; summed over the six cases three plans tie, the default among them.  The rate of 64-bit integer atomics itself, the kernels apart from the
+ * call, f64 handles and denser worlds have not been measured.  Nothing asserts or promises a time.
+ *   Accepted and refused on the handles of nbody_pair_counts.  Refused with NBODY_ERR_INVALID (nbody_last_error names the
+ * call): spec NULL; an origin that is not finite; a spacing that is not finite or <= 0; a dimension < 1; nx ny nz >
+ * NBODY_DEPOSIT_MAX_CELLS; an unknown scheme or quantity; project_axis outside -1 .. 2 or naming an axis whose dimension is
+ * not 1; reserved != 0; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without
+ * touching a device.
+ *   OUT OF SCOPE: anisotropic cells; higher-order (PCS) stencils; interlacing and the deconvolution of the window; per-axis
+ * periodicity; the velocity moments' ratios (a dispersion map is three calls and a host division); multi-rank handles. */
+#define NBODY_DEPOSIT_NGP 0
+#define NBODY_DEPOSIT_CIC 1
+#define NBODY_DEPOSIT_TSC 2
+#define NBODY_DEPOSIT_MASS 0        /* q = m                                   */
+#define NBODY_DEPOSIT_MOMENTUM_X 1  /* q = m vx                                */
+#define NBODY_DEPOSIT_MOMENTUM_Y 2  /* q = m vy                                */
+#define NBODY_DEPOSIT_MOMENTUM_Z 3  /* q = m vz                                */
+#define NBODY_DEPOSIT_MV2 4         /* q = m ((vx vx + vy vy) + vz vz)         */
+#define NBODY_DEPOSIT_NUMBER 5      /* q = 1.0                                 */
+#define NBODY_DEPOSIT_MAX_CELLS 134217728   /* 2^27 */
+typedef struct NbodyGridSpec {
+    double origin[3];   /* the low corner of cell (0,0,0) */
+    double spacing;     /* the cell's edge */
+    int32_t dims[3];    /* nx, ny, nz >= 1, product <= NBODY_DEPOSIT_MAX_CELLS */
+    int32_t scheme, quantity;
+    int32_t periodic;   /* 0: terms that fall off the grid are dropped; 1: indices wrap on every axis */
+    int32_t project_axis; /* -1, or 0/1/2: that axis is ignored (dims there must be 1): a column map */
+    int32_t reserved;   /* 0 */
+} NbodyGridSpec;
+int nbody_deposit(NbodyHandle* h, const NbodyGridSpec* spec, double* grid /* [nx][ny][nz], row-major */, size_t cap,
+                  uint64_t counts[4] /* inside, partial, outside, skipped; may be NULL */);
+int nbody_host_deposit(const double* xyz /* [n][3] */, const double* q /* [n] */, size_t n, const NbodyGridSpec* spec,
+                       double* grid, size_t cap, uint64_t counts[4]);
+int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
  * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
  * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
@@ -1072,7 +1160,8 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
 /* Per handle; the library exports no mutable globals.  Names (csrc/kernels.h struct Tuning): cross_sym, sym_packed,
  * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, sym_opp_rot, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
  * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8),
- * pair_hist_combine, pair_hist_flush (nbody_pair_counts and nbody_pair_counts_at: they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * pair_hist_combine, pair_hist_flush (nbody_pair_counts and nbody_pair_counts_at: they change no result), deposit_sort, deposit_combine,
+ * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

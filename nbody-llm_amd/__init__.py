@@ -67,6 +67,10 @@ SEARCH_ALL_PAIRS, SEARCH_CELLS = 0, 1   # nbody_set_pair_search: how the fixed-r
 KERNEL_TOP_HAT, KERNEL_CUBIC_SPLINE = 0, 1   # nbody_density / nbody_density_center: the mass in the sphere over its volume | the M4 spline
 KNN_MAX_K = 32   # nbody_knn, nbody_knn_density, nbody_knn_density_center: the largest k (NBODY_KNN_MAX_K)
 PAIR_COUNT_MAX_BINS = 1024   # nbody_pair_counts / nbody_pair_counts_at: the most bins of one call (NBODY_PAIR_COUNT_MAX_BINS)
+DEPOSIT_NGP, DEPOSIT_CIC, DEPOSIT_TSC = 0, 1, 2   # nbody_deposit: the assignment scheme (1, 2 or 3 cells an axis)
+# nbody_deposit: the quantity q of a body: m | m vx | m vy | m vz | m ((vx vx + vy vy) + vz vz) | 1.0
+DEPOSIT_MASS, DEPOSIT_MOMENTUM_X, DEPOSIT_MOMENTUM_Y, DEPOSIT_MOMENTUM_Z, DEPOSIT_MV2, DEPOSIT_NUMBER = 0, 1, 2, 3, 4, 5
+DEPOSIT_MAX_CELLS = 1 << 27   # nbody_deposit: the most cells of a grid (NBODY_DEPOSIT_MAX_CELLS)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -99,6 +103,7 @@ DECLARED_SYMBOLS = [
     "nbody_neighbors_within", "nbody_density", "nbody_density_center",
     "nbody_knn", "nbody_knn_density", "nbody_knn_density_center",
     "nbody_pair_counts", "nbody_pair_counts_at",
+    "nbody_deposit", "nbody_host_deposit", "nbody_deposit_stats",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -115,6 +120,19 @@ class NbodyLetStats(C.Structure):
     _fields_ = [(k, C.c_uint64) for k in ("steps", "bodies_migrated", "nodes_local", "nodes_global", "nodes_sent", "nodes_received",
                                           "bytes_sent", "bytes_allgather_equivalent")] + [("phase_ms", C.c_double * 5)] + \
                [(k, C.c_uint64) for k in ("host_syncs", "migrant_respills", "node_array_peak_bytes", "node_array_bytes")]
+
+
+class GridSpec(C.Structure):
+    """NbodyGridSpec (include/nbody_hip.h, "grid deposit"): the grid, the scheme and the quantity of one nbody_deposit call."""
+    _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double), ("dims", C.c_int32 * 3), ("scheme", C.c_int32), ("quantity", C.c_int32),
+                ("periodic", C.c_int32), ("project_axis", C.c_int32), ("reserved", C.c_int32)]
+
+
+def grid_spec(origin, spacing, dims, scheme=DEPOSIT_CIC, quantity=DEPOSIT_MASS, periodic=False, project_axis=-1) -> GridSpec:
+    """A GridSpec from plain values (origin [3], dims [3])."""
+    o = [float(v) for v in origin]
+    d = [int(v) for v in dims]
+    return GridSpec((C.c_double * 3)(*o), float(spacing), (C.c_int32 * 3)(*d), int(scheme), int(quantity), int(bool(periodic)), int(project_axis), 0)
 
 
 class NbodyExternalComponent(C.Structure):
@@ -298,6 +316,9 @@ _sig("nbody_knn_density", _i, _H, _i, C.c_double, C.c_void_p, C.c_void_p, _sz, C
 _sig("nbody_knn_density_center", _i, _H, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double))
 _sig("nbody_pair_counts", _i, _H, C.c_void_p, _i, C.c_void_p, C.c_void_p)
 _sig("nbody_pair_counts_at", _i, _H, C.c_void_p, _sz, C.c_void_p, _i, C.c_void_p, C.c_void_p)
+_sig("nbody_deposit", _i, _H, C.POINTER(GridSpec), C.c_void_p, _sz, C.c_void_p)
+_sig("nbody_host_deposit", _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(GridSpec), C.c_void_p, _sz, C.c_void_p)
+_sig("nbody_deposit_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -399,6 +420,26 @@ def cell_grid(points, length: float, keys: bool = True) -> dict:
     if rc:
         raise NbodyError(rc, "nbody_host_cell_grid: the length must be finite and > 0")
     return dict(lo=np.array(lo[:], np.float64), side=float(side.value), usable=bool(usable.value), keys=key)
+
+
+def host_deposit(points, q, origin, spacing, dims, scheme=DEPOSIT_CIC, periodic=False, project_axis=-1) -> tuple[np.ndarray, np.ndarray]:
+    """(grid [nx, ny, nz] f64, counts [4] uint64 = inside, partial, outside, skipped): points [n][3] with the quantities q [n]
+    assigned to a regular grid in 64-bit fixed point -- nbody_deposit's arithmetic on the host (nbody_host_deposit; no device
+    needed).  The same points give the same bits in any order."""
+    xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    qq = np.ascontiguousarray(np.asarray(q, np.float64).reshape(-1))
+    if len(qq) != len(xyz):
+        raise ValueError("host_deposit: q must hold one value per point")
+    spec = grid_spec(origin, spacing, dims, scheme, DEPOSIT_MASS, periodic, project_axis)
+    shape = tuple(max(int(v), 0) for v in dims)
+    grid = np.zeros(shape, np.float64)
+    counts = np.zeros(4, np.uint64)
+    n = len(xyz)
+    rc = lib.nbody_host_deposit(xyz.ctypes.data if n else None, qq.ctypes.data if n else None, n, C.byref(spec),
+                                grid.ctypes.data if grid.size else None, grid.size, counts.ctypes.data)
+    if rc:
+        raise NbodyError(rc, "nbody_host_deposit: the spec is not valid (include/nbody_hip.h lists what is refused)")
+    return grid, counts
 
 
 def tidal_matrices(t6) -> np.ndarray:
@@ -854,6 +895,26 @@ class Simulation:
         self._check(lib.nbody_pair_counts_at(self._h, points.ctypes.data if len(points) else None, len(points), edges.ctypes.data, n_bins,
                                              counts.ctypes.data, outside.ctypes.data))
         return counts, outside
+
+    # -- grid deposit (nbody_deposit): the bodies assigned to a regular grid in 64-bit fixed point, read-only, on the device
+    def deposit(self, origin, spacing, dims, scheme=DEPOSIT_CIC, quantity=DEPOSIT_MASS, periodic=False, project_axis=-1) -> tuple[np.ndarray, np.ndarray]:
+        """(grid [nx, ny, nz] f64, counts [4] uint64 = inside, partial, outside, skipped): the bodies' quantity (DEPOSIT_MASS,
+        DEPOSIT_MOMENTUM_X/Y/Z, DEPOSIT_MV2, DEPOSIT_NUMBER) assigned to the cells of edge `spacing` from the low corner `origin`
+        by DEPOSIT_NGP, DEPOSIT_CIC or DEPOSIT_TSC; periodic wraps every axis, else what falls off the grid is dropped;
+        project_axis = 0, 1 or 2 ignores that axis (dims there must be 1): a column map.  The same state gives the same bits
+        (nbody_deposit)."""
+        spec = grid_spec(origin, spacing, dims, scheme, quantity, periodic, project_axis)
+        grid = np.zeros(tuple(max(int(v), 0) for v in dims), np.float64)
+        counts = np.zeros(4, np.uint64)
+        self._check(lib.nbody_deposit(self._h, C.byref(spec), grid.ctypes.data if grid.size else None, grid.size, counts.ctypes.data))
+        return grid, counts
+
+    def deposit_stats(self) -> np.ndarray:
+        """[4] uint64: {1 once a deposit reached the device, the last one's plan (deposit_sort | deposit_combine << 1 |
+        deposit_lds << 2), its terms on the grid, the 64-bit atomics it sent to global memory} (nbody_deposit_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_deposit_stats(self._h, out))
+        return np.array(out[:], np.uint64)
 
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits
     @property

@@ -42,6 +42,9 @@ struct Tuning {
     int pair_hist_combine = 0;  // k_pair_hist: lanes of a wave that hit one slot at the same partner: 0 each adds its own 1, 1 the first counting lane's
                                 // slot is added once for all its lanes, 2 every distinct slot is (kernels_paircount.h hist_add)
     int pair_hist_flush = 0;    // k_pair_hist / k_cells_pair_hist: tiles of 256 partners between two flushes of a block's LDS words; 0 = 65 535, the most
+    int deposit_sort = 1;       // nbody_deposit: 1 the rows ordered by home cell before k_deposit, 0 in row order (kernels_deposit.h Plan)
+    int deposit_combine = 1;    // k_deposit: 1 a wave's runs of equal cells are summed by a segmented scan and added once, 0 every lane adds its own term
+    int deposit_lds = 1;        // k_deposit: 1 additions go through the block's tagged LDS table of 1 024 int64 slots, 0 straight to the cells
     // the following select code that only the tuning build carries (make -C csrc tuning: -DNBODY_TUNING); the release
     // library refuses any value but the default
     int bh_walk_variant = 0;    // 1 wave-cooperative, 2 two lanes per body, 3 hot records in LDS, 4 cooperative window, 5 cooperative block walk  [NBODY_BH_VARIANT]

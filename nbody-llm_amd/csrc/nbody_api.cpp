@@ -14,6 +14,7 @@
 #include "nbody_within.h"
 #include "nbody_knn.h"
 #include "nbody_paircount.h"
+#include "nbody_deposit.h"
 #include "nbody_cells.h"
 
 #include <algorithm>
@@ -692,6 +693,30 @@ int nbody_pair_counts_at(NbodyHandle* h, const double* points, size_t m, const d
     return with_bodies(h, [&](auto& b) { return nbody::paircount::pair_counts_at(h, b.sh, b.n_local, points, m, e2, counts, outside); });
 }
 
+// ---- grid deposit (nbody_deposit.cpp): a read-only call under the census's contract, and its host twin
+int nbody_deposit(NbodyHandle* h, const NbodyGridSpec* spec, double* grid, size_t cap, uint64_t counts[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_deposit");
+    if (rc) return rc;
+    const std::string why = nbody::deposit::spec_refusal(spec, true);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, "nbody_deposit: " + why);
+    if (grid && cap < nbody::deposit::cells_of(nbody::deposit::grid_of(*spec)))
+        return fail(h, NBODY_ERR_CAPACITY, "nbody_deposit: cap is smaller than the number of cells");
+    return with_bodies(h, [&](auto& b) { return nbody::deposit::deposit(h, b.sh, b.n_local, *spec, grid, counts); });
+}
+
+int nbody_host_deposit(const double* xyz, const double* q, size_t n, const NbodyGridSpec* spec, double* grid, size_t cap, uint64_t counts[4]) {
+    return nbody::deposit::host_entry(xyz, q, n, spec, grid, cap, counts);
+}
+
+int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_deposit_stats: ") + why);
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_deposit_stats: out is NULL");
+    std::copy(h->deposit_last, h->deposit_last + 4, out);
+    return NBODY_OK;
+}
+
 // ---- pair search (nbody_cells.cpp): a setting of the handle that the eight fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
@@ -1219,6 +1244,8 @@ const Knob kKnobs[] = {
     {"bf64_min_bodies", &nbody::Tuning::bf64_min_bodies, false}, {"bf64_ipt", &nbody::Tuning::bf64_ipt, false},
     {"bf64_rot", &nbody::Tuning::bf64_rot, false}, {"bf64_waves", &nbody::Tuning::bf64_waves, false},
     {"pair_hist_combine", &nbody::Tuning::pair_hist_combine, false}, {"pair_hist_flush", &nbody::Tuning::pair_hist_flush, false},
+    {"deposit_sort", &nbody::Tuning::deposit_sort, false}, {"deposit_combine", &nbody::Tuning::deposit_combine, false},
+    {"deposit_lds", &nbody::Tuning::deposit_lds, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},

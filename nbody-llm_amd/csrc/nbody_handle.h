@@ -623,6 +623,7 @@ struct NbodyHandle {
     TracerState tr;
     ExternalField ext;
     PairSearch search;
+    uint64_t deposit_last[4] = {0, 0, 0, 0};   // nbody_deposit_stats: {a call reached the device, its plan, terms on the grid, global atomics}
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;

@@ -32,7 +32,9 @@
 // density centre (nbody_knn_density_center), on a line of its own.  The BINS + 1 edges of --pair-counts are formed here in f64:
 //     edges[0] = LO,  edges[BINS] = HI,  and for 0 < b < BINS
 //     lin: edges[b] = LO + (HI - LO) * (double(b) / double(BINS))      log: edges[b] = LO * pow(HI / LO, double(b) / double(BINS))
-// and printed with 17 significant digits, which name each double exactly.
+// and printed with 17 significant digits, which name each double exactly.  --deposit ngp|cic|tsc:N:HALF prints the mass of
+// the final state assigned to the N^3 cells of the cube [-HALF, HALF)^3 (nbody_deposit; spacing = (2 HALF) / N in f64): one
+// line with the four counts, one with the sum over the cells (in cell order) and the heaviest cell.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -62,6 +64,7 @@ static void usage() {
                  "                 [--density R[:tophat|spline]]   (the density centre of the final state, the largest density, r50 about that centre)\n"
                  "                 [--pair-counts LO:HI:BINS[:log|lin]]   (the pairs of the final state per bin of separation; log needs LO > 0)\n"
                  "                 [--knn K[:HINT]]   (every body's K nearest neighbours, 1 <= K <= 32: the median and largest K-th distance, the Casertano-Hut centre)\n"
+                 "                 [--deposit ngp|cic|tsc:N:HALF]   (the mass of the final state on the N^3 cells of [-HALF, HALF)^3)\n"
                  "                 [--pair-search all|cells]   (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
@@ -203,13 +206,33 @@ static void print_pair_counts(Sim& sim, const std::vector<double>& edges) {
     std::printf("Pair counts outside: below %llu beyond %llu\n", (unsigned long long)outside[0], (unsigned long long)outside[1]);
 }
 
+// the lines of --deposit: nbody_deposit of the mass over spec
+template <class Sim>
+static void print_deposit(Sim& sim, const NbodyGridSpec& spec) {
+    std::vector<double> grid;
+    uint64_t counts[4] = {0, 0, 0, 0};
+    sim.deposit(spec, grid, counts);
+    double sum = 0.0;
+    size_t top = 0;
+    for (size_t c = 0; c < grid.size(); ++c) {
+        sum += grid[c];
+        if (grid[c] > grid[top]) top = c;
+    }
+    const size_t ny = size_t(spec.dims[1]), nz = size_t(spec.dims[2]);
+    std::printf("Deposit: scheme %d dims %d %d %d spacing %.17e inside %llu partial %llu outside %llu skipped %llu\n", spec.scheme, spec.dims[0],
+                spec.dims[1], spec.dims[2], spec.spacing, (unsigned long long)counts[0], (unsigned long long)counts[1],
+                (unsigned long long)counts[2], (unsigned long long)counts[3]);
+    std::printf("Deposit sum %.17e max %.17e at %zu %zu %zu\n", sum, grid.empty() ? 0.0 : grid[top], top / (ny * nz), top / nz % ny, top % nz);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
                double width, unsigned long long seed, const std::string& integrator, const std::string& dump, int multipole,
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
-               double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint) {
+               double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint,
+               const NbodyGridSpec* deposit_spec) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -280,6 +303,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (density_radius > 0.0) print_density(*sim, density_radius, density_kernel);
         if (!pair_edges.empty()) print_pair_counts(*sim, pair_edges);
         if (knn_k > 0) print_knn(*sim, knn_k, knn_hint);
+        if (deposit_spec) print_deposit(*sim, *deposit_spec);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -326,6 +350,8 @@ int main(int argc, char** argv) {
     int density_kernel = NBODY_KERNEL_CUBIC_SPLINE;
     std::vector<double> pair_edges;
     int knn_k = 0;
+    NbodyGridSpec deposit_spec{};
+    bool deposit = false;
     double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -412,6 +438,26 @@ int main(int argc, char** argv) {
                 if (end == arg || *end || !(knn_hint > 0.0) || !std::isfinite(knn_hint)) { usage(); return 2; }
             }
         }
+        else if (!std::strcmp(argv[i], "--deposit")) {
+            const std::string arg = next();
+            const size_t c1 = arg.find(':'), c2 = c1 == std::string::npos ? c1 : arg.find(':', c1 + 1);
+            if (c2 == std::string::npos) { usage(); return 2; }
+            const std::string scheme = arg.substr(0, c1);
+            char* end = nullptr;
+            const long cells = std::strtol(arg.c_str() + c1 + 1, &end, 10);
+            if (end != arg.c_str() + c2) { usage(); return 2; }
+            const double half = std::strtod(arg.c_str() + c2 + 1, &end);
+            if (*end || !std::isfinite(half) || !(half > 0.0) || cells < 1 || cells > 512) { usage(); return 2; }
+            if (scheme == "ngp") deposit_spec.scheme = NBODY_DEPOSIT_NGP;
+            else if (scheme == "cic") deposit_spec.scheme = NBODY_DEPOSIT_CIC;
+            else if (scheme == "tsc") deposit_spec.scheme = NBODY_DEPOSIT_TSC;
+            else { usage(); return 2; }
+            for (int c = 0; c < 3; ++c) { deposit_spec.origin[c] = -half; deposit_spec.dims[c] = int32_t(cells); }
+            deposit_spec.spacing = (2.0 * half) / double(cells);
+            deposit_spec.quantity = NBODY_DEPOSIT_MASS;
+            deposit_spec.project_axis = -1;
+            deposit = true;
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -459,6 +505,6 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr);
 }

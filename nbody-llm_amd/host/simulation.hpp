@@ -408,6 +408,20 @@ public:
         counts.assign(edges.empty() ? 0 : edges.size() - 1, 0);
         check(nbody_pair_counts_at(h_, xyz.data(), xyz.size() / 3, edges.data(), int(edges.size()) - 1, counts.data(), outside));
     }
+    // grid deposit (nbody_deposit): the bodies' quantity (spec.quantity: NBODY_DEPOSIT_MASS ...) assigned to the cells of
+    // spec by NBODY_DEPOSIT_NGP / CIC / TSC in 64-bit fixed point -- the same state gives the same bits --; grid = [nx][ny][nz]
+    // row-major, counts = {inside, partial, outside, skipped}; read-only, the handles moments() takes.  deposit_stats: {a call
+    // reached the device, its plan, terms on the grid, 64-bit atomics sent to global memory} (nbody_deposit_stats).
+    // host_deposit: the same arithmetic on the host for n points {x, y, z} and their q (nbody_host_deposit; no device)
+    void deposit(const NbodyGridSpec& spec, std::vector<double>& grid, uint64_t counts[4]) {
+        grid.assign(size_t(spec.dims[0] > 0 ? spec.dims[0] : 0) * size_t(spec.dims[1] > 0 ? spec.dims[1] : 0) *
+                        size_t(spec.dims[2] > 0 ? spec.dims[2] : 0), 0.0);
+        check(nbody_deposit(h_, &spec, grid.empty() ? nullptr : grid.data(), grid.size(), counts));
+    }
+    void deposit_stats(uint64_t out[4]) { check(nbody_deposit_stats(h_, out)); }
+    static int host_deposit(const double* xyz, const double* q, size_t n, const NbodyGridSpec& spec, double* grid, size_t cap, uint64_t counts[4]) {
+        return nbody_host_deposit(xyz, q, n, &spec, grid, cap, counts);
+    }
     // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs
     // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
