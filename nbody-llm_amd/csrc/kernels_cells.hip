@@ -11,13 +11,10 @@
 //   k_cells_keys     key[i] of every row (rows past the live count and ungridded bodies: all ones), row[i] = i
 //   (rocprim::radix_sort_pairs, stable, on (key, row): the gridded bodies cell after cell, ascending row within a cell)
 //   k_cells_gather   the positions in that order; the distinct keys counted from the boundary flags (an integer atomicAdd)
-//   k_cells_link     one gridded body per lane in key order, so a wave's lanes share cells.  The three cells k_z - 1 .. k_z + 1
-//                    of one (k_x, k_y) column are one contiguous key range, clamped at the walls: two binary searches over
-//                    the sorted keys find it.  Key order is (k_x, k_y, k_z) order, so every candidate that stands after the
-//                    lane's own place lies in the rest of its own column or in the four columns (0, +1), (+1, -1), (+1, 0),
-//                    (+1, +1): each unordered candidate pair is evaluated once, from its earlier body.  Where r2 < B2 the
-//                    lane unites the ORIGINAL indices (fof_union.h; the proof that stale reads are harmless is DESIGN 3.18's)
-//   k_cells_nearest  the same walk over all nine columns: the least r2 < R2 and among equal r2 the lowest ORIGINAL index -- a
+//   k_cells_link     one gridded body per lane in key order, so a wave's lanes share cells; cell_walk.h's half walk: each
+//                    unordered candidate pair is evaluated once, from its earlier body.  Where r2 < B2 the lane unites the
+//                    ORIGINAL indices (fof_union.h; the proof that stale reads are harmless is DESIGN 3.18's)
+//   k_cells_nearest  the full walk, over all nine columns: the least r2 < R2 and among equal r2 the lowest ORIGINAL index -- a
 //                    rule on (r2, index) alone, so the order in which cells are visited cannot show
 //   k_cells_within   k_cells_nearest's walk for the neighbour lists of kernels_within.h: a pass that counts every body's
 //                    neighbours with r2 < R2, and after the caller's integer scan a pass that writes their ORIGINAL indices
@@ -27,11 +24,14 @@
 //                    binned by bin_slot, counted in a block-private LDS histogram that is added to the call's 64-bit slots
 // The walks count their candidate pairs (place t after place s) in integers: shuffles, then one atomicAdd per wave.
 #include "kernels_cells.h"
+#include "cell_walk.h"
+#include "device_util.h"   // inf64, live_count, wave_add
 #include "fof_union.h"
 #include "kernels_paircount.h"   // bin_slot, hist_begin, hist_flush
 #include "kernels_knn.h"   // list_slots
 #include "knn_list.h"
 #include "real.h"      // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -39,12 +39,10 @@
 namespace nbody {
 
 using pairs::kPairBlock;
-using cells::kCellBits;
-using cells::kCellMax;
+using cells::cell_walk;
+using cells::Walk;
 
 namespace {
-
-__device__ __forceinline__ int live_count(const int* __restrict__ count, int n_upper) { return max(0, min(*count, n_upper)); }
 
 // a double as an integer of the same order (-0.0 below +0.0), and back
 __host__ __device__ inline unsigned long long ordered_of(double v) {
@@ -57,33 +55,6 @@ inline double double_of(unsigned long long o) {
     double v;
     __builtin_memcpy(&v, &u, sizeof(v));
     return v;
-}
-
-// the first place in keys[lo, hi) whose key is >= k (kAfter: > k); hi when there is none
-template <bool kAfter>
-__device__ __forceinline__ int key_bound(const uint64_t* __restrict__ keys, int lo, int hi, uint64_t k) {
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        const uint64_t v = keys[mid];
-        if (kAfter ? v <= k : v < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// the places [a, b) of column (cx, cy), cells z0 .. z1, among the n gridded bodies; false: the column lies outside the grid
-__device__ __forceinline__ bool column_range(const uint64_t* __restrict__ keys, int from, int n, long long cx, long long cy, uint64_t z0,
-                                             uint64_t z1, int* a, int* b) {
-    if (cx < 0 || cy < 0 || cx > (long long)kCellMax || cy > (long long)kCellMax) return false;
-    *a = key_bound<false>(keys, from, n, cells::cell_key(uint64_t(cx), uint64_t(cy), z0));
-    *b = key_bound<true>(keys, *a, n, cells::cell_key(uint64_t(cx), uint64_t(cy), z1));
-    return true;
-}
-
-// the sum of v over the wave into *total (an integer: the order cannot show); every lane of the wave calls it
-__device__ __forceinline__ void wave_add(unsigned long long v, unsigned long long* total) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (threadIdx.x % 64 == 0 && v) atomicAdd(total, v);
 }
 
 }  // namespace
@@ -153,24 +124,13 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_link(int n_gridded, const 
     const int s = blockIdx.x * kPairBlock + threadIdx.x;
     unsigned long long cand = 0;
     if (s < n_gridded) {
-        const uint64_t key = keys[s];
-        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
-        const uint64_t kz = key & kCellMax;
-        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;   // clamped at the walls
         const double4 pi = spos[s];
         const int i = rows[s];
         const fof::DevParent forest{parent};
-        for (int c = 0; c < 5; ++c) {   // (0, 0) | (0, +1) | (+1, -1), (+1, 0), (+1, +1)
-            const int dx = c >= 2, dy = c == 0 ? 0 : c == 1 ? 1 : c - 3;
-            int a, b;
-            if (!column_range(keys, s + 1, n_gridded, kx + dx, ky + dy, c == 0 ? kz : z0, z1, &a, &b)) continue;
-            // (own column: from the lane's own cell on, the places after s; the cell below holds earlier places only)
-            cand += (unsigned long long)(b - a);
-            for (int t = a; t < b; ++t) {
-                const double r2 = fof::pair_dist2(pi, spos[t]);
-                if (r2 < B2) fof::fof_link(forest, i, rows[t]);   // (strict; a NaN never links)
-            }
-        }
+        cand = cell_walk<Walk::half>(keys, n_gridded, s, [&](int t) {
+            const double r2 = fof::pair_dist2(pi, spos[t]);
+            if (r2 < B2) fof::fof_link(forest, i, rows[t]);   // (strict; a NaN never links)
+        });
     }
     wave_add(cand, &counters->candidates);
 }
@@ -179,7 +139,7 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_nearest_init(int n_upper, 
     const int i = blockIdx.x * kPairBlock + threadIdx.x;
     if (i >= n_upper) return;
     partner[i] = -1;
-    energy[i] = __longlong_as_double(0x7ff0000000000000ll);
+    energy[i] = inf64();
 }
 
 __global__ __launch_bounds__(kPairBlock) void k_cells_nearest(int n_gridded, const uint64_t* __restrict__ keys, const int* __restrict__ rows,
@@ -188,25 +148,15 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_nearest(int n_gridded, con
     const int s = blockIdx.x * kPairBlock + threadIdx.x;
     unsigned long long cand = 0;
     if (s < n_gridded) {
-        const uint64_t key = keys[s];
-        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
-        const uint64_t kz = key & kCellMax;
-        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;
         const double4 pi = spos[s];
-        double best = __longlong_as_double(0x7ff0000000000000ll);
+        double best = inf64();
         int best_j = -1;
-        for (int c = 0; c < 9; ++c) {
-            int a, b;
-            if (!column_range(keys, 0, n_gridded, kx + (c / 3 - 1), ky + (c % 3 - 1), z0, z1, &a, &b)) continue;
-            const int after = max(a, s + 1);
-            if (b > after) cand += (unsigned long long)(b - after);
-            for (int t = a; t < b; ++t) {
-                const double r2 = fof::pair_dist2(pi, spos[t]);
-                if (t == s || !(r2 < R2)) continue;   // (strict; a NaN is never within R)
-                const int j = rows[t];
-                if (r2 < best || (r2 == best && j < best_j)) { best = r2; best_j = j; }
-            }
-        }
+        cand = cell_walk<Walk::full>(keys, n_gridded, s, [&](int t) {
+            const double r2 = fof::pair_dist2(pi, spos[t]);
+            if (!(r2 < R2)) return;   // (strict; a NaN is never within R)
+            const int j = rows[t];
+            if (r2 < best || (r2 == best && j < best_j)) { best = r2; best_j = j; }
+        });
         partner[rows[s]] = best_j;
         energy[rows[s]] = best;
     }
@@ -224,31 +174,21 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_within(int n_gridded, cons
     const int s = blockIdx.x * kPairBlock + threadIdx.x;
     unsigned long long cand = 0, hits = 0;
     if (s < n_gridded) {
-        const uint64_t key = keys[s];
-        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
-        const uint64_t kz = key & kCellMax;
-        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;
         const double4 pi = spos[s];
         unsigned at = kFill ? unsigned(offset[rows[s]]) : 0u;
-        for (int c = 0; c < 9; ++c) {
-            int a, b;
-            if (!column_range(keys, 0, n_gridded, kx + (c / 3 - 1), ky + (c % 3 - 1), z0, z1, &a, &b)) continue;
-            const int after = max(a, s + 1);
-            if (!kFill && b > after) cand += (unsigned long long)(b - after);
-            for (int t = a; t < b; ++t) {
-                const double r2 = fof::pair_dist2(pi, spos[t]);
-                if (t == s || !(r2 < R2)) continue;   // (strict; a NaN is never within R)
-                if constexpr (kFill) {
-                    if (at < cap) raw[at] = rows[t];   // (at < cap always: the count pass saw the same state)
-                    ++at;
-                } else {
-                    ++hits;
-                }
+        cand = cell_walk<Walk::full>(keys, n_gridded, s, [&](int t) {
+            const double r2 = fof::pair_dist2(pi, spos[t]);
+            if (!(r2 < R2)) return;   // (strict; a NaN is never within R)
+            if constexpr (kFill) {
+                if (at < cap) raw[at] = rows[t];   // (at < cap always: the count pass saw the same state)
+                ++at;
+            } else {
+                ++hits;
             }
-        }
+        });
         if constexpr (!kFill) found[rows[s]] = int(hits);
     }
-    if constexpr (!kFill) {
+    if constexpr (!kFill) {   // (kFill: total and counters are null, and the walk's count is dropped)
         wave_add(hits, total);
         wave_add(cand, &counters->candidates);
     }
@@ -269,29 +209,19 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_knn(int n_gridded, const u
     const int s = blockIdx.x * kPairBlock + tid;
     unsigned long long cand = 0;
     if (s < n_gridded) {
-        const uint64_t key = keys[s];
-        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
-        const uint64_t kz = key & kCellMax;
-        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;
         const double4 pi = spos[s];
         knn::ListState st;
-        for (int c = 0; c < 9; ++c) {
-            int a, b;
-            if (!column_range(keys, 0, n_gridded, kx + (c / 3 - 1), ky + (c % 3 - 1), z0, z1, &a, &b)) continue;
-            const int after = max(a, s + 1);
-            if (b > after) cand += (unsigned long long)(b - after);
-            for (int t = a; t < b; ++t) {
-                const double r2 = fof::pair_dist2(pi, spos[t]);
-                if (t == s || !(r2 < R2)) continue;   // (strict; a NaN is never within R)
-                const int j = rows[t];
-                if (st.admits(r2, j)) knn::list_insert(lists, tid, k, st, r2, j);
-            }
-        }
+        cand = cell_walk<Walk::full>(keys, n_gridded, s, [&](int t) {
+            const double r2 = fof::pair_dist2(pi, spos[t]);
+            if (!(r2 < R2)) return;   // (strict; a NaN is never within R)
+            const int j = rows[t];
+            if (st.admits(r2, j)) knn::list_insert(lists, tid, k, st, r2, j);
+        });
         const size_t row = size_t(rows[s]);   // (< the live count <= n_upper)
         found[row] = st.held;
         for (int slot = 0; slot < k; ++slot) {
             neighbor[row * size_t(k) + size_t(slot)] = slot < st.held ? lists.j[slot][tid] : -1;
-            dist2[row * size_t(k) + size_t(slot)] = slot < st.held ? lists.r2[slot][tid] : knn::list_inf();
+            dist2[row * size_t(k) + size_t(slot)] = slot < st.held ? lists.r2[slot][tid] : inf64();
         }
     }
     wave_add(cand, &counters->candidates);
@@ -313,28 +243,18 @@ __global__ __launch_bounds__(kPairBlock) void k_cells_pair_hist(int n_gridded, c
     const int s = blockIdx.x * kPairBlock + threadIdx.x;
     unsigned long long cand = 0;
     if (s < n_gridded) {
-        const uint64_t key = keys[s];
-        const long long kx = (long long)(key >> (2 * kCellBits)), ky = (long long)((key >> kCellBits) & kCellMax);
-        const uint64_t kz = key & kCellMax;
-        const uint64_t z0 = kz ? kz - 1 : 0, z1 = kz < kCellMax ? kz + 1 : kCellMax;   // clamped at the walls
         const double4 pi = spos[s];
         unsigned used = 0;
-        for (int c = 0; c < 5; ++c) {   // (0, 0) | (0, +1) | (+1, -1), (+1, 0), (+1, +1)
-            const int dx = c >= 2, dy = c == 0 ? 0 : c == 1 ? 1 : c - 3;
-            int a, b;
-            if (!column_range(keys, s + 1, n_gridded, kx + dx, ky + dy, c == 0 ? kz : z0, z1, &a, &b)) continue;
-            cand += (unsigned long long)(b - a);
-            for (int t = a; t < b; ++t) {
-                const int slot = paircount::bin_slot(e2, n_bins, top, fof::pair_dist2(pi, spos[t]));
-                if (slot > n_bins) continue;   // (beyond the last edge, or a NaN: counted by subtraction)
-                if (used < lane_budget) {
-                    atomicAdd(hist + slot, 1u);
-                    ++used;
-                } else {
-                    atomicAdd(out + slot, 1ull);
-                }
+        cand = cell_walk<Walk::half>(keys, n_gridded, s, [&](int t) {
+            const int slot = paircount::bin_slot(e2, n_bins, top, fof::pair_dist2(pi, spos[t]));
+            if (slot > n_bins) return;   // (beyond the last edge, or a NaN: counted by subtraction)
+            if (used < lane_budget) {
+                atomicAdd(hist + slot, 1u);
+                ++used;
+            } else {
+                atomicAdd(out + slot, 1ull);
             }
-        }
+        });
     }
     paircount::hist_flush(hist, n_bins, out);
     wave_add(cand, &counters->candidates);
@@ -351,7 +271,6 @@ size_t bounds_of(const BoundsWords& w, double lo[3], double hi[3]) {
 }
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 size_t sort_tmp_bytes(size_t n_upper) {
     size_t b = 0;
     uint64_t* k = nullptr;
@@ -359,25 +278,20 @@ size_t sort_tmp_bytes(size_t n_upper) {
     (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_upper, 0, 64, 0);
     return b;
 }
-}  // namespace
-
-size_t scratch_bytes(size_t n_upper) {
-    return up256(sizeof(Counters)) + up256(2 * n_upper * sizeof(uint64_t)) + up256(2 * n_upper * sizeof(int)) +
-           up256(n_upper * sizeof(double4)) + up256(sort_tmp_bytes(n_upper));
-}
-
-CellScratch scratch_layout(void* base, size_t n_upper) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+CellScratch layout(Carver& c, size_t n_upper) {
     CellScratch w;
-    w.counters = static_cast<Counters*>(take(sizeof(Counters)));
-    w.keys = static_cast<uint64_t*>(take(2 * n_upper * sizeof(uint64_t)));
-    w.rows = static_cast<int*>(take(2 * n_upper * sizeof(int)));
-    w.spos = static_cast<double4*>(take(n_upper * sizeof(double4)));
+    w.counters = c.take<Counters>(1);
+    w.keys = c.take<uint64_t>(2 * n_upper);
+    w.rows = c.take<int>(2 * n_upper);
+    w.spos = c.take<double4>(n_upper);
     w.sort_bytes = sort_tmp_bytes(n_upper);
-    w.sort_tmp = take(w.sort_bytes);
+    w.sort_tmp = c.take<char>(w.sort_bytes);
     return w;
 }
+}  // namespace
+
+size_t scratch_bytes(size_t n_upper) { Carver c; layout(c, n_upper); return c.offset(); }
+CellScratch scratch_layout(void* base, size_t n_upper) { Carver c(base); return layout(c, n_upper); }
 
 template <class F>
 void launch_bounds(hipStream_t s, const ShardT<F>& sh, int n_upper, BoundsWords* bounds) {

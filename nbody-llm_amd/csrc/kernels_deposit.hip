@@ -20,8 +20,10 @@
 //   k_deposit_convert  grid[c] = ldexp((double) acc[c], -S), in place
 // S is formed on the device from the live count and the largest |q| (deposit_grid.h scale_of): no host round trip in between.
 #include "kernels_deposit.h"
+#include "device_util.h"   // live_count, wave_add
 #include "kernels.h"   // tuning()
 #include "real.h"      // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -31,14 +33,6 @@ using deposit::kDepositBlock;
 using deposit::kTileSlots;
 
 namespace {
-
-__device__ __forceinline__ int live_count(const int* __restrict__ count, int n_upper) { return max(0, min(*count, n_upper)); }
-
-// the sum of v over the wave into *total (an integer: the order cannot show); every lane of the wave calls it
-__device__ __forceinline__ void wave_add(unsigned long long v, unsigned long long* total) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (threadIdx.x % 64 == 0 && v) atomicAdd(total, v);
-}
 
 __device__ __forceinline__ double quantity_of(int quantity, const double4 p, const double4 v) {
     switch (quantity) {
@@ -227,7 +221,6 @@ Plan make_plan() {
 }
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 int key_bits(size_t cells) {   // the bits of the largest key, `cells` itself
     int b = 1;
     while ((size_t(1) << b) <= cells) ++b;
@@ -240,30 +233,25 @@ size_t sort_tmp_bytes(size_t n_upper, size_t cells) {
     (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_upper, 0, unsigned(key_bits(cells)), 0);
     return b;
 }
-}  // namespace
-
-size_t scratch_bytes(size_t n_upper, size_t cells, bool with_grid, bool sorted) {
-    size_t b = up256(sizeof(Words)) + up256(n_upper * sizeof(double));
-    if (with_grid) b += up256(cells * sizeof(long long));
-    if (with_grid && sorted)
-        b += up256(2 * n_upper * sizeof(uint32_t)) + up256(2 * n_upper * sizeof(int)) + up256(sort_tmp_bytes(n_upper, cells));
-    return b;
-}
-
-Scratch scratch_layout(void* base, size_t n_upper, size_t cells, bool with_grid, bool sorted) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+Scratch layout(Carver& c, size_t n_upper, size_t cells, bool with_grid, bool sorted) {
     Scratch w;
-    w.words = static_cast<Words*>(take(sizeof(Words)));
-    w.q = static_cast<double*>(take(n_upper * sizeof(double)));
-    if (with_grid) w.acc = static_cast<long long*>(take(cells * sizeof(long long)));
+    w.words = c.take<Words>(1);
+    w.q = c.take<double>(n_upper);
+    if (with_grid) w.acc = c.take<long long>(cells);
     if (with_grid && sorted) {
-        w.keys = static_cast<uint32_t*>(take(2 * n_upper * sizeof(uint32_t)));
-        w.rows = static_cast<int*>(take(2 * n_upper * sizeof(int)));
+        w.keys = c.take<uint32_t>(2 * n_upper);
+        w.rows = c.take<int>(2 * n_upper);
         w.sort_bytes = sort_tmp_bytes(n_upper, cells);
-        w.sort_tmp = take(w.sort_bytes);
+        w.sort_tmp = c.take<char>(w.sort_bytes);
     }
     return w;
+}
+}  // namespace
+
+size_t scratch_bytes(size_t n_upper, size_t cells, bool with_grid, bool sorted) { Carver c; layout(c, n_upper, cells, with_grid, sorted); return c.offset(); }
+Scratch scratch_layout(void* base, size_t n_upper, size_t cells, bool with_grid, bool sorted) {
+    Carver c(base);
+    return layout(c, n_upper, cells, with_grid, sorted);
 }
 
 template <class F>

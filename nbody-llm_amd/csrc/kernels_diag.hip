@@ -15,6 +15,7 @@
 //   k_diag_radii    one lane per fraction: binary search over the prefixes, sqrt of the key found
 #include "kernels_diag.h"
 #include "real.h"   // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -213,7 +214,6 @@ void launch_diag_moments(hipStream_t s, const ShardT<F>& sh, int n_upper, double
 }
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
 size_t sort_tmp_bytes(size_t n_upper) {
     size_t b = 0;
     unsigned long long* k = nullptr;
@@ -221,32 +221,25 @@ size_t sort_tmp_bytes(size_t n_upper) {
     (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_upper, 0, 64, 0);
     return b;
 }
-}  // namespace
-
-size_t radii_scratch_bytes(size_t n_upper, size_t n_frac) {
+RadiiScratch layout(Carver& c, size_t n_upper, size_t n_frac) {
     const size_t tiles = size_t(blocks_for(int(n_upper)));
-    return up256(2 * n_upper * sizeof(unsigned long long)) + up256(2 * n_upper * sizeof(int)) + up256(n_upper * sizeof(double)) +
-           up256(2 * tiles * sizeof(double)) + up256(sizeof(int)) + up256(3 * sizeof(double)) + up256(n_frac * sizeof(double)) +
-           up256((n_frac + 1) * sizeof(double)) + up256(sort_tmp_bytes(n_upper));
-}
-
-RadiiScratch radii_scratch_layout(void* base, size_t n_upper, size_t n_frac) {
-    const size_t tiles = size_t(blocks_for(int(n_upper)));
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* p = at; at += up256(bytes); return static_cast<void*>(p); };
     RadiiScratch w;
-    w.keys = static_cast<unsigned long long*>(take(2 * n_upper * sizeof(unsigned long long)));
-    w.idx = static_cast<int*>(take(2 * n_upper * sizeof(int)));
-    w.c = static_cast<double*>(take(n_upper * sizeof(double)));
-    w.totals = static_cast<double*>(take(2 * tiles * sizeof(double)));
-    w.n_valid = static_cast<int*>(take(sizeof(int)));
-    w.center = static_cast<double*>(take(3 * sizeof(double)));
-    w.fractions = static_cast<double*>(take(n_frac * sizeof(double)));
-    w.out = static_cast<double*>(take((n_frac + 1) * sizeof(double)));
+    w.keys = c.take<unsigned long long>(2 * n_upper);
+    w.idx = c.take<int>(2 * n_upper);
+    w.c = c.take<double>(n_upper);
+    w.totals = c.take<double>(2 * tiles);
+    w.n_valid = c.take<int>(1);
+    w.center = c.take<double>(3);
+    w.fractions = c.take<double>(n_frac);
+    w.out = c.take<double>(n_frac + 1);
     w.sort_bytes = sort_tmp_bytes(n_upper);
-    w.sort_tmp = take(w.sort_bytes);
+    w.sort_tmp = c.take<char>(w.sort_bytes);
     return w;
 }
+}  // namespace
+
+size_t radii_scratch_bytes(size_t n_upper, size_t n_frac) { Carver c; layout(c, n_upper, n_frac); return c.offset(); }
+RadiiScratch radii_scratch_layout(void* base, size_t n_upper, size_t n_frac) { Carver c(base); return layout(c, n_upper, n_frac); }
 
 template <class F>
 int launch_diag_radii(hipStream_t s, const ShardT<F>& sh, int n_upper, int n_frac, const RadiiScratch& w) {

@@ -26,7 +26,9 @@
 //   k_fof_sums     one wave per listed group: the seven sums in the order the header fixes, and the NbodyGroup record
 #include "kernels_fof.h"
 #include "fof_union.h"
+#include "pair_tiles.h"
 #include "real.h"      // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -38,12 +40,6 @@ namespace nbody {
 using pairs::kPairBlock;
 using fof::DevParent;     // kernels_fof.h: shared with k_cells_link
 using fof::pair_dist2;
-
-namespace {
-
-__device__ __forceinline__ int live_count(const int* __restrict__ count, int n_upper) { return max(0, min(*count, n_upper)); }
-
-}  // namespace
 
 __global__ __launch_bounds__(kPairBlock) void k_fof_init(const int* __restrict__ count, int n_upper, int* __restrict__ parent,
                                                          int* __restrict__ size) {
@@ -57,28 +53,20 @@ template <class F>
 __global__ __launch_bounds__(kPairBlock) void k_fof_link(const typename Real<F>::V4* __restrict__ pos, const int* __restrict__ count,
                                                          int n_upper, int groups, int K, double B2, int* parent) {
     __shared__ double4 tx[kPairBlock];
-    const int tid = threadIdx.x;
-    const int group = int(blockIdx.x) % groups, slice = int(blockIdx.x) / groups;
     const int n = live_count(count, n_upper);
-    const int first = group * kPairBlock;   // the lowest body of this block
-    const int hi = int((long long)n * (slice + 1) / K);
-    if (hi - 1 <= first) return;   // (block-uniform: no partner j > i for any of its bodies)
-    const int lo = max(int((long long)n * slice / K), first);
-    const int i = first + tid;
+    pairs::PairFrame f(groups, K, n);
+    if (!f.triangle()) return;   // (block-uniform: no partner j > i for any of its bodies)
+    const int i = f.first + int(threadIdx.x);
     const bool live = i < n;
     const int mine = live ? i : INT_MAX;   // (no j is above it: a lane without a body links nothing)
     const double4 pi = live ? widen(pos[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
     const DevParent forest{parent};
-    for (int t0 = lo; t0 < hi; t0 += kPairBlock) {
-        const int cnt = min(kPairBlock, hi - t0);
-        __syncthreads();
-        if (tid < cnt) tx[tid] = widen(pos[t0 + tid]);   // (t0 + tid < hi <= n <= n_upper)
-        __syncthreads();
-        for (int t = 0; t < cnt; ++t) {
-            const double r2 = pair_dist2(pi, tx[t]);   // wave-uniform addresses: LDS broadcasts
-            if (r2 < B2 && t0 + t > mine) fof::fof_link(forest, i, t0 + t);   // (strict; a NaN never links)
-        }
-    }
+    pairs::for_each_partner(
+        f, [&](int slot, int j) { tx[slot] = widen(pos[j]); },   // (j < hi <= n <= n_upper)
+        [&](int j, int t) {
+            const double r2 = pair_dist2(pi, tx[t]);
+            if (r2 < B2 && j > mine) fof::fof_link(forest, i, j);   // (strict; a NaN never links)
+        });
 }
 
 __global__ __launch_bounds__(kPairBlock) void k_fof_flatten(const int* __restrict__ count, int n_upper, const int* __restrict__ parent,
@@ -152,13 +140,6 @@ __global__ __launch_bounds__(kPairBlock) void k_fof_sums(const typename Real<F>:
 namespace fof {
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-size_t scan_tmp_bytes(size_t n_upper) {
-    size_t b = 0;
-    int* v = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, n_upper, rocprim::plus<int>(), 0);
-    return b;
-}
 size_t sort_tmp_bytes(size_t n_upper) {
     size_t b = 0;
     unsigned* k = nullptr;
@@ -166,28 +147,22 @@ size_t sort_tmp_bytes(size_t n_upper) {
     (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n_upper, 0, 31, 0);
     return b;
 }
-}  // namespace
-
-size_t scratch_bytes(size_t n_upper) {
-    return 8 * up256(n_upper * sizeof(int)) + up256(2 * n_upper * sizeof(unsigned)) + up256(2 * n_upper * sizeof(int)) +
-           up256(2 * sizeof(int)) + up256(scan_tmp_bytes(n_upper)) + up256(sort_tmp_bytes(n_upper));
-}
-
-FofScratch scratch_layout(void* base, size_t n_upper) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+FofScratch layout(Carver& c, size_t n_upper) {
     FofScratch w;
-    for (int** p : {&w.parent, &w.label, &w.size, &w.flag, &w.listed, &w.slot, &w.offset, &w.slot_root})
-        *p = static_cast<int*>(take(n_upper * sizeof(int)));
-    w.keys = static_cast<unsigned*>(take(2 * n_upper * sizeof(unsigned)));
-    w.rows = static_cast<int*>(take(2 * n_upper * sizeof(int)));
-    w.total = static_cast<int*>(take(2 * sizeof(int)));
-    w.scan_bytes = scan_tmp_bytes(n_upper);
-    w.scan_tmp = take(w.scan_bytes);
+    for (int** p : {&w.parent, &w.label, &w.size, &w.flag, &w.listed, &w.slot, &w.offset, &w.slot_root}) *p = c.take<int>(n_upper);
+    w.keys = c.take<unsigned>(2 * n_upper);
+    w.rows = c.take<int>(2 * n_upper);
+    w.total = c.take<int>(2);
+    w.scan_bytes = pairs::scan_tmp_bytes(n_upper);
+    w.scan_tmp = c.take<char>(w.scan_bytes);
     w.sort_bytes = sort_tmp_bytes(n_upper);
-    w.sort_tmp = take(w.sort_bytes);
+    w.sort_tmp = c.take<char>(w.sort_bytes);
     return w;
 }
+}  // namespace
+
+size_t scratch_bytes(size_t n_upper) { Carver c; layout(c, n_upper); return c.offset(); }
+FofScratch scratch_layout(void* base, size_t n_upper) { Carver c(base); return layout(c, n_upper); }
 
 template <class F>
 void launch_components(hipStream_t s, const ShardT<F>& sh, int n_upper, const pairs::PartnerPlan& p, double B2, const FofScratch& w) {

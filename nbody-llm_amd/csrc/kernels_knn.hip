@@ -23,6 +23,7 @@
 #include "kernels_fof.h"   // pair_dist2
 #include "knn_list.h"
 #include "real.h"          // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_pairs(const typename Real<F>
     __shared__ knn::ListLds<kSlots> lists;
     const int tid = threadIdx.x;
     const int group = int(blockIdx.x) % groups, slice = int(blockIdx.x) / groups;
-    const int n = max(0, min(*count, n_upper));
+    const int n = live_count(count, n_upper);
     const int q = group * kPairBlock + tid;   // the row's place: rec is indexed by it
     int i = -1;
     if constexpr (kList) {
@@ -50,6 +51,8 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_pairs(const typename Real<F>
     const double4 pi = live ? widen(pos[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
     const int lo = int((long long)n * slice / K), hi = int((long long)n * (slice + 1) / K);
     knn::ListState st;
+    // pair_tiles.h's loop, written out: through for_each_partner the compiler folds the three tests below into one mask and
+    // the pass over all rows measures 5% slower at k = 6
     for (int t0 = lo; t0 < hi; t0 += kPairBlock) {
         const int m = min(kPairBlock, hi - t0);
         __syncthreads();
@@ -65,7 +68,7 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_pairs(const typename Real<F>
         const size_t stride = size_t(groups) * kPairBlock;
         for (int slot = 0; slot < k; ++slot) {
             const size_t at = (size_t(slice) * size_t(k) + size_t(slot)) * stride + size_t(q);
-            rec_r2[at] = slot < st.held ? lists.r2[slot][tid] : knn::list_inf();
+            rec_r2[at] = slot < st.held ? lists.r2[slot][tid] : inf64();
             rec_j[at] = slot < st.held ? lists.j[slot][tid] : -1;
         }
     }
@@ -79,7 +82,7 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_merge(const int* __restrict_
     __shared__ knn::ListLds<kSlots> lists;
     const int tid = threadIdx.x;
     const int q = blockIdx.x * kPairBlock + tid;
-    const int n = max(0, min(*count, n_upper));
+    const int n = live_count(count, n_upper);
     int i = -1;
     if (list) {
         if (q < rows) i = list[q];
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_merge(const int* __restrict_
     }
     for (int slot = 0; slot < k; ++slot) {
         neighbor[size_t(i) * size_t(k) + size_t(slot)] = slot < st.held ? lists.j[slot][tid] : -1;
-        dist2[size_t(i) * size_t(k) + size_t(slot)] = slot < st.held ? lists.r2[slot][tid] : knn::list_inf();
+        dist2[size_t(i) * size_t(k) + size_t(slot)] = slot < st.held ? lists.r2[slot][tid] : inf64();
     }
 }
 
@@ -108,7 +111,7 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_flag(const int* __restrict__
                                                          int* __restrict__ flag) {
     const int i = blockIdx.x * kPairBlock + threadIdx.x;
     if (i >= n_upper) return;
-    flag[i] = i < max(0, min(*count, n_upper)) && found[i] < k ? 1 : 0;
+    flag[i] = i < live_count(count, n_upper) && found[i] < k ? 1 : 0;
 }
 
 __global__ __launch_bounds__(kPairBlock) void k_knn_compact(int n_upper, const int* __restrict__ flag, const int* __restrict__ offset,
@@ -125,10 +128,10 @@ __global__ __launch_bounds__(kPairBlock) void k_knn_density(const typename Real<
                                                             const double* __restrict__ dist2, double* __restrict__ rho,
                                                             double* __restrict__ rk2) {
     const int i = blockIdx.x * kPairBlock + threadIdx.x;
-    const int n = max(0, min(*count, n_upper));
+    const int n = live_count(count, n_upper);
     if (i >= n) return;
     const int* mine = neighbor + size_t(i) * size_t(k);
-    double d = 0.0, r2 = knn::list_inf();
+    double d = 0.0, r2 = inf64();
     if (mine[k - 1] >= 0) {   // the list is complete
         double M = 0.0;
         for (int slot = 0; slot < k - 1; ++slot) {
@@ -148,48 +151,33 @@ namespace knn {
 using pairs::blocks_for;
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-size_t scan_tmp_bytes(size_t n_upper) {
-    size_t b = 0;
-    int* v = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, n_upper, rocprim::plus<int>(), 0);
-    return b;
+void records(Carver& c, const PartnerPlan& p, int k, KnnScratch* w) {
+    const size_t entries = size_t(p.K) * size_t(k) * size_t(p.groups) * kPairBlock;
+    w->rec_r2 = c.take<double>(entries);
+    w->rec_j = c.take<int>(entries);
 }
-size_t record_entries(const PartnerPlan& p, int k) { return size_t(p.K) * size_t(k) * size_t(p.groups) * kPairBlock; }
-}  // namespace
-
-size_t scratch_bytes(size_t n_upper, int k, bool cells) {
-    size_t b = up256(n_upper * size_t(k) * sizeof(int)) + up256(n_upper * size_t(k) * sizeof(double));
-    if (cells) b += 4 * up256(n_upper * sizeof(int)) + up256(sizeof(int)) + up256(scan_tmp_bytes(n_upper));
-    return b;
-}
-
-size_t record_bytes(const PartnerPlan& p, int k) {
-    return up256(record_entries(p, k) * sizeof(double)) + up256(record_entries(p, k) * sizeof(int));
-}
-
-void record_layout(void* base, const PartnerPlan& p, int k, KnnScratch* w) {
-    w->rec_r2 = static_cast<double*>(base);
-    w->rec_j = reinterpret_cast<int*>(static_cast<char*>(base) + up256(record_entries(p, k) * sizeof(double)));
-}
-
-KnnScratch scratch_layout(void* base, size_t n_upper, int k, bool cells) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+KnnScratch layout(Carver& c, size_t n_upper, int k, bool cells) {
     KnnScratch w;
-    w.dist2 = static_cast<double*>(take(n_upper * size_t(k) * sizeof(double)));
-    w.neighbor = static_cast<int*>(take(n_upper * size_t(k) * sizeof(int)));
+    w.dist2 = c.take<double>(n_upper * size_t(k));
+    w.neighbor = c.take<int>(n_upper * size_t(k));
     if (cells) {
-        w.found = static_cast<int*>(take(n_upper * sizeof(int)));
-        w.flag = static_cast<int*>(take(n_upper * sizeof(int)));
-        w.offset = static_cast<int*>(take(n_upper * sizeof(int)));
-        w.list = static_cast<int*>(take(n_upper * sizeof(int)));
-        w.total = static_cast<int*>(take(sizeof(int)));
-        w.scan_bytes = scan_tmp_bytes(n_upper);
-        w.scan_tmp = take(w.scan_bytes);
+        w.found = c.take<int>(n_upper);
+        w.flag = c.take<int>(n_upper);
+        w.offset = c.take<int>(n_upper);
+        w.list = c.take<int>(n_upper);
+        w.total = c.take<int>(1);
+        w.scan_bytes = pairs::scan_tmp_bytes(n_upper);
+        w.scan_tmp = c.take<char>(w.scan_bytes);
     }
     return w;
 }
+}  // namespace
+
+size_t scratch_bytes(size_t n_upper, int k, bool cells) { Carver c; layout(c, n_upper, k, cells); return c.offset(); }
+KnnScratch scratch_layout(void* base, size_t n_upper, int k, bool cells) { Carver c(base); return layout(c, n_upper, k, cells); }
+
+size_t record_bytes(const PartnerPlan& p, int k) { Carver c; KnnScratch w; records(c, p, k, &w); return c.offset(); }
+void record_layout(void* base, const PartnerPlan& p, int k, KnnScratch* w) { Carver c(base); records(c, p, k, w); }
 
 namespace {
 template <class F, int kSlots>

@@ -18,7 +18,9 @@
 #include "kernels_paircount.h"
 #include "kernels.h"       // nbody::tuning()
 #include "kernels_fof.h"   // pair_dist2
+#include "pair_tiles.h"
 #include "real.h"          // widen
+#include "scratch_carve.h"
 
 #include <algorithm>
 #include <climits>
@@ -37,46 +39,39 @@ __global__ __launch_bounds__(kPairBlock) void k_pair_hist(const typename Real<F>
     __shared__ double4 tx[kPairBlock];
     __shared__ double e2[kMaxBins + 1];
     __shared__ unsigned hist[kSlots];
-    const int tid = threadIdx.x;
-    const int group = int(blockIdx.x) % groups, slice = int(blockIdx.x) / groups;
-    const int n = max(0, min(*count, n_upper));
-    const int first = group * kPairBlock;   // the lowest body of this block
-    const int partners = kCross ? m : n;
-    const int hi = int((long long)partners * (slice + 1) / K);
-    int lo = int((long long)partners * slice / K);
-    if (first >= n) return;   // (block-uniform: no live body)
+    const int n = live_count(count, n_upper);
+    pairs::PairFrame f(groups, K, kCross ? m : n);
+    if (f.first >= n) return;   // (block-uniform: no live body)
     if constexpr (!kCross) {
-        if (hi - 1 <= first) return;   // (block-uniform: no partner j > i for any of its bodies)
-        lo = max(lo, first);
+        if (!f.triangle()) return;   // (block-uniform: no partner j > i for any of its bodies)
     }
     paircount::hist_begin(e2_global, n_bins, e2, hist);   // (the tile loop's first barrier stands between this and any use)
-    const int i = first + tid;
+    const int i = f.first + int(threadIdx.x);
     const bool live = i < n;
     const int mine = !live ? INT_MAX : kCross ? -1 : i;   // the partners above `mine` count: none | all | j > i
     const double4 pi = live ? widen(pos[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
     int tiles = 0;
-    for (int t0 = lo; t0 < hi; t0 += kPairBlock) {
-        const int cnt = min(kPairBlock, hi - t0);
-        __syncthreads();
-        if (tid < cnt) {   // (t0 + tid < hi <= the partners)
+    pairs::for_each_partner(
+        f,
+        [&](int slot, int j) {
             if constexpr (kCross) {
-                const double* q = points + 3 * size_t(t0 + tid);
-                tx[tid] = make_double4(q[0], q[1], q[2], 0.0);
+                const double* q = points + 3 * size_t(j);
+                tx[slot] = make_double4(q[0], q[1], q[2], 0.0);
             } else {
-                tx[tid] = widen(pos[t0 + tid]);
+                tx[slot] = widen(pos[j]);
             }
-        }
-        __syncthreads();
-        for (int t = 0; t < cnt; ++t) {
-            const double r2 = fof::pair_dist2(pi, tx[t]);   // wave-uniform addresses: LDS broadcasts
-            const int slot = t0 + t > mine ? paircount::bin_slot(e2, n_bins, top, r2) : -1;
+        },
+        [&](int j, int t) {
+            const double r2 = fof::pair_dist2(pi, tx[t]);
+            const int slot = j > mine ? paircount::bin_slot(e2, n_bins, top, r2) : -1;
             paircount::hist_add<kCombine>(hist, slot);
-        }
-        if (++tiles == flush_tiles) {   // (block-uniform)
-            paircount::hist_flush(hist, n_bins, out);
-            tiles = 0;
-        }
-    }
+        },
+        [&] {
+            if (++tiles == flush_tiles) {   // (block-uniform)
+                paircount::hist_flush(hist, n_bins, out);
+                tiles = 0;
+            }
+        });
     paircount::hist_flush(hist, n_bins, out);
 }
 
@@ -91,7 +86,13 @@ HistPlan make_hist_plan() {
 }
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
+HistScratch layout(Carver& c, int n_bins, size_t batch) {
+    HistScratch w;
+    w.e2 = c.take<double>(size_t(n_bins + 1));
+    w.hist = c.take<unsigned long long>(size_t(n_bins + 2));
+    if (batch) w.points = c.take<double>(batch * 3);
+    return w;
+}
 
 template <class F, bool kCross>
 void launch(hipStream_t s, const ShardT<F>& sh, int n_upper, int m, const PartnerPlan& p, const HistPlan& hp, int n_bins, const HistScratch& w) {
@@ -107,20 +108,8 @@ void launch(hipStream_t s, const ShardT<F>& sh, int n_upper, int m, const Partne
 }
 }  // namespace
 
-size_t scratch_bytes(int n_bins, size_t batch) {
-    return up256(size_t(n_bins + 1) * sizeof(double)) + up256(size_t(n_bins + 2) * sizeof(unsigned long long)) +
-           up256(batch * 3 * sizeof(double));
-}
-
-HistScratch scratch_layout(void* base, int n_bins, size_t batch) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
-    HistScratch w;
-    w.e2 = static_cast<double*>(take(size_t(n_bins + 1) * sizeof(double)));
-    w.hist = static_cast<unsigned long long*>(take(size_t(n_bins + 2) * sizeof(unsigned long long)));
-    if (batch) w.points = static_cast<double*>(take(batch * 3 * sizeof(double)));
-    return w;
-}
+size_t scratch_bytes(int n_bins, size_t batch) { Carver c; layout(c, n_bins, batch); return c.offset(); }
+HistScratch scratch_layout(void* base, int n_bins, size_t batch) { Carver c(base); return layout(c, n_bins, batch); }
 
 template <class F>
 void launch_auto(hipStream_t s, const ShardT<F>& sh, int n_upper, const PartnerPlan& p, const HistPlan& hp, int n_bins, const HistScratch& w) {

@@ -11,6 +11,9 @@ constexpr int kPairBlock = 256;   // bodies per block of k_partner, and partners
 
 inline int blocks_for(int n) { return n <= 0 ? 0 : (n + kPairBlock - 1) / kPairBlock; }
 
+// the temporary storage of rocprim::exclusive_scan over n ints with plus<int>: the scan of every query's flags and counts
+size_t scan_tmp_bytes(size_t n);
+
 // k_partner's grid for n_upper >= live bodies: groups of kPairBlock bodies x K partner slices, about bf64_waves waves in all
 // (make_hm_act_plan's rule: a slice holds 64 partners or more); slice s of n live bodies is [n s / K, n (s + 1) / K)
 struct PartnerPlan { int groups = 0, K = 1; };

@@ -19,7 +19,9 @@
 //                    flags of every live row for the retain that follows (k_compact / k_hm_compact), and *escaped raised
 #include "kernels_pairs.h"
 #include "kernels.h"   // nbody::tuning()
+#include "pair_tiles.h"
 #include "real.h"      // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -30,8 +32,6 @@ namespace nbody {
 using pairs::kPairBlock;
 
 namespace {
-
-__device__ __forceinline__ double inf64() { return __longlong_as_double(0x7ff0000000000000ll); }
 
 // e_ij = 0.5 w2 - (g (m_i + m_j)) / sqrt(r2): d and w change sign with i <-> j, their squares do not, and the sum of the masses
 // commutes -- e_ij == e_ji bit for bit
@@ -57,33 +57,28 @@ __global__ __launch_bounds__(kPairBlock) void k_partner(const typename Real<F>::
                                                         int n_upper, int groups, int K, double g, double soft2,
                                                         double* __restrict__ rec_e, int* __restrict__ rec_j) {
     __shared__ double4 tx[kPairBlock], tv[kDist ? 1 : kPairBlock];
-    const int tid = threadIdx.x;
-    const int group = int(blockIdx.x) % groups, slice = int(blockIdx.x) / groups;
-    const int n = min(*count, n_upper);
-    const int i = group * kPairBlock + tid;
+    const int n = live_count(count, n_upper);
+    const pairs::PairFrame f(groups, K, n);
+    const int i = f.first + int(threadIdx.x);
     const bool live = i < n;
     const double4 pi = live ? widen(pos[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
     const double4 vi = live && !kDist ? widen(vel[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
-    const int lo = int((long long)n * slice / K), hi = int((long long)n * (slice + 1) / K);
     double best = inf64();
     int best_j = -1;
-    for (int t0 = lo; t0 < hi; t0 += kPairBlock) {
-        const int cnt = min(kPairBlock, hi - t0);
-        __syncthreads();
-        if (tid < cnt) {
-            tx[tid] = widen(pos[t0 + tid]);
-            if constexpr (!kDist) tv[tid] = widen(vel[t0 + tid]);
-        }
-        __syncthreads();
-        for (int t = 0; t < cnt; ++t) {
-            double e;   // wave-uniform addresses: LDS broadcasts
+    pairs::for_each_partner(
+        f,
+        [&](int slot, int j) {
+            tx[slot] = widen(pos[j]);
+            if constexpr (!kDist) tv[slot] = widen(vel[j]);
+        },
+        [&](int j, int t) {
+            double e;
             if constexpr (kDist) e = pair_dist2(pi, tx[t]);
             else e = pair_energy(pi, vi, tx[t], tv[t], g, soft2);
-            if (t0 + t != i && e < best) { best = e; best_j = t0 + t; }     // (a NaN never wins; the i == i pair is left out)
-        }
-    }
+            if (j != i && e < best) { best = e; best_j = j; }     // (a NaN never wins; the i == i pair is left out)
+        });
     if (live) {
-        const size_t row = size_t(slice) * (size_t(groups) * kPairBlock) + size_t(i);
+        const size_t row = size_t(f.slice) * (size_t(groups) * kPairBlock) + size_t(i);
         rec_e[row] = best;
         rec_j[row] = best_j;
     }
@@ -237,45 +232,39 @@ PartnerPlan make_partner_plan(int n_upper, int partners) {
     return p;
 }
 
-namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-size_t scan_tmp_bytes(size_t n_upper) {
+size_t scan_tmp_bytes(size_t n) {
     size_t b = 0;
     int* v = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, n_upper, rocprim::plus<int>(), 0);
+    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, n, rocprim::plus<int>(), 0);
     return b;
+}
+
+namespace {
+PairScratch layout(Carver& c, size_t n_upper, const PartnerPlan& p, bool want_pairs) {
+    const size_t rows = size_t(p.K) * size_t(p.groups) * kPairBlock;
+    PairScratch w;
+    w.rec_e = c.take<double>(rows);
+    w.rec_j = c.take<int>(rows);
+    w.energy = c.take<double>(n_upper);
+    w.partner = c.take<int>(n_upper);
+    if (want_pairs) {
+        w.flag = c.take<int>(n_upper);
+        w.offset = c.take<int>(n_upper);
+        w.total = c.take<int>(1);
+        static_assert(sizeof(NbodyContact) <= sizeof(NbodyBoundPair), "the list block is sized for the larger record");
+        w.pairs = c.take<NbodyBoundPair>(n_upper / 2 + 1);
+        w.contacts = reinterpret_cast<NbodyContact*>(w.pairs);   // (a call lists one kind)
+        w.scan_bytes = scan_tmp_bytes(n_upper);
+        w.scan_tmp = c.take<char>(w.scan_bytes);
+    }
+    return w;
 }
 }  // namespace
 
-size_t scratch_bytes(size_t n_upper, const PartnerPlan& p, bool want_pairs) {
-    const size_t rows = size_t(p.K) * size_t(p.groups) * kPairBlock;
-    size_t b = up256(rows * sizeof(double)) + up256(rows * sizeof(int)) + up256(n_upper * sizeof(double)) + up256(n_upper * sizeof(int));
-    if (want_pairs)
-        b += 2 * up256(n_upper * sizeof(int)) + up256(sizeof(int)) + up256((n_upper / 2 + 1) * sizeof(NbodyBoundPair)) +
-             up256(scan_tmp_bytes(n_upper));
-    return b;
-}
-
+size_t scratch_bytes(size_t n_upper, const PartnerPlan& p, bool want_pairs) { Carver c; layout(c, n_upper, p, want_pairs); return c.offset(); }
 PairScratch scratch_layout(void* base, size_t n_upper, const PartnerPlan& p, bool want_pairs) {
-    const size_t rows = size_t(p.K) * size_t(p.groups) * kPairBlock;
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
-    PairScratch w;
-    w.rec_e = static_cast<double*>(take(rows * sizeof(double)));
-    w.rec_j = static_cast<int*>(take(rows * sizeof(int)));
-    w.energy = static_cast<double*>(take(n_upper * sizeof(double)));
-    w.partner = static_cast<int*>(take(n_upper * sizeof(int)));
-    if (want_pairs) {
-        w.flag = static_cast<int*>(take(n_upper * sizeof(int)));
-        w.offset = static_cast<int*>(take(n_upper * sizeof(int)));
-        w.total = static_cast<int*>(take(sizeof(int)));
-        static_assert(sizeof(NbodyContact) <= sizeof(NbodyBoundPair), "the list block is sized for the larger record");
-        w.pairs = static_cast<NbodyBoundPair*>(take((n_upper / 2 + 1) * sizeof(NbodyBoundPair)));
-        w.contacts = reinterpret_cast<NbodyContact*>(w.pairs);   // (a call lists one kind)
-        w.scan_bytes = scan_tmp_bytes(n_upper);
-        w.scan_tmp = take(w.scan_bytes);
-    }
-    return w;
+    Carver c(base);
+    return layout(c, n_upper, p, want_pairs);
 }
 
 template <class F>

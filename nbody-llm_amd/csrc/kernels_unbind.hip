@@ -26,6 +26,7 @@
 //   k_unbind_records  one wave per reported group: kinetic and potential in seven_sums' shape, and the NbodyBoundGroup record
 #include "kernels_unbind.h"
 #include "real.h"   // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -243,36 +244,23 @@ __global__ __launch_bounds__(kPairBlock) void k_unbind_records(int n_groups, con
 namespace fof {
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-size_t scan_tmp_bytes(size_t n) {
-    size_t b = 0;
-    int* v = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, n, rocprim::plus<int>(), 0);
-    return b;
-}
 int waves_grid(int n_groups) { return (n_groups + kPairBlock / 64 - 1) / (kPairBlock / 64); }
-}  // namespace
-
-size_t unbind_scratch_bytes(size_t n_members, size_t n_groups) {
-    return up256(n_groups * sizeof(UnbindGroup)) + 4 * up256(n_members * sizeof(int)) + 4 * up256(n_members * sizeof(double)) +
-           4 * up256(n_groups * sizeof(int)) + up256(n_groups * sizeof(NbodyBoundGroup)) + up256(3 * sizeof(int)) +
-           up256(std::max(scan_tmp_bytes(n_members), scan_tmp_bytes(n_groups)));
-}
-
-UnbindScratch unbind_layout(void* base, size_t n_members, size_t n_groups) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+UnbindScratch layout(Carver& c, size_t n_members, size_t n_groups) {
     UnbindScratch u;
-    u.grp = static_cast<UnbindGroup*>(take(n_groups * sizeof(UnbindGroup)));
-    for (int** p : {&u.alive, &u.mark, &u.dest, &u.out_members}) *p = static_cast<int*>(take(n_members * sizeof(int)));
-    for (double** p : {&u.energy, &u.kinetic, &u.potential, &u.out_energy}) *p = static_cast<double*>(take(n_members * sizeof(double)));
-    for (int** p : {&u.keep, &u.kept, &u.slot, &u.offset}) *p = static_cast<int*>(take(n_groups * sizeof(int)));
-    u.out = static_cast<NbodyBoundGroup*>(take(n_groups * sizeof(NbodyBoundGroup)));
-    u.counters = static_cast<int*>(take(3 * sizeof(int)));
-    u.scan_bytes = std::max(scan_tmp_bytes(n_members), scan_tmp_bytes(n_groups));
-    u.scan_tmp = take(u.scan_bytes);
+    u.grp = c.take<UnbindGroup>(n_groups);
+    for (int** p : {&u.alive, &u.mark, &u.dest, &u.out_members}) *p = c.take<int>(n_members);
+    for (double** p : {&u.energy, &u.kinetic, &u.potential, &u.out_energy}) *p = c.take<double>(n_members);
+    for (int** p : {&u.keep, &u.kept, &u.slot, &u.offset}) *p = c.take<int>(n_groups);
+    u.out = c.take<NbodyBoundGroup>(n_groups);
+    u.counters = c.take<int>(3);
+    u.scan_bytes = std::max(pairs::scan_tmp_bytes(n_members), pairs::scan_tmp_bytes(n_groups));
+    u.scan_tmp = c.take<char>(u.scan_bytes);
     return u;
 }
+}  // namespace
+
+size_t unbind_scratch_bytes(size_t n_members, size_t n_groups) { Carver c; layout(c, n_members, n_groups); return c.offset(); }
+UnbindScratch unbind_layout(void* base, size_t n_members, size_t n_groups) { Carver c(base); return layout(c, n_members, n_groups); }
 
 void launch_unbind_init(hipStream_t s, int n_members, int n_groups, const FofScratch& w, const UnbindScratch& u) {
     if (n_members <= 0) return;

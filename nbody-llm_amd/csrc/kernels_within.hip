@@ -19,7 +19,9 @@
 //   k_within_center   one body per lane, four LDS sums of 256 doubles, k_diag_moments' pairwise tree per block
 #include "kernels_within.h"
 #include "kernels_fof.h"   // pair_dist2
+#include "pair_tiles.h"
 #include "real.h"          // widen
+#include "scratch_carve.h"
 
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -37,37 +39,29 @@ __global__ __launch_bounds__(kPairBlock) void k_within_pairs(const typename Real
                                                              const int* __restrict__ place, int* __restrict__ neighbor,
                                                              unsigned cap, unsigned long long* total) {
     __shared__ double4 tx[kPairBlock];
-    const int tid = threadIdx.x;
-    const int group = int(blockIdx.x) % groups, slice = int(blockIdx.x) / groups;
-    const int n = max(0, min(*count, n_upper));
-    const int i = group * kPairBlock + tid;
+    const int n = live_count(count, n_upper);
+    const pairs::PairFrame f(groups, K, n);
+    const int i = f.first + int(threadIdx.x);
     const bool live = i < n;
     const double4 pi = live ? widen(pos[i]) : make_double4(0.0, 0.0, 0.0, 0.0);
-    const int lo = int((long long)n * slice / K), hi = int((long long)n * (slice + 1) / K);
-    unsigned at = kFill && live ? unsigned(place[size_t(i) * K + slice]) : 0u;
+    unsigned at = kFill && live ? unsigned(place[size_t(i) * K + f.slice]) : 0u;
     int found = 0;
-    for (int t0 = lo; t0 < hi; t0 += kPairBlock) {
-        const int m = min(kPairBlock, hi - t0);
-        __syncthreads();
-        if (tid < m) tx[tid] = widen(pos[t0 + tid]);
-        __syncthreads();
-        for (int t = 0; t < m; ++t) {
-            const double r2 = fof::pair_dist2(pi, tx[t]);   // wave-uniform addresses: LDS broadcasts
-            if (live && t0 + t != i && r2 < R2) {           // (strict; a NaN is never within R)
+    pairs::for_each_partner(
+        f, [&](int slot, int j) { tx[slot] = widen(pos[j]); },
+        [&](int j, int t) {
+            const double r2 = fof::pair_dist2(pi, tx[t]);
+            if (r2 < R2 && j != i && live) {           // (strict; a NaN is never within R)
                 if constexpr (kFill) {
-                    if (at < cap) neighbor[at] = t0 + t;    // (at < cap always: the count pass saw the same state)
+                    if (at < cap) neighbor[at] = j;    // (at < cap always: the count pass saw the same state)
                     ++at;
                 } else {
                     ++found;
                 }
             }
-        }
-    }
+        });
     if constexpr (!kFill) {
-        if (i < n_upper) cnt[size_t(i) * K + slice] = found;   // (rows past the live count: 0)
-        unsigned long long v = (unsigned long long)found;
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);   // (every lane of the wave is here)
-        if (tid % 64 == 0 && v) atomicAdd(total, v);
+        if (i < n_upper) cnt[size_t(i) * K + f.slice] = found;   // (rows past the live count: 0)
+        wave_add((unsigned long long)found, total);             // (every lane of the wave is here)
     }
 }
 
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(kPairBlock) void k_within_density(const typename Re
                                                                const int* __restrict__ neighbor, double* __restrict__ rho,
                                                                int* __restrict__ terms) {
     const int i = blockIdx.x * kPairBlock + threadIdx.x;
-    const int n = max(0, min(*count, n_upper));
+    const int n = live_count(count, n_upper);
     if (i >= n) return;
     const double4 pi = widen(pos[i]);
     const double own = kSpline ? pi.w * spline_w(0.0) : pi.w;   // the body's own term: u = 0, no r2
@@ -118,7 +112,7 @@ __global__ __launch_bounds__(kPairBlock) void k_within_center(const typename Rea
     const int t = threadIdx.x;
     const int i = blockIdx.x * kPairBlock + t;
     double term[kCenterSums] = {0.0, 0.0, 0.0, 0.0};
-    if (i < max(0, min(*count, n_upper))) {
+    if (i < live_count(count, n_upper)) {
         const double4 p = widen(pos[i]);
         const double r = rho[i];
         term[0] = r;
@@ -144,13 +138,6 @@ namespace within {
 using pairs::blocks_for;
 
 namespace {
-size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-size_t scan_tmp_bytes(size_t words) {
-    size_t b = 0;
-    int* v = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, b, v, v, 0, words, rocprim::plus<int>(), 0);
-    return b;
-}
 // the bits that hold every index below n_upper
 unsigned key_bits(size_t n_upper) {
     unsigned bits = 1;
@@ -163,43 +150,36 @@ size_t sort_tmp_bytes(size_t n_upper, size_t total) {
     (void)rocprim::segmented_radix_sort_keys(nullptr, b, v, v, unsigned(total), unsigned(n_upper), v, v, 0, key_bits(n_upper), 0);
     return b;
 }
-}  // namespace
-
-size_t count_scratch_bytes(size_t n_upper, int K) {
-    const size_t words = n_upper * size_t(K) + 1;
-    return up256(sizeof(unsigned long long)) + 2 * up256(words * sizeof(int)) + (K > 1 ? up256((n_upper + 1) * sizeof(int)) : 0) +
-           up256(scan_tmp_bytes(words));
-}
-
-CountScratch count_scratch_layout(void* base, size_t n_upper, int K) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+CountScratch count_layout(Carver& at, size_t n_upper, int K) {
     CountScratch c;
     c.words = n_upper * size_t(K) + 1;
-    c.total = static_cast<unsigned long long*>(take(sizeof(unsigned long long)));
-    c.count = static_cast<int*>(take(c.words * sizeof(int)));
-    c.place = static_cast<int*>(take(c.words * sizeof(int)));
-    c.offset = K > 1 ? static_cast<int*>(take((n_upper + 1) * sizeof(int))) : c.place;
-    c.scan_bytes = scan_tmp_bytes(c.words);
-    c.scan_tmp = take(c.scan_bytes);
+    c.total = at.take<unsigned long long>(1);
+    c.count = at.take<int>(c.words);
+    c.place = at.take<int>(c.words);
+    c.offset = K > 1 ? at.take<int>(n_upper + 1) : c.place;
+    c.scan_bytes = pairs::scan_tmp_bytes(c.words);
+    c.scan_tmp = at.take<char>(c.scan_bytes);
     return c;
 }
-
-size_t list_scratch_bytes(size_t n_upper, size_t total, bool sorted) {
-    return up256(total * sizeof(int)) + (sorted ? up256(total * sizeof(int)) + up256(sort_tmp_bytes(n_upper, total)) : 0);
-}
-
-ListScratch list_scratch_layout(void* base, size_t n_upper, size_t total, bool sorted) {
-    char* at = static_cast<char*>(base);
-    auto take = [&at](size_t bytes) { char* q = at; at += up256(bytes); return static_cast<void*>(q); };
+ListScratch list_layout(Carver& at, size_t n_upper, size_t total, bool sorted) {
     ListScratch l;
-    l.neighbor = static_cast<int*>(take(total * sizeof(int)));
+    l.neighbor = at.take<int>(total);
     if (sorted) {
-        l.raw = static_cast<int*>(take(total * sizeof(int)));
+        l.raw = at.take<int>(total);
         l.sort_bytes = sort_tmp_bytes(n_upper, total);
-        l.sort_tmp = take(l.sort_bytes);
+        l.sort_tmp = at.take<char>(l.sort_bytes);
     }
     return l;
+}
+}  // namespace
+
+size_t count_scratch_bytes(size_t n_upper, int K) { Carver at; count_layout(at, n_upper, K); return at.offset(); }
+CountScratch count_scratch_layout(void* base, size_t n_upper, int K) { Carver at(base); return count_layout(at, n_upper, K); }
+
+size_t list_scratch_bytes(size_t n_upper, size_t total, bool sorted) { Carver at; list_layout(at, n_upper, total, sorted); return at.offset(); }
+ListScratch list_scratch_layout(void* base, size_t n_upper, size_t total, bool sorted) {
+    Carver at(base);
+    return list_layout(at, n_upper, total, sorted);
 }
 
 void launch_clear(hipStream_t s, const CountScratch& c) {

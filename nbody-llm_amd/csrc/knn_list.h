@@ -3,6 +3,7 @@
 // ascending in (r2, index).  Nothing here adds or multiplies: the lists hold bits that the callers computed.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "device_util.h"     // inf64
 #include "kernels_pairs.h"   // kPairBlock
 
 namespace nbody { namespace knn {
@@ -15,13 +16,11 @@ struct ListLds {
     int j[kSlots][pairs::kPairBlock];
 };
 
-__device__ __forceinline__ double list_inf() { return __longlong_as_double(0x7ff0000000000000ll); }
-
 // One lane's list and what admits a candidate to it: `held` entries (<= k), and the last entry of a full list -- {+inf, INT_MAX}
 // while it is not full, so every r2 < +inf comes before it
 struct ListState {
     int held = 0;
-    double last_r2 = list_inf();
+    double last_r2 = inf64();
     int last_j = 0x7fffffff;
     // (r2, j) comes before the last entry of a full list, or the list is not full and r2 < +inf; a NaN never does
     __device__ __forceinline__ bool admits(double r2, int j) const { return r2 < last_r2 || (r2 == last_r2 && j < last_j); }

@@ -1,7 +1,9 @@
 // sanitize_handle_mem.cpp -- the bookkeeping of nbody-llm_amd/csrc/handle_mem.h (the registry of a handle's device and pinned
 // blocks, the one grow, the scoped scratch) over a malloc-backed seam that counts its calls and can fail the k-th allocation.
+// And the carver of nbody-llm_amd/csrc/scratch_carve.h, which lays a call's scratch out inside one such block.
 // Built with -fsanitize=address,undefined by tests/test_handle_mem.py; prints "ok" only when every check held.
 #include "handle_mem.h"
+#include "scratch_carve.h"
 
 #include <cstdint>
 #include <cstdio>
@@ -173,6 +175,49 @@ void check_bad_free() {
     CHECK(pinned == nullptr && g_frees == frees + 1 && balanced());
 }
 
+// 7: the scratch carver (scratch_carve.h) alone: for sequences of (count, type) takes, zero-length ones among them, the
+// measuring pass and the placing pass end at the same offset, every block starts at a multiple of 256 bytes, and the blocks are
+// disjoint and lie inside the measured size (every byte of every block is written: ASan sees the allocation's end)
+struct Take { size_t count, size; };
+template <class T>
+char* take_as(nbody::Carver& c, size_t count) { return reinterpret_cast<char*>(c.take<T>(count)); }
+char* take_one(nbody::Carver& c, const Take& t) {
+    struct Wide { double d[5]; };   // 40 bytes: no power of two
+    switch (t.size) {
+    case 1: return take_as<char>(c, t.count);
+    case 4: return take_as<int>(c, t.count);
+    case 8: return take_as<double>(c, t.count);
+    default: return take_as<Wide>(c, t.count);
+    }
+}
+void check_carver() {
+    CHECK(nbody::up256(0) == 0 && nbody::up256(1) == 256 && nbody::up256(256) == 256 && nbody::up256(257) == 512);
+    const Take seqs[][6] = {
+        {{1, 8}, {257, 4}, {0, 8}, {64, 4}, {3, 40}, {255, 1}},
+        {{0, 4}, {0, 8}, {0, 1}, {0, 40}, {0, 4}, {0, 8}},
+        {{0, 40}, {1, 1}, {256, 1}, {257, 1}, {0, 4}, {65536, 8}},
+        {{7, 40}, {0, 1}, {1, 4}, {1, 4}, {32, 8}, {33, 8}},
+    };
+    for (const auto& seq : seqs) {
+        nbody::Carver measure;
+        for (const Take& t : seq) CHECK(take_one(measure, t) == nullptr);
+        const size_t bytes = measure.offset();
+        char* base = nullptr;
+        CHECK(posix_memalign(reinterpret_cast<void**>(&base), 256, bytes ? bytes : 1) == 0);
+        nbody::Carver place(base);
+        size_t end = 0;   // where the block before ended: the blocks ascend, so disjoint means start >= end
+        for (const Take& t : seq) {
+            char* p = take_one(place, t);
+            const size_t at = size_t(p - base), len = t.count * t.size;
+            CHECK(at % 256 == 0 && at >= end && at + len <= bytes);
+            std::memset(p, 0x5a, len);
+            end = at + len;
+        }
+        CHECK(place.offset() == bytes && bytes % 256 == 0);
+        std::free(base);
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -182,6 +227,7 @@ int main() {
     check_grow_keep();
     check_scratch();
     check_bad_free();
+    check_carver();
     if (g_failed || !balanced()) { std::printf("%d checks failed\n", g_failed); return 1; }
     std::printf("ok\n");
     return 0;
