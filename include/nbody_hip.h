@@ -1245,6 +1245,17 @@ int nbody_debug_let_set_balance(NbodyHandle* h, int by_work);
 /* the key-range bounds the next classification will use ([world_size + 1]; redrawn every step at the world's quantiles) */
 int nbody_debug_let_bounds(NbodyHandle* h, unsigned long long* out);
 int nbody_debug_let_set_prune(NbodyHandle* h, int prune);
+/* The node array this rank's last force pass (a step's, or nbody_update_forces') walked, in the walk's order: its slice and
+ * the imports in the order of their global pre-order indices.  Per held node: com_mass {x, y, z, m}; width; link = the
+ * position in this array the walk goes to when it accepts the node or passes it by (a leaf's is its own position + 1; the
+ * array's length ends the walk); global_index = its index in the world's pre-order node array; leaf = 1 for a body's leaf;
+ * origin = 0 a private node of this rank's slice, 1 a private node imported from a partner, 2 a spanning cell of this
+ * rank's slice, 3 an imported spanning cell.  Arrays hold `cap` nodes (com_mass: 4 floats a node) and may each be NULL;
+ * all NULL counts only; fewer than *n_nodes: NBODY_ERR_CAPACITY.  NBODY_ERR_INVALID on handles that are not
+ * NBODY_SHARD_SPATIAL and before the first force pass after an upload.  Reads only: the state, nbody_stats, nbody_let_stats
+ * and the bits of later steps are what they would be without the call. */
+int nbody_debug_let_export_held(NbodyHandle* h, float* com_mass, float* width, int32_t* link, int32_t* global_index, int32_t* leaf,
+                                int32_t* origin, size_t cap, size_t* n_nodes);
 
 /* ---- host-only entry (no device needed): the plan of the symmetric scheme across shards ---------- */
 /* Which pairs between shards `rank` evaluates (rows {shard, first chunk, last chunk, first own set,

@@ -86,7 +86,7 @@ DECLARED_SYMBOLS = [
     "nbody_set_settings_f64", "nbody_get_settings_f64", "nbody_set_bounds_f64", "nbody_step_by_f64", "nbody_elapsed_f64",
     "nbody_tree_export_f64", "nbody_ic_plummer_f64", "nbody_ic_disc_f64",
     "nbody_download_ids", "nbody_let_stats", "nbody_debug_let_phase", "nbody_debug_let_exchange", "nbody_debug_let_set_prune",
-    "nbody_debug_let_bounds", "nbody_debug_let_set_balance",
+    "nbody_debug_let_bounds", "nbody_debug_let_set_balance", "nbody_debug_let_export_held",
     "nbody_comm_local_id", "nbody_comm_transport", "nbody_host_exchange_layout",
     "nbody_set_tuning", "nbody_get_tuning", "nbody_is_tuning_build", "nbody_tree_export_cells", "nbody_host_launch_plan",
     "nbody_get_config", "nbody_potentials", "nbody_energy_world", "nbody_field_at", "nbody_tidal_at",
@@ -284,6 +284,7 @@ _sig("nbody_debug_let_exchange", _i, _H, _H, _i)
 _sig("nbody_debug_let_set_prune", _i, _H, _i)
 _sig("nbody_debug_let_bounds", _i, _H, C.c_void_p)
 _sig("nbody_debug_let_set_balance", _i, _H, _i)
+_sig("nbody_debug_let_export_held", _i, _H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
 _sig("nbody_host_exchange_layout", _i, C.c_void_p, _i, _i, C.c_longlong, _i, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_sz))
 _sig("nbody_host_launch_plan", _i, _sz, _f, _i, C.POINTER(_i))
 _sig("nbody_tracers_upload", _i, _H, C.c_void_p, _sz, _sz, _sz)
@@ -1196,6 +1197,20 @@ class Simulation:
     def set_balance(self, by_work: bool):
         """NBODY_SHARD_SPATIAL: redraw the bounds at the quantiles of the last walk's visit counts (default) or of the body count."""
         self._check(lib.nbody_debug_let_set_balance(self._h, int(bool(by_work))))
+
+    def let_held(self) -> dict:
+        """NBODY_SHARD_SPATIAL test hook (nbody_debug_let_export_held): the node array this rank's last force pass walked, in the
+        walk's order.  `com_mass` [m, 4] f32, `width` [m] f32, `skip` [m] i32 (positions in this array: what oracle.bh_walk_list
+        follows), `global_index` [m] i32, `leaf` [m] bool, `origin` [m] i32 (0 slice, 1 import, 2 own spanning cell, 3 imported
+        spanning cell)."""
+        n = C.c_size_t(0)
+        self._check(lib.nbody_debug_let_export_held(self._h, None, None, None, None, None, None, 0, C.byref(n)))
+        m = n.value
+        com, width = np.zeros((m, 4), np.float32), np.zeros(m, np.float32)
+        skip, gi, leaf, origin = (np.zeros(m, np.int32) for _ in range(4))
+        self._check(lib.nbody_debug_let_export_held(self._h, com.ctypes.data, width.ctypes.data, skip.ctypes.data, gi.ctypes.data,
+                                                    leaf.ctypes.data, origin.ctypes.data, m, C.byref(n)))
+        return dict(com_mass=com, width=width, skip=skip, global_index=gi, leaf=leaf.astype(bool), origin=origin)
 
     def set_prune(self, on: bool):
         self._check(lib.nbody_debug_let_set_prune(self._h, int(bool(on))))

@@ -89,6 +89,9 @@ void launch_assemble(hipStream_t s, const float4* slice, int local_cap, const Le
                      const int* offsets, const int* top_index, const float4* top_nodes, int G, int me, void* layout, int* split, float4* held,
                      int n_split, int* seg_first /* n_split > 1: [n_split + 1] where the walk's segments start (global cuts) */);
 size_t layout_bytes();
+// what `layout` holds after launch_assemble: list q of the staged imports starts at record in_at[q] and lands at position
+// base[q] of the held array; the slice lands at own_base, n_own nodes long; total = nodes held
+struct HaloLayout { int in_at[kMaxRanks], base[kMaxRanks], own_base, n_own, total, pad; };
 
 }  // namespace let
 }  // namespace nbody

@@ -603,7 +603,6 @@ __global__ __launch_bounds__(kPackThreads) void k_let_pack(const float4* __restr
 // A link to global index t becomes the number of held nodes with a smaller index: exact when t is held -- and a node a
 // body can get to IS held (it is a child of a cell the body opened) -- and the next held node otherwise (a link nobody
 // follows).  A leaf's link is "the next node", which that rule keeps (the DIRECT walk tells leaves by it).
-struct HaloLayout { int in_at[kMaxRanks], base[kMaxRanks], own_base, n_own, total, pad; };
 __global__ void k_let_layout(const int* __restrict__ in_n, const int* __restrict__ info, int G, int me, HaloLayout* __restrict__ lay, int* __restrict__ split) {
     if (threadIdx.x != 0) return;
     int at = 0, pos = 0;

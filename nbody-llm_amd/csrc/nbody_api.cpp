@@ -1327,6 +1327,15 @@ int nbody_debug_let_exchange(NbodyHandle* h, NbodyHandle* peer, int which) {
 
 int nbody_debug_let_set_prune(NbodyHandle* h, int prune);   // (nbody_let.cpp owns the state)
 
+int nbody_debug_let_export_held(NbodyHandle* h, float* com_mass, float* width, int32_t* link, int32_t* global_index, int32_t* leaf,
+                                int32_t* origin, size_t cap, size_t* n_nodes) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (!h->let) return fail(h, NBODY_ERR_INVALID, "nbody_debug_let_export_held: not an NBODY_SHARD_SPATIAL handle");
+    int rc = use_device(h);
+    if (rc) return rc;
+    return nbody::let::export_held(h, com_mass, width, link, global_index, leaf, origin, cap, n_nodes);
+}
+
 int nbody_local_range(const NbodyHandle* h, size_t* first, size_t* count) {
     if (!h) return NBODY_ERR_INVALID;
     if (first) *first = h->first_global;

@@ -25,6 +25,7 @@
 #include "nbody_pot.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 
@@ -105,6 +106,8 @@ struct State {
     TreeDevWork work;
     NbodyLetStats st{};
     std::vector<int> recv_n;      // emulation / production: records received from each rank this pass
+    bool held_valid = false;      // d_held is what the last finished pass walked (export_held); phase 0 and an upload end that
+    std::vector<int> held_in_n;   // [G] the import counts that pass was assembled with
     hipEvent_t ev[2][10] = {};    // begin/end of the five phases (nbody_set_profiling), two sets: a step's are read during the next
     bool ev_made = false, ev_live[2] = {false, false};
     int ev_set = 0;               // the set the pass under way records into
@@ -224,6 +227,7 @@ int phase0(NbodyHandle* h, State& s, float dt, bool drift) {
     auto& b = nbody32::bodies(h);
     Shard& sh = b.sh;
     PhaseTimer timer(h, s, 0);
+    s.held_valid = false;
     int rc = ensure_node_buffers(h, s);
     if (rc) return rc;
     if (drift) {
@@ -303,6 +307,8 @@ int phase4(NbodyHandle* h, State& s, float dt, bool kick, bool potentials = fals
         HIP_TRY(h, hipMemcpyAsync(s.d_in_n, s.h_in_pin, sizeof(int) * size_t(s.G), hipMemcpyHostToDevice, h->stream));
         launch_assemble(h->stream, s.d_slice, s.local_cap, s.d_let_recv, int(staged_upper), s.d_in_n, s.d_tree_info, s.d_offsets, s.d_top_index,
                         s.d_top_nodes, s.G, s.me, s.d_layout, s.d_split, s.d_held, K, s.d_seg_first);
+        s.held_in_n = s.recv_n;
+        s.held_valid = true;
     }
     TreeDev td;
     td.nodes = s.d_held; td.n_nodes = int(std::min<size_t>(s.held_cap, 0x7fffffff));
@@ -457,6 +463,7 @@ int upload(NbodyHandle* h, const void* aos, size_t n, size_t stride) {
     HIP_TRY(h, hipMemsetAsync(s.d_send_count, 0, sizeof(int) * s.G, h->stream));
     HIP_TRY(h, hipMemsetAsync(s.d_flags, 0, 4 * sizeof(int), h->stream));
     s.have_pred = false;   // (the first step after an upload learns the migrant counts the slow way)
+    s.held_valid = false;
     b.n_local = m;
     b.seg_count_host[0] = int(m);
     b.h_counts[0] = int(m);
@@ -955,6 +962,57 @@ int potential_pass(NbodyHandle* h) {
     auto& b = nbody32::bodies(h);
     int rc = pot::begin(h, size_t(b.sh.seg_cap));
     return rc ? rc : pass(h, 0.f, false, true);
+}
+
+// ---- test hook: the node array the last pass walked, as the walk read it (include/nbody_hip.h nbody_debug_let_export_held).
+// Device-to-host copies and host arithmetic only; nothing of the state, the counters or the statistics is written.
+int export_held(NbodyHandle* h, float* com_mass, float* width, int32_t* link, int32_t* global_index, int32_t* leaf, int32_t* origin, size_t cap,
+                size_t* n_out) {
+    State& s = *h->let;
+    if (!s.held_valid) return fail(h, NBODY_ERR_INVALID, "nbody_debug_let_export_held: no force pass has finished on this handle since its last upload");
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HaloLayout lay;
+    HIP_TRY(h, hipMemcpy(&lay, s.d_layout, sizeof(HaloLayout), hipMemcpyDeviceToHost));
+    const size_t total = size_t(std::max(0, lay.total)), n_own = size_t(std::max(0, lay.n_own));
+    if (total > s.held_cap || n_own > total) return fail(h, NBODY_ERR_INVALID, "nbody_debug_let_export_held: the held array's layout is inconsistent");
+    if (n_out) *n_out = total;
+    if (!com_mass && !width && !link && !global_index && !leaf && !origin) return NBODY_OK;
+    if (total > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_debug_let_export_held: buffer too small");
+    const size_t n_in = total - n_own;
+    if (n_in > s.let_recv_cap) return fail(h, NBODY_ERR_INVALID, "nbody_debug_let_export_held: the held array's layout is inconsistent");
+    std::vector<float4> held(2 * total);
+    std::vector<LetRecord> staged(n_in);
+    std::vector<int> offsets(size_t(s.G) + 1), top_index(size_t(s.G) * kLevels);
+    if (total) HIP_TRY(h, hipMemcpy(held.data(), s.d_held, held.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    if (n_in) HIP_TRY(h, hipMemcpy(staged.data(), s.d_let_recv, n_in * sizeof(LetRecord), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(offsets.data(), s.d_offsets, offsets.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(top_index.data(), s.d_top_index, top_index.size() * sizeof(int), hipMemcpyDeviceToHost));
+    auto bits = [](float f) { int32_t i; std::memcpy(&i, &f, 4); return i; };
+    std::vector<int32_t> gi(total, -1), from(total, 0);
+    for (size_t k = 0; k < n_own; ++k) gi[size_t(lay.own_base) + k] = int32_t(offsets[size_t(s.me)] + int(k));
+    for (int q = 0; q < s.G; ++q) {
+        if (q == s.me) continue;
+        const size_t cnt = size_t(std::max(0, s.held_in_n[size_t(q)]));
+        if (size_t(lay.in_at[q]) + cnt > n_in || size_t(lay.base[q]) + cnt > total)
+            return fail(h, NBODY_ERR_INVALID, "nbody_debug_let_export_held: the held array's layout is inconsistent");
+        for (size_t k = 0; k < cnt; ++k) {
+            gi[size_t(lay.base[q]) + k] = bits(staged[size_t(lay.in_at[q]) + k].b.z);
+            from[size_t(lay.base[q]) + k] = 1;
+        }
+    }
+    std::vector<int> tops;   // the spanning cells' global indices, ascending
+    for (int t : top_index) if (t >= 0) tops.push_back(t);
+    std::sort(tops.begin(), tops.end());
+    for (size_t p = 0; p < total; ++p) {
+        const float4 A = held[2 * p], B = held[2 * p + 1];
+        if (com_mass) { com_mass[4 * p] = A.x; com_mass[4 * p + 1] = A.y; com_mass[4 * p + 2] = A.z; com_mass[4 * p + 3] = A.w; }
+        if (width) width[p] = std::sqrt(B.x);   // exact: the record holds the rounded square of the width
+        if (link) link[p] = bits(B.y);
+        if (global_index) global_index[p] = gi[p];
+        if (leaf) leaf[p] = bits(B.w) >= 0 ? 1 : 0;
+        if (origin) origin[p] = from[p] + (std::binary_search(tops.begin(), tops.end(), int(gi[p])) ? 2 : 0);
+    }
+    return NBODY_OK;
 }
 
 // ---- one-process emulation: phases and exchanges driven from outside

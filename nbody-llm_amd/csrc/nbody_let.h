@@ -28,6 +28,9 @@ int check_flags(NbodyHandle* h);            // turns the device's sticky flags i
 // one-process emulation of G ranks (tests): the phases between the exchanges, and the exchanges as copies
 int debug_phase(NbodyHandle* h, int phase, float dt);
 int debug_exchange(NbodyHandle* h, NbodyHandle* peer, int which);
+// the node array the last pass walked, in the walk's order (nbody_debug_let_export_held): copies only, nothing is written
+int export_held(NbodyHandle* h, float* com_mass, float* width, int32_t* link, int32_t* global_index, int32_t* leaf, int32_t* origin, size_t cap,
+                size_t* n_out);
 
 }  // namespace let
 }  // namespace nbody

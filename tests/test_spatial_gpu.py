@@ -6,6 +6,7 @@ over the array of the nodes a rank holds (its slice and the imports, in global-i
 import numpy as np
 import pytest
 
+from let_list import check_counts, replay
 
 pytestmark = pytest.mark.gpu
 BOX = ((0.0, 0.0, 0.0), 64.0)
@@ -142,6 +143,9 @@ def test_spatial_forces_equal_the_single_shard_device_tree(gpu, orc, G, n, leaf,
     rec, idx = nb.spatial_gather(sims, n)
     stats = [s.stats() for s in sims]
     ls = [s.let_stats() for s in sims]
+    # every rank's accepted and visited totals are EXACTLY those of its own node list replayed for its own bodies (let_list)
+    refs = [replay(orc, s.let_held(), s.get_points()["position"], st.theta2, st.g, st.g_soft, 1 if leaf == "direct" else 0) for s in sims]
+    check_counts(stats, refs, f"G={G} n={n} {leaf} prune={prune}")
     close(sims)
     with nb.Simulation(ics, *BOX, method=nb.BARNES_HUT, math_mode=nb.FAST, tree_build=nb.TREE_DEVICE, leaf_mode=lm) as one:
         one.settings = st
