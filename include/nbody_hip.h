@@ -1101,6 +1101,73 @@ int nbody_deposit(NbodyHandle* h, const NbodyGridSpec* spec, double* grid /* [nx
 int nbody_host_deposit(const double* xyz /* [n][3] */, const double* q /* [n] */, size_t n, const NbodyGridSpec* spec,
                        double* grid, size_t cap, uint64_t counts[4]);
 int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]);
+/* ---- grid sample: a grid read back at the bodies or at points, values and gradients (no reference counterpart) ------------
+ * The transpose of nbody_deposit: the same NGP / CIC / TSC weights, the cells READ instead of added to.  With it a
+ * particle-mesh step can be finished -- deposit the mass, solve Poisson's equation on the grid with any FFT, sample the
+ * potential's gradient at the bodies -- and a force found that way conserves momentum only when both directions use the same
+ * assignment, which is why the call shares deposit_grid.h's stencil.  Also: the grid density at each body, a tabulated
+ * background potential at tracer positions, a velocity field along a path.
+ *   nbody_grid_sample samples at the handle's bodies: rows in nbody_download's order, *n_out = the live count, as nbody_knn
+ * reports them; cap = the rows out (and cls) hold; cap smaller than the live count: NBODY_ERR_CAPACITY with *n_out set and
+ * nothing written.  nbody_grid_sample_at samples at n_points caller points {x, y, z}: the handle lends its stream and its
+ * memory only, as for nbody_external_at (it may hold no body).  Both are READ-ONLY calls under the contract of nbody_deposit;
+ * the only thing a call leaves behind is the record nbody_grid_sample_stats reads.  nbody_host_grid_sample is the same
+ * arithmetic on the host (no device needed).  The quantity field of the spec is ignored by all three.
+ *   grid: [fields][nx][ny][nz] row-major doubles, fields in 1 .. NBODY_SAMPLE_MAX_FIELDS, fields nx ny nz <=
+ * NBODY_DEPOSIT_MAX_CELLS.  out: [n][fields] (NBODY_SAMPLE_VALUE) or [n][3] (the gradients, which take one field).  cls
+ * (may be NULL): each row's class; counts (may be NULL) = {inside, partial, outside, skipped}, which add up to n.
+ *   THE ARITHMETIC (csrc/sample_grid.h, restated in tests/sample_ref.py), all f64, every operation rounded on its own, nothing
+ * contracted into an FMA; an NBODY_F32 handle's positions are widened exactly first.  A gather has no addition-order problem:
+ * THE SAME INPUT GIVES THE SAME BITS on the device, on the host and in the restatement, whatever the launch shape and the
+ * sample_sort and sample_pregrad knobs are.
+ *     the stencil of a point is the deposit's for q = 0.0: the skip rule, the weights, the ignored axis, the wrap
+ *     VALUE, field f:   s = +0.0; for a, then b, then c innermost over the stencil's cells, a term whose cell is dropped
+ *                       skipped:  w = (wx[a] wy[b]) wz[c];  s = s + w G_f[cell];  out[i][f] = s.  IEEE as it stands: a zero
+ *                       weight times an infinite cell is NaN.
+ *     GRADIENT, component k at stencil cell i:
+ *         order 2:  D = (G[i + e_k] - G[i - e_k]) / (2.0 spacing)
+ *         order 4:  D = (8.0 (G[i + e_k] - G[i - e_k]) - (G[i + 2 e_k] - G[i - 2 e_k])) / (12.0 spacing)
+ *       the denominator is formed once per call; the neighbours' indices wrap when periodic (an axis of 1 or 2 cells then
+ *       gives exact zeros); otherwise a term is dropped FOR THAT COMPONENT when a cell its difference reads is off the grid.
+ *       out[i][k] = the sum of w D in VALUE's order; along project_axis it is +0.0 and nothing is read.  The result is +grad:
+ *       the caller negates it for an acceleration.
+ *     SKIPPED: the stencil refuses the point (a coordinate that is not finite, !(|u| < 2^31)); OUTSIDE: no stencil cell is on
+ *     the grid; both give +0.0 everywhere.  INSIDE: every read of every component landed -- for a gradient that is the
+ *     stencil widened by 1 or 2 cells on every axis in use; always when periodic.  PARTIAL: everything else.
+ *   n == 0 (no body, no point): NBODY_OK, counts zeroed, nothing else written.
+ *   nbody_grid_sample_stats: out = {1 once a call on this handle reached the device else 0, the plan the last such call USED as
+ * sample_sort | sample_pregrad << 1, the grid reads k_sample issued, 0}.  A DIAGNOSTIC AID for tools/sample_bench.py and the
+ * tests of the plans, NOT A STABLE CONTRACT.
+ *   HOW (csrc/kernels_sample.hip): one copy of the grid to the device; the bodies' positions widened into the call's scratch
+ * (the points: uploaded); sample_sort = 1 (default): the home-cell keys and the stable rocPRIM sort of the deposit, so that
+ * neighbouring lanes gather from neighbouring cells; k_sample -- one lane per point of that order, the up to 27 offsets
+ * unrolled with constant indices, the grid read through const __restrict__ vector loads, each lane writing its own row, the
+ * counts from ballots and one integer atomic per wave and class; no floating-point atomics, no LDS, no lane waits for another.
+ * In the gradient ops the stencil cells along the differentiated axis share their reads (TSC order 2: 5 cells, not 6; order
+ * 4: 7, not 12).  sample_pregrad = 1 (default 0): k_grid_diff first writes the three difference grids for all cells and
+ * k_sample reads them as three fields, recomputing from the indices which terms are dropped; it is treated as 0 when 3 nx ny nz
+ * > NBODY_DEPOSIT_MAX_CELLS, and the stats report the plan used.  Nothing chooses a plan for the caller.  nbody_grid_sample_at
+ * works through its points in batches of 2^22 after the one copy of the grid.
+ *   NOT TIMED ON AN MI355X beyond the single run of tools/sample_bench.py that DESIGN 3.25 records.  Nothing asserts or
+ * promises a time.
+ *   Accepted and refused on the handles of nbody_deposit.  Refused with NBODY_ERR_INVALID (nbody_last_error names the call):
+ * whatever nbody_host_deposit refuses in a spec; fields outside 1 .. 4; fields != 1 with a gradient; an unknown op; fields nx
+ * ny nz > NBODY_DEPOSIT_MAX_CELLS; grid NULL; out NULL or xyz NULL with n > 0; n_points > 2^31 - 1; handles of a multi-rank
+ * world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
+ *   OUT OF SCOPE: a grid component of nbody_set_external_field (a tabulated background in the kick: the natural follow-up, but
+ * it touches the step kernels); a device-resident grid kept between calls; the Poisson solve itself; PCS stencils;
+ * interlacing and deconvolution; multi-rank handles. */
+#define NBODY_SAMPLE_VALUE 0      /* the grid's value                                   out [n][fields] */
+#define NBODY_SAMPLE_GRADIENT2 1  /* central differences of order 2, fields must be 1   out [n][3]      */
+#define NBODY_SAMPLE_GRADIENT4 2  /* central differences of order 4, fields must be 1   out [n][3]      */
+#define NBODY_SAMPLE_MAX_FIELDS 4
+int nbody_grid_sample(NbodyHandle* h, const NbodyGridSpec* spec, const double* grid /* [fields][nx][ny][nz] */, int fields, int op,
+                      double* out, uint8_t* cls /* [n], may be NULL */, size_t cap, size_t* n_out, uint64_t counts[4] /* may be NULL */);
+int nbody_grid_sample_at(NbodyHandle* h, const NbodyGridSpec* spec, const double* grid, int fields, int op,
+                         const double* xyz /* [n_points][3] */, size_t n_points, double* out, uint8_t* cls, uint64_t counts[4]);
+int nbody_host_grid_sample(const double* xyz /* [n][3] */, size_t n, const NbodyGridSpec* spec, const double* grid, int fields, int op,
+                           double* out, uint8_t* cls, uint64_t counts[4]);
+int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
  * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
  * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
@@ -1161,7 +1228,8 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
  * bf_fast_variant, sym_wpb, sym_rounds, sym_reduce_split, sym_opp_rot, cross_slots, cross_ipt, cross_wpb, bh_walk_split, bh_walk_order,
  * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8),
  * pair_hist_combine, pair_hist_flush (nbody_pair_counts and nbody_pair_counts_at: they change no result), deposit_sort, deposit_combine,
- * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result), sample_sort, sample_pregrad (nbody_grid_sample and
+ * nbody_grid_sample_at: the plan, defaults 1, 0; they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

@@ -71,6 +71,9 @@ DEPOSIT_NGP, DEPOSIT_CIC, DEPOSIT_TSC = 0, 1, 2   # nbody_deposit: the assignmen
 # nbody_deposit: the quantity q of a body: m | m vx | m vy | m vz | m ((vx vx + vy vy) + vz vz) | 1.0
 DEPOSIT_MASS, DEPOSIT_MOMENTUM_X, DEPOSIT_MOMENTUM_Y, DEPOSIT_MOMENTUM_Z, DEPOSIT_MV2, DEPOSIT_NUMBER = 0, 1, 2, 3, 4, 5
 DEPOSIT_MAX_CELLS = 1 << 27   # nbody_deposit: the most cells of a grid (NBODY_DEPOSIT_MAX_CELLS)
+# nbody_grid_sample: the grid's value [n][fields] | its gradient by central differences of order 2 | of order 4 [n][3]
+SAMPLE_VALUE, SAMPLE_GRADIENT2, SAMPLE_GRADIENT4 = 0, 1, 2
+SAMPLE_MAX_FIELDS = 4   # nbody_grid_sample: the most fields of a grid (NBODY_SAMPLE_MAX_FIELDS)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -104,6 +107,7 @@ DECLARED_SYMBOLS = [
     "nbody_knn", "nbody_knn_density", "nbody_knn_density_center",
     "nbody_pair_counts", "nbody_pair_counts_at",
     "nbody_deposit", "nbody_host_deposit", "nbody_deposit_stats",
+    "nbody_grid_sample", "nbody_grid_sample_at", "nbody_host_grid_sample", "nbody_grid_sample_stats",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -320,6 +324,10 @@ _sig("nbody_pair_counts_at", _i, _H, C.c_void_p, _sz, C.c_void_p, _i, C.c_void_p
 _sig("nbody_deposit", _i, _H, C.POINTER(GridSpec), C.c_void_p, _sz, C.c_void_p)
 _sig("nbody_host_deposit", _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(GridSpec), C.c_void_p, _sz, C.c_void_p)
 _sig("nbody_deposit_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_grid_sample", _i, _H, C.POINTER(GridSpec), C.c_void_p, _i, _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p)
+_sig("nbody_grid_sample_at", _i, _H, C.POINTER(GridSpec), C.c_void_p, _i, _i, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("nbody_host_grid_sample", _i, C.c_void_p, _sz, C.POINTER(GridSpec), C.c_void_p, _i, _i, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("nbody_grid_sample_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -441,6 +449,35 @@ def host_deposit(points, q, origin, spacing, dims, scheme=DEPOSIT_CIC, periodic=
     if rc:
         raise NbodyError(rc, "nbody_host_deposit: the spec is not valid (include/nbody_hip.h lists what is refused)")
     return grid, counts
+
+
+def _sample_grid(grid, origin, spacing, scheme, op, periodic, project_axis):
+    """(grid as contiguous f64 [fields][nx][ny][nz], fields, its GridSpec, the doubles of a row of out) of a grid_sample call"""
+    g = np.ascontiguousarray(grid, np.float64)
+    if g.ndim == 3:
+        g = g[None]
+    if g.ndim != 4:
+        raise ValueError("grid_sample: grid must be [nx, ny, nz] or [fields, nx, ny, nz]")
+    fields = int(g.shape[0])
+    spec = grid_spec(origin, spacing, g.shape[1:], scheme, DEPOSIT_MASS, periodic, project_axis)
+    return g, fields, spec, fields if int(op) == SAMPLE_VALUE else 3
+
+
+def host_grid_sample(points, grid, origin, spacing, scheme=DEPOSIT_CIC, op=SAMPLE_VALUE, periodic=False, project_axis=-1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(out [n, fields] or [n, 3] f64, cls [n] uint8, counts [4] uint64 = inside, partial, outside, skipped): the grid ([nx, ny,
+    nz] or [fields, nx, ny, nz]) read back at points [n][3] with the deposit's weights -- nbody_grid_sample's arithmetic on the
+    host (nbody_host_grid_sample; no device needed)."""
+    xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    g, fields, spec, width = _sample_grid(grid, origin, spacing, scheme, op, periodic, project_axis)
+    n = len(xyz)
+    out = np.zeros((n, width), np.float64)
+    cls = np.zeros(n, np.uint8)
+    counts = np.zeros(4, np.uint64)
+    rc = lib.nbody_host_grid_sample(xyz.ctypes.data if n else None, n, C.byref(spec), g.ctypes.data if g.size else None, fields, int(op),
+                                    out.ctypes.data if out.size else None, cls.ctypes.data if n else None, counts.ctypes.data)
+    if rc:
+        raise NbodyError(rc, "nbody_host_grid_sample: the call is not valid (include/nbody_hip.h lists what is refused)")
+    return out, cls, counts
 
 
 def tidal_matrices(t6) -> np.ndarray:
@@ -915,6 +952,44 @@ class Simulation:
         deposit_lds << 2), its terms on the grid, the 64-bit atomics it sent to global memory} (nbody_deposit_stats)."""
         out = (C.c_uint64 * 4)()
         self._check(lib.nbody_deposit_stats(self._h, out))
+        return np.array(out[:], np.uint64)
+
+    # -- grid sample (nbody_grid_sample, nbody_grid_sample_at): a grid read back with the deposit's weights, read-only, on the device
+    def grid_sample(self, grid, origin, spacing, scheme=DEPOSIT_CIC, op=SAMPLE_VALUE, periodic=False, project_axis=-1,
+                    points=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(out [n, fields] or [n, 3] f64, cls [n] uint8, counts [4] uint64 = inside, partial, outside, skipped): the grid ([nx,
+        ny, nz] or [fields, nx, ny, nz], cells of edge `spacing` from the low corner `origin`) read back at the bodies, in
+        get_points() order, or at points [n][3], with the weights of DEPOSIT_NGP, DEPOSIT_CIC or DEPOSIT_TSC -- the transpose of
+        deposit().  SAMPLE_VALUE: the fields' values; SAMPLE_GRADIENT2 / SAMPLE_GRADIENT4: +grad of one field by central
+        differences of order 2 / 4.  The same input gives the same bits as host_grid_sample (nbody_grid_sample,
+        nbody_grid_sample_at)."""
+        g, fields, spec, width = _sample_grid(grid, origin, spacing, scheme, op, periodic, project_axis)
+        counts = np.zeros(4, np.uint64)
+        if points is not None:
+            xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+            n = len(xyz)
+            out = np.zeros((n, width), np.float64)
+            cls = np.zeros(n, np.uint8)
+            self._check(lib.nbody_grid_sample_at(self._h, C.byref(spec), g.ctypes.data if g.size else None, fields, int(op),
+                                                 xyz.ctypes.data if n else None, n, out.ctypes.data if out.size else None,
+                                                 cls.ctypes.data if n else None, counts.ctypes.data))
+            return out, cls, counts
+        # (sized from the capacity, not from nbody_count, which would refresh the host's view of the body count: potentials())
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        cap = max(int(cfg.capacity), 1)
+        out = np.zeros((cap, width), np.float64)
+        cls = np.zeros(cap, np.uint8)
+        n = C.c_size_t(0)
+        self._check(lib.nbody_grid_sample(self._h, C.byref(spec), g.ctypes.data if g.size else None, fields, int(op), out.ctypes.data,
+                                          cls.ctypes.data, cap, C.byref(n), counts.ctypes.data))
+        return out[: n.value], cls[: n.value], counts
+
+    def grid_sample_stats(self) -> np.ndarray:
+        """[4] uint64: {1 once a grid sample reached the device, the plan the last one used (sample_sort | sample_pregrad << 1),
+        the grid reads its sample kernel issued, 0} (nbody_grid_sample_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_grid_sample_stats(self._h, out))
         return np.array(out[:], np.uint64)
 
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits

@@ -45,6 +45,8 @@ struct Tuning {
     int deposit_sort = 1;       // nbody_deposit: 1 the rows ordered by home cell before k_deposit, 0 in row order (kernels_deposit.h Plan)
     int deposit_combine = 1;    // k_deposit: 1 a wave's runs of equal cells are summed by a segmented scan and added once, 0 every lane adds its own term
     int deposit_lds = 1;        // k_deposit: 1 additions go through the block's tagged LDS table of 1 024 int64 slots, 0 straight to the cells
+    int sample_sort = 1;        // nbody_grid_sample(_at): 1 the points visited in home-cell order, 0 in row order (kernels_sample.h Plan)
+    int sample_pregrad = 0;     // the gradient ops: 1 k_grid_diff writes the three difference grids first and k_sample reads them as three fields, 0 differences on the fly
     // the following select code that only the tuning build carries (make -C csrc tuning: -DNBODY_TUNING); the release
     // library refuses any value but the default
     int bh_walk_variant = 0;    // 1 wave-cooperative, 2 two lanes per body, 3 hot records in LDS, 4 cooperative window, 5 cooperative block walk  [NBODY_BH_VARIANT]

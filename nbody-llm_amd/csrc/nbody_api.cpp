@@ -15,6 +15,7 @@
 #include "nbody_knn.h"
 #include "nbody_paircount.h"
 #include "nbody_deposit.h"
+#include "nbody_sample.h"
 #include "nbody_cells.h"
 
 #include <algorithm>
@@ -717,6 +718,49 @@ int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]) {
     return NBODY_OK;
 }
 
+// ---- grid sample (nbody_sample.cpp): two read-only calls under the census's contract, and their host twin
+namespace {
+int sample_enter(NbodyHandle* h, const char* call, const NbodyGridSpec* spec, const double* grid, int fields, int op) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    const std::string why = nbody::sample::call_refusal(spec, grid, fields, op);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return NBODY_OK;
+}
+}  // namespace
+
+int nbody_grid_sample(NbodyHandle* h, const NbodyGridSpec* spec, const double* grid, int fields, int op, double* out, uint8_t* cls, size_t cap,
+                      size_t* n_out, uint64_t counts[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = sample_enter(h, "nbody_grid_sample", spec, grid, fields, op);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) { return nbody::sample::at_bodies(h, b.sh, b.n_local, *spec, grid, fields, op, out, cls, cap, n_out, counts); });
+}
+
+int nbody_grid_sample_at(NbodyHandle* h, const NbodyGridSpec* spec, const double* grid, int fields, int op, const double* xyz, size_t n_points,
+                         double* out, uint8_t* cls, uint64_t counts[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = sample_enter(h, "nbody_grid_sample_at", spec, grid, fields, op);
+    if (rc) return rc;
+    if (n_points > size_t(0x7fffffff)) return fail(h, NBODY_ERR_INVALID, "nbody_grid_sample_at: n_points must not exceed 2^31 - 1");
+    if (n_points && !xyz) return fail(h, NBODY_ERR_INVALID, "nbody_grid_sample_at: xyz is NULL");
+    if (n_points && !out) return fail(h, NBODY_ERR_INVALID, "nbody_grid_sample_at: out is NULL");
+    return nbody::sample::at_points(h, *spec, grid, fields, op, xyz, n_points, out, cls, counts);
+}
+
+int nbody_host_grid_sample(const double* xyz, size_t n, const NbodyGridSpec* spec, const double* grid, int fields, int op, double* out,
+                           uint8_t* cls, uint64_t counts[4]) {
+    return nbody::sample::host_entry(xyz, n, spec, grid, fields, op, out, cls, counts);
+}
+
+int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_grid_sample_stats: ") + why);
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_grid_sample_stats: out is NULL");
+    std::copy(h->sample_last, h->sample_last + 4, out);
+    return NBODY_OK;
+}
+
 // ---- pair search (nbody_cells.cpp): a setting of the handle that the eight fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
@@ -1246,6 +1290,7 @@ const Knob kKnobs[] = {
     {"pair_hist_combine", &nbody::Tuning::pair_hist_combine, false}, {"pair_hist_flush", &nbody::Tuning::pair_hist_flush, false},
     {"deposit_sort", &nbody::Tuning::deposit_sort, false}, {"deposit_combine", &nbody::Tuning::deposit_combine, false},
     {"deposit_lds", &nbody::Tuning::deposit_lds, false},
+    {"sample_sort", &nbody::Tuning::sample_sort, false}, {"sample_pregrad", &nbody::Tuning::sample_pregrad, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},

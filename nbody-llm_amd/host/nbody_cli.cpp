@@ -34,7 +34,9 @@
 //     lin: edges[b] = LO + (HI - LO) * (double(b) / double(BINS))      log: edges[b] = LO * pow(HI / LO, double(b) / double(BINS))
 // and printed with 17 significant digits, which name each double exactly.  --deposit ngp|cic|tsc:N:HALF prints the mass of
 // the final state assigned to the N^3 cells of the cube [-HALF, HALF)^3 (nbody_deposit; spacing = (2 HALF) / N in f64): one
-// line with the four counts, one with the sum over the cells (in cell order) and the heaviest cell.
+// line with the four counts, one with the sum over the cells (in cell order) and the heaviest cell.  --sample value|grad2|grad4
+// (with --deposit only) reads that mass grid back at the bodies of the final state with the same spec (nbody_grid_sample): one
+// line with the four counts, then the first eight bodies' outputs with 17 significant digits.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -65,6 +67,7 @@ static void usage() {
                  "                 [--pair-counts LO:HI:BINS[:log|lin]]   (the pairs of the final state per bin of separation; log needs LO > 0)\n"
                  "                 [--knn K[:HINT]]   (every body's K nearest neighbours, 1 <= K <= 32: the median and largest K-th distance, the Casertano-Hut centre)\n"
                  "                 [--deposit ngp|cic|tsc:N:HALF]   (the mass of the final state on the N^3 cells of [-HALF, HALF)^3)\n"
+                 "                 [--sample value|grad2|grad4]   (with --deposit: that grid read back at the bodies, its value or its gradient)\n"
                  "                 [--pair-search all|cells]   (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
@@ -225,6 +228,24 @@ static void print_deposit(Sim& sim, const NbodyGridSpec& spec) {
     std::printf("Deposit sum %.17e max %.17e at %zu %zu %zu\n", sum, grid.empty() ? 0.0 : grid[top], top / (ny * nz), top / nz % ny, top % nz);
 }
 
+// the lines of --sample: the mass grid of --deposit read back at the bodies with the same spec (nbody_grid_sample)
+template <class Sim>
+static void print_sample(Sim& sim, const NbodyGridSpec& spec, int op) {
+    std::vector<double> grid, out;
+    std::vector<uint8_t> cls;
+    uint64_t counts[4] = {0, 0, 0, 0};
+    sim.deposit(spec, grid, counts);
+    sim.grid_sample(spec, grid, 1, op, out, cls, counts);
+    const size_t width = op == NBODY_SAMPLE_VALUE ? 1 : 3;
+    std::printf("Sample: op %d bodies %zu inside %llu partial %llu outside %llu skipped %llu\n", op, cls.size(), (unsigned long long)counts[0],
+                (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3]);
+    for (size_t i = 0; i < cls.size() && i < 8; ++i) {
+        std::printf("Sample body %zu class %d", i, int(cls[i]));
+        for (size_t k = 0; k < width; ++k) std::printf(" %.17e", out[i * width + k]);
+        std::printf("\n");
+    }
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
@@ -232,7 +253,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
                double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint,
-               const NbodyGridSpec* deposit_spec) {
+               const NbodyGridSpec* deposit_spec, int sample_op) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -304,6 +325,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (!pair_edges.empty()) print_pair_counts(*sim, pair_edges);
         if (knn_k > 0) print_knn(*sim, knn_k, knn_hint);
         if (deposit_spec) print_deposit(*sim, *deposit_spec);
+        if (deposit_spec && sample_op >= 0) print_sample(*sim, *deposit_spec, sample_op);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -352,6 +374,7 @@ int main(int argc, char** argv) {
     int knn_k = 0;
     NbodyGridSpec deposit_spec{};
     bool deposit = false;
+    int sample_op = -1;
     double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -458,6 +481,13 @@ int main(int argc, char** argv) {
             deposit_spec.project_axis = -1;
             deposit = true;
         }
+        else if (!std::strcmp(argv[i], "--sample")) {
+            const std::string arg = next();
+            if (arg == "value") sample_op = NBODY_SAMPLE_VALUE;
+            else if (arg == "grad2") sample_op = NBODY_SAMPLE_GRADIENT2;
+            else if (arg == "grad4") sample_op = NBODY_SAMPLE_GRADIENT4;
+            else { usage(); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -504,7 +534,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--fof-bound needs --fof\n");
         return 2;
     }
+    if (sample_op >= 0 && !deposit) {
+        std::fprintf(stderr, "--sample needs --deposit\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op);
 }

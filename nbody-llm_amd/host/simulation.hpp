@@ -422,6 +422,35 @@ public:
     static int host_deposit(const double* xyz, const double* q, size_t n, const NbodyGridSpec& spec, double* grid, size_t cap, uint64_t counts[4]) {
         return nbody_host_deposit(xyz, q, n, &spec, grid, cap, counts);
     }
+    // grid sample (nbody_grid_sample, nbody_grid_sample_at): grid = [fields][nx][ny][nz] read back with spec's NBODY_DEPOSIT_NGP /
+    // CIC / TSC weights (the transpose of deposit) at the bodies, in get_points() order, or at the n points xyz = {x, y, z}; op =
+    // NBODY_SAMPLE_VALUE (out [n][fields]) or NBODY_SAMPLE_GRADIENT2 / 4 (+grad of one field by central differences, out [n][3]);
+    // cls = each row's class, counts = {inside, partial, outside, skipped}; read-only, the handles deposit() takes.
+    // grid_sample_stats: {a call reached the device, the plan it used, grid reads of the sample kernel, 0}.  host_grid_sample:
+    // the same arithmetic on the host (nbody_host_grid_sample; no device)
+    void grid_sample(const NbodyGridSpec& spec, const std::vector<double>& grid, int fields, int op, std::vector<double>& out,
+                     std::vector<uint8_t>& cls, uint64_t counts[4]) {
+        const size_t width = op == NBODY_SAMPLE_VALUE ? size_t(fields > 0 ? fields : 0) : 3;
+        size_t n = 0;
+        check(nbody_count(h_, &n));
+        out.assign(n * width, 0.0);
+        cls.assign(n, 0);
+        check(nbody_grid_sample(h_, &spec, grid.data(), fields, op, out.data(), cls.data(), n, &n, counts));
+        out.resize(n * width);
+        cls.resize(n);
+    }
+    void grid_sample_at(const NbodyGridSpec& spec, const std::vector<double>& grid, int fields, int op, const std::vector<double>& xyz,
+                        std::vector<double>& out, std::vector<uint8_t>& cls, uint64_t counts[4]) {
+        const size_t n = xyz.size() / 3, width = op == NBODY_SAMPLE_VALUE ? size_t(fields > 0 ? fields : 0) : 3;
+        out.assign(n * width, 0.0);
+        cls.assign(n, 0);
+        check(nbody_grid_sample_at(h_, &spec, grid.data(), fields, op, xyz.data(), n, out.data(), cls.data(), counts));
+    }
+    void grid_sample_stats(uint64_t out[4]) { check(nbody_grid_sample_stats(h_, out)); }
+    static int host_grid_sample(const double* xyz, size_t n, const NbodyGridSpec& spec, const double* grid, int fields, int op, double* out,
+                                uint8_t* cls, uint64_t counts[4]) {
+        return nbody_host_grid_sample(xyz, n, &spec, grid, fields, op, out, cls, counts);
+    }
     // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs
     // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
