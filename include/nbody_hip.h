@@ -1103,7 +1103,7 @@ int nbody_host_deposit(const double* xyz /* [n][3] */, const double* q /* [n] */
 int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- grid sample: a grid read back at the bodies or at points, values and gradients (no reference counterpart) ------------
  * The transpose of nbody_deposit: the same NGP / CIC / TSC weights, the cells READ instead of added to.  With it a
- * particle-mesh step can be finished -- deposit the mass, solve Poisson's equation on the grid with any FFT, sample the
+ * particle-mesh step can be finished -- deposit the mass, solve Poisson's equation on the grid (nbody_grid_poisson below, or any FFT), sample the
  * potential's gradient at the bodies -- and a force found that way conserves momentum only when both directions use the same
  * assignment, which is why the call shares deposit_grid.h's stencil.  Also: the grid density at each body, a tabulated
  * background potential at tracer positions, a velocity field along a path.
@@ -1155,7 +1155,7 @@ int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]);
  * ny nz > NBODY_DEPOSIT_MAX_CELLS; grid NULL; out NULL or xyz NULL with n > 0; n_points > 2^31 - 1; handles of a multi-rank
  * world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
  *   OUT OF SCOPE: a grid component of nbody_set_external_field (a tabulated background in the kick: the natural follow-up, but
- * it touches the step kernels); a device-resident grid kept between calls; the Poisson solve itself; PCS stencils;
+ * it touches the step kernels); a device-resident grid kept between calls; PCS stencils;
  * interlacing and deconvolution; multi-rank handles. */
 #define NBODY_SAMPLE_VALUE 0      /* the grid's value                                   out [n][fields] */
 #define NBODY_SAMPLE_GRADIENT2 1  /* central differences of order 2, fields must be 1   out [n][3]      */
@@ -1168,6 +1168,86 @@ int nbody_grid_sample_at(NbodyHandle* h, const NbodyGridSpec* spec, const double
 int nbody_host_grid_sample(const double* xyz /* [n][3] */, size_t n, const NbodyGridSpec* spec, const double* grid, int fields, int op,
                            double* out, uint8_t* cls, uint64_t counts[4]);
 int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]);
+/* ---- grid Poisson: the potential of a mass grid by a hand-written f64 FFT (no reference counterpart) ----------------------
+ * What stands between nbody_deposit and nbody_grid_sample in a particle-mesh field: mass is what nbody_deposit returns with
+ * NBODY_DEPOSIT_MASS -- mass per cell, not density --, phi the potential at the cell centres; handed to nbody_grid_sample
+ * with NBODY_SAMPLE_GRADIENT2 or GRADIENT4 it gives +grad phi.  spec->periodic selects the boundary condition:
+ *   PERIODIC (periodic = 1): the Green's function of the continuous Laplacian (NBODY_POISSON_SPECTRAL) or of the 7-point one,
+ * the mate of NBODY_SAMPLE_GRADIENT2 (NBODY_POISSON_DIFF2); deconvolve = 0, 1 or 2 divides that many powers of the window of
+ * spec->scheme out.  The mean of the mass is removed; the mean of phi is zero.
+ *   ISOLATED (periodic = 0): Hockney-Eastwood zero padding -- phi[c] = -g sum_c' mass[c'] Kr(c - c') with Kr = 1 / sqrt(r^2 +
+ * soften^2) between cell centres and no self term when soften = 0 -- which a direct sum over the cells reproduces to rounding.
+ *   The spec is checked exactly as nbody_host_deposit checks it; in addition every dimension is a power of two.  origin and
+ * quantity are ignored, scheme matters only for deconvolve.  An axis of one cell is neither transformed nor padded, so
+ * project_axis grids are such grids.  mass and phi may be the same array.  cap = the doubles phi holds; cap < nx ny nz:
+ * NBODY_ERR_CAPACITY with phi untouched.
+ *   The handle lends its stream and its memory only, as for nbody_grid_sample_at (it may hold no body).  A READ-ONLY call
+ * under the contract of nbody_deposit: scratch goes through the handle's registry and is freed inside the call; it leaves no
+ * trace in state, stats, tracers or the bits of any later step; the one thing left behind is the record
+ * nbody_grid_poisson_stats reads.  nbody_host_grid_poisson is the same arithmetic on the host (no device needed, one thread).
+ *   THE ARITHMETIC (csrc/poisson_grid.h, restated in tests/poisson_ref.py), all f64, every operation rounded on its own, nothing
+ * contracted into an FMA.  Every output is a fixed expression tree of the inputs -- no sum is longer than a butterfly's two
+ * operands -- so THE SAME INPUT GIVES THE SAME BITS on the device, on the host and in the restatement, whatever the launch
+ * shape and the poisson_lds and poisson_tile knobs are.
+ *     the real grid becomes complex with imaginary parts +0.0.  Per axis of length L = 2^p: the bit-reversal permutation, then
+ *     stages s = 1 .. p of radix 2, decimation in time; the butterfly on (a, b) with w = T[j L / 2^s]:
+ *         t.re = w.re b.re - w.im b.im;  t.im = w.re b.im + w.im b.re;  a' = a + t;  b' = a - t     (no shortcut for any w)
+ *     axis order z, y, x, forward and inverse; the inverse uses (w.re, -w.im); one multiplication by 1 / points at the end.
+ *     T[k] = (cos(a), -sin(a)), a = (2 pi k) / L, is made ON THE HOST from std::cos and std::sin and uploaded -- the device
+ *     never evaluates a sine, a cosine or a pi --, with T[0] = (1, +0) and T[L / 4] = (+0, -1) written as constants;
+ *     nbody_host_poisson_twiddles returns the table of one length (a power of two in 2 .. 4096; else NBODY_ERR_INVALID).
+ *     PERIODIC: per axis of n cells, on the host, m = i <= n / 2 ? i : i - n:
+ *         SPECTRAL  k = (2 pi m) / (n spacing), K[i] = k k;      DIFF2  v = (2 sin((pi i) / n)) / spacing, K[i] = v v
+ *         deconvolve = d > 0:  a = (pi m) / n, s = sin(a) / a, D[i] = 1 / (s multiplied d (scheme + 1) times), D[0] = 1
+ *       an axis of one cell has K = 0 and D = 1.  c = -((4 pi g) / ((spacing spacing) spacing)), once.  Per mode
+ *         den = (Kx[i] + Ky[j]) + Kz[l];  f = den == 0 ? +0.0 : c / den;  d > 0: f = f ((Dx Dy) Dz);  phi^ = (f rho^.re, f rho^.im)
+ *       and phi[cell] = value.re (1 / points) + 0.0.
+ *     ISOLATED: every axis of more than one cell is padded to 2 n with +0.0.  On the padded grid Kr = 1 / sqrt(r2), r2 = ((dx dx
+ *       + dy dy) + dz dz) + soften soften, d_c = spacing m_c, m_c = i <= n_c ? i : 2 n_c - i (0 on an axis of one cell); at the
+ *       origin Kr = soften > 0 ? 1 / soften : +0.0.  sqrt and the division are IEEE on both sides.  Kr goes through the same
+ *       transform, each mode is the full complex product in the butterfly's form, and phi[cell] = (-g) (value.re (1 / points))
+ *       + 0.0 for the nx ny nz corner.  (The + 0.0: a zero result is +0.0, so an all-zero grid gives +0.0 everywhere.)
+ *   nbody_grid_poisson_stats: out = {1 once a call on this handle reached the device else 0, the plan the last such call USED as
+ * poisson_lds | lines per block of the strided passes << 1, the butterfly launches, the complex points transformed (points
+ * times the 3-D transforms: 2 periodic, 3 isolated)}.  A DIAGNOSTIC AID for tools/poisson_bench.py and the tests of the plans,
+ * NOT A STABLE CONTRACT: what the four words mean may change with the kernels.
+ *   HOW (csrc/kernels_poisson.hip): one copy of the grid up and one down.  k_poisson_load writes real to complex and pads;
+ * k_poisson_kernel fills Kr (isolated only); k_poisson_fft_lds (poisson_lds = 1, the default) -- a block holds whole lines of
+ * one axis in LDS, up to 4 096 complex points (64 KB, so one line of the longest axis always fits), reverses the bits on the
+ * way in, runs all p stages out of LDS with a barrier between stages and writes back; along the strided axes y and x it takes
+ * a tile of poisson_tile (default 16, 1 .. 64, rounded down to a power of two and to what fits) z-adjacent lines, so that
+ * global loads and stores stay contiguous along z; the LDS image is padded by one point in 16 and one in 256 against bank
+ * conflicts.  poisson_lds = 0: k_poisson_bitrev and one k_poisson_fft_stage launch per stage over global memory, the plain
+ * variant and the cross-check.  k_poisson_green (periodic) or k_poisson_mul (isolated), the inverse passes, k_poisson_store
+ * (the scale, the corner, -g).  No floating-point atomics.  Nothing chooses a plan for the caller.
+ *   COST: 16 bytes per padded point of scratch (32 isolated); every axis pass reads and writes every point once under the LDS
+ * plan and p times under the plain one.  NOT TIMED ON AN MI355X beyond the single run of tools/poisson_bench.py that DESIGN
+ * 3.26 records.  Nothing asserts or promises a time.
+ *   Accepted and refused on the handles of nbody_deposit.  Refused with NBODY_ERR_INVALID (nbody_last_error names the call):
+ * whatever nbody_host_deposit refuses in a spec; a dimension that is not a power of two; a padded axis longer than
+ * NBODY_POISSON_MAX_AXIS; padded points above NBODY_POISSON_MAX_POINTS; ps NULL; g or soften not finite; soften < 0; soften
+ * != 0, green or deconvolve set for the wrong boundary condition; an unknown green; deconvolve outside 0 .. 2; reserved words
+ * not 0; mass or phi NULL; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without
+ * touching a device.
+ *   OUT OF SCOPE: real-to-complex transforms (the call does twice the necessary work); axes longer than 4 096;
+ * non-power-of-two dimensions; a transformed kernel or a device grid kept between calls; fusing deposit, solve and sample
+ * without the host round trips; a 4th-order Green's function; interlacing; multi-rank handles; a PM term in the step kernels. */
+#define NBODY_POISSON_SPECTRAL 0   /* periodic: -k^2 of the continuous Laplacian            */
+#define NBODY_POISSON_DIFF2    1   /* periodic: the 7-point Laplacian, the mate of GRADIENT2 */
+#define NBODY_POISSON_MAX_AXIS   4096        /* transform length of an axis (after padding) */
+#define NBODY_POISSON_MAX_POINTS 134217728   /* 2^27 complex points (after padding)         */
+typedef struct NbodyPoissonSpec {
+    double  g;           /* gravitational constant, finite */
+    double  soften;      /* isolated only: epsilon >= 0, finite; must be 0 when periodic */
+    int32_t green;       /* periodic only: SPECTRAL | DIFF2; must be 0 when isolated */
+    int32_t deconvolve;  /* periodic only: 0, 1 or 2 powers of the spec's scheme window divided out */
+    int32_t reserved[2]; /* 0 */
+} NbodyPoissonSpec;
+int nbody_grid_poisson(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPoissonSpec* ps,
+                       const double* mass /* [nx][ny][nz] */, double* phi /* [nx][ny][nz] */, size_t cap);
+int nbody_host_grid_poisson(const NbodyGridSpec* spec, const NbodyPoissonSpec* ps, const double* mass, double* phi, size_t cap);
+int nbody_host_poisson_twiddles(int length, double* out /* [length/2][2] */);
+int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
  * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
  * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
@@ -1229,7 +1309,8 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
  * bh_reduce_split, tree_max_tie, bf64_min_bodies, bf64_ipt, bf64_rot, bf64_waves (f64 fast brute force; a Hermite handle's pair-jerk pass reads bf64_ipt as 4 unless it is 8),
  * pair_hist_combine, pair_hist_flush (nbody_pair_counts and nbody_pair_counts_at: they change no result), deposit_sort, deposit_combine,
  * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result), sample_sort, sample_pregrad (nbody_grid_sample and
- * nbody_grid_sample_at: the plan, defaults 1, 0; they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * nbody_grid_sample_at: the plan, defaults 1, 0; they change no result), poisson_lds, poisson_tile (nbody_grid_poisson: the plan,
+ * defaults 1, 16; they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

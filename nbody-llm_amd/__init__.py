@@ -74,6 +74,10 @@ DEPOSIT_MAX_CELLS = 1 << 27   # nbody_deposit: the most cells of a grid (NBODY_D
 # nbody_grid_sample: the grid's value [n][fields] | its gradient by central differences of order 2 | of order 4 [n][3]
 SAMPLE_VALUE, SAMPLE_GRADIENT2, SAMPLE_GRADIENT4 = 0, 1, 2
 SAMPLE_MAX_FIELDS = 4   # nbody_grid_sample: the most fields of a grid (NBODY_SAMPLE_MAX_FIELDS)
+# nbody_grid_poisson, periodic: -k^2 of the continuous Laplacian | the 7-point Laplacian, the mate of SAMPLE_GRADIENT2
+POISSON_SPECTRAL, POISSON_DIFF2 = 0, 1
+POISSON_MAX_AXIS = 4096        # nbody_grid_poisson: the longest transform length of an axis, after padding (NBODY_POISSON_MAX_AXIS)
+POISSON_MAX_POINTS = 1 << 27   # nbody_grid_poisson: the most complex points, after padding (NBODY_POISSON_MAX_POINTS)
 
 #: every symbol include/nbody_hip.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -108,6 +112,7 @@ DECLARED_SYMBOLS = [
     "nbody_pair_counts", "nbody_pair_counts_at",
     "nbody_deposit", "nbody_host_deposit", "nbody_deposit_stats",
     "nbody_grid_sample", "nbody_grid_sample_at", "nbody_host_grid_sample", "nbody_grid_sample_stats",
+    "nbody_grid_poisson", "nbody_host_grid_poisson", "nbody_host_poisson_twiddles", "nbody_grid_poisson_stats",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -137,6 +142,11 @@ def grid_spec(origin, spacing, dims, scheme=DEPOSIT_CIC, quantity=DEPOSIT_MASS, 
     o = [float(v) for v in origin]
     d = [int(v) for v in dims]
     return GridSpec((C.c_double * 3)(*o), float(spacing), (C.c_int32 * 3)(*d), int(scheme), int(quantity), int(bool(periodic)), int(project_axis), 0)
+
+
+class NbodyPoissonSpec(C.Structure):
+    """NbodyPoissonSpec (include/nbody_hip.h, "grid Poisson"): the constants of one nbody_grid_poisson call."""
+    _fields_ = [("g", C.c_double), ("soften", C.c_double), ("green", C.c_int32), ("deconvolve", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 class NbodyExternalComponent(C.Structure):
@@ -328,6 +338,10 @@ _sig("nbody_grid_sample", _i, _H, C.POINTER(GridSpec), C.c_void_p, _i, _i, C.c_v
 _sig("nbody_grid_sample_at", _i, _H, C.POINTER(GridSpec), C.c_void_p, _i, _i, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("nbody_host_grid_sample", _i, C.c_void_p, _sz, C.POINTER(GridSpec), C.c_void_p, _i, _i, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("nbody_grid_sample_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_grid_poisson", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPoissonSpec), C.c_void_p, C.c_void_p, _sz)
+_sig("nbody_host_grid_poisson", _i, C.POINTER(GridSpec), C.POINTER(NbodyPoissonSpec), C.c_void_p, C.c_void_p, _sz)
+_sig("nbody_host_poisson_twiddles", _i, _i, C.c_void_p)
+_sig("nbody_grid_poisson_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -478,6 +492,38 @@ def host_grid_sample(points, grid, origin, spacing, scheme=DEPOSIT_CIC, op=SAMPL
     if rc:
         raise NbodyError(rc, "nbody_host_grid_sample: the call is not valid (include/nbody_hip.h lists what is refused)")
     return out, cls, counts
+
+
+def _poisson_call(mass, spacing, g, periodic, green, soften, deconvolve, scheme):
+    """(mass as contiguous f64 [nx][ny][nz], its GridSpec, the NbodyPoissonSpec) of a grid_poisson call"""
+    m = np.ascontiguousarray(mass, np.float64)
+    if m.ndim != 3:
+        raise ValueError("grid_poisson: mass must be [nx, ny, nz]")
+    spec = grid_spec((0.0, 0.0, 0.0), spacing, m.shape, scheme, DEPOSIT_MASS, periodic, -1)
+    ps = NbodyPoissonSpec(float(g), float(soften), int(green), int(deconvolve), (C.c_int32 * 2)(0, 0))
+    return m, spec, ps
+
+
+def host_grid_poisson(mass, spacing, g, periodic=False, green=POISSON_SPECTRAL, soften=0.0, deconvolve=0, scheme=DEPOSIT_CIC) -> np.ndarray:
+    """phi [nx, ny, nz] f64 at the cell centres from the mass per cell [nx, ny, nz] (what host_deposit returns for DEPOSIT_MASS;
+    powers of two) -- nbody_grid_poisson's arithmetic on the host (nbody_host_grid_poisson; no device needed).  periodic: green =
+    POISSON_SPECTRAL or POISSON_DIFF2 and deconvolve = 0, 1 or 2 powers of the scheme's window; isolated: soften >= 0."""
+    m, spec, ps = _poisson_call(mass, spacing, g, periodic, green, soften, deconvolve, scheme)
+    phi = np.zeros(m.shape, np.float64)
+    rc = lib.nbody_host_grid_poisson(C.byref(spec), C.byref(ps), m.ctypes.data if m.size else None, phi.ctypes.data if phi.size else None, phi.size)
+    if rc:
+        raise NbodyError(rc, "nbody_host_grid_poisson: the call is not valid (include/nbody_hip.h lists what is refused)")
+    return phi
+
+
+def host_poisson_twiddles(length: int) -> np.ndarray:
+    """[length / 2, 2] f64: the table {cos, -sin}((2 pi k) / length) every transform of that length reads, on the device as on
+    the host (nbody_host_poisson_twiddles); length a power of two in 2 .. POISSON_MAX_AXIS."""
+    out = np.zeros((max(int(length) // 2, 1), 2), np.float64)
+    rc = lib.nbody_host_poisson_twiddles(int(length), out.ctypes.data)
+    if rc:
+        raise NbodyError(rc, "nbody_host_poisson_twiddles: length must be a power of two in 2 .. 4096")
+    return out
 
 
 def tidal_matrices(t6) -> np.ndarray:
@@ -990,6 +1036,26 @@ class Simulation:
         the grid reads its sample kernel issued, 0} (nbody_grid_sample_stats)."""
         out = (C.c_uint64 * 4)()
         self._check(lib.nbody_grid_sample_stats(self._h, out))
+        return np.array(out[:], np.uint64)
+
+    # -- grid Poisson (nbody_grid_poisson): the potential of a mass grid by the library's own f64 FFT, read-only, on the device
+    def grid_poisson(self, mass, spacing, g, periodic=False, green=POISSON_SPECTRAL, soften=0.0, deconvolve=0, scheme=DEPOSIT_CIC) -> np.ndarray:
+        """phi [nx, ny, nz] f64 at the cell centres from the mass per cell [nx, ny, nz] (what deposit() returns for DEPOSIT_MASS;
+        powers of two).  periodic: green = POISSON_SPECTRAL or POISSON_DIFF2, deconvolve = 0, 1 or 2 powers of the scheme's
+        window; isolated: zero padding, soften >= 0.  grid_sample(phi, ..., op=SAMPLE_GRADIENT2) then gives +grad phi.  The
+        handle lends its stream and its memory only.  The same input gives the same bits as host_grid_poisson
+        (nbody_grid_poisson)."""
+        m, spec, ps = _poisson_call(mass, spacing, g, periodic, green, soften, deconvolve, scheme)
+        phi = np.zeros(m.shape, np.float64)
+        self._check(lib.nbody_grid_poisson(self._h, C.byref(spec), C.byref(ps), m.ctypes.data if m.size else None,
+                                           phi.ctypes.data if phi.size else None, phi.size))
+        return phi
+
+    def grid_poisson_stats(self) -> np.ndarray:
+        """[4] uint64: {1 once a grid Poisson solve reached the device, the plan the last one used (poisson_lds | poisson_tile
+        << 1), its butterfly launches, the complex points it transformed} (nbody_grid_poisson_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_grid_poisson_stats(self._h, out))
         return np.array(out[:], np.uint64)
 
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits

@@ -15,6 +15,7 @@
 #include "nbody_knn.h"
 #include "nbody_paircount.h"
 #include "nbody_deposit.h"
+#include "nbody_poisson.h"
 #include "nbody_sample.h"
 #include "nbody_cells.h"
 
@@ -761,6 +762,32 @@ int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]) {
     return NBODY_OK;
 }
 
+// ---- grid Poisson (nbody_poisson.cpp): a read-only call under the census's contract, and its host twins
+int nbody_grid_poisson(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPoissonSpec* ps, const double* mass, double* phi, size_t cap) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = diag_enter(h, "nbody_grid_poisson");
+    if (rc) return rc;
+    const std::string why = nbody::poisson::call_refusal(spec, ps, mass, phi);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, "nbody_grid_poisson: " + why);
+    if (cap < nbody::poisson::shape_of(*spec).cells())
+        return fail(h, NBODY_ERR_CAPACITY, "nbody_grid_poisson: cap is smaller than the number of cells");
+    return nbody::poisson::solve(h, *spec, *ps, mass, phi);
+}
+
+int nbody_host_grid_poisson(const NbodyGridSpec* spec, const NbodyPoissonSpec* ps, const double* mass, double* phi, size_t cap) {
+    return nbody::poisson::host_entry(spec, ps, mass, phi, cap);
+}
+
+int nbody_host_poisson_twiddles(int length, double* out) { return nbody::poisson::host_twiddles(length, out); }
+
+int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_grid_poisson_stats: ") + why);
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_grid_poisson_stats: out is NULL");
+    std::copy(h->poisson_last, h->poisson_last + 4, out);
+    return NBODY_OK;
+}
+
 // ---- pair search (nbody_cells.cpp): a setting of the handle that the eight fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
@@ -1291,6 +1318,7 @@ const Knob kKnobs[] = {
     {"deposit_sort", &nbody::Tuning::deposit_sort, false}, {"deposit_combine", &nbody::Tuning::deposit_combine, false},
     {"deposit_lds", &nbody::Tuning::deposit_lds, false},
     {"sample_sort", &nbody::Tuning::sample_sort, false}, {"sample_pregrad", &nbody::Tuning::sample_pregrad, false},
+    {"poisson_lds", &nbody::Tuning::poisson_lds, false}, {"poisson_tile", &nbody::Tuning::poisson_tile, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},

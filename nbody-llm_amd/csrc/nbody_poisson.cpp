@@ -1,0 +1,67 @@
+// nbody_poisson.cpp -- nbody_grid_poisson (include/nbody_hip.h, "grid Poisson"): the tables made on the host, the scratch of a
+// call, the one copy of the grid up, the launches of kernels_poisson.hip and the one copy down.  The host twin is poisson_grid.h's.
+#include "nbody_poisson.h"
+
+#include <string>
+
+namespace nbody { namespace poisson {
+
+namespace {
+
+template <class T>
+hipError_t upload(NbodyHandle* h, T* dst, const std::vector<T>& src) {
+    if (src.empty()) return hipSuccess;
+    return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->stream);
+}
+
+// the grid and the tables on their way to the device (t outlives the call's synchronisation)
+hipError_t upload_all(NbodyHandle* h, const Shape& sh, const Tables& t, const double* mass, const Scratch& w) {
+    hipError_t e = hipMemcpyAsync(w.real, mass, sh.cells() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    for (int c = 0; c < 3 && e == hipSuccess; ++c) {
+        e = upload(h, w.tw[c], t.tw[c]);
+        if (e == hipSuccess) e = upload(h, w.K[c], t.K[c]);
+        if (e == hipSuccess) e = upload(h, w.D[c], t.D[c]);
+    }
+    return e;
+}
+
+}  // namespace
+
+int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi) {
+    const Shape sh = shape_of(spec);
+    const Tables t = tables_of(spec, ps, sh);
+    const Plan plan = make_plan();
+    const bool deconvolve = sh.periodic && ps.deconvolve > 0;
+    ScratchDev scratch(h->mem);
+    HIP_TRY(h, scratch.alloc(scratch_bytes(sh, deconvolve)));
+    const Scratch w = scratch_layout(scratch.get(), sh, deconvolve);
+    hipError_t e = upload_all(h, sh, t, mass, w);
+    int launches = 0, transforms = 2;
+    if (e == hipSuccess) {
+        launch_load(h->stream, sh, w);
+        launches += launch_transform(h->stream, sh, plan, w.x, w, false);
+        if (sh.periodic) {
+            launch_green(h->stream, sh, t.c, deconvolve, w);
+        } else {
+            launch_kernel(h->stream, sh, spec.spacing, ps.soften, w);
+            launches += launch_transform(h->stream, sh, plan, w.k, w, false);
+            launch_mul(h->stream, sh, w);
+            transforms = 3;
+        }
+        launches += launch_transform(h->stream, sh, plan, w.x, w, true);
+        launch_store(h->stream, sh, ps.g, t.inv_points, w);
+        e = hipGetLastError();
+    }
+    // (phi is the user's and t this frame's: whatever was enqueued is waited for before either goes out of reach)
+    if (e == hipSuccess) e = hipMemcpyAsync(phi, w.real, sh.cells() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t e_sync = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = e_sync;
+    HIP_TRY(h, e);
+    h->poisson_last[0] = 1;
+    h->poisson_last[1] = uint64_t(plan.code());
+    h->poisson_last[2] = uint64_t(launches);
+    h->poisson_last[3] = uint64_t(sh.points()) * uint64_t(transforms);
+    return NBODY_OK;
+}
+
+}}  // namespace nbody::poisson

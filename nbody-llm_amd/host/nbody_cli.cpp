@@ -36,7 +36,9 @@
 // the final state assigned to the N^3 cells of the cube [-HALF, HALF)^3 (nbody_deposit; spacing = (2 HALF) / N in f64): one
 // line with the four counts, one with the sum over the cells (in cell order) and the heaviest cell.  --sample value|grad2|grad4
 // (with --deposit only) reads that mass grid back at the bodies of the final state with the same spec (nbody_grid_sample): one
-// line with the four counts, then the first eight bodies' outputs with 17 significant digits.
+// line with the four counts, then the first eight bodies' outputs with 17 significant digits.  --poisson isolated|spectral|diff2
+// (with --deposit only, N a power of two) solves Poisson's equation on that mass grid (nbody_grid_poisson; the periodic modes
+// deposit with wrapped indices): one line with the mode and the grid, one with the sum of phi and its lowest cell.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -68,7 +70,8 @@ static void usage() {
                  "                 [--knn K[:HINT]]   (every body's K nearest neighbours, 1 <= K <= 32: the median and largest K-th distance, the Casertano-Hut centre)\n"
                  "                 [--deposit ngp|cic|tsc:N:HALF]   (the mass of the final state on the N^3 cells of [-HALF, HALF)^3)\n"
                  "                 [--sample value|grad2|grad4]   (with --deposit: that grid read back at the bodies, its value or its gradient)\n"
-                 "                 [--pair-search all|cells]   (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
+                 "                 [--poisson isolated|spectral|diff2]   (with --deposit, N a power of two: the potential of that mass grid, zero-padded or periodic)\n"
+                 "                 [--pair-search all|cells]  (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
 
 // KIND:p...[:cx:cy:cz] -> a component; false if the text is not one
@@ -246,6 +249,29 @@ static void print_sample(Sim& sim, const NbodyGridSpec& spec, int op) {
     }
 }
 
+// the lines of --poisson: the mass grid of --deposit (wrapped for the periodic modes) solved for the potential (nbody_grid_poisson)
+template <class Sim>
+static void print_poisson(Sim& sim, NbodyGridSpec spec, int mode, double g) {
+    std::vector<double> mass, phi;
+    uint64_t counts[4] = {0, 0, 0, 0};
+    spec.periodic = mode > 0;
+    sim.deposit(spec, mass, counts);
+    NbodyPoissonSpec ps{};
+    ps.g = g;
+    ps.green = mode == 2 ? NBODY_POISSON_DIFF2 : NBODY_POISSON_SPECTRAL;
+    sim.grid_poisson(spec, ps, mass, phi);
+    double sum = 0.0;
+    size_t low = 0;
+    for (size_t c = 0; c < phi.size(); ++c) {
+        sum += phi[c];
+        if (phi[c] < phi[low]) low = c;
+    }
+    const size_t ny = size_t(spec.dims[1]), nz = size_t(spec.dims[2]);
+    std::printf("Poisson: %s g %.17e dims %d %d %d spacing %.17e\n", mode == 0 ? "isolated" : mode == 1 ? "periodic spectral" : "periodic diff2", g,
+                spec.dims[0], spec.dims[1], spec.dims[2], spec.spacing);
+    std::printf("Poisson sum %.17e min %.17e at %zu %zu %zu\n", sum, phi.empty() ? 0.0 : phi[low], low / (ny * nz), low / nz % ny, low % nz);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
@@ -253,7 +279,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
                double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint,
-               const NbodyGridSpec* deposit_spec, int sample_op) {
+               const NbodyGridSpec* deposit_spec, int sample_op, int poisson_mode) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -326,6 +352,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (knn_k > 0) print_knn(*sim, knn_k, knn_hint);
         if (deposit_spec) print_deposit(*sim, *deposit_spec);
         if (deposit_spec && sample_op >= 0) print_sample(*sim, *deposit_spec, sample_op);
+        if (deposit_spec && poisson_mode >= 0) print_poisson(*sim, *deposit_spec, poisson_mode, double(sim->settings_mut().g));
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -375,6 +402,7 @@ int main(int argc, char** argv) {
     NbodyGridSpec deposit_spec{};
     bool deposit = false;
     int sample_op = -1;
+    int poisson_mode = -1;   // 0 isolated, 1 periodic spectral, 2 periodic diff2
     double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -488,6 +516,13 @@ int main(int argc, char** argv) {
             else if (arg == "grad4") sample_op = NBODY_SAMPLE_GRADIENT4;
             else { usage(); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--poisson")) {
+            const std::string arg = next();
+            if (arg == "isolated") poisson_mode = 0;
+            else if (arg == "spectral") poisson_mode = 1;
+            else if (arg == "diff2") poisson_mode = 2;
+            else { usage(); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -538,7 +573,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--sample needs --deposit\n");
         return 2;
     }
+    if (poisson_mode >= 0 && !deposit) {
+        std::fprintf(stderr, "--poisson needs --deposit\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode);
 }

@@ -451,6 +451,20 @@ public:
                                 uint8_t* cls, uint64_t counts[4]) {
         return nbody_host_grid_sample(xyz, n, &spec, grid, fields, op, out, cls, counts);
     }
+    // grid Poisson (nbody_grid_poisson): phi [nx][ny][nz] at the cell centres from the mass per cell (deposit() with
+    // NBODY_DEPOSIT_MASS; powers of two) by the library's own f64 FFT -- spec.periodic = 1: ps.green = NBODY_POISSON_SPECTRAL |
+    // DIFF2, ps.deconvolve powers of the scheme's window; 0: zero padding, ps.soften.  The handle lends its stream and its memory
+    // only.  grid_poisson_stats: {a call reached the device, the plan it used, butterfly launches, complex points transformed}.
+    // host_grid_poisson, host_poisson_twiddles: the same arithmetic and its twiddle table on the host (no device)
+    void grid_poisson(const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const std::vector<double>& mass, std::vector<double>& phi) {
+        phi.assign(mass.size(), 0.0);
+        check(nbody_grid_poisson(h_, &spec, &ps, mass.data(), phi.data(), phi.size()));
+    }
+    void grid_poisson_stats(uint64_t out[4]) { check(nbody_grid_poisson_stats(h_, out)); }
+    static int host_grid_poisson(const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi, size_t cap) {
+        return nbody_host_grid_poisson(&spec, &ps, mass, phi, cap);
+    }
+    static int host_poisson_twiddles(int length, double* out) { return nbody_host_poisson_twiddles(length, out); }
     // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs
     // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
