@@ -181,6 +181,8 @@ struct TreeDevWork {  // arrays of the last build (inside its workspace)
     const unsigned long long* keys2 = nullptr;  // levels 21..41, defined inside groups of equal keys only
     const int* wpre = nullptr;                  // exclusive prefix sums of the bodies' weights over the sorted order (tree_scan_sorted with weights)
     const void* incl = nullptr;                 // inclusive prefix sums {m, m x, m y, m z} over the sorted bodies (4 doubles each: the high parts of the build's double-double sums)
+    const void* incl_lo = nullptr;              // their low parts, same layout
+    const int* massive = nullptr;               // inclusive count of the sorted bodies whose mass is not 0
 };
 struct TreeCatLists {  // sharded runs: side buffer of the device build, the part that does not depend on the position type
     int* flags = nullptr;

@@ -23,16 +23,16 @@
 //     one variable-size send/recv round; the receiver lays the nodes it HOLDS -- its slice and the imports -- out in the order
 //     of their global indices and turns every link into a position in that order (launch_assemble).
 // The walk (k_bh_walk) then runs over that array as over a complete tree: every node a body visits is there.
-// Fast math, device build; node values come from prefix sums over the LOCAL sorted order (the high parts of the build's double-double sums), so against the single-shard
-// device build a centre of mass can differ in its last f32 bit (counts agree to ~1e-6, tested).
+// Fast math, device build; node values come from the build's double-double prefix sums over the LOCAL sorted order, a rank's
+// own part of a spanning cell by the single build's rule (k_let_contrib), so against the single-shard device build a centre of
+// mass can differ in its last f32 bit (counts agree to ~1e-6, tested).
 #include "kernels_let.h"
+#include "dd_sum.h"
 
 namespace nbody {
 namespace let {
 
 namespace {
-
-struct Sum4 { double m, x, y, z; };
 
 __device__ __forceinline__ int common_levels(unsigned long long a, unsigned long long b) {
     const unsigned long long x = a ^ b;
@@ -283,6 +283,7 @@ __global__ void k_let_edges(const EndInfo* __restrict__ ends, int G, int me, int
 // ---- after the local emit: my RoundB record (node count, flags, what I add to every spanning cell)
 __global__ __launch_bounds__(64) void k_let_contrib(const unsigned long long* __restrict__ keys, const signed char* __restrict__ delta,
                                                     const int* __restrict__ base, const Sum4* __restrict__ incl,
+                                                    const Sum4* __restrict__ incl_lo, const int* __restrict__ massive,
                                                     const int* __restrict__ count, const int* __restrict__ info /* {n_nodes, flags} */,
                                                     const EndInfo* __restrict__ ends, const int* __restrict__ edge, int G, int me,
                                                     RoundB* __restrict__ mine, const int* __restrict__ wpre, int by_work,
@@ -331,6 +332,9 @@ __global__ __launch_bounds__(64) void k_let_contrib(const unsigned long long* __
         while (a < b) { const int mid = (a + b) >> 1; if (keys[mid] <= hi) a = mid + 1; else b = mid; }
         const int t = a;
         c.cnt = t;
+        // A prefix from my FIRST body: every body of it lies inside the cell, nothing is subtracted, so the high part -- the
+        // double nearest to the double-double sum -- is within 2^-53 of the cell's own scale already, and a prefix of massless
+        // bodies is exactly 0.  The low parts would buy nothing here.
         if (t > 0) { const Sum4 s = incl[t - 1]; c.m = s.m; c.mx = s.x; c.my = s.y; c.mz = s.z; }
         c.base_after = t < n ? base[t] : info[0];
     } else if (n > 0 && r == me) {
@@ -341,10 +345,15 @@ __global__ __launch_bounds__(64) void k_let_contrib(const unsigned long long* __
             int a = 0, b = n - 1;  // first of my bodies in the cell
             while (a < b) { const int mid = (a + b) >> 1; if (keys[mid] >= lo) b = mid; else a = mid + 1; }
             const int ko = a;
-            const Sum4 up = incl[n - 1];
-            const Sum4 bf = ko > 0 ? incl[ko - 1] : Sum4{0.0, 0.0, 0.0, 0.0};
+            // my part of it: a difference of two prefixes, which carries the rounding of everything sorted before the cell on this
+            // rank -- taken in double-double and made exactly 0 for massless bodies, as k_tree_emit does for a whole cell
+            const Sum4 zero4 = Sum4{0.0, 0.0, 0.0, 0.0};
+            const DD4 up = DD4{incl[n - 1], incl_lo[n - 1]};
+            const DD4 bf = ko > 0 ? DD4{incl[ko - 1], incl_lo[ko - 1]} : DD4{zero4, zero4};
+            const bool massless = massive[n - 1] - (ko > 0 ? massive[ko - 1] : 0) == 0;
+            const Sum4 part = massless ? zero4 : dd4_diff(up, bf);
             c.cnt = n - ko;
-            c.m = up.m - bf.m; c.mx = up.x - bf.x; c.my = up.y - bf.y; c.mz = up.z - bf.z;
+            c.m = part.m; c.mx = part.x; c.my = part.y; c.mz = part.z;
             const int dprev = ko > 0 ? delta[ko - 1] : edge[0];
             c.base_after = base[ko] + (d - (dprev + 1));   // its index in my slice
         }
@@ -397,6 +406,7 @@ __global__ __launch_bounds__(64) void k_let_finalize(const RoundB* __restrict__ 
         float w = width;
         for (int q = 0; q < d; ++q) w = w * 0.5f;    // create_orthant halves the width exactly
         gi = offsets[r] + own.base_after;
+        // (a cell of massless bodies only: every part is exactly +0, so this is k_tree_emit's mass 0 and 0 / 0, bit for bit)
         const float4 A = make_float4(float(mx / m), float(my / m), float(mz / m), float(m));
         top_nodes[2 * (r * kLevels + d)] = A;
         top_nodes[2 * (r * kLevels + d) + 1] = make_float4(w * w, __int_as_float(skip), __int_as_float(gi), __int_as_float(-1));
@@ -727,7 +737,8 @@ void launch_edges(hipStream_t s, const EndInfo* ends, int G, int me, int* edge) 
 }
 void launch_contrib(hipStream_t s, const Shard& sh, const TreeDevWork& w, const int* info, const EndInfo* ends, const int* edge, int G, int me,
                     RoundB* mine, bool balance_by_work, const int* own_flags) {
-    hipLaunchKernelGGL(k_let_contrib, dim3(G), dim3(64), 0, s, w.keys, w.delta, w.base, static_cast<const Sum4*>(w.incl), sh.own_count(), info,
+    hipLaunchKernelGGL(k_let_contrib, dim3(G), dim3(64), 0, s, w.keys, w.delta, w.base, static_cast<const Sum4*>(w.incl), static_cast<const Sum4*>(w.incl_lo),
+                       w.massive, sh.own_count(), info,
                        ends, edge, G, me, mine, w.wpre, balance_by_work ? 1 : 0, own_flags);
 }
 void launch_offsets(hipStream_t s, const RoundB* rb, int G, int* offsets, int* out_flags, unsigned long long* bounds) {

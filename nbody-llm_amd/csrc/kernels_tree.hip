@@ -29,6 +29,7 @@
 // far below an ulp of the coordinates by then) make the build report "too deep"; the one-GPU caller falls back to the
 // host build (which goes to depth 192 before it gives up), the spatial-shard caller returns NBODY_ERR_TREE_DEPTH.
 #include "kernels.h"
+#include "dd_sum.h"
 #include "kernels_field.h"
 #include "kernels_f64.h"   // Node64: the F = f64 instantiation of the build writes 64-byte records
 
@@ -47,51 +48,13 @@ namespace {
 
 constexpr int kLevels = 21;
 
-struct Sum4 { double m, x, y, z; };
-// The prefix sums are double-double: hi + lo, |lo| <= ulp(hi) / 2, every component of {m, m x, m y, m z} its own pair.  A cell's
-// sums are differences of two prefixes, and a difference carries the rounding of everything sorted before the cell: in
-// plain f64 that is 2^-53 of the prefix (a two-body cell of 1e-12 dust behind a body of mass 1 lost its centre of mass
-// altogether), in double-double about 2^-100 of it (the count is in tests/tree_moments.py).
-struct DD4 { Sum4 hi, lo; };
-
-// s + e = a + b exactly (Knuth; no assumption on the sizes)
-__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
-    s = a + b;
-    const double bb = s - a;
-    e = (a - (s - bb)) + (b - bb);
-}
-// the same for |a| >= |b| (Dekker)
-__device__ __forceinline__ void fast_two_sum(double a, double b, double& s, double& e) {
-    s = a + b;
-    e = b - (s - a);
-}
-// (ah + al) + (bh + bl), the accurate variant: the error is a few 2^-106 of |a + b| even when the high parts cancel, which is
-// what taking a difference of prefixes does
-__device__ __forceinline__ void dd_add(double ah, double al, double bh, double bl, double& rh, double& rl) {
-    double s, e, t, f;
-    two_sum(ah, bh, s, e);
-    two_sum(al, bl, t, f);
-    e += t;
-    fast_two_sum(s, e, s, e);
-    e += f;
-    fast_two_sum(s, e, rh, rl);
-}
+// Sum4, DD4, two_sum, fast_two_sum, dd_add, dd4_diff: dd_sum.h (kernels_let.hip takes the same differences)
 __device__ __forceinline__ DD4 dd4_add(const DD4& a, const DD4& b) {
     DD4 r;
     dd_add(a.hi.m, a.lo.m, b.hi.m, b.lo.m, r.hi.m, r.lo.m);
     dd_add(a.hi.x, a.lo.x, b.hi.x, b.lo.x, r.hi.x, r.lo.x);
     dd_add(a.hi.y, a.lo.y, b.hi.y, b.lo.y, r.hi.y, r.lo.y);
     dd_add(a.hi.z, a.lo.z, b.hi.z, b.lo.z, r.hi.z, r.lo.z);
-    return r;
-}
-// upto - before, rounded to one double per component (hi of the normalised difference is the double nearest to it)
-__device__ __forceinline__ Sum4 dd4_diff(const DD4& upto, const DD4& before) {
-    Sum4 r;
-    double lo;
-    dd_add(upto.hi.m, upto.lo.m, -before.hi.m, -before.lo.m, r.m, lo);
-    dd_add(upto.hi.x, upto.lo.x, -before.hi.x, -before.lo.x, r.x, lo);
-    dd_add(upto.hi.y, upto.lo.y, -before.hi.y, -before.lo.y, r.y, lo);
-    dd_add(upto.hi.z, upto.lo.z, -before.hi.z, -before.lo.z, r.z, lo);
     return r;
 }
 // What a body's terms are kept as between k_tree_delta_totals and k_tree_scan: f32 bodies' products fit a double, their low
@@ -723,7 +686,7 @@ struct BuildLayout {
     int *ids_in, *ids, *emit_count, *base, *wpre;
     signed char* delta;
     void* sums;             // per sorted body: the terms {m, m x, m y, m z} as TermOf<P4> (room for the larger kind)
-    Sum4 *incl, *incl_lo;   // their inclusive prefix sums, high and low parts (two arrays: kernels_let.hip reads the high parts)
+    Sum4 *incl, *incl_lo;   // their inclusive prefix sums, high and low parts (two arrays; kernels_let.hip reads both)
     int* massive;           // inclusive count of bodies whose mass is not 0
     int* counters;   // [1] k_tree_ties: groups listed for the workgroup sort (cleared by k_tree_keys)
 };
@@ -758,6 +721,7 @@ int sort_keys_t(hipStream_t s, const P4* pos, const int* d_count, int n_upper, c
                 int* out_info, TreeDevWork* work) {
     const BuildLayout L = build_layout(workspace, n_cap);
     work->keys = L.keys; work->keys2 = L.keys2; work->wpre = L.wpre; work->delta = L.delta; work->base = L.base; work->ids = L.ids; work->incl = L.incl;
+    work->incl_lo = L.incl_lo; work->massive = L.massive;
     const int n = n_upper;
     if (n <= 0) { (void)hipMemsetAsync(out_info, 0, 2 * sizeof(int), s); return 0; }  // (k_tree_keys clears it otherwise)
     hipLaunchKernelGGL((k_tree_keys<P4, Real>), dim3((n + 255) / 256), dim3(256), 0, s, pos, d_count, n, center[0], center[1], center[2], width,

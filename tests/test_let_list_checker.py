@@ -32,15 +32,15 @@ def rounded_tree(nb, orc):
     return rec, tree
 
 
-def cut_world(orc, rec, tree, leaf_mode, prune):
-    """The rank_input records of RANKS ranks cut from `tree`, with the replay's own sums as accelerations and counts."""
+def cut_world(orc, rec, tree, leaf_mode, prune, n_ranks=RANKS):
+    """The rank_input records of n_ranks ranks cut from `tree`, with the replay's own sums as accelerations and counts."""
     skip = tree["skip"].astype(np.int64)
     m = len(skip)
     idx = np.arange(m)
     leaves = np.flatnonzero(skip == idx + 1)
     n = len(leaves)
     first, last = np.searchsorted(leaves, idx, side="left"), np.searchsorted(leaves, skip, side="left")
-    cuts = np.array([n * r // RANKS for r in range(RANKS + 1)])
+    cuts = tree_moments.rank_cuts(n, n_ranks)
     rank_of_leaf = np.searchsorted(cuts[1:], np.arange(n), side="right")
     owner = rank_of_leaf[first]
     spanning = rank_of_leaf[last - 1] != owner
@@ -48,7 +48,7 @@ def cut_world(orc, rec, tree, leaf_mode, prune):
     cm = tree["com_mass"].astype(np.float64)
     w2 = tree["width"].astype(np.float64) ** 2
     ranks = []
-    for r in range(RANKS):
+    for r in range(n_ranks):
         mine = leaves[cuts[r]:cuts[r + 1]]
         pos = tree["com_mass"][mine, :3]
         lo, hi = pos.min(0).astype(np.float64), pos.max(0).astype(np.float64)
@@ -245,3 +245,99 @@ def test_detectable_share(nb, orc):
         print(f"\n[let list] leaf={leaf_mode}: {det / tot:.1%} of {tot} terms individually detectable at R = {LET_LIST_RTOL_F32:g} "
               f"({det_in / tot_in:.1%} of the {tot_in} imported ones)")
         assert det / tot > 0.65
+
+
+# ---------------------------------------------------------------------------------------------- light and massless cells on a boundary
+# The planted fault here is a whole scheme: the spanning cells' moments formed from per-rank f64 prefix sums, the owner's part a
+# difference of two of them (tree_moments.rank_prefix_moments: what the spatial build did while it read the high parts of its
+# double-double prefixes only).  On worlds of comparable masses that is a correctly rounded store; behind a sun it is not.
+def planted_world(nb, orc, ics, n_ranks, residue_ulps=0.0):
+    """(ranks, tree, facts, planted com_mass): the oracle's tree of `ics` with exact moments rounded once (rounded_tree), and
+    ranks cut from it after rank_prefix_moments replaced the spanning cells' moments; `tree` and `facts` are the honest ones."""
+    rec = ics.astype(orc.P32)
+    tree = orc.bh_build_tree(rec, *BOX)
+    ex = tree_moments.exact_moments(tree)
+    tree["com_mass"][ex["cell"], :3] = ex["X"].astype(np.float32)
+    tree["com_mass"][ex["cell"], 3] = ex["M"].astype(np.float32)
+    row = np.full(len(tree["skip"]), -1, np.int64)
+    row[ex["cell"]] = np.arange(len(ex["cell"]))
+    facts = dict(shape=let_list.tree_shape(tree["skip"]), exact=ex, row=row)
+    planted = tree_moments.rank_prefix_moments(tree, n_ranks, residue_ulps)
+    ranks = cut_world(orc, rec, dict(tree, com_mass=planted), 0, True, n_ranks)
+    return ranks, tree, facts, planted
+
+
+def held_as(ranks, node):
+    """origin of `node` on every rank (-1: not held)"""
+    out = []
+    for rk in ranks:
+        at = np.flatnonzero(rk["held"]["global_index"] == node)
+        out.append(int(rk["held"]["origin"][at[0]]) if len(at) else -1)
+    return out
+
+
+@pytest.mark.parametrize("dust", tree_moments.LET_DUST_MASSES)
+@pytest.mark.parametrize("n_ranks,n", tree_moments.LET_DUST_CASES)
+def test_prefix_difference_spanning_cells_fail_on_dust(nb, orc, n_ranks, n, dust):
+    """Every (ranks, n, dust) of the GPU test: the structure check trips on the planted scheme, alone, names spanning cells only,
+    and at least one held spanning cell lies more than 10 LET_MOMENT_R u from its exact moments (a condition on the inputs: a
+    lucky rounding on the device cannot hide a fault of that size)."""
+    ranks, tree, facts, _ = planted_world(nb, orc, tree_moments.dust_world(nb, n, dust), n_ranks)
+    hit, fails = tripped(orc, ranks, tree, facts, 0)
+    assert hit == {"structure"}, fails
+    lines = [line for line in fails["structure"] if "exact moments" in line]
+    assert lines and len(lines) == len(fails["structure"]), fails
+    for line in lines:
+        origins = [int(v) for v in line.split("origins [")[1].split("]")[0].split(",")]
+        assert origins and min(origins) >= 2, line
+    worst = 0.0
+    for r, rk in enumerate(ranks):
+        h = rk["held"]
+        tops = np.flatnonzero(h["origin"] >= 2)
+        only = {k: v[tops] for k, v in h.items()}
+        relink(only, tree["skip"])
+        _, (rm, rc) = let_list.structure_failures(only, tree, facts, f"rank {r}")
+        worst = max(worst, rm, rc)
+    print(f"\n[let list] dust {dust:g} on {n_ranks} ranks, n={n}: planted spanning cells up to {worst:.3g} u from their exact moments")
+    assert worst > 10 * let_list.LET_MOMENT_R
+
+
+@pytest.mark.parametrize("own_side_only", [False, True])
+@pytest.mark.parametrize("n_ranks,n,r", tree_moments.LET_MASSLESS_CASES)
+def test_massless_boundary_worlds(nb, orc, n_ranks, n, r, own_side_only):
+    """control_world with a massless cell across boundary r (or one whose owner's part is massless).  A prefix sum does not move
+    when a massless body is added, so the planted scheme leaves an own part of exactly 0 there -- and so does the device, whose
+    high parts are the doubles nearest to two prefixes of the same exact value: mass +0 and 0 / 0, the single tree's values, and
+    the planted arrays pass.  With one ulp of the owner's prefix left in that part (two prefixes that associate differently and
+    are not correctly rounded) the cell gets a mass and a finite centre, and the massless check names it."""
+    base = tree_moments.control_world(nb, n)
+    tree0 = orc.bh_build_tree(base.astype(orc.P32), *BOX)
+    ics, node = tree_moments.massless_boundary(base, tree0, n_ranks, r, own_side_only)
+    ranks, tree, facts, planted = planted_world(nb, orc, ics, n_ranks)
+    assert np.array_equal(tree["skip"], tree0["skip"]) and np.array_equal(tree["com_mass"][:, :3][tree["skip"] == np.arange(len(tree["skip"])) + 1],
+                                                                          tree0["com_mass"][:, :3][tree0["skip"] == np.arange(len(tree0["skip"])) + 1])
+    held = held_as(ranks, node)
+    assert held[r - 1] == 2 and held[r] == 3 and all(o in (-1, 3) for q, o in enumerate(held) if q != r - 1), held
+    M = facts["exact"]["M"][facts["row"][node]]
+    assert (M != 0) == own_side_only
+    hit, fails = tripped(orc, ranks, tree, facts, 0)
+    assert not hit, fails
+    if not own_side_only:
+        assert planted[node, 3] == 0 and not np.signbit(planted[node, 3]) and np.isnan(planted[node, :3]).all()
+        for sign in (1.0, -1.0):
+            ranks, _, _, planted = planted_world(nb, orc, ics, n_ranks, residue_ulps=sign)
+            assert planted[node, 3] != 0 and np.sign(planted[node, 3]) == sign
+            hit, fails = tripped(orc, ranks, tree, facts, 0)
+            assert "structure" in hit and any("massless cells differ" in line and str(node) in line for line in fails["structure"]), fails
+
+
+@pytest.mark.parametrize("name,n_ranks,n", [("control", 2, 300), ("control", 3, 1025), ("control", 3, 5000), ("plummer", 2, 300), ("plummer", 3, 1001),
+                                            ("plummer", 5, 64), ("plummer", 8, 300), ("plummer", 4, 4097)])
+def test_prefix_difference_spanning_cells_pass_on_the_old_worlds(nb, orc, name, n_ranks, n):
+    """control_world and the Plummer worlds of tests/test_let_walk_list_gpu.py: the planted scheme passes every check there, at
+    the same LET_MOMENT_R.  The worlds above add a check that these never made."""
+    ics = tree_moments.control_world(nb, n) if name == "control" else nb.plummer(n, seed=700 + n)
+    ranks, tree, facts, _ = planted_world(nb, orc, ics, n_ranks)
+    info = check_world(orc, ranks, tree, THETA2, G, EPS, 0, facts, what=f"{name} n={n} on {n_ranks} ranks, planted")
+    print(f"\n[let list] {name} n={n} on {n_ranks} ranks, planted prefix differences: moments {info['moments'][0]:.3f} u / {info['moments'][1]:.3f} u")
+    assert max(info["moments"]) <= let_list.LET_MOMENT_R

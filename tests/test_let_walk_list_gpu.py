@@ -11,7 +11,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from let_list import check_world, one_tree_facts, rank_input
+import tree_moments as tm
+from bh_list import LIST_RTOL_F32, check_walk
+from let_list import LET_MOMENT_R, check_world, one_tree_facts, rank_input
 
 pytestmark = pytest.mark.gpu
 BOX = ((0.0, 0.0, 0.0), 64.0)
@@ -264,3 +266,149 @@ def test_refusals_name_the_call(gpu):
         assert e.value.code == nb.NBODY_ERR_INVALID and "nbody_debug_let_export_held" in str(e.value)
     finally:
         close(sims)
+
+
+# ---------------------------------------------------------------------------------------------- light and massless cells on a rank boundary
+# tree_moments' boundary worlds: a rank that holds a sun and then dust up to its bound, so that the cells that span the bound
+# are dust only and a difference of the rank's prefix sums cancels to a few bodies of 1e-12 or 1e-15 behind a mass of 1; and a
+# cell across a bound whose bodies (or whose owner's bodies) are massless.  tests/test_let_list_checker.py shows on the CPU
+# that spanning cells formed from the high parts of the prefixes alone miss LET_MOMENT_R by more than 10x on every dust case.
+ST_DUST = (G_NEWTON, 0.01, 1e-3, 0.25)
+
+
+@pytest.mark.parametrize("leaf", LEAVES)
+@pytest.mark.parametrize("dust", tm.LET_DUST_MASSES)
+@pytest.mark.parametrize("G,n", tm.LET_DUST_CASES)
+def test_dust_across_the_boundaries(gpu, orc, G, n, dust, leaf):
+    """Two suns in dust on G ranks, one pruned force pass, all five checks.  With the spanning cells' own parts taken from the high
+    parts of the prefixes alone these cases gave held spanning cells 4 to 1.4e6 u from their exact moments."""
+    nb = gpu
+    ics = tm.dust_world(nb, n, dust)
+    tree, facts = single_tree(nb, ("dust", n, dust), ics, BOX)
+    sims = make_world(nb, ics, G, BOX, nb.Settings(*ST_DUST), leaf)
+    try:
+        checked_pass(nb, orc, sims, tree, facts, leaf, f"dust {dust:g} G={G} n={n} {leaf}")
+        assert sum(len(s) for s in sims) == n
+        assert all(np.isfinite(s.get_points()["acceleration"]).all() for s in sims)
+    finally:
+        close(sims)
+
+
+@pytest.mark.parametrize("own_side_only", [False, True])
+@pytest.mark.parametrize("G,n,r", tm.LET_MASSLESS_CASES)
+def test_massless_cells_across_a_boundary(gpu, orc, G, n, r, own_side_only):
+    """control_world with every body of the deepest cell across boundary r massless (or only the owner's part of it): the cell is
+    held by both neighbours as a spanning cell and -- with exact M = 0 -- has the single-handle tree's bits, mass +0 and that
+    tree's NaN centre, which every walk opens; no acceleration is non-finite."""
+    nb = gpu
+    base = tm.control_world(nb, n)
+    tree0, _ = single_tree(nb, ("control", n), base, BOX)
+    ics, node = tm.massless_boundary(base, tree0, G, r, own_side_only)
+    tree, facts = single_tree(nb, ("massless", n, G, r, own_side_only), ics, BOX)
+    assert np.array_equal(tree["skip"], tree0["skip"])
+    M = facts["exact"]["M"][facts["row"][node]]
+    assert (M != 0) == own_side_only
+    for leaf in LEAVES:
+        sims = make_world(nb, ics, G, BOX, nb.Settings(*ST_DUST), leaf)
+        try:
+            checked_pass(nb, orc, sims, tree, facts, leaf, f"massless {'own part' if own_side_only else 'cell'} G={G} n={n} {leaf}")
+            for q, s in enumerate(sims):
+                h = s.let_held()
+                at = np.flatnonzero(h["global_index"] == node)
+                if q in (r - 1, r):
+                    assert len(at) == 1 and h["origin"][at[0]] == (2 if q == r - 1 else 3), (q, at, h["origin"][at])
+                for p in at:
+                    assert h["origin"][p] >= 2
+                    got, want = h["com_mass"][p].view(np.uint32), tree["com_mass"][node].view(np.uint32)
+                    print(f"[let list] rank {q}: cell {node} holds {[hex(v) for v in got.tolist()]}, the single tree {[hex(v) for v in want.tolist()]}")
+                    if not own_side_only:
+                        assert np.array_equal(got, want) and got[3] == 0 and np.isnan(h["com_mass"][p, :3]).all()
+                assert np.isfinite(s.get_points()["acceleration"]).all()
+        finally:
+            close(sims)
+
+
+@pytest.mark.parametrize("leaf", LEAVES)
+def test_dust_after_migration(gpu, orc, leaf):
+    """The 1e-12 dust in the width-8 box on 3 ranks: three full steps (bodies leave, the bounds are redrawn at the work quantiles
+    and move into different dust), then a checked force pass against the single tree of the survivors; both suns are there."""
+    nb = gpu
+    G, n = 3, 5000
+    box = ((0.0, 0.0, 0.0), 8.0)
+    ics = tm.dust_world(nb, n, 1e-12)
+    sims = make_world(nb, ics, G, box, nb.Settings(G_NEWTON, 0.05, 2e-2, 0.5), leaf)
+    try:
+        for _ in range(3):
+            nb.spatial_step(sims)
+        rec, idx = nb.spatial_gather(sims, n)
+        assert 2 < len(rec) < n and np.count_nonzero(rec["mass"] == 1.0) == 2
+        tree, facts = single_tree(nb, ("dust migrated", leaf), np.ascontiguousarray(rec), box)
+        checked_pass(nb, orc, sims, tree, facts, leaf, f"dust 1e-12 after 3 steps G={G} n={len(rec)} {leaf}")
+        assert all(np.isfinite(s.get_points()["acceleration"]).all() for s in sims)
+    finally:
+        close(sims)
+
+
+def test_dust_accelerations_of_the_ranks_against_the_single_handle(gpu, orc):
+    """End to end on the 1e-12 dust, 2 ranks, n = 1 025, theta2 = 0.25, the reference's leaf rule: every rank's accelerations
+    against the single-handle device-tree handle's, by the derivation of
+    test_tree_moments_gpu.test_dust_accelerations_device_tree_against_host_tree:
+
+        |a_rank - a_one| <= LIST_RTOL_F32 (T_rank + T_one) + D_i,
+
+    D_i summed over the internal cells body i accepts with b_j = SCHEME_R + LET_MOMENT_R: the single tree's stored moments lie
+    within SCHEME_R u of the exact ones (tests/test_tree_moments_gpu.py), a held cell's -- spanning or private -- within
+    LET_MOMENT_R u (the structure check of the pass, made here), so the two differ by at most their sum; LET_MOMENT_R stands
+    where the host build's n_j + 2 stood.  Both walks accept the same nodes for every body (asserted, by global index): with this
+    seed (dust_world: 400 + n) no opening test flips."""
+    nb = gpu
+    G, n = 2, 1025
+    ics = tm.dust_world(nb, n, 1e-12)
+    st = nb.Settings(*ST_DUST)
+    with nb.Simulation(ics, *BOX, method=nb.BARNES_HUT, math_mode=nb.FAST, tree_build=nb.TREE_DEVICE) as one:
+        one.settings = st
+        one.update_forces()
+        t1, a1 = one.tree(), one.get_points()["acceleration"].astype(np.float64)
+    ref1 = orc.bh_walk_list(t1, ics["position"], st.theta2, st.g, st.g_soft)
+    check_walk(a1, ref1, LIST_RTOL_F32, what="single handle")
+    facts = one_tree_facts(t1)
+    ex = facts["exact"]
+    u = tm.U[np.dtype(np.float32)]
+    b = np.zeros(len(t1["skip"]))
+    absA = np.zeros(len(t1["skip"]))
+    b[ex["cell"]] = tm.SCHEME_R[np.dtype(np.float32)] + LET_MOMENT_R
+    absA[ex["cell"]] = np.sqrt((np.asarray(ex["A"], np.float64) ** 2).sum(axis=1))
+    eps2 = float(np.float32(st.g_soft) * np.float32(st.g_soft))
+    sims = make_world(nb, ics, G, BOX, st, "reference")
+    worst = 0.0
+    try:
+        info = checked_pass(nb, orc, sims, t1, facts, "reference", f"dust 1e-12 end to end G={G} n={n}")
+        seen = 0
+        for r, s in enumerate(sims):
+            h, pts, ids = s.let_held(), s.get_points(), s.download_ids()
+            assert np.array_equal(pts["position"].view(np.uint32), ics["position"][ids].view(np.uint32))
+            held_tree = dict(com_mass=np.ascontiguousarray(h["com_mass"], np.float32), width=h["width"], skip=h["skip"])
+            gi = h["global_index"].astype(np.int64)
+            ref_r = info["refs"][r]
+            for k, i in enumerate(ids.tolist()):
+                p = ics["position"][i:i + 1]
+                lst = orc.bh_walk_list(t1, p, st.theta2, st.g, st.g_soft, list_body=0)["list"]
+                mine = orc.bh_walk_list(held_tree, p, st.theta2, st.g, st.g_soft, list_body=0)["list"]
+                assert np.array_equal(gi[mine], lst), f"rank {r} body {i}: the walks accept different nodes"
+                cm = t1["com_mass"][lst].astype(np.float64)
+                d = cm[:, :3] - p.astype(np.float64)
+                dc = b[lst] * u * absA[lst]
+                s_ = np.sqrt((d * d).sum(axis=1) + eps2)
+                tmag = st.g * cm[:, 3] * np.sqrt((d * d).sum(axis=1)) / s_ ** 3
+                s_short = np.maximum(s_ - dc, 0.0)
+                with np.errstate(divide="ignore"):
+                    D = float((tmag * b[lst] * u + 2.0 * st.g * cm[:, 3] * (1.0 + b[lst] * u) * dc / s_short ** 3)[b[lst] > 0].sum())
+                bound = LIST_RTOL_F32 * (ref_r["T"][k] + ref1["T"][i]) + D
+                diff = float(np.linalg.norm(pts["acceleration"][k].astype(np.float64) - a1[i]))
+                assert diff <= bound, f"rank {r} body {i}: |a_rank - a_one| = {diff:.3e} beyond {bound:.3e} (moment term {D:.3e})"
+                worst = max(worst, diff / bound if bound > 0 else 0.0)
+                seen += 1
+        assert seen == n
+    finally:
+        close(sims)
+    print(f"dust 1e-12 end to end on {G} ranks: worst |a_rank - a_one| / bound = {worst:.3g}")

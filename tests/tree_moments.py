@@ -201,6 +201,66 @@ def prefix_difference_moments(tree) -> np.ndarray:
     return out
 
 
+def rank_cuts(n: int, ranks: int) -> np.ndarray:
+    """First sorted position of every spatial rank, and n: the first ownership bounds are the keys at the sorted positions
+    r n / G (nbody_let.cpp: h_bounds), and the leaves of a tree in pre-order are the bodies in that sorted order."""
+    return np.array([min(n, r * n // ranks) for r in range(ranks + 1)], np.int64)
+
+
+def spanning_cells(tree, ranks: int):
+    """(nodes, owner) of the internal cells of `tree` whose leaves lie on more than one of `ranks` spatial ranks; a cell belongs
+    to the rank of its first leaf."""
+    leaf, first, last = leaves_of(tree)
+    cuts = rank_cuts(len(leaf), ranks)
+    skip = np.asarray(tree["skip"], np.int64)
+    cells = np.flatnonzero(skip != np.arange(len(skip)) + 1)
+    owner = np.searchsorted(cuts[1:], first[cells], side="right")
+    ends = np.searchsorted(cuts[1:], last[cells] - 1, side="right")
+    span = ends != owner
+    return cells[span], owner[span]
+
+
+def rank_prefix_moments(tree, ranks: int, residue_ulps: float = 0.0) -> np.ndarray:
+    """com_mass of `tree` with the moments of every cell that spans spatial ranks rebuilt the way the spatial-shard build formed
+    them while it read the HIGH parts of the prefix sums only (kernels_let.hip: k_let_contrib, k_let_finalize), in its order:
+    per rank an inclusive f64 cumulative sum of {m, m x, m y, m z} over that rank's own bodies; the owner's part the difference
+    of two of its entries (last body, body before the cell's first); every later rank's part a plain prefix of its sums; the
+    parts added up in f64 in rank order; S_a / M in f64; one store to f32.  prefix_difference_moments per rank, in short.
+    (The planted fault of tests/test_let_list_checker.py.  np.cumsum is a sequential fold: it drifts by up to one rounding of
+    the prefix per body, where the high part of a double-double prefix is the double nearest to the prefix, half an ulp off;
+    either way a difference of two entries is off by roundings of the PREFIX, 2^-53 P, whatever is left of the cell.)
+
+    Adding a massless body changes neither kind of prefix, so an own part of massless bodies comes out as exactly 0 here as on
+    the device.  `residue_ulps` leaves that many ulps of the owner's prefix in such a part instead, in all four sums: what two
+    prefixes that associate differently leave behind when neither is the correctly rounded sum (plain f64 block scans)."""
+    cm = np.asarray(tree["com_mass"])
+    assert cm.dtype == np.float32
+    leaf, first, last = leaves_of(tree)
+    cuts = rank_cuts(len(leaf), ranks)
+    b = cm[leaf].astype(np.float64)
+    terms = np.concatenate([b[:, 3:4], b[:, 3:4] * b[:, :3]], axis=1)
+    incl = [np.cumsum(terms[cuts[r]:cuts[r + 1]], axis=0) for r in range(ranks)]
+    out = cm.copy()
+    cells, owners = spanning_cells(tree, ranks)
+    for i, o in zip(cells.tolist(), owners.tolist()):
+        a, e = int(first[i]), int(last[i])
+        up = incl[o][-1]
+        before = incl[o][a - cuts[o] - 1] if a > cuts[o] else np.zeros(4)
+        s = up - before
+        if residue_ulps and not b[a:cuts[o + 1], 3].any():
+            s = s + residue_ulps * np.spacing(np.abs(up))
+        for q in range(o + 1, ranks):
+            t = min(e, int(cuts[q + 1])) - int(cuts[q])
+            if t <= 0:
+                break
+            s = s + incl[q][t - 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = s[1:] / s[0]
+        out[i, :3] = np.where(np.isnan(c), np.float32(np.nan), c.astype(np.float32))   # (one NaN, whatever sign the host's 0 / 0 has)
+        out[i, 3] = np.float32(s[0])
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- the test worlds
 # Every coordinate and mass is an f32-representable value, also in the f64 records (generated in f32, then widened), so the
 # products m x are exact in f64.  `nb` is the package (its Plummer generator and record types); seeds are fixed.
@@ -273,6 +333,38 @@ def massless_world(nb, n=300, f64=False):
     mass = np.concatenate([np.full(n + 1, 2.0 ** -9), np.zeros(8)])
     vel = np.concatenate([ics["velocity"], np.zeros((9, 3), np.float32)])
     return _records(nb, pos, mass, f64, vel)
+
+
+# The worlds that put light and massless cells on a spatial rank's boundary (tests/test_let_list_checker.py on the CPU,
+# tests/test_let_walk_list_gpu.py on the ranks): dust_world(nb, n, dust, first=True) on `ranks` ranks -- sun A sorts before
+# almost everything, so rank 0 holds a sun and then dust up to its bound, and the spanning cells below the first level or two
+# on its last body's path are dust only -- and control_world with massless_boundary applied at boundary r.
+LET_DUST_CASES = ((2, 1025), (3, 5000), (8, 1025))          # (ranks, n)
+LET_DUST_MASSES = (1e-12, 1e-15)
+LET_MASSLESS_CASES = ((2, 300, 1), (3, 300, 2), (2, 1025, 1), (3, 1025, 1))   # (ranks, n, boundary r)
+
+
+def massless_boundary(ics, tree, ranks, r, own_side_only=False):
+    """(bodies, node): `ics` with a massless cell across the boundary between spatial ranks r - 1 and r of a world of `ranks`.
+    `tree` is a tree of `ics` (Simulation.tree() or the oracle's: its leaves in pre-order are the bodies in sorted order, bit
+    copies of the records).  `node` is the deepest internal node that holds both the leaf before and the leaf at sorted
+    position r n / ranks, where the first ownership bound is drawn; every body under it gets mass 0 -- with `own_side_only`
+    only those before the boundary, the part of the rank that owns the cell.  Masses move no key, so neither the order nor the
+    bound changes: `node` is a cell with a part on each side whose exact M is 0 (or whose owner's part is exactly massless)."""
+    leaf, first, last = leaves_of(tree)
+    n = len(leaf)
+    assert n == len(ics) and 0 < r < ranks
+    p = int(rank_cuts(n, ranks)[r])
+    assert 0 < p < n
+    skip = np.asarray(tree["skip"], np.int64)
+    holds = np.flatnonzero((skip != np.arange(len(skip)) + 1) & (first <= p - 1) & (last > p))
+    node = int(holds.max())      # the cells that hold both are a chain of ancestors: the deepest comes last in pre-order
+    where = {row.tobytes(): k for k, row in enumerate(np.ascontiguousarray(ics["position"], np.float32))}
+    assert len(where) == n
+    under = np.asarray(tree["com_mass"], np.float32)[leaf[first[node]:(p if own_side_only else last[node])], :3]
+    out = ics.copy()
+    out["mass"][[where[np.ascontiguousarray(row).tobytes()] for row in under]] = 0
+    return out, node
 
 
 def light_pairs(ics):
