@@ -1230,8 +1230,8 @@ int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]);
  * not 0; mass or phi NULL; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without
  * touching a device.
  *   OUT OF SCOPE: real-to-complex transforms (the call does twice the necessary work); axes longer than 4 096;
- * non-power-of-two dimensions; a transformed kernel or a device grid kept between calls; fusing deposit, solve and sample
- * without the host round trips; a 4th-order Green's function; interlacing; multi-rank handles; a PM term in the step kernels. */
+ * non-power-of-two dimensions; a transformed kernel or a device grid kept between calls (nbody_pm_field below fuses deposit,
+ * solve and sample without the host round trips); a 4th-order Green's function; interlacing; multi-rank handles; a PM term in the step kernels. */
 #define NBODY_POISSON_SPECTRAL 0   /* periodic: -k^2 of the continuous Laplacian            */
 #define NBODY_POISSON_DIFF2    1   /* periodic: the 7-point Laplacian, the mate of GRADIENT2 */
 #define NBODY_POISSON_MAX_AXIS   4096        /* transform length of an axis (after padding) */
@@ -1248,6 +1248,79 @@ int nbody_grid_poisson(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPoi
 int nbody_host_grid_poisson(const NbodyGridSpec* spec, const NbodyPoissonSpec* ps, const double* mass, double* phi, size_t cap);
 int nbody_host_poisson_twiddles(int length, double* out /* [length/2][2] */);
 int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]);
+/* ---- particle-mesh field: deposit, solve and sample in one call, on the device (no reference counterpart) ------------------
+ * The mesh acceleration and potential of the handle's bodies, at the bodies themselves (nbody_pm_field) or at n_points caller
+ * points (nbody_pm_field_at): the only O(N + M log M) force of this library, M the cells.  NO NEW ARITHMETIC.  THE DEFINITION
+ * is the composition of the three host calls above, byte for byte; with P = the points (the bodies, or xyz):
+ *     M    = nbody_host_deposit(bodies, m, spec)                      counts[0..3] = its counts
+ *     Phi  = nbody_host_grid_poisson(spec, pm->poisson, M)
+ *     grad = nbody_host_grid_sample(P, spec, Phi, 1, pm->gradient)    cls, counts[4..7] = its classes and counts
+ *     acc[i][k] = 0.0 - grad[i][k]                                    (so a zero is +0.0)
+ *     phi[i]    = nbody_host_grid_sample(P, spec, Phi, 1, NBODY_SAMPLE_VALUE)[i]
+ * nbody_host_pm_field is literally that (no device needed; xyz == NULL: P is the bodies and n_points is ignored), and the device
+ * calls return these bytes under every plan, on NBODY_F32 and NBODY_F64 handles alike (an NBODY_F32 handle's positions and
+ * masses are widened exactly, as in the three calls).  cls is the class of the GRADIENT's sample (the stencil widened by the
+ * difference's reach), not the value's.
+ *   WHAT A PM FORCE IS AND IS NOT.  Its resolution is about two cells: below that the force falls under Newton's, smoothly for
+ * CIC and TSC.  A body feels its own mesh image: its mass is part of M, nothing subtracts it, and phi at a body includes
+ * the body's own smeared potential (with soften = 0 on an isolated grid the own cell alone contributes nothing).  Momentum is conserved
+ * -- sum m_i acc_i = 0 to rounding -- ONLY BECAUSE deposit and sample share one stencil (deposit_grid.h's), and on a periodic
+ * grid; bodies off an isolated grid push and are not pushed.  There is no short-range correction: this is PM, not P3M or TreePM.
+ *   nbody_pm_field: rows in nbody_download's order, *n_out = the live count; cap = the rows acc (and phi, cls) hold; cap
+ * smaller than the live count: NBODY_ERR_CAPACITY with *n_out set and nothing written.  n == 0: NBODY_OK, counts zeroed,
+ * nothing else written.  nbody_pm_field_at on a handle that holds no body: every output is +0.0.  phi, cls, n_out and counts
+ * may be NULL.
+ *   READ-ONLY calls under the contract of nbody_deposit: tracers and the external field play no part; on a Hermite handle the
+ * bodies are the held (x0, v0); the live count is read on the device, so a call right after a retain inside unsynchronised
+ * nbody_steps is valid; scratch is ONE allocation through the handle's registry, freed inside the call.  A call leaves nothing
+ * behind but the record nbody_pm_field_stats reads: the records of nbody_deposit_stats, nbody_grid_sample_stats and
+ * nbody_grid_poisson_stats stay as they were.
+ *   HOW (csrc/nbody_pm.cpp, csrc/kernels_pm.hip).  One allocation holds the pieces of all three stages; the deposit's int64
+ * sums, converted in place to doubles, ARE the Poisson stage's real grid, and after k_poisson_store that grid IS the sampler's:
+ * no grid crosses the bus.  The only copies are the Poisson tables up and the rows, classes and words down, with one
+ * hipStreamSynchronize at the end (at the bodies a second one, for the live count of the capacity check, as in
+ * nbody_grid_sample).  The existing deposit_*, poisson_* and sample_sort knobs are honoured.  Two knobs of its own, which change
+ * no result:
+ *     pm_share_sort (default 1)  at the bodies, with deposit_sort and sample_sort both on, the home-cell keys and the stable
+ *                 rocPRIM sort are made ONCE (the sampler's keys, which depend on the position alone) and used by k_deposit and by
+ *                 the gather; 0: two sorts, the cross-check.  nbody_pm_field_at always sorts bodies and points apart.
+ *     pm_gather (default 1)  k_pm_gather<kReach, kScheme>: one lane per point in home-cell order, ONE stencil set-up giving acc
+ *                 and phi together; each of the four outputs is the very expression tree of the matching k_sample instance
+ *                 (csrc/sample_device.h holds the sums both kernels call).  The x component of the gradient reads every stencil
+ *                 cell already, so phi costs no further grid read for CIC and TSC (NGP: the own cell, one read; a grid whose
+ *                 project_axis is 0: the value's own reads).  phi == NULL skips the value sum and its store.  Counts from
+ *                 ballots and one integer atomic per wave and class; no floating-point atomics, no LDS.  0: two k_sample
+ *                 launches over the device grid, gradient then value, honouring sample_pregrad, and a negation: the cross-check.
+ * nbody_pm_field_at deposits and solves once, then works through its points in the sampler's batches of 2^22.
+ *   nbody_pm_field_stats: out = {1 once a call on this handle reached the device else 0, the plan the last such call USED as
+ * pm_gather | pm_share_sort << 1 (the second bit only where one sort did serve both), the grid reads of the gather (pm_gather =
+ * 0: of the two k_sample launches together), the radix sorts enqueued}.  A DIAGNOSTIC AID for tools/pm_bench.py and the tests
+ * of the plans, NOT A STABLE CONTRACT.
+ *   COST: the scratch of the three calls less two grids (8 bytes per cell each).  NOT TIMED ON AN MI355X beyond the single run
+ * of tools/pm_bench.py that DESIGN 3.27 records.  Nothing asserts or promises a time.
+ *   Accepted and refused on the handles of nbody_deposit.  Refused with NBODY_ERR_INVALID (nbody_last_error names the call):
+ * whatever nbody_deposit, nbody_grid_poisson or nbody_grid_sample refuses in a spec or a Poisson spec; spec->quantity !=
+ * NBODY_DEPOSIT_MASS; pm NULL; a gradient that is not NBODY_SAMPLE_GRADIENT2 or NBODY_SAMPLE_GRADIENT4; reserved words that
+ * are not 0; acc NULL with rows to write; xyz NULL with n_points > 0 (the device call); n_points > 2^31 - 1; handles of a
+ * multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
+ *   OUT OF SCOPE, in this order: a PM term in the step kernels; a short-range (TreePM) split; a transformed isolated kernel
+ * kept between calls; real-to-complex transforms; a world-wide mesh energy; multi-rank handles. */
+typedef struct NbodyPmSpec {
+    NbodyPoissonSpec poisson;   /* as for nbody_grid_poisson */
+    int32_t gradient;           /* NBODY_SAMPLE_GRADIENT2 or NBODY_SAMPLE_GRADIENT4 */
+    int32_t reserved[3];        /* 0 */
+} NbodyPmSpec;
+int nbody_pm_field(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm,
+                   double* acc /* [n][3] */, double* phi /* [n], may be NULL */, uint8_t* cls /* [n], may be NULL */,
+                   size_t cap, size_t* n_out, uint64_t counts[8] /* may be NULL */);
+int nbody_pm_field_at(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm,
+                      const double* xyz /* [n_points][3] */, size_t n_points,
+                      double* acc, double* phi, uint8_t* cls, uint64_t counts[8]);
+int nbody_host_pm_field(const double* body_xyz, const double* body_m, size_t n_bodies,
+                        const NbodyGridSpec* spec, const NbodyPmSpec* pm,
+                        const double* xyz /* NULL: the bodies themselves */, size_t n_points,
+                        double* acc, double* phi, uint8_t* cls, uint64_t counts[8]);
+int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
  * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
  * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
@@ -1310,7 +1383,8 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
  * pair_hist_combine, pair_hist_flush (nbody_pair_counts and nbody_pair_counts_at: they change no result), deposit_sort, deposit_combine,
  * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result), sample_sort, sample_pregrad (nbody_grid_sample and
  * nbody_grid_sample_at: the plan, defaults 1, 0; they change no result), poisson_lds, poisson_tile (nbody_grid_poisson: the plan,
- * defaults 1, 16; they change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * defaults 1, 16; they change no result), pm_gather, pm_share_sort (nbody_pm_field and nbody_pm_field_at: the plan, defaults 1, 1; they
+ * change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

@@ -113,6 +113,7 @@ DECLARED_SYMBOLS = [
     "nbody_deposit", "nbody_host_deposit", "nbody_deposit_stats",
     "nbody_grid_sample", "nbody_grid_sample_at", "nbody_host_grid_sample", "nbody_grid_sample_stats",
     "nbody_grid_poisson", "nbody_host_grid_poisson", "nbody_host_poisson_twiddles", "nbody_grid_poisson_stats",
+    "nbody_pm_field", "nbody_pm_field_at", "nbody_host_pm_field", "nbody_pm_field_stats",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -147,6 +148,11 @@ def grid_spec(origin, spacing, dims, scheme=DEPOSIT_CIC, quantity=DEPOSIT_MASS, 
 class NbodyPoissonSpec(C.Structure):
     """NbodyPoissonSpec (include/nbody_hip.h, "grid Poisson"): the constants of one nbody_grid_poisson call."""
     _fields_ = [("g", C.c_double), ("soften", C.c_double), ("green", C.c_int32), ("deconvolve", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class NbodyPmSpec(C.Structure):
+    """NbodyPmSpec (include/nbody_hip.h, "particle-mesh field"): the Poisson constants and the gradient of one nbody_pm_field call."""
+    _fields_ = [("poisson", NbodyPoissonSpec), ("gradient", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class NbodyExternalComponent(C.Structure):
@@ -342,6 +348,11 @@ _sig("nbody_grid_poisson", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPoissonSp
 _sig("nbody_host_grid_poisson", _i, C.POINTER(GridSpec), C.POINTER(NbodyPoissonSpec), C.c_void_p, C.c_void_p, _sz)
 _sig("nbody_host_poisson_twiddles", _i, _i, C.c_void_p)
 _sig("nbody_grid_poisson_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_pm_field", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p)
+_sig("nbody_pm_field_at", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("nbody_host_pm_field", _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.c_void_p, _sz, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p)
+_sig("nbody_pm_field_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -524,6 +535,40 @@ def host_poisson_twiddles(length: int) -> np.ndarray:
     if rc:
         raise NbodyError(rc, "nbody_host_poisson_twiddles: length must be a power of two in 2 .. 4096")
     return out
+
+
+def pm_spec(g, gradient=SAMPLE_GRADIENT2, green=POISSON_SPECTRAL, soften=0.0, deconvolve=0) -> NbodyPmSpec:
+    """An NbodyPmSpec from plain values: the constants of grid_poisson and SAMPLE_GRADIENT2 or SAMPLE_GRADIENT4."""
+    ps = NbodyPoissonSpec(float(g), float(soften), int(green), int(deconvolve), (C.c_int32 * 2)(0, 0))
+    return NbodyPmSpec(ps, int(gradient), (C.c_int32 * 3)(0, 0, 0))
+
+
+def host_pm_field(bodies, mass, origin, spacing, dims, g, scheme=DEPOSIT_CIC, gradient=SAMPLE_GRADIENT2, periodic=False, green=POISSON_SPECTRAL,
+                  soften=0.0, deconvolve=0, project_axis=-1, points=None, phi=True) -> tuple[np.ndarray, np.ndarray | None, np.ndarray, np.ndarray]:
+    """(acc [n, 3] f64, phi [n] f64 | None, cls [n] uint8, counts [8] uint64 = the deposit's four and the gradient sample's four): the
+    particle-mesh field of the bodies [nb][3] with masses [nb] at the bodies themselves, or at points [n][3] -- host_deposit,
+    host_grid_poisson and host_grid_sample composed, acc = 0.0 - grad (nbody_host_pm_field; no device needed)."""
+    bxyz = np.ascontiguousarray(np.asarray(bodies, np.float64).reshape(-1, 3))
+    bm = np.ascontiguousarray(np.asarray(mass, np.float64).reshape(-1))
+    if len(bm) != len(bxyz):
+        raise ValueError("host_pm_field: mass must hold one value per body")
+    spec = grid_spec(origin, spacing, dims, scheme, DEPOSIT_MASS, periodic, project_axis)
+    pm = pm_spec(g, gradient, green, soften, deconvolve)
+    xyz = None if points is None else np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n = len(bxyz) if xyz is None else len(xyz)
+    acc = np.zeros((n, 3), np.float64)
+    val = np.zeros(n, np.float64) if phi else None
+    cls = np.zeros(n, np.uint8)
+    counts = np.zeros(8, np.uint64)
+    # (a non-NULL xyz even for no point: NULL means the bodies)
+    hold = np.zeros(3, np.float64)
+    xp = None if xyz is None else (xyz.ctypes.data if len(xyz) else hold.ctypes.data)
+    rc = lib.nbody_host_pm_field(bxyz.ctypes.data if len(bxyz) else None, bm.ctypes.data if len(bm) else None, len(bxyz), C.byref(spec), C.byref(pm),
+                                 xp, 0 if xyz is None else len(xyz), acc.ctypes.data if n else None, val.ctypes.data if phi and n else None,
+                                 cls.ctypes.data if n else None, counts.ctypes.data)
+    if rc:
+        raise NbodyError(rc, "nbody_host_pm_field: the call is not valid (include/nbody_hip.h lists what is refused)")
+    return acc, val, cls, counts
 
 
 def tidal_matrices(t6) -> np.ndarray:
@@ -1056,6 +1101,44 @@ class Simulation:
         << 1), its butterfly launches, the complex points it transformed} (nbody_grid_poisson_stats)."""
         out = (C.c_uint64 * 4)()
         self._check(lib.nbody_grid_poisson_stats(self._h, out))
+        return np.array(out[:], np.uint64)
+
+    # -- particle-mesh field (nbody_pm_field, nbody_pm_field_at): deposit, solve and sample in one call, the grid never leaves the device
+    def pm_field(self, origin, spacing, dims, g, scheme=DEPOSIT_CIC, gradient=SAMPLE_GRADIENT2, periodic=False, green=POISSON_SPECTRAL,
+                 soften=0.0, deconvolve=0, project_axis=-1, points=None, phi=True) -> tuple[np.ndarray, np.ndarray | None, np.ndarray, np.ndarray]:
+        """(acc [n, 3] f64, phi [n] f64 | None, cls [n] uint8, counts [8] uint64 = the deposit's four and the gradient sample's
+        four): the mesh acceleration -grad phi and the potential of the handle's bodies -- deposit(DEPOSIT_MASS), grid_poisson and
+        grid_sample(gradient) composed on the device -- at the bodies, in get_points() order, or at points [n][3].  The same
+        bits as host_pm_field, whatever the plan (nbody_pm_field, nbody_pm_field_at)."""
+        spec = grid_spec(origin, spacing, dims, scheme, DEPOSIT_MASS, periodic, project_axis)
+        pm = pm_spec(g, gradient, green, soften, deconvolve)
+        counts = np.zeros(8, np.uint64)
+        if points is not None:
+            xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+            n = len(xyz)
+            acc = np.zeros((n, 3), np.float64)
+            val = np.zeros(n, np.float64) if phi else None
+            cls = np.zeros(n, np.uint8)
+            self._check(lib.nbody_pm_field_at(self._h, C.byref(spec), C.byref(pm), xyz.ctypes.data if n else None, n, acc.ctypes.data if n else None,
+                                              val.ctypes.data if phi and n else None, cls.ctypes.data if n else None, counts.ctypes.data))
+            return acc, val, cls, counts
+        # (sized from the capacity, not from nbody_count, which would refresh the host's view of the body count: potentials())
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        cap = max(int(cfg.capacity), 1)
+        acc = np.zeros((cap, 3), np.float64)
+        val = np.zeros(cap, np.float64) if phi else None
+        cls = np.zeros(cap, np.uint8)
+        n = C.c_size_t(0)
+        self._check(lib.nbody_pm_field(self._h, C.byref(spec), C.byref(pm), acc.ctypes.data, val.ctypes.data if phi else None, cls.ctypes.data, cap,
+                                       C.byref(n), counts.ctypes.data))
+        return acc[: n.value], None if val is None else val[: n.value], cls[: n.value], counts
+
+    def pm_field_stats(self) -> np.ndarray:
+        """[4] uint64: {1 once a particle-mesh call reached the device, the plan the last one used (pm_gather | pm_share_sort << 1),
+        the grid reads of its gather, the radix sorts it enqueued} (nbody_pm_field_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_pm_field_stats(self._h, out))
         return np.array(out[:], np.uint64)
 
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits

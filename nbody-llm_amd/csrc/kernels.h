@@ -49,6 +49,8 @@ struct Tuning {
     int sample_pregrad = 0;     // the gradient ops: 1 k_grid_diff writes the three difference grids first and k_sample reads them as three fields, 0 differences on the fly
     int poisson_lds = 1;        // nbody_grid_poisson: 1 k_poisson_fft_lds, whole lines through LDS; 0 one k_poisson_fft_stage launch per stage (kernels_poisson.h Plan)
     int poisson_tile = 16;      // k_poisson_fft_lds, the strided axes: z-adjacent lines per block, 1 .. 64, rounded down to a power of two and to what fits
+    int pm_gather = 1;          // nbody_pm_field(_at): 1 k_pm_gather, acc and phi off one stencil set-up; 0 two k_sample launches and a negation (kernels_pm.h Plan)
+    int pm_share_sort = 1;      // nbody_pm_field: 1 one home-cell order serves k_deposit and the gather when deposit_sort and sample_sort are both on; 0 each stage sorts
     // the following select code that only the tuning build carries (make -C csrc tuning: -DNBODY_TUNING); the release
     // library refuses any value but the default
     int bh_walk_variant = 0;    // 1 wave-cooperative, 2 two lanes per body, 3 hot records in LDS, 4 cooperative window, 5 cooperative block walk  [NBODY_BH_VARIANT]

@@ -48,8 +48,10 @@ template <class F>
 void launch_q(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& g, int quantity, const Scratch& w);
 
 // w.acc zeroed; p.sort: k_deposit_keys<F> and the stable radix sort of (home cell, row); k_deposit<F>; k_deposit_convert.
-// Returns 0, or -1 when the rocPRIM call could not be enqueued.
+// Returns 0, or -1 when the rocPRIM call could not be enqueued.  ordered_rows (nbody_pm.cpp): the n_upper rows in home-cell order,
+// made already -- no keys and no sort here, whatever p.sort says, and w.keys, w.rows and w.sort_tmp are not touched.
 template <class F>
-int launch_deposit(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& g, const Plan& p, const Scratch& w);
+int launch_deposit(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& g, const Plan& p, const Scratch& w,
+                   const int* ordered_rows = nullptr);
 
 }}  // namespace nbody::deposit

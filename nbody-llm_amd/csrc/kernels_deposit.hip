@@ -263,12 +263,12 @@ void launch_q(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& g, in
 }
 
 template <class F>
-int launch_deposit(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& g, const Plan& p, const Scratch& w) {
+int launch_deposit(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& g, const Plan& p, const Scratch& w, const int* ordered_rows) {
     const size_t cells = cells_of(g);
     (void)hipMemsetAsync(w.acc, 0, cells * sizeof(long long), s);
     if (n_upper > 0) {
-        const int* rows = nullptr;
-        if (p.sort) {
+        const int* rows = ordered_rows;
+        if (p.sort && !ordered_rows) {
             hipLaunchKernelGGL(k_deposit_keys<F>, dim3(blocks_for(n_upper)), dim3(kDepositBlock), 0, s, sh.own_pos(), sh.own_count(), n_upper, g,
                                uint32_t(cells), w.q, w.keys, w.rows);
             size_t tb = w.sort_bytes;
@@ -293,7 +293,7 @@ int launch_deposit(hipStream_t s, const ShardT<F>& sh, int n_upper, const Grid& 
 
 template void launch_q<float>(hipStream_t, const ShardT<float>&, int, const Grid&, int, const Scratch&);
 template void launch_q<double>(hipStream_t, const ShardT<double>&, int, const Grid&, int, const Scratch&);
-template int launch_deposit<float>(hipStream_t, const ShardT<float>&, int, const Grid&, const Plan&, const Scratch&);
-template int launch_deposit<double>(hipStream_t, const ShardT<double>&, int, const Grid&, const Plan&, const Scratch&);
+template int launch_deposit<float>(hipStream_t, const ShardT<float>&, int, const Grid&, const Plan&, const Scratch&, const int*);
+template int launch_deposit<double>(hipStream_t, const ShardT<double>&, int, const Grid&, const Plan&, const Scratch&, const int*);
 
 }}  // namespace nbody::deposit

@@ -34,8 +34,9 @@ struct Scratch {
     double* K[3] = {nullptr, nullptr, nullptr};    // [n] periodic
     double* D[3] = {nullptr, nullptr, nullptr};    // [n] periodic, deconvolve > 0
 };
-size_t scratch_bytes(const Shape& sh, bool deconvolve);
-Scratch scratch_layout(void* base, const Shape& sh, bool deconvolve);
+// own_real == false (nbody_pm.cpp): no room for w.real, which the caller points at a grid that is on the device already
+size_t scratch_bytes(const Shape& sh, bool deconvolve, bool own_real = true);
+Scratch scratch_layout(void* base, const Shape& sh, bool deconvolve, bool own_real = true);
 
 // k_poisson_load: w.x from w.real, +0.0 in the imaginary parts and in the padding
 void launch_load(hipStream_t s, const Shape& sh, const Scratch& w);

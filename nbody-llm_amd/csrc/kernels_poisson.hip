@@ -180,9 +180,9 @@ size_t floor_pow2(size_t v) {
     return p;
 }
 
-Scratch layout(Carver& c, const Shape& sh, bool deconvolve) {
+Scratch layout(Carver& c, const Shape& sh, bool deconvolve, bool own_real) {
     Scratch w;
-    w.real = c.take<double>(sh.cells());
+    if (own_real) w.real = c.take<double>(sh.cells());
     w.x = c.take<Cx>(sh.points());
     if (!sh.periodic) w.k = c.take<Cx>(sh.points());
     for (int a = 0; a < 3; ++a) {
@@ -209,10 +209,10 @@ int lines_per_block(const Plan& p, size_t L, size_t inner, size_t lines) {
     return int(std::min({size_t(p.tile), inner, size_t(kLdsPoints) / L}));   // (all three powers of two, L <= kLdsPoints)
 }
 
-size_t scratch_bytes(const Shape& sh, bool deconvolve) { Carver c; layout(c, sh, deconvolve); return c.offset(); }
-Scratch scratch_layout(void* base, const Shape& sh, bool deconvolve) {
+size_t scratch_bytes(const Shape& sh, bool deconvolve, bool own_real) { Carver c; layout(c, sh, deconvolve, own_real); return c.offset(); }
+Scratch scratch_layout(void* base, const Shape& sh, bool deconvolve, bool own_real) {
     Carver c(base);
-    return layout(c, sh, deconvolve);
+    return layout(c, sh, deconvolve, own_real);
 }
 
 void launch_load(hipStream_t s, const Shape& sh, const Scratch& w) {

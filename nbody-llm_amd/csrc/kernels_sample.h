@@ -39,8 +39,9 @@ struct Scratch {
     void* sort_tmp = nullptr;
     size_t sort_bytes = 0;
 };
-size_t scratch_bytes(size_t n, size_t cells, int fields, int op, const Plan& p);
-Scratch scratch_layout(void* base, size_t n, size_t cells, int fields, int op, const Plan& p);
+// own_grid == false (nbody_pm.cpp): no room for w.grid, which the caller points at a grid that is on the device already
+size_t scratch_bytes(size_t n, size_t cells, int fields, int op, const Plan& p, bool own_grid = true);
+Scratch scratch_layout(void* base, size_t n, size_t cells, int fields, int op, const Plan& p, bool own_grid = true);
 
 // k_sample_stage<F>: w.xyz of every live row of sh
 template <class F>
@@ -49,8 +50,14 @@ void launch_stage(hipStream_t s, const ShardT<F>& sh, int n_upper, const Scratch
 // k_grid_diff: w.diff from w.grid (one field)
 void launch_diff(hipStream_t s, const Grid& g, int op, const Scratch& w);
 
-// w.words zeroed; p.sort: k_sample_keys and the stable radix sort of (home cell, row); k_sample over the n rows of w.xyz, of
-// which the first *count are live (count == nullptr: all n).  Returns 0, or -1 when the rocPRIM call could not be enqueued.
-int launch_sample(hipStream_t s, const int* count, int n, const Grid& g, int fields, int op, const Plan& p, const Scratch& w);
+// k_sample_keys and the stable radix sort of (home cell, row) over the n rows of w.xyz: w.rows + n is the rows in key order.
+// Returns 0, or -1 when the rocPRIM call could not be enqueued.
+int launch_order(hipStream_t s, const int* count, int n, const Grid& g, const Scratch& w);
+
+// w.words zeroed; p.sort: launch_order, unless `ordered` says that w.rows + n holds the order of these rows already; k_sample
+// over the n rows of w.xyz, of which the first *count are live (count == nullptr: all n).  Returns 0, or -1 when the rocPRIM
+// call could not be enqueued.
+int launch_sample(hipStream_t s, const int* count, int n, const Grid& g, int fields, int op, const Plan& p, const Scratch& w,
+                  bool ordered = false);
 
 }}  // namespace nbody::sample

@@ -15,7 +15,7 @@
 //                   component's stencil cells share their reads along the differentiated axis: cnt + 2 reach cells there, not
 //                   2 reach cnt.  The counts come from ballots and one integer atomic per wave and class.
 #include "kernels_sample.h"
-#include "device_util.h"   // live_count, wave_add
+#include "sample_device.h"   // the stencil set-up, the sums and the counts, shared with kernels_pm.hip
 #include "kernels.h"   // tuning()
 #include "real.h"      // widen
 #include "scratch_carve.h"
@@ -25,92 +25,14 @@
 namespace nbody {
 
 using sample::kSampleBlock;
+using sample::count_classes;
+using sample::drop_unreached;
+using sample::gradient_component;
+using sample::weighted_sum;
 
 namespace {
 
 enum { kModeValue = 0, kModeGrad2 = 1, kModeGrad4 = 2, kModePre = 3 };
-
-// the linear index of a cell from its three indices on the grid (< 2^27: int arithmetic holds it)
-__device__ __forceinline__ int cell_of(const deposit::Grid& g, int ix, int iy, int iz) { return (ix * g.dims[1] + iy) * g.dims[2] + iz; }
-
-// the sum of w G[cell] over the stencil in sample_grid.h's order; an index of -1 drops the term
-template <int kCnt>
-__device__ __forceinline__ double weighted_sum(const deposit::Grid& g, const double* __restrict__ G, const int (&ix)[kCnt], const int (&iy)[kCnt],
-                                               const int (&iz)[kCnt], const double (&wx)[3], const double (&wy)[3], const double (&wz)[3],
-                                               unsigned long long& reads) {
-    double v[kCnt][kCnt][kCnt];
-#pragma unroll
-    for (int a = 0; a < kCnt; ++a)
-#pragma unroll
-        for (int b = 0; b < kCnt; ++b)
-#pragma unroll
-            for (int c = 0; c < kCnt; ++c) {
-                const bool ok = ix[a] >= 0 && iy[b] >= 0 && iz[c] >= 0;
-                v[a][b][c] = ok ? G[cell_of(g, ix[a], iy[b], iz[c])] : 0.0;
-                reads += ok;
-            }
-    double sum = 0.0;
-#pragma unroll
-    for (int a = 0; a < kCnt; ++a)
-#pragma unroll
-        for (int b = 0; b < kCnt; ++b)
-#pragma unroll
-            for (int c = 0; c < kCnt; ++c)
-                if (ix[a] >= 0 && iy[b] >= 0 && iz[c] >= 0) sum = sum + ((wx[a] * wy[b]) * wz[c]) * v[a][b][c];
-    return sum;
-}
-
-// component K of the gradient, the differences formed on the fly: the kCnt + 2 kReach cells along axis K from first_k - kReach
-// on are read once for each of the other two axes' stencil cells
-template <int K, int kCnt, int kReach>
-__device__ __forceinline__ double gradient_component(const deposit::Grid& g, const double* __restrict__ G, bool active, long long first_k,
-                                                     const int (&ix)[kCnt], const int (&iy)[kCnt], const int (&iz)[kCnt], const double (&wx)[3],
-                                                     const double (&wy)[3], const double (&wz)[3], double den, unsigned long long& reads) {
-    constexpr int kExt = kCnt + 2 * kReach;
-    int e[kExt];
-#pragma unroll
-    for (int j = 0; j < kExt; ++j) e[j] = active ? int(deposit::cell_on_axis(first_k - kReach + j, g.dims[K], g.periodic)) : -1;
-    double v[kExt][kCnt][kCnt];   // [along K][the lower of the other two axes][the higher]
-#pragma unroll
-    for (int j = 0; j < kExt; ++j)
-#pragma unroll
-        for (int p = 0; p < kCnt; ++p)
-#pragma unroll
-            for (int q = 0; q < kCnt; ++q) {
-                v[j][p][q] = 0.0;
-                if (kCnt == 1 && j == kReach) continue;   // NGP: no difference reads its own cell
-                const int cx = K == 0 ? e[j] : ix[p], cy = K == 1 ? e[j] : K == 0 ? iy[p] : iy[q], cz = K == 2 ? e[j] : iz[q];
-                const bool ok = cx >= 0 && cy >= 0 && cz >= 0;
-                if (ok) v[j][p][q] = G[cell_of(g, cx, cy, cz)];
-                reads += ok;
-            }
-    double sum = 0.0;
-#pragma unroll
-    for (int a = 0; a < kCnt; ++a)
-#pragma unroll
-        for (int b = 0; b < kCnt; ++b)
-#pragma unroll
-            for (int c = 0; c < kCnt; ++c) {
-                const int t = K == 0 ? a : K == 1 ? b : c, p = K == 0 ? b : a, q = K == 2 ? b : c;
-                bool ok = ix[a] >= 0 && iy[b] >= 0 && iz[c] >= 0 && e[t + kReach - 1] >= 0 && e[t + kReach + 1] >= 0;
-                double d;
-                if constexpr (kReach == 1) {
-                    d = sample::diff2(v[t][p][q], v[t + 2][p][q], den);
-                } else {
-                    ok = ok && e[t] >= 0 && e[t + 4] >= 0;
-                    d = sample::diff4(v[t][p][q], v[t + 1][p][q], v[t + 3][p][q], v[t + 4][p][q], den);
-                }
-                if (ok) sum = sum + ((wx[a] * wy[b]) * wz[c]) * d;
-            }
-    return sum;
-}
-
-// ix with the stencil cells dropped whose difference along the axis (first, dim) reads off the grid
-template <int kCnt>
-__device__ __forceinline__ void drop_unreached(const int (&ix)[kCnt], long long first, int dim, int periodic, int reach, int (&kept)[kCnt]) {
-#pragma unroll
-    for (int t = 0; t < kCnt; ++t) kept[t] = periodic || (first + t - reach >= 0 && first + t + reach < (long long)dim) ? ix[t] : -1;
-}
 
 }  // namespace
 
@@ -162,37 +84,13 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample(const double* __restric
                                                          const int* __restrict__ rows, double* __restrict__ out, uint8_t* __restrict__ cls_out,
                                                          sample::Words* words) {
     constexpr int kCnt = kScheme + 1;
-    const int s = blockIdx.x * kSampleBlock + threadIdx.x;
-    const int live = count ? live_count(count, n) : n;
-    int row = -1;
-    if (s < n) {
-        const int r = rows ? rows[s] : s;   // (a permutation of 0 .. n - 1)
-        if (r >= 0 && r < live) row = r;
-    }
-    // (a lane without a row takes the stencil of the grid's corner and drops it: the stencil is then written on every path)
-    const double x = row >= 0 ? xyz[3 * size_t(row)] : g.origin[0], y = row >= 0 ? xyz[3 * size_t(row) + 1] : g.origin[1],
-                 z = row >= 0 ? xyz[3 * size_t(row) + 2] : g.origin[2];
-    deposit::Stencil st;
-    const bool taken = deposit::body_stencil(g, x, y, z, 0.0, &st);
-    const int cls = row < 0 ? -1 : taken ? sample::point_class(g, st, reach) : int(deposit::kSkipped);
-    const bool active = cls == deposit::kInside || cls == deposit::kPartial;
-    // the lane's copy of what the terms need, indexed by constants only from here on
-    long long f0 = 0, f1 = 0, f2 = 0;
-    double wx[3] = {0.0, 0.0, 0.0}, wy[3] = {0.0, 0.0, 0.0}, wz[3] = {0.0, 0.0, 0.0};
-    if (active) {
-        f0 = st.first[0]; f1 = st.first[1]; f2 = st.first[2];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) { wx[t] = st.w[0][t]; wy[t] = st.w[1][t]; wz[t] = st.w[2][t]; }
-    }
-    // the cells an axis has (uniform): kCnt on an axis in use, one on the ignored axis
-    const int ca = g.axis == 0 ? 1 : kCnt, cb = g.axis == 1 ? 1 : kCnt, cc = g.axis == 2 ? 1 : kCnt;
-    int ix[kCnt], iy[kCnt], iz[kCnt];   // the stencil's indices on the grid, -1: the term is dropped
-#pragma unroll
-    for (int t = 0; t < kCnt; ++t) {
-        ix[t] = active && t < ca ? int(deposit::cell_on_axis(f0 + t, g.dims[0], g.periodic)) : -1;
-        iy[t] = active && t < cb ? int(deposit::cell_on_axis(f1 + t, g.dims[1], g.periodic)) : -1;
-        iz[t] = active && t < cc ? int(deposit::cell_on_axis(f2 + t, g.dims[2], g.periodic)) : -1;
-    }
+    sample::LaneStencil<kCnt> lane;   // (sample_device.h: the row, the class and the stencil, indexed by constants only)
+    lane.set_up(xyz, count, n, g, reach, rows, blockIdx.x * kSampleBlock + threadIdx.x);
+    const int row = lane.row, cls = lane.cls;
+    const bool active = lane.active;
+    const long long f0 = lane.f0, f1 = lane.f1, f2 = lane.f2;
+    const auto &wx = lane.wx, &wy = lane.wy, &wz = lane.wz;
+    const auto &ix = lane.ix, &iy = lane.iy, &iz = lane.iz;
     unsigned long long reads = 0;
     if constexpr (kMode == kModeValue) {
         const size_t cells = deposit::cells_of(g);
@@ -230,12 +128,7 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample(const double* __restric
         }
     }
     if (row >= 0) cls_out[row] = uint8_t(cls);
-    unsigned long long n_of[4];   // (every lane of the wave is here)
-    for (int k = 0; k < 4; ++k) n_of[k] = (unsigned long long)__popcll(__ballot(cls == k));
-    if (threadIdx.x % 64 == 0)
-        for (int k = 0; k < 4; ++k)
-            if (n_of[k]) atomicAdd(&words->counts[k], n_of[k]);
-    wave_add(reads, &words->reads);
+    count_classes(cls, reads, words);
 }
 
 namespace sample {
@@ -261,10 +154,10 @@ size_t sort_tmp_bytes(size_t n, size_t cells) {
     (void)rocprim::radix_sort_pairs(nullptr, b, k, k, v, v, n, 0, unsigned(key_bits(cells)), 0);
     return b;
 }
-Scratch layout(Carver& c, size_t n, size_t cells, int fields, int op, const Plan& p) {
+Scratch layout(Carver& c, size_t n, size_t cells, int fields, int op, const Plan& p, bool own_grid) {
     Scratch w;
     w.words = c.take<Words>(1);
-    w.grid = c.take<double>(size_t(fields) * cells);
+    if (own_grid) w.grid = c.take<double>(size_t(fields) * cells);
     if (p.pregrad) w.diff = c.take<double>(3 * cells);
     w.xyz = c.take<double>(3 * n);
     w.out = c.take<double>(size_t(width_of(op, fields)) * n);
@@ -279,10 +172,14 @@ Scratch layout(Carver& c, size_t n, size_t cells, int fields, int op, const Plan
 }
 }  // namespace
 
-size_t scratch_bytes(size_t n, size_t cells, int fields, int op, const Plan& p) { Carver c; layout(c, n, cells, fields, op, p); return c.offset(); }
-Scratch scratch_layout(void* base, size_t n, size_t cells, int fields, int op, const Plan& p) {
+size_t scratch_bytes(size_t n, size_t cells, int fields, int op, const Plan& p, bool own_grid) {
+    Carver c;
+    layout(c, n, cells, fields, op, p, own_grid);
+    return c.offset();
+}
+Scratch scratch_layout(void* base, size_t n, size_t cells, int fields, int op, const Plan& p, bool own_grid) {
     Carver c(base);
-    return layout(c, n, cells, fields, op, p);
+    return layout(c, n, cells, fields, op, p, own_grid);
 }
 
 template <class F>
@@ -301,17 +198,21 @@ void launch_diff(hipStream_t s, const Grid& g, int op, const Scratch& w) {
     else hipLaunchKernelGGL(k_grid_diff<2>, grid, block, 0, s, g, den, cells, w.grid, w.diff);
 }
 
-int launch_sample(hipStream_t s, const int* count, int n, const Grid& g, int fields, int op, const Plan& p, const Scratch& w) {
-    (void)hipMemsetAsync(w.words, 0, sizeof(Words), s);
+int launch_order(hipStream_t s, const int* count, int n, const Grid& g, const Scratch& w) {
     if (n <= 0) return 0;
     const size_t cells = cells_of(g);
+    hipLaunchKernelGGL(k_sample_keys, dim3(blocks_for(size_t(n))), dim3(kSampleBlock), 0, s, w.xyz, count, n, g, uint32_t(cells), w.keys, w.rows);
+    size_t tb = w.sort_bytes;
+    return rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys, w.keys + n, w.rows, w.rows + n, size_t(n), 0, unsigned(key_bits(cells)), s) == hipSuccess ? 0 : -1;
+}
+
+int launch_sample(hipStream_t s, const int* count, int n, const Grid& g, int fields, int op, const Plan& p, const Scratch& w, bool ordered) {
+    (void)hipMemsetAsync(w.words, 0, sizeof(Words), s);
+    if (n <= 0) return 0;
     const dim3 grid(blocks_for(size_t(n))), block(kSampleBlock);
     const int* rows = nullptr;
     if (p.sort) {
-        hipLaunchKernelGGL(k_sample_keys, grid, block, 0, s, w.xyz, count, n, g, uint32_t(cells), w.keys, w.rows);
-        size_t tb = w.sort_bytes;
-        if (rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys, w.keys + n, w.rows, w.rows + n, size_t(n), 0, unsigned(key_bits(cells)), s) != hipSuccess)
-            return -1;
+        if (!ordered && launch_order(s, count, n, g, w) != 0) return -1;
         rows = w.rows + n;
     }
     const int mode = op == NBODY_SAMPLE_VALUE ? kModeValue : p.pregrad ? kModePre : op == NBODY_SAMPLE_GRADIENT2 ? kModeGrad2 : kModeGrad4;

@@ -15,6 +15,7 @@
 #include "nbody_knn.h"
 #include "nbody_paircount.h"
 #include "nbody_deposit.h"
+#include "nbody_pm.h"
 #include "nbody_poisson.h"
 #include "nbody_sample.h"
 #include "nbody_cells.h"
@@ -788,6 +789,49 @@ int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]) {
     return NBODY_OK;
 }
 
+// ---- particle-mesh field (nbody_pm.cpp): two read-only calls under the census's contract, and their host twin
+namespace {
+int pm_enter(NbodyHandle* h, const char* call, const NbodyGridSpec* spec, const NbodyPmSpec* pm) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    const std::string why = nbody::pm::call_refusal(spec, pm);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return NBODY_OK;
+}
+}  // namespace
+
+int nbody_pm_field(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm, double* acc, double* phi, uint8_t* cls, size_t cap,
+                   size_t* n_out, uint64_t counts[8]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = pm_enter(h, "nbody_pm_field", spec, pm);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) { return nbody::pm::at_bodies(h, b.sh, b.n_local, *spec, *pm, acc, phi, cls, cap, n_out, counts); });
+}
+
+int nbody_pm_field_at(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm, const double* xyz, size_t n_points, double* acc,
+                      double* phi, uint8_t* cls, uint64_t counts[8]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = pm_enter(h, "nbody_pm_field_at", spec, pm);
+    if (rc) return rc;
+    if (n_points > size_t(0x7fffffff)) return fail(h, NBODY_ERR_INVALID, "nbody_pm_field_at: n_points must not exceed 2^31 - 1");
+    if (n_points && !xyz) return fail(h, NBODY_ERR_INVALID, "nbody_pm_field_at: xyz is NULL");
+    if (n_points && !acc) return fail(h, NBODY_ERR_INVALID, "nbody_pm_field_at: acc is NULL");
+    return with_bodies(h, [&](auto& b) { return nbody::pm::at_points(h, b.sh, b.n_local, *spec, *pm, xyz, n_points, acc, phi, cls, counts); });
+}
+
+int nbody_host_pm_field(const double* body_xyz, const double* body_m, size_t n_bodies, const NbodyGridSpec* spec, const NbodyPmSpec* pm,
+                        const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t counts[8]) {
+    return nbody::pm::host_entry(body_xyz, body_m, n_bodies, spec, pm, xyz, n_points, acc, phi, cls, counts);
+}
+
+int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_pm_field_stats: ") + why);
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_pm_field_stats: out is NULL");
+    std::copy(h->pm_last, h->pm_last + 4, out);
+    return NBODY_OK;
+}
+
 // ---- pair search (nbody_cells.cpp): a setting of the handle that the eight fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
@@ -1319,6 +1363,7 @@ const Knob kKnobs[] = {
     {"deposit_lds", &nbody::Tuning::deposit_lds, false},
     {"sample_sort", &nbody::Tuning::sample_sort, false}, {"sample_pregrad", &nbody::Tuning::sample_pregrad, false},
     {"poisson_lds", &nbody::Tuning::poisson_lds, false}, {"poisson_tile", &nbody::Tuning::poisson_tile, false},
+    {"pm_gather", &nbody::Tuning::pm_gather, false}, {"pm_share_sort", &nbody::Tuning::pm_share_sort, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},

@@ -14,28 +14,17 @@ hipError_t upload(NbodyHandle* h, T* dst, const std::vector<T>& src) {
     return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->stream);
 }
 
-// the grid and the tables on their way to the device (t outlives the call's synchronisation)
-hipError_t upload_all(NbodyHandle* h, const Shape& sh, const Tables& t, const double* mass, const Scratch& w) {
-    hipError_t e = hipMemcpyAsync(w.real, mass, sh.cells() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+}  // namespace
+
+hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
+                   const Scratch& w, int* launches_out, int* transforms_out) {
+    const bool deconvolve = sh.periodic && ps.deconvolve > 0;
+    hipError_t e = hipSuccess;
     for (int c = 0; c < 3 && e == hipSuccess; ++c) {
         e = upload(h, w.tw[c], t.tw[c]);
         if (e == hipSuccess) e = upload(h, w.K[c], t.K[c]);
         if (e == hipSuccess) e = upload(h, w.D[c], t.D[c]);
     }
-    return e;
-}
-
-}  // namespace
-
-int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi) {
-    const Shape sh = shape_of(spec);
-    const Tables t = tables_of(spec, ps, sh);
-    const Plan plan = make_plan();
-    const bool deconvolve = sh.periodic && ps.deconvolve > 0;
-    ScratchDev scratch(h->mem);
-    HIP_TRY(h, scratch.alloc(scratch_bytes(sh, deconvolve)));
-    const Scratch w = scratch_layout(scratch.get(), sh, deconvolve);
-    hipError_t e = upload_all(h, sh, t, mass, w);
     int launches = 0, transforms = 2;
     if (e == hipSuccess) {
         launch_load(h->stream, sh, w);
@@ -52,6 +41,23 @@ int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps,
         launch_store(h->stream, sh, ps.g, t.inv_points, w);
         e = hipGetLastError();
     }
+    if (launches_out) *launches_out = launches;
+    if (transforms_out) *transforms_out = transforms;
+    return e;
+}
+
+int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi) {
+    const Shape sh = shape_of(spec);
+    const Tables t = tables_of(spec, ps, sh);
+    const Plan plan = make_plan();
+    const bool deconvolve = sh.periodic && ps.deconvolve > 0;
+    ScratchDev scratch(h->mem);
+    HIP_TRY(h, scratch.alloc(scratch_bytes(sh, deconvolve)));
+    const Scratch w = scratch_layout(scratch.get(), sh, deconvolve);
+    // the grid on its way to the device (t outlives the call's synchronisation)
+    hipError_t e = hipMemcpyAsync(w.real, mass, sh.cells() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    int launches = 0, transforms = 2;
+    if (e == hipSuccess) e = enqueue(h, spec, ps, sh, t, plan, w, &launches, &transforms);
     // (phi is the user's and t this frame's: whatever was enqueued is waited for before either goes out of reach)
     if (e == hipSuccess) e = hipMemcpyAsync(phi, w.real, sh.cells() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     const hipError_t e_sync = hipStreamSynchronize(h->stream);

@@ -12,4 +12,11 @@ namespace nbody { namespace poisson {
 // inside the call; nothing of the handle's is written but the record behind nbody_grid_poisson_stats.  mass may be phi.
 int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi);
 
+// What solve enqueues between its two copies, for a caller whose mass is on the device already (nbody_pm.cpp): the tables of t
+// on their way up -- t outlives the caller's synchronisation -- and every launch from k_poisson_load to k_poisson_store, so
+// that w.real, which held the mass, holds phi.  Nothing is waited for and no record is written.  launches_out and
+// transforms_out (may be null): the butterfly launches made and the 3-D transforms (2 periodic, 3 isolated).
+hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
+                   const Scratch& w, int* launches_out, int* transforms_out);
+
 }}  // namespace nbody::poisson

@@ -38,7 +38,9 @@
 // (with --deposit only) reads that mass grid back at the bodies of the final state with the same spec (nbody_grid_sample): one
 // line with the four counts, then the first eight bodies' outputs with 17 significant digits.  --poisson isolated|spectral|diff2
 // (with --deposit only, N a power of two) solves Poisson's equation on that mass grid (nbody_grid_poisson; the periodic modes
-// deposit with wrapped indices): one line with the mode and the grid, one with the sum of phi and its lowest cell.
+// deposit with wrapped indices): one line with the mode and the grid, one with the sum of phi and its lowest cell.  --pm
+// isolated|spectral|diff2:grad2|grad4 (with --deposit only, N a power of two) is the three of them in one call (nbody_pm_field):
+// one line with the mode, the gradient and the eight counts, then the first eight bodies' acc and phi with 17 significant digits.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -70,6 +72,7 @@ static void usage() {
                  "                 [--knn K[:HINT]]   (every body's K nearest neighbours, 1 <= K <= 32: the median and largest K-th distance, the Casertano-Hut centre)\n"
                  "                 [--deposit ngp|cic|tsc:N:HALF]   (the mass of the final state on the N^3 cells of [-HALF, HALF)^3)\n"
                  "                 [--sample value|grad2|grad4]   (with --deposit: that grid read back at the bodies, its value or its gradient)\n"
+                 "                 [--pm isolated|spectral|diff2:grad2|grad4]   (with --deposit, N a power of two: the mesh acceleration and potential at the bodies in one call)\n"
                  "                 [--poisson isolated|spectral|diff2]   (with --deposit, N a power of two: the potential of that mass grid, zero-padded or periodic)\n"
                  "                 [--pair-search all|cells]  (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
@@ -272,6 +275,27 @@ static void print_poisson(Sim& sim, NbodyGridSpec spec, int mode, double g) {
     std::printf("Poisson sum %.17e min %.17e at %zu %zu %zu\n", sum, phi.empty() ? 0.0 : phi[low], low / (ny * nz), low / nz % ny, low % nz);
 }
 
+// the lines of --pm: the mesh field at the bodies in one call (nbody_pm_field): the boundary condition of --poisson, the gradient
+// of --sample; then the first eight bodies' acc and phi with 17 significant digits
+template <class Sim>
+static void print_pm(Sim& sim, NbodyGridSpec spec, int mode, int gradient, double g) {
+    std::vector<double> acc, phi;
+    std::vector<uint8_t> cls;
+    uint64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    spec.periodic = mode > 0;
+    NbodyPmSpec pm{};
+    pm.poisson.g = g;
+    pm.poisson.green = mode == 2 ? NBODY_POISSON_DIFF2 : NBODY_POISSON_SPECTRAL;
+    pm.gradient = gradient;
+    sim.pm_field(spec, pm, acc, phi, cls, counts);
+    std::printf("PM: %s gradient %d g %.17e bodies %zu deposited %llu %llu %llu %llu sampled %llu %llu %llu %llu\n",
+                mode == 0 ? "isolated" : mode == 1 ? "periodic spectral" : "periodic diff2", gradient, g, cls.size(), (unsigned long long)counts[0],
+                (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3], (unsigned long long)counts[4],
+                (unsigned long long)counts[5], (unsigned long long)counts[6], (unsigned long long)counts[7]);
+    for (size_t i = 0; i < cls.size() && i < 8; ++i)
+        std::printf("PM body %zu class %d %.17e %.17e %.17e %.17e\n", i, int(cls[i]), acc[3 * i], acc[3 * i + 1], acc[3 * i + 2], phi[i]);
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
@@ -279,7 +303,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
                double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint,
-               const NbodyGridSpec* deposit_spec, int sample_op, int poisson_mode) {
+               const NbodyGridSpec* deposit_spec, int sample_op, int poisson_mode, int pm_mode, int pm_gradient) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -353,6 +377,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (deposit_spec) print_deposit(*sim, *deposit_spec);
         if (deposit_spec && sample_op >= 0) print_sample(*sim, *deposit_spec, sample_op);
         if (deposit_spec && poisson_mode >= 0) print_poisson(*sim, *deposit_spec, poisson_mode, double(sim->settings_mut().g));
+        if (deposit_spec && pm_mode >= 0) print_pm(*sim, *deposit_spec, pm_mode, pm_gradient, double(sim->settings_mut().g));
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -403,6 +428,7 @@ int main(int argc, char** argv) {
     bool deposit = false;
     int sample_op = -1;
     int poisson_mode = -1;   // 0 isolated, 1 periodic spectral, 2 periodic diff2
+    int pm_mode = -1, pm_gradient = NBODY_SAMPLE_GRADIENT2;   // --pm: the same three modes, and the gradient
     double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -523,6 +549,19 @@ int main(int argc, char** argv) {
             else if (arg == "diff2") poisson_mode = 2;
             else { usage(); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--pm")) {
+            const std::string arg = next();
+            const size_t c = arg.find(':');
+            if (c == std::string::npos) { usage(); return 2; }
+            const std::string mode = arg.substr(0, c), grad = arg.substr(c + 1);
+            if (mode == "isolated") pm_mode = 0;
+            else if (mode == "spectral") pm_mode = 1;
+            else if (mode == "diff2") pm_mode = 2;
+            else { usage(); return 2; }
+            if (grad == "grad2") pm_gradient = NBODY_SAMPLE_GRADIENT2;
+            else if (grad == "grad4") pm_gradient = NBODY_SAMPLE_GRADIENT4;
+            else { usage(); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -577,7 +616,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--poisson needs --deposit\n");
         return 2;
     }
+    if (pm_mode >= 0 && !deposit) {
+        std::fprintf(stderr, "--pm needs --deposit\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient);
 }

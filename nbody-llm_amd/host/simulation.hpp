@@ -465,6 +465,37 @@ public:
         return nbody_host_grid_poisson(&spec, &ps, mass, phi, cap);
     }
     static int host_poisson_twiddles(int length, double* out) { return nbody_host_poisson_twiddles(length, out); }
+    // particle-mesh field (nbody_pm_field, nbody_pm_field_at): deposit(NBODY_DEPOSIT_MASS), grid_poisson(pm.poisson) and
+    // grid_sample(pm.gradient) composed on the device with the grid never leaving it: acc [n][3] = -grad phi, phi [n] (want_phi),
+    // cls [n] = the gradient sample's classes, counts = the deposit's four then the sample's four; at the bodies, in get_points()
+    // order, or at the n points xyz = {x, y, z}.  Read-only, the handles deposit() takes; the same bytes as host_pm_field
+    // (nbody_host_pm_field; no device).  pm_field_stats: {a call reached the device, the plan it used, grid reads of the gather,
+    // radix sorts enqueued}
+    void pm_field(const NbodyGridSpec& spec, const NbodyPmSpec& pm, std::vector<double>& acc, std::vector<double>& phi, std::vector<uint8_t>& cls,
+                  uint64_t counts[8], bool want_phi = true) {
+        size_t n = 0;
+        check(nbody_count(h_, &n));
+        acc.assign(n * 3, 0.0);
+        phi.assign(want_phi ? n : 0, 0.0);
+        cls.assign(n, 0);
+        check(nbody_pm_field(h_, &spec, &pm, acc.data(), want_phi ? phi.data() : nullptr, cls.data(), n, &n, counts));
+        acc.resize(n * 3);
+        phi.resize(want_phi ? n : 0);
+        cls.resize(n);
+    }
+    void pm_field_at(const NbodyGridSpec& spec, const NbodyPmSpec& pm, const std::vector<double>& xyz, std::vector<double>& acc,
+                     std::vector<double>& phi, std::vector<uint8_t>& cls, uint64_t counts[8], bool want_phi = true) {
+        const size_t n = xyz.size() / 3;
+        acc.assign(n * 3, 0.0);
+        phi.assign(want_phi ? n : 0, 0.0);
+        cls.assign(n, 0);
+        check(nbody_pm_field_at(h_, &spec, &pm, xyz.data(), n, acc.data(), want_phi ? phi.data() : nullptr, cls.data(), counts));
+    }
+    void pm_field_stats(uint64_t out[4]) { check(nbody_pm_field_stats(h_, out)); }
+    static int host_pm_field(const double* body_xyz, const double* body_m, size_t n_bodies, const NbodyGridSpec& spec, const NbodyPmSpec& pm,
+                             const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t counts[8]) {
+        return nbody_host_pm_field(body_xyz, body_m, n_bodies, &spec, &pm, xyz, n_points, acc, phi, cls, counts);
+    }
     // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs
     // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
