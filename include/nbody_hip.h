@@ -1230,8 +1230,9 @@ int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]);
  * not 0; mass or phi NULL; handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without
  * touching a device.
  *   OUT OF SCOPE: real-to-complex transforms (the call does twice the necessary work); axes longer than 4 096;
- * non-power-of-two dimensions; a transformed kernel or a device grid kept between calls (nbody_pm_field below fuses deposit,
- * solve and sample without the host round trips); a 4th-order Green's function; interlacing; multi-rank handles; a PM term in the step kernels. */
+ * non-power-of-two dimensions; a transformed kernel or a device grid kept between calls of nbody_grid_poisson itself
+ * (nbody_pm_field below fuses deposit, solve and sample without the host round trips; mesh gravity keeps the kernel and
+ * steps with the field); a 4th-order Green's function; interlacing; multi-rank handles. */
 #define NBODY_POISSON_SPECTRAL 0   /* periodic: -k^2 of the continuous Laplacian            */
 #define NBODY_POISSON_DIFF2    1   /* periodic: the 7-point Laplacian, the mate of GRADIENT2 */
 #define NBODY_POISSON_MAX_AXIS   4096        /* transform length of an axis (after padding) */
@@ -1303,8 +1304,9 @@ int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]);
  * NBODY_DEPOSIT_MASS; pm NULL; a gradient that is not NBODY_SAMPLE_GRADIENT2 or NBODY_SAMPLE_GRADIENT4; reserved words that
  * are not 0; acc NULL with rows to write; xyz NULL with n_points > 0 (the device call); n_points > 2^31 - 1; handles of a
  * multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
- *   OUT OF SCOPE, in this order: a PM term in the step kernels; a short-range (TreePM) split; a transformed isolated kernel
- * kept between calls; real-to-complex transforms; a world-wide mesh energy; multi-rank handles. */
+ *   OUT OF SCOPE, in this order: a short-range (TreePM) split; real-to-complex transforms; a world-wide mesh energy;
+ * multi-rank handles.  (A PM term in the step is "mesh gravity" below, which also keeps an isolated grid's transformed kernel
+ * between its passes; nbody_pm_field itself makes it at every call, as before.) */
 typedef struct NbodyPmSpec {
     NbodyPoissonSpec poisson;   /* as for nbody_grid_poisson */
     int32_t gradient;           /* NBODY_SAMPLE_GRADIENT2 or NBODY_SAMPLE_GRADIENT4 */
@@ -1321,6 +1323,50 @@ int nbody_host_pm_field(const double* body_xyz, const double* body_m, size_t n_b
                         const double* xyz /* NULL: the bodies themselves */, size_t n_points,
                         double* acc, double* phi, uint8_t* cls, uint64_t counts[8]);
 int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]);
+/* ---- mesh gravity: the particle-mesh field as the self-gravity of the step (no reference counterpart) --------------------
+ * nbody_set_mesh_gravity(h, spec, pm): while set, the self-gravity pass of every step and of nbody_update_forces IS the mesh
+ * field of nbody_pm_field; no pair kernel is launched.  spec == NULL and pm == NULL: off.  NO NEW ARITHMETIC.  THE DEFINITION:
+ * with x the half-drifted, retained positions P of the live bodies and their masses m, widened exactly, and g the handle's g as
+ * it stands at the pass, widened exactly,
+ *     acc_pass[i][c] = F( nbody_host_pm_field(P, m, spec, pm with poisson.g := g).acc[i][c] )
+ * F = one IEEE round-to-nearest-even conversion to the handle's dtype (the identity on NBODY_F64 handles).  pm->poisson.g is
+ * NOT READ by a pass (nbody_get_mesh_gravity returns it as set); g_soft plays no part: the mesh's softening is
+ * pm->poisson.soften.  Bodies off an isolated grid get +0.0, as nbody_pm_field gives them.
+ *   THE STEP is otherwise unchanged: half drift, retain, this pass, then kick_half_drift's arithmetic -- v += a dt; x += (v 0.5)
+ * dt, every product rounded on its own.  With an external field set, acc = acc_pass + s(x), exactly as "external field"
+ * states it.  Tracers get the same mesh field at their own half-drifted, retained positions: nbody_host_pm_field with xyz = the
+ * tracers, rounded by F.  nbody_steps(k) gives the bits of k nbody_step_by calls; nbody_clone carries the setting.
+ *   WHAT DOES NOT CHANGE: a handle that never sets mesh gravity runs the code it ran before; one that sets and clears it with no
+ * pass in between gives the bits of one that never did.  nbody_energy*, nbody_potentials, nbody_field_at, nbody_pm_field and
+ * every diagnostic call stay as they are (all-pairs self-gravity, or the mesh call's own spec).  NbodyStats.steps counts as
+ * before; the interaction counters do not move during mesh passes.
+ *   HOW (csrc/nbody_mesh.cpp, csrc/kernels_mesh.hip).  The handle keeps ONE particle-mesh scratch through its registry, made at
+ * the first pass, remade only when the spec or the bound on the bodies or tracers outgrows it, freed on clear and on destroy.
+ * It holds the Poisson tables, sent once, and on an isolated grid the transformed kernel, which depends on dims, spacing and
+ * soften only (-g is applied where phi is written): made once per spec, so a pass does two 3-D transforms, not three, and the
+ * expression tree of every output is nbody_pm_field's.  A pass is ENQUEUE-ONLY: no synchronisation, no allocation, no
+ * read-back; the live count is read on the device and the launches are sized from the host's bound.  Its last stage is
+ * k_mesh_kick<F, kReach, kScheme>: one lane per body in the shared home-cell order, the stencil set-up and gradient sums of
+ * k_pm_gather, 0.0 - grad rounded once to F into the acc row, and -- inside a step without an external field -- the kick and
+ * half drift of the row; no phi, no f64 rows, no LDS, no floating-point atomics.  Two knobs, which change no result:
+ *     mesh_kick_fuse (default 1)    0: nbody_pm_field's gather to f64 rows, a rounding kernel and the leapfrog's own kick
+ *     mesh_keep_kernel (default 1)  0: the transformed kernel is made at every pass
+ * The deposit_*, sample_sort, poisson_*, pm_share_sort and (with mesh_kick_fuse = 0) pm_gather and sample_pregrad knobs are
+ * honoured.
+ *   nbody_mesh_gravity_stats: out = {passes enqueued, the plan the last pass used as mesh_kick_fuse | mesh_keep_kernel << 1 |
+ * (nbody_pm_field_stats's plan word) << 2, 3-D transforms enqueued in total, allocations of the resident state so far}.  A
+ * DIAGNOSTIC AID for tools/mesh_bench.py and the tests of the plans, NOT A STABLE CONTRACT.
+ *   ACCEPTED on NBODY_BRUTE_FORCE handles with world_size == 1 (NBODY_SHARD_INDEX), the leapfrog, both dtypes and both math modes
+ * (the mesh pass has one arithmetic), with or without tracers and an external field.  REFUSED with NBODY_ERR_INVALID
+ * (nbody_last_error names the call; the handle keeps working): whatever nbody_pm_field refuses in a spec or a PM spec;
+ * NBODY_BARNES_HUT handles (their unsynchronised-step accounting is out of scope); multi-rank and NBODY_SHARD_SPATIAL handles;
+ * exactly one of spec and pm NULL; setting mesh gravity while NBODY_INTEGRATOR_HERMITE4 is selected, and selecting Hermite
+ * while mesh gravity is set.
+ *   OUT OF SCOPE: Barnes-Hut handles under the mesh; TreePM or P3M short-range terms; Hermite; a mesh energy; multi-rank
+ * handles.  NOT TIMED beyond what DESIGN 3.28 records.  Nothing asserts or promises a time. */
+int nbody_set_mesh_gravity(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm);   /* spec == NULL and pm == NULL: off */
+int nbody_get_mesh_gravity(const NbodyHandle* h, NbodyGridSpec* spec, NbodyPmSpec* pm, int* on);
+int nbody_mesh_gravity_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- pair search: how the fixed-radius calls find their pairs (no reference counterpart) --------------------------------
  * nbody_fof_labels, nbody_fof_groups, nbody_contacts, nbody_merge_contacts, nbody_neighbors_within, nbody_density,
  * nbody_density_center and nbody_pair_counts ask a FIXED-RADIUS question: only bodies closer than the linking length, the
@@ -1384,7 +1430,8 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
  * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result), sample_sort, sample_pregrad (nbody_grid_sample and
  * nbody_grid_sample_at: the plan, defaults 1, 0; they change no result), poisson_lds, poisson_tile (nbody_grid_poisson: the plan,
  * defaults 1, 16; they change no result), pm_gather, pm_share_sort (nbody_pm_field and nbody_pm_field_at: the plan, defaults 1, 1; they
- * change no result); the environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
+ * change no result), mesh_kick_fuse, mesh_keep_kernel (mesh gravity: the plan, defaults 1, 1; they change no result); the
+ * environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,
  * bh_walk_debug and sym_debug select experimental walks and in-kernel stamps that only the tuning build carries

@@ -114,6 +114,7 @@ DECLARED_SYMBOLS = [
     "nbody_grid_sample", "nbody_grid_sample_at", "nbody_host_grid_sample", "nbody_grid_sample_stats",
     "nbody_grid_poisson", "nbody_host_grid_poisson", "nbody_host_poisson_twiddles", "nbody_grid_poisson_stats",
     "nbody_pm_field", "nbody_pm_field_at", "nbody_host_pm_field", "nbody_pm_field_stats",
+    "nbody_set_mesh_gravity", "nbody_get_mesh_gravity", "nbody_mesh_gravity_stats",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
 
@@ -353,6 +354,9 @@ _sig("nbody_pm_field_at", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C
 _sig("nbody_host_pm_field", _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.c_void_p, _sz, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p)
 _sig("nbody_pm_field_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_set_mesh_gravity", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec))
+_sig("nbody_get_mesh_gravity", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.POINTER(C.c_int))
+_sig("nbody_mesh_gravity_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_set_pair_search", _i, _H, _i)
 _sig("nbody_get_pair_search", _i, _H, C.POINTER(_i))
 _sig("nbody_pair_search_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -541,6 +545,31 @@ def pm_spec(g, gradient=SAMPLE_GRADIENT2, green=POISSON_SPECTRAL, soften=0.0, de
     """An NbodyPmSpec from plain values: the constants of grid_poisson and SAMPLE_GRADIENT2 or SAMPLE_GRADIENT4."""
     ps = NbodyPoissonSpec(float(g), float(soften), int(green), int(deconvolve), (C.c_int32 * 2)(0, 0))
     return NbodyPmSpec(ps, int(gradient), (C.c_int32 * 3)(0, 0, 0))
+
+
+def mesh_gravity_specs(value) -> tuple[GridSpec, NbodyPmSpec]:
+    """The (GridSpec, NbodyPmSpec) pair Simulation.mesh_gravity takes, from such a pair or from a dict of pm_field's keywords.  No
+    device needed; what the pair must satisfy is checked by nbody_set_mesh_gravity."""
+    if isinstance(value, dict):
+        known = {"origin", "spacing", "dims", "g", "scheme", "gradient", "periodic", "green", "soften", "deconvolve", "project_axis"}
+        extra = set(value) - known
+        if extra:
+            raise ValueError(f"mesh_gravity: unknown keys {sorted(extra)}")
+        missing = {"origin", "spacing", "dims"} - set(value)
+        if missing:
+            raise ValueError(f"mesh_gravity: missing keys {sorted(missing)}")
+        spec = grid_spec(value["origin"], value["spacing"], value["dims"], value.get("scheme", DEPOSIT_CIC), DEPOSIT_MASS,
+                         value.get("periodic", False), value.get("project_axis", -1))
+        pm = pm_spec(value.get("g", 1.0), value.get("gradient", SAMPLE_GRADIENT2), value.get("green", POISSON_SPECTRAL),
+                     value.get("soften", 0.0), value.get("deconvolve", 0))
+        return spec, pm
+    try:
+        spec, pm = value
+    except (TypeError, ValueError):
+        raise TypeError("mesh_gravity: a dict, a (GridSpec, NbodyPmSpec) pair or None") from None
+    if not isinstance(spec, GridSpec) or not isinstance(pm, NbodyPmSpec):
+        raise TypeError("mesh_gravity: a dict, a (GridSpec, NbodyPmSpec) pair or None")
+    return spec, pm
 
 
 def host_pm_field(bodies, mass, origin, spacing, dims, g, scheme=DEPOSIT_CIC, gradient=SAMPLE_GRADIENT2, periodic=False, green=POISSON_SPECTRAL,
@@ -1139,6 +1168,32 @@ class Simulation:
         the grid reads of its gather, the radix sorts it enqueued} (nbody_pm_field_stats)."""
         out = (C.c_uint64 * 4)()
         self._check(lib.nbody_pm_field_stats(self._h, out))
+        return np.array(out[:], np.uint64)
+
+    # -- mesh gravity (nbody_set_mesh_gravity): the particle-mesh field as the self-gravity of every step and of update_forces
+    @property
+    def mesh_gravity(self):
+        """None while mesh gravity is off, else the (GridSpec, NbodyPmSpec) pair as set.  Set it from such a pair or from a dict of
+        pm_field's keywords (origin, spacing, dims and, optionally, g, scheme, gradient, periodic, green, soften, deconvolve,
+        project_axis); None clears it.  While set, the self-gravity pass of steps and of update_forces is the mesh field of
+        pm_field with g := the handle's g, rounded once to the handle's dtype; no pair kernel runs.  clone() carries it."""
+        spec, pm, on = GridSpec(), NbodyPmSpec(), C.c_int(0)
+        self._check(lib.nbody_get_mesh_gravity(self._h, C.byref(spec), C.byref(pm), C.byref(on)))
+        return (spec, pm) if on.value else None
+
+    @mesh_gravity.setter
+    def mesh_gravity(self, value):
+        if value is None:
+            self._check(lib.nbody_set_mesh_gravity(self._h, None, None))
+            return
+        spec, pm = mesh_gravity_specs(value)
+        self._check(lib.nbody_set_mesh_gravity(self._h, C.byref(spec), C.byref(pm)))
+
+    def mesh_gravity_stats(self) -> np.ndarray:
+        """[4] uint64: {mesh passes enqueued, the plan the last one used (mesh_kick_fuse | mesh_keep_kernel << 1 | pm_field_stats's
+        plan word << 2), 3-D transforms enqueued in total, allocations of the resident mesh state} (nbody_mesh_gravity_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_mesh_gravity_stats(self._h, out))
         return np.array(out[:], np.uint64)
 
     # -- pair search (nbody_set_pair_search): all pairs, or the 27 cells around a body's own; the results are the same bits

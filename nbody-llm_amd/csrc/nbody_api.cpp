@@ -16,6 +16,7 @@
 #include "nbody_paircount.h"
 #include "nbody_deposit.h"
 #include "nbody_pm.h"
+#include "nbody_mesh.h"
 #include "nbody_poisson.h"
 #include "nbody_sample.h"
 #include "nbody_cells.h"
@@ -96,6 +97,7 @@ void free_all(NbodyHandle* h) {
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     for (auto& ev : h->ev_pending) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto& ev : h->ev_free) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+    nbody::mesh::destroy(h);
     nbody::let::destroy(h);   // (the states, their events and host octrees; their device memory is the registry's like everything else)
     nbody32::destroy(h);
     nbody64::destroy(h);
@@ -243,6 +245,7 @@ int nbody_clone(const NbodyHandle* src, NbodyHandle** out) {
     if (rc) return rc;
     h->tune = src->tune;   // (the knobs shape the fast passes' sums: a clone continues bit for bit like its source)
     h->ext = src->ext;     // (and the external field)
+    if (nbody::mesh::on(src)) nbody::mesh::set(h, src->mesh.spec, src->mesh.pm);   // (and mesh gravity: the clone makes its own resident state)
     if (src->f64) rc = nbody64::clone_state(s, h);
     else {
         rc = nbody32::clone_state(s, h);
@@ -832,6 +835,44 @@ int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]) {
     return NBODY_OK;
 }
 
+// ---- mesh gravity (nbody_mesh.cpp): a setting of the handle that its force passes read
+int nbody_set_mesh_gravity(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = use_device(h);
+    if (rc) return rc;
+    const std::string call = "nbody_set_mesh_gravity: ";
+    if (const char* why = nbody::mesh::refusal(h)) return fail(h, NBODY_ERR_INVALID, call + why);
+    if (!spec && !pm) return nbody::mesh::clear(h);
+    if (!spec || !pm) return fail(h, NBODY_ERR_INVALID, call + "spec and pm must both be given, or both be NULL (off)");
+    const std::string why = nbody::pm::call_refusal(spec, pm);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, call + why);
+    if (h->f64 && nbody64::get_integrator(h) == NBODY_INTEGRATOR_HERMITE4)
+        return fail(h, NBODY_ERR_INVALID, call + "the handle runs the Hermite integrator, which would need the mesh field's jerk (out of scope)");
+    nbody::mesh::set(h, *spec, *pm);
+    return NBODY_OK;
+}
+
+int nbody_get_mesh_gravity(const NbodyHandle* h, NbodyGridSpec* spec, NbodyPmSpec* pm, int* on) {
+    if (!h) return NBODY_ERR_INVALID;
+    NbodyHandle* hh = const_cast<NbodyHandle*>(h);
+    if (const char* why = nbody::mesh::refusal(h)) return fail(hh, NBODY_ERR_INVALID, std::string("nbody_get_mesh_gravity: ") + why);
+    if (on) *on = h->mesh.on ? 1 : 0;
+    if (h->mesh.on && spec) *spec = h->mesh.spec;
+    if (h->mesh.on && pm) *pm = h->mesh.pm;
+    return NBODY_OK;
+}
+
+int nbody_mesh_gravity_stats(NbodyHandle* h, uint64_t out[4]) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (const char* why = nbody::mesh::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_mesh_gravity_stats: ") + why);
+    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_mesh_gravity_stats: out is NULL");
+    out[0] = h->mesh.passes;
+    out[1] = h->mesh.last_plan;
+    out[2] = h->mesh.transforms;
+    out[3] = h->mesh.allocations;
+    return NBODY_OK;
+}
+
 // ---- pair search (nbody_cells.cpp): a setting of the handle that the eight fixed-radius calls above read, and their record
 namespace {
 int search_refusal(NbodyHandle* h, const char* call) {
@@ -1136,6 +1177,8 @@ int nbody_set_integrator(NbodyHandle* h, int integrator) {
                         : h->cfg.world_size != 1            ? "handles of a multi-rank world step with the leapfrog only"
                                                             : nullptr;
         if (why) return fail(h, NBODY_ERR_INVALID, std::string("nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): ") + why + " (brute-force NBODY_F64 handles with world_size == 1 take it)");
+        if (nbody::mesh::on(h))
+            return fail(h, NBODY_ERR_INVALID, "nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): mesh gravity is set, and the Hermite step would need its jerk (nbody_set_mesh_gravity with NULL, NULL removes it)");
         if (nbody::ext::on(h))
             return fail(h, NBODY_ERR_INVALID, "nbody_set_integrator(NBODY_INTEGRATOR_HERMITE4): an external field is set, and the Hermite step would need its jerk (nbody_set_external_field with n == 0 removes it)");
     }
@@ -1364,6 +1407,7 @@ const Knob kKnobs[] = {
     {"sample_sort", &nbody::Tuning::sample_sort, false}, {"sample_pregrad", &nbody::Tuning::sample_pregrad, false},
     {"poisson_lds", &nbody::Tuning::poisson_lds, false}, {"poisson_tile", &nbody::Tuning::poisson_tile, false},
     {"pm_gather", &nbody::Tuning::pm_gather, false}, {"pm_share_sort", &nbody::Tuning::pm_share_sort, false},
+    {"mesh_kick_fuse", &nbody::Tuning::mesh_kick_fuse, false}, {"mesh_keep_kernel", &nbody::Tuning::mesh_keep_kernel, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},
     {"sym_debug", &nbody::Tuning::sym_debug, true},

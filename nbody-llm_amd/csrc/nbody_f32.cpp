@@ -10,6 +10,7 @@
 #include "nbody_pot.h"
 #include "nbody_tracer.h"
 #include "nbody_external.h"
+#include "nbody_mesh.h"
 #include "nbody_pairs.h"
 
 #include <algorithm>
@@ -599,8 +600,20 @@ int partials_wait(NbodyHandle* h) {
     return NBODY_OK;
 }
 
+// mesh gravity: the pass is the mesh field for bodies and tracers, with the step's kicks when it asked for them (as the fused
+// tail takes them); no pair kernel runs
+int mesh_forces(NbodyHandle* h) {
+    State& s = *h->f32;
+    int rc = exchange_wait(h);
+    if (rc) return rc;
+    rc = nbody::mesh::pass<float>(h, s.sh, s.n_local, double(s.g), s.kick_pending ? &s.kick_dt : nullptr, s.tracer_kick ? &s.kick_dt : nullptr);
+    if (!rc) s.kick_pending = false;
+    return rc;
+}
+
 // everything of the force pass that needs no other GPU's partial sums
 int forces_begin(NbodyHandle* h) {
+    if (nbody::mesh::on(h)) return mesh_forces(h);
     return h->cfg.method == NBODY_BARNES_HUT ? bh_forces(h) : bf_forces(h);
 }
 
@@ -891,7 +904,7 @@ int step_forces(NbodyHandle* h, float dt) {
     const bool fuse = !nbody::ext::on(h);
     s.kick_pending = fuse;   // a force pass that ends in a plane reduction applies the kick itself
     s.kick_dt = dt;
-    if (nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE) {
+    if (nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE && !nbody::mesh::on(h)) {   // (mesh gravity: inside the pass, mesh_forces)
         // the tracers' force pass over the half-drifted, retained bodies, with the tracers' kick + half drift.  It reads the
         // bodies' positions and writes tracer state only, so it goes BEFORE the body pass, whose tail may move the bodies
         int rc = nbody::tracer::forces(h, fuse ? &s.kick_dt : nullptr);
@@ -964,7 +977,7 @@ int update_forces(NbodyHandle* h) {
     rc = exchange_begin(h);
     if (rc) return rc;
     rc = forces(h);
-    if (!rc && nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE) rc = nbody::tracer::forces(h, nullptr);   // (Barnes-Hut: inside the pass, walk_tree)
+    if (!rc && nbody::tracer::on(h) && h->cfg.method == NBODY_BRUTE_FORCE && !nbody::mesh::on(h)) rc = nbody::tracer::forces(h, nullptr);   // (Barnes-Hut: inside the pass, walk_tree; mesh gravity: mesh_forces)
     if (!rc && s.last_step_async) {
         s.last_step_async = false;
         rc = resolve_async(h);              // (a force pass outside a step is confirmed at once)

@@ -10,6 +10,7 @@
 #include "kernels_f64.h"
 #include "kernels_hermite.h"
 #include "nbody_external.h"
+#include "nbody_mesh.h"
 #include "nbody_pairs.h"
 #include "nbody_pot.h"
 
@@ -378,7 +379,17 @@ int bh_forces(NbodyHandle* h, State& s) {
     return strict_walk(h, s, t, s.tree.host.max_depth + 2);   // the tree's depth
 }
 
-int forces(NbodyHandle* h, State& s) { return h->cfg.method == NBODY_BARNES_HUT ? bh_forces(h, s) : bf_forces(h, s); }
+// mesh gravity: the pass is the mesh field, with the step's kick when there is one; no pair kernel runs
+int mesh_forces(NbodyHandle* h, State& s) {
+    const int rc = nbody::mesh::pass<double>(h, s.sh, s.n_local, s.g, s.kick_dt, nullptr);
+    if (!rc && s.kick_dt) s.kicked = 1;
+    return rc;
+}
+
+int forces(NbodyHandle* h, State& s) {
+    if (nbody::mesh::on(h)) return mesh_forces(h, s);
+    return h->cfg.method == NBODY_BARNES_HUT ? bh_forces(h, s) : bf_forces(h, s);
+}
 
 // index-block shards: the once-per-step exchange, in place, on the handle's stream
 int exchange(NbodyHandle* h, State& s) {

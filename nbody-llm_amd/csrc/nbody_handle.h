@@ -581,6 +581,18 @@ struct ExternalField {
     NbodyExternalComponent given[NBODY_EXTERNAL_MAX] = {};
 };
 
+// nbody_set_mesh_gravity (nbody_mesh.cpp): the grid and the PM spec as given; on == false (never set, or cleared) keeps every
+// step path as it was.  res: what stays on the device between passes, made by the first pass, freed on clear and on destroy.
+namespace nbody { namespace mesh { struct Resident; } }
+struct MeshGravity {
+    bool on = false;
+    NbodyGridSpec spec{};
+    NbodyPmSpec pm{};
+    nbody::mesh::Resident* res = nullptr;
+    // nbody_mesh_gravity_stats: passes enqueued, the plan the last one used, 3-D transforms enqueued, allocations of the resident state
+    uint64_t passes = 0, last_plan = 0, transforms = 0, allocations = 0;
+};
+
 // nbody_set_pair_search: how the fixed-radius calls find their pairs, and what the last of them left for
 // nbody_pair_search_stats (nbody_cells.h).  Nothing else reads it.
 struct PairSearch {
@@ -622,6 +634,7 @@ struct NbodyHandle {
     FieldBufs field;
     TracerState tr;
     ExternalField ext;
+    MeshGravity mesh;
     PairSearch search;
     uint64_t deposit_last[4] = {0, 0, 0, 0};   // nbody_deposit_stats: {a call reached the device, its plan, terms on the grid, global atomics}
     uint64_t poisson_last[4] = {0, 0, 0, 0};   // nbody_grid_poisson_stats: {a call reached the device, the plan it used, butterfly launches, complex points transformed}

@@ -13,31 +13,18 @@ namespace nbody { namespace pm {
 
 namespace {
 
-// what a call holds on the host until its last synchronisation (the tables are read by copies that are only enqueued)
-struct Call {
-    deposit::Grid g;
-    poisson::Shape shape;
-    poisson::Tables tables;
-    Plans plans;
-    bool deconvolve;
-    int op;
-    Call(const NbodyGridSpec& spec, const NbodyPmSpec& pm, bool bodies)
-        : g(deposit::grid_of(spec)), shape(poisson::shape_of(spec)), tables(poisson::tables_of(spec, pm.poisson, shape)),
-          plans(make_plans(pm.gradient, deposit::cells_of(g), bodies)), deconvolve(shape.periodic && pm.poisson.deconvolve > 0), op(pm.gradient) {}
-};
-
 // what one pass over rows brings down
 struct Down {
     deposit::Words dep{};
     sample::Words rows{}, value{};
 };
 
-// The deposit of the n_upper rows of sh and the solve, enqueued: w.smp.grid (the deposit's sums, the Poisson stage's real) holds
-// phi, and under sample_pregrad the difference grids follow.  ordered_rows: the bodies in home-cell order, made already, or
-// null.  sort_failed: a rocPRIM call could not be enqueued.
+}  // namespace
+
+// (the contracts of enqueue_grid and enqueue_rows are nbody_pm.h's)
 template <class F>
 hipError_t enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const Call& c,
-                        const Scratch& w, const int* ordered_rows, bool* sort_failed, uint64_t* sorts) {
+                        const Scratch& w, const int* ordered_rows, bool* sort_failed, uint64_t* sorts, int held, uint64_t* transforms) {
     const hipStream_t s = h->stream;
     if (n_upper) {
         deposit::launch_q<F>(s, sh, int(n_upper), c.g, NBODY_DEPOSIT_MASS, w.dep);
@@ -51,7 +38,9 @@ hipError_t enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, con
         (void)hipMemsetAsync(w.dep.acc, 0, deposit::cells_of(c.g) * sizeof(long long), s);
     }
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = poisson::enqueue(h, spec, pm.poisson, c.shape, c.tables, c.plans.poi, w.poi, nullptr, nullptr);
+    int made = 0;
+    if (e == hipSuccess) e = poisson::enqueue(h, spec, pm.poisson, c.shape, c.tables, c.plans.poi, w.poi, nullptr, &made, held);
+    if (e == hipSuccess && transforms) *transforms += uint64_t(made);
     if (e == hipSuccess && c.plans.grad.pregrad) {
         sample::launch_diff(s, c.g, c.op, w.smp);
         e = hipGetLastError();
@@ -59,8 +48,6 @@ hipError_t enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, con
     return e;
 }
 
-// One pass over the n rows of w.smp.xyz (count: the live rows' word on the device, or null: all n) against the resident grid,
-// enqueued: w.smp.out = acc, w.phi (with_phi), w.smp.cls.  ordered: w.smp.rows + n holds these rows' order already.
 int enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, uint64_t* sorts) {
     const hipStream_t s = h->stream;
     const Plans& p = c.plans;
@@ -83,6 +70,8 @@ int enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool
     else (void)hipMemsetAsync(v.words, 0, sizeof(sample::Words), s);
     return 0;
 }
+
+namespace {
 
 // the copies of a pass's first `copy` rows and of its words, enqueued (e: what went before; nothing more once it failed)
 hipError_t enqueue_down(NbodyHandle* h, hipError_t e, const Call& c, const Scratch& w, size_t copy, double* acc, double* phi, uint8_t* cls,
@@ -199,6 +188,10 @@ int at_points(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGr
     return NBODY_OK;
 }
 
+template hipError_t enqueue_grid<float>(NbodyHandle*, const ShardT<float>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, const Call&, const Scratch&,
+                                        const int*, bool*, uint64_t*, int, uint64_t*);
+template hipError_t enqueue_grid<double>(NbodyHandle*, const ShardT<double>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, const Call&, const Scratch&,
+                                         const int*, bool*, uint64_t*, int, uint64_t*);
 template int at_bodies<float>(NbodyHandle*, const ShardT<float>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, double*, double*, uint8_t*,
                               size_t, size_t*, uint64_t*);
 template int at_bodies<double>(NbodyHandle*, const ShardT<double>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, double*, double*, uint8_t*,

@@ -20,4 +20,31 @@ template <class F>
 int at_points(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const double* xyz,
               size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t* counts);
 
+// ---- the stages of a call, for a caller that keeps the scratch between calls (nbody_mesh.cpp)
+
+// what a call holds on the host until its last synchronisation (the tables are read by copies that are only enqueued)
+struct Call {
+    deposit::Grid g;
+    poisson::Shape shape;
+    poisson::Tables tables;
+    Plans plans;
+    bool deconvolve;
+    int op;
+    Call(const NbodyGridSpec& spec, const NbodyPmSpec& pm, bool bodies)
+        : g(deposit::grid_of(spec)), shape(poisson::shape_of(spec)), tables(poisson::tables_of(spec, pm.poisson, shape)),
+          plans(make_plans(pm.gradient, deposit::cells_of(g), bodies)), deconvolve(shape.periodic && pm.poisson.deconvolve > 0), op(pm.gradient) {}
+};
+
+// The deposit of the n_upper rows of sh and the solve, enqueued: w.smp.grid (the deposit's sums, the Poisson stage's real) holds
+// phi, and under sample_pregrad the difference grids follow.  ordered_rows: the bodies in home-cell order, made already, or
+// null.  sort_failed: a rocPRIM call could not be enqueued.  held: poisson::enqueue's; transforms (may be null): += the 3-D
+// transforms enqueued.
+template <class F>
+hipError_t enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const Call& c,
+                        const Scratch& w, const int* ordered_rows, bool* sort_failed, uint64_t* sorts, int held = 0, uint64_t* transforms = nullptr);
+
+// One pass over the n rows of w.smp.xyz (count: the live rows' word on the device, or null: all n) against the resident grid,
+// enqueued: w.smp.out = acc, w.phi (with_phi), w.smp.cls.  ordered: w.smp.rows + n holds these rows' order already.
+int enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, uint64_t* sorts);
+
 }}  // namespace nbody::pm

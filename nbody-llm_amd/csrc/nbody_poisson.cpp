@@ -17,10 +17,10 @@ hipError_t upload(NbodyHandle* h, T* dst, const std::vector<T>& src) {
 }  // namespace
 
 hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
-                   const Scratch& w, int* launches_out, int* transforms_out) {
+                   const Scratch& w, int* launches_out, int* transforms_out, int held) {
     const bool deconvolve = sh.periodic && ps.deconvolve > 0;
     hipError_t e = hipSuccess;
-    for (int c = 0; c < 3 && e == hipSuccess; ++c) {
+    for (int c = 0; c < 3 && e == hipSuccess && !(held & kHeldTables); ++c) {
         e = upload(h, w.tw[c], t.tw[c]);
         if (e == hipSuccess) e = upload(h, w.K[c], t.K[c]);
         if (e == hipSuccess) e = upload(h, w.D[c], t.D[c]);
@@ -32,10 +32,12 @@ hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoisson
         if (sh.periodic) {
             launch_green(h->stream, sh, t.c, deconvolve, w);
         } else {
-            launch_kernel(h->stream, sh, spec.spacing, ps.soften, w);
-            launches += launch_transform(h->stream, sh, plan, w.k, w, false);
+            if (!(held & kHeldKernel)) {
+                launch_kernel(h->stream, sh, spec.spacing, ps.soften, w);
+                launches += launch_transform(h->stream, sh, plan, w.k, w, false);
+                transforms = 3;
+            }
             launch_mul(h->stream, sh, w);
-            transforms = 3;
         }
         launches += launch_transform(h->stream, sh, plan, w.x, w, true);
         launch_store(h->stream, sh, ps.g, t.inv_points, w);

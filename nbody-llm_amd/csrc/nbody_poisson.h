@@ -16,7 +16,11 @@ int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps,
 // on their way up -- t outlives the caller's synchronisation -- and every launch from k_poisson_load to k_poisson_store, so
 // that w.real, which held the mass, holds phi.  Nothing is waited for and no record is written.  launches_out and
 // transforms_out (may be null): the butterfly launches made and the 3-D transforms (2 periodic, 3 isolated).
+// held (nbody_mesh.cpp, whose scratch outlives the call): what w holds already and is neither sent nor made again -- the tables
+// (kHeldTables), and on an isolated grid the transformed kernel in w.k (kHeldKernel: two transforms then, every output's
+// expression tree as it was).
+enum { kHeldTables = 1, kHeldKernel = 2 };
 hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
-                   const Scratch& w, int* launches_out, int* transforms_out);
+                   const Scratch& w, int* launches_out, int* transforms_out, int held = 0);
 
 }}  // namespace nbody::poisson

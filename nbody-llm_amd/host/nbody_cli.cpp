@@ -41,6 +41,9 @@
 // deposit with wrapped indices): one line with the mode and the grid, one with the sum of phi and its lowest cell.  --pm
 // isolated|spectral|diff2:grad2|grad4 (with --deposit only, N a power of two) is the three of them in one call (nbody_pm_field):
 // one line with the mode, the gradient and the eight counts, then the first eight bodies' acc and phi with 17 significant digits.
+// --mesh isolated|spectral|diff2:grad2|grad4 (with --deposit only, N a power of two) steps under mesh gravity on that grid
+// (nbody_set_mesh_gravity): one line with the mode, the gradient, the plan and the words of nbody_mesh_gravity_stats, then the
+// first eight bodies' position and acceleration.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -73,6 +76,7 @@ static void usage() {
                  "                 [--deposit ngp|cic|tsc:N:HALF]   (the mass of the final state on the N^3 cells of [-HALF, HALF)^3)\n"
                  "                 [--sample value|grad2|grad4]   (with --deposit: that grid read back at the bodies, its value or its gradient)\n"
                  "                 [--pm isolated|spectral|diff2:grad2|grad4]   (with --deposit, N a power of two: the mesh acceleration and potential at the bodies in one call)\n"
+                 "                 [--mesh isolated|spectral|diff2:grad2|grad4]   (with --deposit, N a power of two: the steps run under mesh gravity on that grid, no pair kernel)\n"
                  "                 [--poisson isolated|spectral|diff2]   (with --deposit, N a power of two: the potential of that mass grid, zero-padded or periodic)\n"
                  "                 [--pair-search all|cells]  (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
 }
@@ -296,6 +300,29 @@ static void print_pm(Sim& sim, NbodyGridSpec spec, int mode, int gradient, doubl
         std::printf("PM body %zu class %d %.17e %.17e %.17e %.17e\n", i, int(cls[i]), acc[3 * i], acc[3 * i + 1], acc[3 * i + 2], phi[i]);
 }
 
+// --mesh: the grid of --deposit and the mode as the (spec, PM spec) pair of nbody_set_mesh_gravity (pm.poisson.g is not read by a pass)
+static NbodyPmSpec mesh_specs(NbodyGridSpec* spec, int mode, int gradient) {
+    spec->periodic = mode > 0;
+    NbodyPmSpec pm{};
+    pm.poisson.g = 1.0;
+    pm.poisson.green = mode == 2 ? NBODY_POISSON_DIFF2 : NBODY_POISSON_SPECTRAL;
+    pm.gradient = gradient;
+    return pm;
+}
+
+// the lines of --mesh: the plan and the words of nbody_mesh_gravity_stats, and the first bodies of the final state
+template <class Sim>
+static void print_mesh(Sim& sim, int mode, int gradient) {
+    uint64_t ms[4] = {0, 0, 0, 0};
+    sim.mesh_gravity_stats(ms);
+    std::printf("MESH: %s gradient %d plan %llu passes %llu transforms %llu allocations %llu\n", mode == 0 ? "isolated" : mode == 1 ? "spectral" : "diff2",
+                gradient, (unsigned long long)ms[1], (unsigned long long)ms[0], (unsigned long long)ms[2], (unsigned long long)ms[3]);
+    const auto& pts = sim.get_points();
+    for (size_t i = 0; i < pts.size() && i < 8; ++i)
+        std::printf("MESH body %zu %.17e %.17e %.17e %.17e %.17e %.17e\n", i, double(pts[i].position[0]), double(pts[i].position[1]),
+                    double(pts[i].position[2]), double(pts[i].acceleration[0]), double(pts[i].acceleration[1]), double(pts[i].acceleration[2]));
+}
+
 template <class F>
 static int run(const std::string& method, const std::string& ic, const std::string& math, const std::string& tree,
                const std::string& leaf, size_t threads, size_t num_points, size_t steps, double dt, double g_soft, double theta2,
@@ -303,7 +330,8 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                double block_eta, int block_levels, size_t n_tracers, const std::vector<NbodyExternalComponent>& external,
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
                double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint,
-               const NbodyGridSpec* deposit_spec, int sample_op, int poisson_mode, int pm_mode, int pm_gradient) {
+               const NbodyGridSpec* deposit_spec, int sample_op, int poisson_mode, int pm_mode, int pm_gradient, int mesh_mode,
+               int mesh_gradient) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -336,6 +364,11 @@ static int run(const std::string& method, const std::string& ic, const std::stri
             sim->set_tracers(tr);
         }
         if (!external.empty()) sim->set_external_field(external);   // (refused where it does not apply: nbody_hip.h)
+        if (deposit_spec && mesh_mode >= 0) {   // (refused where it does not apply: nbody_hip.h)
+            NbodyGridSpec spec = *deposit_spec;
+            const NbodyPmSpec pm = mesh_specs(&spec, mesh_mode, mesh_gradient);
+            sim->set_mesh_gravity(spec, pm);
+        }
         std::printf("Running simulation without rendering...\n");  // main.rs:111
         sim->init();
         const double ext_before = external.empty() ? 0.0 : sim->external_energy();
@@ -378,6 +411,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (deposit_spec && sample_op >= 0) print_sample(*sim, *deposit_spec, sample_op);
         if (deposit_spec && poisson_mode >= 0) print_poisson(*sim, *deposit_spec, poisson_mode, double(sim->settings_mut().g));
         if (deposit_spec && pm_mode >= 0) print_pm(*sim, *deposit_spec, pm_mode, pm_gradient, double(sim->settings_mut().g));
+        if (deposit_spec && mesh_mode >= 0) print_mesh(*sim, mesh_mode, mesh_gradient);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
             sim->pair_search_stats(ps);
@@ -429,6 +463,7 @@ int main(int argc, char** argv) {
     int sample_op = -1;
     int poisson_mode = -1;   // 0 isolated, 1 periodic spectral, 2 periodic diff2
     int pm_mode = -1, pm_gradient = NBODY_SAMPLE_GRADIENT2;   // --pm: the same three modes, and the gradient
+    int mesh_mode = -1, mesh_gradient = NBODY_SAMPLE_GRADIENT2;   // --mesh: the same again, as the step's self-gravity
     double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -562,6 +597,19 @@ int main(int argc, char** argv) {
             else if (grad == "grad4") pm_gradient = NBODY_SAMPLE_GRADIENT4;
             else { usage(); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--mesh")) {
+            const std::string arg = next();
+            const size_t c = arg.find(':');
+            if (c == std::string::npos) { usage(); return 2; }
+            const std::string mode = arg.substr(0, c), grad = arg.substr(c + 1);
+            if (mode == "isolated") mesh_mode = 0;
+            else if (mode == "spectral") mesh_mode = 1;
+            else if (mode == "diff2") mesh_mode = 2;
+            else { usage(); return 2; }
+            if (grad == "grad2") mesh_gradient = NBODY_SAMPLE_GRADIENT2;
+            else if (grad == "grad4") mesh_gradient = NBODY_SAMPLE_GRADIENT4;
+            else { usage(); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--density")) {
             char* end = nullptr;
             const char* arg = next();
@@ -620,7 +668,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--pm needs --deposit\n");
         return 2;
     }
+    if (mesh_mode >= 0 && !deposit) {
+        std::fprintf(stderr, "--mesh needs --deposit\n");
+        return 2;
+    }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient, mesh_mode, mesh_gradient);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient, mesh_mode, mesh_gradient);
 }

@@ -222,6 +222,18 @@ public:
         out.resize(n);
         return out;
     }
+    // mesh gravity (nbody_set_mesh_gravity): while set, the self-gravity pass of every step and of update_forces is the mesh field
+    // of pm_field with g := the handle's g, rounded once to the handle's dtype; clear_mesh_gravity switches it off.  Brute-force
+    // leapfrog handles of a one-rank world, every other handle throws NBODY_ERR_INVALID.  mesh_gravity: false while it is off.
+    // mesh_gravity_stats: {passes enqueued, the plan the last one used, 3-D transforms enqueued, allocations of the resident state}
+    void set_mesh_gravity(const NbodyGridSpec& spec, const NbodyPmSpec& pm) { check(nbody_set_mesh_gravity(h_, &spec, &pm)); }
+    void clear_mesh_gravity() { check(nbody_set_mesh_gravity(h_, nullptr, nullptr)); }
+    bool mesh_gravity(NbodyGridSpec* spec, NbodyPmSpec* pm) const {
+        int on = 0;
+        check(nbody_get_mesh_gravity(h_, spec, pm, &on));
+        return on != 0;
+    }
+    void mesh_gravity_stats(uint64_t out[4]) { check(nbody_mesh_gravity_stats(h_, out)); }
     std::vector<double> external_potentials() {   // phi_ext per body, in get_points() order, f64
         size_t n = 0;
         check(nbody_count(h_, &n));
