@@ -3,9 +3,10 @@
 // kernels_sample.hip's launches as they stand; what is new is
 //
 //   k_mesh_kick<F, kReach, kScheme>  one lane per place of the home-cell order (or per row, unsorted).  The stencil set-up
-//                   (sample_device.h LaneStencil) and the three gradient sums (gradient_component<K>) are the ones k_pm_gather
-//                   calls, so every component is that kernel's expression tree.  No phi sum, no class, no count and no f64 row:
-//                   the lane forms 0.0 - grad, rounds it ONCE to F and stores {ax, ay, az, 0} in the shard's acc row; with a
+//                   and the gradient are sample_device.h's LaneStencil and lane_gradient: the gradient_component<K> calls of
+//                   k_sample and k_pm_gather, so every component is those kernels' expression tree.  No phi sum, no class, no
+//                   count and no f64 row: the lane forms 0.0 - grad, rounds it ONCE to F and stores {ax, ay, az, 0} in the
+//                   shard's acc row; with a
 //                   kick it then applies real.h's kick_half_drift to its own row.  A lane touches its own row only, the grid is
 //                   read-only here, so the order of the lanes changes nothing.  No LDS, no floating-point atomics, no lane waits
 //                   for another.  256 lanes a block, as the gathers: neighbours in home-cell order read neighbouring cells.
@@ -27,14 +28,9 @@ __global__ __launch_bounds__(kSampleBlock) void k_mesh_kick(const double* __rest
     constexpr int kCnt = kScheme + 1;
     sample::LaneStencil<kCnt> lane;
     lane.set_up(xyz, count, n, g, kReach, rows, blockIdx.x * kSampleBlock + threadIdx.x);
-    unsigned long long reads = 0;   // (gradient_component counts them; nobody reads the count here)
-    double grad[3] = {0.0, 0.0, 0.0};   // (the component along the ignored axis stays +0.0 and reads nothing)
-    if (g.axis != 0)
-        grad[0] = sample::gradient_component<0, kCnt, kReach>(g, G, lane.active, lane.f0, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, den, reads);
-    if (g.axis != 1)
-        grad[1] = sample::gradient_component<1, kCnt, kReach>(g, G, lane.active, lane.f1, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, den, reads);
-    if (g.axis != 2)
-        grad[2] = sample::gradient_component<2, kCnt, kReach>(g, G, lane.active, lane.f2, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, den, reads);
+    unsigned long long reads = 0;   // (lane_gradient counts them; nobody reads the count here)
+    double grad[3];
+    sample::lane_gradient<kCnt, kReach>(g, G, lane, den, reads, grad);
     const int row = lane.row;   // (< the live count, which is <= n <= the shard's capacity)
     if (row < 0) return;
     const F ax = F(0.0 - grad[0]), ay = F(0.0 - grad[1]), az = F(0.0 - grad[2]);
@@ -68,16 +64,10 @@ void launch_kick(hipStream_t s, const ShardT<F>& sh, const int* count, int n, co
     const double den = sample::denominator_of(gradient_op, g.spacing);
     const int kick = kick_dt ? 1 : 0;
     const F dt = kick_dt ? *kick_dt : F(0);
-#define NBODY_MESH_KICK(R, S) \
-    hipLaunchKernelGGL((k_mesh_kick<F, R, S>), grid, block, 0, s, w.smp.xyz, count, n, g, den, w.smp.grid, rows, sh.own_pos(), sh.vel, sh.acc, kick, dt)
-#define NBODY_MESH_SCHEMES(R)                                     \
-    if (g.scheme == NBODY_DEPOSIT_NGP) NBODY_MESH_KICK(R, 0);     \
-    else if (g.scheme == NBODY_DEPOSIT_CIC) NBODY_MESH_KICK(R, 1); \
-    else NBODY_MESH_KICK(R, 2)
-    if (gradient_op == NBODY_SAMPLE_GRADIENT2) { NBODY_MESH_SCHEMES(1); }
-    else { NBODY_MESH_SCHEMES(2); }
-#undef NBODY_MESH_SCHEMES
-#undef NBODY_MESH_KICK
+    sample::for_reach_and_scheme(gradient_op, g.scheme, [&](auto reach, auto scheme) {
+        hipLaunchKernelGGL((k_mesh_kick<F, decltype(reach)::value, decltype(scheme)::value>), grid, block, 0, s, w.smp.xyz, count, n, g, den, w.smp.grid,
+                           rows, sh.own_pos(), sh.vel, sh.acc, kick, dt);
+    });
 }
 
 template <class F>

@@ -3,8 +3,8 @@
 // The deposit and the solve are kernels_deposit.hip's and kernels_poisson.hip's launches as they stand; what is new is
 //
 //   k_pm_gather<kReach, kScheme>  one lane per place of the home-cell order (or per row, unsorted).  ONE stencil set-up
-//                   (sample_device.h LaneStencil, k_sample's own) gives the three components of acc and phi together.  Every
-//                   output is the expression tree of the matching k_sample instance, because it is the same function:
+//                   (sample_device.h LaneStencil) gives the three components of acc and phi together.  Every output is the
+//                   expression tree of the matching k_sample instance, because it calls the same functions of sample_device.h:
 //                   gradient_component<K> for the components, and for phi weighted_sum's terms in weighted_sum's order -- summed,
 //                   for CIC and TSC, over the middle kCnt planes that gradient_component<0> has loaded anyway (kWithValue), so
 //                   phi costs no further grid read; NGP reads its own cell once more (no difference reads it), and a grid whose
@@ -33,22 +33,15 @@ __global__ __launch_bounds__(kSampleBlock) void k_pm_gather(const double* __rest
     double grad[3] = {0.0, 0.0, 0.0}, value = 0.0;   // (the component along the ignored axis stays +0.0 and reads nothing)
     if (g.axis != 0) {
         if constexpr (kCnt > 1) {
-            if (with_phi)
-                grad[0] = sample::gradient_component<0, kCnt, kReach, true>(g, G, lane.active, lane.f0, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy,
-                                                                           lane.wz, den, reads, &value);
-            else
-                grad[0] = sample::gradient_component<0, kCnt, kReach>(g, G, lane.active, lane.f0, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz,
-                                                                     den, reads);
+            if (with_phi) grad[0] = sample::gradient_component<0, kCnt, kReach, true>(g, G, lane, den, reads, &value);
+            else grad[0] = sample::gradient_component<0, kCnt, kReach>(g, G, lane, den, reads);
         } else {
-            grad[0] = sample::gradient_component<0, kCnt, kReach>(g, G, lane.active, lane.f0, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, den,
-                                                                 reads);
+            grad[0] = sample::gradient_component<0, kCnt, kReach>(g, G, lane, den, reads);
         }
     }
     if (with_phi && (kCnt == 1 || g.axis == 0)) value = sample::weighted_sum<kCnt>(g, G, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, reads);
-    if (g.axis != 1)
-        grad[1] = sample::gradient_component<1, kCnt, kReach>(g, G, lane.active, lane.f1, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, den, reads);
-    if (g.axis != 2)
-        grad[2] = sample::gradient_component<2, kCnt, kReach>(g, G, lane.active, lane.f2, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, den, reads);
+    if (g.axis != 1) grad[1] = sample::gradient_component<1, kCnt, kReach>(g, G, lane, den, reads);
+    if (g.axis != 2) grad[2] = sample::gradient_component<2, kCnt, kReach>(g, G, lane, den, reads);
     const int row = lane.row;
     if (row >= 0) {
         acc[3 * size_t(row)] = 0.0 - grad[0];
@@ -133,17 +126,10 @@ void launch_gather(hipStream_t s, const int* count, int n, const deposit::Grid& 
     if (n <= 0) return;
     const dim3 grid(sample::blocks_for(size_t(n))), block(kSampleBlock);
     const double den = sample::denominator_of(gradient_op, g.spacing);
-#define NBODY_PM_GATHER(R, S)                                                                                                           \
-    hipLaunchKernelGGL((k_pm_gather<R, S>), grid, block, 0, s, w.smp.xyz, count, n, g, den, w.smp.grid, rows, with_phi ? 1 : 0, w.smp.out, w.phi, \
-                       w.smp.cls, w.smp.words)
-#define NBODY_PM_SCHEMES(R)                                      \
-    if (g.scheme == NBODY_DEPOSIT_NGP) NBODY_PM_GATHER(R, 0);    \
-    else if (g.scheme == NBODY_DEPOSIT_CIC) NBODY_PM_GATHER(R, 1); \
-    else NBODY_PM_GATHER(R, 2)
-    if (gradient_op == NBODY_SAMPLE_GRADIENT2) { NBODY_PM_SCHEMES(1); }
-    else { NBODY_PM_SCHEMES(2); }
-#undef NBODY_PM_SCHEMES
-#undef NBODY_PM_GATHER
+    sample::for_reach_and_scheme(gradient_op, g.scheme, [&](auto reach, auto scheme) {
+        hipLaunchKernelGGL((k_pm_gather<decltype(reach)::value, decltype(scheme)::value>), grid, block, 0, s, w.smp.xyz, count, n, g, den, w.smp.grid,
+                           rows, with_phi ? 1 : 0, w.smp.out, w.phi, w.smp.cls, w.smp.words);
+    });
 }
 
 void launch_negate(hipStream_t s, const int* count, int n, double* rows) {

@@ -54,9 +54,14 @@ void launch_diff(hipStream_t s, const Grid& g, int op, const Scratch& w);
 // Returns 0, or -1 when the rocPRIM call could not be enqueued.
 int launch_order(hipStream_t s, const int* count, int n, const Grid& g, const Scratch& w);
 
-// w.words zeroed; p.sort: launch_order, unless `ordered` says that w.rows + n holds the order of these rows already; k_sample
-// over the n rows of w.xyz, of which the first *count are live (count == nullptr: all n).  Returns 0, or -1 when the rocPRIM
-// call could not be enqueued.
+// The n rows of w.xyz in home-cell order, for a gather: null when `sort` is off (row order); else w.rows + n, made first by
+// launch_order unless `ordered` says that it holds the order of these rows already.  *rc: launch_order's, or 0; *sorts (may be
+// null) += 1 when launch_order was enqueued.
+const int* ordered_rows(hipStream_t s, const int* count, int n, const Grid& g, const Scratch& w, bool sort, bool ordered, int* rc,
+                        uint64_t* sorts = nullptr);
+
+// w.words zeroed; the rows from ordered_rows(p.sort, ordered); k_sample over the n rows of w.xyz, of which the first *count are
+// live (count == nullptr: all n).  Returns 0, or -1 when the rocPRIM call could not be enqueued.
 int launch_sample(hipStream_t s, const int* count, int n, const Grid& g, int fields, int op, const Plan& p, const Scratch& w,
                   bool ordered = false);
 

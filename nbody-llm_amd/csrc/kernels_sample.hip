@@ -13,9 +13,10 @@
 //                   offsets are unrolled, so every index into the lane's arrays is a constant and they stay in registers; the
 //                   loads of a sum are issued together, the sum follows in sample_grid.h's order.  In the gradient ops a
 //                   component's stencil cells share their reads along the differentiated axis: cnt + 2 reach cells there, not
-//                   2 reach cnt.  The counts come from ballots and one integer atomic per wave and class.
+//                   2 reach cnt.  The counts come from ballots and one integer atomic per wave and class.  The stencil set-up,
+//                   the sums, the gradient and the counts are sample_device.h's, which says who else calls them.
 #include "kernels_sample.h"
-#include "sample_device.h"   // the stencil set-up, the sums and the counts, shared with kernels_pm.hip
+#include "sample_device.h"
 #include "kernels.h"   // tuning()
 #include "real.h"      // widen
 #include "scratch_carve.h"
@@ -27,7 +28,6 @@ namespace nbody {
 using sample::kSampleBlock;
 using sample::count_classes;
 using sample::drop_unreached;
-using sample::gradient_component;
 using sample::weighted_sum;
 
 namespace {
@@ -87,15 +87,11 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample(const double* __restric
     sample::LaneStencil<kCnt> lane;   // (sample_device.h: the row, the class and the stencil, indexed by constants only)
     lane.set_up(xyz, count, n, g, reach, rows, blockIdx.x * kSampleBlock + threadIdx.x);
     const int row = lane.row, cls = lane.cls;
-    const bool active = lane.active;
-    const long long f0 = lane.f0, f1 = lane.f1, f2 = lane.f2;
-    const auto &wx = lane.wx, &wy = lane.wy, &wz = lane.wz;
-    const auto &ix = lane.ix, &iy = lane.iy, &iz = lane.iz;
     unsigned long long reads = 0;
     if constexpr (kMode == kModeValue) {
         const size_t cells = deposit::cells_of(g);
         for (int f = 0; f < fields; ++f) {
-            const double sum = weighted_sum<kCnt>(g, G + size_t(f) * cells, ix, iy, iz, wx, wy, wz, reads);
+            const double sum = weighted_sum<kCnt>(g, G + size_t(f) * cells, lane.ix, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, reads);
             if (row >= 0) out[size_t(row) * size_t(fields) + f] = sum;
         }
     } else {
@@ -104,22 +100,19 @@ __global__ __launch_bounds__(kSampleBlock) void k_sample(const double* __restric
             const size_t cells = deposit::cells_of(g);
             int kept[kCnt];
             if (g.axis != 0) {
-                drop_unreached<kCnt>(ix, f0, g.dims[0], g.periodic, reach, kept);
-                grad[0] = weighted_sum<kCnt>(g, G, kept, iy, iz, wx, wy, wz, reads);
+                drop_unreached<kCnt>(lane.ix, lane.f0, g.dims[0], g.periodic, reach, kept);
+                grad[0] = weighted_sum<kCnt>(g, G, kept, lane.iy, lane.iz, lane.wx, lane.wy, lane.wz, reads);
             }
             if (g.axis != 1) {
-                drop_unreached<kCnt>(iy, f1, g.dims[1], g.periodic, reach, kept);
-                grad[1] = weighted_sum<kCnt>(g, G + cells, ix, kept, iz, wx, wy, wz, reads);
+                drop_unreached<kCnt>(lane.iy, lane.f1, g.dims[1], g.periodic, reach, kept);
+                grad[1] = weighted_sum<kCnt>(g, G + cells, lane.ix, kept, lane.iz, lane.wx, lane.wy, lane.wz, reads);
             }
             if (g.axis != 2) {
-                drop_unreached<kCnt>(iz, f2, g.dims[2], g.periodic, reach, kept);
-                grad[2] = weighted_sum<kCnt>(g, G + 2 * cells, ix, iy, kept, wx, wy, wz, reads);
+                drop_unreached<kCnt>(lane.iz, lane.f2, g.dims[2], g.periodic, reach, kept);
+                grad[2] = weighted_sum<kCnt>(g, G + 2 * cells, lane.ix, lane.iy, kept, lane.wx, lane.wy, lane.wz, reads);
             }
         } else {
-            constexpr int kReach = kMode == kModeGrad2 ? 1 : 2;
-            if (g.axis != 0) grad[0] = gradient_component<0, kCnt, kReach>(g, G, active, f0, ix, iy, iz, wx, wy, wz, den, reads);
-            if (g.axis != 1) grad[1] = gradient_component<1, kCnt, kReach>(g, G, active, f1, ix, iy, iz, wx, wy, wz, den, reads);
-            if (g.axis != 2) grad[2] = gradient_component<2, kCnt, kReach>(g, G, active, f2, ix, iy, iz, wx, wy, wz, den, reads);
+            sample::lane_gradient<kCnt, kMode == kModeGrad2 ? 1 : 2>(g, G, lane, den, reads, grad);
         }
         if (row >= 0) {
             out[3 * size_t(row)] = grad[0];
@@ -206,31 +199,34 @@ int launch_order(hipStream_t s, const int* count, int n, const Grid& g, const Sc
     return rocprim::radix_sort_pairs(w.sort_tmp, tb, w.keys, w.keys + n, w.rows, w.rows + n, size_t(n), 0, unsigned(key_bits(cells)), s) == hipSuccess ? 0 : -1;
 }
 
+const int* ordered_rows(hipStream_t s, const int* count, int n, const Grid& g, const Scratch& w, bool sort, bool ordered, int* rc, uint64_t* sorts) {
+    *rc = sort && !ordered ? launch_order(s, count, n, g, w) : 0;
+    if (sort && !ordered && *rc == 0 && sorts) ++*sorts;
+    return sort ? w.rows + n : nullptr;
+}
+
 int launch_sample(hipStream_t s, const int* count, int n, const Grid& g, int fields, int op, const Plan& p, const Scratch& w, bool ordered) {
     (void)hipMemsetAsync(w.words, 0, sizeof(Words), s);
     if (n <= 0) return 0;
     const dim3 grid(blocks_for(size_t(n))), block(kSampleBlock);
-    const int* rows = nullptr;
-    if (p.sort) {
-        if (!ordered && launch_order(s, count, n, g, w) != 0) return -1;
-        rows = w.rows + n;
-    }
+    int rc = 0;
+    const int* rows = ordered_rows(s, count, n, g, w, p.sort != 0, ordered, &rc);
+    if (rc) return -1;
     const int mode = op == NBODY_SAMPLE_VALUE ? kModeValue : p.pregrad ? kModePre : op == NBODY_SAMPLE_GRADIENT2 ? kModeGrad2 : kModeGrad4;
     const double* G = mode == kModePre ? w.diff : w.grid;
     const int reach = reach_of(op);
     const double den = denominator_of(op, g.spacing);
-#define NBODY_SAMPLE(M, S) \
-    hipLaunchKernelGGL((k_sample<M, S>), grid, block, 0, s, w.xyz, count, n, g, fields, reach, den, G, rows, w.out, w.cls, w.words)
-#define NBODY_SAMPLE_SCHEMES(M)                                  \
-    if (g.scheme == NBODY_DEPOSIT_NGP) NBODY_SAMPLE(M, 0);       \
-    else if (g.scheme == NBODY_DEPOSIT_CIC) NBODY_SAMPLE(M, 1);  \
-    else NBODY_SAMPLE(M, 2)
-    if (mode == kModeValue) { NBODY_SAMPLE_SCHEMES(kModeValue); }
-    else if (mode == kModeGrad2) { NBODY_SAMPLE_SCHEMES(kModeGrad2); }
-    else if (mode == kModeGrad4) { NBODY_SAMPLE_SCHEMES(kModeGrad4); }
-    else { NBODY_SAMPLE_SCHEMES(kModePre); }
-#undef NBODY_SAMPLE_SCHEMES
-#undef NBODY_SAMPLE
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, w.xyz, count, n, g, fields, reach, den, G, rows, w.out, w.cls, w.words);
+    };
+    switch (mode) {
+    case kModeValue: for_scheme(g.scheme, [&](auto sc) { launch(k_sample<kModeValue, decltype(sc)::value>); }); break;
+    case kModePre: for_scheme(g.scheme, [&](auto sc) { launch(k_sample<kModePre, decltype(sc)::value>); }); break;
+    default:   // kModeGrad2 | kModeGrad4: the op is a gradient operator
+        for_reach_and_scheme(op, g.scheme, [&](auto r, auto sc) {
+            launch(k_sample<decltype(r)::value == 1 ? kModeGrad2 : kModeGrad4, decltype(sc)::value>);
+        });
+    }
     return 0;
 }
 

@@ -699,6 +699,17 @@ int nbody_pair_counts_at(NbodyHandle* h, const double* points, size_t m, const d
     return with_bodies(h, [&](auto& b) { return nbody::paircount::pair_counts_at(h, b.sh, b.n_local, points, m, e2, counts, outside); });
 }
 
+// ---- the grid calls' records: what the last call of a kind left (nbody_handle.h *_last), under the census's refusals
+namespace {
+int last_stats(NbodyHandle* h, const char* call, uint64_t (NbodyHandle::*last)[4], uint64_t* out) {
+    if (!h) return NBODY_ERR_INVALID;
+    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    if (!out) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": out is NULL");
+    std::copy(h->*last, h->*last + 4, out);
+    return NBODY_OK;
+}
+}  // namespace
+
 // ---- grid deposit (nbody_deposit.cpp): a read-only call under the census's contract, and its host twin
 int nbody_deposit(NbodyHandle* h, const NbodyGridSpec* spec, double* grid, size_t cap, uint64_t counts[4]) {
     if (!h) return NBODY_ERR_INVALID;
@@ -715,13 +726,7 @@ int nbody_host_deposit(const double* xyz, const double* q, size_t n, const Nbody
     return nbody::deposit::host_entry(xyz, q, n, spec, grid, cap, counts);
 }
 
-int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]) {
-    if (!h) return NBODY_ERR_INVALID;
-    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_deposit_stats: ") + why);
-    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_deposit_stats: out is NULL");
-    std::copy(h->deposit_last, h->deposit_last + 4, out);
-    return NBODY_OK;
-}
+int nbody_deposit_stats(NbodyHandle* h, uint64_t out[4]) { return last_stats(h, "nbody_deposit_stats", &NbodyHandle::deposit_last, out); }
 
 // ---- grid sample (nbody_sample.cpp): two read-only calls under the census's contract, and their host twin
 namespace {
@@ -758,13 +763,7 @@ int nbody_host_grid_sample(const double* xyz, size_t n, const NbodyGridSpec* spe
     return nbody::sample::host_entry(xyz, n, spec, grid, fields, op, out, cls, counts);
 }
 
-int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]) {
-    if (!h) return NBODY_ERR_INVALID;
-    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_grid_sample_stats: ") + why);
-    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_grid_sample_stats: out is NULL");
-    std::copy(h->sample_last, h->sample_last + 4, out);
-    return NBODY_OK;
-}
+int nbody_grid_sample_stats(NbodyHandle* h, uint64_t out[4]) { return last_stats(h, "nbody_grid_sample_stats", &NbodyHandle::sample_last, out); }
 
 // ---- grid Poisson (nbody_poisson.cpp): a read-only call under the census's contract, and its host twins
 int nbody_grid_poisson(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPoissonSpec* ps, const double* mass, double* phi, size_t cap) {
@@ -784,13 +783,7 @@ int nbody_host_grid_poisson(const NbodyGridSpec* spec, const NbodyPoissonSpec* p
 
 int nbody_host_poisson_twiddles(int length, double* out) { return nbody::poisson::host_twiddles(length, out); }
 
-int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]) {
-    if (!h) return NBODY_ERR_INVALID;
-    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_grid_poisson_stats: ") + why);
-    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_grid_poisson_stats: out is NULL");
-    std::copy(h->poisson_last, h->poisson_last + 4, out);
-    return NBODY_OK;
-}
+int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]) { return last_stats(h, "nbody_grid_poisson_stats", &NbodyHandle::poisson_last, out); }
 
 // ---- particle-mesh field (nbody_pm.cpp): two read-only calls under the census's contract, and their host twin
 namespace {
@@ -827,13 +820,7 @@ int nbody_host_pm_field(const double* body_xyz, const double* body_m, size_t n_b
     return nbody::pm::host_entry(body_xyz, body_m, n_bodies, spec, pm, xyz, n_points, acc, phi, cls, counts);
 }
 
-int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]) {
-    if (!h) return NBODY_ERR_INVALID;
-    if (const char* why = nbody::diag::refusal(h)) return fail(h, NBODY_ERR_INVALID, std::string("nbody_pm_field_stats: ") + why);
-    if (!out) return fail(h, NBODY_ERR_INVALID, "nbody_pm_field_stats: out is NULL");
-    std::copy(h->pm_last, h->pm_last + 4, out);
-    return NBODY_OK;
-}
+int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]) { return last_stats(h, "nbody_pm_field_stats", &NbodyHandle::pm_last, out); }
 
 // ---- mesh gravity (nbody_mesh.cpp): a setting of the handle that its force passes read
 int nbody_set_mesh_gravity(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm) {

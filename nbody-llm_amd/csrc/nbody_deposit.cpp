@@ -20,17 +20,13 @@ int deposit(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGrid
     HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, cells, grid != nullptr, plan.sort != 0)));
     const Scratch w = scratch_layout(scratch.get(), n_upper, cells, grid != nullptr, plan.sort != 0);
     launch_q<F>(h->stream, sh, int(n_upper), g, spec.quantity, w);
-    bool sort_failed = false;
-    if (grid) sort_failed = launch_deposit<F>(h->stream, sh, int(n_upper), g, plan, w) != 0;
+    Enqueued st;
+    if (grid) st.prim(launch_deposit<F>(h->stream, sh, int(n_upper), g, plan, w));
     Words words{};
-    hipError_t e = hipGetLastError();
-    // (words is a local and grid the caller's: whatever was enqueued is waited for before either goes out of reach)
-    if (e == hipSuccess && !sort_failed) e = hipMemcpyAsync(&words, w.words, sizeof(Words), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && !sort_failed && grid) e = hipMemcpyAsync(grid, w.acc, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e_sync = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = e_sync;
-    HIP_TRY(h, e);
-    if (sort_failed) return fail(h, NBODY_ERR_HIP, "nbody_deposit: rocPRIM call failed");
+    st.last();
+    if (st.ok()) st.hip(hipMemcpyAsync(&words, w.words, sizeof(Words), hipMemcpyDeviceToHost, h->stream));
+    if (st.ok() && grid) st.hip(hipMemcpyAsync(grid, w.acc, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = st.finish(h, "nbody_deposit")) return rc;
     if (counts) std::copy(words.counts, words.counts + 4, counts);
     h->deposit_last[0] = 1;
     h->deposit_last[1] = uint64_t(plan.code());

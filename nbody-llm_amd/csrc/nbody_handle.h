@@ -690,6 +690,57 @@ hipError_t grow_dev_keep(NbodyHandle* h, T*& p, size_t& cap, size_t n, size_t el
     }));
 }
 
+// The live rows of sh: the device's count word copied and waited for, clamped to [0, n_upper] (the host's view of the count is
+// left as it is), for the calls that must know how many rows they will return before they write anything.
+template <class S>
+hipError_t live_rows(NbodyHandle* h, const S& sh, size_t n_upper, size_t* live) {
+    int n_live = 0;
+    hipError_t e = hipSuccess;
+    if (n_upper) {
+        e = hipMemcpyAsync(&n_live, sh.own_count(), sizeof(int), hipMemcpyDeviceToHost, h->stream);
+        const hipError_t e_sync = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = e_sync;
+    }
+    *live = e == hipSuccess ? std::min(size_t(std::max(n_live, 0)), n_upper) : 0;
+    return e;
+}
+
+// what follows it in a call that returns one row per live body; *n_out (may be null) is set even when the buffer is too small
+inline int row_frame(NbodyHandle* h, const char* call, const char* buffer, size_t live, const void* out, size_t cap, size_t* n_out) {
+    if (live && !out) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + buffer + " is NULL");
+    if (n_out) *n_out = live;
+    if (live > cap) return fail(h, NBODY_ERR_CAPACITY, std::string(call) + ": buffer too small");
+    return NBODY_OK;
+}
+
+// What a grid call (deposit, sample, Poisson, PM field, mesh pass) has enqueued on the handle's stream, as one status: a HIP error
+// or a rocPRIM call that could not be enqueued.  Once it is not ok() the caller enqueues nothing more: `if (st.ok()) st.hip(...)`.
+class Enqueued {
+public:
+    bool ok() const { return e_ == hipSuccess && !prim_failed_; }
+    void hip(hipError_t e) { if (ok()) e_ = e; }                // the first failure is kept
+    void prim(int rc) { if (ok() && rc != 0) prim_failed_ = true; }   // rc: a launcher's 0 or -1
+    void last() { if (e_ == hipSuccess) e_ = hipGetLastError(); }     // a launch that failed, asked for even after a rocPRIM failure
+    // nothing waited for: the HIP error first, then the rocPRIM failure under the call's name, then NBODY_OK
+    int result(NbodyHandle* h, const char* call) const {
+        const hipError_t e = e_;
+        HIP_TRY(h, e);
+        if (prim_failed_) return fail(h, NBODY_ERR_HIP, std::string(call) + ": rocPRIM call failed");
+        return NBODY_OK;
+    }
+    // The end of a call that waits: the stream is synchronised ALWAYS, whatever was enqueued and whether or not it failed.  The
+    // copies write the caller's locals and the user's buffers and read host tables of the caller's frame, and the scratch goes
+    // with the frame or is reused by the next batch: none may go out of reach while anything on the stream can touch it.
+    int finish(NbodyHandle* h, const char* call) {
+        const hipError_t e_sync = hipStreamSynchronize(h->stream);
+        if (e_ == hipSuccess) e_ = e_sync;
+        return result(h, call);
+    }
+private:
+    hipError_t e_ = hipSuccess;   // the first that was not hipSuccess
+    bool prim_failed_ = false;
+};
+
 struct ForceTimer {  // HIP events around a force-kernel launch, on the launch stream
     NbodyHandle* h;
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};

@@ -63,12 +63,6 @@ NbodyPmSpec without_g(NbodyPmSpec pm) {
     return pm;
 }
 
-template <class T>
-hipError_t upload(NbodyHandle* h, T* dst, const std::vector<T>& src) {
-    if (src.empty()) return hipSuccess;
-    return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->stream);
-}
-
 // The resident state for n_bodies body rows and n_tracers tracer rows under the current knobs: made at the first pass, remade
 // when the spec, the carving or a bound outgrows it -- before the pass enqueues anything -- and left alone otherwise.
 int ensure(NbodyHandle* h, size_t n_bodies, size_t n_tracers, const Plan& mp) {
@@ -102,12 +96,7 @@ int ensure(NbodyHandle* h, size_t n_bodies, size_t n_tracers, const Plan& mp) {
     r.cap_rows = cap_rows;
     std::copy(key, key + 5, r.layout_key);
     // the Poisson tables, once per block
-    hipError_t e = hipSuccess;
-    for (int a = 0; a < 3 && e == hipSuccess; ++a) {
-        e = upload(h, r.w.poi.tw[a], c.tables.tw[a]);
-        if (e == hipSuccess) e = upload(h, r.w.poi.K[a], c.tables.K[a]);
-        if (e == hipSuccess) e = upload(h, r.w.poi.D[a], c.tables.D[a]);
-    }
+    const hipError_t e = poisson::upload_tables(h, c.tables, r.w.poi);
     HIP_TRY(h, e);
     return NBODY_OK;
 }
@@ -115,27 +104,24 @@ int ensure(NbodyHandle* h, size_t n_bodies, size_t n_tracers, const Plan& mp) {
 // the gather of one vector of rows (the bodies, or the tracers) against the resident grid: w.smp.xyz holds their positions;
 // ordered: w.smp.rows + n holds their home-cell order already
 template <class F>
-int rows_pass(NbodyHandle* h, const Resident& r, const Plan& mp, const ShardT<F>& sh, size_t n, bool ordered, const F* kick_dt, uint64_t* sorts) {
+void rows_pass(NbodyHandle* h, const Resident& r, const Plan& mp, const ShardT<F>& sh, size_t n, bool ordered, const F* kick_dt, Enqueued& st,
+               pm::Tally& tally) {
     const hipStream_t s = h->stream;
     const pm::Call& c = *r.call;
     const pm::Scratch& w = r.w;
+    if (!st.ok()) return;
     if (mp.kick_fuse) {
-        const int* rows = nullptr;
-        if (c.plans.grad.sort) {
-            if (!ordered) {
-                if (sample::launch_order(s, sh.own_count(), int(n), c.g, w.smp) != 0) return -1;
-                ++*sorts;
-            }
-            rows = w.smp.rows + n;
-        }
-        launch_kick<F>(s, sh, sh.own_count(), int(n), c.g, c.op, rows, w, kick_dt);
-        return 0;
+        int rc = 0;
+        const int* rows = sample::ordered_rows(s, sh.own_count(), int(n), c.g, w.smp, c.plans.grad.sort != 0, ordered, &rc, &tally.sorts);
+        st.prim(rc);
+        if (st.ok()) launch_kick<F>(s, sh, sh.own_count(), int(n), c.g, c.op, rows, w, kick_dt);
+        return;
     }
     // the cross-check: nbody_pm_field's own rows in f64, rounded, and the leapfrog's own kick
-    if (pm::enqueue_rows(h, c, sh.own_count(), n, false, ordered, w, sorts) != 0) return -1;
+    pm::enqueue_rows(h, c, sh.own_count(), n, false, ordered, w, st, tally);
+    if (!st.ok()) return;
     launch_round<F>(s, sh, sh.own_count(), int(n), w.smp.out);
     if (kick_dt) nbody::launch_kick_drift<F>(s, sh, int(n), *kick_dt);
-    return 0;
 }
 
 }  // namespace
@@ -155,32 +141,25 @@ int pass(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, const F*
     c.tables.c = poisson::green_constant(g, m.spec.spacing);
     const pm::Scratch& w = r.w;
     const hipStream_t s = h->stream;
-    uint64_t sorts = 0;
-    bool sort_failed = false;
+    Enqueued st;   // (nothing is waited for: the resident state outlives the pass, and result() is asked, not finish())
+    pm::Tally tally;
     sample::launch_stage<F>(s, sh, int(n_upper), w.smp);
-    const int* order = nullptr;   // one order for the deposit and the gather, as in nbody_pm_field
-    const bool shared = c.plans.shared && n_upper > 0;
-    if (shared) {
-        sort_failed = sample::launch_order(s, sh.own_count(), int(n_upper), c.g, w.smp) != 0;
-        order = w.smp.rows + n_upper;
-    }
+    const bool shared = c.plans.shared && n_upper > 0;   // one order for the deposit and the gather, as in nbody_pm_field
+    const int* order = pm::enqueue_shared_order(h, c, sh.own_count(), n_upper, shared, w, st, tally);
     const bool keep = mp.keep_kernel && r.kernel_made && !c.shape.periodic;
-    hipError_t e = hipSuccess;
-    if (!sort_failed)
-        e = pm::enqueue_grid<F>(h, sh, n_upper, m.spec, pm, c, w, order, &sort_failed, &sorts, poisson::kHeldTables | (keep ? poisson::kHeldKernel : 0),
-                                &m.transforms);
-    if (e == hipSuccess && !sort_failed) {
+    pm::enqueue_grid<F>(h, sh, n_upper, m.spec, pm, c, w, order, st, tally, poisson::kHeldTables | (keep ? poisson::kHeldKernel : 0));
+    m.transforms += tally.transforms;
+    if (st.ok()) {
         r.kernel_made = !c.shape.periodic;
-        if (n_upper) sort_failed = rows_pass<F>(h, r, mp, sh, n_upper, shared, kick_dt, &sorts) != 0;
+        if (n_upper) rows_pass<F>(h, r, mp, sh, n_upper, shared, kick_dt, st, tally);
     }
-    if (e == hipSuccess && !sort_failed && n_tracers) {   // the tracers, at their own positions against the same grid
+    if (st.ok() && n_tracers) {   // the tracers, at their own positions against the same grid
         const Shard& t = h->tr.sh;
         sample::launch_stage<float>(s, t, int(n_tracers), w.smp);
-        sort_failed = rows_pass<float>(h, r, mp, t, n_tracers, false, tracer_kick_dt, &sorts) != 0;
+        rows_pass<float>(h, r, mp, t, n_tracers, false, tracer_kick_dt, st, tally);
     }
-    if (e == hipSuccess) e = hipGetLastError();
-    HIP_TRY(h, e);
-    if (sort_failed) return fail(h, NBODY_ERR_HIP, "mesh gravity: rocPRIM call failed");
+    st.last();
+    if (const int rc = st.result(h, "mesh gravity")) return rc;
     m.passes += 1;
     m.last_plan = uint64_t(mp.code()) | uint64_t(c.plans.pm.gather | (c.plans.shared ? 2 : 0)) << 2;
     return NBODY_OK;

@@ -11,25 +11,15 @@
 
 namespace nbody { namespace pairs {
 
-namespace {
-// the live count of sh, at most n_upper (a copy of the device's word; the host's view of the count is left as it is)
-template <class F>
-hipError_t read_live(NbodyHandle* h, const ShardT<F>& sh, int* live) {
-    hipError_t e = hipMemcpyAsync(live, sh.own_count(), sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    return e;
-}
-}  // namespace
-
 template <class F>
 int partners(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, double g_soft, int32_t* partner, double* energy, size_t cap,
              size_t* n_out) {
     if (n_out) *n_out = 0;
     if (!n_upper) return NBODY_OK;
-    int live = 0;
+    size_t n = 0;
     if (!partner && !energy) {   // counts only
-        HIP_TRY(h, read_live(h, sh, &live));
-        if (n_out) *n_out = std::min(size_t(std::max(live, 0)), n_upper);
+        HIP_TRY(h, live_rows(h, sh, n_upper, &n));
+        if (n_out) *n_out = n;
         return NBODY_OK;
     }
     const PartnerPlan plan = make_partner_plan(int(n_upper));
@@ -38,8 +28,7 @@ int partners(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, double g, doub
     const PairScratch w = scratch_layout(scratch.get(), n_upper, plan, false);
     launch_partners<F>(h->stream, sh, int(n_upper), plan, g, g_soft * g_soft, w);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, read_live(h, sh, &live));
-    const size_t n = std::min(size_t(std::max(live, 0)), n_upper);
+    HIP_TRY(h, live_rows(h, sh, n_upper, &n));
     const bool fits = n <= cap;
     // (partner and energy are pageable: the copies return once the data has reached them)
     if (fits && n && partner) HIP_TRY(h, hipMemcpyAsync(partner, w.partner, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -97,10 +86,10 @@ template <class F>
 int nearest(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, int32_t* nearest_out, double* dist2, size_t cap, size_t* n_out) {
     if (n_out) *n_out = 0;
     if (!n_upper) return NBODY_OK;
-    int live = 0;
+    size_t n = 0;
     if (!nearest_out && !dist2) {   // counts only
-        HIP_TRY(h, read_live(h, sh, &live));
-        if (n_out) *n_out = std::min(size_t(std::max(live, 0)), n_upper);
+        HIP_TRY(h, live_rows(h, sh, n_upper, &n));
+        if (n_out) *n_out = n;
         return NBODY_OK;
     }
     const PartnerPlan plan = make_partner_plan(int(n_upper));
@@ -109,8 +98,7 @@ int nearest(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, int32_t* neares
     const PairScratch w = scratch_layout(scratch.get(), n_upper, plan, false);
     launch_nearest<F>(h->stream, sh, int(n_upper), plan, w);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, read_live(h, sh, &live));
-    const size_t n = std::min(size_t(std::max(live, 0)), n_upper);
+    HIP_TRY(h, live_rows(h, sh, n_upper, &n));
     const bool fits = n <= cap;
     if (fits && n && nearest_out) HIP_TRY(h, hipMemcpyAsync(nearest_out, w.partner, n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     if (fits && n && dist2) HIP_TRY(h, hipMemcpyAsync(dist2, w.energy, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));

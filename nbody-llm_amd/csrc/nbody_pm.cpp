@@ -21,43 +21,49 @@ struct Down {
 
 }  // namespace
 
-// (the contracts of enqueue_grid and enqueue_rows are nbody_pm.h's)
+// (the contracts of the stages are nbody_pm.h's)
+const int* enqueue_shared_order(NbodyHandle* h, const Call& c, const int* count, size_t n, bool shared, const Scratch& w, Enqueued& st, Tally& tally) {
+    if (!shared) return nullptr;
+    st.prim(sample::launch_order(h->stream, count, int(n), c.g, w.smp));
+    ++tally.sorts;
+    return w.smp.rows + n;
+}
+
 template <class F>
-hipError_t enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const Call& c,
-                        const Scratch& w, const int* ordered_rows, bool* sort_failed, uint64_t* sorts, int held, uint64_t* transforms) {
+void enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const Call& c,
+                  const Scratch& w, const int* ordered_rows, Enqueued& st, Tally& tally, int held) {
     const hipStream_t s = h->stream;
+    if (!st.ok()) return;
     if (n_upper) {
         deposit::launch_q<F>(s, sh, int(n_upper), c.g, NBODY_DEPOSIT_MASS, w.dep);
-        if (deposit::launch_deposit<F>(s, sh, int(n_upper), c.g, c.plans.dep, w.dep, ordered_rows) != 0) {
-            *sort_failed = true;
-            return hipSuccess;
-        }
-        if (c.plans.dep.sort && !ordered_rows) ++*sorts;
+        st.prim(deposit::launch_deposit<F>(s, sh, int(n_upper), c.g, c.plans.dep, w.dep, ordered_rows));
+        if (!st.ok()) return;
+        if (c.plans.dep.sort && !ordered_rows) ++tally.sorts;
     } else {   // no body: every count 0 and every cell +0.0
         (void)hipMemsetAsync(w.dep.words, 0, sizeof(deposit::Words), s);
         (void)hipMemsetAsync(w.dep.acc, 0, deposit::cells_of(c.g) * sizeof(long long), s);
     }
-    hipError_t e = hipGetLastError();
+    st.last();
     int made = 0;
-    if (e == hipSuccess) e = poisson::enqueue(h, spec, pm.poisson, c.shape, c.tables, c.plans.poi, w.poi, nullptr, &made, held);
-    if (e == hipSuccess && transforms) *transforms += uint64_t(made);
-    if (e == hipSuccess && c.plans.grad.pregrad) {
+    if (st.ok()) st.hip(poisson::enqueue(h, spec, pm.poisson, c.shape, c.tables, c.plans.poi, w.poi, nullptr, &made, held));
+    if (st.ok()) tally.transforms += uint64_t(made);
+    if (st.ok() && c.plans.grad.pregrad) {
         sample::launch_diff(s, c.g, c.op, w.smp);
-        e = hipGetLastError();
+        st.last();
     }
-    return e;
 }
 
-int enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, uint64_t* sorts) {
+void enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, Enqueued& st, Tally& tally) {
     const hipStream_t s = h->stream;
     const Plans& p = c.plans;
-    if (p.grad.sort && !ordered) {
-        if (sample::launch_order(s, count, int(n), c.g, w.smp) != 0) return -1;
-        ++*sorts;
-    }
+    if (!st.ok()) return;
+    int rc = 0;
+    const int* rows = sample::ordered_rows(s, count, int(n), c.g, w.smp, p.grad.sort != 0, ordered, &rc, &tally.sorts);
+    st.prim(rc);
+    if (!st.ok()) return;
     if (p.pm.gather) {
-        launch_gather(s, count, int(n), c.g, c.op, with_phi, p.grad.sort ? w.smp.rows + n : nullptr, w);
-        return 0;
+        launch_gather(s, count, int(n), c.g, c.op, with_phi, rows, w);
+        return;
     }
     // the cross-check: k_sample twice over the same order, gradient then value
     (void)sample::launch_sample(s, count, int(n), c.g, 1, c.op, p.grad, w.smp, true);
@@ -68,22 +74,19 @@ int enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool
     v.words = w.value_words;
     if (with_phi) (void)sample::launch_sample(s, count, int(n), c.g, 1, NBODY_SAMPLE_VALUE, p.value, v, true);
     else (void)hipMemsetAsync(v.words, 0, sizeof(sample::Words), s);
-    return 0;
 }
 
 namespace {
 
-// the copies of a pass's first `copy` rows and of its words, enqueued (e: what went before; nothing more once it failed)
-hipError_t enqueue_down(NbodyHandle* h, hipError_t e, const Call& c, const Scratch& w, size_t copy, double* acc, double* phi, uint8_t* cls,
-                        Down* down) {
+// the copies of a pass's first `copy` rows and of its words
+void enqueue_down(NbodyHandle* h, Enqueued& st, const Call& c, const Scratch& w, size_t copy, double* acc, double* phi, uint8_t* cls, Down* down) {
     const hipStream_t s = h->stream;
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&down->rows, w.smp.words, sizeof(sample::Words), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && !c.plans.pm.gather) e = hipMemcpyAsync(&down->value, w.value_words, sizeof(sample::Words), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && copy) e = hipMemcpyAsync(acc, w.smp.out, copy * 3 * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && copy && phi) e = hipMemcpyAsync(phi, w.phi, copy * sizeof(double), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && copy && cls) e = hipMemcpyAsync(cls, w.smp.cls, copy, hipMemcpyDeviceToHost, s);
-    return e;
+    if (st.ok()) st.last();
+    if (st.ok()) st.hip(hipMemcpyAsync(&down->rows, w.smp.words, sizeof(sample::Words), hipMemcpyDeviceToHost, s));
+    if (st.ok() && !c.plans.pm.gather) st.hip(hipMemcpyAsync(&down->value, w.value_words, sizeof(sample::Words), hipMemcpyDeviceToHost, s));
+    if (st.ok() && copy) st.hip(hipMemcpyAsync(acc, w.smp.out, copy * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (st.ok() && copy && phi) st.hip(hipMemcpyAsync(phi, w.phi, copy * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (st.ok() && copy && cls) st.hip(hipMemcpyAsync(cls, w.smp.cls, copy, hipMemcpyDeviceToHost, s));
 }
 
 void record(NbodyHandle* h, const Call& c, uint64_t reads, uint64_t sorts) {
@@ -99,17 +102,10 @@ template <class F>
 int at_bodies(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, double* acc, double* phi,
               uint8_t* cls, size_t cap, size_t* n_out, uint64_t* counts) {
     // the live count first: a call that is refused, a buffer that is too small included, computes and writes nothing
-    int n_live = 0;
-    if (n_upper) {
-        const hipError_t e = hipMemcpyAsync(&n_live, sh.own_count(), sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        const hipError_t e_sync = hipStreamSynchronize(h->stream);
-        HIP_TRY(h, e);
-        HIP_TRY(h, e_sync);
-    }
-    const size_t live = std::min(size_t(std::max(n_live, 0)), n_upper);
-    if (live && !acc) return fail(h, NBODY_ERR_INVALID, "nbody_pm_field: acc is NULL");
-    if (n_out) *n_out = live;
-    if (live > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_pm_field: buffer too small");
+    size_t live = 0;
+    const hipError_t e = live_rows(h, sh, n_upper, &live);
+    HIP_TRY(h, e);
+    if (const int rc = row_frame(h, "nbody_pm_field", "acc", live, acc, cap, n_out)) return rc;
     if (counts) std::fill(counts, counts + 8, uint64_t(0));
     if (!live) return NBODY_OK;
     const Call c(spec, pm, true);
@@ -117,31 +113,21 @@ int at_bodies(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGr
     HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, n_upper, c.g, c.shape, c.deconvolve, c.op, c.plans)));
     const Scratch w = scratch_layout(scratch.get(), n_upper, n_upper, c.g, c.shape, c.deconvolve, c.op, c.plans);
     const hipStream_t s = h->stream;
-    uint64_t sorts = 0;
-    bool sort_failed = false;
+    Enqueued st;
+    Tally tally;
     sample::launch_stage<F>(s, sh, int(n_upper), w.smp);
-    const int* order = nullptr;   // one order for both stages: the sampler's keys, which depend on the position alone
-    if (c.plans.shared) {
-        sort_failed = sample::launch_order(s, sh.own_count(), int(n_upper), c.g, w.smp) != 0;
-        order = w.smp.rows + n_upper;
-        ++sorts;
-    }
-    hipError_t e = hipSuccess;
-    if (!sort_failed) e = enqueue_grid<F>(h, sh, n_upper, spec, pm, c, w, order, &sort_failed, &sorts);
-    if (e == hipSuccess && !sort_failed) sort_failed = enqueue_rows(h, c, sh.own_count(), n_upper, phi != nullptr, c.plans.shared, w, &sorts) != 0;
-    // (down is a local, the tables are c's and the rows the user's: whatever was enqueued is waited for before any goes out of reach)
+    const int* order = enqueue_shared_order(h, c, sh.own_count(), n_upper, c.plans.shared, w, st, tally);
+    enqueue_grid<F>(h, sh, n_upper, spec, pm, c, w, order, st, tally);
+    enqueue_rows(h, c, sh.own_count(), n_upper, phi != nullptr, c.plans.shared, w, st, tally);
     Down down;
-    if (e == hipSuccess && !sort_failed) e = hipMemcpyAsync(&down.dep, w.dep.words, sizeof(deposit::Words), hipMemcpyDeviceToHost, s);
-    if (!sort_failed) e = enqueue_down(h, e, c, w, live, acc, phi, cls, &down);
-    const hipError_t e_sync = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = e_sync;
-    HIP_TRY(h, e);
-    if (sort_failed) return fail(h, NBODY_ERR_HIP, "nbody_pm_field: rocPRIM call failed");
+    if (st.ok()) st.hip(hipMemcpyAsync(&down.dep, w.dep.words, sizeof(deposit::Words), hipMemcpyDeviceToHost, s));
+    enqueue_down(h, st, c, w, live, acc, phi, cls, &down);
+    if (const int rc = st.finish(h, "nbody_pm_field")) return rc;
     if (counts) {
         std::copy(down.dep.counts, down.dep.counts + 4, counts);
         std::copy(down.rows.counts, down.rows.counts + 4, counts + 4);
     }
-    record(h, c, down.rows.reads + down.value.reads, sorts);
+    record(h, c, down.rows.reads + down.value.reads, tally.sorts);
     return NBODY_OK;
 }
 
@@ -155,25 +141,21 @@ int at_points(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGr
     HIP_TRY(h, scratch.alloc(scratch_bytes(n_upper, batch, c.g, c.shape, c.deconvolve, c.op, c.plans)));
     const Scratch w = scratch_layout(scratch.get(), n_upper, batch, c.g, c.shape, c.deconvolve, c.op, c.plans);
     const hipStream_t s = h->stream;
-    uint64_t sorts = 0, reads = 0, counted[4] = {0, 0, 0, 0};
-    bool sort_failed = false;
+    uint64_t reads = 0, counted[4] = {0, 0, 0, 0};
+    Enqueued st;
+    Tally tally;
     Down down;
-    hipError_t e = enqueue_grid<F>(h, sh, n_upper, spec, pm, c, w, nullptr, &sort_failed, &sorts);
-    if (e == hipSuccess && !sort_failed) e = hipMemcpyAsync(&down.dep, w.dep.words, sizeof(deposit::Words), hipMemcpyDeviceToHost, s);
-    // (every pass ends in a synchronisation, whatever was enqueued: the batch's buffers are reused by the next one, and down, the
-    // tables and the user's rows must not go out of reach before)
+    enqueue_grid<F>(h, sh, n_upper, spec, pm, c, w, nullptr, st, tally);
+    if (st.ok()) st.hip(hipMemcpyAsync(&down.dep, w.dep.words, sizeof(deposit::Words), hipMemcpyDeviceToHost, s));
     size_t at0 = 0;
-    do {
+    do {   // (every pass ends in Enqueued::finish: the batch's buffers are reused by the next one)
         const size_t n = std::min(batch, n_points - at0);
-        if (e == hipSuccess && !sort_failed && n) {
-            e = hipMemcpyAsync(w.smp.xyz, xyz + 3 * at0, n * 3 * sizeof(double), hipMemcpyHostToDevice, s);
-            if (e == hipSuccess) sort_failed = enqueue_rows(h, c, nullptr, n, phi != nullptr, false, w, &sorts) != 0;
-            if (!sort_failed) e = enqueue_down(h, e, c, w, n, acc + 3 * at0, phi ? phi + at0 : nullptr, cls ? cls + at0 : nullptr, &down);
+        if (st.ok() && n) {
+            st.hip(hipMemcpyAsync(w.smp.xyz, xyz + 3 * at0, n * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+            enqueue_rows(h, c, nullptr, n, phi != nullptr, false, w, st, tally);
+            enqueue_down(h, st, c, w, n, acc + 3 * at0, phi ? phi + at0 : nullptr, cls ? cls + at0 : nullptr, &down);
         }
-        const hipError_t e_sync = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = e_sync;
-        HIP_TRY(h, e);
-        if (sort_failed) return fail(h, NBODY_ERR_HIP, "nbody_pm_field_at: rocPRIM call failed");
+        if (const int rc = st.finish(h, "nbody_pm_field_at")) return rc;
         for (int k = 0; k < 4; ++k) counted[k] += down.rows.counts[k];
         reads += down.rows.reads + down.value.reads;
         down.rows = sample::Words{};
@@ -184,14 +166,14 @@ int at_points(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGr
         std::copy(down.dep.counts, down.dep.counts + 4, counts);
         std::copy(counted, counted + 4, counts + 4);
     }
-    record(h, c, reads, sorts);
+    record(h, c, reads, tally.sorts);
     return NBODY_OK;
 }
 
-template hipError_t enqueue_grid<float>(NbodyHandle*, const ShardT<float>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, const Call&, const Scratch&,
-                                        const int*, bool*, uint64_t*, int, uint64_t*);
-template hipError_t enqueue_grid<double>(NbodyHandle*, const ShardT<double>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, const Call&, const Scratch&,
-                                         const int*, bool*, uint64_t*, int, uint64_t*);
+template void enqueue_grid<float>(NbodyHandle*, const ShardT<float>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, const Call&, const Scratch&,
+                                  const int*, Enqueued&, Tally&, int);
+template void enqueue_grid<double>(NbodyHandle*, const ShardT<double>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, const Call&, const Scratch&,
+                                   const int*, Enqueued&, Tally&, int);
 template int at_bodies<float>(NbodyHandle*, const ShardT<float>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, double*, double*, uint8_t*,
                               size_t, size_t*, uint64_t*);
 template int at_bodies<double>(NbodyHandle*, const ShardT<double>&, size_t, const NbodyGridSpec&, const NbodyPmSpec&, double*, double*, uint8_t*,

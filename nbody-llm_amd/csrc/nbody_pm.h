@@ -35,16 +35,22 @@ struct Call {
           plans(make_plans(pm.gradient, deposit::cells_of(g), bodies)), deconvolve(shape.periodic && pm.poisson.deconvolve > 0), op(pm.gradient) {}
 };
 
-// The deposit of the n_upper rows of sh and the solve, enqueued: w.smp.grid (the deposit's sums, the Poisson stage's real) holds
-// phi, and under sample_pregrad the difference grids follow.  ordered_rows: the bodies in home-cell order, made already, or
-// null.  sort_failed: a rocPRIM call could not be enqueued.  held: poisson::enqueue's; transforms (may be null): += the 3-D
-// transforms enqueued.
-template <class F>
-hipError_t enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const Call& c,
-                        const Scratch& w, const int* ordered_rows, bool* sort_failed, uint64_t* sorts, int held = 0, uint64_t* transforms = nullptr);
+// what the stages count as they enqueue; every stage enqueues against st (nbody_handle.h Enqueued) and does nothing once it is not ok
+struct Tally { uint64_t sorts = 0, transforms = 0; };   // radix sorts, 3-D transforms
 
-// One pass over the n rows of w.smp.xyz (count: the live rows' word on the device, or null: all n) against the resident grid,
-// enqueued: w.smp.out = acc, w.phi (with_phi), w.smp.cls.  ordered: w.smp.rows + n holds these rows' order already.
-int enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, uint64_t* sorts);
+// shared: one order for both stages -- the sampler's keys, which depend on the position alone -- over the n rows
+// of w.smp.xyz; returns it (w.smp.rows + n), or null when not shared
+const int* enqueue_shared_order(NbodyHandle* h, const Call& c, const int* count, size_t n, bool shared, const Scratch& w, Enqueued& st, Tally& tally);
+
+// The deposit of the n_upper rows of sh and the solve: w.smp.grid (the deposit's sums, the Poisson stage's real) holds phi, and
+// under sample_pregrad the difference grids follow.  ordered_rows: the bodies in home-cell order, made already, or null.
+// held: poisson::enqueue's.
+template <class F>
+void enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const NbodyPmSpec& pm, const Call& c,
+                  const Scratch& w, const int* ordered_rows, Enqueued& st, Tally& tally, int held = 0);
+
+// One pass over the n rows of w.smp.xyz (count: the live rows' word on the device, or null: all n) against the resident grid:
+// w.smp.out = acc, w.phi (with_phi), w.smp.cls.  ordered: w.smp.rows + n holds these rows' order already.
+void enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, Enqueued& st, Tally& tally);
 
 }}  // namespace nbody::pm

@@ -6,25 +6,23 @@
 
 namespace nbody { namespace poisson {
 
-namespace {
-
-template <class T>
-hipError_t upload(NbodyHandle* h, T* dst, const std::vector<T>& src) {
-    if (src.empty()) return hipSuccess;
-    return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, h->stream);
+hipError_t upload_tables(NbodyHandle* h, const Tables& t, const Scratch& w) {
+    const auto upload = [h](auto* dst, const auto& src) {
+        return src.empty() ? hipSuccess : hipMemcpyAsync(dst, src.data(), src.size() * sizeof(src[0]), hipMemcpyHostToDevice, h->stream);
+    };
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < 3 && e == hipSuccess; ++c) {
+        e = upload(w.tw[c], t.tw[c]);
+        if (e == hipSuccess) e = upload(w.K[c], t.K[c]);
+        if (e == hipSuccess) e = upload(w.D[c], t.D[c]);
+    }
+    return e;
 }
-
-}  // namespace
 
 hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
                    const Scratch& w, int* launches_out, int* transforms_out, int held) {
     const bool deconvolve = sh.periodic && ps.deconvolve > 0;
-    hipError_t e = hipSuccess;
-    for (int c = 0; c < 3 && e == hipSuccess && !(held & kHeldTables); ++c) {
-        e = upload(h, w.tw[c], t.tw[c]);
-        if (e == hipSuccess) e = upload(h, w.K[c], t.K[c]);
-        if (e == hipSuccess) e = upload(h, w.D[c], t.D[c]);
-    }
+    hipError_t e = (held & kHeldTables) ? hipSuccess : upload_tables(h, t, w);
     int launches = 0, transforms = 2;
     if (e == hipSuccess) {
         launch_load(h->stream, sh, w);
@@ -57,14 +55,12 @@ int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps,
     HIP_TRY(h, scratch.alloc(scratch_bytes(sh, deconvolve)));
     const Scratch w = scratch_layout(scratch.get(), sh, deconvolve);
     // the grid on its way to the device (t outlives the call's synchronisation)
-    hipError_t e = hipMemcpyAsync(w.real, mass, sh.cells() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    Enqueued st;
+    st.hip(hipMemcpyAsync(w.real, mass, sh.cells() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     int launches = 0, transforms = 2;
-    if (e == hipSuccess) e = enqueue(h, spec, ps, sh, t, plan, w, &launches, &transforms);
-    // (phi is the user's and t this frame's: whatever was enqueued is waited for before either goes out of reach)
-    if (e == hipSuccess) e = hipMemcpyAsync(phi, w.real, sh.cells() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e_sync = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = e_sync;
-    HIP_TRY(h, e);
+    if (st.ok()) st.hip(enqueue(h, spec, ps, sh, t, plan, w, &launches, &transforms));
+    if (st.ok()) st.hip(hipMemcpyAsync(phi, w.real, sh.cells() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = st.finish(h, "nbody_grid_poisson")) return rc;
     h->poisson_last[0] = 1;
     h->poisson_last[1] = uint64_t(plan.code());
     h->poisson_last[2] = uint64_t(launches);

@@ -20,6 +20,8 @@ int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps,
 // (kHeldTables), and on an isolated grid the transformed kernel in w.k (kHeldKernel: two transforms then, every output's
 // expression tree as it was).
 enum { kHeldTables = 1, kHeldKernel = 2 };
+// the twiddles, the Green factors and the deconvolution factors of t on their way to w's three axes (t outlives the wait)
+hipError_t upload_tables(NbodyHandle* h, const Tables& t, const Scratch& w);
 hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
                    const Scratch& w, int* launches_out, int* transforms_out, int held = 0);
 

@@ -18,21 +18,17 @@ hipError_t upload_grid(NbodyHandle* h, const Grid& g, const double* grid, int fi
 }
 
 // The passes over the n rows of w.xyz (count: the live rows' word on the device, or null: all n), the copy of the first `copy`
-// rows to out and cls and of the words, and the synchronisation, whatever was enqueued.
+// rows to out and cls and of the words, and the synchronisation (Enqueued::finish).
 int passes(NbodyHandle* h, const char* call, const Grid& g, int fields, int op, const Plan& plan, const Scratch& w, const int* count, size_t n,
            size_t copy, double* out, uint8_t* cls, Words* words) {
-    const bool sort_failed = launch_sample(h->stream, count, int(n), g, fields, op, plan, w) != 0;
+    Enqueued st;
+    st.prim(launch_sample(h->stream, count, int(n), g, fields, op, plan, w));
     const size_t width = size_t(width_of(op, fields));
-    hipError_t e = hipGetLastError();
-    // (words is the caller's local, out and cls the user's: whatever was enqueued is waited for before any goes out of reach)
-    if (e == hipSuccess && !sort_failed) e = hipMemcpyAsync(words, w.words, sizeof(Words), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && !sort_failed && copy) e = hipMemcpyAsync(out, w.out, copy * width * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && !sort_failed && copy && cls) e = hipMemcpyAsync(cls, w.cls, copy, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t e_sync = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = e_sync;
-    HIP_TRY(h, e);
-    if (sort_failed) return fail(h, NBODY_ERR_HIP, std::string(call) + ": rocPRIM call failed");
-    return NBODY_OK;
+    st.last();
+    if (st.ok()) st.hip(hipMemcpyAsync(words, w.words, sizeof(Words), hipMemcpyDeviceToHost, h->stream));
+    if (st.ok() && copy) st.hip(hipMemcpyAsync(out, w.out, copy * width * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (st.ok() && copy && cls) st.hip(hipMemcpyAsync(cls, w.cls, copy, hipMemcpyDeviceToHost, h->stream));
+    return st.finish(h, call);
 }
 
 void record(NbodyHandle* h, const Plan& plan, uint64_t reads) {
@@ -48,17 +44,10 @@ template <class F>
 int at_bodies(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const NbodyGridSpec& spec, const double* grid, int fields, int op, double* out,
               uint8_t* cls, size_t cap, size_t* n_out, uint64_t* counts) {
     // the live count first: a call that is refused, a buffer that is too small included, computes and writes nothing
-    int n_live = 0;
-    if (n_upper) {
-        const hipError_t e = hipMemcpyAsync(&n_live, sh.own_count(), sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        const hipError_t e_sync = hipStreamSynchronize(h->stream);
-        HIP_TRY(h, e);
-        HIP_TRY(h, e_sync);
-    }
-    const size_t live = std::min(size_t(std::max(n_live, 0)), n_upper);
-    if (live && !out) return fail(h, NBODY_ERR_INVALID, "nbody_grid_sample: out is NULL");
-    if (n_out) *n_out = live;
-    if (live > cap) return fail(h, NBODY_ERR_CAPACITY, "nbody_grid_sample: buffer too small");
+    size_t live = 0;
+    const hipError_t e = live_rows(h, sh, n_upper, &live);
+    HIP_TRY(h, e);
+    if (const int rc = row_frame(h, "nbody_grid_sample", "out", live, out, cap, n_out)) return rc;
     if (counts) counts[0] = counts[1] = counts[2] = counts[3] = 0;
     if (!live) return NBODY_OK;
     const Grid g = deposit::grid_of(spec);

@@ -21,18 +21,30 @@ GRIDS = {
     "i16x16x1_z": ((-2.0, -2.0, 0.0), 0.25, (16, 16, 1), False, 2),
     "i32x32x32": ((-4.0, -4.0, -4.0), 0.25, (32, 32, 32), False, -1),  # (the GPU tests' extra shape)
     "p32x32x32": ((-4.0, -4.0, -4.0), 0.25, (32, 32, 32), True, -1),
+    "p1x8x8_x": ((0.0, -2.0, -2.0), 0.5, (1, 8, 8), True, 0),          # the ignored axis is x, then y: the GPU tests run these
+    "i1x8x8_x": ((0.0, -2.0, -2.0), 0.5, (1, 8, 8), False, 0),         # four under AXIS_WORLD
+    "p8x1x8_y": ((-2.0, 0.0, -2.0), 0.5, (8, 1, 8), True, 1),
+    "i8x1x8_y": ((-2.0, 0.0, -2.0), 0.5, (8, 1, 8), False, 1),
 }
 CPU_GRIDS = ("p8x8x8", "p16x8x4", "i8x4x2", "i16x16x1_z")
+AXIS_GRIDS = ("p1x8x8_x", "i1x8x8_x", "p8x1x8_y", "i8x1x8_y")
+AXIS_WORLD = "u300"
 WORLDS = ("n1", "n65", "w4099")
 
 
 def world(nb, name, f64):
     """The records of a world, in the handle's dtype: unequal masses, some bodies off a non-periodic grid (a Plummer sphere reaches
-    well past [-2, 2]^3) and, from 65 bodies on, one body that is not finite."""
-    n = {"n1": 1, "n63": 63, "n64": 64, "n65": 65, "n257": 257, "w4099": 4099}[name]
+    well past [-2, 2]^3) and, from 65 bodies on, one body that is not finite.  u300 (AXIS_WORLD): 300 bodies uniform in +-2.3 on every
+    axis, which straddles the faces of AXIS_GRIDS at +-2, with every 25th body moved 3.5 to 6 away from the centre on every axis:
+    off an isolated grid with its whole stencil, whatever the scheme."""
+    n = {"n1": 1, "n63": 63, "n64": 64, "n65": 65, "n257": 257, "u300": 300, "w4099": 4099}[name]
     rng = np.random.default_rng(sum(map(ord, name)))
     rec = nb.plummer(n, seed=17, f64=f64)
     rec["mass"] = rec["mass"] * rng.uniform(0.5, 1.5, n)
+    if name == AXIS_WORLD:
+        xyz = rng.uniform(-2.3, 2.3, (n, 3))
+        xyz[::25] = rng.uniform(3.5, 6.0, (len(xyz[::25]), 3)) * rng.choice((-1.0, 1.0), (len(xyz[::25]), 3))
+        rec["position"] = xyz
     if n >= 65:
         rec["position"][n // 2, 1] = np.nan
         rec["position"][3] = (9.0, -7.5, 0.25)   # off every grid here that is not periodic

@@ -23,6 +23,8 @@ CENTER, WIDE, NARROW = (0.0, 0.0, 0.0), 4.0e3, 4.0   # NARROW: the walls at -2 a
 DTYPES = pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
 WORLDS = ("n1", "n64", "n65", "w4099")
 GRIDS = ("p8x8x8", "p16x8x4", "i8x4x2", "i32x32x32")
+#: (world, its grids) of test 1: every world on every grid above, and the grids whose ignored axis is x or y under their own world
+WORLD_GRIDS = tuple((w, GRIDS) for w in WORLDS) + ((ref.AXIS_WORLD, ref.AXIS_GRIDS),)
 COMBOS = tuple(itertools.product(ref.SCHEMES, ref.GRADIENTS))
 KNOBS = ("mesh_kick_fuse", "mesh_keep_kernel", "pm_share_sort", "pm_gather", "deposit_sort", "sample_sort", "poisson_lds")
 G = 1.25            # the handle's g: what a pass reads
@@ -81,12 +83,12 @@ def stats(sim):
 
 # ------------------------------------------------------------------------------------------------ 1. update_forces
 @DTYPES
-@pytest.mark.parametrize("name", WORLDS)
-def test_update_forces_leaves_the_rounded_host_field_in_the_acc_rows(gpu, name, f64):
+@pytest.mark.parametrize("name,grids", WORLD_GRIDS, ids=[w for w, _ in WORLD_GRIDS])
+def test_update_forces_leaves_the_rounded_host_field_in_the_acc_rows(gpu, name, grids, f64):
     nb = gpu
     rec = world(name, f64)
     with make(nb, rec) as sim:
-        for grid, (scheme, gradient) in itertools.product(GRIDS, COMBOS):
+        for grid, (scheme, gradient) in itertools.product(grids, COMBOS):
             what = f"{name} {grid} scheme {scheme} gradient {gradient}"
             sim.mesh_gravity = mesh_of(grid, scheme, gradient)
             sim.update_forces()
@@ -99,6 +101,12 @@ def test_update_forces_leaves_the_rounded_host_field_in_the_acc_rows(gpu, name, 
             assert got["acceleration"].tobytes() == dev.astype(rec["position"].dtype).tobytes(), f"{what}: against F(pm_field) on the handle"
             for f in ("position", "velocity", "mass"):
                 assert got[f].tobytes() == rec[f].tobytes(), f"{what}: {f} was touched"
+            if grids is ref.AXIS_GRIDS:   # active rows and zero rows (that AXIS_WORLD meets every class: tests/test_pm_checker.py)
+                host = nb.host_pm_field(*ref.bodies(rec), origin, spacing, dims, float(rec["position"].dtype.type(G)), scheme, gradient, periodic,
+                                        project_axis=axis, **poisson_of(grid, gradient))
+                idle = host[2] >= 2   # outside and skipped: +0.0
+                assert not got["acceleration"][idle].any() and got["acceleration"][~idle].any(), what
+                assert not got["acceleration"][:, axis].any() and not np.signbit(got["acceleration"][:, axis]).any(), what
         assert sim.stats().steps == 0
 
 

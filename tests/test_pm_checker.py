@@ -44,6 +44,27 @@ def same_call(got, want, what):
             ref.same_bits(got[k], want[k], f"{what}: {name}")
 
 
+# ------------------------------------------------------------------------------------------------ 0. the GPU tests' axis world
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+def test_the_axis_world_meets_every_class_on_the_axis_grids(nb, f64):
+    """what tests/test_pm_gpu.py and test_mesh_gpu.py rely on: under AXIS_WORLD the host call reports, on the isolated grids of
+    AXIS_GRIDS, bodies inside, partial (of the deposit: CIC and TSC; the one cell of NGP is on the grid or off it), outside (every
+    25th body) and skipped (the body that is not finite), and rows of all four classes; on the periodic ones inside and skipped.
+    Nothing along the ignored axis."""
+    xyz, m = ref.bodies(ref.world(nb, ref.AXIS_WORLD, f64))
+    for grid, scheme, gradient in itertools.product(ref.AXIS_GRIDS, ref.SCHEMES, ref.GRADIENTS):
+        acc, _, cls, counts = host(nb, xyz, m, grid, scheme, gradient, **plan_of(grid, gradient))
+        what = f"{grid} scheme {scheme} gradient {gradient}: {counts}"
+        assert int(counts[:4].sum()) == 300 and int(counts[4:].sum()) == 300, what
+        if ref.GRIDS[grid][3]:
+            assert [int(v) for v in counts] == [299, 0, 0, 1, 299, 0, 0, 1] and set(cls.tolist()) == {0, 3}, what
+        else:
+            assert all(int(counts[k]) > 0 for k in ((0, 2, 3) if scheme == ref.NGP else (0, 1, 2, 3))), what
+            assert all(int(counts[4 + k]) > 0 for k in range(4)) and set(cls.tolist()) == {0, 1, 2, 3}, what
+        along = acc[:, ref.GRIDS[grid][4]]
+        assert not along.any() and not np.signbit(along).any(), what
+
+
 # ------------------------------------------------------------------------------------------------ 1. the same bits
 @pytest.mark.parametrize("world", ref.WORLDS)
 @pytest.mark.parametrize("grid_name", ref.CPU_GRIDS)

@@ -22,6 +22,11 @@ CENTER, WIDTH = (0.0, 0.0, 0.0), 4.0e3
 DTYPES = pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
 ALL_WORLDS = ("n1", "n63", "n64", "n65", "n257", "w4099")
 ALL_GRIDS = ref.CPU_GRIDS + ("i32x32x32",)
+#: (world, its grids) of test 1: every world on every grid above, and the grids whose ignored axis is x or y under their own world
+WORLD_GRIDS = tuple((w, ALL_GRIDS) for w in ALL_WORLDS) + ((ref.AXIS_WORLD, ref.AXIS_GRIDS),)
+PHI_NULL = (("p16x8x4", ref.TSC, ref.GRADIENT4), ("i8x4x2", ref.NGP, ref.GRADIENT2), ("i16x16x1_z", ref.CIC, ref.GRADIENT2))
+AXIS_PHI_NULL = (("i1x8x8_x", ref.TSC, ref.GRADIENT4), ("p1x8x8_x", ref.CIC, ref.GRADIENT2), ("p8x1x8_y", ref.NGP, ref.GRADIENT2),
+                 ("i8x1x8_y", ref.CIC, ref.GRADIENT4))
 KNOBS = ("pm_gather", "pm_share_sort", "deposit_sort", "sample_sort", "poisson_lds", "sample_pregrad")
 G = 1.25
 
@@ -91,6 +96,14 @@ def same_records(a, b, what):
         assert a[f].tobytes() == b[f].tobytes(), f"{what}: {f} differs"
 
 
+def same_classes(got, want, what):
+    """every class the host call reports appears on the device, among the deposit's counts, the rows' counts and the rows (that
+    AXIS_WORLD meets every class there is on the isolated grids of AXIS_GRIDS is asserted on the CPU: tests/test_pm_checker.py)"""
+    for k in range(4):
+        assert int(want[3][k]) == 0 or int(got[3][k]) > 0, f"{what}: class {k} of the deposit is missing"
+        assert int(want[3][4 + k]) == 0 or (int(got[3][4 + k]) > 0 and (got[2] == k).any()), f"{what}: class {k} of the rows is missing"
+
+
 def set_plan(sim, plan):
     for knob, v in zip(KNOBS, plan):
         sim.set_tuning(knob, v)
@@ -98,19 +111,24 @@ def set_plan(sim, plan):
 
 # ------------------------------------------------------------------------------------------------ 1. the host call's bytes
 @DTYPES
-@pytest.mark.parametrize("name", ALL_WORLDS)
-def test_acc_phi_cls_and_counts_are_the_host_call_s_byte_for_byte(gpu, name, f64):
+@pytest.mark.parametrize("name,grids", WORLD_GRIDS, ids=[w for w, _ in WORLD_GRIDS])
+def test_acc_phi_cls_and_counts_are_the_host_call_s_byte_for_byte(gpu, name, grids, f64):
     nb = gpu
     rec = world(name, f64)
     n = len(rec)
     with make(nb, rec) as sim:
-        for grid, scheme, gradient in itertools.product(ALL_GRIDS, ref.SCHEMES, ref.GRADIENTS):
+        for grid, scheme, gradient in itertools.product(grids, ref.SCHEMES, ref.GRADIENTS):
             what = f"{name} {grid} scheme {scheme} gradient {gradient}"
             got = field(sim, grid, scheme, gradient)
-            same_call(got, expected(name, f64, grid, scheme, gradient), what)
+            want = expected(name, f64, grid, scheme, gradient)
+            same_call(got, want, what)
+            same_classes(got, want, what)
             assert got[0].shape == (n, 3) and got[1].shape == (n,) and int(got[3][:4].sum()) == n and int(got[3][4:].sum()) == n, what
+            if ref.GRIDS[grid][4] >= 0:   # nothing along the ignored axis: +0.0 on every row
+                along = got[0][:, ref.GRIDS[grid][4]]
+                assert not along.any() and not np.signbit(along).any(), what
         # phi NULL, cls and counts NULL
-        for grid, scheme, gradient in (("p16x8x4", ref.TSC, ref.GRADIENT4), ("i8x4x2", ref.NGP, ref.GRADIENT2), ("i16x16x1_z", ref.CIC, ref.GRADIENT2)):
+        for grid, scheme, gradient in (AXIS_PHI_NULL if grids is ref.AXIS_GRIDS else PHI_NULL):
             want = expected(name, f64, grid, scheme, gradient)
             got = field(sim, grid, scheme, gradient, phi=False)
             assert got[1] is None
@@ -150,6 +168,27 @@ def test_every_plan_gives_the_same_bytes_and_the_stats_tell_them_apart(gpu, f64)
     nb = gpu
     name = "w4099"
     rec = world(name, f64)
+    # the grids whose ignored axis is x or y, under their own world: every scheme and both gradients under every plan
+    with make(nb, world(ref.AXIS_WORLD, f64)) as sim:
+        for grid, scheme, gradient in itertools.product(ref.AXIS_GRIDS, ref.SCHEMES, ref.GRADIENTS):
+            want = expected(ref.AXIS_WORLD, f64, grid, scheme, gradient)
+            reads = {}
+            for plan in plans():
+                set_plan(sim, plan)
+                what = f"{grid} scheme {scheme} gradient {gradient} plan {plan}"
+                got = field(sim, grid, scheme, gradient)
+                same_call(got, want, what)
+                same_classes(got, want, what)
+                gather, share, dsort, ssort, lds, pregrad = plan
+                shared = share and dsort and ssort
+                stats = [int(v) for v in sim.pm_field_stats()]
+                assert stats[0] == 1 and stats[1] == (gather | (2 if shared else 0)), (what, stats)
+                assert stats[3] == (1 if shared else dsort + ssort), (what, stats)
+                reads.setdefault((gather, pregrad), set()).add(stats[2])
+                if plan[1:] == (1, 1, 1, 1, 0):   # phi NULL under both gathers
+                    same_call(field(sim, grid, scheme, gradient, phi=False), want, f"{what}: phi NULL")
+            assert all(len(v) == 1 for v in reads.values()), reads
+            assert 0 < min(reads[(1, 0)]) <= min(reads[(0, 0)]), reads
     with make(nb, rec) as sim:
         assert [sim.get_tuning(k) for k in KNOBS] == [1, 1, 1, 1, 1, 0]
         for grid, scheme, gradient in (("p16x8x4", ref.TSC, ref.GRADIENT2), ("i32x32x32", ref.CIC, ref.GRADIENT4), ("i16x16x1_z", ref.NGP, ref.GRADIENT2),
