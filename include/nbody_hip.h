@@ -1266,7 +1266,8 @@ int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]);
  * CIC and TSC.  A body feels its own mesh image: its mass is part of M, nothing subtracts it, and phi at a body includes
  * the body's own smeared potential (with soften = 0 on an isolated grid the own cell alone contributes nothing).  Momentum is conserved
  * -- sum m_i acc_i = 0 to rounding -- ONLY BECAUSE deposit and sample share one stencil (deposit_grid.h's), and on a periodic
- * grid; bodies off an isolated grid push and are not pushed.  There is no short-range correction: this is PM, not P3M or TreePM.
+ * grid; bodies off an isolated grid push and are not pushed.  There is no short-range correction: this is PM, not P3M or TreePM
+ * ("P3M field" below adds one on periodic grids).
  *   nbody_pm_field: rows in nbody_download's order, *n_out = the live count; cap = the rows acc (and phi, cls) hold; cap
  * smaller than the live count: NBODY_ERR_CAPACITY with *n_out set and nothing written.  n == 0: NBODY_OK, counts zeroed,
  * nothing else written.  nbody_pm_field_at on a handle that holds no body: every output is +0.0.  phi, cls, n_out and counts
@@ -1304,7 +1305,7 @@ int nbody_grid_poisson_stats(NbodyHandle* h, uint64_t out[4]);
  * NBODY_DEPOSIT_MASS; pm NULL; a gradient that is not NBODY_SAMPLE_GRADIENT2 or NBODY_SAMPLE_GRADIENT4; reserved words that
  * are not 0; acc NULL with rows to write; xyz NULL with n_points > 0 (the device call); n_points > 2^31 - 1; handles of a
  * multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
- *   OUT OF SCOPE, in this order: a short-range (TreePM) split; real-to-complex transforms; a world-wide mesh energy;
+ *   OUT OF SCOPE, in this order: a short-range split HERE (nbody_p3m_field below is its own call); real-to-complex transforms; a world-wide mesh energy;
  * multi-rank handles.  (A PM term in the step is "mesh gravity" below, which also keeps an isolated grid's transformed kernel
  * between its passes; nbody_pm_field itself makes it at every call, as before.) */
 typedef struct NbodyPmSpec {
@@ -1323,6 +1324,91 @@ int nbody_host_pm_field(const double* body_xyz, const double* body_m, size_t n_b
                         const double* xyz /* NULL: the bodies themselves */, size_t n_points,
                         double* acc, double* phi, uint8_t* cls, uint64_t counts[8]);
 int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]);
+/* ---- P3M field: the mesh field plus an exact short-range pair sum (no reference counterpart) ------------------------------
+ * The particle-mesh field above resolves about two cells.  nbody_p3m_field (at the bodies) and nbody_p3m_field_at (at n_points
+ * caller points) split 1/r with a Gaussian of scale r_split: the mesh carries the smooth long-range part, and a periodic,
+ * minimum-image pair sum over the bodies closer than r_cut carries the rest.  PERIODIC GRIDS ONLY.  g is p3m->pm.poisson.g.
+ * All of it is f64, every operation rounded on its own, nothing contracted into an FMA (csrc/p3m_pairs.h states it once for the
+ * device and the host; tests/p3m_ref.py restates it in numpy).  THE DEFINITION:
+ *   MESH PART.  nbody_host_pm_field's composition (above) with one change in the periodic Green stage: the per-axis factor
+ * table is D'[i] = D[i] S[i], one product made on the host, S[i] = exp(-(K[i] (r_split r_split))) with the K[i] the stage
+ * uses already; D[i] = 1 when deconvolve = 0, so the f = f ((Dx Dy) Dz) branch is always taken.  The device evaluates no
+ * exponential, k_poisson_green is unchanged, and nbody_grid_poisson's public spec does not know the split.
+ *   SHORT-RANGE PART.  With x = r / r_split, F(x) = erfc(x / 2) + (x / sqrt(pi)) exp(-x^2 / 4) multiplies the Newtonian force and
+ * P(x) = erfc(x / 2) the Newtonian potential.  nbody_host_p3m_table tabulates both at x_k = k h, h = (r_cut / r_split) / 4096.0,
+ * k = 0 .. 4096, from std::erfc and std::exp:
+ *     x = double(k) h;  e = erfc(x / 2.0);  T[k].F = e + (x / SQRT_PI) exp(-((x x) / 4.0));  T[k].P = e
+ * SQRT_PI = 1.7724538509055159.  The table is uploaded; the device interpolates linearly and never evaluates erfc.
+ *     chain cells  c = the smallest power of two with c spacing >= r_cut.  A body's chain cell is its NGP home cell
+ *                  (floor(u_c), u_c = (x_c - origin_c) / spacing, wrapped into [0, dims_c)) shifted right by log2(c) on each axis.
+ *                  A body that nbody_deposit SKIPS (x, y, z or m not finite, or !(|u_c| < 2^31)) has no chain cell: it feels and
+ *                  exerts no short-range term (its short part is +0.0).  A caller's point takes the same rule with m = 0.0.
+ *     partners     of target i: the bodies of the 27 chain cells around its own, visited dx = -1, 0, +1 outermost, then dy, then
+ *                  dz innermost, chain indices wrapped; within a cell in ascending row; at the bodies j == i is left out.
+ *     term         d_c = x_j,c - x_i,c, then d_c = d_c - rint(d_c / L_c) L_c with L_c = double(dims_c) spacing;
+ *                  r2 = (dx dx + dy dy) + dz dz.  The term counts iff r2 < R2 STRICTLY, R2 = r_cut r_cut, and is skipped when
+ *                  r2 == 0 and soften == 0.  r = sqrt(r2), t = r (4096.0 / r_cut), k = min((int) t, 4095), fr = t - double(k);
+ *                  Fv = T[k].F + fr (T[k + 1].F - T[k].F), Pv likewise;  s2 = r2 + soften soften, inv = 1.0 / sqrt(s2),
+ *                  inv3 = (inv inv) inv.
+ *     sums         ax, ay, az, ph start at +0.0 and run in that one sequential order:  a_c = a_c + ((m_j inv3) Fv) d_c,
+ *                  ph = ph + (m_j inv) Pv.  At the end acc_short_c = g a_c and phi_short = 0.0 - g ph.
+ *   TOTAL.  acc = acc_mesh + acc_short and phi = phi_mesh + phi_short, one addition each.  NBODY_P3M_MESH_ONLY and
+ * NBODY_P3M_SHORT_ONLY return the one part (diagnostic: both still run the mesh stages, because cls and counts are the MESH
+ * PART's under every value of terms).  THE ORDER IS PART OF THE DEFINITION: it depends on the state and the spec only, never on
+ * the launch shape, so the device (under both plans), the host and the restatement give the same bits, on NBODY_F32 and
+ * NBODY_F64 handles alike (positions and masses widened exactly).
+ *   PHYSICS.  phi at a body still contains the body's own long-range image, -g m / (r_split sqrt(pi)), as nbody_pm_field's
+ * contains its smeared image; nothing subtracts it.  r2, the table index and d are exactly antisymmetric in (i, j), so
+ * sum m_i acc_short_i vanishes to rounding.  The walk sees every pair whose minimum-image distance is below r_cut, up to the
+ * rounding of u at cell faces: DESIGN 3.30 states and proves the margin.
+ *   Argument shapes, the NULL rules, the capacity rule, the n == 0 rule, cls and counts are nbody_pm_field's, word for word, and
+ * so is the READ-ONLY contract: scratch is ONE allocation through the handle's registry, freed inside the call; a call leaves
+ * nothing behind but the record nbody_p3m_field_stats reads -- the records of nbody_pm_field_stats, nbody_deposit_stats,
+ * nbody_grid_sample_stats and nbody_grid_poisson_stats stay as they were.
+ *   HOW (csrc/nbody_p3m.cpp, csrc/kernels_p3m.hip).  The mesh stages are nbody_pm_field's own, reused with their knobs; no
+ * grid crosses the bus.  The bodies are keyed by chain cell, ordered by the stable rocPRIM sort the grid calls use, gathered
+ * into that order as {x, y, z, m}, and a dense cell-start table is made by binary search (the chain grid has at most
+ * (dims / c)^3 cells).  k_p3m_short<kAtPoints, kLds>: one block of 128 lanes per chain cell (a block whose cell holds no target
+ * leaves at once); lanes own the cell's targets, in tiles of 128 when it holds more; the partner stream of the 27 cells is
+ * staged through LDS in the defined order as position, mass and row, and every lane runs the same sequential sums.  The pair
+ * counts are integers formed on the device.  No floating-point atomics.  One synchronisation at the end (at the bodies a second
+ * one, for the live count, as in nbody_pm_field).  nbody_p3m_field_at orders its points by their own chain cell, has no self
+ * term and works in the sampler's batches.  One knob, which changes no result:
+ *     p3m_lds (default 1)  0: one lane per target reading the partners from global memory, the plain variant and cross-check
+ *   nbody_p3m_field_stats: out = {1 once a call on this handle reached the device else 0, the plan of the last such call as
+ * p3m_lds | (nbody_pm_field_stats's plan word) << 1, the partners looked at (self left out), the terms with r2 < R2}; the two
+ * pair counts depend on the state and the spec only.  A DIAGNOSTIC AID, NOT A STABLE CONTRACT.
+ *   NOT TIMED ON AN MI355X beyond the single run of tools/p3m_bench.py that DESIGN 3.30 records.  Nothing asserts or promises a
+ * time.
+ *   Refused with NBODY_ERR_INVALID (nbody_last_error names the call): whatever nbody_pm_field refuses; p3m NULL; a grid that is
+ * not periodic; project_axis != -1; any dims_c / c < 4 (the three neighbour cells on an axis must be distinct); r_split not
+ * finite or <= 0; r_cut not finite or outside r_split .. 8 r_split; soften not finite or < 0; an unknown terms; reserved != 0;
+ * handles of a multi-rank world and NBODY_SHARD_SPATIAL handles.  A NULL handle is refused without touching a device.
+ * nbody_host_p3m_table refuses the same r_split and r_cut and a NULL out.
+ *   OUT OF SCOPE: P3M in the step; isolated grids; TreePM; subtracting the self image from phi; a mesh energy; optimal
+ * (Hockney-Eastwood) influence functions and interlacing; multi-rank handles. */
+#define NBODY_P3M_TABLE_INTERVALS 4096
+enum { NBODY_P3M_BOTH = 0, NBODY_P3M_MESH_ONLY = 1, NBODY_P3M_SHORT_ONLY = 2 };
+typedef struct NbodyP3mSpec {
+    NbodyPmSpec pm;      /* as for nbody_pm_field; periodic grids only */
+    double  r_split;     /* r_s > 0, finite: the Gaussian split scale, a length */
+    double  r_cut;       /* finite, r_split <= r_cut <= 8 r_split: short-range terms end here */
+    double  soften;      /* Plummer epsilon >= 0 of the short-range term, finite */
+    int32_t terms;       /* NBODY_P3M_BOTH, NBODY_P3M_MESH_ONLY or NBODY_P3M_SHORT_ONLY */
+    int32_t reserved;    /* 0 */
+} NbodyP3mSpec;
+int nbody_p3m_field(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyP3mSpec* p3m,
+                    double* acc /* [n][3] */, double* phi /* [n], may be NULL */, uint8_t* cls /* [n], may be NULL */,
+                    size_t cap, size_t* n_out, uint64_t counts[8] /* may be NULL */);
+int nbody_p3m_field_at(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyP3mSpec* p3m,
+                       const double* xyz /* [n_points][3] */, size_t n_points,
+                       double* acc, double* phi, uint8_t* cls, uint64_t counts[8]);
+int nbody_host_p3m_field(const double* body_xyz, const double* body_m, size_t n_bodies,
+                         const NbodyGridSpec* spec, const NbodyP3mSpec* p3m,
+                         const double* xyz /* NULL: the bodies themselves */, size_t n_points,
+                         double* acc, double* phi, uint8_t* cls, uint64_t counts[8]);
+int nbody_host_p3m_table(double r_split, double r_cut, double* out /* [4097][2] = {F, P} */);
+int nbody_p3m_field_stats(NbodyHandle* h, uint64_t out[4]);
 /* ---- mesh gravity: the particle-mesh field as the self-gravity of the step (no reference counterpart) --------------------
  * nbody_set_mesh_gravity(h, spec, pm): while set, the self-gravity pass of every step and of nbody_update_forces IS the mesh
  * field of nbody_pm_field; no pair kernel is launched.  spec == NULL and pm == NULL: off.  NO NEW ARITHMETIC.  THE DEFINITION:
@@ -1430,7 +1516,7 @@ const char* nbody_last_error(const NbodyHandle* h); /* h may be NULL: last creat
  * deposit_lds (nbody_deposit: the plan, defaults 1, 1, 1; they change no result), sample_sort, sample_pregrad (nbody_grid_sample and
  * nbody_grid_sample_at: the plan, defaults 1, 0; they change no result), poisson_lds, poisson_tile (nbody_grid_poisson: the plan,
  * defaults 1, 16; they change no result), pm_gather, pm_share_sort (nbody_pm_field and nbody_pm_field_at: the plan, defaults 1, 1; they
- * change no result), mesh_kick_fuse, mesh_keep_kernel (mesh gravity: the plan, defaults 1, 1; they change no result); the
+ * change no result), p3m_lds (nbody_p3m_field and nbody_p3m_field_at: the plan, default 1; it changes no result), mesh_kick_fuse, mesh_keep_kernel (mesh gravity: the plan, defaults 1, 1; they change no result); the
  * environment switches NBODY_CROSS_SYM, NBODY_SYM_PACKED, NBODY_BF_VARIANT, NBODY_SYM_WPB
  * and NBODY_BH_SPLIT preset them at nbody_create.  cross_sym, sym_packed and bf_fast_variant are part of what the ranks of a
  * world agree on at nbody_comm_init and cannot change afterwards.  bh_walk_variant, bh_walk_lds_block, bh_hot_cap,

@@ -114,6 +114,7 @@ DECLARED_SYMBOLS = [
     "nbody_grid_sample", "nbody_grid_sample_at", "nbody_host_grid_sample", "nbody_grid_sample_stats",
     "nbody_grid_poisson", "nbody_host_grid_poisson", "nbody_host_poisson_twiddles", "nbody_grid_poisson_stats",
     "nbody_pm_field", "nbody_pm_field_at", "nbody_host_pm_field", "nbody_pm_field_stats",
+    "nbody_p3m_field", "nbody_p3m_field_at", "nbody_host_p3m_field", "nbody_host_p3m_table", "nbody_p3m_field_stats",
     "nbody_set_mesh_gravity", "nbody_get_mesh_gravity", "nbody_mesh_gravity_stats",
     "nbody_set_pair_search", "nbody_get_pair_search", "nbody_pair_search_stats", "nbody_host_cell_grid",
 ]
@@ -154,6 +155,16 @@ class NbodyPoissonSpec(C.Structure):
 class NbodyPmSpec(C.Structure):
     """NbodyPmSpec (include/nbody_hip.h, "particle-mesh field"): the Poisson constants and the gradient of one nbody_pm_field call."""
     _fields_ = [("poisson", NbodyPoissonSpec), ("gradient", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+P3M_TABLE_INTERVALS = 4096
+P3M_BOTH, P3M_MESH_ONLY, P3M_SHORT_ONLY = 0, 1, 2
+
+
+class NbodyP3mSpec(C.Structure):
+    """NbodyP3mSpec (include/nbody_hip.h, "P3M field"): the PM spec, the split scale, the cutoff, the softening and the terms."""
+    _fields_ = [("pm", NbodyPmSpec), ("r_split", C.c_double), ("r_cut", C.c_double), ("soften", C.c_double), ("terms", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class NbodyExternalComponent(C.Structure):
@@ -354,6 +365,12 @@ _sig("nbody_pm_field_at", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C
 _sig("nbody_host_pm_field", _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.c_void_p, _sz, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p)
 _sig("nbody_pm_field_stats", _i, _H, C.POINTER(C.c_uint64))
+_sig("nbody_p3m_field", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyP3mSpec), C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.POINTER(_sz), C.c_void_p)
+_sig("nbody_p3m_field_at", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyP3mSpec), C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("nbody_host_p3m_field", _i, C.c_void_p, C.c_void_p, _sz, C.POINTER(GridSpec), C.POINTER(NbodyP3mSpec), C.c_void_p, _sz, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p)
+_sig("nbody_host_p3m_table", _i, C.c_double, C.c_double, C.c_void_p)
+_sig("nbody_p3m_field_stats", _i, _H, C.POINTER(C.c_uint64))
 _sig("nbody_set_mesh_gravity", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec))
 _sig("nbody_get_mesh_gravity", _i, _H, C.POINTER(GridSpec), C.POINTER(NbodyPmSpec), C.POINTER(C.c_int))
 _sig("nbody_mesh_gravity_stats", _i, _H, C.POINTER(C.c_uint64))
@@ -597,6 +614,48 @@ def host_pm_field(bodies, mass, origin, spacing, dims, g, scheme=DEPOSIT_CIC, gr
                                  cls.ctypes.data if n else None, counts.ctypes.data)
     if rc:
         raise NbodyError(rc, "nbody_host_pm_field: the call is not valid (include/nbody_hip.h lists what is refused)")
+    return acc, val, cls, counts
+
+
+def p3m_spec(g, r_split, r_cut, gradient=SAMPLE_GRADIENT2, green=POISSON_SPECTRAL, deconvolve=0, soften=0.0, terms=P3M_BOTH) -> NbodyP3mSpec:
+    """An NbodyP3mSpec from plain values: pm_spec's constants (the mesh's own soften is 0: periodic grids only), the split scale
+    r_split, the cutoff r_cut, the Plummer softening of the short-range term and P3M_BOTH, P3M_MESH_ONLY or P3M_SHORT_ONLY."""
+    return NbodyP3mSpec(pm_spec(g, gradient, green, 0.0, deconvolve), float(r_split), float(r_cut), float(soften), int(terms), 0)
+
+
+def host_p3m_table(r_split, r_cut) -> np.ndarray:
+    """[4097, 2] f64: the split factors {F, P} at x_k = k (r_cut / r_split) / 4096 (nbody_host_p3m_table; no device needed)."""
+    out = np.zeros((P3M_TABLE_INTERVALS + 1, 2), np.float64)
+    rc = lib.nbody_host_p3m_table(float(r_split), float(r_cut), out.ctypes.data)
+    if rc:
+        raise NbodyError(rc, "nbody_host_p3m_table: r_split must be finite and > 0 and r_cut finite in r_split .. 8 r_split")
+    return out
+
+
+def host_p3m_field(bodies, mass, origin, spacing, dims, g, r_split, r_cut, scheme=DEPOSIT_CIC, gradient=SAMPLE_GRADIENT2, green=POISSON_SPECTRAL,
+                   deconvolve=0, soften=0.0, terms=P3M_BOTH, points=None, phi=True) -> tuple[np.ndarray, np.ndarray | None, np.ndarray, np.ndarray]:
+    """(acc [n, 3] f64, phi [n] f64 | None, cls [n] uint8, counts [8] uint64): the P3M field of the bodies [nb][3] with masses [nb]
+    on a periodic grid, at the bodies themselves or at points [n][3] -- host_pm_field with the Gaussian split of scale r_split in
+    its Green stage plus the minimum-image pair sum of the bodies closer than r_cut (nbody_host_p3m_field; no device needed)."""
+    bxyz = np.ascontiguousarray(np.asarray(bodies, np.float64).reshape(-1, 3))
+    bm = np.ascontiguousarray(np.asarray(mass, np.float64).reshape(-1))
+    if len(bm) != len(bxyz):
+        raise ValueError("host_p3m_field: mass must hold one value per body")
+    spec = grid_spec(origin, spacing, dims, scheme, DEPOSIT_MASS, True, -1)
+    p3m = p3m_spec(g, r_split, r_cut, gradient, green, deconvolve, soften, terms)
+    xyz = None if points is None else np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n = len(bxyz) if xyz is None else len(xyz)
+    acc = np.zeros((n, 3), np.float64)
+    val = np.zeros(n, np.float64) if phi else None
+    cls = np.zeros(n, np.uint8)
+    counts = np.zeros(8, np.uint64)
+    hold = np.zeros(3, np.float64)   # (a non-NULL xyz even for no point: NULL means the bodies)
+    xp = None if xyz is None else (xyz.ctypes.data if len(xyz) else hold.ctypes.data)
+    rc = lib.nbody_host_p3m_field(bxyz.ctypes.data if len(bxyz) else None, bm.ctypes.data if len(bm) else None, len(bxyz), C.byref(spec),
+                                  C.byref(p3m), xp, 0 if xyz is None else len(xyz), acc.ctypes.data if n else None,
+                                  val.ctypes.data if phi and n else None, cls.ctypes.data if n else None, counts.ctypes.data)
+    if rc:
+        raise NbodyError(rc, "nbody_host_p3m_field: the call is not valid (include/nbody_hip.h lists what is refused)")
     return acc, val, cls, counts
 
 
@@ -1168,6 +1227,43 @@ class Simulation:
         the grid reads of its gather, the radix sorts it enqueued} (nbody_pm_field_stats)."""
         out = (C.c_uint64 * 4)()
         self._check(lib.nbody_pm_field_stats(self._h, out))
+        return np.array(out[:], np.uint64)
+
+    # -- P3M field (nbody_p3m_field, nbody_p3m_field_at): the mesh field with a Gaussian split plus the short-range pair sum
+    def p3m_field(self, origin, spacing, dims, g, r_split, r_cut, scheme=DEPOSIT_CIC, gradient=SAMPLE_GRADIENT2, green=POISSON_SPECTRAL,
+                  deconvolve=0, soften=0.0, terms=P3M_BOTH, points=None, phi=True) -> tuple[np.ndarray, np.ndarray | None, np.ndarray, np.ndarray]:
+        """(acc [n, 3] f64, phi [n] f64 | None, cls [n] uint8, counts [8] uint64): the P3M field of the handle's bodies on a periodic
+        grid, at the bodies, in get_points() order, or at points [n][3].  The same bits as host_p3m_field, whatever the plan
+        (nbody_p3m_field, nbody_p3m_field_at)."""
+        spec = grid_spec(origin, spacing, dims, scheme, DEPOSIT_MASS, True, -1)
+        p3m = p3m_spec(g, r_split, r_cut, gradient, green, deconvolve, soften, terms)
+        counts = np.zeros(8, np.uint64)
+        if points is not None:
+            xyz = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+            n = len(xyz)
+            acc = np.zeros((n, 3), np.float64)
+            val = np.zeros(n, np.float64) if phi else None
+            cls = np.zeros(n, np.uint8)
+            self._check(lib.nbody_p3m_field_at(self._h, C.byref(spec), C.byref(p3m), xyz.ctypes.data if n else None, n, acc.ctypes.data if n else None,
+                                               val.ctypes.data if phi and n else None, cls.ctypes.data if n else None, counts.ctypes.data))
+            return acc, val, cls, counts
+        # (sized from the capacity, not from nbody_count, which would refresh the host's view of the body count: potentials())
+        cfg = NbodyConfig()
+        self._check(lib.nbody_get_config(self._h, C.byref(cfg)))
+        cap = max(int(cfg.capacity), 1)
+        acc = np.zeros((cap, 3), np.float64)
+        val = np.zeros(cap, np.float64) if phi else None
+        cls = np.zeros(cap, np.uint8)
+        n = C.c_size_t(0)
+        self._check(lib.nbody_p3m_field(self._h, C.byref(spec), C.byref(p3m), acc.ctypes.data, val.ctypes.data if phi else None, cls.ctypes.data, cap,
+                                        C.byref(n), counts.ctypes.data))
+        return acc[: n.value], None if val is None else val[: n.value], cls[: n.value], counts
+
+    def p3m_field_stats(self) -> np.ndarray:
+        """[4] uint64: {1 once a P3M call reached the device, the plan the last one used (p3m_lds | pm_field_stats's plan word << 1),
+        the partners its pair sum looked at, the terms with r2 < R2} (nbody_p3m_field_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._check(lib.nbody_p3m_field_stats(self._h, out))
         return np.array(out[:], np.uint64)
 
     # -- mesh gravity (nbody_set_mesh_gravity): the particle-mesh field as the self-gravity of every step and of update_forces

@@ -51,6 +51,7 @@ struct Tuning {
     int poisson_tile = 16;      // k_poisson_fft_lds, the strided axes: z-adjacent lines per block, 1 .. 64, rounded down to a power of two and to what fits
     int pm_gather = 1;          // nbody_pm_field(_at): 1 k_pm_gather, acc and phi off one stencil set-up; 0 two k_sample launches and a negation (kernels_pm.h Plan)
     int pm_share_sort = 1;      // nbody_pm_field: 1 one home-cell order serves k_deposit and the gather when deposit_sort and sample_sort are both on; 0 each stage sorts
+    int p3m_lds = 1;            // nbody_p3m_field(_at): 1 k_p3m_short stages the partner stream of the 27 chain cells through LDS; 0 every lane reads its partners from global memory, the cross-check (kernels_p3m.h Plan)
     int mesh_kick_fuse = 1;     // mesh gravity: 1 k_mesh_kick, the gather rounds into the acc rows and takes a step's kick along; 0 the f64 rows of nbody_pm_field's gather, k_mesh_round and the leapfrog's own kick (kernels_mesh.h Plan)
     int mesh_keep_kernel = 1;   // mesh gravity, isolated grids: 1 the transformed kernel is made once per spec and kept, two 3-D transforms a pass; 0 made at every pass, three
     // the following select code that only the tuning build carries (make -C csrc tuning: -DNBODY_TUNING); the release

@@ -16,6 +16,7 @@
 #include "nbody_paircount.h"
 #include "nbody_deposit.h"
 #include "nbody_pm.h"
+#include "nbody_p3m.h"
 #include "nbody_mesh.h"
 #include "nbody_poisson.h"
 #include "nbody_sample.h"
@@ -822,6 +823,45 @@ int nbody_host_pm_field(const double* body_xyz, const double* body_m, size_t n_b
 
 int nbody_pm_field_stats(NbodyHandle* h, uint64_t out[4]) { return last_stats(h, "nbody_pm_field_stats", &NbodyHandle::pm_last, out); }
 
+// ---- P3M field (nbody_p3m.cpp): two read-only calls under the census's contract, and their host twins
+namespace {
+int p3m_enter(NbodyHandle* h, const char* call, const NbodyGridSpec* spec, const NbodyP3mSpec* p3m) {
+    int rc = diag_enter(h, call);
+    if (rc) return rc;
+    const std::string why = nbody::p3m::call_refusal(spec, p3m);
+    if (!why.empty()) return fail(h, NBODY_ERR_INVALID, std::string(call) + ": " + why);
+    return NBODY_OK;
+}
+}  // namespace
+
+int nbody_p3m_field(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyP3mSpec* p3m, double* acc, double* phi, uint8_t* cls, size_t cap,
+                    size_t* n_out, uint64_t counts[8]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = p3m_enter(h, "nbody_p3m_field", spec, p3m);
+    if (rc) return rc;
+    return with_bodies(h, [&](auto& b) { return nbody::p3m::at_bodies(h, b.sh, b.n_local, *spec, *p3m, acc, phi, cls, cap, n_out, counts); });
+}
+
+int nbody_p3m_field_at(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyP3mSpec* p3m, const double* xyz, size_t n_points, double* acc,
+                       double* phi, uint8_t* cls, uint64_t counts[8]) {
+    if (!h) return NBODY_ERR_INVALID;
+    int rc = p3m_enter(h, "nbody_p3m_field_at", spec, p3m);
+    if (rc) return rc;
+    if (n_points > size_t(0x7fffffff)) return fail(h, NBODY_ERR_INVALID, "nbody_p3m_field_at: n_points must not exceed 2^31 - 1");
+    if (n_points && !xyz) return fail(h, NBODY_ERR_INVALID, "nbody_p3m_field_at: xyz is NULL");
+    if (n_points && !acc) return fail(h, NBODY_ERR_INVALID, "nbody_p3m_field_at: acc is NULL");
+    return with_bodies(h, [&](auto& b) { return nbody::p3m::at_points(h, b.sh, b.n_local, *spec, *p3m, xyz, n_points, acc, phi, cls, counts); });
+}
+
+int nbody_host_p3m_field(const double* body_xyz, const double* body_m, size_t n_bodies, const NbodyGridSpec* spec, const NbodyP3mSpec* p3m,
+                         const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t counts[8]) {
+    return nbody::p3m::host_entry(body_xyz, body_m, n_bodies, spec, p3m, xyz, n_points, acc, phi, cls, counts);
+}
+
+int nbody_host_p3m_table(double r_split, double r_cut, double* out) { return nbody::p3m::host_table(r_split, r_cut, out); }
+
+int nbody_p3m_field_stats(NbodyHandle* h, uint64_t out[4]) { return last_stats(h, "nbody_p3m_field_stats", &NbodyHandle::p3m_last, out); }
+
 // ---- mesh gravity (nbody_mesh.cpp): a setting of the handle that its force passes read
 int nbody_set_mesh_gravity(NbodyHandle* h, const NbodyGridSpec* spec, const NbodyPmSpec* pm) {
     if (!h) return NBODY_ERR_INVALID;
@@ -1394,6 +1434,7 @@ const Knob kKnobs[] = {
     {"sample_sort", &nbody::Tuning::sample_sort, false}, {"sample_pregrad", &nbody::Tuning::sample_pregrad, false},
     {"poisson_lds", &nbody::Tuning::poisson_lds, false}, {"poisson_tile", &nbody::Tuning::poisson_tile, false},
     {"pm_gather", &nbody::Tuning::pm_gather, false}, {"pm_share_sort", &nbody::Tuning::pm_share_sort, false},
+    {"p3m_lds", &nbody::Tuning::p3m_lds, false},
     {"mesh_kick_fuse", &nbody::Tuning::mesh_kick_fuse, false}, {"mesh_keep_kernel", &nbody::Tuning::mesh_keep_kernel, false},
     {"bh_walk_variant", &nbody::Tuning::bh_walk_variant, true}, {"bh_walk_lds_block", &nbody::Tuning::bh_walk_lds_block, true},
     {"bh_hot_cap", &nbody::Tuning::bh_hot_cap, true}, {"bh_walk_debug", &nbody::Tuning::bh_walk_debug, true},

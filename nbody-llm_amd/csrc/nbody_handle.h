@@ -640,6 +640,7 @@ struct NbodyHandle {
     uint64_t poisson_last[4] = {0, 0, 0, 0};   // nbody_grid_poisson_stats: {a call reached the device, the plan it used, butterfly launches, complex points transformed}
     uint64_t sample_last[4] = {0, 0, 0, 0};    // nbody_grid_sample_stats: {a call reached the device, the plan it used, grid reads of k_sample, 0}
     uint64_t pm_last[4] = {0, 0, 0, 0};        // nbody_pm_field_stats: {a call reached the device, the plan it used, grid reads of the gather, radix sorts enqueued}
+    uint64_t p3m_last[4] = {0, 0, 0, 0};       // nbody_p3m_field_stats: {a call reached the device, the plan it used, partners looked at, terms with r2 < R2}
 
     // multi-GPU: what carries the exchanges (RCCL, or the one-device transport of transport_ipc.hip)
     std::unique_ptr<nbody::Transport> tp;

@@ -11,16 +11,6 @@
 
 namespace nbody { namespace pm {
 
-namespace {
-
-// what one pass over rows brings down
-struct Down {
-    deposit::Words dep{};
-    sample::Words rows{}, value{};
-};
-
-}  // namespace
-
 // (the contracts of the stages are nbody_pm.h's)
 const int* enqueue_shared_order(NbodyHandle* h, const Call& c, const int* count, size_t n, bool shared, const Scratch& w, Enqueued& st, Tally& tally) {
     if (!shared) return nullptr;
@@ -45,7 +35,7 @@ void enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const Nbo
     }
     st.last();
     int made = 0;
-    if (st.ok()) st.hip(poisson::enqueue(h, spec, pm.poisson, c.shape, c.tables, c.plans.poi, w.poi, nullptr, &made, held));
+    if (st.ok()) st.hip(poisson::enqueue(h, spec, pm.poisson, c.shape, c.tables, c.plans.poi, w.poi, nullptr, &made, held, c.split));
     if (st.ok()) tally.transforms += uint64_t(made);
     if (st.ok() && c.plans.grad.pregrad) {
         sample::launch_diff(s, c.g, c.op, w.smp);
@@ -76,9 +66,6 @@ void enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, boo
     else (void)hipMemsetAsync(v.words, 0, sizeof(sample::Words), s);
 }
 
-namespace {
-
-// the copies of a pass's first `copy` rows and of its words
 void enqueue_down(NbodyHandle* h, Enqueued& st, const Call& c, const Scratch& w, size_t copy, double* acc, double* phi, uint8_t* cls, Down* down) {
     const hipStream_t s = h->stream;
     if (st.ok()) st.last();
@@ -88,6 +75,8 @@ void enqueue_down(NbodyHandle* h, Enqueued& st, const Call& c, const Scratch& w,
     if (st.ok() && copy && phi) st.hip(hipMemcpyAsync(phi, w.phi, copy * sizeof(double), hipMemcpyDeviceToHost, s));
     if (st.ok() && copy && cls) st.hip(hipMemcpyAsync(cls, w.smp.cls, copy, hipMemcpyDeviceToHost, s));
 }
+
+namespace {
 
 void record(NbodyHandle* h, const Call& c, uint64_t reads, uint64_t sorts) {
     h->pm_last[0] = 1;

@@ -30,9 +30,11 @@ struct Call {
     Plans plans;
     bool deconvolve;
     int op;
-    Call(const NbodyGridSpec& spec, const NbodyPmSpec& pm, bool bodies)
-        : g(deposit::grid_of(spec)), shape(poisson::shape_of(spec)), tables(poisson::tables_of(spec, pm.poisson, shape)),
-          plans(make_plans(pm.gradient, deposit::cells_of(g), bodies)), deconvolve(shape.periodic && pm.poisson.deconvolve > 0), op(pm.gradient) {}
+    bool split;   // r_split > 0 (nbody_p3m.cpp): the tables' D carries the Gaussian split, and `deconvolve` is set with it
+    Call(const NbodyGridSpec& spec, const NbodyPmSpec& pm, bool bodies, double r_split = 0.0)
+        : g(deposit::grid_of(spec)), shape(poisson::shape_of(spec)), tables(poisson::tables_of(spec, pm.poisson, shape, r_split)),
+          plans(make_plans(pm.gradient, deposit::cells_of(g), bodies)),
+          deconvolve(shape.periodic && (pm.poisson.deconvolve > 0 || r_split > 0.0)), op(pm.gradient), split(shape.periodic && r_split > 0.0) {}
 };
 
 // what the stages count as they enqueue; every stage enqueues against st (nbody_handle.h Enqueued) and does nothing once it is not ok
@@ -52,5 +54,13 @@ void enqueue_grid(NbodyHandle* h, const ShardT<F>& sh, size_t n_upper, const Nbo
 // One pass over the n rows of w.smp.xyz (count: the live rows' word on the device, or null: all n) against the resident grid:
 // w.smp.out = acc, w.phi (with_phi), w.smp.cls.  ordered: w.smp.rows + n holds these rows' order already.
 void enqueue_rows(NbodyHandle* h, const Call& c, const int* count, size_t n, bool with_phi, bool ordered, const Scratch& w, Enqueued& st, Tally& tally);
+
+// what one pass over rows brings down
+struct Down {
+    deposit::Words dep{};
+    sample::Words rows{}, value{};
+};
+// the copies of a pass's first `copy` rows (acc, phi and cls, each where not null) and of its words
+void enqueue_down(NbodyHandle* h, Enqueued& st, const Call& c, const Scratch& w, size_t copy, double* acc, double* phi, uint8_t* cls, Down* down);
 
 }}  // namespace nbody::pm

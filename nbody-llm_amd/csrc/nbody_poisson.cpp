@@ -20,8 +20,8 @@ hipError_t upload_tables(NbodyHandle* h, const Tables& t, const Scratch& w) {
 }
 
 hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
-                   const Scratch& w, int* launches_out, int* transforms_out, int held) {
-    const bool deconvolve = sh.periodic && ps.deconvolve > 0;
+                   const Scratch& w, int* launches_out, int* transforms_out, int held, bool split) {
+    const bool deconvolve = sh.periodic && (ps.deconvolve > 0 || split);
     hipError_t e = (held & kHeldTables) ? hipSuccess : upload_tables(h, t, w);
     int launches = 0, transforms = 2;
     if (e == hipSuccess) {

@@ -18,11 +18,12 @@ int solve(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps,
 // transforms_out (may be null): the butterfly launches made and the 3-D transforms (2 periodic, 3 isolated).
 // held (nbody_mesh.cpp, whose scratch outlives the call): what w holds already and is neither sent nor made again -- the tables
 // (kHeldTables), and on an isolated grid the transformed kernel in w.k (kHeldKernel: two transforms then, every output's
-// expression tree as it was).
+// expression tree as it was).  split (nbody_p3m.cpp): t is tables_of(..., r_split > 0), whose D carries the Gaussian split:
+// k_poisson_green multiplies by it whatever ps.deconvolve is, and w was laid out with room for D.
 enum { kHeldTables = 1, kHeldKernel = 2 };
 // the twiddles, the Green factors and the deconvolution factors of t on their way to w's three axes (t outlives the wait)
 hipError_t upload_tables(NbodyHandle* h, const Tables& t, const Scratch& w);
 hipError_t enqueue(NbodyHandle* h, const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const Shape& sh, const Tables& t, const Plan& plan,
-                   const Scratch& w, int* launches_out, int* transforms_out, int held = 0);
+                   const Scratch& w, int* launches_out, int* transforms_out, int held = 0, bool split = false);
 
 }}  // namespace nbody::poisson

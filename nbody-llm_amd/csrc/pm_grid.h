@@ -24,15 +24,15 @@ inline std::string call_refusal(const NbodyGridSpec* spec, const NbodyPmSpec* pm
     return sample::call_refusal(spec, &held, 1, pm->gradient);
 }
 
-// the composition, on a checked call.  xyz == nullptr: the points are the bodies
+// the composition, on a checked call.  xyz == nullptr: the points are the bodies.  r_split (p3m_pairs.h): poisson::host_call's
 inline int host_call(const double* body_xyz, const double* body_m, size_t n_bodies, const NbodyGridSpec& spec, const NbodyPmSpec& pm,
-                     const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t* counts) {
+                     const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t* counts, double r_split = 0.0) {
     const size_t cells = deposit::cells_of(deposit::grid_of(spec));
     std::vector<double> grid(cells, 0.0);   // M, then Phi in place (nbody_host_grid_poisson allows it)
     uint64_t counted[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int rc = deposit::host_call(body_xyz, body_m, n_bodies, spec, grid.data(), cells, counted);
     if (rc) return rc;
-    rc = poisson::host_call(spec, pm.poisson, grid.data(), grid.data());
+    rc = poisson::host_call(spec, pm.poisson, grid.data(), grid.data(), r_split);
     if (rc) return rc;
     const double* P = xyz ? xyz : body_xyz;
     const size_t n = xyz ? n_points : n_bodies;

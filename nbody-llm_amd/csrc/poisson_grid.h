@@ -22,6 +22,9 @@
 //               c = -((FOUR_PI g) / ((spacing spacing) spacing)), once; per mode den = (K_x[i] + K_y[j]) + K_z[l],
 //               f = den == 0 ? +0.0 : c / den;  d > 0: f = f ((D_x[i] D_y[j]) D_z[l]);  phi^ = (f rho^.re, f rho^.im);
 //               phi[cell] = value.re (1 / points) + 0.0   (the + 0.0 here and below: a zero result is +0.0)
+//               split (nbody_p3m_field, r_split > 0; internal, no public spec reaches it): S_c[i] = exp(-(K_c[i] (r_split
+//               r_split))) and D_c[i] <- D_c[i] S_c[i], one product, on the host (D_c[i] = 1 without deconvolution), and the
+//               f ((D_x D_y) D_z) branch is taken whatever d is
 //     ISOLATED  every axis of more than one cell padded to 2 n with +0.0; on the padded grid Kr = 1 / sqrt(r2),
 //               r2 = ((dx dx + dy dy) + dz dz) + soften soften, d_c = spacing m_c, m_c = i <= n_c ? i : 2 n_c - i (0 on an axis
 //               of one cell); at the origin Kr = soften > 0 ? 1 / soften : +0.0.  Kr goes through the same transform, each
@@ -155,8 +158,10 @@ struct Tables {
     double inv_points = 1.0;
 };
 
-inline Tables tables_of(const NbodyGridSpec& s, const NbodyPoissonSpec& ps, const Shape& sh) {
+// r_split > 0 (p3m_pairs.h): the Gaussian split rides in D, which is then made whatever ps.deconvolve is
+inline Tables tables_of(const NbodyGridSpec& s, const NbodyPoissonSpec& ps, const Shape& sh, double r_split = 0.0) {
     Tables t;
+    const bool split = sh.periodic && r_split > 0.0;
     for (int c = 0; c < 3; ++c) {
         if (sh.len[c] > 1) {
             t.tw[c].resize(size_t(sh.len[c] / 2));
@@ -165,9 +170,13 @@ inline Tables tables_of(const NbodyGridSpec& s, const NbodyPoissonSpec& ps, cons
         if (!sh.periodic) continue;
         t.K[c].resize(size_t(sh.n[c]));
         k_table(ps.green, sh.n[c], s.spacing, t.K[c].data());
-        if (ps.deconvolve > 0) {
-            t.D[c].resize(size_t(sh.n[c]));
-            d_table(ps.deconvolve, s.scheme, sh.n[c], t.D[c].data());
+        if (ps.deconvolve > 0 || split) {
+            t.D[c].assign(size_t(sh.n[c]), 1.0);
+            if (ps.deconvolve > 0) d_table(ps.deconvolve, s.scheme, sh.n[c], t.D[c].data());
+        }
+        if (split) {
+            const double rr = r_split * r_split;
+            for (size_t i = 0; i < t.D[c].size(); ++i) t.D[c][i] = t.D[c][i] * std::exp(-(t.K[c][i] * rr));
         }
     }
     t.c = green_constant(ps.g, s.spacing);
@@ -234,9 +243,10 @@ inline std::string call_refusal(const NbodyGridSpec* spec, const NbodyPoissonSpe
     return std::string();
 }
 
-inline int host_call(const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi) {
+// r_split: tables_of's
+inline int host_call(const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, const double* mass, double* phi, double r_split = 0.0) {
     const Shape sh = shape_of(spec);
-    const Tables t = tables_of(spec, ps, sh);
+    const Tables t = tables_of(spec, ps, sh, r_split);
     const size_t points = sh.points();
     const size_t s1 = size_t(sh.len[1]) * size_t(sh.len[2]), s2 = size_t(sh.len[2]);
     std::vector<Cx> x(points, Cx{0.0, 0.0});
@@ -246,7 +256,7 @@ inline int host_call(const NbodyGridSpec& spec, const NbodyPoissonSpec& ps, cons
                 x[size_t(i) * s1 + size_t(j) * s2 + size_t(l)].re = mass[(size_t(i) * size_t(sh.n[1]) + size_t(j)) * size_t(sh.n[2]) + size_t(l)];
     host_transform(x.data(), sh, t, false);
     if (sh.periodic) {
-        const bool dec = ps.deconvolve > 0;
+        const bool dec = ps.deconvolve > 0 || r_split > 0.0;
         for (int i = 0; i < sh.n[0]; ++i)
             for (int j = 0; j < sh.n[1]; ++j)
                 for (int l = 0; l < sh.n[2]; ++l) {

@@ -41,6 +41,8 @@
 // deposit with wrapped indices): one line with the mode and the grid, one with the sum of phi and its lowest cell.  --pm
 // isolated|spectral|diff2:grad2|grad4 (with --deposit only, N a power of two) is the three of them in one call (nbody_pm_field):
 // one line with the mode, the gradient and the eight counts, then the first eight bodies' acc and phi with 17 significant digits.
+// --p3m spectral|diff2:grad2|grad4 (with --deposit only) is the P3M field at the bodies (nbody_p3m_field) on that grid taken as
+// periodic, r_split = 1.25 spacing, r_cut = 4.5 r_split: one line with the counts and the pair counts, then the first bodies.
 // --mesh isolated|spectral|diff2:grad2|grad4 (with --deposit only, N a power of two) steps under mesh gravity on that grid
 // (nbody_set_mesh_gravity): one line with the mode, the gradient, the plan and the words of nbody_mesh_gravity_stats, then the
 // first eight bodies' position and acceleration.
@@ -76,6 +78,7 @@ static void usage() {
                  "                 [--deposit ngp|cic|tsc:N:HALF]   (the mass of the final state on the N^3 cells of [-HALF, HALF)^3)\n"
                  "                 [--sample value|grad2|grad4]   (with --deposit: that grid read back at the bodies, its value or its gradient)\n"
                  "                 [--pm isolated|spectral|diff2:grad2|grad4]   (with --deposit, N a power of two: the mesh acceleration and potential at the bodies in one call)\n"
+                 "                 [--p3m spectral|diff2:grad2|grad4]   (with --deposit, N a power of two with N / 8 >= 4: the P3M field at the bodies on that grid taken as periodic, r_split = 1.25 spacing, r_cut = 4.5 r_split)\n"
                  "                 [--mesh isolated|spectral|diff2:grad2|grad4]   (with --deposit, N a power of two: the steps run under mesh gravity on that grid, no pair kernel)\n"
                  "                 [--poisson isolated|spectral|diff2]   (with --deposit, N a power of two: the potential of that mass grid, zero-padded or periodic)\n"
                  "                 [--pair-search all|cells]  (how --merge, --fof, --density, --pair-counts and --knn (with a HINT) find their pairs: all pairs, or the cells of a uniform grid)\n");
@@ -300,6 +303,32 @@ static void print_pm(Sim& sim, NbodyGridSpec spec, int mode, int gradient, doubl
         std::printf("PM body %zu class %d %.17e %.17e %.17e %.17e\n", i, int(cls[i]), acc[3 * i], acc[3 * i + 1], acc[3 * i + 2], phi[i]);
 }
 
+// the lines of --p3m: the P3M field at the bodies in one call (nbody_p3m_field) on the periodic grid of --deposit with r_split =
+// 1.25 spacing, r_cut = 4.5 r_split and no softening; then the first eight bodies' acc and phi with 17 significant digits
+template <class Sim>
+static void print_p3m(Sim& sim, NbodyGridSpec spec, int mode, int gradient, double g) {
+    std::vector<double> acc, phi;
+    std::vector<uint8_t> cls;
+    uint64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st[4] = {0, 0, 0, 0};
+    spec.periodic = 1;
+    NbodyP3mSpec p{};
+    p.pm.poisson.g = g;
+    p.pm.poisson.green = mode == 2 ? NBODY_POISSON_DIFF2 : NBODY_POISSON_SPECTRAL;
+    p.pm.gradient = gradient;
+    p.r_split = 1.25 * spec.spacing;
+    p.r_cut = 4.5 * p.r_split;
+    p.terms = NBODY_P3M_BOTH;
+    sim.p3m_field(spec, p, acc, phi, cls, counts);
+    sim.p3m_field_stats(st);
+    std::printf("P3M: %s gradient %d g %.17e r_split %.17e r_cut %.17e bodies %zu deposited %llu %llu %llu %llu sampled %llu %llu %llu %llu partners %llu terms %llu\n",
+                mode == 2 ? "periodic diff2" : "periodic spectral", gradient, g, p.r_split, p.r_cut, cls.size(), (unsigned long long)counts[0],
+                (unsigned long long)counts[1], (unsigned long long)counts[2], (unsigned long long)counts[3], (unsigned long long)counts[4],
+                (unsigned long long)counts[5], (unsigned long long)counts[6], (unsigned long long)counts[7], (unsigned long long)st[2],
+                (unsigned long long)st[3]);
+    for (size_t i = 0; i < cls.size() && i < 8; ++i)
+        std::printf("P3M body %zu class %d %.17e %.17e %.17e %.17e\n", i, int(cls[i]), acc[3 * i], acc[3 * i + 1], acc[3 * i + 2], phi[i]);
+}
+
 // --mesh: the grid of --deposit and the mode as the (spec, PM spec) pair of nbody_set_mesh_gravity (pm.poisson.g is not read by a pass)
 static NbodyPmSpec mesh_specs(NbodyGridSpec* spec, int mode, int gradient) {
     spec->periodic = mode > 0;
@@ -331,7 +360,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
                bool diagnostics, bool pairs, double merge_radius, size_t merge_every, double fof_b, int fof_min, int fof_bound, int pair_search,
                double density_radius, int density_kernel, const std::vector<double>& pair_edges, int knn_k, double knn_hint,
                const NbodyGridSpec* deposit_spec, int sample_op, int poisson_mode, int pm_mode, int pm_gradient, int mesh_mode,
-               int mesh_gradient) {
+               int mesh_gradient, int p3m_mode, int p3m_gradient) {
     using P = nbody::PointParticleT<F>;
     const bool wide = sizeof(F) == 8;
     std::vector<P> points;
@@ -411,6 +440,7 @@ static int run(const std::string& method, const std::string& ic, const std::stri
         if (deposit_spec && sample_op >= 0) print_sample(*sim, *deposit_spec, sample_op);
         if (deposit_spec && poisson_mode >= 0) print_poisson(*sim, *deposit_spec, poisson_mode, double(sim->settings_mut().g));
         if (deposit_spec && pm_mode >= 0) print_pm(*sim, *deposit_spec, pm_mode, pm_gradient, double(sim->settings_mut().g));
+        if (deposit_spec && p3m_mode >= 0) print_p3m(*sim, *deposit_spec, p3m_mode, p3m_gradient, double(sim->settings_mut().g));
         if (deposit_spec && mesh_mode >= 0) print_mesh(*sim, mesh_mode, mesh_gradient);
         if (pair_search == NBODY_SEARCH_CELLS) {
             uint64_t ps[4] = {0, 0, 0, 0};
@@ -464,6 +494,7 @@ int main(int argc, char** argv) {
     int poisson_mode = -1;   // 0 isolated, 1 periodic spectral, 2 periodic diff2
     int pm_mode = -1, pm_gradient = NBODY_SAMPLE_GRADIENT2;   // --pm: the same three modes, and the gradient
     int mesh_mode = -1, mesh_gradient = NBODY_SAMPLE_GRADIENT2;   // --mesh: the same again, as the step's self-gravity
+    int p3m_mode = -1, p3m_gradient = NBODY_SAMPLE_GRADIENT2;     // --p3m: the two periodic modes, and the gradient
     double knn_hint = 0.0;
     for (int i = 1; i < argc; ++i) {
         auto next = [&]() -> const char* { if (i + 1 >= argc) { usage(); std::exit(2); } return argv[++i]; };
@@ -597,6 +628,18 @@ int main(int argc, char** argv) {
             else if (grad == "grad4") pm_gradient = NBODY_SAMPLE_GRADIENT4;
             else { usage(); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--p3m")) {
+            const std::string arg = next();
+            const size_t c = arg.find(':');
+            if (c == std::string::npos) { usage(); return 2; }
+            const std::string mode = arg.substr(0, c), grad = arg.substr(c + 1);
+            if (mode == "spectral") p3m_mode = 1;
+            else if (mode == "diff2") p3m_mode = 2;
+            else { usage(); return 2; }
+            if (grad == "grad2") p3m_gradient = NBODY_SAMPLE_GRADIENT2;
+            else if (grad == "grad4") p3m_gradient = NBODY_SAMPLE_GRADIENT4;
+            else { usage(); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--mesh")) {
             const std::string arg = next();
             const size_t c = arg.find(':');
@@ -668,11 +711,15 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--pm needs --deposit\n");
         return 2;
     }
+    if (p3m_mode >= 0 && !deposit) {
+        std::fprintf(stderr, "--p3m needs --deposit\n");
+        return 2;
+    }
     if (mesh_mode >= 0 && !deposit) {
         std::fprintf(stderr, "--mesh needs --deposit\n");
         return 2;
     }
     if (ic == "plummer" && !width_set) width = 64.0;
-    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient, mesh_mode, mesh_gradient);
-    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient, mesh_mode, mesh_gradient);
+    if (dtype == "f64") return run<double>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient, mesh_mode, mesh_gradient, p3m_mode, p3m_gradient);
+    return run<float>(method, ic, math, tree, leaf, threads, num_points, steps, dt, g_soft, theta2, width, seed, integrator, dump, multipole, block_eta, block_levels, n_tracers, external, diagnostics, pairs, merge_radius, merge_every, fof_b, fof_min, fof_bound, pair_search, density_radius, density_kernel, pair_edges, knn_k, knn_hint, deposit ? &deposit_spec : nullptr, sample_op, poisson_mode, pm_mode, pm_gradient, mesh_mode, mesh_gradient, p3m_mode, p3m_gradient);
 }

@@ -508,6 +508,37 @@ public:
                              const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t counts[8]) {
         return nbody_host_pm_field(body_xyz, body_m, n_bodies, &spec, &pm, xyz, n_points, acc, phi, cls, counts);
     }
+    // P3M field (nbody_p3m_field, nbody_p3m_field_at): pm_field on a periodic grid with the Gaussian split of scale p.r_split in its
+    // Green stage, plus the minimum-image pair sum of the bodies closer than p.r_cut (p.terms picks both parts or one); shapes, cls
+    // and counts as pm_field's.  Read-only; the same bits as host_p3m_field (nbody_host_p3m_field; no device).  host_p3m_table:
+    // the split factors {F, P} [4097][2].  p3m_field_stats: {a call reached the device, the plan it used, partners looked at,
+    // terms with r2 < R2}
+    void p3m_field(const NbodyGridSpec& spec, const NbodyP3mSpec& p, std::vector<double>& acc, std::vector<double>& phi, std::vector<uint8_t>& cls,
+                   uint64_t counts[8], bool want_phi = true) {
+        size_t n = 0;
+        check(nbody_count(h_, &n));
+        acc.assign(n * 3, 0.0);
+        phi.assign(want_phi ? n : 0, 0.0);
+        cls.assign(n, 0);
+        check(nbody_p3m_field(h_, &spec, &p, acc.data(), want_phi ? phi.data() : nullptr, cls.data(), n, &n, counts));
+        acc.resize(n * 3);
+        phi.resize(want_phi ? n : 0);
+        cls.resize(n);
+    }
+    void p3m_field_at(const NbodyGridSpec& spec, const NbodyP3mSpec& p, const std::vector<double>& xyz, std::vector<double>& acc,
+                      std::vector<double>& phi, std::vector<uint8_t>& cls, uint64_t counts[8], bool want_phi = true) {
+        const size_t n = xyz.size() / 3;
+        acc.assign(n * 3, 0.0);
+        phi.assign(want_phi ? n : 0, 0.0);
+        cls.assign(n, 0);
+        check(nbody_p3m_field_at(h_, &spec, &p, xyz.data(), n, acc.data(), want_phi ? phi.data() : nullptr, cls.data(), counts));
+    }
+    void p3m_field_stats(uint64_t out[4]) { check(nbody_p3m_field_stats(h_, out)); }
+    static int host_p3m_field(const double* body_xyz, const double* body_m, size_t n_bodies, const NbodyGridSpec& spec, const NbodyP3mSpec& p,
+                              const double* xyz, size_t n_points, double* acc, double* phi, uint8_t* cls, uint64_t counts[8]) {
+        return nbody_host_p3m_field(body_xyz, body_m, n_bodies, &spec, &p, xyz, n_points, acc, phi, cls, counts);
+    }
+    static int host_p3m_table(double r_split, double r_cut, double* out) { return nbody_host_p3m_table(r_split, r_cut, out); }
     // how fof_labels, fof_groups, contacts, merge_contacts, neighbors_within, density, density_center and pair_counts find their pairs
     // (nbody_set_pair_search): NBODY_SEARCH_ALL_PAIRS, or
     // NBODY_SEARCH_CELLS -- the bodies sorted by the cell of a uniform grid; it changes no result.  pair_search_stats: {1 if the
